@@ -204,6 +204,29 @@ def unit_plan(solver, steps):
     return out
 
 
+DUMP_CELLS = 1 << 19     # --dump-outputs: cells written per array (u + rho + fin = 12 values a cell: <= 48 MiB at fp64)
+DUMP_SEED = 0
+
+
+def dump_outputs(solver, directory):
+    """What the timed steps computed, as get_fields() hands it to a caller -- u[2,X,Y], rho[X,Y] and the populations fin[9,X,Y] --
+    written to directory/{u,rho,fin}.npy in the lattice's dtype.  A lattice of more than DUMP_CELLS cells is sampled: the same
+    DUMP_CELLS cells (numpy default_rng(DUMP_SEED), flat index x * Y + y in ascending order) of every array, so u.npy is [2, n],
+    rho.npy [n] and fin.npy [9, n].  Returns the description that goes into the result line."""
+    u, rho, fin = solver.get_fields(want_fin=True)
+    cells = rho.size
+    sample = None
+    if cells > DUMP_CELLS:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(cells, DUMP_CELLS, replace=False))
+        u, rho, fin = u.reshape(2, -1)[:, idx], rho.reshape(-1)[idx], fin.reshape(9, -1)[:, idx]
+        sample = f"{DUMP_CELLS} of {cells} cells: numpy default_rng({DUMP_SEED}).choice({cells}, {DUMP_CELLS}, replace=False), sorted"
+    os.makedirs(directory, exist_ok=True)
+    for name, arr in (("u", u), ("rho", rho), ("fin", fin)):
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(arr))
+    return {"dir": directory, "files": ["u.npy", "rho.npy", "fin.npy"], "dtype": fin.dtype.name, "sample": sample,
+            "steps_done": solver.steps_done}
+
+
 def timed_rate(config, dev, kernel, arith, steps, warm):
     """MLUPS and ms per step of a whole BASELINE configuration on one GPU, HIP events around `steps` steps (best of two)."""
     s, NY, _ = make_solver(config, "strong", 1, 0, dev, kernel, arith)
@@ -239,10 +262,17 @@ def main():
                     help="auto: as BASELINE.json words the configuration (c3 / c4: strong -- one lattice cut into N slabs; c5: weak)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extra", action="store_true", help="skip the short side measurements reported under 'other'")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what they computed (u, rho, fin of the last step; a fixed seeded sample of "
+                         f"{DUMP_CELLS} cells of a larger lattice) to DIR/<name>.npy, so that two builds can be compared output for output")
     a = ap.parse_args()
     if a.cpu_table:
         cpu_table()
         return
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if a.dump_outputs and a.gpus > 1:
+        ap.error("--dump-outputs is supported with --gpus 1 only")
     scaling = DEFAULT_SCALING[a.config] if a.scaling == "auto" else a.scaling
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -346,6 +376,8 @@ def main():
         t = torch.tensor([dt, ev_ms], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt, ev_ms = float(t[0]), float(t[1])
+    # the state the timed steps left, before anything below steps the lattice further or replaces its state
+    dumped = dump_outputs(solver, a.dump_outputs) if a.dump_outputs else None
 
     cells_total = nx * NY
     cells_rank = nx * rows[1]
@@ -488,6 +520,8 @@ def main():
                                         "a loaded device when the warm-up starts"},
             "roofline": roof,
         }
+        if dumped:
+            out["dump_outputs"] = dumped
         if other:
             out["other"] = other
     solver.close()

@@ -26,7 +26,9 @@ def test_header_and_bindings_list_the_same_entry_points():
 
 def test_library_exports_every_declared_symbol():
     assert os.path.exists(_lib.LIB_PATH), "liblbm_hip.so not built (run __graft_entry__.build())"
-    L = ctypes.CDLL(_lib.LIB_PATH)
+    # (through the package's loader, never a bare CDLL: loading the library first binds it -- and so the whole process, RCCL
+    # included -- to /opt/rocm's HIP runtime instead of PyTorch's, and every later test of the session that uses RCCL fails)
+    L = _lib.lib()
     for n in declared_functions():
         assert hasattr(L, n), f"{n} declared in include/lbm.h but not exported"
     hdr = int(re.search(r"#define LBM_ABI_VERSION (\d+)", open(os.path.join(ROOT, "include", "lbm.h")).read()).group(1))

@@ -123,3 +123,56 @@ def test_a_short_slab_leaves_cus_to_its_band_workgroups_per_shader_engine():
     assert -(-17 // 32) + -(-first["workgroups"] // 32) <= 8 and first["workgroups"] > 187, first
     wide = launch_plan(16384, 3 * 2048, 1000.0, dtype=np.float32, arith="fast", rows=(2048, 2048), steps=16)  # several rounds: no reserve
     assert wide["workgroups"] > 256, wide
+
+
+class _FieldsStub:
+    """get_fields() of a solver whose lattice holds distinct values in every cell of every array."""
+
+    def __init__(self, nx, ny, dtype):
+        n = nx * ny
+        self.fin = np.arange(9 * n, dtype=dtype).reshape(9, nx, ny)
+        self.u = -np.arange(2 * n, dtype=dtype).reshape(2, nx, ny)
+        self.rho = np.arange(n, dtype=dtype).reshape(nx, ny) + 0.5
+        self.steps_done = 7
+
+    def get_fields(self, want_fin=False):
+        assert want_fin
+        return self.u.copy(), self.rho.copy(), self.fin.copy()
+
+
+def test_dump_outputs_writes_a_small_lattice_whole(tmp_path):
+    s = _FieldsStub(24, 16, np.float32)
+    d = bench.dump_outputs(s, str(tmp_path / "out"))
+    assert d["sample"] is None and d["dtype"] == "float32" and d["steps_done"] == 7
+    for name in ("u", "rho", "fin"):
+        got = np.load(tmp_path / "out" / f"{name}.npy")
+        assert got.dtype == np.float32 and np.array_equal(got, getattr(s, name)), name
+
+
+def test_dump_outputs_samples_a_large_lattice_the_same_way_every_time(tmp_path, monkeypatch):
+    monkeypatch.setattr(bench, "DUMP_CELLS", 100)
+    nx, ny = 40, 30
+    s = _FieldsStub(nx, ny, np.float64)
+    a = bench.dump_outputs(s, str(tmp_path / "a"))
+    b = bench.dump_outputs(_FieldsStub(nx, ny, np.float64), str(tmp_path / "b"))
+    assert a["sample"] and a["sample"] == b["sample"] and a["dtype"] == "float64"
+    rho = np.load(tmp_path / "a" / "rho.npy")
+    idx = (rho - 0.5).astype(np.int64)                        # rho of cell i is i + 0.5: the sampled flat indices
+    assert rho.shape == (100,) and np.all(np.diff(idx) > 0) and idx[-1] < nx * ny
+    x, y = idx // ny, idx % ny
+    assert np.array_equal(np.load(tmp_path / "a" / "u.npy"), s.u[:, x, y])
+    assert np.array_equal(np.load(tmp_path / "a" / "fin.npy"), s.fin[:, x, y])
+    for name in ("u", "rho", "fin"):
+        assert np.array_equal(np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")), name
+
+
+def test_dump_outputs_stays_within_64_mib_on_every_configuration():
+    for cfg, (nx, ny, _, dtype, *_rest) in bench.CONFIGS.items():
+        cells = min(nx * ny, bench.DUMP_CELLS)
+        assert cells * (2 + 1 + 9) * np.dtype(dtype).itemsize <= 64 << 20, cfg
+
+
+def test_bench_refuses_a_step_count_below_one():
+    env = dict(os.environ, WORLD_SIZE="1")
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, env=env)
+    assert p.returncode != 0 and "--steps" in p.stderr

@@ -1,5 +1,5 @@
 """Multi-slab host logic on CPU: (1) several slabs in one process, (2) world_size-2 and -3
-torch.distributed runs over gloo, incl. world 8 with multi-step launch units.  The compute is the stand-in stepper (tests/slab_standin.py);
+torch.distributed runs over gloo, incl. world 5 with multi-step launch units.  The compute is the stand-in stepper (tests/slab_standin.py);
 the code under test is the product's slab.py (partition, neighbours, side/plane conventions,
 driver ordering, P2P transport).  The result must be bit-identical to the undivided oracle."""
 import os
@@ -85,9 +85,12 @@ def _worker(rank, world, port, nx, ny, steps, sem, coll, q, unit=1):
 
 
 @pytest.mark.parametrize("world,sem,coll,unit,ny,steps", [(2, "mrt_gpu", "MRT", 1, 19, 10), (2, "mrt_py", "SRT", 1, 19, 10), (3, "mrt_gpu", "SRT", 1, 19, 10),
-                                                           # multi-step launch units with deep halos, several calls (world 2, 3, 8)
+                                                           # multi-step launch units with deep halos, several calls (world 2, 3, 5); world 5
+                                                           # cuts 52 rows into slabs of 11 and 10 rows, three of them middle slabs.  Five ranks
+                                                           # at most: every rank imports PyTorch, which loads the HIP runtime, and a GPU node
+                                                           # allows six processes per GPU -- the ranks and this test's own process.
                                                            (2, "mrt_gpu", "MRT", 5, 23, [1, 12, 4]), (3, "mrt_gpu", "MRT", 4, 31, [9, 7]),
-                                                           (8, "mrt_gpu", "MRT", 5, 83, [1, 5, 8])])
+                                                           (5, "mrt_gpu", "MRT", 5, 52, [1, 5, 8])])
 def test_gloo_halo_driver_equals_single_domain(world, sem, coll, unit, ny, steps):
     import torch.multiprocessing as mp
     nx = 16
