@@ -280,7 +280,7 @@ int lbm_comm_init(lbm_ctx* c, int nranks, int rank, const void* uid128) {
         // Neighbours must run the same launch plan (they post matching send / receive sequences): compare it once.
         constexpr int NW = 16;
         const int32_t mine[NW] = {LBM_ABI_VERSION, c->p.nx, c->p.ny, c->p.dtype, c->p.semantics, c->p.turb, c->geo.pitch,
-                                  c->geo.row != c->geo.pitch ? 1 : 0, c->use_tb ? (c->stream ? 2 : 1) : 0, c->tb_steps, c->tb_f, c->deep_halo ? 1 : 0,
+                                  c->geo.row != c->geo.pitch ? 1 : 0, c->kern == Kern::none ? 0 : streaming(c) ? 2 : 1, c->tb_steps, c->tb_f, c->deep_halo ? 1 : 0,
                                   c->frame_fused ? 1 : 0, c->lazy_lag ? 1 : 0, c->p.collision, c->p.arith};
         // (UNEXECUTED ON HARDWARE until a run with two GPUs exists: every box so far had one.)  The three blocks [mine | from LOW | from
         // HIGH] are built on the host and uploaded by ONE synchronous copy, so nothing on the null stream can race with the receives

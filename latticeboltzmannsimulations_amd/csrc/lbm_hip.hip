@@ -188,21 +188,13 @@ lbm_ctx* lbm_create(const lbm_params* p, char* err, size_t errlen) {
     if (p->device < 0 || p->device >= ndev) return bail("device ordinal out of range");
     if ((e = hipSetDevice(p->device)) != hipSuccess) return bail(std::string("hipSetDevice: ") + hipGetErrorString(e));
 
+    hipDeviceProp_t prop;
+    const int ncu = hipGetDeviceProperties(&prop, p->device) == hipSuccess && prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     std::string plan_err;
-    lbm_ctx* c = plan_ctx(p, true, plan_err);
+    lbm_ctx* c = plan_ctx(p, ncu, true, plan_err);
     if (!c) return bail(plan_err);
     const size_t bytes = c->lat_bytes;
     auto cleanup = [&](const std::string& m) -> lbm_ctx* { lbm_destroy(c); return bail(m); };
-    {
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, p->device) == hipSuccess && prop.multiProcessorCount > 0) c->ncu = prop.multiProcessorCount;
-    }
-    // beside the streaming kernel one frame workgroup fits on a CU: as many workgroups as CUs, not more (8192^2 fp64: 187 GLUPS
-    // with 64 cells = 512 workgroups, 201 with 128 = 256; profiles/r02_logs/stream_ab20.log)
-    if (c->frame_beside && !p->frame_seg) {
-        const long long per = 2LL * p->nx + 2LL * ((p->ny_local_min ? p->ny_local_min : p->ny_local) - 2 * c->tb_f);
-        c->frame_seg = std::max(64, (int)(((per + c->ncu - 1) / c->ncu + 7) / 8 * 8));
-    }
     if ((e = hipStreamCreateWithFlags(&c->s_compute, hipStreamNonBlocking)) != hipSuccess) return cleanup("hipStreamCreate");
     {   // halo exchange stream at the highest priority: its (tiny) RCCL kernels must not queue behind the
         // thousands of workgroups of the interior kernel they are meant to overlap
@@ -233,7 +225,7 @@ lbm_ctx* lbm_create(const lbm_params* p, char* err, size_t errlen) {
             if (lbm_set_relaxation(c, i, p->omega, p->omegam, p->omega_e, p->omega_eps, p->omega_q) != LBM_OK) return cleanup(c->err);
     }
     if (lbm_init_equilibrium(c) != LBM_OK) return cleanup(c->err);
-    if (c->stream && c->tail_tiles && warm_stream(c) != LBM_OK) return cleanup("warm-up launch of the streaming kernel");
+    if (c->tail_tiles && warm_stream(c) != LBM_OK) return cleanup("warm-up launch of the streaming kernel");   // (see warm_stream)
     return c;
 }
 

@@ -31,6 +31,16 @@
 constexpr int LAT_LAG = 9;    // lat[LAT_LAG]: the lattice of the step before the last, recomputed on demand (lazy one-step lag)
 constexpr int NLAT = 10;
 
+// The kernel of the multi-step launch units (ordered: the streaming kernels last, the two with the walls inside after the one with
+// a wall frame):
+//   none          one step per launch
+//   tile2         k_step2_deep: two steps per launch
+//   tile          k_stepS_deep: three to five steps per launch, in-place LDS tiles (+ the wall frame)
+//   stream        k_stream: the strip-streaming kernel (lbm_stream.hpp, up to 8 steps per launch); its wall frame inside the launch or beside it
+//   stream_walls  k_stream_walls / k_stream_walls_slab: ... with the walls inside (no frame)
+//   stream_pairs  k_stream_pairs: ... and two rows per wave (twelve waves, up to 10 steps per launch; a lone lattice)
+enum class Kern { none, tile2, tile, stream, stream_walls, stream_pairs };
+
 struct lbm_ctx {
     lbm_params p{};
     int es = 0;  // element size
@@ -63,7 +73,7 @@ struct lbm_ctx {
     bool use_vec = false;       // vector kernel (MRT_GPU.py semantics, nx multiple of the vector width)
     bool use_nt = false;        // non-temporal loads/stores: lattice far larger than the 256 MiB Infinity Cache
     bool push = false;          // LBM_KERNEL_PUSH: the reference's two-launch push scheme (lat[0], lat[1]: fin ping-pong; lat[2]: ftemp)
-    bool use_tb = false;        // several steps per launch (temporal blocking)
+    Kern kern = Kern::none;     // several steps per launch (temporal blocking): by which kernel
     int edge_rows = 0;          // rows next to each interface of lat[cur] that work on s_comm wrote (and s_comm's stream order therefore covers):
                                 // the frame width after a multi-step unit, 1 after a single step, 0 at the start of a call (see exchange_ready)
     bool tail_tiles = false;    // streaming contexts (lone, fp32): units of 3 .. 5 steps through the tile kernel (A/B: LBM_FLAG_NO_TAIL_TILES)
@@ -71,13 +81,10 @@ struct lbm_ctx {
     bool edge_reserve = true;   // streaming kernel between slabs: a one-round bulk launch leaves CUs to the edge workgroups (A/B: LBM_FLAG_NO_EDGE_RESERVE)
     bool edge_first = true;     // streaming kernel between slabs: release the bulk launch behind the edge launch (A/B: LBM_FLAG_NO_EDGE_FIRST)
     bool frame_wide = true;     // frame passes through the scratch lattices: workgroups of 1024 threads (A/B: LBM_FLAG_FRAME_NARROW)
-    bool frame_beside = false;  // streaming kernel of a lone lattice: the frame passes as a kernel of their own on the second stream, BESIDE the
+    bool frame_beside = false;  // Kern::stream on a lone lattice: the frame passes as a kernel of their own on the second stream, BESIDE the
                                 // streaming workgroups (no LDS, ~70 VGPRs: fits next to them when the streaming kernel leaves registers)
-    bool stream = false;        // ... by the strip-streaming kernel (lbm_stream.hpp: large lone lattices, up to 8 steps per launch)
-    bool stream_walls = false;  // ... with the walls inside (k_stream_walls: a lone lattice in MRT_GPU.py semantics; no frame) (opt-in: LBM_FLAG_STREAM_WALLS)
-    bool stream_pairs = false;  // ... and two rows per wave (k_stream_pairs: twelve waves, up to 10 steps per launch) (opt-in: LBM_FLAG_STREAM_PAIRS)
     int ncu = 256;              // compute units of the device (the streaming kernel runs one workgroup per CU)
-    int tb_steps = 2;           // ... or three to five (in-place LDS tile kernel), up to eight (streaming kernel)
+    int tb_steps = 2;           // steps per launch: two, three to five (tile kernel), up to eight (streaming kernel), ten (pairs)
     int tb_f = TB_F;            // frame width
     int batch = 1;              // independent lattices per buffer (lbm_params.batch)
     long long bstride = 0;      // elements from one lattice of the batch to the next
@@ -222,6 +229,16 @@ inline bool has_neighbour(const lbm_ctx* c, int side) {
 inline bool is_slab(const lbm_ctx* c) { return has_neighbour(c, LBM_SIDE_LOW) || has_neighbour(c, LBM_SIDE_HIGH); }
 // the library itself moves the halos (RCCL between ranks, or the one-GPU loopback)
 inline bool own_transport(const lbm_ctx* c) { return c->comm != nullptr && (c->nranks > 1 || c->loopback); }
+inline bool streaming(const lbm_ctx* c) { return c->kern >= Kern::stream; }
+inline bool walls_inside(const lbm_ctx* c) { return c->kern >= Kern::stream_walls; }
+
+// How a launch unit of S >= 2 steps runs (unit_route):
+//   one_launch    a lone lattice: frame and bulk (or the walls inside) in ONE launch on s_compute
+//   edges_bulk    a slab under the streaming kernel: the edge launch (launch_stream_edges), then the bulk launch
+//   fused_frame   all frame passes in one launch (launch_frame_multi / k_frame_beside), then the bulk launch
+//   frame_passes  one launch per frame pass (launch_frame), then the bulk launch
+//   single_steps  S single steps (the replay of the lagged lattice only)
+enum class Route { one_launch, edges_bulk, fused_frame, frame_passes, single_steps };
 
 // Deep halo for a multi-step of S steps: the S complete rows (all planes, ghost columns included) next to each interface go to
 // the neighbour's ghost rows in ONE message per side; the S frame passes then recompute a shrinking band of the neighbour's
@@ -251,8 +268,9 @@ StreamPlan plan_stream_on(const lbm_ctx* c, int S, int ncu, long long* cost_out)
 StreamPlan plan_stream(const lbm_ctx* c, int S);
 bool lag_replayable(const lbm_ctx* c, int S);
 int unit_steps(const lbm_ctx* c, int left, bool raw);
+Route unit_route(const lbm_ctx* c, int S, bool replay);
 std::string validate_params(const lbm_params* p);
-lbm_ctx* plan_ctx(const lbm_params* p, bool device, std::string& err_out);
+lbm_ctx* plan_ctx(const lbm_params* p, int ncu, bool device, std::string& err_out);
 // lbm_launch.hip
 int ensure_scratch(lbm_ctx* c, int n);
 int launch_rows(lbm_ctx* c, int from, int to, int row0, int stride, int nrows, hipStream_t s);

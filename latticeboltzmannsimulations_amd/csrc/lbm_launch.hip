@@ -97,23 +97,40 @@ int launch_frame_multi(lbm_ctx* c, int from, int to, int S, hipStream_t s, bool 
     return LBM_OK;
 }
 
+// k_stream_walls_slab over rows [ybeg, yend) between the slab's edge bands (bands = 0: the bulk launch), or over the interface bands
+// `bands` (bit 0: low, bit 1: high) alone, each of which starts elo / ehi rows inside the neighbour's rows (the edge launch).
+static int launch_walls_slab(lbm_ctx* c, int from, int to, hipStream_t s, int S, int ybeg, int yend, int bands, int elo, int ehi) {
+    dispatch(c->p, [&](auto v) {
+        using VT = decltype(v);
+        using R = typename VT::R;
+        if constexpr (VT::SEM == SEM_GPU) {
+            const StreamPlan pl = plan_stream(c, S);
+            const int nwg = pl.nstrips * (bands ? (bands & 1) + (bands >> 1) : pl.nsegy);
+            hipLaunchKernelGGL((k_stream_walls_slab<R, VT::COLL, VT::TURB>), dim3(nwg), dim3(ST_NT), 0, s, (const R*)c->lat[from], (R*)c->lat[to],
+                               c->geo, relax_of<R>(c->p), S, pl.nstrips, pl.H, bands ? 0 : (c->xcd_bands ? 1 : 0), ybeg, yend, bands, elo, ehi,
+                               bands ? c->tb_f : 0);
+        }
+    });
+    HIP_TRY(c, hipGetLastError());
+    return LBM_OK;
+}
+
 int launch_stream(lbm_ctx* c, int from, int to, hipStream_t s, int S, bool with_frame) {
-    if (c->stream_walls) {
+    if (walls_inside(c)) {
         // walls included, no frame at all: the whole lattice in one launch (with_frame), or a slab's rows between its edge bands
         const bool slab = is_slab(c);
         if (slab == with_frame) return fail(c, LBM_ERR_STATE, "internal: the streaming kernel with the walls inside takes a whole lone lattice or a slab's bulk rows");
-        const int ybeg = has_neighbour(c, LBM_SIDE_LOW) ? c->tb_f : 0, yend = c->geo.ny - (has_neighbour(c, LBM_SIDE_HIGH) ? c->tb_f : 0);
+        if (slab)
+            return launch_walls_slab(c, from, to, s, S, has_neighbour(c, LBM_SIDE_LOW) ? c->tb_f : 0,
+                                     c->geo.ny - (has_neighbour(c, LBM_SIDE_HIGH) ? c->tb_f : 0), 0, 0, 0);
         dispatch(c->p, [&](auto v) {
             using VT = decltype(v);
             using R = typename VT::R;
             if constexpr (VT::SEM == SEM_GPU) {
                 const StreamPlan pl = plan_stream(c, S);
-                if (c->stream_pairs)
+                if (c->kern == Kern::stream_pairs)
                     hipLaunchKernelGGL((k_stream_pairs<R, VT::COLL, VT::TURB>), dim3(pl.nstrips * pl.nsegy), dim3(64 * pairs_waves(S)), 0, s,
                                        (const R*)c->lat[from], (R*)c->lat[to], c->geo, relax_of<R>(c->p), S, pl.nstrips, pl.H, c->xcd_bands ? 1 : 0);
-                else if (slab)
-                    hipLaunchKernelGGL((k_stream_walls_slab<R, VT::COLL, VT::TURB>), dim3(pl.nstrips * pl.nsegy), dim3(ST_NT), 0, s, (const R*)c->lat[from],
-                                       (R*)c->lat[to], c->geo, relax_of<R>(c->p), S, pl.nstrips, pl.H, c->xcd_bands ? 1 : 0, ybeg, yend, 0, 0, 0, 0);
                 else
                     hipLaunchKernelGGL((k_stream_walls<R, VT::COLL, VT::TURB>), dim3(pl.nstrips * pl.nsegy), dim3(ST_NT), 0, s, (const R*)c->lat[from],
                                        (R*)c->lat[to], c->geo, relax_of<R>(c->p), S, pl.nstrips, pl.H, c->xcd_bands ? 1 : 0);
@@ -149,20 +166,8 @@ int launch_stream(lbm_ctx* c, int from, int to, hipStream_t s, int S, bool with_
 // streaming segment that starts in the neighbour's rows of the deep halo.  It writes every row the next exchange sends.
 // extra: rows of the neighbours' side owned on top (1 for the lagged lattice, see frame_passes).
 int launch_stream_edges(lbm_ctx* c, int from, int to, hipStream_t s, int S, bool lo, bool hi, int extra) {
-    if (c->stream_walls) {   // the walls inside: the edge launch is the interface bands alone, over the whole width (side-wall cells in line)
-        dispatch(c->p, [&](auto v) {
-            using VT = decltype(v);
-            using R = typename VT::R;
-            if constexpr (VT::SEM == SEM_GPU) {
-                const StreamPlan pl = plan_stream(c, S);
-                hipLaunchKernelGGL((k_stream_walls_slab<R, VT::COLL, VT::TURB>), dim3(pl.nstrips * ((lo ? 1 : 0) + (hi ? 1 : 0))), dim3(ST_NT), 0, s,
-                                   (const R*)c->lat[from], (R*)c->lat[to], c->geo, relax_of<R>(c->p), S, pl.nstrips, pl.H, 0, 0, 0,
-                                   (lo ? 1 : 0) | (hi ? 2 : 0), lo ? 1 + extra : 0, hi ? 1 + extra : 0, c->tb_f);
-            }
-        });
-        HIP_TRY(c, hipGetLastError());
-        return LBM_OK;
-    }
+    // the walls inside: the edge launch is the interface bands alone, over the whole width (side-wall cells in line)
+    if (walls_inside(c)) return launch_walls_slab(c, from, to, s, S, 0, 0, (lo ? 1 : 0) | (hi ? 2 : 0), lo ? 1 + extra : 0, hi ? 1 + extra : 0);
     const bool use_lds = frame_lds_fits(c, S, false, extra, ST_LDS_BYTES);
     if (!use_lds) {
         const int rc = ensure_scratch(c, S - 1);
@@ -188,26 +193,13 @@ int launch_stream_edges(lbm_ctx* c, int from, int to, hipStream_t s, int S, bool
 }
 
 // The first launch of the streaming kernel in a process costs ~1.4 ms (code upload, 144 KiB of LDS, scratch set-up).  Where the first
-// units of a run may go to the tile kernel (tail_tiles) that cost would land in the middle of a run -- in the driver's 20 timed
-// steps after a 5-step warm-up, for one -- so lbm_create pays it: one workgroup that returns at once (its segment is empty).
+// units of a run may go to the tile kernel (tail_tiles: Kern::stream on a lone fp32 lattice) that cost would land in the middle of a
+// run -- in the driver's 20 timed steps after a 5-step warm-up, for one -- so lbm_create pays it: one workgroup that returns at once
+// (its segment is empty).
 int warm_stream(lbm_ctx* c) {
     dispatch(c->p, [&](auto v) {
         using VT = decltype(v);
         using R = typename VT::R;
-        if constexpr (VT::SEM == SEM_GPU) {
-            if (c->stream_walls) {   // (H = 0: the one workgroup's segment is empty)
-                if (c->stream_pairs)
-                    hipLaunchKernelGGL((k_stream_pairs<R, VT::COLL, VT::TURB>), dim3(1), dim3(64 * pairs_waves(c->tb_steps)), 0, c->s_compute, (const R*)c->lat[0],
-                                       (R*)c->lat[1], c->geo, relax_of<R>(c->p), c->tb_steps, 1, 0, 0);
-                else if (is_slab(c))   // (rows [0, 0): empty)
-                    hipLaunchKernelGGL((k_stream_walls_slab<R, VT::COLL, VT::TURB>), dim3(1), dim3(ST_NT), 0, c->s_compute, (const R*)c->lat[0], (R*)c->lat[1],
-                                       c->geo, relax_of<R>(c->p), c->tb_steps, 1, 0, 0, 0, 0, 0, 0, 0, 0);
-                else
-                    hipLaunchKernelGGL((k_stream_walls<R, VT::COLL, VT::TURB>), dim3(1), dim3(ST_NT), 0, c->s_compute, (const R*)c->lat[0], (R*)c->lat[1],
-                                       c->geo, relax_of<R>(c->p), c->tb_steps, 1, 0, 0);
-                return;
-            }
-        }
         const int F = c->tb_f;
         const FramePtrs<R> fp = frame_ptrs<R>(c, 0, 1, 1);
         hipLaunchKernelGGL((k_stream<R, VT::COLL, VT::SEM, VT::TURB>), dim3(1), dim3(ST_NT), 0, c->s_compute, (const R*)c->lat[0], (R*)c->lat[1],
@@ -217,13 +209,20 @@ int warm_stream(lbm_ctx* c) {
     return LBM_OK;
 }
 
+// The bulk launch of a unit (with_frame: and the frame, the unit's only launch) by the context's kernel.
 int launch_deep(lbm_ctx* c, int from, int to, hipStream_t s, int steps, bool with_frame) {
     // A short unit of a lone fp32 lattice (the tail of a call: 3 .. 5 steps) goes to the tile kernel: a launch of the streaming
     // kernel costs nearly the same whatever its length (4096^2 fast: 311 us for four steps, 374 for eight), the tile kernel's four
     // steps take ~290 (strict ~300 against ~350): the driver's 20 timed steps, fast 1088 -> 1066 us, strict 1466 -> 1412
     // (profiles/r02_logs/tail_tiles.log)
-    const bool tail = c->stream && c->tail_tiles && c->frame_fused && with_frame && steps >= 3 && steps <= 5;
-    if (c->stream && !tail) return launch_stream(c, from, to, s, steps, with_frame);
+    switch (c->kern) {
+        case Kern::stream:
+            if (c->tail_tiles && c->frame_fused && with_frame && steps >= 3 && steps <= 5) break;
+            [[fallthrough]];
+        case Kern::stream_walls:
+        case Kern::stream_pairs: return launch_stream(c, from, to, s, steps, with_frame);
+        default: break;
+    }
     const int S_tile = steps >= 3 ? (steps == 4 || steps == 5 ? steps : 3) : 2;
     const bool tile_frame_lds = frame_lds_fits(c, S_tile, false, 0, TILE_FRAME_LDS_BYTES);
     if (with_frame && steps >= 3 && !tile_frame_lds) {
@@ -272,6 +271,23 @@ void finish_unit(lbm_ctx* c, int S) {
     c->lag = S - 1;
     c->lag_valid = false;
     c->thin_valid = false;
+}
+
+// The frame work of a unit of S steps on route `route` (edges_bulk, fused_frame or frame_passes: unit_route), lat[from] -> lat[to] on
+// stream s.  extra: rows of the neighbours' side owned on top (see launch_frame_multi).  The per-pass frame goes through the scratch
+// lattices; a slab without the deep halo exchanges one row after every pass but the last.
+static int launch_frame_work(lbm_ctx* c, Route route, int from, int to, hipStream_t s, int S, int extra) {
+    const bool lo = has_neighbour(c, LBM_SIDE_LOW), hi = has_neighbour(c, LBM_SIDE_HIGH), deep = is_slab(c) && c->deep_halo;
+    if (route == Route::edges_bulk) return launch_stream_edges(c, from, to, s, S, lo, hi, extra);
+    if (route == Route::fused_frame) return launch_frame_multi(c, from, to, S, s, deep && lo, deep && hi, extra);
+    int rc = ensure_scratch(c, 2);
+    for (int i = 1; i <= S && rc == LBM_OK; ++i) {
+        const int next = i == S ? to : 2 + ((i - 1) & 1), ext = deep ? S - i + extra : 0;
+        rc = launch_frame(c, from, next, c->tb_f + S - i, s, lo ? ext : 0, hi ? ext : 0);
+        if (rc == LBM_OK && is_slab(c) && !deep && i < S) rc = enqueue_exchange(c, next);
+        from = next;
+    }
+    return rc;
 }
 
 // Every launch unit (one single step or one multi-step) of a slab follows one protocol on the two streams:
@@ -328,8 +344,8 @@ int single_step(lbm_ctx* c, bool* comm_used, bool rccl_x) {
 // is the unit's only exchange; otherwise every pass but the last is followed by a one-row exchange.  (Running row and
 // column strips as separate launches on separate streams was measured and lost 8 %: profiles/r01_logs/perf31.log, perf35.log.)
 int multi_step(lbm_ctx* c, bool* comm_used, int S, bool rccl_x) {
-    const bool slab = is_slab(c);
-    if (!slab && ((c->stream_walls && S >= 2) || (S >= 3 && c->frame_fused && !(c->stream && c->frame_beside)))) {   // a lone lattice: frame and tiles in ONE launch, everything on the compute stream
+    const Route route = unit_route(c, S, false);
+    if (route == Route::one_launch) {   // a lone lattice: frame and tiles in ONE launch, everything on the compute stream
         if (c->edges_pending) {   // (frame launches of an earlier unit on the second stream, if any)
             HIP_TRY(c, hipStreamWaitEvent(c->s_compute, c->ev_edges, 0));
             c->edges_pending = false;
@@ -340,7 +356,7 @@ int multi_step(lbm_ctx* c, bool* comm_used, int S, bool rccl_x) {
         finish_unit(c, S);
         return LBM_OK;
     }
-    const bool deep = slab && c->deep_halo;
+    const bool slab = is_slab(c), deep = slab && c->deep_halo;
     if (slab && !deep && !rccl_x) return fail(c, LBM_ERR_STATE, "a multi-step unit of a slab needs the deep halo (MRT_GPU semantics) or the in-library exchange");
     const int a = c->cur, b = c->cur ^ 1;
     int rc;
@@ -353,9 +369,7 @@ int multi_step(lbm_ctx* c, bool* comm_used, int S, bool rccl_x) {
     if (rc) return rc;
     HIP_TRY(c, hipStreamWaitEvent(c->s_comm, c->ev_int, 0));
     HIP_TRY(c, hipStreamWaitEvent(c->s_compute, c->ev_edges, 0));   // this unit's tile kernel needs the previous unit's frame
-    int from = a;
-    const bool has_lo = has_neighbour(c, LBM_SIDE_LOW), has_hi = has_neighbour(c, LBM_SIDE_HIGH);
-    if ((c->frame_fused || c->stream_walls) && S >= 3 && c->stream && deep) {
+    if (route == Route::edges_bulk) {
         // The streaming kernel between slabs: the edge launch (interface rows + column strips, everything the next exchange sends)
         // here, the bulk launch below.  Both become ready when the previous bulk launch ends, and the bulk launch -- one
         // workgroup per CU for its whole run -- must not take the CUs first: the edge workgroups would run last, and the next
@@ -388,26 +402,9 @@ int multi_step(lbm_ctx* c, bool* comm_used, int S, bool rccl_x) {
             HIP_TRY(c, hipEventRecord(c->ev_go, c->s_comm));
             HIP_TRY(c, hipStreamWaitEvent(c->s_compute, c->ev_go, 0));
         }
-        rc = launch_stream_edges(c, a, b, c->s_comm, S, has_lo, has_hi, 0);
-        if (rc) return rc;
-    } else if (c->frame_fused && S >= 3 && (!slab || deep)) {
-        rc = launch_frame_multi(c, a, b, S, c->s_comm, deep && has_lo, deep && has_hi);
-        if (rc) return rc;
-    } else {
-      rc = ensure_scratch(c, 2);
-      if (rc) return rc;
-      for (int i = 1; i <= S; ++i) {
-        const int to = i == S ? b : 2 + ((i - 1) & 1);
-        const int ext = deep ? S - i : 0;
-        rc = launch_frame(c, from, to, c->tb_f + S - i, c->s_comm, has_lo ? ext : 0, has_hi ? ext : 0);
-        if (rc) return rc;
-        if (slab && !deep && i < S) {
-            rc = enqueue_exchange(c, to);
-            if (rc) return rc;
-        }
-        from = to;
-      }
     }
+    rc = launch_frame_work(c, route, a, b, c->s_comm, S, 0);
+    if (rc) return rc;
     HIP_TRY(c, hipEventRecord(c->ev_edges, c->s_comm));
     c->edges_pending = true;
     rc = launch_deep(c, a, b, c->s_compute, S);
@@ -433,31 +430,17 @@ int prev_lattice(lbm_ctx* c, int* which) {
         HIP_TRY(c, hipMemsetAsync(c->lat[LAT_LAG], 0, c->lat_bytes, c->s_compute));
     }
     const int k = c->lag, from = c->cur ^ 1;
-    const bool slab = is_slab(c);
-    int rc;
-    if (k >= 3 && c->tb_steps >= 3) {   // one multi-step launch of k steps (a slab: from the deep halo still in lat[from]'s ghost rows)
-        if (!slab && (c->frame_fused || c->stream_walls)) {
-            rc = launch_deep(c, from, LAT_LAG, c->s_compute, k, true);
-        } else {
-            const bool lo = has_neighbour(c, LBM_SIDE_LOW), hi = has_neighbour(c, LBM_SIDE_HIGH);
-            // one row more than a launch unit computes: the field export pulls the slab's first / last row from the first ghost
-            // rows of this lattice (the unit received S = k + 1 rows per side: enough)
-            if ((c->frame_fused || c->stream_walls) && c->stream && c->deep_halo) rc = launch_stream_edges(c, from, LAT_LAG, c->s_compute, k, lo, hi, 1);
-            else if (c->frame_fused) rc = launch_frame_multi(c, from, LAT_LAG, k, c->s_compute, lo, hi, 1);
-            else {
-                rc = ensure_scratch(c, 2);
-                int f = from;
-                for (int i = 1; i <= k && rc == LBM_OK; ++i) {
-                    const int to = i == k ? LAT_LAG : 2 + ((i - 1) & 1);
-                    rc = launch_frame(c, f, to, c->tb_f + k - i, c->s_compute, lo ? k - i + 1 : 0, hi ? k - i + 1 : 0);
-                    f = to;
-                }
-            }
-            if (rc == LBM_OK) rc = launch_deep(c, from, LAT_LAG, c->s_compute, k);
-        }
-        if (rc) return rc;
+    const Route route = unit_route(c, k, true);
+    int rc = LBM_OK;
+    if (route == Route::one_launch) {
+        rc = launch_deep(c, from, LAT_LAG, c->s_compute, k, true);
+    } else if (route != Route::single_steps) {   // the frame, then the bulk (a slab: from the deep halo still in lat[from]'s ghost rows)
+        // one row more than a launch unit computes (extra = 1): the field export pulls the slab's first / last row from the first
+        // ghost rows of this lattice (the unit received S = k + 1 rows per side: enough)
+        rc = launch_frame_work(c, route, from, LAT_LAG, c->s_compute, k, 1);
+        if (rc == LBM_OK) rc = launch_deep(c, from, LAT_LAG, c->s_compute, k);
     } else {                            // k single steps (a lone lattice), through scratch lattice 2
-        if (slab) return fail(c, LBM_ERR_STATE, "internal: the last unit of a slab cannot be replayed");
+        if (is_slab(c)) return fail(c, LBM_ERR_STATE, "internal: the last unit of a slab cannot be replayed");
         if (k > 1 && (rc = ensure_scratch(c, 2)) != LBM_OK) return rc;
         int f = from;
         for (int i = 1; i <= k; ++i) {
@@ -468,6 +451,7 @@ int prev_lattice(lbm_ctx* c, int* which) {
             f = to;
         }
     }
+    if (rc) return rc;
     c->raw[LAT_LAG] = 0;
     c->lag_valid = true;
     return LBM_OK;
@@ -509,7 +493,7 @@ int step_many(lbm_ctx* c, int nsteps) {
         return fail(c, LBM_ERR_STATE, "lbm_step on a slab without a communicator: its ghost rows would never be exchanged (attach one with "
                                       "lbm_comm_init, or drive the slab with lbm_step_edges/interior/finish, lbm_step_unit and the lbm_halo_* calls)");
     bool comm_used = false;
-    if (c->use_tb || slab)   // (a lone lattice stepping one step per launch uses one stream, no events)
+    if (c->kern != Kern::none || slab)   // (a lone lattice stepping one step per launch uses one stream, no events)
         HIP_TRY(c, hipEventRecord(c->ev_int, c->s_compute));   // everything enqueued so far (init, upload, earlier calls)
     c->edge_rows = 0;        // the first exchange of the call waits for it
     int left = nsteps;
@@ -579,7 +563,7 @@ int lbm_step_finish(lbm_ctx* c) {
 int lbm_step_unit(lbm_ctx* c, int S) {
     if (!c) return LBM_ERR_INVALID;
     HIP_TRY(c, hipSetDevice(c->p.device));
-    if (c->push || !c->use_tb) return fail(c, LBM_ERR_STATE, "lbm_step_unit: this context steps one step per launch (lbm_next_unit() is 1)");
+    if (c->push || c->kern == Kern::none) return fail(c, LBM_ERR_STATE, "lbm_step_unit: this context steps one step per launch (lbm_next_unit() is 1)");
     if (own_transport(c)) return fail(c, LBM_ERR_STATE, "lbm_step_unit: a communicator is attached, lbm_step() moves the halos itself");
     if (c->raw[c->cur]) return fail(c, LBM_ERR_STATE, "lbm_step_unit: the first step after an upload is a single step");
     const bool ok = c->tb_steps == 2 ? S == 2 : (S >= 3 && S <= c->tb_steps);

@@ -361,7 +361,7 @@ def launch_plan(xsize, ysize, Re, steps=0, ncu=0, RT="MRT", uLB=0.08, semantics=
     y0, nyl = (0, ny) if rows is None else (int(rows[0]), int(rows[1]))
     relax = relaxation(float(Re), ny, float(uLB), 1.0 if semantics == "mrt_py" else 1.2, 1.2)
     p = _params(xsize, ny, y0, nyl, dtype, RT, semantics, kernel, turb, 0, layout, batch, arith, min_rows, tuning, uLB, relax)
-    buf = ctypes.create_string_buffer(1024)
+    buf = ctypes.create_string_buffer(1024 + 2 * max(int(steps), 0))   # (the plan, then at most "1," per step)
     rc = L.lib().lbm_plan(ctypes.byref(p), int(ncu), int(steps), buf, len(buf))
     text = buf.value.decode()
     if rc < 0:

@@ -305,6 +305,32 @@ def test_seeded_random_configurations_of_the_streaming_kernel():
         assert np.array_equal(fin, want[2]) and np.array_equal(u, want[0]) and np.array_equal(rho, want[1]), what
 
 
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+def test_two_step_streaming_slabs_keep_the_wall_frame(dtype):
+    """Slabs that would take the walls inside the streaming kernel, run with two steps per launch: a two-step unit has no edge
+    launch, so they plan k_stream (frame passes + bulk launch) and stay bit-identical to the oracle."""
+    nx, ny, chunks = 320, 600, (1, 7, 12, 5)
+    o = CavityOracleC(nx, ny, 1000.0, semantics="mrt_gpu", collision="MRT", dtype=dtype)
+    for n in chunks:
+        o.step(n)
+    parts = partition_rows(ny, 3)
+    slabs = [CavitySolver(nx, ny, 1000.0, RT="MRT", dtype=dtype, kernel="stream", rows=r, tuning=dict(tb_steps=2)) for r in parts]
+    try:
+        for sl in slabs:
+            d = sl.describe()
+            assert d["kernel"] == "k_stream" and d["steps_per_launch"] == 2, d
+        drv = LocalSlabs(slabs)
+        for n in chunks:
+            drv.step(n)
+        u = np.zeros_like(o.u); rho = np.zeros_like(o.rho); fin = np.zeros_like(o.fin)
+        for sl in slabs:
+            sl.get_fields(u=u, rho=rho, fin=fin)
+    finally:
+        for sl in slabs:
+            sl.close()
+    assert np.array_equal(fin, o.fin) and np.array_equal(u, o.u) and np.array_equal(rho, o.rho)
+
+
 def test_two_steps_per_launch_needs_its_preconditions():
     with pytest.raises(RuntimeError, match="kernel = TB"):
         CavitySolver(24, 64, 100.0, kernel="tb")
