@@ -20,10 +20,7 @@
 #include <vector>
 
 #include "../../include/lbm.h"
-#include "lbm_kernels.hpp"
-
-#include "lbm_tiles_inst.hpp"   // extern template declarations of k_stepS_deep (lbm_tiles_f32.hip / lbm_tiles_f64.hip)
-#include "lbm_stream.hpp"       // ... and of k_stream, k_stream_walls, k_stream_pairs (lbm_stream*_f32.hip / _f64.hip)
+#include "lbm_inst.hpp"   // the kernels, and extern template declarations of the multi-step ones (compiled in lbm_{tiles,stream*}_f32/f64.hip)
 
 // ------------------------------------------------------------------------------------
 // context
@@ -203,6 +200,15 @@ void dispatch(const lbm_params& p, F&& f) {
     if (p.dtype == LBM_F32) by_coll(float{});
     else by_coll(double{});
 }
+// A launcher's body: f(Variant) enqueues the kernels of the context's variant, then the launch error check
+template <typename F>
+int launch_variant(lbm_ctx* c, F&& f) {
+    dispatch(c->p, f);
+    HIP_TRY(c, hipGetLastError());
+    return LBM_OK;
+}
+// segments of L cells that cover n cells of a frame strip (the fused frame passes run one workgroup per segment, frame_passes)
+inline int frame_segs(int n, int L) { return (n + L - 1) / L; }
 struct StreamPlan { int nstrips, nsegy, H; };
 
 // Waiting for the device: poll for a short while, then block.  A blocking hipStreamSynchronize / hipEventSynchronize wakes the host

@@ -1,0 +1,51 @@
+// lbm_inst.hpp -- the explicit instantiations of the multi-step kernels: one list of the operator variants that dispatch() (lbm_host.hpp)
+// can produce, and one line per kernel family over it.  The host units see `extern` declarations of every family for both real types.
+// An instantiation unit lbm_<family>_<real>.hip defines LBM_INST as its family's line for its real type (e.g. LBM_INST_STREAMW(float))
+// and holds those definitions alone: one unit per family and real type, compiled in parallel.
+#pragma once
+#include "lbm_stream.hpp"
+
+// (real, collision operator, semantics, Smagorinsky) -- MRT_GPU.py semantics: six collision variants, with and without the closure
+#define LBM_GPU_VARIANTS(M, R)                                                                                                  \
+    M(R, C_SRT, SEM_GPU, false) M(R, C_TRT, SEM_GPU, false) M(R, C_MRT, SEM_GPU, false)                                         \
+    M(R, C_MRT_FAST, SEM_GPU, false) M(R, C_SRT_FAST, SEM_GPU, false) M(R, C_TRT_FAST, SEM_GPU, false)                          \
+    M(R, C_SRT, SEM_GPU, true) M(R, C_TRT, SEM_GPU, true) M(R, C_MRT, SEM_GPU, true)                                            \
+    M(R, C_MRT_FAST, SEM_GPU, true) M(R, C_SRT_FAST, SEM_GPU, true) M(R, C_TRT_FAST, SEM_GPU, true)
+// ... MRT.py semantics: the three strict ones
+#define LBM_PY_VARIANTS(M, R) M(R, C_SRT, SEM_PY, false) M(R, C_TRT, SEM_PY, false) M(R, C_MRT, SEM_PY, false)
+
+// one instantiation of each kernel (LBM_X: `extern`, or nothing in the unit that compiles it)
+#define LBM_TILE_ONE(R, COLL, SEM, S, TURB)                                                                                     \
+    LBM_X template __global__ void k_stepS_deep<R, COLL, SEM, S, false, TURB>(const R* __restrict__, R* __restrict__, Geo, Relax<R>, Batch<R>, \
+                                                                              int, int, int, int, int, FramePtrs<R>, int, int, int, int, int);
+#define LBM_TILE_S(R, COLL, SEM, TURB) LBM_TILE_ONE(R, COLL, SEM, 3, TURB) LBM_TILE_ONE(R, COLL, SEM, 4, TURB) LBM_TILE_ONE(R, COLL, SEM, 5, TURB)
+#define LBM_STREAM_ONE(R, COLL, SEM, TURB)                                                                                      \
+    LBM_X template __global__ void k_stream<R, COLL, SEM, TURB>(const R* __restrict__, R* __restrict__, Geo, Relax<R>, int, int, int, int, int, \
+                                                                int, FramePtrs<R>, int, int, int, int, int, int, int, int, int);
+#define LBM_STREAMW_ONE(R, COLL, SEM, TURB) \
+    LBM_X template __global__ void k_stream_walls<R, COLL, TURB>(const R* __restrict__, R* __restrict__, Geo, Relax<R>, int, int, int, int);
+#define LBM_STREAMS_ONE(R, COLL, SEM, TURB)                                                                                     \
+    LBM_X template __global__ void k_stream_walls_slab<R, COLL, TURB>(const R* __restrict__, R* __restrict__, Geo, Relax<R>, int, int, int, int, \
+                                                                      int, int, int, int, int, int);
+#define LBM_STREAMP_ONE(R, COLL, SEM, TURB) \
+    LBM_X template __global__ void k_stream_pairs<R, COLL, TURB>(const R* __restrict__, R* __restrict__, Geo, Relax<R>, int, int, int, int);
+
+// the families: the tile kernel (S = 3 .. 5 steps per launch) and k_stream in both semantics, the kernels with the walls inside
+// (k_stream_walls, k_stream_walls_slab, k_stream_pairs) in MRT_GPU.py semantics
+#define LBM_INST_TILES(R) LBM_GPU_VARIANTS(LBM_TILE_S, R) LBM_PY_VARIANTS(LBM_TILE_S, R)
+#define LBM_INST_STREAM(R) LBM_GPU_VARIANTS(LBM_STREAM_ONE, R) LBM_PY_VARIANTS(LBM_STREAM_ONE, R)
+#define LBM_INST_STREAMW(R) LBM_GPU_VARIANTS(LBM_STREAMW_ONE, R)
+#define LBM_INST_STREAMS(R) LBM_GPU_VARIANTS(LBM_STREAMS_ONE, R)
+#define LBM_INST_STREAMP(R) LBM_GPU_VARIANTS(LBM_STREAMP_ONE, R)
+
+#ifdef LBM_INST
+#define LBM_X
+LBM_INST
+#else
+#define LBM_X extern
+LBM_INST_TILES(float) LBM_INST_TILES(double)
+LBM_INST_STREAM(float) LBM_INST_STREAM(double)
+LBM_INST_STREAMW(float) LBM_INST_STREAMW(double)
+LBM_INST_STREAMS(float) LBM_INST_STREAMS(double)
+LBM_INST_STREAMP(float) LBM_INST_STREAMP(double)
+#endif

@@ -1,6 +1,6 @@
 // lbm_kernels.hpp -- the __global__ kernels of liblbm_hip.so (templates; see lbm_device.hpp for the per-cell operators).
-// Included by the host units (through lbm_host.hpp) and by lbm_tiles_f32.hip / lbm_tiles_f64.hip, which hold the explicit
-// instantiations of the multi-step tile kernel so that the three translation units compile in parallel (lbm_tiles_inst.hpp).
+// Included by the host units (through lbm_host.hpp) and by the units that hold the explicit instantiations of the multi-step
+// kernels, so that those compile in parallel (lbm_inst.hpp).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -24,6 +24,14 @@ struct Batch {
         w = bt.w[(z)];                 \
     }
 
+// Workgroups are dealt round-robin to the 8 XCDs (each with its own L2): workgroup b of the first 8 (n / 8) of n becomes the one that
+// gives every XCD a contiguous band of them (the rest keep their place).  Speed only: any placement is correct.
+__device__ __forceinline__ int xcd_band(int b, int n) {
+    const int per = n >> 3;
+    if (b < (per << 3)) b = (b & 7) * per + (b >> 3);
+    return b;
+}
+
 // Generic fused step: one thread per cell, rows y = row0 + blockIdx.y * row_stride.
 template <typename R, int COLL, int SEM, bool TURB>
 __global__ __launch_bounds__(BLK) void k_step_generic(const R* __restrict__ src, R* __restrict__ dst, Geo geo,
@@ -46,9 +54,7 @@ template <typename R, int COLL, int V, bool NT, bool TURB>
 __global__ __launch_bounds__(BLK, LBM_VEC_MIN_WAVES) void k_step_vec(const R* __restrict__ src, R* __restrict__ dst, Geo geo, Relax<R> w,
                                                   Batch<R> bt, int raw, int row0, int row_stride, int nxb, int nblocks) {
     LBM_BATCH_SELECT(blockIdx.y)
-    int b = blockIdx.x;
-    const int per = nblocks >> 3;
-    if (b < (per << 3)) b = (b & 7) * per + (b >> 3);
+    const int b = xcd_band(blockIdx.x, nblocks);
     const int y = row0 + (b / nxb) * row_stride;
     const int gy = geo.y0 + y;
     if (gy == 0 || gy == geo.NY - 1) {
@@ -83,9 +89,7 @@ __global__ __launch_bounds__(TB_NT) void k_step2_deep(const R* __restrict__ src,
     LBM_BATCH_SELECT(blockIdx.y)
     constexpr int V = 16 / (int)sizeof(R), TX = tb_txv<TURB>() * V, TY = tb_ty<TURB>();
     __shared__ __align__(16) R lds[(TURB ? Q + 2 : Q) * (TY + 2) * (TX + 2 * V)];
-    int b = blockIdx.x;
-    const int per = ntiles >> 3;
-    if (b < (per << 3)) b = (b & 7) * per + (b >> 3);   // every XCD walks its own band of tile rows
+    const int b = xcd_band(blockIdx.x, ntiles);   // every XCD walks its own band of tile rows
     update_tile2<R, COLL, V, TX, TY, TB_NT, TURB>(src, dst, geo, w, lds, TB_F + (b % ntx) * TX, TB_F + (b / ntx) * TY, xe, ye);
 }
 
@@ -235,9 +239,7 @@ __global__ __launch_bounds__(512, 4) void k_stepS_deep(const R* __restrict__ src
         return;
     }
     LBM_BATCH_SELECT(blockIdx.y)
-    int b = blockIdx.x - nframe;
-    const int per = ntiles >> 3;
-    if (b < (per << 3)) b = (b & 7) * per + (b >> 3);
+    const int b = xcd_band(blockIdx.x - nframe, ntiles);
     update_tile_inplace<R, COLL, V, TX, TY, S, TURB, RV>(src, dst, geo, w, lds_raw + V, F + (b % ntx) * TX, F + (b / ntx) * TY, xe, ye);
 }
 

@@ -29,7 +29,7 @@ int ensure_scratch(lbm_ctx* c, int n) {
 // One single step, lat[from] -> lat[to], on local rows row0 + i*stride, i in [0, nrows).
 int launch_rows(lbm_ctx* c, int from, int to, int row0, int stride, int nrows, hipStream_t s) {
     if (nrows <= 0) return LBM_OK;
-    dispatch(c->p, [&](auto v) {
+    return launch_variant(c, [&](auto v) {
         using VT = decltype(v);
         using R = typename VT::R;
         const R* src = (const R*)c->lat[from];
@@ -49,13 +49,11 @@ int launch_rows(lbm_ctx* c, int from, int to, int row0, int stride, int nrows, h
                                c->geo, relax_of<R>(c->p), batch_of<R>(c), raw, row0, stride);
         }
     });
-    HIP_TRY(c, hipGetLastError());
-    return LBM_OK;
 }
 
 // One single step on the frame of width W, lat[from] -> lat[to] (one pass of a multi-step; never a raw lattice).
 int launch_frame(lbm_ctx* c, int from, int to, int W, hipStream_t s, int elo, int ehi) {
-    dispatch(c->p, [&](auto v) {
+    return launch_variant(c, [&](auto v) {
         using VT = decltype(v);
         using R = typename VT::R;
         constexpr int V = 16 / (int)sizeof(R);
@@ -64,100 +62,102 @@ int launch_frame(lbm_ctx* c, int from, int to, int W, hipStream_t s, int elo, in
         hipLaunchKernelGGL((k_step_frame<R, VT::COLL, VT::SEM, VT::TURB>), dim3((unsigned)((cells + BLK - 1) / BLK), c->batch), dim3(BLK), 0, s,
                            (const R*)c->lat[from], (R*)c->lat[to], c->geo, relax_of<R>(c->p), batch_of<R>(c), W, elo, ehi, vec_rows);
     });
-    HIP_TRY(c, hipGetLastError());
-    return LBM_OK;
+}
+
+// The wall frame of a unit of S steps as the fused frame passes cut it (frame_passes): the two row strips in nsegx segments of L
+// columns each, the two column strips over the rows [ybeg, yend) in nsegy segments of L rows each, one workgroup per segment (nframe
+// of them; 0 when the launch has no frame).  in_lds: the passes keep their intermediate results in LDS windows (frame_lds_fits with
+// `budget` bytes, deep_rows and extra); where they do not, the scratch lattices are allocated here.
+struct FrameLayout {
+    int F, L, nsegx, nsegy, nframe;
+    bool in_lds;
+};
+static int frame_layout(lbm_ctx* c, FrameLayout& fl, int S, int ybeg, int yend, long long budget, bool deep_rows, int extra, bool with_frame = true) {
+    fl.F = c->tb_f;
+    fl.L = c->frame_seg;
+    fl.nsegx = frame_segs(c->geo.nx, fl.L);
+    fl.nsegy = frame_segs(yend - ybeg, fl.L);
+    fl.nframe = with_frame ? 2 * fl.nsegx + 2 * fl.nsegy : 0;
+    fl.in_lds = frame_lds_fits(c, S, deep_rows, extra, budget);
+    return with_frame && !fl.in_lds ? ensure_scratch(c, S - 1) : LBM_OK;
 }
 
 // extra: rows of the neighbours' side that the row strips own on top of the slab's (see frame_passes)
 int launch_frame_multi(lbm_ctx* c, int from, int to, int S, hipStream_t s, bool lo, bool hi, int extra) {
+    // (beside the streaming kernel: k_frame_beside has no LDS, its passes go through the scratch lattices)
     const bool beside = c->frame_beside && !lo && !hi && c->batch == 1;
-    if (beside || !frame_lds_fits(c, S, lo || hi, extra)) {
-        const int rc = ensure_scratch(c, S - 1);
-        if (rc) return rc;
-    }
-    dispatch(c->p, [&](auto v) {
+    FrameLayout fl;
+    const int rc = frame_layout(c, fl, S, c->tb_f, c->geo.ny - c->tb_f, beside ? 0 : FRAME_LDS_BYTES, lo || hi, extra);
+    if (rc) return rc;
+    return launch_variant(c, [&](auto v) {
         using VT = decltype(v);
         using R = typename VT::R;
         const FramePtrs<R> fp = frame_ptrs<R>(c, from, to, S);
-        const int F = c->tb_f, L = c->frame_seg, nsegx = (c->geo.nx + L - 1) / L, nsegy = (c->geo.ny - 2 * F + L - 1) / L;
-        if (beside) {
-            hipLaunchKernelGGL((k_frame_beside<R, VT::COLL, VT::SEM, VT::TURB>), dim3(2 * nsegx + 2 * nsegy), dim3(BLK), 0, s, fp, c->geo, relax_of<R>(c->p), F, S,
-                               nsegx, nsegy, L);
-            return;
-        }
-        const bool in_lds = frame_lds_fits(c, S, lo || hi, extra);
-        if (!in_lds && c->frame_wide)
-            hipLaunchKernelGGL((k_frame_multi<R, VT::COLL, VT::SEM, VT::TURB, 1024>), dim3(2 * nsegx + 2 * nsegy, c->batch), dim3(1024), 0, s, fp, c->geo,
-                               relax_of<R>(c->p), batch_of<R>(c), F, S, nsegx, nsegy, lo ? 1 + extra : 0, hi ? 1 + extra : 0, L, 0);
+        if (beside)
+            hipLaunchKernelGGL((k_frame_beside<R, VT::COLL, VT::SEM, VT::TURB>), dim3(fl.nframe), dim3(BLK), 0, s, fp, c->geo, relax_of<R>(c->p), fl.F, S,
+                               fl.nsegx, fl.nsegy, fl.L);
+        else if (!fl.in_lds && c->frame_wide)
+            hipLaunchKernelGGL((k_frame_multi<R, VT::COLL, VT::SEM, VT::TURB, 1024>), dim3(fl.nframe, c->batch), dim3(1024), 0, s, fp, c->geo,
+                               relax_of<R>(c->p), batch_of<R>(c), fl.F, S, fl.nsegx, fl.nsegy, lo ? 1 + extra : 0, hi ? 1 + extra : 0, fl.L, 0);
         else
-            hipLaunchKernelGGL((k_frame_multi<R, VT::COLL, VT::SEM, VT::TURB, BLK>), dim3(2 * nsegx + 2 * nsegy, c->batch), dim3(BLK), 0, s, fp, c->geo,
-                               relax_of<R>(c->p), batch_of<R>(c), F, S, nsegx, nsegy, lo ? 1 + extra : 0, hi ? 1 + extra : 0, L, in_lds ? 1 : 0);
+            hipLaunchKernelGGL((k_frame_multi<R, VT::COLL, VT::SEM, VT::TURB, BLK>), dim3(fl.nframe, c->batch), dim3(BLK), 0, s, fp, c->geo,
+                               relax_of<R>(c->p), batch_of<R>(c), fl.F, S, fl.nsegx, fl.nsegy, lo ? 1 + extra : 0, hi ? 1 + extra : 0, fl.L,
+                               fl.in_lds ? 1 : 0);
     });
-    HIP_TRY(c, hipGetLastError());
-    return LBM_OK;
 }
 
-// k_stream_walls_slab over rows [ybeg, yend) between the slab's edge bands (bands = 0: the bulk launch), or over the interface bands
-// `bands` (bit 0: low, bit 1: high) alone, each of which starts elo / ehi rows inside the neighbour's rows (the edge launch).
-static int launch_walls_slab(lbm_ctx* c, int from, int to, hipStream_t s, int S, int ybeg, int yend, int bands, int elo, int ehi) {
-    dispatch(c->p, [&](auto v) {
+// The one launcher of k_stream: the frame workgroups of fl, then nstrips x nseg streaming segments of the strip plan pl below row ye.
+// lo / hi / bands: the interface bands of an edge launch (launch_stream_edges; 0: the segments start at row F).
+static int launch_k_stream(lbm_ctx* c, int from, int to, hipStream_t s, int S, const FrameLayout& fl, const StreamPlan& pl, int nseg, int ye,
+                           int lo, int hi, int bands, bool xcd_bands) {
+    return launch_variant(c, [&](auto v) {
+        using VT = decltype(v);
+        using R = typename VT::R;
+        hipLaunchKernelGGL((k_stream<R, VT::COLL, VT::SEM, VT::TURB>), dim3(fl.nframe + pl.nstrips * nseg), dim3(ST_NT), 0, s, (const R*)c->lat[from],
+                           (R*)c->lat[to], c->geo, relax_of<R>(c->p), S, fl.F, c->geo.nx - fl.F, ye, pl.nstrips, pl.H, frame_ptrs<R>(c, from, to, S),
+                           fl.nframe, fl.nsegx, fl.nsegy, fl.L, fl.in_lds ? 1 : 0, lo, hi, bands, xcd_bands ? 1 : 0);
+    });
+}
+
+// The kernels with the walls inside: a lone lattice whole (k_stream_walls, or k_stream_pairs) or a slab by k_stream_walls_slab over the
+// rows [ybeg, yend) between its edge bands (bands = 0: the bulk launch), or over the interface bands `bands` (bit 0: low, bit 1: high)
+// alone, each of which starts elo / ehi rows inside the neighbour's rows (the edge launch).
+static int launch_walls(lbm_ctx* c, int from, int to, hipStream_t s, int S, int ybeg, int yend, int bands, int elo, int ehi) {
+    const StreamPlan pl = plan_stream(c, S);
+    const int xcd = c->xcd_bands ? 1 : 0;
+    return launch_variant(c, [&](auto v) {
         using VT = decltype(v);
         using R = typename VT::R;
         if constexpr (VT::SEM == SEM_GPU) {
-            const StreamPlan pl = plan_stream(c, S);
-            const int nwg = pl.nstrips * (bands ? (bands & 1) + (bands >> 1) : pl.nsegy);
-            hipLaunchKernelGGL((k_stream_walls_slab<R, VT::COLL, VT::TURB>), dim3(nwg), dim3(ST_NT), 0, s, (const R*)c->lat[from], (R*)c->lat[to],
-                               c->geo, relax_of<R>(c->p), S, pl.nstrips, pl.H, bands ? 0 : (c->xcd_bands ? 1 : 0), ybeg, yend, bands, elo, ehi,
-                               bands ? c->tb_f : 0);
+            const R* src = (const R*)c->lat[from];
+            R* dst = (R*)c->lat[to];
+            if (is_slab(c))
+                hipLaunchKernelGGL((k_stream_walls_slab<R, VT::COLL, VT::TURB>), dim3(pl.nstrips * (bands ? (bands & 1) + (bands >> 1) : pl.nsegy)),
+                                   dim3(ST_NT), 0, s, src, dst, c->geo, relax_of<R>(c->p), S, pl.nstrips, pl.H, bands ? 0 : xcd, ybeg, yend, bands,
+                                   elo, ehi, bands ? c->tb_f : 0);
+            else if (c->kern == Kern::stream_pairs)
+                hipLaunchKernelGGL((k_stream_pairs<R, VT::COLL, VT::TURB>), dim3(pl.nstrips * pl.nsegy), dim3(64 * pairs_waves(S)), 0, s, src, dst,
+                                   c->geo, relax_of<R>(c->p), S, pl.nstrips, pl.H, xcd);
+            else
+                hipLaunchKernelGGL((k_stream_walls<R, VT::COLL, VT::TURB>), dim3(pl.nstrips * pl.nsegy), dim3(ST_NT), 0, s, src, dst, c->geo,
+                                   relax_of<R>(c->p), S, pl.nstrips, pl.H, xcd);
         }
     });
-    HIP_TRY(c, hipGetLastError());
-    return LBM_OK;
 }
 
 int launch_stream(lbm_ctx* c, int from, int to, hipStream_t s, int S, bool with_frame) {
+    const int F = c->tb_f, ny = c->geo.ny;
     if (walls_inside(c)) {
         // walls included, no frame at all: the whole lattice in one launch (with_frame), or a slab's rows between its edge bands
         const bool slab = is_slab(c);
         if (slab == with_frame) return fail(c, LBM_ERR_STATE, "internal: the streaming kernel with the walls inside takes a whole lone lattice or a slab's bulk rows");
-        if (slab)
-            return launch_walls_slab(c, from, to, s, S, has_neighbour(c, LBM_SIDE_LOW) ? c->tb_f : 0,
-                                     c->geo.ny - (has_neighbour(c, LBM_SIDE_HIGH) ? c->tb_f : 0), 0, 0, 0);
-        dispatch(c->p, [&](auto v) {
-            using VT = decltype(v);
-            using R = typename VT::R;
-            if constexpr (VT::SEM == SEM_GPU) {
-                const StreamPlan pl = plan_stream(c, S);
-                if (c->kern == Kern::stream_pairs)
-                    hipLaunchKernelGGL((k_stream_pairs<R, VT::COLL, VT::TURB>), dim3(pl.nstrips * pl.nsegy), dim3(64 * pairs_waves(S)), 0, s,
-                                       (const R*)c->lat[from], (R*)c->lat[to], c->geo, relax_of<R>(c->p), S, pl.nstrips, pl.H, c->xcd_bands ? 1 : 0);
-                else
-                    hipLaunchKernelGGL((k_stream_walls<R, VT::COLL, VT::TURB>), dim3(pl.nstrips * pl.nsegy), dim3(ST_NT), 0, s, (const R*)c->lat[from],
-                                       (R*)c->lat[to], c->geo, relax_of<R>(c->p), S, pl.nstrips, pl.H, c->xcd_bands ? 1 : 0);
-            }
-        });
-        HIP_TRY(c, hipGetLastError());
-        return LBM_OK;
+        return launch_walls(c, from, to, s, S, has_neighbour(c, LBM_SIDE_LOW) ? F : 0, ny - (has_neighbour(c, LBM_SIDE_HIGH) ? F : 0), 0, 0, 0);
     }
-    const bool use_lds = frame_lds_fits(c, S, false, 0, ST_LDS_BYTES);
-    if (with_frame && !use_lds) {
-        const int rc = ensure_scratch(c, S - 1);
-        if (rc) return rc;
-    }
-    dispatch(c->p, [&](auto v) {
-        using VT = decltype(v);
-        using R = typename VT::R;
-        const int F = c->tb_f, xe = c->geo.nx - F, ye = c->geo.ny - F;
-        const StreamPlan pl = plan_stream(c, S);
-        const FramePtrs<R> fp = frame_ptrs<R>(c, from, to, S);
-        const int L = c->frame_seg, nsegx = (c->geo.nx + L - 1) / L, nsegy = (c->geo.ny - 2 * F + L - 1) / L;
-        const int nframe = with_frame ? 2 * nsegx + 2 * nsegy : 0;
-        hipLaunchKernelGGL((k_stream<R, VT::COLL, VT::SEM, VT::TURB>), dim3(nframe + pl.nstrips * pl.nsegy), dim3(ST_NT), 0, s,
-                           (const R*)c->lat[from], (R*)c->lat[to], c->geo, relax_of<R>(c->p), S, F, xe, ye, pl.nstrips, pl.H,
-                           fp, nframe, nsegx, nsegy, L, use_lds ? 1 : 0, 0, 0, 0, c->xcd_bands ? 1 : 0);
-    });
-    HIP_TRY(c, hipGetLastError());
-    return LBM_OK;
+    FrameLayout fl;
+    const int rc = frame_layout(c, fl, S, F, ny - F, ST_LDS_BYTES, false, 0, with_frame);
+    if (rc) return rc;
+    const StreamPlan pl = plan_stream(c, S);
+    return launch_k_stream(c, from, to, s, S, fl, pl, pl.nsegy, ny - F, 0, 0, 0, c->xcd_bands);
 }
 
 // The edge launch of a slab's unit under the streaming kernel: everything but the bulk rows [F, ny - F) x [F, nx - F) -- the wall
@@ -166,47 +166,23 @@ int launch_stream(lbm_ctx* c, int from, int to, hipStream_t s, int S, bool with_
 // streaming segment that starts in the neighbour's rows of the deep halo.  It writes every row the next exchange sends.
 // extra: rows of the neighbours' side owned on top (1 for the lagged lattice, see frame_passes).
 int launch_stream_edges(lbm_ctx* c, int from, int to, hipStream_t s, int S, bool lo, bool hi, int extra) {
+    const int elo = lo ? 1 + extra : 0, ehi = hi ? 1 + extra : 0, bands = (lo ? 1 : 0) | (hi ? 2 : 0);
     // the walls inside: the edge launch is the interface bands alone, over the whole width (side-wall cells in line)
-    if (walls_inside(c)) return launch_walls_slab(c, from, to, s, S, 0, 0, (lo ? 1 : 0) | (hi ? 2 : 0), lo ? 1 + extra : 0, hi ? 1 + extra : 0);
-    const bool use_lds = frame_lds_fits(c, S, false, extra, ST_LDS_BYTES);
-    if (!use_lds) {
-        const int rc = ensure_scratch(c, S - 1);
-        if (rc) return rc;
-    }
-    dispatch(c->p, [&](auto v) {
-        using VT = decltype(v);
-        using R = typename VT::R;
-        const int F = c->tb_f, xe = c->geo.nx - F, ye = c->geo.ny - F;
-        const StreamPlan pl = plan_stream(c, S);
-        const FramePtrs<R> fp = frame_ptrs<R>(c, from, to, S);
-        const int bands = (lo ? 1 : 0) | (hi ? 2 : 0);
-        const int ybeg = lo ? -extra : F, yend = hi ? c->geo.ny + extra : c->geo.ny - F;
-        const int L = c->frame_seg, nsegx = (c->geo.nx + L - 1) / L, nsegy = (yend - ybeg + L - 1) / L;
-        const int nframe = 2 * nsegx + 2 * nsegy;
-        hipLaunchKernelGGL((k_stream<R, VT::COLL, VT::SEM, VT::TURB>), dim3(nframe + pl.nstrips * ((lo ? 1 : 0) + (hi ? 1 : 0))), dim3(ST_NT), 0, s,
-                           (const R*)c->lat[from], (R*)c->lat[to], c->geo, relax_of<R>(c->p), S, F, xe, ye, pl.nstrips, pl.H,
-                           fp, nframe, nsegx, nsegy, L, use_lds ? 1 : 0, lo ? 1 + extra : 0,
-                           hi ? 1 + extra : 0, bands, 0);
-    });
-    HIP_TRY(c, hipGetLastError());
-    return LBM_OK;
+    if (walls_inside(c)) return launch_walls(c, from, to, s, S, 0, 0, bands, elo, ehi);
+    const int F = c->tb_f, ny = c->geo.ny;
+    FrameLayout fl;
+    const int rc = frame_layout(c, fl, S, lo ? -extra : F, hi ? ny + extra : ny - F, ST_LDS_BYTES, false, extra);
+    if (rc) return rc;
+    return launch_k_stream(c, from, to, s, S, fl, plan_stream(c, S), (lo ? 1 : 0) + (hi ? 1 : 0), ny - F, elo, ehi, bands, false);
 }
 
 // The first launch of the streaming kernel in a process costs ~1.4 ms (code upload, 144 KiB of LDS, scratch set-up).  Where the first
 // units of a run may go to the tile kernel (tail_tiles: Kern::stream on a lone fp32 lattice) that cost would land in the middle of a
 // run -- in the driver's 20 timed steps after a 5-step warm-up, for one -- so lbm_create pays it: one workgroup that returns at once
-// (its segment is empty).
+// (its segment, rows [F, ye = F), is empty).
 int warm_stream(lbm_ctx* c) {
-    dispatch(c->p, [&](auto v) {
-        using VT = decltype(v);
-        using R = typename VT::R;
-        const int F = c->tb_f;
-        const FramePtrs<R> fp = frame_ptrs<R>(c, 0, 1, 1);
-        hipLaunchKernelGGL((k_stream<R, VT::COLL, VT::SEM, VT::TURB>), dim3(1), dim3(ST_NT), 0, c->s_compute, (const R*)c->lat[0], (R*)c->lat[1],
-                           c->geo, relax_of<R>(c->p), c->tb_steps, F, c->geo.nx - F, /*ye=*/F, 1, 1, fp, 0, 1, 1, c->frame_seg, 0, 0, 0, 0, 0);
-    });
-    HIP_TRY(c, hipGetLastError());
-    return LBM_OK;
+    const FrameLayout none{c->tb_f, c->frame_seg, 1, 1, 0, false};
+    return launch_k_stream(c, 0, 1, c->s_compute, c->tb_steps, none, StreamPlan{1, 1, 1}, 1, c->tb_f, 0, 0, 0, false);
 }
 
 // The bulk launch of a unit (with_frame: and the frame, the unit's only launch) by the context's kernel.
@@ -223,44 +199,35 @@ int launch_deep(lbm_ctx* c, int from, int to, hipStream_t s, int steps, bool wit
         case Kern::stream_pairs: return launch_stream(c, from, to, s, steps, with_frame);
         default: break;
     }
-    const int S_tile = steps >= 3 ? (steps == 4 || steps == 5 ? steps : 3) : 2;
-    const bool tile_frame_lds = frame_lds_fits(c, S_tile, false, 0, TILE_FRAME_LDS_BYTES);
-    if (with_frame && steps >= 3 && !tile_frame_lds) {
-        const int rc = ensure_scratch(c, S_tile - 1);
-        if (rc) return rc;
-    }
-    dispatch(c->p, [&](auto v) {
+    const int F = c->tb_f, xe = c->geo.nx - F, ye = c->geo.ny - F;
+    if (steps < 3)
+        return launch_variant(c, [&](auto v) {
+            using VT = decltype(v);
+            using R = typename VT::R;
+            constexpr int V = 16 / (int)sizeof(R), TX = tb_txv<VT::TURB>() * V, TY = tb_ty<VT::TURB>();
+            const int ntx = (xe - TB_F + TX - 1) / TX, nty = (ye - TB_F + TY - 1) / TY;   // two steps: F = TB_F
+            hipLaunchKernelGGL((k_step2_deep<R, VT::COLL, VT::TURB>), dim3(ntx * nty, c->batch), dim3(TB_NT), 0, s, (const R*)c->lat[from],
+                               (R*)c->lat[to], c->geo, relax_of<R>(c->p), batch_of<R>(c), xe, ye, ntx, ntx * nty);
+        });
+    const int S_tile = steps == 4 || steps == 5 ? steps : 3;
+    FrameLayout fl;
+    const int rc = frame_layout(c, fl, S_tile, F, c->geo.ny - F, TILE_FRAME_LDS_BYTES, false, 0, with_frame);
+    if (rc) return rc;
+    return launch_variant(c, [&](auto v) {
         using VT = decltype(v);
         using R = typename VT::R;
-        const int F = c->tb_f, xe = c->geo.nx - F, ye = c->geo.ny - F;
-        if (steps >= 3) {
-            constexpr int V = 16 / (int)sizeof(R);
-            auto go = [&](auto steps, auto wide) {
-                constexpr int S = decltype(steps)::value;
-                constexpr bool WIDE = decltype(wide)::value;
-                constexpr int PVC = WIDE ? 32 : 16, RV = (S - 1 + V - 1) / V, TX = (PVC - 2 * RV) * V, TY = 512 / PVC - 2 * (S - 1);
-                const int ntx = (xe - F + TX - 1) / TX, nty = (ye - F + TY - 1) / TY;
-                const FramePtrs<R> fp = frame_ptrs<R>(c, from, to, S);
-                const int L = c->frame_seg, nsegx = (c->geo.nx + L - 1) / L, nsegy = (c->geo.ny - 2 * F + L - 1) / L;
-                const int nframe = with_frame ? 2 * nsegx + 2 * nsegy : 0;
-                hipLaunchKernelGGL((k_stepS_deep<R, VT::COLL, VT::SEM, S, WIDE, VT::TURB>), dim3(nframe + ntx * nty, c->batch), dim3(512), 0, s,
-                                   (const R*)c->lat[from], (R*)c->lat[to], c->geo, relax_of<R>(c->p), batch_of<R>(c), F, xe, ye, ntx, ntx * nty,
-                                   fp, nframe, nsegx, nsegy, L, tile_frame_lds ? 1 : 0);
-            };
-            {   // (fp64: the x rim of S >= 4 is two vectors wide)
-                if (steps == 4) { go(std::integral_constant<int, 4>{}, std::false_type{}); return; }
-                if (steps == 5) { go(std::integral_constant<int, 5>{}, std::false_type{}); return; }
-            }
-            go(std::integral_constant<int, 3>{}, std::false_type{});
-            return;
-        }
-        constexpr int V = 16 / (int)sizeof(R), TX = tb_txv<VT::TURB>() * V, TY = tb_ty<VT::TURB>();
-        const int ntx = (xe - TB_F + TX - 1) / TX, nty = (ye - TB_F + TY - 1) / TY;   // two steps: F = TB_F
-        hipLaunchKernelGGL((k_step2_deep<R, VT::COLL, VT::TURB>), dim3(ntx * nty, c->batch), dim3(TB_NT), 0, s, (const R*)c->lat[from],
-                           (R*)c->lat[to], c->geo, relax_of<R>(c->p), batch_of<R>(c), xe, ye, ntx, ntx * nty);
+        constexpr int V = 16 / (int)sizeof(R);
+        auto go = [&](auto steps) {   // (fp64: the x rim of S >= 4 is two vectors wide)
+            constexpr int S = decltype(steps)::value, PVC = 16, RV = (S - 1 + V - 1) / V, TX = (PVC - 2 * RV) * V, TY = 512 / PVC - 2 * (S - 1);
+            const int ntx = (xe - F + TX - 1) / TX, nty = (ye - F + TY - 1) / TY;
+            hipLaunchKernelGGL((k_stepS_deep<R, VT::COLL, VT::SEM, S, false, VT::TURB>), dim3(fl.nframe + ntx * nty, c->batch), dim3(512), 0, s,
+                               (const R*)c->lat[from], (R*)c->lat[to], c->geo, relax_of<R>(c->p), batch_of<R>(c), F, xe, ye, ntx, ntx * nty,
+                               frame_ptrs<R>(c, from, to, S), fl.nframe, fl.nsegx, fl.nsegy, fl.L, fl.in_lds ? 1 : 0);
+        };
+        if (S_tile == 4) go(std::integral_constant<int, 4>{});
+        else if (S_tile == 5) go(std::integral_constant<int, 5>{});
+        else go(std::integral_constant<int, 3>{});
     });
-    HIP_TRY(c, hipGetLastError());
-    return LBM_OK;
 }
 
 // bookkeeping after a launch unit of S steps lat[cur] -> lat[cur ^ 1]
@@ -459,7 +426,7 @@ int prev_lattice(lbm_ctx* c, int* which) {
 
 // One step of the push scheme: collide-and-push lat[cur] -> ftemp (lat[2]); wall rules on ftemp + copy -> lat[cur ^ 1].
 int push_step(lbm_ctx* c) {
-    dispatch(c->p, [&](auto v) {
+    const int rc = launch_variant(c, [&](auto v) {
         using VT = decltype(v);
         using R = typename VT::R;
         const dim3 g = grid_rows(c, c->geo.ny);
@@ -468,7 +435,7 @@ int push_step(lbm_ctx* c) {
         hipLaunchKernelGGL((k_push_bc<R, VT::COLL, VT::SEM>), g, dim3(BLK), 0, c->s_compute, (const R*)c->lat[c->cur], (R*)c->lat[2],
                            (R*)c->lat[c->cur ^ 1], c->geo, (R)c->p.uLB);
     });
-    HIP_TRY(c, hipGetLastError());
+    if (rc) return rc;
     finish_unit(c, 1);
     return LBM_OK;
 }

@@ -53,7 +53,7 @@ StreamPlan plan_stream(const lbm_ctx* c, int S) {
     if ((long long)p0.nstrips * p0.nsegy > c->ncu) return p0;     // several rounds: the bulk launch is released behind the edge launch instead
     const int nb = (has_neighbour(c, LBM_SIDE_LOW) ? 1 : 0) + (has_neighbour(c, LBM_SIDE_HIGH) ? 1 : 0), L = c->frame_seg;
     const long long n_edge = walls ? (long long)nb * p0.nstrips     // (the walls inside: the interface bands alone)
-                                   : (long long)nb * p0.nstrips + 2LL * ((c->geo.ny + L - 1) / L) + (2LL - nb) * ((c->geo.nx + L - 1) / L);
+                                   : (long long)nb * p0.nstrips + 2LL * frame_segs(c->geo.ny, L) + (2LL - nb) * frame_segs(c->geo.nx, L);
     const long long edge_it = c->tb_f + 2 * (S - 1) + ST_WAVES - 1;
     // (measured: a bulk launch longer than ~1.5 edge workgroups overlaps the frame variant's ~100 short edge workgroups well enough as
     // it is.  With the walls inside the edge launch is the 2 x nstrips band workgroups alone, each of which holds a CU -- all its LDS --

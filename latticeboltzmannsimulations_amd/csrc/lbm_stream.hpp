@@ -483,6 +483,8 @@ __global__ __launch_bounds__(ST_NT) void k_stream(const R* __restrict__ src, R* 
     }
     constexpr int V = 16 / (int)sizeof(R);
     int b = blockIdx.x - nframe;
+    // (the remap of xcd_band and the edge rows are written out here and in k_stream_walls_slab, which also spells out walls_strip: as
+    // calls of shared helpers they change how the compiler lays out the branches of these two kernels)
     if (xcd_bands) {
         // consecutive workgroups go to consecutive XCDs (each with its own L2): give every XCD a contiguous run of segments, so
         // that the strips that share rim columns -- read at the same time, the workgroups march in step -- share an L2
@@ -507,25 +509,33 @@ __global__ __launch_bounds__(ST_NT) void k_stream(const R* __restrict__ src, R* 
     stream_segment<R, COLL, TURB>(src, dst, geo, w, lds, S, xs, ya, yb, xe);
 }
 
+// The strips of the kernels with the walls inside (k_stream_walls, k_stream_walls_slab, k_stream_pairs): strip i starts at
+// xs = min(i TXu, nx - 64 V) with TXu = 64 V - 2 R useful columns between two rims (no rim at a wall) and owns the columns
+// [own_lo, own_hi) = [i TXu + R, (i + 1) TXu + R), the first one from 0, the last one to nx.  The host counts them with
+// stream_walls_strips, the device places them with walls_strip: the two rules sit together here.
+__host__ __device__ constexpr int stream_walls_strips(int nx, int S, int V) {
+    return nx <= 64 * V ? 1 : (nx - 64 * V + (64 * V - 2 * stream_rim(S, V)) - 1) / (64 * V - 2 * stream_rim(S, V)) + 1;
+}
+template <int V>
+__device__ __forceinline__ void walls_strip(const Geo& geo, int S, int strip, int nstrips, int& xs, int& own_lo, int& own_hi) {
+    const int R_ = stream_rim(S, V), TXu = 64 * V - 2 * R_;
+    xs = min(strip * TXu, max(geo.nx - 64 * V, 0));
+    own_lo = strip == 0 ? 0 : strip * TXu + R_;
+    own_hi = strip == nstrips - 1 ? geo.nx : (strip + 1) * TXu + R_;
+}
+
 // The streaming kernel with the walls inside (see "the walls inside the streaming kernel" above): a lone lattice in MRT_GPU.py
-// semantics, nx a multiple of the vector width.  grid: nstrips * nsegy segments; strip i starts at min(i TXu, nx - 64 V) with
-// TXu = 64 V - 2 R useful columns between two rims (no rim at a wall) and owns the columns [i TXu + R, (i + 1) TXu + R), the
-// first one from 0, the last one to nx; segment j owns the rows [j H, (j + 1) H).  No frame, no scratch lattices.
+// semantics, nx a multiple of the vector width.  grid: nstrips * nsegy segments (walls_strip); segment j owns the rows [j H, (j + 1) H).
+// No frame, no scratch lattices.
 template <typename R, int COLL, bool TURB>
 __global__ __launch_bounds__(ST_NT) void k_stream_walls(const R* __restrict__ src, R* __restrict__ dst, Geo geo, Relax<R> w, int S, int nstrips, int H,
                                                         int xcd_bands) {
     __shared__ __align__(16) R lds[ST_LDS_BYTES / sizeof(R)];
-    constexpr int V = 16 / (int)sizeof(R), W = 64 * V;
-    int b = blockIdx.x;
-    if (xcd_bands) {   // (as k_stream: every XCD a contiguous run of segments)
-        const int per = (int)gridDim.x >> 3;
-        if (b < (per << 3)) b = (b & 7) * per + (b >> 3);
-    }
+    constexpr int V = 16 / (int)sizeof(R);
+    const int b = xcd_bands ? xcd_band(blockIdx.x, gridDim.x) : (int)blockIdx.x;   // (as k_stream: every XCD a contiguous run of segments)
     const int strip = b % nstrips, sy = b / nstrips;
-    const int R_ = stream_rim(S, V), TXu = W - 2 * R_;
-    const int xs = min(strip * TXu, max(geo.nx - W, 0));
-    const int own_lo = strip == 0 ? 0 : strip * TXu + R_;
-    const int own_hi = strip == nstrips - 1 ? geo.nx : (strip + 1) * TXu + R_;
+    int xs, own_lo, own_hi;
+    walls_strip<V>(geo, S, strip, nstrips, xs, own_lo, own_hi);
     const int ya = sy * H, yb = min(geo.ny, ya + H);
     if (ya >= yb) return;
     stream_segment<R, COLL, TURB, true>(src, dst, geo, w, lds, S, xs, ya, yb, 0, own_lo, own_hi);
@@ -539,7 +549,7 @@ __global__ __launch_bounds__(ST_NT) void k_stream_walls_slab(const R* __restrict
                                                              int xcd_bands, int ybeg, int yend, int bands, int lo, int hi, int F) {
     __shared__ __align__(16) R lds[ST_LDS_BYTES / sizeof(R)];
     constexpr int V = 16 / (int)sizeof(R), W = 64 * V;
-    int b = blockIdx.x;
+    int b = blockIdx.x;   // (xcd_band and walls_strip written out: see k_stream)
     if (xcd_bands) {
         const int per = (int)gridDim.x >> 3;
         if (b < (per << 3)) b = (b & 7) * per + (b >> 3);
@@ -559,10 +569,6 @@ __global__ __launch_bounds__(ST_NT) void k_stream_walls_slab(const R* __restrict
     }
     if (ya >= yb) return;
     stream_segment<R, COLL, TURB, true, true>(src, dst, geo, w, lds, S, xs, ya, yb, 0, own_lo, own_hi);
-}
-// strips of k_stream_walls for a lattice nx wide (host and device agree through this one function)
-__host__ __device__ constexpr int stream_walls_strips(int nx, int S, int V) {
-    return nx <= 64 * V ? 1 : (nx - 64 * V + (64 * V - 2 * stream_rim(S, V)) - 1) / (64 * V - 2 * stream_rim(S, V)) + 1;
 }
 
 // ---- two rows per wave (k_stream_pairs) -------------------------------------------------------------------------------------------
@@ -817,92 +823,12 @@ template <typename R, int COLL, bool TURB>
 __global__ __launch_bounds__(SP_NT) void k_stream_pairs(const R* __restrict__ src, R* __restrict__ dst, Geo geo, Relax<R> w, int S, int nstrips, int H,
                                                         int xcd_bands) {
     __shared__ __align__(16) R lds[SP_LDS_BYTES / sizeof(R)];
-    constexpr int V = 16 / (int)sizeof(R), W = 64 * V;
-    int b = blockIdx.x;
-    if (xcd_bands) {
-        const int per = (int)gridDim.x >> 3;
-        if (b < (per << 3)) b = (b & 7) * per + (b >> 3);
-    }
+    constexpr int V = 16 / (int)sizeof(R);
+    const int b = xcd_bands ? xcd_band(blockIdx.x, gridDim.x) : (int)blockIdx.x;
     const int strip = b % nstrips, sy = b / nstrips;
-    const int R_ = stream_rim(S, V), TXu = W - 2 * R_;
-    const int xs = min(strip * TXu, max(geo.nx - W, 0));
-    const int own_lo = strip == 0 ? 0 : strip * TXu + R_;
-    const int own_hi = strip == nstrips - 1 ? geo.nx : (strip + 1) * TXu + R_;
+    int xs, own_lo, own_hi;
+    walls_strip<V>(geo, S, strip, nstrips, xs, own_lo, own_hi);
     const int ya = sy * H, yb = min(geo.ny, ya + H);
     if (ya >= yb) return;
     stream_pairs_segment<R, COLL, TURB>(src, dst, geo, w, lds, S, xs, ya, yb, own_lo, own_hi);
 }
-
-#ifndef LBM_STREAMP_EXTERN
-#define LBM_STREAMP_EXTERN extern
-#endif
-#define LBM_STREAMP_ONE(R, COLL, TURB)                                                                                    \
-    LBM_STREAMP_EXTERN template __global__ void k_stream_pairs<R, COLL, TURB>(const R* __restrict__, R* __restrict__, Geo, Relax<R>, int, int, int, int);
-#define LBM_STREAMP_ALL(R)                                                                                                \
-    LBM_STREAMP_ONE(R, C_SRT, false) LBM_STREAMP_ONE(R, C_TRT, false) LBM_STREAMP_ONE(R, C_MRT, false)                      \
-    LBM_STREAMP_ONE(R, C_MRT_FAST, false) LBM_STREAMP_ONE(R, C_SRT_FAST, false) LBM_STREAMP_ONE(R, C_TRT_FAST, false)       \
-    LBM_STREAMP_ONE(R, C_SRT, true) LBM_STREAMP_ONE(R, C_TRT, true) LBM_STREAMP_ONE(R, C_MRT, true)                         \
-    LBM_STREAMP_ONE(R, C_MRT_FAST, true) LBM_STREAMP_ONE(R, C_SRT_FAST, true) LBM_STREAMP_ONE(R, C_TRT_FAST, true)
-#if !defined(LBM_STREAM_ONLY_F64) && !defined(LBM_STREAMP_SKIP)
-LBM_STREAMP_ALL(float)
-#endif
-#if !defined(LBM_STREAM_ONLY_F32) && !defined(LBM_STREAMP_SKIP)
-LBM_STREAMP_ALL(double)
-#endif
-
-// explicit instantiations live in lbm_stream_f32.hip / lbm_stream_f64.hip and lbm_streamw_f32.hip / lbm_streamw_f64.hip
-// (LBM_STREAM_EXTERN / LBM_STREAMW_EXTERN empty there)
-#ifndef LBM_STREAMW_EXTERN
-#define LBM_STREAMW_EXTERN extern
-#endif
-#define LBM_STREAMW_ONE(R, COLL, TURB)                                                                                    \
-    LBM_STREAMW_EXTERN template __global__ void k_stream_walls<R, COLL, TURB>(const R* __restrict__, R* __restrict__, Geo, Relax<R>, int, int, int, int);
-#define LBM_STREAMW_ALL(R)                                                                                                \
-    LBM_STREAMW_ONE(R, C_SRT, false) LBM_STREAMW_ONE(R, C_TRT, false) LBM_STREAMW_ONE(R, C_MRT, false)                      \
-    LBM_STREAMW_ONE(R, C_MRT_FAST, false) LBM_STREAMW_ONE(R, C_SRT_FAST, false) LBM_STREAMW_ONE(R, C_TRT_FAST, false)       \
-    LBM_STREAMW_ONE(R, C_SRT, true) LBM_STREAMW_ONE(R, C_TRT, true) LBM_STREAMW_ONE(R, C_MRT, true)                         \
-    LBM_STREAMW_ONE(R, C_MRT_FAST, true) LBM_STREAMW_ONE(R, C_SRT_FAST, true) LBM_STREAMW_ONE(R, C_TRT_FAST, true)
-#if !defined(LBM_STREAM_ONLY_F64) && !defined(LBM_STREAMW_SKIP)
-LBM_STREAMW_ALL(float)
-#endif
-#if !defined(LBM_STREAM_ONLY_F32) && !defined(LBM_STREAMW_SKIP)
-LBM_STREAMW_ALL(double)
-#endif
-
-// ... the slab variant of the same: lbm_streams_f32.hip / lbm_streams_f64.hip
-#ifndef LBM_STREAMS_EXTERN
-#define LBM_STREAMS_EXTERN extern
-#endif
-#define LBM_STREAMS_ONE(R, COLL, TURB)                                                                                    \
-    LBM_STREAMS_EXTERN template __global__ void k_stream_walls_slab<R, COLL, TURB>(const R* __restrict__, R* __restrict__, Geo, Relax<R>, int, int, int, \
-                                                                                   int, int, int, int, int, int, int);
-#define LBM_STREAMS_ALL(R)                                                                                                \
-    LBM_STREAMS_ONE(R, C_SRT, false) LBM_STREAMS_ONE(R, C_TRT, false) LBM_STREAMS_ONE(R, C_MRT, false)                      \
-    LBM_STREAMS_ONE(R, C_MRT_FAST, false) LBM_STREAMS_ONE(R, C_SRT_FAST, false) LBM_STREAMS_ONE(R, C_TRT_FAST, false)       \
-    LBM_STREAMS_ONE(R, C_SRT, true) LBM_STREAMS_ONE(R, C_TRT, true) LBM_STREAMS_ONE(R, C_MRT, true)                         \
-    LBM_STREAMS_ONE(R, C_MRT_FAST, true) LBM_STREAMS_ONE(R, C_SRT_FAST, true) LBM_STREAMS_ONE(R, C_TRT_FAST, true)
-#if !defined(LBM_STREAM_ONLY_F64) && !defined(LBM_STREAMS_SKIP)
-LBM_STREAMS_ALL(float)
-#endif
-#if !defined(LBM_STREAM_ONLY_F32) && !defined(LBM_STREAMS_SKIP)
-LBM_STREAMS_ALL(double)
-#endif
-
-#ifndef LBM_STREAM_EXTERN
-#define LBM_STREAM_EXTERN extern
-#endif
-#define LBM_STREAM_ONE(R, COLL, SEM, TURB)                                                                               \
-    LBM_STREAM_EXTERN template __global__ void k_stream<R, COLL, SEM, TURB>(const R* __restrict__, R* __restrict__, Geo, Relax<R>, int, int, int, int, \
-                                                                          int, int, FramePtrs<R>, int, int, int, int, int, int, int, int, int);
-#define LBM_STREAM_ALL(R)                                                                                                \
-    LBM_STREAM_ONE(R, C_SRT, SEM_GPU, false) LBM_STREAM_ONE(R, C_TRT, SEM_GPU, false) LBM_STREAM_ONE(R, C_MRT, SEM_GPU, false)          \
-    LBM_STREAM_ONE(R, C_MRT_FAST, SEM_GPU, false) LBM_STREAM_ONE(R, C_SRT_FAST, SEM_GPU, false) LBM_STREAM_ONE(R, C_TRT_FAST, SEM_GPU, false) \
-    LBM_STREAM_ONE(R, C_SRT, SEM_GPU, true) LBM_STREAM_ONE(R, C_TRT, SEM_GPU, true) LBM_STREAM_ONE(R, C_MRT, SEM_GPU, true)             \
-    LBM_STREAM_ONE(R, C_MRT_FAST, SEM_GPU, true) LBM_STREAM_ONE(R, C_SRT_FAST, SEM_GPU, true) LBM_STREAM_ONE(R, C_TRT_FAST, SEM_GPU, true) \
-    LBM_STREAM_ONE(R, C_SRT, SEM_PY, false) LBM_STREAM_ONE(R, C_TRT, SEM_PY, false) LBM_STREAM_ONE(R, C_MRT, SEM_PY, false)
-#if !defined(LBM_STREAM_ONLY_F64) && !defined(LBM_STREAM_SKIP)
-LBM_STREAM_ALL(float)
-#endif
-#if !defined(LBM_STREAM_ONLY_F32) && !defined(LBM_STREAM_SKIP)
-LBM_STREAM_ALL(double)
-#endif

@@ -1,7 +1,3 @@
-// lbm_streamw_f64.hip -- explicit instantiations of the streaming kernel with the walls inside, double (k_stream_walls, lbm_stream.hpp)
-#define LBM_STREAMW_EXTERN
-#define LBM_STREAM_ONLY_F64
-#define LBM_STREAM_SKIP
-#define LBM_STREAMP_SKIP
-#define LBM_STREAMS_SKIP
-#include "lbm_stream.hpp"
+// lbm_streamw_f64.hip -- explicit instantiations of the streaming kernel with the walls inside (k_stream_walls), double (lbm_inst.hpp)
+#define LBM_INST LBM_INST_STREAMW(double)
+#include "lbm_inst.hpp"

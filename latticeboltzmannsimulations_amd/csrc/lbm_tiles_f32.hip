@@ -1,5 +1,3 @@
-// lbm_tiles_f32.hip -- explicit instantiations of the multi-step tile kernel, float (see lbm_tiles_inst.hpp)
-#include "lbm_kernels.hpp"
-#define LBM_TILE_EXTERN
-#define LBM_TILES_ONLY_F32
-#include "lbm_tiles_inst.hpp"
+// lbm_tiles_f32.hip -- explicit instantiations of the multi-step tile kernel (k_stepS_deep), float (lbm_inst.hpp)
+#define LBM_INST LBM_INST_TILES(float)
+#include "lbm_inst.hpp"
