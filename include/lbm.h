@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define LBM_ABI_VERSION 3
+#define LBM_ABI_VERSION 4
 
 typedef enum lbm_status {
     LBM_OK = 0,
@@ -46,7 +46,7 @@ enum { LBM_KERNEL_AUTO = 0,      /* fastest applicable: STREAM (large lattices),
        LBM_KERNEL_STREAM = 5 };  /* up to 8 time steps per launch, streamed down column strips (rows held in registers, neighbour rows
                                     through LDS): what AUTO picks for large lone lattices; otherwise as TB */
 enum { LBM_LAYOUT_AUTO = 0, LBM_LAYOUT_PLANES = 1, LBM_LAYOUT_ROWS = 2 }; /* device arrays: [k][y][x] or [y][k][x] */
-enum { LBM_ARITH_STRICT = 0, LBM_ARITH_FAST = 1 };
+enum { LBM_ARITH_STRICT = 0, LBM_ARITH_FAST = 1, LBM_ARITH_PROMOTED = 2 };
 enum { LBM_SIDE_LOW = 0, LBM_SIDE_HIGH = 1 };           /* slab neighbour towards smaller / larger y */
 /* lbm_params.flags: A/B switches of the launch plan (all off = the measured defaults); results never depend on them */
 enum { LBM_FLAG_NO_DEEP_HALO = 1,        /* between slabs: a one-row exchange after every frame pass of a multi-step launch instead
@@ -99,7 +99,12 @@ typedef struct lbm_params {
                             Smagorinsky closure's divisions / square root by the hardware's reciprocal / square-root
                             instructions (fp32: 1 ulp; fp64: refined by Newton steps).
                             Results agree with the strict form to rounding, not bit for bit.  MRT_GPU semantics only
-                            (with LBM_SEM_MRT_PY the strict form is used). */
+                            (with LBM_SEM_MRT_PY the strict form is used).
+                            LBM_ARITH_PROMOTED: the arithmetic of MRT_GPU.py's CUDA text -- the strict form, with the
+                            sub-expressions that its double literals make double (equilibrium bracket, MRT m_eq sums,
+                            Smagorinsky tau) evaluated in double and rounded to float once; fp32 results bit-identical to
+                            the oracles' promote = True.  fp64: the same as STRICT.  MRT_GPU semantics only (rejected with
+                            LBM_SEM_MRT_PY); not with LBM_FLAG_STREAM_PAIRS. */
     int32_t ny_local_min; /* slabs: the smallest ny_local of ALL ranks (0: = ny_local).  The launch plan (steps per launch, frame
                             width, deep halo) is derived from it, so that every rank of a decomposition runs the same exchange
                             protocol whatever its own share of the rows; lbm_comm_init() cross-checks the plan with both neighbours. */

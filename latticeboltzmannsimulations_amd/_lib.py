@@ -22,14 +22,14 @@ LBM_SEM_MRT_PY, LBM_SEM_MRT_GPU = 0, 1
 LBM_KERNEL_AUTO, LBM_KERNEL_GENERIC, LBM_KERNEL_VEC, LBM_KERNEL_TB, LBM_KERNEL_PUSH, LBM_KERNEL_STREAM = 0, 1, 2, 3, 4, 5
 LBM_LAYOUT_AUTO, LBM_LAYOUT_PLANES, LBM_LAYOUT_ROWS = 0, 1, 2
 LBM_SIDE_LOW, LBM_SIDE_HIGH = 0, 1
-LBM_ARITH_STRICT, LBM_ARITH_FAST = 0, 1
+LBM_ARITH_STRICT, LBM_ARITH_FAST, LBM_ARITH_PROMOTED = 0, 1, 2
 # lbm_params.flags (A/B switches of the launch plan; results never depend on them)
 LBM_FLAG_NO_DEEP_HALO, LBM_FLAG_FRAME_UNFUSED, LBM_FLAG_FRAME_FUSED_BATCH, LBM_FLAG_NO_FRAME_LDS = 1, 2, 4, 8
 LBM_FLAG_NT_ON, LBM_FLAG_NT_OFF, LBM_FLAG_COMM_PRIORITY_OFF, LBM_FLAG_EAGER_LAG = 16, 32, 64, 128
 LBM_FLAG_FRAME_BESIDE_ON, LBM_FLAG_FRAME_BESIDE_OFF, LBM_FLAG_FRAME_NARROW, LBM_FLAG_NO_EDGE_FIRST = 512, 1024, 2048, 4096
 LBM_FLAG_NO_EDGE_RESERVE, LBM_FLAG_NO_XCD_BANDS, LBM_FLAG_NO_TAIL_TILES, LBM_FLAG_STREAM_WALLS = 8192, 16384, 32768, 65536
 LBM_FLAG_STREAM_PAIRS, LBM_FLAG_NO_STREAM_WALLS = 131072, 262144
-ABI_VERSION = 3        # = LBM_ABI_VERSION of include/lbm.h (tests/test_abi.py keeps them equal)
+ABI_VERSION = 4        # = LBM_ABI_VERSION of include/lbm.h (tests/test_abi.py keeps them equal)
 
 
 class lbm_params(ctypes.Structure):

@@ -24,9 +24,14 @@ enum { C_SRT = 0, C_TRT = 1, C_MRT = 2,
        // lbm_params.arith = LBM_ARITH_FAST: not the reference's operation order / rounding --
        C_MRT_FAST = 3,     // the MRT operator in factored form with fused multiply-adds
        C_SRT_FAST = 4,     // SRT / TRT as in the strict form, but u = j * rcp(rho) and the closure's divisions and square root by
-       C_TRT_FAST = 5 };   // v_rcp_f32 / v_sqrt_f32 (1 ulp; fp64: v_rcp_f64 / v_rsq_f64 + Newton) instead of the IEEE sequences
-constexpr bool coll_is_mrt(int c) { return c == C_MRT || c == C_MRT_FAST; }
-constexpr bool coll_is_fast(int c) { return c >= C_MRT_FAST; }
+       C_TRT_FAST = 5,     // v_rcp_f32 / v_sqrt_f32 (1 ulp; fp64: v_rcp_f64 / v_rsq_f64 + Newton) instead of the IEEE sequences
+       // lbm_params.arith = LBM_ARITH_PROMOTED (fp32 only): the strict operators, but the sub-expressions that MRT_GPU.py's CUDA text
+       // evaluates in double -- its double literals in float expressions, C's usual arithmetic conversions (MRT_GPU.py:385, 410,
+       // 638-642, 652) -- are evaluated in double and rounded to float once, as the CPU oracles' promote = True
+       C_SRT_PROM = 6, C_TRT_PROM = 7, C_MRT_PROM = 8 };
+constexpr bool coll_is_mrt(int c) { return c == C_MRT || c == C_MRT_FAST || c == C_MRT_PROM; }
+constexpr bool coll_is_fast(int c) { return c == C_MRT_FAST || c == C_SRT_FAST || c == C_TRT_FAST; }
+constexpr bool coll_is_prom(int c) { return c == C_SRT_PROM || c == C_TRT_PROM || c == C_MRT_PROM; }
 
 template <typename R>
 struct Relax {  // a2: MRT_GPU.py:63-93
@@ -109,10 +114,32 @@ template <bool FAST> __device__ __forceinline__ f32x2 sqrt_(f32x2 a) {
     return FAST ? f32x2{__builtin_amdgcn_sqrtf(a.x), __builtin_amdgcn_sqrtf(a.y)} : f32x2{sqrtf(a.x), sqrtf(a.y)};
 }
 
-template <typename T>
+// Promoted arithmetic works on one fp32 value at a time (packed math has no double lanes): f applied to each lane of f32x2 arguments
+template <typename F> __device__ __forceinline__ float lanes(F f, float a, float b) { return f(a, b); }
+template <typename F> __device__ __forceinline__ f32x2 lanes(F f, f32x2 a, f32x2 b) { return f32x2{f(a.x, b.x), f(a.y, b.y)}; }
+template <typename F> __device__ __forceinline__ float lanes(F f, float a, float b, float c) { return f(a, b, c); }
+template <typename F> __device__ __forceinline__ f32x2 lanes(F f, f32x2 a, f32x2 b, f32x2 c) { return f32x2{f(a.x, b.x, c.x), f(a.y, b.y, c.y)}; }
+
+// promoted equilibrium (MRT_GPU.py:410,652 `rho_l*t_g[k]*(1. + 3.0*cu + 9*0.5*cu*cu - 3.0*0.5*usqr)`): rt = rho t_k
+// is float * float, the bracket and its product with rt are double, one rounding at the store
+__device__ __forceinline__ float feq_prom(float rt, float cu, float usqr) {
+    const double c = (double)cu;
+    return (float)((double)rt * (((1. + 3.0 * c) + (4.5 * c) * c) - 1.5 * (double)usqr));
+}
+__device__ __forceinline__ f32x2 feq_prom(f32x2 rt, f32x2 cu, f32x2 usqr) {
+    return f32x2{feq_prom(rt.x, cu.x, usqr.x), feq_prom(rt.y, cu.y, usqr.y)};
+}
+
+// PROM (fp32 only): the promoted form above
+template <typename T, bool PROM = false>
 __device__ __forceinline__ void equ(T rho, T ux, T uy, T (&feq)[Q]) {
     typedef typename ScalarOf<T>::type S;
     const T usqr = ux * ux + uy * uy;
+    if constexpr (PROM) {
+#pragma unroll
+        for (int k = 0; k < Q; ++k) feq[k] = feq_prom(rho * weight<S>(k), cu_of<T>(k, ux, uy), usqr);
+        return;
+    }
     const T c = (S)1.5 * usqr;
 #pragma unroll
     for (int k = 0; k < Q; ++k) {
@@ -149,10 +176,10 @@ __device__ __forceinline__ void collide(const T (&f)[Q], T rho, const T (&feq)[Q
                                         const Relax<typename ScalarOf<T>::type>& w, T w_nu, T (&out)[Q]) {
     // w_nu: the viscous rate of each cell (w.w_nu, or the Smagorinsky value); the other rates are lattice-wide scalars
     typedef typename ScalarOf<T>::type R;
-    if (COLL == C_SRT || COLL == C_SRT_FAST) {
+    if (COLL == C_SRT || COLL == C_SRT_FAST || COLL == C_SRT_PROM) {
 #pragma unroll
         for (int k = 0; k < Q; ++k) out[k] = f[k] - w_nu * (f[k] - feq[k]);
-    } else if (COLL == C_TRT || COLL == C_TRT_FAST) {
+    } else if (COLL == C_TRT || COLL == C_TRT_FAST || COLL == C_TRT_PROM) {
         T fp[Q], fm[Q], ep[Q], em[Q];
         constexpr int pa[4] = {2, 5, 6, 1}, pb[4] = {4, 7, 8, 3};
 #pragma unroll
@@ -229,6 +256,15 @@ __device__ __forceinline__ void collide(const T (&f)[Q], T rho, const T (&feq)[Q
         meq[6] = -jy + (R)3.0 * ((jy * jy) * jy);
         meq[7] = jx * jx - jy * jy;
         meq[8] = jx * jy;
+        if constexpr (COLL == C_MRT_PROM) {
+            // MRT_GPU.py:638-642: the literals -2.0, 3.0, 9.0 make these four sums double, one rounding each;
+            // the products of jx, jy among themselves stay float (and the strict form's multiply-add for meq[1] is not used here)
+            const T s = jx * jx + jy * jy, p4 = ((jx * jx) * jy) * jy, x3 = (jx * jx) * jx, y3 = (jy * jy) * jy;
+            meq[1] = lanes([](float r, float a) { return (float)(-2.0 * (double)r + 3.0 * (double)a); }, rho, s);
+            meq[2] = lanes([](float a, float r, float b) { return (float)((-3.0 * (double)a + (double)r) + 9.0 * (double)b); }, s, rho, p4);
+            meq[4] = lanes([](float j, float a) { return (float)((double)(-j) + 3.0 * (double)a); }, jx, x3);
+            meq[6] = lanes([](float j, float a) { return (float)((double)(-j) + 3.0 * (double)a); }, jy, y3);
+        }
         // The reference relaxes all nine moments, three of them with rate 0 (MRT.py:141, MRT_GPU.py:650: m[k] - 0 * (m[k] - meq[k]) for the
         // density and the two momenta).  That is m[k] itself, bit for bit, for every finite input: 0 * x = +-0 and m - (+-0) = m unless m is
         // a zero of the other sign -- and there meq[k] = m[k] (k = 3, 5: x - x = +0, so the product is +0 and -0 - (+0) = -0 stays), while
@@ -321,7 +357,7 @@ __device__ __forceinline__ void equ_collide(const T (&g)[Q], T rho, T ux, T uy, 
         if (TURB) q2 = rho * (ux * uy);
     } else {
         T fe[Q];
-        if (!coll_is_mrt(COLL) || TURB) equ<T>(rho, ux, uy, fe);     // (the plain MRT operator needs neither u nor feq: MRT_GPU.py:633-648)
+        if (!coll_is_mrt(COLL) || TURB) equ<T, coll_is_prom(COLL)>(rho, ux, uy, fe);     // (the plain MRT operator needs neither u nor feq: MRT_GPU.py:633-648)
         collide<T, COLL>(g, rho, fe, w, w_nu, out);
         if (TURB) q2 = diag_flux<T>(fe);
     }
@@ -332,17 +368,25 @@ __device__ __forceinline__ double real_abs(double x) { return fabs(x); }
 __device__ __forceinline__ f32x2 real_abs(f32x2 x) { return f32x2{fabsf(x.x), fabsf(x.y)}; }
 
 // T: scalar real or f32x2; the result is the per-cell relaxation rate (a T, not a scalar)
-template <typename T, bool FAST = false>
+template <typename T, bool FAST = false, bool PROM = false>
 __device__ __forceinline__ T smagorinsky_tau(const T (&f)[Q], T qeq_prev, T rho_prev, typename ScalarOf<T>::type omega) {   // taus_g, MRT_GPU.py:385-387
     typedef typename ScalarOf<T>::type R;
     const R tau0 = (R)1.0 / omega;
     const T q = diag_flux<T>(f) - qeq_prev;
+    if constexpr (PROM) {
+        // MRT_GPU.py:385: tau*tau is float * float, Cs2 the float 0.025f, abs(float) float; the rest is double
+        // (18*1.4142 is a double constant) -- IEEE double square root and division -- and rounded to float once
+        const R tt = tau0 * tau0;
+        return lanes([tau0, tt](float qq, float rp) {
+            return (float)(0.5 * ((double)tau0 + sqrt((double)tt + (((18 * 1.4142) * (double)0.025f) * (double)fabsf(qq)) / (double)rp)));
+        }, q, rho_prev);
+    }
     return (R)0.5 * (tau0 + sqrt_<FAST>(tau0 * tau0 + div_<FAST>(((R)(18 * 1.4142) * (R)0.025) * real_abs(q), rho_prev)));
 }
-template <typename T, bool FAST = false>
+template <typename T, bool FAST = false, bool PROM = false>
 __device__ __forceinline__ T smagorinsky_omega(const T (&f)[Q], T qeq_prev, T rho_prev, typename ScalarOf<T>::type omega) {
     typedef typename ScalarOf<T>::type R;
-    return div_<FAST>(T((R)1.0), smagorinsky_tau<T, FAST>(f, qeq_prev, rho_prev, omega));
+    return div_<FAST>(T((R)1.0), smagorinsky_tau<T, FAST, PROM>(f, qeq_prev, rho_prev, omega));
 }
 
 // a8: wall rules on the populations of ONE perimeter cell, given the equilibrium of the
@@ -422,8 +466,8 @@ __device__ __forceinline__ auto wall_rho_at(const A& a, const Geo& g, int x, int
 
 // Gather the post-stream, post-wall-rule populations of cell (x, y) from a lattice that
 // holds post-collision values (+ kept slots + parked wall densities); raw != 0: the lattice
-// holds plain populations (state just set by the host), nothing to stream.
-template <typename R, int SEM, typename AS>
+// holds plain populations (state just set by the host), nothing to stream.  PROM: the wall rules' equilibrium in the promoted form.
+template <typename R, int SEM, typename AS, bool PROM = false>
 __device__ __forceinline__ void gather_a(const R* __restrict__ src, const AS& as, const Geo& geo, int raw, R uLB, int x, int y, R (&g)[Q]) {
     const int gy = geo.y0 + y;
     if (raw) {
@@ -436,13 +480,13 @@ __device__ __forceinline__ void gather_a(const R* __restrict__ src, const AS& as
     if (x == 0 || x == geo.nx - 1 || gy == 0 || gy == geo.NY - 1) {
         const R rho_w = src[wall_rho_at(as, geo, x, y, gy)];
         R fe[Q];
-        equ<R>(rho_w, gy == 0 ? uLB : (R)0, (R)0, fe);
+        equ<R, PROM>(rho_w, gy == 0 ? uLB : (R)0, (R)0, fe);
         wall_rules<R, SEM>(g, fe, x, gy, geo.nx, geo.NY);
     }
 }
-template <typename R, int SEM>
+template <typename R, int SEM, bool PROM = false>
 __device__ __forceinline__ void gather(const R* __restrict__ src, const Geo& geo, int raw, R uLB, int x, int y, R (&g)[Q]) {
-    gather_a<R, SEM, Geo>(src, geo, geo, raw, uLB, x, y, g);
+    gather_a<R, SEM, Geo, PROM>(src, geo, geo, raw, uLB, x, y, g);
 }
 
 // One fused update of cell (x, y): gather -> (kept slots) -> moments -> collide -> store.
@@ -452,7 +496,7 @@ __device__ __forceinline__ void update_cell_a(const R* __restrict__ src, const A
                                               const Relax<R>& w0, int raw, int x, int y) {
     const int X = geo.nx, Y = geo.NY, gy = geo.y0 + y;
     R g[Q];
-    gather_a<R, SEM, AS>(src, as, geo, raw, w0.uLB, x, y, g);
+    gather_a<R, SEM, AS, coll_is_prom(COLL)>(src, as, geo, raw, w0.uLB, x, y, g);
     // kept slots: a slot outside its streaming window keeps its value; park it where the
     // next pull of this cell will look for it.
     const bool near_edge = (x <= 0) || (x >= X - 2) || (gy <= 0) || (gy >= Y - 2);
@@ -466,7 +510,7 @@ __device__ __forceinline__ void update_cell_a(const R* __restrict__ src, const A
     const auto me_s = as.at(x, y);
     const Relax<R>& w = w0;
     R w_nu = w0.w_nu;
-    if (TURB) w_nu = smagorinsky_omega<R, coll_is_fast(COLL)>(g, src[K_QEQ * as.plane + me_s], src[K_RHO * as.plane + me_s], w0.w_nu);
+    if (TURB) w_nu = smagorinsky_omega<R, coll_is_fast(COLL), coll_is_prom(COLL)>(g, src[K_QEQ * as.plane + me_s], src[K_RHO * as.plane + me_s], w0.w_nu);
     macros<R, coll_is_fast(COLL)>(g, x, gy, X, Y, w.uLB, rho, ux, uy);
     equ_collide<R, COLL, TURB>(g, rho, ux, uy, w, w_nu, out, q2);
     if (TURB) {
@@ -555,7 +599,7 @@ __device__ __forceinline__ void update_vec(const R* __restrict__ src, R* __restr
             if (right) { g[3] = (R)0 + g[1]; g[6] = (R)0 + g[8]; g[7] = (R)0 + g[5]; }
         }
         R w_nu = w0.w_nu;
-        if (TURB) w_nu = smagorinsky_omega<R, coll_is_fast(COLL)>(g, hq[c], hr[c], w0.w_nu);
+        if (TURB) w_nu = smagorinsky_omega<R, coll_is_fast(COLL), coll_is_prom(COLL)>(g, hq[c], hr[c], w0.w_nu);
         R rho = ((((((((g[0] + g[1]) + g[2]) + g[3]) + g[4]) + g[5]) + g[6]) + g[7]) + g[8]);
         R ux = (R)0, uy = (R)0;
         if (!coll_is_mrt(COLL) || TURB) {   // the plain MRT operator needs neither u nor feq (MRT_GPU.py:633-648)
@@ -608,7 +652,7 @@ __device__ __forceinline__ void collide_vec(const typename VecT<R, V>::type (&in
 #pragma unroll
             for (int k = 0; k < Q; ++k) g[k] = p == 0 ? in[k].xy : in[k].zw;
             f32x2 w_nu = (f32x2)(w0.w_nu);
-            if (TURB) w_nu = smagorinsky_omega<f32x2, coll_is_fast(COLL)>(g, p == 0 ? hq.xy : hq.zw, p == 0 ? hr.xy : hr.zw, w0.w_nu);
+            if (TURB) w_nu = smagorinsky_omega<f32x2, coll_is_fast(COLL), coll_is_prom(COLL)>(g, p == 0 ? hq.xy : hq.zw, p == 0 ? hr.xy : hr.zw, w0.w_nu);
             f32x2 rho = ((((((((g[0] + g[1]) + g[2]) + g[3]) + g[4]) + g[5]) + g[6]) + g[7]) + g[8]);
             if (kind == 1) rho = ((g[0] + g[1]) + g[3]) + 2.f * ((g[2] + g[5]) + g[6]);
             f32x2 ux = f32x2(0.f), uy = f32x2(0.f);
@@ -643,7 +687,7 @@ __device__ __forceinline__ void collide_vec(const typename VecT<R, V>::type (&in
 #pragma unroll
             for (int k = 0; k < Q; ++k) g[k] = in[k][c];
             R w_nu = w0.w_nu;
-            if (TURB) w_nu = smagorinsky_omega<R, coll_is_fast(COLL)>(g, hq[c], hr[c], w0.w_nu);
+            if (TURB) w_nu = smagorinsky_omega<R, coll_is_fast(COLL), coll_is_prom(COLL)>(g, hq[c], hr[c], w0.w_nu);
             R rho = ((((((((g[0] + g[1]) + g[2]) + g[3]) + g[4]) + g[5]) + g[6]) + g[7]) + g[8]);
             if (kind == 1) rho = ((g[0] + g[1]) + g[3]) + (R)2. * ((g[2] + g[5]) + g[6]);
             R ux = (R)0, uy = (R)0;

@@ -98,11 +98,19 @@ int stage_to_host(lbm_ctx* c, const void* stage, void* host, int host_dtype, int
 // grid of the host-layout <-> lattice kernels: tiles of trx<R>() columns x 32 rows
 template <typename R>
 dim3 grid_tiles(const lbm_ctx* c) { return dim3((c->geo.nx + trx<R>() - 1) / trx<R>(), (c->geo.ny + 31) / 32, c->batch); }
+// arith = promoted in fp32: the k_*_prom twins of the kernels that form an equilibrium outside the collision (fp64 promoted = strict)
+inline bool promoted_f32(const lbm_ctx* c) { return c->p.dtype == LBM_F32 && c->p.arith == LBM_ARITH_PROMOTED; }
 
 template <typename R>
 int export_fin_t(lbm_ctx* c) {
     const dim3 g = grid_tiles<R>(c);
     const R* src = (const R*)c->lat[c->cur];
+    if constexpr (std::is_same<R, float>::value)
+        if (promoted_f32(c)) {
+            hipLaunchKernelGGL((k_export_fin_prom<R>), g, dim3(BLK), 0, c->s_compute, src, c->geo, c->raw[c->cur], (R)c->p.uLB, (R*)c->stage, c->bstride);
+            HIP_TRY(c, hipGetLastError());
+            return LBM_OK;
+        }
     if (c->p.semantics == LBM_SEM_MRT_PY)
         hipLaunchKernelGGL((k_export_fin<R, SEM_PY>), g, dim3(BLK), 0, c->s_compute, src, c->geo, c->raw[c->cur], (R)c->p.uLB, (R*)c->stage, c->bstride);
     else
@@ -120,6 +128,12 @@ int export_macro_t(lbm_ctx* c) {
     int rc = prev_lattice(c, &which);
     if (rc) return rc;
     const R* src = (const R*)c->lat[which];
+    if constexpr (std::is_same<R, float>::value)
+        if (promoted_f32(c)) {
+            hipLaunchKernelGGL((k_export_macro_prom<R>), g, dim3(BLK), 0, c->s_compute, src, c->geo, c->raw[which], (R)c->p.uLB, (R*)c->stage, c->bstride);
+            HIP_TRY(c, hipGetLastError());
+            return LBM_OK;
+        }
     if (c->p.semantics == LBM_SEM_MRT_PY)
         hipLaunchKernelGGL((k_export_macro<R, SEM_PY>), g, dim3(BLK), 0, c->s_compute, src, c->geo, c->raw[which], (R)c->p.uLB, (R*)c->stage, c->bstride);
     else
@@ -134,6 +148,12 @@ int export_tau_t(lbm_ctx* c) {
     int rc = prev_lattice(c, &which);
     if (rc) return rc;
     const R* src = (const R*)c->lat[which];
+    if constexpr (std::is_same<R, float>::value)
+        if (promoted_f32(c)) {
+            hipLaunchKernelGGL((k_export_tau_prom<R>), grid_tiles<R>(c), dim3(BLK), 0, c->s_compute, src, c->geo, c->raw[which], relax_of<R>(c->p), batch_of<R>(c), c->p.turb, (R*)c->stage);
+            HIP_TRY(c, hipGetLastError());
+            return LBM_OK;
+        }
     if (c->p.arith == LBM_ARITH_FAST)
         hipLaunchKernelGGL((k_export_tau<R, true>), grid_tiles<R>(c), dim3(BLK), 0, c->s_compute, src, c->geo, c->raw[which], relax_of<R>(c->p), batch_of<R>(c), c->p.turb, (R*)c->stage);
     else
@@ -151,6 +171,12 @@ int reduce_u_t(lbm_ctx* c) {
     if (rc) return rc;
     const R* src = (const R*)c->lat[which];
     const dim3 g(RED_BLOCKS, 1, c->batch);
+    if constexpr (std::is_same<R, float>::value)
+        if (promoted_f32(c)) {
+            hipLaunchKernelGGL((k_reduce_u_prom<R>), g, dim3(BLK), 0, c->s_compute, src, c->geo, c->raw[which], (R)c->p.uLB, c->bstride, c->red_dev);
+            HIP_TRY(c, hipGetLastError());
+            return LBM_OK;
+        }
     if (c->p.semantics == LBM_SEM_MRT_PY)
         hipLaunchKernelGGL((k_reduce_u<R, SEM_PY>), g, dim3(BLK), 0, c->s_compute, src, c->geo, c->raw[which], (R)c->p.uLB, c->bstride, c->red_dev);
     else
@@ -260,7 +286,9 @@ int lbm_init_equilibrium(lbm_ctx* c) {
     if (rc) return rc;
     c->cur = 0; c->raw[0] = 1; c->raw[1] = 1; c->nsteps = 0; c->lag = 0; c->lag_valid = false; c->thin_valid = false;
     const dim3 g = grid_rows(c, c->geo.ny);
-    if (c->p.dtype == LBM_F32)
+    if (promoted_f32(c))
+        hipLaunchKernelGGL((k_init_prom<float>), g, dim3(BLK), 0, c->s_compute, (float*)c->lat[0], c->geo, (float)c->p.uLB, c->p.turb, c->bstride);
+    else if (c->p.dtype == LBM_F32)
         hipLaunchKernelGGL((k_init<float>), g, dim3(BLK), 0, c->s_compute, (float*)c->lat[0], c->geo, (float)c->p.uLB, c->p.turb, c->bstride);
     else
         hipLaunchKernelGGL((k_init<double>), g, dim3(BLK), 0, c->s_compute, (double*)c->lat[0], c->geo, (double)c->p.uLB, c->p.turb, c->bstride);
@@ -278,7 +306,9 @@ int lbm_set_state(lbm_ctx* c, const void* fin_host, int host_dtype) {
     rc = host_to_stage(c, fin_host, host_dtype, Q * c->batch);   // [B][9][nx][ny] is B * 9 planes
     if (rc) return rc;
     c->cur = 0; c->raw[0] = 1; c->raw[1] = 1; c->nsteps = 0; c->lag = 0; c->lag_valid = false; c->thin_valid = false;
-    if (c->p.dtype == LBM_F32)
+    if (promoted_f32(c))
+        hipLaunchKernelGGL((k_import_prom<float>), grid_tiles<float>(c), dim3(BLK), 0, c->s_compute, (const float*)c->stage, (float*)c->lat[0], c->geo, (float)c->p.uLB, c->p.turb, c->bstride);
+    else if (c->p.dtype == LBM_F32)
         hipLaunchKernelGGL((k_import<float>), grid_tiles<float>(c), dim3(BLK), 0, c->s_compute, (const float*)c->stage, (float*)c->lat[0], c->geo, (float)c->p.uLB, c->p.turb, c->bstride);
     else
         hipLaunchKernelGGL((k_import<double>), grid_tiles<double>(c), dim3(BLK), 0, c->s_compute, (const double*)c->stage, (double*)c->lat[0], c->geo, (double)c->p.uLB, c->p.turb, c->bstride);

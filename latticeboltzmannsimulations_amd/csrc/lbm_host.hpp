@@ -171,29 +171,41 @@ struct Variant {
     static constexpr bool TURB = TURB_;
 };
 
+// arith = promoted: fp32 takes the promoted operators, fp64 the strict ones (the promotion's casts are no-ops there).
 template <typename F>
 void dispatch(const lbm_params& p, F&& f) {
     auto by_sem = [&](auto real, auto coll) {
         using R = decltype(real);
         constexpr int C = decltype(coll)::value;
         constexpr int CS = C == C_MRT_FAST ? C_MRT : (C == C_SRT_FAST ? C_SRT : (C == C_TRT_FAST ? C_TRT : C));
-        if (p.semantics == LBM_SEM_MRT_PY) f(Variant<R, CS, SEM_PY, false>{});   // (arith = fast: MRT_GPU semantics only)
-        else if (p.turb) f(Variant<R, C, SEM_GPU, true>{});
-        else f(Variant<R, C, SEM_GPU, false>{});
+        if constexpr (coll_is_prom(C)) {   // (MRT_GPU semantics only: validate_params)
+            if (p.turb) f(Variant<R, C, SEM_GPU, true>{});
+            else f(Variant<R, C, SEM_GPU, false>{});
+        } else {
+            if (p.semantics == LBM_SEM_MRT_PY) f(Variant<R, CS, SEM_PY, false>{});   // (arith = fast: MRT_GPU semantics only)
+            else if (p.turb) f(Variant<R, C, SEM_GPU, true>{});
+            else f(Variant<R, C, SEM_GPU, false>{});
+        }
+    };
+    auto pick = [&](auto real, auto strict, auto fast, auto prom) {
+        if (p.arith == LBM_ARITH_FAST) by_sem(real, fast);
+        else if constexpr (std::is_same<decltype(real), float>::value) {
+            if (p.arith == LBM_ARITH_PROMOTED) by_sem(real, prom);
+            else by_sem(real, strict);
+        } else {
+            by_sem(real, strict);
+        }
     };
     auto by_coll = [&](auto real) {
         switch (p.collision) {
             case LBM_SRT:
-                if (p.arith == LBM_ARITH_FAST) by_sem(real, std::integral_constant<int, C_SRT_FAST>{});
-                else by_sem(real, std::integral_constant<int, C_SRT>{});
+                pick(real, std::integral_constant<int, C_SRT>{}, std::integral_constant<int, C_SRT_FAST>{}, std::integral_constant<int, C_SRT_PROM>{});
                 break;
             case LBM_TRT:
-                if (p.arith == LBM_ARITH_FAST) by_sem(real, std::integral_constant<int, C_TRT_FAST>{});
-                else by_sem(real, std::integral_constant<int, C_TRT>{});
+                pick(real, std::integral_constant<int, C_TRT>{}, std::integral_constant<int, C_TRT_FAST>{}, std::integral_constant<int, C_TRT_PROM>{});
                 break;
             default:
-                if (p.arith == LBM_ARITH_FAST) by_sem(real, std::integral_constant<int, C_MRT_FAST>{});
-                else by_sem(real, std::integral_constant<int, C_MRT>{});
+                pick(real, std::integral_constant<int, C_MRT>{}, std::integral_constant<int, C_MRT_FAST>{}, std::integral_constant<int, C_MRT_PROM>{});
                 break;
         }
     };

@@ -13,6 +13,10 @@
     M(R, C_MRT_FAST, SEM_GPU, true) M(R, C_SRT_FAST, SEM_GPU, true) M(R, C_TRT_FAST, SEM_GPU, true)
 // ... MRT.py semantics: the three strict ones
 #define LBM_PY_VARIANTS(M, R) M(R, C_SRT, SEM_PY, false) M(R, C_TRT, SEM_PY, false) M(R, C_MRT, SEM_PY, false)
+// ... arith = promoted (float only: fp64 runs the strict variants), MRT_GPU.py semantics: the three promoted operators, with and without the closure
+#define LBM_PROM_VARIANTS(M, R)                                                                                                 \
+    M(R, C_SRT_PROM, SEM_GPU, false) M(R, C_TRT_PROM, SEM_GPU, false) M(R, C_MRT_PROM, SEM_GPU, false)                          \
+    M(R, C_SRT_PROM, SEM_GPU, true) M(R, C_TRT_PROM, SEM_GPU, true) M(R, C_MRT_PROM, SEM_GPU, true)
 
 // one instantiation of each kernel (LBM_X: `extern`, or nothing in the unit that compiles it)
 #define LBM_TILE_ONE(R, COLL, SEM, S, TURB)                                                                                     \
@@ -37,6 +41,9 @@
 #define LBM_INST_STREAMW(R) LBM_GPU_VARIANTS(LBM_STREAMW_ONE, R)
 #define LBM_INST_STREAMS(R) LBM_GPU_VARIANTS(LBM_STREAMS_ONE, R)
 #define LBM_INST_STREAMP(R) LBM_GPU_VARIANTS(LBM_STREAMP_ONE, R)
+// the promoted operators in every family but k_stream_pairs (plan_kernel refuses stream_pairs with arith = promoted), in two units of their own
+#define LBM_INST_TILES_PROM(R) LBM_PROM_VARIANTS(LBM_TILE_S, R)
+#define LBM_INST_STREAM_PROM(R) LBM_PROM_VARIANTS(LBM_STREAM_ONE, R) LBM_PROM_VARIANTS(LBM_STREAMW_ONE, R) LBM_PROM_VARIANTS(LBM_STREAMS_ONE, R)
 
 #ifdef LBM_INST
 #define LBM_X
@@ -48,4 +55,5 @@ LBM_INST_STREAM(float) LBM_INST_STREAM(double)
 LBM_INST_STREAMW(float) LBM_INST_STREAMW(double)
 LBM_INST_STREAMS(float) LBM_INST_STREAMS(double)
 LBM_INST_STREAMP(float) LBM_INST_STREAMP(double)
+LBM_INST_TILES_PROM(float) LBM_INST_STREAM_PROM(float)
 #endif

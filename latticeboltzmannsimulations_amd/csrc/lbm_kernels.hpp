@@ -328,7 +328,7 @@ __global__ __launch_bounds__(BLK) void k_push_bc(const R* __restrict__ fin_old, 
 #pragma unroll
         for (int k = 0; k < Q; ++k) f0[k] = fin_old[k * geo.plane + me];
         macros<R, coll_is_fast(COLL)>(f0, x, gy, X, Y, uLB, rho, ux, uy);
-        equ<R>(rho, ux, uy, fe);
+        equ<R, coll_is_prom(COLL)>(rho, ux, uy, fe);
         wall_rules<R, SEM>(g, fe, x, gy, X, Y);
 #pragma unroll
         for (int k = 0; k < Q; ++k) ftemp[k * geo.plane + me] = g[k];
@@ -337,21 +337,30 @@ __global__ __launch_bounds__(BLK) void k_push_bc(const R* __restrict__ fin_old, 
     for (int k = 0; k < Q; ++k) fin_new[k * geo.plane + me] = g[k];
 }
 
-// init: raw populations = equ(rho = 1, u = (uLB on the global lid row, 0))  (MRT.py:260-268)
-template <typename R>
-__global__ __launch_bounds__(BLK) void k_init(R* __restrict__ lat, Geo geo, R uLB, int turb, long long bstride) {
+// init: raw populations = equ(rho = 1, u = (uLB on the global lid row, 0))  (MRT.py:260-268); PROM: the promoted equilibrium (k_init_prom,
+// arith = promoted; the host-layout kernels below have such twins too, at the end of this file)
+template <typename R, bool PROM>
+__device__ __forceinline__ void init_body(R* __restrict__ lat, Geo geo, R uLB, int turb, long long bstride) {
     const int x = blockIdx.x * BLK + threadIdx.x;
     const int y = blockIdx.y;
     if (x >= geo.nx) return;
     lat += blockIdx.z * bstride;
     R fe[Q];
-    equ<R>((R)1, (geo.y0 + y) == 0 ? uLB : (R)0, (R)0, fe);
+    equ<R, PROM>((R)1, (geo.y0 + y) == 0 ? uLB : (R)0, (R)0, fe);
 #pragma unroll
     for (int k = 0; k < Q; ++k) lat[k * geo.plane + geo.at(x, y)] = fe[k];
     if (turb) {   // Smagorinsky history: feq_g starts as a copy of fin, rho_g as 1 (MRT_GPU.py:324-326)
         lat[K_QEQ * geo.plane + geo.at(x, y)] = diag_flux<R>(fe);
         lat[K_RHO * geo.plane + geo.at(x, y)] = (R)1;
     }
+}
+template <typename R>
+__global__ __launch_bounds__(BLK) void k_init(R* __restrict__ lat, Geo geo, R uLB, int turb, long long bstride) {
+    init_body<R, false>(lat, geo, uLB, turb, bstride);
+}
+template <typename R>
+__global__ __launch_bounds__(BLK) void k_init_prom(R* __restrict__ lat, Geo geo, R uLB, int turb, long long bstride) {
+    init_body<R, true>(lat, geo, uLB, turb, bstride);
 }
 
 // ---- host layout <-> lattice ---------------------------------------------------------------------------------------------
@@ -512,3 +521,149 @@ __global__ __launch_bounds__(BLK) void k_reduce_u(const R* __restrict__ src, Geo
     if (threadIdx.x == 0) partial[(size_t)blockIdx.z * gridDim.x + blockIdx.x] = red[0];
 }
 
+// ---- the twins of the kernels above for arith = promoted (fp32, MRT_GPU semantics): their equilibria -- the history of an uploaded state,
+// the lid's wall rule in the gather -- and the Smagorinsky tau take the promoted form (equ<R, true>, gather<R, SEM_GPU, true>,
+// smagorinsky_tau<R, false, true>).  Written out again rather than shared with the kernels above as device functions: inlined from a
+// helper, those kernels' code changes (operand order, scheduling), and they are meant to stay exactly as they are.
+template <typename R>
+__global__ __launch_bounds__(BLK) void k_import_prom(const R* __restrict__ stage, R* __restrict__ lat, Geo geo, R uLB, int turb, long long bstride) {
+    constexpr int TRX = trx<R>(), RY = BLK / TRX;
+    __shared__ R t[Q][TRX][33];
+    const long long n = (long long)geo.nx * geo.ny;
+    lat += blockIdx.z * bstride;
+    stage += blockIdx.z * (Q * n);
+    const int x0 = blockIdx.x * TRX, y0 = blockIdx.y * 32;
+    {
+        const int yy = threadIdx.x & 31, xb = threadIdx.x >> 5;
+        for (int xx = xb; xx < TRX; xx += BLK / 32)
+            if (x0 + xx < geo.nx && y0 + yy < geo.ny) {
+#pragma unroll
+                for (int k = 0; k < Q; ++k) t[k][xx][yy] = stage[k * n + (long long)(x0 + xx) * geo.ny + y0 + yy];
+            }
+    }
+    __syncthreads();
+    const int tx = threadIdx.x % TRX, x = x0 + tx;
+    for (int ty = threadIdx.x / TRX; ty < 32; ty += RY) {
+        const int y = y0 + ty;
+        if (x >= geo.nx || y >= geo.ny) continue;
+        R g[Q];
+#pragma unroll
+        for (int k = 0; k < Q; ++k) {
+            g[k] = t[k][tx][ty];
+            lat[k * geo.plane + geo.at(x, y)] = g[k];
+        }
+        if (turb) {
+            R rho, ux, uy, fe[Q];
+            macros<R>(g, x, geo.y0 + y, geo.nx, geo.NY, uLB, rho, ux, uy);
+            equ<R, true>(rho, ux, uy, fe);
+            lat[K_QEQ * geo.plane + geo.at(x, y)] = diag_flux<R>(fe);
+            lat[K_RHO * geo.plane + geo.at(x, y)] = rho;
+        }
+    }
+}
+
+template <typename R>
+__global__ __launch_bounds__(BLK) void k_export_fin_prom(const R* __restrict__ src, Geo geo, int raw, R uLB, R* __restrict__ stage, long long bstride) {
+    constexpr int TRX = trx<R>(), RY = BLK / TRX;
+    __shared__ R t[Q][TRX][33];
+    const long long n = (long long)geo.nx * geo.ny;
+    src += blockIdx.z * bstride;
+    stage += blockIdx.z * (Q * n);
+    const int x0 = blockIdx.x * TRX, y0 = blockIdx.y * 32;
+    const int tx = threadIdx.x % TRX, x = x0 + tx;
+    for (int ty = threadIdx.x / TRX; ty < 32; ty += RY) {
+        const int y = y0 + ty;
+        if (x >= geo.nx || y >= geo.ny) continue;
+        R g[Q];
+        gather<R, SEM_GPU, true>(src, geo, raw, uLB, x, y, g);
+#pragma unroll
+        for (int k = 0; k < Q; ++k) t[k][tx][ty] = g[k];
+    }
+    __syncthreads();
+    const int yy = threadIdx.x & 31, xb = threadIdx.x >> 5;
+    for (int xx = xb; xx < TRX; xx += BLK / 32)
+        if (x0 + xx < geo.nx && y0 + yy < geo.ny) {
+#pragma unroll
+            for (int k = 0; k < Q; ++k) stage[k * n + (long long)(x0 + xx) * geo.ny + y0 + yy] = t[k][xx][yy];
+        }
+}
+
+template <typename R>
+__global__ __launch_bounds__(BLK) void k_export_macro_prom(const R* __restrict__ src, Geo geo, int raw, R uLB, R* __restrict__ stage, long long bstride) {
+    constexpr int TRX = trx<R>(), RY = BLK / TRX;
+    __shared__ R t[3][TRX][33];
+    const long long n = (long long)geo.nx * geo.ny;
+    src += blockIdx.z * bstride;
+    stage += blockIdx.z * (3 * n);
+    const int x0 = blockIdx.x * TRX, y0 = blockIdx.y * 32;
+    const int tx = threadIdx.x % TRX, x = x0 + tx;
+    for (int ty = threadIdx.x / TRX; ty < 32; ty += RY) {
+        const int y = y0 + ty;
+        if (x >= geo.nx || y >= geo.ny) continue;
+        R g[Q], rho, ux, uy;
+        gather<R, SEM_GPU, true>(src, geo, raw, uLB, x, y, g);
+        macros<R>(g, x, geo.y0 + y, geo.nx, geo.NY, uLB, rho, ux, uy);
+        t[0][tx][ty] = ux; t[1][tx][ty] = uy; t[2][tx][ty] = rho;
+    }
+    __syncthreads();
+    const int yy = threadIdx.x & 31, xb = threadIdx.x >> 5;
+    for (int xx = xb; xx < TRX; xx += BLK / 32)
+        if (x0 + xx < geo.nx && y0 + yy < geo.ny) {
+            const long long o = (long long)(x0 + xx) * geo.ny + y0 + yy;
+            stage[o] = t[0][xx][yy];
+            stage[n + o] = t[1][xx][yy];
+            stage[2 * n + o] = t[2][xx][yy];
+        }
+}
+
+// (the third mode of k_export_tau, next to <R, FAST>: the promoted tau)
+template <typename R>
+__global__ __launch_bounds__(BLK) void k_export_tau_prom(const R* __restrict__ src, Geo geo, int raw, Relax<R> w, Batch<R> bt, int turb,
+                                                         R* __restrict__ stage) {
+    constexpr int TRX = trx<R>(), RY = BLK / TRX;
+    __shared__ R t[TRX][33];
+    const long long n = (long long)geo.nx * geo.ny;
+    if (bt.w) { src += blockIdx.z * bt.stride; w = bt.w[blockIdx.z]; }
+    stage += blockIdx.z * n;
+    const int x0 = blockIdx.x * TRX, y0 = blockIdx.y * 32;
+    const int tx = threadIdx.x % TRX, x = x0 + tx;
+    for (int ty = threadIdx.x / TRX; ty < 32; ty += RY) {
+        const int y = y0 + ty;
+        if (x >= geo.nx || y >= geo.ny) continue;
+        R tau = (R)1.0 / w.w_nu;
+        if (turb) {
+            R g[Q];
+            gather<R, SEM_GPU, true>(src, geo, raw, w.uLB, x, y, g);
+            const long long me = geo.at(x, y);
+            tau = smagorinsky_tau<R, false, true>(g, src[K_QEQ * geo.plane + me], src[K_RHO * geo.plane + me], w.w_nu);
+        }
+        t[tx][ty] = tau;
+    }
+    __syncthreads();
+    const int yy = threadIdx.x & 31, xb = threadIdx.x >> 5;
+    for (int xx = xb; xx < TRX; xx += BLK / 32)
+        if (x0 + xx < geo.nx && y0 + yy < geo.ny) stage[(long long)(x0 + xx) * geo.ny + y0 + yy] = t[xx][yy];
+}
+
+template <typename R>
+__global__ __launch_bounds__(BLK) void k_reduce_u_prom(const R* __restrict__ src, Geo geo, int raw, R uLB, long long bstride,
+                                                       double* __restrict__ partial) {
+    __shared__ double red[BLK];
+    src += blockIdx.z * bstride;
+    const long long n = (long long)geo.nx * geo.ny;
+    double acc = 0.0;
+    for (long long i = (long long)blockIdx.x * BLK + threadIdx.x; i < n; i += (long long)gridDim.x * BLK) {
+        const int y = (int)(i / geo.nx), x = (int)(i - (long long)y * geo.nx);
+        R g[Q], rho, ux, uy;
+        gather<R, SEM_GPU, true>(src, geo, raw, uLB, x, y, g);
+        macros<R>(g, x, geo.y0 + y, geo.nx, geo.NY, uLB, rho, ux, uy);
+        acc += (double)ux + (double)uy;
+    }
+    red[threadIdx.x] = acc;
+    __syncthreads();
+    for (int s = BLK / 2; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) partial[(size_t)blockIdx.z * gridDim.x + blockIdx.x] = red[0];
+}

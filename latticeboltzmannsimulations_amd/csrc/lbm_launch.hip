@@ -135,7 +135,10 @@ static int launch_walls(lbm_ctx* c, int from, int to, hipStream_t s, int S, int 
                 hipLaunchKernelGGL((k_stream_walls_slab<R, VT::COLL, VT::TURB>), dim3(pl.nstrips * (bands ? (bands & 1) + (bands >> 1) : pl.nsegy)),
                                    dim3(ST_NT), 0, s, src, dst, c->geo, relax_of<R>(c->p), S, pl.nstrips, pl.H, bands ? 0 : xcd, ybeg, yend, bands,
                                    elo, ehi, bands ? c->tb_f : 0);
-            else if (c->kern == Kern::stream_pairs)
+            else if constexpr (coll_is_prom(VT::COLL)) {   // (not compiled for the promoted operators: plan_kernel refuses stream_pairs with them)
+                hipLaunchKernelGGL((k_stream_walls<R, VT::COLL, VT::TURB>), dim3(pl.nstrips * pl.nsegy), dim3(ST_NT), 0, s, src, dst, c->geo,
+                                   relax_of<R>(c->p), S, pl.nstrips, pl.H, xcd);
+            } else if (c->kern == Kern::stream_pairs)
                 hipLaunchKernelGGL((k_stream_pairs<R, VT::COLL, VT::TURB>), dim3(pl.nstrips * pl.nsegy), dim3(64 * pairs_waves(S)), 0, s, src, dst,
                                    c->geo, relax_of<R>(c->p), S, pl.nstrips, pl.H, xcd);
             else

@@ -151,7 +151,13 @@ std::string validate_params(const lbm_params* p) {
         return std::string("kernel = PUSH (the reference's two-launch scheme, for A/B) takes one whole lattice without the closure");
     if (p->layout < LBM_LAYOUT_AUTO || p->layout > LBM_LAYOUT_ROWS) return std::string("bad layout");
     if (p->batch < 0 || p->batch > 65535) return std::string("batch must be 0 .. 65535");
-    if (p->arith != LBM_ARITH_STRICT && p->arith != LBM_ARITH_FAST) return std::string("arith must be LBM_ARITH_STRICT or LBM_ARITH_FAST");
+    if (p->arith != LBM_ARITH_STRICT && p->arith != LBM_ARITH_FAST && p->arith != LBM_ARITH_PROMOTED)
+        return std::string("arith must be LBM_ARITH_STRICT, LBM_ARITH_FAST or LBM_ARITH_PROMOTED");
+    if (p->arith == LBM_ARITH_PROMOTED && p->semantics != LBM_SEM_MRT_GPU)
+        return std::string("arith = promoted exists only with MRT_GPU semantics (promotion is a property of MRT_GPU.py's CUDA text; "
+                           "MRT.py semantics is NumPy fp64)");
+    if (p->arith == LBM_ARITH_PROMOTED && (p->flags & LBM_FLAG_STREAM_PAIRS))
+        return std::string("arith = promoted does not run on the streaming kernel with two rows per wave (LBM_FLAG_STREAM_PAIRS)");
     if (p->batch > 1 && (p->y0 != 0 || p->ny_local != p->ny)) return std::string("a batch of lattices cannot be slab-decomposed");
     if (p->ny_local_min < 0 || p->ny_local_min > p->ny_local) return std::string("ny_local_min must be 0 or the smallest ny_local of all ranks (<= ny_local)");
     if (p->tb_steps != 0 && (p->tb_steps < 2 || p->tb_steps > SP_MAX_S)) return std::string("tb_steps must be 0 (default) or 2 .. " + std::to_string(SP_MAX_S));
@@ -246,6 +252,9 @@ static std::string plan_kernel(lbm_ctx* c, bool device) {
     // operator's 52 B: a dozen registers parked once per BLOCK, outside the level loop -- what costs is a reload inside it).
     // r03, second half: a slab too (its deep halo is complete rows of the same lattice format, side-wall cells included): the edge
     // launch shrinks to the interface bands, the column strips and the lid / bottom row strip of the frame go
+    // arith = promoted, fp32 (hipcc -Rpass-analysis=kernel-resource-usage): k_stream_walls MRT 128 VGPRs + 8 B of scratch per lane, SRT
+    // 128 + 104 B; k_stream_walls_slab MRT 0 B, SRT 92 B -- inside the bounds below, as the strict operators: the same rule, the walls inside
+    // for MRT and SRT without the closure, in the dry run as on the device (fp64 promoted runs the strict variants)
     const int forced = p->flags & (LBM_FLAG_STREAM_WALLS | LBM_FLAG_STREAM_PAIRS);
     const bool walls_ok = c->batch == 1 && p->semantics == LBM_SEM_MRT_GPU && (!slab || !(p->flags & LBM_FLAG_NO_DEEP_HALO));
     bool walls_pay = !p->turb && (p->collision == LBM_MRT || p->collision == LBM_SRT);

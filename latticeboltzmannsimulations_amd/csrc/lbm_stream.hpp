@@ -148,8 +148,9 @@ __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(
 // The wall rules of a wall row, applied to the pulled populations in[] of the lane's V cells before the collision (collide_vec then
 // takes the row's macroscopic overrides: `kind`).  rw: the cells' previous density (lid; out: this level's); wl / wr: the lane's first / last cell is
 // the left / right corner cell of the lattice; kl / kr: that corner's kept slot (in: the value of the step before, out: this step's).
-// Only in[] and a few temporaries are live here (outv is not yet): the wall rows cost the kernel no registers.
-template <typename R, int V>
+// Only in[] and a few temporaries are live here (outv is not yet): the wall rows cost the kernel no registers.  PROM: the lid's
+// equilibrium in the promoted form (feq_prom, one cell at a time).
+template <typename R, int V, bool PROM = false>
 __device__ __forceinline__ void wall_row_rules(typename VecT<R, V>::type (&in)[Q], typename VecT<R, V>::type& rw, bool lid, R uLB, bool wl, bool wr,
                                                R& kl, R& kr) {
     typedef typename VecT<R, V>::type T;
@@ -157,7 +158,18 @@ __device__ __forceinline__ void wall_row_rules(typename VecT<R, V>::type (&in)[Q
         // equilibrium of the cell's previous state: rho parked, u = (uLB, 0) -- the expression of equ<>, one direction at a time
         const T ux = T(uLB), uy = T((R)0);
         const T cq = (R)1.5 * (ux * ux + uy * uy);
-        auto fek = [&](int k) { const T cu = cu_of<T>(k, ux, uy); return (rw * weight<R>(k)) * ((((R)1. + (R)3.0 * cu) + ((R)4.5 * cu) * cu) - cq); };
+        auto fek = [&](int k) {
+            const T cu = cu_of<T>(k, ux, uy);
+            if constexpr (PROM) {
+                const T rt = rw * weight<R>(k), usqr = ux * ux + uy * uy;
+                T fe;
+#pragma unroll
+                for (int c = 0; c < V; ++c) fe[c] = feq_prom(rt[c], cu[c], usqr[c]);
+                return fe;
+            } else {
+                return (rw * weight<R>(k)) * ((((R)1. + (R)3.0 * cu) + ((R)4.5 * cu) * cu) - cq);
+            }
+        };
         if (wl) {   // x == 0 first (MRT_GPU.py:674-677); slot 7 is the kept one
             const R g7 = kl;
             in[1][0] = (fek(1)[0] - fek(3)[0]) + in[3][0];
@@ -369,7 +381,7 @@ __device__ __forceinline__ void stream_segment(const R* __restrict__ src, R* __r
                         kl = st[ROW + lane];
                         kr = st[2 * ROW + lane];
                     }
-                    wall_row_rules<R, V>(in, rw, lid, w.uLB, wl, wr, kl, kr);
+                    wall_row_rules<R, V, coll_is_prom(COLL)>(in, rw, lid, w.uLB, wl, wr, kl, kr);
                     kind = lid ? 1 : 2;
                 } else if (side_strip && (first || narrow)) {
                     // side-wall cells of an ordinary row (MRT_GPU.py:674-682 at rest, update_vec): from level 1 on the rule rides on the lane
@@ -687,7 +699,7 @@ __device__ __forceinline__ void stream_pairs_segment(const R* __restrict__ src, 
                     kl = st[ROW + lane];
                     kr = st[2 * ROW + lane];
                 }
-                wall_row_rules<R, V>(in, rw, lid, w.uLB, wl, wr, kl, kr);
+                wall_row_rules<R, V, coll_is_prom(COLL)>(in, rw, lid, w.uLB, wl, wr, kl, kr);
                 kind = lid ? 1 : 2;
                 if (lid) *reinterpret_cast<T*>(st + lane * V) = rw;
                 st[ROW + lane] = kl;

@@ -114,7 +114,8 @@ def main(argv=None):
     ap.add_argument("--Pinterval", type=int, default=10000)
     ap.add_argument("--maxIt", type=int, default=3000000)
     ap.add_argument("--OutputFolder", default="./output")
-    ap.add_argument("--arith", choices=["strict", "fast"], default="strict", help="fast: agrees with strict to rounding, ~1.3x faster")
+    ap.add_argument("--arith", choices=["strict", "fast", "promoted"], default="strict",
+                    help="fast: agrees with strict to rounding, ~1.3x faster; promoted: MRT_GPU.py's CUDA text arithmetic (fp32)")
     ap.add_argument("--convergence", choices=["host", "device"], default="host",
                     help="device: the convergence test on lbm_mean_u (reduced on the GPU) instead of the downloaded field")
     a = ap.parse_args(argv)

@@ -130,7 +130,7 @@ def run_cavity(maxIt=3000000, Re=10000.0, RT="SRT", turb=1, xsize=32 * 5, ysize=
     say("the value of uLB is ", uLB)
     say("xsize value is ", xsize)
     make = CavitySolver if solver_factory is None else solver_factory
-    extra = {} if arith == "strict" else {"arith": arith}      # 'fast': see CavitySolver (agrees with 'strict' to rounding)
+    extra = {} if arith == "strict" else {"arith": arith}      # 'fast' / 'promoted': see CavitySolver
     solver = make(xsize, ysize, Re, RT=RT, uLB=uLB, semantics=semantics, dtype=dtype, turb=turb, device=device, **extra)
     relax = solver.relax
     say("Re chosen  is ", Re)
@@ -236,7 +236,7 @@ def main(argv=None):
     ap.add_argument("--OutputFolder", default="./output")
     ap.add_argument("--dtype", choices=["float32", "float64"], default="float32")
     ap.add_argument("--semantics", choices=["mrt_gpu", "mrt_py"], default="mrt_gpu")
-    ap.add_argument("--arith", choices=["strict", "fast"], default="strict")
+    ap.add_argument("--arith", choices=["strict", "fast", "promoted"], default="strict")
     ap.add_argument("--convergence", choices=["host", "device"], default="host")
     ap.add_argument("--vtk-correct", action="store_true", help="write .vtr point data (consistent file) instead of the reference's layout")
     a = ap.parse_args(argv)

@@ -13,7 +13,7 @@ _COLL = {"SRT": L.LBM_SRT, "TRT": L.LBM_TRT, "MRT": L.LBM_MRT}
 _SEM = {"mrt_py": L.LBM_SEM_MRT_PY, "mrt_gpu": L.LBM_SEM_MRT_GPU}
 _KERNEL = {"auto": L.LBM_KERNEL_AUTO, "generic": L.LBM_KERNEL_GENERIC, "vec": L.LBM_KERNEL_VEC, "tb": L.LBM_KERNEL_TB,
            "push": L.LBM_KERNEL_PUSH, "stream": L.LBM_KERNEL_STREAM}
-_ARITH = {"strict": L.LBM_ARITH_STRICT, "fast": L.LBM_ARITH_FAST}
+_ARITH = {"strict": L.LBM_ARITH_STRICT, "fast": L.LBM_ARITH_FAST, "promoted": L.LBM_ARITH_PROMOTED}
 _LAYOUT = {"auto": L.LBM_LAYOUT_AUTO, "planes": L.LBM_LAYOUT_PLANES, "rows": L.LBM_LAYOUT_ROWS}
 
 
@@ -70,8 +70,11 @@ class CavitySolver:
                    'tb' (three to five steps per launch through LDS; what 'auto' picks when it applies) |
                    'push' (the reference's two-launch push scheme, for A/B only)
     layout       : device arrays 'planes' [k][y][x], 'rows' [y][k][x], 'auto' (= rows)
-    arith        : 'strict' (default; the reference's operation order, bit-identical to the CPU restatement the tests check against) or 'fast' (MRT operator
-                   in factored form, about half the arithmetic, agrees to rounding)
+    arith        : 'strict' (default; the reference's operation order, bit-identical to the CPU restatement the tests check against), 'fast' (MRT operator
+                   in factored form, about half the arithmetic, agrees to rounding) or 'promoted' (MRT_GPU.py's CUDA text: the strict order, with
+                   the sub-expressions its double literals make double -- equilibrium bracket, MRT m_eq sums, Smagorinsky tau -- evaluated in
+                   double and rounded to float once; fp32 bit-identical to the oracles' promote=True, fp64 the same as 'strict';
+                   semantics='mrt_gpu' only)
     min_rows     : slabs: the smallest ny_local of ALL slabs of the decomposition (lbm_params.ny_local_min) -- the launch plan is
                    derived from it, so that neighbours run the same exchange protocol
     tuning       : A/B switches of the launch plan, none of which changes a result: tb_steps (2..5 steps per launch; 2..8 with kernel='stream'),
@@ -103,6 +106,7 @@ class CavitySolver:
         self.relax = relaxation(self.Re, self.ny, self.uLB, omega_eps, omega_q)
         self.y0, self.ny_local = (0, self.ny) if rows is None else (int(rows[0]), int(rows[1]))
         self.turb = int(turb)
+        self.arith = arith
         p = _params(self.nx, self.ny, self.y0, self.ny_local, self.dtype, RT, semantics, kernel, turb, device, layout, self.batch, arith,
                     min_rows, tuning, self.uLB, self.relax)
         err = ctypes.create_string_buffer(512)
@@ -233,13 +237,15 @@ class CavitySolver:
         u, rho, fin = self.get_fields(want_fin=True)
         path = _npz(path)
         np.savez(path, fin=fin, steps_done=self.steps_done, nx=self.nx, ny=self.ny, Re=self.Re, RT=self.RT, uLB=self.uLB,
-                 semantics=self.semantics, dtype=self.dtype.name, rows=np.array([self.y0, self.ny_local]), turb=self.turb, u=u, rho=rho)
+                 semantics=self.semantics, dtype=self.dtype.name, rows=np.array([self.y0, self.ny_local]), turb=self.turb, u=u, rho=rho,
+                 arith=self.arith)
         return path
 
     def load_checkpoint(self, path, strict=True):
         """Upload the populations of a checkpoint written by save_checkpoint; returns the number of steps the checkpointed
         run had done.  The lattice size must match; with `strict` (default) so must dtype, semantics, collision operator,
-        closure and Reynolds number -- a continuation is bit-identical only then.  The array is the whole lattice, so a slab
+        closure and Reynolds number -- a continuation is bit-identical only then -- and, where either side is 'promoted', the
+        arithmetic (strict and fast states mix as before; a checkpoint without the key counts as strict).  The array is the whole lattice, so a slab
         may restart from a checkpoint of the undivided lattice (each context reads its own rows) but not from another slab's."""
         with np.load(_npz(path), allow_pickle=False) as z:
             if int(z["nx"]) != self.nx or int(z["ny"]) != self.ny:
@@ -252,6 +258,9 @@ class CavitySolver:
                             turb=int(z["turb"]) if "turb" in z else self.turb)
                 want = dict(dtype=self.dtype.name, semantics=self.semantics, RT=self.RT, Re=self.Re, uLB=self.uLB, turb=self.turb)
                 diff = {k: (have[k], want[k]) for k in want if have[k] != want[k]}
+                arith = str(z["arith"]) if "arith" in z else "strict"
+                if "promoted" in (arith, self.arith) and arith != self.arith:
+                    diff["arith"] = (arith, self.arith)
                 if diff:
                     raise ValueError(f"checkpoint was written by a different run (checkpoint, this solver): {diff}")
             self.set_state(np.ascontiguousarray(z["fin"]))
@@ -342,6 +351,8 @@ def _params(nx, ny, y0, ny_local, dtype, RT, semantics, kernel, turb, device, la
     p.kernel, p.turb, p.device = _KERNEL[kernel], int(turb), int(device)
     p.layout = _LAYOUT[layout]
     p.batch = int(batch)
+    if arith not in _ARITH:
+        raise ValueError("arith must be 'strict', 'fast' or 'promoted'")
     p.arith = _ARITH[arith]
     p.ny_local_min = 0 if min_rows is None else int(min_rows)
     p.tb_steps, p.frame_seg, p.flags = _tuning(tuning)

@@ -1,0 +1,210 @@
+"""arith='promoted' on the device: every fp32 state the library exposes -- fin, u, rho, the Smagorinsky history (through the steps
+that follow), get_tau -- is bit-identical to the oracle with promote=True (MRT_GPU.py's CUDA text: its double-literal sub-expressions
+evaluated in double, rounded once), for every operator, with and without the closure, on every kernel and launch plan the library
+can choose.  fp64: the same bits as arith='strict'."""
+import os
+import sys
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from oracle.lbm_ref import CavityOracleC, set_threads, max_threads      # noqa: E402
+from latticeboltzmannsimulations_amd import CavityBatch, CavitySolver  # noqa: E402
+from latticeboltzmannsimulations_amd.slab import LocalSlabs, partition_rows  # noqa: E402
+from latticeboltzmannsimulations_amd.solver import launch_plan  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+OPS = [("SRT", 0), ("SRT", 1), ("TRT", 0), ("TRT", 1), ("MRT", 0), ("MRT", 1)]
+COUNTS = (1, 7, 20, 100)
+
+
+def _oracle(nx, ny, Re, coll, turb):
+    return CavityOracleC(nx, ny, Re, semantics="mrt_gpu", collision=coll, dtype=np.float32, turb=turb, promote=True)
+
+
+def _same(s, o, what):
+    u, rho, fin = s.get_fields(want_fin=True)
+    assert np.array_equal(fin, o.fin), what
+    assert np.array_equal(u, o.u), what
+    assert np.array_equal(rho, o.rho), what
+
+
+def _run(nx, ny, coll, turb, counts=COUNTS, Re=1000.0, **kw):
+    o = _oracle(nx, ny, Re, coll, turb)
+    with CavitySolver(nx, ny, Re, RT=coll, dtype=np.float32, turb=turb, arith="promoted", **kw) as s:
+        done = 0
+        for n in counts:
+            s.step(n - done)
+            o.step(n - done)
+            done = n
+            _same(s, o, (coll, turb, kw, n))
+        return s.describe()
+
+
+@pytest.mark.parametrize("coll,turb", OPS)
+@pytest.mark.parametrize("kernel", ["generic", "vec"])
+def test_single_step_kernels(kernel, coll, turb):
+    _run(68, 52, coll, turb, kernel=kernel)
+
+
+@pytest.mark.parametrize("coll,turb", OPS)
+@pytest.mark.parametrize("tb_steps", [2, 3, 4, 5])
+def test_tile_kernels(tb_steps, coll, turb):
+    d = _run(96, 80, coll, turb, kernel="tb", tuning=dict(tb_steps=tb_steps))
+    assert d["kernel"] == ("k_step2_deep" if tb_steps == 2 else "k_stepS_deep") and d["steps_per_launch"] == tb_steps
+
+
+@pytest.mark.parametrize("coll,turb", OPS)
+@pytest.mark.parametrize("mode", ["frame3", "frame8", "walls"])
+def test_streaming_kernels(mode, coll, turb):
+    # two strips (the second partial) and several row segments; call lengths leave tail units and single steps
+    tune = dict(stream_walls=True) if mode == "walls" else dict(stream_walls=False, tb_steps=3 if mode == "frame3" else 8)
+    d = _run(264, 150, coll, turb, counts=(1, 7, 20, 37), kernel="stream", tuning=tune)
+    assert d["kernel"] == ("k_stream_walls" if mode == "walls" else "k_stream")
+
+
+@pytest.mark.parametrize("coll", ["SRT", "TRT", "MRT"])
+def test_push_kernel(coll):
+    _run(68, 52, coll, 0, kernel="push")
+
+
+def test_auto_c3_mrt_4096():
+    """The C3 shape (4096^2 MRT, the benchmark's lattice) on the AUTO route for the 20 steps of the driver's bench."""
+    n = 4096
+    set_threads(max(1, min(max_threads(), 16)))
+    try:
+        o = _oracle(n, n, 1000.0, "MRT", 0).step(20)
+    finally:
+        set_threads(1)
+    with CavitySolver(n, n, 1000.0, RT="MRT", dtype=np.float32, arith="promoted") as s:
+        assert s.describe()["kernel"] == launch_plan(n, n, 1000.0, RT="MRT", arith="promoted")["kernel"] == "k_stream_walls"
+        s.step(20)
+        _same(s, o, "C3")
+
+
+def test_auto_datagen_shape():
+    """384^2 SRT + closure (the datagen lattice and the reference script's default mode) on the AUTO route, 200 steps."""
+    d = _run(384, 384, "SRT", 1, counts=(200,))
+    assert d["kernel"] == "k_stepS_deep"
+
+
+def test_batch_of_three_reynolds_numbers():
+    Re = [400.0, 1000.0, 5000.0]
+    with CavityBatch(96, 80, Re, RT="SRT", dtype=np.float32, turb=1, arith="promoted") as b:
+        b.step(30)
+        u, rho, fin = b.get_fields(want_fin=True)
+    for i, r in enumerate(Re):
+        o = _oracle(96, 80, r, "SRT", 1).step(30)
+        assert np.array_equal(fin[i], o.fin) and np.array_equal(u[i], o.u) and np.array_equal(rho[i], o.rho), r
+
+
+@pytest.mark.parametrize("coll,turb,kernel,nx,ny,nslabs", [("MRT", 0, "auto", 132, 67, 3), ("SRT", 1, "auto", 132, 67, 2),
+                                                          ("MRT", 0, "stream", 132, 200, 2), ("SRT", 0, "stream", 132, 200, 2)])
+def test_slabs_on_one_device(coll, turb, kernel, nx, ny, nslabs):
+    """Slabs driven through their launch units, the halos moved by the caller (LocalSlabs), against the oracle on the whole lattice."""
+    steps = 40
+    o = _oracle(nx, ny, 400.0, coll, turb).step(steps)
+    slabs = [CavitySolver(nx, ny, 400.0, RT=coll, dtype=np.float32, turb=turb, kernel=kernel, arith="promoted", rows=r)
+             for r in partition_rows(ny, nslabs)]
+    try:
+        LocalSlabs(slabs).step(steps)
+        u = np.zeros_like(o.u); rho = np.zeros_like(o.rho); fin = np.zeros_like(o.fin)
+        for s in slabs:
+            s.get_fields(u=u, rho=rho, fin=fin)
+    finally:
+        for s in slabs:
+            s.close()
+    assert np.array_equal(fin, o.fin) and np.array_equal(u, o.u) and np.array_equal(rho, o.rho)
+
+
+def test_init_and_set_state():
+    nx, ny = 96, 80
+    with CavitySolver(nx, ny, 1000.0, RT="SRT", dtype=np.float32, turb=1, arith="promoted") as s:
+        _, _, fin0 = s.get_fields(want_fin=True)
+        assert np.array_equal(fin0, _oracle(nx, ny, 1000.0, "SRT", 1).fin)      # init_equilibrium (lbmref_init, promote)
+        state = _oracle(nx, ny, 1000.0, "SRT", 1).step(30).fin
+        s.set_state(state)
+        o = _oracle(nx, ny, 1000.0, "SRT", 1)
+        o.set_state(state)                                                        # history of the uploaded state (lbmref_history)
+        done = 0
+        for n in (1, 7, 20):
+            s.step(n - done)
+            o.step(n - done)
+            done = n
+            _same(s, o, n)
+
+
+def _promoted_tau(o, omega):
+    """taus_g of MRT_GPU.py:385 in lbm_ref.c:97-101's order from the oracle's state: float tau0*tau0 and |q|, the rest in double, one rounding."""
+    f, fe = o.fin, o.feq
+    q = (-f[8] + (f[7] + (-f[6] + f[5]))) - (-fe[8] + (fe[7] + (-fe[6] + fe[5])))       # float32 throughout
+    tau0 = np.float32(1.0) / np.float32(omega)
+    tt, aq = tau0 * tau0, np.abs(q)
+    t = 0.5 * (np.float64(tau0) + np.sqrt(np.float64(tt) + ((18 * 1.4142) * np.float64(np.float32(0.025))) * aq.astype(np.float64)
+                                          / o.rho.astype(np.float64)))
+    return t.astype(np.float32)
+
+
+@pytest.mark.parametrize("kernel", ["tb", "stream"])
+def test_get_tau(kernel):
+    nx, ny = (132, 99) if kernel == "tb" else (132, 130)
+    with CavitySolver(nx, ny, 5000.0, RT="SRT", dtype=np.float32, turb=1, kernel=kernel, arith="promoted") as s:
+        o = _oracle(nx, ny, 5000.0, "SRT", 1)
+        for n in (1, 7, 1, 13):
+            s.step(n)
+            o.step(s.steps_done - 1 - o.nsteps)     # one step behind: the state and history the last iteration started from
+            want = _promoted_tau(o, s.relax["omega"])
+            got = s.get_tau()
+            assert got.dtype == np.float32 and np.array_equal(got, want), n
+
+
+@pytest.mark.parametrize("coll,turb", [("MRT", 0), ("SRT", 1)])
+def test_promoted_is_not_strict(coll, turb):
+    n = 128
+    fins = {}
+    for arith in ("strict", "promoted"):
+        with CavitySolver(n, n, 1000.0, RT=coll, dtype=np.float32, turb=turb, arith=arith) as s:
+            s.step(100)
+            fins[arith] = s.get_fields(want_fin=True)[2]
+    assert not np.array_equal(fins["strict"], fins["promoted"])
+
+
+@pytest.mark.parametrize("coll,turb", [("MRT", 0), ("SRT", 1)])
+@pytest.mark.parametrize("kernel,n", [("tb", 96), ("stream", 132)])
+def test_fp64_promoted_equals_strict(kernel, n, coll, turb):
+    out = {}
+    for arith in ("strict", "promoted"):
+        with CavitySolver(n, n, 1000.0, RT=coll, dtype=np.float64, turb=turb, kernel=kernel, arith=arith) as s:
+            s.step(50)
+            out[arith] = s.get_fields(want_fin=True) + (s.get_tau(),)
+    assert all(np.array_equal(a, b) for a, b in zip(out["strict"], out["promoted"]))
+
+
+def test_describe_matches_the_dry_run():
+    for n in (160, 384, 1024, 2048, 4096):
+        for coll, turb in OPS:
+            kw = dict(RT=coll, turb=turb, arith="promoted")
+            with CavitySolver(n, n, 1000.0, dtype=np.float32, **kw) as s:
+                got = s.describe()
+            want = launch_plan(n, n, 1000.0, **kw)
+            assert got["kernel"] == want["kernel"] and got["steps_per_launch"] == want["steps_per_launch"], (n, coll, turb)
+
+
+def test_checkpoint_round_trip(tmp_path):
+    kw = dict(RT="MRT", dtype=np.float32)
+    with CavitySolver(96, 80, 1000.0, arith="promoted", **kw) as s:
+        s.step(30)
+        path = s.save_checkpoint(tmp_path / "prom")
+        s.step(20)
+        want = s.get_fields(want_fin=True)
+    with CavitySolver(96, 80, 1000.0, arith="promoted", **kw) as r:
+        assert r.load_checkpoint(path) == 30
+        r.step(20)
+        got = r.get_fields(want_fin=True)
+    assert all(np.array_equal(a, b) for a, b in zip(got, want))
+    with CavitySolver(96, 80, 1000.0, arith="strict", **kw) as t:
+        with pytest.raises(ValueError, match="arith"):
+            t.load_checkpoint(path)
+        assert t.load_checkpoint(path, strict=False) == 30
