@@ -173,8 +173,9 @@ __device__ __forceinline__ f32x2 fma_(f32x2 a, f32x2 b, f32x2 c) { return __buil
 // +-1, +-2, +-4 entries of M are exact scalings: value-identical to the dense products.
 template <typename T, int COLL>
 __device__ __forceinline__ void collide(const T (&f)[Q], T rho, const T (&feq)[Q],
-                                        const Relax<typename ScalarOf<T>::type>& w, T w_nu, T (&out)[Q]) {
+                                        const Relax<typename ScalarOf<T>::type>& w, T w_nu, T (&out)[Q], bool lid = false) {
     // w_nu: the viscous rate of each cell (w.w_nu, or the Smagorinsky value); the other rates are lattice-wide scalars
+    // lid (C_MRT_FAST only): the cells are on the lid row, where rho is the overridden rho_l, not the population sum m0
     typedef typename ScalarOf<T>::type R;
     if (COLL == C_SRT || COLL == C_SRT_FAST || COLL == C_SRT_PROM) {
 #pragma unroll
@@ -197,9 +198,13 @@ __device__ __forceinline__ void collide(const T (&f)[Q], T rho, const T (&feq)[Q
         // The same operator, m = M f, m* = m - S (m - m_eq), f* = Minv m*, with the sums of M and Minv factored through the
         // pairs f1 +- f3, f2 +- f4, f5 +- f7, f6 +- f8 and explicit fused multiply-adds: ~75 operations per cell instead of
         // ~190.  Algebraically identical to the branch below, NOT the reference's operation order: results differ from the
-        // strict form in the last bits (tolerances in tests/test_gpu_parity.py::test_fast_arithmetic_*).  The operations are
-        // spelled out (no compiler contraction), so every kernel variant performs the same ones and a lattice gives the same
-        // bits however it is cut into tiles, frames or slabs.
+        // strict form in the last bits (tests/test_arith_error_budget_gpu.py bounds the difference against a long-double reference;
+        // tests/test_arith_error_budget_cpu.py checks the algebra).  The operations are spelled out (no compiler contraction), so
+        // every kernel variant performs the same ones and a lattice gives the same bits however it is cut into tiles, frames or slabs.
+        // m_eq[1], m_eq[2] take the density the strict form takes: rho, which is m0 everywhere but on the lid row (rho_l = f0 + f1
+        // + f3 + 2 (f2 + f5 + f6), MRT_GPU.py:400-405,638-642).  m0 itself relaxes at rate 0 and goes into the back transform as r.
+        // Off the lid the factored sum r stands in for rho (same number up to rounding), so the interior's operations are those of
+        // the sum already formed; `lid` is a compile-time false in every kernel that never holds a lid cell.
         const T a13 = f[1] + f[3], d13 = f[1] - f[3], a24 = f[2] + f[4], d24 = f[2] - f[4];
         const T a57 = f[5] + f[7], d57 = f[5] - f[7], a68 = f[6] + f[8], d68 = f[6] - f[8];
         const T sa = a13 + a24, sd = a57 + a68, dm = d57 - d68, dp = d57 + d68;
@@ -211,8 +216,9 @@ __device__ __forceinline__ void collide(const T (&f)[Q], T rho, const T (&feq)[Q
         T qx = fma_(T((R)-2), d13, dm), qy = fma_(T((R)-2), d24, dp);       // m4, m6
         T pxx = a13 - a24, pxy = a57 - a68;                                 // m7, m8
         const T jx2 = jx * jx, jy2 = jy * jy, j23 = (R)3 * (jx2 + jy2);
-        e = fma_(T(-w.w_e), e - fma_(T((R)-2), r, j23), e);
-        eps = fma_(T(-w.w_eps), eps - fma_(T((R)9), jx2 * jy2, r - j23), eps);
+        const T rq = lid ? rho : r;                                         // the density of m_eq[1], m_eq[2]
+        e = fma_(T(-w.w_e), e - fma_(T((R)-2), rq, j23), e);
+        eps = fma_(T(-w.w_eps), eps - fma_(T((R)9), jx2 * jy2, rq - j23), eps);
         qx = fma_(T(-w.w_q), qx - jx * fma_(T((R)3), jx2, T((R)-1)), qx);
         qy = fma_(T(-w.w_q), qy - jy * fma_(T((R)3), jy2, T((R)-1)), qy);
         pxx = fma_(-w_nu, pxx - (jx2 - jy2), pxx);
@@ -314,7 +320,8 @@ __device__ __forceinline__ T diag_flux(const T (&f)[Q]) {   // product = cx cy f
 // exactly.  Same operator, other rounding: NOT the reference's operation order (tolerances: tests/test_gpu_parity.py::test_fast_arithmetic_*);
 // one spelling for every kernel, so a lattice gives the same bits however it is cut.
 template <typename T, int COLL, bool TURB>
-__device__ __forceinline__ void equ_collide(const T (&g)[Q], T rho, T ux, T uy, const Relax<typename ScalarOf<T>::type>& w, T w_nu, T (&out)[Q], T& q2) {
+__device__ __forceinline__ void equ_collide(const T (&g)[Q], T rho, T ux, T uy, const Relax<typename ScalarOf<T>::type>& w, T w_nu, T (&out)[Q], T& q2,
+                                            bool lid = false) {   // lid: the cells are on the lid row (only the factored MRT form asks)
     typedef typename ScalarOf<T>::type R;
     // (fp32 SRT with the closure keeps the unfused sequence: at the streaming kernels' 128 registers the fused one spills there -- 4096^2
     // 256 -> 210 GLUPS, while fp64 gains, 108 -> 134; without the closure it is what lets fp32 SRT take the walls kernel, 251 -> 414)
@@ -353,7 +360,7 @@ __device__ __forceinline__ void equ_collide(const T (&g)[Q], T rho, T ux, T uy, 
         // (the MRT operator needs neither u nor feq, MRT_GPU.py:633-648; the closure's history sum_k cx cy feq_k is rho ux uy, see above --
         // the nine equilibria the strict form builds for it are left out: 4096^2 MRT + closure fp32 212 -> 283 GLUPS, fp64 91 -> 117)
         T fe[Q];
-        collide<T, COLL>(g, rho, fe, w, w_nu, out);
+        collide<T, COLL>(g, rho, fe, w, w_nu, out, lid);
         if (TURB) q2 = rho * (ux * uy);
     } else {
         T fe[Q];
@@ -512,7 +519,7 @@ __device__ __forceinline__ void update_cell_a(const R* __restrict__ src, const A
     R w_nu = w0.w_nu;
     if (TURB) w_nu = smagorinsky_omega<R, coll_is_fast(COLL), coll_is_prom(COLL)>(g, src[K_QEQ * as.plane + me_s], src[K_RHO * as.plane + me_s], w0.w_nu);
     macros<R, coll_is_fast(COLL)>(g, x, gy, X, Y, w.uLB, rho, ux, uy);
-    equ_collide<R, COLL, TURB>(g, rho, ux, uy, w, w_nu, out, q2);
+    equ_collide<R, COLL, TURB>(g, rho, ux, uy, w, w_nu, out, q2, COLL == C_MRT_FAST && gy == 0);
     if (TURB) {
         dst[K_QEQ * ad.plane + me] = q2;
         dst[K_RHO * ad.plane + me] = rho;
@@ -666,7 +673,7 @@ __device__ __forceinline__ void collide_vec(const typename VecT<R, V>::type (&in
                     ux = f32x2(kind == 1 ? w0.uLB : 0.f); uy = f32x2(0.f);
                 }
             }
-            equ_collide<f32x2, COLL, TURB>(g, rho, ux, uy, w0, w_nu, out, q2);
+            equ_collide<f32x2, COLL, TURB>(g, rho, ux, uy, w0, w_nu, out, q2, COLL == C_MRT_FAST && kind == 1);
 #pragma unroll
             for (int k = 0; k < Q; ++k) {
                 if (p == 0) outv[k].xy = out[k];
@@ -700,7 +707,7 @@ __device__ __forceinline__ void collide_vec(const typename VecT<R, V>::type (&in
                     ux = kind == 1 ? w0.uLB : (R)0; uy = (R)0;
                 }
             }
-            equ_collide<R, COLL, TURB>(g, rho, ux, uy, w0, w_nu, out, q2);
+            equ_collide<R, COLL, TURB>(g, rho, ux, uy, w0, w_nu, out, q2, COLL == C_MRT_FAST && kind == 1);
 #pragma unroll
             for (int k = 0; k < Q; ++k) outv[k][c] = out[k];
             if (TURB) { hq[c] = q2; hr[c] = rho; }

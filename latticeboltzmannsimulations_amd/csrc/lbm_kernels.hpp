@@ -305,7 +305,7 @@ __global__ __launch_bounds__(BLK) void k_push_collide(const R* __restrict__ fin,
 #pragma unroll
     for (int k = 0; k < Q; ++k) g[k] = fin[k * geo.plane + me];
     macros<R, coll_is_fast(COLL)>(g, x, gy, X, Y, w.uLB, rho, ux, uy);
-    equ_collide<R, COLL, false>(g, rho, ux, uy, w, w.w_nu, out, q2);
+    equ_collide<R, COLL, false>(g, rho, ux, uy, w, w.w_nu, out, q2, COLL == C_MRT_FAST && gy == 0);
 #pragma unroll
     for (int k = 0; k < Q; ++k) {
         const int dx = x + cxk(k), dgy = gy - cyk(k);

@@ -57,11 +57,25 @@ M_GS_INV = np.array([
 
 
 def weights(dtype):
-    """MRT.py:142-144 / MRT_GPU.py:363."""
+    """MRT.py:142-144 / MRT_GPU.py:363.  np.longdouble: the rationals rounded once to long double, not the fp64 literals."""
+    if np.dtype(dtype) == np.longdouble:
+        L = np.longdouble
+        return np.array([L(4) / 9] + [L(1) / 9] * 4 + [L(1) / 36] * 4, dtype=np.longdouble)
     t = 1.0 / 36. * np.ones(9)
     t[1:5] = 1.0 / 9.0
     t[0] = 4.0 / 9.0
     return t.astype(dtype)
+
+
+# 36 * M_GS_INV is an integer matrix: the long-double reference divides it by 36 in long double (one rounding per entry)
+M_GS_INV_36 = np.rint(36 * M_GS_INV).astype(np.int64)
+assert np.array_equal(M_GS_INV_36 / 36.0, M_GS_INV)
+
+
+def m_gs_inv(dtype):
+    if np.dtype(dtype) == np.longdouble:
+        return M_GS_INV_36.astype(np.longdouble) / np.longdouble(36)
+    return M_GS_INV.astype(dtype)
 
 
 def relaxation(Re, ny_global, uLB=0.08, omega_eps=1.2, omega_q=1.2):
@@ -98,10 +112,18 @@ class CavityOracle:
     """Whole-domain stepper on reference-layout arrays fin[9, X, Y]."""
 
     def __init__(self, nx, ny, Re, uLB=0.08, semantics="mrt_py", collision="SRT",
-                 dtype=np.float64, omega_eps=None, omega_q=None, ny_global=None, turb=0, promote=False):
+                 dtype=np.float64, omega_eps=None, omega_q=None, ny_global=None, turb=0, promote=False,
+                 omega_e=None, omegam=None, param_dtype=None):
         """promote: the sub-expressions of MRT_GPU.py's CUDA text that carry `double` literals (lines 385, 410, 638-642, 652) are
         evaluated in double and rounded once to the lattice type -- what C's usual arithmetic conversions prescribe for that text;
-        everything else stays an operation of the lattice type.  (nvcc's default FMA contraction is a further, unknowable, step.)"""
+        everything else stays an operation of the lattice type.  (nvcc's default FMA contraction is a further, unknowable, step.)
+
+        omega_e, omegam: explicit MRT energy rate and TRT odd rate (as lbm_set_relaxation sets them); default: relaxation().
+
+        dtype=np.longdouble is the extended-precision reference of the tests' error budgets: weights and M_GS_INV are the exact
+        rationals rounded once to long double, and every operation rounds to the 64-bit mantissa.  param_dtype (default: dtype, or
+        float64 for long double) is the lattice type the device runs in: the rates, uLB and the closure's constants are rounded to
+        it first, so the reference solves the problem the device was given."""
         assert semantics in ("mrt_py", "mrt_gpu") and collision in ("SRT", "TRT", "MRT")
         assert not (promote and semantics != "mrt_gpu"), "promotion is a property of MRT_GPU.py's CUDA text"
         self.promote = bool(promote)
@@ -111,21 +133,31 @@ class CavityOracle:
         self.sem, self.coll = semantics, collision
         self.dtype = np.dtype(dtype)
         R = self.R = self.dtype.type
+        if self.dtype == np.longdouble:
+            assert np.finfo(np.longdouble).nmant >= 63, "the long-double reference needs an 80-bit (or wider) long double"
+            assert not promote, "promotion is a property of a float lattice"
+        P = np.dtype(param_dtype if param_dtype is not None else (np.float64 if self.dtype == np.longdouble else dtype)).type
+        self.par = lambda v: R(P(v))      # a parameter as the device holds it, in the arithmetic type
         if omega_eps is None:
             omega_eps = 1.0 if semantics == "mrt_py" else 1.2   # MRT.py:72 vs MRT_GPU.py:90
         if omega_q is None:
             omega_q = 1.2
         self.relax = relaxation(Re, ny if ny_global is None else ny_global, uLB, omega_eps, omega_q)
+        if omega_e is not None:
+            self.relax["omega_e"] = omega_e
+        if omegam is not None:
+            self.relax["omegam"] = omegam
         self.t = weights(dtype)
-        self.MI = M_GS_INV.astype(dtype)
+        self.MI = m_gs_inv(dtype)
         rl = self.relax
-        self.omega_vec = [R(0.0), R(rl["omega_e"]), R(rl["omega_eps"]), R(0.0), R(rl["omega_q"]),
-                          R(0.0), R(rl["omega_q"]), R(rl["omega"]), R(rl["omega"])]
+        par = self.par
+        self.omega_vec = [R(0.0), par(rl["omega_e"]), par(rl["omega_eps"]), R(0.0), par(rl["omega_q"]),
+                          R(0.0), par(rl["omega_q"]), par(rl["omega"]), par(rl["omega"])]
         # A.7 init (MRT.py:206,260-268)
         self.rho = np.ones((nx, ny), dtype=dtype)
         self.u = np.zeros((2, nx, ny), dtype=dtype)
         iv = np.zeros((2, nx, ny), dtype=dtype)
-        iv[0, :, 0] = uLB
+        iv[0, :, 0] = self.par(uLB)
         self.fin = equ(self.rho, iv[0], iv[1], self.t, self.promote)
         self.feq = self.fin.copy()          # feq_g starts as a copy of fin (MRT_GPU.py:325)
         self.fpost = self.fin.copy()
@@ -143,14 +175,18 @@ class CavityOracle:
         ux[0, 1:] = 0; uy[0, 1:] = 0                                       # MRT.py:341
         ux[X - 1, 1:] = 0; uy[X - 1, 1:] = 0
         ux[:, Y - 1] = 0; uy[:, Y - 1] = 0
-        ux[:, 0] = R(self.uLB); uy[:, 0] = 0                               # MRT.py:342
+        ux[:, 0] = self.par(self.uLB); uy[:, 0] = 0                               # MRT.py:342
         return rho, ux, uy
 
     # --- Smagorinsky relaxation rate (MRT_GPU.py:368-387; the Van Driest lines 370-373 are dead
     #     code because Cs2 is overwritten at 374) ------------------------------------------
     def smagorinsky_omega(self, f, feq_prev, rho_prev):
+        return self.R(1.0) / self.smagorinsky_tau(f, feq_prev, rho_prev)
+
+    def smagorinsky_tau(self, f, feq_prev, rho_prev):
+        """tau + tau_turbulent (taus_g, MRT_GPU.py:387)."""
         R = self.R
-        tau0 = R(1.0) / R(self.relax["omega"])
+        tau0 = R(1.0) / self.par(self.relax["omega"])
         # product = c_x c_y f_k + product, k = 0..8: only the diagonals contribute
         p1 = -f[8] + (f[7] + (-f[6] + f[5]))
         p2 = -feq_prev[8] + (feq_prev[7] + (-feq_prev[6] + feq_prev[5]))
@@ -161,20 +197,19 @@ class CavityOracle:
             D = np.float64
             tau = (D(0.5) * (D(tau0) + np.sqrt(D(tau0 * tau0) + ((D(18 * 1.4142) * D(R(0.025))) * np.abs(q).astype(D))
                                                / rho_prev.astype(D)))).astype(self.dtype)
-            return R(1.0) / tau
-        tau = R(0.5) * (tau0 + np.sqrt(tau0 * tau0 + ((R(18 * 1.4142) * R(0.025)) * np.abs(q)) / rho_prev))
-        return R(1.0) / tau
+            return tau
+        return R(0.5) * (tau0 + np.sqrt(tau0 * tau0 + ((self.par(18 * 1.4142) * self.par(0.025)) * np.abs(q)) / rho_prev))
 
     # --- a6: collision operators -------------------------------------------------------
     def collide(self, f, rho, feq, w_nu=None):
         R = self.R
         rl = self.relax
         if w_nu is None:
-            w_nu = R(rl["omega"])
+            w_nu = self.par(rl["omega"])
         if self.coll == "SRT":                                             # MRT.py:396 / MRT_GPU.py:413
             return f - w_nu * (f - feq)
         if self.coll == "TRT":                                             # MRT_GPU.py:455-462,514-525
-            op, om = w_nu, R(rl["omegam"])
+            op, om = w_nu, self.par(rl["omegam"])
             fp = np.empty_like(f); fm = np.empty_like(f)
             ep = np.empty_like(f); em = np.empty_like(f)
             for a, b in ((2, 4), (5, 7), (6, 8), (1, 3)):
@@ -278,8 +313,12 @@ class CavityOracle:
 
     # --- a9: one iteration -------------------------------------------------------------
     def step(self, n=1):
+        R = self.R
         for _ in range(n):
-            w_nu = self.smagorinsky_omega(self.fin, self.feq, self.rho) if self.turb else None
+            w_nu = None
+            if self.turb:
+                self.tau = self.smagorinsky_tau(self.fin, self.feq, self.rho)     # what lbm_get_tau returns
+                w_nu = R(1.0) / self.tau
             rho, ux, uy = self.macros(self.fin)
             feq = equ(rho, ux, uy, self.t, self.promote)
             fpost = self.collide(self.fin, rho, feq, w_nu)

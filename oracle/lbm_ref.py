@@ -62,9 +62,10 @@ class CavityOracleC:
     """Same interface as oracle.lbm_numpy.CavityOracle, backed by lbm_ref.c."""
 
     def __init__(self, nx, ny, Re, uLB=0.08, semantics="mrt_py", collision="SRT", dtype=np.float64,
-                 omega_eps=None, omega_q=None, ny_global=None, turb=0, promote=False):
+                 omega_eps=None, omega_q=None, ny_global=None, turb=0, promote=False, omega_e=None, omegam=None):
         """promote: evaluate the sub-expressions of MRT_GPU.py's CUDA text that carry `double` literals in double and round once to
-        the lattice type (C's usual arithmetic conversions; lbm_ref.c, PROMOTE).  No effect on an fp64 lattice."""
+        the lattice type (C's usual arithmetic conversions; lbm_ref.c, PROMOTE).  No effect on an fp64 lattice.
+        omega_e, omegam: explicit MRT energy rate and TRT odd rate (as lbm_set_relaxation sets them); default: relaxation()."""
         from .lbm_numpy import relaxation
         assert not (promote and semantics != "mrt_gpu"), "promotion is a property of MRT_GPU.py's CUDA text"
         self.promote = int(bool(promote))
@@ -77,6 +78,10 @@ class CavityOracleC:
         if omega_q is None:
             omega_q = 1.2
         self.relax = relaxation(Re, ny if ny_global is None else ny_global, uLB, omega_eps, omega_q)
+        if omega_e is not None:
+            self.relax["omega_e"] = omega_e
+        if omegam is not None:
+            self.relax["omegam"] = omegam
         self._w = relax_vector(self.relax)
         self._suf = "f64" if self.dtype == np.float64 else "f32"
         self._ct = ctypes.c_double if self.dtype == np.float64 else ctypes.c_float
