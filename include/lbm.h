@@ -35,8 +35,19 @@ typedef enum lbm_status {
 
 enum { LBM_F32 = 0, LBM_F64 = 1 };                      /* storage and arithmetic type */
 enum { LBM_SRT = 0, LBM_TRT = 1, LBM_MRT = 2 };         /* RT = 'SRT' | 'TRT' | 'MRT'  (MRT_GPU.py:48) */
-enum { LBM_SEM_MRT_PY = 0, LBM_SEM_MRT_GPU = 1 };       /* streaming windows + wall rules of MRT.py:404-453
-                                                           or of MRT_GPU.py:412,674-692 */
+enum { LBM_SEM_MRT_PY = 0, LBM_SEM_MRT_GPU = 1,        /* streaming windows + wall rules of MRT.py:404-453
+                                                           or of MRT_GPU.py:412,674-692 (wet-node walls) */
+       LBM_SEM_BOUNCE_BACK = 2 };                       /* half-way bounce-back walls (link-based, the reference's "BB" option,
+                                                           MRT_GPU.py:281): every lattice cell is a fluid cell, the walls sit half
+                                                           a cell outside the lattice, the lid half a cell beyond global row 0.
+                                                           The slot k of cell (x, y) pulls from (x - cx_k, y + cy_k); a source
+                                                           outside the lattice gives the cell's own post-collision population of
+                                                           the opposite direction instead, plus -- source row above the lid --
+                                                           Ladd's moving-wall term 6 w_k rho_w (c_k . u_lid) = cx_k (rho_w uLB) / 6
+                                                           (diagonals only), rho_w = the density of the cell's last macroscopic
+                                                           state.  No macroscopic override on any cell.  Relaxation rates as
+                                                           MRT_GPU (omega_eps = 1.2).  Not with turb = 1, arith = promoted,
+                                                           kernel = PUSH / VEC or LBM_FLAG_STREAM_WALLS / STREAM_PAIRS. */
 enum { LBM_KERNEL_AUTO = 0,      /* fastest applicable: STREAM (large lattices), TB (lattices from 64 x 64 cells), else VEC, else GENERIC */
        LBM_KERNEL_GENERIC = 1,   /* one step per launch, one thread per cell (all semantics) */
        LBM_KERNEL_VEC = 2,       /* one step per launch, 16 B per access (MRT_GPU semantics) */
@@ -84,7 +95,7 @@ typedef struct lbm_params {
     int32_t ny_local;    /* rows owned by this context (= ny when not slab-decomposed, >= 2) */
     int32_t dtype;       /* LBM_F32 | LBM_F64 */
     int32_t collision;   /* LBM_SRT | LBM_TRT | LBM_MRT */
-    int32_t semantics;   /* LBM_SEM_MRT_PY | LBM_SEM_MRT_GPU */
+    int32_t semantics;   /* LBM_SEM_MRT_PY | LBM_SEM_MRT_GPU | LBM_SEM_BOUNCE_BACK */
     int32_t kernel;      /* LBM_KERNEL_* */
     int32_t turb;        /* 0 | 1: Smagorinsky closure of MRT_GPU.py:368-387 (MRT_GPU semantics only) */
     int32_t device;      /* HIP device ordinal (reference: cuda.Device(0), MRT_GPU.py:29) */

@@ -18,7 +18,7 @@ LINK_FLAGS = ["-ldl"]   # RCCL is bound lazily with dlopen inside the library
 
 LBM_F32, LBM_F64 = 0, 1
 LBM_SRT, LBM_TRT, LBM_MRT = 0, 1, 2
-LBM_SEM_MRT_PY, LBM_SEM_MRT_GPU = 0, 1
+LBM_SEM_MRT_PY, LBM_SEM_MRT_GPU, LBM_SEM_BOUNCE_BACK = 0, 1, 2
 LBM_KERNEL_AUTO, LBM_KERNEL_GENERIC, LBM_KERNEL_VEC, LBM_KERNEL_TB, LBM_KERNEL_PUSH, LBM_KERNEL_STREAM = 0, 1, 2, 3, 4, 5
 LBM_LAYOUT_AUTO, LBM_LAYOUT_PLANES, LBM_LAYOUT_ROWS = 0, 1, 2
 LBM_SIDE_LOW, LBM_SIDE_HIGH = 0, 1
@@ -66,7 +66,7 @@ def build(force=False, verbose=False):
         if verbose:
             print(" ".join(cmd))
         subprocess.check_call(cmd)
-    with ThreadPoolExecutor(max_workers=min(len(units), os.cpu_count() or 4)) as pool:
+    with ThreadPoolExecutor(max_workers=min(len(units), os.cpu_count() or 4, 16)) as pool:   # (at most 16 compiles at once)
         list(pool.map(compile_one, zip(units, objs)))
     cmd = [HIPCC, "--offload-arch=gfx950", "-fPIC", "-shared", "-o", LIB_PATH] + objs + LINK_FLAGS
     if verbose:

@@ -19,7 +19,7 @@ constexpr int GHY = 10; // ghost rows above and below a lattice: row -1 / ny is 
 __host__ __device__ constexpr int cxk(int k) { return k == 1 || k == 5 || k == 8 ? 1 : (k == 3 || k == 6 || k == 7 ? -1 : 0); }
 __host__ __device__ constexpr int cyk(int k) { return k == 2 || k == 5 || k == 6 ? 1 : (k == 4 || k == 7 || k == 8 ? -1 : 0); }
 
-enum { SEM_PY = 0, SEM_GPU = 1 };
+enum { SEM_PY = 0, SEM_GPU = 1, SEM_BB = 2 };   // = lbm_params.semantics (LBM_SEM_MRT_PY, LBM_SEM_MRT_GPU, LBM_SEM_BOUNCE_BACK)
 enum { C_SRT = 0, C_TRT = 1, C_MRT = 2,
        // lbm_params.arith = LBM_ARITH_FAST: not the reference's operation order / rounding --
        C_MRT_FAST = 3,     // the MRT operator in factored form with fused multiply-adds
@@ -46,12 +46,15 @@ template <typename T> struct ScalarOf { typedef T type; };
 template <> struct ScalarOf<f32x2> { typedef float type; };
 
 // Destination window of direction k (a7).  SEM_PY: the truncated slices of MRT.py:404-414;
-// SEM_GPU: "neighbour inside the lattice", MRT_GPU.py:412.  gy is the GLOBAL row.
+// SEM_GPU: "neighbour inside the lattice", MRT_GPU.py:412.  SEM_BB: every slot of every cell streams (a source outside the
+// lattice is the bounce-back of gather_a, not a kept slot).  gy is the GLOBAL row.
 template <int SEM>
 __device__ __forceinline__ bool in_window(int k, int x, int gy, int X, int Y) {
     const int cx = cxk(k), cy = cyk(k);
     bool ok = true;
-    if (SEM == SEM_PY) {
+    if (SEM == SEM_BB) {
+        return true;
+    } else if (SEM == SEM_PY) {
         if (cx > 0) ok = ok && (x >= 1) && (x <= X - 2);
         if (cx < 0) ok = ok && (x <= X - 3);
         if (cy > 0) ok = ok && (gy <= Y - 3);
@@ -149,12 +152,13 @@ __device__ __forceinline__ void equ(T rho, T ux, T uy, T (&feq)[Q]) {
 }
 
 // a4 + a5: moments with the macroscopic wall overrides (MRT.py:292,320-321,337,341-342;
-// MRT_GPU.py:389-405).  rho_sum is the plain sum (used by nothing but kept for clarity).
-template <typename R, bool FAST = false>
+// MRT_GPU.py:389-405).  SEM_BB: the plain moments on every cell (all of them are fluid cells; no override).
+template <typename R, bool FAST = false, int SEM = SEM_GPU>
 __device__ __forceinline__ void macros(const R (&f)[Q], int x, int gy, int X, int Y, R uLB, R& rho, R& ux, R& uy) {
     rho = ((((((((f[0] + f[1]) + f[2]) + f[3]) + f[4]) + f[5]) + f[6]) + f[7]) + f[8]);
     ux = div_<FAST>((((((f[1] - f[3]) + f[5]) - f[6]) - f[7]) + f[8]), rho);
     uy = div_<FAST>((((((f[2] - f[4]) + f[5]) + f[6]) - f[7]) - f[8]), rho);
+    if (SEM == SEM_BB) return;
     if (x == 0 || x == X - 1 || gy == Y - 1) { ux = (R)0; uy = (R)0; }
     if (gy == 0) {
         rho = ((f[0] + f[1]) + f[3]) + (R)2. * ((f[2] + f[5]) + f[6]);
@@ -471,6 +475,13 @@ __device__ __forceinline__ auto wall_rho_at(const A& a, const Geo& g, int x, int
     return a.at(g.nx, y);
 }
 
+// Half-way bounce-back (SEM_BB): the opposite direction of k, and Ladd's moving-wall term of a slot whose source lies beyond the
+// lid, 6 w_k rho_w (c_k . u_lid) with u_lid = (uLB, 0): +-t for the diagonals k = 8 / 7 (cx = +1 / -1), 0 for k = 4 (nothing is
+// added there).  rho_w: the cell's parked density.  The one spelling of the term; tests/bounce_back_ref.py restates it.
+__host__ __device__ constexpr int opp(int k) { return k == 0 ? 0 : (k < 5 ? (k + 1) % 4 + 1 : (k - 3) % 4 + 5); }
+template <typename R>
+__device__ __forceinline__ R lid_term(R rho_w, R uLB) { return (rho_w * uLB) * (R)(1.0 / 6.0); }
+
 // Gather the post-stream, post-wall-rule populations of cell (x, y) from a lattice that
 // holds post-collision values (+ kept slots + parked wall densities); raw != 0: the lattice
 // holds plain populations (state just set by the host), nothing to stream.  PROM: the wall rules' equilibrium in the promoted form.
@@ -484,6 +495,24 @@ __device__ __forceinline__ void gather_a(const R* __restrict__ src, const AS& as
     }
 #pragma unroll
     for (int k = 0; k < Q; ++k) g[k] = src[k * as.plane + as.at(x - cxk(k), y + cyk(k))];
+    if (SEM == SEM_BB) {
+        // a source outside [0, nx) x [0, NY): the cell's own post-collision population of the opposite direction; beyond the lid
+        // (corner ghosts included) plus the lid term.  The cell's own slots were stored at its own position by update_cell_a (every
+        // slot streams); the ghost positions of the pulls above are read but not used here.
+        if (x == 0 || x == geo.nx - 1 || gy == 0 || gy == geo.NY - 1) {
+#pragma unroll
+            for (int k = 1; k < Q; ++k) {
+                const int sx = x - cxk(k), sgy = gy + cyk(k);
+                if (sx < 0 || sx >= geo.nx || sgy < 0 || sgy >= geo.NY) g[k] = src[opp(k) * as.plane + as.at(x, y)];
+            }
+            if (gy == 0) {
+                const R t = lid_term<R>(src[wall_rho_at(as, geo, x, y, gy)], uLB);
+                g[8] = g[8] + t;
+                g[7] = g[7] - t;
+            }
+        }
+        return;
+    }
     if (x == 0 || x == geo.nx - 1 || gy == 0 || gy == geo.NY - 1) {
         const R rho_w = src[wall_rho_at(as, geo, x, y, gy)];
         R fe[Q];
@@ -518,8 +547,8 @@ __device__ __forceinline__ void update_cell_a(const R* __restrict__ src, const A
     const Relax<R>& w = w0;
     R w_nu = w0.w_nu;
     if (TURB) w_nu = smagorinsky_omega<R, coll_is_fast(COLL), coll_is_prom(COLL)>(g, src[K_QEQ * as.plane + me_s], src[K_RHO * as.plane + me_s], w0.w_nu);
-    macros<R, coll_is_fast(COLL)>(g, x, gy, X, Y, w.uLB, rho, ux, uy);
-    equ_collide<R, COLL, TURB>(g, rho, ux, uy, w, w_nu, out, q2, COLL == C_MRT_FAST && gy == 0);
+    macros<R, coll_is_fast(COLL), SEM>(g, x, gy, X, Y, w.uLB, rho, ux, uy);
+    equ_collide<R, COLL, TURB>(g, rho, ux, uy, w, w_nu, out, q2, COLL == C_MRT_FAST && gy == 0 && SEM != SEM_BB);
     if (TURB) {
         dst[K_QEQ * ad.plane + me] = q2;
         dst[K_RHO * ad.plane + me] = rho;

@@ -113,6 +113,8 @@ int export_fin_t(lbm_ctx* c) {
         }
     if (c->p.semantics == LBM_SEM_MRT_PY)
         hipLaunchKernelGGL((k_export_fin<R, SEM_PY>), g, dim3(BLK), 0, c->s_compute, src, c->geo, c->raw[c->cur], (R)c->p.uLB, (R*)c->stage, c->bstride);
+    else if (c->p.semantics == LBM_SEM_BOUNCE_BACK)
+        hipLaunchKernelGGL((k_export_fin<R, SEM_BB>), g, dim3(BLK), 0, c->s_compute, src, c->geo, c->raw[c->cur], (R)c->p.uLB, (R*)c->stage, c->bstride);
     else
         hipLaunchKernelGGL((k_export_fin<R, SEM_GPU>), g, dim3(BLK), 0, c->s_compute, src, c->geo, c->raw[c->cur], (R)c->p.uLB, (R*)c->stage, c->bstride);
     HIP_TRY(c, hipGetLastError());
@@ -136,6 +138,8 @@ int export_macro_t(lbm_ctx* c) {
         }
     if (c->p.semantics == LBM_SEM_MRT_PY)
         hipLaunchKernelGGL((k_export_macro<R, SEM_PY>), g, dim3(BLK), 0, c->s_compute, src, c->geo, c->raw[which], (R)c->p.uLB, (R*)c->stage, c->bstride);
+    else if (c->p.semantics == LBM_SEM_BOUNCE_BACK)
+        hipLaunchKernelGGL((k_export_macro<R, SEM_BB>), g, dim3(BLK), 0, c->s_compute, src, c->geo, c->raw[which], (R)c->p.uLB, (R*)c->stage, c->bstride);
     else
         hipLaunchKernelGGL((k_export_macro<R, SEM_GPU>), g, dim3(BLK), 0, c->s_compute, src, c->geo, c->raw[which], (R)c->p.uLB, (R*)c->stage, c->bstride);
     HIP_TRY(c, hipGetLastError());
@@ -179,6 +183,8 @@ int reduce_u_t(lbm_ctx* c) {
         }
     if (c->p.semantics == LBM_SEM_MRT_PY)
         hipLaunchKernelGGL((k_reduce_u<R, SEM_PY>), g, dim3(BLK), 0, c->s_compute, src, c->geo, c->raw[which], (R)c->p.uLB, c->bstride, c->red_dev);
+    else if (c->p.semantics == LBM_SEM_BOUNCE_BACK)
+        hipLaunchKernelGGL((k_reduce_u<R, SEM_BB>), g, dim3(BLK), 0, c->s_compute, src, c->geo, c->raw[which], (R)c->p.uLB, c->bstride, c->red_dev);
     else
         hipLaunchKernelGGL((k_reduce_u<R, SEM_GPU>), g, dim3(BLK), 0, c->s_compute, src, c->geo, c->raw[which], (R)c->p.uLB, c->bstride, c->red_dev);
     HIP_TRY(c, hipGetLastError());

@@ -183,6 +183,7 @@ void dispatch(const lbm_params& p, F&& f) {
             else f(Variant<R, C, SEM_GPU, false>{});
         } else {
             if (p.semantics == LBM_SEM_MRT_PY) f(Variant<R, CS, SEM_PY, false>{});   // (arith = fast: MRT_GPU semantics only)
+            else if (p.semantics == LBM_SEM_BOUNCE_BACK) f(Variant<R, C, SEM_BB, false>{});   // (strict and fast; no closure: validate_params)
             else if (p.turb) f(Variant<R, C, SEM_GPU, true>{});
             else f(Variant<R, C, SEM_GPU, false>{});
         }

@@ -13,6 +13,10 @@
     M(R, C_MRT_FAST, SEM_GPU, true) M(R, C_SRT_FAST, SEM_GPU, true) M(R, C_TRT_FAST, SEM_GPU, true)
 // ... MRT.py semantics: the three strict ones
 #define LBM_PY_VARIANTS(M, R) M(R, C_SRT, SEM_PY, false) M(R, C_TRT, SEM_PY, false) M(R, C_MRT, SEM_PY, false)
+// ... half-way bounce-back: the three strict operators and the three fast ones, no closure (validate_params)
+#define LBM_BB_VARIANTS(M, R)                                                                                                   \
+    M(R, C_SRT, SEM_BB, false) M(R, C_TRT, SEM_BB, false) M(R, C_MRT, SEM_BB, false)                                            \
+    M(R, C_MRT_FAST, SEM_BB, false) M(R, C_SRT_FAST, SEM_BB, false) M(R, C_TRT_FAST, SEM_BB, false)
 // ... arith = promoted (float only: fp64 runs the strict variants), MRT_GPU.py semantics: the three promoted operators, with and without the closure
 #define LBM_PROM_VARIANTS(M, R)                                                                                                 \
     M(R, C_SRT_PROM, SEM_GPU, false) M(R, C_TRT_PROM, SEM_GPU, false) M(R, C_MRT_PROM, SEM_GPU, false)                          \
@@ -44,6 +48,10 @@
 // the promoted operators in every family but k_stream_pairs (plan_kernel refuses stream_pairs with arith = promoted), in two units of their own
 #define LBM_INST_TILES_PROM(R) LBM_PROM_VARIANTS(LBM_TILE_S, R)
 #define LBM_INST_STREAM_PROM(R) LBM_PROM_VARIANTS(LBM_STREAM_ONE, R) LBM_PROM_VARIANTS(LBM_STREAMW_ONE, R) LBM_PROM_VARIANTS(LBM_STREAMS_ONE, R)
+// bounce-back walls in the tile kernel and in k_stream (the frame workgroups of both run the wall rules; the walls-inside kernels refuse
+// the semantics), in units of their own.  The tiles and the streaming segments themselves never compute a perimeter cell.
+#define LBM_INST_TILES_BB(R) LBM_BB_VARIANTS(LBM_TILE_S, R)
+#define LBM_INST_STREAM_BB(R) LBM_BB_VARIANTS(LBM_STREAM_ONE, R)
 
 #ifdef LBM_INST
 #define LBM_X
@@ -56,4 +64,6 @@ LBM_INST_STREAMW(float) LBM_INST_STREAMW(double)
 LBM_INST_STREAMS(float) LBM_INST_STREAMS(double)
 LBM_INST_STREAMP(float) LBM_INST_STREAMP(double)
 LBM_INST_TILES_PROM(float) LBM_INST_STREAM_PROM(float)
+LBM_INST_TILES_BB(float) LBM_INST_TILES_BB(double)
+LBM_INST_STREAM_BB(float) LBM_INST_STREAM_BB(double)
 #endif

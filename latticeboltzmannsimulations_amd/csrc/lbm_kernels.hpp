@@ -434,7 +434,7 @@ __global__ __launch_bounds__(BLK) void k_export_fin(const R* __restrict__ src, G
         }
 }
 
-// lattice -> staging: macroscopic fields (with wall overrides) of the populations gathered
+// lattice -> staging: macroscopic fields (with wall overrides; SEM_BB: none) of the populations gathered
 // from `src`; stage = [ux | uy | rho], each [nx][ny_local]
 template <typename R, int SEM>
 __global__ __launch_bounds__(BLK) void k_export_macro(const R* __restrict__ src, Geo geo, int raw, R uLB,
@@ -451,7 +451,7 @@ __global__ __launch_bounds__(BLK) void k_export_macro(const R* __restrict__ src,
         if (x >= geo.nx || y >= geo.ny) continue;
         R g[Q], rho, ux, uy;
         gather<R, SEM>(src, geo, raw, uLB, x, y, g);
-        macros<R>(g, x, geo.y0 + y, geo.nx, geo.NY, uLB, rho, ux, uy);
+        macros<R, false, SEM>(g, x, geo.y0 + y, geo.nx, geo.NY, uLB, rho, ux, uy);
         t[0][tx][ty] = ux; t[1][tx][ty] = uy; t[2][tx][ty] = rho;
     }
     __syncthreads();
@@ -509,7 +509,7 @@ __global__ __launch_bounds__(BLK) void k_reduce_u(const R* __restrict__ src, Geo
         const int y = (int)(i / geo.nx), x = (int)(i - (long long)y * geo.nx);
         R g[Q], rho, ux, uy;
         gather<R, SEM>(src, geo, raw, uLB, x, y, g);
-        macros<R>(g, x, geo.y0 + y, geo.nx, geo.NY, uLB, rho, ux, uy);
+        macros<R, false, SEM>(g, x, geo.y0 + y, geo.nx, geo.NY, uLB, rho, ux, uy);
         acc += (double)ux + (double)uy;
     }
     red[threadIdx.x] = acc;

@@ -433,10 +433,12 @@ int push_step(lbm_ctx* c) {
         using VT = decltype(v);
         using R = typename VT::R;
         const dim3 g = grid_rows(c, c->geo.ny);
-        hipLaunchKernelGGL((k_push_collide<R, VT::COLL, VT::SEM>), g, dim3(BLK), 0, c->s_compute, (const R*)c->lat[c->cur], (R*)c->lat[2], c->geo,
-                           relax_of<R>(c->p));
-        hipLaunchKernelGGL((k_push_bc<R, VT::COLL, VT::SEM>), g, dim3(BLK), 0, c->s_compute, (const R*)c->lat[c->cur], (R*)c->lat[2],
-                           (R*)c->lat[c->cur ^ 1], c->geo, (R)c->p.uLB);
+        if constexpr (VT::SEM != SEM_BB) {   // (validate_params refuses the push scheme with bounce-back walls)
+            hipLaunchKernelGGL((k_push_collide<R, VT::COLL, VT::SEM>), g, dim3(BLK), 0, c->s_compute, (const R*)c->lat[c->cur], (R*)c->lat[2], c->geo,
+                               relax_of<R>(c->p));
+            hipLaunchKernelGGL((k_push_bc<R, VT::COLL, VT::SEM>), g, dim3(BLK), 0, c->s_compute, (const R*)c->lat[c->cur], (R*)c->lat[2],
+                               (R*)c->lat[c->cur ^ 1], c->geo, (R)c->p.uLB);
+        }
     });
     if (rc) return rc;
     finish_unit(c, 1);

@@ -143,7 +143,7 @@ std::string validate_params(const lbm_params* p) {
     if (p->ny_local > 65535) return std::string("ny_local > 65535 not supported");
     if (p->dtype != LBM_F32 && p->dtype != LBM_F64) return std::string("dtype must be LBM_F32 or LBM_F64");
     if (p->collision < LBM_SRT || p->collision > LBM_MRT) return std::string("collision must be SRT, TRT or MRT");
-    if (p->semantics != LBM_SEM_MRT_PY && p->semantics != LBM_SEM_MRT_GPU) return std::string("bad semantics");
+    if (p->semantics != LBM_SEM_MRT_PY && p->semantics != LBM_SEM_MRT_GPU && p->semantics != LBM_SEM_BOUNCE_BACK) return std::string("bad semantics");
     if (p->turb != 0 && p->turb != 1) return std::string("turb must be 0 or 1");
     if (p->turb == 1 && p->semantics != LBM_SEM_MRT_GPU) return std::string("turb = 1 (Smagorinsky, MRT_GPU.py:368-387) exists only with MRT_GPU semantics");
     if (p->kernel < LBM_KERNEL_AUTO || p->kernel > LBM_KERNEL_STREAM) return std::string("bad kernel variant");
@@ -158,6 +158,17 @@ std::string validate_params(const lbm_params* p) {
                            "MRT.py semantics is NumPy fp64)");
     if (p->arith == LBM_ARITH_PROMOTED && (p->flags & LBM_FLAG_STREAM_PAIRS))
         return std::string("arith = promoted does not run on the streaming kernel with two rows per wave (LBM_FLAG_STREAM_PAIRS)");
+    if (p->semantics == LBM_SEM_BOUNCE_BACK) {
+        // half-way bounce-back lives in the gather of the single-step operators and of the frame passes (lbm_device.hpp); the kernels
+        // with walls of their own (push scheme, vector rows, the streaming kernels with the walls inside) know only the wet-node rules
+        if (p->arith == LBM_ARITH_PROMOTED)
+            return std::string("arith = promoted (MRT_GPU.py's CUDA text) does not exist with bounce-back walls (LBM_SEM_BOUNCE_BACK)");
+        if (p->kernel == LBM_KERNEL_PUSH || p->kernel == LBM_KERNEL_VEC)
+            return std::string("kernel = PUSH / VEC have MRT_GPU.py's wall rules built in: bounce-back walls (LBM_SEM_BOUNCE_BACK) run GENERIC, TB or STREAM");
+        if (p->flags & (LBM_FLAG_STREAM_WALLS | LBM_FLAG_STREAM_PAIRS))
+            return std::string("LBM_FLAG_STREAM_WALLS / STREAM_PAIRS: the streaming kernels with the walls inside have MRT_GPU.py's wall rules built in, "
+                               "bounce-back walls (LBM_SEM_BOUNCE_BACK) run with the wall frame");
+    }
     if (p->batch > 1 && (p->y0 != 0 || p->ny_local != p->ny)) return std::string("a batch of lattices cannot be slab-decomposed");
     if (p->ny_local_min < 0 || p->ny_local_min > p->ny_local) return std::string("ny_local_min must be 0 or the smallest ny_local of all ranks (<= ny_local)");
     if (p->tb_steps != 0 && (p->tb_steps < 2 || p->tb_steps > SP_MAX_S)) return std::string("tb_steps must be 0 (default) or 2 .. " + std::to_string(SP_MAX_S));
@@ -289,7 +300,8 @@ static std::string plan_steps(lbm_ctx* c) {
         // inwards as plain pull-and-collide cells: with MRT_GPU.py's full streaming windows every cell but the wall cells
         // themselves is one (in_window), so F >= S; MRT.py's truncated windows leave kept slots in the cell next to the right /
         // bottom wall too, so F >= S + 1.
-        const int fmin = p->semantics == LBM_SEM_MRT_GPU ? 0 : 1;
+        // (bounce-back: every cell but the perimeter cells is a plain one too, F >= S)
+        const int fmin = p->semantics == LBM_SEM_MRT_PY ? 1 : 0;
         c->tb_f = (c->tb_steps + fmin + 3) / 4 * 4;
         while (c->tb_steps > 2 && (p->nx < 2 * c->tb_f + 16 || nyp < 2 * c->tb_f + 16)) {   // (tiny lattices: keep an interior)
             c->tb_steps -= 1;
@@ -303,7 +315,7 @@ static std::string plan_steps(lbm_ctx* c) {
         if (c->kern == Kern::stream_walls && is_slab(c) && c->tb_steps < 3) c->kern = Kern::stream;
         // (with the walls inside the tails stay on the streaming kernel: the tile kernel's four steps are no faster any more -- 247 against 256
         // GLUPS fast, 223 / 225 strict -- and the change of kernel inside a call costs: the driver's 20 steps, repeated, 337 -> 371 GLUPS)
-        c->tail_tiles = c->kern == Kern::stream && !is_slab(c) && c->es == 4 && p->semantics == LBM_SEM_MRT_GPU && !(p->flags & LBM_FLAG_NO_TAIL_TILES);
+        c->tail_tiles = c->kern == Kern::stream && !is_slab(c) && c->es == 4 && p->semantics != LBM_SEM_MRT_PY && !(p->flags & LBM_FLAG_NO_TAIL_TILES);
         return std::string();
     }
     // Steps per launch: the in-place LDS tile kernel with S = 4 (fp32) or 3 (fp64), also with the Smagorinsky closure (its
@@ -410,6 +422,8 @@ lbm_ctx* plan_ctx(const lbm_params* p, int ncu, bool device, std::string& err_ou
     c->edge_first = !(p->flags & LBM_FLAG_NO_EDGE_FIRST);
     c->edge_reserve = !(p->flags & LBM_FLAG_NO_EDGE_RESERVE);
     c->xcd_bands = !(p->flags & LBM_FLAG_NO_XCD_BANDS);
+    // (bounce-back slabs exchange one row per frame pass, as MRT.py semantics: the recomputed band of the neighbour's rows is not
+    // implemented for its gather)
     c->deep_halo = p->semantics == LBM_SEM_MRT_GPU && !(p->flags & LBM_FLAG_NO_DEEP_HALO);
     c->use_nt = (p->flags & LBM_FLAG_NT_ON) ? true : (p->flags & LBM_FLAG_NT_OFF) ? false : (c->lat_bytes > ((size_t)192 << 20));
     c->lazy_lag = !(p->flags & LBM_FLAG_EAGER_LAG);
@@ -453,10 +467,12 @@ int lbm_describe(const lbm_ctx* c, char* buf, size_t len) {
     for (int i = 0; i < NLAT; ++i) nlat += c->lat[i] ? 1 : 0;
     const int n = std::snprintf(buf, len, "kernel=%s steps_per_launch=%d frame=%d stream=%d vec=%d nt=%d deep_halo=%d frame_fused=%d lazy_lag=%d "
                                 "layout=%s workgroups=%lld wave_updates=%lld cells_per_lane=%d slab=%d frame_beside=%d frame_seg=%d "
-                                "lattices=%d lattice_bytes=%lld",
+                                "lattices=%d lattice_bytes=%lld%s",
                                 names[(int)c->kern], S, c->kern != Kern::none ? (walls_inside(c) && !is_slab(c) ? 0 : c->tb_f) : 0, streaming(c) ? 1 : 0, c->use_vec ? 1 : 0, c->use_nt ? 1 : 0, c->deep_halo ? 1 : 0,
                                 c->frame_fused ? 1 : 0, c->lazy_lag ? 1 : 0, c->geo.row != c->geo.pitch ? "rows" : "planes", wgs, wave_updates, V,
-                                is_slab(c) ? 1 : 0, c->frame_beside ? 1 : 0, c->frame_seg, nlat, (long long)c->lat_bytes);
+                                is_slab(c) ? 1 : 0, c->frame_beside ? 1 : 0, c->frame_seg, nlat, (long long)c->lat_bytes,
+                                // (the wall model, where it is not one of the two wet-node semantics whose plans predate the field)
+                                c->p.semantics == LBM_SEM_BOUNCE_BACK ? " semantics=bounce_back" : "");
     return n < 0 ? LBM_ERR_INVALID : (n >= (int)len ? (int)len - 1 : n);
 }
 

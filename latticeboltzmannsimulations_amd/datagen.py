@@ -24,12 +24,15 @@ import numpy as np
 from .solver import CavityBatch
 
 
-def _solve_batch(idx, Re_range, xsize, ysize, RT, turb, uLB, maxIt, Pinterval, tolerance, device, dtype, say, out, arith, convergence="host"):
+def _solve_batch(idx, Re_range, xsize, ysize, RT, turb, uLB, maxIt, Pinterval, tolerance, device, dtype, say, out, arith, convergence="host",
+                 semantics="mrt_gpu"):
     """Runs the lattices Re_range[idx] in lock step; fills out = (f_final, u_final, its) rows idx.  The per-lattice logic is
     the reference's loop body (MRT_GPU_datagen.py:707-731,862-871): a check after iteration It = 0, Pinterval, 2 Pinterval, ...
     (i.e. after It + 1 steps), `count` consecutive-or-not hits of |mean(u) - mean(u_past)| / uLB < tolerance, stop at count > 5."""
     f_final, u_final, its = out
-    with CavityBatch(xsize, ysize, [float(Re_range[i]) for i in idx], RT=RT, uLB=uLB, dtype=dtype, turb=turb, device=device, arith=arith) as b:
+    sem = {} if semantics == "mrt_gpu" else {"semantics": semantics}
+    with CavityBatch(xsize, ysize, [float(Re_range[i]) for i in idx], RT=RT, uLB=uLB, dtype=dtype, turb=turb, device=device, arith=arith,
+                     **sem) as b:
         feq_initial = b.get_fields(want_fin=True, out_dtype=np.float32)[2][0]      # fin = equ(1, InitVel) = feq_initial
         count = [0] * len(idx)
         past = [0.0] * len(idx)
@@ -74,8 +77,15 @@ def _solve_batch(idx, Re_range, xsize, ysize, RT, turb, uLB, maxIt, Pinterval, t
 
 def generate(Re_range=None, xsize=32 * 12, ysize=32 * 12, RT="SRT", turb=1, uLB=0.08, maxIt=3000000, Pinterval=10000,
              tolerance=0.0000001, OutputFolder="./output", save=True, concurrent=64, devices=(0,), dtype=np.float32,
-             quiet=False, arith="strict", convergence="host"):
-    """Returns (feq_initial, f_final, u_final, Re_range, iterations_per_Re); writes the four .npy files when `save`."""
+             quiet=False, arith="strict", convergence="host", BC="EB-NEBB "):
+    """Returns (feq_initial, f_final, u_final, Re_range, iterations_per_Re); writes the four .npy files when `save`.
+    BC: 'EB-NEBB ' (default, the wet-node walls of MRT_GPU.py) or 'BB' (half-way bounce-back, semantics='bounce_back': the
+    cavity's mass is conserved to rounding; needs turb=0)."""
+    if BC.strip() not in ("EB-NEBB", "BB"):
+        raise ValueError("BC must be 'EB-NEBB ' or 'BB'")
+    semantics = "bounce_back" if BC.strip() == "BB" else "mrt_gpu"
+    if semantics == "bounce_back" and turb:
+        raise ValueError("BC='BB' runs without the Smagorinsky closure: pass turb=0")
     say = (lambda *a: None) if quiet else print
     Re_range = np.arange(100, 5100, 10) if Re_range is None else np.asarray(Re_range)   # MRT_GPU_datagen.py:55
     n = len(Re_range)
@@ -86,7 +96,7 @@ def generate(Re_range=None, xsize=32 * 12, ysize=32 * 12, RT="SRT", turb=1, uLB=
 
     def work(k):
         return _solve_batch(chunks[k], Re_range, xsize, ysize, RT, turb, uLB, maxIt, Pinterval, tolerance,
-                            devices[k % len(devices)], dtype, say, out, arith, convergence)
+                            devices[k % len(devices)], dtype, say, out, arith, convergence, semantics)
     if len(devices) > 1 and len(chunks) > 1:
         with ThreadPoolExecutor(max_workers=len(devices)) as pool:      # lbm_step runs in C with the GIL released
             feq = list(pool.map(work, range(len(chunks))))
@@ -118,9 +128,12 @@ def main(argv=None):
                     help="fast: agrees with strict to rounding, ~1.3x faster; promoted: MRT_GPU.py's CUDA text arithmetic (fp32)")
     ap.add_argument("--convergence", choices=["host", "device"], default="host",
                     help="device: the convergence test on lbm_mean_u (reduced on the GPU) instead of the downloaded field")
+    ap.add_argument("--BC", choices=["EB-NEBB", "BB"], default="EB-NEBB",
+                    help="wall model: EB-NEBB wet-node walls (with the Smagorinsky closure), or BB half-way bounce-back (without it)")
     a = ap.parse_args(argv)
+    bb = dict(BC="BB", turb=0) if a.BC == "BB" else {}
     generate(np.arange(*a.Re), xsize=a.size, ysize=a.size, concurrent=a.concurrent, Pinterval=a.Pinterval, maxIt=a.maxIt,
-             OutputFolder=a.OutputFolder, arith=a.arith, convergence=a.convergence)
+             OutputFolder=a.OutputFolder, arith=a.arith, convergence=a.convergence, **bb)
     return 0
 
 

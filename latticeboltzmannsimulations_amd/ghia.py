@@ -147,18 +147,44 @@ TYPOS = (("uy", 400, 2), ("ux", 3200, 9), ("ux", 10000, 8))
 PAPER_MISPRINTS = (("uy", 400, 5),)
 
 
-def profile_errors(u, Re, uLB, mask_typos=False):
+def _walls(walls):
+    if walls not in ("nodes", "halfway"):
+        raise ValueError("walls must be 'nodes' or 'halfway'")
+    return walls == "halfway"
+
+
+def _halfway_centrelines(u, uLB):
+    """u_x on the vertical and u_y on the horizontal centreline x = 0.5 / y = 0.5 of a lattice whose walls sit half a cell outside it:
+    the middle column (row) of an odd size, the mean of the two middle ones of an even size."""
+    _, X, Y = u.shape
+    ux = u[0, X // 2, :] if X % 2 else 0.5 * (u[0, X // 2 - 1, :] + u[0, X // 2, :])
+    uy = u[1, :, Y // 2] if Y % 2 else 0.5 * (u[1, :, Y // 2 - 1] + u[1, :, Y // 2])
+    return ux / uLB, uy / uLB
+
+
+def profile_errors(u, Re, uLB, mask_typos=False, walls="nodes"):
     """Geometrically consistent comparison with Ghia (not in the reference): the lattice node
     (x, y) sits at (x/(X-1), 1 - y/(Y-1)); linear interpolation of the LBM centrelines at the
     Ghia sample positions.  Returns (max |dUx|, max |dUy|) in lid-velocity units; mask_typos leaves
-    out the table entries listed in TYPOS and PAPER_MISPRINTS."""
+    out the table entries listed in TYPOS and PAPER_MISPRINTS.
+    walls='halfway' (semantics='bounce_back': the walls half a cell outside the lattice): cell x sits at (x + 0.5)/X, row y at
+    height 1 - (y + 0.5)/Y, the centrelines are taken at x = 0.5 / y = 0.5 (_halfway_centrelines), and the walls' own velocities
+    (u_x = 1 on the lid, 0 on the bottom; u_y = 0 on the side walls) close the interpolation between the outermost cells and the walls."""
     _, X, Y = u.shape
     Yg, Uxg, Xg, Uyg = ghia_profiles(Re)
-    ux, uy = centrelines(u.astype(np.float64), uLB)
-    height = 1.0 - np.arange(Y) / (Y - 1.0)            # decreasing in y
+    if _walls(walls):
+        ux, uy = _halfway_centrelines(u.astype(np.float64), uLB)
+        height = np.concatenate(([1.0], 1.0 - (np.arange(Y) + 0.5) / Y, [0.0]))
+        ux = np.concatenate(([1.0], ux, [0.0]))
+        xs = np.concatenate(([0.0], (np.arange(X) + 0.5) / X, [1.0]))
+        uy = np.concatenate(([0.0], uy, [0.0]))
+    else:
+        ux, uy = centrelines(u.astype(np.float64), uLB)
+        height = 1.0 - np.arange(Y) / (Y - 1.0)            # decreasing in y
+        xs = np.arange(X) / (X - 1.0)
     ux_i = np.interp(Yg, height[::-1], ux[::-1])
     # cy = +1 populations move towards y - 1, i.e. towards the lid: u[1] > 0 is Ghia's v > 0
-    uy_i = np.interp(Xg, np.arange(X) / (X - 1.0), uy)
+    uy_i = np.interp(Xg, xs, uy)
     kx, ky = np.ones(len(Yg), bool), np.ones(len(Xg), bool)
     if mask_typos:
         for col, re_, row in TYPOS + PAPER_MISPRINTS:
@@ -185,16 +211,21 @@ def nearest_vortex_error(loc, Re, X, Y):
     return float(d[i]), i
 
 
-def primary_vortex_error(u, Re, uLB):
+def primary_vortex_error(u, Re, uLB, walls="nodes"):
     """(dx, dy) between the minimum of |u|^2 inside the central box 0.25 .. 0.75 of the cavity -- the primary vortex; not in the
     reference, whose two-minima search does not tell the vortices apart -- and the `Primary` row of Ghia's vortex table (VORTEX_GHIA
-    rows 0 / 7; MRT.py:105,113-116), in the reference's plot coordinates."""
+    rows 0 / 7; MRT.py:105,113-116), in the reference's plot coordinates.  walls='halfway': the cell (x, y) sits at
+    ((x + 0.5)/X, 1 - (y + 0.5)/Y) (see profile_errors)."""
+    halfway = _walls(walls)
     _, X, Y = u.shape
     usq = u[0].astype(np.float64) ** 2 + u[1].astype(np.float64) ** 2
     box = np.full_like(usq, np.inf)
     x0, x1, y0, y1 = X // 4, X - X // 4, Y // 4, Y - Y // 4
     box[x0:x1, y0:y1] = usq[x0:x1, y0:y1]
     loc = np.unravel_index(np.argmin(box), box.shape)
-    px, py = vortex_position(loc, X, Y)
+    if halfway:
+        px, py = (loc[0] + 0.5) / X, 1.0 - (loc[1] + 0.5) / Y
+    else:
+        px, py = vortex_position(loc, X, Y)
     j = _col(Re)
     return px - VORTEX_GHIA[0, j], py - VORTEX_GHIA[7, j]

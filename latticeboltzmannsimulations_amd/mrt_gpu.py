@@ -112,7 +112,7 @@ def _dashboard(path, u, rho, It, hist, Re, RT, regime, BC, xsize, ysize, uLB, re
 def run_cavity(maxIt=3000000, Re=10000.0, RT="SRT", turb=1, xsize=32 * 5, ysize=32 * 5, uLB=0.08,
                Pinterval=3000, SavePlot=True, SaveVTK=False, project="ldc", OutputFolder="./output",
                dtype=np.float32, semantics="mrt_gpu", device=0, quiet=False, solver_factory=None, arith="strict",
-               convergence="host", vtk_correct=False):
+               convergence="host", vtk_correct=False, BC="EB-NEBB "):
     """Run the lid-driven cavity like MRT_GPU.py does; returns a :class:`CavityResult`.
 
     Argument names and defaults are the module constants of MRT_GPU.py:38-58.
@@ -122,9 +122,21 @@ def run_cavity(maxIt=3000000, Re=10000.0, RT="SRT", turb=1, xsize=32 * 5, ysize=
     convergence: 'host' (default) -- the reference's test as written, on NumPy's float32 mean of the downloaded u
     (MRT_GPU.py:883-889); 'device' -- the same test on lbm_mean_u(), the mean reduced on the GPU in double (8 bytes cross
     PCIe instead of the field; the two means differ in the last bits of a float, so a run may stop one check apart).
-    vtk_correct: write the .vtr files as point data (VTKWrapper.saveToVTK(correct=True)) instead of the reference's layout."""
+    vtk_correct: write the .vtr files as point data (VTKWrapper.saveToVTK(correct=True)) instead of the reference's layout.
+    BC: the wall model, the two options of MRT_GPU.py:281 -- 'EB-NEBB ' (default: the wet-node walls of `semantics`) or 'BB'
+    (half-way bounce-back with the moving-lid term: semantics='bounce_back', which BC='BB' selects; no Smagorinsky closure, turb=0)."""
     if convergence not in ("host", "device"):
         raise ValueError("convergence must be 'host' or 'device'")
+    if BC.strip() not in ("EB-NEBB", "BB"):
+        raise ValueError("BC must be 'EB-NEBB ' or 'BB'")
+    if BC.strip() == "BB":
+        if semantics not in ("mrt_gpu", "bounce_back"):
+            raise ValueError(f"BC='BB' selects semantics='bounce_back', not {semantics!r}")
+        if turb:
+            raise ValueError("BC='BB' runs without the Smagorinsky closure: pass turb=0")
+        semantics = "bounce_back"
+    elif semantics == "bounce_back":
+        raise ValueError("semantics='bounce_back' is BC='BB'")
     say = (lambda *a: None) if quiet else print
     tstart = timer()
     say("the value of uLB is ", uLB)
@@ -154,7 +166,7 @@ def run_cavity(maxIt=3000000, Re=10000.0, RT="SRT", turb=1, xsize=32 * 5, ysize=
     grid = (np.arange(0, xsize, dtype="float64"), np.arange(0, ysize, dtype="float64"), np.arange(0, 1, dtype="float64"))
     velZ = np.zeros((xsize, ysize, 1), dtype=np.float32)   # same dtype as the float32 host fields (MRT_GPU.py:207)
     regime = "Laminar" if turb == 1 else "Turbulent"   # labels exactly as (mis)assigned at MRT_GPU.py:277-280
-    BC = "EB-NEBB "
+    BC = "BB" if semantics == "bounce_back" else "EB-NEBB "   # (the dashboard's label; MRT_GPU.py:281 spells the default so)
     res = CavityResult()
     u = np.zeros((2, xsize, ysize), dtype=np.float32)
     mean_past = 0.0
@@ -236,6 +248,8 @@ def main(argv=None):
     ap.add_argument("--OutputFolder", default="./output")
     ap.add_argument("--dtype", choices=["float32", "float64"], default="float32")
     ap.add_argument("--semantics", choices=["mrt_gpu", "mrt_py"], default="mrt_gpu")
+    ap.add_argument("--BC", choices=["EB-NEBB", "BB"], default="EB-NEBB",
+                    help="wall model (MRT_GPU.py:281): EB-NEBB wet-node walls, or BB half-way bounce-back (needs --turb 0)")
     ap.add_argument("--arith", choices=["strict", "fast", "promoted"], default="strict")
     ap.add_argument("--convergence", choices=["host", "device"], default="host")
     ap.add_argument("--vtk-correct", action="store_true", help="write .vtr point data (consistent file) instead of the reference's layout")
@@ -243,7 +257,7 @@ def main(argv=None):
     r = run_cavity(maxIt=a.maxIt, Re=a.Re, RT=a.RT, turb=a.turb, xsize=a.xsize, ysize=a.ysize, uLB=a.uLB,
                    Pinterval=a.Pinterval, SavePlot=not a.no_plot, SaveVTK=a.vtk, project=a.project,
                    OutputFolder=a.OutputFolder, dtype=np.dtype(a.dtype), semantics=a.semantics, arith=a.arith,
-                   convergence=a.convergence, vtk_correct=a.vtk_correct)
+                   convergence=a.convergence, vtk_correct=a.vtk_correct, BC="BB" if a.BC == "BB" else "EB-NEBB ")
     print("MLUPS : ", r.mlups)
     return 0
 

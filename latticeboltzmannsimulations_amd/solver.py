@@ -10,7 +10,7 @@ from . import _lib as L
 
 _DT = {np.dtype(np.float32): L.LBM_F32, np.dtype(np.float64): L.LBM_F64}
 _COLL = {"SRT": L.LBM_SRT, "TRT": L.LBM_TRT, "MRT": L.LBM_MRT}
-_SEM = {"mrt_py": L.LBM_SEM_MRT_PY, "mrt_gpu": L.LBM_SEM_MRT_GPU}
+_SEM = {"mrt_py": L.LBM_SEM_MRT_PY, "mrt_gpu": L.LBM_SEM_MRT_GPU, "bounce_back": L.LBM_SEM_BOUNCE_BACK}
 _KERNEL = {"auto": L.LBM_KERNEL_AUTO, "generic": L.LBM_KERNEL_GENERIC, "vec": L.LBM_KERNEL_VEC, "tb": L.LBM_KERNEL_TB,
            "push": L.LBM_KERNEL_PUSH, "stream": L.LBM_KERNEL_STREAM}
 _ARITH = {"strict": L.LBM_ARITH_STRICT, "fast": L.LBM_ARITH_FAST, "promoted": L.LBM_ARITH_PROMOTED}
@@ -64,6 +64,9 @@ class CavitySolver:
     RT           : 'SRT' | 'TRT' | 'MRT' (MRT_GPU.py:48)
     semantics    : 'mrt_gpu' (full streaming windows + NEBB on four walls, MRT_GPU.py:412,674-692)
                    or 'mrt_py' (the CPU script's windows and wall rules, MRT.py:404-453)
+                   or 'bounce_back' (half-way bounce-back walls with Ladd's moving-lid term, the reference's 'BB' option,
+                   MRT_GPU.py:281: every cell is a fluid cell, walls half a cell outside the lattice, mass conserved to rounding;
+                   relaxation rates as 'mrt_gpu'; kernels 'auto' / 'generic' / 'tb' / 'stream', arith 'strict' / 'fast', turb=0)
     dtype        : float32 (what MRT_GPU.py stores, MRT_GPU.py:207) or float64 (what MRT.py computes in)
     rows         : (y0, ny_local) when this object holds only a slab
     kernel       : 'auto' | 'generic' (one thread per cell) | 'vec' (16 B per access, MRT_GPU.py semantics) |
@@ -96,7 +99,7 @@ class CavitySolver:
         if RT not in _COLL:
             raise ValueError("RT must be 'SRT', 'TRT' or 'MRT'")
         if semantics not in _SEM:
-            raise ValueError("semantics must be 'mrt_gpu' or 'mrt_py'")
+            raise ValueError("semantics must be 'mrt_gpu', 'mrt_py' or 'bounce_back'")
         if omega_eps is None:
             omega_eps = 1.0 if semantics == "mrt_py" else 1.2      # MRT.py:72 vs MRT_GPU.py:90
         if omega_q is None:

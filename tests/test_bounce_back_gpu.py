@@ -1,0 +1,203 @@
+"""GPU tests of the half-way bounce-back walls (semantics='bounce_back', LBM_SEM_BOUNCE_BACK): strict arithmetic bit for bit against
+the NumPy reference tests/bounce_back_ref.py on every kernel that takes the semantics (generic, tb, stream), batches, slabs and
+checkpoints bit for bit against the lone whole lattice, `fast` arithmetic within a bound, and the physics of the wall model (Ghia
+centrelines at the half-way positions, mass)."""
+import os
+import sys
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+from bounce_back_ref import BounceBackOracle  # noqa: E402
+from latticeboltzmannsimulations_amd import CavityBatch, CavitySolver, ghia  # noqa: E402
+from latticeboltzmannsimulations_amd.slab import LocalSlabs, partition_rows  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+BB = dict(semantics="bounce_back")
+
+
+def _perturbed(nx, ny, dtype, seed):
+    """A non-trivial state for set_state: equilibrium-like populations with a seeded perturbation of a few per cent."""
+    rng = np.random.default_rng(seed)
+    t = np.array([4 / 9] + [1 / 9] * 4 + [1 / 36] * 4)
+    return (t[:, None, None] * (1.0 + 0.03 * rng.standard_normal((9, nx, ny)))).astype(dtype)
+
+
+def _same(s, o, what):
+    u, rho, fin = s.get_fields(want_fin=True)
+    assert np.array_equal(fin, o.fin), f"{what}: fin differs, max abs {np.abs(fin - o.fin).max()}"
+    assert np.array_equal(rho, o.rho), f"{what}: rho differs"
+    assert np.array_equal(u, o.u), f"{what}: u differs"
+
+
+# kernel -> lattices: the frame and the tiles' ragged edges (tb: nx a multiple of the vector width; stream: nx, ny >= 64)
+SIZES = {"generic": [(70, 66), (128, 96)], "tb": [(128, 96), (200, 160)], "stream": [(200, 160), (256, 256)]}
+
+
+@pytest.mark.parametrize("kernel", ["generic", "tb", "stream"])
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+@pytest.mark.parametrize("coll", ["SRT", "TRT", "MRT"])
+def test_strict_bit_identical_to_reference(coll, dtype, kernel):
+    """1, 7 and 37 steps (not multiples of any launch unit) from the initial equilibrium, then from set_state of a perturbed state."""
+    for nx, ny in SIZES[kernel]:
+        Re = 100.0 if nx < 150 else 1000.0
+        o = BounceBackOracle(nx, ny, Re, collision=coll, dtype=dtype)
+        with CavitySolver(nx, ny, Re, RT=coll, dtype=dtype, kernel=kernel, **BB) as s:
+            assert s.describe()["semantics"] == "bounce_back"
+            for n in (1, 7, 37):
+                s.step(n); o.step(n)
+                _same(s, o, f"{nx}x{ny} {kernel} after {o.nsteps}")
+            f = _perturbed(nx, ny, dtype, nx * ny)
+            s.set_state(f); o.set_state(f)
+            for n in (1, 7, 37):
+                s.step(n); o.step(n)
+                _same(s, o, f"{nx}x{ny} {kernel} set_state + {o.nsteps}")
+
+
+@pytest.mark.parametrize("arith", ["strict", "fast"])
+def test_kernels_agree_at_4096(arith):
+    """4096^2 fp32 MRT: the one-step kernel, the tile kernel and the streaming kernel (with the wall frame) give the same bits."""
+    want = None
+    for kernel in ("generic", "tb", "stream"):
+        with CavitySolver(4096, 4096, 1000.0, RT="MRT", dtype=np.float32, arith=arith, kernel=kernel, **BB) as s:
+            s.step(1); s.step(19)
+            got = s.get_fields(want_fin=True)
+        if want is None:
+            want = got
+            continue
+        for a, b, name in zip(want, got, ("u", "rho", "fin")):
+            assert np.array_equal(a, b), f"{kernel} {arith}: {name} differs from generic"
+        del got
+
+
+@pytest.mark.parametrize("kernel", ["auto", "tb"])
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+def test_batch_of_mixed_re_equals_lattices_alone(kernel, dtype):
+    Res = [100.0, 400.0, 1000.0, 3200.0]
+    with CavityBatch(128, 96, Res, RT="MRT", dtype=dtype, kernel=kernel, **BB) as b:
+        b.step(1); b.step(22)
+        u, rho, fin = b.get_fields(want_fin=True)
+    for i, Re in enumerate(Res):
+        with CavitySolver(128, 96, Re, RT="MRT", dtype=dtype, kernel=kernel, **BB) as s:
+            s.step(23)
+            u1, r1, f1 = s.get_fields(want_fin=True)
+        assert np.array_equal(fin[i], f1) and np.array_equal(u[i], u1) and np.array_equal(rho[i], r1), Re
+
+
+@pytest.mark.parametrize("kernel", ["generic", "tb", "stream"])
+@pytest.mark.parametrize("coll,dtype", [("MRT", np.float32), ("SRT", np.float64), ("TRT", np.float32)])
+def test_slabs_equal_the_whole_lattice(kernel, coll, dtype):
+    """Three slabs (first with the lid, middle, last with the bottom wall) whose halos are moved by the caller (LocalSlabs), against
+    the whole lattice, bit for bit; also from a perturbed state."""
+    nx, ny = 128, 3 * 70 + 1
+    parts = partition_rows(ny, 3)
+    mr = min(n for _, n in parts)
+    with CavitySolver(nx, ny, 400.0, RT=coll, dtype=dtype, kernel="generic", **BB) as whole:
+        slabs = [CavitySolver(nx, ny, 400.0, RT=coll, dtype=dtype, kernel=kernel, rows=r, min_rows=mr, **BB) for r in parts]
+        try:
+            drv = LocalSlabs(slabs)
+            for phase in range(2):
+                if phase:
+                    f = _perturbed(nx, ny, dtype, 7)
+                    whole.set_state(f)
+                    for sl in slabs:
+                        sl.set_state(f)
+                    drv = LocalSlabs(slabs)
+                for n in (1, 7, 37):
+                    whole.step(n); drv.step(n)
+                    uw, rw, fw = whole.get_fields(want_fin=True)
+                    u = np.zeros_like(uw); rho = np.zeros_like(rw); fin = np.zeros_like(fw)
+                    for sl in slabs:
+                        sl.get_fields(u=u, rho=rho, fin=fin)
+                    assert np.array_equal(fin, fw) and np.array_equal(u, uw) and np.array_equal(rho, rw), (phase, n)
+        finally:
+            for sl in slabs:
+                sl.close()
+
+
+def test_checkpoint_round_trip(tmp_path):
+    with CavitySolver(128, 96, 1000.0, RT="MRT", dtype=np.float32, **BB) as s:
+        s.step(25)
+        path = s.save_checkpoint(str(tmp_path / "bb"))
+        s.step(30)
+        want = s.get_fields(want_fin=True)
+    with CavitySolver(128, 96, 1000.0, RT="MRT", dtype=np.float32, **BB) as r:
+        assert r.load_checkpoint(path) == 25
+        r.step(30)
+        got = r.get_fields(want_fin=True)
+    assert all(np.array_equal(a, b) for a, b in zip(want, got))
+    with CavitySolver(128, 96, 1000.0, RT="MRT", dtype=np.float32) as nebb:
+        with pytest.raises(ValueError, match="semantics"):
+            nebb.load_checkpoint(path)
+
+
+# fast arithmetic against strict fp64 (the GPU's strict fp64 = the reference, bit for bit, test above): max |f_fast - f_ref| / max |f_ref|
+# over the populations after 2000 steps of a 128 x 96 lattice at Re 1000, every operator.  Measured (MI355X, FAST_MEASURED: the fp32
+# figures are mostly fp32's own distance from fp64); the bounds are the largest of each type with a factor of four of headroom, as
+# tests/test_arith_error_budget_gpu.py sets its bounds.
+FAST_MEASURED = {(np.float32, "SRT"): 2.940e-05, (np.float32, "TRT"): 2.956e-05, (np.float32, "MRT"): 1.616e-05,
+                 (np.float64, "SRT"): 1.419e-14, (np.float64, "TRT"): 1.476e-14, (np.float64, "MRT"): 2.920e-15}
+FAST_BOUND = {np.float32: 1.2e-4, np.float64: 6e-14}
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+@pytest.mark.parametrize("coll", ["SRT", "TRT", "MRT"])
+def test_fast_arithmetic_within_bound(coll, dtype):
+    with CavitySolver(128, 96, 1000.0, RT=coll, dtype=np.float64, kernel="generic", **BB) as ref:
+        ref.step(2000)
+        f_ref = ref.get_fields(want_fin=True)[2]
+    errs = []
+    for kernel in ("generic", "tb"):
+        with CavitySolver(128, 96, 1000.0, RT=coll, dtype=dtype, arith="fast", kernel=kernel, **BB) as s:
+            s.step(2000)
+            f = s.get_fields(want_fin=True, out_dtype=np.float64)[2]
+        errs.append(float(np.abs(f - f_ref).max() / np.abs(f_ref).max()))
+    print(f"fast {coll} {np.dtype(dtype).name}: {errs[0]:.3e}")
+    assert errs[0] == errs[1], "fast arithmetic differs between the kernels"
+    assert errs[0] < FAST_BOUND[dtype], errs
+
+
+def _converge(s, cap, every=3000):
+    prev, quiet = None, 0
+    while s.steps_done < cap and quiet <= 5:
+        s.step(every)
+        m = s.mean_u()
+        quiet = quiet + 1 if (prev is not None and abs(m - prev) / 0.08 < 1e-8) else 0
+        prev = m
+    u, rho, fin = s.get_fields(want_fin=True, out_dtype=np.float64)
+    return u, fin
+
+
+@pytest.mark.parametrize("Re,n,dtype,arith,kernel,cap,tol", [
+    (100, 128, np.float64, "strict", "auto", 600_000, 0.03),
+    (1000, 256, np.float32, "fast", "stream", 600_000, 0.05)])
+def test_converged_bounce_back_cavity(Re, n, dtype, arith, kernel, cap, tol):
+    """Run to the reference's convergence criterion (MRT_GPU.py:883-889, on the device mean; fp32 means do not settle to 1e-8, that run
+    stops at `cap`): the centrelines at the half-way positions against Ghia, the reference's own r2 metric, and the mass.
+    Measured (MI355X): Re 100, 128^2 fp64 strict -- 60 000 steps, profile errors 0.0065 / 0.0050, r2 0.944, mass drift 3.3e-12;
+    Re 1000, 256^2 fp32 fast, kernel stream -- 600 000 steps (cap), profile errors 0.0079 / 0.0078, r2 0.944, mass drift 3.9e-3 against
+    3.1e-3 for the wet-node walls of the same configuration.  The wall rule conserves mass exactly (fp64: 3e-12 after 60 000 steps); in
+    fp32 the collision's own rounding -- sum_k f*_k differs from sum_k f_k by an ulp or so per cell and step -- adds up over 600 000 steps
+    (at most ~6e5 x 2^-24 = 0.036), and that is what both fp32 figures show.  The expectation that fp32 bounce-back drifts 10x less
+    than the wet-node walls therefore does not hold; the fp32 assertion bounds the rounding drift instead and records the comparison."""
+    with CavitySolver(n, n, float(Re), RT="MRT", dtype=dtype, arith=arith, kernel=kernel, **BB) as s:
+        u, fin = _converge(s, cap)
+        steps = s.steps_done
+    ex, ey = ghia.profile_errors(u, Re, 0.08, walls="halfway")
+    r2 = ghia.r2_value(u, Re, 0.08)
+    drift = abs(fin.sum() - n * n) / (n * n)
+    print(f"BB Re {Re} {n}^2 {np.dtype(dtype).name} {arith}: steps {steps}, profile errors {ex:.4f} {ey:.4f}, r2 {r2:.4f}, mass drift {drift:.3e}")
+    assert ex < tol and ey < tol, (ex, ey, steps)
+    assert r2 > 0.9
+    if dtype == np.float64:
+        assert drift < 1e-10, drift
+    else:
+        with CavitySolver(n, n, float(Re), RT="MRT", dtype=dtype, arith=arith, kernel=kernel) as w:
+            w.step(steps)
+            _, _, fw = w.get_fields(want_fin=True, out_dtype=np.float64)
+        nebb = abs(fw.sum() - n * n) / (n * n)
+        print(f"  NEBB mass drift over the same {steps} steps: {nebb:.3e}")
+        assert drift < 1e-2, (drift, nebb)

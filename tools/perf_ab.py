@@ -4,7 +4,7 @@
     python tools/perf_ab.py [--steps 600] [--reps 3] case [case ...]
 
 A case is  size:dtype:arith[:key=value,...]  e.g.  4096:f32:fast   4096:f32:strict:tb_steps=4   8192x1024:f64:fast:coll=SRT,turb=1
-(keys: coll, turb, kernel, layout and every CavitySolver tuning switch).  Prints GLUPS (best of --reps timings of --steps steps
+(keys: coll, turb, kernel, layout, sem (semantics: mrt_gpu, mrt_py, bounce_back) and every CavitySolver tuning switch).  Prints GLUPS (best of --reps timings of --steps steps
 after a device wake-up and a warm-up) and microseconds per step, one line per case.
 """
 import argparse
@@ -30,6 +30,8 @@ def parse(case):
                 kw["RT"] = v
             elif k in ("kernel", "layout"):
                 kw[k] = v
+            elif k == "sem":
+                kw["semantics"] = v
             elif k == "turb":
                 kw["turb"] = int(v)
             elif k in ("tb_steps", "frame_seg"):
