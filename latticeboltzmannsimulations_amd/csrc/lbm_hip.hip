@@ -98,97 +98,56 @@ int stage_to_host(lbm_ctx* c, const void* stage, void* host, int host_dtype, int
 // grid of the host-layout <-> lattice kernels: tiles of trx<R>() columns x 32 rows
 template <typename R>
 dim3 grid_tiles(const lbm_ctx* c) { return dim3((c->geo.nx + trx<R>() - 1) / trx<R>(), (c->geo.ny + 31) / 32, c->batch); }
-// arith = promoted in fp32: the k_*_prom twins of the kernels that form an equilibrium outside the collision (fp64 promoted = strict)
-inline bool promoted_f32(const lbm_ctx* c) { return c->p.dtype == LBM_F32 && c->p.arith == LBM_ARITH_PROMOTED; }
 
-template <typename R>
-int export_fin_t(lbm_ctx* c) {
-    const dim3 g = grid_tiles<R>(c);
-    const R* src = (const R*)c->lat[c->cur];
-    if constexpr (std::is_same<R, float>::value)
-        if (promoted_f32(c)) {
-            hipLaunchKernelGGL((k_export_fin_prom<R>), g, dim3(BLK), 0, c->s_compute, src, c->geo, c->raw[c->cur], (R)c->p.uLB, (R*)c->stage, c->bstride);
-            HIP_TRY(c, hipGetLastError());
-            return LBM_OK;
-        }
-    if (c->p.semantics == LBM_SEM_MRT_PY)
-        hipLaunchKernelGGL((k_export_fin<R, SEM_PY>), g, dim3(BLK), 0, c->s_compute, src, c->geo, c->raw[c->cur], (R)c->p.uLB, (R*)c->stage, c->bstride);
-    else if (c->p.semantics == LBM_SEM_BOUNCE_BACK)
-        hipLaunchKernelGGL((k_export_fin<R, SEM_BB>), g, dim3(BLK), 0, c->s_compute, src, c->geo, c->raw[c->cur], (R)c->p.uLB, (R*)c->stage, c->bstride);
-    else
-        hipLaunchKernelGGL((k_export_fin<R, SEM_GPU>), g, dim3(BLK), 0, c->s_compute, src, c->geo, c->raw[c->cur], (R)c->p.uLB, (R*)c->stage, c->bstride);
-    HIP_TRY(c, hipGetLastError());
-    return LBM_OK;
+int export_fin(lbm_ctx* c) {
+    return launch_variant(c, [&](auto v) {
+        using VT = decltype(v);
+        using R = typename VT::R;
+        hipLaunchKernelGGL((k_export_fin<R, VT::SEM, coll_is_prom(VT::COLL)>), grid_tiles<R>(c), dim3(BLK), 0, c->s_compute, (const R*)c->lat[c->cur],
+                           c->geo, c->raw[c->cur], (R)c->p.uLB, (R*)c->stage, c->bstride);
+    });
 }
 
-template <typename R>
-int export_macro_t(lbm_ctx* c) {
-    const dim3 g = grid_tiles<R>(c);
+int export_macro(lbm_ctx* c) {
     // the fields of the LAST iteration are the moments of the state that iteration started
     // from, i.e. of the previous lattice (prev_lattice: still intact after a single step, recomputed after a multi-step unit)
     int which = 0;
     int rc = prev_lattice(c, &which);
     if (rc) return rc;
-    const R* src = (const R*)c->lat[which];
-    if constexpr (std::is_same<R, float>::value)
-        if (promoted_f32(c)) {
-            hipLaunchKernelGGL((k_export_macro_prom<R>), g, dim3(BLK), 0, c->s_compute, src, c->geo, c->raw[which], (R)c->p.uLB, (R*)c->stage, c->bstride);
-            HIP_TRY(c, hipGetLastError());
-            return LBM_OK;
-        }
-    if (c->p.semantics == LBM_SEM_MRT_PY)
-        hipLaunchKernelGGL((k_export_macro<R, SEM_PY>), g, dim3(BLK), 0, c->s_compute, src, c->geo, c->raw[which], (R)c->p.uLB, (R*)c->stage, c->bstride);
-    else if (c->p.semantics == LBM_SEM_BOUNCE_BACK)
-        hipLaunchKernelGGL((k_export_macro<R, SEM_BB>), g, dim3(BLK), 0, c->s_compute, src, c->geo, c->raw[which], (R)c->p.uLB, (R*)c->stage, c->bstride);
-    else
-        hipLaunchKernelGGL((k_export_macro<R, SEM_GPU>), g, dim3(BLK), 0, c->s_compute, src, c->geo, c->raw[which], (R)c->p.uLB, (R*)c->stage, c->bstride);
-    HIP_TRY(c, hipGetLastError());
-    return LBM_OK;
+    return launch_variant(c, [&](auto v) {
+        using VT = decltype(v);
+        using R = typename VT::R;
+        hipLaunchKernelGGL((k_export_macro<R, VT::SEM, coll_is_prom(VT::COLL)>), grid_tiles<R>(c), dim3(BLK), 0, c->s_compute, (const R*)c->lat[which],
+                           c->geo, c->raw[which], (R)c->p.uLB, (R*)c->stage, c->bstride);
+    });
 }
 
-template <typename R>
-int export_tau_t(lbm_ctx* c) {
+// (MRT.py semantics with arith = fast runs the strict variant, so FAST is false there; that case has no closure (validate_params), and
+// either instantiation writes the same 1 / omega)
+int export_tau(lbm_ctx* c) {
     int which = 0;
     int rc = prev_lattice(c, &which);
     if (rc) return rc;
-    const R* src = (const R*)c->lat[which];
-    if constexpr (std::is_same<R, float>::value)
-        if (promoted_f32(c)) {
-            hipLaunchKernelGGL((k_export_tau_prom<R>), grid_tiles<R>(c), dim3(BLK), 0, c->s_compute, src, c->geo, c->raw[which], relax_of<R>(c->p), batch_of<R>(c), c->p.turb, (R*)c->stage);
-            HIP_TRY(c, hipGetLastError());
-            return LBM_OK;
-        }
-    if (c->p.arith == LBM_ARITH_FAST)
-        hipLaunchKernelGGL((k_export_tau<R, true>), grid_tiles<R>(c), dim3(BLK), 0, c->s_compute, src, c->geo, c->raw[which], relax_of<R>(c->p), batch_of<R>(c), c->p.turb, (R*)c->stage);
-    else
-        hipLaunchKernelGGL((k_export_tau<R, false>), grid_tiles<R>(c), dim3(BLK), 0, c->s_compute, src, c->geo, c->raw[which], relax_of<R>(c->p), batch_of<R>(c), c->p.turb, (R*)c->stage);
-    HIP_TRY(c, hipGetLastError());
-    return LBM_OK;
+    return launch_variant(c, [&](auto v) {
+        using VT = decltype(v);
+        using R = typename VT::R;
+        hipLaunchKernelGGL((k_export_tau<R, coll_is_fast(VT::COLL), coll_is_prom(VT::COLL)>), grid_tiles<R>(c), dim3(BLK), 0, c->s_compute,
+                           (const R*)c->lat[which], c->geo, c->raw[which], relax_of<R>(c->p), batch_of<R>(c), c->p.turb, (R*)c->stage);
+    });
 }
 
 constexpr int RED_BLOCKS = 1024;   // partial sums per lattice of lbm_mean_u
 
-template <typename R>
-int reduce_u_t(lbm_ctx* c) {
+int reduce_u(lbm_ctx* c) {
     int which = 0;
     int rc = prev_lattice(c, &which);
     if (rc) return rc;
-    const R* src = (const R*)c->lat[which];
-    const dim3 g(RED_BLOCKS, 1, c->batch);
-    if constexpr (std::is_same<R, float>::value)
-        if (promoted_f32(c)) {
-            hipLaunchKernelGGL((k_reduce_u_prom<R>), g, dim3(BLK), 0, c->s_compute, src, c->geo, c->raw[which], (R)c->p.uLB, c->bstride, c->red_dev);
-            HIP_TRY(c, hipGetLastError());
-            return LBM_OK;
-        }
-    if (c->p.semantics == LBM_SEM_MRT_PY)
-        hipLaunchKernelGGL((k_reduce_u<R, SEM_PY>), g, dim3(BLK), 0, c->s_compute, src, c->geo, c->raw[which], (R)c->p.uLB, c->bstride, c->red_dev);
-    else if (c->p.semantics == LBM_SEM_BOUNCE_BACK)
-        hipLaunchKernelGGL((k_reduce_u<R, SEM_BB>), g, dim3(BLK), 0, c->s_compute, src, c->geo, c->raw[which], (R)c->p.uLB, c->bstride, c->red_dev);
-    else
-        hipLaunchKernelGGL((k_reduce_u<R, SEM_GPU>), g, dim3(BLK), 0, c->s_compute, src, c->geo, c->raw[which], (R)c->p.uLB, c->bstride, c->red_dev);
-    HIP_TRY(c, hipGetLastError());
-    return LBM_OK;
+    return launch_variant(c, [&](auto v) {
+        using VT = decltype(v);
+        using R = typename VT::R;
+        hipLaunchKernelGGL((k_reduce_u<R, VT::SEM, coll_is_prom(VT::COLL)>), dim3(RED_BLOCKS, 1, c->batch), dim3(BLK), 0, c->s_compute,
+                           (const R*)c->lat[which], c->geo, c->raw[which], (R)c->p.uLB, c->bstride, c->red_dev);
+    });
 }
 }  // namespace lbmhost
 
@@ -292,13 +251,12 @@ int lbm_init_equilibrium(lbm_ctx* c) {
     if (rc) return rc;
     c->cur = 0; c->raw[0] = 1; c->raw[1] = 1; c->nsteps = 0; c->lag = 0; c->lag_valid = false; c->thin_valid = false;
     const dim3 g = grid_rows(c, c->geo.ny);
-    if (promoted_f32(c))
-        hipLaunchKernelGGL((k_init_prom<float>), g, dim3(BLK), 0, c->s_compute, (float*)c->lat[0], c->geo, (float)c->p.uLB, c->p.turb, c->bstride);
-    else if (c->p.dtype == LBM_F32)
-        hipLaunchKernelGGL((k_init<float>), g, dim3(BLK), 0, c->s_compute, (float*)c->lat[0], c->geo, (float)c->p.uLB, c->p.turb, c->bstride);
-    else
-        hipLaunchKernelGGL((k_init<double>), g, dim3(BLK), 0, c->s_compute, (double*)c->lat[0], c->geo, (double)c->p.uLB, c->p.turb, c->bstride);
-    HIP_TRY(c, hipGetLastError());
+    rc = launch_variant(c, [&](auto v) {
+        using VT = decltype(v);
+        using R = typename VT::R;
+        hipLaunchKernelGGL((k_init<R, coll_is_prom(VT::COLL)>), g, dim3(BLK), 0, c->s_compute, (R*)c->lat[0], c->geo, (R)c->p.uLB, c->p.turb, c->bstride);
+    });
+    if (rc) return rc;
     return push_reset(c);
 }
 
@@ -312,13 +270,13 @@ int lbm_set_state(lbm_ctx* c, const void* fin_host, int host_dtype) {
     rc = host_to_stage(c, fin_host, host_dtype, Q * c->batch);   // [B][9][nx][ny] is B * 9 planes
     if (rc) return rc;
     c->cur = 0; c->raw[0] = 1; c->raw[1] = 1; c->nsteps = 0; c->lag = 0; c->lag_valid = false; c->thin_valid = false;
-    if (promoted_f32(c))
-        hipLaunchKernelGGL((k_import_prom<float>), grid_tiles<float>(c), dim3(BLK), 0, c->s_compute, (const float*)c->stage, (float*)c->lat[0], c->geo, (float)c->p.uLB, c->p.turb, c->bstride);
-    else if (c->p.dtype == LBM_F32)
-        hipLaunchKernelGGL((k_import<float>), grid_tiles<float>(c), dim3(BLK), 0, c->s_compute, (const float*)c->stage, (float*)c->lat[0], c->geo, (float)c->p.uLB, c->p.turb, c->bstride);
-    else
-        hipLaunchKernelGGL((k_import<double>), grid_tiles<double>(c), dim3(BLK), 0, c->s_compute, (const double*)c->stage, (double*)c->lat[0], c->geo, (double)c->p.uLB, c->p.turb, c->bstride);
-    HIP_TRY(c, hipGetLastError());
+    rc = launch_variant(c, [&](auto v) {
+        using VT = decltype(v);
+        using R = typename VT::R;
+        hipLaunchKernelGGL((k_import<R, coll_is_prom(VT::COLL)>), grid_tiles<R>(c), dim3(BLK), 0, c->s_compute, (const R*)c->stage, (R*)c->lat[0], c->geo,
+                           (R)c->p.uLB, c->p.turb, c->bstride);
+    });
+    if (rc) return rc;
     rc = push_reset(c);
     if (rc) return rc;
     HIP_TRY(c, hipStreamSynchronize(c->s_compute));
@@ -366,7 +324,7 @@ int lbm_get_fields(lbm_ctx* c, void* u_host, void* rho_host, void* fin_host, int
     if (rc) return rc;
     const size_t hes = host_dtype == LBM_F32 ? 4 : 8;
     if (u_host || rho_host) {
-        rc = c->p.dtype == LBM_F32 ? export_macro_t<float>(c) : export_macro_t<double>(c);
+        rc = export_macro(c);
         if (rc) return rc;
         HIP_TRY(c, hipStreamSynchronize(c->s_compute));
         for (int b = 0; b < c->batch; ++b) {   // staging of lattice b: [ux | uy | rho]; host: u[B][2][nx][NY], rho[B][nx][NY]
@@ -377,7 +335,7 @@ int lbm_get_fields(lbm_ctx* c, void* u_host, void* rho_host, void* fin_host, int
         }
     }
     if (fin_host) {
-        rc = c->p.dtype == LBM_F32 ? export_fin_t<float>(c) : export_fin_t<double>(c);
+        rc = export_fin(c);
         if (rc) return rc;
         HIP_TRY(c, hipStreamSynchronize(c->s_compute));
         rc = stage_to_host(c, c->stage, fin_host, host_dtype, Q * c->batch);
@@ -395,7 +353,7 @@ int lbm_mean_u(lbm_ctx* c, double* mean_out) {
         hipError_t e = hipMalloc((void**)&c->red_dev, ((size_t)RED_BLOCKS + 1) * c->batch * sizeof(double));
         if (e != hipSuccess) return fail(c, LBM_ERR_NOMEM, std::string("hipMalloc(reduction): ") + hipGetErrorString(e));
     }
-    rc = c->p.dtype == LBM_F32 ? reduce_u_t<float>(c) : reduce_u_t<double>(c);
+    rc = reduce_u(c);
     if (rc) return rc;
     double* res = c->red_dev + (size_t)RED_BLOCKS * c->batch;
     const double scale = 1.0 / (2.0 * (double)c->geo.nx * (double)c->geo.ny);
@@ -414,7 +372,7 @@ int lbm_get_tau(lbm_ctx* c, void* tau_host, int host_dtype) {
     const size_t n = (size_t)c->geo.nx * c->geo.ny;
     rc = ensure_stage(c, (size_t)12 * n * c->es * c->batch);
     if (rc) return rc;
-    rc = c->p.dtype == LBM_F32 ? export_tau_t<float>(c) : export_tau_t<double>(c);
+    rc = export_tau(c);
     if (rc) return rc;
     HIP_TRY(c, hipStreamSynchronize(c->s_compute));
     return stage_to_host(c, c->stage, tau_host, host_dtype, c->batch);

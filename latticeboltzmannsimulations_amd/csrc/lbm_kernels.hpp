@@ -337,10 +337,9 @@ __global__ __launch_bounds__(BLK) void k_push_bc(const R* __restrict__ fin_old, 
     for (int k = 0; k < Q; ++k) fin_new[k * geo.plane + me] = g[k];
 }
 
-// init: raw populations = equ(rho = 1, u = (uLB on the global lid row, 0))  (MRT.py:260-268); PROM: the promoted equilibrium (k_init_prom,
-// arith = promoted; the host-layout kernels below have such twins too, at the end of this file)
+// init: raw populations = equ(rho = 1, u = (uLB on the global lid row, 0))  (MRT.py:260-268); PROM: the promoted equilibrium (arith = promoted)
 template <typename R, bool PROM>
-__device__ __forceinline__ void init_body(R* __restrict__ lat, Geo geo, R uLB, int turb, long long bstride) {
+__global__ __launch_bounds__(BLK) void k_init(R* __restrict__ lat, Geo geo, R uLB, int turb, long long bstride) {
     const int x = blockIdx.x * BLK + threadIdx.x;
     const int y = blockIdx.y;
     if (x >= geo.nx) return;
@@ -354,22 +353,16 @@ __device__ __forceinline__ void init_body(R* __restrict__ lat, Geo geo, R uLB, i
         lat[K_RHO * geo.plane + geo.at(x, y)] = (R)1;
     }
 }
-template <typename R>
-__global__ __launch_bounds__(BLK) void k_init(R* __restrict__ lat, Geo geo, R uLB, int turb, long long bstride) {
-    init_body<R, false>(lat, geo, uLB, turb, bstride);
-}
-template <typename R>
-__global__ __launch_bounds__(BLK) void k_init_prom(R* __restrict__ lat, Geo geo, R uLB, int turb, long long bstride) {
-    init_body<R, true>(lat, geo, uLB, turb, bstride);
-}
 
 // ---- host layout <-> lattice ---------------------------------------------------------------------------------------------
 // The staging buffers hold the reference's host layout ([plane][nx][ny_local], y fastest); the lattice is x fastest.  Each
 // workgroup moves a tile of TRX columns x 32 rows through LDS, so that both sides are accessed along their fast axis.
+// SEM, FAST, PROM: those of the context's Variant (dispatch); PROM: the equilibria formed here -- the history of an uploaded state,
+// the lid's wall rule in the gather -- and the Smagorinsky tau take the promoted form.
 template <typename R> constexpr int trx() { return sizeof(R) == 4 ? 32 : 16; }   // 9 planes x TRX x 33 reals = 38 KiB of LDS
 
 // staging -> raw lattice
-template <typename R>
+template <typename R, bool PROM>
 __global__ __launch_bounds__(BLK) void k_import(const R* __restrict__ stage, R* __restrict__ lat, Geo geo, R uLB, int turb, long long bstride) {
     constexpr int TRX = trx<R>(), RY = BLK / TRX;
     __shared__ R t[Q][TRX][33];
@@ -399,7 +392,7 @@ __global__ __launch_bounds__(BLK) void k_import(const R* __restrict__ stage, R* 
         if (turb) {   // history := equilibrium / density of the uploaded state (there is no "previous step")
             R rho, ux, uy, fe[Q];
             macros<R>(g, x, geo.y0 + y, geo.nx, geo.NY, uLB, rho, ux, uy);
-            equ<R>(rho, ux, uy, fe);
+            equ<R, PROM>(rho, ux, uy, fe);
             lat[K_QEQ * geo.plane + geo.at(x, y)] = diag_flux<R>(fe);
             lat[K_RHO * geo.plane + geo.at(x, y)] = rho;
         }
@@ -407,7 +400,7 @@ __global__ __launch_bounds__(BLK) void k_import(const R* __restrict__ stage, R* 
 }
 
 // lattice -> staging: current populations (post stream + wall rules) in host layout
-template <typename R, int SEM>
+template <typename R, int SEM, bool PROM>
 __global__ __launch_bounds__(BLK) void k_export_fin(const R* __restrict__ src, Geo geo, int raw, R uLB,
                                                     R* __restrict__ stage, long long bstride) {
     constexpr int TRX = trx<R>(), RY = BLK / TRX;
@@ -421,7 +414,7 @@ __global__ __launch_bounds__(BLK) void k_export_fin(const R* __restrict__ src, G
         const int y = y0 + ty;
         if (x >= geo.nx || y >= geo.ny) continue;
         R g[Q];
-        gather<R, SEM>(src, geo, raw, uLB, x, y, g);
+        gather<R, SEM, PROM>(src, geo, raw, uLB, x, y, g);
 #pragma unroll
         for (int k = 0; k < Q; ++k) t[k][tx][ty] = g[k];
     }
@@ -436,7 +429,7 @@ __global__ __launch_bounds__(BLK) void k_export_fin(const R* __restrict__ src, G
 
 // lattice -> staging: macroscopic fields (with wall overrides; SEM_BB: none) of the populations gathered
 // from `src`; stage = [ux | uy | rho], each [nx][ny_local]
-template <typename R, int SEM>
+template <typename R, int SEM, bool PROM>
 __global__ __launch_bounds__(BLK) void k_export_macro(const R* __restrict__ src, Geo geo, int raw, R uLB,
                                                       R* __restrict__ stage, long long bstride) {
     constexpr int TRX = trx<R>(), RY = BLK / TRX;
@@ -450,7 +443,7 @@ __global__ __launch_bounds__(BLK) void k_export_macro(const R* __restrict__ src,
         const int y = y0 + ty;
         if (x >= geo.nx || y >= geo.ny) continue;
         R g[Q], rho, ux, uy;
-        gather<R, SEM>(src, geo, raw, uLB, x, y, g);
+        gather<R, SEM, PROM>(src, geo, raw, uLB, x, y, g);
         macros<R, false, SEM>(g, x, geo.y0 + y, geo.nx, geo.NY, uLB, rho, ux, uy);
         t[0][tx][ty] = ux; t[1][tx][ty] = uy; t[2][tx][ty] = rho;
     }
@@ -467,7 +460,7 @@ __global__ __launch_bounds__(BLK) void k_export_macro(const R* __restrict__ src,
 
 // lattice -> staging: relaxation time tau + tau_turbulent of the iteration that starts from the populations gathered from `src`
 // (taus_g, MRT_GPU.py:385-387); turb = 0: the constant 1 / omega.  stage = [nx][ny_local]
-template <typename R, bool FAST>
+template <typename R, bool FAST, bool PROM>
 __global__ __launch_bounds__(BLK) void k_export_tau(const R* __restrict__ src, Geo geo, int raw, Relax<R> w, Batch<R> bt, int turb,
                                                     R* __restrict__ stage) {
     constexpr int TRX = trx<R>(), RY = BLK / TRX;
@@ -483,9 +476,9 @@ __global__ __launch_bounds__(BLK) void k_export_tau(const R* __restrict__ src, G
         R tau = (R)1.0 / w.w_nu;
         if (turb) {
             R g[Q];
-            gather<R, SEM_GPU>(src, geo, raw, w.uLB, x, y, g);
+            gather<R, SEM_GPU, PROM>(src, geo, raw, w.uLB, x, y, g);
             const long long me = geo.at(x, y);
-            tau = smagorinsky_tau<R, FAST>(g, src[K_QEQ * geo.plane + me], src[K_RHO * geo.plane + me], w.w_nu);
+            tau = smagorinsky_tau<R, FAST, PROM>(g, src[K_QEQ * geo.plane + me], src[K_RHO * geo.plane + me], w.w_nu);
         }
         t[tx][ty] = tau;
     }
@@ -498,7 +491,7 @@ __global__ __launch_bounds__(BLK) void k_export_tau(const R* __restrict__ src, G
 // Sum over the slab of ux + uy of the macroscopic state gathered from `src` (what k_export_macro would write), in double:
 // partial[blockIdx.z * gridDim.x + blockIdx.x] = the block's sum; k_reduce_final adds the partial sums of each lattice in
 // index order -- a fixed summation tree, so the result does not vary from run to run.
-template <typename R, int SEM>
+template <typename R, int SEM, bool PROM>
 __global__ __launch_bounds__(BLK) void k_reduce_u(const R* __restrict__ src, Geo geo, int raw, R uLB, long long bstride,
                                                   double* __restrict__ partial) {
     __shared__ double red[BLK];
@@ -508,155 +501,8 @@ __global__ __launch_bounds__(BLK) void k_reduce_u(const R* __restrict__ src, Geo
     for (long long i = (long long)blockIdx.x * BLK + threadIdx.x; i < n; i += (long long)gridDim.x * BLK) {
         const int y = (int)(i / geo.nx), x = (int)(i - (long long)y * geo.nx);
         R g[Q], rho, ux, uy;
-        gather<R, SEM>(src, geo, raw, uLB, x, y, g);
+        gather<R, SEM, PROM>(src, geo, raw, uLB, x, y, g);
         macros<R, false, SEM>(g, x, geo.y0 + y, geo.nx, geo.NY, uLB, rho, ux, uy);
-        acc += (double)ux + (double)uy;
-    }
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    for (int s = BLK / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) partial[(size_t)blockIdx.z * gridDim.x + blockIdx.x] = red[0];
-}
-
-// ---- the twins of the kernels above for arith = promoted (fp32, MRT_GPU semantics): their equilibria -- the history of an uploaded state,
-// the lid's wall rule in the gather -- and the Smagorinsky tau take the promoted form (equ<R, true>, gather<R, SEM_GPU, true>,
-// smagorinsky_tau<R, false, true>).  Written out again rather than shared with the kernels above as device functions: inlined from a
-// helper, those kernels' code changes (operand order, scheduling), and they are meant to stay exactly as they are.
-template <typename R>
-__global__ __launch_bounds__(BLK) void k_import_prom(const R* __restrict__ stage, R* __restrict__ lat, Geo geo, R uLB, int turb, long long bstride) {
-    constexpr int TRX = trx<R>(), RY = BLK / TRX;
-    __shared__ R t[Q][TRX][33];
-    const long long n = (long long)geo.nx * geo.ny;
-    lat += blockIdx.z * bstride;
-    stage += blockIdx.z * (Q * n);
-    const int x0 = blockIdx.x * TRX, y0 = blockIdx.y * 32;
-    {
-        const int yy = threadIdx.x & 31, xb = threadIdx.x >> 5;
-        for (int xx = xb; xx < TRX; xx += BLK / 32)
-            if (x0 + xx < geo.nx && y0 + yy < geo.ny) {
-#pragma unroll
-                for (int k = 0; k < Q; ++k) t[k][xx][yy] = stage[k * n + (long long)(x0 + xx) * geo.ny + y0 + yy];
-            }
-    }
-    __syncthreads();
-    const int tx = threadIdx.x % TRX, x = x0 + tx;
-    for (int ty = threadIdx.x / TRX; ty < 32; ty += RY) {
-        const int y = y0 + ty;
-        if (x >= geo.nx || y >= geo.ny) continue;
-        R g[Q];
-#pragma unroll
-        for (int k = 0; k < Q; ++k) {
-            g[k] = t[k][tx][ty];
-            lat[k * geo.plane + geo.at(x, y)] = g[k];
-        }
-        if (turb) {
-            R rho, ux, uy, fe[Q];
-            macros<R>(g, x, geo.y0 + y, geo.nx, geo.NY, uLB, rho, ux, uy);
-            equ<R, true>(rho, ux, uy, fe);
-            lat[K_QEQ * geo.plane + geo.at(x, y)] = diag_flux<R>(fe);
-            lat[K_RHO * geo.plane + geo.at(x, y)] = rho;
-        }
-    }
-}
-
-template <typename R>
-__global__ __launch_bounds__(BLK) void k_export_fin_prom(const R* __restrict__ src, Geo geo, int raw, R uLB, R* __restrict__ stage, long long bstride) {
-    constexpr int TRX = trx<R>(), RY = BLK / TRX;
-    __shared__ R t[Q][TRX][33];
-    const long long n = (long long)geo.nx * geo.ny;
-    src += blockIdx.z * bstride;
-    stage += blockIdx.z * (Q * n);
-    const int x0 = blockIdx.x * TRX, y0 = blockIdx.y * 32;
-    const int tx = threadIdx.x % TRX, x = x0 + tx;
-    for (int ty = threadIdx.x / TRX; ty < 32; ty += RY) {
-        const int y = y0 + ty;
-        if (x >= geo.nx || y >= geo.ny) continue;
-        R g[Q];
-        gather<R, SEM_GPU, true>(src, geo, raw, uLB, x, y, g);
-#pragma unroll
-        for (int k = 0; k < Q; ++k) t[k][tx][ty] = g[k];
-    }
-    __syncthreads();
-    const int yy = threadIdx.x & 31, xb = threadIdx.x >> 5;
-    for (int xx = xb; xx < TRX; xx += BLK / 32)
-        if (x0 + xx < geo.nx && y0 + yy < geo.ny) {
-#pragma unroll
-            for (int k = 0; k < Q; ++k) stage[k * n + (long long)(x0 + xx) * geo.ny + y0 + yy] = t[k][xx][yy];
-        }
-}
-
-template <typename R>
-__global__ __launch_bounds__(BLK) void k_export_macro_prom(const R* __restrict__ src, Geo geo, int raw, R uLB, R* __restrict__ stage, long long bstride) {
-    constexpr int TRX = trx<R>(), RY = BLK / TRX;
-    __shared__ R t[3][TRX][33];
-    const long long n = (long long)geo.nx * geo.ny;
-    src += blockIdx.z * bstride;
-    stage += blockIdx.z * (3 * n);
-    const int x0 = blockIdx.x * TRX, y0 = blockIdx.y * 32;
-    const int tx = threadIdx.x % TRX, x = x0 + tx;
-    for (int ty = threadIdx.x / TRX; ty < 32; ty += RY) {
-        const int y = y0 + ty;
-        if (x >= geo.nx || y >= geo.ny) continue;
-        R g[Q], rho, ux, uy;
-        gather<R, SEM_GPU, true>(src, geo, raw, uLB, x, y, g);
-        macros<R>(g, x, geo.y0 + y, geo.nx, geo.NY, uLB, rho, ux, uy);
-        t[0][tx][ty] = ux; t[1][tx][ty] = uy; t[2][tx][ty] = rho;
-    }
-    __syncthreads();
-    const int yy = threadIdx.x & 31, xb = threadIdx.x >> 5;
-    for (int xx = xb; xx < TRX; xx += BLK / 32)
-        if (x0 + xx < geo.nx && y0 + yy < geo.ny) {
-            const long long o = (long long)(x0 + xx) * geo.ny + y0 + yy;
-            stage[o] = t[0][xx][yy];
-            stage[n + o] = t[1][xx][yy];
-            stage[2 * n + o] = t[2][xx][yy];
-        }
-}
-
-// (the third mode of k_export_tau, next to <R, FAST>: the promoted tau)
-template <typename R>
-__global__ __launch_bounds__(BLK) void k_export_tau_prom(const R* __restrict__ src, Geo geo, int raw, Relax<R> w, Batch<R> bt, int turb,
-                                                         R* __restrict__ stage) {
-    constexpr int TRX = trx<R>(), RY = BLK / TRX;
-    __shared__ R t[TRX][33];
-    const long long n = (long long)geo.nx * geo.ny;
-    if (bt.w) { src += blockIdx.z * bt.stride; w = bt.w[blockIdx.z]; }
-    stage += blockIdx.z * n;
-    const int x0 = blockIdx.x * TRX, y0 = blockIdx.y * 32;
-    const int tx = threadIdx.x % TRX, x = x0 + tx;
-    for (int ty = threadIdx.x / TRX; ty < 32; ty += RY) {
-        const int y = y0 + ty;
-        if (x >= geo.nx || y >= geo.ny) continue;
-        R tau = (R)1.0 / w.w_nu;
-        if (turb) {
-            R g[Q];
-            gather<R, SEM_GPU, true>(src, geo, raw, w.uLB, x, y, g);
-            const long long me = geo.at(x, y);
-            tau = smagorinsky_tau<R, false, true>(g, src[K_QEQ * geo.plane + me], src[K_RHO * geo.plane + me], w.w_nu);
-        }
-        t[tx][ty] = tau;
-    }
-    __syncthreads();
-    const int yy = threadIdx.x & 31, xb = threadIdx.x >> 5;
-    for (int xx = xb; xx < TRX; xx += BLK / 32)
-        if (x0 + xx < geo.nx && y0 + yy < geo.ny) stage[(long long)(x0 + xx) * geo.ny + y0 + yy] = t[xx][yy];
-}
-
-template <typename R>
-__global__ __launch_bounds__(BLK) void k_reduce_u_prom(const R* __restrict__ src, Geo geo, int raw, R uLB, long long bstride,
-                                                       double* __restrict__ partial) {
-    __shared__ double red[BLK];
-    src += blockIdx.z * bstride;
-    const long long n = (long long)geo.nx * geo.ny;
-    double acc = 0.0;
-    for (long long i = (long long)blockIdx.x * BLK + threadIdx.x; i < n; i += (long long)gridDim.x * BLK) {
-        const int y = (int)(i / geo.nx), x = (int)(i - (long long)y * geo.nx);
-        R g[Q], rho, ux, uy;
-        gather<R, SEM_GPU, true>(src, geo, raw, uLB, x, y, g);
-        macros<R>(g, x, geo.y0 + y, geo.nx, geo.NY, uLB, rho, ux, uy);
         acc += (double)ux + (double)uy;
     }
     red[threadIdx.x] = acc;

@@ -160,6 +160,25 @@ def test_get_tau(kernel):
             assert got.dtype == np.float32 and np.array_equal(got, want), n
 
 
+def test_mean_u():
+    """lbm_mean_u == mean of the u that lbm_get_fields returns (accumulated in double, run-to-run identical), for a single lattice
+    and a batch, after single-step and multi-step units."""
+    with CavitySolver(132, 99, 5000.0, RT="SRT", dtype=np.float32, turb=1, kernel="tb", arith="promoted") as s:
+        for n in (1, 7, 1, 13):
+            s.step(n)
+            u, _ = s.get_fields()
+            m = s.mean_u()
+            assert m == s.mean_u()
+            assert abs(m - float(np.mean(u.astype(np.float64)))) < 1e-12, n
+    with CavityBatch(96, 80, [400.0, 1000.0, 5000.0], RT="SRT", dtype=np.float32, turb=1, arith="promoted") as b:
+        for n in (1, 7, 1, 13):
+            b.step(n)
+            u, _ = b.get_fields()
+            m = b.mean_u()
+            assert m.shape == (3,) and np.array_equal(m, b.mean_u())
+            assert np.abs(m - u.astype(np.float64).reshape(3, -1).mean(axis=1)).max() < 1e-12, n
+
+
 @pytest.mark.parametrize("coll,turb", [("MRT", 0), ("SRT", 1)])
 def test_promoted_is_not_strict(coll, turb):
     n = 128
