@@ -171,7 +171,8 @@ int lbm_step(lbm_ctx* c, int nsteps);
 /* replaces: the implicit synchronisation of cuda.memcpy_dtoh (MRT_GPU.py:755) */
 int lbm_sync(lbm_ctx* c);
 /* replaces: the commented cuda.Event timing (MRTTiledPull.py:364-365,536-549): runs nsteps
- * steps between two HIP events on the compute stream and returns the elapsed milliseconds */
+ * steps between two HIP events on the compute stream and returns the elapsed milliseconds (automatic samples of the time
+ * statistics included, lbm_stats_begin) */
 int lbm_time_steps(lbm_ctx* c, int nsteps, double* ms);
 /* iterations performed since the last lbm_init_equilibrium / lbm_set_state */
 long long lbm_steps_done(const lbm_ctx* c);
@@ -212,6 +213,35 @@ int lbm_mean_u(lbm_ctx* c, double* mean_out);
  * tau_host[nx][ny] receives the relaxation time tau + tau_turbulent of the LAST iteration; with turb = 0 the constant
  * 1 / omega.  With batch = B > 1: tau_host[B][nx][ny]. */
 int lbm_get_tau(lbm_ctx* c, void* tau_host, int host_dtype);
+
+/* --- time statistics ------------------------------------------------------------------- */
+/* No reference counterpart: the time-mean velocity and density and the Reynolds stresses over a window of iterations, accumulated
+ * on the device (the LES run of MRT_GPU.py:46-49 needs them).  A SAMPLE at step count n is exactly the u[2][X][Y] and rho[X][Y] that
+ * lbm_get_fields would return right after n steps, whatever the kernel route, dtype, operator, arithmetic, closure, semantics, batch
+ * or slab.  The device keeps six double sums per cell, S_u, S_v, S_rho, S_uu, S_vv, S_uv: every sample value converted to double,
+ * every product rounded in double and then added (no FMA contraction), samples added in sample order (one thread per cell, no
+ * atomics).  The read-out S / count is one IEEE double division, so the results are bit-identical to the host loop
+ *     step(k); u, rho = get_fields(); acc += u.astype(f64); acc2 += u64 * u64; ...; acc / count.
+ * Statistics are not part of a checkpoint; lbm_init_equilibrium, lbm_set_state and lbm_destroy end them.
+ *
+ * lbm_stats_begin: allocates the sums on the first call (48 B per cell and lattice; never inside lbm_step), zeroes them and records
+ *   n0 = lbm_steps_done().  every > 0: lbm_step (and lbm_time_steps, whose time then includes the samples) samples by itself at step
+ *   counts n0 + every, n0 + 2 every, ...; after any lbm_step call the count covers exactly the samples with n <= lbm_steps_done().
+ *   The sample of n is taken from the lattice after n - 1 steps, so the launch units are cut where one starts at n - 1: an `every`
+ *   below the steps per launch (8 on the streaming path) shortens the units -- correct, but slower.  lbm_step_unit and the split-step
+ *   calls refuse to run while automatic sampling is on.  every = 0: manual sampling only.  On a slab every > 0 is LBM_ERR_STATE
+ *   (the cuts would split the launch units, and ranks that began differently would post different exchanges): slabs call
+ *   lbm_stats_sample at the same step counts on every rank.  Calling it again restarts from zero.
+ * lbm_stats_sample: adds what lbm_get_fields returns now (the same lagged lattice); LBM_ERR_STATE before the first step.
+ * lbm_stats_get: means over the samples, float64, whole-lattice host arrays mean_u[2][X][Y], mean_rho[X][Y], second[3][X][Y] (E[uu],
+ *   E[vv], E[uv]); with batch = B a leading [B].  Only the context's own rows are written; any pointer may be NULL.  With
+ *   count == 0 only *count is written.
+ * lbm_stats_end: stops sampling and frees the sums.
+ * lbm_stats_sample / _get return LBM_ERR_STATE while statistics are off. */
+int lbm_stats_begin(lbm_ctx* c, int every);
+int lbm_stats_sample(lbm_ctx* c);
+int lbm_stats_get(lbm_ctx* c, double* mean_u, double* mean_rho, double* second, long long* count);
+int lbm_stats_end(lbm_ctx* c);
 
 /* --- slab decomposition, externally driven exchange ---------------------------------- */
 /* No reference counterpart (the reference is single-GPU, MRT_GPU.py:29).  A step of a slab

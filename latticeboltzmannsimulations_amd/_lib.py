@@ -98,6 +98,10 @@ SIGNATURES = {
     "lbm_get_fields": (_i, [_vp, _vp, _vp, _vp, _i]),
     "lbm_mean_u": (_i, [_vp, ctypes.POINTER(_d)]),
     "lbm_get_tau": (_i, [_vp, _vp, _i]),
+    "lbm_stats_begin": (_i, [_vp, _i]),
+    "lbm_stats_sample": (_i, [_vp]),
+    "lbm_stats_get": (_i, [_vp, _vp, _vp, _vp, ctypes.POINTER(ctypes.c_longlong)]),
+    "lbm_stats_end": (_i, [_vp]),
     "lbm_halo_elems": (_i, [_vp]),
     "lbm_halo_export": (_i, [_vp, _i, _vp]),
     "lbm_halo_import": (_i, [_vp, _i, _vp]),

@@ -59,6 +59,12 @@ struct lbm_ctx {
     void* stage = nullptr;
     size_t stage_bytes = 0;
     double* red_dev = nullptr;  // lbm_mean_u: partial sums + results
+    // Time statistics (lbm_stats_*): six double sums per cell (k_stats_accumulate), null while statistics are off.  Automatic sampling
+    // (stats_every > 0) takes the sample of step count n = stats_next from lat[cur] when a unit would start at n - 1 (step_many).
+    double* stats_dev = nullptr;
+    long long stats_count = 0;  // samples enqueued
+    int stats_every = 0;
+    long long stats_next = 0;
     ncclComm_t comm = nullptr;
     int nranks = 1, rank = 0;
     bool thin_valid = false;    // the one-row halo of lat[cur] has been exchanged (by the RCCL path, on s_comm)
@@ -300,6 +306,7 @@ int launch_stream_edges(lbm_ctx* c, int from, int to, hipStream_t s, int S, bool
 int warm_stream(lbm_ctx* c);
 int launch_deep(lbm_ctx* c, int from, int to, hipStream_t s, int steps, bool with_frame = false);
 void finish_unit(lbm_ctx* c, int S);
+int stats_accumulate(lbm_ctx* c, int which);
 int single_step(lbm_ctx* c, bool* comm_used, bool rccl_x);
 int multi_step(lbm_ctx* c, bool* comm_used, int S, bool rccl_x);
 int prev_lattice(lbm_ctx* c, int* which);

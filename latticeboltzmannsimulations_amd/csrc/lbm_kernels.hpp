@@ -513,3 +513,39 @@ __global__ __launch_bounds__(BLK) void k_reduce_u(const R* __restrict__ src, Geo
     }
     if (threadIdx.x == 0) partial[(size_t)blockIdx.z * gridDim.x + blockIdx.x] = red[0];
 }
+
+// Time statistics (lbm_stats_*): per cell, the macroscopic state k_export_macro would export from `src` (the same gather + macros, so
+// the same bits), converted to double and added to six running sums acc = [S_u | S_v | S_rho | S_uu | S_vv | S_uv], each plane
+// [ny_local][nxa], x fastest (nxa = nx rounded up to even; lattice b of a batch at acc + b * 6 * ny_local * nxa; the padding column
+// stays 0).  One lane owns the two neighbouring cells 2i, 2i + 1 of the flattened plane: every access to the sums is 16 B per lane and
+// coalesced along x.  Contraction off: each product is rounded in double, then added -- the same operations, in the same order, as
+// the host loop  acc += u.astype(f64); acc2 += u64 * u64  over lbm_get_fields.  One thread owns a cell: no atomics, samples add in
+// the order they are enqueued.  Pure streaming: 9 * sizeof(R) + 48 B read and 48 B written per cell.
+template <typename R, int SEM, bool PROM>
+__global__ __launch_bounds__(BLK) void k_stats_accumulate(const R* __restrict__ src, Geo geo, int raw, R uLB, long long bstride,
+                                                          double* __restrict__ acc) {
+#pragma clang fp contract(off)
+    typedef double d2 __attribute__((ext_vector_type(2)));
+    const int nxh = (geo.nx + 1) >> 1;
+    const long long npairs = (long long)geo.ny * nxh;   // = half the elements of one plane
+    src += blockIdx.z * bstride;
+    d2* a = (d2*)acc + blockIdx.z * 6 * npairs;
+    for (long long i = (long long)blockIdx.x * BLK + threadIdx.x; i < npairs; i += (long long)gridDim.x * BLK) {
+        const int y = (int)(i / nxh), x = 2 * (int)(i - (long long)y * nxh);
+        d2 u = {0.0, 0.0}, v = {0.0, 0.0}, r = {0.0, 0.0};
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            if (x + j >= geo.nx) break;   // (the padding column of an odd nx)
+            R g[Q], rho, ux, uy;
+            gather<R, SEM, PROM>(src, geo, raw, uLB, x + j, y, g);
+            macros<R, false, SEM>(g, x + j, geo.y0 + y, geo.nx, geo.NY, uLB, rho, ux, uy);
+            u[j] = (double)ux; v[j] = (double)uy; r[j] = (double)rho;
+        }
+        a[i] = a[i] + u;
+        a[npairs + i] = a[npairs + i] + v;
+        a[2 * npairs + i] = a[2 * npairs + i] + r;
+        a[3 * npairs + i] = a[3 * npairs + i] + u * u;
+        a[4 * npairs + i] = a[4 * npairs + i] + v * v;
+        a[5 * npairs + i] = a[5 * npairs + i] + u * v;
+    }
+}

@@ -452,10 +452,50 @@ int push_reset(lbm_ctx* c) {
     return LBM_OK;
 }
 
+// One sample of the time statistics from lat[which] (the lattice whose gathered populations are the state the sampled iteration
+// starts from), on the compute stream.
+int stats_accumulate(lbm_ctx* c, int which) {
+    constexpr long long STATS_BLOCKS = 2048;   // grid-stride beyond that (a pure streaming kernel)
+    const long long npairs = (long long)c->geo.ny * ((c->geo.nx + 1) / 2);
+    const int blocks = (int)std::min<long long>((npairs + BLK - 1) / BLK, STATS_BLOCKS);
+    const int rc = launch_variant(c, [&](auto v) {
+        using VT = decltype(v);
+        using R = typename VT::R;
+        hipLaunchKernelGGL((k_stats_accumulate<R, VT::SEM, coll_is_prom(VT::COLL)>), dim3(blocks, 1, c->batch), dim3(BLK), 0, c->s_compute,
+                           (const R*)c->lat[which], c->geo, c->raw[which], (R)c->p.uLB, c->bstride, c->stats_dev);
+    });
+    if (rc) return rc;
+    ++c->stats_count;
+    return LBM_OK;
+}
+
+// Automatic sampling (lbm_stats_begin with every > 0; a lone lattice).  The sample of step count n is the macroscopic state of the
+// lattice after n - 1 steps, so the unit plan is cut where a unit starts at n - 1 and the sample is taken there from lat[cur], with
+// its raw flag: no lag replay.  A call that ends at n - 1 takes it at the start of the next call.
+static int sample_if_due(lbm_ctx* c) {
+    if (c->stats_every <= 0 || c->nsteps + 1 != c->stats_next) return LBM_OK;
+    if (c->edges_pending) {   // (frame work of the last unit on the second stream wrote part of lat[cur])
+        HIP_TRY(c, hipStreamWaitEvent(c->s_compute, c->ev_edges, 0));
+        c->edges_pending = false;
+    }
+    const int rc = stats_accumulate(c, c->cur);
+    if (rc) return rc;
+    c->int_stale = true;      // (s_comm must not rewrite lat[cur] before the sample has read it)
+    c->stats_next += c->stats_every;
+    return LBM_OK;
+}
+
+// steps the unit planner may spend before the next cut (all of them with automatic sampling off)
+static int steps_to_cut(const lbm_ctx* c, int left) {
+    if (c->stats_every <= 0) return left;
+    return (int)std::min<long long>(left, c->stats_next - 1 - c->nsteps);
+}
+
 int step_many(lbm_ctx* c, int nsteps) {
     if (c->push) {
         for (int i = 0; i < nsteps; ++i) {
-            int rc = push_step(c);
+            int rc = sample_if_due(c);
+            if (rc == LBM_OK) rc = push_step(c);
             if (rc) return rc;
         }
         return LBM_OK;
@@ -470,8 +510,10 @@ int step_many(lbm_ctx* c, int nsteps) {
     c->edge_rows = 0;        // the first exchange of the call waits for it
     int left = nsteps;
     while (left > 0) {
-        const int S = unit_steps(c, left, c->raw[c->cur] != 0);
-        const int rc = S > 1 ? multi_step(c, &comm_used, S, true) : single_step(c, &comm_used, true);
+        int rc = sample_if_due(c);
+        if (rc) return rc;
+        const int S = unit_steps(c, steps_to_cut(c, left), c->raw[c->cur] != 0);
+        rc = S > 1 ? multi_step(c, &comm_used, S, true) : single_step(c, &comm_used, true);
         if (rc) return rc;
         left -= S;
     }
@@ -514,6 +556,7 @@ int lbm_time_steps(lbm_ctx* c, int nsteps, double* ms) {
 int lbm_step_edges(lbm_ctx* c) {
     if (!c) return LBM_ERR_INVALID;
     if (c->push) return fail(c, LBM_ERR_STATE, "the split-step calls do not apply to kernel = PUSH");
+    if (c->stats_every > 0) return fail(c, LBM_ERR_STATE, "automatic sampling (lbm_stats_begin, every > 0) runs inside lbm_step only");
     HIP_TRY(c, hipSetDevice(c->p.device));
     return launch_rows(c, c->cur, c->cur ^ 1, 0, c->geo.ny - 1, 2, c->s_compute);
 }
@@ -537,6 +580,7 @@ int lbm_step_unit(lbm_ctx* c, int S) {
     HIP_TRY(c, hipSetDevice(c->p.device));
     if (c->push || c->kern == Kern::none) return fail(c, LBM_ERR_STATE, "lbm_step_unit: this context steps one step per launch (lbm_next_unit() is 1)");
     if (own_transport(c)) return fail(c, LBM_ERR_STATE, "lbm_step_unit: a communicator is attached, lbm_step() moves the halos itself");
+    if (c->stats_every > 0) return fail(c, LBM_ERR_STATE, "lbm_step_unit: automatic sampling (lbm_stats_begin, every > 0) runs inside lbm_step only");
     if (c->raw[c->cur]) return fail(c, LBM_ERR_STATE, "lbm_step_unit: the first step after an upload is a single step");
     const bool ok = c->tb_steps == 2 ? S == 2 : (S >= 3 && S <= c->tb_steps);
     if (!ok)

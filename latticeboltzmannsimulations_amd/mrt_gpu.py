@@ -35,6 +35,14 @@ class CavityResult:
         self.regression = []   # (iteration, value) at every output iteration
         self.elapsed = 0.0
         self.mlups = 0.0
+        # time statistics (run_cavity(AverageFrom=...)): float64 means and central moments over the samples, or None
+        self.u_mean = None
+        self.rho_mean = None
+        self.uu = None
+        self.vv = None
+        self.uv = None
+        self.samples = 0
+        self.regression_mean = []   # (iteration, value of the time-mean) at every output iteration with samples
 
 
 CS2_EFFECTIVE, CS_BULK = 0.025, 0.16     # MRT_GPU.py:350,374-376: Van Driest damping is overwritten by Cs2 = 0.025
@@ -112,7 +120,7 @@ def _dashboard(path, u, rho, It, hist, Re, RT, regime, BC, xsize, ysize, uLB, re
 def run_cavity(maxIt=3000000, Re=10000.0, RT="SRT", turb=1, xsize=32 * 5, ysize=32 * 5, uLB=0.08,
                Pinterval=3000, SavePlot=True, SaveVTK=False, project="ldc", OutputFolder="./output",
                dtype=np.float32, semantics="mrt_gpu", device=0, quiet=False, solver_factory=None, arith="strict",
-               convergence="host", vtk_correct=False, BC="EB-NEBB "):
+               convergence="host", vtk_correct=False, BC="EB-NEBB ", AverageFrom=None, AverageEvery=100):
     """Run the lid-driven cavity like MRT_GPU.py does; returns a :class:`CavityResult`.
 
     Argument names and defaults are the module constants of MRT_GPU.py:38-58.
@@ -124,9 +132,15 @@ def run_cavity(maxIt=3000000, Re=10000.0, RT="SRT", turb=1, xsize=32 * 5, ysize=
     PCIe instead of the field; the two means differ in the last bits of a float, so a run may stop one check apart).
     vtk_correct: write the .vtr files as point data (VTKWrapper.saveToVTK(correct=True)) instead of the reference's layout.
     BC: the wall model, the two options of MRT_GPU.py:281 -- 'EB-NEBB ' (default: the wet-node walls of `semantics`) or 'BB'
-    (half-way bounce-back with the moving-lid term: semantics='bounce_back', which BC='BB' selects; no Smagorinsky closure, turb=0)."""
+    (half-way bounce-back with the moving-lid term: semantics='bounce_back', which BC='BB' selects; no Smagorinsky closure, turb=0).
+    AverageFrom: time statistics on the device (CavitySolver.begin_statistics) from iteration AverageFrom on -- samples of the fields
+    after AverageFrom + AverageEvery, AverageFrom + 2 AverageEvery, ... iterations; every output iteration with samples then prints
+    the Ghia regression value of the time-mean and, with SaveVTK, writes <project>_mean.#####.vtr; the result carries u_mean,
+    rho_mean, uu, vv, uv (central moments), samples and regression_mean.  None (default): no statistics, nothing changes."""
     if convergence not in ("host", "device"):
         raise ValueError("convergence must be 'host' or 'device'")
+    if AverageFrom is not None and (int(AverageFrom) < 0 or int(AverageEvery) < 1):
+        raise ValueError("AverageFrom must be >= 0 and AverageEvery >= 1")
     if BC.strip() not in ("EB-NEBB", "BB"):
         raise ValueError("BC must be 'EB-NEBB ' or 'BB'")
     if BC.strip() == "BB":
@@ -174,13 +188,28 @@ def run_cavity(maxIt=3000000, Re=10000.0, RT="SRT", turb=1, xsize=32 * 5, ysize=
     done = 0          # iterations performed
     have_ghia = int(round(float(Re))) in ghia.RE_COLUMNS
     outputs = SaveVTK or SavePlot
+    averaging = False
+
+    def advance(n):   # n iterations; statistics begin once `done` reaches AverageFrom
+        nonlocal averaging
+        if AverageFrom is None or averaging or done + n < AverageFrom:
+            solver.step(n)
+            return
+        k = int(AverageFrom) - done
+        if k > 0:
+            solver.step(k)
+        solver.begin_statistics(int(AverageEvery))
+        averaging = True
+        if n > k:
+            solver.step(n - k)
+
     It = 0
     while It < maxIt:
         # iterations It .. next output iteration (inclusive) in one enqueue
         nxt = It if (It % Pinterval == 0) else min(maxIt - 1, (It // Pinterval + 1) * Pinterval)
         if not outputs:
             nxt = maxIt - 1
-        solver.step(nxt - It + 1)
+        advance(nxt - It + 1)
         done = nxt + 1
         It = nxt
         if (It % Pinterval == 0) and outputs:
@@ -191,6 +220,11 @@ def run_cavity(maxIt=3000000, Re=10000.0, RT="SRT", turb=1, xsize=32 * 5, ysize=
                 reg_val = ghia.r2_value(u, Re, uLB)
                 res.regression.append((It, float(reg_val)))
                 say("current regression value is " + str(reg_val))
+            stats = solver.statistics() if averaging else None
+            if stats is not None and stats["samples"] and have_ghia:
+                reg_mean = ghia.r2_value(stats["u"], Re, uLB)
+                res.regression_mean.append((It, float(reg_mean)))
+                say("current regression value of the time-mean is " + str(reg_mean))
             say("current mean velocity value is " + str(np.mean(u) / uLB))
             if SavePlot and have_ghia:
                 tau_mean = float(np.mean(solver.get_tau())) if (turb == 1 and hasattr(solver, "get_tau")) else None
@@ -203,6 +237,10 @@ def run_cavity(maxIt=3000000, Re=10000.0, RT="SRT", turb=1, xsize=32 * 5, ysize=
                 try:
                     saveToVTK((Vel[0], Vel[1], velZ), np.reshape(rho, (xsize, ysize, 1)), project,
                               str(int(It / Pinterval)).zfill(5), grid, correct=vtk_correct)
+                    if stats is not None and stats["samples"]:
+                        Vm = np.reshape(stats["u"], (2, xsize, ysize, 1))
+                        saveToVTK((Vm[0], Vm[1], np.zeros((xsize, ysize, 1))), np.reshape(stats["rho"], (xsize, ysize, 1)),
+                                  project + "_mean", str(int(It / Pinterval)).zfill(5), grid, correct=vtk_correct)
                 finally:
                     os.chdir(cwd)
             say("time elapsed is ", (timer() - tstart), "seconds")
@@ -223,6 +261,9 @@ def run_cavity(maxIt=3000000, Re=10000.0, RT="SRT", turb=1, xsize=32 * 5, ysize=
         It += 1
     solver.sync()
     res.u, res.rho = solver.get_fields(out_dtype=np.float32)
+    if averaging:
+        st = solver.statistics()
+        res.u_mean, res.rho_mean, res.uu, res.vv, res.uv, res.samples = st["u"], st["rho"], st["uu"], st["vv"], st["uv"], st["samples"]
     res.iterations = done
     res.elapsed = timer() - tstart
     res.mlups = xsize * ysize * done * 1e-6 / res.elapsed        # as printed by MRTTiledPull.py:703
@@ -253,11 +294,14 @@ def main(argv=None):
     ap.add_argument("--arith", choices=["strict", "fast", "promoted"], default="strict")
     ap.add_argument("--convergence", choices=["host", "device"], default="host")
     ap.add_argument("--vtk-correct", action="store_true", help="write .vtr point data (consistent file) instead of the reference's layout")
+    ap.add_argument("--average-from", type=int, default=None, help="time statistics on the device from this iteration on")
+    ap.add_argument("--average-every", type=int, default=100, help="iterations between two samples of the time statistics")
     a = ap.parse_args(argv)
     r = run_cavity(maxIt=a.maxIt, Re=a.Re, RT=a.RT, turb=a.turb, xsize=a.xsize, ysize=a.ysize, uLB=a.uLB,
                    Pinterval=a.Pinterval, SavePlot=not a.no_plot, SaveVTK=a.vtk, project=a.project,
                    OutputFolder=a.OutputFolder, dtype=np.dtype(a.dtype), semantics=a.semantics, arith=a.arith,
-                   convergence=a.convergence, vtk_correct=a.vtk_correct, BC="BB" if a.BC == "BB" else "EB-NEBB ")
+                   convergence=a.convergence, vtk_correct=a.vtk_correct, BC="BB" if a.BC == "BB" else "EB-NEBB ",
+                   AverageFrom=a.average_from, AverageEvery=a.average_every)
     print("MLUPS : ", r.mlups)
     return 0
 

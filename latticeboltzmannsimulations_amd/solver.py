@@ -233,10 +233,44 @@ class CavitySolver:
         self._check(self.lib.lbm_get_tau(self._h, tau.ctypes.data, _DT[tau.dtype]), "lbm_get_tau")
         return tau
 
+    # -- time statistics (lbm_stats_*) -------------------------------------------------------
+    def begin_statistics(self, every=0):
+        """Start (or restart from zero) the time statistics of u and rho on the device (lbm_stats_begin).  every > 0: step()
+        samples by itself at steps_done + every, + 2 every, ...; every = 0: samples only through sample_statistics().  A sample is
+        exactly what get_fields() would return after that step.  Not on a slab with every > 0 (sample by hand there)."""
+        self._check(self.lib.lbm_stats_begin(self._h, int(every)), "lbm_stats_begin")
+        return self
+
+    def sample_statistics(self):
+        """Add the fields get_fields() would return now to the statistics (lbm_stats_sample)."""
+        self._check(self.lib.lbm_stats_sample(self._h), "lbm_stats_sample")
+        return self
+
+    def end_statistics(self):
+        """Stop sampling and free the device sums (lbm_stats_end)."""
+        self._check(self.lib.lbm_stats_end(self._h), "lbm_stats_end")
+
+    def statistics(self):
+        """The time statistics so far, float64, whole-lattice shaped (a slab fills its own rows): u [2,X,Y] and rho [X,Y], the
+        means; uu, vv, uv [X,Y], the central moments E[ab] - E[a] E[b] (computed here from the device's means of the products);
+        samples, the number of samples.  With no sample yet the arrays are None.  A batch carries a leading [B]."""
+        lead = self._lead
+        mu = np.zeros(lead + (2, self.nx, self.ny))
+        mrho = np.zeros(lead + (self.nx, self.ny))
+        sec = np.zeros(lead + (3, self.nx, self.ny))
+        n = ctypes.c_longlong(0)
+        self._check(self.lib.lbm_stats_get(self._h, mu.ctypes.data, mrho.ctypes.data, sec.ctypes.data, ctypes.byref(n)), "lbm_stats_get")
+        if n.value == 0:
+            return dict(u=None, rho=None, uu=None, vv=None, uv=None, samples=0)
+        ux, uy = mu[..., 0, :, :], mu[..., 1, :, :]
+        return dict(u=mu, rho=mrho, uu=sec[..., 0, :, :] - ux * ux, vv=sec[..., 1, :, :] - uy * uy, uv=sec[..., 2, :, :] - ux * uy,
+                    samples=int(n.value))
+
     # -- checkpoint / restart (the reference has neither; SURVEY 8f item 4) -------------------
     def save_checkpoint(self, path):
         """Write the populations and the run parameters to `path` (.npz).  Restarting from it continues bit-identically
-        (the state of the scheme is `fin`); with turb = 1 the one-step Smagorinsky history restarts from the state."""
+        (the state of the scheme is `fin`); with turb = 1 the one-step Smagorinsky history restarts from the state.  The time
+        statistics (begin_statistics) are not part of a checkpoint, and load_checkpoint ends them."""
         u, rho, fin = self.get_fields(want_fin=True)
         path = _npz(path)
         np.savez(path, fin=fin, steps_done=self.steps_done, nx=self.nx, ny=self.ny, Re=self.Re, RT=self.RT, uLB=self.uLB,
