@@ -85,7 +85,7 @@ const int* side_planes(int side) {
 }
 
 char* plane_row(lbm_ctx* c, int which, int k, int y) {
-    return (char*)c->lat[which] + ((size_t)k * c->geo.plane + (size_t)c->geo.at(0, y)) * c->es;
+    return (char*)c->lat[which] + ((size_t)k * c->plan.geo.plane + (size_t)c->plan.geo.at(0, y)) * c->plan.es;
 }
 
 #ifdef LBM_DEBUG
@@ -101,12 +101,12 @@ constexpr bool debug_skip_exchange() { return false; }
 int enqueue_exchange(lbm_ctx* c, int which) {
     if (debug_skip_exchange()) return LBM_OK;
     const ncclDataType_t dt = c->p.dtype == LBM_F32 ? ncclFloat : ncclDouble;
-    const int ny = c->geo.ny;
+    const int ny = c->plan.geo.ny;
     NCCL_TRY(c, rccl().GroupStart());
     for (int side = 0; side < 2; ++side) {
         int peer = side == LBM_SIDE_LOW ? c->rank - 1 : c->rank + 1;
         if (c->loopback) peer = 0;                 // the slab is its own neighbour
-        if (!has_neighbour(c, side)) continue;
+        if (!has_neighbour(c->plan, side)) continue;
         // planes leaving / arriving through this side.  In loopback mode both sides talk to rank 0, and RCCL
         // pairs the i-th send to a peer with the i-th receive from it: what leaves through the OTHER side is
         // sent here, so that the HIGH row lands in the LOW ghost row and vice versa (periodic wrap).
@@ -118,10 +118,10 @@ int enqueue_exchange(lbm_ctx* c, int which) {
         for (int j = 0; j < 3; ++j) {
             int lo, hi;
             halo_range(c, out[j], &lo, &hi);
-            NCCL_TRY(c, rccl().Send(plane_row(c, which, out[j], send_row) + (size_t)lo * c->es, (size_t)(hi - lo + 1), dt,
+            NCCL_TRY(c, rccl().Send(plane_row(c, which, out[j], send_row) + (size_t)lo * c->plan.es, (size_t)(hi - lo + 1), dt,
                                  peer, c->comm, c->s_comm));
             halo_range(c, in[j], &lo, &hi);
-            NCCL_TRY(c, rccl().Recv(plane_row(c, which, in[j], recv_row) + (size_t)lo * c->es, (size_t)(hi - lo + 1), dt,
+            NCCL_TRY(c, rccl().Recv(plane_row(c, which, in[j], recv_row) + (size_t)lo * c->plan.es, (size_t)(hi - lo + 1), dt,
                                  peer, c->comm, c->s_comm));
         }
     }
@@ -130,19 +130,19 @@ int enqueue_exchange(lbm_ctx* c, int which) {
 }
 RowBlocks deep_blocks(lbm_ctx* c, int which, int r0, int S) {
     RowBlocks b;
-    const int nplanes = c->p.turb ? Q + 2 : Q;
-    const bool rows_layout = c->geo.row != c->geo.pitch;
-    auto at = [&](int k) { return (char*)c->lat[which] + ((size_t)k * c->geo.plane + (size_t)(r0 + GHY) * c->geo.row) * c->es; };
+    const int nplanes = c->plan.nplanes;
+    const bool rows_layout = c->plan.geo.row != c->plan.geo.pitch;
+    auto at = [&](int k) { return (char*)c->lat[which] + ((size_t)k * c->plan.geo.plane + (size_t)(r0 + GHY) * c->plan.geo.row) * c->plan.es; };
     if (rows_layout) {
-        b.n = 1; b.ptr[0] = at(0); b.elems = (size_t)S * c->geo.row;
+        b.n = 1; b.ptr[0] = at(0); b.elems = (size_t)S * c->plan.geo.row;
     } else {
-        b.n = nplanes; b.elems = (size_t)S * c->geo.pitch;
+        b.n = nplanes; b.elems = (size_t)S * c->plan.geo.pitch;
         for (int k = 0; k < nplanes; ++k) b.ptr[k] = at(k);
     }
     return b;
 }
-int deep_send_row0(const lbm_ctx* c, int side, int S) { return side == LBM_SIDE_LOW ? 0 : c->geo.ny - S; }
-int deep_recv_row0(const lbm_ctx* c, int side, int S) { return side == LBM_SIDE_LOW ? -S : c->geo.ny; }
+int deep_send_row0(const lbm_ctx* c, int side, int S) { return side == LBM_SIDE_LOW ? 0 : c->plan.geo.ny - S; }
+int deep_recv_row0(const lbm_ctx* c, int side, int S) { return side == LBM_SIDE_LOW ? -S : c->plan.geo.ny; }
 
 int enqueue_deep_exchange(lbm_ctx* c, int which, int S) {
     if (debug_skip_exchange()) return LBM_OK;
@@ -151,7 +151,7 @@ int enqueue_deep_exchange(lbm_ctx* c, int which, int S) {
     for (int side = 0; side < 2; ++side) {
         int peer = side == LBM_SIDE_LOW ? c->rank - 1 : c->rank + 1;
         if (c->loopback) peer = 0;
-        if (!has_neighbour(c, side)) continue;
+        if (!has_neighbour(c->plan, side)) continue;
         const int sside = c->loopback ? (side ^ 1) : side;   // see enqueue_exchange
         const RowBlocks snd = deep_blocks(c, which, deep_send_row0(c, sside, S), S);
         const RowBlocks rcv = deep_blocks(c, which, deep_recv_row0(c, side, S), S);
@@ -190,13 +190,13 @@ int join_comm(lbm_ctx* c) {
 }
 // lbm_halo_export_rows / lbm_halo_import_rows: the send / receive blocks of an S-step exchange, through host memory.
 static int copy_rows(lbm_ctx* c, int side, int nrows, void* buf, bool out) {
-    if (!c || !buf || (side != LBM_SIDE_LOW && side != LBM_SIDE_HIGH) || nrows < 1 || nrows >= GHY || nrows > c->geo.ny)
+    if (!c || !buf || (side != LBM_SIDE_LOW && side != LBM_SIDE_HIGH) || nrows < 1 || nrows >= GHY || nrows > c->plan.geo.ny)
         return fail(c, LBM_ERR_INVALID, "lbm_halo_export_rows / lbm_halo_import_rows: bad argument (1 <= nrows <= " + std::to_string(GHY - 1) +
                                         ", the ghost rows of a lattice, and <= ny_local)");
-    if (c->batch > 1) return fail(c, LBM_ERR_STATE, "a batch of lattices has no slab halos");
+    if (c->plan.batch > 1) return fail(c, LBM_ERR_STATE, "a batch of lattices has no slab halos");
     HIP_TRY(c, hipSetDevice(c->p.device));
     const RowBlocks b = deep_blocks(c, c->cur, out ? deep_send_row0(c, side, nrows) : deep_recv_row0(c, side, nrows), nrows);
-    const size_t bytes = b.elems * c->es;
+    const size_t bytes = b.elems * c->plan.es;
     for (int i = 0; i < b.n; ++i) {
         char* p = (char*)buf + (size_t)i * bytes;
         HIP_TRY(c, hipMemcpyAsync(out ? (void*)p : (void*)b.ptr[i], out ? (const void*)b.ptr[i] : (const void*)p, bytes, hipMemcpyDefault, c->s_compute));
@@ -210,15 +210,15 @@ using namespace lbmhost;
 
 extern "C" {
 
-int lbm_halo_elems(const lbm_ctx* c) { return c ? 3 * c->geo.nx : 0; }
+int lbm_halo_elems(const lbm_ctx* c) { return c ? 3 * c->plan.geo.nx : 0; }
 
 int lbm_halo_export(lbm_ctx* c, int side, void* buf) {
     if (!c || !buf || (side != LBM_SIDE_LOW && side != LBM_SIDE_HIGH)) return fail(c, LBM_ERR_INVALID, "lbm_halo_export: bad argument");
-    if (c->batch > 1) return fail(c, LBM_ERR_STATE, "a batch of lattices has no slab halos");
+    if (c->plan.batch > 1) return fail(c, LBM_ERR_STATE, "a batch of lattices has no slab halos");
     HIP_TRY(c, hipSetDevice(c->p.device));
     const int* pl = side_planes(side);
-    const int row = side == LBM_SIDE_LOW ? 0 : c->geo.ny - 1;
-    const size_t rb = (size_t)c->geo.nx * c->es;
+    const int row = side == LBM_SIDE_LOW ? 0 : c->plan.geo.ny - 1;
+    const size_t rb = (size_t)c->plan.geo.nx * c->plan.es;
     for (int j = 0; j < 3; ++j)
         HIP_TRY(c, hipMemcpyAsync((char*)buf + j * rb, plane_row(c, c->cur, pl[j], row), rb, hipMemcpyDefault, c->s_compute));
     HIP_TRY(c, hipStreamSynchronize(c->s_compute));
@@ -227,16 +227,16 @@ int lbm_halo_export(lbm_ctx* c, int side, void* buf) {
 
 int lbm_halo_import(lbm_ctx* c, int side, const void* buf) {
     if (!c || !buf || (side != LBM_SIDE_LOW && side != LBM_SIDE_HIGH)) return fail(c, LBM_ERR_INVALID, "lbm_halo_import: bad argument");
-    if (c->batch > 1) return fail(c, LBM_ERR_STATE, "a batch of lattices has no slab halos");
+    if (c->plan.batch > 1) return fail(c, LBM_ERR_STATE, "a batch of lattices has no slab halos");
     HIP_TRY(c, hipSetDevice(c->p.device));
     const int* pl = side_planes(side ^ 1);  // what arrives through `side` left the neighbour's opposite side
-    const int row = side == LBM_SIDE_LOW ? -1 : c->geo.ny;
-    const size_t rb = (size_t)c->geo.nx * c->es;
+    const int row = side == LBM_SIDE_LOW ? -1 : c->plan.geo.ny;
+    const size_t rb = (size_t)c->plan.geo.nx * c->plan.es;
     for (int j = 0; j < 3; ++j) {
         int lo, hi;
         halo_range(c, pl[j], &lo, &hi);
-        HIP_TRY(c, hipMemcpyAsync(plane_row(c, c->cur, pl[j], row) + (size_t)lo * c->es, (const char*)buf + j * rb + (size_t)lo * c->es,
-                                  (size_t)(hi - lo + 1) * c->es, hipMemcpyDefault, c->s_compute));
+        HIP_TRY(c, hipMemcpyAsync(plane_row(c, c->cur, pl[j], row) + (size_t)lo * c->plan.es, (const char*)buf + j * rb + (size_t)lo * c->plan.es,
+                                  (size_t)(hi - lo + 1) * c->plan.es, hipMemcpyDefault, c->s_compute));
     }
     HIP_TRY(c, hipStreamSynchronize(c->s_compute));
     return LBM_OK;
@@ -244,7 +244,7 @@ int lbm_halo_import(lbm_ctx* c, int side, const void* buf) {
 
 long long lbm_halo_rows_elems(const lbm_ctx* c, int nrows) {
     if (!c || nrows < 1 || nrows >= GHY) return 0;
-    return (long long)nrows * (c->p.turb ? Q + 2 : Q) * c->geo.pitch;
+    return (long long)nrows * c->plan.nplanes * c->plan.geo.pitch;
 }
 
 int lbm_halo_export_rows(lbm_ctx* c, int side, int nrows, void* buf) { return copy_rows(c, side, nrows, buf, true); }
@@ -263,9 +263,9 @@ int lbm_comm_unique_id(void* uid_out128) {
 int lbm_comm_init(lbm_ctx* c, int nranks, int rank, const void* uid128) {
     if (!c || !uid128 || nranks < 1 || rank < 0 || rank >= nranks) return fail(c, LBM_ERR_INVALID, "lbm_comm_init: bad argument");
     if (c->comm) return fail(c, LBM_ERR_STATE, "communicator already attached");
-    if (c->batch > 1 || c->push) return fail(c, LBM_ERR_STATE, "a batch of lattices / kernel = PUSH cannot be slab-decomposed");
+    if (c->plan.batch > 1 || c->plan.push) return fail(c, LBM_ERR_STATE, "a batch of lattices / kernel = PUSH cannot be slab-decomposed");
     // rank r holds the r-th slab from the lid: the exchange partners are rank - 1 / rank + 1
-    if ((rank > 0) != has_neighbour(c, LBM_SIDE_LOW) || (rank < nranks - 1) != has_neighbour(c, LBM_SIDE_HIGH))
+    if ((rank > 0) != has_neighbour(c->plan, LBM_SIDE_LOW) || (rank < nranks - 1) != has_neighbour(c->plan, LBM_SIDE_HIGH))
         return fail(c, LBM_ERR_INVALID, "lbm_comm_init: rank 0 must hold the slab at the lid (y0 = 0), the last rank the one at the bottom wall, "
                                         "every other rank a slab in between");
     if (!rccl().ok) return fail(c, LBM_ERR_COMM, rccl().err);
@@ -279,9 +279,10 @@ int lbm_comm_init(lbm_ctx* c, int nranks, int rank, const void* uid128) {
     if (nranks > 1) {
         // Neighbours must run the same launch plan (they post matching send / receive sequences): compare it once.
         constexpr int NW = 16;
-        const int32_t mine[NW] = {LBM_ABI_VERSION, c->p.nx, c->p.ny, c->p.dtype, c->p.semantics, c->p.turb, c->geo.pitch,
-                                  c->geo.row != c->geo.pitch ? 1 : 0, c->kern == Kern::none ? 0 : streaming(c) ? 2 : 1, c->tb_steps, c->tb_f, c->deep_halo ? 1 : 0,
-                                  c->frame_fused ? 1 : 0, c->lazy_lag ? 1 : 0, c->p.collision, c->p.arith};
+        const Plan& pl = c->plan;
+        const int32_t mine[NW] = {LBM_ABI_VERSION, c->p.nx, c->p.ny, c->p.dtype, c->p.semantics, c->p.turb, pl.geo.pitch,
+                                  pl.geo.row != pl.geo.pitch ? 1 : 0, pl.kern == Kern::none ? 0 : streaming(pl) ? 2 : 1, pl.tb_steps, pl.tb_f,
+                                  pl.deep_halo ? 1 : 0, pl.frame_fused ? 1 : 0, pl.lazy_lag ? 1 : 0, c->p.collision, c->p.arith};
         // (UNEXECUTED ON HARDWARE until a run with two GPUs exists: every box so far had one.)  The three blocks [mine | from LOW | from
         // HIGH] are built on the host and uploaded by ONE synchronous copy, so nothing on the null stream can race with the receives
         // that s_comm (a non-blocking stream) enqueues below; a failed send / receive still closes the RCCL group, and every failure
@@ -302,7 +303,7 @@ int lbm_comm_init(lbm_ctx* c, int nranks, int rank, const void* uid128) {
         ncclResult_t r = rccl().GroupStart();
         if (r == ncclSuccess) {
             for (int side = 0; side < 2 && r == ncclSuccess; ++side) {
-                if (!has_neighbour(c, side)) continue;
+                if (!has_neighbour(c->plan, side)) continue;
                 const int peer = side == LBM_SIDE_LOW ? rank - 1 : rank + 1;
                 r = rccl().Send(dev, NW, ncclInt32, peer, c->comm, c->s_comm);
                 if (r == ncclSuccess) r = rccl().Recv(dev + (1 + side) * NW, NW, ncclInt32, peer, c->comm, c->s_comm);
@@ -321,7 +322,7 @@ int lbm_comm_init(lbm_ctx* c, int nranks, int rank, const void* uid128) {
         static const char* what[NW] = {"ABI version", "nx", "ny", "dtype", "semantics", "turb", "row pitch", "layout", "steps-per-launch path (0 none, 1 tile, 2 streaming kernel)",
                                        "steps per launch", "frame width", "deep halo", "fused frame", "lazy lag", "collision", "arith"};
         for (int side = 0; side < 2; ++side) {
-            if (!has_neighbour(c, side)) continue;
+            if (!has_neighbour(c->plan, side)) continue;
             for (int i = 0; i < NW; ++i)
                 if (theirs[side * NW + i] != mine[i]) {
                     drop_comm();
@@ -338,7 +339,7 @@ int lbm_comm_init(lbm_ctx* c, int nranks, int rank, const void* uid128) {
 int lbm_comm_loopback(lbm_ctx* c) {
     if (!c) return LBM_ERR_INVALID;
     if (c->comm) return fail(c, LBM_ERR_STATE, "communicator already attached");
-    if (c->geo.y0 == 0 || c->geo.y0 + c->geo.ny == c->geo.NY)
+    if (c->plan.geo.y0 == 0 || c->plan.geo.y0 + c->plan.geo.ny == c->plan.geo.NY)
         return fail(c, LBM_ERR_INVALID, "lbm_comm_loopback needs a slab that touches neither the lid nor the bottom wall");
     if (!rccl().ok) return fail(c, LBM_ERR_COMM, rccl().err);
     HIP_TRY(c, hipSetDevice(c->p.device));

@@ -66,14 +66,14 @@ void convert_rows(D* dst, const S* src, size_t planes_nx, int ny, int NY, int y0
 }
 
 int host_to_stage(lbm_ctx* c, const void* host, int host_dtype, int planes) {
-    const int nx = c->geo.nx, ny = c->geo.ny, NY = c->geo.NY, y0 = c->geo.y0;
+    const int nx = c->plan.geo.nx, ny = c->plan.geo.ny, NY = c->plan.geo.NY, y0 = c->plan.geo.y0;
     const size_t rows = (size_t)planes * nx;
     if (host_dtype == c->p.dtype) {
-        HIP_TRY(c, hipMemcpy2D(c->stage, (size_t)ny * c->es, (const char*)host + (size_t)y0 * c->es, (size_t)NY * c->es,
-                               (size_t)ny * c->es, rows, hipMemcpyHostToDevice));
+        HIP_TRY(c, hipMemcpy2D(c->stage, (size_t)ny * c->plan.es, (const char*)host + (size_t)y0 * c->plan.es, (size_t)NY * c->plan.es,
+                               (size_t)ny * c->plan.es, rows, hipMemcpyHostToDevice));
         return LBM_OK;
     }
-    std::vector<char> tmp(rows * ny * c->es);
+    std::vector<char> tmp(rows * ny * c->plan.es);
     if (c->p.dtype == LBM_F32) convert_rows((float*)tmp.data(), (const double*)host, rows, ny, NY, y0, false);
     else convert_rows((double*)tmp.data(), (const float*)host, rows, ny, NY, y0, false);
     HIP_TRY(c, hipMemcpy(c->stage, tmp.data(), tmp.size(), hipMemcpyHostToDevice));
@@ -81,14 +81,14 @@ int host_to_stage(lbm_ctx* c, const void* host, int host_dtype, int planes) {
 }
 
 int stage_to_host(lbm_ctx* c, const void* stage, void* host, int host_dtype, int planes) {
-    const int nx = c->geo.nx, ny = c->geo.ny, NY = c->geo.NY, y0 = c->geo.y0;
+    const int nx = c->plan.geo.nx, ny = c->plan.geo.ny, NY = c->plan.geo.NY, y0 = c->plan.geo.y0;
     const size_t rows = (size_t)planes * nx;
     if (host_dtype == c->p.dtype) {
-        HIP_TRY(c, hipMemcpy2D((char*)host + (size_t)y0 * c->es, (size_t)NY * c->es, stage, (size_t)ny * c->es,
-                               (size_t)ny * c->es, rows, hipMemcpyDeviceToHost));
+        HIP_TRY(c, hipMemcpy2D((char*)host + (size_t)y0 * c->plan.es, (size_t)NY * c->plan.es, stage, (size_t)ny * c->plan.es,
+                               (size_t)ny * c->plan.es, rows, hipMemcpyDeviceToHost));
         return LBM_OK;
     }
-    std::vector<char> tmp(rows * ny * c->es);
+    std::vector<char> tmp(rows * ny * c->plan.es);
     HIP_TRY(c, hipMemcpy(tmp.data(), stage, tmp.size(), hipMemcpyDeviceToHost));
     if (c->p.dtype == LBM_F32) convert_rows((double*)host, (const float*)tmp.data(), rows, ny, NY, y0, true);
     else convert_rows((float*)host, (const double*)tmp.data(), rows, ny, NY, y0, true);
@@ -97,14 +97,14 @@ int stage_to_host(lbm_ctx* c, const void* stage, void* host, int host_dtype, int
 
 // grid of the host-layout <-> lattice kernels: tiles of trx<R>() columns x 32 rows
 template <typename R>
-dim3 grid_tiles(const lbm_ctx* c) { return dim3((c->geo.nx + trx<R>() - 1) / trx<R>(), (c->geo.ny + 31) / 32, c->batch); }
+dim3 grid_tiles(const lbm_ctx* c) { return dim3((c->plan.geo.nx + trx<R>() - 1) / trx<R>(), (c->plan.geo.ny + 31) / 32, c->plan.batch); }
 
 int export_fin(lbm_ctx* c) {
     return launch_variant(c, [&](auto v) {
         using VT = decltype(v);
         using R = typename VT::R;
         hipLaunchKernelGGL((k_export_fin<R, VT::SEM, coll_is_prom(VT::COLL)>), grid_tiles<R>(c), dim3(BLK), 0, c->s_compute, (const R*)c->lat[c->cur],
-                           c->geo, c->raw[c->cur], (R)c->p.uLB, (R*)c->stage, c->bstride);
+                           c->plan.geo, c->raw[c->cur], (R)c->p.uLB, (R*)c->stage, c->plan.bstride);
     });
 }
 
@@ -118,7 +118,7 @@ int export_macro(lbm_ctx* c) {
         using VT = decltype(v);
         using R = typename VT::R;
         hipLaunchKernelGGL((k_export_macro<R, VT::SEM, coll_is_prom(VT::COLL)>), grid_tiles<R>(c), dim3(BLK), 0, c->s_compute, (const R*)c->lat[which],
-                           c->geo, c->raw[which], (R)c->p.uLB, (R*)c->stage, c->bstride);
+                           c->plan.geo, c->raw[which], (R)c->p.uLB, (R*)c->stage, c->plan.bstride);
     });
 }
 
@@ -132,7 +132,7 @@ int export_tau(lbm_ctx* c) {
         using VT = decltype(v);
         using R = typename VT::R;
         hipLaunchKernelGGL((k_export_tau<R, coll_is_fast(VT::COLL), coll_is_prom(VT::COLL)>), grid_tiles<R>(c), dim3(BLK), 0, c->s_compute,
-                           (const R*)c->lat[which], c->geo, c->raw[which], relax_of<R>(c->p), batch_of<R>(c), c->p.turb, (R*)c->stage);
+                           (const R*)c->lat[which], c->plan.geo, c->raw[which], relax_of<R>(c->p), batch_of<R>(c), c->p.turb, (R*)c->stage);
     });
 }
 
@@ -145,8 +145,8 @@ int reduce_u(lbm_ctx* c) {
     return launch_variant(c, [&](auto v) {
         using VT = decltype(v);
         using R = typename VT::R;
-        hipLaunchKernelGGL((k_reduce_u<R, VT::SEM, coll_is_prom(VT::COLL)>), dim3(RED_BLOCKS, 1, c->batch), dim3(BLK), 0, c->s_compute,
-                           (const R*)c->lat[which], c->geo, c->raw[which], (R)c->p.uLB, c->bstride, c->red_dev);
+        hipLaunchKernelGGL((k_reduce_u<R, VT::SEM, coll_is_prom(VT::COLL)>), dim3(RED_BLOCKS, 1, c->plan.batch), dim3(BLK), 0, c->s_compute,
+                           (const R*)c->lat[which], c->plan.geo, c->raw[which], (R)c->p.uLB, c->plan.bstride, c->red_dev);
     });
 }
 
@@ -191,17 +191,19 @@ lbm_ctx* lbm_create(const lbm_params* p, char* err, size_t errlen) {
 
     hipDeviceProp_t prop;
     const int ncu = hipGetDeviceProperties(&prop, p->device) == hipSuccess && prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+    Plan plan;
     std::string plan_err;
-    lbm_ctx* c = plan_ctx(p, ncu, true, plan_err);
-    if (!c) return bail(plan_err);
-    const size_t bytes = c->lat_bytes;
+    if (!make_plan(*p, ncu, true, plan, plan_err)) return bail(plan_err);
+    lbm_ctx* c = new (std::nothrow) lbm_ctx(*p, plan);
+    if (!c) return bail("out of host memory");
+    const size_t bytes = c->plan.lat_bytes;
     auto cleanup = [&](const std::string& m) -> lbm_ctx* { lbm_destroy(c); return bail(m); };
     if ((e = hipStreamCreateWithFlags(&c->s_compute, hipStreamNonBlocking)) != hipSuccess) return cleanup("hipStreamCreate");
     {   // halo exchange stream at the highest priority: its (tiny) RCCL kernels must not queue behind the
         // thousands of workgroups of the interior kernel they are meant to overlap
         int lo = 0, hi = 0;
         (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
-        if (p->flags & LBM_FLAG_COMM_PRIORITY_OFF) hi = lo;   // A/B: same priority as the compute stream
+        if (!c->plan.comm_priority) hi = lo;   // A/B: same priority as the compute stream
         if ((e = hipStreamCreateWithPriority(&c->s_comm, hipStreamNonBlocking, hi)) != hipSuccess) return cleanup("hipStreamCreate");
     }
     // (the events between the two streams of this context order kernels of ONE device: no system-scope release with every record -- a
@@ -214,19 +216,19 @@ lbm_ctx* lbm_create(const lbm_params* p, char* err, size_t errlen) {
     if ((e = hipEventCreate(&c->ev_t0)) != hipSuccess) return cleanup("hipEventCreate");
     if ((e = hipEventCreate(&c->ev_t1)) != hipSuccess) return cleanup("hipEventCreate");
     // the two lattices (+ ftemp of the push scheme); the scratch lattices of the frame passes come on first use (ensure_scratch)
-    for (int i = 0; i < (c->push ? 3 : 2); ++i) {
+    for (int i = 0; i < (c->plan.push ? 3 : 2); ++i) {
         if ((e = hipMalloc(&c->lat[i], bytes)) != hipSuccess) return cleanup(std::string("hipMalloc(lattice): ") + hipGetErrorString(e));
         // on the compute stream: the streams are non-blocking, a null-stream memset would race with the kernels
         if ((e = hipMemsetAsync(c->lat[i], 0, bytes, c->s_compute)) != hipSuccess) return cleanup(std::string("hipMemset: ") + hipGetErrorString(e));
     }
-    if (c->batch > 1) {   // every lattice starts with the rates of lbm_params; lbm_set_relaxation() changes them one by one
-        const size_t rb = c->es == 4 ? sizeof(Relax<float>) : sizeof(Relax<double>);
-        if ((e = hipMalloc(&c->relax_dev, rb * c->batch)) != hipSuccess) return cleanup(std::string("hipMalloc(relaxation): ") + hipGetErrorString(e));
-        for (int i = 0; i < c->batch; ++i)
+    if (c->plan.batch > 1) {   // every lattice starts with the rates of lbm_params; lbm_set_relaxation() changes them one by one
+        const size_t rb = c->plan.es == 4 ? sizeof(Relax<float>) : sizeof(Relax<double>);
+        if ((e = hipMalloc(&c->relax_dev, rb * c->plan.batch)) != hipSuccess) return cleanup(std::string("hipMalloc(relaxation): ") + hipGetErrorString(e));
+        for (int i = 0; i < c->plan.batch; ++i)
             if (lbm_set_relaxation(c, i, p->omega, p->omegam, p->omega_e, p->omega_eps, p->omega_q) != LBM_OK) return cleanup(c->err);
     }
     if (lbm_init_equilibrium(c) != LBM_OK) return cleanup(c->err);
-    if (c->tail_tiles && warm_stream(c) != LBM_OK) return cleanup("warm-up launch of the streaming kernel");   // (see warm_stream)
+    if (c->plan.tail_tiles && warm_stream(c) != LBM_OK) return cleanup("warm-up launch of the streaming kernel");   // (see warm_stream)
     return c;
 }
 
@@ -262,11 +264,11 @@ int lbm_init_equilibrium(lbm_ctx* c) {
     if (rc) return rc;
     stats_free(c);
     c->cur = 0; c->raw[0] = 1; c->raw[1] = 1; c->nsteps = 0; c->lag = 0; c->lag_valid = false; c->thin_valid = false;
-    const dim3 g = grid_rows(c, c->geo.ny);
+    const dim3 g = grid_rows(c, c->plan.geo.ny);
     rc = launch_variant(c, [&](auto v) {
         using VT = decltype(v);
         using R = typename VT::R;
-        hipLaunchKernelGGL((k_init<R, coll_is_prom(VT::COLL)>), g, dim3(BLK), 0, c->s_compute, (R*)c->lat[0], c->geo, (R)c->p.uLB, c->p.turb, c->bstride);
+        hipLaunchKernelGGL((k_init<R, coll_is_prom(VT::COLL)>), g, dim3(BLK), 0, c->s_compute, (R*)c->lat[0], c->plan.geo, (R)c->p.uLB, c->p.turb, c->plan.bstride);
     });
     if (rc) return rc;
     return push_reset(c);
@@ -277,17 +279,17 @@ int lbm_set_state(lbm_ctx* c, const void* fin_host, int host_dtype) {
     HIP_TRY(c, hipSetDevice(c->p.device));
     int rc = sync_all(c);
     if (rc) return rc;
-    rc = ensure_stage(c, (size_t)12 * c->geo.nx * c->geo.ny * c->es * c->batch);
+    rc = ensure_stage(c, (size_t)12 * c->plan.geo.nx * c->plan.geo.ny * c->plan.es * c->plan.batch);
     if (rc) return rc;
-    rc = host_to_stage(c, fin_host, host_dtype, Q * c->batch);   // [B][9][nx][ny] is B * 9 planes
+    rc = host_to_stage(c, fin_host, host_dtype, Q * c->plan.batch);   // [B][9][nx][ny] is B * 9 planes
     if (rc) return rc;
     stats_free(c);
     c->cur = 0; c->raw[0] = 1; c->raw[1] = 1; c->nsteps = 0; c->lag = 0; c->lag_valid = false; c->thin_valid = false;
     rc = launch_variant(c, [&](auto v) {
         using VT = decltype(v);
         using R = typename VT::R;
-        hipLaunchKernelGGL((k_import<R, coll_is_prom(VT::COLL)>), grid_tiles<R>(c), dim3(BLK), 0, c->s_compute, (const R*)c->stage, (R*)c->lat[0], c->geo,
-                           (R)c->p.uLB, c->p.turb, c->bstride);
+        hipLaunchKernelGGL((k_import<R, coll_is_prom(VT::COLL)>), grid_tiles<R>(c), dim3(BLK), 0, c->s_compute, (const R*)c->stage, (R*)c->lat[0], c->plan.geo,
+                           (R)c->p.uLB, c->p.turb, c->plan.bstride);
     });
     if (rc) return rc;
     rc = push_reset(c);
@@ -297,18 +299,18 @@ int lbm_set_state(lbm_ctx* c, const void* fin_host, int host_dtype) {
 }
 
 int lbm_set_relaxation(lbm_ctx* c, int index, double omega, double omegam, double omega_e, double omega_eps, double omega_q) {
-    if (!c || index < 0 || index >= c->batch) return fail(c, LBM_ERR_INVALID, "lbm_set_relaxation: index out of range");
+    if (!c || index < 0 || index >= c->plan.batch) return fail(c, LBM_ERR_INVALID, "lbm_set_relaxation: index out of range");
     HIP_TRY(c, hipSetDevice(c->p.device));
     lbm_params q = c->p;
     q.omega = omega; q.omegam = omegam; q.omega_e = omega_e; q.omega_eps = omega_eps; q.omega_q = omega_q;
-    if (c->batch == 1) {   // rates travel by value with every launch
+    if (c->plan.batch == 1) {   // rates travel by value with every launch
         c->p = q;
         return LBM_OK;
     }
     // ordered behind the steps already enqueued: the copy goes through the compute stream (pageable source, so the call
     // returns only after the runtime has staged it)
     HIP_TRY(c, hipStreamSynchronize(c->s_comm));
-    if (c->es == 4) {
+    if (c->plan.es == 4) {
         const Relax<float> w = relax_of<float>(q);
         HIP_TRY(c, hipMemcpyAsync((Relax<float>*)c->relax_dev + index, &w, sizeof(w), hipMemcpyHostToDevice, c->s_compute));
     } else {
@@ -332,26 +334,26 @@ int lbm_get_fields(lbm_ctx* c, void* u_host, void* rho_host, void* fin_host, int
     HIP_TRY(c, hipSetDevice(c->p.device));
     int rc = sync_all(c);
     if (rc) return rc;
-    const size_t n = (size_t)c->geo.nx * c->geo.ny;
-    rc = ensure_stage(c, (size_t)12 * n * c->es * c->batch);
+    const size_t n = (size_t)c->plan.geo.nx * c->plan.geo.ny;
+    rc = ensure_stage(c, (size_t)12 * n * c->plan.es * c->plan.batch);
     if (rc) return rc;
     const size_t hes = host_dtype == LBM_F32 ? 4 : 8;
     if (u_host || rho_host) {
         rc = export_macro(c);
         if (rc) return rc;
         HIP_TRY(c, hipStreamSynchronize(c->s_compute));
-        for (int b = 0; b < c->batch; ++b) {   // staging of lattice b: [ux | uy | rho]; host: u[B][2][nx][NY], rho[B][nx][NY]
-            const char* st = (const char*)c->stage + (size_t)b * 3 * n * c->es;
-            const size_t hn = (size_t)c->geo.nx * c->geo.NY * hes;
+        for (int b = 0; b < c->plan.batch; ++b) {   // staging of lattice b: [ux | uy | rho]; host: u[B][2][nx][NY], rho[B][nx][NY]
+            const char* st = (const char*)c->stage + (size_t)b * 3 * n * c->plan.es;
+            const size_t hn = (size_t)c->plan.geo.nx * c->plan.geo.NY * hes;
             if (u_host) { rc = stage_to_host(c, st, (char*)u_host + (size_t)b * 2 * hn, host_dtype, 2); if (rc) return rc; }
-            if (rho_host) { rc = stage_to_host(c, st + 2 * n * c->es, (char*)rho_host + (size_t)b * hn, host_dtype, 1); if (rc) return rc; }
+            if (rho_host) { rc = stage_to_host(c, st + 2 * n * c->plan.es, (char*)rho_host + (size_t)b * hn, host_dtype, 1); if (rc) return rc; }
         }
     }
     if (fin_host) {
         rc = export_fin(c);
         if (rc) return rc;
         HIP_TRY(c, hipStreamSynchronize(c->s_compute));
-        rc = stage_to_host(c, c->stage, fin_host, host_dtype, Q * c->batch);
+        rc = stage_to_host(c, c->stage, fin_host, host_dtype, Q * c->plan.batch);
         if (rc) return rc;
     }
     return LBM_OK;
@@ -363,16 +365,16 @@ int lbm_mean_u(lbm_ctx* c, double* mean_out) {
     int rc = sync_all(c);
     if (rc) return rc;
     if (!c->red_dev) {
-        hipError_t e = hipMalloc((void**)&c->red_dev, ((size_t)RED_BLOCKS + 1) * c->batch * sizeof(double));
+        hipError_t e = hipMalloc((void**)&c->red_dev, ((size_t)RED_BLOCKS + 1) * c->plan.batch * sizeof(double));
         if (e != hipSuccess) return fail(c, LBM_ERR_NOMEM, std::string("hipMalloc(reduction): ") + hipGetErrorString(e));
     }
     rc = reduce_u(c);
     if (rc) return rc;
-    double* res = c->red_dev + (size_t)RED_BLOCKS * c->batch;
-    const double scale = 1.0 / (2.0 * (double)c->geo.nx * (double)c->geo.ny);
-    hipLaunchKernelGGL(k_reduce_final, dim3((c->batch + BLK - 1) / BLK), dim3(BLK), 0, c->s_compute, c->red_dev, RED_BLOCKS, c->batch, scale, res);
+    double* res = c->red_dev + (size_t)RED_BLOCKS * c->plan.batch;
+    const double scale = 1.0 / (2.0 * (double)c->plan.geo.nx * (double)c->plan.geo.ny);
+    hipLaunchKernelGGL(k_reduce_final, dim3((c->plan.batch + BLK - 1) / BLK), dim3(BLK), 0, c->s_compute, c->red_dev, RED_BLOCKS, c->plan.batch, scale, res);
     HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(mean_out, res, (size_t)c->batch * sizeof(double), hipMemcpyDeviceToHost, c->s_compute));
+    HIP_TRY(c, hipMemcpyAsync(mean_out, res, (size_t)c->plan.batch * sizeof(double), hipMemcpyDeviceToHost, c->s_compute));
     HIP_TRY(c, hipStreamSynchronize(c->s_compute));
     return LBM_OK;
 }
@@ -382,24 +384,24 @@ int lbm_get_tau(lbm_ctx* c, void* tau_host, int host_dtype) {
     HIP_TRY(c, hipSetDevice(c->p.device));
     int rc = sync_all(c);
     if (rc) return rc;
-    const size_t n = (size_t)c->geo.nx * c->geo.ny;
-    rc = ensure_stage(c, (size_t)12 * n * c->es * c->batch);
+    const size_t n = (size_t)c->plan.geo.nx * c->plan.geo.ny;
+    rc = ensure_stage(c, (size_t)12 * n * c->plan.es * c->plan.batch);
     if (rc) return rc;
     rc = export_tau(c);
     if (rc) return rc;
     HIP_TRY(c, hipStreamSynchronize(c->s_compute));
-    return stage_to_host(c, c->stage, tau_host, host_dtype, c->batch);
+    return stage_to_host(c, c->stage, tau_host, host_dtype, c->plan.batch);
 }
 
 int lbm_stats_begin(lbm_ctx* c, int every) {
     if (!c || every < 0) return fail(c, LBM_ERR_INVALID, "lbm_stats_begin: bad argument");
-    if (every > 0 && is_slab(c))
+    if (every > 0 && is_slab(c->plan))
         return fail(c, LBM_ERR_STATE, "lbm_stats_begin: no automatic sampling on a slab (every = 0, and lbm_stats_sample at the same step "
                                       "counts on every slab)");
     HIP_TRY(c, hipSetDevice(c->p.device));
     int rc = sync_all(c);
     if (rc) return rc;
-    const size_t bytes = (size_t)c->batch * 6 * c->geo.ny * (2 * ((c->geo.nx + 1) / 2)) * sizeof(double);
+    const size_t bytes = (size_t)c->plan.batch * 6 * c->plan.geo.ny * (2 * ((c->plan.geo.nx + 1) / 2)) * sizeof(double);
     if (!c->stats_dev) {
         hipError_t e = hipMalloc((void**)&c->stats_dev, bytes);
         if (e != hipSuccess) {
@@ -435,11 +437,11 @@ int lbm_stats_get(lbm_ctx* c, double* mean_u, double* mean_rho, double* second, 
     if (rc) return rc;
     if (count) *count = c->stats_count;
     if (c->stats_count == 0) return LBM_OK;
-    const int nx = c->geo.nx, ny = c->geo.ny, NY = c->geo.NY, y0 = c->geo.y0, nxa = 2 * ((nx + 1) / 2);
+    const int nx = c->plan.geo.nx, ny = c->plan.geo.ny, NY = c->plan.geo.NY, y0 = c->plan.geo.y0, nxa = 2 * ((nx + 1) / 2);
     const size_t hn = (size_t)nx * NY, dn = (size_t)ny * nxa;
     const double n = (double)c->stats_count;
     std::vector<double> pl(dn);
-    for (int b = 0; b < c->batch; ++b)
+    for (int b = 0; b < c->plan.batch; ++b)
         for (int q = 0; q < 6; ++q) {   // device [b][q][y][x] -> host [b][2][x][Y] (u), [b][x][Y] (rho), [b][3][x][Y] (second moments)
             double* dst = q < 2 ? (mean_u ? mean_u + ((size_t)b * 2 + q) * hn : nullptr)
                         : q == 2 ? (mean_rho ? mean_rho + (size_t)b * hn : nullptr)
@@ -492,7 +494,7 @@ int lbm_fma_rate(lbm_ctx* c, double ms_total, double* tflops) {
     if (!c || !tflops || !(ms_total > 0) || ms_total > 2000) return fail(c, LBM_ERR_INVALID, "lbm_fma_rate: bad argument (0 < ms <= 2000)");
     HIP_TRY(c, hipSetDevice(c->p.device));
     float* sink = nullptr;
-    const int blocks = c->ncu * 8, iters = 4096;
+    const int blocks = c->plan.ncu * 8, iters = 4096;
     HIP_TRY(c, hipMalloc((void**)&sink, (size_t)blocks * BLK * sizeof(float)));
     auto run = [&](int n, float* ms) -> hipError_t {
         (void)hipEventRecord(c->ev_t0, c->s_compute);

@@ -1,5 +1,6 @@
-// lbm_host.hpp -- what the host-side translation units of liblbm_hip.so share: the context (struct lbm_ctx), the lazily bound
-// RCCL table, the error macros, the variant dispatcher and the prototypes of every host function that crosses a unit.
+// lbm_host.hpp -- what the host-side translation units of liblbm_hip.so share: the launch plan (struct Plan), the context (struct
+// lbm_ctx), the lazily bound RCCL table, the error macros, the variant dispatcher and the prototypes of every host function that
+// crosses a unit.
 //   lbm_hip.hip     context life cycle, state upload / field export, probes              (C ABI: create .. get_tau, probes)
 //   lbm_plan.hip    parameter validation, launch planning, unit sequence, the dry run    (C ABI: next_unit, describe, plan)
 //   lbm_launch.hip  kernel launches and the step loop (single / multi-step units, lag)   (C ABI: step*, time_steps)
@@ -38,12 +39,50 @@ constexpr int NLAT = 10;
 //   stream_pairs  k_stream_pairs: ... and two rows per wave (twelve waves, up to 10 steps per launch; a lone lattice)
 enum class Kern { none, tile2, tile, stream, stream_walls, stream_pairs };
 
-struct lbm_ctx {
-    lbm_params p{};
+// The launch plan: which kernels run, in which units, with which halo protocol.  A pure function of lbm_params and the device's
+// compute units (make_plan, lbm_plan.hip -- the only writer), so that neighbouring slabs derive the same one (lbm_comm_init
+// cross-checks) and the dry run lbm_plan describes what lbm_create builds.  A context holds it const.
+struct Plan {
+    // ---- geometry and sizes
     int es = 0;  // element size
     Geo geo{};
-    void* lat[NLAT] = {};       // [0], [1]: the two lattices; [2] .. [8]: frame scratch of the multi-step; [LAT_LAG]: see above
+    int nplanes = Q;            // planes of a lattice: the populations (+ the two Smagorinsky history planes)
+    int semantics = LBM_SEM_MRT_GPU;   // lbm_params.semantics, for the readers of the plan alone (describe_plan)
+    int batch = 1;              // independent lattices per buffer (lbm_params.batch)
+    long long bstride = 0;      // elements from one lattice of the batch to the next
     size_t lat_bytes = 0;
+    int ncu = 256;              // compute units of the device (the streaming kernel runs one workgroup per CU)
+    // ---- kernel choice
+    bool use_vec = false;       // vector kernel (MRT_GPU.py semantics, nx multiple of the vector width)
+    bool use_nt = false;        // non-temporal loads/stores: lattice far larger than the 256 MiB Infinity Cache
+    bool push = false;          // LBM_KERNEL_PUSH: the reference's two-launch push scheme (lat[0], lat[1]: fin ping-pong; lat[2]: ftemp)
+    Kern kern = Kern::none;     // several steps per launch (temporal blocking): by which kernel
+    int tb_steps = 2;           // steps per launch: two, three to five (tile kernel), up to eight (streaming kernel), ten (pairs)
+    int tb_f = TB_F;            // frame width
+    bool tail_tiles = false;    // streaming contexts (lone, fp32): units of 3 .. 5 steps through the tile kernel (A/B: LBM_FLAG_NO_TAIL_TILES)
+    // ---- the frame
+    bool frame_fused = true;    // all frame passes of a multi-step in one launch (LBM_FLAG_FRAME_UNFUSED: one launch per pass)
+    bool frame_lds = true;      // ... keeping the intermediate passes in LDS when their windows fit (LBM_FLAG_NO_FRAME_LDS: scratch lattices)
+    bool frame_wide = true;     // frame passes through the scratch lattices: workgroups of 1024 threads (A/B: LBM_FLAG_FRAME_NARROW)
+    bool frame_beside = false;  // Kern::stream on a lone lattice: the frame passes as a kernel of their own on the second stream, BESIDE the
+                                // streaming workgroups (no LDS, ~70 VGPRs: fits next to them when the streaming kernel leaves registers)
+    int frame_seg = 64;         // cells of the frame per workgroup of the fused frame passes (lbm_params.frame_seg)
+    // ---- switches
+    bool deep_halo = false;     // multi-steps between slabs exchange once per launch (MRT_GPU semantics; LBM_FLAG_NO_DEEP_HALO disables)
+    bool lazy_lag = true;       // (LBM_FLAG_EAGER_LAG: every lbm_step call ends with a single step instead)
+    bool xcd_bands = true;      // streaming kernel: contiguous runs of segments per XCD (A/B: LBM_FLAG_NO_XCD_BANDS)
+    bool edge_first = true;     // streaming kernel between slabs: release the bulk launch behind the edge launch (A/B: LBM_FLAG_NO_EDGE_FIRST)
+    bool edge_reserve = true;   // streaming kernel between slabs: a one-round bulk launch leaves CUs to the edge workgroups (A/B: LBM_FLAG_NO_EDGE_RESERVE)
+    bool comm_priority = true;  // the halo exchange stream at the highest priority (A/B: LBM_FLAG_COMM_PRIORITY_OFF, the compute stream's)
+};
+
+// Run state.  What was decided once is in `plan`; p stays for the fields later code branches on (dtype, collision, semantics, turb,
+// arith, device) and for the relaxation rates, which lbm_set_relaxation rewrites.
+struct lbm_ctx {
+    lbm_ctx(const lbm_params& p_, const Plan& plan_) : p(p_), plan(plan_) {}
+    lbm_params p;
+    const Plan plan;
+    void* lat[NLAT] = {};       // [0], [1]: the two lattices; [2] .. [8]: frame scratch of the multi-step; [LAT_LAG]: see above
     int raw[NLAT] = {1, 1, 0, 0, 0, 0, 0, 0, 0, 0};
     int cur = 0;  // lat[cur] is the source of the next step
     long long nsteps = 0;
@@ -53,7 +92,6 @@ struct lbm_ctx {
     // lbm_get_tau ask (lag_valid: done already) -- bit-identical, and off the path of lbm_step.
     int lag = 0;
     bool lag_valid = false;
-    bool lazy_lag = true;       // (LBM_FLAG_EAGER_LAG: every lbm_step call ends with a single step instead)
     hipStream_t s_compute = nullptr, s_comm = nullptr;
     hipEvent_t ev_edges = nullptr, ev_halo = nullptr, ev_int = nullptr, ev_go = nullptr, ev_t0 = nullptr, ev_t1 = nullptr;
     void* stage = nullptr;
@@ -68,29 +106,9 @@ struct lbm_ctx {
     ncclComm_t comm = nullptr;
     int nranks = 1, rank = 0;
     bool thin_valid = false;    // the one-row halo of lat[cur] has been exchanged (by the RCCL path, on s_comm)
-    bool frame_lds = true;      // ... keeping the intermediate passes in LDS when their windows fit (LBM_FLAG_NO_FRAME_LDS: scratch lattices)
-    int frame_seg = 64;         // cells of the frame per workgroup of the fused frame passes (lbm_params.frame_seg)
-    bool frame_fused = true;    // all frame passes of a multi-step in one launch (LBM_FLAG_FRAME_UNFUSED: one launch per pass)
-    bool deep_halo = false;     // multi-steps between slabs exchange once per launch (MRT_GPU semantics; LBM_FLAG_NO_DEEP_HALO disables)
     bool loopback = false;      // diagnostic: 1-rank communicator, the slab exchanges halos with itself
-    bool use_vec = false;       // vector kernel (MRT_GPU.py semantics, nx multiple of the vector width)
-    bool use_nt = false;        // non-temporal loads/stores: lattice far larger than the 256 MiB Infinity Cache
-    bool push = false;          // LBM_KERNEL_PUSH: the reference's two-launch push scheme (lat[0], lat[1]: fin ping-pong; lat[2]: ftemp)
-    Kern kern = Kern::none;     // several steps per launch (temporal blocking): by which kernel
     int edge_rows = 0;          // rows next to each interface of lat[cur] that work on s_comm wrote (and s_comm's stream order therefore covers):
                                 // the frame width after a multi-step unit, 1 after a single step, 0 at the start of a call (see exchange_ready)
-    bool tail_tiles = false;    // streaming contexts (lone, fp32): units of 3 .. 5 steps through the tile kernel (A/B: LBM_FLAG_NO_TAIL_TILES)
-    bool xcd_bands = true;      // streaming kernel: contiguous runs of segments per XCD (A/B: LBM_FLAG_NO_XCD_BANDS)
-    bool edge_reserve = true;   // streaming kernel between slabs: a one-round bulk launch leaves CUs to the edge workgroups (A/B: LBM_FLAG_NO_EDGE_RESERVE)
-    bool edge_first = true;     // streaming kernel between slabs: release the bulk launch behind the edge launch (A/B: LBM_FLAG_NO_EDGE_FIRST)
-    bool frame_wide = true;     // frame passes through the scratch lattices: workgroups of 1024 threads (A/B: LBM_FLAG_FRAME_NARROW)
-    bool frame_beside = false;  // Kern::stream on a lone lattice: the frame passes as a kernel of their own on the second stream, BESIDE the
-                                // streaming workgroups (no LDS, ~70 VGPRs: fits next to them when the streaming kernel leaves registers)
-    int ncu = 256;              // compute units of the device (the streaming kernel runs one workgroup per CU)
-    int tb_steps = 2;           // steps per launch: two, three to five (tile kernel), up to eight (streaming kernel), ten (pairs)
-    int tb_f = TB_F;            // frame width
-    int batch = 1;              // independent lattices per buffer (lbm_params.batch)
-    long long bstride = 0;      // elements from one lattice of the batch to the next
     void* relax_dev = nullptr;  // batch > 1: Relax<real>[batch] on the device
     // The units of a lone lattice that need no second stream (frame and tiles / the walls inside: ONE launch on s_compute) neither wait for
     // ev_edges nor record ev_int -- two event operations per unit, 7 - 8 % of a launch-bound lattice's step (160^2: 3.51 -> 3.24 us).  Instead:
@@ -144,6 +162,15 @@ inline int flush_int(lbm_ctx* c) {
     }
     return LBM_OK;
 }
+// ev_edges, waited for lazily (lbm_ctx::edges_pending): whoever puts work on s_compute that needs what s_comm wrote (the frame work of an
+// earlier multi-step unit) calls this first
+inline int join_edges(lbm_ctx* c) {
+    if (c->edges_pending) {
+        HIP_TRY(c, hipStreamWaitEvent(c->s_compute, c->ev_edges, 0));
+        c->edges_pending = false;
+    }
+    return LBM_OK;
+}
 
 template <typename R>
 Relax<R> relax_of(const lbm_params& p) {
@@ -155,7 +182,7 @@ Relax<R> relax_of(const lbm_params& p) {
 
 template <typename R>
 Batch<R> batch_of(const lbm_ctx* c) {
-    return Batch<R>{c->bstride, c->batch > 1 ? (const Relax<R>*)c->relax_dev : nullptr};
+    return Batch<R>{c->plan.bstride, c->plan.batch > 1 ? (const Relax<R>*)c->relax_dev : nullptr};
 }
 
 // output lattices of the S frame passes lat[from] -> lat[to]: the scratch lattices (null when never needed, see ensure_scratch), then lat[to]
@@ -167,7 +194,7 @@ FramePtrs<R> frame_ptrs(const lbm_ctx* c, int from, int to, int S) {
     return fp;
 }
 
-inline dim3 grid_rows(const lbm_ctx* c, int nrows) { return dim3((c->geo.nx + BLK - 1) / BLK, nrows, c->batch); }
+inline dim3 grid_rows(const lbm_ctx* c, int nrows) { return dim3((c->plan.geo.nx + BLK - 1) / BLK, nrows, c->plan.batch); }
 
 // Run-time parameters -> compile-time kernel variant (real type, collision operator, semantics, Smagorinsky).
 template <typename R_, int COLL_, int SEM_, bool TURB_>
@@ -248,14 +275,15 @@ bool spin_until_ready(Q&& query) {
 // Is there a slab beyond this side?  Geometry decides (the slab does not touch the lid / the bottom wall there): the frame
 // passes of a multi-step extend into the ghost rows of such a side whatever moves the rows -- RCCL between ranks
 // (lbm_comm_init checks that rank r holds the r-th slab), the loopback diagnostic, or the caller (lbm_halo_*_rows).
-inline bool has_neighbour(const lbm_ctx* c, int side) {
-    return side == LBM_SIDE_LOW ? c->geo.y0 > 0 : c->geo.y0 + c->geo.ny < c->geo.NY;
+inline bool has_neighbour(const Plan& pl, int side) {
+    return side == LBM_SIDE_LOW ? pl.geo.y0 > 0 : pl.geo.y0 + pl.geo.ny < pl.geo.NY;
 }
-inline bool is_slab(const lbm_ctx* c) { return has_neighbour(c, LBM_SIDE_LOW) || has_neighbour(c, LBM_SIDE_HIGH); }
+inline int neighbours(const Plan& pl) { return (has_neighbour(pl, LBM_SIDE_LOW) ? 1 : 0) + (has_neighbour(pl, LBM_SIDE_HIGH) ? 1 : 0); }
+inline bool is_slab(const Plan& pl) { return neighbours(pl) > 0; }
 // the library itself moves the halos (RCCL between ranks, or the one-GPU loopback)
 inline bool own_transport(const lbm_ctx* c) { return c->comm != nullptr && (c->nranks > 1 || c->loopback); }
-inline bool streaming(const lbm_ctx* c) { return c->kern >= Kern::stream; }
-inline bool walls_inside(const lbm_ctx* c) { return c->kern >= Kern::stream_walls; }
+inline bool streaming(const Plan& pl) { return pl.kern >= Kern::stream; }
+inline bool walls_inside(const Plan& pl) { return pl.kern >= Kern::stream_walls; }
 
 // How a launch unit of S >= 2 steps runs (unit_route):
 //   one_launch    a lone lattice: frame and bulk (or the walls inside) in ONE launch on s_compute
@@ -287,15 +315,15 @@ int sync_all(lbm_ctx* c);
 int host_to_stage(lbm_ctx* c, const void* host, int host_dtype, int planes);
 int stage_to_host(lbm_ctx* c, const void* stage, void* host, int host_dtype, int planes);
 // lbm_plan.hip
-bool frame_lds_fits(const lbm_ctx* c, int S, bool deep_rows, int extra = 0, long long budget = FRAME_LDS_BYTES);
+bool frame_lds_fits(const Plan& pl, int S, bool deep_rows, int extra = 0, long long budget = FRAME_LDS_BYTES);
 int pairs_waves(int S);
-StreamPlan plan_stream_on(const lbm_ctx* c, int S, int ncu, long long* cost_out);
-StreamPlan plan_stream(const lbm_ctx* c, int S);
-bool lag_replayable(const lbm_ctx* c, int S);
-int unit_steps(const lbm_ctx* c, int left, bool raw);
-Route unit_route(const lbm_ctx* c, int S, bool replay);
+StreamPlan plan_stream_on(const Plan& pl, int S, int ncu, long long* cost_out);
+StreamPlan plan_stream(const Plan& pl, int S);
+bool lag_replayable(const Plan& pl, int S);
+int unit_steps(const Plan& pl, int left, bool raw, bool own_transport);
+Route unit_route(const Plan& pl, int S, bool replay);
 std::string validate_params(const lbm_params* p);
-lbm_ctx* plan_ctx(const lbm_params* p, int ncu, bool device, std::string& err_out);
+bool make_plan(const lbm_params& p, int ncu, bool device, Plan& pl, std::string& err);
 // lbm_launch.hip
 int ensure_scratch(lbm_ctx* c, int n);
 int launch_rows(lbm_ctx* c, int from, int to, int row0, int stride, int nrows, hipStream_t s);

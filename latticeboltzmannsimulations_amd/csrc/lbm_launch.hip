@@ -14,12 +14,12 @@ int ensure_scratch(lbm_ctx* c, int n) {
     bool fresh = false;
     for (int i = 2; i < 2 + n && i < LAT_LAG; ++i) {
         if (c->lat[i]) continue;
-        hipError_t e = hipMalloc(&c->lat[i], c->lat_bytes);
+        hipError_t e = hipMalloc(&c->lat[i], c->plan.lat_bytes);
         if (e != hipSuccess) {
             c->lat[i] = nullptr;
             return fail(c, LBM_ERR_NOMEM, std::string("hipMalloc(scratch lattice of the frame passes): ") + hipGetErrorString(e));
         }
-        HIP_TRY(c, hipMemsetAsync(c->lat[i], 0, c->lat_bytes, c->s_compute));
+        HIP_TRY(c, hipMemsetAsync(c->lat[i], 0, c->plan.lat_bytes, c->s_compute));
         fresh = true;
     }
     if (fresh) HIP_TRY(c, hipStreamSynchronize(c->s_compute));
@@ -35,18 +35,18 @@ int launch_rows(lbm_ctx* c, int from, int to, int row0, int stride, int nrows, h
         const R* src = (const R*)c->lat[from];
         R* dst = (R*)c->lat[to];
         const int raw = c->raw[from];
-        if (VT::SEM == SEM_GPU && c->use_vec) {
+        if (VT::SEM == SEM_GPU && c->plan.use_vec) {
             constexpr int V = 16 / (int)sizeof(R);
-            const int nxb = (c->geo.nx / V + BLK - 1) / BLK, nblocks = nxb * nrows;
-            if (c->use_nt)
-                hipLaunchKernelGGL((k_step_vec<R, VT::COLL, V, true, VT::TURB>), dim3(nblocks, c->batch), dim3(BLK), 0, s, src, dst, c->geo,
+            const int nxb = (c->plan.geo.nx / V + BLK - 1) / BLK, nblocks = nxb * nrows;
+            if (c->plan.use_nt)
+                hipLaunchKernelGGL((k_step_vec<R, VT::COLL, V, true, VT::TURB>), dim3(nblocks, c->plan.batch), dim3(BLK), 0, s, src, dst, c->plan.geo,
                                    relax_of<R>(c->p), batch_of<R>(c), raw, row0, stride, nxb, nblocks);
             else
-                hipLaunchKernelGGL((k_step_vec<R, VT::COLL, V, false, VT::TURB>), dim3(nblocks, c->batch), dim3(BLK), 0, s, src, dst, c->geo,
+                hipLaunchKernelGGL((k_step_vec<R, VT::COLL, V, false, VT::TURB>), dim3(nblocks, c->plan.batch), dim3(BLK), 0, s, src, dst, c->plan.geo,
                                    relax_of<R>(c->p), batch_of<R>(c), raw, row0, stride, nxb, nblocks);
         } else {
             hipLaunchKernelGGL((k_step_generic<R, VT::COLL, VT::SEM, VT::TURB>), grid_rows(c, nrows), dim3(BLK), 0, s, src, dst,
-                               c->geo, relax_of<R>(c->p), batch_of<R>(c), raw, row0, stride);
+                               c->plan.geo, relax_of<R>(c->p), batch_of<R>(c), raw, row0, stride);
         }
     });
 }
@@ -57,10 +57,10 @@ int launch_frame(lbm_ctx* c, int from, int to, int W, hipStream_t s, int elo, in
         using VT = decltype(v);
         using R = typename VT::R;
         constexpr int V = 16 / (int)sizeof(R);
-        const int vec_rows = VT::SEM == SEM_GPU && c->use_vec && c->geo.nx % V == 0 ? 1 : 0;   // row strips by vector cells
-        const long long cells = (2LL * W + elo + ehi) * (vec_rows ? c->geo.nx / V : c->geo.nx) + 2LL * W * (c->geo.ny - 2 * W);
-        hipLaunchKernelGGL((k_step_frame<R, VT::COLL, VT::SEM, VT::TURB>), dim3((unsigned)((cells + BLK - 1) / BLK), c->batch), dim3(BLK), 0, s,
-                           (const R*)c->lat[from], (R*)c->lat[to], c->geo, relax_of<R>(c->p), batch_of<R>(c), W, elo, ehi, vec_rows);
+        const int vec_rows = VT::SEM == SEM_GPU && c->plan.use_vec && c->plan.geo.nx % V == 0 ? 1 : 0;   // row strips by vector cells
+        const long long cells = (2LL * W + elo + ehi) * (vec_rows ? c->plan.geo.nx / V : c->plan.geo.nx) + 2LL * W * (c->plan.geo.ny - 2 * W);
+        hipLaunchKernelGGL((k_step_frame<R, VT::COLL, VT::SEM, VT::TURB>), dim3((unsigned)((cells + BLK - 1) / BLK), c->plan.batch), dim3(BLK), 0, s,
+                           (const R*)c->lat[from], (R*)c->lat[to], c->plan.geo, relax_of<R>(c->p), batch_of<R>(c), W, elo, ehi, vec_rows);
     });
 }
 
@@ -73,34 +73,34 @@ struct FrameLayout {
     bool in_lds;
 };
 static int frame_layout(lbm_ctx* c, FrameLayout& fl, int S, int ybeg, int yend, long long budget, bool deep_rows, int extra, bool with_frame = true) {
-    fl.F = c->tb_f;
-    fl.L = c->frame_seg;
-    fl.nsegx = frame_segs(c->geo.nx, fl.L);
+    fl.F = c->plan.tb_f;
+    fl.L = c->plan.frame_seg;
+    fl.nsegx = frame_segs(c->plan.geo.nx, fl.L);
     fl.nsegy = frame_segs(yend - ybeg, fl.L);
     fl.nframe = with_frame ? 2 * fl.nsegx + 2 * fl.nsegy : 0;
-    fl.in_lds = frame_lds_fits(c, S, deep_rows, extra, budget);
+    fl.in_lds = frame_lds_fits(c->plan, S, deep_rows, extra, budget);
     return with_frame && !fl.in_lds ? ensure_scratch(c, S - 1) : LBM_OK;
 }
 
 // extra: rows of the neighbours' side that the row strips own on top of the slab's (see frame_passes)
 int launch_frame_multi(lbm_ctx* c, int from, int to, int S, hipStream_t s, bool lo, bool hi, int extra) {
     // (beside the streaming kernel: k_frame_beside has no LDS, its passes go through the scratch lattices)
-    const bool beside = c->frame_beside && !lo && !hi && c->batch == 1;
+    const bool beside = c->plan.frame_beside && !lo && !hi && c->plan.batch == 1;
     FrameLayout fl;
-    const int rc = frame_layout(c, fl, S, c->tb_f, c->geo.ny - c->tb_f, beside ? 0 : FRAME_LDS_BYTES, lo || hi, extra);
+    const int rc = frame_layout(c, fl, S, c->plan.tb_f, c->plan.geo.ny - c->plan.tb_f, beside ? 0 : FRAME_LDS_BYTES, lo || hi, extra);
     if (rc) return rc;
     return launch_variant(c, [&](auto v) {
         using VT = decltype(v);
         using R = typename VT::R;
         const FramePtrs<R> fp = frame_ptrs<R>(c, from, to, S);
         if (beside)
-            hipLaunchKernelGGL((k_frame_beside<R, VT::COLL, VT::SEM, VT::TURB>), dim3(fl.nframe), dim3(BLK), 0, s, fp, c->geo, relax_of<R>(c->p), fl.F, S,
+            hipLaunchKernelGGL((k_frame_beside<R, VT::COLL, VT::SEM, VT::TURB>), dim3(fl.nframe), dim3(BLK), 0, s, fp, c->plan.geo, relax_of<R>(c->p), fl.F, S,
                                fl.nsegx, fl.nsegy, fl.L);
-        else if (!fl.in_lds && c->frame_wide)
-            hipLaunchKernelGGL((k_frame_multi<R, VT::COLL, VT::SEM, VT::TURB, 1024>), dim3(fl.nframe, c->batch), dim3(1024), 0, s, fp, c->geo,
+        else if (!fl.in_lds && c->plan.frame_wide)
+            hipLaunchKernelGGL((k_frame_multi<R, VT::COLL, VT::SEM, VT::TURB, 1024>), dim3(fl.nframe, c->plan.batch), dim3(1024), 0, s, fp, c->plan.geo,
                                relax_of<R>(c->p), batch_of<R>(c), fl.F, S, fl.nsegx, fl.nsegy, lo ? 1 + extra : 0, hi ? 1 + extra : 0, fl.L, 0);
         else
-            hipLaunchKernelGGL((k_frame_multi<R, VT::COLL, VT::SEM, VT::TURB, BLK>), dim3(fl.nframe, c->batch), dim3(BLK), 0, s, fp, c->geo,
+            hipLaunchKernelGGL((k_frame_multi<R, VT::COLL, VT::SEM, VT::TURB, BLK>), dim3(fl.nframe, c->plan.batch), dim3(BLK), 0, s, fp, c->plan.geo,
                                relax_of<R>(c->p), batch_of<R>(c), fl.F, S, fl.nsegx, fl.nsegy, lo ? 1 + extra : 0, hi ? 1 + extra : 0, fl.L,
                                fl.in_lds ? 1 : 0);
     });
@@ -114,7 +114,7 @@ static int launch_k_stream(lbm_ctx* c, int from, int to, hipStream_t s, int S, c
         using VT = decltype(v);
         using R = typename VT::R;
         hipLaunchKernelGGL((k_stream<R, VT::COLL, VT::SEM, VT::TURB>), dim3(fl.nframe + pl.nstrips * nseg), dim3(ST_NT), 0, s, (const R*)c->lat[from],
-                           (R*)c->lat[to], c->geo, relax_of<R>(c->p), S, fl.F, c->geo.nx - fl.F, ye, pl.nstrips, pl.H, frame_ptrs<R>(c, from, to, S),
+                           (R*)c->lat[to], c->plan.geo, relax_of<R>(c->p), S, fl.F, c->plan.geo.nx - fl.F, ye, pl.nstrips, pl.H, frame_ptrs<R>(c, from, to, S),
                            fl.nframe, fl.nsegx, fl.nsegy, fl.L, fl.in_lds ? 1 : 0, lo, hi, bands, xcd_bands ? 1 : 0);
     });
 }
@@ -123,44 +123,44 @@ static int launch_k_stream(lbm_ctx* c, int from, int to, hipStream_t s, int S, c
 // rows [ybeg, yend) between its edge bands (bands = 0: the bulk launch), or over the interface bands `bands` (bit 0: low, bit 1: high)
 // alone, each of which starts elo / ehi rows inside the neighbour's rows (the edge launch).
 static int launch_walls(lbm_ctx* c, int from, int to, hipStream_t s, int S, int ybeg, int yend, int bands, int elo, int ehi) {
-    const StreamPlan pl = plan_stream(c, S);
-    const int xcd = c->xcd_bands ? 1 : 0;
+    const StreamPlan pl = plan_stream(c->plan, S);
+    const int xcd = c->plan.xcd_bands ? 1 : 0;
     return launch_variant(c, [&](auto v) {
         using VT = decltype(v);
         using R = typename VT::R;
         if constexpr (VT::SEM == SEM_GPU) {
             const R* src = (const R*)c->lat[from];
             R* dst = (R*)c->lat[to];
-            if (is_slab(c))
+            if (is_slab(c->plan))
                 hipLaunchKernelGGL((k_stream_walls_slab<R, VT::COLL, VT::TURB>), dim3(pl.nstrips * (bands ? (bands & 1) + (bands >> 1) : pl.nsegy)),
-                                   dim3(ST_NT), 0, s, src, dst, c->geo, relax_of<R>(c->p), S, pl.nstrips, pl.H, bands ? 0 : xcd, ybeg, yend, bands,
-                                   elo, ehi, bands ? c->tb_f : 0);
+                                   dim3(ST_NT), 0, s, src, dst, c->plan.geo, relax_of<R>(c->p), S, pl.nstrips, pl.H, bands ? 0 : xcd, ybeg, yend, bands,
+                                   elo, ehi, bands ? c->plan.tb_f : 0);
             else if constexpr (coll_is_prom(VT::COLL)) {   // (not compiled for the promoted operators: plan_kernel refuses stream_pairs with them)
-                hipLaunchKernelGGL((k_stream_walls<R, VT::COLL, VT::TURB>), dim3(pl.nstrips * pl.nsegy), dim3(ST_NT), 0, s, src, dst, c->geo,
+                hipLaunchKernelGGL((k_stream_walls<R, VT::COLL, VT::TURB>), dim3(pl.nstrips * pl.nsegy), dim3(ST_NT), 0, s, src, dst, c->plan.geo,
                                    relax_of<R>(c->p), S, pl.nstrips, pl.H, xcd);
-            } else if (c->kern == Kern::stream_pairs)
+            } else if (c->plan.kern == Kern::stream_pairs)
                 hipLaunchKernelGGL((k_stream_pairs<R, VT::COLL, VT::TURB>), dim3(pl.nstrips * pl.nsegy), dim3(64 * pairs_waves(S)), 0, s, src, dst,
-                                   c->geo, relax_of<R>(c->p), S, pl.nstrips, pl.H, xcd);
+                                   c->plan.geo, relax_of<R>(c->p), S, pl.nstrips, pl.H, xcd);
             else
-                hipLaunchKernelGGL((k_stream_walls<R, VT::COLL, VT::TURB>), dim3(pl.nstrips * pl.nsegy), dim3(ST_NT), 0, s, src, dst, c->geo,
+                hipLaunchKernelGGL((k_stream_walls<R, VT::COLL, VT::TURB>), dim3(pl.nstrips * pl.nsegy), dim3(ST_NT), 0, s, src, dst, c->plan.geo,
                                    relax_of<R>(c->p), S, pl.nstrips, pl.H, xcd);
         }
     });
 }
 
 int launch_stream(lbm_ctx* c, int from, int to, hipStream_t s, int S, bool with_frame) {
-    const int F = c->tb_f, ny = c->geo.ny;
-    if (walls_inside(c)) {
+    const int F = c->plan.tb_f, ny = c->plan.geo.ny;
+    if (walls_inside(c->plan)) {
         // walls included, no frame at all: the whole lattice in one launch (with_frame), or a slab's rows between its edge bands
-        const bool slab = is_slab(c);
+        const bool slab = is_slab(c->plan);
         if (slab == with_frame) return fail(c, LBM_ERR_STATE, "internal: the streaming kernel with the walls inside takes a whole lone lattice or a slab's bulk rows");
-        return launch_walls(c, from, to, s, S, has_neighbour(c, LBM_SIDE_LOW) ? F : 0, ny - (has_neighbour(c, LBM_SIDE_HIGH) ? F : 0), 0, 0, 0);
+        return launch_walls(c, from, to, s, S, has_neighbour(c->plan, LBM_SIDE_LOW) ? F : 0, ny - (has_neighbour(c->plan, LBM_SIDE_HIGH) ? F : 0), 0, 0, 0);
     }
     FrameLayout fl;
     const int rc = frame_layout(c, fl, S, F, ny - F, ST_LDS_BYTES, false, 0, with_frame);
     if (rc) return rc;
-    const StreamPlan pl = plan_stream(c, S);
-    return launch_k_stream(c, from, to, s, S, fl, pl, pl.nsegy, ny - F, 0, 0, 0, c->xcd_bands);
+    const StreamPlan pl = plan_stream(c->plan, S);
+    return launch_k_stream(c, from, to, s, S, fl, pl, pl.nsegy, ny - F, 0, 0, 0, c->plan.xcd_bands);
 }
 
 // The edge launch of a slab's unit under the streaming kernel: everything but the bulk rows [F, ny - F) x [F, nx - F) -- the wall
@@ -171,12 +171,12 @@ int launch_stream(lbm_ctx* c, int from, int to, hipStream_t s, int S, bool with_
 int launch_stream_edges(lbm_ctx* c, int from, int to, hipStream_t s, int S, bool lo, bool hi, int extra) {
     const int elo = lo ? 1 + extra : 0, ehi = hi ? 1 + extra : 0, bands = (lo ? 1 : 0) | (hi ? 2 : 0);
     // the walls inside: the edge launch is the interface bands alone, over the whole width (side-wall cells in line)
-    if (walls_inside(c)) return launch_walls(c, from, to, s, S, 0, 0, bands, elo, ehi);
-    const int F = c->tb_f, ny = c->geo.ny;
+    if (walls_inside(c->plan)) return launch_walls(c, from, to, s, S, 0, 0, bands, elo, ehi);
+    const int F = c->plan.tb_f, ny = c->plan.geo.ny;
     FrameLayout fl;
     const int rc = frame_layout(c, fl, S, lo ? -extra : F, hi ? ny + extra : ny - F, ST_LDS_BYTES, false, extra);
     if (rc) return rc;
-    return launch_k_stream(c, from, to, s, S, fl, plan_stream(c, S), (lo ? 1 : 0) + (hi ? 1 : 0), ny - F, elo, ehi, bands, false);
+    return launch_k_stream(c, from, to, s, S, fl, plan_stream(c->plan, S), (lo ? 1 : 0) + (hi ? 1 : 0), ny - F, elo, ehi, bands, false);
 }
 
 // The first launch of the streaming kernel in a process costs ~1.4 ms (code upload, 144 KiB of LDS, scratch set-up).  Where the first
@@ -184,8 +184,8 @@ int launch_stream_edges(lbm_ctx* c, int from, int to, hipStream_t s, int S, bool
 // run -- in the driver's 20 timed steps after a 5-step warm-up, for one -- so lbm_create pays it: one workgroup that returns at once
 // (its segment, rows [F, ye = F), is empty).
 int warm_stream(lbm_ctx* c) {
-    const FrameLayout none{c->tb_f, c->frame_seg, 1, 1, 0, false};
-    return launch_k_stream(c, 0, 1, c->s_compute, c->tb_steps, none, StreamPlan{1, 1, 1}, 1, c->tb_f, 0, 0, 0, false);
+    const FrameLayout none{c->plan.tb_f, c->plan.frame_seg, 1, 1, 0, false};
+    return launch_k_stream(c, 0, 1, c->s_compute, c->plan.tb_steps, none, StreamPlan{1, 1, 1}, 1, c->plan.tb_f, 0, 0, 0, false);
 }
 
 // The bulk launch of a unit (with_frame: and the frame, the unit's only launch) by the context's kernel.
@@ -194,27 +194,27 @@ int launch_deep(lbm_ctx* c, int from, int to, hipStream_t s, int steps, bool wit
     // kernel costs nearly the same whatever its length (4096^2 fast: 311 us for four steps, 374 for eight), the tile kernel's four
     // steps take ~290 (strict ~300 against ~350): the driver's 20 timed steps, fast 1088 -> 1066 us, strict 1466 -> 1412
     // (profiles/r02_logs/tail_tiles.log)
-    switch (c->kern) {
+    switch (c->plan.kern) {
         case Kern::stream:
-            if (c->tail_tiles && c->frame_fused && with_frame && steps >= 3 && steps <= 5) break;
+            if (c->plan.tail_tiles && c->plan.frame_fused && with_frame && steps >= 3 && steps <= 5) break;
             [[fallthrough]];
         case Kern::stream_walls:
         case Kern::stream_pairs: return launch_stream(c, from, to, s, steps, with_frame);
         default: break;
     }
-    const int F = c->tb_f, xe = c->geo.nx - F, ye = c->geo.ny - F;
+    const int F = c->plan.tb_f, xe = c->plan.geo.nx - F, ye = c->plan.geo.ny - F;
     if (steps < 3)
         return launch_variant(c, [&](auto v) {
             using VT = decltype(v);
             using R = typename VT::R;
             constexpr int V = 16 / (int)sizeof(R), TX = tb_txv<VT::TURB>() * V, TY = tb_ty<VT::TURB>();
             const int ntx = (xe - TB_F + TX - 1) / TX, nty = (ye - TB_F + TY - 1) / TY;   // two steps: F = TB_F
-            hipLaunchKernelGGL((k_step2_deep<R, VT::COLL, VT::TURB>), dim3(ntx * nty, c->batch), dim3(TB_NT), 0, s, (const R*)c->lat[from],
-                               (R*)c->lat[to], c->geo, relax_of<R>(c->p), batch_of<R>(c), xe, ye, ntx, ntx * nty);
+            hipLaunchKernelGGL((k_step2_deep<R, VT::COLL, VT::TURB>), dim3(ntx * nty, c->plan.batch), dim3(TB_NT), 0, s, (const R*)c->lat[from],
+                               (R*)c->lat[to], c->plan.geo, relax_of<R>(c->p), batch_of<R>(c), xe, ye, ntx, ntx * nty);
         });
     const int S_tile = steps == 4 || steps == 5 ? steps : 3;
     FrameLayout fl;
-    const int rc = frame_layout(c, fl, S_tile, F, c->geo.ny - F, TILE_FRAME_LDS_BYTES, false, 0, with_frame);
+    const int rc = frame_layout(c, fl, S_tile, F, c->plan.geo.ny - F, TILE_FRAME_LDS_BYTES, false, 0, with_frame);
     if (rc) return rc;
     return launch_variant(c, [&](auto v) {
         using VT = decltype(v);
@@ -223,8 +223,8 @@ int launch_deep(lbm_ctx* c, int from, int to, hipStream_t s, int steps, bool wit
         auto go = [&](auto steps) {   // (fp64: the x rim of S >= 4 is two vectors wide)
             constexpr int S = decltype(steps)::value, PVC = 16, RV = (S - 1 + V - 1) / V, TX = (PVC - 2 * RV) * V, TY = 512 / PVC - 2 * (S - 1);
             const int ntx = (xe - F + TX - 1) / TX, nty = (ye - F + TY - 1) / TY;
-            hipLaunchKernelGGL((k_stepS_deep<R, VT::COLL, VT::SEM, S, false, VT::TURB>), dim3(fl.nframe + ntx * nty, c->batch), dim3(512), 0, s,
-                               (const R*)c->lat[from], (R*)c->lat[to], c->geo, relax_of<R>(c->p), batch_of<R>(c), F, xe, ye, ntx, ntx * nty,
+            hipLaunchKernelGGL((k_stepS_deep<R, VT::COLL, VT::SEM, S, false, VT::TURB>), dim3(fl.nframe + ntx * nty, c->plan.batch), dim3(512), 0, s,
+                               (const R*)c->lat[from], (R*)c->lat[to], c->plan.geo, relax_of<R>(c->p), batch_of<R>(c), F, xe, ye, ntx, ntx * nty,
                                frame_ptrs<R>(c, from, to, S), fl.nframe, fl.nsegx, fl.nsegy, fl.L, fl.in_lds ? 1 : 0);
         };
         if (S_tile == 4) go(std::integral_constant<int, 4>{});
@@ -236,7 +236,7 @@ int launch_deep(lbm_ctx* c, int from, int to, hipStream_t s, int steps, bool wit
 // bookkeeping after a launch unit of S steps lat[cur] -> lat[cur ^ 1]
 void finish_unit(lbm_ctx* c, int S) {
     c->cur ^= 1;
-    c->raw[c->cur] = c->push ? 1 : 0;   // (push scheme: the lattices hold plain populations, nothing to stream at read time)
+    c->raw[c->cur] = c->plan.push ? 1 : 0;   // (push scheme: the lattices hold plain populations, nothing to stream at read time)
     c->nsteps += S;
     c->lag = S - 1;
     c->lag_valid = false;
@@ -247,14 +247,14 @@ void finish_unit(lbm_ctx* c, int S) {
 // stream s.  extra: rows of the neighbours' side owned on top (see launch_frame_multi).  The per-pass frame goes through the scratch
 // lattices; a slab without the deep halo exchanges one row after every pass but the last.
 static int launch_frame_work(lbm_ctx* c, Route route, int from, int to, hipStream_t s, int S, int extra) {
-    const bool lo = has_neighbour(c, LBM_SIDE_LOW), hi = has_neighbour(c, LBM_SIDE_HIGH), deep = is_slab(c) && c->deep_halo;
+    const bool lo = has_neighbour(c->plan, LBM_SIDE_LOW), hi = has_neighbour(c->plan, LBM_SIDE_HIGH), deep = is_slab(c->plan) && c->plan.deep_halo;
     if (route == Route::edges_bulk) return launch_stream_edges(c, from, to, s, S, lo, hi, extra);
     if (route == Route::fused_frame) return launch_frame_multi(c, from, to, S, s, deep && lo, deep && hi, extra);
     int rc = ensure_scratch(c, 2);
     for (int i = 1; i <= S && rc == LBM_OK; ++i) {
         const int next = i == S ? to : 2 + ((i - 1) & 1), ext = deep ? S - i + extra : 0;
-        rc = launch_frame(c, from, next, c->tb_f + S - i, s, lo ? ext : 0, hi ? ext : 0);
-        if (rc == LBM_OK && is_slab(c) && !deep && i < S) rc = enqueue_exchange(c, next);
+        rc = launch_frame(c, from, next, c->plan.tb_f + S - i, s, lo ? ext : 0, hi ? ext : 0);
+        if (rc == LBM_OK && is_slab(c->plan) && !deep && i < S) rc = enqueue_exchange(c, next);
         from = next;
     }
     return rc;
@@ -270,8 +270,8 @@ static int launch_frame_work(lbm_ctx* c, Route route, int from, int to, hipStrea
 // s_compute where that premise does not hold); the small kernels run beside the bulk kernel of the same unit.  Nothing is carried from one unit to the next except thin_valid (a one-row halo that is
 // already in place, e.g. the one lbm_step leaves for lbm_get_fields).
 int single_step(lbm_ctx* c, bool* comm_used, bool rccl_x) {
-    const int ny = c->geo.ny, a = c->cur, b = c->cur ^ 1;
-    if (is_slab(c)) {
+    const int ny = c->plan.geo.ny, a = c->cur, b = c->cur ^ 1;
+    if (is_slab(c->plan)) {
         // edge rows 0 and ny-1 (they read the ghost rows) | interior rows
         if (rccl_x && !c->raw[a] && !c->thin_valid) {   // (a raw lattice is not streamed: no halo needed)
             int rc = exchange_ready(c, 1);
@@ -294,11 +294,8 @@ int single_step(lbm_ctx* c, bool* comm_used, bool rccl_x) {
         *comm_used = true;
         return LBM_OK;
     }
-    if (c->edges_pending) {   // frame kernels of an earlier multi-step
-        HIP_TRY(c, hipStreamWaitEvent(c->s_compute, c->ev_edges, 0));
-        c->edges_pending = false;
-    }
-    int rc = launch_rows(c, a, b, 0, 1, ny, c->s_compute);
+    int rc = join_edges(c);   // frame kernels of an earlier multi-step
+    if (rc == LBM_OK) rc = launch_rows(c, a, b, 0, 1, ny, c->s_compute);
     if (rc) return rc;
     c->int_stale = true;
     finish_unit(c, 1);
@@ -314,19 +311,16 @@ int single_step(lbm_ctx* c, bool* comm_used, bool rccl_x) {
 // is the unit's only exchange; otherwise every pass but the last is followed by a one-row exchange.  (Running row and
 // column strips as separate launches on separate streams was measured and lost 8 %: profiles/r01_logs/perf31.log, perf35.log.)
 int multi_step(lbm_ctx* c, bool* comm_used, int S, bool rccl_x) {
-    const Route route = unit_route(c, S, false);
+    const Route route = unit_route(c->plan, S, false);
     if (route == Route::one_launch) {   // a lone lattice: frame and tiles in ONE launch, everything on the compute stream
-        if (c->edges_pending) {   // (frame launches of an earlier unit on the second stream, if any)
-            HIP_TRY(c, hipStreamWaitEvent(c->s_compute, c->ev_edges, 0));
-            c->edges_pending = false;
-        }
-        int rc = launch_deep(c, c->cur, c->cur ^ 1, c->s_compute, S, true);
+        int rc = join_edges(c);   // (frame launches of an earlier unit on the second stream, if any)
+        if (rc == LBM_OK) rc = launch_deep(c, c->cur, c->cur ^ 1, c->s_compute, S, true);
         if (rc) return rc;
         c->int_stale = true;      // (ev_int is recorded when something on s_comm is made to wait for it: flush_int)
         finish_unit(c, S);
         return LBM_OK;
     }
-    const bool slab = is_slab(c), deep = slab && c->deep_halo;
+    const bool slab = is_slab(c->plan), deep = slab && c->plan.deep_halo;
     if (slab && !deep && !rccl_x) return fail(c, LBM_ERR_STATE, "a multi-step unit of a slab needs the deep halo (MRT_GPU semantics) or the in-library exchange");
     const int a = c->cur, b = c->cur ^ 1;
     int rc;
@@ -367,8 +361,8 @@ int multi_step(lbm_ctx* c, bool* comm_used, int S, bool rccl_x) {
         //     does not need; E_n has had the whole of B_{n-1} to finish, so this costs only when a neighbour is that late -- and then G_n,
         //     which B_{n+1} needs, waits for the same exchange anyway.
         // (the events are re-recorded every unit: a wait refers to the last record before it in host order -- the one named above)
-        const StreamPlan pl = plan_stream(c, S);
-        if (c->edge_first && (long long)pl.nstrips * pl.nsegy > c->ncu) {
+        const StreamPlan pl = plan_stream(c->plan, S);
+        if (c->plan.edge_first && (long long)pl.nstrips * pl.nsegy > c->plan.ncu) {
             HIP_TRY(c, hipEventRecord(c->ev_go, c->s_comm));
             HIP_TRY(c, hipStreamWaitEvent(c->s_compute, c->ev_go, 0));
         }
@@ -382,7 +376,7 @@ int multi_step(lbm_ctx* c, bool* comm_used, int S, bool rccl_x) {
     HIP_TRY(c, hipEventRecord(c->ev_int, c->s_compute));
     c->int_stale = false;
     finish_unit(c, S);
-    c->edge_rows = c->tb_f;
+    c->edge_rows = c->plan.tb_f;
     *comm_used = true;
     return LBM_OK;
 }
@@ -395,12 +389,12 @@ int prev_lattice(lbm_ctx* c, int* which) {
     *which = LAT_LAG;
     if (c->lag_valid) return LBM_OK;
     if (!c->lat[LAT_LAG]) {
-        hipError_t e = hipMalloc(&c->lat[LAT_LAG], c->lat_bytes);
+        hipError_t e = hipMalloc(&c->lat[LAT_LAG], c->plan.lat_bytes);
         if (e != hipSuccess) return fail(c, LBM_ERR_NOMEM, std::string("hipMalloc(lag lattice): ") + hipGetErrorString(e));
-        HIP_TRY(c, hipMemsetAsync(c->lat[LAT_LAG], 0, c->lat_bytes, c->s_compute));
+        HIP_TRY(c, hipMemsetAsync(c->lat[LAT_LAG], 0, c->plan.lat_bytes, c->s_compute));
     }
     const int k = c->lag, from = c->cur ^ 1;
-    const Route route = unit_route(c, k, true);
+    const Route route = unit_route(c->plan, k, true);
     int rc = LBM_OK;
     if (route == Route::one_launch) {
         rc = launch_deep(c, from, LAT_LAG, c->s_compute, k, true);
@@ -410,13 +404,13 @@ int prev_lattice(lbm_ctx* c, int* which) {
         rc = launch_frame_work(c, route, from, LAT_LAG, c->s_compute, k, 1);
         if (rc == LBM_OK) rc = launch_deep(c, from, LAT_LAG, c->s_compute, k);
     } else {                            // k single steps (a lone lattice), through scratch lattice 2
-        if (is_slab(c)) return fail(c, LBM_ERR_STATE, "internal: the last unit of a slab cannot be replayed");
+        if (is_slab(c->plan)) return fail(c, LBM_ERR_STATE, "internal: the last unit of a slab cannot be replayed");
         if (k > 1 && (rc = ensure_scratch(c, 2)) != LBM_OK) return rc;
         int f = from;
         for (int i = 1; i <= k; ++i) {
             const int to = i == k ? LAT_LAG : (f == 2 ? 3 : 2);
             c->raw[to] = 0;
-            rc = launch_rows(c, f, to, 0, 1, c->geo.ny, c->s_compute);
+            rc = launch_rows(c, f, to, 0, 1, c->plan.geo.ny, c->s_compute);
             if (rc) return rc;
             f = to;
         }
@@ -432,12 +426,12 @@ int push_step(lbm_ctx* c) {
     const int rc = launch_variant(c, [&](auto v) {
         using VT = decltype(v);
         using R = typename VT::R;
-        const dim3 g = grid_rows(c, c->geo.ny);
+        const dim3 g = grid_rows(c, c->plan.geo.ny);
         if constexpr (VT::SEM != SEM_BB) {   // (validate_params refuses the push scheme with bounce-back walls)
-            hipLaunchKernelGGL((k_push_collide<R, VT::COLL, VT::SEM>), g, dim3(BLK), 0, c->s_compute, (const R*)c->lat[c->cur], (R*)c->lat[2], c->geo,
+            hipLaunchKernelGGL((k_push_collide<R, VT::COLL, VT::SEM>), g, dim3(BLK), 0, c->s_compute, (const R*)c->lat[c->cur], (R*)c->lat[2], c->plan.geo,
                                relax_of<R>(c->p));
             hipLaunchKernelGGL((k_push_bc<R, VT::COLL, VT::SEM>), g, dim3(BLK), 0, c->s_compute, (const R*)c->lat[c->cur], (R*)c->lat[2],
-                               (R*)c->lat[c->cur ^ 1], c->geo, (R)c->p.uLB);
+                               (R*)c->lat[c->cur ^ 1], c->plan.geo, (R)c->p.uLB);
         }
     });
     if (rc) return rc;
@@ -447,8 +441,8 @@ int push_step(lbm_ctx* c) {
 
 // ftemp starts as a copy of fin (MRT_GPU.py:324)
 int push_reset(lbm_ctx* c) {
-    if (!c->push) return LBM_OK;
-    HIP_TRY(c, hipMemcpyAsync(c->lat[2], c->lat[0], (size_t)c->bstride * c->es, hipMemcpyDeviceToDevice, c->s_compute));
+    if (!c->plan.push) return LBM_OK;
+    HIP_TRY(c, hipMemcpyAsync(c->lat[2], c->lat[0], (size_t)c->plan.bstride * c->plan.es, hipMemcpyDeviceToDevice, c->s_compute));
     return LBM_OK;
 }
 
@@ -456,13 +450,13 @@ int push_reset(lbm_ctx* c) {
 // starts from), on the compute stream.
 int stats_accumulate(lbm_ctx* c, int which) {
     constexpr long long STATS_BLOCKS = 2048;   // grid-stride beyond that (a pure streaming kernel)
-    const long long npairs = (long long)c->geo.ny * ((c->geo.nx + 1) / 2);
+    const long long npairs = (long long)c->plan.geo.ny * ((c->plan.geo.nx + 1) / 2);
     const int blocks = (int)std::min<long long>((npairs + BLK - 1) / BLK, STATS_BLOCKS);
     const int rc = launch_variant(c, [&](auto v) {
         using VT = decltype(v);
         using R = typename VT::R;
-        hipLaunchKernelGGL((k_stats_accumulate<R, VT::SEM, coll_is_prom(VT::COLL)>), dim3(blocks, 1, c->batch), dim3(BLK), 0, c->s_compute,
-                           (const R*)c->lat[which], c->geo, c->raw[which], (R)c->p.uLB, c->bstride, c->stats_dev);
+        hipLaunchKernelGGL((k_stats_accumulate<R, VT::SEM, coll_is_prom(VT::COLL)>), dim3(blocks, 1, c->plan.batch), dim3(BLK), 0, c->s_compute,
+                           (const R*)c->lat[which], c->plan.geo, c->raw[which], (R)c->p.uLB, c->plan.bstride, c->stats_dev);
     });
     if (rc) return rc;
     ++c->stats_count;
@@ -474,11 +468,8 @@ int stats_accumulate(lbm_ctx* c, int which) {
 // its raw flag: no lag replay.  A call that ends at n - 1 takes it at the start of the next call.
 static int sample_if_due(lbm_ctx* c) {
     if (c->stats_every <= 0 || c->nsteps + 1 != c->stats_next) return LBM_OK;
-    if (c->edges_pending) {   // (frame work of the last unit on the second stream wrote part of lat[cur])
-        HIP_TRY(c, hipStreamWaitEvent(c->s_compute, c->ev_edges, 0));
-        c->edges_pending = false;
-    }
-    const int rc = stats_accumulate(c, c->cur);
+    int rc = join_edges(c);   // (frame work of the last unit on the second stream wrote part of lat[cur])
+    if (rc == LBM_OK) rc = stats_accumulate(c, c->cur);
     if (rc) return rc;
     c->int_stale = true;      // (s_comm must not rewrite lat[cur] before the sample has read it)
     c->stats_next += c->stats_every;
@@ -492,7 +483,7 @@ static int steps_to_cut(const lbm_ctx* c, int left) {
 }
 
 int step_many(lbm_ctx* c, int nsteps) {
-    if (c->push) {
+    if (c->plan.push) {
         for (int i = 0; i < nsteps; ++i) {
             int rc = sample_if_due(c);
             if (rc == LBM_OK) rc = push_step(c);
@@ -500,19 +491,19 @@ int step_many(lbm_ctx* c, int nsteps) {
         }
         return LBM_OK;
     }
-    const bool slab = is_slab(c);
+    const bool slab = is_slab(c->plan);
     if (slab && !own_transport(c))
         return fail(c, LBM_ERR_STATE, "lbm_step on a slab without a communicator: its ghost rows would never be exchanged (attach one with "
                                       "lbm_comm_init, or drive the slab with lbm_step_edges/interior/finish, lbm_step_unit and the lbm_halo_* calls)");
     bool comm_used = false;
-    if (c->kern != Kern::none || slab)   // (a lone lattice stepping one step per launch uses one stream, no events)
+    if (c->plan.kern != Kern::none || slab)   // (a lone lattice stepping one step per launch uses one stream, no events)
         HIP_TRY(c, hipEventRecord(c->ev_int, c->s_compute));   // everything enqueued so far (init, upload, earlier calls)
     c->edge_rows = 0;        // the first exchange of the call waits for it
     int left = nsteps;
     while (left > 0) {
         int rc = sample_if_due(c);
         if (rc) return rc;
-        const int S = unit_steps(c, steps_to_cut(c, left), c->raw[c->cur] != 0);
+        const int S = unit_steps(c->plan, steps_to_cut(c, left), c->raw[c->cur] != 0, own_transport(c));
         rc = S > 1 ? multi_step(c, &comm_used, S, true) : single_step(c, &comm_used, true);
         if (rc) return rc;
         left -= S;
@@ -555,22 +546,22 @@ int lbm_time_steps(lbm_ctx* c, int nsteps, double* ms) {
 
 int lbm_step_edges(lbm_ctx* c) {
     if (!c) return LBM_ERR_INVALID;
-    if (c->push) return fail(c, LBM_ERR_STATE, "the split-step calls do not apply to kernel = PUSH");
+    if (c->plan.push) return fail(c, LBM_ERR_STATE, "the split-step calls do not apply to kernel = PUSH");
     if (c->stats_every > 0) return fail(c, LBM_ERR_STATE, "automatic sampling (lbm_stats_begin, every > 0) runs inside lbm_step only");
     HIP_TRY(c, hipSetDevice(c->p.device));
-    return launch_rows(c, c->cur, c->cur ^ 1, 0, c->geo.ny - 1, 2, c->s_compute);
+    return launch_rows(c, c->cur, c->cur ^ 1, 0, c->plan.geo.ny - 1, 2, c->s_compute);
 }
 
 int lbm_step_interior(lbm_ctx* c) {
     if (!c) return LBM_ERR_INVALID;
-    if (c->push) return fail(c, LBM_ERR_STATE, "the split-step calls do not apply to kernel = PUSH");
+    if (c->plan.push) return fail(c, LBM_ERR_STATE, "the split-step calls do not apply to kernel = PUSH");
     HIP_TRY(c, hipSetDevice(c->p.device));
-    return launch_rows(c, c->cur, c->cur ^ 1, 1, 1, c->geo.ny - 2, c->s_compute);
+    return launch_rows(c, c->cur, c->cur ^ 1, 1, 1, c->plan.geo.ny - 2, c->s_compute);
 }
 
 int lbm_step_finish(lbm_ctx* c) {
     if (!c) return LBM_ERR_INVALID;
-    if (c->push) return fail(c, LBM_ERR_STATE, "the split-step calls do not apply to kernel = PUSH");
+    if (c->plan.push) return fail(c, LBM_ERR_STATE, "the split-step calls do not apply to kernel = PUSH");
     finish_unit(c, 1);
     return LBM_OK;
 }
@@ -578,16 +569,16 @@ int lbm_step_finish(lbm_ctx* c) {
 int lbm_step_unit(lbm_ctx* c, int S) {
     if (!c) return LBM_ERR_INVALID;
     HIP_TRY(c, hipSetDevice(c->p.device));
-    if (c->push || c->kern == Kern::none) return fail(c, LBM_ERR_STATE, "lbm_step_unit: this context steps one step per launch (lbm_next_unit() is 1)");
+    if (c->plan.push || c->plan.kern == Kern::none) return fail(c, LBM_ERR_STATE, "lbm_step_unit: this context steps one step per launch (lbm_next_unit() is 1)");
     if (own_transport(c)) return fail(c, LBM_ERR_STATE, "lbm_step_unit: a communicator is attached, lbm_step() moves the halos itself");
     if (c->stats_every > 0) return fail(c, LBM_ERR_STATE, "lbm_step_unit: automatic sampling (lbm_stats_begin, every > 0) runs inside lbm_step only");
     if (c->raw[c->cur]) return fail(c, LBM_ERR_STATE, "lbm_step_unit: the first step after an upload is a single step");
-    const bool ok = c->tb_steps == 2 ? S == 2 : (S >= 3 && S <= c->tb_steps);
+    const bool ok = c->plan.tb_steps == 2 ? S == 2 : (S >= 3 && S <= c->plan.tb_steps);
     if (!ok)
-        return fail(c, LBM_ERR_INVALID, c->tb_steps == 2 ? std::string("lbm_step_unit: this context runs units of 2 steps")
-                                                         : "lbm_step_unit: unit_steps must be 3 .. " + std::to_string(c->tb_steps) +
+        return fail(c, LBM_ERR_INVALID, c->plan.tb_steps == 2 ? std::string("lbm_step_unit: this context runs units of 2 steps")
+                                                         : "lbm_step_unit: unit_steps must be 3 .. " + std::to_string(c->plan.tb_steps) +
                                                                " (this context's steps per launch; lbm_next_unit plans 4 or more on a slab)");
-    if (is_slab(c) && !c->deep_halo) return fail(c, LBM_ERR_STATE, "lbm_step_unit on a slab needs the deep halo (MRT_GPU semantics)");
+    if (is_slab(c->plan) && !c->plan.deep_halo) return fail(c, LBM_ERR_STATE, "lbm_step_unit on a slab needs the deep halo (MRT_GPU semantics)");
     bool comm_used = false;
     HIP_TRY(c, hipEventRecord(c->ev_int, c->s_compute));   // everything enqueued so far, the imported rows included
     c->edge_rows = 0;

@@ -7,30 +7,29 @@ namespace lbmhost {
 // All S frame passes lat[from] -> lat[to] in one launch (k_frame_multi); lo / hi: the slab has a neighbour below row 0 / above
 // row ny - 1 whose rows lie in the ghost rows (deep halo).
 // Do the LDS windows of the fused frame passes fit (two buffers of the largest pass-1 rectangle plus its ring)?
-bool frame_lds_fits(const lbm_ctx* c, int S, bool deep_rows, int extra, long long budget) {
-    if (!c->frame_lds) return false;
-    const int F = c->tb_f, L = c->frame_seg, m = S - 1, np = c->p.turb ? Q + 2 : Q;
+bool frame_lds_fits(const Plan& pl, int S, bool deep_rows, int extra, long long budget) {
+    if (!pl.frame_lds) return false;
+    const int F = pl.tb_f, L = pl.frame_seg, m = S - 1, np = pl.nplanes;
     const long long row_strip = (long long)(L + 2 * m + 2) * (F + m + (deep_rows ? m + extra : 0) + 2);
     const long long col_strip = (long long)(F + m + 2) * (L + 2 * m + extra + 2);
-    return 2 * np * std::max(row_strip, col_strip) * c->es <= budget;
+    return 2 * np * std::max(row_strip, col_strip) * pl.es <= budget;
 }
 // waves per workgroup of k_stream_pairs for S steps per launch: two idle pair-slots to load the next pair in
 int pairs_waves(int S) { return std::min(SP_MAX_WAVES, S + 2); }
-StreamPlan plan_stream_on(const lbm_ctx* c, int S, int ncu, long long* cost_out) {
-    const bool walls = walls_inside(c);
-    const int V = 16 / c->es, Rr = stream_rim(S, V), TXu = 64 * V - 2 * Rr, F = walls ? 0 : c->tb_f;
-    const int cols = c->geo.nx - 2 * F;
+StreamPlan plan_stream_on(const Plan& pl, int S, int ncu, long long* cost_out) {
+    const bool walls = walls_inside(pl);
+    const int V = 16 / pl.es, Rr = stream_rim(S, V), TXu = 64 * V - 2 * Rr, F = walls ? 0 : pl.tb_f;
+    const int cols = pl.geo.nx - 2 * F;
     // (with the walls inside: strips over the whole width, no rim at a wall; segments over the whole height -- of a slab: over the rows
     // between its edge bands, tb_f rows next to each interface)
-    const int rows = walls ? c->geo.ny - c->tb_f * ((has_neighbour(c, LBM_SIDE_LOW) ? 1 : 0) + (has_neighbour(c, LBM_SIDE_HIGH) ? 1 : 0))
-                           : c->geo.ny - 2 * F;
-    StreamPlan best{walls ? stream_walls_strips(c->geo.nx, S, V) : (cols + TXu - 1) / TXu, 1, rows};
+    const int rows = walls ? pl.geo.ny - pl.tb_f * neighbours(pl) : pl.geo.ny - 2 * F;
+    StreamPlan best{walls ? stream_walls_strips(pl.geo.nx, S, V) : (cols + TXu - 1) / TXu, 1, rows};
     long long best_cost = -1;
     for (int n = 1; n <= 256 && n * 8 <= std::max(rows, 8); ++n) {
         const int H = (rows + n - 1) / n, nseg = (rows + H - 1) / H;
         const long long segs = (long long)best.nstrips * nseg, rounds = (segs + ncu - 1) / ncu;
         long long iters = H + 2 * (S - 1) + ST_WAVES - 1;      // (block b starts in iteration b and takes 16: stream_segment)
-        if (c->kern == Kern::stream_pairs) {   // W waves, a pair of rows each: 2 W iterations per W pairs
+        if (pl.kern == Kern::stream_pairs) {   // W waves, a pair of rows each: 2 W iterations per W pairs
             const long long Wv = pairs_waves(S), np = (H + 2 * (S - 1) + 1) / 2;
             iters = 2 * Wv * ((np + Wv - 1) / Wv) + 2 * Wv;
         }
@@ -45,16 +44,16 @@ StreamPlan plan_stream_on(const lbm_ctx* c, int S, int ncu, long long* cost_out)
 // unit costs bulk + edges.  For a short slab it is cheaper to plan the bulk launch on fewer CUs and leave the others to the edge
 // workgroups (4096 x 512 fp32 slab in loopback: 145 -> 176 GLUPS; taller slabs lose a few per cent -- 4096 x 1024 247 -> 240, 4096 x
 // 2048 282 -> 270 -- hence the limit below; profiles/r02_logs/slab_loopback9.log).  Costs in pipeline iterations.
-StreamPlan plan_stream(const lbm_ctx* c, int S) {
+StreamPlan plan_stream(const Plan& pl, int S) {
     long long cost0 = 0;
-    const StreamPlan p0 = plan_stream_on(c, S, c->ncu, &cost0);
-    const bool walls = walls_inside(c);
-    if (!(is_slab(c) && c->deep_halo && (c->frame_fused || walls) && c->edge_reserve) || S < 3) return p0;
-    if ((long long)p0.nstrips * p0.nsegy > c->ncu) return p0;     // several rounds: the bulk launch is released behind the edge launch instead
-    const int nb = (has_neighbour(c, LBM_SIDE_LOW) ? 1 : 0) + (has_neighbour(c, LBM_SIDE_HIGH) ? 1 : 0), L = c->frame_seg;
+    const StreamPlan p0 = plan_stream_on(pl, S, pl.ncu, &cost0);
+    const bool walls = walls_inside(pl);
+    if (!(is_slab(pl) && pl.deep_halo && (pl.frame_fused || walls) && pl.edge_reserve) || S < 3) return p0;
+    if ((long long)p0.nstrips * p0.nsegy > pl.ncu) return p0;     // several rounds: the bulk launch is released behind the edge launch instead
+    const int nb = neighbours(pl), L = pl.frame_seg;
     const long long n_edge = walls ? (long long)nb * p0.nstrips     // (the walls inside: the interface bands alone)
-                                   : (long long)nb * p0.nstrips + 2LL * frame_segs(c->geo.ny, L) + (2LL - nb) * frame_segs(c->geo.nx, L);
-    const long long edge_it = c->tb_f + 2 * (S - 1) + ST_WAVES - 1;
+                                   : (long long)nb * p0.nstrips + 2LL * frame_segs(pl.geo.ny, L) + (2LL - nb) * frame_segs(pl.geo.nx, L);
+    const long long edge_it = pl.tb_f + 2 * (S - 1) + ST_WAVES - 1;
     // (measured: a bulk launch longer than ~1.5 edge workgroups overlaps the frame variant's ~100 short edge workgroups well enough as
     // it is.  With the walls inside the edge launch is the 2 x nstrips band workgroups alone, each of which holds a CU -- all its LDS --
     // for edge_it iterations, and the bulk workgroups that find no CU start that much later: leaving them room pays up to a bulk launch
@@ -62,7 +61,7 @@ StreamPlan plan_stream(const lbm_ctx* c, int S) {
     // profiles/r03_logs/slab_walls.log)
     if (walls ? cost0 > 3 * edge_it : 4 * cost0 > 7 * edge_it) return p0;   // (the frame variant: segments of up to ~35 rows, as measured in r02)
     StreamPlan best = p0;
-    long long best_cost = cost0 + edge_it * ((n_edge + c->ncu - 1) / c->ncu);
+    long long best_cost = cost0 + edge_it * ((n_edge + pl.ncu - 1) / pl.ncu);
     // (workgroups go to the eight XCDs in turn and, inside an XCD, to its four shader engines in turn, whatever is free where: "room" is
     // per shader engine, 8 CUs.  Kernel trace of the 4096 x 1024 slab, 34 + 221 workgroups on 256 CUs: XCD 0 is dealt 5 + 28 and its last
     // bulk workgroup starts when an edge workgroup ends, 43 us late; 34 + 204 -- 31 per XCD at most -- still waits, 34 + 187 does not
@@ -70,45 +69,46 @@ StreamPlan plan_stream(const lbm_ctx* c, int S) {
     // to the edge workgroups are counted in units of 32, rounded up.)
     const long long grain = walls ? 32 : 1;
     auto in_grains = [&](long long n) { return (n + grain - 1) / grain * grain; };
-    if (walls && in_grains((long long)p0.nstrips * p0.nsegy) + in_grains(n_edge) <= c->ncu) best_cost = std::max(cost0, edge_it);   // (room for both)
+    if (walls && in_grains((long long)p0.nstrips * p0.nsegy) + in_grains(n_edge) <= pl.ncu) best_cost = std::max(cost0, edge_it);   // (room for both)
     // (div > 1: the edge workgroups in several rounds on fewer CUs -- the frame variant's many short ones; the band workgroups of the
     // walls variant are all dispatched at once, ahead of the bulk launch, and hold what they get)
     for (int div = 1; div <= (walls ? 1 : 3); ++div) {
         const long long r = in_grains((n_edge + div - 1) / div);
-        if (r < 1 || r > c->ncu / 2) continue;
+        if (r < 1 || r > pl.ncu / 2) continue;
         long long cb = 0;
-        const StreamPlan p = plan_stream_on(c, S, c->ncu - (int)r, &cb);
+        const StreamPlan sp = plan_stream_on(pl, S, pl.ncu - (int)r, &cb);
         const long long cost = std::max(cb, edge_it * ((n_edge + r - 1) / r));
-        if (cost < best_cost) { best_cost = cost; best = p; }
+        if (cost < best_cost) { best_cost = cost; best = sp; }
     }
     return best;
 }
 
 // Can the lattice of the step before the last be recomputed after a unit of S steps (lazy lag)?  A lone lattice: always (any
 // number of single or multi-step launches).  A slab: from the deep halo the unit received, with one launch of S - 1 >= 3 steps.
-bool lag_replayable(const lbm_ctx* c, int S) {
+bool lag_replayable(const Plan& pl, int S) {
     if (S <= 1) return true;
-    if (!c->lazy_lag || c->push) return false;
-    if (!is_slab(c)) return true;
-    return c->deep_halo && S - 1 >= 3;
+    if (!pl.lazy_lag || pl.push) return false;
+    if (!is_slab(pl)) return true;
+    return pl.deep_halo && S - 1 >= 3;
 }
 
 // Steps of the next unit when `left` steps remain.  The first step after an upload reads raw populations (a single step).
 // A unit is at most tb_steps long and at least `min_unit` (3: the in-place kernel's minimum; 4 on slabs so that the last unit
 // of a call can be replayed for the one-step lag of u / rho; 2 for the two-phase kernel); what is left below that goes in
 // single steps.  LBM_FLAG_EAGER_LAG (and slabs that cannot replay): the LAST step of a call is always a single step.
-int unit_steps(const lbm_ctx* c, int left, bool raw) {
+// own_transport: the library itself moves the halos of this context (run state: a communicator is attached; the dry run has none).
+int unit_steps(const Plan& pl, int left, bool raw, bool own_transport) {
     if (left < 1) return 0;
-    if (c->kern == Kern::none || raw) return 1;
-    const int T = c->tb_steps;
-    if (is_slab(c) && !c->deep_halo && !own_transport(c)) return 1;   // (per-pass exchanges cannot be driven from outside)
-    if (!lag_replayable(c, T)) {
+    if (pl.kern == Kern::none || raw) return 1;
+    const int T = pl.tb_steps;
+    if (is_slab(pl) && !pl.deep_halo && !own_transport) return 1;   // (per-pass exchanges cannot be driven from outside)
+    if (!lag_replayable(pl, T)) {
         if (left >= T + 1) return T;
         if (T >= 3 && left - 1 >= 3) return left - 1;
         return 1;
     }
     if (T == 2) return left >= 2 ? 2 : 1;
-    const int m = is_slab(c) ? 4 : 3;
+    const int m = is_slab(pl) ? 4 : 3;
     if (left >= T) {
         const int r = left - T;
         if (r == 0 || r >= m) return T;
@@ -120,14 +120,14 @@ int unit_steps(const lbm_ctx* c, int left, bool raw) {
 
 // The route of a launch unit of S >= 2 steps (multi_step), or of the replay of the lagged lattice, S = lag (prev_lattice).  A slab
 // replays only with the deep halo (lag_replayable).
-Route unit_route(const lbm_ctx* c, int S, bool replay) {
-    const bool slab = is_slab(c), deep = slab && c->deep_halo;
+Route unit_route(const Plan& pl, int S, bool replay) {
+    const bool slab = is_slab(pl), deep = slab && pl.deep_halo;
     if (replay && S < 3) return Route::single_steps;
     // (the replay runs on s_compute alone: a frame that units run beside the streaming kernel goes inside the launch there)
-    if (!slab && ((walls_inside(c) && S >= 2) || (S >= 3 && c->frame_fused && (replay || !(c->kern == Kern::stream && c->frame_beside)))))
+    if (!slab && ((walls_inside(pl) && S >= 2) || (S >= 3 && pl.frame_fused && (replay || !(pl.kern == Kern::stream && pl.frame_beside)))))
         return Route::one_launch;
-    if (S >= 3 && deep && streaming(c) && (c->frame_fused || walls_inside(c))) return Route::edges_bulk;
-    if (S >= 3 && c->frame_fused && (!slab || deep)) return Route::fused_frame;
+    if (S >= 3 && deep && streaming(pl) && (pl.frame_fused || walls_inside(pl))) return Route::edges_bulk;
+    if (S >= 3 && pl.frame_fused && (!slab || deep)) return Route::fused_frame;
     return Route::frame_passes;
 }
 
@@ -180,54 +180,83 @@ std::string validate_params(const lbm_params* p) {
 // The launch plan.  Everything that shapes the exchange protocol between slabs (several steps per launch or not, how many, frame
 // width, deep halo) is derived from ny_plan = the smallest slab of the decomposition, never from this rank's own share of the
 // rows: neighbours must post matching send / receive sequences (lbm_comm_init cross-checks).
-static int ny_plan(const lbm_params* p) { return p->ny_local_min > 0 ? p->ny_local_min : p->ny_local; }
+static int ny_plan(const lbm_params& p) { return p.ny_local_min > 0 ? p.ny_local_min : p.ny_local; }
 // a lone lattice whose multi-step unit is ONE launch (frame inside): no batch, no slab, fused frame passes
-static bool one_launch(const lbm_ctx* c) { return c->batch == 1 && !is_slab(c) && !(c->p.flags & LBM_FLAG_FRAME_UNFUSED); }
+static bool one_launch(const Plan& pl) { return pl.batch == 1 && !is_slab(pl) && pl.frame_fused; }
+
+// lbm_params.flags, decoded -- the one place that reads them (validate_params apart, which checks the caller's input).  The switches
+// that are plan fields go into the plan; the bits that force or forbid a choice make_plan otherwise takes by its rules come back.
+struct Forced {
+    int nt = 0, frame_beside = 0;   // +1: on, -1: off, 0: by the rule
+    bool stream_walls = false, stream_pairs = false, no_stream_walls = false, no_tail_tiles = false;
+};
+static Forced decode_flags(const lbm_params& p, Plan& pl) {
+    const auto on = [&](int bit) { return (p.flags & bit) != 0; };
+    // (bounce-back slabs exchange one row per frame pass, as MRT.py semantics: the recomputed band of the neighbour's rows is not
+    // implemented for its gather)
+    pl.deep_halo = p.semantics == LBM_SEM_MRT_GPU && !on(LBM_FLAG_NO_DEEP_HALO);
+    pl.frame_fused = !on(LBM_FLAG_FRAME_UNFUSED);
+    pl.frame_lds = !on(LBM_FLAG_NO_FRAME_LDS);
+    pl.frame_wide = !on(LBM_FLAG_FRAME_NARROW);
+    pl.lazy_lag = !on(LBM_FLAG_EAGER_LAG);
+    pl.xcd_bands = !on(LBM_FLAG_NO_XCD_BANDS);
+    pl.edge_first = !on(LBM_FLAG_NO_EDGE_FIRST);
+    pl.edge_reserve = !on(LBM_FLAG_NO_EDGE_RESERVE);
+    pl.comm_priority = !on(LBM_FLAG_COMM_PRIORITY_OFF);
+    Forced f;
+    f.nt = on(LBM_FLAG_NT_ON) ? 1 : on(LBM_FLAG_NT_OFF) ? -1 : 0;
+    f.frame_beside = on(LBM_FLAG_FRAME_BESIDE_ON) ? 1 : on(LBM_FLAG_FRAME_BESIDE_OFF) ? -1 : 0;
+    f.stream_walls = on(LBM_FLAG_STREAM_WALLS);
+    f.stream_pairs = on(LBM_FLAG_STREAM_PAIRS);
+    f.no_stream_walls = on(LBM_FLAG_NO_STREAM_WALLS);
+    f.no_tail_tiles = on(LBM_FLAG_NO_TAIL_TILES);
+    return f;
+}
 
 // Geometry and memory layout of the lattice (of each lattice of a batch).
-static void plan_geometry(lbm_ctx* c) {
-    const lbm_params* p = &c->p;
-    c->es = p->dtype == LBM_F32 ? 4 : 8;
-    c->geo.nx = p->nx;
-    c->geo.ny = p->ny_local;
-    c->geo.y0 = p->y0;
-    c->geo.NY = p->ny;
-    c->geo.pitch = ((p->nx + 2 * GH) + 3) / 4 * 4;
-    const int nplanes = p->turb ? Q + 2 : Q;   // + the two Smagorinsky history planes
-    if (p->layout == LBM_LAYOUT_PLANES) {
-        c->geo.plane = (long long)c->geo.pitch * (p->ny_local + 2 * GHY);
-        c->geo.row = c->geo.pitch;
+static void plan_geometry(Plan& pl, const lbm_params& p, const Forced& f) {
+    pl.es = p.dtype == LBM_F32 ? 4 : 8;
+    pl.geo.nx = p.nx;
+    pl.geo.ny = p.ny_local;
+    pl.geo.y0 = p.y0;
+    pl.geo.NY = p.ny;
+    pl.geo.pitch = ((p.nx + 2 * GH) + 3) / 4 * 4;
+    pl.nplanes = p.turb ? Q + 2 : Q;   // + the two Smagorinsky history planes
+    pl.semantics = p.semantics;
+    if (p.layout == LBM_LAYOUT_PLANES) {
+        pl.geo.plane = (long long)pl.geo.pitch * (p.ny_local + 2 * GHY);
+        pl.geo.row = pl.geo.pitch;
     } else {  // LBM_LAYOUT_ROWS (default): +10 % on the 18-stream pattern, see DESIGN.md
-        c->geo.plane = c->geo.pitch;
-        c->geo.row = (long long)nplanes * c->geo.pitch;
+        pl.geo.plane = pl.geo.pitch;
+        pl.geo.row = (long long)pl.nplanes * pl.geo.pitch;
     }
-    c->batch = p->batch > 1 ? p->batch : 1;
-    c->bstride = (long long)nplanes * c->geo.pitch * (p->ny_local + 2 * GHY);   // lattice z of a batch starts z * bstride elements in
-    c->lat_bytes = (size_t)c->bstride * c->batch * c->es;
+    pl.batch = p.batch > 1 ? p.batch : 1;
+    pl.bstride = (long long)pl.nplanes * pl.geo.pitch * (p.ny_local + 2 * GHY);   // lattice z of a batch starts z * bstride elements in
+    pl.lat_bytes = (size_t)pl.bstride * pl.batch * pl.es;
+    pl.use_nt = f.nt ? f.nt > 0 : pl.lat_bytes > ((size_t)192 << 20);
 }
 
 // The kernel of the multi-step units: the AUTO thresholds, or the one the caller forces ("" = fine).  Between the tile kernels
 // (two steps or more) plan_steps decides, which also keeps a two-step slab off the walls-inside kernel.  With `device` the scratch
 // size of the walls-inside kernel is checked.
-static std::string plan_kernel(lbm_ctx* c, bool device) {
-    const lbm_params* p = &c->p;
-    const int nyp = ny_plan(p), V = 16 / c->es;
-    const bool slab = is_slab(c);
-    const bool can_vec = p->semantics == LBM_SEM_MRT_GPU && p->nx % V == 0;
-    if (p->kernel == LBM_KERNEL_VEC && !can_vec) return "kernel = VEC needs MRT_GPU semantics and nx % (16 / sizeof(real)) == 0";
-    c->push = p->kernel == LBM_KERNEL_PUSH;
-    c->use_vec = can_vec && p->kernel != LBM_KERNEL_GENERIC && !c->push;
-    const bool can_tb = p->nx % V == 0 && p->nx >= 32 && nyp >= 32;
-    if (p->kernel == LBM_KERNEL_TB && !can_tb) return "kernel = TB needs nx % (16 / sizeof(real)) == 0, nx >= 32 and ny_local >= 32 (on every rank)";
+static std::string plan_kernel(Plan& pl, const lbm_params& p, const Forced& f, bool device) {
+    const int nyp = ny_plan(p), V = 16 / pl.es;
+    const bool slab = is_slab(pl);
+    const bool can_vec = p.semantics == LBM_SEM_MRT_GPU && p.nx % V == 0;
+    if (p.kernel == LBM_KERNEL_VEC && !can_vec) return "kernel = VEC needs MRT_GPU semantics and nx % (16 / sizeof(real)) == 0";
+    pl.push = p.kernel == LBM_KERNEL_PUSH;
+    pl.use_vec = can_vec && p.kernel != LBM_KERNEL_GENERIC && !pl.push;
+    const bool can_tb = p.nx % V == 0 && p.nx >= 32 && nyp >= 32;
+    if (p.kernel == LBM_KERNEL_TB && !can_tb) return "kernel = TB needs nx % (16 / sizeof(real)) == 0, nx >= 32 and ny_local >= 32 (on every rank)";
     // measured crossover: with one launch per frame pass (batches, LBM_FLAG_FRAME_UNFUSED) a multi-step pays from ~768^2 cells
     // (profiles/r01_logs/perf4.log); with the frame inside the tile launch a unit is ONE launch and wins from the smallest
     // lattices the in-place kernel takes (perf41.log, perf43.log: 160^2 4.1-4.5 us per step against 5.1 one step per launch)
-    const bool big = one_launch(c) ? (p->nx >= 64 && nyp >= 64) : (long long)p->nx * nyp * c->batch >= 768LL * 768LL;
+    const bool big = one_launch(pl) ? (p.nx >= 64 && nyp >= 64) : (long long)p.nx * nyp * pl.batch >= 768LL * 768LL;
     // The strip-streaming kernel (lbm_stream.hpp): one workgroup per CU marches down a strip of 240 fp32 / 112 fp64 useful
     // columns, up to 8 steps per launch, no rim in y.  It needs tall segments to amortise its pipeline fill, i.e. a large
     // lattice (AUTO: below); kernel = STREAM forces it.  Between slabs the unit is an edge launch + a bulk launch (multi_step).
-    const bool can_stream = can_tb && p->nx >= 64 && nyp >= 64 && c->batch == 1;
-    if (p->kernel == LBM_KERNEL_STREAM && !can_stream)
+    const bool can_stream = can_tb && p.nx >= 64 && nyp >= 64 && pl.batch == 1;
+    if (p.kernel == LBM_KERNEL_STREAM && !can_stream)
         return "kernel = STREAM takes one lattice (no batch) with nx % (16 / sizeof(real)) == 0, nx >= 64, ny_local >= 64 (on every rank)";
     // AUTO (profiles/r02_logs/stream_ab3.log, slab_loopback5.log; fast MRT, GLUPS stream / tile): lone 2048^2 219 / 238, 4096 x 1024 229 /
     // 240, 4096 x 2048 296 / 268, 3072^2 306 / 274, fp64 8192 x 1024 157 / 129 -> from 8 Mi cells (fp64: 2048^2 134 / 129, 2560^2 150 / 135, 4096 x
@@ -236,21 +265,21 @@ static std::string plan_kernel(lbm_ctx* c, bool device) {
     // 2048^2 200 / 185, 4096 x 1024 247 / 181, 4096 x 2048 280 / 233, fp64 8192 x 1024 133 / 117, 2048 x 512 110 / 96 -> from 1 Mi cells
     // and 512 rows.  Lattices
     // narrower than 2048 (few strips, not measured) keep the earlier 3072^2 rule.
-    const long long cells_plan = (long long)p->nx * nyp;
+    const long long cells_plan = (long long)p.nx * nyp;
     // r03 (profiles/r03_logs/auto_sweep.log): a lone lattice whose operator variant takes the walls inside (no frame workgroups ahead of the
     // streaming ones; waves that end with their last block) pays earlier -- stream / tile, fast MRT: fp32 4096 x 512 238 / 224, 2048^2 303 /
     // 263, 4096 x 1024 317 / 257 but 1536^2 241 / 248, 2048 x 1024 228 / 237 -> wide lattices from 2 Mi cells, the others from 4 Mi at
     // 2048 columns; fp64 1024^2 112 / 101 (strict 84.5 / 82), 2048 x 512 109 / 100, 1280^2 134 / 113, 1536^2 151 / 116 but 768^2 80 / 87 -> from
     // 1 Mi cells and 1024 columns
-    const bool walls_variant = c->batch == 1 && !slab && p->semantics == LBM_SEM_MRT_GPU && !p->turb && !(p->flags & LBM_FLAG_NO_STREAM_WALLS) &&
-                               (p->collision == LBM_MRT || p->collision == LBM_SRT);
-    const bool walls_pays = walls_variant && (c->es == 8 ? p->nx >= 1024 && cells_plan >= (1LL << 20)
-                                                         : (p->nx >= 4096 && cells_plan >= (2LL << 20)) || (p->nx >= 2048 && cells_plan >= (4LL << 20)));
+    const bool walls_variant = pl.batch == 1 && !slab && p.semantics == LBM_SEM_MRT_GPU && !p.turb && !f.no_stream_walls &&
+                               (p.collision == LBM_MRT || p.collision == LBM_SRT);
+    const bool walls_pays = walls_variant && (pl.es == 8 ? p.nx >= 1024 && cells_plan >= (1LL << 20)
+                                                         : (p.nx >= 4096 && cells_plan >= (2LL << 20)) || (p.nx >= 2048 && cells_plan >= (4LL << 20)));
     const bool stream_pays = walls_pays ||
-                             (p->nx >= 2048 ? (slab ? cells_plan >= (1LL << 20) && nyp >= 512 : cells_plan >= ((c->es == 8 ? 4LL : 8LL) << 20))
+                             (p.nx >= 2048 ? (slab ? cells_plan >= (1LL << 20) && nyp >= 512 : cells_plan >= ((pl.es == 8 ? 4LL : 8LL) << 20))
                                             : cells_plan >= 3072LL * 3072);
-    if (!can_stream || !(p->kernel == LBM_KERNEL_STREAM || (p->kernel == LBM_KERNEL_AUTO && stream_pays))) {
-        c->kern = can_tb && (p->kernel == LBM_KERNEL_TB || (p->kernel == LBM_KERNEL_AUTO && big)) ? Kern::tile : Kern::none;
+    if (!can_stream || !(p.kernel == LBM_KERNEL_STREAM || (p.kernel == LBM_KERNEL_AUTO && stream_pays))) {
+        pl.kern = can_tb && (p.kernel == LBM_KERNEL_TB || (p.kernel == LBM_KERNEL_AUTO && big)) ? Kern::tile : Kern::none;
         return std::string();
     }
     // The walls inside the streaming kernel (k_stream_walls, lbm_stream.hpp): a lone lattice in MRT_GPU.py semantics needs no
@@ -266,11 +295,11 @@ static std::string plan_kernel(lbm_ctx* c, bool device) {
     // arith = promoted, fp32 (hipcc -Rpass-analysis=kernel-resource-usage): k_stream_walls MRT 128 VGPRs + 8 B of scratch per lane, SRT
     // 128 + 104 B; k_stream_walls_slab MRT 0 B, SRT 92 B -- inside the bounds below, as the strict operators: the same rule, the walls inside
     // for MRT and SRT without the closure, in the dry run as on the device (fp64 promoted runs the strict variants)
-    const int forced = p->flags & (LBM_FLAG_STREAM_WALLS | LBM_FLAG_STREAM_PAIRS);
-    const bool walls_ok = c->batch == 1 && p->semantics == LBM_SEM_MRT_GPU && (!slab || !(p->flags & LBM_FLAG_NO_DEEP_HALO));
-    bool walls_pay = !p->turb && (p->collision == LBM_MRT || p->collision == LBM_SRT);
+    const bool forced = f.stream_walls || f.stream_pairs;
+    const bool walls_ok = pl.batch == 1 && p.semantics == LBM_SEM_MRT_GPU && (!slab || pl.deep_halo);
+    bool walls_pay = !p.turb && (p.collision == LBM_MRT || p.collision == LBM_SRT);
     if (walls_ok && walls_pay && device && !forced) {
-        dispatch(c->p, [&](auto v) {
+        dispatch(p, [&](auto v) {
             using VT = decltype(v);
             using R = typename VT::R;
             if constexpr (VT::SEM == SEM_GPU) {
@@ -278,44 +307,43 @@ static std::string plan_kernel(lbm_ctx* c, bool device) {
                 const void* kern = slab ? reinterpret_cast<const void*>(&k_stream_walls_slab<R, VT::COLL, VT::TURB>)
                                         : reinterpret_cast<const void*>(&k_stream_walls<R, VT::COLL, VT::TURB>);
                 // (SRT: ~25 registers parked per block, outside the level loop, 96 - 120 B; 412 GLUPS fast all the same)
-                if (hipFuncGetAttributes(&at, kern) != hipSuccess || at.localSizeBytes > (p->collision == LBM_SRT ? 128u : 64u))
+                if (hipFuncGetAttributes(&at, kern) != hipSuccess || at.localSizeBytes > (p.collision == LBM_SRT ? 128u : 64u))
                     walls_pay = false;
             }
         });
     }
-    const bool walls = walls_ok && !(p->flags & LBM_FLAG_NO_STREAM_WALLS) && (walls_pay || forced);
+    const bool walls = walls_ok && !f.no_stream_walls && (walls_pay || forced);
     // ... and two rows per wave (k_stream_pairs): twelve waves that all work in every iteration, 10 steps per launch by default (up
     // to SP_MAX_S), a launch that costs in proportion to its steps -- so no tile-kernel tails
-    c->kern = !walls ? Kern::stream : !slab && (p->flags & LBM_FLAG_STREAM_PAIRS) ? Kern::stream_pairs : Kern::stream_walls;
+    pl.kern = !walls ? Kern::stream : !slab && f.stream_pairs ? Kern::stream_pairs : Kern::stream_walls;
     return std::string();
 }
 
 // Steps per launch (tb_steps) and the frame width (tb_f) of the kernel plan_kernel chose ("" = fine).
-static std::string plan_steps(lbm_ctx* c) {
-    const lbm_params* p = &c->p;
+static std::string plan_steps(Plan& pl, const lbm_params& p, const Forced& f) {
     const int nyp = ny_plan(p);
-    if (streaming(c)) {
-        c->tb_steps = p->tb_steps ? p->tb_steps : ST_MAX_S;
+    if (streaming(pl)) {
+        pl.tb_steps = p.tb_steps ? p.tb_steps : ST_MAX_S;
         // Frame width F, a multiple of the vector width.  Level 1 of the streaming kernel computes the cells from F - (S - 1)
         // inwards as plain pull-and-collide cells: with MRT_GPU.py's full streaming windows every cell but the wall cells
         // themselves is one (in_window), so F >= S; MRT.py's truncated windows leave kept slots in the cell next to the right /
         // bottom wall too, so F >= S + 1.
         // (bounce-back: every cell but the perimeter cells is a plain one too, F >= S)
-        const int fmin = p->semantics == LBM_SEM_MRT_PY ? 1 : 0;
-        c->tb_f = (c->tb_steps + fmin + 3) / 4 * 4;
-        while (c->tb_steps > 2 && (p->nx < 2 * c->tb_f + 16 || nyp < 2 * c->tb_f + 16)) {   // (tiny lattices: keep an interior)
-            c->tb_steps -= 1;
-            c->tb_f = (c->tb_steps + fmin + 3) / 4 * 4;
+        const int fmin = p.semantics == LBM_SEM_MRT_PY ? 1 : 0;
+        pl.tb_f = (pl.tb_steps + fmin + 3) / 4 * 4;
+        while (pl.tb_steps > 2 && (p.nx < 2 * pl.tb_f + 16 || nyp < 2 * pl.tb_f + 16)) {   // (tiny lattices: keep an interior)
+            pl.tb_steps -= 1;
+            pl.tb_f = (pl.tb_steps + fmin + 3) / 4 * 4;
         }
-        if (c->kern == Kern::stream_pairs) c->tb_steps = p->tb_steps ? p->tb_steps : 10;
-        else if (c->tb_steps > ST_MAX_S)
+        if (pl.kern == Kern::stream_pairs) pl.tb_steps = p.tb_steps ? p.tb_steps : 10;
+        else if (pl.tb_steps > ST_MAX_S)
             return "tb_steps " + std::to_string(ST_MAX_S + 1) + " .. " + std::to_string(SP_MAX_S) + " need the streaming kernel with two rows per wave (a lone lattice, MRT_GPU semantics)";
         // A slab's unit of two steps has no edge launch (multi_step takes it through the frame passes): the walls-inside kernel, which
         // would write the frame's columns too, is not used there.
-        if (c->kern == Kern::stream_walls && is_slab(c) && c->tb_steps < 3) c->kern = Kern::stream;
+        if (pl.kern == Kern::stream_walls && is_slab(pl) && pl.tb_steps < 3) pl.kern = Kern::stream;
         // (with the walls inside the tails stay on the streaming kernel: the tile kernel's four steps are no faster any more -- 247 against 256
         // GLUPS fast, 223 / 225 strict -- and the change of kernel inside a call costs: the driver's 20 steps, repeated, 337 -> 371 GLUPS)
-        c->tail_tiles = c->kern == Kern::stream && !is_slab(c) && c->es == 4 && p->semantics != LBM_SEM_MRT_PY && !(p->flags & LBM_FLAG_NO_TAIL_TILES);
+        pl.tail_tiles = pl.kern == Kern::stream && !is_slab(pl) && pl.es == 4 && p.semantics != LBM_SEM_MRT_PY && !f.no_tail_tiles;
         return std::string();
     }
     // Steps per launch: the in-place LDS tile kernel with S = 4 (fp32) or 3 (fp64), also with the Smagorinsky closure (its
@@ -324,28 +352,28 @@ static std::string plan_steps(lbm_ctx* c) {
     // three 176, four 207, five 207 GLUPS; fp64 two 75, three 99 (its x rim of V = 2 cells allows no more)
     // with the closure (perf23.log, 4096^2 fp32, S = 2 / 3 / 4): SRT 108 / 150 / 162, TRT 110 / 145 / 124 (S = 4 spills
     // under the 128-register occupancy floor), MRT 109 / 111 / 115; fp64 SRT 57 / 81 / 83, MRT 61 / 72 / 73
-    const bool trt_turb = p->turb && p->collision == LBM_TRT;
+    const bool trt_turb = p.turb && p.collision == LBM_TRT;
     // arith = FAST (perf28.log, perf29.log, perf40.log): at S = 5 the strict MRT form is arithmetic-bound (209 GLUPS, as at
     // S = 4), the factored one is not: S = 3 / 4 / 5 = 184 / 227 / 277 GLUPS; SRT 189 / 237 / 250, with the closure 152 / 188 /
     // 217; MRT + closure 150 / 187 / 202; TRT 185 / 210 / 210, with the closure 152 / 163 / 156
-    const bool fast = p->arith == LBM_ARITH_FAST;
+    const bool fast = p.arith == LBM_ARITH_FAST;
     // r02: with the exact-product multiply-adds of the strict MRT operator (lbm_device.hpp) five steps pay there too
     // (profiles/r02_logs/strict_steps.log: 4096^2 fp32 226 -> 236 GLUPS, 1024^2 134 -> 145; fp64 2048^2 S = 3 / 4 / 5 = 85 / 97 / 98)
-    const bool mrt_plain = p->collision == LBM_MRT && !p->turb;
-    const int want32 = fast ? (p->collision == LBM_TRT ? 4 : 5) : (trt_turb ? 3 : (mrt_plain ? 5 : 4));
+    const bool mrt_plain = p.collision == LBM_MRT && !p.turb;
+    const int want32 = fast ? (p.collision == LBM_TRT ? 4 : 5) : (trt_turb ? 3 : (mrt_plain ? 5 : 4));
     // fp64 (perf46.log; an x rim of two vectors from four steps on): the factored MRT operator S = 3 / 4 / 5 = 98 / 123 / 142 GLUPS
     // at 4096^2 (8192 x 1024: 91 / 109 / 129); the strict operator is arithmetic-bound (103 / 105 / 103)
     // (SRT + closure fp64: 81 / 88 / 88 GLUPS)
-    const int want64 = p->collision == LBM_MRT ? (fast || mrt_plain ? 5 : 3) : 4;
+    const int want64 = p.collision == LBM_MRT ? (fast || mrt_plain ? 5 : 3) : 4;
     // a lone small lattice is bound by the launch, not by arithmetic or bandwidth: more steps per launch whatever the operator
     // (perf52.log, strict: 160^2 fp32 4.33 -> 4.13 us per step with five, fp64 5.02 -> 4.65 with four)
-    const bool small_lone = one_launch(c) && (long long)p->nx * nyp <= 512LL * 512;
-    const int want = p->tb_steps ? p->tb_steps : small_lone ? (p->dtype == LBM_F32 ? 5 : std::max(4, want64))
-                                                            : (p->dtype == LBM_F32 ? want32 : want64);
+    const bool small_lone = one_launch(pl) && (long long)p.nx * nyp <= 512LL * 512;
+    const int want = p.tb_steps ? p.tb_steps : small_lone ? (p.dtype == LBM_F32 ? 5 : std::max(4, want64))
+                                                            : (p.dtype == LBM_F32 ? want32 : want64);
     if (want > 5) return "tb_steps 6 .. " + std::to_string(SP_MAX_S) + " need kernel = STREAM (above " + std::to_string(ST_MAX_S) + ": a lone lattice in MRT_GPU semantics)";
-    c->tb_steps = want == 2 ? 2 : ((want == 4 || want == 5) && p->nx >= 64 && nyp >= 64 ? want : 3);
-    c->tb_f = c->tb_steps >= 4 ? 2 * TB_F : TB_F;   // F >= S + 1 and a multiple of the vector width
-    if (c->kern == Kern::tile && c->tb_steps == 2) c->kern = Kern::tile2;
+    pl.tb_steps = want == 2 ? 2 : ((want == 4 || want == 5) && p.nx >= 64 && nyp >= 64 ? want : 3);
+    pl.tb_f = pl.tb_steps >= 4 ? 2 * TB_F : TB_F;   // F >= S + 1 and a multiple of the vector width
+    if (pl.kern == Kern::tile && pl.tb_steps == 2) pl.kern = Kern::tile2;
     // tile shape of the three-step kernel, A/B in one run (profiles/r01_logs/perf14.log): 14 vectors x 28 rows beats
     // 30 x 12 by 5 % for fp32 MRT (less rim arithmetic), ties for fp64 and SRT.  (The wide variant is no longer compiled.)
     return std::string();
@@ -353,8 +381,7 @@ static std::string plan_steps(lbm_ctx* c) {
 
 // The frame: beside the streaming kernel or not, fused passes or one launch per pass, cells per workgroup, LDS windows.  With
 // `device` the register counts of two kernels are read for the frame_beside rule.
-static void plan_frame(lbm_ctx* c, bool device) {
-    const lbm_params* p = &c->p;
+static void plan_frame(Plan& pl, const lbm_params& p, const Forced& f, bool device) {
     // The wall frame of a lone lattice: inside the launch (its first workgroups; they hold a CU each for ~43 us before the
     // streaming workgroups start) or as a kernel of its own on the second stream that runs BESIDE them.  The latter needs
     // room next to a streaming workgroup, which takes all the LDS and four waves per SIMD: chosen when the registers of
@@ -362,18 +389,18 @@ static void plan_frame(lbm_ctx* c, bool device) {
     // operators without the Smagorinsky closure -- and only in fp64, where it pays: 4096 x 4096 fast MRT 153 -> 169 GLUPS;
     // in fp32 the frame waves slow the streaming waves by more than the 43 us they save, 367 -> 338
     // (profiles/r02_logs/stream_ab18.log).  (A slab's frame is its edge launch, multi_step; no frame at all with the walls inside.)
-    if (c->kern == Kern::stream && !is_slab(c) && (p->flags & LBM_FLAG_FRAME_BESIDE_ON)) {
-        c->frame_beside = true;
-    } else if (c->kern == Kern::stream && !is_slab(c) && !(p->flags & LBM_FLAG_FRAME_BESIDE_OFF) && c->es == 8 && device) {
+    if (pl.kern == Kern::stream && !is_slab(pl) && f.frame_beside > 0) {
+        pl.frame_beside = true;
+    } else if (pl.kern == Kern::stream && !is_slab(pl) && f.frame_beside == 0 && pl.es == 8 && device) {
         int rs = 1 << 20, rf = 1 << 20;
-        dispatch(c->p, [&](auto v) {
+        dispatch(p, [&](auto v) {
             using VT = decltype(v);
             using R = typename VT::R;
             hipFuncAttributes at;
             if (hipFuncGetAttributes(&at, reinterpret_cast<const void*>(&k_stream<R, VT::COLL, VT::SEM, VT::TURB>)) == hipSuccess) rs = at.numRegs;
             if (hipFuncGetAttributes(&at, reinterpret_cast<const void*>(&k_frame_beside<R, VT::COLL, VT::SEM, VT::TURB>)) == hipSuccess) rf = at.numRegs;
         });
-        c->frame_beside = (rs + 7) / 8 * 8 * 4 + (rf + 7) / 8 * 8 <= 512;
+        pl.frame_beside = (rs + 7) / 8 * 8 * 4 + (rf + 7) / 8 * 8 <= 512;
     }
     // measured (profiles/r01_logs/perf37.log, perf38.log): one launch per unit instead of S + 1 and no cross-stream dependency:
     // 4096^2 fp32 278 -> 294 GLUPS, 1024^2 fp64 67 -> 91, 1024^2 fp32 96 -> 135; a batch of 64 x 384^2 loses 5 % (its many
@@ -381,55 +408,77 @@ static void plan_frame(lbm_ctx* c, bool device) {
     // (r02: with the pass windows of 64-cell segments in the launch's LDS -- 76 KiB, below -- batches gain most from the fused
     // frame: 64 x 384^2 fp32 fast 132 -> 176 GLUPS aggregate, strict 120 -> 140, fp64 81 -> 86 with 24-cell segments;
     // profiles/r02_logs/batch_ab.log.  LBM_FLAG_FRAME_FUSED_BATCH is accepted and no longer needed.)
-    c->frame_fused = !(p->flags & LBM_FLAG_FRAME_UNFUSED);
-    c->frame_lds = !(p->flags & LBM_FLAG_NO_FRAME_LDS);
-    c->frame_wide = !(p->flags & LBM_FLAG_FRAME_NARROW);
-    if ((c->frame_seg = p->frame_seg)) return;
+    if ((pl.frame_seg = p.frame_seg)) return;
     // cells of the frame per workgroup (perf43.log): short segments finish a pass in one sweep of the workgroup and suit
     // lattices whose launch is over when the frame chain is (160^2: 4.1 us per step with 16, 6.3 with 64); long ones compute
     // less overlap and suit large lattices (2048^2: 244 GLUPS with 64, 215 with 16)
-    const long long cells1 = (long long)p->nx * ny_plan(p) * c->batch;   // (what fills the device: all lattices of a batch)
-    c->frame_seg = cells1 <= 512LL * 512 ? 16 : (cells1 <= 1024LL * 1024 ? 32 : 64);
+    const long long cells1 = (long long)p.nx * ny_plan(p) * pl.batch;   // (what fills the device: all lattices of a batch)
+    pl.frame_seg = cells1 <= 512LL * 512 ? 16 : (cells1 <= 1024LL * 1024 ? 32 : 64);
     // a lone lattice under the tile kernel: the longest segment (in steps of 8 cells, not below 16) whose pass windows fit the
     // launch's LDS -- fp64 windows are twice the size (1024^2 fp64, five passes: 32-cell segments 85 KiB, 24-cell 69 KiB)
-    if (c->kern == Kern::tile && c->frame_fused && !is_slab(c) && c->frame_lds)
-        while (c->frame_seg > 16 && !frame_lds_fits(c, c->tb_steps, false, 0, TILE_FRAME_LDS_BYTES)) c->frame_seg -= 8;
+    if (pl.kern == Kern::tile && pl.frame_fused && !is_slab(pl) && pl.frame_lds)
+        while (pl.frame_seg > 16 && !frame_lds_fits(pl, pl.tb_steps, false, 0, TILE_FRAME_LDS_BYTES)) pl.frame_seg -= 8;
     // the same for the frame workgroups inside a launch of the streaming kernel (144 KiB; fp64, eight passes: 40-cell segments):
     // 4096^2 fp64 strict 113 -> 117 GLUPS, fast with the frame inside 162 -> 171, slab 8192 x 1024 in loopback 142 -> 158
-    if (streaming(c) && c->frame_lds)
-        while (c->frame_seg > 16 && !frame_lds_fits(c, c->tb_steps, false, 1, ST_LDS_BYTES)) c->frame_seg -= 8;
+    if (streaming(pl) && pl.frame_lds)
+        while (pl.frame_seg > 16 && !frame_lds_fits(pl, pl.tb_steps, false, 1, ST_LDS_BYTES)) pl.frame_seg -= 8;
     // beside the streaming kernel one frame workgroup fits on a CU: as many workgroups as CUs, not more (8192^2 fp64: 187 GLUPS
     // with 64 cells = 512 workgroups, 201 with 128 = 256; profiles/r02_logs/stream_ab20.log)
-    if (c->frame_beside) {
-        const long long per = 2LL * p->nx + 2LL * (ny_plan(p) - 2 * c->tb_f);
-        c->frame_seg = std::max(64, (int)(((per + c->ncu - 1) / c->ncu + 7) / 8 * 8));
+    if (pl.frame_beside) {
+        const long long per = 2LL * p.nx + 2LL * (ny_plan(p) - 2 * pl.tb_f);
+        pl.frame_seg = std::max(64, (int)(((per + pl.ncu - 1) / pl.ncu + 7) / 8 * 8));
     }
 }
 
-// Context with geometry and LAUNCH PLAN filled in from lbm_params and the device's compute units alone -- no HIP call unless
-// `device` (then the scratch size and register counts of kernels are read, see plan_kernel and plan_frame).  lbm_create continues
-// from here; lbm_plan (a dry run: what would every rank of a decomposition plan?) stops here.
-lbm_ctx* plan_ctx(const lbm_params* p, int ncu, bool device, std::string& err_out) {
-    lbm_ctx* c = new (std::nothrow) lbm_ctx();
-    if (!c) return (err_out = "out of host memory", nullptr);
-    c->p = *p;
-    c->ncu = ncu;
-    plan_geometry(c);
-    err_out = plan_kernel(c, device);
-    if (err_out.empty()) err_out = plan_steps(c);
-    if (!err_out.empty()) return (delete c, nullptr);
-    plan_frame(c, device);
-    c->edge_first = !(p->flags & LBM_FLAG_NO_EDGE_FIRST);
-    c->edge_reserve = !(p->flags & LBM_FLAG_NO_EDGE_RESERVE);
-    c->xcd_bands = !(p->flags & LBM_FLAG_NO_XCD_BANDS);
-    // (bounce-back slabs exchange one row per frame pass, as MRT.py semantics: the recomputed band of the neighbour's rows is not
-    // implemented for its gather)
-    c->deep_halo = p->semantics == LBM_SEM_MRT_GPU && !(p->flags & LBM_FLAG_NO_DEEP_HALO);
-    c->use_nt = (p->flags & LBM_FLAG_NT_ON) ? true : (p->flags & LBM_FLAG_NT_OFF) ? false : (c->lat_bytes > ((size_t)192 << 20));
-    c->lazy_lag = !(p->flags & LBM_FLAG_EAGER_LAG);
-    return c;
+// The LAUNCH PLAN from lbm_params and the device's compute units alone -- no HIP call unless `device` (then the scratch size and
+// register counts of kernels are read, see plan_kernel and plan_frame).  The flags are decoded first, so that no step below depends on
+// which others ran before it for a switch.  lbm_create builds its context around the result; lbm_plan (a dry run: what would every
+// rank of a decomposition plan?) describes it.  false: err says why these parameters have no plan.
+bool make_plan(const lbm_params& p, int ncu, bool device, Plan& pl, std::string& err) {
+    pl = Plan{};
+    pl.ncu = ncu;
+    const Forced f = decode_flags(p, pl);
+    plan_geometry(pl, p, f);
+    err = plan_kernel(pl, p, f, device);
+    if (err.empty()) err = plan_steps(pl, p, f);
+    if (!err.empty()) return false;
+    plan_frame(pl, p, f, device);
+    return true;
 }
 
+// The describe text of a plan (lbm_describe, and the head of lbm_plan's).  lattices_held: device lattices held now (2 + scratch lattices
+// in use + the lagged one; the dry run holds none): footprint = lattices_held * lattice_bytes.  Returns the length written, as snprintf.
+static int describe_plan(const Plan& pl, int lattices_held, char* buf, size_t len) {
+    static const char* const names[] = {"none", "k_step2_deep", "k_stepS_deep", "k_stream", "k_stream_walls", "k_stream_pairs"};
+    const int S = pl.kern != Kern::none ? pl.tb_steps : 1;
+    long long wgs = 0, wave_updates = 0;   // per launch of S steps: workgroups of the bulk kernel; (wave, level) updates they perform
+    const int V = 16 / pl.es;
+    if (streaming(pl)) {
+        const StreamPlan sp = plan_stream(pl, S);
+        wgs = (long long)sp.nstrips * sp.nsegy;
+        const int nbr = neighbours(pl);
+        const long long rows = pl.geo.ny - (walls_inside(pl) ? nbr * pl.tb_f : 2 * pl.tb_f);
+        // (with the walls inside a segment that starts / ends at a wall has no lead rows beyond it; a slab's bulk launch only)
+        wave_updates = (long long)sp.nstrips * (rows + ((long long)sp.nsegy * 2 - (walls_inside(pl) ? 2 - nbr : 0)) * (S - 1)) * S;
+    } else if (pl.kern == Kern::tile) {
+        const int F = pl.tb_f, RV = (S - 1 + V - 1) / V, TX = (16 - 2 * RV) * V, TY = 32 - 2 * (S - 1);
+        const long long ntx = (pl.geo.nx - 2 * F + TX - 1) / TX, nty = (pl.geo.ny - 2 * F + TY - 1) / TY;
+        wgs = ntx * nty * pl.batch;
+        long long per = 0;                 // active waves per step: rows [s - 1, 32 - (s - 1)) of 16 lanes -> (32 - 2 (s - 1)) / 4 waves
+        for (int s = 1; s <= S; ++s) per += (32 - 2 * (s - 1)) / 4 + ((32 - 2 * (s - 1)) % 4 ? 1 : 0);
+        wave_updates = wgs * per;
+    }
+    const int n = std::snprintf(buf, len, "kernel=%s steps_per_launch=%d frame=%d stream=%d vec=%d nt=%d deep_halo=%d frame_fused=%d lazy_lag=%d "
+                                "layout=%s workgroups=%lld wave_updates=%lld cells_per_lane=%d slab=%d frame_beside=%d frame_seg=%d "
+                                "lattices=%d lattice_bytes=%lld%s",
+                                names[(int)pl.kern], S, pl.kern != Kern::none ? (walls_inside(pl) && !is_slab(pl) ? 0 : pl.tb_f) : 0, streaming(pl) ? 1 : 0,
+                                pl.use_vec ? 1 : 0, pl.use_nt ? 1 : 0, pl.deep_halo ? 1 : 0, pl.frame_fused ? 1 : 0, pl.lazy_lag ? 1 : 0,
+                                pl.geo.row != pl.geo.pitch ? "rows" : "planes", wgs, wave_updates, V, is_slab(pl) ? 1 : 0, pl.frame_beside ? 1 : 0,
+                                pl.frame_seg, lattices_held, (long long)pl.lat_bytes,
+                                // (the wall model, where it is not one of the two wet-node semantics whose plans predate the field)
+                                pl.semantics == LBM_SEM_BOUNCE_BACK ? " semantics=bounce_back" : "");
+    return n < 0 ? LBM_ERR_INVALID : (n >= (int)len ? (int)len - 1 : n);
+}
 }  // namespace lbmhost
 
 using namespace lbmhost;
@@ -438,42 +487,15 @@ extern "C" {
 
 int lbm_next_unit(const lbm_ctx* c, int steps_left) {
     if (!c || steps_left < 0) return LBM_ERR_INVALID;
-    if (c->push) return steps_left > 0 ? 1 : 0;
-    return unit_steps(c, steps_left, c->raw[c->cur] != 0);
+    if (c->plan.push) return steps_left > 0 ? 1 : 0;
+    return unit_steps(c->plan, steps_left, c->raw[c->cur] != 0, own_transport(c));
 }
 
 int lbm_describe(const lbm_ctx* c, char* buf, size_t len) {
     if (!c || !buf || len == 0) return LBM_ERR_INVALID;
-    static const char* const names[] = {"none", "k_step2_deep", "k_stepS_deep", "k_stream", "k_stream_walls", "k_stream_pairs"};
-    const int S = c->kern != Kern::none ? c->tb_steps : 1;
-    long long wgs = 0, wave_updates = 0;   // per launch of S steps: workgroups of the bulk kernel; (wave, level) updates they perform
-    const int V = 16 / c->es;
-    if (streaming(c)) {
-        const StreamPlan pl = plan_stream(c, S);
-        wgs = (long long)pl.nstrips * pl.nsegy;
-        const int nbr = (has_neighbour(c, LBM_SIDE_LOW) ? 1 : 0) + (has_neighbour(c, LBM_SIDE_HIGH) ? 1 : 0);
-        const long long rows = c->geo.ny - (walls_inside(c) ? nbr * c->tb_f : 2 * c->tb_f);
-        // (with the walls inside a segment that starts / ends at a wall has no lead rows beyond it; a slab's bulk launch only)
-        wave_updates = (long long)pl.nstrips * (rows + ((long long)pl.nsegy * 2 - (walls_inside(c) ? 2 - nbr : 0)) * (S - 1)) * S;
-    } else if (c->kern == Kern::tile) {
-        const int F = c->tb_f, RV = (S - 1 + V - 1) / V, TX = (16 - 2 * RV) * V, TY = 32 - 2 * (S - 1);
-        const long long ntx = (c->geo.nx - 2 * F + TX - 1) / TX, nty = (c->geo.ny - 2 * F + TY - 1) / TY;
-        wgs = ntx * nty * c->batch;
-        long long per = 0;                 // active waves per step: rows [s - 1, 32 - (s - 1)) of 16 lanes -> (32 - 2 (s - 1)) / 4 waves
-        for (int s = 1; s <= S; ++s) per += (32 - 2 * (s - 1)) / 4 + ((32 - 2 * (s - 1)) % 4 ? 1 : 0);
-        wave_updates = wgs * per;
-    }
-    int nlat = 0;                          // device lattices held now (2 + scratch lattices in use + the lagged one): footprint = nlat * lattice_bytes
+    int nlat = 0;
     for (int i = 0; i < NLAT; ++i) nlat += c->lat[i] ? 1 : 0;
-    const int n = std::snprintf(buf, len, "kernel=%s steps_per_launch=%d frame=%d stream=%d vec=%d nt=%d deep_halo=%d frame_fused=%d lazy_lag=%d "
-                                "layout=%s workgroups=%lld wave_updates=%lld cells_per_lane=%d slab=%d frame_beside=%d frame_seg=%d "
-                                "lattices=%d lattice_bytes=%lld%s",
-                                names[(int)c->kern], S, c->kern != Kern::none ? (walls_inside(c) && !is_slab(c) ? 0 : c->tb_f) : 0, streaming(c) ? 1 : 0, c->use_vec ? 1 : 0, c->use_nt ? 1 : 0, c->deep_halo ? 1 : 0,
-                                c->frame_fused ? 1 : 0, c->lazy_lag ? 1 : 0, c->geo.row != c->geo.pitch ? "rows" : "planes", wgs, wave_updates, V,
-                                is_slab(c) ? 1 : 0, c->frame_beside ? 1 : 0, c->frame_seg, nlat, (long long)c->lat_bytes,
-                                // (the wall model, where it is not one of the two wet-node semantics whose plans predate the field)
-                                c->p.semantics == LBM_SEM_BOUNCE_BACK ? " semantics=bounce_back" : "");
-    return n < 0 ? LBM_ERR_INVALID : (n >= (int)len ? (int)len - 1 : n);
+    return describe_plan(c->plan, nlat, buf, len);
 }
 
 // Dry run of the launch plan: what lbm_create(p) would plan and which launch units lbm_step(steps) would then run from a fresh
@@ -484,23 +506,21 @@ int lbm_describe(const lbm_ctx* c, char* buf, size_t len) {
 // unless forced by a flag (lone lattices only: no effect on the protocol).  A buffer too small for the whole text is an error.
 int lbm_plan(const lbm_params* p, int ncu, int steps, char* buf, size_t len) {
     if (!buf || len == 0) return LBM_ERR_INVALID;
-    const std::string bad = validate_params(p);
-    std::string perr;
-    lbm_ctx* c = bad.empty() ? plan_ctx(p, ncu > 0 ? ncu : 256, false, perr) : nullptr;
-    if (!c) {
-        std::snprintf(buf, len, "error: %s", (bad.empty() ? perr : bad).c_str());
+    std::string err = validate_params(p);
+    Plan pl;
+    if (!err.empty() || !make_plan(*p, ncu > 0 ? ncu : 256, false, pl, err)) {
+        std::snprintf(buf, len, "error: %s", err.c_str());
         return LBM_ERR_INVALID;
     }
     char head[512];
-    const int n = lbm_describe(c, head, sizeof(head));
+    const int n = describe_plan(pl, 0, head, sizeof(head));
     std::string t = std::string(head, n > 0 ? n : 0) + " units=";
     for (int left = steps, raw = 1; left > 0; raw = 0) {
-        const int S = unit_steps(c, left, raw);
+        const int S = unit_steps(pl, left, raw, false);   // (no communicator: what a context answers before lbm_comm_init)
         t += std::to_string(S);
         left -= S;
         if (left > 0) t += ",";
     }
-    delete c;
     if (t.size() >= len) {
         std::snprintf(buf, len, "error: buffer too small");
         return LBM_ERR_INVALID;
