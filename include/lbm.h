@@ -172,7 +172,7 @@ int lbm_step(lbm_ctx* c, int nsteps);
 int lbm_sync(lbm_ctx* c);
 /* replaces: the commented cuda.Event timing (MRTTiledPull.py:364-365,536-549): runs nsteps
  * steps between two HIP events on the compute stream and returns the elapsed milliseconds (automatic samples of the time
- * statistics included, lbm_stats_begin) */
+ * statistics and of a monitor series included, lbm_stats_begin / lbm_monitor_begin) */
 int lbm_time_steps(lbm_ctx* c, int nsteps, double* ms);
 /* iterations performed since the last lbm_init_equilibrium / lbm_set_state */
 long long lbm_steps_done(const lbm_ctx* c);
@@ -242,6 +242,81 @@ int lbm_stats_begin(lbm_ctx* c, int every);
 int lbm_stats_sample(lbm_ctx* c);
 int lbm_stats_get(lbm_ctx* c, double* mean_u, double* mean_rho, double* second, long long* count);
 int lbm_stats_end(lbm_ctx* c);
+
+/* --- run monitor ------------------------------------------------------------------------- */
+/* replaces: what an output iteration of MRT_GPU.py:752-889 computes from the downloaded u and rho -- the two NaN-masked arg-mins of
+ * |u|^2 (vortex search, MRT_GPU.py:764-778), np.mean(u), the middle column and row -- by ONE pass over the lattice on the device that
+ * leaves a small record per lattice; no field crosses PCIe.  A SAMPLE at step count n is exactly the u[2][X][Y], rho[X][Y] that
+ * lbm_get_fields(host_dtype) would return right after n steps (same lagged lattice, gather + macros, wall overrides), whatever the
+ * kernel route, dtype, operator, arithmetic, closure, semantics, batch or slab.  Every value is first rounded to host_dtype, as
+ * lbm_get_fields does, then converted to double; everything below is computed in double without contraction.  Per cell
+ *     q = (ux * ux + uy * uy) / (uLB * uLB)         (each product rounded, then the sum, then one IEEE division by the double uLB * uLB)
+ * which is the `usq` of the reference's search operation for operation.
+ *
+ * lbm_monitor_spec: host_dtype (LBM_F32 | LBM_F64); the search window [x_lo, x_hi) x [y_lo, y_hi), y in GLOBAL rows; nboxes <= 4
+ *   exclusion boxes box[i] = {x_lo, x_hi, y_lo, y_hi} in the same form; nprobes <= 8 probe cells probe[i] = {x, global y}.  Window and
+ *   boxes need 0 <= lo <= hi <= nx (ny); a probe must be a cell of the lattice.  Anything else is LBM_ERR_INVALID.
+ * lbm_monitor_record (all doubles, one per lattice of the batch):
+ *   step       the step count whose fields it describes
+ *   nonfinite  own cells where any of ux, uy, rho is not finite; those cells are left out of everything else but the probes
+ *   sum_ux, sum_uy, sum_rho, sum_q   sums over the context's own finite cells, walls included
+ *   max_q      the maximum of q over the same cells (-inf when there is none)
+ *   min_q, min_x, min_y   the minimum of q over the finite cells inside the window and outside every box, with its cell (global y);
+ *              ties go to the smaller x, then the smaller y -- the first hit of np.nanargmin on the [X][Y] host array.  No candidate:
+ *              min_q = +inf, min_x = min_y = -1
+ *   probe[i]   ux, uy, rho at probe cell i; NaN for unused probes and for probes outside this context's rows
+ * The sums are accumulated in a fixed tree (lane, wave, workgroup, then the workgroups' partial results in index order) without
+ * atomics: identical from run to run, and identical between the one-shot call and a series.
+ *
+ * lbm_monitor: one record per lattice of the fields lbm_get_fields would return now (records_out[batch]); synchronises.
+ *   LBM_ERR_STATE before the first step.
+ * lbm_monitor_begin: starts a series with room for `capacity` samples (capacity x batch records on the device, allocated here, never
+ *   inside lbm_step).  every > 0: lbm_step and lbm_time_steps take the sample of step counts n0 + every, n0 + 2 every, ... by themselves,
+ *   from the lattice after n - 1 steps where a launch unit starts there -- the mechanism and the rules of lbm_stats_begin (the units are
+ *   cut at the earlier of the two samplers' next sample; lbm_step_unit and the split-step calls refuse; LBM_ERR_STATE on a slab).
+ *   every = 0: samples through lbm_monitor_sample only.  A sample writes slot `count` of the device buffer; nothing returns to the host
+ *   before lbm_monitor_read.  With the buffer full further samples are not taken but counted in `dropped`; stepping is unaffected.
+ *   Calling it again restarts the series.
+ * lbm_monitor_sample: the record of the fields lbm_get_fields would return now, appended to the series.
+ * lbm_monitor_read: synchronises; *count = samples held, *dropped = samples not taken; records_out[min(count, max_records)][batch]
+ *   receives the oldest records (may be NULL with max_records = 0).  The series goes on.
+ * lbm_monitor_end: stops sampling and frees the series.  lbm_init_equilibrium, lbm_set_state and lbm_destroy end it too; it is not part
+ *   of a checkpoint.  lbm_monitor_sample / _read return LBM_ERR_STATE while no series is on.
+ * lbm_get_lines: the column x and the global row gy of the fields lbm_get_fields(host_dtype) would return, the same bits:
+ *   col_out[B][3][NY] receives ux, uy, rho of column x (own rows only), row_out[B][3][nx] those of row gy (written only if this
+ *   context owns that row).  Either pointer may be NULL (its index is then ignored).  Synchronises. */
+enum { LBM_MONITOR_MAX_BOXES = 4, LBM_MONITOR_MAX_PROBES = 8 };
+typedef struct lbm_monitor_spec {
+    int32_t struct_size;  /* = sizeof(lbm_monitor_spec) */
+    int32_t host_dtype;
+    int32_t x_lo;
+    int32_t x_hi;
+    int32_t y_lo;
+    int32_t y_hi;
+    int32_t nboxes;
+    int32_t nprobes;
+    int32_t box[4][4];
+    int32_t probe[8][2];
+} lbm_monitor_spec;
+typedef struct lbm_monitor_record {
+    double step;
+    double nonfinite;
+    double sum_ux;
+    double sum_uy;
+    double sum_rho;
+    double sum_q;
+    double max_q;
+    double min_q;
+    double min_x;
+    double min_y;
+    double probe[8][3];
+} lbm_monitor_record;
+int lbm_monitor(lbm_ctx* c, const lbm_monitor_spec* spec, lbm_monitor_record* records_out);
+int lbm_monitor_begin(lbm_ctx* c, const lbm_monitor_spec* spec, int every, int capacity);
+int lbm_monitor_sample(lbm_ctx* c);
+int lbm_monitor_read(lbm_ctx* c, lbm_monitor_record* records_out, int max_records, long long* count, long long* dropped);
+int lbm_monitor_end(lbm_ctx* c);
+int lbm_get_lines(lbm_ctx* c, int x, int gy, void* col_out, void* row_out, int host_dtype);
 
 /* --- slab decomposition, externally driven exchange ---------------------------------- */
 /* No reference counterpart (the reference is single-GPU, MRT_GPU.py:29).  A step of a slab

@@ -43,13 +43,27 @@ class lbm_params(ctypes.Structure):
                 ("omega_e", ctypes.c_double), ("omega_eps", ctypes.c_double), ("omega_q", ctypes.c_double)]
 
 
+LBM_MONITOR_MAX_BOXES, LBM_MONITOR_MAX_PROBES = 4, 8
+
+
+class lbm_monitor_spec(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_int32), ("host_dtype", ctypes.c_int32), ("x_lo", ctypes.c_int32), ("x_hi", ctypes.c_int32),
+                ("y_lo", ctypes.c_int32), ("y_hi", ctypes.c_int32), ("nboxes", ctypes.c_int32), ("nprobes", ctypes.c_int32),
+                ("box", (ctypes.c_int32 * 4) * LBM_MONITOR_MAX_BOXES), ("probe", (ctypes.c_int32 * 2) * LBM_MONITOR_MAX_PROBES)]
+
+
+class lbm_monitor_record(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_double) for n in ("step", "nonfinite", "sum_ux", "sum_uy", "sum_rho", "sum_q", "max_q", "min_q", "min_x",
+                                               "min_y")] + [("probe", (ctypes.c_double * 3) * LBM_MONITOR_MAX_PROBES)]
+
+
 def sources():
     return [os.path.join(_CSRC, f) for f in sorted(os.listdir(_CSRC)) if f.endswith((".hip", ".hpp"))] + [HEADER]
 
 
 def build(force=False, verbose=False):
-    """Compile csrc/*.hip for gfx950 into liblbm_hip.so next to this file (in-tree).  The translation units (four of host code +
-    C ABI: lbm_hip / lbm_plan / lbm_launch / lbm_comm; the explicit instantiations of the tile and streaming kernels for float and
+    """Compile csrc/*.hip for gfx950 into liblbm_hip.so next to this file (in-tree).  The translation units (five of host code +
+    C ABI: lbm_hip / lbm_plan / lbm_launch / lbm_comm / lbm_monitor; the explicit instantiations of the tile and streaming kernels for float and
     for double) are compiled in parallel into csrc/_obj/ and linked."""
     srcs = sources()
     if not force and os.path.exists(LIB_PATH) and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(s) for s in srcs):
@@ -102,6 +116,13 @@ SIGNATURES = {
     "lbm_stats_sample": (_i, [_vp]),
     "lbm_stats_get": (_i, [_vp, _vp, _vp, _vp, ctypes.POINTER(ctypes.c_longlong)]),
     "lbm_stats_end": (_i, [_vp]),
+    "lbm_monitor": (_i, [_vp, ctypes.POINTER(lbm_monitor_spec), ctypes.POINTER(lbm_monitor_record)]),
+    "lbm_monitor_begin": (_i, [_vp, ctypes.POINTER(lbm_monitor_spec), _i, _i]),
+    "lbm_monitor_sample": (_i, [_vp]),
+    "lbm_monitor_read": (_i, [_vp, ctypes.POINTER(lbm_monitor_record), _i, ctypes.POINTER(ctypes.c_longlong),
+                              ctypes.POINTER(ctypes.c_longlong)]),
+    "lbm_monitor_end": (_i, [_vp]),
+    "lbm_get_lines": (_i, [_vp, _i, _i, _vp, _vp, _i]),
     "lbm_halo_elems": (_i, [_vp]),
     "lbm_halo_export": (_i, [_vp, _i, _vp]),
     "lbm_halo_import": (_i, [_vp, _i, _vp]),

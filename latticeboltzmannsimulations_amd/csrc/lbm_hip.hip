@@ -242,6 +242,7 @@ void lbm_destroy(lbm_ctx* c) {
         if (c->lat[i]) (void)hipFree(c->lat[i]);
     if (c->red_dev) (void)hipFree(c->red_dev);
     stats_free(c);
+    monitor_free(c);
     if (c->stage) (void)hipFree(c->stage);
     if (c->relax_dev) (void)hipFree(c->relax_dev);
     if (c->ev_edges) (void)hipEventDestroy(c->ev_edges);
@@ -263,6 +264,7 @@ int lbm_init_equilibrium(lbm_ctx* c) {
     int rc = sync_all(c);
     if (rc) return rc;
     stats_free(c);
+    monitor_series_free(c);
     c->cur = 0; c->raw[0] = 1; c->raw[1] = 1; c->nsteps = 0; c->lag = 0; c->lag_valid = false; c->thin_valid = false;
     const dim3 g = grid_rows(c, c->plan.geo.ny);
     rc = launch_variant(c, [&](auto v) {
@@ -284,6 +286,7 @@ int lbm_set_state(lbm_ctx* c, const void* fin_host, int host_dtype) {
     rc = host_to_stage(c, fin_host, host_dtype, Q * c->plan.batch);   // [B][9][nx][ny] is B * 9 planes
     if (rc) return rc;
     stats_free(c);
+    monitor_series_free(c);
     c->cur = 0; c->raw[0] = 1; c->raw[1] = 1; c->nsteps = 0; c->lag = 0; c->lag_valid = false; c->thin_valid = false;
     rc = launch_variant(c, [&](auto v) {
         using VT = decltype(v);

@@ -5,6 +5,7 @@
 //   lbm_plan.hip    parameter validation, launch planning, unit sequence, the dry run    (C ABI: next_unit, describe, plan)
 //   lbm_launch.hip  kernel launches and the step loop (single / multi-step units, lag)   (C ABI: step*, time_steps)
 //   lbm_comm.hip    RCCL binding, halo exchanges, host-transported halos                 (C ABI: halo_*, comm_*)
+//   lbm_monitor.hip the run monitor and the line export (kernels: lbm_monitor.hpp)        (C ABI: monitor*, get_lines)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>  // types and prototypes only: RCCL is bound lazily with dlopen (see rccl_api)
@@ -103,6 +104,15 @@ struct lbm_ctx {
     long long stats_count = 0;  // samples enqueued
     int stats_every = 0;
     long long stats_next = 0;
+    // Run monitor (lbm_monitor*, lbm_monitor.hip): mon_part holds the workgroups' partial results of one pass and, behind them, the
+    // records of the one-shot call (allocated on first use, kept); mon_series the records of a series, [capacity][batch], null while
+    // no series is on.  Automatic sampling (mon_every > 0) cuts the units like the statistics do (step_many).
+    double* mon_part = nullptr;
+    lbm_monitor_record* mon_series = nullptr;
+    lbm_monitor_spec mon_spec{};
+    long long mon_capacity = 0, mon_count = 0, mon_dropped = 0;
+    int mon_every = 0;
+    long long mon_next = 0;
     ncclComm_t comm = nullptr;
     int nranks = 1, rank = 0;
     bool thin_valid = false;    // the one-row halo of lat[cur] has been exchanged (by the RCCL path, on s_comm)
@@ -341,6 +351,10 @@ int prev_lattice(lbm_ctx* c, int* which);
 int push_step(lbm_ctx* c);
 int push_reset(lbm_ctx* c);
 int step_many(lbm_ctx* c, int nsteps);
+// lbm_monitor.hip
+int monitor_series_sample(lbm_ctx* c, int which, long long step);
+void monitor_series_free(lbm_ctx* c);
+void monitor_free(lbm_ctx* c);
 // lbm_comm.hip
 rccl_api& rccl();
 void halo_range(const lbm_ctx* c, int k, int* lo, int* hi);

@@ -1,0 +1,237 @@
+// lbm_monitor.hip -- liblbm_hip.so: the run monitor (lbm_monitor, lbm_monitor_begin / _sample / _read / _end) and the export of one
+// column and one row (lbm_get_lines) of the C ABI declared in include/lbm.h.  The kernels are in lbm_monitor.hpp; the automatic
+// samples of a series are taken by step_many (lbm_launch.hip) through monitor_series_sample.  gfx950 only.  DESIGN.md 2.7.
+#include "lbm_host.hpp"
+#include "lbm_monitor.hpp"
+
+namespace lbmhost {
+
+constexpr int MON_BLOCKS = 1024;   // partial results per lattice (as lbm_mean_u: enough workgroups to keep every CU's loads in flight)
+
+static_assert(sizeof(lbm_monitor_record) == (1 + MON_VALS + 3 * LBM_MONITOR_MAX_PROBES) * sizeof(double), "record layout");
+
+// "" or what is wrong with the spec for this context
+static std::string check_spec(const lbm_ctx* c, const lbm_monitor_spec* s) {
+    if (!s) return "null spec";
+    if (s->struct_size != (int32_t)sizeof(lbm_monitor_spec)) return "struct_size is not sizeof(lbm_monitor_spec)";
+    if (s->host_dtype != LBM_F32 && s->host_dtype != LBM_F64) return "host_dtype must be LBM_F32 or LBM_F64";
+    const int nx = c->plan.geo.nx, NY = c->plan.geo.NY;
+    auto range = [](int lo, int hi, int n) { return 0 <= lo && lo <= hi && hi <= n; };
+    if (!range(s->x_lo, s->x_hi, nx) || !range(s->y_lo, s->y_hi, NY)) return "the window is not inside the lattice";
+    if (s->nboxes < 0 || s->nboxes > LBM_MONITOR_MAX_BOXES) return "nboxes must be 0 .. " + std::to_string((int)LBM_MONITOR_MAX_BOXES);
+    if (s->nprobes < 0 || s->nprobes > LBM_MONITOR_MAX_PROBES) return "nprobes must be 0 .. " + std::to_string((int)LBM_MONITOR_MAX_PROBES);
+    for (int b = 0; b < s->nboxes; ++b)
+        if (!range(s->box[b][0], s->box[b][1], nx) || !range(s->box[b][2], s->box[b][3], NY)) return "an exclusion box is not inside the lattice";
+    for (int i = 0; i < s->nprobes; ++i)
+        if (s->probe[i][0] < 0 || s->probe[i][0] >= nx || s->probe[i][1] < 0 || s->probe[i][1] >= NY) return "a probe is not a cell of the lattice";
+    return "";
+}
+
+static MonSpec kernel_spec(const lbm_monitor_spec& s) {
+    MonSpec m{};
+    m.host_f32 = s.host_dtype == LBM_F32;
+    m.x_lo = s.x_lo; m.x_hi = s.x_hi; m.y_lo = s.y_lo; m.y_hi = s.y_hi;
+    m.nboxes = s.nboxes; m.nprobes = s.nprobes;
+    for (int b = 0; b < LBM_MONITOR_MAX_BOXES; ++b)
+        for (int j = 0; j < 4; ++j) m.box[b][j] = s.box[b][j];
+    for (int i = 0; i < LBM_MONITOR_MAX_PROBES; ++i)
+        for (int j = 0; j < 2; ++j) m.probe[i][j] = s.probe[i][j];
+    return m;
+}
+
+static int mon_blocks(const lbm_ctx* c) {
+    const long long n = (long long)c->plan.geo.nx * c->plan.geo.ny;
+    return (int)std::min<long long>((n + BLK - 1) / BLK, MON_BLOCKS);
+}
+
+// the partial results of one pass, and behind them the records of the one-shot call
+static int ensure_partials(lbm_ctx* c) {
+    if (c->mon_part) return LBM_OK;
+    const size_t bytes = (size_t)c->plan.batch * ((size_t)MON_BLOCKS * MON_VALS * sizeof(double) + sizeof(lbm_monitor_record));
+    hipError_t e = hipMalloc((void**)&c->mon_part, bytes);
+    if (e != hipSuccess) {
+        c->mon_part = nullptr;
+        return fail(c, LBM_ERR_NOMEM, std::string("hipMalloc(monitor): ") + hipGetErrorString(e));
+    }
+    return LBM_OK;
+}
+static lbm_monitor_record* one_shot_records(lbm_ctx* c) {
+    return (lbm_monitor_record*)(c->mon_part + (size_t)c->plan.batch * MON_BLOCKS * MON_VALS);
+}
+
+// One sample of lat[which] (the lattice whose gathered populations are the state the sampled iteration starts from) into rec[batch],
+// on the compute stream: the fused pass, then the final pass.
+static int monitor_enqueue(lbm_ctx* c, int which, const lbm_monitor_spec& spec, long long step, lbm_monitor_record* rec) {
+    const MonSpec sp = kernel_spec(spec);
+    const int blocks = mon_blocks(c);
+    const double den = c->p.uLB * c->p.uLB;
+    return launch_variant(c, [&](auto v) {
+        using VT = decltype(v);
+        using R = typename VT::R;
+        hipLaunchKernelGGL((k_monitor<R, VT::SEM, coll_is_prom(VT::COLL)>), dim3(blocks, 1, c->plan.batch), dim3(BLK), 0, c->s_compute,
+                           (const R*)c->lat[which], c->plan.geo, c->raw[which], (R)c->p.uLB, den, c->plan.bstride, sp, c->mon_part);
+        hipLaunchKernelGGL((k_monitor_final<R, VT::SEM, coll_is_prom(VT::COLL)>), dim3(c->plan.batch), dim3(MON_WAVE), 0, c->s_compute,
+                           (const double*)c->mon_part, blocks, (const R*)c->lat[which], c->plan.geo, c->raw[which], (R)c->p.uLB, c->plan.bstride, sp,
+                           (double)step, (double*)rec);
+    });
+}
+
+// The next sample of the series from lat[which]: slot mon_count of the device buffer; a full buffer drops it.
+int monitor_series_sample(lbm_ctx* c, int which, long long step) {
+    if (c->mon_count >= c->mon_capacity) {
+        ++c->mon_dropped;
+        return LBM_OK;
+    }
+    const int rc = monitor_enqueue(c, which, c->mon_spec, step, c->mon_series + (size_t)c->mon_count * c->plan.batch);
+    if (rc) return rc;
+    ++c->mon_count;
+    return LBM_OK;
+}
+
+// Series off (lbm_monitor_end, and whatever replaces the state: init / upload / destroy).  The caller has synchronised the streams.
+void monitor_series_free(lbm_ctx* c) {
+    if (c->mon_series) (void)hipFree(c->mon_series);
+    c->mon_series = nullptr;
+    c->mon_capacity = c->mon_count = c->mon_dropped = 0;
+    c->mon_every = 0;
+    c->mon_next = 0;
+}
+void monitor_free(lbm_ctx* c) {
+    monitor_series_free(c);
+    if (c->mon_part) (void)hipFree(c->mon_part);
+    c->mon_part = nullptr;
+}
+}  // namespace lbmhost
+
+using namespace lbmhost;
+
+extern "C" {
+
+int lbm_monitor(lbm_ctx* c, const lbm_monitor_spec* spec, lbm_monitor_record* records_out) {
+    if (!c || !spec || !records_out) return fail(c, LBM_ERR_INVALID, "lbm_monitor: bad argument");
+    const std::string bad = check_spec(c, spec);
+    if (!bad.empty()) return fail(c, LBM_ERR_INVALID, "lbm_monitor: " + bad);
+    if (c->nsteps == 0) return fail(c, LBM_ERR_STATE, "lbm_monitor: no step yet (the fields of an iteration exist after it)");
+    HIP_TRY(c, hipSetDevice(c->p.device));
+    int rc = sync_all(c);
+    if (rc) return rc;
+    rc = ensure_partials(c);
+    if (rc) return rc;
+    int which = 0;
+    rc = prev_lattice(c, &which);   // (what lbm_get_fields exports: the lattice the last iteration started from)
+    if (rc) return rc;
+    rc = monitor_enqueue(c, which, *spec, c->nsteps, one_shot_records(c));
+    if (rc) return rc;
+    HIP_TRY(c, hipMemcpyAsync(records_out, one_shot_records(c), (size_t)c->plan.batch * sizeof(lbm_monitor_record), hipMemcpyDeviceToHost, c->s_compute));
+    HIP_TRY(c, hipStreamSynchronize(c->s_compute));
+    return LBM_OK;
+}
+
+int lbm_monitor_begin(lbm_ctx* c, const lbm_monitor_spec* spec, int every, int capacity) {
+    if (!c || !spec || every < 0 || capacity < 1) return fail(c, LBM_ERR_INVALID, "lbm_monitor_begin: bad argument");
+    const std::string bad = check_spec(c, spec);
+    if (!bad.empty()) return fail(c, LBM_ERR_INVALID, "lbm_monitor_begin: " + bad);
+    if (every > 0 && is_slab(c->plan))
+        return fail(c, LBM_ERR_STATE, "lbm_monitor_begin: no automatic sampling on a slab (every = 0, and lbm_monitor_sample at the same step "
+                                      "counts on every slab)");
+    HIP_TRY(c, hipSetDevice(c->p.device));
+    int rc = sync_all(c);
+    if (rc) return rc;
+    rc = ensure_partials(c);
+    if (rc) return rc;
+    monitor_series_free(c);
+    hipError_t e = hipMalloc((void**)&c->mon_series, (size_t)capacity * c->plan.batch * sizeof(lbm_monitor_record));
+    if (e != hipSuccess) {
+        c->mon_series = nullptr;
+        return fail(c, LBM_ERR_NOMEM, std::string("hipMalloc(monitor series): ") + hipGetErrorString(e));
+    }
+    c->mon_spec = *spec;
+    c->mon_capacity = capacity;
+    c->mon_every = every;
+    c->mon_next = c->nsteps + every;
+    return LBM_OK;
+}
+
+int lbm_monitor_sample(lbm_ctx* c) {
+    if (!c) return LBM_ERR_INVALID;
+    if (!c->mon_series) return fail(c, LBM_ERR_STATE, "lbm_monitor_sample: no series is on (lbm_monitor_begin)");
+    if (c->nsteps == 0) return fail(c, LBM_ERR_STATE, "lbm_monitor_sample: no step yet (the fields of an iteration exist after it)");
+    HIP_TRY(c, hipSetDevice(c->p.device));
+    int rc = sync_all(c);
+    if (rc) return rc;
+    int which = 0;
+    rc = prev_lattice(c, &which);
+    if (rc) return rc;
+    return monitor_series_sample(c, which, c->nsteps);
+}
+
+int lbm_monitor_read(lbm_ctx* c, lbm_monitor_record* records_out, int max_records, long long* count, long long* dropped) {
+    if (!c || max_records < 0 || (max_records > 0 && !records_out)) return fail(c, LBM_ERR_INVALID, "lbm_monitor_read: bad argument");
+    if (!c->mon_series) return fail(c, LBM_ERR_STATE, "lbm_monitor_read: no series is on (lbm_monitor_begin)");
+    HIP_TRY(c, hipSetDevice(c->p.device));
+    const int rc = sync_all(c);
+    if (rc) return rc;
+    if (count) *count = c->mon_count;
+    if (dropped) *dropped = c->mon_dropped;
+    const long long n = std::min<long long>(c->mon_count, max_records);
+    if (n > 0) HIP_TRY(c, hipMemcpy(records_out, c->mon_series, (size_t)n * c->plan.batch * sizeof(lbm_monitor_record), hipMemcpyDeviceToHost));
+    return LBM_OK;
+}
+
+int lbm_monitor_end(lbm_ctx* c) {
+    if (!c) return LBM_ERR_INVALID;
+    HIP_TRY(c, hipSetDevice(c->p.device));
+    const int rc = sync_all(c);
+    if (rc) return rc;
+    monitor_series_free(c);
+    return LBM_OK;
+}
+
+int lbm_get_lines(lbm_ctx* c, int x, int gy, void* col_out, void* row_out, int host_dtype) {
+    if (!c || (host_dtype != LBM_F32 && host_dtype != LBM_F64)) return fail(c, LBM_ERR_INVALID, "lbm_get_lines: bad argument");
+    const int nx = c->plan.geo.nx, ny = c->plan.geo.ny, NY = c->plan.geo.NY, y0 = c->plan.geo.y0, B = c->plan.batch;
+    if (col_out && (x < 0 || x >= nx)) return fail(c, LBM_ERR_INVALID, "lbm_get_lines: column outside the lattice");
+    if (row_out && (gy < 0 || gy >= NY)) return fail(c, LBM_ERR_INVALID, "lbm_get_lines: row outside the lattice");
+    HIP_TRY(c, hipSetDevice(c->p.device));
+    int rc = sync_all(c);
+    if (rc) return rc;
+    const int cx = col_out ? x : -1;
+    const int ly = row_out && gy >= y0 && gy < y0 + ny ? gy - y0 : -1;
+    if (cx < 0 && ly < 0) return LBM_OK;
+    const size_t per = (size_t)3 * (ny + nx);
+    // (at least what lbm_get_fields asks for, so that the two calls do not reallocate the staging buffer in turn)
+    rc = ensure_stage(c, std::max((size_t)12 * nx * ny, per) * c->plan.es * B);
+    if (rc) return rc;
+    int which = 0;
+    rc = prev_lattice(c, &which);
+    if (rc) return rc;
+    rc = launch_variant(c, [&](auto v) {
+        using VT = decltype(v);
+        using R = typename VT::R;
+        hipLaunchKernelGGL((k_export_lines<R, VT::SEM, coll_is_prom(VT::COLL)>), dim3((ny + nx + BLK - 1) / BLK, 1, B), dim3(BLK), 0, c->s_compute,
+                           (const R*)c->lat[which], c->plan.geo, c->raw[which], (R)c->p.uLB, c->plan.bstride, cx, ly, (R*)c->stage);
+    });
+    if (rc) return rc;
+    std::vector<char> tmp(per * B * c->plan.es);
+    HIP_TRY(c, hipMemcpyAsync(tmp.data(), c->stage, tmp.size(), hipMemcpyDeviceToHost, c->s_compute));
+    HIP_TRY(c, hipStreamSynchronize(c->s_compute));
+    // staging of lattice b: [3][ny] of the column, then [3][nx] of the row, in the lattice's type; the host arrays in host_dtype
+    auto put = [&](void* dst, size_t di, size_t si) {
+        if (c->p.dtype == LBM_F32) {
+            const float v = ((const float*)tmp.data())[si];
+            if (host_dtype == LBM_F32) ((float*)dst)[di] = v; else ((double*)dst)[di] = (double)v;
+        } else {
+            const double v = ((const double*)tmp.data())[si];
+            if (host_dtype == LBM_F32) ((float*)dst)[di] = (float)v; else ((double*)dst)[di] = v;
+        }
+    };
+    for (int b = 0; b < B; ++b)
+        for (int q = 0; q < 3; ++q) {
+            if (cx >= 0)
+                for (int y = 0; y < ny; ++y) put(col_out, ((size_t)b * 3 + q) * NY + y0 + y, b * per + (size_t)q * ny + y);
+            if (ly >= 0)
+                for (int i = 0; i < nx; ++i) put(row_out, ((size_t)b * 3 + q) * nx + i, b * per + (size_t)3 * ny + (size_t)q * nx + i);
+        }
+    return LBM_OK;
+}
+}  // extern "C"

@@ -103,8 +103,26 @@ def centrelines(u, uLB):
 def regression_value(u, Re, uLB):
     """The CPU script's home-made agreement number (MRT.py:557-561)."""
     _, X, Y = u.shape
+    return regression_from_column(u[0, int(X / 2), :], Re, uLB)
+
+
+def r2_from_column(ux_column, Re, uLB):
+    """r2_value from the middle column alone: ux_column = u[0, int(X / 2), :] (what CavitySolver.lines() returns without the field)."""
+    ux_column = np.asarray(ux_column)
+    y_true = ghia_profiles(Re)[1][:-1]
+    ux_tmp = ux_column[sample_rows(ux_column.shape[-1])] / uLB
+    ux_tmp = ux_tmp + 0.001
+    y_pred = np.fliplr(np.atleast_2d(ux_tmp))[0]
+    ss_res = np.sum((y_true - y_pred) ** 2)
+    ss_tot = np.sum((y_true - np.mean(y_true)) ** 2)
+    return 1.0 - ss_res / ss_tot
+
+
+def regression_from_column(ux_column, Re, uLB):
+    """regression_value from the middle column alone, ux_column = u[0, int(X / 2), :] (see r2_from_column)."""
+    ux_column = np.asarray(ux_column)
     ux_ghia = ghia_profiles(Re)[1]
-    ux_tmp = u[0, int(X / 2), sample_rows(Y)] / uLB
+    ux_tmp = ux_column[sample_rows(ux_column.shape[-1])] / uLB
     flipped = np.fliplr(np.atleast_2d(ux_tmp))[0]
     tmp = abs((abs(ux_ghia[:-1]) - abs(flipped)) / (len(ux_tmp) * np.maximum(abs(ux_ghia[:-1]), abs(flipped))))
     return 1 - np.sum(tmp, axis=0)
@@ -114,13 +132,7 @@ def r2_value(u, Re, uLB):
     """The GPU script's metric (MRT_GPU.py:815-821): coefficient of determination
     r2_score(Ux_Ghia[:-1], flipped(Ux_LBM + 0.001)), written out (no sklearn dependency)."""
     _, X, Y = u.shape
-    y_true = ghia_profiles(Re)[1][:-1]
-    ux_tmp = u[0, int(X / 2), sample_rows(Y)] / uLB
-    ux_tmp = ux_tmp + 0.001
-    y_pred = np.fliplr(np.atleast_2d(ux_tmp))[0]
-    ss_res = np.sum((y_true - y_pred) ** 2)
-    ss_tot = np.sum((y_true - np.mean(y_true)) ** 2)
-    return 1.0 - ss_res / ss_tot
+    return r2_from_column(u[0, int(X / 2), :], Re, uLB)
 
 
 def locate_vortices(u, uLB):

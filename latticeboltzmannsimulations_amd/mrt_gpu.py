@@ -23,6 +23,7 @@ import numpy as np
 
 from . import ghia
 from .VTKWrapper import saveToVTK
+from .monitor import vortex_window
 from .solver import CavitySolver
 
 
@@ -43,6 +44,10 @@ class CavityResult:
         self.uv = None
         self.samples = 0
         self.regression_mean = []   # (iteration, value of the time-mean) at every output iteration with samples
+        # run_cavity(monitor="device"): the checks reduced on the device
+        self.diverged = False       # a check found cells that are not finite; the run stopped there
+        self.vortices = []          # (iteration, (x1, y1), (x2, y2)) at every output iteration
+        self.series = None          # run_cavity(MonitorEvery=k): CavitySolver.monitor_series() of the whole run
 
 
 CS2_EFFECTIVE, CS_BULK = 0.025, 0.16     # MRT_GPU.py:350,374-376: Van Driest damping is overwritten by Cs2 = 0.025
@@ -120,7 +125,8 @@ def _dashboard(path, u, rho, It, hist, Re, RT, regime, BC, xsize, ysize, uLB, re
 def run_cavity(maxIt=3000000, Re=10000.0, RT="SRT", turb=1, xsize=32 * 5, ysize=32 * 5, uLB=0.08,
                Pinterval=3000, SavePlot=True, SaveVTK=False, project="ldc", OutputFolder="./output",
                dtype=np.float32, semantics="mrt_gpu", device=0, quiet=False, solver_factory=None, arith="strict",
-               convergence="host", vtk_correct=False, BC="EB-NEBB ", AverageFrom=None, AverageEvery=100):
+               convergence="host", vtk_correct=False, BC="EB-NEBB ", AverageFrom=None, AverageEvery=100, monitor="host",
+               MonitorEvery=None, Probes=()):
     """Run the lid-driven cavity like MRT_GPU.py does; returns a :class:`CavityResult`.
 
     Argument names and defaults are the module constants of MRT_GPU.py:38-58.
@@ -136,7 +142,22 @@ def run_cavity(maxIt=3000000, Re=10000.0, RT="SRT", turb=1, xsize=32 * 5, ysize=
     AverageFrom: time statistics on the device (CavitySolver.begin_statistics) from iteration AverageFrom on -- samples of the fields
     after AverageFrom + AverageEvery, AverageFrom + 2 AverageEvery, ... iterations; every output iteration with samples then prints
     the Ghia regression value of the time-mean and, with SaveVTK, writes <project>_mean.#####.vtr; the result carries u_mean,
-    rho_mean, uu, vv, uv (central moments), samples and regression_mean.  None (default): no statistics, nothing changes."""
+    rho_mean, uu, vv, uv (central moments), samples and regression_mean.  None (default): no statistics, nothing changes.
+    monitor: 'host' (default) -- every check on the downloaded fields, as the reference does; 'device' -- every Pinterval is an output
+    iteration whether or not files are written, and its checks are reduced on the GPU: the regression value from the middle column
+    (CavitySolver.lines), the printed mean velocity from the monitor record's sums, the vortex positions from
+    CavitySolver.locate_vortices (result.vortices), the convergence test on lbm_mean_u (convergence='device' is implied); the fields
+    are downloaded only for the files SavePlot / SaveVTK ask for.  A record with cells that are not finite stops the run:
+    result.diverged, and the iteration is printed.  MonitorEvery=k (with monitor='device'): a series of monitor records on the device
+    from iteration 0 on, one every k iterations, with the cells `Probes` ((x, y), ...; default: the lattice centre) -- returned as
+    result.series, nothing crosses PCIe before the run ends."""
+    if monitor not in ("host", "device"):
+        raise ValueError("monitor must be 'host' or 'device'")
+    on_device = monitor == "device"
+    if MonitorEvery is not None and (not on_device or int(MonitorEvery) < 1):
+        raise ValueError("MonitorEvery needs monitor='device' and must be >= 1")
+    if on_device:
+        convergence = "device"
     if convergence not in ("host", "device"):
         raise ValueError("convergence must be 'host' or 'device'")
     if AverageFrom is not None and (int(AverageFrom) < 0 or int(AverageEvery) < 1):
@@ -187,8 +208,12 @@ def run_cavity(maxIt=3000000, Re=10000.0, RT="SRT", turb=1, xsize=32 * 5, ysize=
     count = 0
     done = 0          # iterations performed
     have_ghia = int(round(float(Re))) in ghia.RE_COLUMNS
-    outputs = SaveVTK or SavePlot
+    outputs = SaveVTK or SavePlot or on_device
     averaging = False
+    if MonitorEvery is not None:
+        probes = tuple(Probes) if len(Probes) else ((int(xsize / 2), int(ysize / 2)),)
+        solver.begin_monitor(every=int(MonitorEvery), capacity=min(maxIt // int(MonitorEvery) + 1, 1 << 18), probes=probes,
+                             out_dtype=np.float32)
 
     def advance(n):   # n iterations; statistics begin once `done` reaches AverageFrom
         nonlocal averaging
@@ -213,11 +238,21 @@ def run_cavity(maxIt=3000000, Re=10000.0, RT="SRT", turb=1, xsize=32 * 5, ysize=
         done = nxt + 1
         It = nxt
         if (It % Pinterval == 0) and outputs:
-            u_past = u.copy()
-            u, rho = solver.get_fields(out_dtype=np.float32)
+            if on_device:
+                # (the sums and the count of cells that are not finite ignore the window: the same pass is the vortex search's first)
+                rec = solver.monitor(window=vortex_window(xsize, ysize)[1], out_dtype=np.float32)
+                if SavePlot or SaveVTK:
+                    u, rho = solver.get_fields(out_dtype=np.float32)
+            else:
+                u_past = u.copy()
+                u, rho = solver.get_fields(out_dtype=np.float32)
             say("current iteration :", It)
+            if on_device and rec["nonfinite"] > 0:
+                say("breaking out of loop because the flow has diverged: " + str(int(rec["nonfinite"])) + " cells are not finite at iteration " + str(It))
+                res.diverged = True
+                break
             if have_ghia:
-                reg_val = ghia.r2_value(u, Re, uLB)
+                reg_val = ghia.r2_from_column(solver.lines(out_dtype=np.float32)[0][0], Re, uLB) if on_device else ghia.r2_value(u, Re, uLB)
                 res.regression.append((It, float(reg_val)))
                 say("current regression value is " + str(reg_val))
             stats = solver.statistics() if averaging else None
@@ -225,7 +260,13 @@ def run_cavity(maxIt=3000000, Re=10000.0, RT="SRT", turb=1, xsize=32 * 5, ysize=
                 reg_mean = ghia.r2_value(stats["u"], Re, uLB)
                 res.regression_mean.append((It, float(reg_mean)))
                 say("current regression value of the time-mean is " + str(reg_mean))
-            say("current mean velocity value is " + str(np.mean(u) / uLB))
+            if on_device:
+                say("current mean velocity value is " + str((rec["sum_ux"] + rec["sum_uy"]) / (2.0 * xsize * ysize) / uLB))
+                loc1, loc2 = solver.locate_vortices(out_dtype=np.float32, first=rec)
+                res.vortices.append((It, loc1, loc2))
+                say("current vortex locations are " + str(loc1) + " and " + str(loc2))
+            else:
+                say("current mean velocity value is " + str(np.mean(u) / uLB))
             if SavePlot and have_ghia:
                 tau_mean = float(np.mean(solver.get_tau())) if (turb == 1 and hasattr(solver, "get_tau")) else None
                 _dashboard(os.path.join(OutputFolder, project + "_" + str(int(It / Pinterval)).zfill(5) + ".png"),
@@ -261,6 +302,8 @@ def run_cavity(maxIt=3000000, Re=10000.0, RT="SRT", turb=1, xsize=32 * 5, ysize=
         It += 1
     solver.sync()
     res.u, res.rho = solver.get_fields(out_dtype=np.float32)
+    if MonitorEvery is not None:
+        res.series = solver.monitor_series()
     if averaging:
         st = solver.statistics()
         res.u_mean, res.rho_mean, res.uu, res.vv, res.uv, res.samples = st["u"], st["rho"], st["uu"], st["vv"], st["uv"], st["samples"]
@@ -296,12 +339,18 @@ def main(argv=None):
     ap.add_argument("--vtk-correct", action="store_true", help="write .vtr point data (consistent file) instead of the reference's layout")
     ap.add_argument("--average-from", type=int, default=None, help="time statistics on the device from this iteration on")
     ap.add_argument("--average-every", type=int, default=100, help="iterations between two samples of the time statistics")
+    ap.add_argument("--monitor", choices=["host", "device"], default="host",
+                    help="device: the checks of an output iteration reduced on the GPU, no field download unless a file needs it")
+    ap.add_argument("--monitor-every", type=int, default=None, help="with --monitor device: a monitor record every this many iterations")
+    ap.add_argument("--probe", type=int, nargs=2, action="append", default=[], metavar=("X", "Y"),
+                    help="probe cell of the monitor series (repeatable; default: the lattice centre)")
     a = ap.parse_args(argv)
     r = run_cavity(maxIt=a.maxIt, Re=a.Re, RT=a.RT, turb=a.turb, xsize=a.xsize, ysize=a.ysize, uLB=a.uLB,
                    Pinterval=a.Pinterval, SavePlot=not a.no_plot, SaveVTK=a.vtk, project=a.project,
                    OutputFolder=a.OutputFolder, dtype=np.dtype(a.dtype), semantics=a.semantics, arith=a.arith,
                    convergence=a.convergence, vtk_correct=a.vtk_correct, BC="BB" if a.BC == "BB" else "EB-NEBB ",
-                   AverageFrom=a.average_from, AverageEvery=a.average_every)
+                   AverageFrom=a.average_from, AverageEvery=a.average_every, monitor=a.monitor, MonitorEvery=a.monitor_every,
+                   Probes=tuple(tuple(p) for p in a.probe))
     print("MLUPS : ", r.mlups)
     return 0
 

@@ -149,6 +149,28 @@ class LocalSlabs(_UnitDriver):
                 st.halo_import_rows(HIGH, nrows, up[i + 1].ctypes.data)
 
 
+    def monitor(self, window=None, exclude=(), probes=(), out_dtype=None):
+        """The monitor record of the WHOLE lattice (CavitySolver.monitor on every slab, combined by monitor.combine: sums and
+        nonfinite added in slab order, the maximum across the slabs, the minimum by (q, x, y), probes from the owning slab)."""
+        from .monitor import combine
+        return combine([st.monitor(window=window, exclude=exclude, probes=probes, out_dtype=out_dtype) for st in self.s])
+
+    def lines(self, x=None, y=None, out_dtype=None):
+        """(column, row) of the whole lattice (CavitySolver.lines): every slab fills its rows of the column, the row comes from the
+        slab that owns it."""
+        return _join_lines([st.lines(x=x, y=y, out_dtype=out_dtype) for st in self.s], [(st.y0, st.ny_local) for st in self.s])
+
+
+def _join_lines(parts, rows):
+    """Column and row of the whole lattice from the slabs' (column, row or None), in slab order."""
+    col = np.array(parts[0][0], copy=True)
+    row = parts[0][1]
+    for (c, r), (y0, n) in zip(parts[1:], rows[1:]):
+        col[..., y0:y0 + n] = c[..., y0:y0 + n]
+        row = r if r is not None else row
+    return col, row
+
+
 class HaloDriver(_UnitDriver):
     """One slab per process, halos moved with torch.distributed point-to-point ops.
 
@@ -174,6 +196,14 @@ class HaloDriver(_UnitDriver):
             self._agree(self._signature(), "launch plan (steps per launch, frame width, kernel path): create every slab with the same "
                                            "parameters and min_rows")
             self.exchange()
+
+    def monitor(self, **spec):
+        """The monitor record of the whole lattice, the same on every rank (global_monitor)."""
+        return global_monitor(self.st, self.world, self.group, **spec)
+
+    def lines(self, **kw):
+        """(column, row) of the whole lattice, the same on every rank (global_lines)."""
+        return global_lines(self.st, self.world, self.group, **kw)
 
     def _steppers(self):
         return [self.st]
@@ -240,6 +270,33 @@ class HaloDriver(_UnitDriver):
         send, recv = self._rows[nrows]
         self._move(send, recv, lambda side, ptr: self.st.halo_export_rows(side, nrows, ptr),
                    lambda side, ptr: self.st.halo_import_rows(side, nrows, ptr))
+
+
+def global_monitor(solver, world=1, group=None, **spec):
+    """The monitor record of the WHOLE lattice from slabs, one per rank: every rank reduces its own rows on its GPU
+    (CavitySolver.monitor(**spec), 272 bytes leave the device) and one all-gather of the records combines them on every rank in rank
+    order (monitor.combine), as global_mean_u combines the means."""
+    from .monitor import combine
+    rec = solver.monitor(**spec)
+    if world <= 1:
+        return combine([rec])
+    import torch.distributed as dist
+    box = [None] * world
+    dist.all_gather_object(box, rec, group=group)
+    return combine(box)
+
+
+def global_lines(solver, world=1, group=None, **kw):
+    """(column, row) of the WHOLE lattice from slabs, one per rank (CavitySolver.lines(**kw) on every rank, gathered in rank order)."""
+    part = solver.lines(**kw)
+    rows = (solver.y0, solver.ny_local)
+    if world <= 1:
+        return _join_lines([part], [rows])
+    import torch.distributed as dist
+    parts, allrows = [None] * world, [None] * world
+    dist.all_gather_object(parts, part, group=group)
+    dist.all_gather_object(allrows, rows, group=group)
+    return _join_lines(parts, allrows)
 
 
 def global_mean_u(solver, world=1, group=None, device="cpu"):

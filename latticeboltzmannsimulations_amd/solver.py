@@ -7,6 +7,7 @@ import ctypes
 import numpy as np
 
 from . import _lib as L
+from . import monitor as M
 
 _DT = {np.dtype(np.float32): L.LBM_F32, np.dtype(np.float64): L.LBM_F64}
 _COLL = {"SRT": L.LBM_SRT, "TRT": L.LBM_TRT, "MRT": L.LBM_MRT}
@@ -265,6 +266,93 @@ class CavitySolver:
         ux, uy = mu[..., 0, :, :], mu[..., 1, :, :]
         return dict(u=mu, rho=mrho, uu=sec[..., 0, :, :] - ux * ux, vv=sec[..., 1, :, :] - uy * uy, uv=sec[..., 2, :, :] - ux * uy,
                     samples=int(n.value))
+
+    # -- run monitor (lbm_monitor*, lbm_get_lines) ------------------------------------------------
+    def _out_code(self, out_dtype):
+        dt = self.dtype if out_dtype is None else np.dtype(out_dtype)
+        if dt not in _DT:
+            raise ValueError("out_dtype must be float32 or float64")
+        return dt, _DT[dt]
+
+    def monitor(self, window=None, exclude=(), probes=(), out_dtype=None):
+        """One pass over the lattice on the device (lbm_monitor): the record monitor.host_monitor(*get_fields(out_dtype=...)) would
+        give, as a dict -- step, nonfinite, sum_ux, sum_uy, sum_rho, sum_q, max_q, min_q, min_x, min_y and probe [len(probes), 3] --
+        without downloading a field.  window (x_lo, x_hi, y_lo, y_hi), half open, global rows (None: the whole lattice); exclude: up
+        to 4 boxes in the same form; probes: up to 8 cells (x, y).  A slab reports its own rows (slab.LocalSlabs.monitor combines
+        them); a batch returns arrays with a leading [B]."""
+        _, code = self._out_code(out_dtype)
+        spec = M.make_spec(self.nx, self.ny, code, window, exclude, probes)
+        rec = (L.lbm_monitor_record * self.batch)()
+        self._check(self.lib.lbm_monitor(self._h, ctypes.byref(spec), rec), "lbm_monitor")
+        out = M.records_to_dict(rec, (self.batch,), spec.nprobes)
+        return out if self._lead else {k: v[0] for k, v in out.items()}
+
+    def lines(self, x=None, y=None, out_dtype=None):
+        """(column, row): ux, uy, rho of column x, [3, Y], and of global row y, [3, X] -- the same bits as get_fields(out_dtype=...)
+        [.., x, :] and [.., :, y] (lbm_get_lines).  Defaults: the middle column and row of the reference's centre-line plots,
+        int(X / 2) and int(Y / 2).  A slab fills its own rows of the column and returns row = None when it does not own row y; a batch
+        carries a leading [B]."""
+        dt, code = self._out_code(out_dtype)
+        x = int(self.nx / 2) if x is None else int(x)
+        y = int(self.ny / 2) if y is None else int(y)
+        col = np.zeros(self._lead + (3, self.ny), dtype=dt)
+        row = np.zeros(self._lead + (3, self.nx), dtype=dt)
+        owns = self.y0 <= y < self.y0 + self.ny_local
+        self._check(self.lib.lbm_get_lines(self._h, x, y, col.ctypes.data, row.ctypes.data, code), "lbm_get_lines")
+        return col, (row if owns else None)
+
+    def locate_vortices(self, out_dtype=np.float32, first=None):
+        """ghia.locate_vortices(get_fields(out_dtype=...)[0], uLB) from two monitor passes: ((x1, y1), (x2, y2)); a batch returns a
+        list of such pairs.  first: a record monitor(window=monitor.vortex_window(X, Y)[1], out_dtype=out_dtype) has just returned for
+        the same step -- its minimum is the first vortex, and that pass is not repeated."""
+        off, win = M.vortex_window(self.nx, self.ny)
+        a = self.monitor(window=win, out_dtype=out_dtype) if first is None else first
+        if not self._lead:
+            loc1 = (int(a["min_x"]), int(a["min_y"]))
+            b = self.monitor(window=win, exclude=(M.vortex_box(loc1, off),), out_dtype=out_dtype)
+            return loc1, (int(b["min_x"]), int(b["min_y"]))
+        out = []
+        for i in range(self.batch):   # (the box differs from lattice to lattice: one pass per lattice, each reads its own entry)
+            loc1 = (int(a["min_x"][i]), int(a["min_y"][i]))
+            b = self.monitor(window=win, exclude=(M.vortex_box(loc1, off),), out_dtype=out_dtype)
+            out.append((loc1, (int(b["min_x"][i]), int(b["min_y"][i]))))
+        return out
+
+    def begin_monitor(self, every=0, capacity=1024, window=None, exclude=(), probes=(), out_dtype=None):
+        """Start (or restart) a series of monitor records on the device (lbm_monitor_begin) with room for `capacity` samples.
+        every > 0: step() samples by itself at steps_done + every, + 2 every, ... -- nothing returns to the host before
+        monitor_series(); every = 0: samples through sample_monitor() only.  Samples beyond the capacity are dropped and counted.
+        Not on a slab with every > 0."""
+        _, code = self._out_code(out_dtype)
+        spec = M.make_spec(self.nx, self.ny, code, window, exclude, probes)
+        self._check(self.lib.lbm_monitor_begin(self._h, ctypes.byref(spec), int(every), int(capacity)), "lbm_monitor_begin")
+        self._mon = (int(capacity), spec.nprobes)
+        return self
+
+    def sample_monitor(self):
+        """Append the record of the fields get_fields() would return now to the series (lbm_monitor_sample)."""
+        self._check(self.lib.lbm_monitor_sample(self._h), "lbm_monitor_sample")
+        return self
+
+    def monitor_series(self):
+        """The series so far (lbm_monitor_read): the keys of monitor() as arrays [count] (a batch: [count, B]; probe: [count(, B),
+        len(probes), 3]), plus count and dropped."""
+        _, nprobes = getattr(self, "_mon", (0, 0))
+        n, dropped = ctypes.c_longlong(0), ctypes.c_longlong(0)
+        self._check(self.lib.lbm_monitor_read(self._h, None, 0, ctypes.byref(n), ctypes.byref(dropped)), "lbm_monitor_read")   # the count
+        count = int(n.value)
+        rec = (L.lbm_monitor_record * (count * self.batch))()
+        if count:
+            self._check(self.lib.lbm_monitor_read(self._h, rec, count, ctypes.byref(n), ctypes.byref(dropped)), "lbm_monitor_read")
+        out = M.records_to_dict(rec, (count, self.batch), nprobes)
+        if not self._lead:
+            out = {k: v[:, 0] for k, v in out.items()}
+        out["count"], out["dropped"] = count, int(dropped.value)
+        return out
+
+    def end_monitor(self):
+        """Stop the series and free its device buffer (lbm_monitor_end)."""
+        self._check(self.lib.lbm_monitor_end(self._h), "lbm_monitor_end")
 
     # -- checkpoint / restart (the reference has neither; SURVEY 8f item 4) -------------------
     def save_checkpoint(self, path):
