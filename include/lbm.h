@@ -318,6 +318,71 @@ int lbm_monitor_read(lbm_ctx* c, lbm_monitor_record* records_out, int max_record
 int lbm_monitor_end(lbm_ctx* c);
 int lbm_get_lines(lbm_ctx* c, int x, int gy, void* col_out, void* row_out, int host_dtype);
 
+/* --- flow topology: stream function, vorticity, vortex extrema ------------------------------- */
+/* replaces: the streamline panel of an output iteration (MRT_GPU.py:808-817) and the comparison with the vortex table of Ghia, Ghia &
+ * Shin, for which the reference downloads u: the stream function psi and the vorticity omega of the sampled fields, and the extrema
+ * of psi inside up to eight windows, computed on the device; the record path moves no field across PCIe.  The SAMPLE is the monitor's:
+ * exactly the u[2][X][Y] that lbm_get_fields(host_dtype) would return now (same lagged lattice, gather + macros, wall overrides, whatever
+ * the kernel route), every value rounded to host_dtype, then converted to double.  Everything below is computed in double without
+ * contraction and is defined operation for operation, so the device equals the NumPy restatement (topology.host_topology,
+ * topology.host_stream_function) bit for bit.
+ *
+ * The index y runs away from the lid and u[1] > 0 points towards the lid (slot k pulls from y + cy_k), so (x, Y = -y) with (ux, uy) is a
+ * right-handed frame.
+ * Stream function, ux = d psi / dY, uy = -d psi / dx, integrated along x from the left wall, row by row (a row never needs another row):
+ *     t[0][y] = 0;  t[x][y] = 0.5 * (uy[x - 1][y] + uy[x][y])  for x >= 1
+ *   summed in a fixed two-level order: blocks of LBM_TOPOLOGY_BLOCK = 64 cells of x (the last may be shorter); inside a block within[x] is
+ *   the running sum of t taken strictly left to right, starting AS the block's first term; across blocks off[0] = 0,
+ *   off[b + 1] = off[b] + (the last within of block b), strictly in order;
+ *     psi[x][y] = -(off[block of x] + within[x]).
+ *   In NumPy:  for b in range(0, X, 64): c = np.cumsum(t[b:b+64], axis=0); psi[b:b+64] = -(off + c); off = off + c[-1]
+ * Vorticity, omega = d uy / dx - d ux / dY = dvdx + dudy (one addition):
+ *     dvdx[x] = 0.5 * (uy[x + 1] - uy[x - 1]) inside, uy[1] - uy[0] at x = 0, uy[X - 1] - uy[X - 2] at x = X - 1; dudy the same along the
+ *   index y with ux.  omega is counter-clockwise positive; Ghia's table lists -omega.
+ * Extrema of psi in a window [x_lo, x_hi) x [y_lo, y_hi): the minimum and the maximum over the cells whose psi is finite, each with its
+ *   cell and the omega of that cell (the same bits as the omega field).  Ties go to the smaller x, then the smaller y, for the minimum
+ *   and the maximum alike (an explicit order on (psi, x, y), as the monitor's minimum).  No candidate: psi = +inf (minimum) / -inf
+ *   (maximum), cell (-1, -1), omega = NaN.
+ * closure: the maximum of |psi[X - 1][y]| over the rows where it is finite (-inf if there is none) -- the net flux each row fails to
+ *   close.  A quality figure: the wet-node walls do not conserve mass, so it is not zero, and an extremum whose |psi| is not well above
+ *   it (the secondary corner eddies on a coarse lattice) is not resolved by this psi.
+ *
+ * lbm_topology_spec: struct_size, host_dtype (LBM_F32 | LBM_F64), nwindows <= LBM_TOPOLOGY_MAX_WINDOWS, window[i] = {x_lo, x_hi, y_lo,
+ *   y_hi} with 0 <= lo <= hi <= nx (ny); anything else is LBM_ERR_INVALID.  The windows are common to the lattices of a batch.
+ * lbm_topology_record (all doubles, one per lattice of the batch): step, closure, window[i].min / .max = {psi, x, y, omega}; windows
+ *   beyond nwindows: psi = omega = NaN, cell (-1, -1).
+ * lbm_topology: records_out[batch] of the fields lbm_get_fields would return now; synchronises.  LBM_ERR_STATE before the first step.
+ * lbm_get_stream_function: the fields whose extrema those are, float64, host layout: psi_out[B][X][Y], omega_out[B][X][Y]; either may be
+ *   NULL.  Synchronises; LBM_ERR_STATE before the first step.
+ * Both return LBM_ERR_STATE on a slab: omega needs rows of the neighbour, and a table over slabs needs a combining step on the host;
+ *   psi itself is row-local, which keeps that later step small.
+ * Device memory is allocated at the first call (never inside lbm_step) and freed by lbm_destroy: the record path takes X * Y / 64 doubles
+ *   of block sums plus one partial result per workgroup; the field path stages two double fields. */
+enum { LBM_TOPOLOGY_MAX_WINDOWS = 8, LBM_TOPOLOGY_BLOCK = 64 };
+typedef struct lbm_topology_spec {
+    int32_t struct_size;  /* = sizeof(lbm_topology_spec) */
+    int32_t host_dtype;
+    int32_t nwindows;
+    int32_t reserved;     /* 0 */
+    int32_t window[8][4];
+} lbm_topology_spec;
+typedef struct lbm_topology_extremum {
+    double psi;
+    double x;
+    double y;
+    double omega;
+} lbm_topology_extremum;
+typedef struct lbm_topology_record {
+    double step;
+    double closure;
+    struct {
+        lbm_topology_extremum min;
+        lbm_topology_extremum max;
+    } window[8];
+} lbm_topology_record;
+int lbm_topology(lbm_ctx* c, const lbm_topology_spec* spec, lbm_topology_record* records_out);
+int lbm_get_stream_function(lbm_ctx* c, double* psi_out, double* omega_out, int host_dtype);
+
 /* --- slab decomposition, externally driven exchange ---------------------------------- */
 /* No reference counterpart (the reference is single-GPU, MRT_GPU.py:29).  A step of a slab
  * is split so that a host-language driver can move halos with any transport:

@@ -57,13 +57,33 @@ class lbm_monitor_record(ctypes.Structure):
                                                "min_y")] + [("probe", (ctypes.c_double * 3) * LBM_MONITOR_MAX_PROBES)]
 
 
+LBM_TOPOLOGY_MAX_WINDOWS, LBM_TOPOLOGY_BLOCK = 8, 64
+
+
+class lbm_topology_spec(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_int32), ("host_dtype", ctypes.c_int32), ("nwindows", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("window", (ctypes.c_int32 * 4) * LBM_TOPOLOGY_MAX_WINDOWS)]
+
+
+class lbm_topology_extremum(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_double) for n in ("psi", "x", "y", "omega")]
+
+
+class _lbm_topology_window(ctypes.Structure):
+    _fields_ = [("min", lbm_topology_extremum), ("max", lbm_topology_extremum)]
+
+
+class lbm_topology_record(ctypes.Structure):
+    _fields_ = [("step", ctypes.c_double), ("closure", ctypes.c_double), ("window", _lbm_topology_window * LBM_TOPOLOGY_MAX_WINDOWS)]
+
+
 def sources():
     return [os.path.join(_CSRC, f) for f in sorted(os.listdir(_CSRC)) if f.endswith((".hip", ".hpp"))] + [HEADER]
 
 
 def build(force=False, verbose=False):
-    """Compile csrc/*.hip for gfx950 into liblbm_hip.so next to this file (in-tree).  The translation units (five of host code +
-    C ABI: lbm_hip / lbm_plan / lbm_launch / lbm_comm / lbm_monitor; the explicit instantiations of the tile and streaming kernels for float and
+    """Compile csrc/*.hip for gfx950 into liblbm_hip.so next to this file (in-tree).  The translation units (six of host code +
+    C ABI: lbm_hip / lbm_plan / lbm_launch / lbm_comm / lbm_monitor / lbm_topology; the explicit instantiations of the tile and streaming kernels for float and
     for double) are compiled in parallel into csrc/_obj/ and linked."""
     srcs = sources()
     if not force and os.path.exists(LIB_PATH) and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(s) for s in srcs):
@@ -123,6 +143,8 @@ SIGNATURES = {
                               ctypes.POINTER(ctypes.c_longlong)]),
     "lbm_monitor_end": (_i, [_vp]),
     "lbm_get_lines": (_i, [_vp, _i, _i, _vp, _vp, _i]),
+    "lbm_topology": (_i, [_vp, ctypes.POINTER(lbm_topology_spec), ctypes.POINTER(lbm_topology_record)]),
+    "lbm_get_stream_function": (_i, [_vp, _vp, _vp, _i]),
     "lbm_halo_elems": (_i, [_vp]),
     "lbm_halo_export": (_i, [_vp, _i, _vp]),
     "lbm_halo_import": (_i, [_vp, _i, _vp]),

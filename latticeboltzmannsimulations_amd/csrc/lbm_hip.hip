@@ -243,6 +243,7 @@ void lbm_destroy(lbm_ctx* c) {
     if (c->red_dev) (void)hipFree(c->red_dev);
     stats_free(c);
     monitor_free(c);
+    topology_free(c);
     if (c->stage) (void)hipFree(c->stage);
     if (c->relax_dev) (void)hipFree(c->relax_dev);
     if (c->ev_edges) (void)hipEventDestroy(c->ev_edges);

@@ -6,6 +6,7 @@
 //   lbm_launch.hip  kernel launches and the step loop (single / multi-step units, lag)   (C ABI: step*, time_steps)
 //   lbm_comm.hip    RCCL binding, halo exchanges, host-transported halos                 (C ABI: halo_*, comm_*)
 //   lbm_monitor.hip the run monitor and the line export (kernels: lbm_monitor.hpp)        (C ABI: monitor*, get_lines)
+//   lbm_topology.hip stream function, vorticity, extrema of psi (kernels: lbm_topology.hpp) (C ABI: topology, get_stream_function)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>  // types and prototypes only: RCCL is bound lazily with dlopen (see rccl_api)
@@ -113,6 +114,10 @@ struct lbm_ctx {
     long long mon_capacity = 0, mon_count = 0, mon_dropped = 0;
     int mon_every = 0;
     long long mon_next = 0;
+    // Flow topology (lbm_topology, lbm_get_stream_function; lbm_topology.hip): topo_part holds the block sums, the partial results and
+    // the records of the record path, topo_fields the staged psi and omega of the field path; each allocated on first use, kept.
+    double* topo_part = nullptr;
+    double* topo_fields = nullptr;
     ncclComm_t comm = nullptr;
     int nranks = 1, rank = 0;
     bool thin_valid = false;    // the one-row halo of lat[cur] has been exchanged (by the RCCL path, on s_comm)
@@ -355,6 +360,8 @@ int step_many(lbm_ctx* c, int nsteps);
 int monitor_series_sample(lbm_ctx* c, int which, long long step);
 void monitor_series_free(lbm_ctx* c);
 void monitor_free(lbm_ctx* c);
+// lbm_topology.hip
+void topology_free(lbm_ctx* c);
 // lbm_comm.hip
 rccl_api& rccl();
 void halo_range(const lbm_ctx* c, int k, int* lo, int* hi);

@@ -1,0 +1,178 @@
+// lbm_topology.hip -- liblbm_hip.so: the flow topology (lbm_topology, lbm_get_stream_function) of the C ABI declared in include/lbm.h:
+// stream function, vorticity and the extrema of psi in up to eight windows of the fields lbm_get_fields would return.  The kernels are
+// in lbm_topology.hpp.  gfx950 only.  DESIGN.md 2.8.
+#include "lbm_host.hpp"
+#include "lbm_topology.hpp"
+
+namespace lbmhost {
+
+static_assert(sizeof(lbm_topology_record) == (2 + 8 * LBM_TOPOLOGY_MAX_WINDOWS) * sizeof(double), "record layout");
+static_assert(sizeof(lbm_topology_spec) == (4 + 4 * LBM_TOPOLOGY_MAX_WINDOWS) * sizeof(int32_t), "spec layout");
+
+// "" or what is wrong with the spec for this context
+static std::string check_spec(const lbm_ctx* c, const lbm_topology_spec* s) {
+    if (!s) return "null spec";
+    if (s->struct_size != (int32_t)sizeof(lbm_topology_spec)) return "struct_size is not sizeof(lbm_topology_spec)";
+    if (s->host_dtype != LBM_F32 && s->host_dtype != LBM_F64) return "host_dtype must be LBM_F32 or LBM_F64";
+    if (s->nwindows < 0 || s->nwindows > LBM_TOPOLOGY_MAX_WINDOWS) return "nwindows must be 0 .. " + std::to_string((int)LBM_TOPOLOGY_MAX_WINDOWS);
+    const int nx = c->plan.geo.nx, NY = c->plan.geo.NY;
+    auto range = [](int lo, int hi, int n) { return 0 <= lo && lo <= hi && hi <= n; };
+    for (int i = 0; i < s->nwindows; ++i)
+        if (!range(s->window[i][0], s->window[i][1], nx) || !range(s->window[i][2], s->window[i][3], NY)) return "a window is not inside the lattice";
+    return "";
+}
+
+// The tiles of one lattice: blocks of x, tiles of rows.
+struct TopoGrid {
+    int nb, nty;
+    size_t nwg() const { return (size_t)nb * nty; }
+};
+static TopoGrid topo_grid(const lbm_ctx* c) {
+    return TopoGrid{(c->plan.geo.nx + TOPO_W - 1) / TOPO_W, (c->plan.geo.ny + TOPO_ROWS - 1) / TOPO_ROWS};
+}
+
+// Device memory of the record path, per lattice: the block sums / offsets [nb][ny], |psi| at the right wall [ny], the partial results
+// [MAX_WINDOWS][nwg][TOPO_PART], the record.  Allocated on first use, kept.
+struct TopoBuf {
+    double *total, *close, *partial;
+    lbm_topology_record* rec;
+};
+static TopoBuf topo_buf(const lbm_ctx* c) {
+    const TopoGrid g = topo_grid(c);
+    const size_t B = c->plan.batch, ny = c->plan.geo.ny;
+    TopoBuf b;
+    b.total = c->topo_part;
+    b.close = b.total + B * g.nb * ny;
+    b.partial = b.close + B * ny;
+    b.rec = (lbm_topology_record*)(b.partial + B * LBM_TOPOLOGY_MAX_WINDOWS * g.nwg() * TOPO_PART);
+    return b;
+}
+static int ensure_topo(lbm_ctx* c, bool fields) {
+    if (!c->topo_part) {
+        const TopoGrid g = topo_grid(c);
+        const size_t B = c->plan.batch, ny = c->plan.geo.ny;
+        const size_t bytes = B * (((size_t)g.nb * ny + ny + LBM_TOPOLOGY_MAX_WINDOWS * g.nwg() * TOPO_PART) * sizeof(double) + sizeof(lbm_topology_record));
+        hipError_t e = hipMalloc((void**)&c->topo_part, bytes);
+        if (e != hipSuccess) {
+            c->topo_part = nullptr;
+            return fail(c, LBM_ERR_NOMEM, std::string("hipMalloc(topology): ") + hipGetErrorString(e));
+        }
+    }
+    if (fields && !c->topo_fields) {   // psi, then omega: [batch][nx][ny] each
+        hipError_t e = hipMalloc((void**)&c->topo_fields, (size_t)2 * c->plan.batch * c->plan.geo.nx * c->plan.geo.ny * sizeof(double));
+        if (e != hipSuccess) {
+            c->topo_fields = nullptr;
+            return fail(c, LBM_ERR_NOMEM, std::string("hipMalloc(stream function): ") + hipGetErrorString(e));
+        }
+    }
+    return LBM_OK;
+}
+
+// psi of lat[which] on the compute stream: block sums, offsets, then the extrema of the spec's windows (and psi itself into psi_out when
+// that is not null); with_record: the final pass into the record buffer.
+static int topology_enqueue(lbm_ctx* c, int which, const TopoSpec& sp, long long step, double* psi_out, bool with_record) {
+    const TopoGrid g = topo_grid(c);
+    const TopoBuf b = topo_buf(c);
+    const dim3 tiles(g.nb, g.nty, c->plan.batch);
+    return launch_variant(c, [&](auto v) {
+        using VT = decltype(v);
+        using R = typename VT::R;
+        constexpr bool PROM = coll_is_prom(VT::COLL);
+        const R* src = (const R*)c->lat[which];
+        hipLaunchKernelGGL((k_topo_totals<R, VT::SEM, PROM>), tiles, dim3(BLK), 0, c->s_compute, src, c->plan.geo, c->raw[which], (R)c->p.uLB,
+                           c->plan.bstride, sp.host_f32, b.total);
+        hipLaunchKernelGGL(k_topo_offsets, dim3((c->plan.geo.ny + BLK - 1) / BLK, 1, c->plan.batch), dim3(BLK), 0, c->s_compute, b.total, g.nb,
+                           c->plan.geo.ny, b.close);
+        if (psi_out)
+            hipLaunchKernelGGL((k_topo_extrema<R, VT::SEM, PROM, true>), tiles, dim3(BLK), 0, c->s_compute, src, c->plan.geo, c->raw[which],
+                               (R)c->p.uLB, c->plan.bstride, sp, (const double*)b.total, b.partial, psi_out);
+        else
+            hipLaunchKernelGGL((k_topo_extrema<R, VT::SEM, PROM, false>), tiles, dim3(BLK), 0, c->s_compute, src, c->plan.geo, c->raw[which],
+                               (R)c->p.uLB, c->plan.bstride, sp, (const double*)b.total, b.partial, (double*)nullptr);
+        if (with_record)
+            hipLaunchKernelGGL((k_topo_final<R, VT::SEM, PROM>), dim3(LBM_TOPOLOGY_MAX_WINDOWS, c->plan.batch), dim3(BLK), 0, c->s_compute,
+                               (const double*)b.partial, (int)g.nwg(), (const double*)b.close, src, c->plan.geo, c->raw[which], (R)c->p.uLB,
+                               c->plan.bstride, sp, (double)step, (double*)b.rec);
+    });
+}
+
+void topology_free(lbm_ctx* c) {
+    if (c->topo_part) (void)hipFree(c->topo_part);
+    if (c->topo_fields) (void)hipFree(c->topo_fields);
+    c->topo_part = c->topo_fields = nullptr;
+}
+}  // namespace lbmhost
+
+using namespace lbmhost;
+
+extern "C" {
+
+int lbm_topology(lbm_ctx* c, const lbm_topology_spec* spec, lbm_topology_record* records_out) {
+    if (!c || !spec || !records_out) return fail(c, LBM_ERR_INVALID, "lbm_topology: bad argument");
+    const std::string bad = check_spec(c, spec);
+    if (!bad.empty()) return fail(c, LBM_ERR_INVALID, "lbm_topology: " + bad);
+    if (is_slab(c->plan)) return fail(c, LBM_ERR_STATE, "lbm_topology: not on a slab (omega needs rows of the neighbour)");
+    if (c->nsteps == 0) return fail(c, LBM_ERR_STATE, "lbm_topology: no step yet (the fields of an iteration exist after it)");
+    HIP_TRY(c, hipSetDevice(c->p.device));
+    int rc = sync_all(c);
+    if (rc) return rc;
+    rc = ensure_topo(c, false);
+    if (rc) return rc;
+    int which = 0;
+    rc = prev_lattice(c, &which);   // (what lbm_get_fields exports: the lattice the last iteration started from)
+    if (rc) return rc;
+    TopoSpec sp{};
+    sp.host_f32 = spec->host_dtype == LBM_F32;
+    sp.nwindows = spec->nwindows;
+    for (int i = 0; i < spec->nwindows; ++i)
+        for (int j = 0; j < 4; ++j) sp.win[i][j] = spec->window[i][j];
+    rc = topology_enqueue(c, which, sp, c->nsteps, nullptr, true);
+    if (rc) return rc;
+    HIP_TRY(c, hipMemcpyAsync(records_out, topo_buf(c).rec, (size_t)c->plan.batch * sizeof(lbm_topology_record), hipMemcpyDeviceToHost, c->s_compute));
+    HIP_TRY(c, hipStreamSynchronize(c->s_compute));
+    return LBM_OK;
+}
+
+int lbm_get_stream_function(lbm_ctx* c, double* psi_out, double* omega_out, int host_dtype) {
+    if (!c || (host_dtype != LBM_F32 && host_dtype != LBM_F64)) return fail(c, LBM_ERR_INVALID, "lbm_get_stream_function: bad argument");
+    if (is_slab(c->plan)) return fail(c, LBM_ERR_STATE, "lbm_get_stream_function: not on a slab (omega needs rows of the neighbour)");
+    if (c->nsteps == 0) return fail(c, LBM_ERR_STATE, "lbm_get_stream_function: no step yet (the fields of an iteration exist after it)");
+    if (!psi_out && !omega_out) return LBM_OK;
+    HIP_TRY(c, hipSetDevice(c->p.device));
+    int rc = sync_all(c);
+    if (rc) return rc;
+    rc = ensure_topo(c, true);
+    if (rc) return rc;
+    const int nx = c->plan.geo.nx, ny = c->plan.geo.ny, B = c->plan.batch;
+    const size_t n = (size_t)nx * ny;
+    int which = 0;
+    rc = prev_lattice(c, &which);
+    if (rc) return rc;
+    double* psi_dev = c->topo_fields;
+    double* omega_dev = c->topo_fields + (size_t)B * n;
+    if (psi_out) {
+        TopoSpec sp{};
+        sp.host_f32 = host_dtype == LBM_F32;
+        rc = topology_enqueue(c, which, sp, c->nsteps, psi_dev, false);
+        if (rc) return rc;
+        HIP_TRY(c, hipMemcpyAsync(psi_out, psi_dev, (size_t)B * n * sizeof(double), hipMemcpyDeviceToHost, c->s_compute));
+    }
+    if (omega_out) {
+        // u as the field export stages it (host layout, the lattice's type), then omega from it, one thread per cell
+        rc = ensure_stage(c, (size_t)12 * n * c->plan.es * B);
+        if (rc) return rc;
+        rc = launch_variant(c, [&](auto v) {
+            using VT = decltype(v);
+            using R = typename VT::R;
+            hipLaunchKernelGGL((k_export_macro<R, VT::SEM, coll_is_prom(VT::COLL)>), dim3((nx + trx<R>() - 1) / trx<R>(), (ny + 31) / 32, B), dim3(BLK), 0,
+                               c->s_compute, (const R*)c->lat[which], c->plan.geo, c->raw[which], (R)c->p.uLB, (R*)c->stage, c->plan.bstride);
+            hipLaunchKernelGGL((k_topo_omega<R>), dim3((unsigned)((n + BLK - 1) / BLK), 1, B), dim3(BLK), 0, c->s_compute, (const R*)c->stage, nx, ny,
+                               (int)(host_dtype == LBM_F32), omega_dev);
+        });
+        if (rc) return rc;
+        HIP_TRY(c, hipMemcpyAsync(omega_out, omega_dev, (size_t)B * n * sizeof(double), hipMemcpyDeviceToHost, c->s_compute));
+    }
+    HIP_TRY(c, hipStreamSynchronize(c->s_compute));
+    return LBM_OK;
+}
+}  // extern "C"

@@ -211,6 +211,25 @@ def vortex_position(loc, X, Y):
     return loc[0] / float(X), (Y - 1 - loc[1]) / float(Y)
 
 
+def vortex_table_errors(table, Re, X, Y):
+    """A vortex table (topology.vortex_table: name -> dict(x, y, ...) or None; names Primary, Top, BL1, BR1 = rows 0 .. 3 of
+    VORTEX_GHIA) against Ghia's for this Re, in the reference's plot coordinates (vortex_position): dict name ->
+    dict(error=(dx, dy) or None, listed=bool).  listed: Ghia's table has the vortex at this Re (a (0, 0) entry means it does not);
+    error is None unless the vortex was found and is listed."""
+    j = _col(Re)
+    out = {}
+    for row, name in enumerate(("Primary", "Top", "BL1", "BR1")):
+        gx, gy = VORTEX_GHIA[row, j], VORTEX_GHIA[7 + row, j]
+        listed = bool(gx != 0 or gy != 0)
+        e = table.get(name)
+        err = None
+        if e is not None and listed:
+            px, py = vortex_position((e["x"], e["y"]), X, Y)
+            err = (float(px - gx), float(py - gy))
+        out[name] = dict(error=err, listed=listed)
+    return out
+
+
 def nearest_vortex_error(loc, Re, X, Y):
     """Distance from a located node (locate_vortices returns the two smallest minima of |u|^2 -- WHICH vortices they are depends on the
     flow: at Re >= 400 the first is the bottom-left corner eddy, not the primary vortex) to the nearest entry of Ghia's vortex table

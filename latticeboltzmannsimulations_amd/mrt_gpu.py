@@ -48,6 +48,7 @@ class CavityResult:
         self.diverged = False       # a check found cells that are not finite; the run stopped there
         self.vortices = []          # (iteration, (x1, y1), (x2, y2)) at every output iteration
         self.series = None          # run_cavity(MonitorEvery=k): CavitySolver.monitor_series() of the whole run
+        self.vortex_tables = []     # run_cavity(vortex_table=True): (iteration, CavitySolver.vortex_table()) at every output iteration
 
 
 CS2_EFFECTIVE, CS_BULK = 0.025, 0.16     # MRT_GPU.py:350,374-376: Van Driest damping is overwritten by Cs2 = 0.025
@@ -122,11 +123,31 @@ def _dashboard(path, u, rho, It, hist, Re, RT, regime, BC, xsize, ysize, uLB, re
     pyplot.close(f)
 
 
+def _vortex_lines(table, Re, xsize, ysize, uLB):
+    """The printed form of a vortex table (topology.vortex_table): per name the position in the reference's plot coordinates,
+    psi / (uLB * xsize) and -omega * xsize / uLB (the sign Ghia tabulates), beside Ghia's position where his table lists the vortex
+    (Re=None: no column for this Reynolds number)."""
+    errs = ghia.vortex_table_errors(table, Re, xsize, ysize) if Re is not None else {}
+    j = ghia.RE_COLUMNS.index(int(round(float(Re)))) if Re is not None else None
+    lines = ["vortex table (x, y from the bottom-left corner; psi / (uLB N); -omega N / uLB; Ghia):"]
+    for row, name in enumerate(("Primary", "Top", "BL1", "BR1")):
+        e = table.get(name)
+        listed = errs.get(name, {}).get("listed", False)
+        g = "(%.4f, %.4f)" % (ghia.VORTEX_GHIA[row, j], ghia.VORTEX_GHIA[7 + row, j]) if listed else "not listed"
+        if e is None:
+            lines.append("  %-8s absent; Ghia %s" % (name, g))
+        else:
+            px, py = ghia.vortex_position((e["x"], e["y"]), xsize, ysize)
+            lines.append("  %-8s (%.4f, %.4f)  psi %.6g  -omega %.6g; Ghia %s" % (name, px, py, e["psi"] / (uLB * xsize),
+                                                                                -e["omega"] * xsize / uLB, g))
+    return lines
+
+
 def run_cavity(maxIt=3000000, Re=10000.0, RT="SRT", turb=1, xsize=32 * 5, ysize=32 * 5, uLB=0.08,
                Pinterval=3000, SavePlot=True, SaveVTK=False, project="ldc", OutputFolder="./output",
                dtype=np.float32, semantics="mrt_gpu", device=0, quiet=False, solver_factory=None, arith="strict",
                convergence="host", vtk_correct=False, BC="EB-NEBB ", AverageFrom=None, AverageEvery=100, monitor="host",
-               MonitorEvery=None, Probes=()):
+               MonitorEvery=None, Probes=(), vortex_table=False):
     """Run the lid-driven cavity like MRT_GPU.py does; returns a :class:`CavityResult`.
 
     Argument names and defaults are the module constants of MRT_GPU.py:38-58.
@@ -150,7 +171,10 @@ def run_cavity(maxIt=3000000, Re=10000.0, RT="SRT", turb=1, xsize=32 * 5, ysize=
     are downloaded only for the files SavePlot / SaveVTK ask for.  A record with cells that are not finite stops the run:
     result.diverged, and the iteration is printed.  MonitorEvery=k (with monitor='device'): a series of monitor records on the device
     from iteration 0 on, one every k iterations, with the cells `Probes` ((x, y), ...; default: the lattice centre) -- returned as
-    result.series, nothing crosses PCIe before the run ends."""
+    result.series, nothing crosses PCIe before the run ends.
+    vortex_table=True: every Pinterval is an output iteration, and each one appends (iteration, CavitySolver.vortex_table()) to
+    result.vortex_tables -- Ghia's named vortices (Primary, Top, BL1, BR1) from the extrema of the stream function, reduced on the device --
+    and prints the table beside Ghia's.  With either monitor mode; False (default): nothing changes."""
     if monitor not in ("host", "device"):
         raise ValueError("monitor must be 'host' or 'device'")
     on_device = monitor == "device"
@@ -208,7 +232,7 @@ def run_cavity(maxIt=3000000, Re=10000.0, RT="SRT", turb=1, xsize=32 * 5, ysize=
     count = 0
     done = 0          # iterations performed
     have_ghia = int(round(float(Re))) in ghia.RE_COLUMNS
-    outputs = SaveVTK or SavePlot or on_device
+    outputs = SaveVTK or SavePlot or on_device or bool(vortex_table)
     averaging = False
     if MonitorEvery is not None:
         probes = tuple(Probes) if len(Probes) else ((int(xsize / 2), int(ysize / 2)),)
@@ -267,6 +291,11 @@ def run_cavity(maxIt=3000000, Re=10000.0, RT="SRT", turb=1, xsize=32 * 5, ysize=
                 say("current vortex locations are " + str(loc1) + " and " + str(loc2))
             else:
                 say("current mean velocity value is " + str(np.mean(u) / uLB))
+            if vortex_table:
+                table = solver.vortex_table(out_dtype=np.float32)
+                res.vortex_tables.append((It, table))
+                for line in _vortex_lines(table, Re if have_ghia else None, xsize, ysize, uLB):
+                    say(line)
             if SavePlot and have_ghia:
                 tau_mean = float(np.mean(solver.get_tau())) if (turb == 1 and hasattr(solver, "get_tau")) else None
                 _dashboard(os.path.join(OutputFolder, project + "_" + str(int(It / Pinterval)).zfill(5) + ".png"),
@@ -344,13 +373,15 @@ def main(argv=None):
     ap.add_argument("--monitor-every", type=int, default=None, help="with --monitor device: a monitor record every this many iterations")
     ap.add_argument("--probe", type=int, nargs=2, action="append", default=[], metavar=("X", "Y"),
                     help="probe cell of the monitor series (repeatable; default: the lattice centre)")
+    ap.add_argument("--vortex-table", action="store_true",
+                    help="at every output iteration: Ghia's named vortices from the stream function's extrema, reduced on the device")
     a = ap.parse_args(argv)
     r = run_cavity(maxIt=a.maxIt, Re=a.Re, RT=a.RT, turb=a.turb, xsize=a.xsize, ysize=a.ysize, uLB=a.uLB,
                    Pinterval=a.Pinterval, SavePlot=not a.no_plot, SaveVTK=a.vtk, project=a.project,
                    OutputFolder=a.OutputFolder, dtype=np.dtype(a.dtype), semantics=a.semantics, arith=a.arith,
                    convergence=a.convergence, vtk_correct=a.vtk_correct, BC="BB" if a.BC == "BB" else "EB-NEBB ",
                    AverageFrom=a.average_from, AverageEvery=a.average_every, monitor=a.monitor, MonitorEvery=a.monitor_every,
-                   Probes=tuple(tuple(p) for p in a.probe))
+                   Probes=tuple(tuple(p) for p in a.probe), vortex_table=a.vortex_table)
     print("MLUPS : ", r.mlups)
     return 0
 

@@ -8,6 +8,7 @@ import numpy as np
 
 from . import _lib as L
 from . import monitor as M
+from . import topology as T
 
 _DT = {np.dtype(np.float32): L.LBM_F32, np.dtype(np.float64): L.LBM_F64}
 _COLL = {"SRT": L.LBM_SRT, "TRT": L.LBM_TRT, "MRT": L.LBM_MRT}
@@ -353,6 +354,37 @@ class CavitySolver:
     def end_monitor(self):
         """Stop the series and free its device buffer (lbm_monitor_end)."""
         self._check(self.lib.lbm_monitor_end(self._h), "lbm_monitor_end")
+
+    # -- flow topology (lbm_topology, lbm_get_stream_function) -------------------------------------
+    def topology(self, windows=(), out_dtype=None):
+        """The extrema of the stream function inside up to 8 windows (x_lo, x_hi, y_lo, y_hi), reduced on the device (lbm_topology):
+        the record topology.host_topology(get_fields(out_dtype=...)[0], uLB, windows) would give, every bit -- step, closure and per
+        window dict(min=..., max=...), each extremum a dict(psi, x, y, omega) -- without downloading a field.  omega is counter-clockwise
+        positive (Ghia's table lists -omega).  A batch returns a list of records (the windows are common); not on a slab."""
+        _, code = self._out_code(out_dtype)
+        spec = T.make_spec(self.nx, self.ny, code, windows)
+        rec = (L.lbm_topology_record * self.batch)()
+        self._check(self.lib.lbm_topology(self._h, ctypes.byref(spec), rec), "lbm_topology")
+        out = T.records_to_dict(rec, spec.nwindows)
+        return out if self._lead else out[0]
+
+    def stream_function(self, out_dtype=None):
+        """(psi, omega), float64 [X, Y], of the fields get_fields(out_dtype=...) would return, computed on the device
+        (lbm_get_stream_function): topology.host_stream_function of those fields, every bit; the extrema topology() reports are
+        extrema of this psi.  A batch carries a leading [B]; not on a slab."""
+        _, code = self._out_code(out_dtype)
+        psi = np.zeros(self._lead + (self.nx, self.ny))
+        omega = np.zeros(self._lead + (self.nx, self.ny))
+        self._check(self.lib.lbm_get_stream_function(self._h, psi.ctypes.data, omega.ctypes.data, code), "lbm_get_stream_function")
+        return psi, omega
+
+    def vortex_table(self, out_dtype=np.float32):
+        """Ghia's named vortices from one device record of four windows (topology.vortex_windows, topology.vortex_table): dict
+        'Primary' | 'Top' | 'BL1' | 'BR1' -> dict(x, y, psi, omega), or None where the vortex is absent.  A batch returns a list."""
+        rec = self.topology(T.vortex_windows(self.nx, self.ny), out_dtype=out_dtype)
+        if self._lead:
+            return [T.vortex_table(r, self.nx, self.ny) for r in rec]
+        return T.vortex_table(rec, self.nx, self.ny)
 
     # -- checkpoint / restart (the reference has neither; SURVEY 8f item 4) -------------------
     def save_checkpoint(self, path):

@@ -1,0 +1,225 @@
+"""CPU tests of the flow topology's host statement (topology.host_stream_function, host_topology, vortex_table), of
+ghia.vortex_table_errors, of the spec validation and of the front end's vortex_table option: exact values on fields whose stream
+function and vorticity are known in closed form, the blocked order of the prefix sum against an explicit loop, the table's
+composition rules on synthetic fields, and one physics pin on the fp64 C oracle."""
+import ctypes
+
+import numpy as np
+import pytest
+
+from latticeboltzmannsimulations_amd import ghia, relaxation
+from latticeboltzmannsimulations_amd import topology as T
+from latticeboltzmannsimulations_amd.mrt_gpu import run_cavity
+from oracle.lbm_ref import CavityOracleC
+
+
+def _field_from_psi(psi):
+    """u[2, X, Y] whose host stream function is exactly `psi` when psi[0] = 0 and every entry is a small dyadic number:
+    uy[0] = 0, uy[x] = 2 (psi[x - 1] - psi[x]) - uy[x - 1], so that t[x] = 0.5 (uy[x - 1] + uy[x]) = psi[x - 1] - psi[x] exactly."""
+    X, Y = psi.shape
+    u = np.zeros((2, X, Y))
+    for x in range(1, X):
+        u[1, x] = 2.0 * (psi[x - 1] - psi[x]) - u[1, x - 1]
+    return u
+
+
+def test_psi_of_a_linear_uy_is_exact_across_three_full_blocks_and_a_short_one():
+    X, Y = 200, 6
+    a = 2.0 ** -np.arange(3, 3 + Y)
+    u = np.zeros((2, X, Y))
+    u[1] = np.arange(X)[:, None] * a[None, :]
+    psi, _ = T.host_stream_function(u)
+    assert T.BLOCK == 64 and X % T.BLOCK == 8
+    assert np.array_equal(psi, -a[None, :] * (np.arange(X)[:, None] ** 2) / 2.0)
+    assert np.array_equal(T.host_stream_function(u.astype(np.float32))[0], psi)      # (exact in float32 too)
+
+
+@pytest.mark.parametrize("X,Y", [(200, 7), (64, 5)])
+def test_the_blocked_order_of_the_prefix_sum_is_the_contract(X, Y):
+    rng = np.random.default_rng(X)
+    u = rng.standard_normal((2, X, Y))
+    want = np.empty((X, Y))
+    for y in range(Y):
+        off = 0.0
+        for b in range(0, X, 64):
+            acc = None
+            for x in range(b, min(b + 64, X)):
+                t = 0.0 if x == 0 else 0.5 * (u[1, x - 1, y] + u[1, x, y])
+                acc = t if acc is None else acc + t
+                want[x, y] = -(off + acc)
+            off = off + acc
+    psi, _ = T.host_stream_function(u)
+    assert np.array_equal(psi, want)
+    if X > 64:   # and it is not the plain running sum
+        plain = -np.cumsum(np.concatenate([np.zeros((1, Y)), 0.5 * (u[1, :-1] + u[1, 1:])]), axis=0)
+        assert not np.array_equal(psi, plain)
+
+
+def test_omega_of_a_rigid_rotation_is_exact_borders_included():
+    X, Y, Om = 37, 21, 2.0 ** -7
+    u = np.zeros((2, X, Y))
+    u[0] = Om * np.arange(Y)[None, :]
+    u[1] = Om * np.arange(X)[:, None]
+    _, omega = T.host_stream_function(u)
+    assert np.array_equal(omega, np.full((X, Y), 2 * Om))
+
+
+def test_extrema_ties_nan_cells_and_empty_windows():
+    X, Y = 70, 9
+    psi = np.zeros((X, Y))
+    psi[10:13, 3:5] = -0.5          # six cells tie for the minimum
+    psi[66, 2] = psi[66, 1] = psi[20, 7] = 0.25     # three tie for the maximum, in two blocks
+    u = _field_from_psi(psi)
+    got_psi, omega = T.host_stream_function(u)
+    assert np.array_equal(got_psi, psi)
+    rec = T.host_topology(u, 0.08, [(0, X, 0, Y), (11, 13, 4, 9), (5, 5, 0, Y), (0, X, 0, 0)], step=3)
+    w = rec["window"]
+    assert rec["step"] == 3 and rec["closure"] == 0.0
+    assert (w[0]["min"]["psi"], w[0]["min"]["x"], w[0]["min"]["y"]) == (-0.5, 10, 3)
+    assert (w[0]["max"]["psi"], w[0]["max"]["x"], w[0]["max"]["y"]) == (0.25, 20, 7)
+    assert w[0]["min"]["omega"] == omega[10, 3] and w[0]["max"]["omega"] == omega[20, 7]
+    assert (w[1]["min"]["x"], w[1]["min"]["y"]) == (11, 4) and (w[1]["max"]["psi"], w[1]["max"]["x"], w[1]["max"]["y"]) == (0.0, 11, 5)
+    for e in (w[2], w[3]):
+        assert (e["min"]["psi"], e["min"]["x"], e["min"]["y"]) == (np.inf, -1, -1) and np.isnan(e["min"]["omega"])
+        assert (e["max"]["psi"], e["max"]["x"], e["max"]["y"]) == (-np.inf, -1, -1) and np.isnan(e["max"]["omega"])
+    # a NaN in uy poisons psi from that cell to the right wall of its row: those cells are skipped, the others are not
+    u[1, 9, 3] = np.nan
+    rec = T.host_topology(u, 0.08, [(0, X, 0, Y), (9, X, 3, 4)])
+    w = rec["window"]
+    assert (w[0]["min"]["psi"], w[0]["min"]["x"], w[0]["min"]["y"]) == (-0.5, 10, 4)
+    assert (w[1]["min"]["x"], w[1]["max"]["x"]) == (-1, -1) and rec["closure"] == 0.0
+    u[1, 9, :] = np.nan
+    assert T.host_topology(u, 0.08, [])["closure"] == -np.inf
+
+
+def _table_field(X, Y, primary, corner=None, corner_psi=0.0):
+    psi = np.zeros((X, Y))
+    psi[primary] = -1.0
+    if corner is not None:
+        psi[corner] = corner_psi
+    return _field_from_psi(psi)
+
+
+def test_vortex_table_composition_rules():
+    X, Y = 40, 32
+    wins = T.vortex_windows(X, Y)
+    assert wins == ((1, 39, 1, 31), (0, 20, 0, 16), (0, 20, 16, 32), (20, 40, 16, 32))
+    # primary negative, a positive extremum inside the bottom-left window, nothing elsewhere
+    t = T.host_vortex_table(_table_field(X, Y, (22, 14), (5, 27), 2.0 ** -6), 0.08)
+    assert t["Primary"]["x"] == 22 and t["Primary"]["y"] == 14 and t["Primary"]["psi"] == -1.0
+    assert (t["BL1"]["x"], t["BL1"]["y"], t["BL1"]["psi"]) == (5, 27, 2.0 ** -6)
+    assert t["Top"] is None and t["BR1"] is None              # the opposite-sign extremum there is 0: rejected
+    # an extremum on the window's border is a slope, not a centre: rejected (x = 19 is the last column of BL1's window, y = 16 its first row)
+    for cell in ((19, 27), (5, 16), (5, 31), (19, 16)):
+        assert T.host_vortex_table(_table_field(X, Y, (22, 14), cell, 2.0 ** -6), 0.08)["BL1"] is None, cell
+    assert T.host_vortex_table(_table_field(X, Y, (22, 14), (20, 27), 2.0 ** -6), 0.08)["BR1"] is None
+    assert T.host_vortex_table(_table_field(X, Y, (22, 14), (21, 27), 2.0 ** -6), 0.08)["BR1"]["x"] == 21
+    # a corner extremum of the primary's own sign is not a corner eddy
+    assert T.host_vortex_table(_table_field(X, Y, (22, 14), (5, 27), -2.0 ** -6), 0.08)["BL1"] is None
+    # the primary obeys the border rule, and a positive primary turns the signs round
+    assert T.host_vortex_table(_table_field(X, Y, (1, 14)), 0.08)["Primary"] is None
+    u = _table_field(X, Y, (22, 14), (30, 20), 2.0 ** -6)
+    u[1] = -u[1]
+    t = T.host_vortex_table(u, 0.08)
+    assert t["Primary"]["psi"] == 1.0 and (t["BR1"]["x"], t["BR1"]["y"], t["BR1"]["psi"]) == (30, 20, -2.0 ** -6)
+    # ties: the smaller x, then the smaller y
+    psi = np.zeros((X, Y))
+    psi[22:24, 14:16] = -1.0
+    t = T.host_vortex_table(_field_from_psi(psi), 0.08)
+    assert (t["Primary"]["x"], t["Primary"]["y"]) == (22, 14)
+    # a field at rest has no vortex at all
+    assert T.host_vortex_table(np.zeros((2, X, Y)), 0.08) == dict(Primary=None, Top=None, BL1=None, BR1=None)
+
+
+def test_vortex_table_errors_against_hand_made_tables():
+    X = Y = 128
+    e = dict(psi=-1.0, omega=-1.0)
+    table = dict(Primary=dict(x=68, y=55, **e), Top=None, BL1=dict(x=11, y=118, **e), BR1=dict(x=110, y=113, **e))
+    got = ghia.vortex_table_errors(table, 1000, X, Y)
+    assert got["Top"] == dict(error=None, listed=False)          # Ghia lists no Top vortex at Re 1000
+    assert all(got[k]["listed"] for k in ("Primary", "BL1", "BR1"))
+    want = dict(Primary=(68 / 128 - 0.5313, 72 / 128 - 0.5625), BL1=(11 / 128 - 0.0859, 9 / 128 - 0.0781), BR1=(110 / 128 - 0.8594, 14 / 128 - 0.1094))
+    for k, v in want.items():
+        assert got[k]["error"] == pytest.approx(v, abs=1e-15) and max(abs(c) for c in got[k]["error"]) < 0.01
+    # listed but not found: no error; found but not listed: no error either, and the flag says why
+    got = ghia.vortex_table_errors(dict(Primary=None, Top=dict(x=3, y=3, **e), BL1=None, BR1=None), 3200, X, Y)
+    assert got["Primary"] == dict(error=None, listed=True) and got["Top"]["listed"] and got["Top"]["error"] is not None
+    got = ghia.vortex_table_errors(dict(Primary=None, Top=dict(x=3, y=3, **e), BL1=None, BR1=None), 100, X, Y)
+    assert got["Top"] == dict(error=None, listed=False) and got["BR1"] == dict(error=None, listed=True)
+    with pytest.raises(KeyError):
+        ghia.vortex_table_errors(table, 123, X, Y)
+
+
+def test_spec_validation():
+    s = T.make_spec(64, 48, 0, [(0, 64, 0, 48), (3, 3, 5, 5)])
+    assert s.struct_size == ctypes.sizeof(T.lbm_topology_spec) == 16 + 8 * 16 and s.nwindows == 2 and list(s.window[1]) == [3, 3, 5, 5]
+    assert ctypes.sizeof(T.lbm_topology_record) == 8 * T.RECORD_DOUBLES
+    for bad in ([(0, 65, 0, 48)], [(-1, 3, 0, 1)], [(5, 4, 0, 1)], [(0, 1, 0, 49)], [(0, 1, 2)], [(0, 1, 0, 1)] * 9):
+        with pytest.raises(ValueError):
+            T.make_spec(64, 48, 0, bad)
+    rec = (T.lbm_topology_record * 2)()
+    rec[1].step, rec[1].closure = 7.0, 0.5
+    rec[1].window[1].max.psi, rec[1].window[1].max.x, rec[1].window[1].max.y, rec[1].window[1].max.omega = 0.25, 4.0, 5.0, -1.0
+    out = T.records_to_dict(rec, 2)
+    assert out[1]["step"] == 7 and out[1]["closure"] == 0.5 and out[1]["window"][1]["max"] == dict(psi=0.25, x=4, y=5, omega=-1.0)
+    assert len(out) == 2 and len(out[0]["window"]) == 2
+
+
+@pytest.fixture(scope="module")
+def oracle_re100():
+    o = CavityOracleC(64, 64, 100.0, semantics="mrt_gpu", collision="MRT", dtype=np.float64)
+    o.step(12000)
+    return np.array(o.u, copy=True)
+
+
+def test_physics_pin_primary_vortex_of_the_fp64_oracle_at_re_100(oracle_re100):
+    """64 x 64, Re 100, MRT, 12 000 steps: the primary vortex within two cells (2 / 64) of Ghia's entry in both coordinates, no Top
+    vortex, psi < 0 there.  The corner eddies are not asserted: at this size their psi is a hundredth of the closure."""
+    u = oracle_re100
+    table = T.host_vortex_table(u, 0.08)
+    err = ghia.vortex_table_errors(table, 100, 64, 64)
+    print("table", table, "errors", err, "closure / (uLB N)", T.host_topology(u, 0.08, [])["closure"] / (0.08 * 64))
+    assert table["Primary"] is not None and table["Top"] is None
+    assert table["Primary"]["psi"] < 0
+    dx, dy = err["Primary"]["error"]
+    assert abs(dx) <= 2 / 64 and abs(dy) <= 2 / 64
+
+
+class OracleStepper:
+    """Same surface as CavitySolver as far as run_cavity(vortex_table=True) uses it; the table through the host statement."""
+
+    def __init__(self, xsize, ysize, Re, RT="MRT", uLB=0.08, semantics="mrt_gpu", dtype=np.float32, turb=0, device=0):
+        self.o = CavityOracleC(xsize, ysize, Re, uLB=uLB, semantics=semantics, collision=RT, dtype=dtype, turb=turb)
+        self.relax = relaxation(Re, ysize, uLB)
+        self.uLB = uLB
+
+    def step(self, n=1):
+        self.o.step(n)
+        return self
+
+    def sync(self):
+        pass
+
+    def get_fields(self, out_dtype=None, **kw):
+        return self.o.u.astype(out_dtype), self.o.rho.astype(out_dtype)
+
+    def vortex_table(self, out_dtype=np.float32):
+        return T.host_vortex_table(self.o.u.astype(out_dtype), self.uLB)
+
+    def close(self):
+        pass
+
+
+def test_front_end_fills_the_vortex_tables(tmp_path, monkeypatch, capsys):
+    monkeypatch.chdir(tmp_path)
+    kw = dict(maxIt=601, Re=100.0, RT="MRT", turb=0, xsize=32, ysize=32, Pinterval=300, SavePlot=False, solver_factory=OracleStepper)
+    r = run_cavity(vortex_table=True, **kw)
+    assert [it for it, _ in r.vortex_tables] == [0, 300, 600] and [it for it, _ in r.regression] == [0, 300, 600]
+    assert set(r.vortex_tables[-1][1]) == set(T.VORTICES) and r.vortex_tables[-1][1]["Primary"] is not None
+    assert r.vortex_tables[-1][1] == T.host_vortex_table(r.u, 0.08)
+    out = capsys.readouterr().out
+    assert out.count("vortex table (") == 3 and "Primary" in out and "Ghia (0.6172, 0.7344)" in out and "Ghia not listed" in out
+    assert not (tmp_path / "output").exists()
+    plain = run_cavity(**kw)                               # the default: no output iteration, no table, nothing printed about it
+    assert plain.vortex_tables == [] and plain.regression == [] and np.array_equal(plain.u, r.u)
+    assert "vortex table" not in capsys.readouterr().out
