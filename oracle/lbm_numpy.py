@@ -8,10 +8,13 @@ This is a restatement, made by reading the source, of the reference's per-step u
   semantics="mrt_py"  : /root/reference/MRT.py:286-453   (NumPy CPU script, fp64, SRT)
   semantics="mrt_gpu" : /root/reference/MRT_GPU.py:336-699 (CUDA text: funRT SRT/TRT/MRT + funBC)
 
-PARITY STATUS: **parity unpinned at bit level.**  MRT.py cannot be imported in the build
-image (it needs numba and numexpr, MRT.py:9,13,21, both absent) and the reference holds no
-tests, golden vectors or committed outputs for this path; MRT_GPU.py needs PyCUDA/CUDA.
-The oracle is pinned (a) at physics level by the reference's own data file GhiaData.csv
+PARITY STATUS: "mrt_gpu" with promote=True on a float32 lattice is pinned bit for bit against
+MRT_GPU.py's own kernel text, cut out of the script and compiled as host C++ without
+multiply-add contraction (oracle/reftext.py, tests/test_mrt_gpu_text_cpu.py); the bits of a
+real nvcc build (--fmad=true) and the script's host-side initialisation are not.  "mrt_py" is
+**unpinned at bit level**: MRT.py cannot be imported in the build image (it needs numba and
+numexpr, MRT.py:9,13,21, both absent) and the reference holds no tests, golden vectors or
+committed outputs for this path.  Beyond that the oracle is pinned (a) at physics level by the reference's own data file GhiaData.csv
 (tests/golden/ghia.npz), (b) by algebraic identities of the operators, and (c) against a
 second, independently written restatement in C (oracle/lbm_ref.c).  SURVEY.md Appendix C
 lists values from a survey-session run of MRT.py that used stand-in modules for the two

@@ -8,10 +8,12 @@
  *   semantics 1 "mrt_gpu" : /root/reference/MRT_GPU.py:336-699 (funRT SRT/TRT/MRT + funBC)
  * in the reference's host layout fin[k][x][y], y fastest, y = 0 the moving lid.
  *
- * PARITY STATUS: parity unpinned at bit level (see oracle/README.md): the reference's
- * MRT.py is not importable in the build image (numba, numexpr absent) and the reference
- * holds no golden vectors for this path.  Pinned by GhiaData.csv at physics level, by
- * operator identities, and by bit-equality with oracle/lbm_numpy.py.
+ * PARITY STATUS (see oracle/README.md): semantics 1 with promote is pinned bit for bit against
+ * MRT_GPU.py's own kernel text compiled without contraction (oracle/reftext.py).  Semantics 0 is
+ * unpinned at bit level: the reference's MRT.py is not importable in the build image (numba,
+ * numexpr absent) and the reference holds no golden vectors for it.  Both are pinned by
+ * GhiaData.csv at physics level, by operator identities, and by bit-equality with
+ * oracle/lbm_numpy.py.
  *
  * Build: see oracle/Makefile  (gcc -O2 -ffp-contract=off: no FMA contraction, so every
  * + - * / is one IEEE operation in the order written).
@@ -60,6 +62,10 @@ enum { COLL_SRT = 0, COLL_TRT = 1, COLL_MRT = 2 };
  * value already promoted by one) as an operand is a double operation, and the sub-expression is rounded to float ONCE, at
  * the assignment.  promote != 0 evaluates exactly those sub-expressions that way; operations between two floats (or an int
  * and a float) stay float operations.  In the double build the casts are no-ops: promote changes nothing (tests assert it).
+ * PINNED: this reading of the text -- which sub-expressions are double, where the one rounding happens, the order of the moments,
+ * the wall rules, the streaming condition, the closure's tau -- equals the text itself, cut out of MRT_GPU.py and compiled as
+ * host C++ with -ffp-contract=off (oracle/reftext.py), bit for bit for SRT / TRT / MRT with and without the closure
+ * (tests/test_mrt_gpu_text_cpu.py).
  * What this still is NOT: nvcc's default --fmad=true may fuse any float multiply-add of the text into one FMA; which ones
  * is the compiler's choice and cannot be read from the text, so no restatement can claim the bits of a real run. */
 

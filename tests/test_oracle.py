@@ -2,7 +2,8 @@
 operator identities, the recorded cross-check of SURVEY.md Appendix C, and the physics-level
 pin against the reference's own data file (GhiaData.csv -> tests/golden/ghia.npz).
 
-Parity status of the oracle itself: *parity unpinned at bit level* -- see oracle/README.md.
+Parity status of the oracle itself: "mrt_gpu" with promotion is pinned against MRT_GPU.py's own kernel
+text (tests/test_mrt_gpu_text_cpu.py); "mrt_py" is *unpinned at bit level* -- see oracle/README.md.
 """
 import hashlib
 import json
