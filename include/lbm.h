@@ -172,7 +172,7 @@ int lbm_step(lbm_ctx* c, int nsteps);
 int lbm_sync(lbm_ctx* c);
 /* replaces: the commented cuda.Event timing (MRTTiledPull.py:364-365,536-549): runs nsteps
  * steps between two HIP events on the compute stream and returns the elapsed milliseconds (automatic samples of the time
- * statistics and of a monitor series included, lbm_stats_begin / lbm_monitor_begin) */
+ * statistics, of a monitor series and of the residual included, lbm_stats_begin / lbm_monitor_begin / lbm_residual_begin) */
 int lbm_time_steps(lbm_ctx* c, int nsteps, double* ms);
 /* iterations performed since the last lbm_init_equilibrium / lbm_set_state */
 long long lbm_steps_done(const lbm_ctx* c);
@@ -317,6 +317,69 @@ int lbm_monitor_sample(lbm_ctx* c);
 int lbm_monitor_read(lbm_ctx* c, lbm_monitor_record* records_out, int max_records, long long* count, long long* dropped);
 int lbm_monitor_end(lbm_ctx* c);
 int lbm_get_lines(lbm_ctx* c, int x, int gy, void* col_out, void* row_out, int host_dtype);
+
+/* --- field residual ------------------------------------------------------------------------ */
+/* No reference counterpart (the reference's stop rule watches np.mean(u), MRT_GPU.py:883-889): the change of the sampled u and rho
+ * between two consecutive samples, reduced on the device to one small record per lattice -- the field residual of a steady run.  The
+ * previous sample stays on the device as a snapshot; no field crosses PCIe.  A SAMPLE is the monitor's: exactly the u[2][X][Y],
+ * rho[X][Y] that lbm_get_fields(host_dtype) would return right after n steps (same lagged lattice, gather + macros, wall overrides),
+ * whatever the kernel route, dtype, operator, arithmetic, closure, semantics, batch or slab.  Every value is first rounded to host_dtype,
+ * then converted to double; everything below is computed in double without contraction.
+ *
+ * The snapshot holds ux, uy, rho of the previous sample for every own cell; after a sample it holds the current sample's values,
+ * bit-preserving, for cells that are not finite too.  (Only the values are specified; the library stores them in the type
+ * lbm_get_fields(host_dtype) hands out, 12 or 24 B per cell and lattice.)
+ * Per cell, with pux, puy, prho the snapshot's values:
+ *     dux = ux - pux;  duy = uy - puy;  d2 = dux * dux + duy * duy        (each product rounded, then the sum)
+ *     u2 = ux * ux + uy * uy
+ *     dr = rho - prho;  dr2 = dr * dr
+ * A cell takes part only if all six values ux, uy, rho, pux, puy, prho are finite.
+ * lbm_residual_record (all doubles, one per lattice of the batch):
+ *   step, step_prev   the step counts of the two samples
+ *   cells             own cells that take part
+ *   nonfinite         own cells that do not
+ *   sum_du2, sum_u2, sum_drho2   sums of d2, u2, dr2 over the cells that take part
+ *   max_du2, max_x, max_y   the maximum of d2 over the same cells with its cell (global y); ties go to the smaller x, then the smaller y
+ *                     (an explicit order on (d2, x, y), as the monitor's minimum) -- the first hit of np.argmax on the [X][Y] host array
+ *   max_drho2         the maximum of dr2
+ *   No cell takes part: max_du2 = max_drho2 = -inf, max_x = max_y = -1.
+ * The sums are accumulated in the monitor's fixed tree (lane, wave, workgroup, then the workgroups' partial results in index order)
+ * without atomics: identical from run to run, and identical between manual and automatic samples.
+ *
+ * lbm_residual_begin: allocates the snapshot, the partial results and room for capacity x batch records (here, never inside lbm_step)
+ *   and records n0 = lbm_steps_done().  The FIRST sample after it only fills the snapshot; every later sample appends one record and
+ *   then replaces the snapshot.  With the buffer full a sample is counted in `dropped`, appends nothing and still refreshes the
+ *   snapshot; stepping is unaffected.  every > 0: lbm_step and lbm_time_steps sample by themselves at step counts n0 + every,
+ *   n0 + 2 every, ..., from the lattice after n - 1 steps where a launch unit starts there -- the mechanism and the rules of
+ *   lbm_stats_begin (a third sampler with its own schedule: the units are cut at the earliest next sample of the three; lbm_step_unit
+ *   and the split-step calls refuse; LBM_ERR_STATE on a slab, where every rank calls lbm_residual_sample at the same step counts and the
+ *   host combines the records).  every = 0: samples through lbm_residual_sample only.  Calling it again restarts the series.
+ *   host_dtype other than LBM_F32 / LBM_F64, every < 0 or capacity < 1: LBM_ERR_INVALID.
+ * lbm_residual_sample: one sample of the fields lbm_get_fields would return now.  LBM_ERR_STATE before the first step and while the
+ *   residual is off.
+ * lbm_residual_read: synchronises; *count = records held, *dropped = samples whose record was not kept;
+ *   records_out[min(count, max_records)][batch] receives the oldest records (may be NULL with max_records = 0).  The series goes on.
+ *   LBM_ERR_STATE while the residual is off.
+ * lbm_residual_end: stops sampling and frees the snapshot and the series.  lbm_init_equilibrium, lbm_set_state and lbm_destroy end
+ *   it too; it is not part of a checkpoint.
+ * A NULL context is LBM_ERR_INVALID everywhere. */
+typedef struct lbm_residual_record {
+    double step;
+    double step_prev;
+    double cells;
+    double nonfinite;
+    double sum_du2;
+    double sum_u2;
+    double sum_drho2;
+    double max_du2;
+    double max_x;
+    double max_y;
+    double max_drho2;
+} lbm_residual_record;
+int lbm_residual_begin(lbm_ctx* c, int host_dtype, int every, int capacity);
+int lbm_residual_sample(lbm_ctx* c);
+int lbm_residual_read(lbm_ctx* c, lbm_residual_record* records_out, int max_records, long long* count, long long* dropped);
+int lbm_residual_end(lbm_ctx* c);
 
 /* --- flow topology: stream function, vorticity, vortex extrema ------------------------------- */
 /* replaces: the streamline panel of an output iteration (MRT_GPU.py:808-817) and the comparison with the vortex table of Ghia, Ghia &

@@ -57,6 +57,11 @@ class lbm_monitor_record(ctypes.Structure):
                                                "min_y")] + [("probe", (ctypes.c_double * 3) * LBM_MONITOR_MAX_PROBES)]
 
 
+class lbm_residual_record(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_double) for n in ("step", "step_prev", "cells", "nonfinite", "sum_du2", "sum_u2", "sum_drho2", "max_du2",
+                                               "max_x", "max_y", "max_drho2")]
+
+
 LBM_TOPOLOGY_MAX_WINDOWS, LBM_TOPOLOGY_BLOCK = 8, 64
 
 
@@ -82,8 +87,8 @@ def sources():
 
 
 def build(force=False, verbose=False):
-    """Compile csrc/*.hip for gfx950 into liblbm_hip.so next to this file (in-tree).  The translation units (six of host code +
-    C ABI: lbm_hip / lbm_plan / lbm_launch / lbm_comm / lbm_monitor / lbm_topology; the explicit instantiations of the tile and streaming kernels for float and
+    """Compile csrc/*.hip for gfx950 into liblbm_hip.so next to this file (in-tree).  The translation units (seven of host code +
+    C ABI: lbm_hip / lbm_plan / lbm_launch / lbm_comm / lbm_monitor / lbm_residual / lbm_topology; the explicit instantiations of the tile and streaming kernels for float and
     for double) are compiled in parallel into csrc/_obj/ and linked."""
     srcs = sources()
     if not force and os.path.exists(LIB_PATH) and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(s) for s in srcs):
@@ -143,6 +148,11 @@ SIGNATURES = {
                               ctypes.POINTER(ctypes.c_longlong)]),
     "lbm_monitor_end": (_i, [_vp]),
     "lbm_get_lines": (_i, [_vp, _i, _i, _vp, _vp, _i]),
+    "lbm_residual_begin": (_i, [_vp, _i, _i, _i]),
+    "lbm_residual_sample": (_i, [_vp]),
+    "lbm_residual_read": (_i, [_vp, ctypes.POINTER(lbm_residual_record), _i, ctypes.POINTER(ctypes.c_longlong),
+                               ctypes.POINTER(ctypes.c_longlong)]),
+    "lbm_residual_end": (_i, [_vp]),
     "lbm_topology": (_i, [_vp, ctypes.POINTER(lbm_topology_spec), ctypes.POINTER(lbm_topology_record)]),
     "lbm_get_stream_function": (_i, [_vp, _vp, _vp, _i]),
     "lbm_halo_elems": (_i, [_vp]),

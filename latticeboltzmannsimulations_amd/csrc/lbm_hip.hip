@@ -243,6 +243,7 @@ void lbm_destroy(lbm_ctx* c) {
     if (c->red_dev) (void)hipFree(c->red_dev);
     stats_free(c);
     monitor_free(c);
+    residual_free(c);
     topology_free(c);
     if (c->stage) (void)hipFree(c->stage);
     if (c->relax_dev) (void)hipFree(c->relax_dev);
@@ -266,6 +267,7 @@ int lbm_init_equilibrium(lbm_ctx* c) {
     if (rc) return rc;
     stats_free(c);
     monitor_series_free(c);
+    residual_free(c);
     c->cur = 0; c->raw[0] = 1; c->raw[1] = 1; c->nsteps = 0; c->lag = 0; c->lag_valid = false; c->thin_valid = false;
     const dim3 g = grid_rows(c, c->plan.geo.ny);
     rc = launch_variant(c, [&](auto v) {
@@ -288,6 +290,7 @@ int lbm_set_state(lbm_ctx* c, const void* fin_host, int host_dtype) {
     if (rc) return rc;
     stats_free(c);
     monitor_series_free(c);
+    residual_free(c);
     c->cur = 0; c->raw[0] = 1; c->raw[1] = 1; c->nsteps = 0; c->lag = 0; c->lag_valid = false; c->thin_valid = false;
     rc = launch_variant(c, [&](auto v) {
         using VT = decltype(v);

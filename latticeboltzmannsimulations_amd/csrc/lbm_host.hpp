@@ -114,6 +114,17 @@ struct lbm_ctx {
     long long mon_capacity = 0, mon_count = 0, mon_dropped = 0;
     int mon_every = 0;
     long long mon_next = 0;
+    // Field residual (lbm_residual_*, lbm_residual.hip): res_snap holds the previous sample (ux, uy, rho of every own cell, in the type
+    // lbm_get_fields(res_host_dtype) hands out), res_part the workgroups' partial results of one pass, res_series the records,
+    // [capacity][batch]; all null while the residual is off.  res_prev: the step count of the snapshot (-1: no sample yet).  Automatic
+    // sampling (res_every > 0) cuts the units like the statistics do (step_many).
+    void* res_snap = nullptr;
+    double* res_part = nullptr;
+    lbm_residual_record* res_series = nullptr;
+    int res_host_dtype = LBM_F32;
+    long long res_capacity = 0, res_count = 0, res_dropped = 0, res_prev = -1;
+    int res_every = 0;
+    long long res_next = 0;
     // Flow topology (lbm_topology, lbm_get_stream_function; lbm_topology.hip): topo_part holds the block sums, the partial results and
     // the records of the record path, topo_fields the staged psi and omega of the field path; each allocated on first use, kept.
     double* topo_part = nullptr;
@@ -362,6 +373,9 @@ void monitor_series_free(lbm_ctx* c);
 void monitor_free(lbm_ctx* c);
 // lbm_topology.hip
 void topology_free(lbm_ctx* c);
+// lbm_residual.hip
+int residual_series_sample(lbm_ctx* c, int which, long long step);
+void residual_free(lbm_ctx* c);
 // lbm_comm.hip
 rccl_api& rccl();
 void halo_range(const lbm_ctx* c, int k, int* lo, int* hi);

@@ -463,30 +463,34 @@ int stats_accumulate(lbm_ctx* c, int which) {
     return LBM_OK;
 }
 
-// Automatic sampling (lbm_stats_begin / lbm_monitor_begin with every > 0; a lone lattice).  The sample of step count n is the
+// Automatic sampling (lbm_stats_begin / lbm_monitor_begin / lbm_residual_begin with every > 0; a lone lattice).  The sample of step count n is the
 // macroscopic state of the lattice after n - 1 steps, so the unit plan is cut where a unit starts at n - 1 and the sample is taken there
-// from lat[cur], with its raw flag: no lag replay.  A call that ends at n - 1 takes it at the start of the next call.  The two samplers
-// keep their own schedules; a step count due for both is read by both.
+// from lat[cur], with its raw flag: no lag replay.  A call that ends at n - 1 takes it at the start of the next call.  The three samplers
+// keep their own schedules; a step count due for several is read by each of them.
 static int sample_if_due(lbm_ctx* c) {
     const bool stats_due = c->stats_every > 0 && c->nsteps + 1 == c->stats_next;
     const bool mon_due = c->mon_every > 0 && c->nsteps + 1 == c->mon_next;
-    if (!stats_due && !mon_due) return LBM_OK;
+    const bool res_due = c->res_every > 0 && c->nsteps + 1 == c->res_next;
+    if (!stats_due && !mon_due && !res_due) return LBM_OK;
     int rc = join_edges(c);   // (frame work of the last unit on the second stream wrote part of lat[cur])
     if (rc == LBM_OK && stats_due) rc = stats_accumulate(c, c->cur);
     if (rc == LBM_OK && mon_due) rc = monitor_series_sample(c, c->cur, c->nsteps + 1);
+    if (rc == LBM_OK && res_due) rc = residual_series_sample(c, c->cur, c->nsteps + 1);
     if (rc) return rc;
     c->int_stale = true;      // (s_comm must not rewrite lat[cur] before the sample has read it)
     if (stats_due) c->stats_next += c->stats_every;
     if (mon_due) c->mon_next += c->mon_every;
+    if (res_due) c->res_next += c->res_every;
     return LBM_OK;
 }
 
-// steps the unit planner may spend before the next cut: the earlier of the two samplers' next sample (all of them with automatic
+// steps the unit planner may spend before the next cut: the earliest of the three samplers' next sample (all of them with automatic
 // sampling off)
 static int steps_to_cut(const lbm_ctx* c, int left) {
     long long n = left;
     if (c->stats_every > 0) n = std::min<long long>(n, c->stats_next - 1 - c->nsteps);
     if (c->mon_every > 0) n = std::min<long long>(n, c->mon_next - 1 - c->nsteps);
+    if (c->res_every > 0) n = std::min<long long>(n, c->res_next - 1 - c->nsteps);
     return (int)n;
 }
 
@@ -557,6 +561,7 @@ int lbm_step_edges(lbm_ctx* c) {
     if (c->plan.push) return fail(c, LBM_ERR_STATE, "the split-step calls do not apply to kernel = PUSH");
     if (c->stats_every > 0) return fail(c, LBM_ERR_STATE, "automatic sampling (lbm_stats_begin, every > 0) runs inside lbm_step only");
     if (c->mon_every > 0) return fail(c, LBM_ERR_STATE, "automatic monitoring (lbm_monitor_begin, every > 0) runs inside lbm_step only");
+    if (c->res_every > 0) return fail(c, LBM_ERR_STATE, "the automatic residual (lbm_residual_begin, every > 0) runs inside lbm_step only");
     HIP_TRY(c, hipSetDevice(c->p.device));
     return launch_rows(c, c->cur, c->cur ^ 1, 0, c->plan.geo.ny - 1, 2, c->s_compute);
 }
@@ -582,6 +587,7 @@ int lbm_step_unit(lbm_ctx* c, int S) {
     if (own_transport(c)) return fail(c, LBM_ERR_STATE, "lbm_step_unit: a communicator is attached, lbm_step() moves the halos itself");
     if (c->stats_every > 0) return fail(c, LBM_ERR_STATE, "lbm_step_unit: automatic sampling (lbm_stats_begin, every > 0) runs inside lbm_step only");
     if (c->mon_every > 0) return fail(c, LBM_ERR_STATE, "lbm_step_unit: automatic monitoring (lbm_monitor_begin, every > 0) runs inside lbm_step only");
+    if (c->res_every > 0) return fail(c, LBM_ERR_STATE, "lbm_step_unit: the automatic residual (lbm_residual_begin, every > 0) runs inside lbm_step only");
     if (c->raw[c->cur]) return fail(c, LBM_ERR_STATE, "lbm_step_unit: the first step after an upload is a single step");
     const bool ok = c->plan.tb_steps == 2 ? S == 2 : (S >= 3 && S <= c->plan.tb_steps);
     if (!ok)

@@ -21,14 +21,19 @@ from timeit import default_timer as timer
 
 import numpy as np
 
+from . import residual as RS
 from .solver import CavityBatch
 
 
 def _solve_batch(idx, Re_range, xsize, ysize, RT, turb, uLB, maxIt, Pinterval, tolerance, device, dtype, say, out, arith, convergence="host",
-                 semantics="mrt_gpu"):
+                 semantics="mrt_gpu", residual_tol=None, residual_final=None):
     """Runs the lattices Re_range[idx] in lock step; fills out = (f_final, u_final, its) rows idx.  The per-lattice logic is
     the reference's loop body (MRT_GPU_datagen.py:707-731,862-871): a check after iteration It = 0, Pinterval, 2 Pinterval, ...
-    (i.e. after It + 1 steps), `count` consecutive-or-not hits of |mean(u) - mean(u_past)| / uLB < tolerance, stop at count > 5."""
+    (i.e. after It + 1 steps), `count` consecutive-or-not hits of |mean(u) - mean(u_past)| / uLB < tolerance, stop at count > 5.
+    residual_tol (criterion='residual'): every check takes a sample of the field residual on the device instead (one record per
+    lattice crosses PCIe), and a lattice stops at the first check whose relative L2 change of u per step is below residual_tol -- the
+    rule of run_cavity(criterion='residual'); residual_final rows idx receive the value each lattice stopped at."""
+    by_residual = residual_tol is not None
     f_final, u_final, its = out
     sem = {} if semantics == "mrt_gpu" else {"semantics": semantics}
     with CavityBatch(xsize, ysize, [float(Re_range[i]) for i in idx], RT=RT, uLB=uLB, dtype=dtype, turb=turb, device=device, arith=arith,
@@ -38,14 +43,32 @@ def _solve_batch(idx, Re_range, xsize, ysize, RT, turb, uLB, maxIt, Pinterval, t
         past = [0.0] * len(idx)
         open_ = set(range(len(idx)))
         It = 0
+        if by_residual:
+            b.begin_residual(every=0, capacity=min(maxIt // int(Pinterval) + 2, 1 << 18), out_dtype=np.float32)
+        nrec = 0
         while open_:
             b.step(It + 1 - b.steps_done)
             # the check value: NumPy's float32 mean of the downloaded field (the reference's own definition), or the mean reduced on
             # the device in double -- B doubles cross PCIe instead of B fields; the fields are then fetched only when a lattice stops
-            means = b.mean_u() if convergence == "device" else None
-            u = None if convergence == "device" else b.get_fields(out_dtype=np.float32)[0]
+            means = b.mean_u() if convergence == "device" and not by_residual else None
+            u = None if convergence == "device" or by_residual else b.get_fields(out_dtype=np.float32)[0]
             finished = []
+            values = None
+            if by_residual:
+                ser = b.sample_residual().residual_series()
+                if ser["count"] > nrec:                    # (the first check only fills the snapshot)
+                    nrec = ser["count"]
+                    values = RS.norms({k: ser[k][nrec - 1] for k in RS.FIELDS}, uLB)["rel_l2_per_step"]
             for j in sorted(open_):
+                if by_residual:
+                    say("current Re is " + str(Re_range[idx[j]]) + " and iteration is " + str(It))
+                    if values is not None:
+                        say("current residual is " + str(values[j]))
+                        residual_final[idx[j]] = values[j]
+                        if RS.below(values[j], residual_tol):
+                            say("breaking out of loop because of convergence")
+                            finished.append(j)
+                    continue
                 mean_u = float(means[j]) if convergence == "device" else float(np.mean(u[j]))
                 say("current Re is " + str(Re_range[idx[j]]) + " and iteration is " + str(It))
                 say("current mean u is " + str(mean_u / uLB))
@@ -77,12 +100,21 @@ def _solve_batch(idx, Re_range, xsize, ysize, RT, turb, uLB, maxIt, Pinterval, t
 
 def generate(Re_range=None, xsize=32 * 12, ysize=32 * 12, RT="SRT", turb=1, uLB=0.08, maxIt=3000000, Pinterval=10000,
              tolerance=0.0000001, OutputFolder="./output", save=True, concurrent=64, devices=(0,), dtype=np.float32,
-             quiet=False, arith="strict", convergence="host", BC="EB-NEBB "):
+             quiet=False, arith="strict", convergence="host", BC="EB-NEBB ", criterion="mean_u", residual_tol=None):
     """Returns (feq_initial, f_final, u_final, Re_range, iterations_per_Re); writes the four .npy files when `save`.
+    criterion: 'mean_u' (default, the reference's rule) or 'residual' -- each lattice stops at the first check whose field residual (the
+    relative L2 change of u per step since the previous check, reduced on the device) is below residual_tol, which must be given; the
+    function then returns a sixth item, residual_final [n], the value each lattice stopped at (the last one seen for a lattice that
+    ran out of iterations, NaN if it saw none), and saves it as residual_final.npy beside the four files, which do not change.
     BC: 'EB-NEBB ' (default, the wet-node walls of MRT_GPU.py) or 'BB' (half-way bounce-back, semantics='bounce_back': the
     cavity's mass is conserved to rounding; needs turb=0)."""
     if BC.strip() not in ("EB-NEBB", "BB"):
         raise ValueError("BC must be 'EB-NEBB ' or 'BB'")
+    if criterion not in ("mean_u", "residual"):
+        raise ValueError("criterion must be 'mean_u' or 'residual'")
+    by_residual = criterion == "residual"
+    if by_residual and (residual_tol is None or not float(residual_tol) > 0.0):
+        raise ValueError("criterion='residual' needs an explicit residual_tol > 0 (the noise floor depends on dtype and lattice size)")
     semantics = "bounce_back" if BC.strip() == "BB" else "mrt_gpu"
     if semantics == "bounce_back" and turb:
         raise ValueError("BC='BB' runs without the Smagorinsky closure: pass turb=0")
@@ -92,11 +124,13 @@ def generate(Re_range=None, xsize=32 * 12, ysize=32 * 12, RT="SRT", turb=1, uLB=
     tstart = timer()
     out = (np.zeros((n, 9, xsize, ysize), dtype=np.float32), np.zeros((n, 2, xsize, ysize), dtype=np.float32),
            np.zeros(n, dtype=np.int64))
+    residual_final = np.full(n, np.nan) if by_residual else None
     chunks = [list(range(i, min(n, i + concurrent))) for i in range(0, n, concurrent)]
 
     def work(k):
         return _solve_batch(chunks[k], Re_range, xsize, ysize, RT, turb, uLB, maxIt, Pinterval, tolerance,
-                            devices[k % len(devices)], dtype, say, out, arith, convergence, semantics)
+                            devices[k % len(devices)], dtype, say, out, arith, convergence, semantics,
+                            float(residual_tol) if by_residual else None, residual_final)
     if len(devices) > 1 and len(chunks) > 1:
         with ThreadPoolExecutor(max_workers=len(devices)) as pool:      # lbm_step runs in C with the GIL released
             feq = list(pool.map(work, range(len(chunks))))
@@ -111,7 +145,11 @@ def generate(Re_range=None, xsize=32 * 12, ysize=32 * 12, RT="SRT", turb=1, uLB=
         np.save(os.path.join(OutputFolder, "f_final.npy"), f_final)
         np.save(os.path.join(OutputFolder, "u_final.npy"), u_final)
         np.save(os.path.join(OutputFolder, "Re_range.npy"), Re_range)
+        if by_residual:
+            np.save(os.path.join(OutputFolder, "residual_final.npy"), residual_final)
     say("TOTAL time elapsed is ", timer() - tstart, "seconds")
+    if by_residual:
+        return feq_initial, f_final, u_final, Re_range, its, residual_final
     return feq_initial, f_final, u_final, Re_range, its
 
 
@@ -130,10 +168,14 @@ def main(argv=None):
                     help="device: the convergence test on lbm_mean_u (reduced on the GPU) instead of the downloaded field")
     ap.add_argument("--BC", choices=["EB-NEBB", "BB"], default="EB-NEBB",
                     help="wall model: EB-NEBB wet-node walls (with the Smagorinsky closure), or BB half-way bounce-back (without it)")
+    ap.add_argument("--criterion", choices=["mean_u", "residual"], default="mean_u",
+                    help="stop rule per lattice: the reference's test on mean(u), or the field residual reduced on the GPU")
+    ap.add_argument("--residual-tol", type=float, default=None, help="with --criterion residual: stop below this value (required, no default)")
     a = ap.parse_args(argv)
     bb = dict(BC="BB", turb=0) if a.BC == "BB" else {}
     generate(np.arange(*a.Re), xsize=a.size, ysize=a.size, concurrent=a.concurrent, Pinterval=a.Pinterval, maxIt=a.maxIt,
-             OutputFolder=a.OutputFolder, arith=a.arith, convergence=a.convergence, **bb)
+             OutputFolder=a.OutputFolder, arith=a.arith, convergence=a.convergence, criterion=a.criterion, residual_tol=a.residual_tol,
+             **bb)
     return 0
 
 

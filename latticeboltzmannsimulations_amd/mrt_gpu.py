@@ -22,6 +22,7 @@ from timeit import default_timer as timer
 import numpy as np
 
 from . import ghia
+from . import residual as RS
 from .VTKWrapper import saveToVTK
 from .monitor import vortex_window
 from .solver import CavitySolver
@@ -49,6 +50,7 @@ class CavityResult:
         self.vortices = []          # (iteration, (x1, y1), (x2, y2)) at every output iteration
         self.series = None          # run_cavity(MonitorEvery=k): CavitySolver.monitor_series() of the whole run
         self.vortex_tables = []     # run_cavity(vortex_table=True): (iteration, CavitySolver.vortex_table()) at every output iteration
+        self.residuals = []         # run_cavity(criterion="residual"): (iteration, residual record) at every output iteration after the first
 
 
 CS2_EFFECTIVE, CS_BULK = 0.025, 0.16     # MRT_GPU.py:350,374-376: Van Driest damping is overwritten by Cs2 = 0.025
@@ -147,7 +149,7 @@ def run_cavity(maxIt=3000000, Re=10000.0, RT="SRT", turb=1, xsize=32 * 5, ysize=
                Pinterval=3000, SavePlot=True, SaveVTK=False, project="ldc", OutputFolder="./output",
                dtype=np.float32, semantics="mrt_gpu", device=0, quiet=False, solver_factory=None, arith="strict",
                convergence="host", vtk_correct=False, BC="EB-NEBB ", AverageFrom=None, AverageEvery=100, monitor="host",
-               MonitorEvery=None, Probes=(), vortex_table=False):
+               MonitorEvery=None, Probes=(), vortex_table=False, criterion="mean_u", residual_tol=None, residual_hits=1):
     """Run the lid-driven cavity like MRT_GPU.py does; returns a :class:`CavityResult`.
 
     Argument names and defaults are the module constants of MRT_GPU.py:38-58.
@@ -174,7 +176,21 @@ def run_cavity(maxIt=3000000, Re=10000.0, RT="SRT", turb=1, xsize=32 * 5, ysize=
     result.series, nothing crosses PCIe before the run ends.
     vortex_table=True: every Pinterval is an output iteration, and each one appends (iteration, CavitySolver.vortex_table()) to
     result.vortex_tables -- Ghia's named vortices (Primary, Top, BL1, BR1) from the extrema of the stream function, reduced on the device --
-    and prints the table beside Ghia's.  With either monitor mode; False (default): nothing changes."""
+    and prints the table beside Ghia's.  With either monitor mode; False (default): nothing changes.
+    criterion: 'mean_u' (default) -- the reference's stop rule above, nothing changes; 'residual' -- the run stops on the field residual
+    instead: every Pinterval is an output iteration, each one takes a sample of the residual on the device
+    (CavitySolver.sample_residual: the change of u and rho since the previous check, no field crosses PCIe), prints
+    `current residual is <relative L2 change of u per step>` (residual.norms(record, uLB)["rel_l2_per_step"]) and appends
+    (iteration, record) to result.residuals; the run ends with result.converged once that value is below residual_tol at
+    residual_hits consecutive checks.  residual_tol has no default -- the floor the residual settles on depends on dtype and lattice
+    size -- and must be given.  With either monitor mode."""
+    if criterion not in ("mean_u", "residual"):
+        raise ValueError("criterion must be 'mean_u' or 'residual'")
+    by_residual = criterion == "residual"
+    if by_residual and (residual_tol is None or not float(residual_tol) > 0.0):
+        raise ValueError("criterion='residual' needs an explicit residual_tol > 0 (the noise floor depends on dtype and lattice size)")
+    if by_residual and int(residual_hits) < 1:
+        raise ValueError("residual_hits must be >= 1")
     if monitor not in ("host", "device"):
         raise ValueError("monitor must be 'host' or 'device'")
     on_device = monitor == "device"
@@ -232,12 +248,20 @@ def run_cavity(maxIt=3000000, Re=10000.0, RT="SRT", turb=1, xsize=32 * 5, ysize=
     count = 0
     done = 0          # iterations performed
     have_ghia = int(round(float(Re))) in ghia.RE_COLUMNS
-    outputs = SaveVTK or SavePlot or on_device or bool(vortex_table)
+    outputs = SaveVTK or SavePlot or on_device or bool(vortex_table) or by_residual
     averaging = False
     if MonitorEvery is not None:
         probes = tuple(Probes) if len(Probes) else ((int(xsize / 2), int(ysize / 2)),)
         solver.begin_monitor(every=int(MonitorEvery), capacity=min(maxIt // int(MonitorEvery) + 1, 1 << 18), probes=probes,
                              out_dtype=np.float32)
+
+    if by_residual:
+        if not hasattr(solver, "sample_residual"):
+            solver.close()
+            raise TypeError("criterion='residual' needs a solver with begin_residual / sample_residual / residual_series (CavitySolver); "
+                            + type(solver).__name__ + " has none")
+        solver.begin_residual(every=0, capacity=min(maxIt // int(Pinterval) + 2, 1 << 18), out_dtype=np.float32)
+    res_hits = 0
 
     def advance(n):   # n iterations; statistics begin once `done` reaches AverageFrom
         nonlocal averaging
@@ -314,7 +338,21 @@ def run_cavity(maxIt=3000000, Re=10000.0, RT="SRT", turb=1, xsize=32 * 5, ysize=
                 finally:
                     os.chdir(cwd)
             say("time elapsed is ", (timer() - tstart), "seconds")
-            if convergence == "device":
+            if by_residual:
+                solver.sample_residual()
+                ser = solver.residual_series()
+                if ser["count"] > len(res.residuals):      # (the first check only fills the snapshot)
+                    rec = RS.record_at(ser, ser["count"] - 1)
+                    value = RS.norms(rec, uLB)["rel_l2_per_step"]
+                    res.residuals.append((It, rec))
+                    say("current residual is " + str(value))
+                    res_hits = res_hits + 1 if RS.below(value, float(residual_tol)) else 0
+                hit = False
+                if res_hits >= int(residual_hits):
+                    say("breaking out of loop because of convergence")
+                    res.converged = True
+                    break
+            elif convergence == "device":
                 mean_now = solver.mean_u()
                 hit = abs(mean_now - mean_past) / uLB < 0.00000001
                 mean_past = mean_now
@@ -373,6 +411,10 @@ def main(argv=None):
     ap.add_argument("--monitor-every", type=int, default=None, help="with --monitor device: a monitor record every this many iterations")
     ap.add_argument("--probe", type=int, nargs=2, action="append", default=[], metavar=("X", "Y"),
                     help="probe cell of the monitor series (repeatable; default: the lattice centre)")
+    ap.add_argument("--criterion", choices=["mean_u", "residual"], default="mean_u",
+                    help="stop rule: the reference's test on mean(u), or the field residual (relative L2 change of u per step) reduced on the GPU")
+    ap.add_argument("--residual-tol", type=float, default=None, help="with --criterion residual: stop below this value (required, no default)")
+    ap.add_argument("--residual-hits", type=int, default=1, help="with --criterion residual: consecutive checks below the tolerance")
     ap.add_argument("--vortex-table", action="store_true",
                     help="at every output iteration: Ghia's named vortices from the stream function's extrema, reduced on the device")
     a = ap.parse_args(argv)
@@ -381,7 +423,8 @@ def main(argv=None):
                    OutputFolder=a.OutputFolder, dtype=np.dtype(a.dtype), semantics=a.semantics, arith=a.arith,
                    convergence=a.convergence, vtk_correct=a.vtk_correct, BC="BB" if a.BC == "BB" else "EB-NEBB ",
                    AverageFrom=a.average_from, AverageEvery=a.average_every, monitor=a.monitor, MonitorEvery=a.monitor_every,
-                   Probes=tuple(tuple(p) for p in a.probe), vortex_table=a.vortex_table)
+                   Probes=tuple(tuple(p) for p in a.probe), vortex_table=a.vortex_table, criterion=a.criterion,
+                   residual_tol=a.residual_tol, residual_hits=a.residual_hits)
     print("MLUPS : ", r.mlups)
     return 0
 

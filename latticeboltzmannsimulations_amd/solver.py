@@ -8,6 +8,7 @@ import numpy as np
 
 from . import _lib as L
 from . import monitor as M
+from . import residual as RS
 from . import topology as T
 
 _DT = {np.dtype(np.float32): L.LBM_F32, np.dtype(np.float64): L.LBM_F64}
@@ -354,6 +355,43 @@ class CavitySolver:
     def end_monitor(self):
         """Stop the series and free its device buffer (lbm_monitor_end)."""
         self._check(self.lib.lbm_monitor_end(self._h), "lbm_monitor_end")
+
+    # -- field residual (lbm_residual_*) --------------------------------------------------------------
+    def begin_residual(self, every=0, capacity=1024, out_dtype=None):
+        """Start (or restart) the field residual on the device (lbm_residual_begin): every sample is compared with the previous one,
+        which stays on the device, and leaves one record -- residual.host_residual of the two get_fields(out_dtype=...) results -- in a
+        buffer with room for `capacity` records.  The first sample only fills the snapshot.  every > 0: step() samples by itself at
+        steps_done + every, + 2 every, ...; every = 0: samples through sample_residual() only.  Records beyond the capacity are dropped
+        and counted; the snapshot is refreshed all the same.  Not on a slab with every > 0 (sample by hand there, and combine the
+        slabs' records with residual.combine)."""
+        _, code = self._out_code(out_dtype)
+        self._check(self.lib.lbm_residual_begin(self._h, code, int(every), int(capacity)), "lbm_residual_begin")
+        return self
+
+    def sample_residual(self):
+        """Compare the fields get_fields() would return now with the previous sample and keep them as the next one
+        (lbm_residual_sample)."""
+        self._check(self.lib.lbm_residual_sample(self._h), "lbm_residual_sample")
+        return self
+
+    def residual_series(self):
+        """The records so far (lbm_residual_read): step, step_prev, cells, nonfinite, sum_du2, sum_u2, sum_drho2, max_du2, max_x, max_y,
+        max_drho2 as arrays [count] (a batch: [count, B]), plus count and dropped.  residual.norms() turns them into the usual norms."""
+        n, dropped = ctypes.c_longlong(0), ctypes.c_longlong(0)
+        self._check(self.lib.lbm_residual_read(self._h, None, 0, ctypes.byref(n), ctypes.byref(dropped)), "lbm_residual_read")   # the count
+        count = int(n.value)
+        rec = (L.lbm_residual_record * (count * self.batch))()
+        if count:
+            self._check(self.lib.lbm_residual_read(self._h, rec, count, ctypes.byref(n), ctypes.byref(dropped)), "lbm_residual_read")
+        out = RS.records_to_dict(rec, (count, self.batch))
+        if not self._lead:
+            out = {k: v[:, 0] for k, v in out.items()}
+        out["count"], out["dropped"] = count, int(dropped.value)
+        return out
+
+    def end_residual(self):
+        """Stop the residual and free its snapshot and records (lbm_residual_end)."""
+        self._check(self.lib.lbm_residual_end(self._h), "lbm_residual_end")
 
     # -- flow topology (lbm_topology, lbm_get_stream_function) -------------------------------------
     def topology(self, windows=(), out_dtype=None):

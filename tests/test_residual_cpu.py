@@ -1,0 +1,241 @@
+"""CPU tests of the field residual: the NumPy statement of the contract (residual.host_residual) on hand-made fields, combine over
+row partitions, the norms, the residual stop rule of run_cavity with a stand-in stepper backed by the oracle, and the null-context
+refusals of the four entry points.  No device is needed."""
+import numpy as np
+import pytest
+
+from latticeboltzmannsimulations_amd import _lib, relaxation, residual
+from latticeboltzmannsimulations_amd.mrt_gpu import run_cavity
+from oracle.lbm_ref import CavityOracleC
+
+SUMS = ("sum_du2", "sum_u2", "sum_drho2")
+EXACT = ("step", "step_prev", "cells", "nonfinite", "max_du2", "max_x", "max_y", "max_drho2")
+
+
+def _fields(X, Y, seed):
+    rng = np.random.default_rng(seed)
+    u = (0.05 * rng.standard_normal((2, X, Y))).astype(np.float32)
+    rho = (1.0 + 0.01 * rng.standard_normal((X, Y))).astype(np.float32)
+    return u, rho
+
+
+def sum_bounds(u_prev, rho_prev, u, rho, rows=None):
+    """2 gamma_n sum |x_i| for the three sums (the derivation of tests/test_monitor_gpu.py::_sum_bounds): a sum of n doubles in any
+    order is within gamma_n = n eps / (1 - n eps), eps = 2^-53, times sum |x_i| of the exact sum, so two orders differ by at most
+    twice that.  All terms are >= 0 here, so sum |x_i| is the sum itself."""
+    y0, n = (0, u.shape[2]) if rows is None else rows
+    a = [x[..., y0:y0 + n].astype(np.float64) for x in (u_prev[0], u_prev[1], rho_prev, u[0], u[1], rho)]
+    ok = np.all([np.isfinite(x) for x in a], axis=0)
+    with np.errstate(all="ignore"):
+        dux, duy, dr = a[3] - a[0], a[4] - a[1], a[5] - a[2]
+        terms = (dux * dux + duy * duy, a[3] * a[3] + a[4] * a[4], dr * dr)
+    cells = int(ok.sum())
+    g = cells * 2.0 ** -53 / (1.0 - cells * 2.0 ** -53)
+    return {k: 2.0 * g * float(np.abs(t[ok]).sum()) for k, t in zip(SUMS, terms)}
+
+
+def test_identical_samples_give_zero_sums_and_the_first_cell():
+    u, rho = _fields(13, 9, 1)
+    r = residual.host_residual(u, rho, u.copy(), rho.copy(), step=20, step_prev=10)
+    assert (r["step"], r["step_prev"], r["cells"], r["nonfinite"]) == (20, 10, 13 * 9, 0)
+    assert r["sum_du2"] == 0.0 and r["sum_drho2"] == 0.0 and r["max_drho2"] == 0.0
+    assert (r["max_du2"], r["max_x"], r["max_y"]) == (0.0, 0, 0)
+    u64 = u.astype(np.float64)
+    assert r["sum_u2"] == pytest.approx(float((u64 * u64).sum()), rel=1e-14)
+
+
+def test_one_changed_cell_gives_exact_values():
+    X, Y = 8, 6
+    u, rho = np.zeros((2, X, Y), dtype=np.float32), np.ones((X, Y), dtype=np.float32)
+    u[0, 2, 3], u[1, 2, 3] = 0.5, 0.25          # (exactly representable: every operation below is exact)
+    u2, rho2 = u.copy(), rho.copy()
+    u2[0, 5, 1], u2[1, 5, 1], rho2[5, 1] = 0.125, -0.25, 1.5
+    r = residual.host_residual(u, rho, u2, rho2)
+    assert r["sum_du2"] == 0.125 ** 2 + 0.25 ** 2 == r["max_du2"] and (r["max_x"], r["max_y"]) == (5, 1)
+    assert r["sum_drho2"] == 0.25 == r["max_drho2"]
+    assert r["sum_u2"] == 0.5 ** 2 + 0.25 ** 2 + 0.125 ** 2 + 0.25 ** 2
+    assert r["cells"] == X * Y and r["nonfinite"] == 0
+
+
+def test_equal_maxima_go_to_the_smaller_x_then_the_smaller_y():
+    X, Y = 8, 6
+    u, rho = np.zeros((2, X, Y), dtype=np.float64), np.ones((X, Y))
+    u2 = u.copy()
+    for x, y in ((5, 1), (3, 4), (3, 2), (6, 0)):
+        u2[0, x, y] = 0.5
+    u2[1, 7, 5] = -0.5                           # the same d2 through the other component
+    r = residual.host_residual(u, rho, u2, rho)
+    assert (r["max_du2"], r["max_x"], r["max_y"]) == (0.25, 3, 2)
+    u2[0, 3, 2] = 0.25
+    r = residual.host_residual(u, rho, u2, rho)
+    assert (r["max_x"], r["max_y"]) == (3, 4)
+
+
+def test_cells_that_are_not_finite_in_either_sample_are_counted_and_left_out():
+    u, rho = _fields(10, 7, 2)
+    u2, rho2 = _fields(10, 7, 3)
+    want = residual.host_residual(u, rho, u2, rho2)
+    a, b, c, d = u.copy(), rho.copy(), u2.copy(), rho2.copy()
+    a[0, 1, 1] = np.nan
+    b[2, 2] = np.inf
+    c[1, 3, 3] = -np.inf
+    d[4, 4] = np.nan
+    c[0, 1, 1] = np.nan                          # a cell bad in both samples counts once
+    r = residual.host_residual(a, b, c, d)
+    assert r["nonfinite"] == 4 and r["cells"] == 70 - 4
+    bad = [(1, 1), (2, 2), (3, 3), (4, 4)]
+    ok = np.ones((10, 7), dtype=bool)
+    for x, y in bad:
+        ok[x, y] = False
+    du = u2.astype(np.float64) - u.astype(np.float64)
+    d2 = du[0] * du[0] + du[1] * du[1]
+    assert r["sum_du2"] == pytest.approx(float(d2[ok].sum()), rel=1e-13) and r["sum_du2"] < want["sum_du2"]
+    assert np.isfinite([r[k] for k in SUMS + ("max_du2", "max_drho2")]).all()
+    every = residual.host_residual(np.full_like(u, np.nan), rho, u2, rho2)
+    assert every["cells"] == 0 and every["nonfinite"] == 70 and every["sum_du2"] == 0.0
+    assert (every["max_du2"], every["max_x"], every["max_y"], every["max_drho2"]) == (-np.inf, -1, -1, -np.inf)
+
+
+def test_rows_restrict_the_record_to_a_slab():
+    u, rho = _fields(12, 10, 4)
+    u2, rho2 = _fields(12, 10, 5)
+    r = residual.host_residual(u, rho, u2, rho2, rows=(3, 4))
+    cut = residual.host_residual(u[:, :, 3:7], rho[:, 3:7], u2[:, :, 3:7], rho2[:, 3:7])
+    assert r["cells"] == 12 * 4
+    for k in SUMS + ("max_du2", "max_drho2", "max_x"):
+        assert r[k] == cut[k], k
+    assert r["max_y"] == cut["max_y"] + 3        # global rows
+
+
+def test_combine_over_three_row_partitions_equals_the_whole_field():
+    X, Y = 37, 29
+    u, rho = _fields(X, Y, 6)
+    u2, rho2 = _fields(X, Y, 7)
+    u2[0, 4, 20] = np.nan
+    for x, y in ((30, 2), (9, 25)):                        # two equal maxima in different partitions: the smaller x wins
+        u[:, x, y], u2[:, x, y] = 0.0, 3.0
+    whole = residual.host_residual(u, rho, u2, rho2, step=9, step_prev=4)
+    parts = [(0, 10), (10, 9), (19, 10)]
+    got = residual.combine([residual.host_residual(u, rho, u2, rho2, rows=p, step=9, step_prev=4) for p in parts])
+    for k in EXACT:
+        assert got[k] == whole[k], k
+    assert (got["max_x"], got["max_y"]) == (9, 25) and got["nonfinite"] == 1
+    tol = sum_bounds(u, rho, u2, rho2)
+    for k in SUMS:
+        assert abs(got[k] - whole[k]) <= tol[k], (k, got[k] - whole[k], tol[k])
+    none = residual.combine([dict(whole, cells=0, nonfinite=5, max_du2=-np.inf, max_x=-1, max_y=-1, max_drho2=-np.inf)] * 2)
+    assert (none["max_du2"], none["max_x"], none["max_y"], none["nonfinite"]) == (-np.inf, -1, -1, 10)
+
+
+def test_norms_of_a_record_with_known_values_and_the_division_per_step():
+    rec = dict(step=350, step_prev=100, cells=400, nonfinite=0, sum_du2=4.0e-10, sum_u2=1.0e-2, sum_drho2=1.6e-9, max_du2=6.4e-11,
+               max_x=3, max_y=4, max_drho2=1e-10)
+    n = residual.norms(rec, 0.08)
+    assert n["rel_l2"] == pytest.approx(2.0e-4) and n["rms_du"] == pytest.approx(1.0e-6 / 0.08)
+    assert n["max_du"] == pytest.approx(8.0e-6 / 0.08) and n["rms_drho"] == pytest.approx(2.0e-6)
+    for k in ("rel_l2", "rms_du", "max_du", "rms_drho"):
+        assert n[k + "_per_step"] == n[k] / 250.0 and isinstance(n[k], float)
+    series = {k: np.array([v, v]) for k, v in rec.items()}
+    assert np.array_equal(residual.norms(series, 0.08)["rel_l2_per_step"], [n["rel_l2_per_step"]] * 2)
+    assert not residual.below(residual.norms(dict(rec, sum_du2=0.0, sum_u2=0.0), 0.08)["rel_l2_per_step"], 1.0)   # 0 / 0 never passes
+
+
+class ResidualStepper:
+    """The surface of CavitySolver as far as run_cavity(criterion='residual') uses it, backed by the oracle; the residual is the host
+    statement on the fields get_fields returns."""
+    last = None
+
+    def __init__(self, xsize, ysize, Re, RT="MRT", uLB=0.08, semantics="mrt_gpu", dtype=np.float32, turb=0, device=0):
+        self.o = CavityOracleC(xsize, ysize, Re, uLB=uLB, semantics=semantics, collision=RT, dtype=dtype, turb=turb)
+        self.relax = relaxation(Re, ysize, uLB)
+        self.steps_done = 0
+        self.records, self.prev, self.capacity = [], None, 0
+        ResidualStepper.last = self
+
+    def step(self, n=1):
+        self.o.step(n)
+        self.steps_done += int(n)
+        return self
+
+    def sync(self):
+        pass
+
+    def close(self):
+        pass
+
+    def get_fields(self, out_dtype=None, **kw):
+        return self.o.u.astype(out_dtype), self.o.rho.astype(out_dtype)
+
+    def mean_u(self):
+        raise AssertionError("the mean-u rule is not evaluated under criterion='residual'")
+
+    def begin_residual(self, every=0, capacity=1024, out_dtype=None):
+        assert every == 0
+        self.records, self.prev, self.capacity, self.out = [], None, capacity, out_dtype
+        return self
+
+    def sample_residual(self):
+        u, rho = self.get_fields(out_dtype=self.out)
+        if self.prev is not None:
+            self.records.append(residual.host_residual(self.prev[1], self.prev[2], u, rho, step=self.steps_done, step_prev=self.prev[0]))
+        self.prev = (self.steps_done, u, rho)
+        return self
+
+    def residual_series(self):
+        out = {k: np.array([r[k] for r in self.records]) for k in residual.FIELDS}
+        out["count"], out["dropped"] = len(self.records), 0
+        return out
+
+
+class PlainStepper(ResidualStepper):
+    begin_residual = sample_residual = residual_series = property()
+
+
+def test_run_cavity_stops_at_the_first_check_below_the_tolerance(capsys):
+    kw = dict(Re=100.0, RT="MRT", turb=0, xsize=24, ysize=24, Pinterval=200, SavePlot=False, solver_factory=ResidualStepper)
+    free = run_cavity(maxIt=2401, criterion="residual", residual_tol=1e-30, quiet=True, **kw)      # never below: the whole sequence
+    assert not free.converged and free.iterations == 2401
+    its = [it for it, _ in free.residuals]
+    assert its == list(range(200, 2401, 200))                  # one entry per check after the first
+    vals = [residual.norms(rec, 0.08)["rel_l2_per_step"] for _, rec in free.residuals]
+    assert all(rec["step"] == it + 1 and rec["step_prev"] == (1 if it == 200 else it - 199) for it, rec in free.residuals)
+    assert all(a > b for a, b in zip(vals[:6], vals[1:7]))     # (falling at first: the choice below is unambiguous)
+    tol = float(np.sqrt(vals[3] * vals[4]))
+    r = run_cavity(maxIt=2401, criterion="residual", residual_tol=tol, **kw)
+    assert r.converged and r.iterations == its[4] + 1 and len(r.residuals) == 5
+    assert ResidualStepper.last.steps_done == its[4] + 1
+    out = capsys.readouterr().out
+    assert "current residual is " + str(vals[4]) in out and "breaking out of loop because of convergence" in out
+    # two consecutive hits: one check later
+    r2 = run_cavity(maxIt=2401, criterion="residual", residual_tol=tol, residual_hits=2, quiet=True, **kw)
+    assert r2.converged and r2.iterations == its[5] + 1
+    # with the device monitor's checks replaced by nothing the stepper has: the default criterion is untouched
+    plain = run_cavity(maxIt=401, SaveVTK=False, quiet=True, **dict(kw, solver_factory=PlainStepper))
+    assert plain.iterations == 401 and plain.residuals == []
+
+
+def test_run_cavity_refuses_the_residual_criterion_without_a_tolerance_or_a_sampler():
+    kw = dict(maxIt=401, Re=100.0, RT="MRT", turb=0, xsize=16, ysize=16, Pinterval=200, SavePlot=False, quiet=True)
+    with pytest.raises(ValueError, match="residual_tol"):
+        run_cavity(criterion="residual", solver_factory=ResidualStepper, **kw)
+    with pytest.raises(ValueError, match="criterion"):
+        run_cavity(criterion="field", solver_factory=ResidualStepper, **kw)
+    with pytest.raises(TypeError, match="sample_residual"):
+        run_cavity(criterion="residual", residual_tol=1e-6, solver_factory=PlainStepper, **kw)
+
+
+def test_datagen_refuses_the_residual_criterion_without_a_tolerance():
+    from latticeboltzmannsimulations_amd import datagen
+    with pytest.raises(ValueError, match="residual_tol"):
+        datagen.generate(Re_range=[100.0], xsize=16, ysize=16, criterion="residual", save=False, quiet=True)
+
+
+def test_null_context_is_rejected_by_the_four_entry_points():
+    L = _lib.lib()
+    rec = (_lib.lbm_residual_record * 1)()
+    assert L.lbm_residual_begin(None, 0, 0, 4) == -1             # LBM_ERR_INVALID
+    assert L.lbm_residual_sample(None) == -1
+    assert L.lbm_residual_read(None, rec, 1, None, None) == -1
+    assert L.lbm_residual_end(None) == -1
+    import ctypes
+    assert ctypes.sizeof(_lib.lbm_residual_record) == 11 * 8 == residual.RECORD_DOUBLES * 8
