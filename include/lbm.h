@@ -214,25 +214,47 @@ int lbm_mean_u(lbm_ctx* c, double* mean_out);
  * 1 / omega.  With batch = B > 1: tau_host[B][nx][ny]. */
 int lbm_get_tau(lbm_ctx* c, void* tau_host, int host_dtype);
 
+/* --- the samplers: what the time statistics, the run monitor and the field residual share ------------------------------- */
+/* A SAMPLE at step count n is exactly the u[2][X][Y] and rho[X][Y] that lbm_get_fields would return right after n steps (the same
+ * lagged lattice, gather + macros, wall overrides), whatever the kernel route, dtype, operator, arithmetic, closure, semantics, batch
+ * or slab.  lbm_<sampler>_sample takes the sample of the fields lbm_get_fields would return now; it returns LBM_ERR_STATE before the
+ * first step and while the sampler is off.
+ *
+ * THE SCHEDULE.  lbm_<sampler>_begin(..., every, ...) records n0 = lbm_steps_done().  every > 0: lbm_step (and lbm_time_steps, whose
+ * time then includes the samples) samples by itself at step counts n0 + every, n0 + 2 every, ...; after any lbm_step call exactly the
+ * samples with n <= lbm_steps_done() have been taken.  The sample of n is taken from the lattice after n - 1 steps, so the launch
+ * units are cut where one starts at n - 1: an `every` below the steps per launch (8 on the streaming path) shortens the units --
+ * correct, but slower.  Every sampler keeps its own schedule; the units are cut at the earliest next sample of the three, and
+ * samplers due at the same step count read the same lattice, the statistics first, then the monitor, then the residual.
+ * lbm_step_unit and the split-step calls refuse to run (LBM_ERR_STATE) while any sampler samples automatically.  every = 0: manual
+ * sampling only.  On a slab every > 0 is LBM_ERR_STATE (the cuts would split the launch units, and ranks that began differently would
+ * post different exchanges): slabs call lbm_<sampler>_sample at the same step counts on every rank and the host combines the results.
+ * Calling _begin again restarts the sampler.  lbm_<sampler>_end stops it and frees what _begin allocated; lbm_init_equilibrium,
+ * lbm_set_state and lbm_destroy end every sampler too, and none is part of a checkpoint.
+ *
+ * A SERIES (monitor, residual).  _begin allocates room for `capacity` samples, capacity x batch records on the device (there, never
+ * inside lbm_step).  A sample writes the next free slot; nothing returns to the host before lbm_<sampler>_read.  With the buffer full a
+ * sample leaves no record and is counted in `dropped`; stepping is unaffected.  _read synchronises; *count = records held, *dropped =
+ * samples that left none; records_out[min(count, max_records)][batch] receives the oldest records (may be NULL with max_records = 0).
+ * The series goes on.  _read returns LBM_ERR_STATE while no series is on.
+ *
+ * THE TREE (monitor, residual, topology).  Sums, extrema and their cells are reduced without atomics in a fixed order: a lane folds
+ * its cells in grid-stride order, the 64 lanes of a wave combine by shuffles (offsets 32, 16, ..., 1), the waves of a workgroup in
+ * index order, then the workgroups' partial results in index order.  Results are therefore identical from run to run, between manual
+ * and automatic samples, and between a one-shot call and a series.  An extremum's cell is chosen by an explicit total order (value,
+ * x, y), never by "first seen".
+ * A NULL context is LBM_ERR_INVALID everywhere. */
+
 /* --- time statistics ------------------------------------------------------------------- */
 /* No reference counterpart: the time-mean velocity and density and the Reynolds stresses over a window of iterations, accumulated
- * on the device (the LES run of MRT_GPU.py:46-49 needs them).  A SAMPLE at step count n is exactly the u[2][X][Y] and rho[X][Y] that
- * lbm_get_fields would return right after n steps, whatever the kernel route, dtype, operator, arithmetic, closure, semantics, batch
- * or slab.  The device keeps six double sums per cell, S_u, S_v, S_rho, S_uu, S_vv, S_uv: every sample value converted to double,
+ * on the device (the LES run of MRT_GPU.py:46-49 needs them), from the samples defined above.  The device keeps six double sums per cell, S_u, S_v, S_rho, S_uu, S_vv, S_uv: every sample value converted to double,
  * every product rounded in double and then added (no FMA contraction), samples added in sample order (one thread per cell, no
  * atomics).  The read-out S / count is one IEEE double division, so the results are bit-identical to the host loop
  *     step(k); u, rho = get_fields(); acc += u.astype(f64); acc2 += u64 * u64; ...; acc / count.
- * Statistics are not part of a checkpoint; lbm_init_equilibrium, lbm_set_state and lbm_destroy end them.
  *
- * lbm_stats_begin: allocates the sums on the first call (48 B per cell and lattice; never inside lbm_step), zeroes them and records
- *   n0 = lbm_steps_done().  every > 0: lbm_step (and lbm_time_steps, whose time then includes the samples) samples by itself at step
- *   counts n0 + every, n0 + 2 every, ...; after any lbm_step call the count covers exactly the samples with n <= lbm_steps_done().
- *   The sample of n is taken from the lattice after n - 1 steps, so the launch units are cut where one starts at n - 1: an `every`
- *   below the steps per launch (8 on the streaming path) shortens the units -- correct, but slower.  lbm_step_unit and the split-step
- *   calls refuse to run while automatic sampling is on.  every = 0: manual sampling only.  On a slab every > 0 is LBM_ERR_STATE
- *   (the cuts would split the launch units, and ranks that began differently would post different exchanges): slabs call
- *   lbm_stats_sample at the same step counts on every rank.  Calling it again restarts from zero.
- * lbm_stats_sample: adds what lbm_get_fields returns now (the same lagged lattice); LBM_ERR_STATE before the first step.
+ * lbm_stats_begin: allocates the sums on the first call (48 B per cell and lattice; never inside lbm_step), zeroes them and starts the
+ *   schedule (above); after any lbm_step call the count covers exactly the samples with n <= lbm_steps_done().
+ * lbm_stats_sample: adds what lbm_get_fields returns now.
  * lbm_stats_get: means over the samples, float64, whole-lattice host arrays mean_u[2][X][Y], mean_rho[X][Y], second[3][X][Y] (E[uu],
  *   E[vv], E[uv]); with batch = B a leading [B].  Only the context's own rows are written; any pointer may be NULL.  With
  *   count == 0 only *count is written.
@@ -246,10 +268,8 @@ int lbm_stats_end(lbm_ctx* c);
 /* --- run monitor ------------------------------------------------------------------------- */
 /* replaces: what an output iteration of MRT_GPU.py:752-889 computes from the downloaded u and rho -- the two NaN-masked arg-mins of
  * |u|^2 (vortex search, MRT_GPU.py:764-778), np.mean(u), the middle column and row -- by ONE pass over the lattice on the device that
- * leaves a small record per lattice; no field crosses PCIe.  A SAMPLE at step count n is exactly the u[2][X][Y], rho[X][Y] that
- * lbm_get_fields(host_dtype) would return right after n steps (same lagged lattice, gather + macros, wall overrides), whatever the
- * kernel route, dtype, operator, arithmetic, closure, semantics, batch or slab.  Every value is first rounded to host_dtype, as
- * lbm_get_fields does, then converted to double; everything below is computed in double without contraction.  Per cell
+ * leaves a small record per lattice; no field crosses PCIe.  The SAMPLE is the one defined above, of lbm_get_fields(host_dtype): every
+ * value is first rounded to host_dtype, as lbm_get_fields does, then converted to double; everything below is computed in double without contraction.  Per cell
  *     q = (ux * ux + uy * uy) / (uLB * uLB)         (each product rounded, then the sum, then one IEEE division by the double uLB * uLB)
  * which is the `usq` of the reference's search operation for operation.
  *
@@ -265,23 +285,12 @@ int lbm_stats_end(lbm_ctx* c);
  *              ties go to the smaller x, then the smaller y -- the first hit of np.nanargmin on the [X][Y] host array.  No candidate:
  *              min_q = +inf, min_x = min_y = -1
  *   probe[i]   ux, uy, rho at probe cell i; NaN for unused probes and for probes outside this context's rows
- * The sums are accumulated in a fixed tree (lane, wave, workgroup, then the workgroups' partial results in index order) without
- * atomics: identical from run to run, and identical between the one-shot call and a series.
+ * Reduced by the tree described above.
  *
  * lbm_monitor: one record per lattice of the fields lbm_get_fields would return now (records_out[batch]); synchronises.
  *   LBM_ERR_STATE before the first step.
- * lbm_monitor_begin: starts a series with room for `capacity` samples (capacity x batch records on the device, allocated here, never
- *   inside lbm_step).  every > 0: lbm_step and lbm_time_steps take the sample of step counts n0 + every, n0 + 2 every, ... by themselves,
- *   from the lattice after n - 1 steps where a launch unit starts there -- the mechanism and the rules of lbm_stats_begin (the units are
- *   cut at the earlier of the two samplers' next sample; lbm_step_unit and the split-step calls refuse; LBM_ERR_STATE on a slab).
- *   every = 0: samples through lbm_monitor_sample only.  A sample writes slot `count` of the device buffer; nothing returns to the host
- *   before lbm_monitor_read.  With the buffer full further samples are not taken but counted in `dropped`; stepping is unaffected.
- *   Calling it again restarts the series.
- * lbm_monitor_sample: the record of the fields lbm_get_fields would return now, appended to the series.
- * lbm_monitor_read: synchronises; *count = samples held, *dropped = samples not taken; records_out[min(count, max_records)][batch]
- *   receives the oldest records (may be NULL with max_records = 0).  The series goes on.
- * lbm_monitor_end: stops sampling and frees the series.  lbm_init_equilibrium, lbm_set_state and lbm_destroy end it too; it is not part
- *   of a checkpoint.  lbm_monitor_sample / _read return LBM_ERR_STATE while no series is on.
+ * lbm_monitor_begin / _sample / _read / _end: a series of these records with the schedule above; a sample that finds the buffer
+ *   full is not taken.  spec == NULL, every < 0 or capacity < 1: LBM_ERR_INVALID.
  * lbm_get_lines: the column x and the global row gy of the fields lbm_get_fields(host_dtype) would return, the same bits:
  *   col_out[B][3][NY] receives ux, uy, rho of column x (own rows only), row_out[B][3][nx] those of row gy (written only if this
  *   context owns that row).  Either pointer may be NULL (its index is then ignored).  Synchronises. */
@@ -321,10 +330,8 @@ int lbm_get_lines(lbm_ctx* c, int x, int gy, void* col_out, void* row_out, int h
 /* --- field residual ------------------------------------------------------------------------ */
 /* No reference counterpart (the reference's stop rule watches np.mean(u), MRT_GPU.py:883-889): the change of the sampled u and rho
  * between two consecutive samples, reduced on the device to one small record per lattice -- the field residual of a steady run.  The
- * previous sample stays on the device as a snapshot; no field crosses PCIe.  A SAMPLE is the monitor's: exactly the u[2][X][Y],
- * rho[X][Y] that lbm_get_fields(host_dtype) would return right after n steps (same lagged lattice, gather + macros, wall overrides),
- * whatever the kernel route, dtype, operator, arithmetic, closure, semantics, batch or slab.  Every value is first rounded to host_dtype,
- * then converted to double; everything below is computed in double without contraction.
+ * previous sample stays on the device as a snapshot; no field crosses PCIe.  The SAMPLE is the monitor's: the one defined above, of
+ * lbm_get_fields(host_dtype), every value first rounded to host_dtype, then converted to double; everything below is computed in double without contraction.
  *
  * The snapshot holds ux, uy, rho of the previous sample for every own cell; after a sample it holds the current sample's values,
  * bit-preserving, for cells that are not finite too.  (Only the values are specified; the library stores them in the type
@@ -343,26 +350,12 @@ int lbm_get_lines(lbm_ctx* c, int x, int gy, void* col_out, void* row_out, int h
  *                     (an explicit order on (d2, x, y), as the monitor's minimum) -- the first hit of np.argmax on the [X][Y] host array
  *   max_drho2         the maximum of dr2
  *   No cell takes part: max_du2 = max_drho2 = -inf, max_x = max_y = -1.
- * The sums are accumulated in the monitor's fixed tree (lane, wave, workgroup, then the workgroups' partial results in index order)
- * without atomics: identical from run to run, and identical between manual and automatic samples.
+ * Reduced by the tree described above.
  *
- * lbm_residual_begin: allocates the snapshot, the partial results and room for capacity x batch records (here, never inside lbm_step)
- *   and records n0 = lbm_steps_done().  The FIRST sample after it only fills the snapshot; every later sample appends one record and
- *   then replaces the snapshot.  With the buffer full a sample is counted in `dropped`, appends nothing and still refreshes the
- *   snapshot; stepping is unaffected.  every > 0: lbm_step and lbm_time_steps sample by themselves at step counts n0 + every,
- *   n0 + 2 every, ..., from the lattice after n - 1 steps where a launch unit starts there -- the mechanism and the rules of
- *   lbm_stats_begin (a third sampler with its own schedule: the units are cut at the earliest next sample of the three; lbm_step_unit
- *   and the split-step calls refuse; LBM_ERR_STATE on a slab, where every rank calls lbm_residual_sample at the same step counts and the
- *   host combines the records).  every = 0: samples through lbm_residual_sample only.  Calling it again restarts the series.
- *   host_dtype other than LBM_F32 / LBM_F64, every < 0 or capacity < 1: LBM_ERR_INVALID.
- * lbm_residual_sample: one sample of the fields lbm_get_fields would return now.  LBM_ERR_STATE before the first step and while the
- *   residual is off.
- * lbm_residual_read: synchronises; *count = records held, *dropped = samples whose record was not kept;
- *   records_out[min(count, max_records)][batch] receives the oldest records (may be NULL with max_records = 0).  The series goes on.
- *   LBM_ERR_STATE while the residual is off.
- * lbm_residual_end: stops sampling and frees the snapshot and the series.  lbm_init_equilibrium, lbm_set_state and lbm_destroy end
- *   it too; it is not part of a checkpoint.
- * A NULL context is LBM_ERR_INVALID everywhere. */
+ * lbm_residual_begin / _sample / _read / _end: a series of these records with the schedule above; _begin also allocates the snapshot
+ *   and the partial results.  The FIRST sample after _begin only fills the snapshot; every later sample appends one record and then
+ *   replaces the snapshot; a sample that finds the buffer full still refreshes the snapshot.  host_dtype other than LBM_F32 / LBM_F64,
+ *   every < 0 or capacity < 1: LBM_ERR_INVALID. */
 typedef struct lbm_residual_record {
     double step;
     double step_prev;

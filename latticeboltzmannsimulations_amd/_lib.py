@@ -87,8 +87,8 @@ def sources():
 
 
 def build(force=False, verbose=False):
-    """Compile csrc/*.hip for gfx950 into liblbm_hip.so next to this file (in-tree).  The translation units (seven of host code +
-    C ABI: lbm_hip / lbm_plan / lbm_launch / lbm_comm / lbm_monitor / lbm_residual / lbm_topology; the explicit instantiations of the tile and streaming kernels for float and
+    """Compile csrc/*.hip for gfx950 into liblbm_hip.so next to this file (in-tree).  The translation units (eight of host code +
+    C ABI: lbm_hip / lbm_plan / lbm_launch / lbm_comm / lbm_sampling / lbm_monitor / lbm_residual / lbm_topology; the explicit instantiations of the tile and streaming kernels for float and
     for double) are compiled in parallel into csrc/_obj/ and linked."""
     srcs = sources()
     if not force and os.path.exists(LIB_PATH) and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(s) for s in srcs):

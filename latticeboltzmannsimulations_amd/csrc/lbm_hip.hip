@@ -1,5 +1,5 @@
 // lbm_hip.hip -- liblbm_hip.so: context life cycle, state upload, field export and the bandwidth / FMA probes of the C ABI declared
-// in include/lbm.h (the other host units: lbm_plan.hip, lbm_launch.hip, lbm_comm.hip; shared declarations: lbm_host.hpp).
+// in include/lbm.h (the other host units are listed in lbm_host.hpp, which holds the shared declarations).
 // gfx950 only.  See DESIGN.md for the data layout and the per-kernel roofline notes.
 #include "lbm_host.hpp"
 
@@ -150,14 +150,11 @@ int reduce_u(lbm_ctx* c) {
     });
 }
 
-// Statistics off: the sums freed, the schedule cleared (lbm_stats_end, and whatever replaces the state: init / upload / destroy).
-// The caller has synchronised the streams.
-static void stats_free(lbm_ctx* c) {
-    if (c->stats_dev) (void)hipFree(c->stats_dev);
-    c->stats_dev = nullptr;
-    c->stats_count = 0;
-    c->stats_every = 0;
-    c->stats_next = 0;
+// What lbm_init_equilibrium and lbm_set_state share: the three samplers ended, the run state of a fresh lattice in lat[0].  The caller
+// has synchronised the streams.
+static void reset_run_state(lbm_ctx* c) {
+    for (int i = 0; i < NSAMPLERS; ++i) sampler_free(c, i);
+    c->cur = 0; c->raw[0] = 1; c->raw[1] = 1; c->nsteps = 0; c->lag = 0; c->lag_valid = false; c->thin_valid = false;
 }
 }  // namespace lbmhost
 
@@ -241,9 +238,8 @@ void lbm_destroy(lbm_ctx* c) {
     for (int i = 0; i < NLAT; ++i)
         if (c->lat[i]) (void)hipFree(c->lat[i]);
     if (c->red_dev) (void)hipFree(c->red_dev);
-    stats_free(c);
+    for (int i = 0; i < NSAMPLERS; ++i) sampler_free(c, i);
     monitor_free(c);
-    residual_free(c);
     topology_free(c);
     if (c->stage) (void)hipFree(c->stage);
     if (c->relax_dev) (void)hipFree(c->relax_dev);
@@ -265,10 +261,7 @@ int lbm_init_equilibrium(lbm_ctx* c) {
     HIP_TRY(c, hipSetDevice(c->p.device));
     int rc = sync_all(c);
     if (rc) return rc;
-    stats_free(c);
-    monitor_series_free(c);
-    residual_free(c);
-    c->cur = 0; c->raw[0] = 1; c->raw[1] = 1; c->nsteps = 0; c->lag = 0; c->lag_valid = false; c->thin_valid = false;
+    reset_run_state(c);
     const dim3 g = grid_rows(c, c->plan.geo.ny);
     rc = launch_variant(c, [&](auto v) {
         using VT = decltype(v);
@@ -288,10 +281,7 @@ int lbm_set_state(lbm_ctx* c, const void* fin_host, int host_dtype) {
     if (rc) return rc;
     rc = host_to_stage(c, fin_host, host_dtype, Q * c->plan.batch);   // [B][9][nx][ny] is B * 9 planes
     if (rc) return rc;
-    stats_free(c);
-    monitor_series_free(c);
-    residual_free(c);
-    c->cur = 0; c->raw[0] = 1; c->raw[1] = 1; c->nsteps = 0; c->lag = 0; c->lag_valid = false; c->thin_valid = false;
+    reset_run_state(c);
     rc = launch_variant(c, [&](auto v) {
         using VT = decltype(v);
         using R = typename VT::R;
@@ -398,76 +388,6 @@ int lbm_get_tau(lbm_ctx* c, void* tau_host, int host_dtype) {
     if (rc) return rc;
     HIP_TRY(c, hipStreamSynchronize(c->s_compute));
     return stage_to_host(c, c->stage, tau_host, host_dtype, c->plan.batch);
-}
-
-int lbm_stats_begin(lbm_ctx* c, int every) {
-    if (!c || every < 0) return fail(c, LBM_ERR_INVALID, "lbm_stats_begin: bad argument");
-    if (every > 0 && is_slab(c->plan))
-        return fail(c, LBM_ERR_STATE, "lbm_stats_begin: no automatic sampling on a slab (every = 0, and lbm_stats_sample at the same step "
-                                      "counts on every slab)");
-    HIP_TRY(c, hipSetDevice(c->p.device));
-    int rc = sync_all(c);
-    if (rc) return rc;
-    const size_t bytes = (size_t)c->plan.batch * 6 * c->plan.geo.ny * (2 * ((c->plan.geo.nx + 1) / 2)) * sizeof(double);
-    if (!c->stats_dev) {
-        hipError_t e = hipMalloc((void**)&c->stats_dev, bytes);
-        if (e != hipSuccess) {
-            c->stats_dev = nullptr;
-            return fail(c, LBM_ERR_NOMEM, std::string("hipMalloc(statistics): ") + hipGetErrorString(e));
-        }
-    }
-    HIP_TRY(c, hipMemsetAsync(c->stats_dev, 0, bytes, c->s_compute));
-    c->stats_count = 0;
-    c->stats_every = every;
-    c->stats_next = c->nsteps + every;
-    return LBM_OK;
-}
-
-int lbm_stats_sample(lbm_ctx* c) {
-    if (!c) return LBM_ERR_INVALID;
-    if (!c->stats_dev) return fail(c, LBM_ERR_STATE, "lbm_stats_sample: statistics are off (lbm_stats_begin)");
-    if (c->nsteps == 0) return fail(c, LBM_ERR_STATE, "lbm_stats_sample: no step yet (the fields of an iteration exist after it)");
-    HIP_TRY(c, hipSetDevice(c->p.device));
-    int rc = sync_all(c);
-    if (rc) return rc;
-    int which = 0;
-    rc = prev_lattice(c, &which);   // (what lbm_get_fields exports: the lattice the last iteration started from)
-    if (rc) return rc;
-    return stats_accumulate(c, which);
-}
-
-int lbm_stats_get(lbm_ctx* c, double* mean_u, double* mean_rho, double* second, long long* count) {
-    if (!c) return LBM_ERR_INVALID;
-    if (!c->stats_dev) return fail(c, LBM_ERR_STATE, "lbm_stats_get: statistics are off (lbm_stats_begin)");
-    HIP_TRY(c, hipSetDevice(c->p.device));
-    int rc = sync_all(c);
-    if (rc) return rc;
-    if (count) *count = c->stats_count;
-    if (c->stats_count == 0) return LBM_OK;
-    const int nx = c->plan.geo.nx, ny = c->plan.geo.ny, NY = c->plan.geo.NY, y0 = c->plan.geo.y0, nxa = 2 * ((nx + 1) / 2);
-    const size_t hn = (size_t)nx * NY, dn = (size_t)ny * nxa;
-    const double n = (double)c->stats_count;
-    std::vector<double> pl(dn);
-    for (int b = 0; b < c->plan.batch; ++b)
-        for (int q = 0; q < 6; ++q) {   // device [b][q][y][x] -> host [b][2][x][Y] (u), [b][x][Y] (rho), [b][3][x][Y] (second moments)
-            double* dst = q < 2 ? (mean_u ? mean_u + ((size_t)b * 2 + q) * hn : nullptr)
-                        : q == 2 ? (mean_rho ? mean_rho + (size_t)b * hn : nullptr)
-                                 : (second ? second + ((size_t)b * 3 + q - 3) * hn : nullptr);
-            if (!dst) continue;
-            HIP_TRY(c, hipMemcpy(pl.data(), c->stats_dev + ((size_t)b * 6 + q) * dn, dn * sizeof(double), hipMemcpyDeviceToHost));
-            for (int x = 0; x < nx; ++x)
-                for (int y = 0; y < ny; ++y) dst[(size_t)x * NY + y0 + y] = pl[(size_t)y * nxa + x] / n;
-        }
-    return LBM_OK;
-}
-
-int lbm_stats_end(lbm_ctx* c) {
-    if (!c) return LBM_ERR_INVALID;
-    HIP_TRY(c, hipSetDevice(c->p.device));
-    const int rc = sync_all(c);
-    if (rc) return rc;
-    stats_free(c);
-    return LBM_OK;
 }
 
 int lbm_copy_bandwidth(lbm_ctx* c, size_t bytes, int iters, double* gbps) {

@@ -4,8 +4,11 @@
 //   lbm_hip.hip     context life cycle, state upload / field export, probes              (C ABI: create .. get_tau, probes)
 //   lbm_plan.hip    parameter validation, launch planning, unit sequence, the dry run    (C ABI: next_unit, describe, plan)
 //   lbm_launch.hip  kernel launches and the step loop (single / multi-step units, lag)   (C ABI: step*, time_steps)
+//   lbm_sampling.hip what the samplers share (schedule: lbm_schedule.hpp; record series; the sampling prologue), the time statistics
+//                                                                                          (C ABI: stats_*)
 //   lbm_comm.hip    RCCL binding, halo exchanges, host-transported halos                 (C ABI: halo_*, comm_*)
 //   lbm_monitor.hip the run monitor and the line export (kernels: lbm_monitor.hpp)        (C ABI: monitor*, get_lines)
+//   lbm_residual.hip the field residual (kernels: lbm_residual.hpp)                        (C ABI: residual_*)
 //   lbm_topology.hip stream function, vorticity, extrema of psi (kernels: lbm_topology.hpp) (C ABI: topology, get_stream_function)
 #pragma once
 #include <hip/hip_runtime.h>
@@ -23,6 +26,7 @@
 #include <vector>
 
 #include "../../include/lbm.h"
+#include "lbm_schedule.hpp"
 #include "lbm_inst.hpp"   // the kernels, and extern template declarations of the multi-step ones (compiled in lbm_{tiles,stream*}_f32/f64.hip)
 
 // ------------------------------------------------------------------------------------
@@ -78,6 +82,13 @@ struct Plan {
     bool comm_priority = true;  // the halo exchange stream at the highest priority (A/B: LBM_FLAG_COMM_PRIORITY_OFF, the compute stream's)
 };
 
+// The records of a series on the device, [capacity][batch], and how many samples it holds and has dropped (series_* in lbm_sampling.hip).
+struct Series {
+    void* dev = nullptr;
+    size_t sample_bytes = 0;    // one sample: the records of the batch
+    long long capacity = 0, count = 0, dropped = 0;
+};
+
 // Run state.  What was decided once is in `plan`; p stays for the fields later code branches on (dtype, collision, semantics, turb,
 // arith, device) and for the relaxation rates, which lbm_set_relaxation rewrites.
 struct lbm_ctx {
@@ -99,32 +110,25 @@ struct lbm_ctx {
     void* stage = nullptr;
     size_t stage_bytes = 0;
     double* red_dev = nullptr;  // lbm_mean_u: partial sums + results
-    // Time statistics (lbm_stats_*): six double sums per cell (k_stats_accumulate), null while statistics are off.  Automatic sampling
-    // (stats_every > 0) takes the sample of step count n = stats_next from lat[cur] when a unit would start at n - 1 (step_many).
+    // The samplers (lbm_sampling.hip).  sampler[i]: the schedule of automatic sampling, which takes the sample of step count n from
+    // lat[cur] when a unit would start at n - 1 (step_many); a Series: the records of a series on the device, null while it is off.
+    lbmhost::Sampler sampler[lbmhost::NSAMPLERS];
+    // Time statistics (lbm_stats_*): six double sums per cell (k_stats_accumulate), null while statistics are off.
     double* stats_dev = nullptr;
     long long stats_count = 0;  // samples enqueued
-    int stats_every = 0;
-    long long stats_next = 0;
     // Run monitor (lbm_monitor*, lbm_monitor.hip): mon_part holds the workgroups' partial results of one pass and, behind them, the
-    // records of the one-shot call (allocated on first use, kept); mon_series the records of a series, [capacity][batch], null while
-    // no series is on.  Automatic sampling (mon_every > 0) cuts the units like the statistics do (step_many).
+    // records of the one-shot call (allocated on first use, kept).
     double* mon_part = nullptr;
-    lbm_monitor_record* mon_series = nullptr;
+    Series mon_series;
     lbm_monitor_spec mon_spec{};
-    long long mon_capacity = 0, mon_count = 0, mon_dropped = 0;
-    int mon_every = 0;
-    long long mon_next = 0;
     // Field residual (lbm_residual_*, lbm_residual.hip): res_snap holds the previous sample (ux, uy, rho of every own cell, in the type
-    // lbm_get_fields(res_host_dtype) hands out), res_part the workgroups' partial results of one pass, res_series the records,
-    // [capacity][batch]; all null while the residual is off.  res_prev: the step count of the snapshot (-1: no sample yet).  Automatic
-    // sampling (res_every > 0) cuts the units like the statistics do (step_many).
+    // lbm_get_fields(res_host_dtype) hands out), res_part the workgroups' partial results of one pass; null while the residual is off.
+    // res_prev: the step count of the snapshot (-1: no sample yet).
     void* res_snap = nullptr;
     double* res_part = nullptr;
-    lbm_residual_record* res_series = nullptr;
+    Series res_series;
     int res_host_dtype = LBM_F32;
-    long long res_capacity = 0, res_count = 0, res_dropped = 0, res_prev = -1;
-    int res_every = 0;
-    long long res_next = 0;
+    long long res_prev = -1;
     // Flow topology (lbm_topology, lbm_get_stream_function; lbm_topology.hip): topo_part holds the block sums, the partial results and
     // the records of the record path, topo_fields the staged psi and omega of the field path; each allocated on first use, kept.
     double* topo_part = nullptr;
@@ -360,16 +364,24 @@ int launch_stream_edges(lbm_ctx* c, int from, int to, hipStream_t s, int S, bool
 int warm_stream(lbm_ctx* c);
 int launch_deep(lbm_ctx* c, int from, int to, hipStream_t s, int steps, bool with_frame = false);
 void finish_unit(lbm_ctx* c, int S);
-int stats_accumulate(lbm_ctx* c, int which);
 int single_step(lbm_ctx* c, bool* comm_used, bool rccl_x);
 int multi_step(lbm_ctx* c, bool* comm_used, int S, bool rccl_x);
 int prev_lattice(lbm_ctx* c, int* which);
 int push_step(lbm_ctx* c);
 int push_reset(lbm_ctx* c);
 int step_many(lbm_ctx* c, int nsteps);
+// lbm_sampling.hip
+int series_alloc(lbm_ctx* c, Series& s, size_t record_bytes, int capacity, const char* what);
+void* series_slot(Series& s);
+int series_read(lbm_ctx* c, Series lbm_ctx::*series, const char* call, void* records_out, int max_records, long long* count, long long* dropped);
+void series_free(Series& s);
+int sampler_begin(lbm_ctx* c, int sampler, int every);
+int sample_now(lbm_ctx* c, int sampler, bool on);
+int sample_if_due(lbm_ctx* c);
+void sampler_free(lbm_ctx* c, int sampler);
+int sampler_end(lbm_ctx* c, int sampler);
 // lbm_monitor.hip
 int monitor_series_sample(lbm_ctx* c, int which, long long step);
-void monitor_series_free(lbm_ctx* c);
 void monitor_free(lbm_ctx* c);
 // lbm_topology.hip
 void topology_free(lbm_ctx* c);

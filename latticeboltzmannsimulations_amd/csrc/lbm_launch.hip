@@ -446,54 +446,6 @@ int push_reset(lbm_ctx* c) {
     return LBM_OK;
 }
 
-// One sample of the time statistics from lat[which] (the lattice whose gathered populations are the state the sampled iteration
-// starts from), on the compute stream.
-int stats_accumulate(lbm_ctx* c, int which) {
-    constexpr long long STATS_BLOCKS = 2048;   // grid-stride beyond that (a pure streaming kernel)
-    const long long npairs = (long long)c->plan.geo.ny * ((c->plan.geo.nx + 1) / 2);
-    const int blocks = (int)std::min<long long>((npairs + BLK - 1) / BLK, STATS_BLOCKS);
-    const int rc = launch_variant(c, [&](auto v) {
-        using VT = decltype(v);
-        using R = typename VT::R;
-        hipLaunchKernelGGL((k_stats_accumulate<R, VT::SEM, coll_is_prom(VT::COLL)>), dim3(blocks, 1, c->plan.batch), dim3(BLK), 0, c->s_compute,
-                           (const R*)c->lat[which], c->plan.geo, c->raw[which], (R)c->p.uLB, c->plan.bstride, c->stats_dev);
-    });
-    if (rc) return rc;
-    ++c->stats_count;
-    return LBM_OK;
-}
-
-// Automatic sampling (lbm_stats_begin / lbm_monitor_begin / lbm_residual_begin with every > 0; a lone lattice).  The sample of step count n is the
-// macroscopic state of the lattice after n - 1 steps, so the unit plan is cut where a unit starts at n - 1 and the sample is taken there
-// from lat[cur], with its raw flag: no lag replay.  A call that ends at n - 1 takes it at the start of the next call.  The three samplers
-// keep their own schedules; a step count due for several is read by each of them.
-static int sample_if_due(lbm_ctx* c) {
-    const bool stats_due = c->stats_every > 0 && c->nsteps + 1 == c->stats_next;
-    const bool mon_due = c->mon_every > 0 && c->nsteps + 1 == c->mon_next;
-    const bool res_due = c->res_every > 0 && c->nsteps + 1 == c->res_next;
-    if (!stats_due && !mon_due && !res_due) return LBM_OK;
-    int rc = join_edges(c);   // (frame work of the last unit on the second stream wrote part of lat[cur])
-    if (rc == LBM_OK && stats_due) rc = stats_accumulate(c, c->cur);
-    if (rc == LBM_OK && mon_due) rc = monitor_series_sample(c, c->cur, c->nsteps + 1);
-    if (rc == LBM_OK && res_due) rc = residual_series_sample(c, c->cur, c->nsteps + 1);
-    if (rc) return rc;
-    c->int_stale = true;      // (s_comm must not rewrite lat[cur] before the sample has read it)
-    if (stats_due) c->stats_next += c->stats_every;
-    if (mon_due) c->mon_next += c->mon_every;
-    if (res_due) c->res_next += c->res_every;
-    return LBM_OK;
-}
-
-// steps the unit planner may spend before the next cut: the earliest of the three samplers' next sample (all of them with automatic
-// sampling off)
-static int steps_to_cut(const lbm_ctx* c, int left) {
-    long long n = left;
-    if (c->stats_every > 0) n = std::min<long long>(n, c->stats_next - 1 - c->nsteps);
-    if (c->mon_every > 0) n = std::min<long long>(n, c->mon_next - 1 - c->nsteps);
-    if (c->res_every > 0) n = std::min<long long>(n, c->res_next - 1 - c->nsteps);
-    return (int)n;
-}
-
 int step_many(lbm_ctx* c, int nsteps) {
     if (c->plan.push) {
         for (int i = 0; i < nsteps; ++i) {
@@ -515,7 +467,7 @@ int step_many(lbm_ctx* c, int nsteps) {
     while (left > 0) {
         int rc = sample_if_due(c);
         if (rc) return rc;
-        const int S = unit_steps(c->plan, steps_to_cut(c, left), c->raw[c->cur] != 0, own_transport(c));
+        const int S = unit_steps(c->plan, (int)steps_to_cut(c->sampler, c->nsteps, left), c->raw[c->cur] != 0, own_transport(c));
         rc = S > 1 ? multi_step(c, &comm_used, S, true) : single_step(c, &comm_used, true);
         if (rc) return rc;
         left -= S;
@@ -559,9 +511,8 @@ int lbm_time_steps(lbm_ctx* c, int nsteps, double* ms) {
 int lbm_step_edges(lbm_ctx* c) {
     if (!c) return LBM_ERR_INVALID;
     if (c->plan.push) return fail(c, LBM_ERR_STATE, "the split-step calls do not apply to kernel = PUSH");
-    if (c->stats_every > 0) return fail(c, LBM_ERR_STATE, "automatic sampling (lbm_stats_begin, every > 0) runs inside lbm_step only");
-    if (c->mon_every > 0) return fail(c, LBM_ERR_STATE, "automatic monitoring (lbm_monitor_begin, every > 0) runs inside lbm_step only");
-    if (c->res_every > 0) return fail(c, LBM_ERR_STATE, "the automatic residual (lbm_residual_begin, every > 0) runs inside lbm_step only");
+    if (const char* stem = automatic_sampler(c->sampler))
+        return fail(c, LBM_ERR_STATE, std::string("lbm_step_edges: automatic sampling (") + stem + "_begin, every > 0) runs inside lbm_step only");
     HIP_TRY(c, hipSetDevice(c->p.device));
     return launch_rows(c, c->cur, c->cur ^ 1, 0, c->plan.geo.ny - 1, 2, c->s_compute);
 }
@@ -585,9 +536,8 @@ int lbm_step_unit(lbm_ctx* c, int S) {
     HIP_TRY(c, hipSetDevice(c->p.device));
     if (c->plan.push || c->plan.kern == Kern::none) return fail(c, LBM_ERR_STATE, "lbm_step_unit: this context steps one step per launch (lbm_next_unit() is 1)");
     if (own_transport(c)) return fail(c, LBM_ERR_STATE, "lbm_step_unit: a communicator is attached, lbm_step() moves the halos itself");
-    if (c->stats_every > 0) return fail(c, LBM_ERR_STATE, "lbm_step_unit: automatic sampling (lbm_stats_begin, every > 0) runs inside lbm_step only");
-    if (c->mon_every > 0) return fail(c, LBM_ERR_STATE, "lbm_step_unit: automatic monitoring (lbm_monitor_begin, every > 0) runs inside lbm_step only");
-    if (c->res_every > 0) return fail(c, LBM_ERR_STATE, "lbm_step_unit: the automatic residual (lbm_residual_begin, every > 0) runs inside lbm_step only");
+    if (const char* stem = automatic_sampler(c->sampler))
+        return fail(c, LBM_ERR_STATE, std::string("lbm_step_unit: automatic sampling (") + stem + "_begin, every > 0) runs inside lbm_step only");
     if (c->raw[c->cur]) return fail(c, LBM_ERR_STATE, "lbm_step_unit: the first step after an upload is a single step");
     const bool ok = c->plan.tb_steps == 2 ? S == 2 : (S >= 3 && S <= c->plan.tb_steps);
     if (!ok)

@@ -1,6 +1,6 @@
 // lbm_monitor.hip -- liblbm_hip.so: the run monitor (lbm_monitor, lbm_monitor_begin / _sample / _read / _end) and the export of one
 // column and one row (lbm_get_lines) of the C ABI declared in include/lbm.h.  The kernels are in lbm_monitor.hpp; the automatic
-// samples of a series are taken by step_many (lbm_launch.hip) through monitor_series_sample.  gfx950 only.  DESIGN.md 2.7.
+// samples of a series are taken by sample_if_due (lbm_sampling.hip) through monitor_series_sample.  gfx950 only.  DESIGN.md 2.7.
 #include "lbm_host.hpp"
 #include "lbm_monitor.hpp"
 
@@ -70,34 +70,24 @@ static int monitor_enqueue(lbm_ctx* c, int which, const lbm_monitor_spec& spec, 
         using R = typename VT::R;
         hipLaunchKernelGGL((k_monitor<R, VT::SEM, coll_is_prom(VT::COLL)>), dim3(blocks, 1, c->plan.batch), dim3(BLK), 0, c->s_compute,
                            (const R*)c->lat[which], c->plan.geo, c->raw[which], (R)c->p.uLB, den, c->plan.bstride, sp, c->mon_part);
-        hipLaunchKernelGGL((k_monitor_final<R, VT::SEM, coll_is_prom(VT::COLL)>), dim3(c->plan.batch), dim3(MON_WAVE), 0, c->s_compute,
+        hipLaunchKernelGGL((k_monitor_final<R, VT::SEM, coll_is_prom(VT::COLL)>), dim3(c->plan.batch), dim3(RED_WAVE), 0, c->s_compute,
                            (const double*)c->mon_part, blocks, (const R*)c->lat[which], c->plan.geo, c->raw[which], (R)c->p.uLB, c->plan.bstride, sp,
                            (double)step, (double*)rec);
     });
 }
 
-// The next sample of the series from lat[which]: slot mon_count of the device buffer; a full buffer drops it.
+// The next sample of the series from lat[which], unless its buffer is full.
 int monitor_series_sample(lbm_ctx* c, int which, long long step) {
-    if (c->mon_count >= c->mon_capacity) {
-        ++c->mon_dropped;
-        return LBM_OK;
-    }
-    const int rc = monitor_enqueue(c, which, c->mon_spec, step, c->mon_series + (size_t)c->mon_count * c->plan.batch);
+    void* slot = series_slot(c->mon_series);
+    if (!slot) return LBM_OK;
+    const int rc = monitor_enqueue(c, which, c->mon_spec, step, (lbm_monitor_record*)slot);
     if (rc) return rc;
-    ++c->mon_count;
+    ++c->mon_series.count;
     return LBM_OK;
 }
 
-// Series off (lbm_monitor_end, and whatever replaces the state: init / upload / destroy).  The caller has synchronised the streams.
-void monitor_series_free(lbm_ctx* c) {
-    if (c->mon_series) (void)hipFree(c->mon_series);
-    c->mon_series = nullptr;
-    c->mon_capacity = c->mon_count = c->mon_dropped = 0;
-    c->mon_every = 0;
-    c->mon_next = 0;
-}
+// (lbm_destroy, beside sampler_free)
 void monitor_free(lbm_ctx* c) {
-    monitor_series_free(c);
     if (c->mon_part) (void)hipFree(c->mon_part);
     c->mon_part = nullptr;
 }
@@ -131,61 +121,24 @@ int lbm_monitor_begin(lbm_ctx* c, const lbm_monitor_spec* spec, int every, int c
     if (!c || !spec || every < 0 || capacity < 1) return fail(c, LBM_ERR_INVALID, "lbm_monitor_begin: bad argument");
     const std::string bad = check_spec(c, spec);
     if (!bad.empty()) return fail(c, LBM_ERR_INVALID, "lbm_monitor_begin: " + bad);
-    if (every > 0 && is_slab(c->plan))
-        return fail(c, LBM_ERR_STATE, "lbm_monitor_begin: no automatic sampling on a slab (every = 0, and lbm_monitor_sample at the same step "
-                                      "counts on every slab)");
-    HIP_TRY(c, hipSetDevice(c->p.device));
-    int rc = sync_all(c);
+    int rc = sampler_begin(c, SMP_MONITOR, every);
+    if (rc == LBM_OK) rc = ensure_partials(c);
     if (rc) return rc;
-    rc = ensure_partials(c);
+    sampler_free(c, SMP_MONITOR);
+    rc = series_alloc(c, c->mon_series, sizeof(lbm_monitor_record), capacity, "monitor series");
     if (rc) return rc;
-    monitor_series_free(c);
-    hipError_t e = hipMalloc((void**)&c->mon_series, (size_t)capacity * c->plan.batch * sizeof(lbm_monitor_record));
-    if (e != hipSuccess) {
-        c->mon_series = nullptr;
-        return fail(c, LBM_ERR_NOMEM, std::string("hipMalloc(monitor series): ") + hipGetErrorString(e));
-    }
     c->mon_spec = *spec;
-    c->mon_capacity = capacity;
-    c->mon_every = every;
-    c->mon_next = c->nsteps + every;
+    c->sampler[SMP_MONITOR].arm(c->nsteps, every);
     return LBM_OK;
 }
 
-int lbm_monitor_sample(lbm_ctx* c) {
-    if (!c) return LBM_ERR_INVALID;
-    if (!c->mon_series) return fail(c, LBM_ERR_STATE, "lbm_monitor_sample: no series is on (lbm_monitor_begin)");
-    if (c->nsteps == 0) return fail(c, LBM_ERR_STATE, "lbm_monitor_sample: no step yet (the fields of an iteration exist after it)");
-    HIP_TRY(c, hipSetDevice(c->p.device));
-    int rc = sync_all(c);
-    if (rc) return rc;
-    int which = 0;
-    rc = prev_lattice(c, &which);
-    if (rc) return rc;
-    return monitor_series_sample(c, which, c->nsteps);
-}
+int lbm_monitor_sample(lbm_ctx* c) { return sample_now(c, SMP_MONITOR, c && c->mon_series.dev); }
 
 int lbm_monitor_read(lbm_ctx* c, lbm_monitor_record* records_out, int max_records, long long* count, long long* dropped) {
-    if (!c || max_records < 0 || (max_records > 0 && !records_out)) return fail(c, LBM_ERR_INVALID, "lbm_monitor_read: bad argument");
-    if (!c->mon_series) return fail(c, LBM_ERR_STATE, "lbm_monitor_read: no series is on (lbm_monitor_begin)");
-    HIP_TRY(c, hipSetDevice(c->p.device));
-    const int rc = sync_all(c);
-    if (rc) return rc;
-    if (count) *count = c->mon_count;
-    if (dropped) *dropped = c->mon_dropped;
-    const long long n = std::min<long long>(c->mon_count, max_records);
-    if (n > 0) HIP_TRY(c, hipMemcpy(records_out, c->mon_series, (size_t)n * c->plan.batch * sizeof(lbm_monitor_record), hipMemcpyDeviceToHost));
-    return LBM_OK;
+    return series_read(c, &lbm_ctx::mon_series, "lbm_monitor_read", records_out, max_records, count, dropped);
 }
 
-int lbm_monitor_end(lbm_ctx* c) {
-    if (!c) return LBM_ERR_INVALID;
-    HIP_TRY(c, hipSetDevice(c->p.device));
-    const int rc = sync_all(c);
-    if (rc) return rc;
-    monitor_series_free(c);
-    return LBM_OK;
-}
+int lbm_monitor_end(lbm_ctx* c) { return sampler_end(c, SMP_MONITOR); }
 
 int lbm_get_lines(lbm_ctx* c, int x, int gy, void* col_out, void* row_out, int host_dtype) {
     if (!c || (host_dtype != LBM_F32 && host_dtype != LBM_F64)) return fail(c, LBM_ERR_INVALID, "lbm_get_lines: bad argument");

@@ -4,6 +4,7 @@
 // lbm_monitor.hip alone.
 #pragma once
 #include "lbm_kernels.hpp"
+#include "lbm_reduce.hpp"
 
 // Window, boxes and probes of lbm_monitor_spec, by value in the kernel arguments.
 struct MonSpec {
@@ -14,18 +15,21 @@ struct MonSpec {
     int probe[LBM_MONITOR_MAX_PROBES][2];
 };
 
-// What a lane, a wave, a workgroup and the final pass carry: five sums, the maximum and the (q, x, y) minimum (x < 0: none yet).
+// What a lane, a wave, a workgroup and the final pass carry (an accumulator of lbm_reduce.hpp): five sums, the maximum and the
+// (q, x, y) minimum (x < 0: none yet).
 struct MonAcc {
     double nonfinite, sum_ux, sum_uy, sum_rho, sum_q, max_q, min_q;
     int min_x, min_y;
+    static constexpr int VALS = 9;
+    static __device__ __forceinline__ MonAcc identity() { return MonAcc{0.0, 0.0, 0.0, 0.0, 0.0, -__builtin_inf(), __builtin_inf(), -1, -1}; }
+    static __device__ __forceinline__ void fold(MonAcc& a, const MonAcc& b);   // = mon_fold
+    template <typename F>
+    __device__ __forceinline__ void each(F&& f) {
+        f(nonfinite); f(sum_ux); f(sum_uy); f(sum_rho); f(sum_q); f(max_q); f(min_q); f(min_x); f(min_y);
+    }
 };
-constexpr int MON_VALS = 9;          // doubles of one partial result: the members of MonAcc in order
-constexpr int MON_WAVE = 64;
+constexpr int MON_VALS = MonAcc::VALS;   // doubles of one partial result: the members of MonAcc in order
 constexpr int MON_REC = (int)(sizeof(lbm_monitor_record) / sizeof(double));
-
-__device__ __forceinline__ MonAcc mon_identity() {
-    return MonAcc{0.0, 0.0, 0.0, 0.0, 0.0, -__builtin_inf(), __builtin_inf(), -1, -1};
-}
 
 // Is candidate a the minimum rather than b?  Explicitly on (q, x, y): the device visits the cells x fastest, np.nanargmin on the
 // [X][Y] host array y fastest, so "first seen" would pick another cell among equal q.
@@ -51,48 +55,23 @@ __device__ __forceinline__ void mon_fold(MonAcc& a, const MonAcc& b) {
     mon_take(mon_before(b.min_q, b.min_x, b.min_y, a.min_q, a.min_x, a.min_y), a.min_q, a.min_x, a.min_y, b.min_q, b.min_x, b.min_y);
 }
 
-// wave-64 tree through shuffles: lane 0 ends with the wave's result
-__device__ __forceinline__ void mon_wave_reduce(MonAcc& a) {
-#pragma unroll
-    for (int off = MON_WAVE / 2; off > 0; off >>= 1) {
-        MonAcc b;
-        b.nonfinite = __shfl_down(a.nonfinite, off, MON_WAVE);
-        b.sum_ux = __shfl_down(a.sum_ux, off, MON_WAVE);
-        b.sum_uy = __shfl_down(a.sum_uy, off, MON_WAVE);
-        b.sum_rho = __shfl_down(a.sum_rho, off, MON_WAVE);
-        b.sum_q = __shfl_down(a.sum_q, off, MON_WAVE);
-        b.max_q = __shfl_down(a.max_q, off, MON_WAVE);
-        b.min_q = __shfl_down(a.min_q, off, MON_WAVE);
-        b.min_x = __shfl_down(a.min_x, off, MON_WAVE);
-        b.min_y = __shfl_down(a.min_y, off, MON_WAVE);
-        mon_fold(a, b);
-    }
-}
-
-__device__ __forceinline__ void mon_store(double* __restrict__ p, const MonAcc& a) {
-    p[0] = a.nonfinite; p[1] = a.sum_ux; p[2] = a.sum_uy; p[3] = a.sum_rho; p[4] = a.sum_q; p[5] = a.max_q; p[6] = a.min_q;
-    p[7] = (double)a.min_x; p[8] = (double)a.min_y;
-}
-__device__ __forceinline__ MonAcc mon_load(const double* __restrict__ p) {
-    return MonAcc{p[0], p[1], p[2], p[3], p[4], p[5], p[6], (int)p[7], (int)p[8]};
-}
+__device__ __forceinline__ void MonAcc::fold(MonAcc& a, const MonAcc& b) { mon_fold(a, b); }
 
 // the value lbm_get_fields(host_dtype) would hand out, as a double
 template <typename R>
 __device__ __forceinline__ double mon_value(R v, int host_f32) { return host_f32 ? (double)(float)v : (double)v; }
 
 // The fused monitor pass: grid-stride over the cells of one lattice (blockIdx.z: lattice of the batch), x fastest; per cell the gather +
-// macros of k_export_macro.  Lanes reduce by wave-64 shuffles, the workgroup's four waves through 4 x MON_VALS doubles of LDS; one
-// partial result per workgroup: partial[(blockIdx.z * gridDim.x + blockIdx.x) * MON_VALS ...].  No atomics.  Reads the nine planes
-// once, like k_reduce_u.
+// macros of k_export_macro.  The tree of lbm_reduce.hpp leaves one partial result per workgroup:
+// partial[(blockIdx.z * gridDim.x + blockIdx.x) * MON_VALS ...].  Reads the nine planes once, like k_reduce_u.
 template <typename R, int SEM, bool PROM>
 __global__ __launch_bounds__(BLK) void k_monitor(const R* __restrict__ src, Geo geo, int raw, R uLB, double den, long long bstride, MonSpec sp,
                                                  double* __restrict__ partial) {
 #pragma clang fp contract(off)
-    __shared__ double sh[BLK / MON_WAVE][MON_VALS];
+    __shared__ double sh[BLK / RED_WAVE][MON_VALS];
     src += blockIdx.z * bstride;
     const long long n = (long long)geo.nx * geo.ny;
-    MonAcc a = mon_identity();
+    MonAcc a = MonAcc::identity();
     for (long long i = (long long)blockIdx.x * BLK + threadIdx.x; i < n; i += (long long)gridDim.x * BLK) {
         const int y = (int)(i / geo.nx), x = (int)(i - (long long)y * geo.nx), gy = geo.y0 + y;
         R g[Q], rho, ux, uy;
@@ -115,33 +94,22 @@ __global__ __launch_bounds__(BLK) void k_monitor(const R* __restrict__ src, Geo 
             in = in && !(x >= sp.box[b][0] && x < sp.box[b][1] && gy >= sp.box[b][2] && gy < sp.box[b][3]);
         mon_take(in & mon_before(q, x, gy, a.min_q, a.min_x, a.min_y), a.min_q, a.min_x, a.min_y, q, x, gy);
     }
-    mon_wave_reduce(a);
-    const int wave = threadIdx.x / MON_WAVE;
-    if (threadIdx.x % MON_WAVE == 0) mon_store(sh[wave], a);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < BLK / MON_WAVE; ++w) mon_fold(a, mon_load(sh[w]));
-        mon_store(partial + ((size_t)blockIdx.z * gridDim.x + blockIdx.x) * MON_VALS, a);
-    }
+    red_wave(a);
+    if (red_workgroup<MonAcc, BLK / RED_WAVE>(a, sh)) red_store(partial + ((size_t)blockIdx.z * gridDim.x + blockIdx.x) * MON_VALS, a);
 }
 
-// The final pass, one wave per lattice: lane l folds the partial results l * chunk .. (l + 1) * chunk - 1 in index order, the lanes
-// combine by the same shuffle tree, lane 0 writes the record; lanes 0 .. 7 evaluate the probe cells (gather + macros of the one cell).
-// rec: the records of this sample, [batch].
+// The final pass, one wave per lattice (red_final): lane 0 writes the record; lanes 0 .. 7 evaluate the probe cells (gather + macros
+// of the one cell).  rec: the records of this sample, [batch].
 template <typename R, int SEM, bool PROM>
-__global__ __launch_bounds__(MON_WAVE) void k_monitor_final(const double* __restrict__ partial, int nper, const R* __restrict__ src, Geo geo, int raw,
+__global__ __launch_bounds__(RED_WAVE) void k_monitor_final(const double* __restrict__ partial, int nper, const R* __restrict__ src, Geo geo, int raw,
                                                             R uLB, long long bstride, MonSpec sp, double step, double* __restrict__ rec) {
     const int z = blockIdx.x, lane = threadIdx.x;
     src += z * bstride;
-    partial += (size_t)z * nper * MON_VALS;
     rec += (size_t)z * MON_REC;
-    const int chunk = (nper + MON_WAVE - 1) / MON_WAVE;
-    MonAcc a = mon_identity();
-    for (int i = lane * chunk; i < nper && i < (lane + 1) * chunk; ++i) mon_fold(a, mon_load(partial + (size_t)i * MON_VALS));
-    mon_wave_reduce(a);
+    const MonAcc a = red_final<MonAcc>(partial + (size_t)z * nper * MON_VALS, nper);
     if (lane == 0) {
         rec[0] = step;
-        mon_store(rec + 1, a);
+        red_store(rec + 1, a);
     }
     if (lane < LBM_MONITOR_MAX_PROBES) {
         double v[3] = {__builtin_nan(""), __builtin_nan(""), __builtin_nan("")};

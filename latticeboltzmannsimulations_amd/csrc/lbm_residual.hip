@@ -1,7 +1,7 @@
 // lbm_residual.hip -- liblbm_hip.so: the field residual (lbm_residual_begin / _sample / _read / _end) of the C ABI declared in
 // include/lbm.h: the change of the sampled u and rho between two consecutive samples, reduced on the device to one record per
 // lattice; the previous sample stays on the device as a snapshot.  The kernels are in lbm_residual.hpp; the automatic samples are
-// taken by step_many (lbm_launch.hip) through residual_series_sample.  gfx950 only.  DESIGN.md 2.9.
+// taken by sample_if_due (lbm_sampling.hip) through residual_series_sample.  gfx950 only.  DESIGN.md 2.9.
 #include "lbm_host.hpp"
 #include "lbm_residual.hpp"
 
@@ -21,7 +21,7 @@ static int res_blocks(const lbm_ctx* c) { return (int)std::min<long long>((snap_
 
 // One sample of lat[which] (the lattice whose gathered populations are the state the sampled iteration starts from), on the compute
 // stream: the pass that compares with the snapshot and replaces it; then, unless this is the series' first sample or its buffer is
-// full, the final pass into slot res_count.
+// full, the final pass into the series' next slot.
 int residual_series_sample(lbm_ctx* c, int which, long long step) {
     const int blocks = res_blocks(c);
     const int rc = launch_variant(c, [&](auto v) {
@@ -43,29 +43,23 @@ int residual_series_sample(lbm_ctx* c, int which, long long step) {
     const long long prev = c->res_prev;
     c->res_prev = step;
     if (prev < 0) return LBM_OK;   // the first sample only fills the snapshot
-    if (c->res_count >= c->res_capacity) {
-        ++c->res_dropped;
-        return LBM_OK;
-    }
-    hipLaunchKernelGGL(k_residual_final, dim3(c->plan.batch), dim3(RES_WAVE), 0, c->s_compute, (const double*)c->res_part, blocks, (double)step,
-                       (double)prev, (double*)(c->res_series + (size_t)c->res_count * c->plan.batch));
+    void* slot = series_slot(c->res_series);
+    if (!slot) return LBM_OK;
+    hipLaunchKernelGGL(k_residual_final, dim3(c->plan.batch), dim3(RED_WAVE), 0, c->s_compute, (const double*)c->res_part, blocks, (double)step,
+                       (double)prev, (double*)slot);
     HIP_TRY(c, hipGetLastError());
-    ++c->res_count;
+    ++c->res_series.count;
     return LBM_OK;
 }
 
-// Residual off (lbm_residual_end, and whatever replaces the state: init / upload / destroy).  The caller has synchronised the streams.
+// What lbm_residual_begin allocated (sampler_free).
 void residual_free(lbm_ctx* c) {
     if (c->res_snap) (void)hipFree(c->res_snap);
     if (c->res_part) (void)hipFree(c->res_part);
-    if (c->res_series) (void)hipFree(c->res_series);
+    series_free(c->res_series);
     c->res_snap = nullptr;
     c->res_part = nullptr;
-    c->res_series = nullptr;
-    c->res_capacity = c->res_count = c->res_dropped = 0;
     c->res_prev = -1;
-    c->res_every = 0;
-    c->res_next = 0;
 }
 }  // namespace lbmhost
 
@@ -76,64 +70,31 @@ extern "C" {
 int lbm_residual_begin(lbm_ctx* c, int host_dtype, int every, int capacity) {
     if (!c || (host_dtype != LBM_F32 && host_dtype != LBM_F64) || every < 0 || capacity < 1)
         return fail(c, LBM_ERR_INVALID, "lbm_residual_begin: bad argument");
-    if (every > 0 && is_slab(c->plan))
-        return fail(c, LBM_ERR_STATE, "lbm_residual_begin: no automatic sampling on a slab (every = 0, and lbm_residual_sample at the same step "
-                                      "counts on every slab)");
-    HIP_TRY(c, hipSetDevice(c->p.device));
-    int rc = sync_all(c);
+    int rc = sampler_begin(c, SMP_RESIDUAL, every);
     if (rc) return rc;
-    residual_free(c);
+    sampler_free(c, SMP_RESIDUAL);
     c->res_host_dtype = host_dtype;
     const size_t snap_bytes = (size_t)c->plan.batch * 3 * (size_t)snap_groups(c) * 16;
     const size_t part_bytes = (size_t)c->plan.batch * RES_BLOCKS * RES_VALS * sizeof(double);
-    const size_t series_bytes = (size_t)capacity * c->plan.batch * sizeof(lbm_residual_record);
     hipError_t e = hipMalloc(&c->res_snap, snap_bytes);
     if (e == hipSuccess) e = hipMalloc((void**)&c->res_part, part_bytes);
-    if (e == hipSuccess) e = hipMalloc((void**)&c->res_series, series_bytes);
-    if (e != hipSuccess) {
-        residual_free(c);
-        return fail(c, LBM_ERR_NOMEM, std::string("hipMalloc(residual): ") + hipGetErrorString(e));
+    rc = e == hipSuccess ? series_alloc(c, c->res_series, sizeof(lbm_residual_record), capacity, "residual series")
+                         : fail(c, LBM_ERR_NOMEM, std::string("hipMalloc(residual): ") + hipGetErrorString(e));
+    if (rc) {
+        sampler_free(c, SMP_RESIDUAL);
+        return rc;
     }
     // (the first sample reads the snapshot like every other and discards what it reduces: give it defined values)
     HIP_TRY(c, hipMemsetAsync(c->res_snap, 0, snap_bytes, c->s_compute));
-    c->res_capacity = capacity;
-    c->res_every = every;
-    c->res_next = c->nsteps + every;
+    c->sampler[SMP_RESIDUAL].arm(c->nsteps, every);
     return LBM_OK;
 }
 
-int lbm_residual_sample(lbm_ctx* c) {
-    if (!c) return LBM_ERR_INVALID;
-    if (!c->res_snap) return fail(c, LBM_ERR_STATE, "lbm_residual_sample: the residual is off (lbm_residual_begin)");
-    if (c->nsteps == 0) return fail(c, LBM_ERR_STATE, "lbm_residual_sample: no step yet (the fields of an iteration exist after it)");
-    HIP_TRY(c, hipSetDevice(c->p.device));
-    int rc = sync_all(c);
-    if (rc) return rc;
-    int which = 0;
-    rc = prev_lattice(c, &which);   // (what lbm_get_fields exports: the lattice the last iteration started from)
-    if (rc) return rc;
-    return residual_series_sample(c, which, c->nsteps);
-}
+int lbm_residual_sample(lbm_ctx* c) { return sample_now(c, SMP_RESIDUAL, c && c->res_snap); }
 
 int lbm_residual_read(lbm_ctx* c, lbm_residual_record* records_out, int max_records, long long* count, long long* dropped) {
-    if (!c || max_records < 0 || (max_records > 0 && !records_out)) return fail(c, LBM_ERR_INVALID, "lbm_residual_read: bad argument");
-    if (!c->res_snap) return fail(c, LBM_ERR_STATE, "lbm_residual_read: the residual is off (lbm_residual_begin)");
-    HIP_TRY(c, hipSetDevice(c->p.device));
-    const int rc = sync_all(c);
-    if (rc) return rc;
-    if (count) *count = c->res_count;
-    if (dropped) *dropped = c->res_dropped;
-    const long long n = std::min<long long>(c->res_count, max_records);
-    if (n > 0) HIP_TRY(c, hipMemcpy(records_out, c->res_series, (size_t)n * c->plan.batch * sizeof(lbm_residual_record), hipMemcpyDeviceToHost));
-    return LBM_OK;
+    return series_read(c, &lbm_ctx::res_series, "lbm_residual_read", records_out, max_records, count, dropped);
 }
 
-int lbm_residual_end(lbm_ctx* c) {
-    if (!c) return LBM_ERR_INVALID;
-    HIP_TRY(c, hipSetDevice(c->p.device));
-    const int rc = sync_all(c);
-    if (rc) return rc;
-    residual_free(c);
-    return LBM_OK;
-}
+int lbm_residual_end(lbm_ctx* c) { return sampler_end(c, SMP_RESIDUAL); }
 }  // extern "C"

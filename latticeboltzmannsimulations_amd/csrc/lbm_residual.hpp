@@ -1,25 +1,27 @@
 // lbm_residual.hpp -- kernels of the field residual (lbm_residual_*; contract in include/lbm.h): one streaming pass over the lattice
 // that forms the macroscopic state k_export_macro would export, compares it with the snapshot of the previous sample, replaces the
 // snapshot and reduces the differences to nine numbers per workgroup; a small kernel that folds the workgroups' results, in index
-// order, into the record.  The reduction is the monitor's tree (lane, wave-64 shuffles, the workgroup's waves through LDS, one
-// partial result per workgroup, no atomics).  Included by lbm_residual.hip alone.
+// order, into the record.  The reduction is the tree of lbm_reduce.hpp.  Included by lbm_residual.hip alone.
 #pragma once
 #include "lbm_kernels.hpp"
+#include "lbm_reduce.hpp"
 
-// What a lane, a wave, a workgroup and the final pass carry: two counts, three sums, the (d2, x, y) maximum (x < 0: none yet) and the
-// maximum of dr2.
+// What a lane, a wave, a workgroup and the final pass carry (an accumulator of lbm_reduce.hpp): two counts, three sums, the
+// (d2, x, y) maximum (x < 0: none yet) and the maximum of dr2.
 struct ResAcc {
     double cells, nonfinite, sum_du2, sum_u2, sum_drho2, max_du2;
     int max_x, max_y;
     double max_drho2;
+    static constexpr int VALS = 9;
+    static __device__ __forceinline__ ResAcc identity() { return ResAcc{0.0, 0.0, 0.0, 0.0, 0.0, -__builtin_inf(), -1, -1, -__builtin_inf()}; }
+    static __device__ __forceinline__ void fold(ResAcc& a, const ResAcc& b);   // = res_fold
+    template <typename F>
+    __device__ __forceinline__ void each(F&& f) {
+        f(cells); f(nonfinite); f(sum_du2); f(sum_u2); f(sum_drho2); f(max_du2); f(max_x); f(max_y); f(max_drho2);
+    }
 };
-constexpr int RES_VALS = 9;          // doubles of one partial result: the members of ResAcc in order
-constexpr int RES_WAVE = 64;
+constexpr int RES_VALS = ResAcc::VALS;   // doubles of one partial result: the members of ResAcc in order
 constexpr int RES_REC = (int)(sizeof(lbm_residual_record) / sizeof(double));
-
-__device__ __forceinline__ ResAcc res_identity() {
-    return ResAcc{0.0, 0.0, 0.0, 0.0, 0.0, -__builtin_inf(), -1, -1, -__builtin_inf()};
-}
 
 // Is candidate a the maximum rather than b?  Explicitly on (d2, x, y): the larger d2, then the smaller x, then the smaller y -- the
 // first hit of np.argmax on the [X][Y] host array, whatever order the device visits the cells in.
@@ -42,31 +44,7 @@ __device__ __forceinline__ void res_fold(ResAcc& a, const ResAcc& b) {
     a.max_drho2 = b.max_drho2 > a.max_drho2 ? b.max_drho2 : a.max_drho2;
 }
 
-// wave-64 tree through shuffles: lane 0 ends with the wave's result
-__device__ __forceinline__ void res_wave_reduce(ResAcc& a) {
-#pragma unroll
-    for (int off = RES_WAVE / 2; off > 0; off >>= 1) {
-        ResAcc b;
-        b.cells = __shfl_down(a.cells, off, RES_WAVE);
-        b.nonfinite = __shfl_down(a.nonfinite, off, RES_WAVE);
-        b.sum_du2 = __shfl_down(a.sum_du2, off, RES_WAVE);
-        b.sum_u2 = __shfl_down(a.sum_u2, off, RES_WAVE);
-        b.sum_drho2 = __shfl_down(a.sum_drho2, off, RES_WAVE);
-        b.max_du2 = __shfl_down(a.max_du2, off, RES_WAVE);
-        b.max_x = __shfl_down(a.max_x, off, RES_WAVE);
-        b.max_y = __shfl_down(a.max_y, off, RES_WAVE);
-        b.max_drho2 = __shfl_down(a.max_drho2, off, RES_WAVE);
-        res_fold(a, b);
-    }
-}
-
-__device__ __forceinline__ void res_store(double* __restrict__ p, const ResAcc& a) {
-    p[0] = a.cells; p[1] = a.nonfinite; p[2] = a.sum_du2; p[3] = a.sum_u2; p[4] = a.sum_drho2; p[5] = a.max_du2;
-    p[6] = (double)a.max_x; p[7] = (double)a.max_y; p[8] = a.max_drho2;
-}
-__device__ __forceinline__ ResAcc res_load(const double* __restrict__ p) {
-    return ResAcc{p[0], p[1], p[2], p[3], p[4], p[5], (int)p[6], (int)p[7], p[8]};
-}
+__device__ __forceinline__ void ResAcc::fold(ResAcc& a, const ResAcc& b) { res_fold(a, b); }
 
 // The snapshot: three planes [ux | uy | rho] per lattice, each [ny_local][nxa], x fastest, nxa = nx rounded up to a whole number of
 // lane groups; element type S = the type lbm_get_fields(host_dtype) hands out (float unless lattice and host_dtype are both double), so
@@ -89,12 +67,12 @@ __global__ __launch_bounds__(BLK) void k_residual(const R* __restrict__ src, Geo
 #pragma clang fp contract(off)
     constexpr int CPL = ResGroup<S>::CPL;
     typedef typename ResGroup<S>::vec vec;
-    __shared__ double sh[BLK / RES_WAVE][RES_VALS];
+    __shared__ double sh[BLK / RED_WAVE][RES_VALS];
     const int nxg = (geo.nx + CPL - 1) / CPL;
     const long long ngroups = (long long)geo.ny * nxg;   // = the elements of one plane / CPL
     src += blockIdx.z * bstride;
     vec* sn = (vec*)snap + blockIdx.z * 3 * ngroups;
-    ResAcc a = res_identity();
+    ResAcc a = ResAcc::identity();
     for (long long i = (long long)blockIdx.x * BLK + threadIdx.x; i < ngroups; i += (long long)gridDim.x * BLK) {
         const int y = (int)(i / nxg), x = CPL * (int)(i - (long long)y * nxg), gy = geo.y0 + y;
         const vec pu = sn[i], pv = sn[ngroups + i], pr = sn[2 * ngroups + i];
@@ -132,30 +110,19 @@ __global__ __launch_bounds__(BLK) void k_residual(const R* __restrict__ src, Geo
         }
         sn[i] = cu; sn[ngroups + i] = cv; sn[2 * ngroups + i] = cr;
     }
-    res_wave_reduce(a);
-    const int wave = threadIdx.x / RES_WAVE;
-    if (threadIdx.x % RES_WAVE == 0) res_store(sh[wave], a);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < BLK / RES_WAVE; ++w) res_fold(a, res_load(sh[w]));
-        res_store(partial + ((size_t)blockIdx.z * gridDim.x + blockIdx.x) * RES_VALS, a);
-    }
+    red_wave(a);
+    if (red_workgroup<ResAcc, BLK / RED_WAVE>(a, sh)) red_store(partial + ((size_t)blockIdx.z * gridDim.x + blockIdx.x) * RES_VALS, a);
 }
 
-// The final pass, one wave per lattice: lane l folds the partial results l * chunk .. (l + 1) * chunk - 1 in index order, the lanes
-// combine by the same shuffle tree, lane 0 writes the record.  rec: the records of this sample, [batch].
-__global__ __launch_bounds__(RES_WAVE) void k_residual_final(const double* __restrict__ partial, int nper, double step, double step_prev,
+// The final pass, one wave per lattice (red_final): lane 0 writes the record.  rec: the records of this sample, [batch].
+__global__ __launch_bounds__(RED_WAVE) void k_residual_final(const double* __restrict__ partial, int nper, double step, double step_prev,
                                                              double* __restrict__ rec) {
-    const int z = blockIdx.x, lane = threadIdx.x;
-    partial += (size_t)z * nper * RES_VALS;
+    const int z = blockIdx.x;
     rec += (size_t)z * RES_REC;
-    const int chunk = (nper + RES_WAVE - 1) / RES_WAVE;
-    ResAcc a = res_identity();
-    for (int i = lane * chunk; i < nper && i < (lane + 1) * chunk; ++i) res_fold(a, res_load(partial + (size_t)i * RES_VALS));
-    res_wave_reduce(a);
-    if (lane == 0) {
+    const ResAcc a = red_final<ResAcc>(partial + (size_t)z * nper * RES_VALS, nper);
+    if (threadIdx.x == 0) {
         rec[0] = step;
         rec[1] = step_prev;
-        res_store(rec + 2, a);
+        red_store(rec + 2, a);
     }
 }

@@ -5,8 +5,8 @@
 //   k_topo_totals    a workgroup takes TOPO_ROWS rows x one block of LBM_TOPOLOGY_BLOCK cells of x, plus the cell to its left: the
 //                    gather runs along x (coalesced), uy goes to LDS as doubles, one thread per row sums the block's terms in order
 //   k_topo_offsets   one thread per row: the exclusive scan of the row's block totals, in order, and |psi| at the right wall
-//   k_topo_extrema   the same tile and the same in-order sums, psi = -(off + within); per window the candidates go lane -> wave
-//                    (shuffles) -> workgroup (LDS) -> one partial result per workgroup; FIELDS: psi leaves the tile in host layout
+//   k_topo_extrema   the same tile and the same in-order sums, psi = -(off + within); per window the candidates go through the tree of
+//                    lbm_reduce.hpp to one partial result per workgroup; FIELDS: psi leaves the tile in host layout
 //   k_topo_final     one workgroup per (window, lattice) folds the partial results and evaluates omega at the two extrema
 //   k_topo_omega     the omega field from the staged u of the export path, one thread per cell
 // Minimum and maximum are taken by a total order on (psi, x, y), so no result depends on the shape of a tree or on scheduling.
@@ -47,18 +47,22 @@ __device__ __forceinline__ void topo_fold(TopoCand& a, const TopoCand& b) {
     a.x = take ? b.x : a.x;
     a.y = take ? b.y : a.y;
 }
-template <bool MAX>
-__device__ __forceinline__ void topo_wave_reduce(TopoCand& a) {
-#pragma unroll
-    for (int off = MON_WAVE / 2; off > 0; off >>= 1) {
-        TopoCand b;
-        b.psi = __shfl_down(a.psi, off, MON_WAVE);
-        b.x = __shfl_down(a.x, off, MON_WAVE);
-        b.y = __shfl_down(a.y, off, MON_WAVE);
-        topo_fold<MAX>(a, b);
-    }
-}
 __device__ __forceinline__ TopoCand topo_none(bool max) { return TopoCand{max ? -__builtin_inf() : __builtin_inf(), -1, -1}; }
+
+// The minimum and the maximum side by side, an accumulator of lbm_reduce.hpp: the six doubles of a partial result.
+struct TopoPair {
+    TopoCand lo, hi;
+    static constexpr int VALS = TOPO_PART;
+    static __device__ __forceinline__ TopoPair identity() { return TopoPair{topo_none(false), topo_none(true)}; }
+    static __device__ __forceinline__ void fold(TopoPair& a, const TopoPair& b) {
+        topo_fold<false>(a.lo, b.lo);
+        topo_fold<true>(a.hi, b.hi);
+    }
+    template <typename F>
+    __device__ __forceinline__ void each(F&& f) {
+        f(lo.psi); f(lo.x); f(lo.y); f(hi.psi); f(hi.x); f(hi.y);
+    }
+};
 
 // ux, uy of cell (x, y) as lbm_get_fields(host_dtype) hands them out, in double
 template <typename R, int SEM, bool PROM>
@@ -150,7 +154,7 @@ template <typename R, int SEM, bool PROM, bool FIELDS>
 __global__ __launch_bounds__(BLK) void k_topo_extrema(const R* __restrict__ src, Geo geo, int raw, R uLB, long long bstride, TopoSpec sp,
                                                      const double* __restrict__ offs, double* __restrict__ partial, double* __restrict__ psi_out) {
     __shared__ double u[TOPO_ROWS][TOPO_PITCH];
-    __shared__ double sh[BLK / MON_WAVE][TOPO_PART];
+    __shared__ double sh[BLK / RED_WAVE][TOPO_PART];
     src += blockIdx.z * bstride;
     const int x0 = blockIdx.x * TOPO_W, ty0 = blockIdx.y * TOPO_ROWS, w = min(TOPO_W, geo.nx - x0), h = min(TOPO_ROWS, geo.ny - ty0);
     topo_tile_load<R, SEM, PROM>(src, geo, raw, uLB, sp.host_f32, x0, ty0, u);
@@ -164,35 +168,22 @@ __global__ __launch_bounds__(BLK) void k_topo_extrema(const R* __restrict__ src,
         if (r < h)
             for (int j = threadIdx.x / TOPO_ROWS; j < w; j += BLK / TOPO_ROWS) psi_out[(size_t)(x0 + j) * geo.ny + ty0 + r] = u[r][j];
     }
-    const int nwg = gridDim.x * gridDim.y, wg = blockIdx.y * gridDim.x + blockIdx.x, wave = threadIdx.x / MON_WAVE;
+    const int nwg = gridDim.x * gridDim.y, wg = blockIdx.y * gridDim.x + blockIdx.x;
     for (int i = 0; i < sp.nwindows; ++i) {   // (uniform: every thread of the workgroup takes the same trips)
         const int xa = max(sp.win[i][0], x0), xb = min(sp.win[i][1], x0 + w), ya = max(sp.win[i][2], ty0), yb = min(sp.win[i][3], ty0 + h);
-        TopoCand lo = topo_none(false), hi = topo_none(true);
+        TopoPair e = TopoPair::identity();
         if (xa < xb && ya < yb) {
             for (int t = threadIdx.x; t < TOPO_ROWS * TOPO_W; t += BLK) {
                 const int r = t / TOPO_W, j = t % TOPO_W, x = x0 + j, y = ty0 + r;
                 if (x < xa || x >= xb || y < ya || y >= yb) continue;
                 const TopoCand c{u[r][j], x, y};
                 if (!__builtin_isfinite(c.psi)) continue;
-                topo_fold<false>(lo, c);
-                topo_fold<true>(hi, c);
+                TopoPair::fold(e, TopoPair{c, c});
             }
-            topo_wave_reduce<false>(lo);
-            topo_wave_reduce<true>(hi);
+            red_wave(e);
         }
-        if (threadIdx.x % MON_WAVE == 0) {
-            double* s = sh[wave];
-            s[0] = lo.psi; s[1] = (double)lo.x; s[2] = (double)lo.y; s[3] = hi.psi; s[4] = (double)hi.x; s[5] = (double)hi.y;
-        }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            for (int v = 1; v < BLK / MON_WAVE; ++v) {
-                topo_fold<false>(lo, TopoCand{sh[v][0], (int)sh[v][1], (int)sh[v][2]});
-                topo_fold<true>(hi, TopoCand{sh[v][3], (int)sh[v][4], (int)sh[v][5]});
-            }
-            double* p = partial + (((size_t)blockIdx.z * LBM_TOPOLOGY_MAX_WINDOWS + i) * nwg + wg) * TOPO_PART;
-            p[0] = lo.psi; p[1] = (double)lo.x; p[2] = (double)lo.y; p[3] = hi.psi; p[4] = (double)hi.x; p[5] = (double)hi.y;
-        }
+        if (red_workgroup<TopoPair, BLK / RED_WAVE>(e, sh))
+            red_store(partial + (((size_t)blockIdx.z * LBM_TOPOLOGY_MAX_WINDOWS + i) * nwg + wg) * TOPO_PART, e);
         __syncthreads();
     }
 }
@@ -217,8 +208,8 @@ __device__ __forceinline__ double topo_omega_at(const R* __restrict__ src, const
 template <typename R, int SEM, bool PROM>
 __global__ __launch_bounds__(BLK) void k_topo_final(const double* __restrict__ partial, int nwg, const double* __restrict__ close, const R* __restrict__ src,
                                                    Geo geo, int raw, R uLB, long long bstride, TopoSpec sp, double step, double* __restrict__ rec) {
-    __shared__ double sh[BLK / MON_WAVE][TOPO_PART + 1];
-    const int i = blockIdx.x, z = blockIdx.y, wave = threadIdx.x / MON_WAVE;
+    __shared__ double sh[BLK / RED_WAVE][TOPO_PART + 1];
+    const int i = blockIdx.x, z = blockIdx.y, wave = threadIdx.x / RED_WAVE;
     src += z * bstride;
     rec += (size_t)z * TOPO_REC;
     double* out = rec + 2 + 8 * i;   // min {psi, x, y, omega}, max {psi, x, y, omega}
@@ -228,12 +219,8 @@ __global__ __launch_bounds__(BLK) void k_topo_final(const double* __restrict__ p
         if (i > 0) return;   // (a spec without windows: the workgroup of window 0 still writes step and closure)
     }
     const double* p = partial + ((size_t)z * LBM_TOPOLOGY_MAX_WINDOWS + i) * nwg * TOPO_PART;
-    TopoCand lo = topo_none(false), hi = topo_none(true);
-    for (int k = threadIdx.x; used && k < nwg; k += BLK) {
-        const double* q = p + (size_t)k * TOPO_PART;
-        topo_fold<false>(lo, TopoCand{q[0], (int)q[1], (int)q[2]});
-        topo_fold<true>(hi, TopoCand{q[3], (int)q[4], (int)q[5]});
-    }
+    TopoPair e = TopoPair::identity();
+    for (int k = threadIdx.x; used && k < nwg; k += BLK) TopoPair::fold(e, red_load<TopoPair>(p + (size_t)k * TOPO_PART));
     double cl = -__builtin_inf();
     if (i == 0) {
         close += (size_t)z * geo.ny;
@@ -242,22 +229,21 @@ __global__ __launch_bounds__(BLK) void k_topo_final(const double* __restrict__ p
             cl = (__builtin_isfinite(v) && v > cl) ? v : cl;
         }
 #pragma unroll
-        for (int off = MON_WAVE / 2; off > 0; off >>= 1) {
-            const double v = __shfl_down(cl, off, MON_WAVE);
+        for (int off = RED_WAVE / 2; off > 0; off >>= 1) {
+            const double v = __shfl_down(cl, off, RED_WAVE);
             cl = v > cl ? v : cl;
         }
     }
-    topo_wave_reduce<false>(lo);
-    topo_wave_reduce<true>(hi);
-    if (threadIdx.x % MON_WAVE == 0) {
-        double* s = sh[wave];
-        s[0] = lo.psi; s[1] = (double)lo.x; s[2] = (double)lo.y; s[3] = hi.psi; s[4] = (double)hi.x; s[5] = (double)hi.y; s[6] = cl;
+    red_wave(e);
+    if (threadIdx.x % RED_WAVE == 0) {
+        red_store(sh[wave], e);
+        sh[wave][TOPO_PART] = cl;
     }
     __syncthreads();
     if (used && threadIdx.x < 2) {   // thread 0: the minimum, thread 1: the maximum
         const int o = 3 * threadIdx.x;
         TopoCand c{sh[0][o], (int)sh[0][o + 1], (int)sh[0][o + 2]};
-        for (int v = 1; v < BLK / MON_WAVE; ++v) {
+        for (int v = 1; v < BLK / RED_WAVE; ++v) {
             const TopoCand b{sh[v][o], (int)sh[v][o + 1], (int)sh[v][o + 2]};
             if (threadIdx.x == 0) topo_fold<false>(c, b); else topo_fold<true>(c, b);
         }
@@ -266,7 +252,7 @@ __global__ __launch_bounds__(BLK) void k_topo_final(const double* __restrict__ p
         e[3] = c.x >= 0 ? topo_omega_at<R, SEM, PROM>(src, geo, raw, uLB, sp.host_f32, c.x, c.y) : __builtin_nan("");
     }
     if (i == 0 && threadIdx.x == 0) {
-        for (int v = 1; v < BLK / MON_WAVE; ++v) cl = sh[v][6] > cl ? sh[v][6] : cl;
+        for (int v = 1; v < BLK / RED_WAVE; ++v) cl = sh[v][TOPO_PART] > cl ? sh[v][TOPO_PART] : cl;
         rec[0] = step;
         rec[1] = cl;
     }

@@ -124,14 +124,21 @@ def make_spec(X, Y, host_dtype, window=None, exclude=(), probes=()):
     return s
 
 
+def fields_to_dict(buf, shape, doubles, names, integers):
+    """An array of records (ctypes) of `doubles` float64 each -> (a, out): the float64 array of shape + (doubles,) and the dict of
+    its leading fields `names` as arrays of `shape`, those of `integers` as int64.  Shared with residual.records_to_dict."""
+    full = tuple(shape) + (doubles,)
+    a = np.frombuffer(buf, dtype=np.float64).reshape(full).copy() if ctypes.sizeof(buf) else np.zeros(full)
+    out = {k: a[..., i] for i, k in enumerate(names)}
+    for k in integers:
+        out[k] = out[k].astype(np.int64)
+    return a, out
+
+
 def records_to_dict(buf, shape, nprobes):
     """An array of lbm_monitor_record (ctypes) -> dict of float64 arrays of `shape` (probe: shape + (nprobes, 3)); min_x, min_y and
     nonfinite as int64."""
-    a = np.frombuffer(buf, dtype=np.float64).reshape(tuple(shape) + (RECORD_DOUBLES,)).copy() if ctypes.sizeof(buf) else \
-        np.zeros(tuple(shape) + (RECORD_DOUBLES,))
-    out = {k: a[..., i] for i, k in enumerate(SCALARS)}
-    for k in ("step", "nonfinite", "min_x", "min_y"):
-        out[k] = out[k].astype(np.int64)
+    a, out = fields_to_dict(buf, shape, RECORD_DOUBLES, SCALARS, ("step", "nonfinite", "min_x", "min_y"))
     out["probe"] = a[..., len(SCALARS):].reshape(tuple(shape) + (MAX_PROBES, 3))[..., :nprobes, :]
     return out
 

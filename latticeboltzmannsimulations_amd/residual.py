@@ -5,11 +5,10 @@ it keeps on the device, and reduces the differences to a small record per lattic
 NumPy -- the documentation of the contract, the checker the tests compare the device with, and the way to the same numbers for users
 without a GPU.  Everything in a record equals host_residual of two get_fields() results exactly, except the three sums, which depend on
 the order of summation (the device's is a fixed tree, NumPy's pairwise)."""
-import ctypes
-
 import numpy as np
 
 from ._lib import lbm_residual_record  # noqa: F401  (the ctypes mirror of the header's struct)
+from .monitor import fields_to_dict
 
 FIELDS = ("step", "step_prev", "cells", "nonfinite", "sum_du2", "sum_u2", "sum_drho2", "max_du2", "max_x", "max_y", "max_drho2")
 INTEGERS = ("step", "step_prev", "cells", "nonfinite", "max_x", "max_y")
@@ -107,12 +106,7 @@ def below(value, tol):
 # -- the C ABI's struct ---------------------------------------------------------------------
 def records_to_dict(buf, shape):
     """An array of lbm_residual_record (ctypes) -> dict of float64 arrays of `shape`; the counts, steps and the cell as int64."""
-    a = np.frombuffer(buf, dtype=np.float64).reshape(tuple(shape) + (RECORD_DOUBLES,)).copy() if ctypes.sizeof(buf) else \
-        np.zeros(tuple(shape) + (RECORD_DOUBLES,))
-    out = {k: a[..., i] for i, k in enumerate(FIELDS)}
-    for k in INTEGERS:
-        out[k] = out[k].astype(np.int64)
-    return out
+    return fields_to_dict(buf, shape, RECORD_DOUBLES, FIELDS, INTEGERS)[1]
 
 
 def record_at(series, i, b=None):

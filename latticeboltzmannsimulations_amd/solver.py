@@ -336,21 +336,26 @@ class CavitySolver:
         self._check(self.lib.lbm_monitor_sample(self._h), "lbm_monitor_sample")
         return self
 
-    def monitor_series(self):
-        """The series so far (lbm_monitor_read): the keys of monitor() as arrays [count] (a batch: [count, B]; probe: [count(, B),
-        len(probes), 3]), plus count and dropped."""
-        _, nprobes = getattr(self, "_mon", (0, 0))
+    def _series(self, read, record, to_dict):
+        """A record series (lbm_monitor_read / lbm_residual_read) in two calls, the count and then the records: to_dict(records,
+        (count, B)) without the [B] axis of a lone lattice, plus count and dropped."""
         n, dropped = ctypes.c_longlong(0), ctypes.c_longlong(0)
-        self._check(self.lib.lbm_monitor_read(self._h, None, 0, ctypes.byref(n), ctypes.byref(dropped)), "lbm_monitor_read")   # the count
+        self._check(read(self._h, None, 0, ctypes.byref(n), ctypes.byref(dropped)), read.__name__)
         count = int(n.value)
-        rec = (L.lbm_monitor_record * (count * self.batch))()
+        rec = (record * (count * self.batch))()
         if count:
-            self._check(self.lib.lbm_monitor_read(self._h, rec, count, ctypes.byref(n), ctypes.byref(dropped)), "lbm_monitor_read")
-        out = M.records_to_dict(rec, (count, self.batch), nprobes)
+            self._check(read(self._h, rec, count, ctypes.byref(n), ctypes.byref(dropped)), read.__name__)
+        out = to_dict(rec, (count, self.batch))
         if not self._lead:
             out = {k: v[:, 0] for k, v in out.items()}
         out["count"], out["dropped"] = count, int(dropped.value)
         return out
+
+    def monitor_series(self):
+        """The series so far (lbm_monitor_read): the keys of monitor() as arrays [count] (a batch: [count, B]; probe: [count(, B),
+        len(probes), 3]), plus count and dropped."""
+        _, nprobes = getattr(self, "_mon", (0, 0))
+        return self._series(self.lib.lbm_monitor_read, L.lbm_monitor_record, lambda rec, shape: M.records_to_dict(rec, shape, nprobes))
 
     def end_monitor(self):
         """Stop the series and free its device buffer (lbm_monitor_end)."""
@@ -377,17 +382,7 @@ class CavitySolver:
     def residual_series(self):
         """The records so far (lbm_residual_read): step, step_prev, cells, nonfinite, sum_du2, sum_u2, sum_drho2, max_du2, max_x, max_y,
         max_drho2 as arrays [count] (a batch: [count, B]), plus count and dropped.  residual.norms() turns them into the usual norms."""
-        n, dropped = ctypes.c_longlong(0), ctypes.c_longlong(0)
-        self._check(self.lib.lbm_residual_read(self._h, None, 0, ctypes.byref(n), ctypes.byref(dropped)), "lbm_residual_read")   # the count
-        count = int(n.value)
-        rec = (L.lbm_residual_record * (count * self.batch))()
-        if count:
-            self._check(self.lib.lbm_residual_read(self._h, rec, count, ctypes.byref(n), ctypes.byref(dropped)), "lbm_residual_read")
-        out = RS.records_to_dict(rec, (count, self.batch))
-        if not self._lead:
-            out = {k: v[:, 0] for k, v in out.items()}
-        out["count"], out["dropped"] = count, int(dropped.value)
-        return out
+        return self._series(self.lib.lbm_residual_read, L.lbm_residual_record, RS.records_to_dict)
 
     def end_residual(self):
         """Stop the residual and free its snapshot and records (lbm_residual_end)."""

@@ -179,7 +179,7 @@ class HostStats:
 
 
 SERIES = [(every, kernel, False) for kernel in ("tb", "stream") for every in (1, 3, 8, 13)] + \
-         [(3, "generic", False), (8, "push", False), (3, "tb", True), (3, "stream", True)]
+         [(3, "generic", False), (8, "push", False), (3, "tb", True), (3, "stream", True), (4, "stream", True), (5, "tb", True)]
 MON = dict(window=(4, 120, 4, 150), probes=((66, 80), (1, 1)))
 
 
@@ -187,7 +187,8 @@ MON = dict(window=(4, 120, 4, 150), probes=((66, 80), (1, 1)))
 def test_automatic_samples_equal_manual_samples_and_leave_the_stepping_alone(every, kernel, beside):
     """lbm_step calls that do not line up with `every` (below and above the steps per launch); the series is bitwise the manual
     samples of a second context stepped to the same counts, and fin / u / rho equal that context's.  beside: the time statistics
-    sample every 5 and a monitor series every 4 next to it; all three stay exact."""
+    sample every 5 and a monitor series every 4 next to it; all three stay exact.  With the residual every 4 or 5 as well, two
+    samplers fall due together at many step counts and all three at step 20."""
     (nx, ny), dtype = SIZE[kernel], np.float32
     kw = dict(dtype=dtype, kernel=kernel, turb=0 if kernel == "push" else 1)
     with CavitySolver(nx, ny, 1000.0, **kw) as s, CavitySolver(nx, ny, 1000.0, **kw) as ref:
@@ -248,6 +249,45 @@ def test_capacity_and_dropped_samples():
         s.sample_residual().step(3).sample_residual().step(2).sample_residual()
         got = s.residual_series()
         assert got["count"] == 1 and got["dropped"] == 1 and (got["step"][0], got["step_prev"][0]) == (25, 22)
+
+
+def test_monitor_and_residual_series_are_independent():
+    """A monitor series with room for 2 records and a residual series with room for 64, both every 3, over 20 steps in calls of 7 and
+    13: samples at 3, 6, ..., 18.  The monitor keeps 2 records and drops 4; the residual keeps all 5 (steps 6 .. 18), bitwise the manual
+    samples of a second context; the stepping is unaffected; ending the monitor series leaves the residual series readable and
+    sampling on schedule."""
+    nx, ny = SIZE["tb"]
+    kw = dict(dtype=np.float32, kernel="tb")
+    with CavitySolver(nx, ny, 1000.0, **kw) as s, CavitySolver(nx, ny, 1000.0, **kw) as ref:
+        f = _perturbed(nx, ny, np.float32, 17)
+        s.set_state(f); ref.set_state(f)
+        s.begin_monitor(every=3, capacity=2, **MON)
+        s.begin_residual(every=3, capacity=64)
+        ref.begin_residual(every=0, capacity=64)
+        s.step(7).step(13)
+        mon = []
+        for n in range(3, 21, 3):
+            ref.step(n - ref.steps_done).sample_residual()
+            if len(mon) < 2:
+                mon.append(ref.monitor(**MON))
+        ref.step(20 - ref.steps_done)
+        ms, got, want = s.monitor_series(), s.residual_series(), ref.residual_series()
+        assert ms["count"] == 2 and ms["dropped"] == 4 and list(ms["step"]) == [3, 6]
+        for i, w in enumerate(mon):
+            assert all(np.array_equal(ms[k][i], w[k], equal_nan=True) for k in ("step", "sum_ux", "sum_q", "min_q", "min_x", "min_y", "probe"))
+        assert got["count"] == want["count"] == 5 and got["dropped"] == 0 and list(got["step"]) == list(range(6, 21, 3))
+        _same_bits(got, want, "beside a full monitor series")
+        a, b = s.get_fields(want_fin=True), ref.get_fields(want_fin=True)
+        assert all(np.array_equal(x, y) for x, y in zip(a, b))
+        s.end_monitor()
+        with pytest.raises(RuntimeError, match=r"\(-4\)"):
+            s.monitor_series()
+        _same_bits(s.residual_series(), want, "after the monitor series ended")
+        s.step(3)                                          # (the sample of step count 21 is taken where the unit from 20 starts)
+        ref.step(1).sample_residual().step(2)
+        got, want = s.residual_series(), ref.residual_series()
+        assert got["count"] == 6 and got["dropped"] == 0 and (got["step"][5], got["step_prev"][5]) == (21, 18)
+        _same_bits(got, want, "on schedule after the monitor series ended")
 
 
 def test_batch_of_mixed_reynolds_numbers_gives_each_lattice_its_own_record():
