@@ -23,61 +23,58 @@ import numpy as np
 
 from . import residual as RS
 from .solver import CavityBatch
+from .stopping import MeanUStop, ResidualStop, by_residual, wall_model
 
 
 def _solve_batch(idx, Re_range, xsize, ysize, RT, turb, uLB, maxIt, Pinterval, tolerance, device, dtype, say, out, arith, convergence="host",
-                 semantics="mrt_gpu", residual_tol=None, residual_final=None):
+                 semantics="mrt_gpu", residual_tol=None, residual_final=None, batch_factory=None):
     """Runs the lattices Re_range[idx] in lock step; fills out = (f_final, u_final, its) rows idx.  The per-lattice logic is
     the reference's loop body (MRT_GPU_datagen.py:707-731,862-871): a check after iteration It = 0, Pinterval, 2 Pinterval, ...
-    (i.e. after It + 1 steps), `count` consecutive-or-not hits of |mean(u) - mean(u_past)| / uLB < tolerance, stop at count > 5.
-    residual_tol (criterion='residual'): every check takes a sample of the field residual on the device instead (one record per
-    lattice crosses PCIe), and a lattice stops at the first check whose relative L2 change of u per step is below residual_tol -- the
-    rule of run_cavity(criterion='residual'); residual_final rows idx receive the value each lattice stopped at."""
-    by_residual = residual_tol is not None
+    (i.e. after It + 1 steps), and a lattice stops where its stop rule says so (stopping.MeanUStop with `tolerance`).
+    residual_final (criterion='residual'): every check takes a sample of the field residual on the device instead (one record per
+    lattice crosses PCIe), and a lattice stops at the first check below residual_tol (stopping.ResidualStop) -- the rule of
+    run_cavity(criterion='residual'); residual_final rows idx receive the value each lattice stopped at."""
+    by_res = residual_final is not None
     f_final, u_final, its = out
     sem = {} if semantics == "mrt_gpu" else {"semantics": semantics}
-    with CavityBatch(xsize, ysize, [float(Re_range[i]) for i in idx], RT=RT, uLB=uLB, dtype=dtype, turb=turb, device=device, arith=arith,
-                     **sem) as b:
+    make = CavityBatch if batch_factory is None else batch_factory
+    with make(xsize, ysize, [float(Re_range[i]) for i in idx], RT=RT, uLB=uLB, dtype=dtype, turb=turb, device=device, arith=arith, **sem) as b:
         feq_initial = b.get_fields(want_fin=True, out_dtype=np.float32)[2][0]      # fin = equ(1, InitVel) = feq_initial
-        count = [0] * len(idx)
-        past = [0.0] * len(idx)
+        stops = [ResidualStop(uLB, residual_tol) if by_res else MeanUStop(uLB, tolerance) for _ in idx]
         open_ = set(range(len(idx)))
         It = 0
-        if by_residual:
+        if by_res:
             b.begin_residual(every=0, capacity=min(maxIt // int(Pinterval) + 2, 1 << 18), out_dtype=np.float32)
-        nrec = 0
+        seen = 0
         while open_:
             b.step(It + 1 - b.steps_done)
             # the check value: NumPy's float32 mean of the downloaded field (the reference's own definition), or the mean reduced on
             # the device in double -- B doubles cross PCIe instead of B fields; the fields are then fetched only when a lattice stops
-            means = b.mean_u() if convergence == "device" and not by_residual else None
-            u = None if convergence == "device" or by_residual else b.get_fields(out_dtype=np.float32)[0]
-            finished = []
-            values = None
-            if by_residual:
+            means = u = ser = None
+            if by_res:
                 ser = b.sample_residual().residual_series()
-                if ser["count"] > nrec:                    # (the first check only fills the snapshot)
-                    nrec = ser["count"]
-                    values = RS.norms({k: ser[k][nrec - 1] for k in RS.FIELDS}, uLB)["rel_l2_per_step"]
+            elif convergence == "device":
+                means = b.mean_u()
+            else:
+                u = b.get_fields(out_dtype=np.float32)[0]
+            finished = []
             for j in sorted(open_):
-                if by_residual:
-                    say("current Re is " + str(Re_range[idx[j]]) + " and iteration is " + str(It))
-                    if values is not None:
-                        say("current residual is " + str(values[j]))
-                        residual_final[idx[j]] = values[j]
-                        if RS.below(values[j], residual_tol):
-                            say("breaking out of loop because of convergence")
-                            finished.append(j)
-                    continue
-                mean_u = float(means[j]) if convergence == "device" else float(np.mean(u[j]))
                 say("current Re is " + str(Re_range[idx[j]]) + " and iteration is " + str(It))
-                say("current mean u is " + str(mean_u / uLB))
-                if abs(mean_u - past[j]) / uLB < tolerance:
-                    count[j] += 1
-                    if count[j] > 5:
-                        say("breaking out of loop because of convergence")
-                        finished.append(j)
-                past[j] = mean_u
+                if by_res:
+                    rec = RS.latest(ser, seen, j)
+                    done = False
+                    if rec is not None:
+                        residual_final[idx[j]], done = stops[j].update(rec)
+                        say("current residual is " + str(residual_final[idx[j]]))
+                else:
+                    mean_u = float(np.mean(u[j]) if means is None else means[j])
+                    say("current mean u is " + str(mean_u / uLB))
+                    done = stops[j].update(mean_u)
+                if done:
+                    say("breaking out of loop because of convergence")
+                    finished.append(j)
+            if by_res:
+                seen = ser["count"]
             last = It + Pinterval > maxIt - 1          # no further check: the rest finishes the loop like the reference
             if finished:
                 if u is None:
@@ -100,37 +97,31 @@ def _solve_batch(idx, Re_range, xsize, ysize, RT, turb, uLB, maxIt, Pinterval, t
 
 def generate(Re_range=None, xsize=32 * 12, ysize=32 * 12, RT="SRT", turb=1, uLB=0.08, maxIt=3000000, Pinterval=10000,
              tolerance=0.0000001, OutputFolder="./output", save=True, concurrent=64, devices=(0,), dtype=np.float32,
-             quiet=False, arith="strict", convergence="host", BC="EB-NEBB ", criterion="mean_u", residual_tol=None):
+             quiet=False, arith="strict", convergence="host", BC="EB-NEBB ", criterion="mean_u", residual_tol=None, batch_factory=None):
     """Returns (feq_initial, f_final, u_final, Re_range, iterations_per_Re); writes the four .npy files when `save`.
     criterion: 'mean_u' (default, the reference's rule) or 'residual' -- each lattice stops at the first check whose field residual (the
     relative L2 change of u per step since the previous check, reduced on the device) is below residual_tol, which must be given; the
     function then returns a sixth item, residual_final [n], the value each lattice stopped at (the last one seen for a lattice that
     ran out of iterations, NaN if it saw none), and saves it as residual_final.npy beside the four files, which do not change.
     BC: 'EB-NEBB ' (default, the wet-node walls of MRT_GPU.py) or 'BB' (half-way bounce-back, semantics='bounce_back': the
-    cavity's mass is conserved to rounding; needs turb=0)."""
-    if BC.strip() not in ("EB-NEBB", "BB"):
-        raise ValueError("BC must be 'EB-NEBB ' or 'BB'")
-    if criterion not in ("mean_u", "residual"):
-        raise ValueError("criterion must be 'mean_u' or 'residual'")
-    by_residual = criterion == "residual"
-    if by_residual and (residual_tol is None or not float(residual_tol) > 0.0):
-        raise ValueError("criterion='residual' needs an explicit residual_tol > 0 (the noise floor depends on dtype and lattice size)")
-    semantics = "bounce_back" if BC.strip() == "BB" else "mrt_gpu"
-    if semantics == "bounce_back" and turb:
-        raise ValueError("BC='BB' runs without the Smagorinsky closure: pass turb=0")
+    cavity's mass is conserved to rounding; needs turb=0).
+    batch_factory (default: CavityBatch, i.e. liblbm_hip.so) exists so that the sweep's loop can be unit-tested with a stand-in, like
+    run_cavity's solver_factory; it is not a fallback."""
+    semantics = wall_model(BC, "mrt_gpu", turb)
+    by_res = by_residual(criterion, residual_tol)
     say = (lambda *a: None) if quiet else print
     Re_range = np.arange(100, 5100, 10) if Re_range is None else np.asarray(Re_range)   # MRT_GPU_datagen.py:55
     n = len(Re_range)
     tstart = timer()
     out = (np.zeros((n, 9, xsize, ysize), dtype=np.float32), np.zeros((n, 2, xsize, ysize), dtype=np.float32),
            np.zeros(n, dtype=np.int64))
-    residual_final = np.full(n, np.nan) if by_residual else None
+    residual_final = np.full(n, np.nan) if by_res else None
     chunks = [list(range(i, min(n, i + concurrent))) for i in range(0, n, concurrent)]
 
     def work(k):
         return _solve_batch(chunks[k], Re_range, xsize, ysize, RT, turb, uLB, maxIt, Pinterval, tolerance,
                             devices[k % len(devices)], dtype, say, out, arith, convergence, semantics,
-                            float(residual_tol) if by_residual else None, residual_final)
+                            float(residual_tol) if by_res else None, residual_final, batch_factory)
     if len(devices) > 1 and len(chunks) > 1:
         with ThreadPoolExecutor(max_workers=len(devices)) as pool:      # lbm_step runs in C with the GIL released
             feq = list(pool.map(work, range(len(chunks))))
@@ -145,10 +136,10 @@ def generate(Re_range=None, xsize=32 * 12, ysize=32 * 12, RT="SRT", turb=1, uLB=
         np.save(os.path.join(OutputFolder, "f_final.npy"), f_final)
         np.save(os.path.join(OutputFolder, "u_final.npy"), u_final)
         np.save(os.path.join(OutputFolder, "Re_range.npy"), Re_range)
-        if by_residual:
+        if by_res:
             np.save(os.path.join(OutputFolder, "residual_final.npy"), residual_final)
     say("TOTAL time elapsed is ", timer() - tstart, "seconds")
-    if by_residual:
+    if by_res:
         return feq_initial, f_final, u_final, Re_range, its, residual_final
     return feq_initial, f_final, u_final, Re_range, its
 

@@ -17,7 +17,9 @@ Differences, on purpose:
   (overwritten at line 374) and are not reproduced.
 """
 import os
+from collections import namedtuple
 from timeit import default_timer as timer
+from types import SimpleNamespace
 
 import numpy as np
 
@@ -26,6 +28,7 @@ from . import residual as RS
 from .VTKWrapper import saveToVTK
 from .monitor import vortex_window
 from .solver import CavitySolver
+from .stopping import MeanUStop, ResidualStop, by_residual, wall_model
 
 
 class CavityResult:
@@ -145,6 +148,155 @@ def _vortex_lines(table, Re, xsize, ysize, uLB):
     return lines
 
 
+def _check_arguments(criterion, residual_tol, residual_hits, monitor, MonitorEvery, convergence, AverageFrom, AverageEvery, BC, semantics, turb):
+    """(criterion is 'residual', semantics); ValueError for an argument run_cavity cannot run with."""
+    residual = by_residual(criterion, residual_tol, residual_hits)
+    if monitor not in ("host", "device"):
+        raise ValueError("monitor must be 'host' or 'device'")
+    if MonitorEvery is not None and (monitor != "device" or int(MonitorEvery) < 1):
+        raise ValueError("MonitorEvery needs monitor='device' and must be >= 1")
+    if monitor != "device" and convergence not in ("host", "device"):
+        raise ValueError("convergence must be 'host' or 'device'")
+    if AverageFrom is not None and (int(AverageFrom) < 0 or int(AverageEvery) < 1):
+        raise ValueError("AverageFrom must be >= 0 and AverageEvery >= 1")
+    return residual, wall_model(BC, semantics, turb)
+
+
+def _banner(say, Re, RT, turb, relax):
+    say("Re chosen  is ", Re)
+    say("RT chosen is ", RT)
+    say("Turbulence is on" if turb == 1 else "Turbulence is off")
+    say("the value of tau(/Dt) is ", 1 / relax["omega"])
+    if RT == "SRT":
+        say(" the value of omega is ", relax["omega"])
+    elif RT == "TRT":
+        say("the value of deltaTRT is ", 1.0 / 3.5)
+        say("omegap, omegam :", round(relax["omega"], 4), " , ", round(relax["omegam"], 4))
+    else:
+        say("omega omegap omegam omega_nu omega_e omega_eps omega_q")
+        say(relax["omega"], relax["omega"], relax["omegam"], relax["omega"], relax["omega_e"], relax["omega_eps"],
+            relax["omega_q"])
+
+
+# What one output iteration found: the count of cells that are not finite (device checks only; nothing else is filled then), the Ghia
+# regression value of the fields and of their time-mean (None: no Ghia column, no samples), the statistics if they hold samples, the
+# mean velocity as it is printed, the two vortex positions (device checks only), the vortex table if it is asked for and (u, rho) if they
+# were downloaded.
+Check = namedtuple("Check", "nonfinite reg_val reg_mean stats mean_velocity vortices table fields", defaults=(None,) * 7)
+
+
+def _time_mean(solver, run, averaging):
+    """(the time statistics if they hold samples, the regression value of their mean) -- None where there is none."""
+    stats = solver.statistics() if averaging else None
+    if stats is None or not stats["samples"]:
+        return None, None
+    return stats, ghia.r2_value(stats["u"], run.Re, run.uLB) if run.have_ghia else None
+
+
+def _check_host(solver, run, averaging):
+    """The checks of an output iteration on the downloaded fields, as the reference does them."""
+    u, rho = solver.get_fields(out_dtype=np.float32)
+    reg_val = ghia.r2_value(u, run.Re, run.uLB) if run.have_ghia else None
+    stats, reg_mean = _time_mean(solver, run, averaging)
+    table = solver.vortex_table(out_dtype=np.float32) if run.vortex_table else None
+    return Check(0, reg_val, reg_mean, stats, np.mean(u) / run.uLB, None, table, (u, rho))
+
+
+def _check_device(solver, run, averaging):
+    """The same checks reduced on the device; the fields are downloaded only when a file needs them."""
+    # (the sums and the count of cells that are not finite ignore the window: the same pass is the vortex search's first)
+    rec = solver.monitor(window=vortex_window(run.xsize, run.ysize)[1], out_dtype=np.float32)
+    fields = solver.get_fields(out_dtype=np.float32) if run.SavePlot or run.SaveVTK else None
+    if rec["nonfinite"] > 0:
+        return Check(int(rec["nonfinite"]), fields=fields)
+    reg_val = ghia.r2_from_column(solver.lines(out_dtype=np.float32)[0][0], run.Re, run.uLB) if run.have_ghia else None
+    stats, reg_mean = _time_mean(solver, run, averaging)
+    mean_velocity = (rec["sum_ux"] + rec["sum_uy"]) / (2.0 * run.xsize * run.ysize) / run.uLB
+    vortices = solver.locate_vortices(out_dtype=np.float32, first=rec)
+    table = solver.vortex_table(out_dtype=np.float32) if run.vortex_table else None
+    return Check(0, reg_val, reg_mean, stats, mean_velocity, vortices, table, fields)
+
+
+def _report(say, res, run, c, It):
+    """What a check found, into the result and onto stdout, in the reference's order."""
+    if c.reg_val is not None:
+        res.regression.append((It, float(c.reg_val)))
+        say("current regression value is " + str(c.reg_val))
+    if c.reg_mean is not None:
+        res.regression_mean.append((It, float(c.reg_mean)))
+        say("current regression value of the time-mean is " + str(c.reg_mean))
+    say("current mean velocity value is " + str(c.mean_velocity))
+    if c.vortices is not None:
+        res.vortices.append((It,) + c.vortices)
+        say("current vortex locations are " + str(c.vortices[0]) + " and " + str(c.vortices[1]))
+    if c.table is not None:
+        res.vortex_tables.append((It, c.table))
+        for line in _vortex_lines(c.table, run.Re if run.have_ghia else None, run.xsize, run.ysize, run.uLB):
+            say(line)
+
+
+def _begin_series(solver, run, maxIt, MonitorEvery, Probes, by_res):
+    """Start the record series a run keeps on the device: the monitor's (MonitorEvery) and the residual's (criterion='residual')."""
+    if MonitorEvery is not None:
+        probes = tuple(Probes) if len(Probes) else ((int(run.xsize / 2), int(run.ysize / 2)),)
+        solver.begin_monitor(every=int(MonitorEvery), capacity=min(maxIt // int(MonitorEvery) + 1, 1 << 18), probes=probes,
+                             out_dtype=np.float32)
+    if by_res:
+        if not hasattr(solver, "sample_residual"):
+            raise TypeError("criterion='residual' needs a solver with begin_residual / sample_residual / residual_series (CavitySolver); "
+                            + type(solver).__name__ + " has none")
+        solver.begin_residual(every=0, capacity=min(maxIt // int(run.Pinterval) + 2, 1 << 18), out_dtype=np.float32)
+
+
+def _residual_check(say, res, solver, stop, It):
+    """One sample of the field residual; True when it completes the run (the first check only fills the snapshot)."""
+    solver.sample_residual()
+    rec = RS.latest(solver.residual_series(), len(res.residuals))
+    if rec is None:
+        return False
+    value, finished = stop.update(rec)
+    res.residuals.append((It, rec))
+    say("current residual is " + str(value))
+    return finished
+
+
+def _collect(res, solver, with_series, averaging):
+    """The end of a run: the fields, the monitor series and the time statistics into the result."""
+    solver.sync()
+    res.u, res.rho = solver.get_fields(out_dtype=np.float32)
+    if with_series:
+        res.series = solver.monitor_series()
+    if averaging:
+        st = solver.statistics()
+        res.u_mean, res.rho_mean, res.uu, res.vv, res.uv, res.samples = st["u"], st["rho"], st["uu"], st["vv"], st["uv"], st["samples"]
+
+
+def _write_files(solver, run, c, It, hist):
+    """The dashboard and the .vtr files of output iteration It (and <project>_mean.#####.vtr once the statistics hold samples)."""
+    xsize, ysize = run.xsize, run.ysize
+    index = str(int(It / run.Pinterval)).zfill(5)
+    if run.SavePlot and run.have_ghia:
+        u, rho = c.fields
+        tau_mean = float(np.mean(solver.get_tau())) if (run.turb == 1 and hasattr(solver, "get_tau")) else None
+        _dashboard(os.path.join(run.OutputFolder, run.project + "_" + index + ".png"), u, rho, It, hist, run.Re, run.RT, run.regime, run.BC,
+                   xsize, ysize, run.uLB, solver.relax, tau_mean)
+    if run.SaveVTK:
+        u, rho = c.fields
+        grid = (np.arange(0, xsize, dtype="float64"), np.arange(0, ysize, dtype="float64"), np.arange(0, 1, dtype="float64"))
+        velZ = np.zeros((xsize, ysize, 1), dtype=np.float32)   # same dtype as the float32 host fields (MRT_GPU.py:207)
+        Vel = np.reshape(u, (2, xsize, ysize, 1))
+        cwd = os.getcwd()
+        os.chdir(run.OutputFolder)
+        try:
+            saveToVTK((Vel[0], Vel[1], velZ), np.reshape(rho, (xsize, ysize, 1)), run.project, index, grid, correct=run.vtk_correct)
+            if c.stats is not None:
+                Vm = np.reshape(c.stats["u"], (2, xsize, ysize, 1))
+                saveToVTK((Vm[0], Vm[1], np.zeros((xsize, ysize, 1))), np.reshape(c.stats["rho"], (xsize, ysize, 1)),
+                          run.project + "_mean", index, grid, correct=run.vtk_correct)
+        finally:
+            os.chdir(cwd)
+
+
 def run_cavity(maxIt=3000000, Re=10000.0, RT="SRT", turb=1, xsize=32 * 5, ysize=32 * 5, uLB=0.08,
                Pinterval=3000, SavePlot=True, SaveVTK=False, project="ldc", OutputFolder="./output",
                dtype=np.float32, semantics="mrt_gpu", device=0, quiet=False, solver_factory=None, arith="strict",
@@ -184,34 +336,9 @@ def run_cavity(maxIt=3000000, Re=10000.0, RT="SRT", turb=1, xsize=32 * 5, ysize=
     (iteration, record) to result.residuals; the run ends with result.converged once that value is below residual_tol at
     residual_hits consecutive checks.  residual_tol has no default -- the floor the residual settles on depends on dtype and lattice
     size -- and must be given.  With either monitor mode."""
-    if criterion not in ("mean_u", "residual"):
-        raise ValueError("criterion must be 'mean_u' or 'residual'")
-    by_residual = criterion == "residual"
-    if by_residual and (residual_tol is None or not float(residual_tol) > 0.0):
-        raise ValueError("criterion='residual' needs an explicit residual_tol > 0 (the noise floor depends on dtype and lattice size)")
-    if by_residual and int(residual_hits) < 1:
-        raise ValueError("residual_hits must be >= 1")
-    if monitor not in ("host", "device"):
-        raise ValueError("monitor must be 'host' or 'device'")
+    by_res, semantics = _check_arguments(criterion, residual_tol, residual_hits, monitor, MonitorEvery, convergence, AverageFrom,
+                                         AverageEvery, BC, semantics, turb)
     on_device = monitor == "device"
-    if MonitorEvery is not None and (not on_device or int(MonitorEvery) < 1):
-        raise ValueError("MonitorEvery needs monitor='device' and must be >= 1")
-    if on_device:
-        convergence = "device"
-    if convergence not in ("host", "device"):
-        raise ValueError("convergence must be 'host' or 'device'")
-    if AverageFrom is not None and (int(AverageFrom) < 0 or int(AverageEvery) < 1):
-        raise ValueError("AverageFrom must be >= 0 and AverageEvery >= 1")
-    if BC.strip() not in ("EB-NEBB", "BB"):
-        raise ValueError("BC must be 'EB-NEBB ' or 'BB'")
-    if BC.strip() == "BB":
-        if semantics not in ("mrt_gpu", "bounce_back"):
-            raise ValueError(f"BC='BB' selects semantics='bounce_back', not {semantics!r}")
-        if turb:
-            raise ValueError("BC='BB' runs without the Smagorinsky closure: pass turb=0")
-        semantics = "bounce_back"
-    elif semantics == "bounce_back":
-        raise ValueError("semantics='bounce_back' is BC='BB'")
     say = (lambda *a: None) if quiet else print
     tstart = timer()
     say("the value of uLB is ", uLB)
@@ -219,49 +346,21 @@ def run_cavity(maxIt=3000000, Re=10000.0, RT="SRT", turb=1, xsize=32 * 5, ysize=
     make = CavitySolver if solver_factory is None else solver_factory
     extra = {} if arith == "strict" else {"arith": arith}      # 'fast' / 'promoted': see CavitySolver
     solver = make(xsize, ysize, Re, RT=RT, uLB=uLB, semantics=semantics, dtype=dtype, turb=turb, device=device, **extra)
-    relax = solver.relax
-    say("Re chosen  is ", Re)
-    say("RT chosen is ", RT)
-    say("Turbulence is on" if turb == 1 else "Turbulence is off")
-    say("the value of tau(/Dt) is ", 1 / relax["omega"])
-    if RT == "SRT":
-        say(" the value of omega is ", relax["omega"])
-    elif RT == "TRT":
-        say("the value of deltaTRT is ", 1.0 / 3.5)
-        say("omegap, omegam :", round(relax["omega"], 4), " , ", round(relax["omegam"], 4))
-    else:
-        say("omega omegap omegam omega_nu omega_e omega_eps omega_q")
-        say(relax["omega"], relax["omega"], relax["omegam"], relax["omega"], relax["omega_e"], relax["omega_eps"],
-            relax["omega_q"])
+    _banner(say, Re, RT, turb, solver.relax)
     if (SavePlot or SaveVTK) and not os.path.isdir(OutputFolder):
         try:
             os.makedirs(OutputFolder)
         except OSError:
             pass
-    grid = (np.arange(0, xsize, dtype="float64"), np.arange(0, ysize, dtype="float64"), np.arange(0, 1, dtype="float64"))
-    velZ = np.zeros((xsize, ysize, 1), dtype=np.float32)   # same dtype as the float32 host fields (MRT_GPU.py:207)
-    regime = "Laminar" if turb == 1 else "Turbulent"   # labels exactly as (mis)assigned at MRT_GPU.py:277-280
-    BC = "BB" if semantics == "bounce_back" else "EB-NEBB "   # (the dashboard's label; MRT_GPU.py:281 spells the default so)
+    run = SimpleNamespace(Re=Re, RT=RT, turb=turb, xsize=xsize, ysize=ysize, uLB=uLB, Pinterval=Pinterval, SavePlot=SavePlot, SaveVTK=SaveVTK,
+                          project=project, OutputFolder=OutputFolder, vtk_correct=vtk_correct, vortex_table=bool(vortex_table),
+                          have_ghia=int(round(float(Re))) in ghia.RE_COLUMNS,
+                          regime="Laminar" if turb == 1 else "Turbulent",   # labels exactly as (mis)assigned at MRT_GPU.py:277-280
+                          BC="BB" if semantics == "bounce_back" else "EB-NEBB ")   # (the dashboard's label; MRT_GPU.py:281 spells the default so)
     res = CavityResult()
-    u = np.zeros((2, xsize, ysize), dtype=np.float32)
-    mean_past = 0.0
-    count = 0
     done = 0          # iterations performed
-    have_ghia = int(round(float(Re))) in ghia.RE_COLUMNS
-    outputs = SaveVTK or SavePlot or on_device or bool(vortex_table) or by_residual
+    outputs = SaveVTK or SavePlot or on_device or bool(vortex_table) or by_res
     averaging = False
-    if MonitorEvery is not None:
-        probes = tuple(Probes) if len(Probes) else ((int(xsize / 2), int(ysize / 2)),)
-        solver.begin_monitor(every=int(MonitorEvery), capacity=min(maxIt // int(MonitorEvery) + 1, 1 << 18), probes=probes,
-                             out_dtype=np.float32)
-
-    if by_residual:
-        if not hasattr(solver, "sample_residual"):
-            solver.close()
-            raise TypeError("criterion='residual' needs a solver with begin_residual / sample_residual / residual_series (CavitySolver); "
-                            + type(solver).__name__ + " has none")
-        solver.begin_residual(every=0, capacity=min(maxIt // int(Pinterval) + 2, 1 << 18), out_dtype=np.float32)
-    res_hits = 0
 
     def advance(n):   # n iterations; statistics begin once `done` reaches AverageFrom
         nonlocal averaging
@@ -276,109 +375,46 @@ def run_cavity(maxIt=3000000, Re=10000.0, RT="SRT", turb=1, xsize=32 * 5, ysize=
         if n > k:
             solver.step(n - k)
 
-    It = 0
-    while It < maxIt:
-        # iterations It .. next output iteration (inclusive) in one enqueue
-        nxt = It if (It % Pinterval == 0) else min(maxIt - 1, (It // Pinterval + 1) * Pinterval)
-        if not outputs:
-            nxt = maxIt - 1
-        advance(nxt - It + 1)
-        done = nxt + 1
-        It = nxt
-        if (It % Pinterval == 0) and outputs:
-            if on_device:
-                # (the sums and the count of cells that are not finite ignore the window: the same pass is the vortex search's first)
-                rec = solver.monitor(window=vortex_window(xsize, ysize)[1], out_dtype=np.float32)
-                if SavePlot or SaveVTK:
-                    u, rho = solver.get_fields(out_dtype=np.float32)
-            else:
-                u_past = u.copy()
-                u, rho = solver.get_fields(out_dtype=np.float32)
-            say("current iteration :", It)
-            if on_device and rec["nonfinite"] > 0:
-                say("breaking out of loop because the flow has diverged: " + str(int(rec["nonfinite"])) + " cells are not finite at iteration " + str(It))
-                res.diverged = True
-                break
-            if have_ghia:
-                reg_val = ghia.r2_from_column(solver.lines(out_dtype=np.float32)[0][0], Re, uLB) if on_device else ghia.r2_value(u, Re, uLB)
-                res.regression.append((It, float(reg_val)))
-                say("current regression value is " + str(reg_val))
-            stats = solver.statistics() if averaging else None
-            if stats is not None and stats["samples"] and have_ghia:
-                reg_mean = ghia.r2_value(stats["u"], Re, uLB)
-                res.regression_mean.append((It, float(reg_mean)))
-                say("current regression value of the time-mean is " + str(reg_mean))
-            if on_device:
-                say("current mean velocity value is " + str((rec["sum_ux"] + rec["sum_uy"]) / (2.0 * xsize * ysize) / uLB))
-                loc1, loc2 = solver.locate_vortices(out_dtype=np.float32, first=rec)
-                res.vortices.append((It, loc1, loc2))
-                say("current vortex locations are " + str(loc1) + " and " + str(loc2))
-            else:
-                say("current mean velocity value is " + str(np.mean(u) / uLB))
-            if vortex_table:
-                table = solver.vortex_table(out_dtype=np.float32)
-                res.vortex_tables.append((It, table))
-                for line in _vortex_lines(table, Re if have_ghia else None, xsize, ysize, uLB):
-                    say(line)
-            if SavePlot and have_ghia:
-                tau_mean = float(np.mean(solver.get_tau())) if (turb == 1 and hasattr(solver, "get_tau")) else None
-                _dashboard(os.path.join(OutputFolder, project + "_" + str(int(It / Pinterval)).zfill(5) + ".png"),
-                           u, rho, It, res.regression, Re, RT, regime, BC, xsize, ysize, uLB, relax, tau_mean)
-            if SaveVTK:
-                Vel = np.reshape(u, (2, xsize, ysize, 1))
-                cwd = os.getcwd()
-                os.chdir(OutputFolder)
-                try:
-                    saveToVTK((Vel[0], Vel[1], velZ), np.reshape(rho, (xsize, ysize, 1)), project,
-                              str(int(It / Pinterval)).zfill(5), grid, correct=vtk_correct)
-                    if stats is not None and stats["samples"]:
-                        Vm = np.reshape(stats["u"], (2, xsize, ysize, 1))
-                        saveToVTK((Vm[0], Vm[1], np.zeros((xsize, ysize, 1))), np.reshape(stats["rho"], (xsize, ysize, 1)),
-                                  project + "_mean", str(int(It / Pinterval)).zfill(5), grid, correct=vtk_correct)
-                finally:
-                    os.chdir(cwd)
-            say("time elapsed is ", (timer() - tstart), "seconds")
-            if by_residual:
-                solver.sample_residual()
-                ser = solver.residual_series()
-                if ser["count"] > len(res.residuals):      # (the first check only fills the snapshot)
-                    rec = RS.record_at(ser, ser["count"] - 1)
-                    value = RS.norms(rec, uLB)["rel_l2_per_step"]
-                    res.residuals.append((It, rec))
-                    say("current residual is " + str(value))
-                    res_hits = res_hits + 1 if RS.below(value, float(residual_tol)) else 0
-                hit = False
-                if res_hits >= int(residual_hits):
+    try:
+        _begin_series(solver, run, maxIt, MonitorEvery, Probes, by_res)
+        stop = ResidualStop(uLB, residual_tol, residual_hits) if by_res else MeanUStop(uLB, 0.00000001)      # MRT_GPU.py:883-889
+        It = 0
+        while It < maxIt:
+            # iterations It .. next output iteration (inclusive) in one enqueue
+            nxt = It if (It % Pinterval == 0) else min(maxIt - 1, (It // Pinterval + 1) * Pinterval)
+            if not outputs:
+                nxt = maxIt - 1
+            advance(nxt - It + 1)
+            done = nxt + 1
+            It = nxt
+            if (It % Pinterval == 0) and outputs:
+                c = _check_device(solver, run, averaging) if on_device else _check_host(solver, run, averaging)
+                say("current iteration :", It)
+                if c.nonfinite:
+                    say("breaking out of loop because the flow has diverged: " + str(c.nonfinite) + " cells are not finite at iteration " + str(It))
+                    res.diverged = True
+                    break
+                _report(say, res, run, c, It)
+                _write_files(solver, run, c, It, res.regression)
+                say("time elapsed is ", (timer() - tstart), "seconds")
+                if by_res:
+                    finished = _residual_check(say, res, solver, stop, It)
+                else:
+                    finished = stop.update(solver.mean_u() if on_device or convergence == "device" else np.mean(c.fields[0]))
+                if finished:
                     say("breaking out of loop because of convergence")
                     res.converged = True
                     break
-            elif convergence == "device":
-                mean_now = solver.mean_u()
-                hit = abs(mean_now - mean_past) / uLB < 0.00000001
-                mean_past = mean_now
-            else:
-                hit = abs(np.mean(u) - np.mean(u_past)) / uLB < 0.00000001      # MRT_GPU.py:883-889
-            if hit:
-                count = count + 1
-                if count > 5:
-                    say("breaking out of loop because of convergence")
-                    res.converged = True
-                    break
-            if It == maxIt - 1:
-                say("max iterations reached. More needed for convergence.")
-        It += 1
-    solver.sync()
-    res.u, res.rho = solver.get_fields(out_dtype=np.float32)
-    if MonitorEvery is not None:
-        res.series = solver.monitor_series()
-    if averaging:
-        st = solver.statistics()
-        res.u_mean, res.rho_mean, res.uu, res.vv, res.uv, res.samples = st["u"], st["rho"], st["uu"], st["vv"], st["uv"], st["samples"]
-    res.iterations = done
-    res.elapsed = timer() - tstart
-    res.mlups = xsize * ysize * done * 1e-6 / res.elapsed        # as printed by MRTTiledPull.py:703
-    say("TOTAL time elapsed is ", res.elapsed, "seconds")
-    solver.close()
+                if It == maxIt - 1:
+                    say("max iterations reached. More needed for convergence.")
+            It += 1
+        _collect(res, solver, MonitorEvery is not None, averaging)
+        res.iterations = done
+        res.elapsed = timer() - tstart
+        res.mlups = xsize * ysize * done * 1e-6 / res.elapsed        # as printed by MRTTiledPull.py:703
+        say("TOTAL time elapsed is ", res.elapsed, "seconds")
+    finally:
+        solver.close()
     return res
 
 

@@ -112,3 +112,9 @@ def records_to_dict(buf, shape):
 def record_at(series, i, b=None):
     """Record i of a residual_series() dict (lattice b of a batch) as a dict of scalars."""
     return {k: (series[k][i] if b is None else series[k][i, b]) for k in FIELDS}
+
+
+def latest(series, seen, b=None):
+    """The newest record of a residual_series() dict (lattice b of a batch) if the series holds more than the `seen` records the caller
+    has had, else None: the first sample of a run only fills the snapshot and leaves no record."""
+    return record_at(series, series["count"] - 1, b) if series["count"] > seen else None

@@ -1,0 +1,62 @@
+"""What the two front ends (mrt_gpu.run_cavity, datagen.generate) share: the two stop rules, each as an object that is asked once per
+check, and the checks of the arguments that select the wall model and the stop rule."""
+from . import residual as RS
+
+
+class MeanUStop:
+    """The reference's rule (MRT_GPU.py:883-889, MRT_GPU_datagen.py:862-871): |mean(u) - mean(u) at the previous check| / uLB < tolerance
+    is a hit, consecutive or not, and the `hits`-th hit ends the run.  The arithmetic is done on the values as they are handed in --
+    NumPy float32 scalars keep float32's rounding, Python floats double's --, so which check stops a run depends on the caller's type."""
+
+    def __init__(self, uLB, tolerance, hits=6):
+        self.uLB, self.tolerance, self.hits = uLB, tolerance, hits
+        self.past, self.count = 0, 0
+
+    def update(self, mean):
+        """True when this check completes the run."""
+        hit = abs(mean - self.past) / self.uLB < self.tolerance
+        self.past = mean
+        self.count += bool(hit)
+        return bool(hit) and self.count >= self.hits
+
+
+class ResidualStop:
+    """The field-residual rule: the relative L2 change of u per step (residual.norms) below `tol` at `hits` consecutive checks."""
+
+    def __init__(self, uLB, tol, hits=1):
+        self.uLB, self.tol, self.hits, self.count = uLB, float(tol), int(hits), 0
+
+    def update(self, record):
+        """(value, done) for the residual record of this check."""
+        value = RS.norms(record, self.uLB)["rel_l2_per_step"]
+        self.count = self.count + 1 if RS.below(value, self.tol) else 0
+        return value, self.count >= self.hits
+
+
+def wall_model(BC, semantics, turb):
+    """The semantics the wall model BC selects: 'EB-NEBB ' keeps `semantics`, 'BB' is 'bounce_back' (without the closure)."""
+    bc = BC.strip()
+    if bc not in ("EB-NEBB", "BB"):
+        raise ValueError("BC must be 'EB-NEBB ' or 'BB'")
+    if bc == "BB":
+        if semantics not in ("mrt_gpu", "bounce_back"):
+            raise ValueError(f"BC='BB' selects semantics='bounce_back', not {semantics!r}")
+        if turb:
+            raise ValueError("BC='BB' runs without the Smagorinsky closure: pass turb=0")
+        return "bounce_back"
+    if semantics == "bounce_back":
+        raise ValueError("semantics='bounce_back' is BC='BB'")
+    return semantics
+
+
+def by_residual(criterion, residual_tol, residual_hits=1):
+    """True for criterion='residual' (False for 'mean_u'), with its arguments checked."""
+    if criterion not in ("mean_u", "residual"):
+        raise ValueError("criterion must be 'mean_u' or 'residual'")
+    if criterion == "mean_u":
+        return False
+    if residual_tol is None or not float(residual_tol) > 0.0:
+        raise ValueError("criterion='residual' needs an explicit residual_tol > 0 (the noise floor depends on dtype and lattice size)")
+    if int(residual_hits) < 1:
+        raise ValueError("residual_hits must be >= 1")
+    return True

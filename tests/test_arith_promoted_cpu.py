@@ -8,9 +8,9 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from latticeboltzmannsimulations_amd import _lib as L  # noqa: E402
-from latticeboltzmannsimulations_amd import datagen, mrt_gpu, relaxation  # noqa: E402
+from latticeboltzmannsimulations_amd import datagen, mrt_gpu  # noqa: E402
 from latticeboltzmannsimulations_amd.solver import launch_plan  # noqa: E402
-from oracle.lbm_ref import CavityOracleC  # noqa: E402
+from front_end_standin import standin  # noqa: E402
 
 HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "lbm.h")
 
@@ -55,42 +55,15 @@ def test_promoted_rejections():
         launch_plan(128, 128, 100.0, arith="promote")
 
 
-class PromotedOracleStepper:
-    """Stand-in for CavitySolver as far as run_cavity uses it (as in test_front_end_cpu.py), recording the arith it was given."""
-    seen = []
-
-    def __init__(self, xsize, ysize, Re, RT="MRT", uLB=0.08, semantics="mrt_gpu", dtype=np.float32, turb=0, device=0, arith="strict"):
-        PromotedOracleStepper.seen.append(arith)
-        self.o = CavityOracleC(xsize, ysize, Re, uLB=uLB, semantics=semantics, collision=RT, dtype=dtype, turb=turb,
-                               promote=arith == "promoted")
-        self.relax = relaxation(Re, ysize, uLB)
-
-    def step(self, n=1):
-        self.o.step(n)
-        return self
-
-    def sync(self):
-        pass
-
-    def get_fields(self, out_dtype=None, **kw):
-        return self.o.u.astype(out_dtype), self.o.rho.astype(out_dtype)
-
-    def mean_u(self):
-        return float(np.mean(self.o.u.astype(np.float64)))
-
-    def get_tau(self):
-        return np.ones(self.o.rho.shape)
-
-    def close(self):
-        pass
+PromotedOracleStepper = standin()        # `made` records the arith it was given
 
 
 def test_run_cavity_passes_promoted(tmp_path, monkeypatch):
     monkeypatch.chdir(tmp_path)
-    PromotedOracleStepper.seen = []
+    PromotedOracleStepper.made.clear()
     r = mrt_gpu.run_cavity(maxIt=21, Re=100.0, RT="SRT", turb=1, xsize=32, ysize=32, Pinterval=10, SavePlot=False, SaveVTK=False,
                            solver_factory=PromotedOracleStepper, arith="promoted", quiet=True)
-    assert PromotedOracleStepper.seen == ["promoted"] and r.iterations == 21
+    assert [kw["arith"] for kw in PromotedOracleStepper.made] == ["promoted"] and r.iterations == 21
 
 
 def test_command_lines_accept_promoted(monkeypatch):

@@ -10,6 +10,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 from bounce_back_ref import BOUNCE, BounceBackOracle  # noqa: E402
+from front_end_standin import standin  # noqa: E402
 from oracle import lbm_numpy as on  # noqa: E402
 from latticeboltzmannsimulations_amd import datagen, ghia, launch_plan, mrt_gpu  # noqa: E402
 from latticeboltzmannsimulations_amd import _lib as L  # noqa: E402
@@ -119,35 +120,7 @@ def test_stream_walls_off_is_accepted():
 
 
 # ---- front end --------------------------------------------------------------------------------------------------------------
-class _StandIn:
-    made = []
-
-    def __init__(self, xsize, ysize, Re, **kw):
-        _StandIn.made.append(kw)
-        o = BounceBackOracle(xsize, ysize, Re, collision=kw["RT"], dtype=np.float64)
-        self.o, self.relax, self.steps_done = o, o.relax, 0
-
-    def step(self, n):
-        self.o.step(n)
-        self.steps_done += n
-
-    def get_fields(self, want_fin=False, **kw):
-        return (self.o.u, self.o.rho, self.o.fin) if want_fin else (self.o.u, self.o.rho)
-
-    def mean_u(self):
-        return float(np.mean(self.o.u))
-
-    def sync(self):
-        pass
-
-    def close(self):
-        pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
+_StandIn = standin(source="bounce_back")
 
 
 def test_run_cavity_passes_bounce_back_through(tmp_path):

@@ -1,46 +1,17 @@
 """CPU test of the drop-in front end's HOST logic (mrt_gpu.run_cavity: which iterations produce output, the
 reference's metric and prints, PNG / VTK files, convergence stop) with a stand-in stepper backed by the oracle.
-The product has no CPU stepper; the stand-in lives here, in tests/."""
+The product has no CPU stepper; the stand-in lives in tests/front_end_standin.py."""
 import os
 
 import numpy as np
 import pytest
 
-from latticeboltzmannsimulations_amd import relaxation
 from latticeboltzmannsimulations_amd.mrt_gpu import run_cavity
+from front_end_standin import standin
 from oracle.lbm_ref import CavityOracleC
 
 
-class OracleStepper:
-    """Same surface as CavitySolver as far as run_cavity uses it."""
-    calls = []
-    mean_calls = 0
-
-    def __init__(self, xsize, ysize, Re, RT="MRT", uLB=0.08, semantics="mrt_gpu", dtype=np.float32, turb=0, device=0):
-        self.o = CavityOracleC(xsize, ysize, Re, uLB=uLB, semantics=semantics, collision=RT, dtype=dtype, turb=turb)
-        self.relax = relaxation(Re, ysize, uLB)
-        OracleStepper.calls = []
-
-    def step(self, n=1):
-        OracleStepper.calls.append(int(n))
-        self.o.step(n)
-        return self
-
-    def sync(self):
-        pass
-
-    def get_fields(self, out_dtype=None, **kw):
-        return self.o.u.astype(out_dtype), self.o.rho.astype(out_dtype)
-
-    def mean_u(self):          # lbm_mean_u: the mean accumulated in double
-        OracleStepper.mean_calls += 1
-        return float(np.mean(self.o.u.astype(np.float64)))
-
-    def get_tau(self):
-        return np.full(self.o.rho.shape, 1.0 / self.relax["omega"] + 0.01)
-
-    def close(self):
-        pass
+OracleStepper = standin()
 
 
 def test_output_iterations_batches_and_files(tmp_path, monkeypatch, capsys):
@@ -78,7 +49,6 @@ def test_convergence_on_the_device_mean_stops_within_one_check_of_the_host_crite
     kw = dict(maxIt=10 ** 7, Re=100.0, RT="MRT", turb=0, xsize=16, ysize=16, Pinterval=400, SavePlot=False, SaveVTK=True,
               dtype=np.float64, solver_factory=OracleStepper, quiet=True)
     host = run_cavity(**kw)
-    OracleStepper.mean_calls = 0
     dev = run_cavity(convergence="device", **kw)
     assert host.converged and dev.converged and OracleStepper.mean_calls >= 6
     assert abs(dev.iterations - host.iterations) <= 400

@@ -4,9 +4,9 @@ refusals of the four entry points.  No device is needed."""
 import numpy as np
 import pytest
 
-from latticeboltzmannsimulations_amd import _lib, relaxation, residual
+from front_end_standin import standin
+from latticeboltzmannsimulations_amd import _lib, residual
 from latticeboltzmannsimulations_amd.mrt_gpu import run_cavity
-from oracle.lbm_ref import CavityOracleC
 
 SUMS = ("sum_du2", "sum_u2", "sum_drho2")
 EXACT = ("step", "step_prev", "cells", "nonfinite", "max_du2", "max_x", "max_y", "max_drho2")
@@ -140,55 +140,8 @@ def test_norms_of_a_record_with_known_values_and_the_division_per_step():
     assert not residual.below(residual.norms(dict(rec, sum_du2=0.0, sum_u2=0.0), 0.08)["rel_l2_per_step"], 1.0)   # 0 / 0 never passes
 
 
-class ResidualStepper:
-    """The surface of CavitySolver as far as run_cavity(criterion='residual') uses it, backed by the oracle; the residual is the host
-    statement on the fields get_fields returns."""
-    last = None
-
-    def __init__(self, xsize, ysize, Re, RT="MRT", uLB=0.08, semantics="mrt_gpu", dtype=np.float32, turb=0, device=0):
-        self.o = CavityOracleC(xsize, ysize, Re, uLB=uLB, semantics=semantics, collision=RT, dtype=dtype, turb=turb)
-        self.relax = relaxation(Re, ysize, uLB)
-        self.steps_done = 0
-        self.records, self.prev, self.capacity = [], None, 0
-        ResidualStepper.last = self
-
-    def step(self, n=1):
-        self.o.step(n)
-        self.steps_done += int(n)
-        return self
-
-    def sync(self):
-        pass
-
-    def close(self):
-        pass
-
-    def get_fields(self, out_dtype=None, **kw):
-        return self.o.u.astype(out_dtype), self.o.rho.astype(out_dtype)
-
-    def mean_u(self):
-        raise AssertionError("the mean-u rule is not evaluated under criterion='residual'")
-
-    def begin_residual(self, every=0, capacity=1024, out_dtype=None):
-        assert every == 0
-        self.records, self.prev, self.capacity, self.out = [], None, capacity, out_dtype
-        return self
-
-    def sample_residual(self):
-        u, rho = self.get_fields(out_dtype=self.out)
-        if self.prev is not None:
-            self.records.append(residual.host_residual(self.prev[1], self.prev[2], u, rho, step=self.steps_done, step_prev=self.prev[0]))
-        self.prev = (self.steps_done, u, rho)
-        return self
-
-    def residual_series(self):
-        out = {k: np.array([r[k] for r in self.records]) for k in residual.FIELDS}
-        out["count"], out["dropped"] = len(self.records), 0
-        return out
-
-
-class PlainStepper(ResidualStepper):
-    begin_residual = sample_residual = residual_series = property()
+ResidualStepper = standin()
+PlainStepper = standin(without=("residual",))
 
 
 def test_run_cavity_stops_at_the_first_check_below_the_tolerance(capsys):
@@ -204,6 +157,7 @@ def test_run_cavity_stops_at_the_first_check_below_the_tolerance(capsys):
     r = run_cavity(maxIt=2401, criterion="residual", residual_tol=tol, **kw)
     assert r.converged and r.iterations == its[4] + 1 and len(r.residuals) == 5
     assert ResidualStepper.last.steps_done == its[4] + 1
+    assert ResidualStepper.mean_calls == 0                     # the mean-u rule is not evaluated under criterion='residual'
     out = capsys.readouterr().out
     assert "current residual is " + str(vals[4]) in out and "breaking out of loop because of convergence" in out
     # two consecutive hits: one check later

@@ -7,7 +7,8 @@ import ctypes
 import numpy as np
 import pytest
 
-from latticeboltzmannsimulations_amd import ghia, relaxation
+from front_end_standin import standin
+from latticeboltzmannsimulations_amd import ghia
 from latticeboltzmannsimulations_amd import topology as T
 from latticeboltzmannsimulations_amd.mrt_gpu import run_cavity
 from oracle.lbm_ref import CavityOracleC
@@ -185,29 +186,7 @@ def test_physics_pin_primary_vortex_of_the_fp64_oracle_at_re_100(oracle_re100):
     assert abs(dx) <= 2 / 64 and abs(dy) <= 2 / 64
 
 
-class OracleStepper:
-    """Same surface as CavitySolver as far as run_cavity(vortex_table=True) uses it; the table through the host statement."""
-
-    def __init__(self, xsize, ysize, Re, RT="MRT", uLB=0.08, semantics="mrt_gpu", dtype=np.float32, turb=0, device=0):
-        self.o = CavityOracleC(xsize, ysize, Re, uLB=uLB, semantics=semantics, collision=RT, dtype=dtype, turb=turb)
-        self.relax = relaxation(Re, ysize, uLB)
-        self.uLB = uLB
-
-    def step(self, n=1):
-        self.o.step(n)
-        return self
-
-    def sync(self):
-        pass
-
-    def get_fields(self, out_dtype=None, **kw):
-        return self.o.u.astype(out_dtype), self.o.rho.astype(out_dtype)
-
-    def vortex_table(self, out_dtype=np.float32):
-        return T.host_vortex_table(self.o.u.astype(out_dtype), self.uLB)
-
-    def close(self):
-        pass
+OracleStepper = standin()        # the table through the host statement
 
 
 def test_front_end_fills_the_vortex_tables(tmp_path, monkeypatch, capsys):
