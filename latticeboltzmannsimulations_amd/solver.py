@@ -77,7 +77,7 @@ class CavitySolver:
                    'push' (the reference's two-launch push scheme, for A/B only)
     layout       : device arrays 'planes' [k][y][x], 'rows' [y][k][x], 'auto' (= rows)
     arith        : 'strict' (default; the reference's operation order, bit-identical to the CPU restatement the tests check against), 'fast' (MRT operator
-                   in factored form, about half the arithmetic, agrees to rounding) or 'promoted' (MRT_GPU.py's CUDA text: the strict order, with
+                   in factored form, about half the arithmetic, agrees to rounding; semantics='mrt_py' runs the strict form for it) or 'promoted' (MRT_GPU.py's CUDA text: the strict order, with
                    the sub-expressions its double literals make double -- equilibrium bracket, MRT m_eq sums, Smagorinsky tau -- evaluated in
                    double and rounded to float once; fp32 bit-identical to the oracles' promote=True, fp64 the same as 'strict';
                    semantics='mrt_gpu' only)

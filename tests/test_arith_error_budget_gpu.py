@@ -34,6 +34,32 @@ Maxima over the four states, both rate sets and the five read-outs (ratios over 
 The median fin ratio is 0.98 for fast (56 % of the read-outs below 1) and 0.99 for promoted: neither form is the more accurate one.
 Against the parent's factored MRT (m_eq[1], m_eq[2] from the population sum on the lid row) the one-step check fails from S1, S2
 and S3 with the largest error on row 0: 1.8e4 - 2.7e4 eps in fp32, 1e13 eps in fp64; from S0 it passes.
+
+The other two wall semantics (test_fast_stays_within_the_budget_under_the_other_walls): MRT.py's walls (`mrt_py`; reference
+CavityOracleC for the bits, CavityOracle in long double with MRT.py's omega_eps = 1.0) and half-way bounce-back (`bounce_back`;
+tests/bounce_back_ref.py in the lattice type for the bits and in long double), without closure and promoted (both refused), the same
+lattice, states, rate sets and read-outs.  Measured on an MI355X, maxima as above; every ratio is inside K = 4 x 2.31, so K stays:
+
+| semantics | lattice | operator | err after 1 step, in eps: strict / fast | fin err after 26 steps: strict / fast | largest ratio: fast |
+|---|---|---|---|---|---|
+| mrt_py | fp32 | SRT | 4.4 / 4.4 | 1.8e-6 / 1.8e-6 | 1.00 |
+| mrt_py | fp32 | TRT | 4.4 / 4.4 | 2.1e-6 / 2.1e-6 | 1.00 |
+| mrt_py | fp32 | MRT | 2.6 / 2.6 | 7.2e-7 / 7.2e-7 | 1.00 |
+| mrt_py | fp64 | SRT | 4.5 / 4.5 | 4.9e-15 / 4.9e-15 | 1.00 |
+| mrt_py | fp64 | TRT | 4.5 / 4.5 | 5.1e-15 / 5.1e-15 | 1.00 |
+| mrt_py | fp64 | MRT | 2.7 / 2.7 | 2.2e-15 / 2.2e-15 | 1.00 |
+| bounce_back | fp32 | SRT | 4.4 / 4.9 | 1.9e-6 / 1.4e-6 | 1.28 |
+| bounce_back | fp32 | TRT | 4.4 / 4.9 | 2.3e-6 / 1.9e-6 | 1.56 |
+| bounce_back | fp32 | MRT | 2.6 / 2.4 | 7.0e-7 / 6.2e-7 | 2.66 |
+| bounce_back | fp64 | SRT | 4.6 / 4.7 | 4.4e-15 / 4.4e-15 | 1.32 |
+| bounce_back | fp64 | TRT | 4.6 / 4.7 | 4.8e-15 / 5.3e-15 | 1.44 |
+| bounce_back | fp64 | MRT | 2.7 / 2.7 | 2.0e-15 / 1.8e-15 | 1.57 |
+
+Under MRT.py's walls fast and strict are the same numbers in all 240 read-outs: dispatch() (lbm_host.hpp) gives arith = fast the strict
+operators there, as include/lbm.h documents for lbm_params.arith, so measure() asserts the oracle's bits for fast as well.  Under
+bounce-back the median fin ratio is 0.88 - 1.05 per row; the largest ratio, 2.66 (fp32 MRT, u after 2 steps from S0), is where
+err_strict is about 1 eps.  The largest fin error sits on a wall cell in 51 of the 240 read-outs (39 of 240 for the strict operators
+under MRT.py's walls), with ratios <= 1.15 there: no wall row, column or corner stands out, and no bug was found in the wall paths.
 """
 import os
 import sys
@@ -45,6 +71,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from oracle.lbm_numpy import CavityOracle      # noqa: E402
 from oracle.lbm_ref import CavityOracleC       # noqa: E402
 from oracle.states import STATES, state        # noqa: E402
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from bounce_back_ref import BounceBackOracle   # noqa: E402
 from latticeboltzmannsimulations_amd import CavityBatch, CavitySolver  # noqa: E402
 from latticeboltzmannsimulations_amd.slab import LocalSlabs, partition_rows  # noqa: E402
 
@@ -88,11 +116,30 @@ def _errs(got, ref):
     return e
 
 
-def measure(dtype, coll, turb, st, rates):
-    """err of every arithmetic mode after every call: {arith: [(steps, {field: err}, where_fin)]}.  Asserts that strict is the C
-    oracle's bits.  Also used by the measurement script that set K."""
-    modes = ["strict", "fast"] + (["promoted"] if dtype == np.float32 else [])
-    kw = dict(RT=coll, dtype=dtype, turb=turb)
+def _lattice_oracle(sem, nx, ny, coll, dtype, turb, rates, promote=False):
+    """The oracle in the lattice type that strict (and promoted) must equal bit for bit: the C oracle for MRT_GPU.py's and MRT.py's
+    walls, tests/bounce_back_ref.py for bounce-back (there is no C oracle of it).  The default omega_eps is each semantics' own
+    (1.0 for mrt_py), as in solver.py."""
+    if sem == "bounce_back":
+        assert not turb and not promote
+        return BounceBackOracle(nx, ny, RE, collision=coll, dtype=dtype, **rates)
+    return CavityOracleC(nx, ny, RE, semantics=sem, collision=coll, dtype=dtype, turb=turb, promote=promote, **rates)
+
+
+def _long_double_oracle(sem, nx, ny, coll, dtype, turb, rates):
+    """The budget's reference: the NumPy oracle of the semantics in long double, rates and uLB rounded to the lattice type first."""
+    kw = dict(collision=coll, dtype=np.longdouble, param_dtype=dtype, **rates)
+    if sem == "bounce_back":
+        return BounceBackOracle(nx, ny, RE, **kw)
+    return CavityOracle(nx, ny, RE, semantics=sem, turb=turb, **kw)
+
+
+def measure(dtype, coll, turb, st, rates, sem="mrt_gpu"):
+    """err of every arithmetic mode after every call: {arith: [(steps, {field: err}, where_fin)]}.  Asserts that strict is the
+    lattice-type oracle's bits -- and fast too under MRT.py's walls, where the library runs the strict operators for it
+    (include/lbm.h, lbm_params.arith).  Also used by the measurement script that set K."""
+    modes = ["strict", "fast"] + (["promoted"] if dtype == np.float32 and sem == "mrt_gpu" else [])
+    kw = dict(RT=coll, dtype=dtype, turb=turb, semantics=sem)
     solvers = {a: CavitySolver(NX, NY, RE, arith=a, **kw) for a in modes}
     try:
         f0 = solvers["strict"].get_fields(want_fin=True)[2] if st == "S0" else state(st, NX, NY, dtype)
@@ -100,8 +147,8 @@ def measure(dtype, coll, turb, st, rates):
             if rates:
                 s.set_relaxation(0, **rates)
             s.set_state(f0)
-        C = CavityOracleC(NX, NY, RE, semantics="mrt_gpu", collision=coll, dtype=dtype, turb=turb, **rates)
-        L = CavityOracle(NX, NY, RE, semantics="mrt_gpu", collision=coll, dtype=np.longdouble, param_dtype=dtype, turb=turb, **rates)
+        C = _lattice_oracle(sem, NX, NY, coll, dtype, turb, rates)
+        L = _long_double_oracle(sem, NX, NY, coll, dtype, turb, rates)
         C.set_state(f0)
         L.set_state(f0.astype(np.longdouble))
         out = {a: [] for a in modes}
@@ -111,9 +158,9 @@ def measure(dtype, coll, turb, st, rates):
             for a, s in solvers.items():
                 s.step(n)
                 got = _fields(s, turb)
-                if a == "strict":
+                if a == "strict" or (a == "fast" and sem == "mrt_py"):      # (MRT.py's walls: fast runs the strict operators, lbm.h)
                     assert np.array_equal(got["fin"], C.fin) and np.array_equal(got["u"], C.u) and np.array_equal(got["rho"], C.rho), \
-                        ("strict differs from the C oracle", coll, turb, st, rates, L.nsteps)
+                        (a + " differs from the oracle", sem, coll, turb, st, rates, L.nsteps)
                 out[a].append((L.nsteps, _errs(got, ref), _where(got["fin"], ref["fin"])))
         return out
     finally:
@@ -121,24 +168,39 @@ def measure(dtype, coll, turb, st, rates):
             s.close()
 
 
+def _assert_budget(m, tag0, dtype, rates):
+    eps = float(np.finfo(dtype).eps)
+    for a in m:
+        if a == "strict":
+            continue
+        for (steps, e, at), (_, es, _) in zip(m[a], m["strict"]):
+            tag = (a, np.dtype(dtype).name) + tag0 + ("distinct" if rates else "default", steps)
+            if steps == 1 and a == "fast":
+                for k, v in e.items():
+                    assert v <= 32 * eps, (tag, k, v / eps, "eps after one step; largest fin error at (k, x, y) =", at)
+            for k, v in e.items():
+                bound = K * max(es[k], eps)
+                assert v <= bound, (tag, k, v, "ratio", v / max(es[k], eps), "largest fin error at (k, x, y) =", at)
+
+
 @pytest.mark.parametrize("st", STATES)
 @pytest.mark.parametrize("coll,turb", [("SRT", 0), ("SRT", 1), ("TRT", 0), ("TRT", 1), ("MRT", 0), ("MRT", 1)])
 @pytest.mark.parametrize("dtype", [np.float32, np.float64])
 def test_fast_and_promoted_stay_within_the_budget(dtype, coll, turb, st):
-    eps = float(np.finfo(dtype).eps)
     for rates in ({}, DISTINCT):
-        m = measure(dtype, coll, turb, st, rates)
-        for a in m:
-            if a == "strict":
-                continue
-            for (steps, e, at), (_, es, _) in zip(m[a], m["strict"]):
-                tag = (a, np.dtype(dtype).name, coll, turb, st, "distinct" if rates else "default", steps)
-                if steps == 1 and a == "fast":
-                    for k, v in e.items():
-                        assert v <= 32 * eps, (tag, k, v / eps, "eps after one step; largest fin error at (k, x, y) =", at)
-                for k, v in e.items():
-                    bound = K * max(es[k], eps)
-                    assert v <= bound, (tag, k, v, "ratio", v / max(es[k], eps), "largest fin error at (k, x, y) =", at)
+        _assert_budget(measure(dtype, coll, turb, st, rates), (coll, turb, st), dtype, rates)
+
+
+@pytest.mark.parametrize("st", STATES)
+@pytest.mark.parametrize("coll", ["SRT", "TRT", "MRT"])
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+@pytest.mark.parametrize("sem", ["mrt_py", "bounce_back"])
+def test_fast_stays_within_the_budget_under_the_other_walls(sem, dtype, coll, st):
+    """The same budget under MRT.py's walls and under bounce-back (neither takes the closure or promoted): strict is the lattice-type
+    oracle's bits at both rate sets, fast <= 32 eps after one step and <= K max(err_strict, eps) at every read-out.  Under MRT.py's
+    walls fast is the oracle's bits as well (measure()), so its ratio is 1 by construction; the budget is what holds it if that changes."""
+    for rates in ({}, DISTINCT):
+        _assert_budget(measure(dtype, coll, 0, st, rates, sem), (sem, coll, st), dtype, rates)
 
 
 # ---- the same bits from an off-equilibrium state in every kernel family ----------------------------------------------------------
@@ -146,6 +208,16 @@ def test_fast_and_promoted_stay_within_the_budget(dtype, coll, turb, st):
 FAMILIES = [("generic", 0, {}), ("vec", 0, {}), ("push", 0, {})] + [("tb", s, {}) for s in (2, 3, 4, 5)] + [
     ("stream", 3, dict(stream_walls=False)), ("stream", 8, dict(stream_walls=False)), ("stream", 5, dict(stream_walls=True)),
     ("stream", 8, dict(stream_pairs=True))]
+# MRT.py's walls and bounce-back: the kernels lbm_plan accepts for them, each with the kernel and the steps per launch that describe()
+# must report (tests/test_arith_error_budget_walls_cpu.py confirms every entry by a dry run).  vec, the streaming kernels with the walls
+# inside and, under bounce-back, the push scheme know only MRT_GPU.py's walls.
+WALL_FAMILIES = {
+    "mrt_py": [("generic", 0, {}, "none", 1), ("push", 0, {}, "none", 1),
+               ("tb", 2, {}, "k_step2_deep", 2), ("tb", 3, {}, "k_stepS_deep", 3), ("tb", 4, {}, "k_stepS_deep", 4), ("tb", 5, {}, "k_stepS_deep", 5),
+               ("stream", 3, dict(stream_walls=False), "k_stream", 3), ("stream", 8, dict(stream_walls=False), "k_stream", 8)],
+    "bounce_back": [("generic", 0, {}, "none", 1),
+                    ("tb", 2, {}, "k_step2_deep", 2), ("tb", 3, {}, "k_stepS_deep", 3), ("tb", 4, {}, "k_stepS_deep", 4), ("tb", 5, {}, "k_stepS_deep", 5),
+                    ("stream", 3, dict(stream_walls=False), "k_stream", 3), ("stream", 8, dict(stream_walls=False), "k_stream", 8)]}
 FAM_CALLS = (1, 2, 7, 20)
 BATCH_RATES = [dict(Re=400.0, omega_e=1.13, omega_eps=1.41, omega_q=1.67, omegam=1.31),
                dict(Re=1000.0, omega_e=0.9, omega_eps=1.55, omega_q=1.25, omegam=1.7),
@@ -156,8 +228,8 @@ def _shape(kernel):
     return (264, 150) if kernel == "stream" else (96, 80)
 
 
-def _open(nx, ny, coll, turb, dtype, arith, kernel, tbs, tune, rows=None):
-    s = CavitySolver(nx, ny, RE, RT=coll, dtype=dtype, turb=turb, arith=arith, kernel=kernel, rows=rows,
+def _open(nx, ny, coll, turb, dtype, arith, kernel, tbs, tune, rows=None, sem="mrt_gpu"):
+    s = CavitySolver(nx, ny, RE, RT=coll, dtype=dtype, turb=turb, arith=arith, kernel=kernel, rows=rows, semantics=sem,
                      tuning=dict(tb_steps=tbs, **tune))
     s.set_relaxation(0, **DISTINCT)
     return s
@@ -178,38 +250,46 @@ def _same_bits(a, b, what):
             assert np.array_equal(x[k], y[k]), (what, "call", i, k, np.abs(x[k] - y[k]).max())
 
 
-@pytest.mark.parametrize("coll,turb", [("SRT", 0), ("SRT", 1), ("TRT", 0), ("TRT", 1), ("MRT", 0), ("MRT", 1)])
-@pytest.mark.parametrize("dtype", [np.float32, np.float64])
-def test_fast_gives_the_same_bits_in_every_kernel_from_an_off_equilibrium_state(dtype, coll, turb):
-    """arith = fast from S2 at the distinct rates: generic, vec, push (no closure), tb 2-5, stream (frame 3 / 8, walls 5, pairs 8) give the
-    same bits, fields and tau after every call; so do the smallest lattices (5 x 4, 6 x 6), a batch of three lattices with their own
-    rates (each = the lattice alone) and three slabs, the first holding the lid."""
+def _plan_is(s, want):
+    """describe() reports the kernel and the steps per launch the family list names (a refusal raises in _open; a re-route fails here)."""
+    if want:
+        d = s.describe()
+        assert (d["kernel"], d["steps_per_launch"]) == want, (d["kernel"], d["steps_per_launch"], want)
+
+
+def _fast_same_bits_everywhere(sem, families, dtype, coll, turb):
+    """arith = fast from S2 at the distinct rates: every family of `families` (kernel, tb_steps, tuning[, kernel name, steps that
+    describe() must report]) gives the bits of the generic kernel, fields and tau after every call; so do the smallest lattices
+    (5 x 4, 6 x 6), a batch of three lattices with their own rates (each = the lattice alone) and three slabs, the first holding
+    the lid."""
     refs = {}
-    for kernel, tbs, tune in FAMILIES:
+    for kernel, tbs, tune, *want in families:
         if kernel == "push" and turb:
             continue                      # the push scheme takes no closure (lbm_create refuses it)
         nx, ny = _shape(kernel)
         f0 = state("S2", nx, ny, dtype)
         if (nx, ny) not in refs:
-            with _open(nx, ny, coll, turb, dtype, "fast", "generic", 0, {}) as g:
+            with _open(nx, ny, coll, turb, dtype, "fast", "generic", 0, {}, sem=sem) as g:
                 refs[nx, ny] = _stepped(g, f0, FAM_CALLS)
-        with _open(nx, ny, coll, turb, dtype, "fast", kernel, tbs, tune) as s:
+        with _open(nx, ny, coll, turb, dtype, "fast", kernel, tbs, tune, sem=sem) as s:
             got = _stepped(s, f0, FAM_CALLS)
             if kernel == "tb":
                 assert s.describe()["steps_per_launch"] == tbs
+            _plan_is(s, tuple(want))
         _same_bits(refs[nx, ny], got, (kernel, tbs, tune))
     for nx, ny in ((5, 4), (6, 6)):
         f0 = state("S2", nx, ny, dtype)
-        with _open(nx, ny, coll, turb, dtype, "fast", "generic", 0, {}) as g, _open(nx, ny, coll, turb, dtype, "fast", "auto", 0, {}) as a:
+        with _open(nx, ny, coll, turb, dtype, "fast", "generic", 0, {}, sem=sem) as g, \
+                _open(nx, ny, coll, turb, dtype, "fast", "auto", 0, {}, sem=sem) as a:
             _same_bits(_stepped(g, f0, FAM_CALLS), _stepped(a, f0, FAM_CALLS), (nx, ny))
     nx, ny = 96, 80
     f0 = state("S2", nx, ny, dtype)
     alone = []
     for r in BATCH_RATES:
-        with CavitySolver(nx, ny, RE, RT=coll, dtype=dtype, turb=turb, arith="fast", kernel="generic") as g:
+        with CavitySolver(nx, ny, RE, RT=coll, dtype=dtype, turb=turb, arith="fast", kernel="generic", semantics=sem) as g:
             g.set_relaxation(0, **r)
             alone.append(_stepped(g, f0, (29,))[0])
-    with CavityBatch(nx, ny, [r["Re"] for r in BATCH_RATES], RT=coll, dtype=dtype, turb=turb, arith="fast") as b:
+    with CavityBatch(nx, ny, [r["Re"] for r in BATCH_RATES], RT=coll, dtype=dtype, turb=turb, arith="fast", semantics=sem) as b:
         for i, r in enumerate(BATCH_RATES):
             b.set_relaxation(i, **r)
         b.set_state(np.ascontiguousarray(np.stack([f0] * 3)))
@@ -221,7 +301,7 @@ def test_fast_gives_the_same_bits_in_every_kernel_from_an_off_equilibrium_state(
         if turb:
             got["tau"] = tau[i]
         _same_bits([alone[i]], [got], ("batch", i))
-    slabs = [_open(nx, ny, coll, turb, dtype, "fast", "auto", 0, {}, rows=r) for r in partition_rows(ny, 3)]
+    slabs = [_open(nx, ny, coll, turb, dtype, "fast", "auto", 0, {}, rows=r, sem=sem) for r in partition_rows(ny, 3)]
     try:
         assert slabs[0].y0 == 0
         for s in slabs:
@@ -233,9 +313,38 @@ def test_fast_gives_the_same_bits_in_every_kernel_from_an_off_equilibrium_state(
     finally:
         for s in slabs:
             s.close()
-    with _open(nx, ny, coll, turb, dtype, "fast", "generic", 0, {}) as g:
+    with _open(nx, ny, coll, turb, dtype, "fast", "generic", 0, {}, sem=sem) as g:
         ref = _stepped(g, f0, (29,))[0]
     _same_bits([dict(fin=ref["fin"], u=ref["u"], rho=ref["rho"])], [dict(fin=fin, u=u, rho=rho)], "slabs")
+
+
+def _strict_equals_the_oracle_everywhere(sem, families, dtype, arith, coll, turb):
+    """From S2 at the distinct rates, every family and the smallest lattices with `auto` against the lattice-type oracle at the same
+    rates, bit for bit after every call."""
+    prom = arith == "promoted"
+    runs = [(_shape(kernel), kernel, tbs, tune, tuple(want)) for kernel, tbs, tune, *want in families
+            if not ((prom and tune.get("stream_pairs")) or (kernel == "push" and turb))]
+    for (nx, ny), kernel, tbs, tune, want in runs + [(shape, "auto", 0, {}, ()) for shape in ((5, 4), (6, 6))]:
+        f0 = state("S2", nx, ny, dtype)
+        o = _lattice_oracle(sem, nx, ny, coll, dtype, turb, DISTINCT, prom)
+        o.set_state(f0)
+        with _open(nx, ny, coll, turb, dtype, arith, kernel, tbs, tune, sem=sem) as s:
+            _plan_is(s, want)
+            s.set_state(f0)
+            for n in FAM_CALLS:
+                s.step(n); o.step(n)
+                u, rho, fin = s.get_fields(want_fin=True)
+                assert np.array_equal(fin, o.fin) and np.array_equal(u, o.u) and np.array_equal(rho, o.rho), \
+                    ((nx, ny), kernel, tbs, tune, o.nsteps)
+
+
+@pytest.mark.parametrize("coll,turb", [("SRT", 0), ("SRT", 1), ("TRT", 0), ("TRT", 1), ("MRT", 0), ("MRT", 1)])
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+def test_fast_gives_the_same_bits_in_every_kernel_from_an_off_equilibrium_state(dtype, coll, turb):
+    """arith = fast from S2 at the distinct rates: generic, vec, push (no closure), tb 2-5, stream (frame 3 / 8, walls 5, pairs 8) give the
+    same bits, fields and tau after every call; so do the smallest lattices (5 x 4, 6 x 6), a batch of three lattices with their own
+    rates (each = the lattice alone) and three slabs, the first holding the lid."""
+    _fast_same_bits_everywhere("mrt_gpu", FAMILIES, dtype, coll, turb)
 
 
 @pytest.mark.parametrize("coll,turb", [("SRT", 0), ("SRT", 1), ("TRT", 0), ("TRT", 1), ("MRT", 0), ("MRT", 1)])
@@ -243,27 +352,24 @@ def test_fast_gives_the_same_bits_in_every_kernel_from_an_off_equilibrium_state(
 def test_strict_and_promoted_match_the_oracle_at_distinct_rates_in_every_kernel(dtype, arith, coll, turb):
     """The same kernel list from S2 at the distinct rates, strict (fp32, fp64) and promoted (fp32; not the two-rows-per-wave
     kernel, which refuses it) against the C oracle at the same rates, bit for bit after every call."""
-    prom = arith == "promoted"
-    for kernel, tbs, tune in FAMILIES:
-        if (prom and tune.get("stream_pairs")) or (kernel == "push" and turb):
-            continue
-        nx, ny = _shape(kernel)
-        f0 = state("S2", nx, ny, dtype)
-        o = CavityOracleC(nx, ny, RE, semantics="mrt_gpu", collision=coll, dtype=dtype, turb=turb, promote=prom, **DISTINCT)
-        o.set_state(f0)
-        with _open(nx, ny, coll, turb, dtype, arith, kernel, tbs, tune) as s:
-            s.set_state(f0)
-            for n in FAM_CALLS:
-                s.step(n); o.step(n)
-                u, rho, fin = s.get_fields(want_fin=True)
-                assert np.array_equal(fin, o.fin) and np.array_equal(u, o.u) and np.array_equal(rho, o.rho), (kernel, tbs, tune, o.nsteps)
-    for nx, ny in ((5, 4), (6, 6)):
-        f0 = state("S2", nx, ny, dtype)
-        o = CavityOracleC(nx, ny, RE, semantics="mrt_gpu", collision=coll, dtype=dtype, turb=turb, promote=prom, **DISTINCT)
-        o.set_state(f0)
-        with _open(nx, ny, coll, turb, dtype, arith, "auto", 0, {}) as s:
-            s.set_state(f0)
-            for n in FAM_CALLS:
-                s.step(n); o.step(n)
-                u, rho, fin = s.get_fields(want_fin=True)
-                assert np.array_equal(fin, o.fin) and np.array_equal(u, o.u) and np.array_equal(rho, o.rho), ((nx, ny), o.nsteps)
+    _strict_equals_the_oracle_everywhere("mrt_gpu", FAMILIES, dtype, arith, coll, turb)
+
+
+@pytest.mark.parametrize("coll", ["SRT", "TRT", "MRT"])
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+@pytest.mark.parametrize("sem", ["mrt_py", "bounce_back"])
+def test_fast_gives_the_same_bits_in_every_kernel_under_the_other_walls(sem, dtype, coll):
+    """WALL_FAMILIES[sem] (generic, push under MRT.py's walls, tb 2-5, stream with the frame at 3 / 8 steps), the smallest lattices,
+    the batch and the slabs: one set of bits for arith = fast.  Under MRT.py's walls those are the oracle's bits in every family."""
+    _fast_same_bits_everywhere(sem, WALL_FAMILIES[sem], dtype, coll, 0)
+    if sem == "mrt_py":
+        _strict_equals_the_oracle_everywhere(sem, WALL_FAMILIES[sem], dtype, "fast", coll, 0)
+
+
+@pytest.mark.parametrize("coll", ["SRT", "TRT", "MRT"])
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+@pytest.mark.parametrize("sem", ["mrt_py", "bounce_back"])
+def test_strict_matches_the_oracle_at_distinct_rates_in_every_kernel_under_the_other_walls(sem, dtype, coll):
+    """WALL_FAMILIES[sem] and the smallest lattices, strict, against the C oracle (MRT.py's walls) or tests/bounce_back_ref.py
+    (bounce-back) at the distinct rates, bit for bit after every call."""
+    _strict_equals_the_oracle_everywhere(sem, WALL_FAMILIES[sem], dtype, "strict", coll, 0)

@@ -137,7 +137,8 @@ def test_checkpoint_round_trip(tmp_path):
 # fast arithmetic against strict fp64 (the GPU's strict fp64 = the reference, bit for bit, test above): max |f_fast - f_ref| / max |f_ref|
 # over the populations after 2000 steps of a 128 x 96 lattice at Re 1000, every operator.  Measured (MI355X, FAST_MEASURED: the fp32
 # figures are mostly fp32's own distance from fp64); the bounds are the largest of each type with a factor of four of headroom, as
-# tests/test_arith_error_budget_gpu.py sets its bounds.
+# tests/test_arith_error_budget_gpu.py sets its bounds.  The tighter check, against a long-double reference from off-equilibrium states after
+# 1 .. 26 steps, is that file's test_fast_stays_within_the_budget_under_the_other_walls.
 FAST_MEASURED = {(np.float32, "SRT"): 2.940e-05, (np.float32, "TRT"): 2.956e-05, (np.float32, "MRT"): 1.616e-05,
                  (np.float64, "SRT"): 1.419e-14, (np.float64, "TRT"): 1.476e-14, (np.float64, "MRT"): 2.920e-15}
 FAST_BOUND = {np.float32: 1.2e-4, np.float64: 6e-14}
