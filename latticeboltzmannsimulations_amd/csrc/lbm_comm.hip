@@ -1,5 +1,5 @@
-// lbm_comm.hip -- the lazily bound RCCL table, ghost-row exchanges between y-slabs (one step and S steps deep), their ordering
-// against the compute stream, and the host-transported halo entry points.
+// lbm_comm.hip -- the lazily bound RCCL table, ghost-row exchanges between y-slabs (one step and S steps deep) and the
+// host-transported halo entry points.
 #include "lbm_host.hpp"
 
 namespace lbmhost {
@@ -164,30 +164,6 @@ int enqueue_deep_exchange(lbm_ctx* c, int which, int S) {
     return LBM_OK;
 }
 
-// An exchange is enqueued on s_comm AHEAD of the wait for the previous bulk kernel, so that it runs beside it.  That is only right if
-// the rows it sends were written by work on s_comm itself: the previous unit's frame passes / edge launch (F rows) or edge kernel
-// (one row).  The S rows of a deep exchange after a SINGLE step, and any exchange at the start of a call (the lattice may come from
-// an upload, an import or a recomputation on s_compute), must wait for s_compute first -- found by a soak of several solvers in
-// one process (tools/soak.py seq: the first solver of a process was slow enough to hide it; profiles/r02_logs/soak_bisect2.log).
-int exchange_ready(lbm_ctx* c, int rows) {
-#ifdef LBM_DEBUG
-    static const bool off = std::getenv("LBM_DEBUG_NO_EXCHANGE_READY") != nullptr;   // (debug builds: shows that the tests see the race)
-    if (off) return LBM_OK;
-#endif
-    if (c->edge_rows < rows) {
-        const int rc = flush_int(c);
-        if (rc) return rc;
-        HIP_TRY(c, hipStreamWaitEvent(c->s_comm, c->ev_int, 0));
-    }
-    return LBM_OK;
-}
-
-// later single-stream work (export, timing event, externally driven calls) must see the s_comm results
-int join_comm(lbm_ctx* c) {
-    HIP_TRY(c, hipEventRecord(c->ev_halo, c->s_comm));
-    HIP_TRY(c, hipStreamWaitEvent(c->s_compute, c->ev_halo, 0));
-    return LBM_OK;
-}
 // lbm_halo_export_rows / lbm_halo_import_rows: the send / receive blocks of an S-step exchange, through host memory.
 static int copy_rows(lbm_ctx* c, int side, int nrows, void* buf, bool out) {
     if (!c || !buf || (side != LBM_SIDE_LOW && side != LBM_SIDE_HIGH) || nrows < 1 || nrows >= GHY || nrows > c->plan.geo.ny)
@@ -275,7 +251,7 @@ int lbm_comm_init(lbm_ctx* c, int nranks, int rank, const void* uid128) {
     NCCL_TRY(c, rccl().CommInitRank(&c->comm, nranks, id, rank));
     c->nranks = nranks;
     c->rank = rank;
-    c->thin_valid = false;
+    c->order.set_thin_valid(false);
     if (nranks > 1) {
         // Neighbours must run the same launch plan (they post matching send / receive sequences): compare it once.
         constexpr int NW = 16;
@@ -349,7 +325,7 @@ int lbm_comm_loopback(lbm_ctx* c) {
     c->nranks = 1;
     c->rank = 0;
     c->loopback = true;
-    c->thin_valid = false;
+    c->order.set_thin_valid(false);
     return LBM_OK;
 }
 }  // extern "C"

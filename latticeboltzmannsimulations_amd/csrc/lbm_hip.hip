@@ -154,7 +154,8 @@ int reduce_u(lbm_ctx* c) {
 // has synchronised the streams.
 static void reset_run_state(lbm_ctx* c) {
     for (int i = 0; i < NSAMPLERS; ++i) sampler_free(c, i);
-    c->cur = 0; c->raw[0] = 1; c->raw[1] = 1; c->nsteps = 0; c->lag = 0; c->lag_valid = false; c->thin_valid = false;
+    c->cur = 0; c->raw[0] = 1; c->raw[1] = 1; c->nsteps = 0; c->lag = 0; c->lag_valid = false;
+    c->order.reset();
 }
 }  // namespace lbmhost
 
@@ -193,6 +194,9 @@ lbm_ctx* lbm_create(const lbm_params* p, char* err, size_t errlen) {
     if (!make_plan(*p, ncu, true, plan, plan_err)) return bail(plan_err);
     lbm_ctx* c = new (std::nothrow) lbm_ctx(*p, plan);
     if (!c) return bail("out of host memory");
+#ifdef LBM_DEBUG
+    c->order.debug_no_exchange_ready = std::getenv("LBM_DEBUG_NO_EXCHANGE_READY") != nullptr;
+#endif
     const size_t bytes = c->plan.lat_bytes;
     auto cleanup = [&](const std::string& m) -> lbm_ctx* { lbm_destroy(c); return bail(m); };
     if ((e = hipStreamCreateWithFlags(&c->s_compute, hipStreamNonBlocking)) != hipSuccess) return cleanup("hipStreamCreate");

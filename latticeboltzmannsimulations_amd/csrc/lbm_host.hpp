@@ -3,13 +3,16 @@
 // crosses a unit.
 //   lbm_hip.hip     context life cycle, state upload / field export, probes              (C ABI: create .. get_tau, probes)
 //   lbm_plan.hip    parameter validation, launch planning, unit sequence, the dry run    (C ABI: next_unit, describe, plan)
-//   lbm_launch.hip  kernel launches and the step loop (single / multi-step units, lag)   (C ABI: step*, time_steps)
+//   lbm_launch.hip  kernel launches and the step loop (run_unit, the lagged lattice)      (C ABI: step*, time_steps)
 //   lbm_sampling.hip what the samplers share (schedule: lbm_schedule.hpp; record series; the sampling prologue), the time statistics
 //                                                                                          (C ABI: stats_*)
 //   lbm_comm.hip    RCCL binding, halo exchanges, host-transported halos                 (C ABI: halo_*, comm_*)
 //   lbm_monitor.hip the run monitor and the line export (kernels: lbm_monitor.hpp)        (C ABI: monitor*, get_lines)
 //   lbm_residual.hip the field residual (kernels: lbm_residual.hpp)                        (C ABI: residual_*)
 //   lbm_topology.hip stream function, vorticity, extrema of psi (kernels: lbm_topology.hpp) (C ABI: topology, get_stream_function)
+// and two headers free of HIP, each driven by a CPU test through a program of its own:
+//   lbm_schedule.hpp the schedule of automatic sampling
+//   lbm_order.hpp    the ordering of the two streams: the state carried between units, the skeletons of a unit, the argument
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>  // types and prototypes only: RCCL is bound lazily with dlopen (see rccl_api)
@@ -27,6 +30,7 @@
 
 #include "../../include/lbm.h"
 #include "lbm_schedule.hpp"
+#include "lbm_order.hpp"
 #include "lbm_inst.hpp"   // the kernels, and extern template declarations of the multi-step ones (compiled in lbm_{tiles,stream*}_f32/f64.hip)
 
 // ------------------------------------------------------------------------------------
@@ -135,15 +139,9 @@ struct lbm_ctx {
     double* topo_fields = nullptr;
     ncclComm_t comm = nullptr;
     int nranks = 1, rank = 0;
-    bool thin_valid = false;    // the one-row halo of lat[cur] has been exchanged (by the RCCL path, on s_comm)
     bool loopback = false;      // diagnostic: 1-rank communicator, the slab exchanges halos with itself
-    int edge_rows = 0;          // rows next to each interface of lat[cur] that work on s_comm wrote (and s_comm's stream order therefore covers):
-                                // the frame width after a multi-step unit, 1 after a single step, 0 at the start of a call (see exchange_ready)
+    lbmhost::Order order;       // what the two streams carry from one unit to the next (lbm_order.hpp); its device: HipDev below
     void* relax_dev = nullptr;  // batch > 1: Relax<real>[batch] on the device
-    // The units of a lone lattice that need no second stream (frame and tiles / the walls inside: ONE launch on s_compute) neither wait for
-    // ev_edges nor record ev_int -- two event operations per unit, 7 - 8 % of a launch-bound lattice's step (160^2: 3.51 -> 3.24 us).  Instead:
-    bool int_stale = false;      // s_compute has work that ev_int does not cover yet: flush_int() before s_comm is made to wait for ev_int
-    bool edges_pending = false;  // ev_edges was recorded (work on s_comm) and s_compute has not been made to wait for it since
     std::string err;
 };
 
@@ -184,23 +182,20 @@ inline int fail(lbm_ctx* c, int code, const std::string& msg) {
             return fail((c), LBM_ERR_COMM, std::string(#expr) + ": " + rccl().GetErrorString(r_));     \
     } while (0)
 
-// ev_int, recorded lazily (lbm_ctx::int_stale): whoever makes s_comm wait for ev_int calls this first
-inline int flush_int(lbm_ctx* c) {
-    if (c->int_stale) {
-        HIP_TRY(c, hipEventRecord(c->ev_int, c->s_compute));
-        c->int_stale = false;
+// The device of c->order: its events and streams are the context's.
+struct HipDev {
+    lbm_ctx* c;
+    hipStream_t stream(Stream s) const { return s == Stream::COMPUTE ? c->s_compute : c->s_comm; }
+    hipEvent_t event(Event e) const { return e == Event::INT ? c->ev_int : e == Event::EDGES ? c->ev_edges : e == Event::GO ? c->ev_go : c->ev_halo; }
+    int record(Event e, Stream s) {
+        HIP_TRY(c, hipEventRecord(event(e), stream(s)));
+        return LBM_OK;
     }
-    return LBM_OK;
-}
-// ev_edges, waited for lazily (lbm_ctx::edges_pending): whoever puts work on s_compute that needs what s_comm wrote (the frame work of an
-// earlier multi-step unit) calls this first
-inline int join_edges(lbm_ctx* c) {
-    if (c->edges_pending) {
-        HIP_TRY(c, hipStreamWaitEvent(c->s_compute, c->ev_edges, 0));
-        c->edges_pending = false;
+    int wait(Stream s, Event e) {
+        HIP_TRY(c, hipStreamWaitEvent(stream(s), event(e), 0));
+        return LBM_OK;
     }
-    return LBM_OK;
-}
+};
 
 template <typename R>
 Relax<R> relax_of(const lbm_params& p) {
@@ -364,8 +359,7 @@ int launch_stream_edges(lbm_ctx* c, int from, int to, hipStream_t s, int S, bool
 int warm_stream(lbm_ctx* c);
 int launch_deep(lbm_ctx* c, int from, int to, hipStream_t s, int steps, bool with_frame = false);
 void finish_unit(lbm_ctx* c, int S);
-int single_step(lbm_ctx* c, bool* comm_used, bool rccl_x);
-int multi_step(lbm_ctx* c, bool* comm_used, int S, bool rccl_x);
+int run_unit(lbm_ctx* c, bool* comm_used, int S, bool rccl_x);
 int prev_lattice(lbm_ctx* c, int* which);
 int push_step(lbm_ctx* c);
 int push_reset(lbm_ctx* c);
@@ -398,6 +392,4 @@ RowBlocks deep_blocks(lbm_ctx* c, int which, int r0, int S);
 int deep_send_row0(const lbm_ctx* c, int side, int S);
 int deep_recv_row0(const lbm_ctx* c, int side, int S);
 int enqueue_deep_exchange(lbm_ctx* c, int which, int S);
-int exchange_ready(lbm_ctx* c, int rows);
-int join_comm(lbm_ctx* c);
 }  // namespace lbmhost

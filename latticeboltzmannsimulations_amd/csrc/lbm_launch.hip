@@ -1,5 +1,5 @@
-// lbm_launch.hip -- kernel launches (row kernels, frame passes, tile kernel, streaming kernels) and the step loop: single-step and
-// multi-step units, the lagged lattice, the overlap of halo exchange and interior work.
+// lbm_launch.hip -- kernel launches (row kernels, frame passes, tile kernel, streaming kernels) and the step loop: the launch unit
+// (run_unit: which work goes on which stream; their ordering is lbm_order.hpp's), the lagged lattice.
 #include "lbm_host.hpp"
 
 namespace lbmhost {
@@ -240,7 +240,7 @@ void finish_unit(lbm_ctx* c, int S) {
     c->nsteps += S;
     c->lag = S - 1;
     c->lag_valid = false;
-    c->thin_valid = false;
+    c->order.set_thin_valid(false);
 }
 
 // The frame work of a unit of S steps on route `route` (edges_bulk, fused_frame or frame_passes: unit_route), lat[from] -> lat[to] on
@@ -260,124 +260,53 @@ static int launch_frame_work(lbm_ctx* c, Route route, int from, int to, hipStrea
     return rc;
 }
 
-// Every launch unit (one single step or one multi-step) of a slab follows one protocol on the two streams:
-//   s_comm    (highest priority): [the unit's halo exchange -- RCCL, or nothing when the caller has moved the rows] ->
-//                                 waits ev_int (bulk kernel of the previous unit) -> wall / slab-edge work of this unit ->
-//                                 records ev_edges;
-//   s_compute                   : waits ev_edges of the PREVIOUS unit, runs the bulk kernel, records ev_int.
-// The exchange of a unit is enqueued first: it only touches rows that the edge / frame kernels of the previous unit wrote
-// (same stream, in order) and ghost rows, so it runs beside the previous unit's bulk kernel (exchange_ready() adds the wait for
-// s_compute where that premise does not hold); the small kernels run beside the bulk kernel of the same unit.  Nothing is carried from one unit to the next except thin_valid (a one-row halo that is
-// already in place, e.g. the one lbm_step leaves for lbm_get_fields).
-int single_step(lbm_ctx* c, bool* comm_used, bool rccl_x) {
+// One launch unit of S >= 1 steps, lat[a] (state n) -> lat[b] (state n + S).  It picks the unit's work and hands it to the skeleton
+// that orders the two streams (lbm_order.hpp, with the argument why that order is enough):
+//   a lone lattice in one launch   all rows (S = 1), or frame and bulk / the walls inside (launch_deep, with_frame) on s_compute;
+//   S = 1 on a slab                the edge rows 0 and ny - 1, which read the ghost rows, on s_comm | the interior rows on s_compute;
+//   S >= 2 on two streams          the frame work (launch_frame_work) on s_comm | the bulk kernel (launch_deep) on s_compute.
+// Bulk: the deep-interior kernel on cells >= tb_f away from walls and slab edges.  Frame: S ordinary single steps on strips of
+// decreasing width (tb_f + S - i for pass i; pass i+1 pulls from one cell further out than it writes), through the scratch lattices,
+// the last one into lat[b]; under the streaming kernel the frame work of a slab is its edge launch (launch_stream_edges: column
+// strips + the interface rows as short streaming segments).  (Running row and column strips as separate launches on separate
+// streams was measured and lost 8 %: profiles/r01_logs/perf31.log, perf35.log.)
+// rccl_x: the library moves the halos (lbm_step); otherwise the caller has (lbm_step_unit).  The unit's exchange: a raw lattice is
+// not streamed and needs none; with the deep halo (MRT_GPU semantics, S >= 2) the S rows next to each interface, of which the row
+// strips of pass i use S - i, the unit's only exchange; otherwise one row, unless the last call left it in place, and
+// one more after every frame pass but the last (launch_frame_work).
+int run_unit(lbm_ctx* c, bool* comm_used, int S, bool rccl_x) {
     const int ny = c->plan.geo.ny, a = c->cur, b = c->cur ^ 1;
-    if (is_slab(c->plan)) {
-        // edge rows 0 and ny-1 (they read the ghost rows) | interior rows
-        if (rccl_x && !c->raw[a] && !c->thin_valid) {   // (a raw lattice is not streamed: no halo needed)
-            int rc = exchange_ready(c, 1);
-            if (rc == LBM_OK) rc = enqueue_exchange(c, a);
-            if (rc) return rc;
-        }
-        int rc = flush_int(c);
-        if (rc) return rc;
-        HIP_TRY(c, hipStreamWaitEvent(c->s_comm, c->ev_int, 0));
-        rc = launch_rows(c, a, b, 0, ny - 1, 2, c->s_comm);
-        if (rc) return rc;
-        HIP_TRY(c, hipStreamWaitEvent(c->s_compute, c->ev_edges, 0));
-        HIP_TRY(c, hipEventRecord(c->ev_edges, c->s_comm));
-        c->edges_pending = true;
-        rc = launch_rows(c, a, b, 1, 1, ny - 2, c->s_compute);
-        if (rc) return rc;
-        HIP_TRY(c, hipEventRecord(c->ev_int, c->s_compute));
-        finish_unit(c, 1);
-        c->edge_rows = 1;
-        *comm_used = true;
-        return LBM_OK;
-    }
-    int rc = join_edges(c);   // frame kernels of an earlier multi-step
-    if (rc == LBM_OK) rc = launch_rows(c, a, b, 0, 1, ny, c->s_compute);
-    if (rc) return rc;
-    c->int_stale = true;
-    finish_unit(c, 1);
-    return LBM_OK;
-}
-
-// S steps: lat[a] (state n) -> lat[b] (state n+S).  Bulk: the deep-interior kernel on cells >= tb_f away
-// from walls and slab edges.  Frame: S ordinary single steps on strips of decreasing width (tb_f + S - i for pass i; pass i+1
-// pulls from one cell further out than it writes), through the scratch lattices, the last one into lat[b].
-// Between slabs the frame passes and the exchanges share the second stream, beside the tile kernel; under the streaming kernel the
-// frame work of a slab is its edge launch (launch_stream_edges: column strips + the interface rows as short streaming segments).  With the deep halo
-// (MRT_GPU semantics) the row strips of pass i start S - i rows inside the neighbour's rows received before the unit, and that
-// is the unit's only exchange; otherwise every pass but the last is followed by a one-row exchange.  (Running row and
-// column strips as separate launches on separate streams was measured and lost 8 %: profiles/r01_logs/perf31.log, perf35.log.)
-int multi_step(lbm_ctx* c, bool* comm_used, int S, bool rccl_x) {
-    const Route route = unit_route(c->plan, S, false);
-    if (route == Route::one_launch) {   // a lone lattice: frame and tiles in ONE launch, everything on the compute stream
-        int rc = join_edges(c);   // (frame launches of an earlier unit on the second stream, if any)
-        if (rc == LBM_OK) rc = launch_deep(c, c->cur, c->cur ^ 1, c->s_compute, S, true);
-        if (rc) return rc;
-        c->int_stale = true;      // (ev_int is recorded when something on s_comm is made to wait for it: flush_int)
-        finish_unit(c, S);
-        return LBM_OK;
-    }
-    const bool slab = is_slab(c->plan), deep = slab && c->plan.deep_halo;
-    if (slab && !deep && !rccl_x) return fail(c, LBM_ERR_STATE, "a multi-step unit of a slab needs the deep halo (MRT_GPU semantics) or the in-library exchange");
-    const int a = c->cur, b = c->cur ^ 1;
+    const bool slab = is_slab(c->plan), deep = slab && S > 1 && c->plan.deep_halo;
+    const Route route = S > 1 ? unit_route(c->plan, S, false) : Route::one_launch;
+    HipDev dev{c};
     int rc;
-    if (slab && rccl_x && (deep || !c->thin_valid)) {
-        rc = exchange_ready(c, deep ? S : 1);
-        if (rc == LBM_OK) rc = deep ? enqueue_deep_exchange(c, a, S) : enqueue_exchange(c, a);
-        if (rc) return rc;
-    }
-    rc = flush_int(c);
-    if (rc) return rc;
-    HIP_TRY(c, hipStreamWaitEvent(c->s_comm, c->ev_int, 0));
-    HIP_TRY(c, hipStreamWaitEvent(c->s_compute, c->ev_edges, 0));   // this unit's tile kernel needs the previous unit's frame
-    if (route == Route::edges_bulk) {
-        // The streaming kernel between slabs: the edge launch (interface rows + column strips, everything the next exchange sends)
-        // here, the bulk launch below.  Both become ready when the previous bulk launch ends, and the bulk launch -- one
-        // workgroup per CU for its whole run -- must not take the CUs first: the edge workgroups would run last, and the next
-        // exchange after them, in the open.  So the bulk launch is released from THIS stream, one cross-stream hop behind the
-        // edge launch -- when the bulk launch runs more than one round of workgroups (16384 x 2048 fp32 slab in loopback 319 -> 359
-        // GLUPS, 8192 x 1024 fp64 133 -> 142); a one-round launch does not gain and a short one loses (4096 x 4096 355 -> 351,
-        // 4096 x 1024 249 -> 205: profiles/r02_logs/slab_loopback7.log).
-        //
-        // Why the release (ev_go) and the early exchange cannot break an ordering -- unit n goes lat[a] -> lat[b]; E = exchange, G = edge
-        // launch, B = bulk launch; s_comm runs  E_n, wait(ev_int: B_{n-1}), [record ev_go], G_n, record ev_edges;  s_compute runs
-        // wait(ev_edges: G_{n-1}), [wait ev_go], B_n, record ev_int:
-        //   * E_n sends rows [0, S) / [ny - S, ny) of lat[a] and fills lat[a]'s ghost rows.  The rows it sends lie inside the F >= S edge
-        //     rows G_{n-1} wrote -- same stream, earlier -- unless the previous unit was no streaming unit: then edge_rows < S and
-        //     exchange_ready() makes s_comm wait for ev_int first.  Nothing else touches those rows or lat[a]'s ghost rows meanwhile:
-        //     B_{n-1}, which may still run, writes lat[a]'s rows [F, ny - F) only and reads lat[b].
-        //   * G_n reads lat[a] up to F + S - 1 rows from an interface plus the ghost rows: written by G_{n-1} and E_n (same stream,
-        //     earlier) and by B_{n-1} (the wait on ev_int sits between E_n and G_n).  It writes lat[b]'s edge rows, last read by
-        //     G_{n-1} / E_{n-1} (same stream, earlier) and by B_{n-1} (waited for).
-        //   * B_n reads lat[a]'s rows from F - (S - 1) on: B_{n-1}'s (same stream) and G_{n-1}'s (the wait on ev_edges, recorded after
-        //     G_{n-1}).  It writes lat[b]'s rows [F, ny - F): last read by B_{n-1} (same stream) and G_{n-1} (waited for).  The next
-        //     exchange E_{n+1}, which may run beside B_n, touches lat[b]'s edge and ghost rows only -- disjoint from B_n's.
-        //   * ev_go only ADDS an edge: B_n after everything s_comm had enqueued when it was recorded (E_n and the wait for B_{n-1}).  It is
-        //     recorded (host order) before s_compute is told to wait for it, and what it waits for -- ev_int of unit n - 1 -- was recorded
-        //     on s_compute before that wait: no cycle, no wait on an event not yet recorded.  Its price: B_n also waits for E_n, which it
-        //     does not need; E_n has had the whole of B_{n-1} to finish, so this costs only when a neighbour is that late -- and then G_n,
-        //     which B_{n+1} needs, waits for the same exchange anyway.
-        // (the events are re-recorded every unit: a wait refers to the last record before it in host order -- the one named above)
-        const StreamPlan pl = plan_stream(c->plan, S);
-        if (c->plan.edge_first && (long long)pl.nstrips * pl.nsegy > c->plan.ncu) {
-            HIP_TRY(c, hipEventRecord(c->ev_go, c->s_comm));
-            HIP_TRY(c, hipStreamWaitEvent(c->s_compute, c->ev_go, 0));
+    if (S > 1 ? route == Route::one_launch : !slab) {
+        rc = one_stream_unit(c->order, dev, [&] {
+            return S > 1 ? launch_deep(c, a, b, c->s_compute, S, true) : launch_rows(c, a, b, 0, 1, ny, c->s_compute);
+        });
+    } else {
+        if (S > 1 && slab && !deep && !rccl_x) return fail(c, LBM_ERR_STATE, "a multi-step unit of a slab needs the deep halo (MRT_GPU semantics) or the in-library exchange");
+        const bool exchange = slab && rccl_x && !c->raw[a] && (deep || !c->order.thin_valid());
+        // The streaming kernel between slabs: edge launch and bulk launch both become ready when the previous bulk launch ends, and the
+        // bulk launch -- one workgroup per CU for its whole run -- must not take the CUs first: the edge workgroups would run last, and
+        // the next exchange after them, in the open.  So the bulk launch is held one cross-stream hop behind the edge launch -- when it
+        // runs more than one round of workgroups (16384 x 2048 fp32 slab in loopback 319 -> 359 GLUPS, 8192 x 1024 fp64 133 -> 142); a
+        // one-round launch does not gain and a short one loses (4096 x 4096 355 -> 351, 4096 x 1024 249 -> 205:
+        // profiles/r02_logs/slab_loopback7.log).
+        bool hold = false;
+        if (route == Route::edges_bulk && c->plan.edge_first) {
+            const StreamPlan pl = plan_stream(c->plan, S);
+            hold = (long long)pl.nstrips * pl.nsegy > c->plan.ncu;
         }
+        rc = two_stream_unit(
+            c->order, dev, exchange ? (deep ? S : 1) : 0, hold, S > 1 ? c->plan.tb_f : 1,
+            [&] { return deep ? enqueue_deep_exchange(c, a, S) : enqueue_exchange(c, a); },
+            [&] { return S > 1 ? launch_frame_work(c, route, a, b, c->s_comm, S, 0) : launch_rows(c, a, b, 0, ny - 1, 2, c->s_comm); },
+            [&] { return S > 1 ? launch_deep(c, a, b, c->s_compute, S) : launch_rows(c, a, b, 1, 1, ny - 2, c->s_compute); });
+        *comm_used = true;
     }
-    rc = launch_frame_work(c, route, a, b, c->s_comm, S, 0);
     if (rc) return rc;
-    HIP_TRY(c, hipEventRecord(c->ev_edges, c->s_comm));
-    c->edges_pending = true;
-    rc = launch_deep(c, a, b, c->s_compute, S);
-    if (rc) return rc;
-    HIP_TRY(c, hipEventRecord(c->ev_int, c->s_compute));
-    c->int_stale = false;
     finish_unit(c, S);
-    c->edge_rows = c->plan.tb_f;
-    *comm_used = true;
     return LBM_OK;
 }
 
@@ -395,7 +324,9 @@ int prev_lattice(lbm_ctx* c, int* which) {
     }
     const int k = c->lag, from = c->cur ^ 1;
     const Route route = unit_route(c->plan, k, true);
-    int rc = LBM_OK;
+    HipDev dev{c};
+    int rc = c->order.one_stream(dev);   // (everything below runs on s_compute)
+    if (rc) return rc;
     if (route == Route::one_launch) {
         rc = launch_deep(c, from, LAT_LAG, c->s_compute, k, true);
     } else if (route != Route::single_steps) {   // the frame, then the bulk (a slab: from the deep halo still in lat[from]'s ghost rows)
@@ -460,27 +391,26 @@ int step_many(lbm_ctx* c, int nsteps) {
         return fail(c, LBM_ERR_STATE, "lbm_step on a slab without a communicator: its ghost rows would never be exchanged (attach one with "
                                       "lbm_comm_init, or drive the slab with lbm_step_edges/interior/finish, lbm_step_unit and the lbm_halo_* calls)");
     bool comm_used = false;
-    if (c->plan.kern != Kern::none || slab)   // (a lone lattice stepping one step per launch uses one stream, no events)
-        HIP_TRY(c, hipEventRecord(c->ev_int, c->s_compute));   // everything enqueued so far (init, upload, earlier calls)
-    c->edge_rows = 0;        // the first exchange of the call waits for it
+    HipDev dev{c};
+    int rc = c->order.begin_call(dev, c->plan.kern != Kern::none || slab);   // (a lone lattice stepping one step per launch uses one stream, no events)
+    if (rc) return rc;
     int left = nsteps;
     while (left > 0) {
-        int rc = sample_if_due(c);
+        rc = sample_if_due(c);
         if (rc) return rc;
         const int S = unit_steps(c->plan, (int)steps_to_cut(c->sampler, c->nsteps, left), c->raw[c->cur] != 0, own_transport(c));
-        rc = S > 1 ? multi_step(c, &comm_used, S, true) : single_step(c, &comm_used, true);
+        rc = run_unit(c, &comm_used, S, true);
         if (rc) return rc;
         left -= S;
     }
     if (slab && nsteps > 0 && !c->raw[c->cur]) {   // the populations lbm_get_fields returns for the slab's first / last row need the one-row halo
-        int rc = exchange_ready(c, 1);
+        rc = c->order.before_exchange(dev, 1);
         if (rc == LBM_OK) rc = enqueue_exchange(c, c->cur);
         if (rc) return rc;
-        c->thin_valid = true;
+        c->order.set_thin_valid(true);
         comm_used = true;
     }
-    if (comm_used) return join_comm(c);
-    return LBM_OK;
+    return comm_used ? c->order.end_call(dev) : LBM_OK;
 }
 }  // namespace lbmhost
 
@@ -546,11 +476,10 @@ int lbm_step_unit(lbm_ctx* c, int S) {
                                                                " (this context's steps per launch; lbm_next_unit plans 4 or more on a slab)");
     if (is_slab(c->plan) && !c->plan.deep_halo) return fail(c, LBM_ERR_STATE, "lbm_step_unit on a slab needs the deep halo (MRT_GPU semantics)");
     bool comm_used = false;
-    HIP_TRY(c, hipEventRecord(c->ev_int, c->s_compute));   // everything enqueued so far, the imported rows included
-    c->edge_rows = 0;
-    int rc = multi_step(c, &comm_used, S, false);
+    HipDev dev{c};
+    int rc = c->order.begin_call(dev, true);   // (INT covers the imported rows)
+    if (rc == LBM_OK) rc = run_unit(c, &comm_used, S, false);
     if (rc) return rc;
-    if (comm_used) return join_comm(c);
-    return LBM_OK;
+    return comm_used ? c->order.end_call(dev) : LBM_OK;
 }
 }  // extern "C"

@@ -39,7 +39,7 @@ StreamPlan plan_stream_on(const Plan& pl, int S, int ncu, long long* cost_out) {
     if (cost_out) *cost_out = best_cost;
     return best;
 }
-// Between slabs the unit has an edge launch beside the bulk launch (multi_step).  A bulk launch of ONE round takes every CU for its
+// Between slabs the unit has an edge launch beside the bulk launch (run_unit).  A bulk launch of ONE round takes every CU for its
 // whole run, the edge workgroups (a CU each, ~48 pipeline iterations) then run after it and the next exchange after them: the
 // unit costs bulk + edges.  For a short slab it is cheaper to plan the bulk launch on fewer CUs and leave the others to the edge
 // workgroups (4096 x 512 fp32 slab in loopback: 145 -> 176 GLUPS; taller slabs lose a few per cent -- 4096 x 1024 247 -> 240, 4096 x
@@ -118,7 +118,7 @@ int unit_steps(const Plan& pl, int left, bool raw, bool own_transport) {
     return left >= m ? left : 1;
 }
 
-// The route of a launch unit of S >= 2 steps (multi_step), or of the replay of the lagged lattice, S = lag (prev_lattice).  A slab
+// The route of a launch unit of S >= 2 steps (run_unit), or of the replay of the lagged lattice, S = lag (prev_lattice).  A slab
 // replays only with the deep halo (lag_replayable).
 Route unit_route(const Plan& pl, int S, bool replay) {
     const bool slab = is_slab(pl), deep = slab && pl.deep_halo;
@@ -254,7 +254,7 @@ static std::string plan_kernel(Plan& pl, const lbm_params& p, const Forced& f, b
     const bool big = one_launch(pl) ? (p.nx >= 64 && nyp >= 64) : (long long)p.nx * nyp * pl.batch >= 768LL * 768LL;
     // The strip-streaming kernel (lbm_stream.hpp): one workgroup per CU marches down a strip of 240 fp32 / 112 fp64 useful
     // columns, up to 8 steps per launch, no rim in y.  It needs tall segments to amortise its pipeline fill, i.e. a large
-    // lattice (AUTO: below); kernel = STREAM forces it.  Between slabs the unit is an edge launch + a bulk launch (multi_step).
+    // lattice (AUTO: below); kernel = STREAM forces it.  Between slabs the unit is an edge launch + a bulk launch (run_unit).
     const bool can_stream = can_tb && p.nx >= 64 && nyp >= 64 && pl.batch == 1;
     if (p.kernel == LBM_KERNEL_STREAM && !can_stream)
         return "kernel = STREAM takes one lattice (no batch) with nx % (16 / sizeof(real)) == 0, nx >= 64, ny_local >= 64 (on every rank)";
@@ -338,7 +338,7 @@ static std::string plan_steps(Plan& pl, const lbm_params& p, const Forced& f) {
         if (pl.kern == Kern::stream_pairs) pl.tb_steps = p.tb_steps ? p.tb_steps : 10;
         else if (pl.tb_steps > ST_MAX_S)
             return "tb_steps " + std::to_string(ST_MAX_S + 1) + " .. " + std::to_string(SP_MAX_S) + " need the streaming kernel with two rows per wave (a lone lattice, MRT_GPU semantics)";
-        // A slab's unit of two steps has no edge launch (multi_step takes it through the frame passes): the walls-inside kernel, which
+        // A slab's unit of two steps has no edge launch (run_unit takes it through the frame passes): the walls-inside kernel, which
         // would write the frame's columns too, is not used there.
         if (pl.kern == Kern::stream_walls && is_slab(pl) && pl.tb_steps < 3) pl.kern = Kern::stream;
         // (with the walls inside the tails stay on the streaming kernel: the tile kernel's four steps are no faster any more -- 247 against 256
@@ -388,7 +388,7 @@ static void plan_frame(Plan& pl, const lbm_params& p, const Forced& f, bool devi
     // four streaming waves and one frame wave fit the 512 per SIMD lane (allocated in blocks of 8) -- the factored
     // operators without the Smagorinsky closure -- and only in fp64, where it pays: 4096 x 4096 fast MRT 153 -> 169 GLUPS;
     // in fp32 the frame waves slow the streaming waves by more than the 43 us they save, 367 -> 338
-    // (profiles/r02_logs/stream_ab18.log).  (A slab's frame is its edge launch, multi_step; no frame at all with the walls inside.)
+    // (profiles/r02_logs/stream_ab18.log).  (A slab's frame is its edge launch, run_unit; no frame at all with the walls inside.)
     if (pl.kern == Kern::stream && !is_slab(pl) && f.frame_beside > 0) {
         pl.frame_beside = true;
     } else if (pl.kern == Kern::stream && !is_slab(pl) && f.frame_beside == 0 && pl.es == 8 && device) {

@@ -103,11 +103,12 @@ int sample_if_due(lbm_ctx* c) {
     bool due[NSAMPLERS], any = false;
     for (int i = 0; i < NSAMPLERS; ++i) any |= due[i] = c->sampler[i].due(c->nsteps);
     if (!any) return LBM_OK;
-    int rc = join_edges(c);   // (frame work of the last unit on the second stream wrote part of lat[cur])
+    // (frame work of the last unit on the second stream wrote part of lat[cur], and s_comm must not rewrite it before the sample has read it)
+    HipDev dev{c};
+    int rc = c->order.one_stream(dev);
     for (int i = 0; i < NSAMPLERS && rc == LBM_OK; ++i)
         if (due[i]) rc = sample_from(c, i, c->cur, c->nsteps + 1);
     if (rc) return rc;
-    c->int_stale = true;      // (s_comm must not rewrite lat[cur] before the sample has read it)
     for (int i = 0; i < NSAMPLERS; ++i)
         if (due[i]) c->sampler[i].advance();
     return LBM_OK;

@@ -97,11 +97,18 @@ def test_bit_identical_to_host_loop_and_stepping_unchanged(cfg):
     """From an upload (the first sample is the raw step's), lbm_step calls that do not line up with `every`; then statistics begun
     again mid-run after a multi-step unit.  After every call: the device statistics equal the host loop over get_fields() of a second
     context at the same step counts, and fin / u / rho equal that context's (automatic sampling does not perturb the stepping)."""
+    _sampled_run_equals_host_loop(cfg, CASES.index(cfg))
+
+
+def _sampled_run_equals_host_loop(cfg, i, tuning=None, described=None):
+    """The body of the tests above and below; i picks `every` of the two phases and the uploaded state, `described` is what
+    describe() must say of both contexts."""
     kernel, dtype, coll, turb, sem, arith = cfg
     nx, ny = (97, 80) if kernel == "generic" else (192, 160)
-    i = CASES.index(cfg)
-    kw = dict(RT=coll, dtype=dtype, turb=turb, semantics=sem, kernel=kernel, arith=arith)
+    kw = dict(RT=coll, dtype=dtype, turb=turb, semantics=sem, kernel=kernel, arith=arith, tuning=tuning)
     with CavitySolver(nx, ny, 1000.0, **kw) as s, CavitySolver(nx, ny, 1000.0, **kw) as ref:
+        for name, value in (described or {}).items():
+            assert s.describe()[name] == value and ref.describe()[name] == value, (name, s.describe()[name])
         f = _perturbed(nx, ny, dtype, i)
         s.set_state(f); ref.set_state(f)
         for phase, (every, calls) in enumerate(((EVERY[i % 4], (5, 20, 1, 13)), (EVERY[(i + 1) % 4], (17, 5, 20, 1)))):
@@ -120,6 +127,17 @@ def test_bit_identical_to_host_loop_and_stepping_unchanged(cfg):
                 _same_stats(s, host, f"{_ids(cfg)} every={every} after {s.steps_done}")
                 a, b = s.get_fields(want_fin=True), ref.get_fields(want_fin=True)
                 assert all(np.array_equal(x, y) for x, y in zip(a, b)), f"{_ids(cfg)}: stepping perturbed at {s.steps_done}"
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64], ids=["float32", "float64"])
+def test_samples_between_two_stream_units_of_a_lone_lattice(dtype):
+    """The same run where the wall frame of a lone lattice runs beside the streaming kernel, on the second stream: calls (5, 20, 1, 13)
+    with every = 3, then (17, 5, 20, 1) with every = 8, so that automatic samples (one-stream work, which waits for the frame kernels
+    lazily and leaves the bulk kernel's event stale) fall between two-stream units.  Without the switch the register rule picks this
+    route for some variants only."""
+    assert (EVERY[1], EVERY[2]) == (3, 8)
+    _sampled_run_equals_host_loop(("stream", dtype, "MRT", 0, "mrt_gpu", "strict"), 1, tuning={"frame_beside": True, "stream_walls": False},
+                                  described={"frame_beside": 1})
 
 
 def test_auto_route_with_the_walls_inside_the_streaming_kernel():
