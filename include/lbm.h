@@ -48,6 +48,11 @@ enum { LBM_SEM_MRT_PY = 0, LBM_SEM_MRT_GPU = 1,        /* streaming windows + wa
                                                            state.  No macroscopic override on any cell.  Relaxation rates as
                                                            MRT_GPU (omega_eps = 1.2).  Not with turb = 1, arith = promoted,
                                                            kernel = PUSH / VEC or LBM_FLAG_STREAM_WALLS / STREAM_PAIRS. */
+enum { LBM_SEM_BOUNCE_BACK_SOLID = 3 };                 /* LBM_SEM_BOUNCE_BACK plus a per-cell solid mask (lbm_set_solid below): a source that is
+                                                           a solid cell inside the lattice bounces like a source outside it, with nothing
+                                                           added.  Whole lattices only (no slabs), one step per launch: kernel = AUTO
+                                                           (k_step_solid, 16 B per access; k_step_generic where nx is no multiple of the
+                                                           vector width) or GENERIC. */
 enum { LBM_KERNEL_AUTO = 0,      /* fastest applicable: STREAM (large lattices), TB (lattices from 64 x 64 cells), else VEC, else GENERIC */
        LBM_KERNEL_GENERIC = 1,   /* one step per launch, one thread per cell (all semantics) */
        LBM_KERNEL_VEC = 2,       /* one step per launch, 16 B per access (MRT_GPU semantics) */
@@ -95,7 +100,7 @@ typedef struct lbm_params {
     int32_t ny_local;    /* rows owned by this context (= ny when not slab-decomposed, >= 2) */
     int32_t dtype;       /* LBM_F32 | LBM_F64 */
     int32_t collision;   /* LBM_SRT | LBM_TRT | LBM_MRT */
-    int32_t semantics;   /* LBM_SEM_MRT_PY | LBM_SEM_MRT_GPU | LBM_SEM_BOUNCE_BACK */
+    int32_t semantics;   /* LBM_SEM_MRT_PY | LBM_SEM_MRT_GPU | LBM_SEM_BOUNCE_BACK | LBM_SEM_BOUNCE_BACK_SOLID */
     int32_t kernel;      /* LBM_KERNEL_* */
     int32_t turb;        /* 0 | 1: Smagorinsky closure of MRT_GPU.py:368-387 (MRT_GPU semantics only) */
     int32_t device;      /* HIP device ordinal (reference: cuda.Device(0), MRT_GPU.py:29) */
@@ -438,6 +443,47 @@ typedef struct lbm_topology_record {
 } lbm_topology_record;
 int lbm_topology(lbm_ctx* c, const lbm_topology_spec* spec, lbm_topology_record* records_out);
 int lbm_get_stream_function(lbm_ctx* c, double* psi_out, double* omega_out, int host_dtype);
+
+/* --- solid obstacles and the force on them ---------------------------------------------------- */
+/* No reference counterpart (the reference runs the empty box): solid cells inside the bounce-back cavity, LBM_SEM_BOUNCE_BACK_SOLID.
+ * The mask is mask[X][Y] uint8, host layout (y fastest, y = 0 the lid); with batch = B mask[B][X][Y], every lattice its own.  Nonzero
+ * means solid.  Any mask with at least one fluid cell per lattice is valid: solid cells may touch the walls, the lid and each other,
+ * and may enclose fluid.
+ *
+ * Fluid cell, slot k = 1 .. 8, source (x - cx_k, y + cy_k):
+ *   source outside the lattice        exactly the LBM_SEM_BOUNCE_BACK rule, lid term included;
+ *   source inside and solid           the cell's own post-collision population of the opposite direction, nothing added (obstacles
+ *                                     are at rest);
+ *   otherwise                         the source's post-collision population of direction k.
+ *   Moments, collision, rates, the first step after an upload and the parked lid density are those of LBM_SEM_BOUNCE_BACK.
+ * Solid cell: never updated.  Its populations are the constants w_k (4/9, 1/9, 1/36) rounded to the lattice type -- the rest
+ *   equilibrium at rho = 1 -- in both lattices, and a gather on it returns them.  Every export and every sampler therefore sees
+ *   fin_k = w_k, u = exactly 0 and rho = the sum of the nine w_k in the order of the moments there; nothing is NaN, and the stream
+ *   function integrates uy = 0 through a body.
+ *
+ * lbm_set_solid: LBM_ERR_STATE on a context of another semantics; LBM_ERR_INVALID for a mask that leaves a lattice no fluid cell.
+ *   Ends every sampler, stores the mask, derives the link plane (one more plane of both lattices; per cell bit k - 1: the source of
+ *   slot k is a solid cell inside the lattice, bit 8: the cell is solid) and performs lbm_init_equilibrium; solid cells then hold w_k.
+ *   A later lbm_set_state ignores the host values of solid cells and writes w_k there.  A fresh context has the all-fluid mask.
+ * lbm_get_solid: mask_out[B][X][Y] receives 0 / 1.
+ * lbm_solid_force: the momentum-exchange force of the fluid on all solid cells of each lattice, out[batch], all doubles:
+ *   step    the step count
+ *   links   the (fluid cell, slot k) pairs whose source is a solid cell inside the lattice
+ *   fx, fy  sum over the links of 2 c_opp(k) f, f = the fluid cell's post-collision population of direction opp(k) as the lattice holds it
+ *           after the last step, converted to double first.  Components as u: fy > 0 points to the lid.  f equals what lbm_get_fields
+ *           returns as fin_k of that cell, so the host restatement is F = sum_links 2 c_opp(k) fin_k(x, y).
+ *   Reduced by the tree described with the samplers: a lane folds its cells in grid-stride order (slots k = 1 .. 8 in order), no
+ *   atomics, the same bits from run to run.  Synchronises.  LBM_ERR_STATE before the first step.  The partial results are allocated
+ *   at the first call (never inside lbm_step) and freed by lbm_destroy. */
+typedef struct lbm_solid_force_record {
+    double step;
+    double links;
+    double fx;
+    double fy;
+} lbm_solid_force_record;
+int lbm_set_solid(lbm_ctx* c, const uint8_t* mask);
+int lbm_get_solid(lbm_ctx* c, uint8_t* mask_out);
+int lbm_solid_force(lbm_ctx* c, lbm_solid_force_record* out);
 
 /* --- slab decomposition, externally driven exchange ---------------------------------- */
 /* No reference counterpart (the reference is single-GPU, MRT_GPU.py:29).  A step of a slab

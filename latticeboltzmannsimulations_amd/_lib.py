@@ -18,7 +18,7 @@ LINK_FLAGS = ["-ldl"]   # RCCL is bound lazily with dlopen inside the library
 
 LBM_F32, LBM_F64 = 0, 1
 LBM_SRT, LBM_TRT, LBM_MRT = 0, 1, 2
-LBM_SEM_MRT_PY, LBM_SEM_MRT_GPU, LBM_SEM_BOUNCE_BACK = 0, 1, 2
+LBM_SEM_MRT_PY, LBM_SEM_MRT_GPU, LBM_SEM_BOUNCE_BACK, LBM_SEM_BOUNCE_BACK_SOLID = 0, 1, 2, 3
 LBM_KERNEL_AUTO, LBM_KERNEL_GENERIC, LBM_KERNEL_VEC, LBM_KERNEL_TB, LBM_KERNEL_PUSH, LBM_KERNEL_STREAM = 0, 1, 2, 3, 4, 5
 LBM_LAYOUT_AUTO, LBM_LAYOUT_PLANES, LBM_LAYOUT_ROWS = 0, 1, 2
 LBM_SIDE_LOW, LBM_SIDE_HIGH = 0, 1
@@ -82,14 +82,18 @@ class lbm_topology_record(ctypes.Structure):
     _fields_ = [("step", ctypes.c_double), ("closure", ctypes.c_double), ("window", _lbm_topology_window * LBM_TOPOLOGY_MAX_WINDOWS)]
 
 
+class lbm_solid_force_record(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_double) for n in ("step", "links", "fx", "fy")]
+
+
 def sources():
     return [os.path.join(_CSRC, f) for f in sorted(os.listdir(_CSRC)) if f.endswith((".hip", ".hpp"))] + [HEADER]
 
 
 def build(force=False, verbose=False):
     """Compile csrc/*.hip for gfx950 into liblbm_hip.so next to this file (in-tree).  The translation units (eight of host code +
-    C ABI: lbm_hip / lbm_plan / lbm_launch / lbm_comm / lbm_sampling / lbm_monitor / lbm_residual / lbm_topology; the explicit instantiations of the tile and streaming kernels for float and
-    for double) are compiled in parallel into csrc/_obj/ and linked."""
+    C ABI: lbm_hip / lbm_plan / lbm_launch / lbm_comm / lbm_sampling / lbm_monitor / lbm_residual / lbm_topology / lbm_solid; the explicit instantiations of the tile, streaming and
+    solid-mask kernels for float and for double) are compiled in parallel into csrc/_obj/ and linked."""
     srcs = sources()
     if not force and os.path.exists(LIB_PATH) and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(s) for s in srcs):
         return LIB_PATH
@@ -155,6 +159,9 @@ SIGNATURES = {
     "lbm_residual_end": (_i, [_vp]),
     "lbm_topology": (_i, [_vp, ctypes.POINTER(lbm_topology_spec), ctypes.POINTER(lbm_topology_record)]),
     "lbm_get_stream_function": (_i, [_vp, _vp, _vp, _i]),
+    "lbm_set_solid": (_i, [_vp, _vp]),
+    "lbm_get_solid": (_i, [_vp, _vp]),
+    "lbm_solid_force": (_i, [_vp, ctypes.POINTER(lbm_solid_force_record)]),
     "lbm_halo_elems": (_i, [_vp]),
     "lbm_halo_export": (_i, [_vp, _i, _vp]),
     "lbm_halo_import": (_i, [_vp, _i, _vp]),

@@ -19,7 +19,9 @@ constexpr int GHY = 10; // ghost rows above and below a lattice: row -1 / ny is 
 __host__ __device__ constexpr int cxk(int k) { return k == 1 || k == 5 || k == 8 ? 1 : (k == 3 || k == 6 || k == 7 ? -1 : 0); }
 __host__ __device__ constexpr int cyk(int k) { return k == 2 || k == 5 || k == 6 ? 1 : (k == 4 || k == 7 || k == 8 ? -1 : 0); }
 
-enum { SEM_PY = 0, SEM_GPU = 1, SEM_BB = 2 };   // = lbm_params.semantics (LBM_SEM_MRT_PY, LBM_SEM_MRT_GPU, LBM_SEM_BOUNCE_BACK)
+enum { SEM_PY = 0, SEM_GPU = 1, SEM_BB = 2, SEM_SOLID = 3 };   // = lbm_params.semantics (LBM_SEM_MRT_PY, LBM_SEM_MRT_GPU, LBM_SEM_BOUNCE_BACK, LBM_SEM_BOUNCE_BACK_SOLID)
+// SEM_SOLID is SEM_BB plus solid cells: everything that asks "bounce-back walls?" asks sem_is_bb
+constexpr bool sem_is_bb(int sem) { return sem == SEM_BB || sem == SEM_SOLID; }
 enum { C_SRT = 0, C_TRT = 1, C_MRT = 2,
        // lbm_params.arith = LBM_ARITH_FAST: not the reference's operation order / rounding --
        C_MRT_FAST = 3,     // the MRT operator in factored form with fused multiply-adds
@@ -52,7 +54,7 @@ template <int SEM>
 __device__ __forceinline__ bool in_window(int k, int x, int gy, int X, int Y) {
     const int cx = cxk(k), cy = cyk(k);
     bool ok = true;
-    if (SEM == SEM_BB) {
+    if (sem_is_bb(SEM)) {
         return true;
     } else if (SEM == SEM_PY) {
         if (cx > 0) ok = ok && (x >= 1) && (x <= X - 2);
@@ -158,7 +160,7 @@ __device__ __forceinline__ void macros(const R (&f)[Q], int x, int gy, int X, in
     rho = ((((((((f[0] + f[1]) + f[2]) + f[3]) + f[4]) + f[5]) + f[6]) + f[7]) + f[8]);
     ux = div_<FAST>((((((f[1] - f[3]) + f[5]) - f[6]) - f[7]) + f[8]), rho);
     uy = div_<FAST>((((((f[2] - f[4]) + f[5]) + f[6]) - f[7]) - f[8]), rho);
-    if (SEM == SEM_BB) return;
+    if (sem_is_bb(SEM)) return;   // (a solid cell of SEM_SOLID holds w_k: the sums give rho = sum w_k and u = exactly 0)
     if (x == 0 || x == X - 1 || gy == Y - 1) { ux = (R)0; uy = (R)0; }
     if (gy == 0) {
         rho = ((f[0] + f[1]) + f[3]) + (R)2. * ((f[2] + f[5]) + f[6]);
@@ -482,12 +484,27 @@ __host__ __device__ constexpr int opp(int k) { return k == 0 ? 0 : (k < 5 ? (k +
 template <typename R>
 __device__ __forceinline__ R lid_term(R rho_w, R uLB) { return (rho_w * uLB) * (R)(1.0 / 6.0); }
 
+// Solid obstacles (SEM_SOLID): plane K_LINK of the lattice holds one small integer per cell, exact in fp32 and fp64 -- bit k - 1: the
+// source (x - cx_k, y + cy_k) of slot k is a solid cell inside the lattice; bit 8: the cell itself is solid.  Written by lbm_set_solid
+// into both lattices, never by a step.  A solid cell is never updated and holds the rest equilibrium w_k in both lattices.
+constexpr int K_LINK = Q;
+constexpr int LINK_SOLID = 256;
+
 // Gather the post-stream, post-wall-rule populations of cell (x, y) from a lattice that
 // holds post-collision values (+ kept slots + parked wall densities); raw != 0: the lattice
 // holds plain populations (state just set by the host), nothing to stream.  PROM: the wall rules' equilibrium in the promoted form.
 template <typename R, int SEM, typename AS, bool PROM = false>
 __device__ __forceinline__ void gather_a(const R* __restrict__ src, const AS& as, const Geo& geo, int raw, R uLB, int x, int y, R (&g)[Q]) {
     const int gy = geo.y0 + y;
+    int lw = 0;
+    if (SEM == SEM_SOLID) {
+        lw = (int)src[K_LINK * as.plane + as.at(x, y)];
+        if (lw & LINK_SOLID) {   // a solid cell: the constants it holds, whatever its neighbours stream
+#pragma unroll
+            for (int k = 0; k < Q; ++k) g[k] = weight<R>(k);
+            return;
+        }
+    }
     if (raw) {
 #pragma unroll
         for (int k = 0; k < Q; ++k) g[k] = src[k * as.plane + as.at(x, y)];
@@ -495,7 +512,14 @@ __device__ __forceinline__ void gather_a(const R* __restrict__ src, const AS& as
     }
 #pragma unroll
     for (int k = 0; k < Q; ++k) g[k] = src[k * as.plane + as.at(x - cxk(k), y + cyk(k))];
-    if (SEM == SEM_BB) {
+    if (SEM == SEM_SOLID && (lw & 255)) {
+        // a source inside the lattice that is a solid cell: the cell's own post-collision population of the opposite direction, nothing
+        // added (obstacles are at rest).  Disjoint from the sources outside the lattice below.
+#pragma unroll
+        for (int k = 1; k < Q; ++k)
+            if ((lw >> (k - 1)) & 1) g[k] = src[opp(k) * as.plane + as.at(x, y)];
+    }
+    if (sem_is_bb(SEM)) {
         // a source outside [0, nx) x [0, NY): the cell's own post-collision population of the opposite direction; beyond the lid
         // (corner ghosts included) plus the lid term.  The cell's own slots were stored at its own position by update_cell_a (every
         // slot streams); the ghost positions of the pulls above are read but not used here.
@@ -531,6 +555,7 @@ template <typename R, int COLL, int SEM, bool TURB, typename AS, typename AD>
 __device__ __forceinline__ void update_cell_a(const R* __restrict__ src, const AS& as, R* __restrict__ dst, const AD& ad, const Geo& geo,
                                               const Relax<R>& w0, int raw, int x, int y) {
     const int X = geo.nx, Y = geo.NY, gy = geo.y0 + y;
+    if (SEM == SEM_SOLID && ((int)src[K_LINK * as.plane + as.at(x, y)] & LINK_SOLID)) return;   // a solid cell is never updated
     R g[Q];
     gather_a<R, SEM, AS, coll_is_prom(COLL)>(src, as, geo, raw, w0.uLB, x, y, g);
     // kept slots: a slot outside its streaming window keeps its value; park it where the
@@ -548,7 +573,7 @@ __device__ __forceinline__ void update_cell_a(const R* __restrict__ src, const A
     R w_nu = w0.w_nu;
     if (TURB) w_nu = smagorinsky_omega<R, coll_is_fast(COLL), coll_is_prom(COLL)>(g, src[K_QEQ * as.plane + me_s], src[K_RHO * as.plane + me_s], w0.w_nu);
     macros<R, coll_is_fast(COLL), SEM>(g, x, gy, X, Y, w.uLB, rho, ux, uy);
-    equ_collide<R, COLL, TURB>(g, rho, ux, uy, w, w_nu, out, q2, COLL == C_MRT_FAST && gy == 0 && SEM != SEM_BB);
+    equ_collide<R, COLL, TURB>(g, rho, ux, uy, w, w_nu, out, q2, COLL == C_MRT_FAST && gy == 0 && !sem_is_bb(SEM));
     if (TURB) {
         dst[K_QEQ * ad.plane + me] = q2;
         dst[K_RHO * ad.plane + me] = rho;

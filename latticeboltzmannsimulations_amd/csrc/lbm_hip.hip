@@ -222,6 +222,7 @@ lbm_ctx* lbm_create(const lbm_params* p, char* err, size_t errlen) {
         // on the compute stream: the streams are non-blocking, a null-stream memset would race with the kernels
         if ((e = hipMemsetAsync(c->lat[i], 0, bytes, c->s_compute)) != hipSuccess) return cleanup(std::string("hipMemset: ") + hipGetErrorString(e));
     }
+    if (p->semantics == LBM_SEM_BOUNCE_BACK_SOLID) c->solid_mask.assign((size_t)c->plan.batch * p->nx * p->ny, 0);   // all fluid
     if (c->plan.batch > 1) {   // every lattice starts with the rates of lbm_params; lbm_set_relaxation() changes them one by one
         const size_t rb = c->plan.es == 4 ? sizeof(Relax<float>) : sizeof(Relax<double>);
         if ((e = hipMalloc(&c->relax_dev, rb * c->plan.batch)) != hipSuccess) return cleanup(std::string("hipMalloc(relaxation): ") + hipGetErrorString(e));
@@ -245,6 +246,7 @@ void lbm_destroy(lbm_ctx* c) {
     for (int i = 0; i < NSAMPLERS; ++i) sampler_free(c, i);
     monitor_free(c);
     topology_free(c);
+    solid_free(c);
     if (c->stage) (void)hipFree(c->stage);
     if (c->relax_dev) (void)hipFree(c->relax_dev);
     if (c->ev_edges) (void)hipEventDestroy(c->ev_edges);
@@ -272,6 +274,7 @@ int lbm_init_equilibrium(lbm_ctx* c) {
         using R = typename VT::R;
         hipLaunchKernelGGL((k_init<R, coll_is_prom(VT::COLL)>), g, dim3(BLK), 0, c->s_compute, (R*)c->lat[0], c->plan.geo, (R)c->p.uLB, c->p.turb, c->plan.bstride);
     });
+    if (rc == LBM_OK) rc = solid_fix(c);
     if (rc) return rc;
     return push_reset(c);
 }
@@ -292,6 +295,7 @@ int lbm_set_state(lbm_ctx* c, const void* fin_host, int host_dtype) {
         hipLaunchKernelGGL((k_import<R, coll_is_prom(VT::COLL)>), grid_tiles<R>(c), dim3(BLK), 0, c->s_compute, (const R*)c->stage, (R*)c->lat[0], c->plan.geo,
                            (R)c->p.uLB, c->p.turb, c->plan.bstride);
     });
+    if (rc == LBM_OK) rc = solid_fix(c);   // (solid cells: w_k, whatever the host array holds there)
     if (rc) return rc;
     rc = push_reset(c);
     if (rc) return rc;

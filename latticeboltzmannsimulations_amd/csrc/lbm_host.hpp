@@ -10,6 +10,7 @@
 //   lbm_monitor.hip the run monitor and the line export (kernels: lbm_monitor.hpp)        (C ABI: monitor*, get_lines)
 //   lbm_residual.hip the field residual (kernels: lbm_residual.hpp)                        (C ABI: residual_*)
 //   lbm_topology.hip stream function, vorticity, extrema of psi (kernels: lbm_topology.hpp) (C ABI: topology, get_stream_function)
+//   lbm_solid.hip   solid obstacles: the mask and its link plane, the force on the obstacles (step kernel: lbm_solid.hpp) (C ABI: set_solid, get_solid, solid_force)
 // and two headers free of HIP, each driven by a CPU test through a program of its own:
 //   lbm_schedule.hpp the schedule of automatic sampling
 //   lbm_order.hpp    the ordering of the two streams: the state carried between units, the skeletons of a unit, the argument
@@ -31,6 +32,7 @@
 #include "../../include/lbm.h"
 #include "lbm_schedule.hpp"
 #include "lbm_order.hpp"
+#include "lbm_solid.hpp"  // k_step_solid, extern (compiled in lbm_solid_f32/f64.hip)
 #include "lbm_inst.hpp"   // the kernels, and extern template declarations of the multi-step ones (compiled in lbm_{tiles,stream*}_f32/f64.hip)
 
 // ------------------------------------------------------------------------------------
@@ -137,6 +139,11 @@ struct lbm_ctx {
     // the records of the record path, topo_fields the staged psi and omega of the field path; each allocated on first use, kept.
     double* topo_part = nullptr;
     double* topo_fields = nullptr;
+    // Solid obstacles (LBM_SEM_BOUNCE_BACK_SOLID, lbm_solid.hip): the mask as lbm_set_solid stored it, 0 / 1, [batch][nx][ny] (all fluid
+    // in a fresh context; empty in the other semantics); force_dev: the workgroups' partial results of lbm_solid_force and, behind
+    // them, its records (allocated on first use, kept).
+    std::vector<uint8_t> solid_mask;
+    double* force_dev = nullptr;
     ncclComm_t comm = nullptr;
     int nranks = 1, rank = 0;
     bool loopback = false;      // diagnostic: 1-rank communicator, the slab exchanges halos with itself
@@ -242,6 +249,7 @@ void dispatch(const lbm_params& p, F&& f) {
         } else {
             if (p.semantics == LBM_SEM_MRT_PY) f(Variant<R, CS, SEM_PY, false>{});   // (arith = fast: MRT_GPU semantics only)
             else if (p.semantics == LBM_SEM_BOUNCE_BACK) f(Variant<R, C, SEM_BB, false>{});   // (strict and fast; no closure: validate_params)
+            else if (p.semantics == LBM_SEM_BOUNCE_BACK_SOLID) f(Variant<R, C, SEM_SOLID, false>{});   // (the same, one step per launch)
             else if (p.turb) f(Variant<R, C, SEM_GPU, true>{});
             else f(Variant<R, C, SEM_GPU, false>{});
         }
@@ -281,6 +289,8 @@ int launch_variant(lbm_ctx* c, F&& f) {
 // segments of L cells that cover n cells of a frame strip (the fused frame passes run one workgroup per segment, frame_passes)
 inline int frame_segs(int n, int L) { return (n + L - 1) / L; }
 struct StreamPlan { int nstrips, nsegy, H; };
+// the semantics the multi-step kernels, the frame passes and the push scheme are compiled for (solid obstacles step one step per launch)
+constexpr bool sem_multi_step(int sem) { return sem != SEM_SOLID; }
 
 // Waiting for the device: poll for a short while, then block.  A blocking hipStreamSynchronize / hipEventSynchronize wakes the host
 // tens of microseconds after the work is done -- 5 % of the driver's 20-step window of 1.1 ms (profiles/r02_logs/unit_times.log);
@@ -379,6 +389,9 @@ int monitor_series_sample(lbm_ctx* c, int which, long long step);
 void monitor_free(lbm_ctx* c);
 // lbm_topology.hip
 void topology_free(lbm_ctx* c);
+// lbm_solid.hip
+int solid_fix(lbm_ctx* c);
+void solid_free(lbm_ctx* c);
 // lbm_residual.hip
 int residual_series_sample(lbm_ctx* c, int which, long long step);
 void residual_free(lbm_ctx* c);

@@ -35,6 +35,19 @@ int launch_rows(lbm_ctx* c, int from, int to, int row0, int stride, int nrows, h
         const R* src = (const R*)c->lat[from];
         R* dst = (R*)c->lat[to];
         const int raw = c->raw[from];
+        if constexpr (VT::SEM == SEM_SOLID) {
+            if (c->plan.use_vec) {   // (nx a multiple of the vector width, kernel = AUTO: plan_kernel)
+                constexpr int V = 16 / (int)sizeof(R);
+                const int nxb = (c->plan.geo.nx / V + BLK - 1) / BLK, nblocks = nxb * nrows;
+                if (c->plan.use_nt)
+                    hipLaunchKernelGGL((k_step_solid<R, VT::COLL, true>), dim3(nblocks, c->plan.batch), dim3(BLK), 0, s, src, dst, c->plan.geo,
+                                       relax_of<R>(c->p), batch_of<R>(c), raw, row0, stride, nxb, nblocks);
+                else
+                    hipLaunchKernelGGL((k_step_solid<R, VT::COLL, false>), dim3(nblocks, c->plan.batch), dim3(BLK), 0, s, src, dst, c->plan.geo,
+                                       relax_of<R>(c->p), batch_of<R>(c), raw, row0, stride, nxb, nblocks);
+                return;
+            }
+        }
         if (VT::SEM == SEM_GPU && c->plan.use_vec) {
             constexpr int V = 16 / (int)sizeof(R);
             const int nxb = (c->plan.geo.nx / V + BLK - 1) / BLK, nblocks = nxb * nrows;
@@ -59,8 +72,9 @@ int launch_frame(lbm_ctx* c, int from, int to, int W, hipStream_t s, int elo, in
         constexpr int V = 16 / (int)sizeof(R);
         const int vec_rows = VT::SEM == SEM_GPU && c->plan.use_vec && c->plan.geo.nx % V == 0 ? 1 : 0;   // row strips by vector cells
         const long long cells = (2LL * W + elo + ehi) * (vec_rows ? c->plan.geo.nx / V : c->plan.geo.nx) + 2LL * W * (c->plan.geo.ny - 2 * W);
-        hipLaunchKernelGGL((k_step_frame<R, VT::COLL, VT::SEM, VT::TURB>), dim3((unsigned)((cells + BLK - 1) / BLK), c->plan.batch), dim3(BLK), 0, s,
-                           (const R*)c->lat[from], (R*)c->lat[to], c->plan.geo, relax_of<R>(c->p), batch_of<R>(c), W, elo, ehi, vec_rows);
+        if constexpr (sem_multi_step(VT::SEM))
+            hipLaunchKernelGGL((k_step_frame<R, VT::COLL, VT::SEM, VT::TURB>), dim3((unsigned)((cells + BLK - 1) / BLK), c->plan.batch), dim3(BLK), 0, s,
+                               (const R*)c->lat[from], (R*)c->lat[to], c->plan.geo, relax_of<R>(c->p), batch_of<R>(c), W, elo, ehi, vec_rows);
     });
 }
 
@@ -93,7 +107,8 @@ int launch_frame_multi(lbm_ctx* c, int from, int to, int S, hipStream_t s, bool 
         using VT = decltype(v);
         using R = typename VT::R;
         const FramePtrs<R> fp = frame_ptrs<R>(c, from, to, S);
-        if (beside)
+        if constexpr (!sem_multi_step(VT::SEM)) return;
+        else if (beside)
             hipLaunchKernelGGL((k_frame_beside<R, VT::COLL, VT::SEM, VT::TURB>), dim3(fl.nframe), dim3(BLK), 0, s, fp, c->plan.geo, relax_of<R>(c->p), fl.F, S,
                                fl.nsegx, fl.nsegy, fl.L);
         else if (!fl.in_lds && c->plan.frame_wide)
@@ -113,6 +128,7 @@ static int launch_k_stream(lbm_ctx* c, int from, int to, hipStream_t s, int S, c
     return launch_variant(c, [&](auto v) {
         using VT = decltype(v);
         using R = typename VT::R;
+        if constexpr (sem_multi_step(VT::SEM))
         hipLaunchKernelGGL((k_stream<R, VT::COLL, VT::SEM, VT::TURB>), dim3(fl.nframe + pl.nstrips * nseg), dim3(ST_NT), 0, s, (const R*)c->lat[from],
                            (R*)c->lat[to], c->plan.geo, relax_of<R>(c->p), S, fl.F, c->plan.geo.nx - fl.F, ye, pl.nstrips, pl.H, frame_ptrs<R>(c, from, to, S),
                            fl.nframe, fl.nsegx, fl.nsegy, fl.L, fl.in_lds ? 1 : 0, lo, hi, bands, xcd_bands ? 1 : 0);
@@ -223,6 +239,7 @@ int launch_deep(lbm_ctx* c, int from, int to, hipStream_t s, int steps, bool wit
         auto go = [&](auto steps) {   // (fp64: the x rim of S >= 4 is two vectors wide)
             constexpr int S = decltype(steps)::value, PVC = 16, RV = (S - 1 + V - 1) / V, TX = (PVC - 2 * RV) * V, TY = 512 / PVC - 2 * (S - 1);
             const int ntx = (xe - F + TX - 1) / TX, nty = (ye - F + TY - 1) / TY;
+            if constexpr (sem_multi_step(VT::SEM))
             hipLaunchKernelGGL((k_stepS_deep<R, VT::COLL, VT::SEM, S, false, VT::TURB>), dim3(fl.nframe + ntx * nty, c->plan.batch), dim3(512), 0, s,
                                (const R*)c->lat[from], (R*)c->lat[to], c->plan.geo, relax_of<R>(c->p), batch_of<R>(c), F, xe, ye, ntx, ntx * nty,
                                frame_ptrs<R>(c, from, to, S), fl.nframe, fl.nsegx, fl.nsegy, fl.L, fl.in_lds ? 1 : 0);
@@ -358,7 +375,7 @@ int push_step(lbm_ctx* c) {
         using VT = decltype(v);
         using R = typename VT::R;
         const dim3 g = grid_rows(c, c->plan.geo.ny);
-        if constexpr (VT::SEM != SEM_BB) {   // (validate_params refuses the push scheme with bounce-back walls)
+        if constexpr (!sem_is_bb(VT::SEM)) {   // (validate_params refuses the push scheme with bounce-back walls)
             hipLaunchKernelGGL((k_push_collide<R, VT::COLL, VT::SEM>), g, dim3(BLK), 0, c->s_compute, (const R*)c->lat[c->cur], (R*)c->lat[2], c->plan.geo,
                                relax_of<R>(c->p));
             hipLaunchKernelGGL((k_push_bc<R, VT::COLL, VT::SEM>), g, dim3(BLK), 0, c->s_compute, (const R*)c->lat[c->cur], (R*)c->lat[2],

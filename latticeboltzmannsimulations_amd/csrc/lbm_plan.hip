@@ -143,7 +143,7 @@ std::string validate_params(const lbm_params* p) {
     if (p->ny_local > 65535) return std::string("ny_local > 65535 not supported");
     if (p->dtype != LBM_F32 && p->dtype != LBM_F64) return std::string("dtype must be LBM_F32 or LBM_F64");
     if (p->collision < LBM_SRT || p->collision > LBM_MRT) return std::string("collision must be SRT, TRT or MRT");
-    if (p->semantics != LBM_SEM_MRT_PY && p->semantics != LBM_SEM_MRT_GPU && p->semantics != LBM_SEM_BOUNCE_BACK) return std::string("bad semantics");
+    if (p->semantics < LBM_SEM_MRT_PY || p->semantics > LBM_SEM_BOUNCE_BACK_SOLID) return std::string("bad semantics");
     if (p->turb != 0 && p->turb != 1) return std::string("turb must be 0 or 1");
     if (p->turb == 1 && p->semantics != LBM_SEM_MRT_GPU) return std::string("turb = 1 (Smagorinsky, MRT_GPU.py:368-387) exists only with MRT_GPU semantics");
     if (p->kernel < LBM_KERNEL_AUTO || p->kernel > LBM_KERNEL_STREAM) return std::string("bad kernel variant");
@@ -158,7 +158,16 @@ std::string validate_params(const lbm_params* p) {
                            "MRT.py semantics is NumPy fp64)");
     if (p->arith == LBM_ARITH_PROMOTED && (p->flags & LBM_FLAG_STREAM_PAIRS))
         return std::string("arith = promoted does not run on the streaming kernel with two rows per wave (LBM_FLAG_STREAM_PAIRS)");
-    if (p->semantics == LBM_SEM_BOUNCE_BACK) {
+    if (p->semantics == LBM_SEM_BOUNCE_BACK_SOLID) {
+        // solid obstacles: the tile and streaming kernels never compute a cell whose neighbours are not plain fluid, the vector and push
+        // kernels have the wet-node walls built in; the mask is one whole lattice's (of each lattice of a batch)
+        if (p->y0 != 0 || p->ny_local != p->ny)
+            return std::string("solid obstacles (LBM_SEM_BOUNCE_BACK_SOLID) take whole lattices: no slabs (y0 = 0, ny_local = ny)");
+        if (p->kernel != LBM_KERNEL_AUTO && p->kernel != LBM_KERNEL_GENERIC)
+            return std::string("solid obstacles (LBM_SEM_BOUNCE_BACK_SOLID) step one step per launch, kernel = AUTO or GENERIC: TB / STREAM / VEC / PUSH "
+                               "never compute a cell next to a solid one");
+    }
+    if (p->semantics == LBM_SEM_BOUNCE_BACK || p->semantics == LBM_SEM_BOUNCE_BACK_SOLID) {
         // half-way bounce-back lives in the gather of the single-step operators and of the frame passes (lbm_device.hpp); the kernels
         // with walls of their own (push scheme, vector rows, the streaming kernels with the walls inside) know only the wet-node rules
         if (p->arith == LBM_ARITH_PROMOTED)
@@ -222,6 +231,7 @@ static void plan_geometry(Plan& pl, const lbm_params& p, const Forced& f) {
     pl.geo.NY = p.ny;
     pl.geo.pitch = ((p.nx + 2 * GH) + 3) / 4 * 4;
     pl.nplanes = p.turb ? Q + 2 : Q;   // + the two Smagorinsky history planes
+    if (p.semantics == LBM_SEM_BOUNCE_BACK_SOLID) pl.nplanes = Q + 1;   // + the link plane of the solid mask (K_LINK; no closure there)
     pl.semantics = p.semantics;
     if (p.layout == LBM_LAYOUT_PLANES) {
         pl.geo.plane = (long long)pl.geo.pitch * (p.ny_local + 2 * GHY);
@@ -242,6 +252,11 @@ static void plan_geometry(Plan& pl, const lbm_params& p, const Forced& f) {
 static std::string plan_kernel(Plan& pl, const lbm_params& p, const Forced& f, bool device) {
     const int nyp = ny_plan(p), V = 16 / pl.es;
     const bool slab = is_slab(pl);
+    if (p.semantics == LBM_SEM_BOUNCE_BACK_SOLID) {   // one step per launch: k_step_solid (use_vec), or k_step_generic
+        pl.use_vec = p.nx % V == 0 && p.kernel != LBM_KERNEL_GENERIC;
+        pl.kern = Kern::none;
+        return std::string();
+    }
     const bool can_vec = p.semantics == LBM_SEM_MRT_GPU && p.nx % V == 0;
     if (p.kernel == LBM_KERNEL_VEC && !can_vec) return "kernel = VEC needs MRT_GPU semantics and nx % (16 / sizeof(real)) == 0";
     pl.push = p.kernel == LBM_KERNEL_PUSH;
@@ -397,8 +412,10 @@ static void plan_frame(Plan& pl, const lbm_params& p, const Forced& f, bool devi
             using VT = decltype(v);
             using R = typename VT::R;
             hipFuncAttributes at;
-            if (hipFuncGetAttributes(&at, reinterpret_cast<const void*>(&k_stream<R, VT::COLL, VT::SEM, VT::TURB>)) == hipSuccess) rs = at.numRegs;
-            if (hipFuncGetAttributes(&at, reinterpret_cast<const void*>(&k_frame_beside<R, VT::COLL, VT::SEM, VT::TURB>)) == hipSuccess) rf = at.numRegs;
+            if constexpr (sem_multi_step(VT::SEM)) {
+                if (hipFuncGetAttributes(&at, reinterpret_cast<const void*>(&k_stream<R, VT::COLL, VT::SEM, VT::TURB>)) == hipSuccess) rs = at.numRegs;
+                if (hipFuncGetAttributes(&at, reinterpret_cast<const void*>(&k_frame_beside<R, VT::COLL, VT::SEM, VT::TURB>)) == hipSuccess) rf = at.numRegs;
+            }
         });
         pl.frame_beside = (rs + 7) / 8 * 8 * 4 + (rf + 7) / 8 * 8 <= 512;
     }
@@ -468,15 +485,16 @@ static int describe_plan(const Plan& pl, int lattices_held, char* buf, size_t le
         for (int s = 1; s <= S; ++s) per += (32 - 2 * (s - 1)) / 4 + ((32 - 2 * (s - 1)) % 4 ? 1 : 0);
         wave_updates = wgs * per;
     }
+    const bool solid = pl.semantics == LBM_SEM_BOUNCE_BACK_SOLID;   // (names its one-step kernel: it has no multi-step units)
     const int n = std::snprintf(buf, len, "kernel=%s steps_per_launch=%d frame=%d stream=%d vec=%d nt=%d deep_halo=%d frame_fused=%d lazy_lag=%d "
                                 "layout=%s workgroups=%lld wave_updates=%lld cells_per_lane=%d slab=%d frame_beside=%d frame_seg=%d "
                                 "lattices=%d lattice_bytes=%lld%s",
-                                names[(int)pl.kern], S, pl.kern != Kern::none ? (walls_inside(pl) && !is_slab(pl) ? 0 : pl.tb_f) : 0, streaming(pl) ? 1 : 0,
+                                solid ? (pl.use_vec ? "k_step_solid" : "k_step_generic") : names[(int)pl.kern], S, pl.kern != Kern::none ? (walls_inside(pl) && !is_slab(pl) ? 0 : pl.tb_f) : 0, streaming(pl) ? 1 : 0,
                                 pl.use_vec ? 1 : 0, pl.use_nt ? 1 : 0, pl.deep_halo ? 1 : 0, pl.frame_fused ? 1 : 0, pl.lazy_lag ? 1 : 0,
                                 pl.geo.row != pl.geo.pitch ? "rows" : "planes", wgs, wave_updates, V, is_slab(pl) ? 1 : 0, pl.frame_beside ? 1 : 0,
                                 pl.frame_seg, lattices_held, (long long)pl.lat_bytes,
                                 // (the wall model, where it is not one of the two wet-node semantics whose plans predate the field)
-                                pl.semantics == LBM_SEM_BOUNCE_BACK ? " semantics=bounce_back" : "");
+                                pl.semantics == LBM_SEM_BOUNCE_BACK ? " semantics=bounce_back" : solid ? " semantics=bounce_back_solid" : "");
     return n < 0 ? LBM_ERR_INVALID : (n >= (int)len ? (int)len - 1 : n);
 }
 }  // namespace lbmhost

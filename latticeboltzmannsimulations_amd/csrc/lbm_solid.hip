@@ -1,0 +1,194 @@
+// lbm_solid.hip -- liblbm_hip.so: solid obstacles in the bounce-back cavity (lbm_set_solid, lbm_get_solid, lbm_solid_force of the C ABI
+// declared in include/lbm.h; LBM_SEM_BOUNCE_BACK_SOLID).  The rule is gather_a<.., SEM_SOLID> (lbm_device.hpp), the step kernel
+// k_step_solid (lbm_solid.hpp); here: the mask and the link plane derived from it, the constants of solid cells, and the momentum-
+// exchange force reduced by the tree of lbm_reduce.hpp.  gfx950 only.  DESIGN.md 2.10.
+#include "lbm_host.hpp"
+#include "lbm_reduce.hpp"
+
+namespace lbmhost {
+
+static_assert(sizeof(lbm_solid_force_record) == 4 * sizeof(double), "record layout");
+
+// Solid cells hold the rest equilibrium at rho = 1, w_k rounded to the lattice type, in both lattices: written after every
+// initialisation and upload, from the link plane of `a`.
+template <typename R>
+__global__ __launch_bounds__(BLK) void k_solid_fix(R* __restrict__ a, R* __restrict__ b, Geo geo, long long bstride) {
+    const int x = blockIdx.x * BLK + threadIdx.x, y = blockIdx.y;
+    if (x >= geo.nx) return;
+    a += blockIdx.z * bstride;
+    b += blockIdx.z * bstride;
+    const long long me = geo.at(x, y);
+    if (!((int)a[K_LINK * geo.plane + me] & LINK_SOLID)) return;
+#pragma unroll
+    for (int k = 0; k < Q; ++k) {
+        a[k * geo.plane + me] = weight<R>(k);
+        b[k * geo.plane + me] = weight<R>(k);
+    }
+}
+
+// Momentum exchange: over the (fluid cell, slot k) pairs whose source is a solid cell, links += 1, fx += 2 cx_opp(k) f,
+// fy += 2 cy_opp(k) f with f = the cell's post-collision population of direction opp(k) as the lattice holds it, each term converted
+// to double.  A lane folds its cells in grid-stride order, slots k = 1 .. 8 in order; then the tree.
+struct ForceAcc {
+    double links, fx, fy;
+    static constexpr int VALS = 3;
+    static __device__ __forceinline__ ForceAcc identity() { return ForceAcc{0.0, 0.0, 0.0}; }
+    static __device__ __forceinline__ void fold(ForceAcc& a, const ForceAcc& b) {
+#pragma clang fp contract(off)
+        a.links = a.links + b.links;
+        a.fx = a.fx + b.fx;
+        a.fy = a.fy + b.fy;
+    }
+    template <typename F>
+    __device__ __forceinline__ void each(F&& f) { f(links); f(fx); f(fy); }
+};
+constexpr int FORCE_BLOCKS = 256;   // partial results per lattice
+
+template <typename R>
+__global__ __launch_bounds__(BLK) void k_solid_force(const R* __restrict__ src, Geo geo, long long bstride, double* __restrict__ partial) {
+#pragma clang fp contract(off)
+    __shared__ double sh[BLK / RED_WAVE][ForceAcc::VALS];
+    src += blockIdx.z * bstride;
+    const long long n = (long long)geo.nx * geo.ny;
+    ForceAcc a = ForceAcc::identity();
+    for (long long i = (long long)blockIdx.x * BLK + threadIdx.x; i < n; i += (long long)gridDim.x * BLK) {
+        const int y = (int)(i / geo.nx), x = (int)(i - (long long)y * geo.nx);
+        const long long me = geo.at(x, y);
+        const int lw = (int)src[K_LINK * geo.plane + me];
+        if ((lw & LINK_SOLID) || !(lw & 255)) continue;
+#pragma unroll
+        for (int k = 1; k < Q; ++k)
+            if ((lw >> (k - 1)) & 1) {
+                const double f = (double)src[opp(k) * geo.plane + me];
+                a.links = a.links + 1.0;
+                a.fx = a.fx + (double)(2 * cxk(opp(k))) * f;
+                a.fy = a.fy + (double)(2 * cyk(opp(k))) * f;
+            }
+    }
+    red_wave(a);
+    if (red_workgroup<ForceAcc, BLK / RED_WAVE>(a, sh)) red_store(partial + ((size_t)blockIdx.z * gridDim.x + blockIdx.x) * ForceAcc::VALS, a);
+}
+
+// The final pass, one wave per lattice: rec[z] = {step, links, fx, fy}
+__global__ __launch_bounds__(RED_WAVE) void k_solid_force_final(const double* __restrict__ partial, int nper, double step, double* __restrict__ rec) {
+    const int z = blockIdx.x;
+    const ForceAcc a = red_final<ForceAcc>(partial + (size_t)z * nper * ForceAcc::VALS, nper);
+    if (threadIdx.x == 0) {
+        rec[4 * z] = step;
+        red_store(rec + 4 * z + 1, a);
+    }
+}
+
+int solid_fix(lbm_ctx* c) {
+    if (c->p.semantics != LBM_SEM_BOUNCE_BACK_SOLID) return LBM_OK;
+    return launch_variant(c, [&](auto v) {
+        using R = typename decltype(v)::R;
+        hipLaunchKernelGGL((k_solid_fix<R>), grid_rows(c, c->plan.geo.ny), dim3(BLK), 0, c->s_compute, (R*)c->lat[0], (R*)c->lat[1], c->plan.geo,
+                           c->plan.bstride);
+    });
+}
+
+void solid_free(lbm_ctx* c) {
+    if (c->force_dev) (void)hipFree(c->force_dev);
+    c->force_dev = nullptr;
+}
+
+// The link words of one lattice from its mask m[nx][ny] (0 / 1), as the lattice stores them: [ny][nx], x fastest.
+template <typename R>
+static void link_words(const uint8_t* m, int nx, int ny, R* out) {
+    for (int y = 0; y < ny; ++y)
+        for (int x = 0; x < nx; ++x) {
+            int wd = m[(size_t)x * ny + y] ? LINK_SOLID : 0;
+            for (int k = 1; k < Q; ++k) {
+                const int sx = x - cxk(k), sy = y + cyk(k);
+                if (sx >= 0 && sx < nx && sy >= 0 && sy < ny && m[(size_t)sx * ny + sy]) wd |= 1 << (k - 1);
+            }
+            out[(size_t)y * nx + x] = (R)wd;
+        }
+}
+
+// mask: 0 / 1, [batch][nx][ny]
+template <typename R>
+static int upload_links(lbm_ctx* c, const uint8_t* mask) {
+    const Geo& g = c->plan.geo;
+    const size_t n = (size_t)g.nx * g.ny;
+    std::vector<R> words(n);
+    for (int b = 0; b < c->plan.batch; ++b) {
+        link_words<R>(mask + (size_t)b * n, g.nx, g.ny, words.data());
+        for (int l = 0; l < 2; ++l) {   // plane K_LINK of both lattices: rows of nx words, geo.row elements apart
+            R* dst = (R*)c->lat[l] + (size_t)b * c->plan.bstride + K_LINK * g.plane + g.at(0, 0);
+            HIP_TRY(c, hipMemcpy2D(dst, (size_t)g.row * sizeof(R), words.data(), (size_t)g.nx * sizeof(R), (size_t)g.nx * sizeof(R), (size_t)g.ny,
+                                   hipMemcpyHostToDevice));
+        }
+    }
+    return LBM_OK;
+}
+}  // namespace lbmhost
+
+using namespace lbmhost;
+
+extern "C" {
+
+int lbm_set_solid(lbm_ctx* c, const uint8_t* mask) {
+    if (!c || !mask) return fail(c, LBM_ERR_INVALID, "lbm_set_solid: bad argument");
+    if (c->p.semantics != LBM_SEM_BOUNCE_BACK_SOLID)
+        return fail(c, LBM_ERR_STATE, "lbm_set_solid: this context has no solid mask (create it with semantics = LBM_SEM_BOUNCE_BACK_SOLID)");
+    const size_t n = (size_t)c->plan.geo.nx * c->plan.geo.ny;
+    for (int b = 0; b < c->plan.batch; ++b) {
+        size_t solid = 0;
+        for (size_t i = 0; i < n; ++i) solid += mask[(size_t)b * n + i] ? 1 : 0;
+        if (solid == n) return fail(c, LBM_ERR_INVALID, "lbm_set_solid: lattice " + std::to_string(b) + " of the mask has no fluid cell");
+    }
+    HIP_TRY(c, hipSetDevice(c->p.device));
+    int rc = sync_all(c);
+    if (rc) return rc;
+    // The host copy changes only once both lattices hold the new link planes.  A copy that fails part-way leaves the planes of the two
+    // lattices in an undefined mix of the old and the new mask: the call returns LBM_ERR_HIP, lbm_get_solid still reports the old mask,
+    // and the context must be given a mask again (or destroyed) before it steps.
+    std::vector<uint8_t> next(n * c->plan.batch);
+    for (size_t i = 0; i < next.size(); ++i) next[i] = mask[i] ? 1 : 0;
+    rc = c->plan.es == 4 ? upload_links<float>(c, next.data()) : upload_links<double>(c, next.data());
+    if (rc) return rc;
+    c->solid_mask.swap(next);
+    return lbm_init_equilibrium(c);   // (ends every sampler; solid cells get w_k: solid_fix)
+}
+
+int lbm_get_solid(lbm_ctx* c, uint8_t* mask_out) {
+    if (!c || !mask_out) return fail(c, LBM_ERR_INVALID, "lbm_get_solid: bad argument");
+    if (c->p.semantics != LBM_SEM_BOUNCE_BACK_SOLID)
+        return fail(c, LBM_ERR_STATE, "lbm_get_solid: this context has no solid mask (create it with semantics = LBM_SEM_BOUNCE_BACK_SOLID)");
+    std::memcpy(mask_out, c->solid_mask.data(), c->solid_mask.size());
+    return LBM_OK;
+}
+
+int lbm_solid_force(lbm_ctx* c, lbm_solid_force_record* out) {
+    if (!c || !out) return fail(c, LBM_ERR_INVALID, "lbm_solid_force: bad argument");
+    if (c->p.semantics != LBM_SEM_BOUNCE_BACK_SOLID)
+        return fail(c, LBM_ERR_STATE, "lbm_solid_force: this context has no solid mask (create it with semantics = LBM_SEM_BOUNCE_BACK_SOLID)");
+    if (c->nsteps == 0 || c->raw[c->cur])
+        return fail(c, LBM_ERR_STATE, "lbm_solid_force: no step yet (the lattice holds post-collision populations after one)");
+    HIP_TRY(c, hipSetDevice(c->p.device));
+    int rc = sync_all(c);
+    if (rc) return rc;
+    const int B = c->plan.batch;
+    if (!c->force_dev) {
+        hipError_t e = hipMalloc((void**)&c->force_dev, (size_t)B * (FORCE_BLOCKS * ForceAcc::VALS + 4) * sizeof(double));
+        if (e != hipSuccess) {
+            c->force_dev = nullptr;
+            return fail(c, LBM_ERR_NOMEM, std::string("hipMalloc(solid force): ") + hipGetErrorString(e));
+        }
+    }
+    double* rec = c->force_dev + (size_t)B * FORCE_BLOCKS * ForceAcc::VALS;
+    rc = launch_variant(c, [&](auto v) {
+        using R = typename decltype(v)::R;
+        hipLaunchKernelGGL((k_solid_force<R>), dim3(FORCE_BLOCKS, 1, B), dim3(BLK), 0, c->s_compute, (const R*)c->lat[c->cur], c->plan.geo,
+                           c->plan.bstride, c->force_dev);
+        hipLaunchKernelGGL(k_solid_force_final, dim3(B), dim3(RED_WAVE), 0, c->s_compute, (const double*)c->force_dev, FORCE_BLOCKS,
+                           (double)c->nsteps, rec);
+    });
+    if (rc) return rc;
+    HIP_TRY(c, hipMemcpyAsync(out, rec, (size_t)B * sizeof(lbm_solid_force_record), hipMemcpyDeviceToHost, c->s_compute));
+    HIP_TRY(c, hipStreamSynchronize(c->s_compute));
+    return LBM_OK;
+}
+}  // extern "C"

@@ -1,0 +1,4 @@
+// lbm_solid_f32.hip -- the float instantiations of k_step_solid (lbm_solid.hpp): the six operator variants, with and without
+// non-temporal accesses.
+#define LBM_SOLID_INST LBM_INST_SOLID(float)
+#include "lbm_solid.hpp"

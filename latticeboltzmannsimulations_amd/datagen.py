@@ -22,12 +22,13 @@ from timeit import default_timer as timer
 import numpy as np
 
 from . import residual as RS
+from .solid import mask_from
 from .solver import CavityBatch
 from .stopping import MeanUStop, ResidualStop, by_residual, wall_model
 
 
 def _solve_batch(idx, Re_range, xsize, ysize, RT, turb, uLB, maxIt, Pinterval, tolerance, device, dtype, say, out, arith, convergence="host",
-                 semantics="mrt_gpu", residual_tol=None, residual_final=None, batch_factory=None):
+                 semantics="mrt_gpu", residual_tol=None, residual_final=None, batch_factory=None, solid=None):
     """Runs the lattices Re_range[idx] in lock step; fills out = (f_final, u_final, its) rows idx.  The per-lattice logic is
     the reference's loop body (MRT_GPU_datagen.py:707-731,862-871): a check after iteration It = 0, Pinterval, 2 Pinterval, ...
     (i.e. after It + 1 steps), and a lattice stops where its stop rule says so (stopping.MeanUStop with `tolerance`).
@@ -37,6 +38,8 @@ def _solve_batch(idx, Re_range, xsize, ysize, RT, turb, uLB, maxIt, Pinterval, t
     by_res = residual_final is not None
     f_final, u_final, its = out
     sem = {} if semantics == "mrt_gpu" else {"semantics": semantics}
+    if solid is not None:      # [n, X, Y]: every lattice of the batch its own mask
+        sem["solid"] = np.ascontiguousarray(solid[idx])
     make = CavityBatch if batch_factory is None else batch_factory
     with make(xsize, ysize, [float(Re_range[i]) for i in idx], RT=RT, uLB=uLB, dtype=dtype, turb=turb, device=device, arith=arith, **sem) as b:
         feq_initial = b.get_fields(want_fin=True, out_dtype=np.float32)[2][0]      # fin = equ(1, InitVel) = feq_initial
@@ -97,7 +100,8 @@ def _solve_batch(idx, Re_range, xsize, ysize, RT, turb, uLB, maxIt, Pinterval, t
 
 def generate(Re_range=None, xsize=32 * 12, ysize=32 * 12, RT="SRT", turb=1, uLB=0.08, maxIt=3000000, Pinterval=10000,
              tolerance=0.0000001, OutputFolder="./output", save=True, concurrent=64, devices=(0,), dtype=np.float32,
-             quiet=False, arith="strict", convergence="host", BC="EB-NEBB ", criterion="mean_u", residual_tol=None, batch_factory=None):
+             quiet=False, arith="strict", convergence="host", BC="EB-NEBB ", criterion="mean_u", residual_tol=None, batch_factory=None,
+             solid=None):
     """Returns (feq_initial, f_final, u_final, Re_range, iterations_per_Re); writes the four .npy files when `save`.
     criterion: 'mean_u' (default, the reference's rule) or 'residual' -- each lattice stops at the first check whose field residual (the
     relative L2 change of u per step since the previous check, reduced on the device) is below residual_tol, which must be given; the
@@ -105,13 +109,21 @@ def generate(Re_range=None, xsize=32 * 12, ysize=32 * 12, RT="SRT", turb=1, uLB=
     ran out of iterations, NaN if it saw none), and saves it as residual_final.npy beside the four files, which do not change.
     BC: 'EB-NEBB ' (default, the wet-node walls of MRT_GPU.py) or 'BB' (half-way bounce-back, semantics='bounce_back': the
     cavity's mass is conserved to rounding; needs turb=0).
+    solid: solid obstacles at rest inside every cavity (CavitySolver(solid=...); BC='BB' only) -- one mask [X, Y] for all lattices or
+    [n, X, Y], one per Reynolds number; saved as solid.npy [n, X, Y] beside u_final.npy.  None (default): nothing changes.
     batch_factory (default: CavityBatch, i.e. liblbm_hip.so) exists so that the sweep's loop can be unit-tested with a stand-in, like
     run_cavity's solver_factory; it is not a fallback."""
-    semantics = wall_model(BC, "mrt_gpu", turb)
+    semantics = wall_model(BC, "mrt_gpu", turb, solid is not None)
     by_res = by_residual(criterion, residual_tol)
     say = (lambda *a: None) if quiet else print
     Re_range = np.arange(100, 5100, 10) if Re_range is None else np.asarray(Re_range)   # MRT_GPU_datagen.py:55
     n = len(Re_range)
+    if solid is not None:
+        solid = np.asarray(solid) != 0
+        if solid.shape == (xsize, ysize):
+            solid = np.broadcast_to(solid, (n, xsize, ysize))
+        if solid.shape != (n, xsize, ysize):
+            raise ValueError(f"solid must have shape {(xsize, ysize)} or {(n, xsize, ysize)}")
     tstart = timer()
     out = (np.zeros((n, 9, xsize, ysize), dtype=np.float32), np.zeros((n, 2, xsize, ysize), dtype=np.float32),
            np.zeros(n, dtype=np.int64))
@@ -121,7 +133,7 @@ def generate(Re_range=None, xsize=32 * 12, ysize=32 * 12, RT="SRT", turb=1, uLB=
     def work(k):
         return _solve_batch(chunks[k], Re_range, xsize, ysize, RT, turb, uLB, maxIt, Pinterval, tolerance,
                             devices[k % len(devices)], dtype, say, out, arith, convergence, semantics,
-                            float(residual_tol) if by_res else None, residual_final, batch_factory)
+                            float(residual_tol) if by_res else None, residual_final, batch_factory, solid)
     if len(devices) > 1 and len(chunks) > 1:
         with ThreadPoolExecutor(max_workers=len(devices)) as pool:      # lbm_step runs in C with the GIL released
             feq = list(pool.map(work, range(len(chunks))))
@@ -138,6 +150,8 @@ def generate(Re_range=None, xsize=32 * 12, ysize=32 * 12, RT="SRT", turb=1, uLB=
         np.save(os.path.join(OutputFolder, "Re_range.npy"), Re_range)
         if by_res:
             np.save(os.path.join(OutputFolder, "residual_final.npy"), residual_final)
+        if solid is not None:
+            np.save(os.path.join(OutputFolder, "solid.npy"), np.ascontiguousarray(solid))
     say("TOTAL time elapsed is ", timer() - tstart, "seconds")
     if by_res:
         return feq_initial, f_final, u_final, Re_range, its, residual_final
@@ -162,8 +176,16 @@ def main(argv=None):
     ap.add_argument("--criterion", choices=["mean_u", "residual"], default="mean_u",
                     help="stop rule per lattice: the reference's test on mean(u), or the field residual reduced on the GPU")
     ap.add_argument("--residual-tol", type=float, default=None, help="with --criterion residual: stop below this value (required, no default)")
+    ap.add_argument("--solid-box", type=int, nargs=4, action="append", default=[], metavar=("X0", "X1", "Y0", "Y1"),
+                    help="a solid obstacle in every cavity: the cells [X0, X1) x [Y0, Y1), y = 0 the lid (repeatable; needs --BC BB)")
     a = ap.parse_args(argv)
     bb = dict(BC="BB", turb=0) if a.BC == "BB" else {}
+    if a.solid_box:
+        try:
+            bb["solid"] = mask_from(a.size, a.size, a.solid_box)
+            wall_model(a.BC, "mrt_gpu", bb.get("turb", 1), True)
+        except ValueError as e:
+            ap.error(str(e))
     generate(np.arange(*a.Re), xsize=a.size, ysize=a.size, concurrent=a.concurrent, Pinterval=a.Pinterval, maxIt=a.maxIt,
              OutputFolder=a.OutputFolder, arith=a.arith, convergence=a.convergence, criterion=a.criterion, residual_tol=a.residual_tol,
              **bb)

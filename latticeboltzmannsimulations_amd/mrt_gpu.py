@@ -27,6 +27,7 @@ from . import ghia
 from . import residual as RS
 from .VTKWrapper import saveToVTK
 from .monitor import vortex_window
+from .solid import mask_from
 from .solver import CavitySolver
 from .stopping import MeanUStop, ResidualStop, by_residual, wall_model
 
@@ -54,6 +55,7 @@ class CavityResult:
         self.series = None          # run_cavity(MonitorEvery=k): CavitySolver.monitor_series() of the whole run
         self.vortex_tables = []     # run_cavity(vortex_table=True): (iteration, CavitySolver.vortex_table()) at every output iteration
         self.residuals = []         # run_cavity(criterion="residual"): (iteration, residual record) at every output iteration after the first
+        self.forces = []            # run_cavity(solid=mask): (iteration, CavitySolver.solid_force()) at every output iteration
 
 
 CS2_EFFECTIVE, CS_BULK = 0.025, 0.16     # MRT_GPU.py:350,374-376: Van Driest damping is overwritten by Cs2 = 0.025
@@ -148,7 +150,8 @@ def _vortex_lines(table, Re, xsize, ysize, uLB):
     return lines
 
 
-def _check_arguments(criterion, residual_tol, residual_hits, monitor, MonitorEvery, convergence, AverageFrom, AverageEvery, BC, semantics, turb):
+def _check_arguments(criterion, residual_tol, residual_hits, monitor, MonitorEvery, convergence, AverageFrom, AverageEvery, BC, semantics, turb,
+                     solid=None):
     """(criterion is 'residual', semantics); ValueError for an argument run_cavity cannot run with."""
     residual = by_residual(criterion, residual_tol, residual_hits)
     if monitor not in ("host", "device"):
@@ -159,7 +162,7 @@ def _check_arguments(criterion, residual_tol, residual_hits, monitor, MonitorEve
         raise ValueError("convergence must be 'host' or 'device'")
     if AverageFrom is not None and (int(AverageFrom) < 0 or int(AverageEvery) < 1):
         raise ValueError("AverageFrom must be >= 0 and AverageEvery >= 1")
-    return residual, wall_model(BC, semantics, turb)
+    return residual, wall_model(BC, semantics, turb, solid is not None)
 
 
 def _banner(say, Re, RT, turb, relax):
@@ -301,7 +304,7 @@ def run_cavity(maxIt=3000000, Re=10000.0, RT="SRT", turb=1, xsize=32 * 5, ysize=
                Pinterval=3000, SavePlot=True, SaveVTK=False, project="ldc", OutputFolder="./output",
                dtype=np.float32, semantics="mrt_gpu", device=0, quiet=False, solver_factory=None, arith="strict",
                convergence="host", vtk_correct=False, BC="EB-NEBB ", AverageFrom=None, AverageEvery=100, monitor="host",
-               MonitorEvery=None, Probes=(), vortex_table=False, criterion="mean_u", residual_tol=None, residual_hits=1):
+               MonitorEvery=None, Probes=(), vortex_table=False, criterion="mean_u", residual_tol=None, residual_hits=1, solid=None):
     """Run the lid-driven cavity like MRT_GPU.py does; returns a :class:`CavityResult`.
 
     Argument names and defaults are the module constants of MRT_GPU.py:38-58.
@@ -335,9 +338,13 @@ def run_cavity(maxIt=3000000, Re=10000.0, RT="SRT", turb=1, xsize=32 * 5, ysize=
     `current residual is <relative L2 change of u per step>` (residual.norms(record, uLB)["rel_l2_per_step"]) and appends
     (iteration, record) to result.residuals; the run ends with result.converged once that value is below residual_tol at
     residual_hits consecutive checks.  residual_tol has no default -- the floor the residual settles on depends on dtype and lattice
-    size -- and must be given.  With either monitor mode."""
+    size -- and must be given.  With either monitor mode.
+    solid: a mask [xsize, ysize] whose nonzero cells are solid obstacles at rest (CavitySolver(solid=...); BC='BB' only).  Every
+    Pinterval is then an output iteration, each one prints `current force on the obstacles is (fx, fy) over N links` -- the momentum-
+    exchange force reduced on the device, CavitySolver.solid_force() -- and appends (iteration, that record) to result.forces.  None
+    (default): nothing changes."""
     by_res, semantics = _check_arguments(criterion, residual_tol, residual_hits, monitor, MonitorEvery, convergence, AverageFrom,
-                                         AverageEvery, BC, semantics, turb)
+                                         AverageEvery, BC, semantics, turb, solid)
     on_device = monitor == "device"
     say = (lambda *a: None) if quiet else print
     tstart = timer()
@@ -345,6 +352,8 @@ def run_cavity(maxIt=3000000, Re=10000.0, RT="SRT", turb=1, xsize=32 * 5, ysize=
     say("xsize value is ", xsize)
     make = CavitySolver if solver_factory is None else solver_factory
     extra = {} if arith == "strict" else {"arith": arith}      # 'fast' / 'promoted': see CavitySolver
+    if solid is not None:
+        extra["solid"] = solid
     solver = make(xsize, ysize, Re, RT=RT, uLB=uLB, semantics=semantics, dtype=dtype, turb=turb, device=device, **extra)
     _banner(say, Re, RT, turb, solver.relax)
     if (SavePlot or SaveVTK) and not os.path.isdir(OutputFolder):
@@ -359,7 +368,7 @@ def run_cavity(maxIt=3000000, Re=10000.0, RT="SRT", turb=1, xsize=32 * 5, ysize=
                           BC="BB" if semantics == "bounce_back" else "EB-NEBB ")   # (the dashboard's label; MRT_GPU.py:281 spells the default so)
     res = CavityResult()
     done = 0          # iterations performed
-    outputs = SaveVTK or SavePlot or on_device or bool(vortex_table) or by_res
+    outputs = SaveVTK or SavePlot or on_device or bool(vortex_table) or by_res or solid is not None
     averaging = False
 
     def advance(n):   # n iterations; statistics begin once `done` reaches AverageFrom
@@ -395,6 +404,10 @@ def run_cavity(maxIt=3000000, Re=10000.0, RT="SRT", turb=1, xsize=32 * 5, ysize=
                     res.diverged = True
                     break
                 _report(say, res, run, c, It)
+                if solid is not None:
+                    F = solver.solid_force()
+                    res.forces.append((It, F))
+                    say("current force on the obstacles is (" + str(F["fx"]) + ", " + str(F["fy"]) + ") over " + str(F["links"]) + " links")
                 _write_files(solver, run, c, It, res.regression)
                 say("time elapsed is ", (timer() - tstart), "seconds")
                 if by_res:
@@ -453,14 +466,25 @@ def main(argv=None):
     ap.add_argument("--residual-hits", type=int, default=1, help="with --criterion residual: consecutive checks below the tolerance")
     ap.add_argument("--vortex-table", action="store_true",
                     help="at every output iteration: Ghia's named vortices from the stream function's extrema, reduced on the device")
+    ap.add_argument("--solid-box", type=int, nargs=4, action="append", default=[], metavar=("X0", "X1", "Y0", "Y1"),
+                    help="a solid obstacle: the cells [X0, X1) x [Y0, Y1), y = 0 the lid (repeatable; needs --BC BB --turb 0)")
+    ap.add_argument("--solid-file", default=None, help="a .npy mask [xsize, ysize] whose nonzero cells are solid (needs --BC BB --turb 0)")
     a = ap.parse_args(argv)
+    mask = None
+    if a.solid_box or a.solid_file is not None:      # an obstacle the run cannot have is an argument error, through the one check
+        try:
+            mask = mask_from(a.xsize, a.ysize, a.solid_box, a.solid_file)
+            _check_arguments(a.criterion, a.residual_tol, a.residual_hits, a.monitor, a.monitor_every, a.convergence, a.average_from,
+                             a.average_every, a.BC, a.semantics, a.turb, mask)
+        except (ValueError, OSError) as e:
+            ap.error(str(e))
     r = run_cavity(maxIt=a.maxIt, Re=a.Re, RT=a.RT, turb=a.turb, xsize=a.xsize, ysize=a.ysize, uLB=a.uLB,
                    Pinterval=a.Pinterval, SavePlot=not a.no_plot, SaveVTK=a.vtk, project=a.project,
                    OutputFolder=a.OutputFolder, dtype=np.dtype(a.dtype), semantics=a.semantics, arith=a.arith,
                    convergence=a.convergence, vtk_correct=a.vtk_correct, BC="BB" if a.BC == "BB" else "EB-NEBB ",
                    AverageFrom=a.average_from, AverageEvery=a.average_every, monitor=a.monitor, MonitorEvery=a.monitor_every,
                    Probes=tuple(tuple(p) for p in a.probe), vortex_table=a.vortex_table, criterion=a.criterion,
-                   residual_tol=a.residual_tol, residual_hits=a.residual_hits)
+                   residual_tol=a.residual_tol, residual_hits=a.residual_hits, solid=mask)
     print("MLUPS : ", r.mlups)
     return 0
 

@@ -14,6 +14,7 @@ from . import topology as T
 _DT = {np.dtype(np.float32): L.LBM_F32, np.dtype(np.float64): L.LBM_F64}
 _COLL = {"SRT": L.LBM_SRT, "TRT": L.LBM_TRT, "MRT": L.LBM_MRT}
 _SEM = {"mrt_py": L.LBM_SEM_MRT_PY, "mrt_gpu": L.LBM_SEM_MRT_GPU, "bounce_back": L.LBM_SEM_BOUNCE_BACK}
+_SEM_SOLID = "bounce_back_solid"    # what semantics='bounce_back' becomes with solid=...: LBM_SEM_BOUNCE_BACK_SOLID
 _KERNEL = {"auto": L.LBM_KERNEL_AUTO, "generic": L.LBM_KERNEL_GENERIC, "vec": L.LBM_KERNEL_VEC, "tb": L.LBM_KERNEL_TB,
            "push": L.LBM_KERNEL_PUSH, "stream": L.LBM_KERNEL_STREAM}
 _ARITH = {"strict": L.LBM_ARITH_STRICT, "fast": L.LBM_ARITH_FAST, "promoted": L.LBM_ARITH_PROMOTED}
@@ -83,6 +84,10 @@ class CavitySolver:
                    semantics='mrt_gpu' only)
     min_rows     : slabs: the smallest ny_local of ALL slabs of the decomposition (lbm_params.ny_local_min) -- the launch plan is
                    derived from it, so that neighbours run the same exchange protocol
+    solid        : None (default), or a mask [X, Y] (a CavityBatch: [B, X, Y], or [X, Y] for all lattices) whose nonzero cells are solid
+                   obstacles at rest inside the cavity (semantics='bounce_back' only; the context is then LBM_SEM_BOUNCE_BACK_SOLID): a
+                   source that is a solid cell bounces like a wall, solid cells hold the rest equilibrium (u = 0 in every export), one
+                   step per launch (kernel 'auto' or 'generic'), no slabs.  See set_solid, solid, solid_force.
     tuning       : A/B switches of the launch plan, none of which changes a result: tb_steps (2..5 steps per launch; 2..8 with kernel='stream'),
                    frame_seg, and the boolean flags deep_halo, frame_fused, frame_fused_batch, frame_lds, nt, comm_priority,
                    eager_lag, frame_beside, frame_wide, edge_first, edge_reserve, xcd_bands, tail_tiles (lbm_params.tb_steps / frame_seg / flags)
@@ -90,7 +95,7 @@ class CavitySolver:
 
     def __init__(self, xsize, ysize, Re, RT="MRT", uLB=0.08, semantics="mrt_gpu", dtype=np.float32, turb=0,
                  device=0, rows=None, kernel="auto", layout="auto", omega_eps=None, omega_q=None, batch=1, arith="strict",
-                 min_rows=None, tuning=None):
+                 min_rows=None, tuning=None, solid=None):
         self._h = None
         self.batch = int(batch)
         self._lead = getattr(self, "_lead", ())      # leading axes of the host arrays: (B,) for a CavityBatch
@@ -113,13 +118,22 @@ class CavitySolver:
         self.y0, self.ny_local = (0, self.ny) if rows is None else (int(rows[0]), int(rows[1]))
         self.turb = int(turb)
         self.arith = arith
-        p = _params(self.nx, self.ny, self.y0, self.ny_local, self.dtype, RT, semantics, kernel, turb, device, layout, self.batch, arith,
-                    min_rows, tuning, self.uLB, self.relax)
+        self.has_solid = solid is not None
+        if self.has_solid and semantics != "bounce_back":
+            raise ValueError("solid=... needs semantics='bounce_back'")
+        p = _params(self.nx, self.ny, self.y0, self.ny_local, self.dtype, RT, _SEM_SOLID if self.has_solid else semantics, kernel, turb, device,
+                    layout, self.batch, arith, min_rows, tuning, self.uLB, self.relax)
         err = ctypes.create_string_buffer(512)
         h = self.lib.lbm_create(ctypes.byref(p), err, len(err))
         if not h:
             raise RuntimeError("lbm_create: " + err.value.decode())
         self._h = ctypes.c_void_p(h)
+        if self.has_solid:
+            try:
+                self.set_solid(solid)
+            except Exception:
+                self.close()
+                raise
 
     # -- plumbing ---------------------------------------------------------------------
     def _check(self, rc, what):
@@ -419,6 +433,48 @@ class CavitySolver:
             return [T.vortex_table(r, self.nx, self.ny) for r in rec]
         return T.vortex_table(rec, self.nx, self.ny)
 
+    # -- solid obstacles (lbm_set_solid, lbm_get_solid, lbm_solid_force) ---------------------------------
+    def _mask(self, mask):
+        """A mask as the library takes it: uint8 0 / 1, C order, [X, Y] (a batch: [B, X, Y]; one [X, Y] mask serves every lattice)."""
+        m = np.asarray(mask) != 0
+        if self._lead and m.shape == (self.nx, self.ny):
+            m = np.broadcast_to(m, self._lead + m.shape)
+        if m.shape != self._lead + (self.nx, self.ny):
+            raise ValueError(f"solid mask must have shape {self._lead + (self.nx, self.ny)}")
+        return np.ascontiguousarray(m, dtype=np.uint8)
+
+    def _need_solid(self):
+        if not self.has_solid:
+            raise RuntimeError("this solver has no solid mask: create it with semantics='bounce_back', solid=mask")
+
+    def set_solid(self, mask):
+        """A new solid mask (lbm_set_solid): ends every sampler and restarts the lattice from the initial equilibrium, solid cells at
+        the rest equilibrium.  Every lattice needs at least one fluid cell."""
+        self._need_solid()
+        m = self._mask(mask)
+        self._check(self.lib.lbm_set_solid(self._h, m.ctypes.data), "lbm_set_solid")
+        return self
+
+    @property
+    def solid(self):
+        """A copy of the solid mask, bool [X, Y] (a batch: [B, X, Y]); None without solid=..."""
+        if not self.has_solid:
+            return None
+        m = np.zeros(self._lead + (self.nx, self.ny), dtype=np.uint8)
+        self._check(self.lib.lbm_get_solid(self._h, m.ctypes.data), "lbm_get_solid")
+        return m.astype(bool)
+
+    def solid_force(self):
+        """The momentum-exchange force of the fluid on the solid cells, reduced on the device (lbm_solid_force): dict(step, links, fx,
+        fy) -- solid.host_force(get_fields(want_fin=True)[2], mask) to the rounding of a double sum; fy > 0 points to the lid, as u[1].
+        A batch returns arrays [B].  Not before the first step."""
+        self._need_solid()
+        rec = (L.lbm_solid_force_record * self.batch)()
+        self._check(self.lib.lbm_solid_force(self._h, rec), "lbm_solid_force")
+        out = {k: np.array([getattr(r, k) for r in rec]) for k in ("step", "links", "fx", "fy")}
+        out["step"], out["links"] = out["step"].astype(np.int64), out["links"].astype(np.int64)
+        return out if self._lead else {k: v[0].item() for k, v in out.items()}
+
     # -- checkpoint / restart (the reference has neither; SURVEY 8f item 4) -------------------
     def save_checkpoint(self, path):
         """Write the populations and the run parameters to `path` (.npz).  Restarting from it continues bit-identically
@@ -428,14 +484,15 @@ class CavitySolver:
         path = _npz(path)
         np.savez(path, fin=fin, steps_done=self.steps_done, nx=self.nx, ny=self.ny, Re=self.Re, RT=self.RT, uLB=self.uLB,
                  semantics=self.semantics, dtype=self.dtype.name, rows=np.array([self.y0, self.ny_local]), turb=self.turb, u=u, rho=rho,
-                 arith=self.arith)
+                 arith=self.arith, **(dict(solid=self.solid) if self.has_solid else {}))
         return path
 
     def load_checkpoint(self, path, strict=True):
         """Upload the populations of a checkpoint written by save_checkpoint; returns the number of steps the checkpointed
         run had done.  The lattice size must match; with `strict` (default) so must dtype, semantics, collision operator,
         closure and Reynolds number -- a continuation is bit-identical only then -- and, where either side is 'promoted', the
-        arithmetic (strict and fast states mix as before; a checkpoint without the key counts as strict).  The array is the whole lattice, so a slab
+        arithmetic (strict and fast states mix as before; a checkpoint without the key counts as strict) and the solid mask (none on either
+        side, or the same cells; without `strict` the populations are uploaded under this solver's own mask).  The array is the whole lattice, so a slab
         may restart from a checkpoint of the undivided lattice (each context reads its own rows) but not from another slab's."""
         with np.load(_npz(path), allow_pickle=False) as z:
             if int(z["nx"]) != self.nx or int(z["ny"]) != self.ny:
@@ -451,6 +508,10 @@ class CavitySolver:
                 arith = str(z["arith"]) if "arith" in z else "strict"
                 if "promoted" in (arith, self.arith) and arith != self.arith:
                     diff["arith"] = (arith, self.arith)
+                mask = np.asarray(z["solid"], dtype=bool) if "solid" in z else None
+                if (mask is None) != (not self.has_solid) or (mask is not None and not np.array_equal(mask, self.solid)):
+                    diff["solid"] = ("none" if mask is None else f"{int(mask.sum())} solid cells",
+                                     f"{int(self.solid.sum())} solid cells" if self.has_solid else "none")
                 if diff:
                     raise ValueError(f"checkpoint was written by a different run (checkpoint, this solver): {diff}")
             self.set_state(np.ascontiguousarray(z["fin"]))
@@ -537,7 +598,8 @@ def _params(nx, ny, y0, ny_local, dtype, RT, semantics, kernel, turb, device, la
     p = L.lbm_params()
     p.struct_size = ctypes.sizeof(L.lbm_params)
     p.nx, p.ny, p.y0, p.ny_local = int(nx), int(ny), int(y0), int(ny_local)
-    p.dtype, p.collision, p.semantics = _DT[np.dtype(dtype)], _COLL[RT], _SEM[semantics]
+    p.dtype, p.collision = _DT[np.dtype(dtype)], _COLL[RT]
+    p.semantics = L.LBM_SEM_BOUNCE_BACK_SOLID if semantics == _SEM_SOLID else _SEM[semantics]
     p.kernel, p.turb, p.device = _KERNEL[kernel], int(turb), int(device)
     p.layout = _LAYOUT[layout]
     p.batch = int(batch)
@@ -553,11 +615,16 @@ def _params(nx, ny, y0, ny_local, dtype, RT, semantics, kernel, turb, device, la
 
 
 def launch_plan(xsize, ysize, Re, steps=0, ncu=0, RT="MRT", uLB=0.08, semantics="mrt_gpu", dtype=np.float32, turb=0, rows=None,
-                kernel="auto", layout="auto", batch=1, arith="strict", min_rows=None, tuning=None):
+                kernel="auto", layout="auto", batch=1, arith="strict", min_rows=None, tuning=None, solid=False):
     """Dry run (lbm_plan, NO GPU needed): the launch plan lbm_create would derive for these arguments -- the dict of
     CavitySolver.describe() -- plus `units`, the launch units step(steps) would run from a fresh lattice.  All ranks of a slab
     decomposition must agree on kernel / steps_per_launch / frame / deep_halo and on the units: a launcher (bench.py --gpus N) and
-    the CPU tests check that before any rank touches a device."""
+    the CPU tests check that before any rank touches a device.  solid=True: the plan of the same arguments with a solid mask (solid=... of
+    CavitySolver; semantics='bounce_back' only)."""
+    if solid:
+        if semantics != "bounce_back":
+            raise ValueError("solid=True needs semantics='bounce_back'")
+        semantics = _SEM_SOLID
     ny = int(ysize)
     y0, nyl = (0, ny) if rows is None else (int(rows[0]), int(rows[1]))
     relax = relaxation(float(Re), ny, float(uLB), 1.0 if semantics == "mrt_py" else 1.2, 1.2)

@@ -33,11 +33,14 @@ class ResidualStop:
         return value, self.count >= self.hits
 
 
-def wall_model(BC, semantics, turb):
-    """The semantics the wall model BC selects: 'EB-NEBB ' keeps `semantics`, 'BB' is 'bounce_back' (without the closure)."""
+def wall_model(BC, semantics, turb, solid=False):
+    """The semantics the wall model BC selects: 'EB-NEBB ' keeps `semantics`, 'BB' is 'bounce_back' (without the closure).  solid: the
+    run has solid obstacles, which exist with the bounce-back walls only."""
     bc = BC.strip()
     if bc not in ("EB-NEBB", "BB"):
         raise ValueError("BC must be 'EB-NEBB ' or 'BB'")
+    if solid and bc != "BB":
+        raise ValueError("solid obstacles need the bounce-back walls: pass BC='BB' (and turb=0)")
     if bc == "BB":
         if semantics not in ("mrt_gpu", "bounce_back"):
             raise ValueError(f"BC='BB' selects semantics='bounce_back', not {semantics!r}")

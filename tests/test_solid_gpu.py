@@ -1,0 +1,304 @@
+"""GPU tests of solid obstacles in the bounce-back cavity (CavitySolver(..., semantics='bounce_back', solid=mask),
+LBM_SEM_BOUNCE_BACK_SOLID): strict arithmetic bit for bit against the NumPy reference tests/solid_ref.py on the vector kernel
+(k_step_solid) and the generic route, the all-fluid mask against plain bounce-back, `fast` arithmetic within the bound of
+tests/test_bounce_back_gpu.py, batches, the samplers on a masked lattice, the force on the obstacles, a mirror-image pair,
+checkpoints and the error paths."""
+import math
+import os
+import sys
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+from solid_ref import SolidOracle  # noqa: E402
+from test_bounce_back_gpu import FAST_BOUND  # noqa: E402  (the bound of fast bounce-back: the mask selects populations, adds no arithmetic)
+from latticeboltzmannsimulations_amd import CavityBatch, CavitySolver, solid  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+BB = dict(semantics="bounce_back")
+
+
+def _masks(nx, ny, seed=11):
+    """name -> mask: the cases the kernel can get wrong.  Block edges fall at x = 3 and x = 0 (mod 4) -- the last and the first cell of
+    a thread's four (two) -- and, on the wide lattices, straddle the seams between two workgroups' cells at x = 511 | 512 and 1023 | 1024."""
+    z = lambda: np.zeros((nx, ny), dtype=bool)  # noqa: E731
+    out = {"fluid": z()}
+    m = z(); m[nx // 2, ny // 2] = True
+    out["cell"] = m
+    m = z()
+    y0, y1 = max(1, ny // 4), min(ny - 1, ny // 4 + 6)
+    m[19:25, y0:y1] = True                       # columns 19 .. 24
+    for seam in (512, 1024):
+        if nx > seam + 4:
+            m[seam - 5:seam + 5, y0:y1] = True   # columns seam - 5 (= 3 mod 4) .. seam + 4 (= 0 mod 4)
+    out["block"] = m
+    m = z()
+    for i in range(min(nx, ny) - 3):             # a diagonal staircase: solid cells that touch at corners only
+        m[2 + i, 1 + i] = True
+    out["stairs"] = m
+    m = z()                                      # cells on each wall, in each corner and in the lid row
+    m[0, ny // 2] = m[nx - 1, ny // 3] = m[nx // 2, ny - 1] = True
+    m[0, 0] = m[nx - 1, 0] = m[0, ny - 1] = m[nx - 1, ny - 1] = True
+    m[nx // 3:nx // 3 + 5, 0] = True
+    m[7, 0:2] = True
+    out["walls"] = m
+    out["random"] = np.random.default_rng(seed).random((nx, ny)) < 0.2
+    return out
+
+
+def _same(s, o, what):
+    u, rho, fin = s.get_fields(want_fin=True)
+    assert np.isfinite(fin).all() and np.isfinite(u).all() and np.isfinite(rho).all(), f"{what}: not finite"
+    assert np.array_equal(fin, o.fin), f"{what}: fin differs in {np.count_nonzero(fin != o.fin)} values, max abs {np.abs(fin - o.fin).max()}"
+    assert np.array_equal(rho, o.rho), f"{what}: rho differs"
+    assert np.array_equal(u, o.u), f"{what}: u differs"
+    return u, rho, fin
+
+
+def _same_fields(a, b, what):
+    fa, fb = a.get_fields(want_fin=True), b.get_fields(want_fin=True)
+    for x, y, name in zip(fa, fb, ("u", "rho", "fin")):
+        assert np.array_equal(x, y), f"{what}: {name} differs"
+
+
+# 72 x 40: one partial workgroup; 70 x 66: the generic route (70 is no multiple of 4; in fp64 the vector route, 70 % 2 == 0);
+# 1032 x 8: a row spans two workgroups in fp32 (and three in fp64); 520 x 8, fp64: the seam at 511 | 512
+SHAPES = {np.float32: [(72, 40), (70, 66), (1032, 8)], np.float64: [(72, 40), (70, 66), (1032, 8), (520, 8)]}
+CASES = [(c, d, s) for d in (np.float32, np.float64) for c in ("SRT", "TRT", "MRT") for s in SHAPES[d]]
+
+
+@pytest.mark.parametrize("coll,dtype,shape", CASES, ids=lambda v: v if isinstance(v, str) else (f"{v[0]}x{v[1]}" if isinstance(v, tuple) else np.dtype(v).name))
+def test_strict_bit_identical_to_reference(coll, dtype, shape):
+    """After 1, 2, 7 and 37 steps from lbm_set_solid's initial state, then from a set_state of the developed state (whose solid cells
+    the host array fills with rubbish: the library writes w_k there); the default route and kernel='generic' against the reference and
+    against each other."""
+    nx, ny = shape
+    V = 4 if dtype == np.float32 else 2
+    with CavitySolver(nx, ny, 100.0, RT=coll, dtype=dtype, solid=np.zeros(shape, bool), **BB) as s, \
+            CavitySolver(nx, ny, 100.0, RT=coll, dtype=dtype, kernel="generic", solid=np.zeros(shape, bool), **BB) as g:
+        d = s.describe()
+        assert d["semantics"] == "bounce_back_solid" and d["steps_per_launch"] == 1
+        assert d["kernel"] == ("k_step_solid" if nx % V == 0 else "k_step_generic") and g.describe()["kernel"] == "k_step_generic"
+        for name, m in _masks(nx, ny).items():
+            o = SolidOracle(nx, ny, 100.0, mask=m, collision=coll, dtype=dtype)
+            s.set_solid(m); g.set_solid(m)
+            assert np.array_equal(s.solid, m) and s.next_unit(100) == 1
+            for phase in range(2):
+                if phase:
+                    f = o.fin.copy()
+                    o.set_state(f)
+                    f[:, m] = -7.0
+                    s.set_state(f); g.set_state(f)
+                for n in (1, 1, 5, 30):
+                    s.step(n); g.step(n); o.step(n)
+                    what = f"{nx}x{ny} {coll} {np.dtype(dtype).name} mask {name} phase {phase} after {o.nsteps}"
+                    _, _, fin = _same(s, o, what)
+                    _same_fields(g, s, what + " generic")
+                    assert np.array_equal(fin[:, m], np.broadcast_to(o.t[:, None], (9, int(m.sum())))), what + ": solid cells"
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+def test_all_fluid_mask_equals_plain_bounce_back(dtype):
+    for nx, ny in ((72, 40), (1032, 8)):
+        with CavitySolver(nx, ny, 400.0, RT="MRT", dtype=dtype, kernel="generic", **BB) as plain, \
+                CavitySolver(nx, ny, 400.0, RT="MRT", dtype=dtype, solid=np.zeros((nx, ny), bool), **BB) as s:
+            for n in (1, 6, 30):
+                plain.step(n); s.step(n)
+                _same_fields(s, plain, f"{nx}x{ny} after {s.steps_done}")
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+@pytest.mark.parametrize("coll", ["SRT", "TRT", "MRT"])
+def test_fast_arithmetic(coll, dtype):
+    """The configuration of test_bounce_back_gpu.test_fast_arithmetic_within_bound (128 x 96, Re 1000, 2000 steps) with obstacles: the
+    two routes agree bit for bit, and the distance from strict fp64 stays inside that test's bound."""
+    nx, ny = 128, 96
+    m = np.zeros((nx, ny), bool)
+    m[35:49, 30:50] = True
+    m[90, 0:3] = m[0, 60] = m[100:103, ny - 1] = True
+    with CavitySolver(nx, ny, 1000.0, RT=coll, dtype=np.float64, solid=m, **BB) as ref:
+        ref.step(2000)
+        f_ref = ref.get_fields(want_fin=True)[2]
+    got = []
+    for kernel in ("auto", "generic"):
+        with CavitySolver(nx, ny, 1000.0, RT=coll, dtype=dtype, arith="fast", kernel=kernel, solid=m, **BB) as s:
+            assert s.describe()["kernel"] == ("k_step_solid" if kernel == "auto" else "k_step_generic")
+            s.step(2000)
+            got.append(s.get_fields(want_fin=True, out_dtype=np.float64)[2])
+    assert np.array_equal(got[0], got[1]), "fast arithmetic differs between the routes"
+    err = float(np.abs(got[0] - f_ref).max() / np.abs(f_ref).max())
+    print(f"fast solid {coll} {np.dtype(dtype).name}: {err:.3e} (bound {FAST_BOUND[dtype]:.1e})")
+    assert err < FAST_BOUND[dtype], err
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+def test_batch_of_masks_equals_lattices_alone(dtype):
+    nx, ny = 72, 40
+    ms = _masks(nx, ny)
+    masks, Res = np.stack([ms["block"], ms["random"], ms["walls"]]), [100.0, 400.0, 1000.0]
+    with CavityBatch(nx, ny, Res, RT="MRT", dtype=dtype, solid=masks, **BB) as b:
+        assert np.array_equal(b.solid, masks)
+        b.step(1); b.step(22)
+        u, rho, fin = b.get_fields(want_fin=True)
+        F = b.solid_force()
+    for i, Re in enumerate(Res):
+        with CavitySolver(nx, ny, Re, RT="MRT", dtype=dtype, solid=masks[i], **BB) as s:
+            s.step(23)
+            u1, r1, f1 = s.get_fields(want_fin=True)
+            F1 = s.solid_force()
+        assert np.array_equal(fin[i], f1) and np.array_equal(u[i], u1) and np.array_equal(rho[i], r1), Re
+        assert {k: F[k][i] for k in F} == F1, Re
+
+
+def test_samplers_see_a_steady_finite_body():
+    """monitor, residual, topology and statistics on a masked lattice against their host restatements applied to get_fields of the same
+    context (u = 0 in the body), with the assertions of their own GPU tests."""
+    import warnings
+    from test_monitor_gpu import _same_record as same_monitor
+    from test_residual_gpu import _same_record as same_residual
+    from test_statistics_gpu import HostStats, _same_stats
+    from test_topology_gpu import _check as check_topology
+    nx, ny = 72, 40
+    m = _masks(nx, ny)["block"] | _masks(nx, ny)["walls"]
+    for dtype in (np.float32, np.float64):
+        with CavitySolver(nx, ny, 100.0, RT="MRT", dtype=dtype, solid=m, **BB) as s:
+            s.step(30)
+            u, rho = s.get_fields()
+            assert not u[:, m].any() and np.all(rho[m] == rho[m][0]) and abs(float(rho[m][0]) - 1.0) < 1e-6
+            rec = s.monitor(probes=((20, ny // 4 + 1), (3, 3)))
+            assert rec["nonfinite"] == 0
+            same_monitor(rec, u, rho, s.uLB, "monitor", probes=((20, ny // 4 + 1), (3, 3)))
+            host = HostStats()
+            s.begin_statistics(); s.begin_residual()
+            samples = []
+            for n in (0, 3, 4):
+                s.step(n)
+                s.sample_statistics(); s.sample_residual()
+                uu, rr = s.get_fields()
+                host.add(uu, rr)
+                samples.append((s.steps_done, uu, rr))
+            _same_stats(s, host, "statistics")
+            got = s.residual_series()
+            assert got["count"] == 2 and got["dropped"] == 0
+            for i in range(2):
+                r = {k: got[k][i] for k in got if k not in ("count", "dropped")}
+                assert r["nonfinite"] == 0 and r["cells"] == nx * ny
+                same_residual(r, samples[i], samples[i + 1], f"residual {i}")
+            with warnings.catch_warnings():
+                warnings.simplefilter("ignore")
+                check_topology(s, "topology", (dtype,))
+            psi, _ = s.stream_function()
+            assert np.isfinite(psi).all()
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+def test_force_on_the_obstacles(dtype):
+    """links exactly; fx, fy against the exactly rounded host sum within links * 2^-52 * sum |terms|, the worst case of a double sum of
+    that many terms; two calls give the same bits; LBM_ERR_STATE before the first step."""
+    for nx, ny in ((72, 40), (1032, 8)):
+        for name, m in _masks(nx, ny).items():
+            with CavitySolver(nx, ny, 100.0, RT="MRT", dtype=dtype, solid=m, **BB) as s:
+                rec = (s.lib.lbm_solid_force.argtypes[1]._type_ * 1)()
+                assert s.lib.lbm_solid_force(s._h, rec) == -4, "LBM_ERR_STATE before the first step"
+                s.step(23)
+                F, F2 = s.solid_force(), s.solid_force()
+                fin = s.get_fields(want_fin=True)[2]
+            assert F == F2 and F["step"] == 23
+            want = solid.host_force(fin, m)
+            tx, ty = solid.force_terms(fin, m)
+            assert F["links"] == want["links"] == sum(int(l.sum()) for l in solid.links(m)), name
+            for k, t in (("fx", tx), ("fy", ty)):
+                bound = want["links"] * 2.0 ** -52 * math.fsum(np.abs(t).tolist())
+                print(f"{nx}x{ny} {name} {np.dtype(dtype).name} {k}: device {F[k]!r} host {want[k]!r} bound {bound!r}")
+                assert abs(F[k] - want[k]) <= bound, (name, k, F[k], want[k], bound)
+            if name == "fluid":
+                assert F["links"] == 0 and F["fx"] == 0.0 and F["fy"] == 0.0
+
+
+def test_mirror_image_under_a_reversed_lid():
+    """128^2, Re 100, MRT fp64: a 16 x 16 block at x = 32 .. 47 against its mirror image at x = 80 .. 95 under the reversed lid
+    (uLB < 0), 2000 steps.  The mirrored run performs the mirrored operations except where a sum runs over the slots in a fixed order
+    (macros, the MRT moments), so the two agree to rounding, not bit for bit.  Measured (MI355X): max |f - mirror(f')| / max |f| =
+    9.213e-16, against the bound of fast against strict fp64 bounce-back, 6e-14; fx = -0.017285637975456902 and +0.01728563797545738
+    (|fx1 + fx2| = 4.8e-16), fy = 0.013168442393758362 in both runs (difference 0).  The forces are held to what the measured mismatch
+    of the populations allows plus the rounding of the two reductions, a few 1e-14 here."""
+    n = 128
+    m1 = np.zeros((n, n), bool); m1[32:48, 56:72] = True
+    m2 = m1[::-1].copy()
+    assert m2[80:96, 56:72].all() and m2.sum() == 256
+    MIRROR = [0, 3, 2, 1, 4, 6, 5, 8, 7]      # directions under x -> X - 1 - x
+    with CavitySolver(n, n, 100.0, RT="MRT", dtype=np.float64, solid=m1, **BB) as a:
+        a.step(2000)
+        fa, Fa = a.get_fields(want_fin=True)[2], a.solid_force()
+    # (nu = uLB * ny / Re: the reversed lid with Re < 0 keeps the viscosity, hence the same rates)
+    with CavitySolver(n, n, -100.0, RT="MRT", dtype=np.float64, uLB=-0.08, solid=m2, **BB) as b:
+        assert b.relax == a.relax
+        b.step(2000)
+        fb, Fb = b.get_fields(want_fin=True)[2], b.solid_force()
+    fm = fb[MIRROR][:, ::-1]
+    err = float(np.abs(fa - fm).max() / np.abs(fa).max())
+    # a term is 2 c f: the two runs' terms differ by at most 2 err max|f| each (err: the populations' mismatch as just measured), and
+    # each device sum carries at most links * 2^-52 * sum |terms| of its own rounding
+    tx, ty = solid.force_terms(fa, m1)
+    links = solid.host_force(fa, m1)["links"]
+    B, fmax = FAST_BOUND[np.float64], float(np.abs(fa).max())
+    bx = links * 2.0 * err * fmax + 2.0 * links * 2.0 ** -52 * math.fsum(np.abs(tx).tolist())
+    by = links * 2.0 * err * fmax + 2.0 * links * 2.0 ** -52 * math.fsum(np.abs(ty).tolist())
+    print(f"mirror: populations {err:.3e}; fx {Fa['fx']!r} {Fb['fx']!r} (bound {bx:.3e}); fy {Fa['fy']!r} {Fb['fy']!r} (bound {by:.3e})")
+    assert Fa["links"] == Fb["links"] == links > 0
+    assert err < B, err
+    assert abs(Fa["fx"] + Fb["fx"]) <= bx and abs(Fa["fy"] - Fb["fy"]) <= by
+    assert abs(Fa["fx"]) > 1e-6, "the block feels a drag"
+
+
+def test_checkpoint_round_trip_with_a_mask(tmp_path):
+    nx, ny = 72, 40
+    m = _masks(nx, ny)["block"]
+    with CavitySolver(nx, ny, 400.0, RT="MRT", dtype=np.float32, solid=m, **BB) as s:
+        s.step(25)
+        path = s.save_checkpoint(str(tmp_path / "solid"))
+        s.step(30)
+        want = s.get_fields(want_fin=True)
+    with CavitySolver(nx, ny, 400.0, RT="MRT", dtype=np.float32, solid=m, **BB) as r:
+        assert r.load_checkpoint(path) == 25
+        r.step(30)
+        got = r.get_fields(want_fin=True)
+    assert all(np.array_equal(a, b) for a, b in zip(want, got))
+    with CavitySolver(nx, ny, 400.0, RT="MRT", dtype=np.float32, solid=_masks(nx, ny)["cell"], **BB) as other:
+        with pytest.raises(ValueError, match="solid"):
+            other.load_checkpoint(path)
+        assert other.load_checkpoint(path, strict=False) == 25
+        assert np.array_equal(other.solid, _masks(nx, ny)["cell"])
+    with CavitySolver(nx, ny, 400.0, RT="MRT", dtype=np.float32, **BB) as plain:
+        with pytest.raises(ValueError, match="solid"):
+            plain.load_checkpoint(path)
+
+
+def test_error_paths():
+    nx, ny = 72, 40
+    with CavitySolver(nx, ny, 100.0, **BB) as plain:
+        assert plain.solid is None and plain.describe()["semantics"] == "bounce_back"
+        with pytest.raises(RuntimeError, match="no solid mask"):
+            plain.set_solid(np.zeros((nx, ny), bool))
+        m = np.zeros((nx, ny), np.uint8)
+        assert plain.lib.lbm_set_solid(plain._h, m.ctypes.data) == -4 and b"no solid mask" in plain.lib.lbm_last_error(plain._h)
+        assert plain.lib.lbm_get_solid(plain._h, m.ctypes.data) == -4
+    with pytest.raises(RuntimeError, match="no fluid cell"):
+        CavitySolver(nx, ny, 100.0, solid=np.ones((nx, ny), bool), **BB)
+    with CavitySolver(nx, ny, 100.0, solid=np.zeros((nx, ny), bool), **BB) as s:
+        with pytest.raises(RuntimeError, match="no fluid cell"):
+            s.set_solid(np.ones((nx, ny), bool))
+        with pytest.raises(ValueError, match="shape"):
+            s.set_solid(np.zeros((ny, nx), bool))
+        s.step(3)                                   # (the refused masks left the context as it was)
+        assert not s.solid.any() and s.steps_done == 3
+    with pytest.raises(RuntimeError, match="no slabs"):
+        CavitySolver(nx, ny, 100.0, rows=(0, 20), solid=np.zeros((nx, ny), bool), **BB)
+    with pytest.raises(ValueError, match="bounce_back"):
+        CavitySolver(nx, ny, 100.0, solid=np.zeros((nx, ny), bool))
+    for kernel in ("tb", "stream", "vec", "push"):
+        with pytest.raises(RuntimeError, match="one step per launch"):
+            CavitySolver(128, 128, 100.0, kernel=kernel, solid=np.zeros((128, 128), bool), **BB)

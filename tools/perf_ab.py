@@ -4,7 +4,9 @@
     python tools/perf_ab.py [--steps 600] [--reps 3] case [case ...]
 
 A case is  size:dtype:arith[:key=value,...]  e.g.  4096:f32:fast   4096:f32:strict:tb_steps=4   8192x1024:f64:fast:coll=SRT,turb=1
-(keys: coll, turb, kernel, layout, sem (semantics: mrt_gpu, mrt_py, bounce_back) and every CavitySolver tuning switch).  Prints GLUPS (best of --reps timings of --steps steps
+(keys: coll, turb, kernel, layout, sem (semantics: mrt_gpu, mrt_py, bounce_back), solid (with sem=bounce_back: fluid -- the all-fluid mask --,
+block -- one block of an eighth of the width squared in the middle --, random -- 20 % of the cells, seeded), batch (that many lattices,
+GLUPS in aggregate) and every CavitySolver tuning switch).  Prints GLUPS (best of --reps timings of --steps steps
 after a device wake-up and a warm-up) and microseconds per step, one line per case.
 """
 import argparse
@@ -14,7 +16,19 @@ import sys
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from latticeboltzmannsimulations_amd import CavitySolver  # noqa: E402
+from latticeboltzmannsimulations_amd import CavityBatch, CavitySolver  # noqa: E402
+
+
+def solid_mask(kind, nx, ny):
+    m = np.zeros((nx, ny), dtype=bool)
+    if kind == "block":
+        w = max(1, nx // 8)
+        m[(nx - w) // 2:(nx + w) // 2, (ny - w) // 2:(ny + w) // 2] = True
+    elif kind == "random":
+        m = np.random.default_rng(1).random((nx, ny)) < 0.2
+    elif kind != "fluid":
+        raise ValueError("solid must be fluid, block or random")
+    return m
 
 
 def parse(case):
@@ -34,6 +48,10 @@ def parse(case):
                 kw["semantics"] = v
             elif k == "turb":
                 kw["turb"] = int(v)
+            elif k == "solid":
+                kw["solid"] = solid_mask(v, nx, ny)
+            elif k == "batch":
+                kw["batch"] = int(v)
             elif k in ("tb_steps", "frame_seg"):
                 tune[k] = int(v)
             else:
@@ -49,11 +67,13 @@ def main():
     a = ap.parse_args()
     for case in a.cases:
         nx, ny, dtype, arith, kw, tune = parse(case)
-        with CavitySolver(nx, ny, 1000.0, dtype=dtype, arith=arith, tuning=tune, **kw) as s:
+        B = kw.pop("batch", 1)
+        make = (lambda *a_, **k_: CavityBatch(a_[0], a_[1], [a_[2]] * B, **k_)) if B > 1 else CavitySolver
+        with make(nx, ny, 1000.0, dtype=dtype, arith=arith, tuning=tune, **kw) as s:
             s.copy_bandwidth(1 << 30, 60)
             s.step(max(60, a.steps // 10)); s.sync()
             ms = min(s.time_steps(a.steps) for _ in range(a.reps)) / a.steps
-            print(f"{case:48s} S={s.next_unit(1000)}  {nx * ny / ms / 1e6:8.1f} GLUPS  {ms * 1e3:9.2f} us/step", flush=True)
+            print(f"{case:48s} S={s.next_unit(1000)}  {B * nx * ny / ms / 1e6:8.1f} GLUPS  {ms * 1e3:9.2f} us/step", flush=True)
 
 
 if __name__ == "__main__":
