@@ -52,7 +52,8 @@ enum { LBM_SEM_BOUNCE_BACK_SOLID = 3 };                 /* LBM_SEM_BOUNCE_BACK p
                                                            a solid cell inside the lattice bounces like a source outside it, with nothing
                                                            added.  Whole lattices only (no slabs), one step per launch: kernel = AUTO
                                                            (k_step_solid, 16 B per access; k_step_generic where nx is no multiple of the
-                                                           vector width) or GENERIC. */
+                                                           vector width) or GENERIC.  LBM_FLAG_SOLID_TILES: 3 .. 5 steps per launch on the
+                                                           tile kernel instead. */
 enum { LBM_KERNEL_AUTO = 0,      /* fastest applicable: STREAM (large lattices), TB (lattices from 64 x 64 cells), else VEC, else GENERIC */
        LBM_KERNEL_GENERIC = 1,   /* one step per launch, one thread per cell (all semantics) */
        LBM_KERNEL_VEC = 2,       /* one step per launch, 16 B per access (MRT_GPU semantics) */
@@ -86,8 +87,13 @@ enum { LBM_FLAG_NO_DEEP_HALO = 1,        /* between slabs: a one-row exchange af
        LBM_FLAG_STREAM_WALLS = 65536,    /* kernel STREAM, MRT_GPU semantics, a lone lattice or a slab with the deep halo: the cells next to the walls */
        LBM_FLAG_NO_STREAM_WALLS = 262144,/* inside the streaming kernel (k_stream_walls / k_stream_walls_slab: no frame), always / never (default: for the
                                             operator variants whose kernel keeps its level loop free of scratch traffic -- MRT, SRT, no closure) */
-       LBM_FLAG_STREAM_PAIRS = 131072 }; /* ... the walls inside AND two rows per wave, twelve waves, at most 10 steps per launch (k_stream_pairs:
+       LBM_FLAG_STREAM_PAIRS = 131072,   /* ... the walls inside AND two rows per wave, twelve waves, at most 10 steps per launch (k_stream_pairs:
                                             an r03 experiment, no faster than k_stream_walls -- DESIGN 2.4; kept for A/B) */
+       LBM_FLAG_SOLID_TILES = 524288 };  /* LBM_SEM_BOUNCE_BACK_SOLID only (refused elsewhere), kernel = AUTO or TB: the lattice with its solid cells
+                                            steps 3 .. 5 steps per launch on the tile kernel, planned exactly as LBM_SEM_BOUNCE_BACK with kernel = TB
+                                            plans the same lattice (steps per launch, frame, segments, units); tails and the first step after an
+                                            upload stay on k_step_solid.  The same bits as one step per launch.  Needs nx % (16 / sizeof(real)) == 0
+                                            and a size kernel = TB accepts; tb_steps 3 .. 5.  Opt-in: without it nothing changes */
 
 /* The knobs of the reference script (MRT_GPU.py:38-93) as run-time parameters.  The
  * reference bakes them into the CUDA source by '%'-formatting (MRT_GPU.py:422,531,662) and

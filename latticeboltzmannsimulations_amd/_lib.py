@@ -28,7 +28,7 @@ LBM_FLAG_NO_DEEP_HALO, LBM_FLAG_FRAME_UNFUSED, LBM_FLAG_FRAME_FUSED_BATCH, LBM_F
 LBM_FLAG_NT_ON, LBM_FLAG_NT_OFF, LBM_FLAG_COMM_PRIORITY_OFF, LBM_FLAG_EAGER_LAG = 16, 32, 64, 128
 LBM_FLAG_FRAME_BESIDE_ON, LBM_FLAG_FRAME_BESIDE_OFF, LBM_FLAG_FRAME_NARROW, LBM_FLAG_NO_EDGE_FIRST = 512, 1024, 2048, 4096
 LBM_FLAG_NO_EDGE_RESERVE, LBM_FLAG_NO_XCD_BANDS, LBM_FLAG_NO_TAIL_TILES, LBM_FLAG_STREAM_WALLS = 8192, 16384, 32768, 65536
-LBM_FLAG_STREAM_PAIRS, LBM_FLAG_NO_STREAM_WALLS = 131072, 262144
+LBM_FLAG_STREAM_PAIRS, LBM_FLAG_NO_STREAM_WALLS, LBM_FLAG_SOLID_TILES = 131072, 262144, 524288
 ABI_VERSION = 4        # = LBM_ABI_VERSION of include/lbm.h (tests/test_abi.py keeps them equal)
 
 
@@ -93,7 +93,7 @@ def sources():
 def build(force=False, verbose=False):
     """Compile csrc/*.hip for gfx950 into liblbm_hip.so next to this file (in-tree).  The translation units (eight of host code +
     C ABI: lbm_hip / lbm_plan / lbm_launch / lbm_comm / lbm_sampling / lbm_monitor / lbm_residual / lbm_topology / lbm_solid; the explicit instantiations of the tile, streaming and
-    solid-mask kernels for float and for double) are compiled in parallel into csrc/_obj/ and linked."""
+    solid-mask kernels, and of the tile kernel with solid cells, for float and for double) are compiled in parallel into csrc/_obj/ and linked."""
     srcs = sources()
     if not force and os.path.exists(LIB_PATH) and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(s) for s in srcs):
         return LIB_PATH

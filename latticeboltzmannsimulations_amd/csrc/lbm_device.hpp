@@ -7,6 +7,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 namespace lbm {
 
 constexpr int Q = 9;
@@ -493,12 +495,21 @@ constexpr int LINK_SOLID = 256;
 // Gather the post-stream, post-wall-rule populations of cell (x, y) from a lattice that
 // holds post-collision values (+ kept slots + parked wall densities); raw != 0: the lattice
 // holds plain populations (state just set by the host), nothing to stream.  PROM: the wall rules' equilibrium in the promoted form.
+// The link word of cell (x, y) as a gather from `src` sees it.  A lattice carries plane K_LINK itself; an LDS window (the fused frame
+// passes) has no such plane -- no step writes it -- so there the word comes from `lnk`, plane K_LINK of the lattice the unit started from.
+template <typename R, typename AS>
+__device__ __forceinline__ int link_word(const R* __restrict__ src, const AS& as, const Geo& geo, const R* __restrict__ lnk, int x, int y) {
+    if constexpr (std::is_same<AS, Window>::value) return (int)lnk[geo.at(x, y)];
+    else return (int)src[K_LINK * as.plane + as.at(x, y)];
+}
+
 template <typename R, int SEM, typename AS, bool PROM = false>
-__device__ __forceinline__ void gather_a(const R* __restrict__ src, const AS& as, const Geo& geo, int raw, R uLB, int x, int y, R (&g)[Q]) {
+__device__ __forceinline__ void gather_a(const R* __restrict__ src, const AS& as, const Geo& geo, int raw, R uLB, int x, int y, R (&g)[Q],
+                                         const R* __restrict__ lnk = nullptr) {
     const int gy = geo.y0 + y;
     int lw = 0;
     if (SEM == SEM_SOLID) {
-        lw = (int)src[K_LINK * as.plane + as.at(x, y)];
+        lw = link_word<R, AS>(src, as, geo, lnk, x, y);
         if (lw & LINK_SOLID) {   // a solid cell: the constants it holds, whatever its neighbours stream
 #pragma unroll
             for (int k = 0; k < Q; ++k) g[k] = weight<R>(k);
@@ -553,11 +564,12 @@ __device__ __forceinline__ void gather(const R* __restrict__ src, const Geo& geo
 // as / ad: addressing of the source / destination (Geo = lattice in memory, Window = LDS window of the fused frame passes).
 template <typename R, int COLL, int SEM, bool TURB, typename AS, typename AD>
 __device__ __forceinline__ void update_cell_a(const R* __restrict__ src, const AS& as, R* __restrict__ dst, const AD& ad, const Geo& geo,
-                                              const Relax<R>& w0, int raw, int x, int y) {
+                                              const Relax<R>& w0, int raw, int x, int y, const R* __restrict__ lnk = nullptr) {
+    // lnk (SEM_SOLID with an LDS window as the source): plane K_LINK of the lattice, see link_word
     const int X = geo.nx, Y = geo.NY, gy = geo.y0 + y;
-    if (SEM == SEM_SOLID && ((int)src[K_LINK * as.plane + as.at(x, y)] & LINK_SOLID)) return;   // a solid cell is never updated
+    if (SEM == SEM_SOLID && (link_word<R, AS>(src, as, geo, lnk, x, y) & LINK_SOLID)) return;   // a solid cell is never updated
     R g[Q];
-    gather_a<R, SEM, AS, coll_is_prom(COLL)>(src, as, geo, raw, w0.uLB, x, y, g);
+    gather_a<R, SEM, AS, coll_is_prom(COLL)>(src, as, geo, raw, w0.uLB, x, y, g, lnk);
     // kept slots: a slot outside its streaming window keeps its value; park it where the
     // next pull of this cell will look for it.
     const bool near_edge = (x <= 0) || (x >= X - 2) || (gy <= 0) || (gy >= Y - 2);
@@ -850,11 +862,32 @@ __device__ __forceinline__ void update_tile2(const R* __restrict__ src, R* __res
 constexpr int TB_LDS_PLANES = 6;
 __host__ __device__ constexpr int lds_slot(int k) { return k == 2 ? 0 : k == 4 ? 1 : k - 3; }   // 5,6,7,8 -> 2,3,4,5
 
-template <typename R, int COLL, int V, int TX, int TY, int S, bool TURB, int RV = 1>
+// SOLID (SEM_SOLID, off in every other instantiation): the lattice has solid cells.  The rule is cell-local -- a slot whose source is a
+// solid cell takes the cell's OWN post-collision population of the opposite direction -- and the thread keeps its cells' post-collision
+// populations outv[] in registers for all S steps, so a solid link costs no LDS or memory traffic from step 2 on: a select between
+// in[k] and outv[opp(k)].  The thread reads the V link words of its cells once (rim cells included: they can be solid or next to a solid
+// cell and are recomputed like every cell of the shrinking region) and keeps them packed in two registers for the launch: the eight link
+// bits of each cell in `links`, the "solid" bit of each cell in `solid`.  Step 1: the pull from `src`, then one more aligned load of the
+// thread's own vector per direction that has a link in one of its cells.  Solid lanes compute garbage and are overwritten with w_k
+// after every collision: they hold the rest equilibrium in LDS, in the shuffles and in the stores, the constants k_solid_fix wrote.
+// The arithmetic stays collide_vec: the same bits as k_step_generic<.., SEM_SOLID> applied S times.
+template <typename R, int V>
+__device__ __forceinline__ void solid_lanes(typename VecT<R, V>::type (&outv)[Q], unsigned solid) {
+#pragma unroll
+    for (int c = 0; c < V; ++c)
+        if ((solid >> c) & 1u) {
+#pragma unroll
+            for (int k = 0; k < Q; ++k) outv[k][c] = weight<R>(k);
+        }
+}
+
+template <typename R, int COLL, int V, int TX, int TY, int S, bool TURB, int RV = 1, bool SOLID = false>
 __device__ __forceinline__ void update_tile_inplace(const R* __restrict__ src, R* __restrict__ dst, const Geo& geo,
                                                     const Relax<R>& w, R* __restrict__ lds, int tx0, int ty0, int xe, int ye) {
     // RV: vector cells of rim on each side in x (fp64 vectors hold two cells: more than three steps need two of them)
     typedef typename VecT<R, V>::type T;
+    static_assert(!(SOLID && TURB), "no closure with solid cells");
+    unsigned links = 0, solid = 0;   // SOLID: bits 8 c .. 8 c + 7 = the link bits of cell c; bit c = cell c is solid
     constexpr int PW = TX + 2 * RV * V, PH = TY + 2 * (S - 1), PVC = PW / V;
     static_assert(S - 1 <= RV * V, "the x rim is RV * V cells wide");
     static_assert(64 % PVC == 0, "a row of vector cells must not straddle two waves");
@@ -870,7 +903,30 @@ __device__ __forceinline__ void update_tile_inplace(const R* __restrict__ src, R
             hq = vload<R, V, false>(src + K_QEQ * geo.plane + geo.at(x0, y), true);
             hr = vload<R, V, false>(src + K_RHO * geo.plane + geo.at(x0, y), true);
         }
+        if constexpr (SOLID) {
+            const long long me = geo.at(x0, y);
+            const T lk = vload<R, V, false>(src + K_LINK * geo.plane + me, true);
+#pragma unroll
+            for (int c = 0; c < V; ++c) {
+                const unsigned lw = (unsigned)(int)lk[c];
+                links |= (lw & 255u) << (8 * c);
+                solid |= ((lw >> 8) & 1u) << c;
+            }
+            if (links) {
+#pragma unroll
+                for (int k = 1; k < Q; ++k) {
+                    if (!(links & (0x01010101u << (k - 1)))) continue;
+                    const T own = vload<R, V, false>(src + opp(k) * geo.plane + me, true);
+#pragma unroll
+                    for (int c = 0; c < V; ++c)
+                        if ((links >> (8 * c + k - 1)) & 1u) in[k][c] = own[c];
+                }
+            }
+        }
         collide_vec<R, COLL, V, TURB>(in, w, outv, hq, hr);
+        if constexpr (SOLID) {
+            if (solid) solid_lanes<R, V>(outv, solid);
+        }
     }
 #pragma unroll
     for (int s = 2; s <= S; ++s) {
@@ -911,7 +967,26 @@ __device__ __forceinline__ void update_tile_inplace(const R* __restrict__ src, R
         }
         if (s < S) __syncthreads();   // everyone has read before anyone overwrites in place
         // (the rim columns are needed by the next step but not after the last one)
-        if (act && (s < S || (vc >= RV && vc < PVC - RV))) collide_vec<R, COLL, V, TURB>(in, w, outv, hq, hr);
+        if (act && (s < S || (vc >= RV && vc < PVC - RV))) {
+            if constexpr (SOLID) {
+                // outv still holds this thread's post-collision populations of the step before.  Threads without a link skip the selects
+                // (most of a lattice with few obstacles), except in the strict fp64 TRT variant: with the branch its S = 4 and S = 5 kernels
+                // need 16 B of scratch under the 128 registers of the occupancy floor, without it 121 registers and none
+                constexpr bool SKIP = !(sizeof(R) == 8 && COLL == C_TRT);
+                if (!SKIP || links) {
+#pragma unroll
+                    for (int k = 1; k < Q; ++k) {
+#pragma unroll
+                        for (int c = 0; c < V; ++c)
+                            if ((links >> (8 * c + k - 1)) & 1u) in[k][c] = outv[opp(k)][c];
+                    }
+                }
+            }
+            collide_vec<R, COLL, V, TURB>(in, w, outv, hq, hr);
+            if constexpr (SOLID) {
+                if (solid) solid_lanes<R, V>(outv, solid);
+            }
+        }
     }
     if (r >= S - 1 && r < PH - (S - 1) && vc >= RV && vc < PVC - RV && x0 < xe && y < ye) {
         const long long me = geo.at(x0, y);

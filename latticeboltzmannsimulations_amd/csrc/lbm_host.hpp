@@ -72,6 +72,7 @@ struct Plan {
     int tb_steps = 2;           // steps per launch: two, three to five (tile kernel), up to eight (streaming kernel), ten (pairs)
     int tb_f = TB_F;            // frame width
     bool tail_tiles = false;    // streaming contexts (lone, fp32): units of 3 .. 5 steps through the tile kernel (A/B: LBM_FLAG_NO_TAIL_TILES)
+    bool solid_tiles = false;   // LBM_SEM_BOUNCE_BACK_SOLID with LBM_FLAG_SOLID_TILES: kern = tile, planned as LBM_SEM_BOUNCE_BACK with kernel = TB
     // ---- the frame
     bool frame_fused = true;    // all frame passes of a multi-step in one launch (LBM_FLAG_FRAME_UNFUSED: one launch per pass)
     bool frame_lds = true;      // ... keeping the intermediate passes in LDS when their windows fit (LBM_FLAG_NO_FRAME_LDS: scratch lattices)
@@ -289,8 +290,10 @@ int launch_variant(lbm_ctx* c, F&& f) {
 // segments of L cells that cover n cells of a frame strip (the fused frame passes run one workgroup per segment, frame_passes)
 inline int frame_segs(int n, int L) { return (n + L - 1) / L; }
 struct StreamPlan { int nstrips, nsegy, H; };
-// the semantics the multi-step kernels, the frame passes and the push scheme are compiled for (solid obstacles step one step per launch)
-constexpr bool sem_multi_step(int sem) { return sem != SEM_SOLID; }
+// Is a multi-step kernel compiled for the semantics?  The tile kernel and the frame passes: for all of them (solid obstacles run them
+// with LBM_FLAG_SOLID_TILES, one step per launch otherwise: Plan::solid_tiles); the streaming kernels and the frame beside them
+// (`streaming_kernel`): not with solid obstacles.
+constexpr bool sem_multi_step(int sem, bool streaming_kernel = false) { return sem != SEM_SOLID || !streaming_kernel; }
 
 // Waiting for the device: poll for a short while, then block.  A blocking hipStreamSynchronize / hipEventSynchronize wakes the host
 // tens of microseconds after the work is done -- 5 % of the driver's 20-step window of 1.1 ms (profiles/r02_logs/unit_times.log);
@@ -391,6 +394,7 @@ void monitor_free(lbm_ctx* c);
 void topology_free(lbm_ctx* c);
 // lbm_solid.hip
 int solid_fix(lbm_ctx* c);
+int solid_copy_links(lbm_ctx* c, int to);
 void solid_free(lbm_ctx* c);
 // lbm_residual.hip
 int residual_series_sample(lbm_ctx* c, int which, long long step);

@@ -52,6 +52,12 @@
 // the semantics), in units of their own.  The tiles and the streaming segments themselves never compute a perimeter cell.
 #define LBM_INST_TILES_BB(R) LBM_BB_VARIANTS(LBM_TILE_S, R)
 #define LBM_INST_STREAM_BB(R) LBM_BB_VARIANTS(LBM_STREAM_ONE, R)
+// ... and with solid cells inside the bounce-back cavity (LBM_FLAG_SOLID_TILES): the tile kernel over the same six operators, in units
+// of its own (update_tile_inplace's SOLID path; the frame workgroups run gather_a's solid rule)
+#define LBM_SOLID_VARIANTS(M, R)                                                                                                \
+    M(R, C_SRT, SEM_SOLID, false) M(R, C_TRT, SEM_SOLID, false) M(R, C_MRT, SEM_SOLID, false)                                   \
+    M(R, C_MRT_FAST, SEM_SOLID, false) M(R, C_SRT_FAST, SEM_SOLID, false) M(R, C_TRT_FAST, SEM_SOLID, false)
+#define LBM_INST_TILES_SOLID(R) LBM_SOLID_VARIANTS(LBM_TILE_S, R)
 
 #ifdef LBM_INST
 #define LBM_X
@@ -66,4 +72,5 @@ LBM_INST_STREAMP(float) LBM_INST_STREAMP(double)
 LBM_INST_TILES_PROM(float) LBM_INST_STREAM_PROM(float)
 LBM_INST_TILES_BB(float) LBM_INST_TILES_BB(double)
 LBM_INST_STREAM_BB(float) LBM_INST_STREAM_BB(double)
+LBM_INST_TILES_SOLID(float) LBM_INST_TILES_SOLID(double)
 #endif

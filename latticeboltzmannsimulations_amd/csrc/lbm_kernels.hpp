@@ -156,6 +156,9 @@ __device__ __forceinline__ void frame_passes(const FramePtrs<R>& fp, long long b
         win.x0 = xa1 - 1; win.y0 = ya1 - 1; win.pitch = xb1 - xa1 + 2; win.plane = win.pitch * (yb1 - ya1 + 2);
         R* const buf0 = lds;
         R* const buf1 = lds + NP * win.plane;
+        // SEM_SOLID: a window has no link plane (no pass writes one): the passes that read a window look the link words up in the
+        // lattice the unit started from (link_word)
+        const R* const lnk = SEM == SEM_SOLID ? fp.src + boff + K_LINK * geo.plane : nullptr;
         for (int t = threadIdx.x; t < 2 * NP * win.plane; t += NT) lds[t] = (R)0;
         __syncthreads();
         for (int i = 1; i <= S; ++i) {
@@ -171,11 +174,11 @@ __device__ __forceinline__ void frame_passes(const FramePtrs<R>& fp, long long b
                     update_cell_a<R, COLL, SEM, TURB, Geo, Window>(src, geo, wr, win, geo, w, 0, xa + t % wx, ya + t / wx);
             } else if (i < S) {
                 for (int t = threadIdx.x; t < n; t += NT)
-                    update_cell_a<R, COLL, SEM, TURB, Window, Window>(rd, win, wr, win, geo, w, 0, xa + t % wx, ya + t / wx);
+                    update_cell_a<R, COLL, SEM, TURB, Window, Window>(rd, win, wr, win, geo, w, 0, xa + t % wx, ya + t / wx, lnk);
             } else {
                 R* dst = pass_ptr(fp, S - 1) + boff;
                 for (int t = threadIdx.x; t < n; t += NT)
-                    update_cell_a<R, COLL, SEM, TURB, Window, Geo>(rd, win, dst, geo, geo, w, 0, xa + t % wx, ya + t / wx);
+                    update_cell_a<R, COLL, SEM, TURB, Window, Geo>(rd, win, dst, geo, geo, w, 0, xa + t % wx, ya + t / wx, lnk);
             }
             __syncthreads();
         }
@@ -240,7 +243,7 @@ __global__ __launch_bounds__(512, 4) void k_stepS_deep(const R* __restrict__ src
     }
     LBM_BATCH_SELECT(blockIdx.y)
     const int b = xcd_band(blockIdx.x - nframe, ntiles);
-    update_tile_inplace<R, COLL, V, TX, TY, S, TURB, RV>(src, dst, geo, w, lds_raw + V, F + (b % ntx) * TX, F + (b / ntx) * TY, xe, ye);
+    update_tile_inplace<R, COLL, V, TX, TY, S, TURB, RV, SEM == SEM_SOLID>(src, dst, geo, w, lds_raw + V, F + (b % ntx) * TX, F + (b / ntx) * TY, xe, ye);
 }
 
 // One single step on the frame of width W around the slab: rows [0, W) and [ny-W, ny) in full, columns [0, W) and

@@ -20,6 +20,8 @@ int ensure_scratch(lbm_ctx* c, int n) {
             return fail(c, LBM_ERR_NOMEM, std::string("hipMalloc(scratch lattice of the frame passes): ") + hipGetErrorString(e));
         }
         HIP_TRY(c, hipMemsetAsync(c->lat[i], 0, c->plan.lat_bytes, c->s_compute));
+        const int rc = solid_copy_links(c, i);   // (solid obstacles: every lattice a step or an export reads carries the link plane)
+        if (rc) return rc;
         fresh = true;
     }
     if (fresh) HIP_TRY(c, hipStreamSynchronize(c->s_compute));
@@ -107,11 +109,11 @@ int launch_frame_multi(lbm_ctx* c, int from, int to, int S, hipStream_t s, bool 
         using VT = decltype(v);
         using R = typename VT::R;
         const FramePtrs<R> fp = frame_ptrs<R>(c, from, to, S);
-        if constexpr (!sem_multi_step(VT::SEM)) return;
-        else if (beside)
-            hipLaunchKernelGGL((k_frame_beside<R, VT::COLL, VT::SEM, VT::TURB>), dim3(fl.nframe), dim3(BLK), 0, s, fp, c->plan.geo, relax_of<R>(c->p), fl.F, S,
-                               fl.nsegx, fl.nsegy, fl.L);
-        else if (!fl.in_lds && c->plan.frame_wide)
+        if (beside) {   // (Kern::stream only: never with solid obstacles)
+            if constexpr (sem_multi_step(VT::SEM, true))
+                hipLaunchKernelGGL((k_frame_beside<R, VT::COLL, VT::SEM, VT::TURB>), dim3(fl.nframe), dim3(BLK), 0, s, fp, c->plan.geo, relax_of<R>(c->p), fl.F, S,
+                                   fl.nsegx, fl.nsegy, fl.L);
+        } else if (!fl.in_lds && c->plan.frame_wide)
             hipLaunchKernelGGL((k_frame_multi<R, VT::COLL, VT::SEM, VT::TURB, 1024>), dim3(fl.nframe, c->plan.batch), dim3(1024), 0, s, fp, c->plan.geo,
                                relax_of<R>(c->p), batch_of<R>(c), fl.F, S, fl.nsegx, fl.nsegy, lo ? 1 + extra : 0, hi ? 1 + extra : 0, fl.L, 0);
         else
@@ -128,7 +130,7 @@ static int launch_k_stream(lbm_ctx* c, int from, int to, hipStream_t s, int S, c
     return launch_variant(c, [&](auto v) {
         using VT = decltype(v);
         using R = typename VT::R;
-        if constexpr (sem_multi_step(VT::SEM))
+        if constexpr (sem_multi_step(VT::SEM, true))
         hipLaunchKernelGGL((k_stream<R, VT::COLL, VT::SEM, VT::TURB>), dim3(fl.nframe + pl.nstrips * nseg), dim3(ST_NT), 0, s, (const R*)c->lat[from],
                            (R*)c->lat[to], c->plan.geo, relax_of<R>(c->p), S, fl.F, c->plan.geo.nx - fl.F, ye, pl.nstrips, pl.H, frame_ptrs<R>(c, from, to, S),
                            fl.nframe, fl.nsegx, fl.nsegy, fl.L, fl.in_lds ? 1 : 0, lo, hi, bands, xcd_bands ? 1 : 0);
@@ -219,6 +221,7 @@ int launch_deep(lbm_ctx* c, int from, int to, hipStream_t s, int steps, bool wit
         default: break;
     }
     const int F = c->plan.tb_f, xe = c->plan.geo.nx - F, ye = c->plan.geo.ny - F;
+    if (steps < 3 && c->plan.solid_tiles) return fail(c, LBM_ERR_STATE, "internal: solid obstacles have no two-step tile kernel");
     if (steps < 3)
         return launch_variant(c, [&](auto v) {
             using VT = decltype(v);
@@ -338,6 +341,8 @@ int prev_lattice(lbm_ctx* c, int* which) {
         hipError_t e = hipMalloc(&c->lat[LAT_LAG], c->plan.lat_bytes);
         if (e != hipSuccess) return fail(c, LBM_ERR_NOMEM, std::string("hipMalloc(lag lattice): ") + hipGetErrorString(e));
         HIP_TRY(c, hipMemsetAsync(c->lat[LAT_LAG], 0, c->plan.lat_bytes, c->s_compute));
+        const int rc = solid_copy_links(c, LAT_LAG);
+        if (rc) return rc;
     }
     const int k = c->lag, from = c->cur ^ 1;
     const Route route = unit_route(c->plan, k, true);

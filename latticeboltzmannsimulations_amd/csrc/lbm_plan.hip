@@ -9,7 +9,8 @@ namespace lbmhost {
 // Do the LDS windows of the fused frame passes fit (two buffers of the largest pass-1 rectangle plus its ring)?
 bool frame_lds_fits(const Plan& pl, int S, bool deep_rows, int extra, long long budget) {
     if (!pl.frame_lds) return false;
-    const int F = pl.tb_f, L = pl.frame_seg, m = S - 1, np = pl.nplanes;
+    // (the windows hold the populations and the closure's history; the link plane of solid obstacles is read from the lattice: link_word)
+    const int F = pl.tb_f, L = pl.frame_seg, m = S - 1, np = pl.semantics == LBM_SEM_BOUNCE_BACK_SOLID ? Q : pl.nplanes;
     const long long row_strip = (long long)(L + 2 * m + 2) * (F + m + (deep_rows ? m + extra : 0) + 2);
     const long long col_strip = (long long)(F + m + 2) * (L + 2 * m + extra + 2);
     return 2 * np * std::max(row_strip, col_strip) * pl.es <= budget;
@@ -158,14 +159,23 @@ std::string validate_params(const lbm_params* p) {
                            "MRT.py semantics is NumPy fp64)");
     if (p->arith == LBM_ARITH_PROMOTED && (p->flags & LBM_FLAG_STREAM_PAIRS))
         return std::string("arith = promoted does not run on the streaming kernel with two rows per wave (LBM_FLAG_STREAM_PAIRS)");
+    if ((p->flags & LBM_FLAG_SOLID_TILES) && p->semantics != LBM_SEM_BOUNCE_BACK_SOLID)
+        return std::string("LBM_FLAG_SOLID_TILES (solid obstacles on the multi-step tile kernel) needs a solid mask: semantics = LBM_SEM_BOUNCE_BACK_SOLID");
     if (p->semantics == LBM_SEM_BOUNCE_BACK_SOLID) {
-        // solid obstacles: the tile and streaming kernels never compute a cell whose neighbours are not plain fluid, the vector and push
-        // kernels have the wet-node walls built in; the mask is one whole lattice's (of each lattice of a batch)
+        // solid obstacles: the streaming kernels never compute a cell whose neighbours are not plain fluid, nor do the tile kernels
+        // without their solid path (LBM_FLAG_SOLID_TILES: update_tile_inplace); the vector and push kernels have the wet-node walls
+        // built in; the mask is one whole lattice's (of each lattice of a batch)
         if (p->y0 != 0 || p->ny_local != p->ny)
             return std::string("solid obstacles (LBM_SEM_BOUNCE_BACK_SOLID) take whole lattices: no slabs (y0 = 0, ny_local = ny)");
-        if (p->kernel != LBM_KERNEL_AUTO && p->kernel != LBM_KERNEL_GENERIC)
+        if (p->flags & LBM_FLAG_SOLID_TILES) {
+            if (p->kernel != LBM_KERNEL_AUTO && p->kernel != LBM_KERNEL_TB)
+                return std::string("LBM_FLAG_SOLID_TILES runs the tile kernel, kernel = AUTO or TB: STREAM / VEC / PUSH have no solid path, GENERIC is "
+                                   "one step per launch (leave the flag out)");
+            if (p->tb_steps == 2)
+                return std::string("LBM_FLAG_SOLID_TILES: tb_steps must be 0 (default) or 3 .. 5 (the two-step tile kernel has no solid path)");
+        } else if (p->kernel != LBM_KERNEL_AUTO && p->kernel != LBM_KERNEL_GENERIC)
             return std::string("solid obstacles (LBM_SEM_BOUNCE_BACK_SOLID) step one step per launch, kernel = AUTO or GENERIC: TB / STREAM / VEC / PUSH "
-                               "never compute a cell next to a solid one");
+                               "never compute a cell next to a solid one (the tile kernel does with LBM_FLAG_SOLID_TILES)");
     }
     if (p->semantics == LBM_SEM_BOUNCE_BACK || p->semantics == LBM_SEM_BOUNCE_BACK_SOLID) {
         // half-way bounce-back lives in the gather of the single-step operators and of the frame passes (lbm_device.hpp); the kernels
@@ -219,6 +229,7 @@ static Forced decode_flags(const lbm_params& p, Plan& pl) {
     f.stream_pairs = on(LBM_FLAG_STREAM_PAIRS);
     f.no_stream_walls = on(LBM_FLAG_NO_STREAM_WALLS);
     f.no_tail_tiles = on(LBM_FLAG_NO_TAIL_TILES);
+    pl.solid_tiles = on(LBM_FLAG_SOLID_TILES);   // (with LBM_SEM_BOUNCE_BACK_SOLID only: validate_params)
     return f;
 }
 
@@ -255,6 +266,12 @@ static std::string plan_kernel(Plan& pl, const lbm_params& p, const Forced& f, b
     if (p.semantics == LBM_SEM_BOUNCE_BACK_SOLID) {   // one step per launch: k_step_solid (use_vec), or k_step_generic
         pl.use_vec = p.nx % V == 0 && p.kernel != LBM_KERNEL_GENERIC;
         pl.kern = Kern::none;
+        if (!pl.solid_tiles) return std::string();
+        // LBM_FLAG_SOLID_TILES: the tile kernel, wherever LBM_SEM_BOUNCE_BACK with kernel = TB has it (can_tb below; plan_steps and
+        // plan_frame then take the same decisions for both); the single steps of such a context run k_step_solid
+        if (p.nx % V != 0 || p.nx < 32 || nyp < 32)
+            return "LBM_FLAG_SOLID_TILES needs what kernel = TB needs: nx % (16 / sizeof(real)) == 0, nx >= 32 and ny >= 32";
+        pl.kern = Kern::tile;
         return std::string();
     }
     const bool can_vec = p.semantics == LBM_SEM_MRT_GPU && p.nx % V == 0;
@@ -412,7 +429,7 @@ static void plan_frame(Plan& pl, const lbm_params& p, const Forced& f, bool devi
             using VT = decltype(v);
             using R = typename VT::R;
             hipFuncAttributes at;
-            if constexpr (sem_multi_step(VT::SEM)) {
+            if constexpr (sem_multi_step(VT::SEM, true)) {
                 if (hipFuncGetAttributes(&at, reinterpret_cast<const void*>(&k_stream<R, VT::COLL, VT::SEM, VT::TURB>)) == hipSuccess) rs = at.numRegs;
                 if (hipFuncGetAttributes(&at, reinterpret_cast<const void*>(&k_frame_beside<R, VT::COLL, VT::SEM, VT::TURB>)) == hipSuccess) rf = at.numRegs;
             }
@@ -485,11 +502,12 @@ static int describe_plan(const Plan& pl, int lattices_held, char* buf, size_t le
         for (int s = 1; s <= S; ++s) per += (32 - 2 * (s - 1)) / 4 + ((32 - 2 * (s - 1)) % 4 ? 1 : 0);
         wave_updates = wgs * per;
     }
-    const bool solid = pl.semantics == LBM_SEM_BOUNCE_BACK_SOLID;   // (names its one-step kernel: it has no multi-step units)
+    const bool solid = pl.semantics == LBM_SEM_BOUNCE_BACK_SOLID;
+    const bool solid_single = solid && pl.kern == Kern::none;       // (names its one-step kernel: it has no multi-step units)
     const int n = std::snprintf(buf, len, "kernel=%s steps_per_launch=%d frame=%d stream=%d vec=%d nt=%d deep_halo=%d frame_fused=%d lazy_lag=%d "
                                 "layout=%s workgroups=%lld wave_updates=%lld cells_per_lane=%d slab=%d frame_beside=%d frame_seg=%d "
                                 "lattices=%d lattice_bytes=%lld%s",
-                                solid ? (pl.use_vec ? "k_step_solid" : "k_step_generic") : names[(int)pl.kern], S, pl.kern != Kern::none ? (walls_inside(pl) && !is_slab(pl) ? 0 : pl.tb_f) : 0, streaming(pl) ? 1 : 0,
+                                solid_single ? (pl.use_vec ? "k_step_solid" : "k_step_generic") : names[(int)pl.kern], S, pl.kern != Kern::none ? (walls_inside(pl) && !is_slab(pl) ? 0 : pl.tb_f) : 0, streaming(pl) ? 1 : 0,
                                 pl.use_vec ? 1 : 0, pl.use_nt ? 1 : 0, pl.deep_halo ? 1 : 0, pl.frame_fused ? 1 : 0, pl.lazy_lag ? 1 : 0,
                                 pl.geo.row != pl.geo.pitch ? "rows" : "planes", wgs, wave_updates, V, is_slab(pl) ? 1 : 0, pl.frame_beside ? 1 : 0,
                                 pl.frame_seg, lattices_held, (long long)pl.lat_bytes,

@@ -88,6 +88,23 @@ int solid_fix(lbm_ctx* c) {
     });
 }
 
+// Plane K_LINK of lat[0] -> lat[to], all lattices of a batch, on s_compute.  The two lattices get their link planes from lbm_set_solid;
+// the lattices that come later -- the scratch lattices of the frame passes, the lattice of the step before the last (multi-step units:
+// LBM_FLAG_SOLID_TILES) -- are read by the same gathers, which take the link word from their source, and get a copy when they are
+// allocated and at every lbm_set_solid.  Ghost rows and pad columns included (zero in lat[0]).
+int solid_copy_links(lbm_ctx* c, int to) {
+    if (c->p.semantics != LBM_SEM_BOUNCE_BACK_SOLID || to == 0 || !c->lat[to]) return LBM_OK;
+    const Geo& g = c->plan.geo;
+    const size_t es = (size_t)c->plan.es, rows = (size_t)g.ny + 2 * GHY;
+    const bool by_rows = g.row != g.pitch;   // [y][k][x]: one row of the plane per lattice row; [k][y][x]: the plane is contiguous
+    const size_t width = (by_rows ? (size_t)g.pitch : (size_t)g.pitch * rows) * es;
+    const size_t pitch = (by_rows ? (size_t)g.row : (size_t)c->plan.bstride) * es;
+    const size_t height = by_rows ? rows * c->plan.batch : (size_t)c->plan.batch;
+    const size_t off = (size_t)K_LINK * g.plane * es;
+    HIP_TRY(c, hipMemcpy2DAsync((char*)c->lat[to] + off, pitch, (const char*)c->lat[0] + off, pitch, width, height, hipMemcpyDeviceToDevice, c->s_compute));
+    return LBM_OK;
+}
+
 void solid_free(lbm_ctx* c) {
     if (c->force_dev) (void)hipFree(c->force_dev);
     c->force_dev = nullptr;
@@ -148,6 +165,8 @@ int lbm_set_solid(lbm_ctx* c, const uint8_t* mask) {
     std::vector<uint8_t> next(n * c->plan.batch);
     for (size_t i = 0; i < next.size(); ++i) next[i] = mask[i] ? 1 : 0;
     rc = c->plan.es == 4 ? upload_links<float>(c, next.data()) : upload_links<double>(c, next.data());
+    for (int i = 2; i < NLAT && rc == LBM_OK; ++i) rc = solid_copy_links(c, i);   // (the lattices allocated since: scratch, the lagged one)
+    if (rc == LBM_OK) rc = sync_all(c);
     if (rc) return rc;
     c->solid_mask.swap(next);
     return lbm_init_equilibrium(c);   // (ends every sampler; solid cells get w_k: solid_fix)

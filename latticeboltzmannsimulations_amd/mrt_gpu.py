@@ -151,7 +151,7 @@ def _vortex_lines(table, Re, xsize, ysize, uLB):
 
 
 def _check_arguments(criterion, residual_tol, residual_hits, monitor, MonitorEvery, convergence, AverageFrom, AverageEvery, BC, semantics, turb,
-                     solid=None):
+                     solid=None, solid_tiles=False):
     """(criterion is 'residual', semantics); ValueError for an argument run_cavity cannot run with."""
     residual = by_residual(criterion, residual_tol, residual_hits)
     if monitor not in ("host", "device"):
@@ -162,7 +162,7 @@ def _check_arguments(criterion, residual_tol, residual_hits, monitor, MonitorEve
         raise ValueError("convergence must be 'host' or 'device'")
     if AverageFrom is not None and (int(AverageFrom) < 0 or int(AverageEvery) < 1):
         raise ValueError("AverageFrom must be >= 0 and AverageEvery >= 1")
-    return residual, wall_model(BC, semantics, turb, solid is not None)
+    return residual, wall_model(BC, semantics, turb, solid is not None, solid_tiles)
 
 
 def _banner(say, Re, RT, turb, relax):
@@ -304,7 +304,8 @@ def run_cavity(maxIt=3000000, Re=10000.0, RT="SRT", turb=1, xsize=32 * 5, ysize=
                Pinterval=3000, SavePlot=True, SaveVTK=False, project="ldc", OutputFolder="./output",
                dtype=np.float32, semantics="mrt_gpu", device=0, quiet=False, solver_factory=None, arith="strict",
                convergence="host", vtk_correct=False, BC="EB-NEBB ", AverageFrom=None, AverageEvery=100, monitor="host",
-               MonitorEvery=None, Probes=(), vortex_table=False, criterion="mean_u", residual_tol=None, residual_hits=1, solid=None):
+               MonitorEvery=None, Probes=(), vortex_table=False, criterion="mean_u", residual_tol=None, residual_hits=1, solid=None,
+               solid_tiles=False):
     """Run the lid-driven cavity like MRT_GPU.py does; returns a :class:`CavityResult`.
 
     Argument names and defaults are the module constants of MRT_GPU.py:38-58.
@@ -342,9 +343,11 @@ def run_cavity(maxIt=3000000, Re=10000.0, RT="SRT", turb=1, xsize=32 * 5, ysize=
     solid: a mask [xsize, ysize] whose nonzero cells are solid obstacles at rest (CavitySolver(solid=...); BC='BB' only).  Every
     Pinterval is then an output iteration, each one prints `current force on the obstacles is (fx, fy) over N links` -- the momentum-
     exchange force reduced on the device, CavitySolver.solid_force() -- and appends (iteration, that record) to result.forces.  None
-    (default): nothing changes."""
+    (default): nothing changes.
+    solid_tiles=True (with solid=...): the lattice steps three to five steps per launch on the tile kernel
+    (CavitySolver(tuning=dict(solid_tiles=True))) instead of one; the same bits."""
     by_res, semantics = _check_arguments(criterion, residual_tol, residual_hits, monitor, MonitorEvery, convergence, AverageFrom,
-                                         AverageEvery, BC, semantics, turb, solid)
+                                         AverageEvery, BC, semantics, turb, solid, solid_tiles)
     on_device = monitor == "device"
     say = (lambda *a: None) if quiet else print
     tstart = timer()
@@ -354,6 +357,8 @@ def run_cavity(maxIt=3000000, Re=10000.0, RT="SRT", turb=1, xsize=32 * 5, ysize=
     extra = {} if arith == "strict" else {"arith": arith}      # 'fast' / 'promoted': see CavitySolver
     if solid is not None:
         extra["solid"] = solid
+    if solid_tiles:
+        extra["tuning"] = dict(solid_tiles=True)
     solver = make(xsize, ysize, Re, RT=RT, uLB=uLB, semantics=semantics, dtype=dtype, turb=turb, device=device, **extra)
     _banner(say, Re, RT, turb, solver.relax)
     if (SavePlot or SaveVTK) and not os.path.isdir(OutputFolder):
@@ -469,13 +474,15 @@ def main(argv=None):
     ap.add_argument("--solid-box", type=int, nargs=4, action="append", default=[], metavar=("X0", "X1", "Y0", "Y1"),
                     help="a solid obstacle: the cells [X0, X1) x [Y0, Y1), y = 0 the lid (repeatable; needs --BC BB --turb 0)")
     ap.add_argument("--solid-file", default=None, help="a .npy mask [xsize, ysize] whose nonzero cells are solid (needs --BC BB --turb 0)")
+    ap.add_argument("--solid-tiles", action="store_true",
+                    help="with --solid-box / --solid-file: three to five steps per launch on the tile kernel instead of one (the same bits)")
     a = ap.parse_args(argv)
     mask = None
-    if a.solid_box or a.solid_file is not None:      # an obstacle the run cannot have is an argument error, through the one check
+    if a.solid_box or a.solid_file is not None or a.solid_tiles:      # an obstacle the run cannot have is an argument error, through the one check
         try:
             mask = mask_from(a.xsize, a.ysize, a.solid_box, a.solid_file)
             _check_arguments(a.criterion, a.residual_tol, a.residual_hits, a.monitor, a.monitor_every, a.convergence, a.average_from,
-                             a.average_every, a.BC, a.semantics, a.turb, mask)
+                             a.average_every, a.BC, a.semantics, a.turb, mask, a.solid_tiles)
         except (ValueError, OSError) as e:
             ap.error(str(e))
     r = run_cavity(maxIt=a.maxIt, Re=a.Re, RT=a.RT, turb=a.turb, xsize=a.xsize, ysize=a.ysize, uLB=a.uLB,
@@ -484,7 +491,7 @@ def main(argv=None):
                    convergence=a.convergence, vtk_correct=a.vtk_correct, BC="BB" if a.BC == "BB" else "EB-NEBB ",
                    AverageFrom=a.average_from, AverageEvery=a.average_every, monitor=a.monitor, MonitorEvery=a.monitor_every,
                    Probes=tuple(tuple(p) for p in a.probe), vortex_table=a.vortex_table, criterion=a.criterion,
-                   residual_tol=a.residual_tol, residual_hits=a.residual_hits, solid=mask)
+                   residual_tol=a.residual_tol, residual_hits=a.residual_hits, solid=mask, **(dict(solid_tiles=True) if a.solid_tiles else {}))
     print("MLUPS : ", r.mlups)
     return 0
 

@@ -40,7 +40,8 @@ def _tuning(t):
            "comm_priority": L.LBM_FLAG_COMM_PRIORITY_OFF, "frame_wide": L.LBM_FLAG_FRAME_NARROW, "edge_first": L.LBM_FLAG_NO_EDGE_FIRST,
            "edge_reserve": L.LBM_FLAG_NO_EDGE_RESERVE, "xcd_bands": L.LBM_FLAG_NO_XCD_BANDS,
            "tail_tiles": L.LBM_FLAG_NO_TAIL_TILES}
-    on = {"frame_fused_batch": L.LBM_FLAG_FRAME_FUSED_BATCH, "eager_lag": L.LBM_FLAG_EAGER_LAG, "stream_pairs": L.LBM_FLAG_STREAM_PAIRS}
+    on = {"frame_fused_batch": L.LBM_FLAG_FRAME_FUSED_BATCH, "eager_lag": L.LBM_FLAG_EAGER_LAG, "stream_pairs": L.LBM_FLAG_STREAM_PAIRS,
+          "solid_tiles": L.LBM_FLAG_SOLID_TILES}
     if "stream_walls" in t:     # (three states: True / False force it, absent = the library's choice per operator variant)
         flags |= L.LBM_FLAG_STREAM_WALLS if t.pop("stream_walls") else L.LBM_FLAG_NO_STREAM_WALLS
     for k, bit in off.items():
@@ -87,10 +88,12 @@ class CavitySolver:
     solid        : None (default), or a mask [X, Y] (a CavityBatch: [B, X, Y], or [X, Y] for all lattices) whose nonzero cells are solid
                    obstacles at rest inside the cavity (semantics='bounce_back' only; the context is then LBM_SEM_BOUNCE_BACK_SOLID): a
                    source that is a solid cell bounces like a wall, solid cells hold the rest equilibrium (u = 0 in every export), one
-                   step per launch (kernel 'auto' or 'generic'), no slabs.  See set_solid, solid, solid_force.
+                   step per launch (kernel 'auto' or 'generic'), no slabs.  See set_solid, solid, solid_force.  tuning=dict(solid_tiles=True):
+                   three to five steps per launch on the tile kernel instead (kernel 'auto' or 'tb'; planned as plain 'bounce_back' with
+                   kernel='tb' plans the same lattice; the same bits).
     tuning       : A/B switches of the launch plan, none of which changes a result: tb_steps (2..5 steps per launch; 2..8 with kernel='stream'),
                    frame_seg, and the boolean flags deep_halo, frame_fused, frame_fused_batch, frame_lds, nt, comm_priority,
-                   eager_lag, frame_beside, frame_wide, edge_first, edge_reserve, xcd_bands, tail_tiles (lbm_params.tb_steps / frame_seg / flags)
+                   eager_lag, frame_beside, frame_wide, edge_first, edge_reserve, xcd_bands, tail_tiles, solid_tiles (lbm_params.tb_steps / frame_seg / flags)
     """
 
     def __init__(self, xsize, ysize, Re, RT="MRT", uLB=0.08, semantics="mrt_gpu", dtype=np.float32, turb=0,

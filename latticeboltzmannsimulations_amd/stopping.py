@@ -33,12 +33,15 @@ class ResidualStop:
         return value, self.count >= self.hits
 
 
-def wall_model(BC, semantics, turb, solid=False):
+def wall_model(BC, semantics, turb, solid=False, solid_tiles=False):
     """The semantics the wall model BC selects: 'EB-NEBB ' keeps `semantics`, 'BB' is 'bounce_back' (without the closure).  solid: the
-    run has solid obstacles, which exist with the bounce-back walls only."""
+    run has solid obstacles, which exist with the bounce-back walls only.  solid_tiles: it asks for the multi-step tile kernel of a
+    lattice with obstacles (tuning=dict(solid_tiles=True)), which needs some."""
     bc = BC.strip()
     if bc not in ("EB-NEBB", "BB"):
         raise ValueError("BC must be 'EB-NEBB ' or 'BB'")
+    if solid_tiles and not solid:
+        raise ValueError("solid_tiles selects the multi-step tile kernel for a lattice with solid obstacles: it needs solid=... (a mask)")
     if solid and bc != "BB":
         raise ValueError("solid obstacles need the bounce-back walls: pass BC='BB' (and turb=0)")
     if bc == "BB":

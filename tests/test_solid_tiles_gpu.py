@@ -1,0 +1,356 @@
+"""GPU tests of solid obstacles on the multi-step tile kernel (CavitySolver(..., solid=mask, tuning=dict(solid_tiles=True)),
+LBM_FLAG_SOLID_TILES): strict arithmetic bit for bit against the NumPy reference tests/solid_ref.py AND against the same
+solver one step per launch, for every operator, both types and three, four and five steps per launch, with masks placed on the tile
+seams, the frame / tile boundary, the vector-lane boundaries, the corners and the lid row; the frame's scratch-lattice and unfused
+routes; `fast` arithmetic; the all-fluid mask against plain bounce-back tiles; batches; the force, the samplers, checkpoints; describe
+and the error paths.
+
+Shapes: the smallest that give two full tiles and a clipped third per axis.  A tile is 16 vector cells x 32 rows minus its rim: with
+V = 4 (fp32) or 2 (fp64) cells per vector, RV = ceil((S - 1) / V) rim vectors per side and S - 1 rim rows, TX = (16 - 2 RV) V and TY = 32 -
+2 (S - 1); the frame is F = 4 cells wide for S = 3 and 8 for S = 4, 5.  fp32, S = 3: 128 x 72 (120 = 2 x 56 + 8 columns, 64 = 2 x 28 + 8
+rows).  fp32, S = 4 / 5 (F = 8): 136 x 80 (120 = 2 x 56 + 8; 64 = 2 x 26 + 12 = 2 x 24 + 16) -- 128 x 72 has exactly two tiles per row
+there.  fp64: 72 x 72 for every S (S = 3: 64 = 2 x 28 + 8 both ways; S = 4 / 5: 56 = 2 x 24 + 8 columns, 2 x 26 + 4 / 2 x 24 + 8 rows)."""
+import math
+import os
+import sys
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+from solid_ref import SolidOracle  # noqa: E402
+from test_bounce_back_gpu import FAST_BOUND  # noqa: E402
+from test_solid_gpu import _masks  # noqa: E402
+from latticeboltzmannsimulations_amd import CavityBatch, CavitySolver, solid  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+BB = dict(semantics="bounce_back")
+TILES = dict(solid_tiles=True)
+
+
+def _tile(dtype, S):
+    """(F, TX, TY) of the tile kernel for S steps per launch (k_stepS_deep)."""
+    V = 4 if np.dtype(dtype) == np.float32 else 2
+    RV = (S - 1 + V - 1) // V
+    return (4 if S == 3 else 8), (16 - 2 * RV) * V, 32 - 2 * (S - 1)
+
+
+def _shape(dtype, S):
+    if np.dtype(dtype) == np.float64:
+        return 72, 72
+    return (128, 72) if S == 3 else (136, 80)
+
+
+def _seam_masks(nx, ny, dtype, steps):
+    """name -> mask: obstacles on the lines where the tile route changes hands, for every S of `steps` (which share F).
+    seams: 2 x 2 blocks and single cells on the tile seams x = F + i TX - 1 | F + i TX (y likewise), where they cross and alone;
+    rim: single cells and blocks on the frame / tile boundary x, y = F - 1 | F and n - F - 1 | n - F, in the frame's corners, in the
+         lattice's corners and in the lid row;
+    column: two full-height columns, x = F + TX - 1 (= 3 mod 4: the last cell of a vector, the last column of a tile) and x = F + 2 TX
+         (= 0 mod 4: the first); the cavity becomes three chambers;
+    row: two full-width rows, y = F + TY - 1 (the last row of a tile) and y = ny - F (the first row of the bottom frame strip)."""
+    z = lambda: np.zeros((nx, ny), dtype=bool)  # noqa: E731
+    tiles = [_tile(dtype, S) for S in steps]
+    F = tiles[0][0]
+    assert all(t[0] == F for t in tiles)
+    xs = sorted({F + i * TX for _, TX, _ in tiles for i in (1, 2) if F + i * TX < nx - F})
+    ys = sorted({F + j * TY for _, _, TY in tiles for j in (1, 2) if F + j * TY < ny - F})
+    assert len(xs) >= 2 and len(ys) >= 2, "two full tiles and a clipped third per axis"
+    out = {}
+    m = z()
+    m[xs[0] - 1:xs[0] + 1, ys[0] - 1:ys[0] + 1] = True          # a block on the crossing of two seams
+    for y in ys[1:]:
+        m[xs[-1] - 1:xs[-1] + 1, y - 1:y + 1] = True
+    m[xs[0] - 1, F + 3] = m[xs[0], F + 6] = True                 # single cells left and right of a seam ...
+    m[F + 9, ys[0] - 1] = m[F + 13, ys[0]] = True                # ... and above and below one
+    m[xs[-1] - 1, ny - F - 3] = m[xs[-1], ny - F - 5] = True
+    out["seams"] = m
+    m = z()
+    for a, b in ((F - 1, 12), (F, 15), (nx - F - 1, 18), (nx - F, 21)):
+        m[a, b] = True                                           # x on the frame / tile boundary
+    for a, b in ((14, F - 1), (17, F), (22, ny - F - 1), (27, ny - F)):
+        m[a, b] = True                                           # y on it
+    m[F - 1:F + 1, F - 1:F + 1] = True                           # blocks over the corners of the frame
+    m[nx - F - 1:nx - F + 1, ny - F - 1:ny - F + 1] = True
+    m[nx - F - 2:nx - F, F - 2:F] = True
+    m[0, 0] = m[nx - 1, 0] = m[0, ny - 1] = m[nx - 1, ny - 1] = True
+    m[nx // 2:nx // 2 + 6, 0] = True                             # the lid row
+    m[nx // 3, 0:F + 2] = True                                   # from the lid through the frame into a tile
+    out["rim"] = m
+    m = z()
+    m[xs[0] - 1, :] = True
+    m[xs[1], :] = True
+    assert (xs[0] - 1) % 4 == 3 and xs[1] % 4 == 0
+    out["column"] = m
+    m = z()
+    m[:, ys[0] - 1] = True
+    m[:, ny - F] = True
+    out["row"] = m
+    return out
+
+
+def _all_masks(nx, ny, dtype, steps):
+    out = dict(_masks(nx, ny))
+    out.update(_seam_masks(nx, ny, dtype, steps))
+    return out
+
+
+def _fields_equal(got, want, what):
+    for a, b, name in zip(got, want, ("u", "rho", "fin")):
+        assert np.isfinite(a).all(), f"{what}: {name} not finite"
+        assert np.array_equal(a, b), f"{what}: {name} differs in {np.count_nonzero(a != b)} values, max abs {np.abs(a - b).max()}"
+
+
+def _walk(o, single, tiled, marks, what):
+    """Advance the reference, the one-step solver and the tile solvers {S: solver} together; at every step count in marks[S] solver S is
+    compared with the reference and with the one-step route."""
+    n0 = single.steps_done
+    for n in sorted(set().union(*marks.values())):
+        o.step(n - (single.steps_done - n0))
+        single.step(n - (single.steps_done - n0))
+        ref = (o.u, o.rho, o.fin)
+        one = single.get_fields(want_fin=True)
+        _fields_equal(one, ref, f"{what} after {n}: one step per launch against the reference")
+        for S, s in tiled.items():
+            if n in marks[S]:
+                s.step(n - (s.steps_done - n0))
+                got = s.get_fields(want_fin=True)
+                _fields_equal(got, ref, f"{what} S={S} after {n}: against the reference")
+                _fields_equal(got, one, f"{what} S={S} after {n}: against one step per launch")
+
+
+GROUPS = [(c, d, g) for d in (np.float32, np.float64) for c in ("SRT", "TRT", "MRT") for g in ((3,), (4, 5))]
+
+
+@pytest.mark.parametrize("coll,dtype,steps", GROUPS, ids=lambda v: v if isinstance(v, str) else ("S" + "".join(map(str, v)) if isinstance(v, tuple) else np.dtype(v).name))
+def test_strict_bit_identical_to_reference_and_to_one_step_per_launch(coll, dtype, steps):
+    """For every mask: after 1, S, S + 1, 2 S + 2 and 37 steps from set_solid's initial state, then after 1, S + 1 and 2 S + 2 steps from a
+    set_state of the developed field (whose solid cells the host array fills with rubbish).  The solvers live through all masks: every
+    set_solid comes between two step calls and replaces a different mask, after multi-step units have run (the lattice of the step
+    before the last and the scratch lattices exist by then and must follow).  S = 4 and S = 5 share the F = 8 shape and one reference."""
+    nx, ny = _shape(dtype, steps[0])
+    zero = np.zeros((nx, ny), bool)
+    tiled = {S: CavitySolver(nx, ny, 100.0, RT=coll, dtype=dtype, solid=zero, tuning=dict(TILES, tb_steps=S), **BB) for S in steps}
+    single = CavitySolver(nx, ny, 100.0, RT=coll, dtype=dtype, solid=zero, **BB)
+    try:
+        for S, s in tiled.items():
+            d = s.describe()
+            assert (d["kernel"], d["steps_per_launch"], d["frame"], d["semantics"]) == ("k_stepS_deep", S, _tile(dtype, S)[0], "bounce_back_solid")
+        assert single.describe()["kernel"] == "k_step_solid"
+        for name, m in _all_masks(nx, ny, dtype, steps).items():
+            o = SolidOracle(nx, ny, 100.0, mask=m, collision=coll, dtype=dtype)
+            for s in list(tiled.values()) + [single]:
+                s.set_solid(m)
+                assert np.array_equal(s.solid, m) and s.steps_done == 0
+            what = f"{nx}x{ny} {coll} {np.dtype(dtype).name} mask {name}"
+            _walk(o, single, tiled, {S: {1, S, S + 1, 2 * S + 2, 37} for S in steps}, what)
+            f = o.fin.copy()
+            o.set_state(f)
+            f[:, m] = -7.0
+            for s in list(tiled.values()) + [single]:
+                s.set_state(f)
+            _walk(o, single, tiled, {S: {1, S + 1, 2 * S + 2} for S in steps}, what + " from a developed state")
+            fin = tiled[steps[-1]].get_fields(want_fin=True)[2]
+            assert np.array_equal(fin[:, m], np.broadcast_to(o.t[:, None], (9, int(m.sum())))), what + ": solid cells"
+    finally:
+        for s in list(tiled.values()) + [single]:
+            s.close()
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+@pytest.mark.parametrize("tune", [dict(frame_lds=False), dict(frame_fused=False), dict(frame_fused=False, frame_lds=False), dict(eager_lag=True),
+                                  dict(frame_seg=8)], ids=lambda t: "-".join(sorted(t)))
+def test_other_frame_routes(dtype, tune):
+    """The frame passes through the scratch lattices, one launch per pass, and the eager single step at the end of a call: accepted, and
+    the same bits as one step per launch (which the test above holds to the reference)."""
+    for S in (3, 5):
+        nx, ny = _shape(dtype, S)
+        ms = _all_masks(nx, ny, dtype, (S,))
+        with CavitySolver(nx, ny, 100.0, RT="MRT", dtype=dtype, solid=ms["rim"], tuning=dict(TILES, tb_steps=S, **tune), **BB) as s, \
+                CavitySolver(nx, ny, 100.0, RT="MRT", dtype=dtype, solid=ms["rim"], **BB) as g:
+            assert s.describe()["kernel"] == "k_stepS_deep" and s.describe()["frame_fused"] == (0 if "frame_fused" in tune else 1)
+            for name in ("rim", "random", "seams"):
+                if name != "rim":
+                    s.set_solid(ms[name]); g.set_solid(ms[name])
+                for n in (1, S, 2 * S + 3, 17):
+                    s.step(n); g.step(n)
+                    _fields_equal(s.get_fields(want_fin=True), g.get_fields(want_fin=True), f"{tune} S={S} {name} after {s.steps_done}")
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+@pytest.mark.parametrize("coll", ["SRT", "TRT", "MRT"])
+def test_fast_arithmetic(coll, dtype):
+    """The configuration of test_solid_gpu.test_fast_arithmetic (128 x 96, Re 1000, 2000 steps, its mask plus cells on the seams): the tile
+    route and the one-step route agree bit for bit, and the distance from strict fp64 stays inside that test's bound."""
+    nx, ny = 128, 96
+    m = np.zeros((nx, ny), bool)
+    m[35:49, 30:50] = True
+    m[90, 0:3] = m[0, 60] = m[100:103, ny - 1] = True
+    m[62:66, 30:34] = True            # over the seam x = 63 | 64 of S = 5 (F = 8, TX = 56) and the row seam y = 31 | 32 (TY = 24)
+    m[7:9, 70] = m[nx - 9:nx - 7, 75] = True
+    with CavitySolver(nx, ny, 1000.0, RT=coll, dtype=np.float64, solid=m, **BB) as ref:
+        ref.step(2000)
+        f_ref = ref.get_fields(want_fin=True)[2]
+    got = []
+    for tune in (None, TILES, dict(TILES, tb_steps=3)):
+        with CavitySolver(nx, ny, 1000.0, RT=coll, dtype=dtype, arith="fast", solid=m, tuning=tune, **BB) as s:
+            assert s.describe()["kernel"] == ("k_stepS_deep" if tune else "k_step_solid")
+            s.step(2000)
+            got.append(s.get_fields(want_fin=True, out_dtype=np.float64)[2])
+    assert np.array_equal(got[0], got[1]) and np.array_equal(got[0], got[2]), "fast arithmetic differs between the routes"
+    err = float(np.abs(got[1] - f_ref).max() / np.abs(f_ref).max())
+    print(f"fast solid tiles {coll} {np.dtype(dtype).name}: {err:.3e} (bound {FAST_BOUND[dtype]:.1e})")
+    assert err < FAST_BOUND[dtype], err
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+def test_all_fluid_mask_equals_plain_bounce_back_tiles(dtype):
+    for S in (3, 4, 5):
+        nx, ny = _shape(dtype, S)
+        for arith in ("strict", "fast"):
+            with CavitySolver(nx, ny, 400.0, RT="MRT", dtype=dtype, kernel="tb", arith=arith, tuning=dict(tb_steps=S), **BB) as plain, \
+                    CavitySolver(nx, ny, 400.0, RT="MRT", dtype=dtype, arith=arith, solid=np.zeros((nx, ny), bool), tuning=dict(TILES, tb_steps=S), **BB) as s:
+                assert plain.describe()["kernel"] == s.describe()["kernel"] == "k_stepS_deep"
+                for n in (1, S, 2 * S + 1, 30):
+                    assert s.next_unit(n) == plain.next_unit(n)
+                    plain.step(n); s.step(n)
+                    _fields_equal(s.get_fields(want_fin=True), plain.get_fields(want_fin=True), f"{nx}x{ny} S={S} {arith} after {s.steps_done}")
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+def test_batch_of_masks_equals_lattices_alone(dtype):
+    nx, ny = _shape(dtype, 5)
+    ms = _all_masks(nx, ny, dtype, (5,))
+    masks, Res = np.stack([ms["seams"], ms["random"], ms["rim"]]), [100.0, 400.0, 1000.0]
+    for tune in (TILES, dict(TILES, frame_fused=False)):
+        with CavityBatch(nx, ny, Res, RT="MRT", dtype=dtype, solid=masks, tuning=tune, **BB) as b:
+            assert np.array_equal(b.solid, masks) and b.describe()["kernel"] == "k_stepS_deep"
+            b.step(1)
+            assert b.next_unit(100) == 5
+            b.step(22)
+            u, rho, fin = b.get_fields(want_fin=True)
+            F = b.solid_force()
+        for i, Re in enumerate(Res):
+            with CavitySolver(nx, ny, Re, RT="MRT", dtype=dtype, solid=masks[i], **BB) as s:
+                s.step(23)
+                _fields_equal((u[i], rho[i], fin[i]), s.get_fields(want_fin=True), f"lattice {i} {tune}")
+                assert {k: F[k][i] for k in F} == s.solid_force(), Re
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+def test_force_on_the_obstacles(dtype):
+    """After 37 steps: links exactly; fx, fy the bits of the one-step route (the same reduction over the same populations), and against
+    the exactly rounded host sum within links * 2^-52 * sum |terms|, the bound of tests/test_solid_gpu.py."""
+    nx, ny = _shape(dtype, 5)
+    for name, m in _all_masks(nx, ny, dtype, (5,)).items():
+        with CavitySolver(nx, ny, 100.0, RT="MRT", dtype=dtype, solid=m, tuning=TILES, **BB) as s, \
+                CavitySolver(nx, ny, 100.0, RT="MRT", dtype=dtype, solid=m, **BB) as g:
+            rec = (s.lib.lbm_solid_force.argtypes[1]._type_ * 1)()
+            assert s.lib.lbm_solid_force(s._h, rec) == -4, "LBM_ERR_STATE before the first step"
+            s.step(37); g.step(37)
+            F, F2, G = s.solid_force(), s.solid_force(), g.solid_force()
+            fin = s.get_fields(want_fin=True)[2]
+        assert F == F2 == G and F["step"] == 37, (name, F, G)
+        want = solid.host_force(fin, m)
+        tx, ty = solid.force_terms(fin, m)
+        assert F["links"] == want["links"] == sum(int(l.sum()) for l in solid.links(m)), name
+        for k, t in (("fx", tx), ("fy", ty)):
+            bound = want["links"] * 2.0 ** -52 * math.fsum(np.abs(t).tolist())
+            print(f"{nx}x{ny} {name} {np.dtype(dtype).name} {k}: device {F[k]!r} host {want[k]!r} bound {bound!r}")
+            assert abs(F[k] - want[k]) <= bound, (name, k, F[k], want[k], bound)
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+def test_samplers_equal_the_one_step_route(dtype):
+    """monitor, statistics, residual and topology on a masked lattice, sampled by step() itself inside multi-step calls (the units are cut
+    at the samples, the lattice of the step before the last is recomputed): the records of the one-step route."""
+    nx, ny = _shape(dtype, 5)
+    ms = _all_masks(nx, ny, dtype, (5,))
+    m = ms["seams"] | ms["rim"]
+    out = []
+    for tune in (None, TILES):
+        with CavitySolver(nx, ny, 100.0, RT="MRT", dtype=dtype, solid=m, tuning=tune, **BB) as s:
+            s.step(11)
+            probes = ((20, ny // 4 + 1), (3, 3), (nx - 9, ny - 9))
+            s.begin_statistics(every=7); s.begin_residual(every=6); s.begin_monitor(every=5, probes=probes)
+            s.step(37)
+            s.sample_statistics(); s.sample_residual(); s.sample_monitor()
+            rec = s.monitor(probes=probes)
+            assert rec["nonfinite"] == 0 and rec["step"] == 48
+            u = s.get_fields()[0]
+            assert not u[:, m].any()
+            psi, omega = s.stream_function()
+            out.append(dict(monitor=rec, series=s.monitor_series(), stats=s.statistics(), residual=s.residual_series(), topology=s.topology(((0, nx, 0, ny), (8, 40, 8, 40))),
+                            psi=psi, omega=omega, fields=s.get_fields(want_fin=True)))
+    a, b = out
+
+    def same(x, y, what):
+        if isinstance(x, dict):
+            assert x.keys() == y.keys(), what
+            for k in x:
+                same(x[k], y[k], f"{what}.{k}")
+        elif isinstance(x, (list, tuple)):
+            assert len(x) == len(y), what
+            for i, (p, q) in enumerate(zip(x, y)):
+                same(p, q, f"{what}[{i}]")
+        else:
+            assert np.array_equal(np.asarray(x), np.asarray(y), equal_nan=True), what
+    same(a, b, "samplers")
+    assert a["series"]["count"] == 8 and a["stats"]["samples"] == 6 and a["residual"]["count"] == 6
+
+
+def test_checkpoint_round_trip(tmp_path):
+    nx, ny = _shape(np.float32, 5)
+    m = _all_masks(nx, ny, np.float32, (5,))["seams"]
+    with CavitySolver(nx, ny, 400.0, RT="MRT", dtype=np.float32, solid=m, tuning=TILES, **BB) as s:
+        s.step(25)
+        path = s.save_checkpoint(str(tmp_path / "tiles"))
+        s.step(30)
+        want = s.get_fields(want_fin=True)
+    for tune in (TILES, None):      # a continuation on either route
+        with CavitySolver(nx, ny, 400.0, RT="MRT", dtype=np.float32, solid=m, tuning=tune, **BB) as r:
+            assert r.load_checkpoint(path) == 25
+            r.step(30)
+            _fields_equal(r.get_fields(want_fin=True), want, f"restart {tune}")
+
+
+def test_describe_next_unit_and_error_paths():
+    nx, ny = 128, 72
+    zero = np.zeros((nx, ny), bool)
+    for dtype, S in ((np.float32, 5), (np.float64, 5)):
+        with CavitySolver(nx, ny, 100.0, dtype=dtype, solid=zero, tuning=TILES, **BB) as s:
+            d = s.describe()
+            assert d["kernel"] == "k_stepS_deep" and d["steps_per_launch"] == S and d["frame"] == 8 and d["semantics"] == "bounce_back_solid"
+            assert s.next_unit(100) == 1                       # the first step after set_solid reads plain populations
+            s.step(1)
+            assert s.next_unit(100) == S and s.next_unit(2) == 1 and s.next_unit(3) == 3
+            s.step(9)
+            assert s.steps_done == 10 and d["lattices"] == 2
+    with CavitySolver(nx, ny, 100.0, solid=zero, **BB) as s:      # without the switch: as before
+        s.step(1)
+        assert s.describe()["kernel"] == "k_step_solid" and s.next_unit(100) == 1
+    with pytest.raises(RuntimeError, match="needs a solid mask"):
+        CavitySolver(nx, ny, 100.0, tuning=TILES, **BB)
+    with pytest.raises(RuntimeError, match="needs a solid mask"):
+        CavitySolver(nx, ny, 100.0, tuning=TILES)
+    for kernel in ("stream", "vec", "push", "generic"):
+        with pytest.raises(RuntimeError, match="kernel = AUTO or TB"):
+            CavitySolver(nx, ny, 100.0, kernel=kernel, solid=zero, tuning=TILES, **BB)
+    with pytest.raises(RuntimeError, match="needs what kernel = TB needs"):
+        CavitySolver(70, 66, 100.0, solid=np.zeros((70, 66), bool), tuning=TILES, **BB)
+    with pytest.raises(RuntimeError, match="needs what kernel = TB needs"):
+        CavitySolver(28, 64, 100.0, solid=np.zeros((28, 64), bool), tuning=TILES, **BB)
+    with pytest.raises(RuntimeError, match="no slabs"):
+        CavitySolver(nx, ny, 100.0, rows=(0, 36), solid=zero, tuning=TILES, **BB)
+    with pytest.raises(RuntimeError, match="3 .. 5"):
+        CavitySolver(nx, ny, 100.0, solid=zero, tuning=dict(TILES, tb_steps=2), **BB)
+    with pytest.raises(RuntimeError, match="no fluid cell"):
+        CavitySolver(nx, ny, 100.0, solid=np.ones((nx, ny), bool), tuning=TILES, **BB)
+    with CavitySolver(nx, ny, 100.0, solid=zero, kernel="tb", tuning=TILES, **BB) as s:
+        assert s.describe()["kernel"] == "k_stepS_deep"
+        with pytest.raises(RuntimeError, match="no fluid cell"):
+            s.set_solid(np.ones((nx, ny), bool))
+        s.step(7)                                              # (the refused mask left the context as it was)
+        assert not s.solid.any() and s.steps_done == 7

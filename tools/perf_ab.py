@@ -5,9 +5,10 @@
 
 A case is  size:dtype:arith[:key=value,...]  e.g.  4096:f32:fast   4096:f32:strict:tb_steps=4   8192x1024:f64:fast:coll=SRT,turb=1
 (keys: coll, turb, kernel, layout, sem (semantics: mrt_gpu, mrt_py, bounce_back), solid (with sem=bounce_back: fluid -- the all-fluid mask --,
-block -- one block of an eighth of the width squared in the middle --, random -- 20 % of the cells, seeded), batch (that many lattices,
+block -- one block of an eighth of the width squared in the middle --, random -- 20 % of the cells, seeded), route (with solid: single --
+one step per launch, the default -- or tiles -- the multi-step tile kernel, tuning solid_tiles), batch (that many lattices,
 GLUPS in aggregate) and every CavitySolver tuning switch).  Prints GLUPS (best of --reps timings of --steps steps
-after a device wake-up and a warm-up) and microseconds per step, one line per case.
+after a device wake-up and a warm-up), microseconds per step and the GLUPS of every repeat, one line per case.
 """
 import argparse
 import os
@@ -50,6 +51,10 @@ def parse(case):
                 kw["turb"] = int(v)
             elif k == "solid":
                 kw["solid"] = solid_mask(v, nx, ny)
+            elif k == "route":
+                if v not in ("single", "tiles"):
+                    raise ValueError("route must be single or tiles")
+                tune["solid_tiles"] = v == "tiles"
             elif k == "batch":
                 kw["batch"] = int(v)
             elif k in ("tb_steps", "frame_seg"):
@@ -72,8 +77,10 @@ def main():
         with make(nx, ny, 1000.0, dtype=dtype, arith=arith, tuning=tune, **kw) as s:
             s.copy_bandwidth(1 << 30, 60)
             s.step(max(60, a.steps // 10)); s.sync()
-            ms = min(s.time_steps(a.steps) for _ in range(a.reps)) / a.steps
-            print(f"{case:48s} S={s.next_unit(1000)}  {B * nx * ny / ms / 1e6:8.1f} GLUPS  {ms * 1e3:9.2f} us/step", flush=True)
+            reps = [s.time_steps(a.steps) / a.steps for _ in range(a.reps)]
+            ms = min(reps)
+            print(f"{case:48s} S={s.next_unit(1000)}  {B * nx * ny / ms / 1e6:8.1f} GLUPS  {ms * 1e3:9.2f} us/step  "
+                  f"repeats {' '.join('%.1f' % (B * nx * ny / r / 1e6) for r in reps)}", flush=True)
 
 
 if __name__ == "__main__":
