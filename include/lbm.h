@@ -242,8 +242,11 @@ int lbm_get_tau(lbm_ctx* c, void* tau_host, int host_dtype);
  * post different exchanges): slabs call lbm_<sampler>_sample at the same step counts on every rank and the host combines the results.
  * Calling _begin again restarts the sampler.  lbm_<sampler>_end stops it and frees what _begin allocated; lbm_init_equilibrium,
  * lbm_set_state and lbm_destroy end every sampler too, and none is part of a checkpoint.
+ * The force on the bodies of a solid mask (lbm_force_*, below) is a fourth sampler on this schedule, enqueued last, with its own
+ * instant: its sample of step count n is defined on the lattice after n steps, not n - 1, so a launch unit is cut to END at n and the
+ * sample follows that unit, also where the unit is the last of an lbm_step call.
  *
- * A SERIES (monitor, residual).  _begin allocates room for `capacity` samples, capacity x batch records on the device (there, never
+ * A SERIES (monitor, residual, force).  _begin allocates room for `capacity` samples, capacity x batch records on the device (there, never
  * inside lbm_step).  A sample writes the next free slot; nothing returns to the host before lbm_<sampler>_read.  With the buffer full a
  * sample leaves no record and is counted in `dropped`; stepping is unaffected.  _read synchronises; *count = records held, *dropped =
  * samples that left none; records_out[min(count, max_records)][batch] receives the oldest records (may be NULL with max_records = 0).
@@ -490,6 +493,58 @@ typedef struct lbm_solid_force_record {
 int lbm_set_solid(lbm_ctx* c, const uint8_t* mask);
 int lbm_get_solid(lbm_ctx* c, uint8_t* mask_out);
 int lbm_solid_force(lbm_ctx* c, lbm_solid_force_record* out);
+
+/* --- the bodies of a mask: force and torque on each, one-shot and as a series ------------------ */
+/* No reference counterpart.  The solid cells of a lattice are split into nbodies bodies by a label per cell, and every LINK -- a (fluid
+ * cell (x, y), slot k) pair whose source (x - cx_k, y + cy_k) is a solid cell -- belongs to the body of its source cell.  Two bodies
+ * that touch share no link: a link's own cell is fluid.
+ *
+ * lbm_set_solid_bodies: body[B][X][Y] int32, the host layout of the mask; on every solid cell a value in [0, nbodies), ignored on
+ *   fluid cells; 1 <= nbodies <= 256.  centre[B][nbodies][2] = (x0, y0) of each body in index coordinates; NULL takes each body's
+ *   centroid, the mean of its cells' indices in double.  A body without cells gets the centre (0, 0) and has no links.
+ *   LBM_ERR_STATE on a context of another semantics; LBM_ERR_INVALID for a label out of range on a solid cell, a centre that is not
+ *   finite or another bad argument.  Touches neither the lattice nor the step count; ends a running force series and nothing else.
+ *   From the mask and the labels it derives one link list per lattice, sorted by body, then by cell in [y][x] order, then by k, and
+ *   uploads it (there and in lbm_set_solid, never inside lbm_step), so that a sample costs O(links), not a pass over the lattice.
+ *   lbm_set_solid resets to the default, which is also a fresh context's: one body that holds every solid cell, centred at its centroid.
+ * lbm_get_solid_bodies: body_out[B][X][Y] receives the labels (-1 on fluid cells), centre_out[B][nbodies][2] the centres; either may
+ *   be NULL.  lbm_solid_body_count: nbodies (0 for a NULL context or one of another semantics).
+ * lbm_body_force: out[B][nbodies], all doubles:
+ *   step    the step count
+ *   body    the body's label
+ *   links   the links of the body
+ *   fx, fy  sum over them of tx = 2 cx_opp(k) f and ty = 2 cy_opp(k) f, f exactly the population lbm_solid_force uses
+ *   tz      sum over them of rx ty + ry tx, (rx, ry) = (x - cx_k / 2 - x0, y + cy_k / 2 - y0) the link's midpoint relative to the
+ *           body's centre.  The index y grows AWAY from the lid while fy > 0 points TO the lid, so this is the z-moment in the frame
+ *           drawn with the lid on top (X = x, Y = -y): X Fy - Y Fx, positive counter-clockwise.
+ *   Every term is formed in double without contraction, each product rounded, then rx ty + ry tx, then the sum.  Reduced per body by
+ *   THE TREE, without atomics: the body's range of the list is cut into chunks of 2048 links, a workgroup folds one chunk (lane t its
+ *   links t, t + 256, ...), and one wave per body folds the chunks' results in order.  The bits depend on the list and the lattice
+ *   alone: they are the same from run to run, in this call and in a series, for a lattice alone and as a member of a batch, and on
+ *   either kernel route.  A body without links has links = fx = fy = tz = 0.  Synchronises.  LBM_ERR_STATE before the first step and
+ *   on a context of another semantics, as lbm_solid_force, whose records and bits are unchanged.
+ * lbm_force_begin / _sample / _read / _end: A SERIES of these records on THE SCHEDULE, a sample being batch x nbodies records.  With
+ *   n0 = lbm_steps_done() at _begin and every > 0 the records carry step = n0 + every, n0 + 2 every, ..., each bit for bit what
+ *   lbm_body_force returns when called at that step count; after any lbm_step call exactly the samples with n <= lbm_steps_done()
+ *   have been taken.  With LBM_FLAG_SOLID_TILES a multi-step unit ends at every sample.  _begin: LBM_ERR_INVALID for every < 0 or
+ *   capacity < 1, LBM_ERR_STATE before the first step.  lbm_force_sample records the force of the lattice as it is now.  The series
+ *   ends on lbm_force_end, lbm_set_solid_bodies, lbm_set_solid, lbm_init_equilibrium, lbm_set_state and lbm_destroy. */
+typedef struct lbm_body_force_record {
+    double step;
+    double body;
+    double links;
+    double fx;
+    double fy;
+    double tz;
+} lbm_body_force_record;
+int lbm_set_solid_bodies(lbm_ctx* c, const int32_t* body, int nbodies, const double* centre);
+int lbm_get_solid_bodies(lbm_ctx* c, int32_t* body_out, double* centre_out);
+int lbm_solid_body_count(lbm_ctx* c);
+int lbm_body_force(lbm_ctx* c, lbm_body_force_record* out);
+int lbm_force_begin(lbm_ctx* c, int every, int capacity);
+int lbm_force_sample(lbm_ctx* c);
+int lbm_force_read(lbm_ctx* c, lbm_body_force_record* records_out, int max_records, long long* count, long long* dropped);
+int lbm_force_end(lbm_ctx* c);
 
 /* --- slab decomposition, externally driven exchange ---------------------------------- */
 /* No reference counterpart (the reference is single-GPU, MRT_GPU.py:29).  A step of a slab

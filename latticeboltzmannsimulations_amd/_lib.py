@@ -86,13 +86,17 @@ class lbm_solid_force_record(ctypes.Structure):
     _fields_ = [(n, ctypes.c_double) for n in ("step", "links", "fx", "fy")]
 
 
+class lbm_body_force_record(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_double) for n in ("step", "body", "links", "fx", "fy", "tz")]
+
+
 def sources():
     return [os.path.join(_CSRC, f) for f in sorted(os.listdir(_CSRC)) if f.endswith((".hip", ".hpp"))] + [HEADER]
 
 
 def build(force=False, verbose=False):
     """Compile csrc/*.hip for gfx950 into liblbm_hip.so next to this file (in-tree).  The translation units (eight of host code +
-    C ABI: lbm_hip / lbm_plan / lbm_launch / lbm_comm / lbm_sampling / lbm_monitor / lbm_residual / lbm_topology / lbm_solid; the explicit instantiations of the tile, streaming and
+    C ABI: lbm_hip / lbm_plan / lbm_launch / lbm_comm / lbm_sampling / lbm_monitor / lbm_residual / lbm_topology / lbm_solid / lbm_bodies; the explicit instantiations of the tile, streaming and
     solid-mask kernels, and of the tile kernel with solid cells, for float and for double) are compiled in parallel into csrc/_obj/ and linked."""
     srcs = sources()
     if not force and os.path.exists(LIB_PATH) and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(s) for s in srcs):
@@ -162,6 +166,14 @@ SIGNATURES = {
     "lbm_set_solid": (_i, [_vp, _vp]),
     "lbm_get_solid": (_i, [_vp, _vp]),
     "lbm_solid_force": (_i, [_vp, ctypes.POINTER(lbm_solid_force_record)]),
+    "lbm_set_solid_bodies": (_i, [_vp, _vp, _i, _vp]),
+    "lbm_get_solid_bodies": (_i, [_vp, _vp, _vp]),
+    "lbm_solid_body_count": (_i, [_vp]),
+    "lbm_body_force": (_i, [_vp, ctypes.POINTER(lbm_body_force_record)]),
+    "lbm_force_begin": (_i, [_vp, _i, _i]),
+    "lbm_force_sample": (_i, [_vp]),
+    "lbm_force_read": (_i, [_vp, _vp, _i, ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ctypes.c_longlong)]),   # (records: [samples][B][nbodies])
+    "lbm_force_end": (_i, [_vp]),
     "lbm_halo_elems": (_i, [_vp]),
     "lbm_halo_export": (_i, [_vp, _i, _vp]),
     "lbm_halo_import": (_i, [_vp, _i, _vp]),

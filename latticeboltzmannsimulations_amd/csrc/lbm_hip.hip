@@ -150,10 +150,10 @@ int reduce_u(lbm_ctx* c) {
     });
 }
 
-// What lbm_init_equilibrium and lbm_set_state share: the three samplers ended, the run state of a fresh lattice in lat[0].  The caller
+// What lbm_init_equilibrium and lbm_set_state share: the samplers ended, the run state of a fresh lattice in lat[0].  The caller
 // has synchronised the streams.
 static void reset_run_state(lbm_ctx* c) {
-    for (int i = 0; i < NSAMPLERS; ++i) sampler_free(c, i);
+    for (int i = 0; i < NSCHEDULED; ++i) sampler_free(c, i);
     c->cur = 0; c->raw[0] = 1; c->raw[1] = 1; c->nsteps = 0; c->lag = 0; c->lag_valid = false;
     c->order.reset();
 }
@@ -223,6 +223,7 @@ lbm_ctx* lbm_create(const lbm_params* p, char* err, size_t errlen) {
         if ((e = hipMemsetAsync(c->lat[i], 0, bytes, c->s_compute)) != hipSuccess) return cleanup(std::string("hipMemset: ") + hipGetErrorString(e));
     }
     if (p->semantics == LBM_SEM_BOUNCE_BACK_SOLID) c->solid_mask.assign((size_t)c->plan.batch * p->nx * p->ny, 0);   // all fluid
+    if (bodies_default(c) != LBM_OK) return cleanup(c->err);
     if (c->plan.batch > 1) {   // every lattice starts with the rates of lbm_params; lbm_set_relaxation() changes them one by one
         const size_t rb = c->plan.es == 4 ? sizeof(Relax<float>) : sizeof(Relax<double>);
         if ((e = hipMalloc(&c->relax_dev, rb * c->plan.batch)) != hipSuccess) return cleanup(std::string("hipMalloc(relaxation): ") + hipGetErrorString(e));
@@ -243,10 +244,11 @@ void lbm_destroy(lbm_ctx* c) {
     for (int i = 0; i < NLAT; ++i)
         if (c->lat[i]) (void)hipFree(c->lat[i]);
     if (c->red_dev) (void)hipFree(c->red_dev);
-    for (int i = 0; i < NSAMPLERS; ++i) sampler_free(c, i);
+    for (int i = 0; i < NSCHEDULED; ++i) sampler_free(c, i);
     monitor_free(c);
     topology_free(c);
     solid_free(c);
+    bodies_free(c);
     if (c->stage) (void)hipFree(c->stage);
     if (c->relax_dev) (void)hipFree(c->relax_dev);
     if (c->ev_edges) (void)hipEventDestroy(c->ev_edges);

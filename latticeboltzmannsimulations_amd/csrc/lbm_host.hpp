@@ -11,8 +11,10 @@
 //   lbm_residual.hip the field residual (kernels: lbm_residual.hpp)                        (C ABI: residual_*)
 //   lbm_topology.hip stream function, vorticity, extrema of psi (kernels: lbm_topology.hpp) (C ABI: topology, get_stream_function)
 //   lbm_solid.hip   solid obstacles: the mask and its link plane, the force on the obstacles (step kernel: lbm_solid.hpp) (C ABI: set_solid, get_solid, solid_force)
-// and two headers free of HIP, each driven by a CPU test through a program of its own:
+//   lbm_bodies.hip  the bodies of a mask: force and torque on each, one-shot and as a series    (C ABI: set_solid_bodies, get_solid_bodies, body_force, force_*)
+// and three headers free of HIP, each driven by a CPU test through a program of its own:
 //   lbm_schedule.hpp the schedule of automatic sampling
+//   lbm_bodies.hpp   the labels of a mask's bodies, their centroids, the link list and its chunks
 //   lbm_order.hpp    the ordering of the two streams: the state carried between units, the skeletons of a unit, the argument
 #pragma once
 #include <hip/hip_runtime.h>
@@ -32,6 +34,7 @@
 #include "../../include/lbm.h"
 #include "lbm_schedule.hpp"
 #include "lbm_order.hpp"
+#include "lbm_bodies.hpp"
 #include "lbm_solid.hpp"  // k_step_solid, extern (compiled in lbm_solid_f32/f64.hip)
 #include "lbm_inst.hpp"   // the kernels, and extern template declarations of the multi-step ones (compiled in lbm_{tiles,stream*}_f32/f64.hip)
 
@@ -96,6 +99,20 @@ struct Series {
     long long capacity = 0, count = 0, dropped = 0;
 };
 
+// The tables of the bodies on the device (bodies_upload, lbm_bodies.hip), all inside the one allocation `base`: the link list of every
+// lattice, one after the other; chunks[batch][maxchunks]; first[batch][nbodies + 1], each body's range of chunks; centre[batch][nbodies][2];
+// then the workgroups' partial results of one pass and the records of the one-shot call.
+struct BodyTables {
+    void* base = nullptr;
+    const lbmhost::BodyLink* links = nullptr;
+    const lbmhost::BodyChunk* chunks = nullptr;
+    const int32_t* first = nullptr;
+    const double* centre = nullptr;
+    double* partial = nullptr;
+    double* rec = nullptr;
+    int maxchunks = 1;
+};
+
 // Run state.  What was decided once is in `plan`; p stays for the fields later code branches on (dtype, collision, semantics, turb,
 // arith, device) and for the relaxation rates, which lbm_set_relaxation rewrites.
 struct lbm_ctx {
@@ -118,8 +135,9 @@ struct lbm_ctx {
     size_t stage_bytes = 0;
     double* red_dev = nullptr;  // lbm_mean_u: partial sums + results
     // The samplers (lbm_sampling.hip).  sampler[i]: the schedule of automatic sampling, which takes the sample of step count n from
-    // lat[cur] when a unit would start at n - 1 (step_many); a Series: the records of a series on the device, null while it is off.
-    lbmhost::Sampler sampler[lbmhost::NSAMPLERS];
+    // lat[cur] when a unit would start at n - 1 (step_many) -- the force sampler: when a unit has ended at n; a Series: the records of a
+    // series on the device, null while it is off.
+    lbmhost::Sampler sampler[lbmhost::NSCHEDULED];
     // Time statistics (lbm_stats_*): six double sums per cell (k_stats_accumulate), null while statistics are off.
     double* stats_dev = nullptr;
     long long stats_count = 0;  // samples enqueued
@@ -145,6 +163,14 @@ struct lbm_ctx {
     // them, its records (allocated on first use, kept).
     std::vector<uint8_t> solid_mask;
     double* force_dev = nullptr;
+    // The bodies of the mask (lbm_set_solid_bodies, lbm_bodies.hip): body_label[batch][nx][ny], -1 on fluid cells, body_centre[batch]
+    // [nbodies][2]; one body that holds every solid cell after lbm_create and lbm_set_solid.  body: what the device holds of them;
+    // force_series: the records of lbm_force_begin, [capacity][batch][nbodies].
+    int nbodies = 1;
+    std::vector<int32_t> body_label;
+    std::vector<double> body_centre;
+    BodyTables body;
+    Series force_series;
     ncclComm_t comm = nullptr;
     int nranks = 1, rank = 0;
     bool loopback = false;      // diagnostic: 1-rank communicator, the slab exchanges halos with itself
@@ -385,6 +411,7 @@ void series_free(Series& s);
 int sampler_begin(lbm_ctx* c, int sampler, int every);
 int sample_now(lbm_ctx* c, int sampler, bool on);
 int sample_if_due(lbm_ctx* c);
+int sample_after_unit(lbm_ctx* c);
 void sampler_free(lbm_ctx* c, int sampler);
 int sampler_end(lbm_ctx* c, int sampler);
 // lbm_monitor.hip
@@ -396,6 +423,10 @@ void topology_free(lbm_ctx* c);
 int solid_fix(lbm_ctx* c);
 int solid_copy_links(lbm_ctx* c, int to);
 void solid_free(lbm_ctx* c);
+// lbm_bodies.hip
+int bodies_default(lbm_ctx* c);
+void bodies_free(lbm_ctx* c);
+int force_series_sample(lbm_ctx* c);
 // lbm_residual.hip
 int residual_series_sample(lbm_ctx* c, int which, long long step);
 void residual_free(lbm_ctx* c);

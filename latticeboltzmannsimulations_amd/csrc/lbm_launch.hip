@@ -404,6 +404,7 @@ int step_many(lbm_ctx* c, int nsteps) {
         for (int i = 0; i < nsteps; ++i) {
             int rc = sample_if_due(c);
             if (rc == LBM_OK) rc = push_step(c);
+            if (rc == LBM_OK) rc = sample_after_unit(c);
             if (rc) return rc;
         }
         return LBM_OK;
@@ -422,6 +423,7 @@ int step_many(lbm_ctx* c, int nsteps) {
         if (rc) return rc;
         const int S = unit_steps(c->plan, (int)steps_to_cut(c->sampler, c->nsteps, left), c->raw[c->cur] != 0, own_transport(c));
         rc = run_unit(c, &comm_used, S, true);
+        if (rc == LBM_OK) rc = sample_after_unit(c);
         if (rc) return rc;
         left -= S;
     }

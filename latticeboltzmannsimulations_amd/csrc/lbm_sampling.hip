@@ -96,7 +96,7 @@ int sample_now(lbm_ctx* c, int sampler, bool on) {
     return sample_from(c, sampler, which, c->nsteps);
 }
 
-// Automatic sampling (a lone lattice), before every unit of step_many: the samples of step count nsteps + 1, from lat[cur] with its raw
+// Automatic sampling (a lone lattice), before every unit of step_many: the field samples of step count nsteps + 1, from lat[cur] with its raw
 // flag -- no lag replay; a call that ends at n - 1 takes the sample of n at the start of the next call.  The samplers keep their own
 // schedules; a step count due for several is read by each of them, in the order of the enum.
 int sample_if_due(lbm_ctx* c) {
@@ -114,6 +114,18 @@ int sample_if_due(lbm_ctx* c) {
     return LBM_OK;
 }
 
+// After every unit of step_many: the force sample of step count nsteps where one is due, from lat[cur], the lattice after nsteps steps.
+int sample_after_unit(lbm_ctx* c) {
+    Sampler& s = c->sampler[SMP_FORCE];
+    if (!s.due(c->nsteps)) return LBM_OK;
+    HipDev dev{c};   // (as sample_if_due)
+    int rc = c->order.one_stream(dev);
+    if (rc == LBM_OK) rc = force_series_sample(c);
+    if (rc) return rc;
+    s.advance();
+    return LBM_OK;
+}
+
 // A sampler off: what its _begin allocated freed, its schedule cleared (lbm_*_end, and whatever replaces the state: init / upload /
 // destroy).  The caller has synchronised the streams.
 void sampler_free(lbm_ctx* c, int sampler) {
@@ -123,6 +135,8 @@ void sampler_free(lbm_ctx* c, int sampler) {
         c->stats_count = 0;
     } else if (sampler == SMP_MONITOR) {
         series_free(c->mon_series);
+    } else if (sampler == SMP_FORCE) {
+        series_free(c->force_series);
     } else {
         residual_free(c);
     }

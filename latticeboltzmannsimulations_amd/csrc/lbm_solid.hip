@@ -169,6 +169,8 @@ int lbm_set_solid(lbm_ctx* c, const uint8_t* mask) {
     if (rc == LBM_OK) rc = sync_all(c);
     if (rc) return rc;
     c->solid_mask.swap(next);
+    rc = bodies_default(c);   // (one body again, whatever lbm_set_solid_bodies had set)
+    if (rc) return rc;
     return lbm_init_equilibrium(c);   // (ends every sampler; solid cells get w_k: solid_fix)
 }
 

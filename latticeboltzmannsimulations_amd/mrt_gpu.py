@@ -27,7 +27,7 @@ from . import ghia
 from . import residual as RS
 from .VTKWrapper import saveToVTK
 from .monitor import vortex_window
-from .solid import mask_from
+from .solid import labels_from, mask_from
 from .solver import CavitySolver
 from .stopping import MeanUStop, ResidualStop, by_residual, wall_model
 
@@ -56,6 +56,7 @@ class CavityResult:
         self.vortex_tables = []     # run_cavity(vortex_table=True): (iteration, CavitySolver.vortex_table()) at every output iteration
         self.residuals = []         # run_cavity(criterion="residual"): (iteration, residual record) at every output iteration after the first
         self.forces = []            # run_cavity(solid=mask): (iteration, CavitySolver.solid_force()) at every output iteration
+        self.force_series = None    # run_cavity(force_every=N): CavitySolver.force_series() of the whole run
 
 
 CS2_EFFECTIVE, CS_BULK = 0.025, 0.16     # MRT_GPU.py:350,374-376: Van Driest damping is overwritten by Cs2 = 0.025
@@ -151,8 +152,12 @@ def _vortex_lines(table, Re, xsize, ysize, uLB):
 
 
 def _check_arguments(criterion, residual_tol, residual_hits, monitor, MonitorEvery, convergence, AverageFrom, AverageEvery, BC, semantics, turb,
-                     solid=None, solid_tiles=False):
+                     solid=None, solid_tiles=False, bodies=None, force_every=None):
     """(criterion is 'residual', semantics); ValueError for an argument run_cavity cannot run with."""
+    if (bodies is not None or force_every is not None) and solid is None:
+        raise ValueError("bodies and force_every describe the obstacles of a solid mask: they need solid=... (--solid-box / --solid-file)")
+    if force_every is not None and int(force_every) < 1:
+        raise ValueError("force_every must be >= 1")
     residual = by_residual(criterion, residual_tol, residual_hits)
     if monitor not in ("host", "device"):
         raise ValueError("monitor must be 'host' or 'device'")
@@ -305,7 +310,7 @@ def run_cavity(maxIt=3000000, Re=10000.0, RT="SRT", turb=1, xsize=32 * 5, ysize=
                dtype=np.float32, semantics="mrt_gpu", device=0, quiet=False, solver_factory=None, arith="strict",
                convergence="host", vtk_correct=False, BC="EB-NEBB ", AverageFrom=None, AverageEvery=100, monitor="host",
                MonitorEvery=None, Probes=(), vortex_table=False, criterion="mean_u", residual_tol=None, residual_hits=1, solid=None,
-               solid_tiles=False):
+               solid_tiles=False, bodies=None, force_every=None):
     """Run the lid-driven cavity like MRT_GPU.py does; returns a :class:`CavityResult`.
 
     Argument names and defaults are the module constants of MRT_GPU.py:38-58.
@@ -345,9 +350,14 @@ def run_cavity(maxIt=3000000, Re=10000.0, RT="SRT", turb=1, xsize=32 * 5, ysize=
     exchange force reduced on the device, CavitySolver.solid_force() -- and appends (iteration, that record) to result.forces.  None
     (default): nothing changes.
     solid_tiles=True (with solid=...): the lattice steps three to five steps per launch on the tile kernel
-    (CavitySolver(tuning=dict(solid_tiles=True))) instead of one; the same bits."""
+    (CavitySolver(tuning=dict(solid_tiles=True))) instead of one; the same bits.
+    bodies (with solid=...): integer labels [xsize, ysize] that split the solid cells into bodies (CavitySolver(bodies=...)).
+    force_every=N (with solid=...): a series of the force and the torque on every body on the device (CavitySolver.begin_force) from
+    the first iteration on, one sample every N iterations -- step counts 1 + N, 1 + 2 N, ... -- returned as result.force_series; nothing
+    crosses PCIe before the run ends.  With SavePlot or SaveVTK, OutputFolder/force.npy holds [samples, nbodies, 6]: step, body, links,
+    fx, fy, tz.  None (default): nothing changes."""
     by_res, semantics = _check_arguments(criterion, residual_tol, residual_hits, monitor, MonitorEvery, convergence, AverageFrom,
-                                         AverageEvery, BC, semantics, turb, solid, solid_tiles)
+                                         AverageEvery, BC, semantics, turb, solid, solid_tiles, bodies, force_every)
     on_device = monitor == "device"
     say = (lambda *a: None) if quiet else print
     tstart = timer()
@@ -359,6 +369,8 @@ def run_cavity(maxIt=3000000, Re=10000.0, RT="SRT", turb=1, xsize=32 * 5, ysize=
         extra["solid"] = solid
     if solid_tiles:
         extra["tuning"] = dict(solid_tiles=True)
+    if bodies is not None:
+        extra["bodies"] = bodies
     solver = make(xsize, ysize, Re, RT=RT, uLB=uLB, semantics=semantics, dtype=dtype, turb=turb, device=device, **extra)
     _banner(say, Re, RT, turb, solver.relax)
     if (SavePlot or SaveVTK) and not os.path.isdir(OutputFolder):
@@ -399,6 +411,8 @@ def run_cavity(maxIt=3000000, Re=10000.0, RT="SRT", turb=1, xsize=32 * 5, ysize=
             if not outputs:
                 nxt = maxIt - 1
             advance(nxt - It + 1)
+            if force_every is not None and done == 0:      # (the force exists after the first step)
+                solver.begin_force(every=int(force_every), capacity=min(maxIt // int(force_every) + 1, 1 << 18))
             done = nxt + 1
             It = nxt
             if (It % Pinterval == 0) and outputs:
@@ -427,6 +441,11 @@ def run_cavity(maxIt=3000000, Re=10000.0, RT="SRT", turb=1, xsize=32 * 5, ysize=
                     say("max iterations reached. More needed for convergence.")
             It += 1
         _collect(res, solver, MonitorEvery is not None, averaging)
+        if force_every is not None:
+            res.force_series = solver.force_series()
+            if SavePlot or SaveVTK:
+                np.save(os.path.join(OutputFolder, "force.npy"),
+                        np.stack([res.force_series[k].astype(np.float64) for k in ("step", "body", "links", "fx", "fy", "tz")], axis=-1))
         res.iterations = done
         res.elapsed = timer() - tstart
         res.mlups = xsize * ysize * done * 1e-6 / res.elapsed        # as printed by MRTTiledPull.py:703
@@ -476,13 +495,18 @@ def main(argv=None):
     ap.add_argument("--solid-file", default=None, help="a .npy mask [xsize, ysize] whose nonzero cells are solid (needs --BC BB --turb 0)")
     ap.add_argument("--solid-tiles", action="store_true",
                     help="with --solid-box / --solid-file: three to five steps per launch on the tile kernel instead of one (the same bits)")
+    ap.add_argument("--force-every", type=int, default=None,
+                    help="with --solid-box / --solid-file: force and torque on every body, sampled on the device every this many iterations "
+                         "(each --solid-box is a body, in the order given; the nonzero values of an integer --solid-file are body ids, ascending)")
     a = ap.parse_args(argv)
-    mask = None
-    if a.solid_box or a.solid_file is not None or a.solid_tiles:      # an obstacle the run cannot have is an argument error, through the one check
+    mask = labels = None
+    if a.solid_box or a.solid_file is not None or a.solid_tiles or a.force_every is not None:      # an obstacle the run cannot have is an argument error, through the one check
         try:
             mask = mask_from(a.xsize, a.ysize, a.solid_box, a.solid_file)
+            if a.force_every is not None:
+                labels = labels_from(a.xsize, a.ysize, a.solid_box, a.solid_file)[1]
             _check_arguments(a.criterion, a.residual_tol, a.residual_hits, a.monitor, a.monitor_every, a.convergence, a.average_from,
-                             a.average_every, a.BC, a.semantics, a.turb, mask, a.solid_tiles)
+                             a.average_every, a.BC, a.semantics, a.turb, mask, a.solid_tiles, labels, a.force_every)
         except (ValueError, OSError) as e:
             ap.error(str(e))
     r = run_cavity(maxIt=a.maxIt, Re=a.Re, RT=a.RT, turb=a.turb, xsize=a.xsize, ysize=a.ysize, uLB=a.uLB,
@@ -491,7 +515,8 @@ def main(argv=None):
                    convergence=a.convergence, vtk_correct=a.vtk_correct, BC="BB" if a.BC == "BB" else "EB-NEBB ",
                    AverageFrom=a.average_from, AverageEvery=a.average_every, monitor=a.monitor, MonitorEvery=a.monitor_every,
                    Probes=tuple(tuple(p) for p in a.probe), vortex_table=a.vortex_table, criterion=a.criterion,
-                   residual_tol=a.residual_tol, residual_hits=a.residual_hits, solid=mask, **(dict(solid_tiles=True) if a.solid_tiles else {}))
+                   residual_tol=a.residual_tol, residual_hits=a.residual_hits, solid=mask, **(dict(solid_tiles=True) if a.solid_tiles else {}),
+                   **(dict(bodies=labels, force_every=a.force_every) if a.force_every is not None else {}))
     print("MLUPS : ", r.mlups)
     return 0
 

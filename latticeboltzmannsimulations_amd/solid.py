@@ -8,6 +8,15 @@ direction, which is what get_fields returns as fin_k of that cell, so the force 
     F = sum over links of 2 c_opp(k) fin_k(x, y),        c_opp(k) = -c_k,
 
 in the convention of u: F[1] > 0 points to the lid.  lbm_solid_force reduces the same terms on the device (CavitySolver.solid_force).
+
+BODIES.  Labels [X, Y] (integers in [0, nbodies) on the solid cells, ignored elsewhere) split the solid cells into bodies; a link
+belongs to the body of its source cell.  With the centre (x0, y0) of a body in index coordinates and the link's midpoint relative to it,
+(rx, ry) = (x - cx_k / 2 - x0, y + cy_k / 2 - y0), the torque on the body is
+
+    tz = sum over its links of rx ty + ry tx,        (tx, ty) = 2 c_opp(k) fin_k(x, y):
+
+y grows away from the lid while F[1] > 0 points to it, so this is the z-moment in the frame drawn with the lid on top, positive
+counter-clockwise.  lbm_body_force reduces the same terms per body on the device (CavitySolver.body_force, force_series).
 """
 import math
 
@@ -78,3 +87,86 @@ def host_force(fin, mask):
     (math.fsum) of force_terms."""
     tx, ty = force_terms(fin, mask)
     return dict(links=int(tx.size), fx=math.fsum(tx.tolist()), fy=math.fsum(ty.tolist()))
+
+
+def labels_from(nx, ny, boxes=(), path=None):
+    """(mask, labels, nbodies) as the command lines build them: every --solid-box is a body of its own, in the order given, and a later
+    box wins an overlap; the nonzero values of an integer --solid-file array are body ids, the distinct values in ascending order, and
+    follow the boxes (the file wins an overlap).  A file of another type is one body.  (None, None, 0) when neither is given."""
+    if not boxes and path is None:
+        return None, None, 0
+    lab = np.full((int(nx), int(ny)), -1, dtype=np.int32)
+    n = 0
+    for box in boxes:
+        lab[boxes_mask(nx, ny, [box])] = n
+        n += 1
+    if path is not None:
+        f = np.load(path, allow_pickle=False)
+        if f.shape != (nx, ny):
+            raise ValueError(f"solid file {path} holds an array of shape {f.shape}, the lattice is {(nx, ny)}")
+        ids = np.unique(f[f != 0]) if np.issubdtype(f.dtype, np.integer) else []
+        if len(ids) == 0 and np.any(f != 0):
+            lab[f != 0] = n
+            n += 1
+        for v in ids:
+            lab[f == v] = n
+            n += 1
+    return lab >= 0, lab, n
+
+
+def centroids(mask, labels, nbodies):
+    """[nbodies, 2]: the mean (x, y) of each body's cells, float64; (0, 0) for a body without cells (lbm_set_solid_bodies with
+    centre = NULL)."""
+    m = np.asarray(mask) != 0
+    lab = np.asarray(labels)
+    out = np.zeros((int(nbodies), 2))
+    xs, ys = np.nonzero(m)
+    for b in range(int(nbodies)):
+        sel = lab[xs, ys] == b
+        if sel.any():
+            out[b] = float(xs[sel].sum()) / float(sel.sum()), float(ys[sel].sum()) / float(sel.sum())
+    return out
+
+
+def body_links(mask, labels):
+    """The link list of a labelled mask as the library builds it: an int array [links, 4] of (x, y, k, body) -- the fluid cell, the slot
+    and the body of the source cell (x - cx_k, y + cy_k) -- sorted by body, then by cell in [y][x] order, then by k."""
+    lab = np.asarray(labels)
+    rows = []
+    for k, lk in enumerate(links(mask)):
+        if k == 0:
+            continue
+        x, y = np.nonzero(lk)
+        rows.append(np.stack([x, y, np.full(x.shape, k), lab[x - CX[k], y + CY[k]]], axis=1))
+    out = np.concatenate(rows).astype(np.int64)
+    return out[np.lexsort((out[:, 2], out[:, 0], out[:, 1], out[:, 3]))]
+
+
+def body_force_terms(fin, mask, labels, centres):
+    """(body, tx, ty, mx, my): per link of body_links(mask, labels) its body and, as float64, the force terms and the two products
+    rx ty and ry tx of its torque, each product rounded once."""
+    fin = np.asarray(fin)
+    centres = np.asarray(centres, dtype=np.float64)
+    ln = body_links(mask, labels)
+    x, y, k, b = ln[:, 0], ln[:, 1], ln[:, 2], ln[:, 3]
+    cx, cy, opp = np.array(CX), np.array(CY), np.array(OPP)
+    f = fin[k, x, y].astype(np.float64)
+    tx, ty = 2.0 * cx[opp[k]] * f, 2.0 * cy[opp[k]] * f
+    rx = (x.astype(np.float64) - 0.5 * cx[k]) - centres[b, 0]
+    ry = (y.astype(np.float64) + 0.5 * cy[k]) - centres[b, 1]
+    return b, tx, ty, rx * ty, ry * tx
+
+
+def host_body_force(fin, mask, labels, centres):
+    """dict(links, fx, fy, tz) of arrays [nbodies] (nbodies = len(centres)) from the populations fin[9, X, Y] that
+    get_fields(want_fin=True) returns: per body the exactly rounded sums (math.fsum) of body_force_terms."""
+    b, tx, ty, mx, my = body_force_terms(fin, mask, labels, centres)
+    n = len(centres)
+    out = dict(links=np.zeros(n, dtype=np.int64), fx=np.zeros(n), fy=np.zeros(n), tz=np.zeros(n))
+    for i in range(n):
+        sel = b == i
+        out["links"][i] = int(sel.sum())
+        out["fx"][i] = math.fsum(tx[sel].tolist())
+        out["fy"][i] = math.fsum(ty[sel].tolist())
+        out["tz"][i] = math.fsum(mx[sel].tolist() + my[sel].tolist())
+    return out

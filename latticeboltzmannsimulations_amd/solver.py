@@ -9,6 +9,7 @@ import numpy as np
 from . import _lib as L
 from . import monitor as M
 from . import residual as RS
+from . import solid as S
 from . import topology as T
 
 _DT = {np.dtype(np.float32): L.LBM_F32, np.dtype(np.float64): L.LBM_F64}
@@ -91,6 +92,8 @@ class CavitySolver:
                    step per launch (kernel 'auto' or 'generic'), no slabs.  See set_solid, solid, solid_force.  tuning=dict(solid_tiles=True):
                    three to five steps per launch on the tile kernel instead (kernel 'auto' or 'tb'; planned as plain 'bounce_back' with
                    kernel='tb' plans the same lattice; the same bits).
+    bodies       : with solid=...: integer labels of the mask's shape that split the solid cells into bodies, and `centres`, the points
+                   their torques refer to (None: the centroids).  See set_bodies, bodies, body_force, begin_force, force_series.
     tuning       : A/B switches of the launch plan, none of which changes a result: tb_steps (2..5 steps per launch; 2..8 with kernel='stream'),
                    frame_seg, and the boolean flags deep_halo, frame_fused, frame_fused_batch, frame_lds, nt, comm_priority,
                    eager_lag, frame_beside, frame_wide, edge_first, edge_reserve, xcd_bands, tail_tiles, solid_tiles (lbm_params.tb_steps / frame_seg / flags)
@@ -98,7 +101,7 @@ class CavitySolver:
 
     def __init__(self, xsize, ysize, Re, RT="MRT", uLB=0.08, semantics="mrt_gpu", dtype=np.float32, turb=0,
                  device=0, rows=None, kernel="auto", layout="auto", omega_eps=None, omega_q=None, batch=1, arith="strict",
-                 min_rows=None, tuning=None, solid=None):
+                 min_rows=None, tuning=None, solid=None, bodies=None, centres=None):
         self._h = None
         self.batch = int(batch)
         self._lead = getattr(self, "_lead", ())      # leading axes of the host arrays: (B,) for a CavityBatch
@@ -124,6 +127,8 @@ class CavitySolver:
         self.has_solid = solid is not None
         if self.has_solid and semantics != "bounce_back":
             raise ValueError("solid=... needs semantics='bounce_back'")
+        if bodies is not None and not self.has_solid:
+            raise ValueError("bodies=... labels the cells of a solid mask: it needs solid=...")
         p = _params(self.nx, self.ny, self.y0, self.ny_local, self.dtype, RT, _SEM_SOLID if self.has_solid else semantics, kernel, turb, device,
                     layout, self.batch, arith, min_rows, tuning, self.uLB, self.relax)
         err = ctypes.create_string_buffer(512)
@@ -134,6 +139,8 @@ class CavitySolver:
         if self.has_solid:
             try:
                 self.set_solid(solid)
+                if bodies is not None:
+                    self.set_bodies(bodies, centres)
             except Exception:
                 self.close()
                 raise
@@ -456,6 +463,7 @@ class CavitySolver:
         self._need_solid()
         m = self._mask(mask)
         self._check(self.lib.lbm_set_solid(self._h, m.ctypes.data), "lbm_set_solid")
+        self._bodies_given = False
         return self
 
     @property
@@ -478,6 +486,94 @@ class CavitySolver:
         out["step"], out["links"] = out["step"].astype(np.int64), out["links"].astype(np.int64)
         return out if self._lead else {k: v[0].item() for k, v in out.items()}
 
+    # -- the bodies of the mask (lbm_set_solid_bodies, lbm_get_solid_bodies, lbm_body_force, lbm_force_*) ---------
+    def set_bodies(self, labels, centres=None):
+        """Split the solid cells into bodies (lbm_set_solid_bodies): labels is an integer array of the mask's shape (one [X, Y] array
+        serves every lattice of a batch) with a value in [0, nbodies) on every solid cell, nbodies = the largest label on a solid cell
+        + 1 -- or the number of centres where they are given: [nbodies, 2] (a batch: [B, nbodies, 2]) of (x0, y0) in index
+        coordinates, the points the torques refer to; None takes each body's centroid.  Ends a running force series; the lattice and
+        the step count stay.  set_solid returns to one body that holds every solid cell."""
+        self._need_solid()
+        lab = np.asarray(labels)
+        if self._lead and lab.shape == (self.nx, self.ny):
+            lab = np.broadcast_to(lab, self._lead + lab.shape)
+        if lab.shape != self._lead + (self.nx, self.ny) or not np.issubdtype(lab.dtype, np.integer):
+            raise ValueError(f"body labels must be an integer array of shape {self._lead + (self.nx, self.ny)}")
+        lab = np.ascontiguousarray(lab, dtype=np.int32)
+        if centres is None:
+            on = lab[self.solid]
+            n, cen = (int(on.max()) + 1 if on.size else 1), None
+        else:
+            cen = np.asarray(centres, dtype=np.float64)
+            if self._lead and cen.ndim == 2:
+                cen = np.broadcast_to(cen, self._lead + cen.shape)
+            if cen.ndim != len(self._lead) + 2 or cen.shape[:-2] != self._lead or cen.shape[-1] != 2:
+                raise ValueError(f"centres must have shape {self._lead + ('nbodies', 2)}")
+            n, cen = cen.shape[-2], np.ascontiguousarray(cen)
+        self._check(self.lib.lbm_set_solid_bodies(self._h, lab.ctypes.data, n, None if cen is None else cen.ctypes.data), "lbm_set_solid_bodies")
+        self._bodies_given = True      # (a checkpoint then carries them)
+        return self
+
+    @property
+    def nbodies(self):
+        """The number of bodies (1 until set_bodies); 0 without solid=..."""
+        return int(self.lib.lbm_solid_body_count(self._h))
+
+    @property
+    def bodies(self):
+        """(labels, centres): copies of the labels, int32 [X, Y] with -1 on fluid cells, and of the centres, float64 [nbodies, 2] (a
+        batch: [B, X, Y] and [B, nbodies, 2]); None without solid=..."""
+        if not self.has_solid:
+            return None
+        lab = np.zeros(self._lead + (self.nx, self.ny), dtype=np.int32)
+        cen = np.zeros(self._lead + (self.nbodies, 2))
+        self._check(self.lib.lbm_get_solid_bodies(self._h, lab.ctypes.data, cen.ctypes.data), "lbm_get_solid_bodies")
+        return lab, cen
+
+    def _force_dict(self, rec, shape):
+        a = np.frombuffer(rec, dtype=np.float64).reshape(tuple(shape) + (6,)) if len(rec) else np.zeros(tuple(shape) + (6,))
+        out = {k: a[..., i].copy() for i, k in enumerate(("step", "body", "links", "fx", "fy", "tz"))}
+        for k in ("step", "body", "links"):
+            out[k] = out[k].astype(np.int64)
+        return out
+
+    def body_force(self):
+        """The momentum-exchange force and torque of the fluid on every body, reduced on the device from the link list
+        (lbm_body_force): dict(step, body, links, fx, fy, tz) of arrays [nbodies] (a batch: [B, nbodies]) --
+        solid.host_body_force(get_fields(want_fin=True)[2], mask, labels, centres) to the rounding of a double sum.  fy > 0 points to
+        the lid; tz > 0 turns counter-clockwise in the picture with the lid on top.  Not before the first step."""
+        self._need_solid()
+        nb = self.nbodies
+        rec = (L.lbm_body_force_record * (self.batch * nb))()
+        self._check(self.lib.lbm_body_force(self._h, rec), "lbm_body_force")
+        out = self._force_dict(rec, (self.batch, nb))
+        return out if self._lead else {k: v[0] for k, v in out.items()}
+
+    def begin_force(self, every=0, capacity=1024):
+        """Start (or restart) a series of body_force() records on the device (lbm_force_begin) with room for `capacity` samples.
+        every > 0: step() samples by itself at steps_done + every, + 2 every, ... -- each record is what body_force() returns at that
+        step count, every bit, and nothing returns to the host before force_series(); every = 0: samples through sample_force() only.
+        Samples beyond the capacity are dropped and counted.  Not before the first step."""
+        self._need_solid()
+        self._check(self.lib.lbm_force_begin(self._h, int(every), int(capacity)), "lbm_force_begin")
+        return self
+
+    def sample_force(self):
+        """Append the record body_force() would return now to the series (lbm_force_sample)."""
+        self._check(self.lib.lbm_force_sample(self._h), "lbm_force_sample")
+        return self
+
+    def force_series(self):
+        """The series so far (lbm_force_read): the keys of body_force() as arrays [count, nbodies] (a batch: [count, B, nbodies]), plus
+        count and dropped."""
+        nb = self.nbodies
+        sample = L.lbm_body_force_record * nb      # one sample of a lattice
+        return self._series(self.lib.lbm_force_read, sample, lambda rec, shape: self._force_dict(rec, shape + (nb,)))
+
+    def end_force(self):
+        """Stop the series and free its device buffer (lbm_force_end)."""
+        self._check(self.lib.lbm_force_end(self._h), "lbm_force_end")
+
     # -- checkpoint / restart (the reference has neither; SURVEY 8f item 4) -------------------
     def save_checkpoint(self, path):
         """Write the populations and the run parameters to `path` (.npz).  Restarting from it continues bit-identically
@@ -487,7 +583,8 @@ class CavitySolver:
         path = _npz(path)
         np.savez(path, fin=fin, steps_done=self.steps_done, nx=self.nx, ny=self.ny, Re=self.Re, RT=self.RT, uLB=self.uLB,
                  semantics=self.semantics, dtype=self.dtype.name, rows=np.array([self.y0, self.ny_local]), turb=self.turb, u=u, rho=rho,
-                 arith=self.arith, **(dict(solid=self.solid) if self.has_solid else {}))
+                 arith=self.arith, **(dict(solid=self.solid) if self.has_solid else {}),
+                 **(dict(zip(("body_labels", "body_centres"), self.bodies)) if getattr(self, "_bodies_given", False) else {}))
         return path
 
     def load_checkpoint(self, path, strict=True):
@@ -518,6 +615,8 @@ class CavitySolver:
                 if diff:
                     raise ValueError(f"checkpoint was written by a different run (checkpoint, this solver): {diff}")
             self.set_state(np.ascontiguousarray(z["fin"]))
+            if "body_labels" in z and self.has_solid and np.array_equal(np.asarray(z["solid"], dtype=bool), self.solid):
+                self.set_bodies(np.asarray(z["body_labels"]), np.asarray(z["body_centres"]))     # (files without them: the bodies stay)
             return int(z["steps_done"])
 
     # -- slab exchange primitives ---------------------------------------------------------

@@ -6,13 +6,16 @@
 A case is  size:dtype:arith[:key=value,...]  e.g.  4096:f32:fast   4096:f32:strict:tb_steps=4   8192x1024:f64:fast:coll=SRT,turb=1
 (keys: coll, turb, kernel, layout, sem (semantics: mrt_gpu, mrt_py, bounce_back), solid (with sem=bounce_back: fluid -- the all-fluid mask --,
 block -- one block of an eighth of the width squared in the middle --, random -- 20 % of the cells, seeded), route (with solid: single --
-one step per launch, the default -- or tiles -- the multi-step tile kernel, tuning solid_tiles), batch (that many lattices,
-GLUPS in aggregate) and every CavitySolver tuning switch).  Prints GLUPS (best of --reps timings of --steps steps
+one step per launch, the default -- or tiles -- the multi-step tile kernel, tuning solid_tiles), force (with solid: series.E -- the run
+with begin_force(every=E) --, loop.E -- the host loop step(E); solid_force() --, plain.E -- step(E); sync() without any force --, or call -- no stepping: microseconds per call of
+body_force() and of solid_force(); these three are timed with the host clock around work that ends in a synchronisation), batch (that
+many lattices, GLUPS in aggregate) and every CavitySolver tuning switch).  Prints GLUPS (best of --reps timings of --steps steps
 after a device wake-up and a warm-up), microseconds per step and the GLUPS of every repeat, one line per case.
 """
 import argparse
 import os
 import sys
+import time
 
 import numpy as np
 
@@ -55,6 +58,8 @@ def parse(case):
                 if v not in ("single", "tiles"):
                     raise ValueError("route must be single or tiles")
                 tune["solid_tiles"] = v == "tiles"
+            elif k == "force":
+                kw["force"] = v
             elif k == "batch":
                 kw["batch"] = int(v)
             elif k in ("tb_steps", "frame_seg"):
@@ -73,14 +78,47 @@ def main():
     for case in a.cases:
         nx, ny, dtype, arith, kw, tune = parse(case)
         B = kw.pop("batch", 1)
+        force = kw.pop("force", None)
         make = (lambda *a_, **k_: CavityBatch(a_[0], a_[1], [a_[2]] * B, **k_)) if B > 1 else CavitySolver
         with make(nx, ny, 1000.0, dtype=dtype, arith=arith, tuning=tune, **kw) as s:
             s.copy_bandwidth(1 << 30, 60)
             s.step(max(60, a.steps // 10)); s.sync()
-            reps = [s.time_steps(a.steps) / a.steps for _ in range(a.reps)]
+            if force == "call":
+                for name, call in (("body_force", s.body_force), ("solid_force", s.solid_force)):
+                    call()
+                    reps = []
+                    for _ in range(a.reps):
+                        t0 = time.perf_counter()
+                        for _ in range(50):
+                            call()
+                        reps.append((time.perf_counter() - t0) / 50)
+                    print(f"{case:48s} {name:12s} {min(reps) * 1e6:9.2f} us/call  repeats {' '.join('%.2f' % (r * 1e6) for r in reps)}", flush=True)
+                continue
+            if force is not None:
+                mode, every = force.split(".")
+                every = int(every)
+
+                def timed():
+                    if mode == "series":
+                        s.begin_force(every=every, capacity=a.steps // every + 1)
+                    s.sync()
+                    t0 = time.perf_counter()
+                    if mode == "series":
+                        s.step(a.steps)
+                        s.sync()
+                    else:
+                        for _ in range(a.steps // every):
+                            s.step(every)
+                            s.solid_force() if mode == "loop" else s.sync()
+                    return (time.perf_counter() - t0) * 1e3 / a.steps
+                timed()
+                reps = [timed() for _ in range(a.reps)]
+            else:
+                reps = [s.time_steps(a.steps) / a.steps for _ in range(a.reps)]
             ms = min(reps)
             print(f"{case:48s} S={s.next_unit(1000)}  {B * nx * ny / ms / 1e6:8.1f} GLUPS  {ms * 1e3:9.2f} us/step  "
-                  f"repeats {' '.join('%.1f' % (B * nx * ny / r / 1e6) for r in reps)}", flush=True)
+                  f"repeats {' '.join('%.1f' % (B * nx * ny / r / 1e6) for r in reps)}"
+                  + (f"  us/step {' '.join('%.2f' % (r * 1e3) for r in reps)}" if force else ""), flush=True)
 
 
 if __name__ == "__main__":
