@@ -462,7 +462,7 @@ int lbm_get_stream_function(lbm_ctx* c, double* psi_out, double* omega_out, int 
  * Fluid cell, slot k = 1 .. 8, source (x - cx_k, y + cy_k):
  *   source outside the lattice        exactly the LBM_SEM_BOUNCE_BACK rule, lid term included;
  *   source inside and solid           the cell's own post-collision population of the opposite direction, nothing added (obstacles
- *                                     are at rest);
+ *                                     are at rest, until lbm_set_body_motion below gives their surfaces a velocity);
  *   otherwise                         the source's post-collision population of direction k.
  *   Moments, collision, rates, the first step after an upload and the parked lid density are those of LBM_SEM_BOUNCE_BACK.
  * Solid cell: never updated.  Its populations are the constants w_k (4/9, 1/9, 1/36) rounded to the lattice type -- the rest
@@ -545,6 +545,39 @@ int lbm_force_begin(lbm_ctx* c, int every, int capacity);
 int lbm_force_sample(lbm_ctx* c);
 int lbm_force_read(lbm_ctx* c, lbm_body_force_record* records_out, int max_records, long long* count, long long* dropped);
 int lbm_force_end(lbm_ctx* c);
+
+/* --- moving bodies: a wall velocity on the surface of each body ----------------------------------- */
+/* No reference counterpart.  A body keeps its cells and its SURFACE moves: every link of body b carries Ladd's moving-wall term, the term
+ * the lid has, for the body's motion (Ux, Uy, Om) -- Ux, Uy in the components of u (Uy > 0 points to the lid), Om in radians per step,
+ * counter-clockwise positive in the frame drawn with the lid on top, the frame of tz.  Exact for a circular body that rotates; for a
+ * translating body the usual fixed-shape approximation, good for small displacements.  Bodies never change the cells they occupy.
+ *
+ * With tz's midpoint (rx, ry) = (x - cx_k / 2 - x0, y + cy_k / 2 - y0) of the link (cell (x, y), slot k) relative to the body's centre:
+ *     uwx = Ux + Om ry;  uwy = Uy + Om rx;  delta = (6 w_k) (cx_k uwx + cy_k uwy)
+ *   formed on the host in double without contraction, every product and sum rounded in the order written, 6 w_k = 2/3 (k <= 4) or 1/6
+ *   rounded once to double; rho_0 = 1 stands for the density, so delta is a constant of the link.  The result is rounded once to the
+ *   lattice type.
+ * Step: a cell stores fpost_opp(k) + delta in slot opp(k) where it stored fpost_opp(k), one add in the lattice type.  Only the cell's own
+ *   bounce reads that slot, so every gather, export and sampler is unchanged: lbm_get_fields returns the arriving population as fin_k(x, y),
+ *   and a lbm_set_state of that fin is an exact restart.  The first step after an upload stores with delta like every other step; a
+ *   motion set after n steps first shows in the store of step n + 1.
+ * Force: on a link f_in = f, the population the lattice holds, and f_out = f - delta, so lbm_solid_force, lbm_body_force and the force
+ *   series sum (tx, ty) = c_opp(k) (2 f - delta), delta the rounded value converted to double -- with delta = 0 the bits of
+ *   2 c_opp(k) f; midpoint, order of operations and tree as described above.
+ * Mass: in exact arithmetic the sum of delta over the links of a lattice is zero whenever no two touching bodies move differently and no
+ *   moving body pumps through the lattice's edge.  The call forms S = sum delta and A = sum |delta| per lattice, in double over the sorted
+ *   link list, and refuses a motion with |S| > links * 2^-52 * A: a belt on a wall (tangential motion) and a rotating ring that touches the
+ *   perimeter pass, a block on a wall with a wall-normal velocity does not.
+ *
+ * lbm_set_body_motion: motion[B][nbodies][3] = (Ux, Uy, Om) of every body; NULL means all zero.  LBM_ERR_STATE on a context of another
+ *   semantics, and for a nonzero motion on a LBM_FLAG_SOLID_TILES context (the tile kernel keeps obstacles at rest); LBM_ERR_INVALID for a
+ *   value that is not finite and for a motion the flux check refuses (the text names the net flux).  Touches neither the lattice nor the
+ *   step count and ends no sampler.  Builds the table of the deltas on the host and uploads it (there, never inside lbm_step).  An
+ *   all-zero motion frees the table: the context then launches the kernels of obstacles at rest and gives their bits.  lbm_set_solid and
+ *   lbm_set_solid_bodies reset every body to rest.  lbm_describe appends ` wall_motion=1` while a nonzero motion is set.
+ * lbm_get_body_motion: motion_out[B][nbodies][3] receives the motion as set (all zero at rest). */
+int lbm_set_body_motion(lbm_ctx* c, const double* motion);
+int lbm_get_body_motion(lbm_ctx* c, double* motion_out);
 
 /* --- slab decomposition, externally driven exchange ---------------------------------- */
 /* No reference counterpart (the reference is single-GPU, MRT_GPU.py:29).  A step of a slab

@@ -41,10 +41,12 @@ struct BodyAcc {
 // One workgroup per chunk of the list (BODY_CHUNK links of one body; grid x: the chunks of a lattice, padded to the longest of the
 // batch with empty ones; grid z: the lattice).  Lane t folds links t, t + BLK, .. of its chunk in this order; then the tree.  The
 // chunks are cut from the list alone, so a lattice's partial results are the same alone and in a batch.
-template <typename R>
-__global__ __launch_bounds__(BLK) void k_body_force(const R* __restrict__ src, Geo geo, long long bstride, const BodyLink* __restrict__ links,
-                                                    const BodyChunk* __restrict__ chunks, const double* __restrict__ centre, int nbodies,
-                                                    double* __restrict__ partial) {
+// MOVE (k_body_force_move, while a body motion is set): f_out = f - delta, so (tx, ty) = c_opp(k) (2 f - delta), delta the link's entry
+// of link_delta -- the term as the lattice adds it, a double; the midpoint, the order and the tree are the same.
+template <typename R, bool MOVE>
+__device__ __forceinline__ void body_force_chunk(const R* __restrict__ src, const Geo& geo, long long bstride, const BodyLink* __restrict__ links,
+                                                 const BodyChunk* __restrict__ chunks, const double* __restrict__ centre, int nbodies,
+                                                 double* __restrict__ partial, const double* __restrict__ link_delta) {
 #pragma clang fp contract(off)
     __shared__ double sh[BLK / RED_WAVE][BodyAcc::VALS];
     const size_t slot = (size_t)blockIdx.z * gridDim.x + blockIdx.x;
@@ -57,7 +59,15 @@ __global__ __launch_bounds__(BLK) void k_body_force(const R* __restrict__ src, G
             const BodyLink l = links[ch.begin + i];
             const int x = l.x, y = l.yk >> 4, k = l.yk & 15, o = opp(k);
             const double f = (double)src[o * geo.plane + geo.at(x, y)];
-            const double tx = (double)(2 * cxk(o)) * f, ty = (double)(2 * cyk(o)) * f;
+            double tx, ty;
+            if (MOVE) {
+                const double t = 2.0 * f - link_delta[ch.begin + i];
+                tx = (double)cxk(o) * t;
+                ty = (double)cyk(o) * t;
+            } else {
+                tx = (double)(2 * cxk(o)) * f;
+                ty = (double)(2 * cyk(o)) * f;
+            }
             const double rx = ((double)x - 0.5 * (double)cxk(k)) - x0, ry = ((double)y + 0.5 * (double)cyk(k)) - y0;
             a.links = a.links + 1.0;
             a.fx = a.fx + tx;
@@ -67,6 +77,20 @@ __global__ __launch_bounds__(BLK) void k_body_force(const R* __restrict__ src, G
     }
     red_wave(a);
     if (red_workgroup<BodyAcc, BLK / RED_WAVE>(a, sh)) red_store(partial + slot * BodyAcc::VALS, a);
+}
+
+template <typename R>
+__global__ __launch_bounds__(BLK) void k_body_force(const R* __restrict__ src, Geo geo, long long bstride, const BodyLink* __restrict__ links,
+                                                    const BodyChunk* __restrict__ chunks, const double* __restrict__ centre, int nbodies,
+                                                    double* __restrict__ partial) {
+    body_force_chunk<R, false>(src, geo, bstride, links, chunks, centre, nbodies, partial, nullptr);
+}
+
+template <typename R>
+__global__ __launch_bounds__(BLK) void k_body_force_move(const R* __restrict__ src, Geo geo, long long bstride, const BodyLink* __restrict__ links,
+                                                         const BodyChunk* __restrict__ chunks, const double* __restrict__ centre, int nbodies,
+                                                         double* __restrict__ partial, const double* __restrict__ link_delta) {
+    body_force_chunk<R, true>(src, geo, bstride, links, chunks, centre, nbodies, partial, link_delta);
 }
 
 // The final pass, one wave per body and lattice over the body's chunks: rec[z][body] = {step, body, links, fx, fy, tz}
@@ -122,6 +146,7 @@ int bodies_upload(lbm_ctx* c) {
         return fail(c, LBM_ERR_HIP, std::string("hipMemcpy(body tables): ") + hipGetErrorString(e));
     }
     bodies_free(c);
+    motion_rest(c);   // (new labels or a new mask: every body at rest again)
     c->body.base = base;
     c->body.links = (const BodyLink*)base;
     c->body.chunks = (const BodyChunk*)(base + o_chunks);
@@ -152,8 +177,12 @@ static int body_force_enqueue(lbm_ctx* c, double* rec) {
     const BodyTables& t = c->body;
     return launch_variant(c, [&](auto v) {
         using R = typename decltype(v)::R;
-        hipLaunchKernelGGL((k_body_force<R>), dim3(t.maxchunks, 1, c->plan.batch), dim3(BLK), 0, c->s_compute, (const R*)c->lat[c->cur], c->plan.geo,
-                           c->plan.bstride, t.links, t.chunks, t.centre, c->nbodies, t.partial);
+        if (c->motion.base)
+            hipLaunchKernelGGL((k_body_force_move<R>), dim3(t.maxchunks, 1, c->plan.batch), dim3(BLK), 0, c->s_compute, (const R*)c->lat[c->cur],
+                               c->plan.geo, c->plan.bstride, t.links, t.chunks, t.centre, c->nbodies, t.partial, c->motion.link_delta);
+        else
+            hipLaunchKernelGGL((k_body_force<R>), dim3(t.maxchunks, 1, c->plan.batch), dim3(BLK), 0, c->s_compute, (const R*)c->lat[c->cur], c->plan.geo,
+                               c->plan.bstride, t.links, t.chunks, t.centre, c->nbodies, t.partial);
         hipLaunchKernelGGL(k_body_force_final, dim3(c->nbodies, c->plan.batch), dim3(RED_WAVE), 0, c->s_compute, (const double*)t.partial, t.first,
                            t.maxchunks, (double)c->nsteps, rec);
     });

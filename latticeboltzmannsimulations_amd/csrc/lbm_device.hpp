@@ -562,9 +562,13 @@ __device__ __forceinline__ void gather(const R* __restrict__ src, const Geo& geo
 
 // One fused update of cell (x, y): gather -> (kept slots) -> moments -> collide -> store.
 // as / ad: addressing of the source / destination (Geo = lattice in memory, Window = LDS window of the fused frame passes).
-template <typename R, int COLL, int SEM, bool TURB, typename AS, typename AD>
+// MOVE (SEM_SOLID on a lattice in memory, k_step_generic_move of lbm_solid_move.hpp; off everywhere else): the bodies' surfaces move.  A
+// cell with links adds the delta of link k (cell_row / delta: the per-cell table of lbm_wall_motion.hpp) to its post-collision
+// population of direction opp(k) before it stores it, one add in the lattice type; no gather changes.
+template <typename R, int COLL, int SEM, bool TURB, typename AS, typename AD, bool MOVE = false>
 __device__ __forceinline__ void update_cell_a(const R* __restrict__ src, const AS& as, R* __restrict__ dst, const AD& ad, const Geo& geo,
-                                              const Relax<R>& w0, int raw, int x, int y, const R* __restrict__ lnk = nullptr) {
+                                              const Relax<R>& w0, int raw, int x, int y, const R* __restrict__ lnk = nullptr,
+                                              const int32_t* __restrict__ cell_row = nullptr, const R* __restrict__ delta = nullptr) {
     // lnk (SEM_SOLID with an LDS window as the source): plane K_LINK of the lattice, see link_word
     const int X = geo.nx, Y = geo.NY, gy = geo.y0 + y;
     if (SEM == SEM_SOLID && (link_word<R, AS>(src, as, geo, lnk, x, y) & LINK_SOLID)) return;   // a solid cell is never updated
@@ -589,6 +593,15 @@ __device__ __forceinline__ void update_cell_a(const R* __restrict__ src, const A
     if (TURB) {
         dst[K_QEQ * ad.plane + me] = q2;
         dst[K_RHO * ad.plane + me] = rho;
+    }
+    if constexpr (MOVE && SEM == SEM_SOLID) {
+        const int lw = link_word<R, AS>(src, as, geo, lnk, x, y);
+        const int row = (lw & 255) ? cell_row[(long long)y * geo.nx + x] : -1;
+        if (row >= 0) {
+#pragma unroll
+            for (int k = 1; k < Q; ++k)
+                if ((lw >> (k - 1)) & 1) out[opp(k)] = out[opp(k)] + delta[(long long)row * 8 + (k - 1)];
+        }
     }
     if (!near_edge) {
 #pragma unroll

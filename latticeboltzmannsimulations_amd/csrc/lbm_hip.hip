@@ -249,6 +249,7 @@ void lbm_destroy(lbm_ctx* c) {
     topology_free(c);
     solid_free(c);
     bodies_free(c);
+    motion_rest(c);
     if (c->stage) (void)hipFree(c->stage);
     if (c->relax_dev) (void)hipFree(c->relax_dev);
     if (c->ev_edges) (void)hipEventDestroy(c->ev_edges);

@@ -36,6 +36,7 @@
 #include "lbm_order.hpp"
 #include "lbm_bodies.hpp"
 #include "lbm_solid.hpp"  // k_step_solid, extern (compiled in lbm_solid_f32/f64.hip)
+#include "lbm_solid_move.hpp"  // k_step_solid_move, k_step_generic_move, extern (compiled in lbm_solid_move_f32/f64.hip)
 #include "lbm_inst.hpp"   // the kernels, and extern template declarations of the multi-step ones (compiled in lbm_{tiles,stream*}_f32/f64.hip)
 
 // ------------------------------------------------------------------------------------
@@ -113,6 +114,16 @@ struct BodyTables {
     int maxchunks = 1;
 };
 
+// The tables of a nonzero body motion on the device (lbm_set_body_motion), all inside the one allocation `base`: cell_row[batch][ny][nx],
+// -1 or the cell's row in delta[rows][8] (the lattice type; slot k - 1: Ladd's term of the cell's link k), and link_delta, one double per
+// entry of BodyTables::links: the same terms as the lattice adds them, for k_body_force.
+struct MotionTables {
+    void* base = nullptr;
+    const int32_t* cell_row = nullptr;
+    const void* delta = nullptr;
+    const double* link_delta = nullptr;
+};
+
 // Run state.  What was decided once is in `plan`; p stays for the fields later code branches on (dtype, collision, semantics, turb,
 // arith, device) and for the relaxation rates, which lbm_set_relaxation rewrites.
 struct lbm_ctx {
@@ -171,6 +182,11 @@ struct lbm_ctx {
     std::vector<double> body_centre;
     BodyTables body;
     Series force_series;
+    // The motion of the bodies (lbm_set_body_motion, lbm_body_motion.hip): body_motion[batch][nbodies][3] = (Ux, Uy, Om), all zero after
+    // lbm_create, lbm_set_solid and lbm_set_solid_bodies.  motion: the tables on the device, null while every body is at rest -- then the
+    // step and the force run the kernels of a lattice whose obstacles never move.
+    std::vector<double> body_motion;
+    MotionTables motion;
     ncclComm_t comm = nullptr;
     int nranks = 1, rank = 0;
     bool loopback = false;      // diagnostic: 1-rank communicator, the slab exchanges halos with itself
@@ -427,6 +443,8 @@ void solid_free(lbm_ctx* c);
 int bodies_default(lbm_ctx* c);
 void bodies_free(lbm_ctx* c);
 int force_series_sample(lbm_ctx* c);
+// lbm_body_motion.hip
+void motion_rest(lbm_ctx* c);
 // lbm_residual.hip
 int residual_series_sample(lbm_ctx* c, int which, long long step);
 void residual_free(lbm_ctx* c);

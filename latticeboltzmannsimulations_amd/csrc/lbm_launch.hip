@@ -38,6 +38,24 @@ int launch_rows(lbm_ctx* c, int from, int to, int row0, int stride, int nrows, h
         R* dst = (R*)c->lat[to];
         const int raw = c->raw[from];
         if constexpr (VT::SEM == SEM_SOLID) {
+            if (c->motion.base) {   // (a nonzero lbm_set_body_motion: the same two routes with the moving-wall term in their stores)
+                const int32_t* rows = c->motion.cell_row;
+                const R* delta = (const R*)c->motion.delta;
+                if (c->plan.use_vec) {
+                    constexpr int V = 16 / (int)sizeof(R);
+                    const int nxb = (c->plan.geo.nx / V + BLK - 1) / BLK, nblocks = nxb * nrows;
+                    if (c->plan.use_nt)
+                        hipLaunchKernelGGL((k_step_solid_move<R, VT::COLL, true>), dim3(nblocks, c->plan.batch), dim3(BLK), 0, s, src, dst, c->plan.geo,
+                                           relax_of<R>(c->p), batch_of<R>(c), raw, row0, stride, nxb, nblocks, rows, delta);
+                    else
+                        hipLaunchKernelGGL((k_step_solid_move<R, VT::COLL, false>), dim3(nblocks, c->plan.batch), dim3(BLK), 0, s, src, dst, c->plan.geo,
+                                           relax_of<R>(c->p), batch_of<R>(c), raw, row0, stride, nxb, nblocks, rows, delta);
+                } else {
+                    hipLaunchKernelGGL((k_step_generic_move<R, VT::COLL>), grid_rows(c, nrows), dim3(BLK), 0, s, src, dst, c->plan.geo, relax_of<R>(c->p),
+                                       batch_of<R>(c), raw, row0, stride, rows, delta);
+                }
+                return;
+            }
             if (c->plan.use_vec) {   // (nx a multiple of the vector width, kernel = AUTO: plan_kernel)
                 constexpr int V = 16 / (int)sizeof(R);
                 const int nxb = (c->plan.geo.nx / V + BLK - 1) / BLK, nblocks = nxb * nrows;

@@ -44,29 +44,51 @@ struct ForceAcc {
 };
 constexpr int FORCE_BLOCKS = 256;   // partial results per lattice
 
-template <typename R>
-__global__ __launch_bounds__(BLK) void k_solid_force(const R* __restrict__ src, Geo geo, long long bstride, double* __restrict__ partial) {
+// MOVE (k_solid_force_move, while a body motion is set): the surface moves, f_out = f - delta, and the term of a link is
+// c_opp(k) (2 f - delta), delta as the lattice adds it (the cell's row of the table of lbm_wall_motion.hpp) converted to double.
+template <typename R, bool MOVE>
+__device__ __forceinline__ void solid_force_cells(const R* __restrict__ src, const Geo& geo, long long bstride, double* __restrict__ partial,
+                                                  const int32_t* __restrict__ cell_row, const R* __restrict__ delta) {
 #pragma clang fp contract(off)
     __shared__ double sh[BLK / RED_WAVE][ForceAcc::VALS];
     src += blockIdx.z * bstride;
     const long long n = (long long)geo.nx * geo.ny;
+    if (MOVE) cell_row += blockIdx.z * n;
     ForceAcc a = ForceAcc::identity();
     for (long long i = (long long)blockIdx.x * BLK + threadIdx.x; i < n; i += (long long)gridDim.x * BLK) {
         const int y = (int)(i / geo.nx), x = (int)(i - (long long)y * geo.nx);
         const long long me = geo.at(x, y);
         const int lw = (int)src[K_LINK * geo.plane + me];
         if ((lw & LINK_SOLID) || !(lw & 255)) continue;
+        const long long row = MOVE ? cell_row[i] : -1;
 #pragma unroll
         for (int k = 1; k < Q; ++k)
             if ((lw >> (k - 1)) & 1) {
                 const double f = (double)src[opp(k) * geo.plane + me];
                 a.links = a.links + 1.0;
-                a.fx = a.fx + (double)(2 * cxk(opp(k))) * f;
-                a.fy = a.fy + (double)(2 * cyk(opp(k))) * f;
+                if (MOVE) {
+                    const double t = 2.0 * f - (row >= 0 ? (double)delta[row * 8 + (k - 1)] : 0.0);
+                    a.fx = a.fx + (double)cxk(opp(k)) * t;
+                    a.fy = a.fy + (double)cyk(opp(k)) * t;
+                } else {
+                    a.fx = a.fx + (double)(2 * cxk(opp(k))) * f;
+                    a.fy = a.fy + (double)(2 * cyk(opp(k))) * f;
+                }
             }
     }
     red_wave(a);
     if (red_workgroup<ForceAcc, BLK / RED_WAVE>(a, sh)) red_store(partial + ((size_t)blockIdx.z * gridDim.x + blockIdx.x) * ForceAcc::VALS, a);
+}
+
+template <typename R>
+__global__ __launch_bounds__(BLK) void k_solid_force(const R* __restrict__ src, Geo geo, long long bstride, double* __restrict__ partial) {
+    solid_force_cells<R, false>(src, geo, bstride, partial, nullptr, nullptr);
+}
+
+template <typename R>
+__global__ __launch_bounds__(BLK) void k_solid_force_move(const R* __restrict__ src, Geo geo, long long bstride, double* __restrict__ partial,
+                                                          const int32_t* __restrict__ cell_row, const R* __restrict__ delta) {
+    solid_force_cells<R, true>(src, geo, bstride, partial, cell_row, delta);
 }
 
 // The final pass, one wave per lattice: rec[z] = {step, links, fx, fy}
@@ -202,8 +224,12 @@ int lbm_solid_force(lbm_ctx* c, lbm_solid_force_record* out) {
     double* rec = c->force_dev + (size_t)B * FORCE_BLOCKS * ForceAcc::VALS;
     rc = launch_variant(c, [&](auto v) {
         using R = typename decltype(v)::R;
-        hipLaunchKernelGGL((k_solid_force<R>), dim3(FORCE_BLOCKS, 1, B), dim3(BLK), 0, c->s_compute, (const R*)c->lat[c->cur], c->plan.geo,
-                           c->plan.bstride, c->force_dev);
+        if (c->motion.base)
+            hipLaunchKernelGGL((k_solid_force_move<R>), dim3(FORCE_BLOCKS, 1, B), dim3(BLK), 0, c->s_compute, (const R*)c->lat[c->cur], c->plan.geo,
+                               c->plan.bstride, c->force_dev, c->motion.cell_row, (const R*)c->motion.delta);
+        else
+            hipLaunchKernelGGL((k_solid_force<R>), dim3(FORCE_BLOCKS, 1, B), dim3(BLK), 0, c->s_compute, (const R*)c->lat[c->cur], c->plan.geo,
+                               c->plan.bstride, c->force_dev);
         hipLaunchKernelGGL(k_solid_force_final, dim3(B), dim3(RED_WAVE), 0, c->s_compute, (const double*)c->force_dev, FORCE_BLOCKS,
                            (double)c->nsteps, rec);
     });

@@ -1,0 +1,80 @@
+// lbm_wall_motion.hpp -- the wall velocity of moving bodies (lbm_set_body_motion; contract in include/lbm.h): Ladd's term
+// of every link of the list of lbm_bodies.hpp, its sums for the flux check, and the per-cell table the step kernels read.  Arrays are in
+// the host layout of the mask, [nx][ny] with y fastest, one lattice at a time.  Plain C++, nothing from HIP: tests/test_body_motion_cpu.py
+// drives it from a program of its own.
+#pragma once
+#include <cmath>
+#include <cstddef>
+#include <cstdint>
+#include <vector>
+
+#include "lbm_bodies.hpp"
+
+// every product and every sum below is rounded on its own: no fused multiply-add, whatever the compiler's default
+#if defined(__clang__)
+#define LBM_WM_NO_CONTRACT _Pragma("clang fp contract(off)")
+#define LBM_WM_ATTR
+#elif defined(__GNUC__)
+#define LBM_WM_NO_CONTRACT
+#define LBM_WM_ATTR __attribute__((optimize("fp-contract=off")))
+#else
+#define LBM_WM_NO_CONTRACT
+#define LBM_WM_ATTR
+#endif
+
+namespace lbmhost {
+
+// delta of the link (cell (x, y), slot k) of a body with the centre (x0, y0) and the motion (Ux, Uy, Om): 6 w_k (c_k . u_w) at rho_0 = 1,
+// u_w the body's velocity at the link's midpoint -- the midpoint of tz, (rx, ry) = (x - cx_k / 2 - x0, y + cy_k / 2 - y0):
+//     uwx = Ux + Om ry;  uwy = Uy + Om rx;  delta = (6 w_k) (cx_k uwx + cy_k uwy),        6 w_k = 2/3 (k <= 4) or 1/6, rounded once.
+// Ux, Uy in the components of u (Uy > 0 points to the lid); Om counter-clockwise positive in the frame drawn with the lid on top.
+LBM_WM_ATTR inline double wall_delta(int x, int y, int k, double x0, double y0, double Ux, double Uy, double Om) {
+    LBM_WM_NO_CONTRACT
+    const double rx = ((double)x - 0.5 * (double)BODY_CX[k]) - x0, ry = ((double)y + 0.5 * (double)BODY_CY[k]) - y0;
+    const double uwx = Ux + Om * ry, uwy = Uy + Om * rx;
+    const double w6 = k < 5 ? 2.0 / 3.0 : 1.0 / 6.0;
+    return w6 * ((double)BODY_CX[k] * uwx + (double)BODY_CY[k] * uwy);
+}
+
+// delta as the lattice holds it: rounded once to the lattice type, then a double again (what the force subtracts)
+inline double wall_delta_rounded(double d, bool f32) { return f32 ? (double)(float)d : d; }
+
+// What lbm_set_body_motion derives for one lattice.
+struct WallMotion {
+    std::vector<double> delta;      // per link, in the order of the list, in double (not yet rounded to the lattice type)
+    double S = 0.0, A = 0.0;        // sum of delta and of |delta| over the list, in its order: the net flux through the links and its scale
+    std::vector<int32_t> cell_row;  // [ny][nx], x fastest (as the lattice's rows): -1, or the row of the cell in `rows`
+    std::vector<double> rows;       // [rows][8]: slot k - 1 holds the delta of the cell's link k, 0 where it has none
+};
+
+// links[start[0] .. start[nbodies]) of one lattice (body_links), centre[nbodies][2], motion[nbodies][3] = (Ux, Uy, Om).  row_base: the
+// rows of this lattice follow that many rows of the lattices before it (a batch shares one table).
+LBM_WM_ATTR inline WallMotion wall_motion(const std::vector<BodyLink>& links, const long long* start, int nx, int ny, int nbodies, const double* centre,
+                                          const double* motion, long long row_base = 0) {
+    LBM_WM_NO_CONTRACT
+    WallMotion m;
+    m.delta.resize((size_t)(start[nbodies] - start[0]));
+    m.cell_row.assign((size_t)nx * ny, -1);
+    long long nrows = 0;
+    for (int b = 0; b < nbodies; ++b)
+        for (long long i = start[b]; i < start[b + 1]; ++i) {
+            const int x = links[(size_t)i].x, y = links[(size_t)i].yk >> 4, k = links[(size_t)i].yk & 15;
+            const double d = wall_delta(x, y, k, centre[2 * b], centre[2 * b + 1], motion[3 * b], motion[3 * b + 1], motion[3 * b + 2]);
+            m.delta[(size_t)(i - start[0])] = d;
+            m.S = m.S + d;
+            m.A = m.A + std::fabs(d);
+            int32_t& row = m.cell_row[(size_t)y * nx + x];
+            if (row < 0) {
+                row = (int32_t)(row_base + nrows++);
+                m.rows.resize((size_t)nrows * 8, 0.0);
+            }
+            m.rows[(size_t)(row - row_base) * 8 + (k - 1)] = d;
+        }
+    return m;
+}
+
+// The flux check: in exact arithmetic S = 0 whenever no two touching bodies move differently and no moving body pumps through the
+// lattice's edge (the discrete divergence theorem); the rounding of the sum stays below links * 2^-52 * A, and one leaking link is a
+// whole delta.  True: the motion conserves the lattice's mass.
+inline bool wall_motion_closed(const WallMotion& m) { return !(std::fabs(m.S) > (double)m.delta.size() * 0x1p-52 * m.A); }
+}  // namespace lbmhost

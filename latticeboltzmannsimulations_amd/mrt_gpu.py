@@ -152,10 +152,18 @@ def _vortex_lines(table, Re, xsize, ysize, uLB):
 
 
 def _check_arguments(criterion, residual_tol, residual_hits, monitor, MonitorEvery, convergence, AverageFrom, AverageEvery, BC, semantics, turb,
-                     solid=None, solid_tiles=False, bodies=None, force_every=None):
+                     solid=None, solid_tiles=False, bodies=None, force_every=None, body_motion=None):
     """(criterion is 'residual', semantics); ValueError for an argument run_cavity cannot run with."""
     if (bodies is not None or force_every is not None) and solid is None:
         raise ValueError("bodies and force_every describe the obstacles of a solid mask: they need solid=... (--solid-box / --solid-file)")
+    if body_motion is not None:
+        if solid is None:
+            raise ValueError("body_motion moves the obstacles of a solid mask: it needs solid=... (--solid-box / --solid-file)")
+        m = np.asarray(body_motion, dtype=np.float64)
+        if m.ndim != 2 or m.shape[1] != 3 or not np.all(np.isfinite(m)):
+            raise ValueError("body_motion must be a finite array [nbodies, 3] of (Ux, Uy, Omega)")
+        if solid_tiles and np.any(m):
+            raise ValueError("body_motion needs one step per launch: the tile kernel (solid_tiles) keeps obstacles at rest")
     if force_every is not None and int(force_every) < 1:
         raise ValueError("force_every must be >= 1")
     residual = by_residual(criterion, residual_tol, residual_hits)
@@ -310,7 +318,7 @@ def run_cavity(maxIt=3000000, Re=10000.0, RT="SRT", turb=1, xsize=32 * 5, ysize=
                dtype=np.float32, semantics="mrt_gpu", device=0, quiet=False, solver_factory=None, arith="strict",
                convergence="host", vtk_correct=False, BC="EB-NEBB ", AverageFrom=None, AverageEvery=100, monitor="host",
                MonitorEvery=None, Probes=(), vortex_table=False, criterion="mean_u", residual_tol=None, residual_hits=1, solid=None,
-               solid_tiles=False, bodies=None, force_every=None):
+               solid_tiles=False, bodies=None, force_every=None, body_motion=None):
     """Run the lid-driven cavity like MRT_GPU.py does; returns a :class:`CavityResult`.
 
     Argument names and defaults are the module constants of MRT_GPU.py:38-58.
@@ -355,9 +363,11 @@ def run_cavity(maxIt=3000000, Re=10000.0, RT="SRT", turb=1, xsize=32 * 5, ysize=
     force_every=N (with solid=...): a series of the force and the torque on every body on the device (CavitySolver.begin_force) from
     the first iteration on, one sample every N iterations -- step counts 1 + N, 1 + 2 N, ... -- returned as result.force_series; nothing
     crosses PCIe before the run ends.  With SavePlot or SaveVTK, OutputFolder/force.npy holds [samples, nbodies, 6]: step, body, links,
-    fx, fy, tz.  None (default): nothing changes."""
+    fx, fy, tz.  None (default): nothing changes.
+    body_motion (with solid=...): [nbodies, 3] of (Ux, Uy, Omega), the wall velocity on the surface of every body
+    (CavitySolver.set_body_motion) from the first iteration on: the bodies keep their cells.  None (default): obstacles at rest."""
     by_res, semantics = _check_arguments(criterion, residual_tol, residual_hits, monitor, MonitorEvery, convergence, AverageFrom,
-                                         AverageEvery, BC, semantics, turb, solid, solid_tiles, bodies, force_every)
+                                         AverageEvery, BC, semantics, turb, solid, solid_tiles, bodies, force_every, body_motion)
     on_device = monitor == "device"
     say = (lambda *a: None) if quiet else print
     tstart = timer()
@@ -373,6 +383,12 @@ def run_cavity(maxIt=3000000, Re=10000.0, RT="SRT", turb=1, xsize=32 * 5, ysize=
         extra["bodies"] = bodies
     solver = make(xsize, ysize, Re, RT=RT, uLB=uLB, semantics=semantics, dtype=dtype, turb=turb, device=device, **extra)
     _banner(say, Re, RT, turb, solver.relax)
+    if body_motion is not None:
+        try:
+            solver.set_body_motion(np.asarray(body_motion, dtype=np.float64))
+        except Exception:
+            solver.close()
+            raise
     if (SavePlot or SaveVTK) and not os.path.isdir(OutputFolder):
         try:
             os.makedirs(OutputFolder)
@@ -498,15 +514,25 @@ def main(argv=None):
     ap.add_argument("--force-every", type=int, default=None,
                     help="with --solid-box / --solid-file: force and torque on every body, sampled on the device every this many iterations "
                          "(each --solid-box is a body, in the order given; the nonzero values of an integer --solid-file are body ids, ascending)")
+    ap.add_argument("--body-motion", type=float, nargs=4, action="append", default=[], metavar=("BODY", "UX", "UY", "OMEGA"),
+                    help="with --solid-box / --solid-file: the surface of body BODY moves with the velocity (UX, UY) and turns with OMEGA radians "
+                         "per iteration, counter-clockwise with the lid on top, about the body's centroid; the body keeps its cells (repeatable; "
+                         "bodies as for --force-every; not with --solid-tiles)")
     a = ap.parse_args(argv)
-    mask = labels = None
-    if a.solid_box or a.solid_file is not None or a.solid_tiles or a.force_every is not None:      # an obstacle the run cannot have is an argument error, through the one check
+    mask = labels = motion = None
+    if a.solid_box or a.solid_file is not None or a.solid_tiles or a.force_every is not None or a.body_motion:      # an obstacle the run cannot have is an argument error, through the one check
         try:
             mask = mask_from(a.xsize, a.ysize, a.solid_box, a.solid_file)
-            if a.force_every is not None:
-                labels = labels_from(a.xsize, a.ysize, a.solid_box, a.solid_file)[1]
+            if a.force_every is not None or a.body_motion:
+                labels, nbodies = labels_from(a.xsize, a.ysize, a.solid_box, a.solid_file)[1:]
+            if a.body_motion:
+                motion = np.zeros((max(nbodies, 1), 3))
+                for b, ux, uy, om in a.body_motion:
+                    if mask is not None and (b != int(b) or not 0 <= int(b) < nbodies):
+                        raise ValueError(f"--body-motion names body {b:g}, the mask has the bodies 0 .. {nbodies - 1}")
+                    motion[int(b) if mask is not None else 0] = ux, uy, om
             _check_arguments(a.criterion, a.residual_tol, a.residual_hits, a.monitor, a.monitor_every, a.convergence, a.average_from,
-                             a.average_every, a.BC, a.semantics, a.turb, mask, a.solid_tiles, labels, a.force_every)
+                             a.average_every, a.BC, a.semantics, a.turb, mask, a.solid_tiles, labels, a.force_every, motion)
         except (ValueError, OSError) as e:
             ap.error(str(e))
     r = run_cavity(maxIt=a.maxIt, Re=a.Re, RT=a.RT, turb=a.turb, xsize=a.xsize, ysize=a.ysize, uLB=a.uLB,
@@ -516,7 +542,9 @@ def main(argv=None):
                    AverageFrom=a.average_from, AverageEvery=a.average_every, monitor=a.monitor, MonitorEvery=a.monitor_every,
                    Probes=tuple(tuple(p) for p in a.probe), vortex_table=a.vortex_table, criterion=a.criterion,
                    residual_tol=a.residual_tol, residual_hits=a.residual_hits, solid=mask, **(dict(solid_tiles=True) if a.solid_tiles else {}),
-                   **(dict(bodies=labels, force_every=a.force_every) if a.force_every is not None else {}))
+                   **(dict(bodies=labels) if a.force_every is not None or motion is not None else {}),
+                   **(dict(force_every=a.force_every) if a.force_every is not None else {}),
+                   **(dict(body_motion=motion) if motion is not None else {}))
     print("MLUPS : ", r.mlups)
     return 0
 

@@ -68,24 +68,30 @@ def links(mask):
     return out
 
 
-def force_terms(fin, mask):
+def force_terms(fin, mask, delta=None):
     """(tx, ty): the terms 2 cx_opp(k) fin_k and 2 cy_opp(k) fin_k of every link as float64 arrays [links], slots k = 1 .. 8 in order;
-    the zero terms of the axis-aligned slots are kept, so both have one entry per link."""
+    the zero terms of the axis-aligned slots are kept, so both have one entry per link.  delta (wall_delta_field, bodies in motion):
+    the terms are c_opp(k) (2 fin_k - delta_k) instead."""
     fin = np.asarray(fin)
     tx, ty = [], []
     for k, lk in enumerate(links(mask)):
         if k == 0:
             continue
         f = fin[k][lk].astype(np.float64)
-        tx.append(2.0 * CX[OPP[k]] * f)
-        ty.append(2.0 * CY[OPP[k]] * f)
+        if delta is None:
+            tx.append(2.0 * CX[OPP[k]] * f)
+            ty.append(2.0 * CY[OPP[k]] * f)
+        else:
+            t = 2.0 * f - np.asarray(delta, dtype=np.float64)[k][lk]
+            tx.append(float(CX[OPP[k]]) * t)
+            ty.append(float(CY[OPP[k]]) * t)
     return np.concatenate(tx), np.concatenate(ty)
 
 
-def host_force(fin, mask):
+def host_force(fin, mask, delta=None):
     """dict(links, fx, fy) from the populations fin[9, X, Y] that get_fields returns and the mask: the exactly rounded sums
-    (math.fsum) of force_terms."""
-    tx, ty = force_terms(fin, mask)
+    (math.fsum) of force_terms.  delta: wall_delta_field(...) while the bodies move (CavitySolver.set_body_motion)."""
+    tx, ty = force_terms(fin, mask, delta)
     return dict(links=int(tx.size), fx=math.fsum(tx.tolist()), fy=math.fsum(ty.tolist()))
 
 
@@ -142,25 +148,58 @@ def body_links(mask, labels):
     return out[np.lexsort((out[:, 2], out[:, 0], out[:, 1], out[:, 3]))]
 
 
-def body_force_terms(fin, mask, labels, centres):
+def wall_deltas(mask, labels, centres, motion, dtype=None):
+    """(links, delta): body_links(mask, labels) and, per link, Ladd's moving-wall term of lbm_set_body_motion as a float64 array:
+    with motion[nbodies, 3] = (Ux, Uy, Om) of the link's body and its midpoint relative to the body's centre,
+        uwx = Ux + Om ry;  uwy = Uy + Om rx;  delta = (6 w_k) (cx_k uwx + cy_k uwy),        6 w_k = 2/3 (k <= 4) or 1/6,
+    every product and sum rounded in this order.  dtype: the lattice type, to which the library rounds the term once (the value it adds,
+    and the one the force subtracts); None leaves the double."""
+    centres = np.asarray(centres, dtype=np.float64)
+    motion = np.asarray(motion, dtype=np.float64)
+    ln = body_links(mask, labels)
+    x, y, k, b = ln[:, 0], ln[:, 1], ln[:, 2], ln[:, 3]
+    cx, cy = np.array(CX, dtype=np.float64), np.array(CY, dtype=np.float64)
+    rx = (x.astype(np.float64) - 0.5 * cx[k]) - centres[b, 0]
+    ry = (y.astype(np.float64) + 0.5 * cy[k]) - centres[b, 1]
+    uwx = motion[b, 0] + motion[b, 2] * ry
+    uwy = motion[b, 1] + motion[b, 2] * rx
+    d = np.where(k < 5, 2.0 / 3.0, 1.0 / 6.0) * (cx[k] * uwx + cy[k] * uwy)
+    return ln, (d if dtype is None else d.astype(dtype).astype(np.float64))
+
+
+def wall_delta_field(mask, labels, centres, motion, dtype=None):
+    """delta[9, X, Y], float64: wall_deltas at (k, x, y) of every link, zero elsewhere -- what host_force and host_body_force take."""
+    ln, d = wall_deltas(mask, labels, centres, motion, dtype)
+    out = np.zeros((9,) + np.asarray(mask).shape)
+    out[ln[:, 2], ln[:, 0], ln[:, 1]] = d
+    return out
+
+
+def body_force_terms(fin, mask, labels, centres, delta=None):
     """(body, tx, ty, mx, my): per link of body_links(mask, labels) its body and, as float64, the force terms and the two products
-    rx ty and ry tx of its torque, each product rounded once."""
+    rx ty and ry tx of its torque, each product rounded once.  delta (wall_delta_field, bodies in motion): (tx, ty) =
+    c_opp(k) (2 fin_k - delta_k)."""
     fin = np.asarray(fin)
     centres = np.asarray(centres, dtype=np.float64)
     ln = body_links(mask, labels)
     x, y, k, b = ln[:, 0], ln[:, 1], ln[:, 2], ln[:, 3]
     cx, cy, opp = np.array(CX), np.array(CY), np.array(OPP)
     f = fin[k, x, y].astype(np.float64)
-    tx, ty = 2.0 * cx[opp[k]] * f, 2.0 * cy[opp[k]] * f
+    if delta is None:
+        tx, ty = 2.0 * cx[opp[k]] * f, 2.0 * cy[opp[k]] * f
+    else:
+        t = 2.0 * f - np.asarray(delta, dtype=np.float64)[k, x, y]
+        tx, ty = cx[opp[k]].astype(np.float64) * t, cy[opp[k]].astype(np.float64) * t
     rx = (x.astype(np.float64) - 0.5 * cx[k]) - centres[b, 0]
     ry = (y.astype(np.float64) + 0.5 * cy[k]) - centres[b, 1]
     return b, tx, ty, rx * ty, ry * tx
 
 
-def host_body_force(fin, mask, labels, centres):
+def host_body_force(fin, mask, labels, centres, delta=None):
     """dict(links, fx, fy, tz) of arrays [nbodies] (nbodies = len(centres)) from the populations fin[9, X, Y] that
-    get_fields(want_fin=True) returns: per body the exactly rounded sums (math.fsum) of body_force_terms."""
-    b, tx, ty, mx, my = body_force_terms(fin, mask, labels, centres)
+    get_fields(want_fin=True) returns: per body the exactly rounded sums (math.fsum) of body_force_terms.  delta:
+    wall_delta_field(...) while the bodies move."""
+    b, tx, ty, mx, my = body_force_terms(fin, mask, labels, centres, delta)
     n = len(centres)
     out = dict(links=np.zeros(n, dtype=np.int64), fx=np.zeros(n), fy=np.zeros(n), tz=np.zeros(n))
     for i in range(n):

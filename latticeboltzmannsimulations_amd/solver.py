@@ -463,7 +463,7 @@ class CavitySolver:
         self._need_solid()
         m = self._mask(mask)
         self._check(self.lib.lbm_set_solid(self._h, m.ctypes.data), "lbm_set_solid")
-        self._bodies_given = False
+        self._bodies_given = self._motion_given = False
         return self
 
     @property
@@ -511,7 +511,7 @@ class CavitySolver:
                 raise ValueError(f"centres must have shape {self._lead + ('nbodies', 2)}")
             n, cen = cen.shape[-2], np.ascontiguousarray(cen)
         self._check(self.lib.lbm_set_solid_bodies(self._h, lab.ctypes.data, n, None if cen is None else cen.ctypes.data), "lbm_set_solid_bodies")
-        self._bodies_given = True      # (a checkpoint then carries them)
+        self._bodies_given, self._motion_given = True, False      # (a checkpoint then carries them; every body is at rest again)
         return self
 
     @property
@@ -574,6 +574,39 @@ class CavitySolver:
         """Stop the series and free its device buffer (lbm_force_end)."""
         self._check(self.lib.lbm_force_end(self._h), "lbm_force_end")
 
+    # -- moving bodies (lbm_set_body_motion, lbm_get_body_motion) --------------------------------------
+    def set_body_motion(self, motion):
+        """Give the surface of every body a wall velocity (lbm_set_body_motion): motion is [nbodies, 3] (a batch: [B, nbodies, 3], or
+        [nbodies, 3] for every lattice) of (Ux, Uy, Om) -- Ux, Uy in the components of u, Om in radians per step, counter-clockwise
+        positive in the picture with the lid on top, about the body's centre (set_bodies).  None, or all zero: every body at rest, the
+        kernels and the bits of obstacles at rest.  The bodies keep their cells; every link carries Ladd's moving-wall term from the next
+        step on.  The lattice, the step count and the samplers stay.  A motion that would pump mass through a wall, or between two touching
+        bodies, is refused.  set_solid and set_bodies return every body to rest."""
+        self._need_solid()
+        if motion is None:
+            self._check(self.lib.lbm_set_body_motion(self._h, None), "lbm_set_body_motion")
+            self._motion_given = False
+            return self
+        m = np.asarray(motion, dtype=np.float64)
+        nb = self.nbodies
+        if self._lead and m.shape == (nb, 3):
+            m = np.broadcast_to(m, self._lead + m.shape)
+        if m.shape != self._lead + (nb, 3):
+            raise ValueError(f"body motion must have shape {self._lead + (nb, 3)}: (Ux, Uy, Om) of every body")
+        m = np.ascontiguousarray(m)
+        self._check(self.lib.lbm_set_body_motion(self._h, m.ctypes.data), "lbm_set_body_motion")
+        self._motion_given = bool(np.any(m))      # (a checkpoint then carries it)
+        return self
+
+    @property
+    def body_motion(self):
+        """A copy of the motion of the bodies, float64 [nbodies, 3] (a batch: [B, nbodies, 3]), all zero at rest; None without solid=..."""
+        if not self.has_solid:
+            return None
+        m = np.zeros(self._lead + (self.nbodies, 3))
+        self._check(self.lib.lbm_get_body_motion(self._h, m.ctypes.data), "lbm_get_body_motion")
+        return m
+
     # -- checkpoint / restart (the reference has neither; SURVEY 8f item 4) -------------------
     def save_checkpoint(self, path):
         """Write the populations and the run parameters to `path` (.npz).  Restarting from it continues bit-identically
@@ -584,8 +617,18 @@ class CavitySolver:
         np.savez(path, fin=fin, steps_done=self.steps_done, nx=self.nx, ny=self.ny, Re=self.Re, RT=self.RT, uLB=self.uLB,
                  semantics=self.semantics, dtype=self.dtype.name, rows=np.array([self.y0, self.ny_local]), turb=self.turb, u=u, rho=rho,
                  arith=self.arith, **(dict(solid=self.solid) if self.has_solid else {}),
-                 **(dict(zip(("body_labels", "body_centres"), self.bodies)) if getattr(self, "_bodies_given", False) else {}))
+                 **{**(dict(zip(("body_labels", "body_centres"), self.bodies)) if getattr(self, "_bodies_given", False) else {}),
+                    **self._motion_entry()})
         return path
+
+    def _motion_entry(self):
+        """What a checkpoint says of the bodies' motion: nothing at rest (the file of a run without it is what it was), else the
+        motion with the labels and centres it refers to."""
+        if not getattr(self, "_motion_given", False):
+            return {}
+        m = self.body_motion
+        lab, cen = self.bodies
+        return dict(body_motion=m, body_labels=lab, body_centres=cen)
 
     def load_checkpoint(self, path, strict=True):
         """Upload the populations of a checkpoint written by save_checkpoint; returns the number of steps the checkpointed
@@ -617,6 +660,8 @@ class CavitySolver:
             self.set_state(np.ascontiguousarray(z["fin"]))
             if "body_labels" in z and self.has_solid and np.array_equal(np.asarray(z["solid"], dtype=bool), self.solid):
                 self.set_bodies(np.asarray(z["body_labels"]), np.asarray(z["body_centres"]))     # (files without them: the bodies stay)
+                if "body_motion" in z:
+                    self.set_body_motion(np.asarray(z["body_motion"]))
             return int(z["steps_done"])
 
     # -- slab exchange primitives ---------------------------------------------------------

@@ -1,0 +1,287 @@
+"""GPU tests of the wall velocity on solid bodies (CavitySolver.set_body_motion, lbm_set_body_motion): strict arithmetic bit for bit
+against the NumPy reference tests/moving_wall_ref.py on the vector kernel (k_step_solid_move) and the generic route
+(k_step_generic_move); zero motion gives the bits and the kernels of obstacles at rest; `fast` arithmetic within the bound of a mask at
+rest; batches; the force with 2 f - delta, one-shot, as a series and summed; the error paths; the checkpoint; and Taylor-Couette flow
+between a rotating disc and a ring at rest against its closed form."""
+import os
+import sys
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+from moving_wall_ref import MovingWallOracle  # noqa: E402
+from solid_ref import SolidOracle  # noqa: E402
+from test_body_motion_cpu import TC_FACTOR, TC_N, TC_PROFILE_ERR, TC_RE, TC_STEPS, TC_TORQUE_ERR, tc_case, tc_errors  # noqa: E402
+from latticeboltzmannsimulations_amd import CavityBatch, CavitySolver, solid  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+BB = dict(semantics="bounce_back")
+# the bound tests/test_solid_gpu.py::test_fast_arithmetic uses for a mask at rest (FAST_BOUND of tests/test_bounce_back_gpu.py): relative
+# distance of `fast` from strict fp64 after 2000 steps of 128 x 96 at Re 1000.  The moving-wall term is one more exact constant per link.
+FAST_BOUND = {np.float32: 1.2e-4, np.float64: 6e-14}
+
+
+def _cases(nx, ny, seed=11):
+    """name -> (mask, labels, motion [nbodies, 3]): what the store-side add can get wrong.  Rows are placed relative to ny, so that the
+    cases exist on the 8-row lattices; every motion passes the flux check."""
+    y0, y1 = max(1, ny // 4), min(ny - 1, ny // 4 + 6)
+    z = lambda: (np.zeros((nx, ny), dtype=bool), np.zeros((nx, ny), dtype=np.int32))  # noqa: E731
+    out = {}
+    m, lab = z(); m[nx // 2, ny // 2] = True                                        # one cell, turning and sliding
+    out["cell"] = (m, lab, [[0.02, -0.01, 0.03]])
+    m, lab = z()                                                                    # blocks whose edges fall on x = 3 and x = 0 (mod V) and,
+    m[19:25, y0:y1] = True                                                          # on the wide lattices, across the seams between two
+    for seam in (512, 1024):                                                        # workgroups' cells; one body about its centroid
+        if nx > seam + 4:
+            m[seam - 5:seam + 5, y0:y1] = True
+    out["block"] = (m, lab, [[0.01, 0.02, 0.02 / nx]])
+    m, lab = z()                                                                    # a fluid cell linked to two bodies of different motion
+    m[20:23, y0:y1] = True
+    m[24:27, y0:y1] = True; lab[24:27, y0:y1] = 1
+    out["between"] = (m, lab, [[0.03, 0.0, 0.01], [-0.02, 0.01, -0.02]])
+    m, lab = z()                                                                    # a belt on the left wall and one in the lid row: tangential
+    m[0:2, y0:y1] = True
+    m[nx // 3:nx // 3 + 9, 0] = True; lab[nx // 3:nx // 3 + 9, 0] = 1
+    out["belts"] = (m, lab, [[0.0, 0.04, 0.0], [-0.03, 0.0, 0.0]])
+    m, lab = z()                                                                    # interior random 20 %, one cell clear of the perimeter, as
+    m[1:-1, 1:-1] = np.random.default_rng(seed).random((nx - 2, ny - 2)) < 0.2      # one body that rotates about its centroid
+    out["random"] = (m, lab, [[0.0, 0.0, 0.04 / nx]])
+    return out
+
+
+def _same(s, o, what):
+    u, rho, fin = s.get_fields(want_fin=True)
+    assert np.isfinite(fin).all(), f"{what}: not finite"
+    assert np.array_equal(fin, o.fin), f"{what}: fin differs in {np.count_nonzero(fin != o.fin)} values, max abs {np.abs(fin - o.fin).max()}"
+    assert np.array_equal(rho, o.rho) and np.array_equal(u, o.u), f"{what}: u or rho differs"
+    return fin
+
+
+def _same_fields(a, b, what):
+    for x, y, name in zip(a.get_fields(want_fin=True), b.get_fields(want_fin=True), ("u", "rho", "fin")):
+        assert np.array_equal(x, y), f"{what}: {name} differs"
+
+
+# 72 x 40: one partial workgroup; 70 x 66: the generic route in fp32 (70 is no multiple of 4); 1032 x 8 and (fp64) 520 x 8: the seams
+SHAPES = {np.float32: [(72, 40), (70, 66), (1032, 8)], np.float64: [(72, 40), (70, 66), (1032, 8), (520, 8)]}
+CASES = [(c, d, s) for d in (np.float32, np.float64) for c in ("SRT", "TRT", "MRT") for s in SHAPES[d]]
+
+
+@pytest.mark.parametrize("coll,dtype,shape", CASES, ids=lambda v: v if isinstance(v, str) else (f"{v[0]}x{v[1]}" if isinstance(v, tuple) else np.dtype(v).name))
+def test_strict_bit_identical_to_reference(coll, dtype, shape):
+    """After 1, 2, 7 and 37 steps from set_solid's state, then from a set_state of the developed one (an exact restart: the host array
+    is what get_fields returned); then a motion changed between two step calls; the default route and kernel='generic' against the
+    reference and against each other."""
+    nx, ny = shape
+    V = 4 if dtype == np.float32 else 2
+    with CavitySolver(nx, ny, 100.0, RT=coll, dtype=dtype, solid=np.zeros(shape, bool), **BB) as s, \
+            CavitySolver(nx, ny, 100.0, RT=coll, dtype=dtype, kernel="generic", solid=np.zeros(shape, bool), **BB) as g:
+        for name, (m, lab, mot) in _cases(nx, ny).items():
+            o = MovingWallOracle(nx, ny, 100.0, mask=m, labels=lab, motion=mot, collision=coll, dtype=dtype)
+            assert o.closed(), name
+            for x in (s, g):
+                x.set_solid(m).set_bodies(lab)
+                assert not x.body_motion.any() and "wall_motion" not in x.describe()
+                x.set_body_motion(mot)
+                assert np.array_equal(x.body_motion, np.asarray(mot)) and x.describe()["wall_motion"] == 1 and x.steps_done == 0
+            assert s.describe()["kernel"] == ("k_step_solid" if nx % V == 0 else "k_step_generic")
+            for phase in range(2):
+                if phase:
+                    f = o.fin.copy()
+                    o.set_state(f)
+                    s.set_state(f); g.set_state(f)
+                for n in (1, 1, 5, 30):
+                    s.step(n); g.step(n); o.step(n)
+                    what = f"{nx}x{ny} {coll} {np.dtype(dtype).name} case {name} phase {phase} after {o.nsteps}"
+                    fin = _same(s, o, what)
+                    _same_fields(g, s, what + " generic")
+                    assert np.array_equal(fin[:, m], np.broadcast_to(o.t[:, None], (9, int(m.sum())))), what + ": solid cells"
+            other = -0.5 * np.asarray(mot)                                          # a motion changed between two step calls
+            for x in (s, g, o):
+                (x.set_motion if x is o else x.set_body_motion)(other)
+            s.step(3); g.step(3); o.step(3)
+            _same(s, o, f"{nx}x{ny} {coll} case {name}: after the change of motion")
+            _same_fields(g, s, f"{nx}x{ny} {coll} case {name}: after the change of motion, generic")
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+def test_zero_motion_is_a_context_at_rest(dtype):
+    """No call, a NULL motion, an all-zero one, and rest after a motion: the bits of a context that never heard of motion (SolidOracle's),
+    and lbm_describe shows no wall_motion."""
+    nx, ny = 72, 40
+    m, lab, mot = _cases(nx, ny)["between"]
+    o = SolidOracle(nx, ny, 100.0, mask=m, collision="MRT", dtype=dtype).step(12)
+    for kernel in ("auto", "generic"):
+        with CavitySolver(nx, ny, 100.0, RT="MRT", dtype=dtype, kernel=kernel, solid=m, bodies=lab, **BB) as never, \
+                CavitySolver(nx, ny, 100.0, RT="MRT", dtype=dtype, kernel=kernel, solid=m, bodies=lab, **BB) as s:
+            s.set_body_motion(None).set_body_motion(np.zeros((2, 3)))
+            s.set_body_motion(mot)
+            assert s.describe()["wall_motion"] == 1
+            s.set_body_motion(np.zeros((2, 3)))
+            assert "wall_motion" not in s.describe() and "wall_motion" not in never.describe() and not s.body_motion.any()
+            never.step(12); s.step(12)
+            _same(never, o, f"never {kernel}")
+            _same(s, o, f"zero {kernel}")
+            Fs, Fn = s.body_force(), never.body_force()
+            assert all(np.array_equal(Fs[k], Fn[k]) for k in ("links", "fx", "fy", "tz")) and s.solid_force() == never.solid_force()
+            s.set_body_motion(mot)
+            s.set_bodies(lab)                                                        # new tables: every body at rest again
+            assert "wall_motion" not in s.describe() and not s.body_motion.any()
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+@pytest.mark.parametrize("coll", ["SRT", "TRT", "MRT"])
+def test_fast_arithmetic(coll, dtype):
+    """The configuration of tests/test_solid_gpu.py::test_fast_arithmetic (128 x 96, Re 1000, 2000 steps) with its block turning and
+    sliding: the two routes agree bit for bit, and the distance from strict fp64 stays inside that test's bound."""
+    nx, ny = 128, 96
+    m = np.zeros((nx, ny), bool)
+    m[35:49, 30:50] = True
+    mot = [[0.01, -0.005, 0.002]]
+    with CavitySolver(nx, ny, 1000.0, RT=coll, dtype=np.float64, solid=m, **BB) as ref:
+        ref.set_body_motion(mot).step(2000)
+        f_ref = ref.get_fields(want_fin=True)[2]
+    got = []
+    for kernel in ("auto", "generic"):
+        with CavitySolver(nx, ny, 1000.0, RT=coll, dtype=dtype, arith="fast", kernel=kernel, solid=m, **BB) as s:
+            s.set_body_motion(mot).step(2000)
+            got.append(s.get_fields(want_fin=True, out_dtype=np.float64)[2])
+    assert np.array_equal(got[0], got[1]), "fast arithmetic differs between the routes"
+    err = float(np.abs(got[0] - f_ref).max() / np.abs(f_ref).max())
+    print(f"fast moving {coll} {np.dtype(dtype).name}: {err:.3e} (bound {FAST_BOUND[dtype]:.1e})")
+    assert err < FAST_BOUND[dtype], err
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+def test_batch_equals_lattices_alone(dtype):
+    """Three masks, motions and Reynolds numbers side by side: every lattice as it would run alone, populations and forces."""
+    nx, ny = 72, 40
+    cs = _cases(nx, ny)
+    names, Re = ("block", "between", "random"), (100.0, 250.0, 400.0)
+    nb = 2
+    masks = np.stack([cs[n][0] for n in names])
+    labels = np.stack([cs[n][1] for n in names])
+    mots = np.stack([np.vstack([cs[n][2], np.zeros((nb - len(cs[n][2]), 3))]) for n in names])
+    cen = np.stack([solid.centroids(cs[n][0], cs[n][1], nb) for n in names])
+    with CavityBatch(nx, ny, Re, RT="TRT", dtype=dtype, solid=masks, **BB) as b:
+        b.set_bodies(labels, cen).set_body_motion(mots)
+        assert np.array_equal(b.body_motion, mots)
+        b.step(25)
+        u, rho, fin = b.get_fields(want_fin=True)
+        F, T = b.body_force(), b.solid_force()
+        for i, n in enumerate(names):
+            with CavitySolver(nx, ny, Re[i], RT="TRT", dtype=dtype, solid=masks[i], **BB) as s:
+                s.set_bodies(labels[i], cen[i]).set_body_motion(mots[i]).step(25)
+                lu, lrho, lfin = s.get_fields(want_fin=True)
+                assert np.array_equal(fin[i], lfin) and np.array_equal(u[i], lu) and np.array_equal(rho[i], lrho), n
+                lF, lT = s.body_force(), s.solid_force()
+                assert all(np.array_equal(F[k][i], lF[k]) for k in F), n
+                assert all(T[k][i] == lT[k] for k in T), n
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+def test_force_subtracts_delta(dtype):
+    """links exact; fx, fy, tz of lbm_body_force within links * 2^-52 * sum |terms| of the exactly rounded host sum with 2 f - delta; a
+    series sample equals the one-shot call; lbm_solid_force equals the sum over the bodies within the same bound."""
+    nx, ny = 72, 40
+    for name in ("between", "belts", "random"):
+        m, lab, mot = _cases(nx, ny)[name]
+        o = MovingWallOracle(nx, ny, 100.0, mask=m, labels=lab, motion=mot, collision="MRT", dtype=dtype).step(9)
+        with CavitySolver(nx, ny, 100.0, RT="MRT", dtype=dtype, solid=m, bodies=lab, **BB) as s:
+            s.set_body_motion(mot).step(2)
+            s.begin_force(every=7, capacity=4)
+            s.step(7)
+            _same(s, o, name)
+            F, want = s.body_force(), o.body_force()
+            assert np.array_equal(F["links"], want["links"]) and np.array_equal(F["step"], np.full(len(want["links"]), 9)), name
+            for k, a in (("fx", "abs_x"), ("fy", "abs_y"), ("tz", "abs_z")):
+                bound = want["links"] * 2.0 ** -52 * want[a]
+                print(f"{name} {np.dtype(dtype).name} {k}: device {F[k]!r} host {want[k]!r} bound {bound!r}")
+                assert np.all(np.abs(F[k] - want[k]) <= bound), (name, k)
+            d = solid.wall_delta_field(m, lab, s.bodies[1], mot, dtype)              # the public restatement on public outputs
+            H = solid.host_body_force(o.fin, m, np.where(m, lab, -1), s.bodies[1], d)
+            assert np.all(np.abs(F["fx"] - H["fx"]) <= want["links"] * 2.0 ** -52 * want["abs_x"]), name
+            ser = s.force_series()
+            assert ser["count"] == 1 and all(np.array_equal(ser[k][0], F[k]) for k in ("step", "body", "links", "fx", "fy", "tz")), name
+            T, wt = s.solid_force(), o.force()
+            assert T["links"] == wt["links"] == int(want["links"].sum()) and T["step"] == 9
+            assert abs(T["fx"] - wt["fx"]) <= wt["links"] * 2.0 ** -52 * wt["abs_x"] and abs(T["fy"] - wt["fy"]) <= wt["links"] * 2.0 ** -52 * wt["abs_y"]
+            assert abs(T["fx"] - F["fx"].sum()) <= 2 * wt["links"] * 2.0 ** -52 * wt["abs_x"], name
+            assert abs(T["fy"] - F["fy"].sum()) <= 2 * wt["links"] * 2.0 ** -52 * wt["abs_y"], name
+            if name == "between":                                                   # (delta is in the force: at rest it differs)
+                s.set_body_motion(None)
+                assert s.body_force()["fx"][0] != F["fx"][0]
+
+
+def test_error_paths():
+    nx, ny = 136, 80
+    m = np.zeros((nx, ny), bool); m[0:4, 10:20] = True
+    with CavitySolver(nx, ny, 100.0, RT="MRT", solid=m, **BB) as s:
+        with pytest.raises(RuntimeError, match="net flux"):                      # a block on the left wall with a wall-normal velocity
+            s.set_body_motion([[0.03, 0.0, 0.0]])
+        assert "wall_motion" not in s.describe() and not s.body_motion.any()
+        s.set_body_motion([[0.0, 0.03, 0.0]])                                     # (tangential: a belt)
+        with pytest.raises(RuntimeError, match="not finite"):
+            s.set_body_motion([[0.0, float("inf"), 0.0]])
+        assert s.describe()["wall_motion"] == 1                                   # (a refused call changes nothing)
+        with pytest.raises(ValueError, match=r"\(1, 3\)"):
+            s.set_body_motion(np.zeros((2, 3)))
+    with CavitySolver(nx, ny, 100.0, RT="MRT", solid=m, tuning=dict(solid_tiles=True), **BB) as t:
+        t.set_body_motion(np.zeros((1, 3)))                                       # (rest is what the tile kernel runs)
+        with pytest.raises(RuntimeError, match="tile kernel keeps obstacles at rest"):
+            t.set_body_motion([[0.0, 0.03, 0.0]])
+    with CavitySolver(nx, ny, 100.0, RT="MRT", **BB) as p:
+        with pytest.raises(RuntimeError, match="no solid mask"):
+            p.set_body_motion([[0.0, 0.0, 0.0]])
+        assert p.body_motion is None
+        assert p.lib.lbm_set_body_motion(p._h, None) == -4 and b"LBM_SEM_BOUNCE_BACK_SOLID" in p.lib.lbm_last_error(p._h)
+
+
+def test_checkpoint_round_trip(tmp_path):
+    nx, ny = 72, 40
+    m, lab, mot = _cases(nx, ny)["between"]
+    with CavitySolver(nx, ny, 100.0, RT="TRT", dtype=np.float64, solid=m, bodies=lab, **BB) as a:
+        a.set_body_motion(mot).step(11)
+        path = a.save_checkpoint(str(tmp_path / "moving"))
+        a.step(6)
+        with CavitySolver(nx, ny, 100.0, RT="TRT", dtype=np.float64, solid=m, **BB) as b:
+            assert b.load_checkpoint(path) == 11 and np.array_equal(b.body_motion, np.asarray(mot)) and b.describe()["wall_motion"] == 1
+            b.step(6)
+            _same_fields(a, b, "restart")
+            Fa, Fb = a.body_force(), b.body_force()
+            assert all(np.array_equal(Fa[k], Fb[k]) for k in ("links", "fx", "fy", "tz"))
+
+
+@pytest.fixture(scope="module")
+def tc_reference():
+    case = tc_case()
+    o = MovingWallOracle(TC_N, TC_N, TC_RE, mask=case["mask"], labels=case["labels"], centres=case["centres"], motion=case["motion"],
+                         collision="TRT", dtype=np.float64)
+    return o.step(TC_STEPS), case
+
+
+def test_taylor_couette_strict_fp64_is_the_reference(tc_reference):
+    o, case = tc_reference
+    with CavitySolver(TC_N, TC_N, TC_RE, RT="TRT", dtype=np.float64, solid=case["mask"], **BB) as s:
+        s.set_bodies(case["labels"], case["centres"]).set_body_motion(case["motion"]).step(TC_STEPS)
+        _same(s, o, "Taylor-Couette, strict fp64")
+        F, want = s.body_force(), o.body_force()
+        assert np.all(np.abs(F["tz"] - want["tz"]) <= want["links"] * 2.0 ** -52 * want["abs_z"])
+        (e_in, e_out), e_prof = tc_errors(s.get_fields()[0], F["tz"], case)
+        print(f"Taylor-Couette strict fp64: torque errors {e_in:.6e} {e_out:.6e}, profile error {e_prof:.6e}")
+        assert max(e_in, e_out) <= TC_FACTOR * TC_TORQUE_ERR and e_prof <= TC_FACTOR * TC_PROFILE_ERR
+
+
+def test_taylor_couette_fast_fp32_meets_the_closed_form():
+    """fp32 `fast` stays within the same recorded bound of the closed form: torque of both bodies and the tangential velocity profile."""
+    case = tc_case()
+    with CavitySolver(TC_N, TC_N, TC_RE, RT="TRT", dtype=np.float32, arith="fast", solid=case["mask"], **BB) as s:
+        s.set_bodies(case["labels"], case["centres"]).set_body_motion(case["motion"]).step(TC_STEPS)
+        F = s.body_force()
+        (e_in, e_out), e_prof = tc_errors(s.get_fields(out_dtype=np.float64)[0], F["tz"], case)
+        print(f"Taylor-Couette fast fp32: torque errors {e_in:.6e} {e_out:.6e}, profile error {e_prof:.6e}, tz {F['tz'][0]!r} {F['tz'][1]!r}")
+        assert max(e_in, e_out) <= TC_FACTOR * TC_TORQUE_ERR and e_prof <= TC_FACTOR * TC_PROFILE_ERR
+        assert F["tz"][0] < 0.0 < F["tz"][1]

@@ -5,7 +5,10 @@
 
 A case is  size:dtype:arith[:key=value,...]  e.g.  4096:f32:fast   4096:f32:strict:tb_steps=4   8192x1024:f64:fast:coll=SRT,turb=1
 (keys: coll, turb, kernel, layout, sem (semantics: mrt_gpu, mrt_py, bounce_back), solid (with sem=bounce_back: fluid -- the all-fluid mask --,
-block -- one block of an eighth of the width squared in the middle --, random -- 20 % of the cells, seeded), route (with solid: single --
+block -- one block of an eighth of the width squared in the middle --, disc -- one disc of an eighth of the width across in the middle --,
+random -- 20 % of the cells, seeded --, interior -- the same, one cell clear of the perimeter), motion (with solid: rest -- set_body_motion of
+zeros, the kernels of obstacles at rest -- or rotate -- the solid cells turn as one body about their centroid, 0.05 at three quarters of the
+width from it; not with route=tiles), route (with solid: single --
 one step per launch, the default -- or tiles -- the multi-step tile kernel, tuning solid_tiles), force (with solid: series.E -- the run
 with begin_force(every=E) --, loop.E -- the host loop step(E); solid_force() --, plain.E -- step(E); sync() without any force --, or call -- no stepping: microseconds per call of
 body_force() and of solid_force(); these three are timed with the host clock around work that ends in a synchronisation), batch (that
@@ -28,10 +31,15 @@ def solid_mask(kind, nx, ny):
     if kind == "block":
         w = max(1, nx // 8)
         m[(nx - w) // 2:(nx + w) // 2, (ny - w) // 2:(ny + w) // 2] = True
-    elif kind == "random":
+    elif kind == "disc":
+        x, y = np.meshgrid(np.arange(nx), np.arange(ny), indexing="ij")
+        m = np.hypot(x - (nx - 1) / 2, y - (ny - 1) / 2) < nx / 16
+    elif kind in ("random", "interior"):
         m = np.random.default_rng(1).random((nx, ny)) < 0.2
+        if kind == "interior":
+            m[0] = m[-1] = m[:, 0] = m[:, -1] = False
     elif kind != "fluid":
-        raise ValueError("solid must be fluid, block or random")
+        raise ValueError("solid must be fluid, block, disc, random or interior")
     return m
 
 
@@ -60,6 +68,10 @@ def parse(case):
                 tune["solid_tiles"] = v == "tiles"
             elif k == "force":
                 kw["force"] = v
+            elif k == "motion":
+                if v not in ("rest", "rotate"):
+                    raise ValueError("motion must be rest or rotate")
+                kw["motion"] = v
             elif k == "batch":
                 kw["batch"] = int(v)
             elif k in ("tb_steps", "frame_seg"):
@@ -79,8 +91,11 @@ def main():
         nx, ny, dtype, arith, kw, tune = parse(case)
         B = kw.pop("batch", 1)
         force = kw.pop("force", None)
+        motion = kw.pop("motion", None)
         make = (lambda *a_, **k_: CavityBatch(a_[0], a_[1], [a_[2]] * B, **k_)) if B > 1 else CavitySolver
         with make(nx, ny, 1000.0, dtype=dtype, arith=arith, tuning=tune, **kw) as s:
+            if motion is not None:
+                s.set_body_motion(np.broadcast_to([0.0, 0.0, 0.05 / (0.75 * nx) if motion == "rotate" else 0.0], (B, 1, 3)[B == 1:]))
             s.copy_bandwidth(1 << 30, 60)
             s.step(max(60, a.steps // 10)); s.sync()
             if force == "call":
@@ -116,7 +131,7 @@ def main():
             else:
                 reps = [s.time_steps(a.steps) / a.steps for _ in range(a.reps)]
             ms = min(reps)
-            print(f"{case:48s} S={s.next_unit(1000)}  {B * nx * ny / ms / 1e6:8.1f} GLUPS  {ms * 1e3:9.2f} us/step  "
+            print(f"{case:48s} S={s.next_unit(1000)}{' move' if s.describe().get('wall_motion') else ''}  {B * nx * ny / ms / 1e6:8.1f} GLUPS  {ms * 1e3:9.2f} us/step  "
                   f"repeats {' '.join('%.1f' % (B * nx * ny / r / 1e6) for r in reps)}"
                   + (f"  us/step {' '.join('%.2f' % (r * 1e3) for r in reps)}" if force else ""), flush=True)
 
