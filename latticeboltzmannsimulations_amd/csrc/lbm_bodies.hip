@@ -107,101 +107,93 @@ __global__ __launch_bounds__(RED_WAVE) void k_body_force_final(const double* __r
     }
 }
 
-void bodies_free(lbm_ctx* c) {
-    if (c->body.base) (void)hipFree(c->body.base);
-    c->body = BodyTables{};
-}
-
-// The tables of the context's mask, labels and centres, built on the host and uploaded; the old ones are freed once the new ones are in
-// place.  The caller has synchronised the streams.
-int bodies_upload(lbm_ctx* c) {
-    const int B = c->plan.batch, nb = c->nbodies, nx = c->plan.geo.nx, ny = c->plan.geo.ny;
-    const size_t n = (size_t)nx * ny;
-    std::vector<BodyLink> links;
-    std::vector<long long> start((size_t)B * (nb + 1));
-    std::vector<std::vector<BodyChunk>> chunks(B);
-    std::vector<int32_t> first((size_t)B * (nb + 1));
-    size_t maxchunks = 1;
-    for (int b = 0; b < B; ++b) {
-        body_links(c->solid_mask.data() + b * n, c->body_label.data() + b * n, nx, ny, nb, links, start.data() + (size_t)b * (nb + 1));
-        body_chunks(start.data() + (size_t)b * (nb + 1), nb, chunks[b], first.data() + (size_t)b * (nb + 1));
-        maxchunks = std::max(maxchunks, chunks[b].size());
-    }
-    if (maxchunks > 0x7fffffffu) return fail(c, LBM_ERR_INVALID, "the mask has too many links for the force tables");
-    std::vector<BodyChunk> table(B * maxchunks, BodyChunk{0, 0, 0});
-    for (int b = 0; b < B; ++b) std::copy(chunks[b].begin(), chunks[b].end(), table.begin() + b * maxchunks);
-    auto pad8 = [](size_t v) { return (v + 7) & ~(size_t)7; };
-    const size_t o_chunks = std::max<size_t>(8, links.size() * sizeof(BodyLink)), o_first = o_chunks + table.size() * sizeof(BodyChunk),
-                 o_centre = o_first + pad8(first.size() * sizeof(int32_t)), o_partial = o_centre + c->body_centre.size() * sizeof(double),
-                 o_rec = o_partial + B * maxchunks * BodyAcc::VALS * sizeof(double), bytes = o_rec + (size_t)B * nb * REC * sizeof(double);
-    char* base = nullptr;
-    hipError_t e = hipMalloc((void**)&base, bytes);
-    if (e != hipSuccess) return fail(c, LBM_ERR_NOMEM, std::string("hipMalloc(body tables): ") + hipGetErrorString(e));
-    e = links.empty() ? hipSuccess : hipMemcpy(base, links.data(), links.size() * sizeof(BodyLink), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(base + o_chunks, table.data(), table.size() * sizeof(BodyChunk), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(base + o_first, first.data(), first.size() * sizeof(int32_t), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(base + o_centre, c->body_centre.data(), c->body_centre.size() * sizeof(double), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        (void)hipFree(base);
-        return fail(c, LBM_ERR_HIP, std::string("hipMemcpy(body tables): ") + hipGetErrorString(e));
-    }
-    bodies_free(c);
-    motion_rest(c);   // (new labels or a new mask: every body at rest again)
-    c->body.base = base;
-    c->body.links = (const BodyLink*)base;
-    c->body.chunks = (const BodyChunk*)(base + o_chunks);
-    c->body.first = (const int32_t*)(base + o_first);
-    c->body.centre = (const double*)(base + o_centre);
-    c->body.partial = (double*)(base + o_partial);
-    c->body.rec = (double*)(base + o_rec);
-    c->body.maxchunks = (int)maxchunks;
+// The tables of the mask, labels and centres of `o` (lbm_bodies.hpp lays them out), built on the host and uploaded into `out`.
+static int body_tables(lbm_ctx* c, const std::vector<uint8_t>& mask, const Obstacles& o, BodyTables& out) {
+    const BodyParts t = body_parts(mask.data(), o.label.data(), o.centre.data(), c->plan.batch, c->plan.geo.nx, c->plan.geo.ny, o.nbodies, BodyAcc::VALS, REC);
+    if (t.maxchunks > 0x7fffffffu) return fail(c, LBM_ERR_INVALID, "the mask has too many links for the force tables");
+    Pack<HipMem> p = upload<HipMem>(t.parts(), "body tables");
+    if (!p.err.empty()) return fail(c, p.no_memory ? LBM_ERR_NOMEM : LBM_ERR_HIP, p.err);
+    out.links = p.at<const BodyLink>(BodyParts::LINKS);
+    out.chunks = p.at<const BodyChunk>(BodyParts::CHUNKS);
+    out.first = p.at<const int32_t>(BodyParts::FIRST);
+    out.centre = p.at<const double>(BodyParts::CENTRE);
+    out.partial = p.at<double>(BodyParts::PARTIAL);
+    out.rec = p.at<double>(BodyParts::REC);
+    out.maxchunks = (int)t.maxchunks;
+    out.base = std::move(p.buf);
     return LBM_OK;
 }
 
-// The default: one body that holds every solid cell, centred at its centroid (a fresh context, and after every lbm_set_solid).
-int bodies_default(lbm_ctx* c) {
-    if (c->p.semantics != LBM_SEM_BOUNCE_BACK_SOLID) return LBM_OK;
-    const int B = c->plan.batch;
-    const size_t n = (size_t)c->plan.geo.nx * c->plan.geo.ny;
-    c->nbodies = 1;
-    c->body_label.resize(B * n);
-    for (size_t i = 0; i < B * n; ++i) c->body_label[i] = c->solid_mask[i] ? 0 : -1;
-    c->body_centre.assign((size_t)B * 2, 0.0);
-    for (int b = 0; b < B; ++b)
-        body_centroids(c->solid_mask.data() + b * n, c->body_label.data() + b * n, c->plan.geo.nx, c->plan.geo.ny, 1, c->body_centre.data() + 2 * b);
-    return bodies_upload(c);
+// The one writer of c->obs.  `next` holds the new host state of `level` (mask; nbodies, label, centre; motion) and nothing else.  The
+// levels below it are reset -- a new mask: one body that holds every solid cell, centred at its centroid; new bodies: every body at
+// rest -- the tables of everything that changed are built aside, and only then does the context change, by moves: on any failure
+// its obstacle state is what it was.  before_commit runs between the two (lbm_set_solid: the link planes).  The caller has
+// synchronised the streams.
+int obstacles_change(lbm_ctx* c, ObsLevel level, Obstacles& next, int (*before_commit)(lbm_ctx*, const Obstacles&)) {
+    Obstacles& cur = c->obs;
+    const int B = c->plan.batch, nx = c->plan.geo.nx, ny = c->plan.geo.ny;
+    const size_t n = (size_t)nx * ny;
+    int rc = LBM_OK;
+    if (level == ObsLevel::mask) {
+        next.nbodies = 1;
+        next.label.resize(B * n);
+        for (size_t i = 0; i < B * n; ++i) next.label[i] = next.mask[i] ? 0 : -1;
+        next.centre.assign((size_t)B * 2, 0.0);
+        for (int b = 0; b < B; ++b) body_centroids(next.mask.data() + b * n, next.label.data() + b * n, nx, ny, 1, next.centre.data() + 2 * b);
+    }
+    if (level != ObsLevel::motion) {
+        next.motion.assign((size_t)B * next.nbodies * 3, 0.0);
+        rc = body_tables(c, level == ObsLevel::mask ? next.mask : cur.mask, next, next.body);
+    } else {
+        rc = motion_tables(c, next, next.moving);
+    }
+    if (rc == LBM_OK && before_commit) rc = before_commit(c, next);
+    if (rc) return rc;
+    if (level == ObsLevel::mask) cur.mask = std::move(next.mask);
+    if (level != ObsLevel::motion) {
+        sampler_free(c, SMP_FORCE);   // (its records are per body)
+        cur.nbodies = next.nbodies;
+        cur.label = std::move(next.label);
+        cur.centre = std::move(next.centre);
+        cur.body = std::move(next.body);
+    }
+    cur.motion = std::move(next.motion);
+    cur.moving = std::move(next.moving);
+    return LBM_OK;
 }
 
 // One sample from lat[cur], the lattice after c->nsteps steps, into rec[batch][nbodies] on the device; on the compute stream.
 static int body_force_enqueue(lbm_ctx* c, double* rec) {
-    const BodyTables& t = c->body;
+    const BodyTables& t = c->obs.body;
+    const int nbodies = c->obs.nbodies;
+    const double* link_delta = c->obs.moving.base ? c->obs.moving.link_delta : nullptr;
     return launch_variant(c, [&](auto v) {
         using R = typename decltype(v)::R;
-        if (c->motion.base)
-            hipLaunchKernelGGL((k_body_force_move<R>), dim3(t.maxchunks, 1, c->plan.batch), dim3(BLK), 0, c->s_compute, (const R*)c->lat[c->cur],
-                               c->plan.geo, c->plan.bstride, t.links, t.chunks, t.centre, c->nbodies, t.partial, c->motion.link_delta);
+        if (link_delta)
+            hipLaunchKernelGGL((k_body_force_move<R>), dim3(t.maxchunks, 1, c->plan.batch), dim3(BLK), 0, c->s_compute, c->lat[c->cur].as<const R>(),
+                               c->plan.geo, c->plan.bstride, t.links, t.chunks, t.centre, nbodies, t.partial, link_delta);
         else
-            hipLaunchKernelGGL((k_body_force<R>), dim3(t.maxchunks, 1, c->plan.batch), dim3(BLK), 0, c->s_compute, (const R*)c->lat[c->cur], c->plan.geo,
-                               c->plan.bstride, t.links, t.chunks, t.centre, c->nbodies, t.partial);
-        hipLaunchKernelGGL(k_body_force_final, dim3(c->nbodies, c->plan.batch), dim3(RED_WAVE), 0, c->s_compute, (const double*)t.partial, t.first,
+            hipLaunchKernelGGL((k_body_force<R>), dim3(t.maxchunks, 1, c->plan.batch), dim3(BLK), 0, c->s_compute, c->lat[c->cur].as<const R>(), c->plan.geo,
+                               c->plan.bstride, t.links, t.chunks, t.centre, nbodies, t.partial);
+        hipLaunchKernelGGL(k_body_force_final, dim3(nbodies, c->plan.batch), dim3(RED_WAVE), 0, c->s_compute, (const double*)t.partial, t.first,
                            t.maxchunks, (double)c->nsteps, rec);
     });
 }
 
 // The next sample of the series (lbm_force_sample, and sample_after_unit of the step loop).
 int force_series_sample(lbm_ctx* c) {
-    void* slot = series_slot(c->force_series);
+    void* slot = series_slot(c->obs.force_series);
     if (!slot) return LBM_OK;
     const int rc = body_force_enqueue(c, (double*)slot);
     if (rc) return rc;
-    ++c->force_series.count;
+    ++c->obs.force_series.count;
     return LBM_OK;
 }
 
 // What the calls share: a context with a mask whose lattice holds post-collision populations.
 static int force_ready(lbm_ctx* c, const char* call, bool stepped) {
-    if (c->p.semantics != LBM_SEM_BOUNCE_BACK_SOLID)
-        return fail(c, LBM_ERR_STATE, std::string(call) + ": this context has no solid mask (create it with semantics = LBM_SEM_BOUNCE_BACK_SOLID)");
+    const int rc = need_solid(c, call);
+    if (rc) return rc;
     if (stepped && (c->nsteps == 0 || c->raw[c->cur]))
         return fail(c, LBM_ERR_STATE, std::string(call) + ": no step yet (the lattice holds post-collision populations after one)");
     return LBM_OK;
@@ -219,7 +211,8 @@ int lbm_set_solid_bodies(lbm_ctx* c, const int32_t* body, int nbodies, const dou
     if (!body || nbodies < 1 || nbodies > BODY_MAX) return fail(c, LBM_ERR_INVALID, "lbm_set_solid_bodies: bad argument (1 <= nbodies <= 256)");
     const int B = c->plan.batch;
     const size_t n = (size_t)c->plan.geo.nx * c->plan.geo.ny;
-    const long long bad = body_bad_label(c->solid_mask.data(), body, B * n, nbodies);
+    const std::vector<uint8_t>& mask = c->obs.mask;
+    const long long bad = body_bad_label(mask.data(), body, B * n, nbodies);
     if (bad >= 0)
         return fail(c, LBM_ERR_INVALID, "lbm_set_solid_bodies: the label of solid cell " + std::to_string(bad) + " is not in [0, nbodies)");
     for (size_t i = 0; centre && i < (size_t)B * nbodies * 2; ++i)
@@ -227,37 +220,27 @@ int lbm_set_solid_bodies(lbm_ctx* c, const int32_t* body, int nbodies, const dou
     HIP_TRY(c, hipSetDevice(c->p.device));
     rc = sync_all(c);
     if (rc) return rc;
-    sampler_free(c, SMP_FORCE);
-    // (as lbm_set_solid: the context changes once the new tables are on the device)
-    std::vector<int32_t> label(B * n);
-    for (size_t i = 0; i < B * n; ++i) label[i] = c->solid_mask[i] ? body[i] : -1;
-    std::vector<double> cen((size_t)B * nbodies * 2);
-    for (int b = 0; b < B; ++b) {
-        if (centre) std::copy(centre + (size_t)b * nbodies * 2, centre + (size_t)(b + 1) * nbodies * 2, cen.begin() + (size_t)b * nbodies * 2);
-        else body_centroids(c->solid_mask.data() + b * n, label.data() + b * n, c->plan.geo.nx, c->plan.geo.ny, nbodies, cen.data() + (size_t)b * nbodies * 2);
-    }
-    std::swap(c->nbodies, nbodies);
-    c->body_label.swap(label);
-    c->body_centre.swap(cen);
-    rc = bodies_upload(c);
-    if (rc) {
-        std::swap(c->nbodies, nbodies);
-        c->body_label.swap(label);
-        c->body_centre.swap(cen);
-    }
-    return rc;
+    Obstacles next;
+    next.nbodies = nbodies;
+    next.label.resize(B * n);
+    for (size_t i = 0; i < B * n; ++i) next.label[i] = mask[i] ? body[i] : -1;
+    if (centre) next.centre.assign(centre, centre + (size_t)B * nbodies * 2);
+    else next.centre.resize((size_t)B * nbodies * 2);
+    for (int b = 0; b < B && !centre; ++b)
+        body_centroids(mask.data() + b * n, next.label.data() + b * n, c->plan.geo.nx, c->plan.geo.ny, nbodies, next.centre.data() + (size_t)b * nbodies * 2);
+    return obstacles_change(c, ObsLevel::bodies, next);
 }
 
 int lbm_get_solid_bodies(lbm_ctx* c, int32_t* body_out, double* centre_out) {
     if (!c) return LBM_ERR_INVALID;
     const int rc = force_ready(c, "lbm_get_solid_bodies", false);
     if (rc) return rc;
-    if (body_out) std::memcpy(body_out, c->body_label.data(), c->body_label.size() * sizeof(int32_t));
-    if (centre_out) std::memcpy(centre_out, c->body_centre.data(), c->body_centre.size() * sizeof(double));
+    if (body_out) std::memcpy(body_out, c->obs.label.data(), c->obs.label.size() * sizeof(int32_t));
+    if (centre_out) std::memcpy(centre_out, c->obs.centre.data(), c->obs.centre.size() * sizeof(double));
     return LBM_OK;
 }
 
-int lbm_solid_body_count(lbm_ctx* c) { return c && c->p.semantics == LBM_SEM_BOUNCE_BACK_SOLID ? c->nbodies : 0; }
+int lbm_solid_body_count(lbm_ctx* c) { return c && c->p.semantics == LBM_SEM_BOUNCE_BACK_SOLID ? c->obs.nbodies : 0; }
 
 int lbm_body_force(lbm_ctx* c, lbm_body_force_record* out) {
     if (!c || !out) return fail(c, LBM_ERR_INVALID, "lbm_body_force: bad argument");
@@ -265,9 +248,9 @@ int lbm_body_force(lbm_ctx* c, lbm_body_force_record* out) {
     if (rc) return rc;
     HIP_TRY(c, hipSetDevice(c->p.device));
     rc = sync_all(c);
-    if (rc == LBM_OK) rc = body_force_enqueue(c, c->body.rec);
+    if (rc == LBM_OK) rc = body_force_enqueue(c, c->obs.body.rec);
     if (rc) return rc;
-    HIP_TRY(c, hipMemcpyAsync(out, c->body.rec, (size_t)c->plan.batch * c->nbodies * sizeof(lbm_body_force_record), hipMemcpyDeviceToHost, c->s_compute));
+    HIP_TRY(c, hipMemcpyAsync(out, c->obs.body.rec, (size_t)c->plan.batch * c->obs.nbodies * sizeof(lbm_body_force_record), hipMemcpyDeviceToHost, c->s_compute));
     HIP_TRY(c, hipStreamSynchronize(c->s_compute));
     return LBM_OK;
 }
@@ -278,7 +261,7 @@ int lbm_force_begin(lbm_ctx* c, int every, int capacity) {
     if (rc == LBM_OK) rc = sampler_begin(c, SMP_FORCE, every);
     if (rc) return rc;
     sampler_free(c, SMP_FORCE);
-    rc = series_alloc(c, c->force_series, (size_t)c->nbodies * sizeof(lbm_body_force_record), capacity, "force series");
+    rc = series_alloc(c, c->obs.force_series, (size_t)c->obs.nbodies * sizeof(lbm_body_force_record), capacity, "force series");
     if (rc) return rc;
     c->sampler[SMP_FORCE].arm(c->nsteps, every, 1);
     return LBM_OK;
@@ -286,7 +269,7 @@ int lbm_force_begin(lbm_ctx* c, int every, int capacity) {
 
 int lbm_force_sample(lbm_ctx* c) {
     if (!c) return LBM_ERR_INVALID;
-    if (!c->force_series.dev) return fail(c, LBM_ERR_STATE, "lbm_force_sample: nothing to sample into (lbm_force_begin)");
+    if (!c->obs.force_series.dev) return fail(c, LBM_ERR_STATE, "lbm_force_sample: nothing to sample into (lbm_force_begin)");
     int rc = force_ready(c, "lbm_force_sample", true);
     if (rc) return rc;
     HIP_TRY(c, hipSetDevice(c->p.device));
@@ -295,7 +278,7 @@ int lbm_force_sample(lbm_ctx* c) {
 }
 
 int lbm_force_read(lbm_ctx* c, lbm_body_force_record* records_out, int max_records, long long* count, long long* dropped) {
-    return series_read(c, &lbm_ctx::force_series, "lbm_force_read", records_out, max_records, count, dropped);
+    return series_read(c, [](const lbm_ctx* x) { return &x->obs.force_series; }, "lbm_force_read", records_out, max_records, count, dropped);
 }
 
 int lbm_force_end(lbm_ctx* c) { return sampler_end(c, SMP_FORCE); }

@@ -1,11 +1,14 @@
 // lbm_bodies.hpp -- the bodies of a solid mask (lbm_set_solid_bodies; contract in include/lbm.h): the check of the
-// labels, the centroids, and the link list that k_body_force (lbm_bodies.hip) walks, with its cut into chunks.  Arrays are in the host
-// layout of the mask, [nx][ny] with y fastest, one lattice at a time.  Plain C++, nothing from HIP: tests/test_body_force_cpu.py drives
-// it from a program of its own.
+// labels, the centroids, and the link list that k_body_force (lbm_bodies.hip) walks, with its cut into chunks; then the tables of a
+// whole batch as the device holds them (body_parts).  Arrays are in the host layout of the mask, [nx][ny] with y fastest, one lattice at
+// a time.  Plain C++, nothing from HIP: tests/test_body_force_cpu.py and tests/test_devmem_cpu.py drive it from programs of their own.
 #pragma once
+#include <algorithm>
 #include <cstddef>
 #include <cstdint>
 #include <vector>
+
+#include "lbm_devmem.hpp"
 
 namespace lbmhost {
 
@@ -85,5 +88,42 @@ inline void body_chunks(const long long* start, int nbodies, std::vector<BodyChu
             chunks.push_back(BodyChunk{i, (int32_t)(start[b + 1] - i < BODY_CHUNK ? start[b + 1] - i : BODY_CHUNK), b});
     }
     first[nbodies] = (int32_t)(chunks.size() - base);
+}
+
+// The tables of the bodies of a whole batch (mask and label [batch][nx][ny], centre[batch][nbodies][2]) as the device holds them in one
+// allocation: the link list of every lattice, one after the other; chunks[batch][maxchunks], padded with empty chunks to the longest
+// lattice's; first[batch][nbodies + 1]; centre; then, only reserved, the workgroups' partial results of one pass (acc_vals doubles per
+// chunk) and the records of the one-shot call (rec_vals doubles per body).
+struct BodyParts {
+    enum { LINKS, CHUNKS, FIRST, CENTRE, PARTIAL, REC };
+    std::vector<BodyLink> links;
+    std::vector<BodyChunk> chunks;
+    std::vector<int32_t> first;
+    std::vector<double> centre;
+    size_t maxchunks = 1, partial_bytes = 0, rec_bytes = 0;
+    std::vector<Part> parts() const {
+        return {{links.data(), links.size() * sizeof(BodyLink)}, {chunks.data(), chunks.size() * sizeof(BodyChunk)},
+                {first.data(), first.size() * sizeof(int32_t)}, {centre.data(), centre.size() * sizeof(double)},
+                {nullptr, partial_bytes}, {nullptr, rec_bytes}};
+    }
+};
+inline BodyParts body_parts(const uint8_t* mask, const int32_t* label, const double* centre, int batch, int nx, int ny, int nbodies, int acc_vals,
+                            int rec_vals) {
+    const size_t n = (size_t)nx * ny, B = (size_t)batch, nb1 = (size_t)nbodies + 1;
+    BodyParts t;
+    std::vector<long long> start(nb1);
+    std::vector<std::vector<BodyChunk>> chunks(B);
+    t.first.resize(B * nb1);
+    for (size_t b = 0; b < B; ++b) {
+        body_links(mask + b * n, label + b * n, nx, ny, nbodies, t.links, start.data());
+        body_chunks(start.data(), nbodies, chunks[b], t.first.data() + b * nb1);
+        if (chunks[b].size() > t.maxchunks) t.maxchunks = chunks[b].size();
+    }
+    t.chunks.assign(B * t.maxchunks, BodyChunk{0, 0, 0});
+    for (size_t b = 0; b < B; ++b) std::copy(chunks[b].begin(), chunks[b].end(), t.chunks.begin() + b * t.maxchunks);
+    t.centre.assign(centre, centre + B * nbodies * 2);
+    t.partial_bytes = B * t.maxchunks * acc_vals * sizeof(double);
+    t.rec_bytes = B * nbodies * rec_vals * sizeof(double);
+    return t;
 }
 }  // namespace lbmhost

@@ -85,7 +85,7 @@ const int* side_planes(int side) {
 }
 
 char* plane_row(lbm_ctx* c, int which, int k, int y) {
-    return (char*)c->lat[which] + ((size_t)k * c->plan.geo.plane + (size_t)c->plan.geo.at(0, y)) * c->plan.es;
+    return c->lat[which].as<char>() + ((size_t)k * c->plan.geo.plane + (size_t)c->plan.geo.at(0, y)) * c->plan.es;
 }
 
 #ifdef LBM_DEBUG
@@ -132,7 +132,7 @@ RowBlocks deep_blocks(lbm_ctx* c, int which, int r0, int S) {
     RowBlocks b;
     const int nplanes = c->plan.nplanes;
     const bool rows_layout = c->plan.geo.row != c->plan.geo.pitch;
-    auto at = [&](int k) { return (char*)c->lat[which] + ((size_t)k * c->plan.geo.plane + (size_t)(r0 + GHY) * c->plan.geo.row) * c->plan.es; };
+    auto at = [&](int k) { return c->lat[which].as<char>() + ((size_t)k * c->plan.geo.plane + (size_t)(r0 + GHY) * c->plan.geo.row) * c->plan.es; };
     if (rows_layout) {
         b.n = 1; b.ptr[0] = at(0); b.elems = (size_t)S * c->plan.geo.row;
     } else {
@@ -267,15 +267,14 @@ int lbm_comm_init(lbm_ctx* c, int nranks, int rank, const void* uid128) {
         int32_t host[3 * NW];
         std::memcpy(host, mine, sizeof(mine));
         std::memset(host + NW, 0xff, 2 * NW * sizeof(int32_t));
-        int32_t* dev = nullptr;
-        hipError_t e = hipMalloc((void**)&dev, sizeof(host));
-        if (e == hipSuccess) e = hipMemcpy(dev, host, sizeof(host), hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipDeviceSynchronize();
-        if (e != hipSuccess) {
-            if (dev) (void)hipFree(dev);
+        Pack<HipMem> words = upload<HipMem>({{host, sizeof(host)}}, "plan words");
+        hipError_t e = hipSuccess;
+        if (words.err.empty() && (e = hipDeviceSynchronize()) != hipSuccess) words.err = hipGetErrorString(e);
+        if (!words.err.empty()) {
             drop_comm();
-            return fail(c, LBM_ERR_HIP, std::string("lbm_comm_init (plan check): ") + hipGetErrorString(e));
+            return fail(c, LBM_ERR_HIP, "lbm_comm_init (plan check): " + words.err);
         }
+        int32_t* dev = words.buf.as<int32_t>();
         ncclResult_t r = rccl().GroupStart();
         if (r == ncclSuccess) {
             for (int side = 0; side < 2 && r == ncclSuccess; ++side) {
@@ -292,7 +291,6 @@ int lbm_comm_init(lbm_ctx* c, int nranks, int rank, const void* uid128) {
             e = hipStreamSynchronize(c->s_comm);
             if (e == hipSuccess) e = hipMemcpy(theirs, dev + NW, sizeof(theirs), hipMemcpyDeviceToHost);
         }
-        (void)hipFree(dev);
         if (r != ncclSuccess) { const std::string m = rccl().GetErrorString(r); drop_comm(); return fail(c, LBM_ERR_COMM, "lbm_comm_init (plan check): " + m); }
         if (e != hipSuccess) { drop_comm(); return fail(c, LBM_ERR_HIP, std::string("lbm_comm_init (plan check): ") + hipGetErrorString(e)); }
         static const char* what[NW] = {"ABI version", "nx", "ny", "dtype", "semantics", "turb", "row pitch", "layout", "steps-per-launch path (0 none, 1 tile, 2 streaming kernel)",

@@ -40,14 +40,7 @@ __global__ __launch_bounds__(BLK) void k_reduce_final(const double* __restrict__
     out[z] = scale * a;
 }
 
-int ensure_stage(lbm_ctx* c, size_t bytes) {
-    if (c->stage_bytes >= bytes) return LBM_OK;
-    if (c->stage) { (void)hipFree(c->stage); c->stage = nullptr; c->stage_bytes = 0; }
-    hipError_t e = hipMalloc(&c->stage, bytes);
-    if (e != hipSuccess) return fail(c, LBM_ERR_NOMEM, std::string("hipMalloc(staging): ") + hipGetErrorString(e));
-    c->stage_bytes = bytes;
-    return LBM_OK;
-}
+int ensure_stage(lbm_ctx* c, size_t bytes) { return alloc_ok(c, c->stage.ensure(bytes, "staging")); }
 int sync_all(lbm_ctx* c) {
     if (!spin_until_ready([&] { return hipStreamQuery(c->s_compute); })) HIP_TRY(c, hipStreamSynchronize(c->s_compute));
     if (!spin_until_ready([&] { return hipStreamQuery(c->s_comm); })) HIP_TRY(c, hipStreamSynchronize(c->s_comm));
@@ -69,14 +62,14 @@ int host_to_stage(lbm_ctx* c, const void* host, int host_dtype, int planes) {
     const int nx = c->plan.geo.nx, ny = c->plan.geo.ny, NY = c->plan.geo.NY, y0 = c->plan.geo.y0;
     const size_t rows = (size_t)planes * nx;
     if (host_dtype == c->p.dtype) {
-        HIP_TRY(c, hipMemcpy2D(c->stage, (size_t)ny * c->plan.es, (const char*)host + (size_t)y0 * c->plan.es, (size_t)NY * c->plan.es,
+        HIP_TRY(c, hipMemcpy2D(c->stage.get(), (size_t)ny * c->plan.es, (const char*)host + (size_t)y0 * c->plan.es, (size_t)NY * c->plan.es,
                                (size_t)ny * c->plan.es, rows, hipMemcpyHostToDevice));
         return LBM_OK;
     }
     std::vector<char> tmp(rows * ny * c->plan.es);
     if (c->p.dtype == LBM_F32) convert_rows((float*)tmp.data(), (const double*)host, rows, ny, NY, y0, false);
     else convert_rows((double*)tmp.data(), (const float*)host, rows, ny, NY, y0, false);
-    HIP_TRY(c, hipMemcpy(c->stage, tmp.data(), tmp.size(), hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(c->stage.get(), tmp.data(), tmp.size(), hipMemcpyHostToDevice));
     return LBM_OK;
 }
 
@@ -103,8 +96,8 @@ int export_fin(lbm_ctx* c) {
     return launch_variant(c, [&](auto v) {
         using VT = decltype(v);
         using R = typename VT::R;
-        hipLaunchKernelGGL((k_export_fin<R, VT::SEM, coll_is_prom(VT::COLL)>), grid_tiles<R>(c), dim3(BLK), 0, c->s_compute, (const R*)c->lat[c->cur],
-                           c->plan.geo, c->raw[c->cur], (R)c->p.uLB, (R*)c->stage, c->plan.bstride);
+        hipLaunchKernelGGL((k_export_fin<R, VT::SEM, coll_is_prom(VT::COLL)>), grid_tiles<R>(c), dim3(BLK), 0, c->s_compute, c->lat[c->cur].as<const R>(),
+                           c->plan.geo, c->raw[c->cur], (R)c->p.uLB, c->stage.as<R>(), c->plan.bstride);
     });
 }
 
@@ -117,8 +110,8 @@ int export_macro(lbm_ctx* c) {
     return launch_variant(c, [&](auto v) {
         using VT = decltype(v);
         using R = typename VT::R;
-        hipLaunchKernelGGL((k_export_macro<R, VT::SEM, coll_is_prom(VT::COLL)>), grid_tiles<R>(c), dim3(BLK), 0, c->s_compute, (const R*)c->lat[which],
-                           c->plan.geo, c->raw[which], (R)c->p.uLB, (R*)c->stage, c->plan.bstride);
+        hipLaunchKernelGGL((k_export_macro<R, VT::SEM, coll_is_prom(VT::COLL)>), grid_tiles<R>(c), dim3(BLK), 0, c->s_compute, c->lat[which].as<const R>(),
+                           c->plan.geo, c->raw[which], (R)c->p.uLB, c->stage.as<R>(), c->plan.bstride);
     });
 }
 
@@ -132,7 +125,7 @@ int export_tau(lbm_ctx* c) {
         using VT = decltype(v);
         using R = typename VT::R;
         hipLaunchKernelGGL((k_export_tau<R, coll_is_fast(VT::COLL), coll_is_prom(VT::COLL)>), grid_tiles<R>(c), dim3(BLK), 0, c->s_compute,
-                           (const R*)c->lat[which], c->plan.geo, c->raw[which], relax_of<R>(c->p), batch_of<R>(c), c->p.turb, (R*)c->stage);
+                           c->lat[which].as<const R>(), c->plan.geo, c->raw[which], relax_of<R>(c->p), batch_of<R>(c), c->p.turb, c->stage.as<R>());
     });
 }
 
@@ -146,7 +139,7 @@ int reduce_u(lbm_ctx* c) {
         using VT = decltype(v);
         using R = typename VT::R;
         hipLaunchKernelGGL((k_reduce_u<R, VT::SEM, coll_is_prom(VT::COLL)>), dim3(RED_BLOCKS, 1, c->plan.batch), dim3(BLK), 0, c->s_compute,
-                           (const R*)c->lat[which], c->plan.geo, c->raw[which], (R)c->p.uLB, c->plan.bstride, c->red_dev);
+                           c->lat[which].as<const R>(), c->plan.geo, c->raw[which], (R)c->p.uLB, c->plan.bstride, c->red_dev.as<double>());
     });
 }
 
@@ -198,7 +191,7 @@ lbm_ctx* lbm_create(const lbm_params* p, char* err, size_t errlen) {
     c->order.debug_no_exchange_ready = std::getenv("LBM_DEBUG_NO_EXCHANGE_READY") != nullptr;
 #endif
     const size_t bytes = c->plan.lat_bytes;
-    auto cleanup = [&](const std::string& m) -> lbm_ctx* { lbm_destroy(c); return bail(m); };
+    auto cleanup = [&](const std::string m) -> lbm_ctx* { lbm_destroy(c); return bail(m); };   // (m by value: it may be c->err)
     if ((e = hipStreamCreateWithFlags(&c->s_compute, hipStreamNonBlocking)) != hipSuccess) return cleanup("hipStreamCreate");
     {   // halo exchange stream at the highest priority: its (tiny) RCCL kernels must not queue behind the
         // thousands of workgroups of the interior kernel they are meant to overlap
@@ -218,15 +211,18 @@ lbm_ctx* lbm_create(const lbm_params* p, char* err, size_t errlen) {
     if ((e = hipEventCreate(&c->ev_t1)) != hipSuccess) return cleanup("hipEventCreate");
     // the two lattices (+ ftemp of the push scheme); the scratch lattices of the frame passes come on first use (ensure_scratch)
     for (int i = 0; i < (c->plan.push ? 3 : 2); ++i) {
-        if ((e = hipMalloc(&c->lat[i], bytes)) != hipSuccess) return cleanup(std::string("hipMalloc(lattice): ") + hipGetErrorString(e));
+        if (alloc_ok(c, c->lat[i].alloc(bytes, "lattice")) != LBM_OK) return cleanup(c->err);
         // on the compute stream: the streams are non-blocking, a null-stream memset would race with the kernels
-        if ((e = hipMemsetAsync(c->lat[i], 0, bytes, c->s_compute)) != hipSuccess) return cleanup(std::string("hipMemset: ") + hipGetErrorString(e));
+        if ((e = hipMemsetAsync(c->lat[i].get(), 0, bytes, c->s_compute)) != hipSuccess) return cleanup(std::string("hipMemset: ") + hipGetErrorString(e));
     }
-    if (p->semantics == LBM_SEM_BOUNCE_BACK_SOLID) c->solid_mask.assign((size_t)c->plan.batch * p->nx * p->ny, 0);   // all fluid
-    if (bodies_default(c) != LBM_OK) return cleanup(c->err);
+    if (p->semantics == LBM_SEM_BOUNCE_BACK_SOLID) {   // all fluid: one body without a cell, at rest
+        Obstacles next;
+        next.mask.assign((size_t)c->plan.batch * p->nx * p->ny, 0);
+        if (obstacles_change(c, ObsLevel::mask, next) != LBM_OK) return cleanup(c->err);
+    }
     if (c->plan.batch > 1) {   // every lattice starts with the rates of lbm_params; lbm_set_relaxation() changes them one by one
         const size_t rb = c->plan.es == 4 ? sizeof(Relax<float>) : sizeof(Relax<double>);
-        if ((e = hipMalloc(&c->relax_dev, rb * c->plan.batch)) != hipSuccess) return cleanup(std::string("hipMalloc(relaxation): ") + hipGetErrorString(e));
+        if (alloc_ok(c, c->relax_dev.alloc(rb * c->plan.batch, "relaxation")) != LBM_OK) return cleanup(c->err);
         for (int i = 0; i < c->plan.batch; ++i)
             if (lbm_set_relaxation(c, i, p->omega, p->omegam, p->omega_e, p->omega_eps, p->omega_q) != LBM_OK) return cleanup(c->err);
     }
@@ -241,17 +237,6 @@ void lbm_destroy(lbm_ctx* c) {
     if (c->s_compute) (void)hipStreamSynchronize(c->s_compute);
     if (c->s_comm) (void)hipStreamSynchronize(c->s_comm);
     if (c->comm && rccl().ok) (void)rccl().CommDestroy(c->comm);
-    for (int i = 0; i < NLAT; ++i)
-        if (c->lat[i]) (void)hipFree(c->lat[i]);
-    if (c->red_dev) (void)hipFree(c->red_dev);
-    for (int i = 0; i < NSCHEDULED; ++i) sampler_free(c, i);
-    monitor_free(c);
-    topology_free(c);
-    solid_free(c);
-    bodies_free(c);
-    motion_rest(c);
-    if (c->stage) (void)hipFree(c->stage);
-    if (c->relax_dev) (void)hipFree(c->relax_dev);
     if (c->ev_edges) (void)hipEventDestroy(c->ev_edges);
     if (c->ev_halo) (void)hipEventDestroy(c->ev_halo);
     if (c->ev_int) (void)hipEventDestroy(c->ev_int);
@@ -260,7 +245,7 @@ void lbm_destroy(lbm_ctx* c) {
     if (c->ev_t1) (void)hipEventDestroy(c->ev_t1);
     if (c->s_compute) (void)hipStreamDestroy(c->s_compute);
     if (c->s_comm) (void)hipStreamDestroy(c->s_comm);
-    delete c;
+    delete c;   // (and with it every buffer: each is a DevBuf)
 }
 
 const char* lbm_last_error(const lbm_ctx* c) { return c ? c->err.c_str() : "null context"; }
@@ -275,7 +260,7 @@ int lbm_init_equilibrium(lbm_ctx* c) {
     rc = launch_variant(c, [&](auto v) {
         using VT = decltype(v);
         using R = typename VT::R;
-        hipLaunchKernelGGL((k_init<R, coll_is_prom(VT::COLL)>), g, dim3(BLK), 0, c->s_compute, (R*)c->lat[0], c->plan.geo, (R)c->p.uLB, c->p.turb, c->plan.bstride);
+        hipLaunchKernelGGL((k_init<R, coll_is_prom(VT::COLL)>), g, dim3(BLK), 0, c->s_compute, c->lat[0].as<R>(), c->plan.geo, (R)c->p.uLB, c->p.turb, c->plan.bstride);
     });
     if (rc == LBM_OK) rc = solid_fix(c);
     if (rc) return rc;
@@ -295,7 +280,7 @@ int lbm_set_state(lbm_ctx* c, const void* fin_host, int host_dtype) {
     rc = launch_variant(c, [&](auto v) {
         using VT = decltype(v);
         using R = typename VT::R;
-        hipLaunchKernelGGL((k_import<R, coll_is_prom(VT::COLL)>), grid_tiles<R>(c), dim3(BLK), 0, c->s_compute, (const R*)c->stage, (R*)c->lat[0], c->plan.geo,
+        hipLaunchKernelGGL((k_import<R, coll_is_prom(VT::COLL)>), grid_tiles<R>(c), dim3(BLK), 0, c->s_compute, c->stage.as<const R>(), c->lat[0].as<R>(), c->plan.geo,
                            (R)c->p.uLB, c->p.turb, c->plan.bstride);
     });
     if (rc == LBM_OK) rc = solid_fix(c);   // (solid cells: w_k, whatever the host array holds there)
@@ -320,10 +305,10 @@ int lbm_set_relaxation(lbm_ctx* c, int index, double omega, double omegam, doubl
     HIP_TRY(c, hipStreamSynchronize(c->s_comm));
     if (c->plan.es == 4) {
         const Relax<float> w = relax_of<float>(q);
-        HIP_TRY(c, hipMemcpyAsync((Relax<float>*)c->relax_dev + index, &w, sizeof(w), hipMemcpyHostToDevice, c->s_compute));
+        HIP_TRY(c, hipMemcpyAsync(c->relax_dev.as<Relax<float>>() + index, &w, sizeof(w), hipMemcpyHostToDevice, c->s_compute));
     } else {
         const Relax<double> w = relax_of<double>(q);
-        HIP_TRY(c, hipMemcpyAsync((Relax<double>*)c->relax_dev + index, &w, sizeof(w), hipMemcpyHostToDevice, c->s_compute));
+        HIP_TRY(c, hipMemcpyAsync(c->relax_dev.as<Relax<double>>() + index, &w, sizeof(w), hipMemcpyHostToDevice, c->s_compute));
     }
     HIP_TRY(c, hipStreamSynchronize(c->s_compute));
     return LBM_OK;
@@ -351,7 +336,7 @@ int lbm_get_fields(lbm_ctx* c, void* u_host, void* rho_host, void* fin_host, int
         if (rc) return rc;
         HIP_TRY(c, hipStreamSynchronize(c->s_compute));
         for (int b = 0; b < c->plan.batch; ++b) {   // staging of lattice b: [ux | uy | rho]; host: u[B][2][nx][NY], rho[B][nx][NY]
-            const char* st = (const char*)c->stage + (size_t)b * 3 * n * c->plan.es;
+            const char* st = c->stage.as<const char>() + (size_t)b * 3 * n * c->plan.es;
             const size_t hn = (size_t)c->plan.geo.nx * c->plan.geo.NY * hes;
             if (u_host) { rc = stage_to_host(c, st, (char*)u_host + (size_t)b * 2 * hn, host_dtype, 2); if (rc) return rc; }
             if (rho_host) { rc = stage_to_host(c, st + 2 * n * c->plan.es, (char*)rho_host + (size_t)b * hn, host_dtype, 1); if (rc) return rc; }
@@ -361,7 +346,7 @@ int lbm_get_fields(lbm_ctx* c, void* u_host, void* rho_host, void* fin_host, int
         rc = export_fin(c);
         if (rc) return rc;
         HIP_TRY(c, hipStreamSynchronize(c->s_compute));
-        rc = stage_to_host(c, c->stage, fin_host, host_dtype, Q * c->plan.batch);
+        rc = stage_to_host(c, c->stage.get(), fin_host, host_dtype, Q * c->plan.batch);
         if (rc) return rc;
     }
     return LBM_OK;
@@ -372,15 +357,12 @@ int lbm_mean_u(lbm_ctx* c, double* mean_out) {
     HIP_TRY(c, hipSetDevice(c->p.device));
     int rc = sync_all(c);
     if (rc) return rc;
-    if (!c->red_dev) {
-        hipError_t e = hipMalloc((void**)&c->red_dev, ((size_t)RED_BLOCKS + 1) * c->plan.batch * sizeof(double));
-        if (e != hipSuccess) return fail(c, LBM_ERR_NOMEM, std::string("hipMalloc(reduction): ") + hipGetErrorString(e));
-    }
-    rc = reduce_u(c);
+    rc = alloc_ok(c, c->red_dev.ensure(((size_t)RED_BLOCKS + 1) * c->plan.batch * sizeof(double), "reduction"));
+    if (rc == LBM_OK) rc = reduce_u(c);
     if (rc) return rc;
-    double* res = c->red_dev + (size_t)RED_BLOCKS * c->plan.batch;
+    double* res = c->red_dev.as<double>() + (size_t)RED_BLOCKS * c->plan.batch;
     const double scale = 1.0 / (2.0 * (double)c->plan.geo.nx * (double)c->plan.geo.ny);
-    hipLaunchKernelGGL(k_reduce_final, dim3((c->plan.batch + BLK - 1) / BLK), dim3(BLK), 0, c->s_compute, c->red_dev, RED_BLOCKS, c->plan.batch, scale, res);
+    hipLaunchKernelGGL(k_reduce_final, dim3((c->plan.batch + BLK - 1) / BLK), dim3(BLK), 0, c->s_compute, c->red_dev.as<double>(), RED_BLOCKS, c->plan.batch, scale, res);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipMemcpyAsync(mean_out, res, (size_t)c->plan.batch * sizeof(double), hipMemcpyDeviceToHost, c->s_compute));
     HIP_TRY(c, hipStreamSynchronize(c->s_compute));
@@ -398,31 +380,28 @@ int lbm_get_tau(lbm_ctx* c, void* tau_host, int host_dtype) {
     rc = export_tau(c);
     if (rc) return rc;
     HIP_TRY(c, hipStreamSynchronize(c->s_compute));
-    return stage_to_host(c, c->stage, tau_host, host_dtype, c->plan.batch);
+    return stage_to_host(c, c->stage.get(), tau_host, host_dtype, c->plan.batch);
 }
 
 int lbm_copy_bandwidth(lbm_ctx* c, size_t bytes, int iters, double* gbps) {
     if (!c || !gbps || iters < 1 || bytes < 16) return fail(c, LBM_ERR_INVALID, "lbm_copy_bandwidth: bad argument");
     HIP_TRY(c, hipSetDevice(c->p.device));
     bytes &= ~(size_t)15;
-    void *a = nullptr, *b = nullptr;
-    if (hipMalloc(&a, bytes) != hipSuccess || hipMalloc(&b, bytes) != hipSuccess) {
-        if (a) (void)hipFree(a);
-        return fail(c, LBM_ERR_NOMEM, "lbm_copy_bandwidth: hipMalloc failed");
-    }
-    (void)hipMemsetAsync(a, 1, bytes, c->s_compute);
+    DevBuf src, dst;
+    if (!src.alloc(bytes, "").empty() || !dst.alloc(bytes, "").empty()) return fail(c, LBM_ERR_NOMEM, "lbm_copy_bandwidth: hipMalloc failed");
+    const uint4* a = src.as<const uint4>();
+    uint4* b = dst.as<uint4>();
+    (void)hipMemsetAsync(src.get(), 1, bytes, c->s_compute);
     const size_t n = bytes / 16;
     const int blocks = 256 * 8;
-    hipLaunchKernelGGL(k_copy16, dim3(blocks), dim3(BLK), 0, c->s_compute, (const uint4*)a, (uint4*)b, n);
+    hipLaunchKernelGGL(k_copy16, dim3(blocks), dim3(BLK), 0, c->s_compute, a, b, n);
     (void)hipEventRecord(c->ev_t0, c->s_compute);
     for (int i = 0; i < iters; ++i)
-        hipLaunchKernelGGL(k_copy16, dim3(blocks), dim3(BLK), 0, c->s_compute, (const uint4*)a, (uint4*)b, n);
+        hipLaunchKernelGGL(k_copy16, dim3(blocks), dim3(BLK), 0, c->s_compute, a, b, n);
     (void)hipEventRecord(c->ev_t1, c->s_compute);
     hipError_t e = hipEventSynchronize(c->ev_t1);
     float ms = 0.f;
     if (e == hipSuccess) e = hipEventElapsedTime(&ms, c->ev_t0, c->ev_t1);
-    (void)hipFree(a);
-    (void)hipFree(b);
     if (e != hipSuccess) return fail(c, LBM_ERR_HIP, std::string("lbm_copy_bandwidth: ") + hipGetErrorString(e));
     *gbps = 2.0 * (double)bytes * iters / (ms * 1e-3) / 1e9;
     return LBM_OK;
@@ -431,9 +410,11 @@ int lbm_copy_bandwidth(lbm_ctx* c, size_t bytes, int iters, double* gbps) {
 int lbm_fma_rate(lbm_ctx* c, double ms_total, double* tflops) {
     if (!c || !tflops || !(ms_total > 0) || ms_total > 2000) return fail(c, LBM_ERR_INVALID, "lbm_fma_rate: bad argument (0 < ms <= 2000)");
     HIP_TRY(c, hipSetDevice(c->p.device));
-    float* sink = nullptr;
     const int blocks = c->plan.ncu * 8, iters = 4096;
-    HIP_TRY(c, hipMalloc((void**)&sink, (size_t)blocks * BLK * sizeof(float)));
+    DevBuf buf;
+    const std::string bad = buf.alloc((size_t)blocks * BLK * sizeof(float), "fma sink");
+    if (!bad.empty()) return fail(c, LBM_ERR_HIP, bad);
+    float* sink = buf.as<float>();
     auto run = [&](int n, float* ms) -> hipError_t {
         (void)hipEventRecord(c->ev_t0, c->s_compute);
         for (int i = 0; i < n; ++i) hipLaunchKernelGGL(k_fma_burn, dim3(blocks), dim3(BLK), 0, c->s_compute, sink, iters, 1.0f + (float)i);
@@ -446,7 +427,6 @@ int lbm_fma_rate(lbm_ctx* c, double ms_total, double* tflops) {
     hipError_t e = run(1, &ms1);                                    // calibration (also the first, slower, launch)
     const int n = e == hipSuccess && ms1 > 0 ? std::max(1, (int)(ms_total / ms1)) : 1;
     if (e == hipSuccess) e = run(n, &ms);
-    (void)hipFree(sink);
     if (e != hipSuccess) return fail(c, LBM_ERR_HIP, std::string("lbm_fma_rate: ") + hipGetErrorString(e));
     // per thread and iteration: 16 packed FMAs = 32 FMAs = 64 flop
     *tflops = (double)n * blocks * BLK * (double)iters * 64.0 / (ms * 1e-3) / 1e12;

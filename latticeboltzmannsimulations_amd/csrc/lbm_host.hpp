@@ -11,10 +11,14 @@
 //   lbm_residual.hip the field residual (kernels: lbm_residual.hpp)                        (C ABI: residual_*)
 //   lbm_topology.hip stream function, vorticity, extrema of psi (kernels: lbm_topology.hpp) (C ABI: topology, get_stream_function)
 //   lbm_solid.hip   solid obstacles: the mask and its link plane, the force on the obstacles (step kernel: lbm_solid.hpp) (C ABI: set_solid, get_solid, solid_force)
-//   lbm_bodies.hip  the bodies of a mask: force and torque on each, one-shot and as a series    (C ABI: set_solid_bodies, get_solid_bodies, body_force, force_*)
-// and three headers free of HIP, each driven by a CPU test through a program of its own:
+//   lbm_bodies.hip  the one writer of the obstacle state (struct Obstacles); the bodies of a mask: force and torque on each, one-shot
+//                   and as a series                                                          (C ABI: set_solid_bodies, get_solid_bodies, body_force, force_*)
+//   lbm_body_motion.hip the wall velocity of moving bodies: its tables                         (C ABI: set_body_motion, get_body_motion)
+// and five headers free of HIP, each driven by a CPU test through a program of its own:
 //   lbm_schedule.hpp the schedule of automatic sampling
-//   lbm_bodies.hpp   the labels of a mask's bodies, their centroids, the link list and its chunks
+//   lbm_devmem.hpp   the owner of a device allocation, and several tables uploaded into one (the device: HipMem below)
+//   lbm_bodies.hpp   the labels of a mask's bodies, their centroids, the link list and its chunks; the tables of a batch
+//   lbm_wall_motion.hpp the moving-wall term of every link, the flux check; the tables of a batch
 //   lbm_order.hpp    the ordering of the two streams: the state carried between units, the skeletons of a unit, the argument
 #pragma once
 #include <hip/hip_runtime.h>
@@ -34,6 +38,7 @@
 #include "../../include/lbm.h"
 #include "lbm_schedule.hpp"
 #include "lbm_order.hpp"
+#include "lbm_devmem.hpp"
 #include "lbm_bodies.hpp"
 #include "lbm_solid.hpp"  // k_step_solid, extern (compiled in lbm_solid_f32/f64.hip)
 #include "lbm_solid_move.hpp"  // k_step_solid_move, k_step_generic_move, extern (compiled in lbm_solid_move_f32/f64.hip)
@@ -93,18 +98,30 @@ struct Plan {
     bool comm_priority = true;  // the halo exchange stream at the highest priority (A/B: LBM_FLAG_COMM_PRIORITY_OFF, the compute stream's)
 };
 
-// The records of a series on the device, [capacity][batch], and how many samples it holds and has dropped (series_* in lbm_sampling.hip).
+// Device memory has one owner each (lbm_devmem.hpp): nothing else in these units allocates or frees.
+struct HipMem {
+    static constexpr const char *ALLOC = "hipMalloc", *COPY = "hipMemcpy";
+    static const char* text(hipError_t e) { return e == hipSuccess ? nullptr : hipGetErrorString(e); }
+    static const char* alloc(void** p, size_t bytes) { return text(hipMalloc(p, bytes)); }
+    static void free(void* p) { (void)hipFree(p); }
+    static const char* copy(void* dst, const void* src, size_t bytes) { return text(hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice)); }
+};
+using DevBuf = lbmhost::DevMem<HipMem>;
+
+// The records of a series on the device, [capacity][batch] (empty while it is off), and how many samples it holds and has dropped
+// (series_* in lbm_sampling.hip).
 struct Series {
-    void* dev = nullptr;
+    DevBuf dev;
     size_t sample_bytes = 0;    // one sample: the records of the batch
     long long capacity = 0, count = 0, dropped = 0;
 };
 
-// The tables of the bodies on the device (bodies_upload, lbm_bodies.hip), all inside the one allocation `base`: the link list of every
-// lattice, one after the other; chunks[batch][maxchunks]; first[batch][nbodies + 1], each body's range of chunks; centre[batch][nbodies][2];
-// then the workgroups' partial results of one pass and the records of the one-shot call.
+// The tables of the bodies on the device (body_tables, lbm_bodies.hip), all inside the one allocation `base`, laid out by
+// lbmhost::BodyParts (lbm_bodies.hpp): the link list of every lattice, one after the other; chunks[batch][maxchunks]; first[batch]
+// [nbodies + 1], each body's range of chunks; centre[batch][nbodies][2]; then the workgroups' partial results of one pass and the
+// records of the one-shot call.
 struct BodyTables {
-    void* base = nullptr;
+    DevBuf base;
     const lbmhost::BodyLink* links = nullptr;
     const lbmhost::BodyChunk* chunks = nullptr;
     const int32_t* first = nullptr;
@@ -114,14 +131,36 @@ struct BodyTables {
     int maxchunks = 1;
 };
 
-// The tables of a nonzero body motion on the device (lbm_set_body_motion), all inside the one allocation `base`: cell_row[batch][ny][nx],
-// -1 or the cell's row in delta[rows][8] (the lattice type; slot k - 1: Ladd's term of the cell's link k), and link_delta, one double per
-// entry of BodyTables::links: the same terms as the lattice adds them, for k_body_force.
+// The tables of a nonzero body motion on the device (motion_tables, lbm_body_motion.hip), all inside the one allocation `base`, laid
+// out by lbmhost::MotionParts (lbm_wall_motion.hpp): cell_row[batch][ny][nx], -1 or the cell's row in delta[rows][8] (the lattice
+// type; slot k - 1: Ladd's term of the cell's link k), and link_delta, one double per entry of BodyTables::links: the same terms as
+// the lattice adds them, for k_body_force.
 struct MotionTables {
-    void* base = nullptr;
+    DevBuf base;
     const int32_t* cell_row = nullptr;
     const void* delta = nullptr;
     const double* link_delta = nullptr;
+};
+
+// Solid obstacles (LBM_SEM_BOUNCE_BACK_SOLID; empty in the other semantics).  Three levels of host state, each with what the device
+// holds of it; obstacles_change (lbm_bodies.hip) is the only writer: a change at one level resets the levels below it.
+//   mask    as lbm_set_solid stored it, 0 / 1, [batch][nx][ny] (all fluid in a fresh context); its link plane lives in the lattices
+//   bodies  label[batch][nx][ny], -1 on fluid cells, centre[batch][nbodies][2]; one body that holds every solid cell after
+//           lbm_create and lbm_set_solid.  body: the tables; force_series: the records of lbm_force_begin, [capacity][batch][nbodies]
+//   motion  motion[batch][nbodies][3] = (Ux, Uy, Om), all zero after lbm_create, lbm_set_solid and lbm_set_solid_bodies.  moving: the
+//           tables, empty while every body is at rest -- then the step and the force run the kernels of obstacles that never move
+// force_part: the workgroups' partial results of lbm_solid_force and, behind them, its records (allocated on first use, kept).
+enum class ObsLevel { mask, bodies, motion };
+struct Obstacles {
+    std::vector<uint8_t> mask;
+    int nbodies = 1;
+    std::vector<int32_t> label;
+    std::vector<double> centre;
+    BodyTables body;
+    Series force_series;
+    std::vector<double> motion;
+    MotionTables moving;
+    DevBuf force_part;
 };
 
 // Run state.  What was decided once is in `plan`; p stays for the fields later code branches on (dtype, collision, semantics, turb,
@@ -130,7 +169,7 @@ struct lbm_ctx {
     lbm_ctx(const lbm_params& p_, const Plan& plan_) : p(p_), plan(plan_) {}
     lbm_params p;
     const Plan plan;
-    void* lat[NLAT] = {};       // [0], [1]: the two lattices; [2] .. [8]: frame scratch of the multi-step; [LAT_LAG]: see above
+    DevBuf lat[NLAT];           // [0], [1]: the two lattices; [2] .. [8]: frame scratch of the multi-step; [LAT_LAG]: see above
     int raw[NLAT] = {1, 1, 0, 0, 0, 0, 0, 0, 0, 0};
     int cur = 0;  // lat[cur] is the source of the next step
     long long nsteps = 0;
@@ -142,56 +181,36 @@ struct lbm_ctx {
     bool lag_valid = false;
     hipStream_t s_compute = nullptr, s_comm = nullptr;
     hipEvent_t ev_edges = nullptr, ev_halo = nullptr, ev_int = nullptr, ev_go = nullptr, ev_t0 = nullptr, ev_t1 = nullptr;
-    void* stage = nullptr;
-    size_t stage_bytes = 0;
-    double* red_dev = nullptr;  // lbm_mean_u: partial sums + results
+    DevBuf stage;               // host <-> lattice staging (ensure_stage)
+    DevBuf red_dev;             // lbm_mean_u: partial sums + results
     // The samplers (lbm_sampling.hip).  sampler[i]: the schedule of automatic sampling, which takes the sample of step count n from
     // lat[cur] when a unit would start at n - 1 (step_many) -- the force sampler: when a unit has ended at n; a Series: the records of a
-    // series on the device, null while it is off.
+    // series on the device, empty while it is off.
     lbmhost::Sampler sampler[lbmhost::NSCHEDULED];
-    // Time statistics (lbm_stats_*): six double sums per cell (k_stats_accumulate), null while statistics are off.
-    double* stats_dev = nullptr;
+    // Time statistics (lbm_stats_*): six double sums per cell (k_stats_accumulate), empty while statistics are off.
+    DevBuf stats_dev;
     long long stats_count = 0;  // samples enqueued
     // Run monitor (lbm_monitor*, lbm_monitor.hip): mon_part holds the workgroups' partial results of one pass and, behind them, the
     // records of the one-shot call (allocated on first use, kept).
-    double* mon_part = nullptr;
+    DevBuf mon_part;
     Series mon_series;
     lbm_monitor_spec mon_spec{};
     // Field residual (lbm_residual_*, lbm_residual.hip): res_snap holds the previous sample (ux, uy, rho of every own cell, in the type
-    // lbm_get_fields(res_host_dtype) hands out), res_part the workgroups' partial results of one pass; null while the residual is off.
+    // lbm_get_fields(res_host_dtype) hands out), res_part the workgroups' partial results of one pass; empty while the residual is off.
     // res_prev: the step count of the snapshot (-1: no sample yet).
-    void* res_snap = nullptr;
-    double* res_part = nullptr;
+    DevBuf res_snap, res_part;
     Series res_series;
     int res_host_dtype = LBM_F32;
     long long res_prev = -1;
     // Flow topology (lbm_topology, lbm_get_stream_function; lbm_topology.hip): topo_part holds the block sums, the partial results and
     // the records of the record path, topo_fields the staged psi and omega of the field path; each allocated on first use, kept.
-    double* topo_part = nullptr;
-    double* topo_fields = nullptr;
-    // Solid obstacles (LBM_SEM_BOUNCE_BACK_SOLID, lbm_solid.hip): the mask as lbm_set_solid stored it, 0 / 1, [batch][nx][ny] (all fluid
-    // in a fresh context; empty in the other semantics); force_dev: the workgroups' partial results of lbm_solid_force and, behind
-    // them, its records (allocated on first use, kept).
-    std::vector<uint8_t> solid_mask;
-    double* force_dev = nullptr;
-    // The bodies of the mask (lbm_set_solid_bodies, lbm_bodies.hip): body_label[batch][nx][ny], -1 on fluid cells, body_centre[batch]
-    // [nbodies][2]; one body that holds every solid cell after lbm_create and lbm_set_solid.  body: what the device holds of them;
-    // force_series: the records of lbm_force_begin, [capacity][batch][nbodies].
-    int nbodies = 1;
-    std::vector<int32_t> body_label;
-    std::vector<double> body_centre;
-    BodyTables body;
-    Series force_series;
-    // The motion of the bodies (lbm_set_body_motion, lbm_body_motion.hip): body_motion[batch][nbodies][3] = (Ux, Uy, Om), all zero after
-    // lbm_create, lbm_set_solid and lbm_set_solid_bodies.  motion: the tables on the device, null while every body is at rest -- then the
-    // step and the force run the kernels of a lattice whose obstacles never move.
-    std::vector<double> body_motion;
-    MotionTables motion;
+    DevBuf topo_part, topo_fields;
+    Obstacles obs;              // (above)
     ncclComm_t comm = nullptr;
     int nranks = 1, rank = 0;
     bool loopback = false;      // diagnostic: 1-rank communicator, the slab exchanges halos with itself
     lbmhost::Order order;       // what the two streams carry from one unit to the next (lbm_order.hpp); its device: HipDev below
-    void* relax_dev = nullptr;  // batch > 1: Relax<real>[batch] on the device
+    DevBuf relax_dev;           // batch > 1: Relax<real>[batch] on the device
     std::string err;
 };
 
@@ -216,6 +235,13 @@ struct rccl_api {
 inline int fail(lbm_ctx* c, int code, const std::string& msg) {
     if (c) c->err = msg;
     return code;
+}
+// what DevBuf::alloc / ensure said: "" or the error
+inline int alloc_ok(lbm_ctx* c, const std::string& err) { return err.empty() ? LBM_OK : fail(c, LBM_ERR_NOMEM, err); }
+// The refusal of the obstacle calls in a context of another semantics.
+inline int need_solid(lbm_ctx* c, const char* call) {
+    if (c->p.semantics == LBM_SEM_BOUNCE_BACK_SOLID) return LBM_OK;
+    return fail(c, LBM_ERR_STATE, std::string(call) + ": this context has no solid mask (create it with semantics = LBM_SEM_BOUNCE_BACK_SOLID)");
 }
 
 #define HIP_TRY(c, expr)                                                                               \
@@ -257,15 +283,15 @@ Relax<R> relax_of(const lbm_params& p) {
 
 template <typename R>
 Batch<R> batch_of(const lbm_ctx* c) {
-    return Batch<R>{c->plan.bstride, c->plan.batch > 1 ? (const Relax<R>*)c->relax_dev : nullptr};
+    return Batch<R>{c->plan.bstride, c->plan.batch > 1 ? c->relax_dev.as<const Relax<R>>() : nullptr};
 }
 
 // output lattices of the S frame passes lat[from] -> lat[to]: the scratch lattices (null when never needed, see ensure_scratch), then lat[to]
 template <typename R>
 FramePtrs<R> frame_ptrs(const lbm_ctx* c, int from, int to, int S) {
     FramePtrs<R> fp;
-    fp.src = (const R*)c->lat[from];
-    for (int i = 0; i < 8; ++i) fp.pass[i] = i < S - 1 ? (R*)c->lat[2 + i] : (R*)c->lat[to];
+    fp.src = c->lat[from].as<const R>();
+    for (int i = 0; i < 8; ++i) fp.pass[i] = (i < S - 1 ? c->lat[2 + i] : c->lat[to]).as<R>();
     return fp;
 }
 
@@ -422,8 +448,8 @@ int step_many(lbm_ctx* c, int nsteps);
 // lbm_sampling.hip
 int series_alloc(lbm_ctx* c, Series& s, size_t record_bytes, int capacity, const char* what);
 void* series_slot(Series& s);
-int series_read(lbm_ctx* c, Series lbm_ctx::*series, const char* call, void* records_out, int max_records, long long* count, long long* dropped);
-void series_free(Series& s);
+int series_read(lbm_ctx* c, const Series* (*series)(const lbm_ctx*), const char* call, void* records_out, int max_records, long long* count,
+                long long* dropped);
 int sampler_begin(lbm_ctx* c, int sampler, int every);
 int sample_now(lbm_ctx* c, int sampler, bool on);
 int sample_if_due(lbm_ctx* c);
@@ -432,19 +458,14 @@ void sampler_free(lbm_ctx* c, int sampler);
 int sampler_end(lbm_ctx* c, int sampler);
 // lbm_monitor.hip
 int monitor_series_sample(lbm_ctx* c, int which, long long step);
-void monitor_free(lbm_ctx* c);
-// lbm_topology.hip
-void topology_free(lbm_ctx* c);
 // lbm_solid.hip
 int solid_fix(lbm_ctx* c);
 int solid_copy_links(lbm_ctx* c, int to);
-void solid_free(lbm_ctx* c);
 // lbm_bodies.hip
-int bodies_default(lbm_ctx* c);
-void bodies_free(lbm_ctx* c);
+int obstacles_change(lbm_ctx* c, ObsLevel level, Obstacles& next, int (*before_commit)(lbm_ctx*, const Obstacles&) = nullptr);
 int force_series_sample(lbm_ctx* c);
 // lbm_body_motion.hip
-void motion_rest(lbm_ctx* c);
+int motion_tables(lbm_ctx* c, const Obstacles& next, MotionTables& out);
 // lbm_residual.hip
 int residual_series_sample(lbm_ctx* c, int which, long long step);
 void residual_free(lbm_ctx* c);

@@ -14,13 +14,10 @@ int ensure_scratch(lbm_ctx* c, int n) {
     bool fresh = false;
     for (int i = 2; i < 2 + n && i < LAT_LAG; ++i) {
         if (c->lat[i]) continue;
-        hipError_t e = hipMalloc(&c->lat[i], c->plan.lat_bytes);
-        if (e != hipSuccess) {
-            c->lat[i] = nullptr;
-            return fail(c, LBM_ERR_NOMEM, std::string("hipMalloc(scratch lattice of the frame passes): ") + hipGetErrorString(e));
-        }
-        HIP_TRY(c, hipMemsetAsync(c->lat[i], 0, c->plan.lat_bytes, c->s_compute));
-        const int rc = solid_copy_links(c, i);   // (solid obstacles: every lattice a step or an export reads carries the link plane)
+        int rc = alloc_ok(c, c->lat[i].alloc(c->plan.lat_bytes, "scratch lattice of the frame passes"));
+        if (rc) return rc;
+        HIP_TRY(c, hipMemsetAsync(c->lat[i].get(), 0, c->plan.lat_bytes, c->s_compute));
+        rc = solid_copy_links(c, i);   // (solid obstacles: every lattice a step or an export reads carries the link plane)
         if (rc) return rc;
         fresh = true;
     }
@@ -34,53 +31,48 @@ int launch_rows(lbm_ctx* c, int from, int to, int row0, int stride, int nrows, h
     return launch_variant(c, [&](auto v) {
         using VT = decltype(v);
         using R = typename VT::R;
-        const R* src = (const R*)c->lat[from];
-        R* dst = (R*)c->lat[to];
+        const R* src = c->lat[from].as<const R>();
+        R* dst = c->lat[to].as<R>();
         const int raw = c->raw[from];
+        // the vector kernels: a block per BLK vectors of a row; NT: non-temporal loads and stores
+        constexpr int V = 16 / (int)sizeof(R);
+        const int nxb = (c->plan.geo.nx / V + BLK - 1) / BLK, nblocks = nxb * nrows;
+        const dim3 gvec(nblocks, c->plan.batch);
+        auto by_nt = [&](auto&& launch) {
+            if (c->plan.use_nt) launch(std::true_type{});
+            else launch(std::false_type{});
+        };
         if constexpr (VT::SEM == SEM_SOLID) {
-            if (c->motion.base) {   // (a nonzero lbm_set_body_motion: the same two routes with the moving-wall term in their stores)
-                const int32_t* rows = c->motion.cell_row;
-                const R* delta = (const R*)c->motion.delta;
-                if (c->plan.use_vec) {
-                    constexpr int V = 16 / (int)sizeof(R);
-                    const int nxb = (c->plan.geo.nx / V + BLK - 1) / BLK, nblocks = nxb * nrows;
-                    if (c->plan.use_nt)
-                        hipLaunchKernelGGL((k_step_solid_move<R, VT::COLL, true>), dim3(nblocks, c->plan.batch), dim3(BLK), 0, s, src, dst, c->plan.geo,
-                                           relax_of<R>(c->p), batch_of<R>(c), raw, row0, stride, nxb, nblocks, rows, delta);
-                    else
-                        hipLaunchKernelGGL((k_step_solid_move<R, VT::COLL, false>), dim3(nblocks, c->plan.batch), dim3(BLK), 0, s, src, dst, c->plan.geo,
-                                           relax_of<R>(c->p), batch_of<R>(c), raw, row0, stride, nxb, nblocks, rows, delta);
-                } else {
-                    hipLaunchKernelGGL((k_step_generic_move<R, VT::COLL>), grid_rows(c, nrows), dim3(BLK), 0, s, src, dst, c->plan.geo, relax_of<R>(c->p),
-                                       batch_of<R>(c), raw, row0, stride, rows, delta);
-                }
-                return;
-            }
+            // (a nonzero lbm_set_body_motion: the same two routes with the moving-wall term in their stores)
+            const MotionTables& m = c->obs.moving;
+            const bool moving = (bool)m.base;
+            const R* delta = (const R*)m.delta;
             if (c->plan.use_vec) {   // (nx a multiple of the vector width, kernel = AUTO: plan_kernel)
-                constexpr int V = 16 / (int)sizeof(R);
-                const int nxb = (c->plan.geo.nx / V + BLK - 1) / BLK, nblocks = nxb * nrows;
-                if (c->plan.use_nt)
-                    hipLaunchKernelGGL((k_step_solid<R, VT::COLL, true>), dim3(nblocks, c->plan.batch), dim3(BLK), 0, s, src, dst, c->plan.geo,
-                                       relax_of<R>(c->p), batch_of<R>(c), raw, row0, stride, nxb, nblocks);
-                else
-                    hipLaunchKernelGGL((k_step_solid<R, VT::COLL, false>), dim3(nblocks, c->plan.batch), dim3(BLK), 0, s, src, dst, c->plan.geo,
-                                       relax_of<R>(c->p), batch_of<R>(c), raw, row0, stride, nxb, nblocks);
+                by_nt([&](auto nt) {
+                    constexpr bool NT = decltype(nt)::value;
+                    if (moving)
+                        hipLaunchKernelGGL((k_step_solid_move<R, VT::COLL, NT>), gvec, dim3(BLK), 0, s, src, dst, c->plan.geo, relax_of<R>(c->p),
+                                           batch_of<R>(c), raw, row0, stride, nxb, nblocks, m.cell_row, delta);
+                    else
+                        hipLaunchKernelGGL((k_step_solid<R, VT::COLL, NT>), gvec, dim3(BLK), 0, s, src, dst, c->plan.geo, relax_of<R>(c->p),
+                                           batch_of<R>(c), raw, row0, stride, nxb, nblocks);
+                });
+                return;
+            }
+            if (moving) {
+                hipLaunchKernelGGL((k_step_generic_move<R, VT::COLL>), grid_rows(c, nrows), dim3(BLK), 0, s, src, dst, c->plan.geo, relax_of<R>(c->p),
+                                   batch_of<R>(c), raw, row0, stride, m.cell_row, delta);
                 return;
             }
         }
-        if (VT::SEM == SEM_GPU && c->plan.use_vec) {
-            constexpr int V = 16 / (int)sizeof(R);
-            const int nxb = (c->plan.geo.nx / V + BLK - 1) / BLK, nblocks = nxb * nrows;
-            if (c->plan.use_nt)
-                hipLaunchKernelGGL((k_step_vec<R, VT::COLL, V, true, VT::TURB>), dim3(nblocks, c->plan.batch), dim3(BLK), 0, s, src, dst, c->plan.geo,
+        if (VT::SEM == SEM_GPU && c->plan.use_vec)
+            by_nt([&](auto nt) {
+                hipLaunchKernelGGL((k_step_vec<R, VT::COLL, V, decltype(nt)::value, VT::TURB>), gvec, dim3(BLK), 0, s, src, dst, c->plan.geo,
                                    relax_of<R>(c->p), batch_of<R>(c), raw, row0, stride, nxb, nblocks);
-            else
-                hipLaunchKernelGGL((k_step_vec<R, VT::COLL, V, false, VT::TURB>), dim3(nblocks, c->plan.batch), dim3(BLK), 0, s, src, dst, c->plan.geo,
-                                   relax_of<R>(c->p), batch_of<R>(c), raw, row0, stride, nxb, nblocks);
-        } else {
-            hipLaunchKernelGGL((k_step_generic<R, VT::COLL, VT::SEM, VT::TURB>), grid_rows(c, nrows), dim3(BLK), 0, s, src, dst,
-                               c->plan.geo, relax_of<R>(c->p), batch_of<R>(c), raw, row0, stride);
-        }
+            });
+        else
+            hipLaunchKernelGGL((k_step_generic<R, VT::COLL, VT::SEM, VT::TURB>), grid_rows(c, nrows), dim3(BLK), 0, s, src, dst, c->plan.geo,
+                               relax_of<R>(c->p), batch_of<R>(c), raw, row0, stride);
     });
 }
 
@@ -94,7 +86,7 @@ int launch_frame(lbm_ctx* c, int from, int to, int W, hipStream_t s, int elo, in
         const long long cells = (2LL * W + elo + ehi) * (vec_rows ? c->plan.geo.nx / V : c->plan.geo.nx) + 2LL * W * (c->plan.geo.ny - 2 * W);
         if constexpr (sem_multi_step(VT::SEM))
             hipLaunchKernelGGL((k_step_frame<R, VT::COLL, VT::SEM, VT::TURB>), dim3((unsigned)((cells + BLK - 1) / BLK), c->plan.batch), dim3(BLK), 0, s,
-                               (const R*)c->lat[from], (R*)c->lat[to], c->plan.geo, relax_of<R>(c->p), batch_of<R>(c), W, elo, ehi, vec_rows);
+                               c->lat[from].as<const R>(), c->lat[to].as<R>(), c->plan.geo, relax_of<R>(c->p), batch_of<R>(c), W, elo, ehi, vec_rows);
     });
 }
 
@@ -149,8 +141,8 @@ static int launch_k_stream(lbm_ctx* c, int from, int to, hipStream_t s, int S, c
         using VT = decltype(v);
         using R = typename VT::R;
         if constexpr (sem_multi_step(VT::SEM, true))
-        hipLaunchKernelGGL((k_stream<R, VT::COLL, VT::SEM, VT::TURB>), dim3(fl.nframe + pl.nstrips * nseg), dim3(ST_NT), 0, s, (const R*)c->lat[from],
-                           (R*)c->lat[to], c->plan.geo, relax_of<R>(c->p), S, fl.F, c->plan.geo.nx - fl.F, ye, pl.nstrips, pl.H, frame_ptrs<R>(c, from, to, S),
+        hipLaunchKernelGGL((k_stream<R, VT::COLL, VT::SEM, VT::TURB>), dim3(fl.nframe + pl.nstrips * nseg), dim3(ST_NT), 0, s, c->lat[from].as<const R>(),
+                           c->lat[to].as<R>(), c->plan.geo, relax_of<R>(c->p), S, fl.F, c->plan.geo.nx - fl.F, ye, pl.nstrips, pl.H, frame_ptrs<R>(c, from, to, S),
                            fl.nframe, fl.nsegx, fl.nsegy, fl.L, fl.in_lds ? 1 : 0, lo, hi, bands, xcd_bands ? 1 : 0);
     });
 }
@@ -165,8 +157,8 @@ static int launch_walls(lbm_ctx* c, int from, int to, hipStream_t s, int S, int 
         using VT = decltype(v);
         using R = typename VT::R;
         if constexpr (VT::SEM == SEM_GPU) {
-            const R* src = (const R*)c->lat[from];
-            R* dst = (R*)c->lat[to];
+            const R* src = c->lat[from].as<const R>();
+            R* dst = c->lat[to].as<R>();
             if (is_slab(c->plan))
                 hipLaunchKernelGGL((k_stream_walls_slab<R, VT::COLL, VT::TURB>), dim3(pl.nstrips * (bands ? (bands & 1) + (bands >> 1) : pl.nsegy)),
                                    dim3(ST_NT), 0, s, src, dst, c->plan.geo, relax_of<R>(c->p), S, pl.nstrips, pl.H, bands ? 0 : xcd, ybeg, yend, bands,
@@ -246,8 +238,8 @@ int launch_deep(lbm_ctx* c, int from, int to, hipStream_t s, int steps, bool wit
             using R = typename VT::R;
             constexpr int V = 16 / (int)sizeof(R), TX = tb_txv<VT::TURB>() * V, TY = tb_ty<VT::TURB>();
             const int ntx = (xe - TB_F + TX - 1) / TX, nty = (ye - TB_F + TY - 1) / TY;   // two steps: F = TB_F
-            hipLaunchKernelGGL((k_step2_deep<R, VT::COLL, VT::TURB>), dim3(ntx * nty, c->plan.batch), dim3(TB_NT), 0, s, (const R*)c->lat[from],
-                               (R*)c->lat[to], c->plan.geo, relax_of<R>(c->p), batch_of<R>(c), xe, ye, ntx, ntx * nty);
+            hipLaunchKernelGGL((k_step2_deep<R, VT::COLL, VT::TURB>), dim3(ntx * nty, c->plan.batch), dim3(TB_NT), 0, s, c->lat[from].as<const R>(),
+                               c->lat[to].as<R>(), c->plan.geo, relax_of<R>(c->p), batch_of<R>(c), xe, ye, ntx, ntx * nty);
         });
     const int S_tile = steps == 4 || steps == 5 ? steps : 3;
     FrameLayout fl;
@@ -262,7 +254,7 @@ int launch_deep(lbm_ctx* c, int from, int to, hipStream_t s, int steps, bool wit
             const int ntx = (xe - F + TX - 1) / TX, nty = (ye - F + TY - 1) / TY;
             if constexpr (sem_multi_step(VT::SEM))
             hipLaunchKernelGGL((k_stepS_deep<R, VT::COLL, VT::SEM, S, false, VT::TURB>), dim3(fl.nframe + ntx * nty, c->plan.batch), dim3(512), 0, s,
-                               (const R*)c->lat[from], (R*)c->lat[to], c->plan.geo, relax_of<R>(c->p), batch_of<R>(c), F, xe, ye, ntx, ntx * nty,
+                               c->lat[from].as<const R>(), c->lat[to].as<R>(), c->plan.geo, relax_of<R>(c->p), batch_of<R>(c), F, xe, ye, ntx, ntx * nty,
                                frame_ptrs<R>(c, from, to, S), fl.nframe, fl.nsegx, fl.nsegy, fl.L, fl.in_lds ? 1 : 0);
         };
         if (S_tile == 4) go(std::integral_constant<int, 4>{});
@@ -356,10 +348,10 @@ int prev_lattice(lbm_ctx* c, int* which) {
     *which = LAT_LAG;
     if (c->lag_valid) return LBM_OK;
     if (!c->lat[LAT_LAG]) {
-        hipError_t e = hipMalloc(&c->lat[LAT_LAG], c->plan.lat_bytes);
-        if (e != hipSuccess) return fail(c, LBM_ERR_NOMEM, std::string("hipMalloc(lag lattice): ") + hipGetErrorString(e));
-        HIP_TRY(c, hipMemsetAsync(c->lat[LAT_LAG], 0, c->plan.lat_bytes, c->s_compute));
-        const int rc = solid_copy_links(c, LAT_LAG);
+        int rc = alloc_ok(c, c->lat[LAT_LAG].alloc(c->plan.lat_bytes, "lag lattice"));
+        if (rc) return rc;
+        HIP_TRY(c, hipMemsetAsync(c->lat[LAT_LAG].get(), 0, c->plan.lat_bytes, c->s_compute));
+        rc = solid_copy_links(c, LAT_LAG);
         if (rc) return rc;
     }
     const int k = c->lag, from = c->cur ^ 1;
@@ -399,10 +391,10 @@ int push_step(lbm_ctx* c) {
         using R = typename VT::R;
         const dim3 g = grid_rows(c, c->plan.geo.ny);
         if constexpr (!sem_is_bb(VT::SEM)) {   // (validate_params refuses the push scheme with bounce-back walls)
-            hipLaunchKernelGGL((k_push_collide<R, VT::COLL, VT::SEM>), g, dim3(BLK), 0, c->s_compute, (const R*)c->lat[c->cur], (R*)c->lat[2], c->plan.geo,
+            hipLaunchKernelGGL((k_push_collide<R, VT::COLL, VT::SEM>), g, dim3(BLK), 0, c->s_compute, c->lat[c->cur].as<const R>(), c->lat[2].as<R>(), c->plan.geo,
                                relax_of<R>(c->p));
-            hipLaunchKernelGGL((k_push_bc<R, VT::COLL, VT::SEM>), g, dim3(BLK), 0, c->s_compute, (const R*)c->lat[c->cur], (R*)c->lat[2],
-                               (R*)c->lat[c->cur ^ 1], c->plan.geo, (R)c->p.uLB);
+            hipLaunchKernelGGL((k_push_bc<R, VT::COLL, VT::SEM>), g, dim3(BLK), 0, c->s_compute, c->lat[c->cur].as<const R>(), c->lat[2].as<R>(),
+                               c->lat[c->cur ^ 1].as<R>(), c->plan.geo, (R)c->p.uLB);
         }
     });
     if (rc) return rc;
@@ -413,7 +405,7 @@ int push_step(lbm_ctx* c) {
 // ftemp starts as a copy of fin (MRT_GPU.py:324)
 int push_reset(lbm_ctx* c) {
     if (!c->plan.push) return LBM_OK;
-    HIP_TRY(c, hipMemcpyAsync(c->lat[2], c->lat[0], (size_t)c->plan.bstride * c->plan.es, hipMemcpyDeviceToDevice, c->s_compute));
+    HIP_TRY(c, hipMemcpyAsync(c->lat[2].get(), c->lat[0].get(), (size_t)c->plan.bstride * c->plan.es, hipMemcpyDeviceToDevice, c->s_compute));
     return LBM_OK;
 }
 

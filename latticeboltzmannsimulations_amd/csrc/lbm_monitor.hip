@@ -46,17 +46,11 @@ static int mon_blocks(const lbm_ctx* c) {
 
 // the partial results of one pass, and behind them the records of the one-shot call
 static int ensure_partials(lbm_ctx* c) {
-    if (c->mon_part) return LBM_OK;
     const size_t bytes = (size_t)c->plan.batch * ((size_t)MON_BLOCKS * MON_VALS * sizeof(double) + sizeof(lbm_monitor_record));
-    hipError_t e = hipMalloc((void**)&c->mon_part, bytes);
-    if (e != hipSuccess) {
-        c->mon_part = nullptr;
-        return fail(c, LBM_ERR_NOMEM, std::string("hipMalloc(monitor): ") + hipGetErrorString(e));
-    }
-    return LBM_OK;
+    return alloc_ok(c, c->mon_part.ensure(bytes, "monitor"));
 }
 static lbm_monitor_record* one_shot_records(lbm_ctx* c) {
-    return (lbm_monitor_record*)(c->mon_part + (size_t)c->plan.batch * MON_BLOCKS * MON_VALS);
+    return (lbm_monitor_record*)(c->mon_part.as<double>() + (size_t)c->plan.batch * MON_BLOCKS * MON_VALS);
 }
 
 // One sample of lat[which] (the lattice whose gathered populations are the state the sampled iteration starts from) into rec[batch],
@@ -69,9 +63,9 @@ static int monitor_enqueue(lbm_ctx* c, int which, const lbm_monitor_spec& spec, 
         using VT = decltype(v);
         using R = typename VT::R;
         hipLaunchKernelGGL((k_monitor<R, VT::SEM, coll_is_prom(VT::COLL)>), dim3(blocks, 1, c->plan.batch), dim3(BLK), 0, c->s_compute,
-                           (const R*)c->lat[which], c->plan.geo, c->raw[which], (R)c->p.uLB, den, c->plan.bstride, sp, c->mon_part);
+                           c->lat[which].as<const R>(), c->plan.geo, c->raw[which], (R)c->p.uLB, den, c->plan.bstride, sp, c->mon_part.as<double>());
         hipLaunchKernelGGL((k_monitor_final<R, VT::SEM, coll_is_prom(VT::COLL)>), dim3(c->plan.batch), dim3(RED_WAVE), 0, c->s_compute,
-                           (const double*)c->mon_part, blocks, (const R*)c->lat[which], c->plan.geo, c->raw[which], (R)c->p.uLB, c->plan.bstride, sp,
+                           c->mon_part.as<const double>(), blocks, c->lat[which].as<const R>(), c->plan.geo, c->raw[which], (R)c->p.uLB, c->plan.bstride, sp,
                            (double)step, (double*)rec);
     });
 }
@@ -86,11 +80,6 @@ int monitor_series_sample(lbm_ctx* c, int which, long long step) {
     return LBM_OK;
 }
 
-// (lbm_destroy, beside sampler_free)
-void monitor_free(lbm_ctx* c) {
-    if (c->mon_part) (void)hipFree(c->mon_part);
-    c->mon_part = nullptr;
-}
 }  // namespace lbmhost
 
 using namespace lbmhost;
@@ -135,7 +124,7 @@ int lbm_monitor_begin(lbm_ctx* c, const lbm_monitor_spec* spec, int every, int c
 int lbm_monitor_sample(lbm_ctx* c) { return sample_now(c, SMP_MONITOR, c && c->mon_series.dev); }
 
 int lbm_monitor_read(lbm_ctx* c, lbm_monitor_record* records_out, int max_records, long long* count, long long* dropped) {
-    return series_read(c, &lbm_ctx::mon_series, "lbm_monitor_read", records_out, max_records, count, dropped);
+    return series_read(c, [](const lbm_ctx* x) { return &x->mon_series; }, "lbm_monitor_read", records_out, max_records, count, dropped);
 }
 
 int lbm_monitor_end(lbm_ctx* c) { return sampler_end(c, SMP_MONITOR); }
@@ -162,11 +151,11 @@ int lbm_get_lines(lbm_ctx* c, int x, int gy, void* col_out, void* row_out, int h
         using VT = decltype(v);
         using R = typename VT::R;
         hipLaunchKernelGGL((k_export_lines<R, VT::SEM, coll_is_prom(VT::COLL)>), dim3((ny + nx + BLK - 1) / BLK, 1, B), dim3(BLK), 0, c->s_compute,
-                           (const R*)c->lat[which], c->plan.geo, c->raw[which], (R)c->p.uLB, c->plan.bstride, cx, ly, (R*)c->stage);
+                           c->lat[which].as<const R>(), c->plan.geo, c->raw[which], (R)c->p.uLB, c->plan.bstride, cx, ly, c->stage.as<R>());
     });
     if (rc) return rc;
     std::vector<char> tmp(per * B * c->plan.es);
-    HIP_TRY(c, hipMemcpyAsync(tmp.data(), c->stage, tmp.size(), hipMemcpyDeviceToHost, c->s_compute));
+    HIP_TRY(c, hipMemcpyAsync(tmp.data(), c->stage.get(), tmp.size(), hipMemcpyDeviceToHost, c->s_compute));
     HIP_TRY(c, hipStreamSynchronize(c->s_compute));
     // staging of lattice b: [3][ny] of the column, then [3][nx] of the row, in the lattice's type; the host arrays in host_dtype
     auto put = [&](void* dst, size_t di, size_t si) {

@@ -532,7 +532,7 @@ int lbm_describe(const lbm_ctx* c, char* buf, size_t len) {
     int nlat = 0;
     for (int i = 0; i < NLAT; ++i) nlat += c->lat[i] ? 1 : 0;
     const int n = describe_plan(c->plan, nlat, buf, len);
-    if (n < 0 || !c->motion.base) return n;
+    if (n < 0 || !c->obs.moving.base) return n;
     // (a nonzero lbm_set_body_motion: the single steps run k_step_solid_move / k_step_generic_move)
     const int m = std::snprintf(buf + n, len - (size_t)n, " wall_motion=1");
     return m < 0 ? n : std::min<int>(n + m, (int)len - 1);

@@ -31,13 +31,13 @@ int residual_series_sample(lbm_ctx* c, int which, long long step) {
         const dim3 grid(blocks, 1, c->plan.batch);
         if constexpr (std::is_same<R, double>::value) {
             if (!snap_is_f32(c)) {
-                hipLaunchKernelGGL((k_residual<double, double, VT::SEM, PROM>), grid, dim3(BLK), 0, c->s_compute, (const double*)c->lat[which],
-                                   c->plan.geo, c->raw[which], (double)c->p.uLB, c->plan.bstride, (double*)c->res_snap, c->res_part);
+                hipLaunchKernelGGL((k_residual<double, double, VT::SEM, PROM>), grid, dim3(BLK), 0, c->s_compute, c->lat[which].as<const double>(),
+                                   c->plan.geo, c->raw[which], (double)c->p.uLB, c->plan.bstride, c->res_snap.as<double>(), c->res_part.as<double>());
                 return;
             }
         }
-        hipLaunchKernelGGL((k_residual<R, float, VT::SEM, PROM>), grid, dim3(BLK), 0, c->s_compute, (const R*)c->lat[which], c->plan.geo,
-                           c->raw[which], (R)c->p.uLB, c->plan.bstride, (float*)c->res_snap, c->res_part);
+        hipLaunchKernelGGL((k_residual<R, float, VT::SEM, PROM>), grid, dim3(BLK), 0, c->s_compute, c->lat[which].as<const R>(), c->plan.geo,
+                           c->raw[which], (R)c->p.uLB, c->plan.bstride, c->res_snap.as<float>(), c->res_part.as<double>());
     });
     if (rc) return rc;
     const long long prev = c->res_prev;
@@ -45,20 +45,18 @@ int residual_series_sample(lbm_ctx* c, int which, long long step) {
     if (prev < 0) return LBM_OK;   // the first sample only fills the snapshot
     void* slot = series_slot(c->res_series);
     if (!slot) return LBM_OK;
-    hipLaunchKernelGGL(k_residual_final, dim3(c->plan.batch), dim3(RED_WAVE), 0, c->s_compute, (const double*)c->res_part, blocks, (double)step,
+    hipLaunchKernelGGL(k_residual_final, dim3(c->plan.batch), dim3(RED_WAVE), 0, c->s_compute, c->res_part.as<const double>(), blocks, (double)step,
                        (double)prev, (double*)slot);
     HIP_TRY(c, hipGetLastError());
     ++c->res_series.count;
     return LBM_OK;
 }
 
-// What lbm_residual_begin allocated (sampler_free).
+// The residual off (sampler_free): what lbm_residual_begin allocated, and no snapshot.
 void residual_free(lbm_ctx* c) {
-    if (c->res_snap) (void)hipFree(c->res_snap);
-    if (c->res_part) (void)hipFree(c->res_part);
-    series_free(c->res_series);
-    c->res_snap = nullptr;
-    c->res_part = nullptr;
+    c->res_snap.release();
+    c->res_part.release();
+    c->res_series = Series{};
     c->res_prev = -1;
 }
 }  // namespace lbmhost
@@ -76,16 +74,15 @@ int lbm_residual_begin(lbm_ctx* c, int host_dtype, int every, int capacity) {
     c->res_host_dtype = host_dtype;
     const size_t snap_bytes = (size_t)c->plan.batch * 3 * (size_t)snap_groups(c) * 16;
     const size_t part_bytes = (size_t)c->plan.batch * RES_BLOCKS * RES_VALS * sizeof(double);
-    hipError_t e = hipMalloc(&c->res_snap, snap_bytes);
-    if (e == hipSuccess) e = hipMalloc((void**)&c->res_part, part_bytes);
-    rc = e == hipSuccess ? series_alloc(c, c->res_series, sizeof(lbm_residual_record), capacity, "residual series")
-                         : fail(c, LBM_ERR_NOMEM, std::string("hipMalloc(residual): ") + hipGetErrorString(e));
+    rc = alloc_ok(c, c->res_snap.alloc(snap_bytes, "residual"));
+    if (rc == LBM_OK) rc = alloc_ok(c, c->res_part.alloc(part_bytes, "residual"));
+    if (rc == LBM_OK) rc = series_alloc(c, c->res_series, sizeof(lbm_residual_record), capacity, "residual series");
     if (rc) {
         sampler_free(c, SMP_RESIDUAL);
         return rc;
     }
     // (the first sample reads the snapshot like every other and discards what it reduces: give it defined values)
-    HIP_TRY(c, hipMemsetAsync(c->res_snap, 0, snap_bytes, c->s_compute));
+    HIP_TRY(c, hipMemsetAsync(c->res_snap.get(), 0, snap_bytes, c->s_compute));
     c->sampler[SMP_RESIDUAL].arm(c->nsteps, every);
     return LBM_OK;
 }
@@ -93,7 +90,7 @@ int lbm_residual_begin(lbm_ctx* c, int host_dtype, int every, int capacity) {
 int lbm_residual_sample(lbm_ctx* c) { return sample_now(c, SMP_RESIDUAL, c && c->res_snap); }
 
 int lbm_residual_read(lbm_ctx* c, lbm_residual_record* records_out, int max_records, long long* count, long long* dropped) {
-    return series_read(c, &lbm_ctx::res_series, "lbm_residual_read", records_out, max_records, count, dropped);
+    return series_read(c, [](const lbm_ctx* x) { return &x->res_series; }, "lbm_residual_read", records_out, max_records, count, dropped);
 }
 
 int lbm_residual_end(lbm_ctx* c) { return sampler_end(c, SMP_RESIDUAL); }

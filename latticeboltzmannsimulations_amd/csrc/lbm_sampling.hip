@@ -9,25 +9,23 @@ namespace lbmhost {
 // Room for `capacity` samples of batch records each; s is off.
 int series_alloc(lbm_ctx* c, Series& s, size_t record_bytes, int capacity, const char* what) {
     const size_t sample_bytes = record_bytes * c->plan.batch;
-    hipError_t e = hipMalloc(&s.dev, (size_t)capacity * sample_bytes);
-    if (e != hipSuccess) {
-        s.dev = nullptr;
-        return fail(c, LBM_ERR_NOMEM, std::string("hipMalloc(") + what + "): " + hipGetErrorString(e));
-    }
+    const int rc = alloc_ok(c, s.dev.alloc((size_t)capacity * sample_bytes, what));
+    if (rc) return rc;
     s.sample_bytes = sample_bytes;
     s.capacity = capacity;
     return LBM_OK;
 }
 // The slot of the next sample (the caller counts it once it is enqueued), or null: the buffer is full, the sample is counted as dropped.
 void* series_slot(Series& s) {
-    if (s.count < s.capacity) return (char*)s.dev + (size_t)s.count * s.sample_bytes;
+    if (s.count < s.capacity) return s.dev.as<char>() + (size_t)s.count * s.sample_bytes;
     ++s.dropped;
     return nullptr;
 }
-// lbm_monitor_read / lbm_residual_read
-int series_read(lbm_ctx* c, Series lbm_ctx::*series, const char* call, void* records_out, int max_records, long long* count, long long* dropped) {
+// lbm_monitor_read / lbm_residual_read / lbm_force_read.  series(c): the context's series, asked for once c is known not to be null.
+int series_read(lbm_ctx* c, const Series* (*series)(const lbm_ctx*), const char* call, void* records_out, int max_records, long long* count,
+                long long* dropped) {
     if (!c || max_records < 0 || (max_records > 0 && !records_out)) return fail(c, LBM_ERR_INVALID, std::string(call) + ": bad argument");
-    const Series& s = c->*series;
+    const Series& s = *series(c);
     if (!s.dev) return fail(c, LBM_ERR_STATE, std::string(call) + ": no series is on (the matching _begin call)");
     HIP_TRY(c, hipSetDevice(c->p.device));
     const int rc = sync_all(c);
@@ -35,13 +33,8 @@ int series_read(lbm_ctx* c, Series lbm_ctx::*series, const char* call, void* rec
     if (count) *count = s.count;
     if (dropped) *dropped = s.dropped;
     const long long n = std::min<long long>(s.count, max_records);
-    if (n > 0) HIP_TRY(c, hipMemcpy(records_out, s.dev, (size_t)n * s.sample_bytes, hipMemcpyDeviceToHost));
+    if (n > 0) HIP_TRY(c, hipMemcpy(records_out, s.dev.get(), (size_t)n * s.sample_bytes, hipMemcpyDeviceToHost));
     return LBM_OK;
-}
-// The caller has synchronised the streams.
-void series_free(Series& s) {
-    if (s.dev) (void)hipFree(s.dev);
-    s = Series{};
 }
 
 // ---- the three samplers ----
@@ -64,7 +57,7 @@ static int stats_accumulate(lbm_ctx* c, int which) {
         using VT = decltype(v);
         using R = typename VT::R;
         hipLaunchKernelGGL((k_stats_accumulate<R, VT::SEM, coll_is_prom(VT::COLL)>), dim3(blocks, 1, c->plan.batch), dim3(BLK), 0, c->s_compute,
-                           (const R*)c->lat[which], c->plan.geo, c->raw[which], (R)c->p.uLB, c->plan.bstride, c->stats_dev);
+                           c->lat[which].as<const R>(), c->plan.geo, c->raw[which], (R)c->p.uLB, c->plan.bstride, c->stats_dev.as<double>());
     });
     if (rc) return rc;
     ++c->stats_count;
@@ -130,13 +123,12 @@ int sample_after_unit(lbm_ctx* c) {
 // destroy).  The caller has synchronised the streams.
 void sampler_free(lbm_ctx* c, int sampler) {
     if (sampler == SMP_STATS) {
-        if (c->stats_dev) (void)hipFree(c->stats_dev);
-        c->stats_dev = nullptr;
+        c->stats_dev.release();
         c->stats_count = 0;
     } else if (sampler == SMP_MONITOR) {
-        series_free(c->mon_series);
+        c->mon_series = Series{};
     } else if (sampler == SMP_FORCE) {
-        series_free(c->force_series);
+        c->obs.force_series = Series{};
     } else {
         residual_free(c);
     }
@@ -162,14 +154,8 @@ int lbm_stats_begin(lbm_ctx* c, int every) {
     const int rc = sampler_begin(c, SMP_STATS, every);
     if (rc) return rc;
     const size_t bytes = (size_t)c->plan.batch * 6 * c->plan.geo.ny * (2 * ((c->plan.geo.nx + 1) / 2)) * sizeof(double);
-    if (!c->stats_dev) {
-        hipError_t e = hipMalloc((void**)&c->stats_dev, bytes);
-        if (e != hipSuccess) {
-            c->stats_dev = nullptr;
-            return fail(c, LBM_ERR_NOMEM, std::string("hipMalloc(statistics): ") + hipGetErrorString(e));
-        }
-    }
-    HIP_TRY(c, hipMemsetAsync(c->stats_dev, 0, bytes, c->s_compute));
+    if (const int bad = alloc_ok(c, c->stats_dev.ensure(bytes, "statistics"))) return bad;
+    HIP_TRY(c, hipMemsetAsync(c->stats_dev.get(), 0, bytes, c->s_compute));
     c->stats_count = 0;
     c->sampler[SMP_STATS].arm(c->nsteps, every);
     return LBM_OK;
@@ -195,7 +181,7 @@ int lbm_stats_get(lbm_ctx* c, double* mean_u, double* mean_rho, double* second, 
                         : q == 2 ? (mean_rho ? mean_rho + (size_t)b * hn : nullptr)
                                  : (second ? second + ((size_t)b * 3 + q - 3) * hn : nullptr);
             if (!dst) continue;
-            HIP_TRY(c, hipMemcpy(pl.data(), c->stats_dev + ((size_t)b * 6 + q) * dn, dn * sizeof(double), hipMemcpyDeviceToHost));
+            HIP_TRY(c, hipMemcpy(pl.data(), c->stats_dev.as<double>() + ((size_t)b * 6 + q) * dn, dn * sizeof(double), hipMemcpyDeviceToHost));
             for (int x = 0; x < nx; ++x)
                 for (int y = 0; y < ny; ++y) dst[(size_t)x * NY + y0 + y] = pl[(size_t)y * nxa + x] / n;
         }

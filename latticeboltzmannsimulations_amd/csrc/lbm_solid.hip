@@ -105,7 +105,7 @@ int solid_fix(lbm_ctx* c) {
     if (c->p.semantics != LBM_SEM_BOUNCE_BACK_SOLID) return LBM_OK;
     return launch_variant(c, [&](auto v) {
         using R = typename decltype(v)::R;
-        hipLaunchKernelGGL((k_solid_fix<R>), grid_rows(c, c->plan.geo.ny), dim3(BLK), 0, c->s_compute, (R*)c->lat[0], (R*)c->lat[1], c->plan.geo,
+        hipLaunchKernelGGL((k_solid_fix<R>), grid_rows(c, c->plan.geo.ny), dim3(BLK), 0, c->s_compute, c->lat[0].as<R>(), c->lat[1].as<R>(), c->plan.geo,
                            c->plan.bstride);
     });
 }
@@ -123,13 +123,8 @@ int solid_copy_links(lbm_ctx* c, int to) {
     const size_t pitch = (by_rows ? (size_t)g.row : (size_t)c->plan.bstride) * es;
     const size_t height = by_rows ? rows * c->plan.batch : (size_t)c->plan.batch;
     const size_t off = (size_t)K_LINK * g.plane * es;
-    HIP_TRY(c, hipMemcpy2DAsync((char*)c->lat[to] + off, pitch, (const char*)c->lat[0] + off, pitch, width, height, hipMemcpyDeviceToDevice, c->s_compute));
+    HIP_TRY(c, hipMemcpy2DAsync(c->lat[to].as<char>() + off, pitch, c->lat[0].as<const char>() + off, pitch, width, height, hipMemcpyDeviceToDevice, c->s_compute));
     return LBM_OK;
-}
-
-void solid_free(lbm_ctx* c) {
-    if (c->force_dev) (void)hipFree(c->force_dev);
-    c->force_dev = nullptr;
 }
 
 // The link words of one lattice from its mask m[nx][ny] (0 / 1), as the lattice stores them: [ny][nx], x fastest.
@@ -148,19 +143,28 @@ static void link_words(const uint8_t* m, int nx, int ny, R* out) {
 
 // mask: 0 / 1, [batch][nx][ny]
 template <typename R>
-static int upload_links(lbm_ctx* c, const uint8_t* mask) {
+static int upload_links_as(lbm_ctx* c, const uint8_t* mask) {
     const Geo& g = c->plan.geo;
     const size_t n = (size_t)g.nx * g.ny;
     std::vector<R> words(n);
     for (int b = 0; b < c->plan.batch; ++b) {
         link_words<R>(mask + (size_t)b * n, g.nx, g.ny, words.data());
         for (int l = 0; l < 2; ++l) {   // plane K_LINK of both lattices: rows of nx words, geo.row elements apart
-            R* dst = (R*)c->lat[l] + (size_t)b * c->plan.bstride + K_LINK * g.plane + g.at(0, 0);
+            R* dst = c->lat[l].as<R>() + (size_t)b * c->plan.bstride + K_LINK * g.plane + g.at(0, 0);
             HIP_TRY(c, hipMemcpy2D(dst, (size_t)g.row * sizeof(R), words.data(), (size_t)g.nx * sizeof(R), (size_t)g.nx * sizeof(R), (size_t)g.ny,
                                    hipMemcpyHostToDevice));
         }
     }
     return LBM_OK;
+}
+
+// The link planes of next.mask into every lattice the context holds, before obstacles_change commits it.  A copy that fails part-way
+// leaves the planes of the two lattices in an undefined mix of the old and the new mask: the call returns LBM_ERR_HIP, lbm_get_solid
+// still reports the old mask, and the context must be given a mask again (or destroyed) before it steps.
+static int upload_links(lbm_ctx* c, const Obstacles& next) {
+    int rc = c->plan.es == 4 ? upload_links_as<float>(c, next.mask.data()) : upload_links_as<double>(c, next.mask.data());
+    for (int i = 2; i < NLAT && rc == LBM_OK; ++i) rc = solid_copy_links(c, i);   // (the lattices allocated since: scratch, the lagged one)
+    return rc ? rc : sync_all(c);
 }
 }  // namespace lbmhost
 
@@ -170,8 +174,8 @@ extern "C" {
 
 int lbm_set_solid(lbm_ctx* c, const uint8_t* mask) {
     if (!c || !mask) return fail(c, LBM_ERR_INVALID, "lbm_set_solid: bad argument");
-    if (c->p.semantics != LBM_SEM_BOUNCE_BACK_SOLID)
-        return fail(c, LBM_ERR_STATE, "lbm_set_solid: this context has no solid mask (create it with semantics = LBM_SEM_BOUNCE_BACK_SOLID)");
+    int rc = need_solid(c, "lbm_set_solid");
+    if (rc) return rc;
     const size_t n = (size_t)c->plan.geo.nx * c->plan.geo.ny;
     for (int b = 0; b < c->plan.batch; ++b) {
         size_t solid = 0;
@@ -179,59 +183,50 @@ int lbm_set_solid(lbm_ctx* c, const uint8_t* mask) {
         if (solid == n) return fail(c, LBM_ERR_INVALID, "lbm_set_solid: lattice " + std::to_string(b) + " of the mask has no fluid cell");
     }
     HIP_TRY(c, hipSetDevice(c->p.device));
-    int rc = sync_all(c);
+    rc = sync_all(c);
     if (rc) return rc;
-    // The host copy changes only once both lattices hold the new link planes.  A copy that fails part-way leaves the planes of the two
-    // lattices in an undefined mix of the old and the new mask: the call returns LBM_ERR_HIP, lbm_get_solid still reports the old mask,
-    // and the context must be given a mask again (or destroyed) before it steps.
-    std::vector<uint8_t> next(n * c->plan.batch);
-    for (size_t i = 0; i < next.size(); ++i) next[i] = mask[i] ? 1 : 0;
-    rc = c->plan.es == 4 ? upload_links<float>(c, next.data()) : upload_links<double>(c, next.data());
-    for (int i = 2; i < NLAT && rc == LBM_OK; ++i) rc = solid_copy_links(c, i);   // (the lattices allocated since: scratch, the lagged one)
-    if (rc == LBM_OK) rc = sync_all(c);
-    if (rc) return rc;
-    c->solid_mask.swap(next);
-    rc = bodies_default(c);   // (one body again, whatever lbm_set_solid_bodies had set)
+    // The host copy changes only once both lattices hold the new link planes (upload_links), and one body again, at rest, whatever
+    // lbm_set_solid_bodies and lbm_set_body_motion had set.
+    Obstacles next;
+    next.mask.resize(n * c->plan.batch);
+    for (size_t i = 0; i < next.mask.size(); ++i) next.mask[i] = mask[i] ? 1 : 0;
+    rc = obstacles_change(c, ObsLevel::mask, next, upload_links);
     if (rc) return rc;
     return lbm_init_equilibrium(c);   // (ends every sampler; solid cells get w_k: solid_fix)
 }
 
 int lbm_get_solid(lbm_ctx* c, uint8_t* mask_out) {
     if (!c || !mask_out) return fail(c, LBM_ERR_INVALID, "lbm_get_solid: bad argument");
-    if (c->p.semantics != LBM_SEM_BOUNCE_BACK_SOLID)
-        return fail(c, LBM_ERR_STATE, "lbm_get_solid: this context has no solid mask (create it with semantics = LBM_SEM_BOUNCE_BACK_SOLID)");
-    std::memcpy(mask_out, c->solid_mask.data(), c->solid_mask.size());
+    const int rc = need_solid(c, "lbm_get_solid");
+    if (rc) return rc;
+    std::memcpy(mask_out, c->obs.mask.data(), c->obs.mask.size());
     return LBM_OK;
 }
 
 int lbm_solid_force(lbm_ctx* c, lbm_solid_force_record* out) {
     if (!c || !out) return fail(c, LBM_ERR_INVALID, "lbm_solid_force: bad argument");
-    if (c->p.semantics != LBM_SEM_BOUNCE_BACK_SOLID)
-        return fail(c, LBM_ERR_STATE, "lbm_solid_force: this context has no solid mask (create it with semantics = LBM_SEM_BOUNCE_BACK_SOLID)");
+    int rc = need_solid(c, "lbm_solid_force");
+    if (rc) return rc;
     if (c->nsteps == 0 || c->raw[c->cur])
         return fail(c, LBM_ERR_STATE, "lbm_solid_force: no step yet (the lattice holds post-collision populations after one)");
     HIP_TRY(c, hipSetDevice(c->p.device));
-    int rc = sync_all(c);
+    rc = sync_all(c);
     if (rc) return rc;
     const int B = c->plan.batch;
-    if (!c->force_dev) {
-        hipError_t e = hipMalloc((void**)&c->force_dev, (size_t)B * (FORCE_BLOCKS * ForceAcc::VALS + 4) * sizeof(double));
-        if (e != hipSuccess) {
-            c->force_dev = nullptr;
-            return fail(c, LBM_ERR_NOMEM, std::string("hipMalloc(solid force): ") + hipGetErrorString(e));
-        }
-    }
-    double* rec = c->force_dev + (size_t)B * FORCE_BLOCKS * ForceAcc::VALS;
+    rc = alloc_ok(c, c->obs.force_part.ensure((size_t)B * (FORCE_BLOCKS * ForceAcc::VALS + 4) * sizeof(double), "solid force"));
+    if (rc) return rc;
+    double* part = c->obs.force_part.as<double>();
+    double* rec = part + (size_t)B * FORCE_BLOCKS * ForceAcc::VALS;
+    const MotionTables& m = c->obs.moving;
     rc = launch_variant(c, [&](auto v) {
         using R = typename decltype(v)::R;
-        if (c->motion.base)
-            hipLaunchKernelGGL((k_solid_force_move<R>), dim3(FORCE_BLOCKS, 1, B), dim3(BLK), 0, c->s_compute, (const R*)c->lat[c->cur], c->plan.geo,
-                               c->plan.bstride, c->force_dev, c->motion.cell_row, (const R*)c->motion.delta);
+        if (m.base)
+            hipLaunchKernelGGL((k_solid_force_move<R>), dim3(FORCE_BLOCKS, 1, B), dim3(BLK), 0, c->s_compute, c->lat[c->cur].as<const R>(), c->plan.geo,
+                               c->plan.bstride, part, m.cell_row, (const R*)m.delta);
         else
-            hipLaunchKernelGGL((k_solid_force<R>), dim3(FORCE_BLOCKS, 1, B), dim3(BLK), 0, c->s_compute, (const R*)c->lat[c->cur], c->plan.geo,
-                               c->plan.bstride, c->force_dev);
-        hipLaunchKernelGGL(k_solid_force_final, dim3(B), dim3(RED_WAVE), 0, c->s_compute, (const double*)c->force_dev, FORCE_BLOCKS,
-                           (double)c->nsteps, rec);
+            hipLaunchKernelGGL((k_solid_force<R>), dim3(FORCE_BLOCKS, 1, B), dim3(BLK), 0, c->s_compute, c->lat[c->cur].as<const R>(), c->plan.geo,
+                               c->plan.bstride, part);
+        hipLaunchKernelGGL(k_solid_force_final, dim3(B), dim3(RED_WAVE), 0, c->s_compute, (const double*)part, FORCE_BLOCKS, (double)c->nsteps, rec);
     });
     if (rc) return rc;
     HIP_TRY(c, hipMemcpyAsync(out, rec, (size_t)B * sizeof(lbm_solid_force_record), hipMemcpyDeviceToHost, c->s_compute));

@@ -41,31 +41,20 @@ static TopoBuf topo_buf(const lbm_ctx* c) {
     const TopoGrid g = topo_grid(c);
     const size_t B = c->plan.batch, ny = c->plan.geo.ny;
     TopoBuf b;
-    b.total = c->topo_part;
+    b.total = c->topo_part.as<double>();
     b.close = b.total + B * g.nb * ny;
     b.partial = b.close + B * ny;
     b.rec = (lbm_topology_record*)(b.partial + B * LBM_TOPOLOGY_MAX_WINDOWS * g.nwg() * TOPO_PART);
     return b;
 }
 static int ensure_topo(lbm_ctx* c, bool fields) {
-    if (!c->topo_part) {
-        const TopoGrid g = topo_grid(c);
-        const size_t B = c->plan.batch, ny = c->plan.geo.ny;
-        const size_t bytes = B * (((size_t)g.nb * ny + ny + LBM_TOPOLOGY_MAX_WINDOWS * g.nwg() * TOPO_PART) * sizeof(double) + sizeof(lbm_topology_record));
-        hipError_t e = hipMalloc((void**)&c->topo_part, bytes);
-        if (e != hipSuccess) {
-            c->topo_part = nullptr;
-            return fail(c, LBM_ERR_NOMEM, std::string("hipMalloc(topology): ") + hipGetErrorString(e));
-        }
-    }
-    if (fields && !c->topo_fields) {   // psi, then omega: [batch][nx][ny] each
-        hipError_t e = hipMalloc((void**)&c->topo_fields, (size_t)2 * c->plan.batch * c->plan.geo.nx * c->plan.geo.ny * sizeof(double));
-        if (e != hipSuccess) {
-            c->topo_fields = nullptr;
-            return fail(c, LBM_ERR_NOMEM, std::string("hipMalloc(stream function): ") + hipGetErrorString(e));
-        }
-    }
-    return LBM_OK;
+    const TopoGrid g = topo_grid(c);
+    const size_t B = c->plan.batch, ny = c->plan.geo.ny;
+    const size_t bytes = B * (((size_t)g.nb * ny + ny + LBM_TOPOLOGY_MAX_WINDOWS * g.nwg() * TOPO_PART) * sizeof(double) + sizeof(lbm_topology_record));
+    const int rc = alloc_ok(c, c->topo_part.ensure(bytes, "topology"));
+    if (rc || !fields) return rc;
+    // psi, then omega: [batch][nx][ny] each
+    return alloc_ok(c, c->topo_fields.ensure((size_t)2 * B * c->plan.geo.nx * ny * sizeof(double), "stream function"));
 }
 
 // psi of lat[which] on the compute stream: block sums, offsets, then the extrema of the spec's windows (and psi itself into psi_out when
@@ -78,7 +67,7 @@ static int topology_enqueue(lbm_ctx* c, int which, const TopoSpec& sp, long long
         using VT = decltype(v);
         using R = typename VT::R;
         constexpr bool PROM = coll_is_prom(VT::COLL);
-        const R* src = (const R*)c->lat[which];
+        const R* src = c->lat[which].as<const R>();
         hipLaunchKernelGGL((k_topo_totals<R, VT::SEM, PROM>), tiles, dim3(BLK), 0, c->s_compute, src, c->plan.geo, c->raw[which], (R)c->p.uLB,
                            c->plan.bstride, sp.host_f32, b.total);
         hipLaunchKernelGGL(k_topo_offsets, dim3((c->plan.geo.ny + BLK - 1) / BLK, 1, c->plan.batch), dim3(BLK), 0, c->s_compute, b.total, g.nb,
@@ -96,11 +85,6 @@ static int topology_enqueue(lbm_ctx* c, int which, const TopoSpec& sp, long long
     });
 }
 
-void topology_free(lbm_ctx* c) {
-    if (c->topo_part) (void)hipFree(c->topo_part);
-    if (c->topo_fields) (void)hipFree(c->topo_fields);
-    c->topo_part = c->topo_fields = nullptr;
-}
 }  // namespace lbmhost
 
 using namespace lbmhost;
@@ -148,8 +132,8 @@ int lbm_get_stream_function(lbm_ctx* c, double* psi_out, double* omega_out, int 
     int which = 0;
     rc = prev_lattice(c, &which);
     if (rc) return rc;
-    double* psi_dev = c->topo_fields;
-    double* omega_dev = c->topo_fields + (size_t)B * n;
+    double* psi_dev = c->topo_fields.as<double>();
+    double* omega_dev = psi_dev + (size_t)B * n;
     if (psi_out) {
         TopoSpec sp{};
         sp.host_f32 = host_dtype == LBM_F32;
@@ -165,8 +149,8 @@ int lbm_get_stream_function(lbm_ctx* c, double* psi_out, double* omega_out, int 
             using VT = decltype(v);
             using R = typename VT::R;
             hipLaunchKernelGGL((k_export_macro<R, VT::SEM, coll_is_prom(VT::COLL)>), dim3((nx + trx<R>() - 1) / trx<R>(), (ny + 31) / 32, B), dim3(BLK), 0,
-                               c->s_compute, (const R*)c->lat[which], c->plan.geo, c->raw[which], (R)c->p.uLB, (R*)c->stage, c->plan.bstride);
-            hipLaunchKernelGGL((k_topo_omega<R>), dim3((unsigned)((n + BLK - 1) / BLK), 1, B), dim3(BLK), 0, c->s_compute, (const R*)c->stage, nx, ny,
+                               c->s_compute, c->lat[which].as<const R>(), c->plan.geo, c->raw[which], (R)c->p.uLB, c->stage.as<R>(), c->plan.bstride);
+            hipLaunchKernelGGL((k_topo_omega<R>), dim3((unsigned)((n + BLK - 1) / BLK), 1, B), dim3(BLK), 0, c->s_compute, c->stage.as<const R>(), nx, ny,
                                (int)(host_dtype == LBM_F32), omega_dev);
         });
         if (rc) return rc;

@@ -1,7 +1,8 @@
 // lbm_wall_motion.hpp -- the wall velocity of moving bodies (lbm_set_body_motion; contract in include/lbm.h): Ladd's term
-// of every link of the list of lbm_bodies.hpp, its sums for the flux check, and the per-cell table the step kernels read.  Arrays are in
-// the host layout of the mask, [nx][ny] with y fastest, one lattice at a time.  Plain C++, nothing from HIP: tests/test_body_motion_cpu.py
-// drives it from a program of its own.
+// of every link of the list of lbm_bodies.hpp, its sums for the flux check, and the per-cell table the step kernels read; then the tables
+// of a whole batch as the device holds them, or the refusal of the flux check (motion_parts).  Arrays are in the host layout of the mask,
+// [nx][ny] with y fastest, one lattice at a time.  Plain C++, nothing from HIP: tests/test_body_motion_cpu.py and tests/test_devmem_cpu.py
+// drive it from programs of their own.
 #pragma once
 #include <cmath>
 #include <cstddef>
@@ -77,4 +78,54 @@ LBM_WM_ATTR inline WallMotion wall_motion(const std::vector<BodyLink>& links, co
 // lattice's edge (the discrete divergence theorem); the rounding of the sum stays below links * 2^-52 * A, and one leaking link is a
 // whole delta.  True: the motion conserves the lattice's mass.
 inline bool wall_motion_closed(const WallMotion& m) { return !(std::fabs(m.S) > (double)m.delta.size() * 0x1p-52 * m.A); }
+
+// The tables of a nonzero motion of a whole batch (mask and label [batch][nx][ny], centre[batch][nbodies][2], motion[batch][nbodies][3])
+// as the device holds them in one allocation: cell_row[batch][ny][nx]; delta[rows][8], already rounded to the lattice type (f32: float);
+// link_delta, one double per entry of the batch's link list (body_parts), the same terms as the lattice adds them.  Or why there are
+// none: the first lattice whose motion fails the flux check, with its sums and its count of links, or too many rows for cell_row.
+struct MotionParts {
+    enum { CELL_ROW, DELTA, LINK_DELTA };
+    enum Refusal { NONE, OPEN_FLUX, TOO_MANY_ROWS };
+    std::vector<int32_t> cell_row;
+    std::vector<char> delta;
+    std::vector<double> link_delta;
+    Refusal refusal = NONE;
+    int lattice = 0;                // OPEN_FLUX: which lattice, and its S, A and links
+    double S = 0.0, A = 0.0;
+    size_t links = 0;
+    std::vector<Part> parts() const {
+        return {{cell_row.data(), cell_row.size() * sizeof(int32_t)}, {delta.data(), delta.size()}, {link_delta.data(), link_delta.size() * sizeof(double)}};
+    }
+};
+inline MotionParts motion_parts(const uint8_t* mask, const int32_t* label, const double* centre, const double* motion, int batch, int nx, int ny,
+                                int nbodies, bool f32) {
+    const size_t n = (size_t)nx * ny;
+    MotionParts t;
+    t.cell_row.resize(batch * n);
+    std::vector<double> rows;
+    for (int b = 0; b < batch; ++b) {
+        std::vector<BodyLink> links;
+        std::vector<long long> start((size_t)nbodies + 1);
+        body_links(mask + b * n, label + b * n, nx, ny, nbodies, links, start.data());
+        const WallMotion m = wall_motion(links, start.data(), nx, ny, nbodies, centre + (size_t)b * nbodies * 2, motion + (size_t)b * nbodies * 3,
+                                         (long long)(rows.size() / 8));
+        if (!wall_motion_closed(m)) {
+            t.refusal = MotionParts::OPEN_FLUX; t.lattice = b; t.S = m.S; t.A = m.A; t.links = m.delta.size();
+            return t;
+        }
+        if (rows.size() / 8 + m.rows.size() / 8 > 0x7fffffffu) {
+            t.refusal = MotionParts::TOO_MANY_ROWS;
+            return t;
+        }
+        std::copy(m.cell_row.begin(), m.cell_row.end(), t.cell_row.begin() + b * n);
+        rows.insert(rows.end(), m.rows.begin(), m.rows.end());
+        for (double d : m.delta) t.link_delta.push_back(wall_delta_rounded(d, f32));
+    }
+    t.delta.resize(rows.size() * (f32 ? sizeof(float) : sizeof(double)));
+    for (size_t i = 0; i < rows.size(); ++i) {
+        if (f32) ((float*)t.delta.data())[i] = (float)rows[i];
+        else ((double*)t.delta.data())[i] = rows[i];
+    }
+    return t;
+}
 }  // namespace lbmhost

@@ -285,3 +285,52 @@ def test_taylor_couette_fast_fp32_meets_the_closed_form():
         print(f"Taylor-Couette fast fp32: torque errors {e_in:.6e} {e_out:.6e}, profile error {e_prof:.6e}, tz {F['tz'][0]!r} {F['tz'][1]!r}")
         assert max(e_in, e_out) <= TC_FACTOR * TC_TORQUE_ERR and e_prof <= TC_FACTOR * TC_PROFILE_ERR
         assert F["tz"][0] < 0.0 < F["tz"][1]
+
+
+def _reset_masks(nx, ny):
+    """(A: mask, labels, motion), B: two bodies that move, then another mask.  The wide lattice takes them from _cases; the 13 x 9 one has
+    room for two small blocks clear of the walls and of each other (every rigid motion of such a body passes the flux check)."""
+    if nx >= 72:
+        return _cases(nx, ny)["between"], _cases(nx, ny)["block"][0]
+    a = np.zeros((nx, ny), bool); lab = np.zeros((nx, ny), np.int32)
+    a[3:5, 3:5] = True
+    a[8:10, 4:6] = True; lab[8:10, 4:6] = 1
+    b = np.zeros((nx, ny), bool); b[5:8, 2:5] = True
+    return (a, lab, [[0.02, -0.01, 0.03], [0.0, 0.01, -0.02]]), b
+
+
+@pytest.mark.parametrize("shape", [(72, 40), (13, 9)], ids=lambda s: f"{s[0]}x{s[1]}")
+def test_new_mask_resets_everything_below_it(shape):
+    """The reset chain of the obstacle state, and the owners of its device memory: a context with bodies, a motion, a force series and
+    the other samplers running, the one-shot buffers of topology, monitor and solid force allocated, is given another mask.  It then
+    has one body at rest and no force series, and computes bit for bit what a context created with that mask computes -- nothing
+    stale, nothing freed twice.  Three contexts, one after the other, in one process.  fp32; 72 x 40 steps through the vector
+    kernels, 13 x 9 through the generic ones."""
+    nx, ny = shape
+    (A, lab, mot), B = _reset_masks(nx, ny)
+    with CavitySolver(nx, ny, 100.0, RT="MRT", dtype=np.float32, solid=B, **BB) as fresh:
+        assert fresh.describe()["kernel"] == ("k_step_solid" if nx % 4 == 0 else "k_step_generic")
+        fresh.step(9)
+        want = fresh.get_fields(want_fin=True), fresh.solid_force(), fresh.body_force()
+    for visit in range(3):
+        with CavitySolver(nx, ny, 100.0, RT="MRT", dtype=np.float32, solid=np.zeros(shape, bool), **BB) as s:
+            s.set_solid(A).set_bodies(lab).set_body_motion(mot).step(3)
+            assert s.nbodies == 2 and s.describe()["wall_motion"] == 1
+            s.begin_force(every=2, capacity=8)
+            s.begin_monitor(every=3, capacity=8)
+            s.begin_residual(every=2, capacity=8)
+            s.begin_statistics(every=1)
+            s.step(7)
+            s.topology(); s.monitor(); s.solid_force()
+            assert s.force_series()["count"] == 3 and s.monitor_series()["count"] >= 1      # (the samplers ran: at 5, 7, 9)
+            s.set_solid(B)
+            assert s.nbodies == 1 and s.body_motion.shape == (1, 3) and not s.body_motion.any(), visit
+            assert "wall_motion" not in s.describe() and s.steps_done == 0, visit
+            assert s.lib.lbm_force_read(s._h, None, 0, None, None) == -4, visit          # LBM_ERR_STATE: no series is on
+            assert np.array_equal(s.solid, B) and np.array_equal(s.bodies[0], np.where(B, 0, -1)), visit
+            s.step(9)
+            for got, ref, name in zip(s.get_fields(want_fin=True), want[0], ("u", "rho", "fin")):
+                assert np.array_equal(got, ref), f"visit {visit}: {name} differs from a fresh context's"
+            assert s.solid_force() == want[1], visit
+            F = s.body_force()
+            assert F.keys() == want[2].keys() and all(np.array_equal(F[k], want[2][k]) for k in F), visit
