@@ -8,7 +8,8 @@ Ladd's moving-wall term at rho_0 = 1 for the body's motion (Ux, Uy, Om) about it
     uwx = Ux + Om ry;          uwy = Uy + Om rx
     delta = (6 w_k) (cx_k uwx + cy_k uwy)                  6 w_k = 2/3 (k <= 4) or 1/6
 
-in double, every product and sum rounded in the order written, then rounded once to the lattice type.  One step: SolidOracle's, then
+in double, every product and sum rounded in the order written, then rounded once to the lattice type (a long-double oracle: to its
+parameter type, the type the device runs in, and widened exactly).  One step: SolidOracle's, then
 fin_k(x, y) += delta on every link (one add in the lattice type; the device adds it to the stored fpost_opp(k), the same sum).  The
 force on a link is c_opp(k) (2 f - delta), f = fin_k(x, y) converted to double.  S = sum delta, A = sum |delta| over the list sorted by
 body, then by cell in [y][x] order, then by k, summed in that order in double (delta before its rounding to the lattice type).
@@ -84,9 +85,11 @@ class MovingWallOracle(SolidOracle):
         for d in self.delta64:
             self.S = self.S + d
             self.A = self.A + abs(d)
-        self.delta = np.zeros((9, self.nx, self.ny), dtype=self.R)              # as the lattice adds it: rounded once to its type
+        # as the lattice adds it: rounded once to the type the device runs in (the oracle's parameter type: its own type, or, for a
+        # long-double oracle, param_dtype), then widened exactly
+        self.delta = np.zeros((9, self.nx, self.ny), dtype=self.R)
         for (x, y, k, _), d in zip(self.links, self.delta64):
-            self.delta[k, x, y] = self.R(d)
+            self.delta[k, x, y] = self.par(d)
         self.moving = bool(np.any(self.motion))
         return self
 

@@ -1,0 +1,391 @@
+"""CPU side of the arithmetic error budget with solid obstacles and moving bodies (the GPU side:
+tests/test_arith_error_budget_solid_gpu.py):
+
+* a link's delta in a long-double MovingWallOracle is the lattice type's value widened, LD(P(d)), as the device's table holds it;
+* the long-double forms of tests/solid_ref.SolidOracle and tests/moving_wall_ref.MovingWallOracle agree with their own fp64 forms to
+  fp64 rounding after 100 steps and are not the same bits; at rest the fluid mass changes by rounding only, and with a closed motion
+  by the flux residue sum delta (after its rounding to the lattice type) per step;
+* a whole step built on the arith="fast" operators (oracle/lbm_fast.py, fed the plain-sum macros) is the dense long-double step on every
+  fluid cell, with solid cells at w_k in both; a step that pulls from the solid cell instead of taking the cell's own opposite
+  population, and one that adds delta before its rounding to the lattice type, fail that check on link cells and only there;
+* the masks, bodies and routes of the GPU file: the masks leave fluid cells and hold what they claim, every motion passes the flux
+  check, the long-double reference stays finite with max|fin| <= 1 for every (shape, state) the GPU tests use, and the routes are what
+  lbm_plan accepts and names, by a dry run."""
+import itertools
+import os
+import sys
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+from bounce_back_ref import BounceBackOracle  # noqa: E402
+from moving_wall_ref import MovingWallOracle, delta_of  # noqa: E402
+from solid_ref import SolidOracle  # noqa: E402
+from oracle.states import state  # noqa: E402
+from test_arith_error_budget_walls_cpu import _FastStep  # noqa: E402
+from test_arith_error_budget_solid_gpu import (BATCH_RATES, BATCH_STEPS, CALLS, DISTINCT, FAM_CALLS, MOVE_STATES, REST_STATES,  # noqa: E402
+                                               SMALLEST, TILES, batch_cases, budget_mask, budget_tile_steps, motion_case, smallest_mask,
+                                               solid_routes)
+from test_solid_tiles_gpu import _tile  # noqa: E402
+from latticeboltzmannsimulations_amd import launch_plan  # noqa: E402
+
+LD = np.longdouble
+EPS_LD = float(np.finfo(LD).eps)
+NX, NY = 32, 24
+COLLS = ("SRT", "TRT", "MRT")
+
+
+def small_mask():
+    """32 x 24: a 4 x 4 block, two lid-row cells, one cell on each side wall and a corner-touching pair."""
+    m = np.zeros((NX, NY), dtype=bool)
+    m[11:15, 8:12] = True
+    m[20:22, 0] = True
+    m[0, 7] = m[NX - 1, 21] = True
+    m[22, 15] = m[23, 16] = True
+    return m
+
+
+def small_bodies():
+    """small_mask() as three bodies: the block (0) and the corner-touching pair (1) translate and rotate; the lid-row and wall cells (2)
+    stay at rest, as the flux check demands of cells on a wall."""
+    m, lab = small_mask(), np.zeros((NX, NY), dtype=np.int32)
+    lab[22, 15] = lab[23, 16] = 1
+    lab[20:22, 0] = lab[0, 7] = lab[NX - 1, 21] = 2
+    return m, lab, np.array([[0.01, 0.02, 0.004], [0.02, -0.01, 0.03], [0.0, 0.0, 0.0]])
+
+
+def _make(cls, coll, dtype, rates, moving, Re=1000.0, **kw):
+    if moving:
+        m, lab, mot = small_bodies()
+        return cls(NX, NY, Re, mask=m, labels=lab, motion=mot, collision=coll, dtype=dtype, **rates, **kw)
+    return cls(NX, NY, Re, mask=small_mask(), collision=coll, dtype=dtype, **rates, **kw)
+
+
+def _fluid_mass(o):
+    return np.sum(o.fin[:, ~o.mask], dtype=LD)
+
+
+# ---- item 1: delta as the device holds it ------------------------------------------------------------------------------------------
+def test_long_double_moving_wall_reference_takes_delta_as_the_device_holds_it():
+    m, lab, mot = small_bodies()
+    seen = {}
+    for P in (np.float32, np.float64):
+        o = MovingWallOracle(NX, NY, 1000.0, mask=m, labels=lab, motion=mot, collision="MRT", dtype=LD, param_dtype=P)
+        assert o.delta.dtype == LD and o.closed() and len(o.links) > 40
+        for (x, y, k, b), d in zip(o.links, o.delta64):
+            assert d == delta_of(x, y, k, o.centres[b], o.motion[b])
+            assert o.delta[k, x, y] == LD(P(d)), (P, x, y, k)
+        on_links = np.zeros(o.delta.shape, dtype=bool)
+        for x, y, k, _ in o.links:
+            on_links[k, x, y] = True
+        assert not o.delta[~on_links].any()
+        lattice = MovingWallOracle(NX, NY, 1000.0, mask=m, labels=lab, motion=mot, collision="MRT", dtype=P)
+        assert lattice.delta.dtype == P and np.array_equal(lattice.delta.astype(LD), o.delta)      # the lattice-type oracle is unchanged
+        seen[P] = o.delta
+    assert not np.array_equal(seen[np.float32], seen[np.float64])
+    default = MovingWallOracle(NX, NY, 1000.0, mask=m, labels=lab, motion=mot, dtype=LD)
+    assert np.array_equal(default.delta, seen[np.float64])
+
+
+# ---- the long-double references against their fp64 forms, and the fluid mass ------------------------------------------------------------
+RE_100_STEPS = 300.0           # on 24 rows the relaxation rates of the GPU budget's 96 x 80 lattice at Re 1000 (nu = uLB ny / Re: 80 / 1000 = 24 / 300)
+FLUID_MASS_MEASURED = 25.4           # eps of long double: the largest relative change of the fluid mass at rest over the 35 runs below
+FLUID_MASS_MOVING_MEASURED = 25.3    # the same with motion, after taking off steps x the flux residue
+
+
+@pytest.mark.parametrize("moving", [False, True], ids=["rest", "moving"])
+@pytest.mark.parametrize("coll", COLLS)
+def test_long_double_solid_references_agree_with_their_fp64_forms_and_keep_the_fluid_mass(coll, moving):
+    """32 x 24, small_mask() -- with motion small_bodies() --, from S0, S2 and S3 at the default and at the distinct rates, 1 + 99 steps, as
+    test_long_double_bounce_back_reference_agrees_with_its_fp64_form_and_keeps_the_mass.  Against the fp64 form of the same class on
+    the fluid cells: <= 1e-13 on fin (relative to max|fin|), u / uLB and rho, and not the same bits; max|fin| <= 1 at the read-outs;
+    solid cells at w_k.  The fluid mass (sum of fin over fluid cells, in long double): at rest it changes by rounding only, measured
+    <= 25.4 long-double eps relative (MRT 10.3 - 13.0, SRT and TRT 21.3 - 25.4); with the closed motion the change less steps x the
+    flux residue is <= 25.3 eps (MRT 10.8 - 13.6, SRT and TRT 21.7 - 25.3), and the change itself is inside steps x |residue| + the
+    rounding allowance; both allowances 4 x the measured value.
+
+    Two Reynolds numbers.  All 36 runs at RE_100_STEPS = 300: nu = uLB ny / Re, so 300 on 24 rows gives the rates of the 96 x 80
+    lattice at Re 1000 on which the GPU file uses these references (tau - 1/2 = 0.0192); measured fin <= 1.3e-14, u / uLB <= 2.1e-14,
+    rho <= 2.0e-14.  And, as the bounce-back test, Re 1000, all runs but TRT from S3 at the default rates (34 of 36; measured fin
+    <= 1.6e-14, u / uLB <= 2.8e-14, rho <= 2.3e-14).  Why that one is left out: at Re 1000 on 24 rows tau - 1/2 is 0.0058 and
+    TRT's default omegam (Lambda = 1 / 3.5) is 0.02: the odd modes are all but undamped, and the flow from S3 grows any perturbation,
+    fp64's rounding among them, with or without obstacles.  There the two precisions of the plain bounce-back cavity differ in u / uLB
+    by 1.3e-14, 1.5e-14, 2.1e-14, 2.8e-14, 3.7e-14 after 20, 40, .. 100 steps; with this mask by 1.1e-14, 1.5e-14, 2.3e-14, 4.3e-14,
+    9.6e-14 at rest and 1.3e-14, 2.1e-14, 2.0e-14, 3.4e-14, 2.0e-13 with motion; over 198 placements of the block and of the pair the
+    median is 1.3e-12, none is below 1e-13 both at rest and with motion, and some side-wall cells make the run diverge in both
+    precisions.  That figure is a property of that flow and not of the two forms, so a bound on it says nothing about the reference;
+    it is left out at rest too, where it happens to read inside the bound.  At Re 300 the same run reads 2.1e-14 and moving the
+    side-wall cells changes it by less than 2x."""
+    cls = MovingWallOracle if moving else SolidOracle
+    misses = []
+    for Re, st, rates in itertools.product((RE_100_STEPS, 1000.0), ("S0", "S2", "S3"), ({}, DISTINCT)):
+        if Re == 1000.0 and coll == "TRT" and st == "S3" and not rates:
+            continue        # omegam = 0.02: that flow grows fp64's rounding past the bound, at rest (9.6e-14) as with motion (see above)
+        f = state(st, NX, NY, np.float64)
+        L = _make(cls, coll, LD, rates, moving, Re=Re)
+        N = _make(cls, coll, np.float64, rates, moving, Re=Re)
+        N.set_state(f)
+        L.set_state(f.astype(LD))
+        fl = ~L.mask
+        assert L.fin.dtype == LD and L.t.dtype == LD and (not moving or (L.delta.dtype == LD and L.closed()))
+        m0 = _fluid_mass(L)
+        flux = np.sum(L.delta, dtype=LD) if moving else LD(0)        # the flux residue: sum of delta as rounded to the lattice type
+        drift = 0.0
+        for n in (1, 99):
+            L.step(n); N.step(n)
+            assert L.fin.dtype == LD and L.rho.dtype == LD and L.u.dtype == LD
+            assert np.isfinite(L.fin).all() and float(np.abs(L.fin).max()) <= 1.0, (Re, st, rates)
+            change = _fluid_mass(L) - m0
+            drift = max(drift, float(abs(change - L.nsteps * flux) / m0) / EPS_LD)
+            assert float(abs(change)) <= L.nsteps * float(abs(flux)) + 4 * (FLUID_MASS_MOVING_MEASURED if moving else FLUID_MASS_MEASURED) * EPS_LD * float(m0), \
+                (Re, st, rates, L.nsteps, float(change), float(flux))
+        assert np.array_equal(L.fin[:, L.mask], np.broadcast_to(L.t[:, None], (9, int(L.mask.sum()))))
+        ref = np.abs(L.fin[:, fl]).max()
+        e = (float(np.abs(N.fin - L.fin)[:, fl].max() / ref), float(np.abs(N.u - L.u)[:, fl].max()) / 0.08, float(np.abs(N.rho - L.rho)[fl].max()))
+        print(f"{cls.__name__} long double vs fp64 Re {Re:.0f} {coll} {st} {'distinct' if rates else 'default'}: fin {e[0]:.2e} u/uLB {e[1]:.2e} "
+              f"rho {e[2]:.2e}; fluid mass drift {drift:.1f} eps; flux residue per step {float(flux):.2e}")
+        if max(e) > 1e-13:
+            misses.append((Re, st, "distinct" if rates else "default", e))
+        assert not np.array_equal(N.fin, L.fin.astype(np.float64)), "the reference really is another precision"
+    assert not misses, ("long double and fp64 differ by more than 1e-13 (fin, u / uLB, rho)", misses)
+
+
+def test_the_flux_residue_of_a_closed_motion_is_what_the_fluid_mass_gains():
+    """The residue sum delta, taken over the oracle's own link list after delta's rounding to the lattice type, with the bodies turning
+    about points off their centroids.  Links pair up through a body along their direction c, where c . (Om x (r - r')) = 0: in fp64 the
+    pairs leave a few 1e-18 of the double arithmetic, and the rounding to fp32, being odd, removes even that (residue exactly 0).  After
+    n steps the fluid mass of the long-double reference has changed by n times the residue, to the rounding allowance of the test above:
+    the change per step is bounded by the residue."""
+    m, lab, mot = small_bodies()
+    for P, coll in ((np.float32, "SRT"), (np.float64, "TRT"), (np.float64, "MRT")):
+        L = MovingWallOracle(NX, NY, 1000.0, mask=m, labels=lab, centres=[[12.3, 9.7], [22.4, 15.1], [0.0, 0.0]], motion=mot, collision=coll,
+                             dtype=LD, param_dtype=P, **DISTINCT)
+        assert L.closed()
+        L.set_state(state("S2", NX, NY, P).astype(LD))
+        flux = LD(0)
+        for x, y, k, _ in L.links:
+            flux = flux + L.delta[k, x, y]
+        assert abs(float(flux)) <= len(L.links) * 2.0 ** -52 * L.A and (P == np.float64 or flux == 0)
+        m0 = _fluid_mass(L)
+        for n in (1, 25):
+            L.step(n)
+            change = _fluid_mass(L) - m0
+            assert float(abs(change - L.nsteps * flux)) <= 4 * FLUID_MASS_MOVING_MEASURED * EPS_LD * float(m0), (coll, L.nsteps, float(change), float(flux))
+            assert float(abs(change)) <= L.nsteps * float(abs(flux)) + 4 * FLUID_MASS_MOVING_MEASURED * EPS_LD * float(m0)
+
+
+# ---- a whole step on the fast operators ------------------------------------------------------------------------------------------------
+class FastSolid(_FastStep, SolidOracle):
+    pass
+
+
+class FastMoving(_FastStep, MovingWallOracle):
+    pass
+
+
+class PulledFromTheSolidCell(FastSolid):
+    """WRONG on purpose: a slot whose source is a solid cell pulls that cell's post-collision population instead of taking the cell's own
+    opposite one."""
+    def stream_bb(self, fpost, rho):
+        return self._pin(BounceBackOracle.stream_bb(self, fpost, rho))
+
+
+class DeltaBeforeItsRounding(FastMoving):
+    """WRONG on purpose: delta is added as computed in double, not as rounded to the lattice type."""
+    def set_motion(self, motion=None):
+        super().set_motion(motion)
+        for (x, y, k, _), d in zip(self.links, self.delta64):
+            self.delta[k, x, y] = self.R(d)
+        return self
+
+
+def _pair(dense, fast, coll, st, moving, **kw):
+    f = state(st, NX, NY, np.float64).astype(LD)
+    d, q = (_make(c, coll, LD, DISTINCT, moving, **kw) for c in (dense, fast))
+    d.set_state(f); q.set_state(f)
+    return d, q
+
+
+def _cell_errors(q, d):
+    fl = ~d.mask
+    return dict(fin=(np.abs(q.fin - d.fin) / np.abs(d.fin[:, fl]).max()).max(axis=0), u=np.abs(q.u - d.u).max(axis=0) / LD(0.08), rho=np.abs(q.rho - d.rho))
+
+
+STEP_MEASURED = 78.1     # eps of long double: the largest per-cell difference over the matrix below
+STEP_TOL = 4 * STEP_MEASURED * EPS_LD
+
+
+@pytest.mark.parametrize("moving", [False, True], ids=["rest", "moving"])
+@pytest.mark.parametrize("coll", COLLS)
+def test_a_step_on_the_fast_operators_is_the_dense_step_on_every_fluid_cell(coll, moving):
+    """FastSolid / FastMoving (_FastStep of tests/test_arith_error_budget_walls_cpu.py on SolidOracle / MovingWallOracle: collide() on
+    oracle/lbm_fast.py, fed the plain-sum macros) from S2 and S3 at the distinct rates, after 1, 2, 5, 13 and 26 steps: fin (relative to
+    max|fin| over the fluid cells), u / uLB and rho against the dense long-double oracle on every fluid cell; solid cells hold w_k in
+    both.  Measured (32 x 24, Re 1000): at most 78.1 long-double eps (SRT 76.6 - 78.1, TRT 53.1 - 64.1, MRT 27.3 - 29.7); the
+    tolerance is 4 x that, 3.4e-17 -- a seventh of an fp64 eps."""
+    worst = 0.0
+    for st in ("S2", "S3"):
+        d, q = _pair(MovingWallOracle if moving else SolidOracle, FastMoving if moving else FastSolid, coll, st, moving)
+        fl = ~d.mask
+        wk = np.broadcast_to(d.t[:, None], (9, int(d.mask.sum())))
+        for n in CALLS:
+            d.step(n); q.step(n)
+            assert q.fin.dtype == LD
+            assert np.array_equal(q.fin[:, d.mask], wk) and np.array_equal(d.fin[:, d.mask], wk), "solid cells hold w_k in both"
+            for k, v in _cell_errors(q, d).items():
+                v = np.where(fl, v, 0)
+                worst = max(worst, float(v.max()))
+                assert float(v.max()) <= STEP_TOL, (st, d.nsteps, k, float(v.max()) / EPS_LD, "eps at", np.unravel_index(int(np.argmax(v)), v.shape))
+    print(f"fast step vs dense {'moving' if moving else 'rest'} {coll}: largest {worst / EPS_LD:.1f} eps")
+
+
+@pytest.mark.parametrize("coll", COLLS)
+def test_the_step_check_sees_a_wrong_link_rule_on_link_cells_only(coll):
+    """The two deliberately wrong restatements, one step from S2 and S3 at the distinct rates: the step check above fails (fin is more
+    than 1e3 tolerances off), on link cells -- fluid cells with a slot whose source is solid -- and on no other cell.  Pulling from the
+    solid cell is wrong on every link (the solid cell's post-collision w_k instead of the cell's own population: >= 1e-5); delta before
+    its rounding differs by the rounding of delta to fp32 (param_dtype=np.float32), where that is not zero."""
+    for st in ("S2", "S3"):
+        for dense, wrong, moving, kw, floor in ((SolidOracle, PulledFromTheSolidCell, False, {}, 1e-5),
+                                                (MovingWallOracle, DeltaBeforeItsRounding, True, dict(param_dtype=np.float32), 0.0)):
+            d, q = _pair(dense, wrong, coll, st, moving, **kw)
+            d.step(1); q.step(1)
+            links = np.any(np.array(d.link_sets()), axis=0)
+            err = _cell_errors(q, d)["fin"]
+            assert float(err[~links & ~d.mask].max(initial=0)) <= STEP_TOL, (wrong.__name__, st)
+            assert float(err[links].max()) > 1e3 * STEP_TOL, (wrong.__name__, st, float(err[links].max()))
+            bad = err > STEP_TOL
+            assert bad.any() and not (bad & ~links).any()
+            if floor:
+                assert bad[links].all() and float(np.abs(q.fin - d.fin).max(axis=0)[links].min()) >= floor
+            else:
+                changed = np.zeros(d.mask.shape, dtype=bool)
+                for (x, y, k, _), d64 in zip(d.links, d.delta64):
+                    changed[x, y] |= LD(d64) != d.delta[k, x, y]
+                assert changed.any() and not (bad & ~changed).any() and bad.sum() >= changed.sum() // 2
+
+
+# ---- the GPU file's masks, bodies and routes ---------------------------------------------------------------------------------------------
+def _budget_shapes():
+    """(nx, ny, dtype, S) of every budget_mask the GPU tests build."""
+    out = set()
+    for dtype in (np.float32, np.float64):
+        out.add((96, 80, dtype, budget_tile_steps(dtype)))
+        for (nx, ny), _, _, S, _, _ in solid_routes(dtype):
+            out.add((nx, ny, dtype, S))
+    return sorted(out, key=lambda t: (t[0], t[1], np.dtype(t[2]).name, t[3]))
+
+
+def test_budget_mask_holds_what_it_claims():
+    assert all(budget_tile_steps(dt) == 5 for dt in (np.float32, np.float64))
+    for nx, ny, dtype, S in _budget_shapes():
+        F, TX, TY = _tile(dtype, S)
+        for seed in (2026, 2027, 2028):
+            m = budget_mask(nx, ny, dtype, S, seed=seed)
+            assert m.shape == (nx, ny) and m.dtype == bool and (~m).sum() > 0.9 * nx * ny, (nx, ny, S)
+            by = ny // 4 + 2
+            assert m[19:25, by:by + 6].all() and 19 % 4 == 3 and 24 % 4 == 0
+            sx, sy = nx // 2 - 6, ny // 2 + 6
+            box = m[sx - 1:sx + 4, sy - 1:sy + 4]
+            assert box.sum() == 3 and all(box[1 + i, 1 + i] for i in range(3)), "three cells that touch at corners only"
+            assert m[nx // 2:nx // 2 + 5, 0].all() and m[nx // 3, 0:3].all()
+            assert m[0, ny // 2] and m[nx - 1, ny // 3] and m[:, ny - 1].any() and m[0, 0]
+            if (nx, ny) != (70, 66):        # (the tile routes and the budget's lattice; 70 x 66 runs one step per launch only)
+                xs, ys = F + TX, F + TY
+                assert m[xs - 1:xs + 1, ys - 1:ys + 1].all(), "a block across the first tile seam in x and y"
+            assert m[F - 1, 12] and m[F, 15] and m[14, F - 1] and m[17, F]
+            inner = m[1:-1, 1:-1].mean()
+            assert 0.03 < inner < 0.09, inner
+        assert not np.array_equal(budget_mask(nx, ny, dtype, S, seed=2026), budget_mask(nx, ny, dtype, S, seed=2027))
+
+
+def test_motion_case_bodies_are_clear_of_the_walls_and_of_each_other():
+    for nx, ny, shifts in ((96, 80, (0, 5, 10)), (70, 66, (0,))):
+        for shift in shifts:
+            m, lab, mot = motion_case(nx, ny, shift)
+            assert mot.shape == (6, 3) and np.all(np.any(mot[:, :2] != 0, axis=1)) and np.all(mot[:, 2] != 0)
+            assert not (m[0].any() or m[-1].any() or m[:, 0].any() or m[:, -1].any())
+            assert sorted(set(lab[m].tolist())) == list(range(6)) and m[lab == 1].sum() == 1
+            o = MovingWallOracle(nx, ny, 1000.0, mask=m, labels=lab, motion=mot, dtype=np.float64)
+            assert o.closed()
+            owners = {}
+            for x, y, k, b in o.links:
+                owners.setdefault((x, y), set()).add(b)
+            both = [c for c, bs in owners.items() if len(bs) > 1]
+            assert both and all(owners[c] == {2, 3} for c in both), "only bodies 2 and 3 share fluid cells"
+            for b in range(6):        # every body's own links sum to zero flux up to rounding: clear of walls and of other bodies
+                d = [v for (x, y, k, bb), v in zip(o.links, o.delta64) if bb == b]
+                assert abs(sum(d)) <= len(d) * 2.0 ** -52 * sum(abs(v) for v in d), b
+            xs4, xs5 = np.nonzero(m & (lab == 4))[0], np.nonzero(m & (lab == 5))[0]
+            assert xs5.min() - xs4.max() - 1 == 3, "three fluid cells between bodies 4 and 5"
+
+
+def _finite_run(o, f, steps, what):
+    o.set_state(f.astype(LD))
+    for _ in range(steps):
+        o.step(1)
+        assert np.isfinite(o.fin).all() and float(np.abs(o.fin).max()) <= 1.0, (what, o.nsteps, float(np.abs(o.fin).max()))
+
+
+@pytest.mark.parametrize("coll", COLLS)
+def test_the_long_double_reference_stays_finite_on_every_shape_and_state_of_the_gpu_tests(coll):
+    """What the GPU file runs, in long double with the parameters of each lattice type: 26 steps on the budget's lattice (every state,
+    both rate sets, at rest and with motion); 30 steps from S2 at the distinct rates on every route's shape, on 70 x 66 with motion and
+    on the smallest lattices; BATCH_STEPS steps of each lattice of the two batches with its own mask, rates and motion.  Finite,
+    max|fin| <= 1 -- a bad mask, speed or rate fails here and not on the device."""
+    steps_c = sum(FAM_CALLS)
+    for dtype in (np.float32, np.float64):
+        mask = budget_mask(96, 80, dtype, budget_tile_steps(dtype))
+        mm, lab, mot = motion_case(96, 80)
+        for rates in ({}, DISTINCT):
+            for st in REST_STATES:
+                o = SolidOracle(96, 80, 1000.0, mask=mask, collision=coll, dtype=LD, param_dtype=dtype, **rates)
+                _finite_run(o, o.fin.copy() if st == "S0" else state(st, 96, 80, dtype), sum(CALLS), ("rest", st, rates))
+            for st in MOVE_STATES:
+                o = MovingWallOracle(96, 80, 1000.0, mask=mm, labels=lab, motion=mot, collision=coll, dtype=LD, param_dtype=dtype, **rates)
+                _finite_run(o, o.fin.copy() if st == "S0" else state(st, 96, 80, dtype), sum(CALLS), ("moving", st, rates))
+        mm, lab, mot = motion_case(70, 66)
+        o = MovingWallOracle(70, 66, 1000.0, mask=mm, labels=lab, motion=mot, collision=coll, dtype=LD, param_dtype=dtype, **DISTINCT)
+        _finite_run(o, state("S2", 70, 66, dtype), steps_c, ("moving 70 x 66", dtype))
+        for nx, ny in SMALLEST:
+            o = SolidOracle(nx, ny, 1000.0, mask=smallest_mask(nx, ny), collision=coll, dtype=LD, param_dtype=dtype, **DISTINCT)
+            _finite_run(o, state("S2", nx, ny, dtype), steps_c, ("smallest", nx, ny, dtype))
+        for moving in (False, True):
+            masks, labels, mots = batch_cases(dtype, moving)
+            for i, r in enumerate(BATCH_RATES):
+                kw = dict({k: v for k, v in r.items() if k != "Re"}, collision=coll, dtype=LD, param_dtype=dtype)
+                o = (MovingWallOracle(96, 80, r["Re"], mask=masks[i], labels=labels[i], motion=mots[i], **kw) if moving else
+                     SolidOracle(96, 80, r["Re"], mask=masks[i], **kw))
+                assert not moving or o.closed()
+                _finite_run(o, state("S2", 96, 80, dtype), BATCH_STEPS, ("batch", "moving" if moving else "rest", i, dtype))
+    for nx, ny, dtype, S in _budget_shapes():
+        o = SolidOracle(nx, ny, 1000.0, mask=budget_mask(nx, ny, dtype, S), collision=coll, dtype=LD, param_dtype=dtype, **DISTINCT)
+        _finite_run(o, state("S2", nx, ny, dtype), steps_c, (nx, ny, S))
+
+
+@pytest.mark.parametrize("arith", ["strict", "fast"])
+@pytest.mark.parametrize("coll", COLLS)
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+def test_the_gpu_tests_solid_routes_are_what_the_plan_accepts(dtype, coll, arith):
+    """Every entry of solid_routes() plans the kernel and the steps per launch it names, the tile entries with the frame of _tile(); the
+    budget's 96 x 80 lattice takes k_step_solid without the switch and the tile kernel with it, alone and as a batch of three; a
+    moving body has no plan of its own (the tile kernel refuses a motion at run time: tests/test_body_motion_gpu.py)."""
+    kw = dict(RT=coll, semantics="bounce_back", solid=True, dtype=dtype, arith=arith)
+    for (nx, ny), kernel, tune, S, name, steps in solid_routes(dtype):
+        p = launch_plan(nx, ny, 1000.0, steps=30, kernel=kernel, tuning=tune or None, **kw)
+        assert (p["kernel"], p["steps_per_launch"], p["semantics"]) == (name, steps, "bounce_back_solid"), (nx, ny, kernel, tune, p)
+        assert max(p["units"]) == steps and p["units"][0] == 1 and sum(p["units"]) == 30
+        if steps > 1:
+            assert p["frame"] == _tile(dtype, S)[0] and p["frame_fused"] == (0 if "frame_fused" in tune else 1), p
+        else:
+            assert p["frame"] == 0
+    for batch in (1, 3):
+        assert launch_plan(96, 80, 1000.0, steps=13, batch=batch, **kw)["kernel"] == "k_step_solid"
+        p = launch_plan(96, 80, 1000.0, steps=13, batch=batch, tuning=TILES, **kw)
+        assert p["kernel"] == "k_stepS_deep" and p["units"][0] == 1 and min(p["units"][1:]) >= 3 and sum(p["units"]) == 13, p
+    V = 4 if dtype == np.float32 else 2
+    for nx, ny in SMALLEST:
+        assert launch_plan(nx, ny, 1000.0, steps=3, **kw)["kernel"] == ("k_step_generic" if nx % V else "k_step_solid")
+        assert launch_plan(nx, ny, 1000.0, steps=3, kernel="generic", **kw)["kernel"] == "k_step_generic"
