@@ -250,9 +250,7 @@ int lbm_body_force(lbm_ctx* c, lbm_body_force_record* out) {
     rc = sync_all(c);
     if (rc == LBM_OK) rc = body_force_enqueue(c, c->obs.body.rec);
     if (rc) return rc;
-    HIP_TRY(c, hipMemcpyAsync(out, c->obs.body.rec, (size_t)c->plan.batch * c->obs.nbodies * sizeof(lbm_body_force_record), hipMemcpyDeviceToHost, c->s_compute));
-    HIP_TRY(c, hipStreamSynchronize(c->s_compute));
-    return LBM_OK;
+    return records_to_host(c, c->obs.body.rec, (size_t)c->plan.batch * c->obs.nbodies * sizeof(lbm_body_force_record), out);
 }
 
 int lbm_force_begin(lbm_ctx* c, int every, int capacity) {

@@ -1,5 +1,5 @@
-// lbm_hip.hip -- liblbm_hip.so: context life cycle, state upload, field export and the bandwidth / FMA probes of the C ABI declared
-// in include/lbm.h (the other host units are listed in lbm_host.hpp, which holds the shared declarations).
+// lbm_hip.hip -- liblbm_hip.so: context life cycle, state upload, field export (with the prologue and the epilogue that every reader of
+// the exported state shares) and the bandwidth / FMA probes of the C ABI declared in include/lbm.h (the other host units are listed in lbm_host.hpp, which holds the shared declarations).
 // gfx950 only.  See DESIGN.md for the data layout and the per-kernel roofline notes.
 #include "lbm_host.hpp"
 
@@ -41,9 +41,27 @@ __global__ __launch_bounds__(BLK) void k_reduce_final(const double* __restrict__
 }
 
 int ensure_stage(lbm_ctx* c, size_t bytes) { return alloc_ok(c, c->stage.ensure(bytes, "staging")); }
+// the staging buffer of the state upload and of every field export: twelve planes' worth per lattice (the populations take nine)
+int ensure_field_stage(lbm_ctx* c) { return ensure_stage(c, (size_t)12 * c->plan.geo.nx * c->plan.geo.ny * c->plan.es * c->plan.batch); }
 int sync_all(lbm_ctx* c) {
     if (!spin_until_ready([&] { return hipStreamQuery(c->s_compute); })) HIP_TRY(c, hipStreamSynchronize(c->s_compute));
     if (!spin_until_ready([&] { return hipStreamQuery(c->s_comm); })) HIP_TRY(c, hipStreamSynchronize(c->s_comm));
+    return LBM_OK;
+}
+
+// What every reader of the exported state starts with: the refusal before the first step (needs_step: the calls that have one), the
+// device, both streams idle, then the lattice the last iteration started from (prev_lattice: still intact after a single step,
+// recomputed after a multi-step unit) -- *which is what fields_of takes.
+int reader_source(lbm_ctx* c, const std::string& call, bool needs_step, int* which) {
+    if (needs_step && c->nsteps == 0) return fail(c, LBM_ERR_STATE, call + ": no step yet (the fields of an iteration exist after it)");
+    HIP_TRY(c, hipSetDevice(c->p.device));
+    const int rc = sync_all(c);
+    return rc ? rc : prev_lattice(c, which);
+}
+// ... and what the one-shot calls end with: the records enqueued on the compute stream, on the host.
+int records_to_host(lbm_ctx* c, const void* dev, size_t bytes, void* out) {
+    HIP_TRY(c, hipMemcpyAsync(out, dev, bytes, hipMemcpyDeviceToHost, c->s_compute));
+    HIP_TRY(c, hipStreamSynchronize(c->s_compute));
     return LBM_OK;
 }
 
@@ -88,58 +106,43 @@ int stage_to_host(lbm_ctx* c, const void* stage, void* host, int host_dtype, int
     return LBM_OK;
 }
 
-// grid of the host-layout <-> lattice kernels: tiles of trx<R>() columns x 32 rows
-template <typename R>
-dim3 grid_tiles(const lbm_ctx* c) { return dim3((c->plan.geo.nx + trx<R>() - 1) / trx<R>(), (c->plan.geo.ny + 31) / 32, c->plan.batch); }
-
+// the populations of lat[cur] as they are now
 int export_fin(lbm_ctx* c) {
     return launch_variant(c, [&](auto v) {
         using VT = decltype(v);
         using R = typename VT::R;
-        hipLaunchKernelGGL((k_export_fin<R, VT::SEM, coll_is_prom(VT::COLL)>), grid_tiles<R>(c), dim3(BLK), 0, c->s_compute, c->lat[c->cur].as<const R>(),
-                           c->plan.geo, c->raw[c->cur], (R)c->p.uLB, c->stage.as<R>(), c->plan.bstride);
+        hipLaunchKernelGGL((k_export_fin<R, VT::SEM, coll_is_prom(VT::COLL)>), grid_tiles<R>(c), dim3(BLK), 0, c->s_compute, fields_of<VT>(c, c->cur), c->stage.as<R>());
     });
 }
 
-int export_macro(lbm_ctx* c) {
-    // the fields of the LAST iteration are the moments of the state that iteration started
-    // from, i.e. of the previous lattice (prev_lattice: still intact after a single step, recomputed after a multi-step unit)
-    int which = 0;
-    int rc = prev_lattice(c, &which);
-    if (rc) return rc;
+// the fields of the LAST iteration: the moments of the state that iteration started from (which: reader_source's)
+int export_macro(lbm_ctx* c, int which) {
     return launch_variant(c, [&](auto v) {
         using VT = decltype(v);
         using R = typename VT::R;
-        hipLaunchKernelGGL((k_export_macro<R, VT::SEM, coll_is_prom(VT::COLL)>), grid_tiles<R>(c), dim3(BLK), 0, c->s_compute, c->lat[which].as<const R>(),
-                           c->plan.geo, c->raw[which], (R)c->p.uLB, c->stage.as<R>(), c->plan.bstride);
+        hipLaunchKernelGGL((k_export_macro<R, VT::SEM, coll_is_prom(VT::COLL)>), grid_tiles<R>(c), dim3(BLK), 0, c->s_compute, fields_of<VT>(c, which), c->stage.as<R>());
     });
 }
 
 // (MRT.py semantics with arith = fast runs the strict variant, so FAST is false there; that case has no closure (validate_params), and
-// either instantiation writes the same 1 / omega)
-int export_tau(lbm_ctx* c) {
-    int which = 0;
-    int rc = prev_lattice(c, &which);
-    if (rc) return rc;
+// either instantiation writes the same 1 / omega.  The closure gathers in MRT_GPU.py semantics, whatever the context's: turb = 0 elsewhere)
+int export_tau(lbm_ctx* c, int which) {
     return launch_variant(c, [&](auto v) {
         using VT = decltype(v);
         using R = typename VT::R;
         hipLaunchKernelGGL((k_export_tau<R, coll_is_fast(VT::COLL), coll_is_prom(VT::COLL)>), grid_tiles<R>(c), dim3(BLK), 0, c->s_compute,
-                           c->lat[which].as<const R>(), c->plan.geo, c->raw[which], relax_of<R>(c->p), batch_of<R>(c), c->p.turb, c->stage.as<R>());
+                           fields_of<Variant<R, VT::COLL, SEM_GPU, VT::TURB>>(c, which), relax_of<R>(c->p), batch_of<R>(c), c->p.turb, c->stage.as<R>());
     });
 }
 
 constexpr int RED_BLOCKS = 1024;   // partial sums per lattice of lbm_mean_u
 
-int reduce_u(lbm_ctx* c) {
-    int which = 0;
-    int rc = prev_lattice(c, &which);
-    if (rc) return rc;
+int reduce_u(lbm_ctx* c, int which) {
     return launch_variant(c, [&](auto v) {
         using VT = decltype(v);
         using R = typename VT::R;
         hipLaunchKernelGGL((k_reduce_u<R, VT::SEM, coll_is_prom(VT::COLL)>), dim3(RED_BLOCKS, 1, c->plan.batch), dim3(BLK), 0, c->s_compute,
-                           c->lat[which].as<const R>(), c->plan.geo, c->raw[which], (R)c->p.uLB, c->plan.bstride, c->red_dev.as<double>());
+                           fields_of<VT>(c, which), c->red_dev.as<double>());
     });
 }
 
@@ -272,7 +275,7 @@ int lbm_set_state(lbm_ctx* c, const void* fin_host, int host_dtype) {
     HIP_TRY(c, hipSetDevice(c->p.device));
     int rc = sync_all(c);
     if (rc) return rc;
-    rc = ensure_stage(c, (size_t)12 * c->plan.geo.nx * c->plan.geo.ny * c->plan.es * c->plan.batch);
+    rc = ensure_field_stage(c);
     if (rc) return rc;
     rc = host_to_stage(c, fin_host, host_dtype, Q * c->plan.batch);   // [B][9][nx][ny] is B * 9 planes
     if (rc) return rc;
@@ -324,15 +327,14 @@ long long lbm_steps_done(const lbm_ctx* c) { return c ? c->nsteps : -1; }
 
 int lbm_get_fields(lbm_ctx* c, void* u_host, void* rho_host, void* fin_host, int host_dtype) {
     if (!c || (host_dtype != LBM_F32 && host_dtype != LBM_F64)) return fail(c, LBM_ERR_INVALID, "lbm_get_fields: bad argument");
-    HIP_TRY(c, hipSetDevice(c->p.device));
-    int rc = sync_all(c);
+    int which = 0;   // (the populations alone: lat[cur] as it is, no replay of the lagged lattice)
+    int rc = u_host || rho_host ? reader_source(c, "lbm_get_fields", false, &which) : lbm_sync(c);
+    if (rc == LBM_OK) rc = ensure_field_stage(c);
     if (rc) return rc;
     const size_t n = (size_t)c->plan.geo.nx * c->plan.geo.ny;
-    rc = ensure_stage(c, (size_t)12 * n * c->plan.es * c->plan.batch);
-    if (rc) return rc;
     const size_t hes = host_dtype == LBM_F32 ? 4 : 8;
     if (u_host || rho_host) {
-        rc = export_macro(c);
+        rc = export_macro(c, which);
         if (rc) return rc;
         HIP_TRY(c, hipStreamSynchronize(c->s_compute));
         for (int b = 0; b < c->plan.batch; ++b) {   // staging of lattice b: [ux | uy | rho]; host: u[B][2][nx][NY], rho[B][nx][NY]
@@ -354,30 +356,24 @@ int lbm_get_fields(lbm_ctx* c, void* u_host, void* rho_host, void* fin_host, int
 
 int lbm_mean_u(lbm_ctx* c, double* mean_out) {
     if (!c || !mean_out) return fail(c, LBM_ERR_INVALID, "lbm_mean_u: bad argument");
-    HIP_TRY(c, hipSetDevice(c->p.device));
-    int rc = sync_all(c);
-    if (rc) return rc;
-    rc = alloc_ok(c, c->red_dev.ensure(((size_t)RED_BLOCKS + 1) * c->plan.batch * sizeof(double), "reduction"));
-    if (rc == LBM_OK) rc = reduce_u(c);
+    int which = 0;
+    int rc = reader_source(c, "lbm_mean_u", false, &which);
+    if (rc == LBM_OK) rc = alloc_ok(c, c->red_dev.ensure(((size_t)RED_BLOCKS + 1) * c->plan.batch * sizeof(double), "reduction"));
+    if (rc == LBM_OK) rc = reduce_u(c, which);
     if (rc) return rc;
     double* res = c->red_dev.as<double>() + (size_t)RED_BLOCKS * c->plan.batch;
     const double scale = 1.0 / (2.0 * (double)c->plan.geo.nx * (double)c->plan.geo.ny);
     hipLaunchKernelGGL(k_reduce_final, dim3((c->plan.batch + BLK - 1) / BLK), dim3(BLK), 0, c->s_compute, c->red_dev.as<double>(), RED_BLOCKS, c->plan.batch, scale, res);
     HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(mean_out, res, (size_t)c->plan.batch * sizeof(double), hipMemcpyDeviceToHost, c->s_compute));
-    HIP_TRY(c, hipStreamSynchronize(c->s_compute));
-    return LBM_OK;
+    return records_to_host(c, res, (size_t)c->plan.batch * sizeof(double), mean_out);
 }
 
 int lbm_get_tau(lbm_ctx* c, void* tau_host, int host_dtype) {
     if (!c || !tau_host || (host_dtype != LBM_F32 && host_dtype != LBM_F64)) return fail(c, LBM_ERR_INVALID, "lbm_get_tau: bad argument");
-    HIP_TRY(c, hipSetDevice(c->p.device));
-    int rc = sync_all(c);
-    if (rc) return rc;
-    const size_t n = (size_t)c->plan.geo.nx * c->plan.geo.ny;
-    rc = ensure_stage(c, (size_t)12 * n * c->plan.es * c->plan.batch);
-    if (rc) return rc;
-    rc = export_tau(c);
+    int which = 0;
+    int rc = reader_source(c, "lbm_get_tau", false, &which);
+    if (rc == LBM_OK) rc = ensure_field_stage(c);
+    if (rc == LBM_OK) rc = export_tau(c, which);
     if (rc) return rc;
     HIP_TRY(c, hipStreamSynchronize(c->s_compute));
     return stage_to_host(c, c->stage.get(), tau_host, host_dtype, c->plan.batch);

@@ -1,7 +1,8 @@
 // lbm_host.hpp -- what the host-side translation units of liblbm_hip.so share: the launch plan (struct Plan), the context (struct
 // lbm_ctx), the lazily bound RCCL table, the error macros, the variant dispatcher and the prototypes of every host function that
 // crosses a unit.
-//   lbm_hip.hip     context life cycle, state upload / field export, probes              (C ABI: create .. get_tau, probes)
+//   lbm_hip.hip     context life cycle, state upload / field export, probes; what every reader of the exported state starts and
+//                   ends with (reader_source, records_to_host)                            (C ABI: create .. get_tau, probes)
 //   lbm_plan.hip    parameter validation, launch planning, unit sequence, the dry run    (C ABI: next_unit, describe, plan)
 //   lbm_launch.hip  kernel launches and the step loop (run_unit, the lagged lattice)      (C ABI: step*, time_steps)
 //   lbm_sampling.hip what the samplers share (schedule: lbm_schedule.hpp; record series; the sampling prologue), the time statistics
@@ -14,6 +15,9 @@
 //   lbm_bodies.hip  the one writer of the obstacle state (struct Obstacles); the bodies of a mask: force and torque on each, one-shot
 //                   and as a series                                                          (C ABI: set_solid_bodies, get_solid_bodies, body_force, force_*)
 //   lbm_body_motion.hip the wall velocity of moving bodies: its tables                         (C ABI: set_body_motion, get_body_motion)
+// one header of device code that the step units never see:
+//   lbm_fields.hpp  the exported state ("what lbm_get_fields would return"): the view Fields that every reader kernel takes -- built
+//                   on the host by fields_of below alone -- and the kernels of the field export, lbm_mean_u and the statistics
 // and five headers free of HIP, each driven by a CPU test through a program of its own:
 //   lbm_schedule.hpp the schedule of automatic sampling
 //   lbm_devmem.hpp   the owner of a device allocation, and several tables uploaded into one (the device: HipMem below)
@@ -42,6 +46,7 @@
 #include "lbm_bodies.hpp"
 #include "lbm_solid.hpp"  // k_step_solid, extern (compiled in lbm_solid_f32/f64.hip)
 #include "lbm_solid_move.hpp"  // k_step_solid_move, k_step_generic_move, extern (compiled in lbm_solid_move_f32/f64.hip)
+#include "lbm_fields.hpp" // the view of the exported state and the kernels of the field export
 #include "lbm_inst.hpp"   // the kernels, and extern template declarations of the multi-step ones (compiled in lbm_{tiles,stream*}_f32/f64.hip)
 
 // ------------------------------------------------------------------------------------
@@ -296,6 +301,9 @@ FramePtrs<R> frame_ptrs(const lbm_ctx* c, int from, int to, int S) {
 }
 
 inline dim3 grid_rows(const lbm_ctx* c, int nrows) { return dim3((c->plan.geo.nx + BLK - 1) / BLK, nrows, c->plan.batch); }
+// grid of the host-layout <-> lattice kernels: tiles of trx<R>() columns x 32 rows
+template <typename R>
+dim3 grid_tiles(const lbm_ctx* c) { return dim3((c->plan.geo.nx + trx<R>() - 1) / trx<R>(), (c->plan.geo.ny + 31) / 32, c->plan.batch); }
 
 // Run-time parameters -> compile-time kernel variant (real type, collision operator, semantics, Smagorinsky).
 template <typename R_, int COLL_, int SEM_, bool TURB_>
@@ -347,6 +355,14 @@ void dispatch(const lbm_params& p, F&& f) {
     };
     if (p.dtype == LBM_F32) by_coll(float{});
     else by_coll(double{});
+}
+// The view of lat[which] for the kernels that read the exported state (VT: the context's Variant): the one place outside the step
+// launchers that pairs a lattice with its raw flag, the lid velocity and the batch stride.  which: reader_source's for what
+// lbm_get_fields exports now; c->cur for the sample of the iteration about to start (sample_if_due) and for the populations.
+template <typename VT>
+Fields<typename VT::R, VT::SEM, coll_is_prom(VT::COLL)> fields_of(const lbm_ctx* c, int which) {
+    using R = typename VT::R;
+    return {c->lat[which].as<const R>(), c->plan.geo, c->raw[which], (R)c->p.uLB, c->plan.bstride};
 }
 // A launcher's body: f(Variant) enqueues the kernels of the context's variant, then the launch error check
 template <typename F>
@@ -417,7 +433,10 @@ struct RowBlocks {
 // ---- host functions that cross a unit (defined in the unit the name of which is given) ----
 // lbm_hip.hip
 int ensure_stage(lbm_ctx* c, size_t bytes);
+int ensure_field_stage(lbm_ctx* c);
 int sync_all(lbm_ctx* c);
+int reader_source(lbm_ctx* c, const std::string& call, bool needs_step, int* which);
+int records_to_host(lbm_ctx* c, const void* dev, size_t bytes, void* out);
 int host_to_stage(lbm_ctx* c, const void* host, int host_dtype, int planes);
 int stage_to_host(lbm_ctx* c, const void* stage, void* host, int host_dtype, int planes);
 // lbm_plan.hip

@@ -63,10 +63,9 @@ static int monitor_enqueue(lbm_ctx* c, int which, const lbm_monitor_spec& spec, 
         using VT = decltype(v);
         using R = typename VT::R;
         hipLaunchKernelGGL((k_monitor<R, VT::SEM, coll_is_prom(VT::COLL)>), dim3(blocks, 1, c->plan.batch), dim3(BLK), 0, c->s_compute,
-                           c->lat[which].as<const R>(), c->plan.geo, c->raw[which], (R)c->p.uLB, den, c->plan.bstride, sp, c->mon_part.as<double>());
+                           fields_of<VT>(c, which), den, sp, c->mon_part.as<double>());
         hipLaunchKernelGGL((k_monitor_final<R, VT::SEM, coll_is_prom(VT::COLL)>), dim3(c->plan.batch), dim3(RED_WAVE), 0, c->s_compute,
-                           c->mon_part.as<const double>(), blocks, c->lat[which].as<const R>(), c->plan.geo, c->raw[which], (R)c->p.uLB, c->plan.bstride, sp,
-                           (double)step, (double*)rec);
+                           c->mon_part.as<const double>(), blocks, fields_of<VT>(c, which), sp, (double)step, (double*)rec);
     });
 }
 
@@ -90,20 +89,12 @@ int lbm_monitor(lbm_ctx* c, const lbm_monitor_spec* spec, lbm_monitor_record* re
     if (!c || !spec || !records_out) return fail(c, LBM_ERR_INVALID, "lbm_monitor: bad argument");
     const std::string bad = check_spec(c, spec);
     if (!bad.empty()) return fail(c, LBM_ERR_INVALID, "lbm_monitor: " + bad);
-    if (c->nsteps == 0) return fail(c, LBM_ERR_STATE, "lbm_monitor: no step yet (the fields of an iteration exist after it)");
-    HIP_TRY(c, hipSetDevice(c->p.device));
-    int rc = sync_all(c);
-    if (rc) return rc;
-    rc = ensure_partials(c);
-    if (rc) return rc;
     int which = 0;
-    rc = prev_lattice(c, &which);   // (what lbm_get_fields exports: the lattice the last iteration started from)
+    int rc = reader_source(c, "lbm_monitor", true, &which);
+    if (rc == LBM_OK) rc = ensure_partials(c);
+    if (rc == LBM_OK) rc = monitor_enqueue(c, which, *spec, c->nsteps, one_shot_records(c));
     if (rc) return rc;
-    rc = monitor_enqueue(c, which, *spec, c->nsteps, one_shot_records(c));
-    if (rc) return rc;
-    HIP_TRY(c, hipMemcpyAsync(records_out, one_shot_records(c), (size_t)c->plan.batch * sizeof(lbm_monitor_record), hipMemcpyDeviceToHost, c->s_compute));
-    HIP_TRY(c, hipStreamSynchronize(c->s_compute));
-    return LBM_OK;
+    return records_to_host(c, one_shot_records(c), (size_t)c->plan.batch * sizeof(lbm_monitor_record), records_out);
 }
 
 int lbm_monitor_begin(lbm_ctx* c, const lbm_monitor_spec* spec, int every, int capacity) {
@@ -134,24 +125,20 @@ int lbm_get_lines(lbm_ctx* c, int x, int gy, void* col_out, void* row_out, int h
     const int nx = c->plan.geo.nx, ny = c->plan.geo.ny, NY = c->plan.geo.NY, y0 = c->plan.geo.y0, B = c->plan.batch;
     if (col_out && (x < 0 || x >= nx)) return fail(c, LBM_ERR_INVALID, "lbm_get_lines: column outside the lattice");
     if (row_out && (gy < 0 || gy >= NY)) return fail(c, LBM_ERR_INVALID, "lbm_get_lines: row outside the lattice");
-    HIP_TRY(c, hipSetDevice(c->p.device));
-    int rc = sync_all(c);
+    int which = 0;
+    int rc = reader_source(c, "lbm_get_lines", false, &which);
     if (rc) return rc;
     const int cx = col_out ? x : -1;
     const int ly = row_out && gy >= y0 && gy < y0 + ny ? gy - y0 : -1;
     if (cx < 0 && ly < 0) return LBM_OK;
-    const size_t per = (size_t)3 * (ny + nx);
-    // (at least what lbm_get_fields asks for, so that the two calls do not reallocate the staging buffer in turn)
-    rc = ensure_stage(c, std::max((size_t)12 * nx * ny, per) * c->plan.es * B);
-    if (rc) return rc;
-    int which = 0;
-    rc = prev_lattice(c, &which);
+    const size_t per = (size_t)3 * (ny + nx);   // (no more than the fields: 3 (nx + ny) <= 12 nx ny)
+    rc = ensure_field_stage(c);
     if (rc) return rc;
     rc = launch_variant(c, [&](auto v) {
         using VT = decltype(v);
         using R = typename VT::R;
         hipLaunchKernelGGL((k_export_lines<R, VT::SEM, coll_is_prom(VT::COLL)>), dim3((ny + nx + BLK - 1) / BLK, 1, B), dim3(BLK), 0, c->s_compute,
-                           c->lat[which].as<const R>(), c->plan.geo, c->raw[which], (R)c->p.uLB, c->plan.bstride, cx, ly, c->stage.as<R>());
+                           fields_of<VT>(c, which), cx, ly, c->stage.as<R>());
     });
     if (rc) return rc;
     std::vector<char> tmp(per * B * c->plan.es);

@@ -1,9 +1,9 @@
 // lbm_monitor.hpp -- kernels of the run monitor (lbm_monitor*, lbm_get_lines; contract in include/lbm.h): one pass over the lattice
-// that reduces the macroscopic state k_export_macro would export to ten numbers per workgroup, a small kernel that folds the
+// that reduces the exported state (the view of lbm_fields.hpp) to ten numbers per workgroup, a small kernel that folds the
 // workgroups' results into the record and evaluates the probe cells, and the export of one column and one row.  Included by
 // lbm_monitor.hip alone.
 #pragma once
-#include "lbm_kernels.hpp"
+#include "lbm_fields.hpp"
 #include "lbm_reduce.hpp"
 
 // Window, boxes and probes of lbm_monitor_spec, by value in the kernel arguments.
@@ -57,27 +57,22 @@ __device__ __forceinline__ void mon_fold(MonAcc& a, const MonAcc& b) {
 
 __device__ __forceinline__ void MonAcc::fold(MonAcc& a, const MonAcc& b) { mon_fold(a, b); }
 
-// the value lbm_get_fields(host_dtype) would hand out, as a double
-template <typename R>
-__device__ __forceinline__ double mon_value(R v, int host_f32) { return host_f32 ? (double)(float)v : (double)v; }
-
-// The fused monitor pass: grid-stride over the cells of one lattice (blockIdx.z: lattice of the batch), x fastest; per cell the gather +
-// macros of k_export_macro.  The tree of lbm_reduce.hpp leaves one partial result per workgroup:
+// The fused monitor pass: grid-stride over the cells of one lattice (blockIdx.z: lattice of the batch), x fastest; per cell the
+// exported values of the view.  The tree of lbm_reduce.hpp leaves one partial result per workgroup:
 // partial[(blockIdx.z * gridDim.x + blockIdx.x) * MON_VALS ...].  Reads the nine planes once, like k_reduce_u.
 template <typename R, int SEM, bool PROM>
-__global__ __launch_bounds__(BLK) void k_monitor(const R* __restrict__ src, Geo geo, int raw, R uLB, double den, long long bstride, MonSpec sp,
-                                                 double* __restrict__ partial) {
+__global__ __launch_bounds__(BLK) void k_monitor(Fields<R, SEM, PROM> f, double den, MonSpec sp, double* __restrict__ partial) {
 #pragma clang fp contract(off)
     __shared__ double sh[BLK / RED_WAVE][MON_VALS];
-    src += blockIdx.z * bstride;
+    const Geo& geo = f.geo;
+    const auto lat = f.lattice(blockIdx.z);
     const long long n = (long long)geo.nx * geo.ny;
     MonAcc a = MonAcc::identity();
     for (long long i = (long long)blockIdx.x * BLK + threadIdx.x; i < n; i += (long long)gridDim.x * BLK) {
         const int y = (int)(i / geo.nx), x = (int)(i - (long long)y * geo.nx), gy = geo.y0 + y;
-        R g[Q], rho, ux, uy;
-        gather<R, SEM, PROM>(src, geo, raw, uLB, x, y, g);
-        macros<R, false, SEM>(g, x, gy, geo.nx, geo.NY, uLB, rho, ux, uy);
-        const double dx = mon_value(ux, sp.host_f32), dy = mon_value(uy, sp.host_f32), dr = mon_value(rho, sp.host_f32);
+        R rho, ux, uy;   // (Fields::exported spelled out: through it this loop came out 21 instructions longer)
+        lat.macro(x, y, ux, uy, rho);
+        const double dx = as_exported(ux, sp.host_f32), dy = as_exported(uy, sp.host_f32), dr = as_exported(rho, sp.host_f32);
         if (!(__builtin_isfinite(dx) && __builtin_isfinite(dy) && __builtin_isfinite(dr))) {
             a.nonfinite = a.nonfinite + 1.0;
             continue;
@@ -98,13 +93,12 @@ __global__ __launch_bounds__(BLK) void k_monitor(const R* __restrict__ src, Geo 
     if (red_workgroup<MonAcc, BLK / RED_WAVE>(a, sh)) red_store(partial + ((size_t)blockIdx.z * gridDim.x + blockIdx.x) * MON_VALS, a);
 }
 
-// The final pass, one wave per lattice (red_final): lane 0 writes the record; lanes 0 .. 7 evaluate the probe cells (gather + macros
-// of the one cell).  rec: the records of this sample, [batch].
+// The final pass, one wave per lattice (red_final): lane 0 writes the record; lanes 0 .. 7 evaluate the probe cells (the exported
+// values of the one cell).  rec: the records of this sample, [batch].
 template <typename R, int SEM, bool PROM>
-__global__ __launch_bounds__(RED_WAVE) void k_monitor_final(const double* __restrict__ partial, int nper, const R* __restrict__ src, Geo geo, int raw,
-                                                            R uLB, long long bstride, MonSpec sp, double step, double* __restrict__ rec) {
+__global__ __launch_bounds__(RED_WAVE) void k_monitor_final(const double* __restrict__ partial, int nper, Fields<R, SEM, PROM> f, MonSpec sp, double step,
+                                                            double* __restrict__ rec) {
     const int z = blockIdx.x, lane = threadIdx.x;
-    src += z * bstride;
     rec += (size_t)z * MON_REC;
     const MonAcc a = red_final<MonAcc>(partial + (size_t)z * nper * MON_VALS, nper);
     if (lane == 0) {
@@ -114,25 +108,19 @@ __global__ __launch_bounds__(RED_WAVE) void k_monitor_final(const double* __rest
     if (lane < LBM_MONITOR_MAX_PROBES) {
         double v[3] = {__builtin_nan(""), __builtin_nan(""), __builtin_nan("")};
         if (lane < sp.nprobes) {
-            const int x = sp.probe[lane][0], y = sp.probe[lane][1] - geo.y0;
-            if (y >= 0 && y < geo.ny) {
-                R g[Q], rho, ux, uy;
-                gather<R, SEM, PROM>(src, geo, raw, uLB, x, y, g);
-                macros<R, false, SEM>(g, x, geo.y0 + y, geo.nx, geo.NY, uLB, rho, ux, uy);
-                v[0] = mon_value(ux, sp.host_f32); v[1] = mon_value(uy, sp.host_f32); v[2] = mon_value(rho, sp.host_f32);
-            }
+            const int x = sp.probe[lane][0], y = sp.probe[lane][1] - f.geo.y0;
+            if (y >= 0 && y < f.geo.ny) f.lattice(z).exported(x, y, sp.host_f32, v[0], v[1], v[2]);
         }
         double* p = rec + 1 + MON_VALS + 3 * lane;
         p[0] = v[0]; p[1] = v[1]; p[2] = v[2];
     }
 }
 
-// Column x (all local rows) and local row ly (ly < 0: none) of the macroscopic state k_export_macro would export, in host layout:
+// Column x (all local rows) and local row ly (ly < 0: none) of the exported state, in host layout:
 // stage of lattice z = [ux | uy | rho][ny] of the column, then [ux | uy | rho][nx] of the row.  One thread per cell of either line.
 template <typename R, int SEM, bool PROM>
-__global__ __launch_bounds__(BLK) void k_export_lines(const R* __restrict__ src, Geo geo, int raw, R uLB, long long bstride, int cx, int ly,
-                                                      R* __restrict__ stage) {
-    src += blockIdx.z * bstride;
+__global__ __launch_bounds__(BLK) void k_export_lines(Fields<R, SEM, PROM> f, int cx, int ly, R* __restrict__ stage) {
+    const Geo& geo = f.geo;
     stage += (size_t)blockIdx.z * 3 * (geo.ny + geo.nx);
     const int t = blockIdx.x * BLK + threadIdx.x;
     int x, y;
@@ -147,8 +135,7 @@ __global__ __launch_bounds__(BLK) void k_export_lines(const R* __restrict__ src,
     } else {
         return;
     }
-    R g[Q], rho, ux, uy;
-    gather<R, SEM, PROM>(src, geo, raw, uLB, x, y, g);
-    macros<R, false, SEM>(g, x, geo.y0 + y, geo.nx, geo.NY, uLB, rho, ux, uy);
+    R rho, ux, uy;
+    f.lattice(blockIdx.z).macro(x, y, ux, uy, rho);
     out[0] = ux; out[n] = uy; out[2 * n] = rho;
 }

@@ -1,9 +1,9 @@
 // lbm_residual.hpp -- kernels of the field residual (lbm_residual_*; contract in include/lbm.h): one streaming pass over the lattice
-// that forms the macroscopic state k_export_macro would export, compares it with the snapshot of the previous sample, replaces the
+// that forms the exported state (the view of lbm_fields.hpp), compares it with the snapshot of the previous sample, replaces the
 // snapshot and reduces the differences to nine numbers per workgroup; a small kernel that folds the workgroups' results, in index
 // order, into the record.  The reduction is the tree of lbm_reduce.hpp.  Included by lbm_residual.hip alone.
 #pragma once
-#include "lbm_kernels.hpp"
+#include "lbm_fields.hpp"
 #include "lbm_reduce.hpp"
 
 // What a lane, a wave, a workgroup and the final pass carry (an accumulator of lbm_reduce.hpp): two counts, three sums, the
@@ -57,20 +57,20 @@ struct ResGroup {
     typedef S vec __attribute__((ext_vector_type(CPL)));
 };
 
-// The sample pass: grid-stride over the lane groups of one lattice (blockIdx.z: lattice of the batch); per cell the gather + macros of
-// k_export_macro.  Reads the snapshot, writes the current sample over it, reduces; one partial result per workgroup:
+// The sample pass: grid-stride over the lane groups of one lattice (blockIdx.z: lattice of the batch); per cell the macroscopic
+// state of the view.  Reads the snapshot, writes the current sample over it, reduces; one partial result per workgroup:
 // partial[(blockIdx.z * gridDim.x + blockIdx.x) * RES_VALS ...].  No atomics.  Pure streaming: 9 sizeof(R) + 3 sizeof(S) read and
 // 3 sizeof(S) written per cell.
 template <typename R, typename S, int SEM, bool PROM>
-__global__ __launch_bounds__(BLK) void k_residual(const R* __restrict__ src, Geo geo, int raw, R uLB, long long bstride, S* __restrict__ snap,
-                                                  double* __restrict__ partial) {
+__global__ __launch_bounds__(BLK) void k_residual(Fields<R, SEM, PROM> f, S* __restrict__ snap, double* __restrict__ partial) {
 #pragma clang fp contract(off)
     constexpr int CPL = ResGroup<S>::CPL;
     typedef typename ResGroup<S>::vec vec;
     __shared__ double sh[BLK / RED_WAVE][RES_VALS];
+    const Geo& geo = f.geo;
     const int nxg = (geo.nx + CPL - 1) / CPL;
     const long long ngroups = (long long)geo.ny * nxg;   // = the elements of one plane / CPL
-    src += blockIdx.z * bstride;
+    const auto lat = f.lattice(blockIdx.z);
     vec* sn = (vec*)snap + blockIdx.z * 3 * ngroups;
     ResAcc a = ResAcc::identity();
     for (long long i = (long long)blockIdx.x * BLK + threadIdx.x; i < ngroups; i += (long long)gridDim.x * BLK) {
@@ -80,10 +80,9 @@ __global__ __launch_bounds__(BLK) void k_residual(const R* __restrict__ src, Geo
 #pragma unroll
         for (int j = 0; j < CPL; ++j) {
             if (x + j >= geo.nx) break;   // (the padding cells of the row's last group)
-            R g[Q], rho, ux, uy;
-            gather<R, SEM, PROM>(src, geo, raw, uLB, x + j, y, g);
-            macros<R, false, SEM>(g, x + j, gy, geo.nx, geo.NY, uLB, rho, ux, uy);
-            cu[j] = (S)ux; cv[j] = (S)uy; cr[j] = (S)rho;
+            R rho, ux, uy;
+            lat.macro(x + j, y, ux, uy, rho);
+            cu[j] = (S)ux; cv[j] = (S)uy; cr[j] = (S)rho;   // (storing through S is the rounding of Fields::exported, see ResGroup)
             const double dux_now = (double)cu[j], duy_now = (double)cv[j], drho_now = (double)cr[j];
             const double pux = (double)pu[j], puy = (double)pv[j], prho = (double)pr[j];
             const bool fin = __builtin_isfinite(dux_now) && __builtin_isfinite(duy_now) && __builtin_isfinite(drho_now) &&

@@ -57,7 +57,7 @@ static int stats_accumulate(lbm_ctx* c, int which) {
         using VT = decltype(v);
         using R = typename VT::R;
         hipLaunchKernelGGL((k_stats_accumulate<R, VT::SEM, coll_is_prom(VT::COLL)>), dim3(blocks, 1, c->plan.batch), dim3(BLK), 0, c->s_compute,
-                           c->lat[which].as<const R>(), c->plan.geo, c->raw[which], (R)c->p.uLB, c->plan.bstride, c->stats_dev.as<double>());
+                           fields_of<VT>(c, which), c->stats_dev.as<double>());
     });
     if (rc) return rc;
     ++c->stats_count;
@@ -73,18 +73,14 @@ static int sample_from(lbm_ctx* c, int sampler, int which, long long step) {
     }
 }
 
-// lbm_stats_sample / lbm_monitor_sample / lbm_residual_sample: a sample of what lbm_get_fields exports now (prev_lattice: the lattice
-// the last iteration started from).  on: the sampler has been begun.
+// lbm_stats_sample / lbm_monitor_sample / lbm_residual_sample: a sample of what lbm_get_fields exports now (reader_source: the
+// lattice the last iteration started from).  on: the sampler has been begun.
 int sample_now(lbm_ctx* c, int sampler, bool on) {
     if (!c) return LBM_ERR_INVALID;
     const std::string stem = SAMPLER_CALLS[sampler];
     if (!on) return fail(c, LBM_ERR_STATE, stem + "_sample: nothing to sample into (" + stem + "_begin)");
-    if (c->nsteps == 0) return fail(c, LBM_ERR_STATE, stem + "_sample: no step yet (the fields of an iteration exist after it)");
-    HIP_TRY(c, hipSetDevice(c->p.device));
-    int rc = sync_all(c);
-    if (rc) return rc;
     int which = 0;
-    rc = prev_lattice(c, &which);
+    const int rc = reader_source(c, stem + "_sample", true, &which);
     if (rc) return rc;
     return sample_from(c, sampler, which, c->nsteps);
 }

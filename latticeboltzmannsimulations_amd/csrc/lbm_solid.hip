@@ -229,8 +229,6 @@ int lbm_solid_force(lbm_ctx* c, lbm_solid_force_record* out) {
         hipLaunchKernelGGL(k_solid_force_final, dim3(B), dim3(RED_WAVE), 0, c->s_compute, (const double*)part, FORCE_BLOCKS, (double)c->nsteps, rec);
     });
     if (rc) return rc;
-    HIP_TRY(c, hipMemcpyAsync(out, rec, (size_t)B * sizeof(lbm_solid_force_record), hipMemcpyDeviceToHost, c->s_compute));
-    HIP_TRY(c, hipStreamSynchronize(c->s_compute));
-    return LBM_OK;
+    return records_to_host(c, rec, (size_t)B * sizeof(lbm_solid_force_record), out);
 }
 }  // extern "C"

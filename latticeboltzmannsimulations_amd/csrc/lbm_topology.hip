@@ -67,21 +67,19 @@ static int topology_enqueue(lbm_ctx* c, int which, const TopoSpec& sp, long long
         using VT = decltype(v);
         using R = typename VT::R;
         constexpr bool PROM = coll_is_prom(VT::COLL);
-        const R* src = c->lat[which].as<const R>();
-        hipLaunchKernelGGL((k_topo_totals<R, VT::SEM, PROM>), tiles, dim3(BLK), 0, c->s_compute, src, c->plan.geo, c->raw[which], (R)c->p.uLB,
-                           c->plan.bstride, sp.host_f32, b.total);
+        const auto f = fields_of<VT>(c, which);
+        hipLaunchKernelGGL((k_topo_totals<R, VT::SEM, PROM>), tiles, dim3(BLK), 0, c->s_compute, f, sp.host_f32, b.total);
         hipLaunchKernelGGL(k_topo_offsets, dim3((c->plan.geo.ny + BLK - 1) / BLK, 1, c->plan.batch), dim3(BLK), 0, c->s_compute, b.total, g.nb,
                            c->plan.geo.ny, b.close);
         if (psi_out)
-            hipLaunchKernelGGL((k_topo_extrema<R, VT::SEM, PROM, true>), tiles, dim3(BLK), 0, c->s_compute, src, c->plan.geo, c->raw[which],
-                               (R)c->p.uLB, c->plan.bstride, sp, (const double*)b.total, b.partial, psi_out);
+            hipLaunchKernelGGL((k_topo_extrema<R, VT::SEM, PROM, true>), tiles, dim3(BLK), 0, c->s_compute, f, sp, (const double*)b.total, b.partial,
+                               psi_out);
         else
-            hipLaunchKernelGGL((k_topo_extrema<R, VT::SEM, PROM, false>), tiles, dim3(BLK), 0, c->s_compute, src, c->plan.geo, c->raw[which],
-                               (R)c->p.uLB, c->plan.bstride, sp, (const double*)b.total, b.partial, (double*)nullptr);
+            hipLaunchKernelGGL((k_topo_extrema<R, VT::SEM, PROM, false>), tiles, dim3(BLK), 0, c->s_compute, f, sp, (const double*)b.total, b.partial,
+                               (double*)nullptr);
         if (with_record)
             hipLaunchKernelGGL((k_topo_final<R, VT::SEM, PROM>), dim3(LBM_TOPOLOGY_MAX_WINDOWS, c->plan.batch), dim3(BLK), 0, c->s_compute,
-                               (const double*)b.partial, (int)g.nwg(), (const double*)b.close, src, c->plan.geo, c->raw[which], (R)c->p.uLB,
-                               c->plan.bstride, sp, (double)step, (double*)b.rec);
+                               (const double*)b.partial, (int)g.nwg(), (const double*)b.close, f, sp, (double)step, (double*)b.rec);
     });
 }
 
@@ -96,14 +94,9 @@ int lbm_topology(lbm_ctx* c, const lbm_topology_spec* spec, lbm_topology_record*
     const std::string bad = check_spec(c, spec);
     if (!bad.empty()) return fail(c, LBM_ERR_INVALID, "lbm_topology: " + bad);
     if (is_slab(c->plan)) return fail(c, LBM_ERR_STATE, "lbm_topology: not on a slab (omega needs rows of the neighbour)");
-    if (c->nsteps == 0) return fail(c, LBM_ERR_STATE, "lbm_topology: no step yet (the fields of an iteration exist after it)");
-    HIP_TRY(c, hipSetDevice(c->p.device));
-    int rc = sync_all(c);
-    if (rc) return rc;
-    rc = ensure_topo(c, false);
-    if (rc) return rc;
     int which = 0;
-    rc = prev_lattice(c, &which);   // (what lbm_get_fields exports: the lattice the last iteration started from)
+    int rc = reader_source(c, "lbm_topology", true, &which);
+    if (rc == LBM_OK) rc = ensure_topo(c, false);
     if (rc) return rc;
     TopoSpec sp{};
     sp.host_f32 = spec->host_dtype == LBM_F32;
@@ -112,26 +105,19 @@ int lbm_topology(lbm_ctx* c, const lbm_topology_spec* spec, lbm_topology_record*
         for (int j = 0; j < 4; ++j) sp.win[i][j] = spec->window[i][j];
     rc = topology_enqueue(c, which, sp, c->nsteps, nullptr, true);
     if (rc) return rc;
-    HIP_TRY(c, hipMemcpyAsync(records_out, topo_buf(c).rec, (size_t)c->plan.batch * sizeof(lbm_topology_record), hipMemcpyDeviceToHost, c->s_compute));
-    HIP_TRY(c, hipStreamSynchronize(c->s_compute));
-    return LBM_OK;
+    return records_to_host(c, topo_buf(c).rec, (size_t)c->plan.batch * sizeof(lbm_topology_record), records_out);
 }
 
 int lbm_get_stream_function(lbm_ctx* c, double* psi_out, double* omega_out, int host_dtype) {
     if (!c || (host_dtype != LBM_F32 && host_dtype != LBM_F64)) return fail(c, LBM_ERR_INVALID, "lbm_get_stream_function: bad argument");
     if (is_slab(c->plan)) return fail(c, LBM_ERR_STATE, "lbm_get_stream_function: not on a slab (omega needs rows of the neighbour)");
-    if (c->nsteps == 0) return fail(c, LBM_ERR_STATE, "lbm_get_stream_function: no step yet (the fields of an iteration exist after it)");
-    if (!psi_out && !omega_out) return LBM_OK;
-    HIP_TRY(c, hipSetDevice(c->p.device));
-    int rc = sync_all(c);
-    if (rc) return rc;
+    int which = 0;
+    int rc = reader_source(c, "lbm_get_stream_function", true, &which);
+    if (rc || (!psi_out && !omega_out)) return rc;
     rc = ensure_topo(c, true);
     if (rc) return rc;
     const int nx = c->plan.geo.nx, ny = c->plan.geo.ny, B = c->plan.batch;
     const size_t n = (size_t)nx * ny;
-    int which = 0;
-    rc = prev_lattice(c, &which);
-    if (rc) return rc;
     double* psi_dev = c->topo_fields.as<double>();
     double* omega_dev = psi_dev + (size_t)B * n;
     if (psi_out) {
@@ -143,13 +129,13 @@ int lbm_get_stream_function(lbm_ctx* c, double* psi_out, double* omega_out, int 
     }
     if (omega_out) {
         // u as the field export stages it (host layout, the lattice's type), then omega from it, one thread per cell
-        rc = ensure_stage(c, (size_t)12 * n * c->plan.es * B);
+        rc = ensure_field_stage(c);
         if (rc) return rc;
         rc = launch_variant(c, [&](auto v) {
             using VT = decltype(v);
             using R = typename VT::R;
-            hipLaunchKernelGGL((k_export_macro<R, VT::SEM, coll_is_prom(VT::COLL)>), dim3((nx + trx<R>() - 1) / trx<R>(), (ny + 31) / 32, B), dim3(BLK), 0,
-                               c->s_compute, c->lat[which].as<const R>(), c->plan.geo, c->raw[which], (R)c->p.uLB, c->stage.as<R>(), c->plan.bstride);
+            hipLaunchKernelGGL((k_export_macro<R, VT::SEM, coll_is_prom(VT::COLL)>), grid_tiles<R>(c), dim3(BLK), 0, c->s_compute, fields_of<VT>(c, which),
+                               c->stage.as<R>());
             hipLaunchKernelGGL((k_topo_omega<R>), dim3((unsigned)((n + BLK - 1) / BLK), 1, B), dim3(BLK), 0, c->s_compute, c->stage.as<const R>(), nx, ny,
                                (int)(host_dtype == LBM_F32), omega_dev);
         });

@@ -1,6 +1,6 @@
 // lbm_topology.hpp -- kernels of the flow topology (lbm_topology, lbm_get_stream_function; contract in include/lbm.h): the stream
 // function psi as a two-level prefix sum along x, its extrema inside up to eight windows, the vorticity omega.  The sample is the
-// monitor's (gather + macros + mon_value).  Included by lbm_topology.hip alone.
+// monitor's (Fields::exported, lbm_fields.hpp).  Included by lbm_topology.hip alone.
 //
 //   k_topo_totals    a workgroup takes TOPO_ROWS rows x one block of LBM_TOPOLOGY_BLOCK cells of x, plus the cell to its left: the
 //                    gather runs along x (coalesced), uy goes to LDS as doubles, one thread per row sums the block's terms in order
@@ -64,14 +64,11 @@ struct TopoPair {
     }
 };
 
-// ux, uy of cell (x, y) as lbm_get_fields(host_dtype) hands them out, in double
-template <typename R, int SEM, bool PROM>
-__device__ __forceinline__ void topo_u(const R* __restrict__ src, const Geo& geo, int raw, R uLB, int host_f32, int x, int y, double& dux, double& duy) {
-    R g[Q], rho, ux, uy;
-    gather<R, SEM, PROM>(src, geo, raw, uLB, x, y, g);
-    macros<R, false, SEM>(g, x, geo.y0 + y, geo.nx, geo.NY, uLB, rho, ux, uy);
-    dux = mon_value(ux, host_f32);
-    duy = mon_value(uy, host_f32);
+// ux, uy of cell (x, y) of the view's lattice as lbm_get_fields(host_dtype) hands them out, in double
+template <typename F>
+__device__ __forceinline__ void topo_u(const F& lat, int host_f32, int x, int y, double& dux, double& duy) {
+    double drho;
+    lat.exported(x, y, host_f32, dux, duy, drho);
 }
 
 // d/di of a line of n >= 2 values at index i from lo = v[i - 1], mid = v[i], hi = v[i + 1] (the one outside the line is not used):
@@ -83,21 +80,21 @@ __device__ __forceinline__ double topo_diff(double lo, double mid, double hi, in
 
 // Phase 1 of a tile: uy of rows ty0 .. ty0 + TOPO_ROWS - 1, cells x0 - 1 .. x0 + TOPO_W - 1 into u[r][j] (j = 0: the left neighbour);
 // cells outside the lattice are left alone (phase 2 does not read them).
-template <typename R, int SEM, bool PROM>
-__device__ __forceinline__ void topo_tile_load(const R* __restrict__ src, const Geo& geo, int raw, R uLB, int host_f32, int x0, int ty0,
-                                               double (*u)[TOPO_PITCH]) {
+template <typename F>
+__device__ __forceinline__ void topo_tile_load(const F& lat, int host_f32, int x0, int ty0, double (*u)[TOPO_PITCH]) {
+    const Geo& geo = lat.geo;
     const int lane = threadIdx.x % TOPO_W;
     for (int r = threadIdx.x / TOPO_W; r < TOPO_ROWS; r += BLK / TOPO_W) {
         const int x = x0 + lane, y = ty0 + r;
         if (x < geo.nx && y < geo.ny) {
             double dux, duy;
-            topo_u<R, SEM, PROM>(src, geo, raw, uLB, host_f32, x, y, dux, duy);
+            topo_u(lat, host_f32, x, y, dux, duy);
             u[r][lane + 1] = duy;
         }
     }
     if (threadIdx.x < TOPO_ROWS && x0 > 0 && ty0 + (int)threadIdx.x < geo.ny) {
         double dux, duy;
-        topo_u<R, SEM, PROM>(src, geo, raw, uLB, host_f32, x0 - 1, ty0 + threadIdx.x, dux, duy);
+        topo_u(lat, host_f32, x0 - 1, ty0 + threadIdx.x, dux, duy);
         u[threadIdx.x][0] = duy;
     }
 }
@@ -119,12 +116,11 @@ __device__ __forceinline__ double topo_tile_scan(double* __restrict__ u, int x0,
 
 // total[(z * nb + b) * ny + y] = the sum of the terms of block b of row y.  Grid (nb, tiles of rows, batch).
 template <typename R, int SEM, bool PROM>
-__global__ __launch_bounds__(BLK) void k_topo_totals(const R* __restrict__ src, Geo geo, int raw, R uLB, long long bstride, int host_f32,
-                                                    double* __restrict__ total) {
+__global__ __launch_bounds__(BLK) void k_topo_totals(Fields<R, SEM, PROM> f, int host_f32, double* __restrict__ total) {
     __shared__ double u[TOPO_ROWS][TOPO_PITCH];
-    src += blockIdx.z * bstride;
+    const Geo& geo = f.geo;
     const int x0 = blockIdx.x * TOPO_W, ty0 = blockIdx.y * TOPO_ROWS;
-    topo_tile_load<R, SEM, PROM>(src, geo, raw, uLB, host_f32, x0, ty0, u);
+    topo_tile_load(f.lattice(blockIdx.z), host_f32, x0, ty0, u);
     __syncthreads();
     const int y = ty0 + threadIdx.x;
     if (threadIdx.x < TOPO_ROWS && y < geo.ny)
@@ -151,13 +147,13 @@ __global__ __launch_bounds__(BLK) void k_topo_offsets(double* __restrict__ total
 // partial[((z * MAX_WINDOWS + w) * nwg + wg) * TOPO_PART ...], wg = blockIdx.y * gridDim.x + blockIdx.x.  FIELDS: psi also goes to
 // psi_out[z][nx][ny] (host layout, written along y).
 template <typename R, int SEM, bool PROM, bool FIELDS>
-__global__ __launch_bounds__(BLK) void k_topo_extrema(const R* __restrict__ src, Geo geo, int raw, R uLB, long long bstride, TopoSpec sp,
-                                                     const double* __restrict__ offs, double* __restrict__ partial, double* __restrict__ psi_out) {
+__global__ __launch_bounds__(BLK) void k_topo_extrema(Fields<R, SEM, PROM> f, TopoSpec sp, const double* __restrict__ offs, double* __restrict__ partial,
+                                                     double* __restrict__ psi_out) {
     __shared__ double u[TOPO_ROWS][TOPO_PITCH];
     __shared__ double sh[BLK / RED_WAVE][TOPO_PART];
-    src += blockIdx.z * bstride;
+    const Geo& geo = f.geo;
     const int x0 = blockIdx.x * TOPO_W, ty0 = blockIdx.y * TOPO_ROWS, w = min(TOPO_W, geo.nx - x0), h = min(TOPO_ROWS, geo.ny - ty0);
-    topo_tile_load<R, SEM, PROM>(src, geo, raw, uLB, sp.host_f32, x0, ty0, u);
+    topo_tile_load(f.lattice(blockIdx.z), sp.host_f32, x0, ty0, u);
     __syncthreads();
     if ((int)threadIdx.x < h)
         topo_tile_scan<true>(u[threadIdx.x], x0, w, offs[((size_t)blockIdx.z * gridDim.x + blockIdx.x) * geo.ny + ty0 + threadIdx.x]);
@@ -189,15 +185,16 @@ __global__ __launch_bounds__(BLK) void k_topo_extrema(const R* __restrict__ src,
 }
 
 // omega of cell (x, y) from the cells around it
-template <typename R, int SEM, bool PROM>
-__device__ __forceinline__ double topo_omega_at(const R* __restrict__ src, const Geo& geo, int raw, R uLB, int host_f32, int x, int y) {
+template <typename F>
+__device__ __forceinline__ double topo_omega_at(const F& lat, int host_f32, int x, int y) {
 #pragma clang fp contract(off)
+    const Geo& geo = lat.geo;
     double ux0, uy0, d, vl = 0.0, vr = 0.0, ul = 0.0, ur = 0.0;
-    topo_u<R, SEM, PROM>(src, geo, raw, uLB, host_f32, x, y, ux0, uy0);
-    if (x > 0) topo_u<R, SEM, PROM>(src, geo, raw, uLB, host_f32, x - 1, y, d, vl);
-    if (x < geo.nx - 1) topo_u<R, SEM, PROM>(src, geo, raw, uLB, host_f32, x + 1, y, d, vr);
-    if (y > 0) topo_u<R, SEM, PROM>(src, geo, raw, uLB, host_f32, x, y - 1, ul, d);
-    if (y < geo.ny - 1) topo_u<R, SEM, PROM>(src, geo, raw, uLB, host_f32, x, y + 1, ur, d);
+    topo_u(lat, host_f32, x, y, ux0, uy0);
+    if (x > 0) topo_u(lat, host_f32, x - 1, y, d, vl);
+    if (x < geo.nx - 1) topo_u(lat, host_f32, x + 1, y, d, vr);
+    if (y > 0) topo_u(lat, host_f32, x, y - 1, ul, d);
+    if (y < geo.ny - 1) topo_u(lat, host_f32, x, y + 1, ur, d);
     const double dvdx = topo_diff(vl, uy0, vr, x, geo.nx), dudy = topo_diff(ul, ux0, ur, y, geo.ny);
     return dvdx + dudy;
 }
@@ -206,11 +203,11 @@ __device__ __forceinline__ double topo_omega_at(const R* __restrict__ src, const
 // extrema and writes the window's entry of the record; the workgroup of window 0 also writes step and closure (the maximum of the
 // finite close[y]; -inf when there is none).  Windows beyond the spec's: psi = omega = NaN, cell (-1, -1).
 template <typename R, int SEM, bool PROM>
-__global__ __launch_bounds__(BLK) void k_topo_final(const double* __restrict__ partial, int nwg, const double* __restrict__ close, const R* __restrict__ src,
-                                                   Geo geo, int raw, R uLB, long long bstride, TopoSpec sp, double step, double* __restrict__ rec) {
+__global__ __launch_bounds__(BLK) void k_topo_final(const double* __restrict__ partial, int nwg, const double* __restrict__ close, Fields<R, SEM, PROM> f,
+                                                   TopoSpec sp, double step, double* __restrict__ rec) {
     __shared__ double sh[BLK / RED_WAVE][TOPO_PART + 1];
     const int i = blockIdx.x, z = blockIdx.y, wave = threadIdx.x / RED_WAVE;
-    src += z * bstride;
+    const Geo& geo = f.geo;
     rec += (size_t)z * TOPO_REC;
     double* out = rec + 2 + 8 * i;   // min {psi, x, y, omega}, max {psi, x, y, omega}
     const bool used = i < sp.nwindows;
@@ -249,7 +246,7 @@ __global__ __launch_bounds__(BLK) void k_topo_final(const double* __restrict__ p
         }
         double* e = out + 4 * threadIdx.x;
         e[0] = c.psi; e[1] = (double)c.x; e[2] = (double)c.y;
-        e[3] = c.x >= 0 ? topo_omega_at<R, SEM, PROM>(src, geo, raw, uLB, sp.host_f32, c.x, c.y) : __builtin_nan("");
+        e[3] = c.x >= 0 ? topo_omega_at(f.lattice(z), sp.host_f32, c.x, c.y) : __builtin_nan("");
     }
     if (i == 0 && threadIdx.x == 0) {
         for (int v = 1; v < BLK / RED_WAVE; ++v) cl = sh[v][TOPO_PART] > cl ? sh[v][TOPO_PART] : cl;
@@ -268,8 +265,8 @@ __global__ __launch_bounds__(BLK) void k_topo_omega(const R* __restrict__ stage,
     const R* ux = stage + blockIdx.z * 3 * n;
     const R* uy = ux + n;
     const int x = (int)(i / ny), y = (int)(i - (long long)x * ny);
-    const double vl = x > 0 ? mon_value(uy[i - ny], host_f32) : 0.0, vr = x < nx - 1 ? mon_value(uy[i + ny], host_f32) : 0.0;
-    const double ul = y > 0 ? mon_value(ux[i - 1], host_f32) : 0.0, ur = y < ny - 1 ? mon_value(ux[i + 1], host_f32) : 0.0;
-    const double dvdx = topo_diff(vl, mon_value(uy[i], host_f32), vr, x, nx), dudy = topo_diff(ul, mon_value(ux[i], host_f32), ur, y, ny);
+    const double vl = x > 0 ? as_exported(uy[i - ny], host_f32) : 0.0, vr = x < nx - 1 ? as_exported(uy[i + ny], host_f32) : 0.0;
+    const double ul = y > 0 ? as_exported(ux[i - 1], host_f32) : 0.0, ur = y < ny - 1 ? as_exported(ux[i + 1], host_f32) : 0.0;
+    const double dvdx = topo_diff(vl, as_exported(uy[i], host_f32), vr, x, nx), dudy = topo_diff(ul, as_exported(ux[i], host_f32), ur, y, ny);
     omega[blockIdx.z * n + i] = dvdx + dudy;
 }

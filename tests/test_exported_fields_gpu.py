@@ -1,0 +1,324 @@
+"""Every reader of the exported state against every source of it, on lattices small enough to fail loudly.
+
+The exported state is what get_fields() returns: the macroscopic state of the lattice the last iteration started from.  That lattice
+is the uploaded one itself (raw) after the first step, the other lattice of the pair after a single step, and a lattice replayed from
+the pair after a unit of several steps.  At each of these instants u, rho = get_fields(out_dtype=...) is the reference, and lines,
+monitor, one statistics sample, the residual between two instants, topology, stream function, mean_u and tau are checked against the
+host statements computed from it -- for the closure in fast arithmetic, the promoted wall equilibrium, MRT.py semantics with kept
+slots, bounce-back walls read in both host types, a solid mask, a batch and three slabs.
+
+Exact fields of a record are compared exactly; its sums (the device adds in another order than numpy) within the bound of a reordered
+double sum, 2 gamma_n sum |x_i| with gamma_n = n eps / (1 - n eps), eps = 2^-53, as tests/test_monitor_gpu.py and
+tests/test_residual_gpu.py state it.  mean_u: within (N - 1) 2^-53 sum |u| / N of the exact mean, N = 2 nx ny terms -- the first-order
+rounding bound of any summation order; the reference sum is math.fsum, which is exact.
+"""
+import ctypes
+import math
+
+import numpy as np
+import pytest
+
+from latticeboltzmannsimulations_amd import CavityBatch, CavitySolver, monitor, residual
+from latticeboltzmannsimulations_amd import topology as T
+from latticeboltzmannsimulations_amd.slab import LocalSlabs, partition_rows
+from oracle.states import state
+
+gpu = pytest.mark.gpu
+
+ULB = 0.08
+MON_EXACT = ("step", "nonfinite", "max_q", "min_q", "min_x", "min_y")
+MON_SUMS = ("sum_ux", "sum_uy", "sum_rho", "sum_q")
+RES_EXACT = ("step", "step_prev", "cells", "nonfinite", "max_du2", "max_x", "max_y", "max_drho2")
+RES_SUMS = ("sum_du2", "sum_u2", "sum_drho2")
+
+
+def _mask(nx, ny):
+    """A block, a cell of the lid row (y = 0) and a corner cell."""
+    m = np.zeros((nx, ny), dtype=bool)
+    m[20:28, 15:22] = True
+    m[30, 0] = True
+    m[nx - 1, ny - 1] = True
+    return m
+
+
+# name -> (constructor, nx, ny, keywords, out_dtypes, a multi-step kernel is planned)
+CONFIGS = {
+    "f32-mrt_gpu-MRT-turb-fast": (CavitySolver, 96, 80, dict(RT="MRT", turb=1, arith="fast"), (np.float32,), True),
+    "f32-mrt_gpu-SRT-promoted": (CavitySolver, 72, 40, dict(RT="SRT", arith="promoted", kernel="tb"), (np.float32,), True),
+    "f64-mrt_py-TRT": (CavitySolver, 70, 66, dict(RT="TRT", semantics="mrt_py", dtype=np.float64), (np.float64,), True),
+    "f64-bounce_back": (CavitySolver, 72, 40, dict(semantics="bounce_back", dtype=np.float64, kernel="tb"), (np.float64, np.float32), True),
+    "f32-solid": (CavitySolver, 72, 40, dict(semantics="bounce_back", solid=_mask(72, 40), tuning=dict(solid_tiles=True)), (np.float32,), True),
+    "f32-batch": (CavityBatch, 64, 64, dict(kernel="tb"), (np.float32,), True),
+}
+CASES = [(name, dt) for name, c in CONFIGS.items() for dt in c[4]]
+
+
+def _spec(nx, ny):
+    return dict(window=(2, nx - 3, 1, ny - 1), exclude=((nx // 3, nx // 2, 0, ny // 2),),
+                probes=((0, 0), (nx - 1, ny - 1), (nx // 2, ny // 2), (17, 0), (nx - 1, 0), (0, ny - 1), (5, ny - 1)))
+
+
+def _windows(nx, ny):
+    return ((1, nx - 1, 1, ny - 1), (min(60, nx // 2), min(70, nx), 0, ny // 2 + 1), (nx - 1, nx, ny // 3, ny))
+
+
+def _gamma2(n):
+    return 2.0 * n * 2.0 ** -53 / (1.0 - n * 2.0 ** -53)
+
+
+def _monitor_equals(got, u, rho, what, rows=None, **spec):
+    want = monitor.host_monitor(u, rho, ULB, rows=rows, step=got["step"], **spec)
+    for k in MON_EXACT:
+        assert got[k] == want[k], f"{what}: monitor {k} {got[k]} != {want[k]}"
+    assert np.array_equal(got["probe"], want["probe"], equal_nan=True), f"{what}: monitor probes"
+    y0, n = (0, u.shape[2]) if rows is None else rows
+    ux, uy, r = (a[:, y0:y0 + n].astype(np.float64) for a in (u[0], u[1], rho))
+    q = (ux * ux + uy * uy) / (ULB * ULB)
+    for k, a in zip(MON_SUMS, (ux, uy, r, q)):
+        tol = _gamma2(a.size) * float(np.abs(a).sum())
+        assert abs(got[k] - want[k]) <= tol, f"{what}: monitor {k} off by {abs(got[k] - want[k])}, bound {tol}"
+
+
+def _residual_equals(got, prev, cur, what, rows=None):
+    """prev, cur: (step, u, rho)."""
+    want = residual.host_residual(prev[1], prev[2], cur[1], cur[2], rows=rows, step=cur[0], step_prev=prev[0])
+    for k in RES_EXACT:
+        assert got[k] == want[k], f"{what}: residual {k} {got[k]} != {want[k]}"
+    y0, n = (0, cur[1].shape[2]) if rows is None else rows
+    a = [x[..., y0:y0 + n].astype(np.float64) for x in (prev[1][0], prev[1][1], prev[2], cur[1][0], cur[1][1], cur[2])]
+    dux, duy, dr = a[3] - a[0], a[4] - a[1], a[5] - a[2]
+    for k, t in zip(RES_SUMS, (dux * dux + duy * duy, a[3] * a[3] + a[4] * a[4], dr * dr)):
+        tol = _gamma2(t.size) * float(np.abs(t).sum())
+        assert abs(got[k] - want[k]) <= tol, f"{what}: residual {k} off by {abs(got[k] - want[k])}, bound {tol}"
+
+
+def _mean_u_equals(got, u, what):
+    """u: the cells the mean runs over, in the lattice's type."""
+    n = u.size
+    want = math.fsum(u.astype(np.float64).ravel()) / n
+    bound = (n - 1) * 2.0 ** -53 * float(np.abs(u.astype(np.float64)).sum()) / n
+    print(f"{what}: mean_u {got!r}, exact {want!r}, off by {abs(got - want):.3e}, bound {bound:.3e}")
+    assert abs(got - want) <= bound, f"{what}: mean_u off by {abs(got - want)}, bound {bound}"
+
+
+def _raw_stats(s):
+    """lbm_stats_get as it comes: E[u], E[rho], (E[uu], E[vv], E[uv]), count."""
+    lead = s._lead
+    mu, mrho, sec = np.zeros(lead + (2, s.nx, s.ny)), np.zeros(lead + (s.nx, s.ny)), np.zeros(lead + (3, s.nx, s.ny))
+    n = ctypes.c_longlong(-1)
+    assert s.lib.lbm_stats_get(s._h, mu.ctypes.data, mrho.ctypes.data, sec.ctypes.data, ctypes.byref(n)) == 0
+    return mu, mrho, sec, n.value
+
+
+def _one_stats_sample(s):
+    s.begin_statistics(0).sample_statistics()
+    out = _raw_stats(s)
+    s.end_statistics()
+    return out
+
+
+def _stats_equal(got, u, rho, what, rows=None):
+    """One sample: the means are the fields of the lattice's type, widened; the second moments their products rounded once."""
+    y0, n = (0, rho.shape[-1]) if rows is None else rows
+    cut = lambda a: a[..., y0:y0 + n]
+    u64, r64 = cut(u.astype(np.float64)), cut(rho.astype(np.float64))
+    ux, uy = u64[..., 0, :, :], u64[..., 1, :, :]
+    assert got[3] == 1, what
+    assert np.array_equal(cut(got[0]), u64) and np.array_equal(cut(got[1]), r64), f"{what}: the statistics sample is not the fields"
+    assert np.array_equal(cut(got[2]), np.stack([ux * ux, uy * uy, ux * uy], axis=-3)), f"{what}: second moments of the sample"
+
+
+def _eq(a, b):
+    return a == b or (a != a and b != b)
+
+
+def _topology_equals(s, b, u, dt, what):
+    """topology() and stream_function() of lattice b (None: a lone lattice) against the host statements of u."""
+    wins = _windows(s.nx, s.ny)
+    want = T.host_topology(u, ULB, wins, step=s.steps_done)
+    got = s.topology(wins, out_dtype=dt)
+    got = got if b is None else got[b]
+    assert got["step"] == want["step"] and got["closure"] == want["closure"], f"{what}: topology step / closure"
+    for i, (g, w) in enumerate(zip(got["window"], want["window"])):
+        for side in ("min", "max"):
+            for k in ("psi", "x", "y", "omega"):
+                assert _eq(g[side][k], w[side][k]), f"{what}: topology window {i} {side} {k}: {g[side]} != {w[side]}"
+    psi, omega = s.stream_function(out_dtype=dt)
+    hpsi, homega = T.host_stream_function(u)
+    assert np.array_equal(psi if b is None else psi[b], hpsi), f"{what}: psi"
+    assert np.array_equal(omega if b is None else omega[b], homega), f"{what}: omega"
+
+
+def _lines_equal(lines, u, rho, nx, ny, what):
+    """lines(x=, y=): the callable of a solver or of the slabs' driver."""
+    for x, y in ((nx // 2, ny // 2), (nx - 1, 0), (0, ny - 1)):
+        col, row = lines(x, y)
+        assert col.dtype == row.dtype == u.dtype
+        assert np.array_equal(col, np.stack([u[0, x], u[1, x], rho[x]])), f"{what}: column {x}"
+        assert np.array_equal(row, np.stack([u[0, :, y], u[1, :, y], rho[:, y]])), f"{what}: row {y}"
+
+
+def _upload(nx, ny, dtype, nlat=None):
+    if nlat is None:
+        return state("S2", nx, ny, dtype, uLB=ULB)
+    return np.stack([state("S2", nx, ny, dtype, uLB=ULB, seed=2026 + b) for b in range(nlat)])
+
+
+@gpu
+@pytest.mark.parametrize("name,dt", CASES, ids=[f"{n}-out_{np.dtype(d).name}" for n, d in CASES])
+def test_every_reader_sees_what_get_fields_returns_from_every_source(name, dt):
+    cls, nx, ny, kw, _, multi = CONFIGS[name]
+    batch = cls is CavityBatch
+    make = (lambda **extra: cls(nx, ny, [100.0, 1000.0], **kw, **extra)) if batch else (lambda **extra: cls(nx, ny, 1000.0, **kw, **extra))
+    turb = kw.get("turb", 0)
+    with make() as s:
+        twin = None
+        try:
+            lat = [None] if not batch else list(range(s.batch))
+            pick = lambda a, b: a if b is None else a[b]
+            f = _upload(nx, ny, s.dtype.type, s.batch if batch else None)
+            s.set_state(f)
+            d = s.describe()
+            assert (d["kernel"] != "none" and d["steps_per_launch"] >= 3) == multi, d
+            if turb:   # tau with the closure: a twin whose calls always end in a single step never replays the lagged lattice
+                twin = make(tuning=dict(eager_lag=True))
+                twin.set_state(f)
+
+            def tau_and_mean(what):
+                u0, _ = s.get_fields()
+                m = s.mean_u()
+                for b in lat:
+                    _mean_u_equals(float(pick(m, b)), pick(u0, b), f"{what} lattice {b}")
+                tau = s.get_tau(out_dtype=dt)
+                if turb:
+                    assert np.array_equal(tau, twin.get_tau(out_dtype=dt)), f"{what}: tau"
+                    assert (tau != tau.flat[0]).any(), f"{what}: the closure left tau constant"
+                else:
+                    for b in lat:
+                        omega = (s.relax_list[b] if batch else s.relax)["omega"]
+                        assert np.all(pick(tau, b) == dt(s.dtype.type(1.0) / s.dtype.type(omega))), f"{what}: tau"
+
+            # ---- before any step: the uploaded populations, raw
+            u, rho = s.get_fields(out_dtype=dt)
+            assert np.isfinite(u).all() and np.isfinite(rho).all()
+            tau_and_mean(f"{name} before any step")
+            if s.has_solid:
+                m = s.solid
+                assert not u[:, m].any() and np.all(rho[m] == rho[m][0]) and abs(float(rho[m][0]) - 1.0) < 1e-6
+            # ---- after step(1): raw; one more: lag 0; a multi-step unit: the lagged lattice, replayed
+            s.begin_residual(out_dtype=dt)
+            prev = None
+            K = d["steps_per_launch"]
+            for n, source in ((1, "raw"), (1, "lag 0"), (K, "replayed")):
+                if source == "replayed" and multi:
+                    assert s.next_unit(n) == n, f"the unit of {n} steps is cut: {s.next_unit(n)}"
+                s.step(n)
+                if twin is not None:
+                    twin.step(n)
+                what = f"{name} out={np.dtype(dt).name} after {s.steps_done} ({source})"
+                u, rho = s.get_fields(out_dtype=dt)
+                u0, rho0 = s.get_fields()
+                assert np.array_equal(u0.astype(dt), u) and np.array_equal(rho0.astype(dt), rho), f"{what}: host rounding"
+                st = _one_stats_sample(s)
+                _stats_equal(st, u0, rho0, what)
+                s.sample_residual()
+                spec = _spec(nx, ny)
+                rec = s.monitor(out_dtype=dt, **spec)
+                for b in lat:
+                    ub, rb = pick(u, b), pick(rho, b)
+                    _lines_equal(lambda x, y: tuple(pick(a, b) for a in s.lines(x=x, y=y, out_dtype=dt)), ub, rb, nx, ny, what)
+                    _monitor_equals({k: pick(v, b) for k, v in rec.items()}, ub, rb, what, **spec)
+                    _topology_equals(s, b, ub, dt, what)
+                cur = (s.steps_done, u, rho)
+                if prev is not None:
+                    series = s.residual_series()
+                    assert series["count"] == (2 if source == "replayed" else 1)
+                    for b in lat:
+                        _residual_equals(residual.record_at(series, series["count"] - 1, b), (prev[0], pick(prev[1], b), pick(prev[2], b)),
+                                         (cur[0], pick(u, b), pick(rho, b)), what)
+                prev = cur
+                tau_and_mean(what)
+                if s.has_solid:
+                    m = s.solid
+                    assert not u[:, m].any() and np.all(rho[m] == rho[m][0])
+        finally:
+            if twin is not None:
+                twin.close()
+
+
+@gpu
+def test_three_slabs_read_what_the_lone_lattice_exports():
+    """96 x 80 in three slabs: the lid and bottom overrides sit on global rows, so geo.y0 decides where they apply.  The slabs are
+    combined as tests/test_monitor_gpu.py, tests/test_residual_gpu.py and tests/test_statistics_gpu.py combine them; the reference is
+    the lone lattice's get_fields().  (Topology and stream function refuse a slab.)"""
+    nx, ny, dt = 96, 80, np.float32
+    parts = partition_rows(ny, 3)
+    mr = min(n for _, n in parts)
+    spec = _spec(nx, ny)
+    with CavitySolver(nx, ny, 1000.0, dtype=dt) as whole:
+        slabs = [CavitySolver(nx, ny, 1000.0, dtype=dt, rows=r, min_rows=mr) for r in parts]
+        try:
+            f = state("S2", nx, ny, dt, uLB=ULB)
+            for st in [whole] + slabs:
+                st.set_state(f)
+            drv = LocalSlabs(slabs)
+
+            def fields_and_means(what):
+                u, rho = whole.get_fields()
+                gu, grho = np.zeros_like(u), np.zeros_like(rho)
+                for sl in slabs:   # (each slab writes its own rows only)
+                    sl.get_fields(u=gu, rho=grho)
+                    _mean_u_equals(sl.mean_u(), u[:, :, sl.y0:sl.y0 + sl.ny_local], f"{what} slab {sl.y0}")
+                    assert np.all(sl.get_tau()[:, sl.y0:sl.y0 + sl.ny_local] == np.float32(1.0) / np.float32(sl.relax["omega"]))
+                assert np.array_equal(gu, u) and np.array_equal(grho, rho), f"{what}: the slabs' fields"
+                return u, rho
+
+            fields_and_means("before any step")
+            for sl in slabs:
+                sl.begin_residual()
+            prev = None
+            for n in (1, 1, 5):
+                whole.step(n); drv.step(n)
+                what = f"slabs after {whole.steps_done}"
+                u, rho = fields_and_means(what)
+                _lines_equal(lambda x, y: drv.lines(x=x, y=y), u, rho, nx, ny, what)
+                _monitor_equals(drv.monitor(**spec), u, rho, what, **spec)
+                for sl in slabs:
+                    rows = (sl.y0, sl.ny_local)
+                    _monitor_equals(sl.monitor(**spec), u, rho, f"{what} slab {sl.y0}", rows=rows, **spec)
+                    _stats_equal(_one_stats_sample(sl), u, rho, f"{what} slab {sl.y0}", rows=rows)
+                    sl.sample_residual()
+                cur = (whole.steps_done, u, rho)
+                if prev is not None:
+                    each = [sl.residual_series() for sl in slabs]
+                    last = each[0]["count"] - 1
+                    _residual_equals(residual.combine([residual.record_at(e, last) for e in each]), prev, cur, what)
+                    for sl, e in zip(slabs, each):
+                        _residual_equals(residual.record_at(e, last), prev, cur, f"{what} slab {sl.y0}", rows=(sl.y0, sl.ny_local))
+                prev = cur
+        finally:
+            for sl in slabs:
+                sl.close()
+
+
+def test_the_host_statements_are_finite_for_the_uploaded_state_on_these_shapes():
+    """No GPU: the plain moments of S2 (the wall overrides only replace values by 0, uLB or a finite sum) through every host statement
+    the GPU tests compare with."""
+    shapes = {(c[1], c[2], np.dtype(c[3].get("dtype", np.float32)).type) for c in CONFIGS.values()} | {(96, 80, np.float32)}
+    for nx, ny, dtype in sorted(shapes, key=str):
+        fields = []
+        for seed in (2026, 2027):
+            f = state("S2", nx, ny, dtype, uLB=ULB, seed=seed)
+            rho = f.sum(axis=0)
+            u = np.stack([(f[1] - f[3] + f[5] - f[6] - f[7] + f[8]) / rho, (f[2] - f[4] + f[5] + f[6] - f[7] - f[8]) / rho])
+            assert np.isfinite(u).all() and np.isfinite(rho).all() and (np.abs(u) < 0.2).all()
+            fields.append((u, rho))
+        (u, rho), (u1, rho1) = fields
+        rec = monitor.host_monitor(u, rho, ULB, step=1, **_spec(nx, ny))
+        assert all(np.isfinite(rec[k]) for k in MON_EXACT + MON_SUMS) and np.isfinite(rec["probe"]).all() and rec["nonfinite"] == 0
+        res = residual.host_residual(u, rho, u1, rho1, step=2, step_prev=1)
+        assert all(np.isfinite(res[k]) for k in RES_EXACT + RES_SUMS) and res["nonfinite"] == 0 and res["cells"] == nx * ny
+        top = T.host_topology(u, ULB, _windows(nx, ny), step=1)
+        assert np.isfinite(top["closure"]) and all(np.isfinite(w[s][k]) for w in top["window"] for s in ("min", "max") for k in ("psi", "omega"))
+        psi, omega = T.host_stream_function(u)
+        assert np.isfinite(psi).all() and np.isfinite(omega).all()
