@@ -1,7 +1,10 @@
-"""Labelled solid masks for the tests of the per-body force (tests/test_body_force_cpu.py, tests/test_body_force_gpu.py).
+"""Labelled solid masks for the tests of the per-body force (tests/test_body_force_cpu.py, tests/test_body_force_gpu.py), and the
+Taylor-Couette case of the moving-body tests (tests/test_body_motion_cpu.py, tests/test_body_motion_gpu.py).
 
 cases(nx, ny) -> name -> (mask bool [nx, ny], labels int32 [nx, ny] or None, nbodies): what the link list, the segments of the
 reduction and the labels can get wrong.  Rows are placed relative to ny, so that the cases exist on the 8-row lattices too."""
+import math
+
 import numpy as np
 
 
@@ -72,3 +75,30 @@ def labels_of(mask, labels):
     """The labels the library reports: `labels` on solid cells (0 for the default body), -1 on fluid cells."""
     lab = np.zeros(mask.shape, dtype=np.int32) if labels is None else labels
     return np.where(mask, lab, -1).astype(np.int32)
+
+
+# ---- Taylor-Couette: the case and what the reference measured on it (DESIGN.md 2.10) -------------------------------------------------------
+TC_N, TC_C, TC_R1, TC_R2, TC_UW, TC_STEPS = 48, 23.5, 6.2, 20.6, 0.05, 6000
+TC_RE = 0.08 * 48 * 6                       # nu = uLB nx / Re = 1/6: tau = 1
+TC_TORQUE_ERR, TC_PROFILE_ERR = 0.0084836, 0.0152721      # |tz / closed form - 1| and max |u_theta - (A r + B / r)| / (Om R1), measured once
+TC_FACTOR = 2.0                             # covers a later change of operator constants and nothing else
+
+
+def tc_case():
+    xs, ys = np.meshgrid(np.arange(TC_N), np.arange(TC_N), indexing="ij")
+    r = np.hypot(xs - TC_C, ys - TC_C)
+    mask = (r < TC_R1) | (r > TC_R2)
+    labels = np.where(r < TC_R1, 0, 1).astype(np.int32)
+    Om = TC_UW / TC_R1
+    return dict(mask=mask, labels=labels, centres=[[TC_C, TC_C], [TC_C, TC_C]], motion=[[0.0, 0.0, Om], [0.0, 0.0, 0.0]], r=r, xs=xs, ys=ys, Om=Om)
+
+
+def tc_errors(u, tz, case):
+    """(torque errors of both bodies, profile error) against the closed form: tz = -+ 4 pi nu Om R1^2 R2^2 / (R2^2 - R1^2), nu = 1/6, and
+    u_theta = A r + B / r for R1 + 1.5 < r < R2 - 1.5, as a fraction of the wall speed."""
+    R1, R2, Om, r = TC_R1, TC_R2, case["Om"], case["r"]
+    T = 4.0 * math.pi * (1.0 / 6.0) * Om * R1 ** 2 * R2 ** 2 / (R2 ** 2 - R1 ** 2)
+    A, B = -Om * R1 ** 2 / (R2 ** 2 - R1 ** 2), Om * R1 ** 2 * R2 ** 2 / (R2 ** 2 - R1 ** 2)
+    sel = (r > R1 + 1.5) & (r < R2 - 1.5)
+    ut = ((case["ys"] - TC_C) * u[0] + (case["xs"] - TC_C) * u[1]) / r          # counter-clockwise with the lid on top
+    return (abs(tz[0] / -T - 1.0), abs(tz[1] / T - 1.0)), float(np.abs(ut - (A * r + B / r))[sel].max() / TC_UW)

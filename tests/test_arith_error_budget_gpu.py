@@ -12,7 +12,7 @@ five steps per launch), fields read after 1, 2, 5, 13 and 26 steps (calls of 1, 
 * after 1 step err_fast <= 32 eps of the lattice type;
 * after every call err <= K max(err_strict, eps) for fast, and for promoted (fp32).
 
-K is set from MI355X measurements over the whole matrix (also in DESIGN.md "Arithmetic contract"): the largest ratio
+K (tests/cases.py) is set from MI355X measurements over the whole matrix (also in DESIGN.md "Arithmetic contract"): the largest ratio
 err / max(err_strict, eps) over every field, state, rate set and step count was 2.31 (fp64 TRT + closure, fast); K = 4 x 2.31.
 Maxima over the four states, both rate sets and the five read-outs (ratios over fin, u, rho and tau):
 
@@ -61,32 +61,20 @@ bounce-back the median fin ratio is 0.88 - 1.05 per row; the largest ratio, 2.66
 err_strict is about 1 eps.  The largest fin error sits on a wall cell in 51 of the 240 read-outs (39 of 240 for the strict operators
 under MRT.py's walls), with ratios <= 1.15 there: no wall row, column or corner stands out, and no bug was found in the wall paths.
 """
-import os
-import sys
-
 import numpy as np
 import pytest
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from oracle.lbm_numpy import CavityOracle      # noqa: E402
-from oracle.lbm_ref import CavityOracleC       # noqa: E402
-from oracle.states import STATES, state        # noqa: E402
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from bounce_back_ref import BounceBackOracle   # noqa: E402
-from latticeboltzmannsimulations_amd import CavityBatch, CavitySolver  # noqa: E402
-from latticeboltzmannsimulations_amd.slab import LocalSlabs, partition_rows  # noqa: E402
+from bounce_back_ref import BounceBackOracle
+from cases import BATCH_RATES, CALLS, DISTINCT, FAM_CALLS, NX, NY, RE, WALL_FAMILIES, _assert_budget, _errs, _fields, _stepped
+from cases import _family_shape as _shape
+from cases import _same_calls as _same_bits
+from oracle.lbm_numpy import CavityOracle
+from oracle.lbm_ref import CavityOracleC
+from oracle.states import STATES, state
+from latticeboltzmannsimulations_amd import CavityBatch, CavitySolver
+from latticeboltzmannsimulations_amd.slab import LocalSlabs, partition_rows
 
 pytestmark = pytest.mark.gpu
-
-NX, NY, RE, ULB = 96, 80, 1000.0, 0.08
-CALLS = (1, 1, 3, 8, 13)
-DISTINCT = dict(omega_e=1.13, omega_eps=1.41, omega_q=1.67, omegam=1.31)
-RATIO_MAX = 2.31       # measured on an MI355X over the whole matrix (see the module docstring)
-K = min(16.0, 4 * RATIO_MAX)
-
-
-def _err(x, ref):
-    return float(np.abs(np.asarray(x, dtype=np.longdouble) - ref).max() / np.abs(ref).max())
 
 
 def _where(x, ref):
@@ -95,25 +83,11 @@ def _where(x, ref):
     return np.unravel_index(int(np.argmax(d)), d.shape)
 
 
-def _fields(s, turb):
-    u, rho, fin = s.get_fields(want_fin=True)
-    out = dict(fin=fin, u=u, rho=rho)
-    if turb:
-        out["tau"] = s.get_tau()
-    return out
-
-
 def _ref_fields(L, turb):
     out = dict(fin=L.fin, u=L.u, rho=L.rho)
     if turb:
         out["tau"] = L.tau
     return out
-
-
-def _errs(got, ref):
-    e = {k: _err(got[k], ref[k]) for k in got}
-    e["u"] *= float(np.abs(ref["u"]).max()) / ULB       # u / uLB
-    return e
 
 
 def _lattice_oracle(sem, nx, ny, coll, dtype, turb, rates, promote=False):
@@ -168,21 +142,6 @@ def measure(dtype, coll, turb, st, rates, sem="mrt_gpu"):
             s.close()
 
 
-def _assert_budget(m, tag0, dtype, rates):
-    eps = float(np.finfo(dtype).eps)
-    for a in m:
-        if a == "strict":
-            continue
-        for (steps, e, at), (_, es, _) in zip(m[a], m["strict"]):
-            tag = (a, np.dtype(dtype).name) + tag0 + ("distinct" if rates else "default", steps)
-            if steps == 1 and a == "fast":
-                for k, v in e.items():
-                    assert v <= 32 * eps, (tag, k, v / eps, "eps after one step; largest fin error at (k, x, y) =", at)
-            for k, v in e.items():
-                bound = K * max(es[k], eps)
-                assert v <= bound, (tag, k, v, "ratio", v / max(es[k], eps), "largest fin error at (k, x, y) =", at)
-
-
 @pytest.mark.parametrize("st", STATES)
 @pytest.mark.parametrize("coll,turb", [("SRT", 0), ("SRT", 1), ("TRT", 0), ("TRT", 1), ("MRT", 0), ("MRT", 1)])
 @pytest.mark.parametrize("dtype", [np.float32, np.float64])
@@ -208,46 +167,11 @@ def test_fast_stays_within_the_budget_under_the_other_walls(sem, dtype, coll, st
 FAMILIES = [("generic", 0, {}), ("vec", 0, {}), ("push", 0, {})] + [("tb", s, {}) for s in (2, 3, 4, 5)] + [
     ("stream", 3, dict(stream_walls=False)), ("stream", 8, dict(stream_walls=False)), ("stream", 5, dict(stream_walls=True)),
     ("stream", 8, dict(stream_pairs=True))]
-# MRT.py's walls and bounce-back: the kernels lbm_plan accepts for them, each with the kernel and the steps per launch that describe()
-# must report (tests/test_arith_error_budget_walls_cpu.py confirms every entry by a dry run).  vec, the streaming kernels with the walls
-# inside and, under bounce-back, the push scheme know only MRT_GPU.py's walls.
-WALL_FAMILIES = {
-    "mrt_py": [("generic", 0, {}, "none", 1), ("push", 0, {}, "none", 1),
-               ("tb", 2, {}, "k_step2_deep", 2), ("tb", 3, {}, "k_stepS_deep", 3), ("tb", 4, {}, "k_stepS_deep", 4), ("tb", 5, {}, "k_stepS_deep", 5),
-               ("stream", 3, dict(stream_walls=False), "k_stream", 3), ("stream", 8, dict(stream_walls=False), "k_stream", 8)],
-    "bounce_back": [("generic", 0, {}, "none", 1),
-                    ("tb", 2, {}, "k_step2_deep", 2), ("tb", 3, {}, "k_stepS_deep", 3), ("tb", 4, {}, "k_stepS_deep", 4), ("tb", 5, {}, "k_stepS_deep", 5),
-                    ("stream", 3, dict(stream_walls=False), "k_stream", 3), ("stream", 8, dict(stream_walls=False), "k_stream", 8)]}
-FAM_CALLS = (1, 2, 7, 20)
-BATCH_RATES = [dict(Re=400.0, omega_e=1.13, omega_eps=1.41, omega_q=1.67, omegam=1.31),
-               dict(Re=1000.0, omega_e=0.9, omega_eps=1.55, omega_q=1.25, omegam=1.7),
-               dict(Re=5000.0, omega_e=1.3, omega_eps=1.05, omega_q=1.8, omegam=1.1)]
-
-
-def _shape(kernel):
-    return (264, 150) if kernel == "stream" else (96, 80)
-
-
 def _open(nx, ny, coll, turb, dtype, arith, kernel, tbs, tune, rows=None, sem="mrt_gpu"):
     s = CavitySolver(nx, ny, RE, RT=coll, dtype=dtype, turb=turb, arith=arith, kernel=kernel, rows=rows, semantics=sem,
                      tuning=dict(tb_steps=tbs, **tune))
     s.set_relaxation(0, **DISTINCT)
     return s
-
-
-def _stepped(s, f0, calls):
-    s.set_state(f0)
-    out = []
-    for n in calls:
-        s.step(n)
-        out.append(_fields(s, s.turb))
-    return out
-
-
-def _same_bits(a, b, what):
-    for i, (x, y) in enumerate(zip(a, b)):
-        for k in x:
-            assert np.array_equal(x[k], y[k]), (what, "call", i, k, np.abs(x[k] - y[k]).max())
 
 
 def _plan_is(s, want):

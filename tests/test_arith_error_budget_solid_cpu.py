@@ -12,24 +12,17 @@ tests/test_arith_error_budget_solid_gpu.py):
   check, the long-double reference stays finite with max|fin| <= 1 for every (shape, state) the GPU tests use, and the routes are what
   lbm_plan accepts and names, by a dry run."""
 import itertools
-import os
-import sys
 
 import numpy as np
 import pytest
 
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-
-from bounce_back_ref import BounceBackOracle  # noqa: E402
-from moving_wall_ref import MovingWallOracle, delta_of  # noqa: E402
-from solid_ref import SolidOracle  # noqa: E402
-from oracle.states import state  # noqa: E402
-from test_arith_error_budget_walls_cpu import _FastStep  # noqa: E402
-from test_arith_error_budget_solid_gpu import (BATCH_RATES, BATCH_STEPS, CALLS, DISTINCT, FAM_CALLS, MOVE_STATES, REST_STATES,  # noqa: E402
-                                               SMALLEST, TILES, batch_cases, budget_mask, budget_tile_steps, motion_case, smallest_mask,
-                                               solid_routes)
-from test_solid_tiles_gpu import _tile  # noqa: E402
-from latticeboltzmannsimulations_amd import launch_plan  # noqa: E402
+from bounce_back_ref import BounceBackOracle
+from cases import (BATCH_RATES, BATCH_STEPS, CALLS, DISTINCT, FAM_CALLS, MOVE_STATES, REST_STATES, SMALLEST, TILES, _FastStep, _tile,
+                   batch_cases, budget_mask, budget_tile_steps, motion_case, smallest_mask, solid_routes)
+from moving_wall_ref import MovingWallOracle, delta_of
+from solid_ref import SolidOracle
+from oracle.states import state
+from latticeboltzmannsimulations_amd import launch_plan
 
 LD = np.longdouble
 EPS_LD = float(np.finfo(LD).eps)
@@ -220,7 +213,7 @@ STEP_TOL = 4 * STEP_MEASURED * EPS_LD
 @pytest.mark.parametrize("moving", [False, True], ids=["rest", "moving"])
 @pytest.mark.parametrize("coll", COLLS)
 def test_a_step_on_the_fast_operators_is_the_dense_step_on_every_fluid_cell(coll, moving):
-    """FastSolid / FastMoving (_FastStep of tests/test_arith_error_budget_walls_cpu.py on SolidOracle / MovingWallOracle: collide() on
+    """FastSolid / FastMoving (_FastStep of tests/cases.py on SolidOracle / MovingWallOracle: collide() on
     oracle/lbm_fast.py, fed the plain-sum macros) from S2 and S3 at the distinct rates, after 1, 2, 5, 13 and 26 steps: fin (relative to
     max|fin| over the fluid cells), u / uLB and rho against the dense long-double oracle on every fluid cell; solid cells hold w_k in
     both.  Measured (32 x 24, Re 1000): at most 78.1 long-double eps (SRT 76.6 - 78.1, TRT 53.1 - 64.1, MRT 27.3 - 29.7); the

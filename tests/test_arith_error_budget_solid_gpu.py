@@ -7,7 +7,7 @@ reference is tests/solid_ref.SolidOracle -- with motion tests/moving_wall_ref.Mo
 every link's delta rounded to the lattice type first; the same class in the lattice type is what strict must equal bit for bit, and its
 error is the budget's denominator.  err is taken over FLUID cells; solid cells must hold w_k exactly.
 
-a. at rest (budget_mask: block, staircase, lid row, walls, corner, tile seams, frame boundary, 5 % scatter): strict (k_step_solid),
+a. at rest (cases.budget_mask: block, staircase, lid row, walls, corner, tile seams, frame boundary, 5 % scatter): strict (k_step_solid),
    fast, and fast on the tile route (solid_tiles) and on kernel="generic" (k_step_generic): the same bits as fast, so inside the
    same budget;
 b. with motion (motion_case: a block and a single cell that translate and rotate, two bodies one fluid column apart with different
@@ -17,7 +17,7 @@ c. from S2 at the distinct rates every solid route gives the oracle's bits (stri
 
 * strict is np.array_equal to the lattice-type oracle at the same rates;
 * after 1 step err_fast <= 32 eps of the lattice type;
-* after every call err_fast <= K max(err_strict, eps), K of tests/test_arith_error_budget_gpu.py.
+* after every call err_fast <= K max(err_strict, eps), K of tests/cases.py (derived in tests/test_arith_error_budget_gpu.py).
 
 Measured on an MI355X (maxima over the states, both rate sets and the five read-outs; ratios err_fast / max(err_strict, eps) over
 fin, u and rho).  The tile route (solid_tiles: one single step, then units of 5, 4 and 3 steps) gives the bits of the one-step route in
@@ -47,123 +47,21 @@ and <= 1.31 there, and on the lid row in 19 and 9: no link cell, no lid-row cell
 was found: strict is the oracle's bits at the distinct rates from every state on every route, fast is one set of bits across the
 routes, and no bug showed in gather_a<..., SEM_SOLID>, the tile kernel's SOLID path or the moving twins.
 """
-import os
-import sys
-
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-
-from oracle.states import state  # noqa: E402
-from moving_wall_ref import MovingWallOracle  # noqa: E402
-from solid_ref import SolidOracle  # noqa: E402
-from test_arith_error_budget_gpu import (BATCH_RATES, CALLS, DISTINCT, FAM_CALLS, K, _assert_budget, _err, _errs,  # noqa: E402,F401
-                                         _same_bits, _stepped)
-from test_solid_tiles_gpu import _shape as _tile_shape  # noqa: E402
-from test_solid_tiles_gpu import _tile  # noqa: E402
-from latticeboltzmannsimulations_amd import CavityBatch, CavitySolver, launch_plan, solid  # noqa: E402
+from cases import (BATCH_RATES, BATCH_STEPS, BB, CALLS, DISTINCT, FAM_CALLS, MOVE_STATES, NX, NY, RE, REST_STATES, SMALLEST, TILES,
+                   _assert_budget, _errs, _stepped, batch_cases, budget_mask, budget_tile_steps, motion_case, smallest_mask, solid_routes)
+from cases import _same_calls as _same_bits
+from oracle.states import state
+from moving_wall_ref import MovingWallOracle
+from solid_ref import SolidOracle
+from latticeboltzmannsimulations_amd import CavityBatch, CavitySolver, solid
 
 pytestmark = pytest.mark.gpu
 
 LD = np.longdouble
-NX, NY, RE, ULB = 96, 80, 1000.0, 0.08
-BB = dict(semantics="bounce_back")
-TILES = dict(solid_tiles=True)
-REST_STATES = ("S0", "S1", "S2", "S3")
-MOVE_STATES = ("S0", "S2", "S3")
 COLLS = ("SRT", "TRT", "MRT")
-
-
-# ---- masks, bodies and routes (tests/test_arith_error_budget_solid_cpu.py checks all of them without a device) -------------------
-def budget_mask(nx, ny, dtype, S, seed=2026):
-    """One mask with what a solid kernel can get wrong, for the tile kernel's geometry at S steps per launch (F, TX, TY of
-    test_solid_tiles_gpu._tile): a 6 x 6 block with its edges on x = 3 and x = 0 (mod 4); three cells that touch at corners only; five
-    lid-row cells and a column from the lid two cells down; a cell on each side wall, one on the bottom row, the corner (0, 0); a
-    2 x 2 block across the first tile seam in x and y; single cells on the frame / tile boundary F - 1 | F; and seeded random 5 % of
-    the interior (kept one cell clear of the staircase, so that it stays one)."""
-    F, TX, TY = _tile(dtype, S)
-    m = np.zeros((nx, ny), dtype=bool)
-    m[1:-1, 1:-1] = np.random.default_rng(seed).random((nx - 2, ny - 2)) < 0.05
-    sx, sy = nx // 2 - 6, ny // 2 + 6
-    m[sx - 1:sx + 4, sy - 1:sy + 4] = False
-    for i in range(3):
-        m[sx + i, sy + i] = True
-    by = ny // 4 + 2
-    m[19:25, by:by + 6] = True                                   # columns 19 (= 3 mod 4) .. 24 (= 0 mod 4)
-    m[nx // 2:nx // 2 + 5, 0] = True
-    m[nx // 3, 0:3] = True
-    m[0, ny // 2] = m[nx - 1, ny // 3] = m[nx // 2 + 7, ny - 1] = m[0, 0] = True
-    xs, ys = F + TX, F + TY
-    if xs < nx - F and ys < ny - F:
-        m[xs - 1:xs + 1, ys - 1:ys + 1] = True
-    for a, b in ((F - 1, 12), (F, 15)):
-        if a < nx - 1 and b < ny - 1:
-            m[a, b] = True
-    for a, b in ((14, F - 1), (17, F)):
-        if a < nx - 1 and b < ny - 1:
-            m[a, b] = True
-    assert not m.all()
-    return m
-
-
-def motion_case(nx, ny, shift=0):
-    """(mask, labels, motion[6, 3]): bodies clear of the walls and of each other, so that every rigid motion passes the flux check.
-    Body 0: a 6 x 6 block (edges on x = 3 and 0 mod 4 for shift = 0) that translates and rotates; 1: a single cell that does the same;
-    2, 3: two 3 x 6 blocks one fluid column apart with different motions (a fluid cell linked to both, the `between` case of
-    tests/test_body_motion_gpu.py); 4, 5: two 2 x 2 blocks three fluid cells apart, with different motions as well.  The speeds are
-    half those of that file: at Re 1000 the SRT populations in the one-column gap between bodies 2 and 3 pass 1 within 21 steps otherwise."""
-    m, lab = np.zeros((nx, ny), dtype=bool), np.zeros((nx, ny), dtype=np.int32)
-    y = ny // 4
-    boxes = [(19, 25, y, y + 6), (nx // 2 + 5, nx // 2 + 6, ny // 2, ny // 2 + 1), (32, 35, y + 9, y + 15), (36, 39, y + 9, y + 15),
-             (44, 46, y, y + 2), (49, 51, y + 1, y + 3)]
-    for b, (x0, x1, y0, y1) in enumerate(boxes):
-        m[x0 + shift:x1 + shift, y0:y1] = True
-        lab[x0 + shift:x1 + shift, y0:y1] = b
-    mot = [[0.005, 0.01, 0.01 / nx], [0.01, -0.005, 0.015], [0.015, 0.0, 0.005], [-0.01, 0.005, -0.01], [0.0, -0.01, 0.0075], [0.0075, 0.005, -0.005]]
-    return m, lab, np.asarray(mot)
-
-
-def solid_routes(dtype):
-    """[(shape, kernel, tuning, S of the mask, kernel name, steps per launch)] of the routes at rest: what describe() must report.  The
-    first entry of a shape is the one the others of that shape are compared with.  k_step_generic runs on 96 x 80 against
-    k_step_solid in both types; on 70 x 66 `auto` is k_step_solid in fp64 (a second real comparison) and k_step_generic itself in
-    fp32 (70 is no multiple of 4: there the fast comparison is of the kernel with itself, and only the strict half says something)."""
-    auto_70 = "k_step_generic" if np.dtype(dtype) == np.float32 else "k_step_solid"
-    out = [((NX, NY), "auto", {}, 5, "k_step_solid", 1), ((NX, NY), "generic", {}, 5, "k_step_generic", 1),
-           ((70, 66), "auto", {}, 5, auto_70, 1), ((70, 66), "generic", {}, 5, "k_step_generic", 1)]
-    for S in (3, 4, 5):
-        out.append((_tile_shape(dtype, S), "auto", dict(TILES, tb_steps=S), S, "k_stepS_deep", S))
-    for S in (3, 5):
-        for extra in (dict(frame_lds=False), dict(frame_fused=False)):
-            out.append((_tile_shape(dtype, S), "auto", dict(TILES, tb_steps=S, **extra), S, "k_stepS_deep", S))
-    return out
-
-
-def budget_tile_steps(dtype):
-    """Steps per launch of the tile route on the budget's lattice (a dry run)."""
-    return launch_plan(NX, NY, RE, steps=13, dtype=dtype, tuning=TILES, solid=True, **BB)["steps_per_launch"]
-
-
-BATCH_STEPS = 29
-SMALLEST = ((6, 6), (13, 9))
-
-
-def batch_cases(dtype, moving):
-    """(masks, labels, motions) of the three lattices of the batch test, lattice i with BATCH_RATES[i]: at rest budget_mask with its own
-    seed (labels and motions None); moving: motion_case shifted by 5 i cells with its speeds scaled by 1 - i / 4."""
-    if not moving:
-        return [budget_mask(NX, NY, dtype, budget_tile_steps(dtype), seed=2026 + i) for i in range(3)], None, None
-    cases = [motion_case(NX, NY, shift=5 * i) for i in range(3)]
-    return [c[0] for c in cases], np.stack([c[1] for c in cases]), np.stack([c[2] * (1.0 - 0.25 * i) for i, c in enumerate(cases)])
-
-
-def smallest_mask(nx, ny):
-    mask = np.zeros((nx, ny), dtype=bool)
-    mask[nx // 2, ny // 2] = True
-    return mask
 
 
 # ---- helpers --------------------------------------------------------------------------------------------------------------------

@@ -7,25 +7,19 @@ tests/test_arith_error_budget_gpu.py):
   produces) is the oracle's dense step in long double in every cell, wall cells included, for MRT_GPU.py's walls, MRT.py's walls
   and bounce-back; the density that m_eq[1], m_eq[2] took before the lid-row fix is seen on row 0 under MRT.py's walls too;
 * the kernel families that the GPU test runs under these two semantics are the ones lbm_plan accepts, by a dry run."""
-import os
-import sys
-
 import numpy as np
 import pytest
 
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-
-from bounce_back_ref import BounceBackOracle  # noqa: E402
-from oracle.lbm_fast import mrt_fast, srt_trt_fast  # noqa: E402
-from oracle.lbm_numpy import CavityOracle  # noqa: E402
-from oracle.states import state  # noqa: E402
-from latticeboltzmannsimulations_amd import launch_plan  # noqa: E402
-from latticeboltzmannsimulations_amd.slab import partition_rows  # noqa: E402
+from bounce_back_ref import BounceBackOracle
+from cases import CALLS, DISTINCT, WALL_FAMILIES, _FastStep
+from cases import _family_shape as _shape
+from oracle.lbm_numpy import CavityOracle
+from oracle.states import state
+from latticeboltzmannsimulations_amd import launch_plan
+from latticeboltzmannsimulations_amd.slab import partition_rows
 
 LD = np.longdouble
-DISTINCT = dict(omega_e=1.13, omega_eps=1.41, omega_q=1.67, omegam=1.31)
 EPS_LD = float(np.finfo(LD).eps)
-CALLS = (1, 1, 3, 8, 13)
 NX, NY = 32, 24
 
 
@@ -73,30 +67,7 @@ def test_long_double_bounce_back_reference_takes_the_parameters_as_the_device_ho
     assert o64.relax["omega_eps"] == 1.41 and BounceBackOracle(8, 6, 1000.0).relax["omega_eps"] == 1.2
 
 
-# ---- a whole step on the fast operators, per wall semantics ----------------------------------------------------------------------
-class _FastStep:
-    """The oracle's step with collide() replaced by the restatements of the device's fast operators, fed the rho, ux, uy of the
-    semantics' own macros(): on row 0 the overridden density and u = (uLB, 0) under MRT.py's and MRT_GPU.py's walls (where
-    lbm_device.hpp passes lid = true to the factored MRT operator), the plain sums everywhere under bounce-back.  (The library
-    compiles the fast operators for MRT_GPU.py's walls and for bounce-back; under MRT.py's walls arith = fast runs the strict ones,
-    include/lbm.h, so that column of the checks below is about the algebra alone.)"""
-    meq_density = "rho"
-
-    def macros(self, f):
-        rho, ux, uy = super().macros(f)
-        self._u = (ux, uy)
-        return rho, ux, uy
-
-    def collide(self, f, rho, feq, w_nu=None):
-        if w_nu is None:
-            w_nu = self.par(self.relax["omega"])
-        if self.coll == "MRT":
-            ov = self.omega_vec
-            return np.array(mrt_fast(f, rho, ov[1], ov[2], ov[4], w_nu, meq_density=self.meq_density))
-        ux, uy = self._u
-        return np.array(srt_trt_fast(self.coll, f, rho, ux, uy, w_nu, self.par(self.relax["omegam"])))
-
-
+# ---- a whole step on the fast operators (_FastStep of tests/cases.py), per wall semantics ------------------------------------------
 class FastCavity(_FastStep, CavityOracle):
     pass
 
@@ -173,7 +144,6 @@ def test_the_gpu_tests_kernel_families_are_what_the_plan_accepts(sem, dtype, col
     the 96 x 80 lattice of the budget takes the multi-step tile kernel with its frame under `auto`, and its three slabs agree on
     one plan; vec is refused for both semantics, and the push scheme and the streaming kernels with the walls inside for bounce-back
     (under MRT.py's walls a request for the latter plans the kernel with the frame)."""
-    from test_arith_error_budget_gpu import WALL_FAMILIES, _shape
     kw = dict(RT=coll, semantics=sem, dtype=dtype, arith=arith)
     for kernel, tbs, tune, name, steps in WALL_FAMILIES[sem]:
         p = launch_plan(*_shape(kernel), 1000.0, steps=20, kernel=kernel, tuning=dict(tb_steps=tbs, **tune), **kw)

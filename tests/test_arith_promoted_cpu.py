@@ -1,16 +1,14 @@
 """arith='promoted' without a GPU: the C ABI constant and version, the dry-run launch plans (lbm_plan) and the front ends' plumbing."""
 import os
 import re
-import sys
 
 import numpy as np
 import pytest
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from latticeboltzmannsimulations_amd import _lib as L  # noqa: E402
-from latticeboltzmannsimulations_amd import datagen, mrt_gpu  # noqa: E402
-from latticeboltzmannsimulations_amd.solver import launch_plan  # noqa: E402
-from front_end_standin import standin  # noqa: E402
+from latticeboltzmannsimulations_amd import _lib as L
+from latticeboltzmannsimulations_amd import datagen, mrt_gpu
+from latticeboltzmannsimulations_amd.solver import launch_plan
+from front_end_standin import standin
 
 HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "lbm.h")
 

@@ -2,17 +2,15 @@
 that follow), get_tau -- is bit-identical to the oracle with promote=True (MRT_GPU.py's CUDA text: its double-literal sub-expressions
 evaluated in double, rounded once), for every operator, with and without the closure, on every kernel and launch plan the library
 can choose.  fp64: the same bits as arith='strict'."""
-import os
-import sys
-
 import numpy as np
 import pytest
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from oracle.lbm_ref import CavityOracleC, set_threads, max_threads      # noqa: E402
-from latticeboltzmannsimulations_amd import CavityBatch, CavitySolver  # noqa: E402
-from latticeboltzmannsimulations_amd.slab import LocalSlabs, partition_rows  # noqa: E402
-from latticeboltzmannsimulations_amd.solver import launch_plan  # noqa: E402
+from checks import same_as_oracle
+from mrt_gpu_text_ref import promoted_tau
+from oracle.lbm_ref import CavityOracleC, set_threads, max_threads
+from latticeboltzmannsimulations_amd import CavityBatch, CavitySolver
+from latticeboltzmannsimulations_amd.slab import LocalSlabs, partition_rows
+from latticeboltzmannsimulations_amd.solver import launch_plan
 
 pytestmark = pytest.mark.gpu
 
@@ -24,13 +22,6 @@ def _oracle(nx, ny, Re, coll, turb):
     return CavityOracleC(nx, ny, Re, semantics="mrt_gpu", collision=coll, dtype=np.float32, turb=turb, promote=True)
 
 
-def _same(s, o, what):
-    u, rho, fin = s.get_fields(want_fin=True)
-    assert np.array_equal(fin, o.fin), what
-    assert np.array_equal(u, o.u), what
-    assert np.array_equal(rho, o.rho), what
-
-
 def _run(nx, ny, coll, turb, counts=COUNTS, Re=1000.0, **kw):
     o = _oracle(nx, ny, Re, coll, turb)
     with CavitySolver(nx, ny, Re, RT=coll, dtype=np.float32, turb=turb, arith="promoted", **kw) as s:
@@ -39,7 +30,7 @@ def _run(nx, ny, coll, turb, counts=COUNTS, Re=1000.0, **kw):
             s.step(n - done)
             o.step(n - done)
             done = n
-            _same(s, o, (coll, turb, kw, n))
+            same_as_oracle(s, o, (coll, turb, kw, n))
         return s.describe()
 
 
@@ -81,7 +72,7 @@ def test_auto_c3_mrt_4096():
     with CavitySolver(n, n, 1000.0, RT="MRT", dtype=np.float32, arith="promoted") as s:
         assert s.describe()["kernel"] == launch_plan(n, n, 1000.0, RT="MRT", arith="promoted")["kernel"] == "k_stream_walls"
         s.step(20)
-        _same(s, o, "C3")
+        same_as_oracle(s, o, "C3")
 
 
 def test_auto_datagen_shape():
@@ -133,18 +124,7 @@ def test_init_and_set_state():
             s.step(n - done)
             o.step(n - done)
             done = n
-            _same(s, o, n)
-
-
-def _promoted_tau(o, omega):
-    """taus_g of MRT_GPU.py:385 in lbm_ref.c:97-101's order from the oracle's state: float tau0*tau0 and |q|, the rest in double, one rounding."""
-    f, fe = o.fin, o.feq
-    q = (-f[8] + (f[7] + (-f[6] + f[5]))) - (-fe[8] + (fe[7] + (-fe[6] + fe[5])))       # float32 throughout
-    tau0 = np.float32(1.0) / np.float32(omega)
-    tt, aq = tau0 * tau0, np.abs(q)
-    t = 0.5 * (np.float64(tau0) + np.sqrt(np.float64(tt) + ((18 * 1.4142) * np.float64(np.float32(0.025))) * aq.astype(np.float64)
-                                          / o.rho.astype(np.float64)))
-    return t.astype(np.float32)
+            same_as_oracle(s, o, n)
 
 
 @pytest.mark.parametrize("kernel", ["tb", "stream"])
@@ -155,7 +135,7 @@ def test_get_tau(kernel):
         for n in (1, 7, 1, 13):
             s.step(n)
             o.step(s.steps_done - 1 - o.nsteps)     # one step behind: the state and history the last iteration started from
-            want = _promoted_tau(o, s.relax["omega"])
+            want = promoted_tau(o, s.relax["omega"])
             got = s.get_tau()
             assert got.dtype == np.float32 and np.array_equal(got, want), n
 

@@ -9,9 +9,8 @@ import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-import bench  # noqa: E402
-from oracle.lbm_ref import CavityOracleC, max_threads, set_threads  # noqa: E402
+import bench
+from oracle.lbm_ref import CavityOracleC, max_threads, set_threads
 
 pytestmark = pytest.mark.gpu
 

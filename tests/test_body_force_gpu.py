@@ -10,18 +10,13 @@ enough for a body of exactly one chunk of 2048 links and one of 2054: the seams 
 fp32 136 x 80 on the tile route with five steps per launch.  A random 20 % mask as one body gives several chunks at every shape;
 1024 x 160 gives more chunks than the final pass has lanes."""
 import math
-import os
-import sys
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-
-import body_cases  # noqa: E402
-from test_bounce_back_gpu import FAST_BOUND  # noqa: E402
-from latticeboltzmannsimulations_amd import CavityBatch, CavitySolver, solid  # noqa: E402
+import body_cases
+from checks import FAST_BOUND
+from latticeboltzmannsimulations_amd import CavityBatch, CavitySolver, solid
 
 pytestmark = pytest.mark.gpu
 BB = dict(semantics="bounce_back")

@@ -3,25 +3,18 @@ against the NumPy reference tests/moving_wall_ref.py on the vector kernel (k_ste
 (k_step_generic_move); zero motion gives the bits and the kernels of obstacles at rest; `fast` arithmetic within the bound of a mask at
 rest; batches; the force with 2 f - delta, one-shot, as a series and summed; the error paths; the checkpoint; and Taylor-Couette flow
 between a rotating disc and a ring at rest against its closed form."""
-import os
-import sys
-
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-
-from moving_wall_ref import MovingWallOracle  # noqa: E402
-from solid_ref import SolidOracle  # noqa: E402
-from test_body_motion_cpu import TC_FACTOR, TC_N, TC_PROFILE_ERR, TC_RE, TC_STEPS, TC_TORQUE_ERR, tc_case, tc_errors  # noqa: E402
-from latticeboltzmannsimulations_amd import CavityBatch, CavitySolver, solid  # noqa: E402
+from body_cases import TC_FACTOR, TC_N, TC_PROFILE_ERR, TC_RE, TC_STEPS, TC_TORQUE_ERR, tc_case, tc_errors
+from checks import FAST_BOUND      # (the bound of a mask at rest: the moving-wall term is one more exact constant per link)
+from checks import same_as_oracle, same_fields
+from moving_wall_ref import MovingWallOracle
+from solid_ref import SolidOracle
+from latticeboltzmannsimulations_amd import CavityBatch, CavitySolver, solid
 
 pytestmark = pytest.mark.gpu
 BB = dict(semantics="bounce_back")
-# the bound tests/test_solid_gpu.py::test_fast_arithmetic uses for a mask at rest (FAST_BOUND of tests/test_bounce_back_gpu.py): relative
-# distance of `fast` from strict fp64 after 2000 steps of 128 x 96 at Re 1000.  The moving-wall term is one more exact constant per link.
-FAST_BOUND = {np.float32: 1.2e-4, np.float64: 6e-14}
 
 
 def _cases(nx, ny, seed=11):
@@ -50,19 +43,6 @@ def _cases(nx, ny, seed=11):
     m[1:-1, 1:-1] = np.random.default_rng(seed).random((nx - 2, ny - 2)) < 0.2      # one body that rotates about its centroid
     out["random"] = (m, lab, [[0.0, 0.0, 0.04 / nx]])
     return out
-
-
-def _same(s, o, what):
-    u, rho, fin = s.get_fields(want_fin=True)
-    assert np.isfinite(fin).all(), f"{what}: not finite"
-    assert np.array_equal(fin, o.fin), f"{what}: fin differs in {np.count_nonzero(fin != o.fin)} values, max abs {np.abs(fin - o.fin).max()}"
-    assert np.array_equal(rho, o.rho) and np.array_equal(u, o.u), f"{what}: u or rho differs"
-    return fin
-
-
-def _same_fields(a, b, what):
-    for x, y, name in zip(a.get_fields(want_fin=True), b.get_fields(want_fin=True), ("u", "rho", "fin")):
-        assert np.array_equal(x, y), f"{what}: {name} differs"
 
 
 # 72 x 40: one partial workgroup; 70 x 66: the generic route in fp32 (70 is no multiple of 4); 1032 x 8 and (fp64) 520 x 8: the seams
@@ -96,15 +76,15 @@ def test_strict_bit_identical_to_reference(coll, dtype, shape):
                 for n in (1, 1, 5, 30):
                     s.step(n); g.step(n); o.step(n)
                     what = f"{nx}x{ny} {coll} {np.dtype(dtype).name} case {name} phase {phase} after {o.nsteps}"
-                    fin = _same(s, o, what)
-                    _same_fields(g, s, what + " generic")
+                    _, _, fin = same_as_oracle(s, o, what)
+                    same_fields(g, s, what + " generic")
                     assert np.array_equal(fin[:, m], np.broadcast_to(o.t[:, None], (9, int(m.sum())))), what + ": solid cells"
             other = -0.5 * np.asarray(mot)                                          # a motion changed between two step calls
             for x in (s, g, o):
                 (x.set_motion if x is o else x.set_body_motion)(other)
             s.step(3); g.step(3); o.step(3)
-            _same(s, o, f"{nx}x{ny} {coll} case {name}: after the change of motion")
-            _same_fields(g, s, f"{nx}x{ny} {coll} case {name}: after the change of motion, generic")
+            same_as_oracle(s, o, f"{nx}x{ny} {coll} case {name}: after the change of motion")
+            same_fields(g, s, f"{nx}x{ny} {coll} case {name}: after the change of motion, generic")
 
 
 @pytest.mark.parametrize("dtype", [np.float32, np.float64])
@@ -123,8 +103,8 @@ def test_zero_motion_is_a_context_at_rest(dtype):
             s.set_body_motion(np.zeros((2, 3)))
             assert "wall_motion" not in s.describe() and "wall_motion" not in never.describe() and not s.body_motion.any()
             never.step(12); s.step(12)
-            _same(never, o, f"never {kernel}")
-            _same(s, o, f"zero {kernel}")
+            same_as_oracle(never, o, f"never {kernel}")
+            same_as_oracle(s, o, f"zero {kernel}")
             Fs, Fn = s.body_force(), never.body_force()
             assert all(np.array_equal(Fs[k], Fn[k]) for k in ("links", "fx", "fy", "tz")) and s.solid_force() == never.solid_force()
             s.set_body_motion(mot)
@@ -194,7 +174,7 @@ def test_force_subtracts_delta(dtype):
             s.set_body_motion(mot).step(2)
             s.begin_force(every=7, capacity=4)
             s.step(7)
-            _same(s, o, name)
+            same_as_oracle(s, o, name)
             F, want = s.body_force(), o.body_force()
             assert np.array_equal(F["links"], want["links"]) and np.array_equal(F["step"], np.full(len(want["links"]), 9)), name
             for k, a in (("fx", "abs_x"), ("fy", "abs_y"), ("tz", "abs_z")):
@@ -250,7 +230,7 @@ def test_checkpoint_round_trip(tmp_path):
         with CavitySolver(nx, ny, 100.0, RT="TRT", dtype=np.float64, solid=m, **BB) as b:
             assert b.load_checkpoint(path) == 11 and np.array_equal(b.body_motion, np.asarray(mot)) and b.describe()["wall_motion"] == 1
             b.step(6)
-            _same_fields(a, b, "restart")
+            same_fields(a, b, "restart")
             Fa, Fb = a.body_force(), b.body_force()
             assert all(np.array_equal(Fa[k], Fb[k]) for k in ("links", "fx", "fy", "tz"))
 
@@ -267,7 +247,7 @@ def test_taylor_couette_strict_fp64_is_the_reference(tc_reference):
     o, case = tc_reference
     with CavitySolver(TC_N, TC_N, TC_RE, RT="TRT", dtype=np.float64, solid=case["mask"], **BB) as s:
         s.set_bodies(case["labels"], case["centres"]).set_body_motion(case["motion"]).step(TC_STEPS)
-        _same(s, o, "Taylor-Couette, strict fp64")
+        same_as_oracle(s, o, "Taylor-Couette, strict fp64")
         F, want = s.body_force(), o.body_force()
         assert np.all(np.abs(F["tz"] - want["tz"]) <= want["links"] * 2.0 ** -52 * want["abs_z"])
         (e_in, e_out), e_prof = tc_errors(s.get_fields()[0], F["tz"], case)

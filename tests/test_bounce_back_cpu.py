@@ -1,20 +1,16 @@
 """CPU tests of the half-way bounce-back walls (semantics='bounce_back'): the NumPy reference the GPU tests check against
 (tests/bounce_back_ref.py), the launch plans and refusals of lbm_plan, and the front end (run_cavity's BC, datagen's BC, ghia's walls)."""
-import os
-import sys
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tests"))
 
-from bounce_back_ref import BOUNCE, BounceBackOracle  # noqa: E402
-from front_end_standin import standin  # noqa: E402
-from oracle import lbm_numpy as on  # noqa: E402
-from latticeboltzmannsimulations_amd import datagen, ghia, launch_plan, mrt_gpu  # noqa: E402
-from latticeboltzmannsimulations_amd import _lib as L  # noqa: E402
-from latticeboltzmannsimulations_amd.solver import _SEM  # noqa: E402
+from bounce_back_ref import BOUNCE, BounceBackOracle
+from front_end_standin import standin
+from oracle import lbm_numpy as on
+from latticeboltzmannsimulations_amd import datagen, ghia, launch_plan, mrt_gpu
+from latticeboltzmannsimulations_amd import _lib as L
+from latticeboltzmannsimulations_amd.solver import _SEM
 
 
 # ---- the reference itself --------------------------------------------------------------------------------------------------

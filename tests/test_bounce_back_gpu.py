@@ -2,35 +2,16 @@
 the NumPy reference tests/bounce_back_ref.py on every kernel that takes the semantics (generic, tb, stream), batches, slabs and
 checkpoints bit for bit against the lone whole lattice, `fast` arithmetic within a bound, and the physics of the wall model (Ghia
 centrelines at the half-way positions, mass)."""
-import os
-import sys
-
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-
-from bounce_back_ref import BounceBackOracle  # noqa: E402
-from latticeboltzmannsimulations_amd import CavityBatch, CavitySolver, ghia  # noqa: E402
-from latticeboltzmannsimulations_amd.slab import LocalSlabs, partition_rows  # noqa: E402
+from bounce_back_ref import BounceBackOracle
+from checks import FAST_BOUND, perturbed, same_as_oracle
+from latticeboltzmannsimulations_amd import CavityBatch, CavitySolver, ghia
+from latticeboltzmannsimulations_amd.slab import LocalSlabs, partition_rows
 
 pytestmark = pytest.mark.gpu
 BB = dict(semantics="bounce_back")
-
-
-def _perturbed(nx, ny, dtype, seed):
-    """A non-trivial state for set_state: equilibrium-like populations with a seeded perturbation of a few per cent."""
-    rng = np.random.default_rng(seed)
-    t = np.array([4 / 9] + [1 / 9] * 4 + [1 / 36] * 4)
-    return (t[:, None, None] * (1.0 + 0.03 * rng.standard_normal((9, nx, ny)))).astype(dtype)
-
-
-def _same(s, o, what):
-    u, rho, fin = s.get_fields(want_fin=True)
-    assert np.array_equal(fin, o.fin), f"{what}: fin differs, max abs {np.abs(fin - o.fin).max()}"
-    assert np.array_equal(rho, o.rho), f"{what}: rho differs"
-    assert np.array_equal(u, o.u), f"{what}: u differs"
 
 
 # kernel -> lattices: the frame and the tiles' ragged edges (tb: nx a multiple of the vector width; stream: nx, ny >= 64)
@@ -49,12 +30,12 @@ def test_strict_bit_identical_to_reference(coll, dtype, kernel):
             assert s.describe()["semantics"] == "bounce_back"
             for n in (1, 7, 37):
                 s.step(n); o.step(n)
-                _same(s, o, f"{nx}x{ny} {kernel} after {o.nsteps}")
-            f = _perturbed(nx, ny, dtype, nx * ny)
+                same_as_oracle(s, o, f"{nx}x{ny} {kernel} after {o.nsteps}")
+            f = perturbed(nx, ny, dtype, nx * ny)
             s.set_state(f); o.set_state(f)
             for n in (1, 7, 37):
                 s.step(n); o.step(n)
-                _same(s, o, f"{nx}x{ny} {kernel} set_state + {o.nsteps}")
+                same_as_oracle(s, o, f"{nx}x{ny} {kernel} set_state + {o.nsteps}")
 
 
 @pytest.mark.parametrize("arith", ["strict", "fast"])
@@ -101,7 +82,7 @@ def test_slabs_equal_the_whole_lattice(kernel, coll, dtype):
             drv = LocalSlabs(slabs)
             for phase in range(2):
                 if phase:
-                    f = _perturbed(nx, ny, dtype, 7)
+                    f = perturbed(nx, ny, dtype, 7)
                     whole.set_state(f)
                     for sl in slabs:
                         sl.set_state(f)
@@ -134,19 +115,10 @@ def test_checkpoint_round_trip(tmp_path):
             nebb.load_checkpoint(path)
 
 
-# fast arithmetic against strict fp64 (the GPU's strict fp64 = the reference, bit for bit, test above): max |f_fast - f_ref| / max |f_ref|
-# over the populations after 2000 steps of a 128 x 96 lattice at Re 1000, every operator.  Measured (MI355X, FAST_MEASURED: the fp32
-# figures are mostly fp32's own distance from fp64); the bounds are the largest of each type with a factor of four of headroom, as
-# tests/test_arith_error_budget_gpu.py sets its bounds.  The tighter check, against a long-double reference from off-equilibrium states after
-# 1 .. 26 steps, is that file's test_fast_stays_within_the_budget_under_the_other_walls.
-FAST_MEASURED = {(np.float32, "SRT"): 2.940e-05, (np.float32, "TRT"): 2.956e-05, (np.float32, "MRT"): 1.616e-05,
-                 (np.float64, "SRT"): 1.419e-14, (np.float64, "TRT"): 1.476e-14, (np.float64, "MRT"): 2.920e-15}
-FAST_BOUND = {np.float32: 1.2e-4, np.float64: 6e-14}
-
-
 @pytest.mark.parametrize("dtype", [np.float32, np.float64])
 @pytest.mark.parametrize("coll", ["SRT", "TRT", "MRT"])
 def test_fast_arithmetic_within_bound(coll, dtype):
+    """`fast` against strict fp64 after 2000 steps of 128 x 96 at Re 1000: the same figure on both kernels, inside checks.FAST_BOUND."""
     with CavitySolver(128, 96, 1000.0, RT=coll, dtype=np.float64, kernel="generic", **BB) as ref:
         ref.step(2000)
         f_ref = ref.get_fields(want_fin=True)[2]

@@ -7,16 +7,14 @@ has them); the tests are skipped where there is no g++."""
 import os
 import shutil
 import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tests"))
 
-import body_cases  # noqa: E402
-from latticeboltzmannsimulations_amd import solid  # noqa: E402
+import body_cases
+from latticeboltzmannsimulations_amd import solid
 
 CSRC = os.path.join(ROOT, "latticeboltzmannsimulations_amd", "csrc")
 ACC, REC = 4, 6             # doubles of an accumulator and of a record, as the program passes them

@@ -8,11 +8,10 @@ host statements computed from it -- for the closure in fast arithmetic, the prom
 slots, bounce-back walls read in both host types, a solid mask, a batch and three slabs.
 
 Exact fields of a record are compared exactly; its sums (the device adds in another order than numpy) within the bound of a reordered
-double sum, 2 gamma_n sum |x_i| with gamma_n = n eps / (1 - n eps), eps = 2^-53, as tests/test_monitor_gpu.py and
-tests/test_residual_gpu.py state it.  mean_u: within (N - 1) 2^-53 sum |u| / N of the exact mean, N = 2 nx ny terms -- the first-order
-rounding bound of any summation order; the reference sum is math.fsum, which is exact.
+double sum, 2 gamma_n sum |x_i| with gamma_n = n eps / (1 - n eps), eps = 2^-53 (same_monitor_record and same_residual_record of
+tests/checks.py, the comparisons of the monitor's and the residual's own tests).  mean_u: within (N - 1) 2^-53 sum |u| / N of the
+exact mean, N = 2 nx ny terms -- the first-order rounding bound of any summation order; the reference sum is math.fsum, which is exact.
 """
-import ctypes
 import math
 
 import numpy as np
@@ -23,13 +22,12 @@ from latticeboltzmannsimulations_amd import topology as T
 from latticeboltzmannsimulations_amd.slab import LocalSlabs, partition_rows
 from oracle.states import state
 
+from cases import windows
+from checks import MON_EXACT, MON_SUMS, RES_EXACT, RES_SUMS, nan_equal, raw_stats, same_monitor_record, same_residual_record
+
 gpu = pytest.mark.gpu
 
 ULB = 0.08
-MON_EXACT = ("step", "nonfinite", "max_q", "min_q", "min_x", "min_y")
-MON_SUMS = ("sum_ux", "sum_uy", "sum_rho", "sum_q")
-RES_EXACT = ("step", "step_prev", "cells", "nonfinite", "max_du2", "max_x", "max_y", "max_drho2")
-RES_SUMS = ("sum_du2", "sum_u2", "sum_drho2")
 
 
 def _mask(nx, ny):
@@ -59,37 +57,7 @@ def _spec(nx, ny):
 
 
 def _windows(nx, ny):
-    return ((1, nx - 1, 1, ny - 1), (min(60, nx // 2), min(70, nx), 0, ny // 2 + 1), (nx - 1, nx, ny // 3, ny))
-
-
-def _gamma2(n):
-    return 2.0 * n * 2.0 ** -53 / (1.0 - n * 2.0 ** -53)
-
-
-def _monitor_equals(got, u, rho, what, rows=None, **spec):
-    want = monitor.host_monitor(u, rho, ULB, rows=rows, step=got["step"], **spec)
-    for k in MON_EXACT:
-        assert got[k] == want[k], f"{what}: monitor {k} {got[k]} != {want[k]}"
-    assert np.array_equal(got["probe"], want["probe"], equal_nan=True), f"{what}: monitor probes"
-    y0, n = (0, u.shape[2]) if rows is None else rows
-    ux, uy, r = (a[:, y0:y0 + n].astype(np.float64) for a in (u[0], u[1], rho))
-    q = (ux * ux + uy * uy) / (ULB * ULB)
-    for k, a in zip(MON_SUMS, (ux, uy, r, q)):
-        tol = _gamma2(a.size) * float(np.abs(a).sum())
-        assert abs(got[k] - want[k]) <= tol, f"{what}: monitor {k} off by {abs(got[k] - want[k])}, bound {tol}"
-
-
-def _residual_equals(got, prev, cur, what, rows=None):
-    """prev, cur: (step, u, rho)."""
-    want = residual.host_residual(prev[1], prev[2], cur[1], cur[2], rows=rows, step=cur[0], step_prev=prev[0])
-    for k in RES_EXACT:
-        assert got[k] == want[k], f"{what}: residual {k} {got[k]} != {want[k]}"
-    y0, n = (0, cur[1].shape[2]) if rows is None else rows
-    a = [x[..., y0:y0 + n].astype(np.float64) for x in (prev[1][0], prev[1][1], prev[2], cur[1][0], cur[1][1], cur[2])]
-    dux, duy, dr = a[3] - a[0], a[4] - a[1], a[5] - a[2]
-    for k, t in zip(RES_SUMS, (dux * dux + duy * duy, a[3] * a[3] + a[4] * a[4], dr * dr)):
-        tol = _gamma2(t.size) * float(np.abs(t).sum())
-        assert abs(got[k] - want[k]) <= tol, f"{what}: residual {k} off by {abs(got[k] - want[k])}, bound {tol}"
+    return windows(nx, ny)[:3]      # (the topology tests' windows without the empty one)
 
 
 def _mean_u_equals(got, u, what):
@@ -101,18 +69,9 @@ def _mean_u_equals(got, u, what):
     assert abs(got - want) <= bound, f"{what}: mean_u off by {abs(got - want)}, bound {bound}"
 
 
-def _raw_stats(s):
-    """lbm_stats_get as it comes: E[u], E[rho], (E[uu], E[vv], E[uv]), count."""
-    lead = s._lead
-    mu, mrho, sec = np.zeros(lead + (2, s.nx, s.ny)), np.zeros(lead + (s.nx, s.ny)), np.zeros(lead + (3, s.nx, s.ny))
-    n = ctypes.c_longlong(-1)
-    assert s.lib.lbm_stats_get(s._h, mu.ctypes.data, mrho.ctypes.data, sec.ctypes.data, ctypes.byref(n)) == 0
-    return mu, mrho, sec, n.value
-
-
 def _one_stats_sample(s):
     s.begin_statistics(0).sample_statistics()
-    out = _raw_stats(s)
+    out = raw_stats(s)
     s.end_statistics()
     return out
 
@@ -128,10 +87,6 @@ def _stats_equal(got, u, rho, what, rows=None):
     assert np.array_equal(cut(got[2]), np.stack([ux * ux, uy * uy, ux * uy], axis=-3)), f"{what}: second moments of the sample"
 
 
-def _eq(a, b):
-    return a == b or (a != a and b != b)
-
-
 def _topology_equals(s, b, u, dt, what):
     """topology() and stream_function() of lattice b (None: a lone lattice) against the host statements of u."""
     wins = _windows(s.nx, s.ny)
@@ -142,7 +97,7 @@ def _topology_equals(s, b, u, dt, what):
     for i, (g, w) in enumerate(zip(got["window"], want["window"])):
         for side in ("min", "max"):
             for k in ("psi", "x", "y", "omega"):
-                assert _eq(g[side][k], w[side][k]), f"{what}: topology window {i} {side} {k}: {g[side]} != {w[side]}"
+                assert nan_equal(g[side][k], w[side][k]), f"{what}: topology window {i} {side} {k}: {g[side]} != {w[side]}"
     psi, omega = s.stream_function(out_dtype=dt)
     hpsi, homega = T.host_stream_function(u)
     assert np.array_equal(psi if b is None else psi[b], hpsi), f"{what}: psi"
@@ -227,14 +182,14 @@ def test_every_reader_sees_what_get_fields_returns_from_every_source(name, dt):
                 for b in lat:
                     ub, rb = pick(u, b), pick(rho, b)
                     _lines_equal(lambda x, y: tuple(pick(a, b) for a in s.lines(x=x, y=y, out_dtype=dt)), ub, rb, nx, ny, what)
-                    _monitor_equals({k: pick(v, b) for k, v in rec.items()}, ub, rb, what, **spec)
+                    same_monitor_record({k: pick(v, b) for k, v in rec.items()}, ub, rb, ULB, what, **spec)
                     _topology_equals(s, b, ub, dt, what)
                 cur = (s.steps_done, u, rho)
                 if prev is not None:
                     series = s.residual_series()
                     assert series["count"] == (2 if source == "replayed" else 1)
                     for b in lat:
-                        _residual_equals(residual.record_at(series, series["count"] - 1, b), (prev[0], pick(prev[1], b), pick(prev[2], b)),
+                        same_residual_record(residual.record_at(series, series["count"] - 1, b), (prev[0], pick(prev[1], b), pick(prev[2], b)),
                                          (cur[0], pick(u, b), pick(rho, b)), what)
                 prev = cur
                 tau_and_mean(what)
@@ -282,19 +237,19 @@ def test_three_slabs_read_what_the_lone_lattice_exports():
                 what = f"slabs after {whole.steps_done}"
                 u, rho = fields_and_means(what)
                 _lines_equal(lambda x, y: drv.lines(x=x, y=y), u, rho, nx, ny, what)
-                _monitor_equals(drv.monitor(**spec), u, rho, what, **spec)
+                same_monitor_record(drv.monitor(**spec), u, rho, ULB, what, **spec)
                 for sl in slabs:
                     rows = (sl.y0, sl.ny_local)
-                    _monitor_equals(sl.monitor(**spec), u, rho, f"{what} slab {sl.y0}", rows=rows, **spec)
+                    same_monitor_record(sl.monitor(**spec), u, rho, ULB, f"{what} slab {sl.y0}", rows=rows, **spec)
                     _stats_equal(_one_stats_sample(sl), u, rho, f"{what} slab {sl.y0}", rows=rows)
                     sl.sample_residual()
                 cur = (whole.steps_done, u, rho)
                 if prev is not None:
                     each = [sl.residual_series() for sl in slabs]
                     last = each[0]["count"] - 1
-                    _residual_equals(residual.combine([residual.record_at(e, last) for e in each]), prev, cur, what)
+                    same_residual_record(residual.combine([residual.record_at(e, last) for e in each]), prev, cur, what)
                     for sl, e in zip(slabs, each):
-                        _residual_equals(residual.record_at(e, last), prev, cur, f"{what} slab {sl.y0}", rows=(sl.y0, sl.ny_local))
+                        same_residual_record(residual.record_at(e, last), prev, cur, f"{what} slab {sl.y0}", rows=(sl.y0, sl.ny_local))
                 prev = cur
         finally:
             for sl in slabs:

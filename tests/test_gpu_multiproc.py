@@ -2,15 +2,11 @@
 torch.distributed over gloo through host buffers (lbm_halo_export / lbm_halo_import): the slab
 kernels, ghost-row conventions and the HaloDriver under real multi-process conditions.  The RCCL
 transport itself needs >= 2 GPUs and is exercised by `bench.py --gpus N` on a multi-GPU node."""
-import os
 import socket
-import sys
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
 
 pytestmark = pytest.mark.gpu
 

@@ -8,41 +8,19 @@ Nothing here reads /root/reference.
 """
 import json
 import os
-import sys
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+from oracle.lbm_ref import CavityOracleC, set_threads, max_threads
+from latticeboltzmannsimulations_amd import CavityBatch, CavitySolver, ghia
+from latticeboltzmannsimulations_amd.slab import LocalSlabs, partition_rows
 
-from oracle.lbm_ref import CavityOracleC, set_threads, max_threads      # noqa: E402
-from latticeboltzmannsimulations_amd import CavityBatch, CavitySolver, ghia            # noqa: E402
-from latticeboltzmannsimulations_amd.slab import LocalSlabs, partition_rows  # noqa: E402
+from checks import same_as_oracle, smooth_state
 
 pytestmark = pytest.mark.gpu
-GOLDEN = os.path.join(ROOT, "tests", "golden")
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 KERNELS = ["generic", "auto"]
-
-
-def same(solver, oracle, what="state"):
-    u, rho, fin = solver.get_fields(want_fin=True)
-    assert np.array_equal(fin, oracle.fin), f"{what}: fin differs, max abs {np.abs(fin - oracle.fin).max()}"
-    assert np.array_equal(u, oracle.u), f"{what}: u differs"
-    assert np.array_equal(rho, oracle.rho), f"{what}: rho differs"
-
-
-def _smooth_state(nx, ny, dtype):
-    """A smooth non-trivial state for slabs in loopback: such a slab never sees the lid, so from the rest state all its rows stay
-    equal and a kernel that read a stale or not-yet-written row would go unnoticed."""
-    x = np.arange(nx, dtype=np.float64)[:, None]
-    y = np.arange(ny, dtype=np.float64)[None, :]
-    base = 1.0 + 1e-3 * np.sin(0.01 * x) * np.cos(0.013 * y) + 5e-4 * np.cos(0.0037 * (x + 2 * y))
-    t = np.array([4 / 9] + [1 / 9] * 4 + [1 / 36] * 4)
-    fin = np.empty((9, nx, ny), dtype=dtype)
-    for k in range(9):
-        fin[k] = (base * (t[k] * (1.0 + 1e-4 * k))).astype(dtype)
-    return fin
 
 
 @pytest.mark.parametrize("kernel", KERNELS)
@@ -56,7 +34,7 @@ def test_hip_step_is_bit_identical_to_oracle(kernel, sem, coll, dtype):
             assert np.array_equal(s.get_fields(want_fin=True)[2], o.fin), "initial equilibrium differs"
             for n in (1, 1, 1, 7, 90):
                 o.step(n); s.step(n)
-                same(s, o, f"{nx}x{ny} after {o.nsteps} steps")
+                same_as_oracle(s, o, f"{nx}x{ny} after {o.nsteps} steps")
             assert s.steps_done == 100
 
 
@@ -68,12 +46,12 @@ def test_device_layouts_give_identical_results(layout, kernel, dtype):
     o = CavityOracleC(nx, ny, 400.0, semantics="mrt_gpu", collision="MRT", dtype=dtype).step(60)
     with CavitySolver(nx, ny, 400.0, RT="MRT", dtype=dtype, kernel=kernel, layout=layout) as s:
         s.step(60)
-        same(s, o, f"layout={layout} kernel={kernel}")
+        same_as_oracle(s, o, f"layout={layout} kernel={kernel}")
     if kernel == "generic":
         o = CavityOracleC(nx, ny, 400.0, semantics="mrt_py", collision="SRT", dtype=dtype).step(60)
         with CavitySolver(nx, ny, 400.0, RT="SRT", semantics="mrt_py", dtype=dtype, layout=layout) as s:
             s.step(60)
-            same(s, o, f"mrt_py layout={layout}")
+            same_as_oracle(s, o, f"mrt_py layout={layout}")
 
 
 @pytest.mark.parametrize("kernel", ["generic", "vec", "tb"])
@@ -86,12 +64,12 @@ def test_smagorinsky_closure_is_bit_identical_to_oracle(kernel, coll, dtype):
         with CavitySolver(nx, ny, 5000.0, RT=coll, dtype=dtype, turb=1, kernel=kernel, layout=layout) as s:
             for n in (1, 2, 57):
                 o.step(n); s.step(n)
-                same(s, o, f"turb {coll} {nx}x{ny} after {o.nsteps}")
+                same_as_oracle(s, o, f"turb {coll} {nx}x{ny} after {o.nsteps}")
             # upload convention: history := equilibrium / density of the uploaded state
             _, _, fin = s.get_fields(want_fin=True)
             s.set_state(fin); o.set_state(fin)
             o.step(9); s.step(9)
-            same(s, o, "turb after set_state")
+            same_as_oracle(s, o, "turb after set_state")
 
 
 def test_smagorinsky_on_slabs():
@@ -119,11 +97,11 @@ def test_two_steps_per_launch_is_bit_identical_to_oracle(sem, coll, dtype):
         with CavitySolver(nx, ny, 400.0, RT=coll, semantics=sem, dtype=dtype, kernel="tb", layout=layout) as s:
             for n in (1, 2, 3, 4, 5, 64):
                 o.step(n); s.step(n)
-                same(s, o, f"tb {sem} {coll} {nx}x{ny} after {o.nsteps} steps")
+                same_as_oracle(s, o, f"tb {sem} {coll} {nx}x{ny} after {o.nsteps} steps")
             _, _, fin = s.get_fields(want_fin=True)
             s.set_state(fin); o.set_state(fin)
             o.step(11); s.step(11)
-            same(s, o, "tb after set_state")
+            same_as_oracle(s, o, "tb after set_state")
 
 
 @pytest.mark.parametrize("sem,coll", [("mrt_gpu", "MRT"), ("mrt_py", "SRT")])
@@ -135,7 +113,7 @@ def test_multi_step_on_thin_and_wide_lattices(sem, coll, dtype):
         o = CavityOracleC(nx, ny, 400.0, semantics=sem, collision=coll, dtype=dtype).step(steps)
         with CavitySolver(nx, ny, 400.0, RT=coll, semantics=sem, dtype=dtype) as s:      # kernel = auto
             s.step(steps)
-            same(s, o, f"{nx}x{ny} {sem} {coll}")
+            same_as_oracle(s, o, f"{nx}x{ny} {sem} {coll}")
 
 
 @pytest.mark.parametrize("dtype", [np.float64, np.float32])
@@ -146,25 +124,25 @@ def test_two_and_three_steps_per_launch_agree(dtype):
         for eager in (False, True):     # lazy one-step lag (u / rho recomputed on demand) and a single last step
             with CavitySolver(132, 99, 400.0, RT="MRT", dtype=dtype, kernel="tb", tuning=dict(tb_steps=steps, eager_lag=eager)) as s:
                 s.step(47)
-                same(s, o, f"tb_steps={steps} eager_lag={eager}")
+                same_as_oracle(s, o, f"tb_steps={steps} eager_lag={eager}")
     for sem, coll in (("mrt_py", "SRT"), ("mrt_gpu", "TRT")):
         o = CavityOracleC(260, 71, 400.0, semantics=sem, collision=coll, dtype=dtype).step(33)
         with CavitySolver(260, 71, 400.0, RT=coll, semantics=sem, dtype=dtype, kernel="tb", tuning=dict(tb_steps=4)) as s:
             s.step(33)
-            same(s, o, f"four steps {sem} {coll}")
+            same_as_oracle(s, o, f"four steps {sem} {coll}")
     # the other routes of the frame passes: one launch per pass on the second stream (row strips by vector cells), and the
     # fused passes through scratch lattices instead of LDS windows; segment lengths that do / do not fit the LDS budget
     o = CavityOracleC(260, 131, 400.0, semantics="mrt_gpu", collision="MRT", dtype=dtype).step(27)
     for tune in (dict(frame_fused=False), dict(frame_lds=False), dict(frame_seg=64), dict(frame_seg=8), dict(nt=True), dict(nt=False)):
         with CavitySolver(260, 131, 400.0, RT="MRT", dtype=dtype, kernel="tb", tuning=tune) as s:
             s.step(27)
-            same(s, o, f"{tune}")
+            same_as_oracle(s, o, f"{tune}")
     # with the Smagorinsky closure: two-phase kernel (history through LDS) and in-place kernel (history in registers)
     o = CavityOracleC(132, 99, 5000.0, semantics="mrt_gpu", collision="MRT", dtype=dtype, turb=1).step(29)
     for steps in (2, 3, 4, 5):
         with CavitySolver(132, 99, 5000.0, RT="MRT", dtype=dtype, turb=1, kernel="tb", tuning=dict(tb_steps=steps)) as s:
             s.step(29)
-            same(s, o, f"turb tb_steps={steps}")
+            same_as_oracle(s, o, f"turb tb_steps={steps}")
 
 
 @pytest.mark.parametrize("dtype,coll,turb", [(np.float32, "MRT", 0), (np.float64, "SRT", 1), (np.float64, "MRT", 0)])
@@ -179,9 +157,9 @@ def test_one_step_lag_after_every_kind_of_last_unit(dtype, coll, turb):
             o.step(n); s.step(n)
             if n % 3 == 0:
                 continue                                   # no read between these calls
-            same(s, o, f"after a call of {n} steps")
+            same_as_oracle(s, o, f"after a call of {n} steps")
             if n % 2:
-                same(s, o, "asked twice")
+                same_as_oracle(s, o, "asked twice")
             m = s.mean_u()
             assert abs(m - float(np.mean(o.u.astype(np.float64)))) < 1e-6 * 0.08
         tau = s.get_tau()
@@ -219,7 +197,7 @@ def test_streaming_kernel_is_bit_identical_to_oracle(sem, coll, turb, dtype, mod
             assert s.describe()["kernel"] == {"pairs": "k_stream_pairs", "walls": "k_stream_walls", "frame": "k_stream"}[mode], s.describe()
             for n in (1, 8, 19, 3, 7, 12):
                 o.step(n); s.step(n)
-                same(s, o, f"stream {nx}x{ny} tb_steps={tbs} {sem} {coll} turb={turb} after {o.nsteps} steps")
+                same_as_oracle(s, o, f"stream {nx}x{ny} tb_steps={tbs} {sem} {coll} turb={turb} after {o.nsteps} steps")
             assert s.next_unit(100) == (tbs or (10 if mode == "pairs" else 8)) or min(nx, ny) < 80
 
 
@@ -247,7 +225,7 @@ def test_seeded_random_configurations_against_oracle():
         with CavitySolver(nx, ny, Re, RT=coll, semantics=sem, dtype=dtype, turb=turb, kernel=kernel, layout=layout) as s:
             for n in chunks:
                 o.step(n); s.step(n)
-            same(s, o, f"case {case}: {nx}x{ny} {sem} {coll} {np.dtype(dtype).name} turb={turb} {kernel} {layout} {chunks}")
+            same_as_oracle(s, o, f"case {case}: {nx}x{ny} {sem} {coll} {np.dtype(dtype).name} turb={turb} {kernel} {layout} {chunks}")
 
 
 def test_seeded_random_configurations_of_the_streaming_kernel():
@@ -345,7 +323,7 @@ def test_config_c1_128_re100_1000_steps():
     with CavitySolver(128, 128, 100.0, RT="SRT", semantics="mrt_py", dtype=np.float64) as s:
         assert s.relax["omega"] == rec["omega"]
         s.step(1000)
-        same(s, o, "C1")
+        same_as_oracle(s, o, "C1")
         u, rho = s.get_fields()
     # north_star gate: centreline u / v within 1e-6 relative (fp64)
     cx, cy = ghia.centrelines(u, 0.08)
@@ -369,7 +347,7 @@ def test_config_c2_1024_re1000_100_steps(coll, sem):
         set_threads(1)
     with CavitySolver(1024, 1024, 1000.0, RT=coll, semantics=sem, dtype=np.float64) as s:
         s.step(100)
-        same(s, o, "C2")
+        same_as_oracle(s, o, "C2")
 
 
 @pytest.mark.parametrize("dtype", [np.float64, np.float32])
@@ -707,9 +685,9 @@ def test_minimum_sizes_and_empty_calls(sem, coll):
                 assert s.steps_done == 0 and np.array_equal(s.get_fields(want_fin=True)[2], o.fin)
                 for n in (1, 2, 22):
                     o.step(n); s.step(n)
-                    same(s, o, f"{nx}x{ny} {sem} {coll} after {o.nsteps}")
+                    same_as_oracle(s, o, f"{nx}x{ny} {sem} {coll} after {o.nsteps}")
                 s.step(0)
-                same(s, o, "after an empty step call")
+                same_as_oracle(s, o, "after an empty step call")
     nx, ny = 12, 8
     o = CavityOracleC(nx, ny, 100.0, semantics=sem, collision=coll, dtype=np.float64).step(15)
     slabs = [CavitySolver(nx, ny, 100.0, RT=coll, semantics=sem, dtype=np.float64, rows=(y0, 2)) for y0 in range(0, ny, 2)]
@@ -739,7 +717,7 @@ def test_config_c3_4096_fp32_against_oracle(steps):
     with CavitySolver(n, n, 1000.0, RT="MRT", dtype=np.float32) as s:
         s.step(steps)
         assert s.next_unit(100) >= 4                                         # (several steps per launch is what ran)
-        same(s, o, f"C3 strict, {steps} steps")
+        same_as_oracle(s, o, f"C3 strict, {steps} steps")
     with CavitySolver(n, n, 1000.0, RT="MRT", dtype=np.float32, arith="fast") as f:
         f.step(steps)
         u, rho, fin = f.get_fields(want_fin=True)
@@ -800,7 +778,7 @@ def test_config_c4_8192_fp64_re3200_slabs_and_oracle():
     with CavitySolver(n, n, 3200.0, RT="MRT", dtype=np.float64) as one:
         assert abs(one.relax["omega"] - 0.8973438621679827) < 1e-15
         one.step(steps)
-        same(one, o, "C4 undivided")
+        same_as_oracle(one, o, "C4 undivided")
     u = np.zeros_like(o.u); rho = np.zeros_like(o.rho); fin = np.zeros_like(o.fin)
     with CavitySolver(n, n, 3200.0, RT="MRT", dtype=np.float64, kernel="vec") as v:
         v.step(steps)
@@ -868,7 +846,7 @@ def test_config_c5_16384_fp32_re5000_slabs():
         s.set_relaxation(0, **o.relax)                                      # omega of Re = 5000 at the GLOBAL height (MRT_GPU.py:63)
         s.set_state(sub)
         s.step(3)
-        same(s, o, "C5 strip, strict")
+        same_as_oracle(s, o, "C5 strip, strict")
 
 
 @pytest.mark.parametrize("kernel", ["generic", "vec", "tb", "stream"])
@@ -1012,12 +990,12 @@ def test_push_scheme_equals_pull_kernels_and_oracle(sem, coll, dtype):
             assert np.array_equal(p.get_fields(want_fin=True)[2], o.fin)
             for n in (1, 2, 3, 40):
                 o.step(n); p.step(n); q.step(n)
-                same(p, o, f"push {sem} {coll} {nx}x{ny} after {o.nsteps}")
+                same_as_oracle(p, o, f"push {sem} {coll} {nx}x{ny} after {o.nsteps}")
                 assert all(np.array_equal(a, b) for a, b in zip(p.get_fields(want_fin=True), q.get_fields(want_fin=True)))
             _, _, fin = p.get_fields(want_fin=True)
             p.set_state(fin); o.set_state(fin)
             o.step(7); p.step(7)
-            same(p, o, "push after set_state")
+            same_as_oracle(p, o, "push after set_state")
     with pytest.raises(RuntimeError, match="PUSH"):
         CavitySolver(64, 64, 100.0, kernel="push", turb=1)
     with pytest.raises(RuntimeError, match="PUSH"):
@@ -1117,7 +1095,7 @@ def test_rccl_exchange_path_in_loopback(dtype, coll, turb, arith, kernel, layout
                      tuning=dict(deep_halo=deep))
     b = CavitySolver(nx, NY, 1000.0, RT=coll, dtype=dtype, rows=rows, turb=turb, kernel="generic", layout=layout, arith=arith)
     a.comm_loopback()
-    fin0 = _smooth_state(nx, NY, dtype)     # (from the rest state a slab in loopback would stay uniform: a stale row would not show)
+    fin0 = smooth_state(nx, NY, dtype)     # (from the rest state a slab in loopback would stay uniform: a stale row would not show)
     a.set_state(fin0); b.set_state(fin0)
     up = np.empty(b.halo_elems(), dtype=dtype); down = np.empty(b.halo_elems(), dtype=dtype)
     for steps in (23, 8, 1, 10):   # several calls: each starts from the one-row halo the previous one left
@@ -1143,7 +1121,7 @@ def test_rccl_loopback_with_mrt_py_windows(kernel, dtype):
     a = CavitySolver(nx, NY, 1000.0, RT="SRT", semantics="mrt_py", dtype=dtype, rows=rows, kernel=kernel)
     b = CavitySolver(nx, NY, 1000.0, RT="SRT", semantics="mrt_py", dtype=dtype, rows=rows, kernel="generic")
     a.comm_loopback()
-    fin0 = _smooth_state(nx, NY, dtype)
+    fin0 = smooth_state(nx, NY, dtype)
     a.set_state(fin0); b.set_state(fin0)
     up = np.empty(b.halo_elems(), dtype=dtype); down = np.empty(b.halo_elems(), dtype=dtype)
     units = set()
@@ -1170,7 +1148,7 @@ def test_streaming_slab_units_at_benchmark_sizes_in_loopback(nx, rows, dtype):
     a = CavitySolver(nx, 3 * rows, 3200.0, RT="MRT", dtype=dtype, rows=(rows, rows), arith="fast")
     b = CavitySolver(nx, 3 * rows, 3200.0, RT="MRT", dtype=dtype, rows=(rows, rows), arith="fast", kernel="vec")
     a.comm_loopback(); b.comm_loopback()
-    fin0 = _smooth_state(nx, 3 * rows, dtype)
+    fin0 = smooth_state(nx, 3 * rows, dtype)
     a.set_state(fin0); b.set_state(fin0)
     del fin0
     assert a.describe()["kernel"] == "k_stream_walls" and a.describe()["slab"] == 1
@@ -1192,7 +1170,7 @@ def test_deep_exchange_after_a_single_step_waits_for_the_interior_kernel(kernel)
     first is slowed by code loading): same slab four times in one process, short calls that start with single steps; expected:
     every run equals one step and one exchange per launch (kernel = vec)."""
     nx, rows = 4096, 1024
-    fin0 = _smooth_state(nx, 3 * rows, np.float32)
+    fin0 = smooth_state(nx, 3 * rows, np.float32)
     def run(k):
         with CavitySolver(nx, 3 * rows, 1000.0, RT="MRT", dtype=np.float32, rows=(rows, rows), arith="fast", kernel=k) as s:
             s.comm_loopback()

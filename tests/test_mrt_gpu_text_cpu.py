@@ -15,12 +15,10 @@ import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-from oracle import reftext  # noqa: E402
-from oracle.lbm_numpy import CavityOracle  # noqa: E402
-from oracle.lbm_ref import CavityOracleC  # noqa: E402
-from mrt_gpu_text_ref import GOLDEN, digest, first_difference, golden, oracle_checkpoints  # noqa: E402
+from oracle import reftext
+from oracle.lbm_numpy import CavityOracle
+from oracle.lbm_ref import CavityOracleC
+from mrt_gpu_text_ref import GOLDEN, digest, first_difference, golden, oracle_checkpoints
 
 reftext.build_all()          # cheap when up to date; nothing without the reference
 

@@ -4,12 +4,12 @@ refusals of the four entry points.  No device is needed."""
 import numpy as np
 import pytest
 
+from checks import RES_EXACT as EXACT
+from checks import RES_SUMS as SUMS
+from checks import residual_sum_bounds
 from front_end_standin import standin
 from latticeboltzmannsimulations_amd import _lib, residual
 from latticeboltzmannsimulations_amd.mrt_gpu import run_cavity
-
-SUMS = ("sum_du2", "sum_u2", "sum_drho2")
-EXACT = ("step", "step_prev", "cells", "nonfinite", "max_du2", "max_x", "max_y", "max_drho2")
 
 
 def _fields(X, Y, seed):
@@ -17,21 +17,6 @@ def _fields(X, Y, seed):
     u = (0.05 * rng.standard_normal((2, X, Y))).astype(np.float32)
     rho = (1.0 + 0.01 * rng.standard_normal((X, Y))).astype(np.float32)
     return u, rho
-
-
-def sum_bounds(u_prev, rho_prev, u, rho, rows=None):
-    """2 gamma_n sum |x_i| for the three sums (the derivation of tests/test_monitor_gpu.py::_sum_bounds): a sum of n doubles in any
-    order is within gamma_n = n eps / (1 - n eps), eps = 2^-53, times sum |x_i| of the exact sum, so two orders differ by at most
-    twice that.  All terms are >= 0 here, so sum |x_i| is the sum itself."""
-    y0, n = (0, u.shape[2]) if rows is None else rows
-    a = [x[..., y0:y0 + n].astype(np.float64) for x in (u_prev[0], u_prev[1], rho_prev, u[0], u[1], rho)]
-    ok = np.all([np.isfinite(x) for x in a], axis=0)
-    with np.errstate(all="ignore"):
-        dux, duy, dr = a[3] - a[0], a[4] - a[1], a[5] - a[2]
-        terms = (dux * dux + duy * duy, a[3] * a[3] + a[4] * a[4], dr * dr)
-    cells = int(ok.sum())
-    g = cells * 2.0 ** -53 / (1.0 - cells * 2.0 ** -53)
-    return {k: 2.0 * g * float(np.abs(t[ok]).sum()) for k, t in zip(SUMS, terms)}
 
 
 def test_identical_samples_give_zero_sums_and_the_first_cell():
@@ -120,7 +105,7 @@ def test_combine_over_three_row_partitions_equals_the_whole_field():
     for k in EXACT:
         assert got[k] == whole[k], k
     assert (got["max_x"], got["max_y"]) == (9, 25) and got["nonfinite"] == 1
-    tol = sum_bounds(u, rho, u2, rho2)
+    tol = residual_sum_bounds((u, rho), (u2, rho2))
     for k in SUMS:
         assert abs(got[k] - whole[k]) <= tol[k], (k, got[k] - whole[k], tol[k])
     none = residual.combine([dict(whole, cells=0, nonfinite=5, max_du2=-np.inf, max_x=-1, max_y=-1, max_drho2=-np.inf)] * 2)

@@ -2,7 +2,6 @@
 get_fields() results of the same context exactly -- the three sums within the bound of a reordered double sum -- on every kernel
 route, semantics and arithmetic; ties and cells that are not finite; automatic samples equal manual ones bit for bit and leave the
 stepping alone, also beside the time statistics and a monitor series; batches and slabs; the life cycle; the two front ends."""
-import itertools
 import warnings
 
 import numpy as np
@@ -11,95 +10,28 @@ import pytest
 from latticeboltzmannsimulations_amd import CavityBatch, CavitySolver, datagen, residual
 from latticeboltzmannsimulations_amd.mrt_gpu import run_cavity
 from latticeboltzmannsimulations_amd.slab import LocalSlabs, partition_rows
-from latticeboltzmannsimulations_amd.solver import launch_plan
+
+from cases import route_cases, route_id
+from checks import RES_EXACT as EXACT
+from checks import RES_SUMS as SUMS
+from checks import HostStats, perturbed, residual_sum_bounds, residual_terms, rest, same_bits, same_residual_record
 
 pytestmark = pytest.mark.gpu
 
 ULB = 0.08
-EXACT = ("step", "step_prev", "cells", "nonfinite", "max_du2", "max_x", "max_y", "max_drho2")
-SUMS = ("sum_du2", "sum_u2", "sum_drho2")
 # the monitor tests' smallest shapes: the odd width leaves a padded last lane group; the tile route; the smallest lattice the
 # streaming tests force kernel="stream" on
 SIZE = {"generic": (97, 80), "tb": (192, 160), "stream": (132, 200), "push": (192, 160)}
 
 
-def _perturbed(nx, ny, dtype, seed):
-    """A non-trivial state for set_state: equilibrium-like populations with a seeded perturbation of a few per cent."""
-    rng = np.random.default_rng(seed)
-    t = np.array([4 / 9] + [1 / 9] * 4 + [1 / 36] * 4)
-    return (t[:, None, None] * (1.0 + 0.03 * rng.standard_normal((9, nx, ny)))).astype(dtype)
-
-
-def _rest(nx, ny, dtype):
-    t = np.array([4 / 9] + [1 / 9] * 4 + [1 / 36] * 4)
-    return np.ascontiguousarray(np.broadcast_to(t[:, None, None], (9, nx, ny))).astype(dtype)
-
-
-def _terms(prev, cur, rows=None):
-    """(ok, d2, u2, dr2) of two (u, rho) samples in float64, restricted to the rows of a slab."""
-    y0, n = (0, cur[0].shape[2]) if rows is None else rows
-    a = [x[..., y0:y0 + n].astype(np.float64) for x in (prev[0][0], prev[0][1], prev[1], cur[0][0], cur[0][1], cur[1])]
-    ok = np.all([np.isfinite(x) for x in a], axis=0)
-    with np.errstate(all="ignore"):
-        dux, duy, dr = a[3] - a[0], a[4] - a[1], a[5] - a[2]
-        return ok, dux * dux + duy * duy, a[3] * a[3] + a[4] * a[4], dr * dr
-
-
-def _sum_bounds(prev, cur, rows=None):
-    """2 gamma_n sum |x_i| for the three sums (tests/test_monitor_gpu.py::_sum_bounds): a sum of n doubles in any order is within
-    gamma_n = n eps / (1 - n eps), eps = 2^-53, times sum |x_i| of the exact sum, so two orders differ by at most twice that."""
-    ok, d2, u2, dr2 = _terms(prev, cur, rows)
-    cells = int(ok.sum())
-    g = cells * 2.0 ** -53 / (1.0 - cells * 2.0 ** -53)
-    return {k: 2.0 * g * float(np.abs(t[ok]).sum()) for k, t in zip(SUMS, (d2, u2, dr2))}
-
-
-def _same_record(got, prev, cur, what, rows=None):
-    """got: a record of the device; prev, cur: (step, u, rho) of the two samples."""
-    want = residual.host_residual(prev[1], prev[2], cur[1], cur[2], rows=rows, step=cur[0], step_prev=prev[0])
-    for k in EXACT:
-        assert got[k] == want[k], f"{what}: {k} {got[k]} != {want[k]}"
-    tol = _sum_bounds(prev[1:], cur[1:], rows)
-    for k in SUMS:
-        print(f"{what}: {k} device {got[k]!r} host {want[k]!r} bound {tol[k]!r}")
-        assert abs(got[k] - want[k]) <= tol[k], f"{what}: {k} off by {abs(got[k] - want[k])}, bound {tol[k]}"
-    return want
-
-
-def _same_bits(a, b, what):
-    for k in residual.FIELDS:
-        assert np.array_equal(np.asarray(a[k]), np.asarray(b[k]), equal_nan=True), f"{what}: {k} differs: {a[k]} {b[k]}"
-
-
-def _valid(cfg):
-    kernel, dtype, coll, turb, sem, arith = cfg
-    try:
-        launch_plan(*SIZE[kernel], 1000.0, RT=coll, dtype=dtype, turb=turb, semantics=sem, kernel=kernel, arith=arith)
-        return True
-    except (RuntimeError, ValueError):
-        return False
-
-
-ROUTES = ["generic", "tb", "stream", "push"]
-ALL = [c for c in itertools.product(ROUTES, [np.float32, np.float64], ["SRT", "TRT", "MRT"], [0, 1], ["mrt_gpu", "mrt_py", "bounce_back"],
-                                    ["strict", "fast"]) if _valid(c)]
 # every route with each of its semantics and arithmetics once, then a sample of the rest drawn with seed 2029, then two fp64 lattices
-# on the multi-step routes (both out_dtypes) and the closure on the streaming route
-_pick = {}
-for c in ALL:
-    _pick.setdefault((c[0], c[4], c[5]), c)
-_others = [c for c in ALL if c not in _pick.values()]
-_rng = np.random.default_rng(2029)
-CASES = list(_pick.values()) + [_others[i] for i in sorted(_rng.choice(len(_others), size=min(6, len(_others)), replace=False))]
-CASES += [c for c in [("tb", np.float64, "MRT", 1, "mrt_gpu", "strict"), ("stream", np.float64, "SRT", 1, "mrt_gpu", "fast"),
-                      ("stream", np.float32, "MRT", 1, "mrt_gpu", "strict")] if c not in CASES]
+# on the multi-step routes (both out_dtypes) and the closure on the streaming route (cases.route_cases)
+CASES = route_cases(["generic", "tb", "stream", "push"], ["strict", "fast"], SIZE, seed=2029, sample=6,
+                    extras=[("tb", np.float64, "MRT", 1, "mrt_gpu", "strict"), ("stream", np.float64, "SRT", 1, "mrt_gpu", "fast"),
+                            ("stream", np.float32, "MRT", 1, "mrt_gpu", "strict")])
 
 
-def _ids(c):
-    return f"{c[0]}-{np.dtype(c[1]).name}-{c[2]}-t{c[3]}-{c[4]}-{c[5]}"
-
-
-@pytest.mark.parametrize("cfg", CASES, ids=_ids)
+@pytest.mark.parametrize("cfg", CASES, ids=route_id)
 def test_device_record_equals_the_host_statement(cfg):
     """From an upload: samples after 1 step (the sample is the raw lattice), 7 and 37 steps -- two records, the second over an uneven
     number of steps and several launch units."""
@@ -108,7 +40,7 @@ def test_device_record_equals_the_host_statement(cfg):
     outs = (np.float32, np.float64) if dtype == np.float64 else (np.float32,)
     with CavitySolver(nx, ny, 1000.0, RT=coll, dtype=dtype, turb=turb, semantics=sem, kernel=kernel, arith=arith) as s:
         for dt in outs:
-            s.set_state(_perturbed(nx, ny, dtype, CASES.index(cfg)))
+            s.set_state(perturbed(nx, ny, dtype, CASES.index(cfg)))
             s.begin_residual(out_dtype=dt)
             samples = []
             for n in (1, 7, 37):
@@ -119,7 +51,7 @@ def test_device_record_equals_the_host_statement(cfg):
             assert got["count"] == 2 and got["dropped"] == 0
             for i in range(2):
                 rec = residual.record_at(got, i)
-                want = _same_record(rec, samples[i], samples[i + 1], f"{_ids(cfg)} out={np.dtype(dt).name} record {i}")
+                want = same_residual_record(rec, samples[i], samples[i + 1], f"{route_id(cfg)} out={np.dtype(dt).name} record {i}")
                 assert want["cells"] == nx * ny and want["max_du2"] > 0.0
             assert list(got["step"]) == [7, 37] and list(got["step_prev"]) == [1, 7]
 
@@ -136,7 +68,7 @@ def test_ties_go_to_the_smaller_x_then_y_and_cells_that_are_not_finite_are_left_
     nx, ny = SIZE[kernel]
     ya, yb = ny // 4, 3 * ny // 4
     strips = ((nx // 3, nx // 3 + 41, ya), (nx // 3 - 9, nx // 3 + 32, yb))
-    fin = _rest(nx, ny, dtype)
+    fin = rest(nx, ny, dtype)
     for a, b, y in strips:
         fin[1, a:b, y] += dtype(0.25)
         fin[3, a, y] = np.nan
@@ -152,7 +84,7 @@ def test_ties_go_to_the_smaller_x_then_y_and_cells_that_are_not_finite_are_left_
         s.sample_residual()
         rec = residual.record_at(s.residual_series(), 0)
         # the premises
-        ok, d2, _, _ = _terms(first[1:], second[1:])
+        ok, d2, _, _ = residual_terms(first[1:], second[1:])
         ties = np.argwhere(ok & (d2 == d2[ok].max()))
         assert {yb - 1, yb, yb + 1} & set(ties[:, 1]) and {ya - 1, ya, ya + 1} & set(ties[:, 1]), "ties on both strips"
         assert len(ties) >= 40 and (np.diff(ties[:, 0]) == 1).any(), "ties between neighbouring cells"
@@ -160,22 +92,10 @@ def test_ties_go_to_the_smaller_x_then_y_and_cells_that_are_not_finite_are_left_
         y_major = min(map(tuple, ties), key=lambda t: (t[1], t[0]))
         assert x_major != y_major and x_major[1] > y_major[1]
         # the record
-        want = _same_record(rec, first, second, f"ties {kernel} {np.dtype(dtype).name}")
+        want = same_residual_record(rec, first, second, f"ties {kernel} {np.dtype(dtype).name}")
         assert (rec["max_x"], rec["max_y"]) == x_major and rec["max_du2"] > 1e-4
         assert rec["nonfinite"] == want["nonfinite"] >= 4 * 9 and rec["cells"] + rec["nonfinite"] == nx * ny
         assert np.isfinite([rec[k] for k in SUMS]).all()
-
-
-class HostStats:
-    """The host loop of the time statistics: acc += u.astype(f64); ...; acc / count."""
-
-    def __init__(self):
-        self.S, self.n = None, 0
-
-    def add(self, u, rho):
-        terms = [u.astype(np.float64), rho.astype(np.float64)]
-        self.S = terms if self.S is None else [a + b for a, b in zip(self.S, terms)]
-        self.n += 1
 
 
 SERIES = [(every, kernel, False) for kernel in ("tb", "stream") for every in (1, 3, 8, 13)] + \
@@ -192,7 +112,7 @@ def test_automatic_samples_equal_manual_samples_and_leave_the_stepping_alone(eve
     (nx, ny), dtype = SIZE[kernel], np.float32
     kw = dict(dtype=dtype, kernel=kernel, turb=0 if kernel == "push" else 1)
     with CavitySolver(nx, ny, 1000.0, **kw) as s, CavitySolver(nx, ny, 1000.0, **kw) as ref:
-        f = _perturbed(nx, ny, dtype, every)
+        f = perturbed(nx, ny, dtype, every)
         s.set_state(f); ref.set_state(f)
         s.begin_residual(every=every, capacity=64)
         ref.begin_residual(every=0, capacity=64)
@@ -215,7 +135,7 @@ def test_automatic_samples_equal_manual_samples_and_leave_the_stepping_alone(eve
             ref.step(s.steps_done - ref.steps_done)
             got, want = s.residual_series(), ref.residual_series()
             assert got["count"] == want["count"] == max(s.steps_done // every - 1, 0) and got["dropped"] == 0
-            _same_bits(got, want, f"every={every} {kernel} after {s.steps_done}")
+            same_bits(got, want, residual.FIELDS, f"every={every} {kernel} after {s.steps_done}")
             a, b = s.get_fields(want_fin=True), ref.get_fields(want_fin=True)
             assert all(np.array_equal(x, y) for x, y in zip(a, b)), f"stepping perturbed at {s.steps_done}"
         assert list(got["step"]) == list(range(2 * every, 40, every)) and list(got["step_prev"]) == list(range(every, 40 - every, every))
@@ -242,7 +162,7 @@ def test_capacity_and_dropped_samples():
         ref.step(22 - ref.steps_done)
         got, want = s.residual_series(), ref.residual_series()
         assert got["count"] == 2 and got["dropped"] == 3 and list(got["step"]) == [10, 13] and list(got["step_prev"]) == [7, 10]
-        _same_bits(got, want, "kept records")
+        same_bits(got, want, residual.FIELDS, "kept records")
         a, b = s.get_fields(want_fin=True), ref.get_fields(want_fin=True)
         assert all(np.array_equal(x, y) for x, y in zip(a, b))
         s.begin_residual(every=0, capacity=1)              # restart: the next sample fills the snapshot again
@@ -259,7 +179,7 @@ def test_monitor_and_residual_series_are_independent():
     nx, ny = SIZE["tb"]
     kw = dict(dtype=np.float32, kernel="tb")
     with CavitySolver(nx, ny, 1000.0, **kw) as s, CavitySolver(nx, ny, 1000.0, **kw) as ref:
-        f = _perturbed(nx, ny, np.float32, 17)
+        f = perturbed(nx, ny, np.float32, 17)
         s.set_state(f); ref.set_state(f)
         s.begin_monitor(every=3, capacity=2, **MON)
         s.begin_residual(every=3, capacity=64)
@@ -276,18 +196,18 @@ def test_monitor_and_residual_series_are_independent():
         for i, w in enumerate(mon):
             assert all(np.array_equal(ms[k][i], w[k], equal_nan=True) for k in ("step", "sum_ux", "sum_q", "min_q", "min_x", "min_y", "probe"))
         assert got["count"] == want["count"] == 5 and got["dropped"] == 0 and list(got["step"]) == list(range(6, 21, 3))
-        _same_bits(got, want, "beside a full monitor series")
+        same_bits(got, want, residual.FIELDS, "beside a full monitor series")
         a, b = s.get_fields(want_fin=True), ref.get_fields(want_fin=True)
         assert all(np.array_equal(x, y) for x, y in zip(a, b))
         s.end_monitor()
         with pytest.raises(RuntimeError, match=r"\(-4\)"):
             s.monitor_series()
-        _same_bits(s.residual_series(), want, "after the monitor series ended")
+        same_bits(s.residual_series(), want, residual.FIELDS, "after the monitor series ended")
         s.step(3)                                          # (the sample of step count 21 is taken where the unit from 20 starts)
         ref.step(1).sample_residual().step(2)
         got, want = s.residual_series(), ref.residual_series()
         assert got["count"] == 6 and got["dropped"] == 0 and (got["step"][5], got["step_prev"][5]) == (21, 18)
-        _same_bits(got, want, "on schedule after the monitor series ended")
+        same_bits(got, want, residual.FIELDS, "on schedule after the monitor series ended")
 
 
 def test_batch_of_mixed_reynolds_numbers_gives_each_lattice_its_own_record():
@@ -307,7 +227,7 @@ def test_batch_of_mixed_reynolds_numbers_gives_each_lattice_its_own_record():
                 s.step(k)
             s.sample_residual()
             lone = s.residual_series()
-        _same_bits({k: series[k][:, b] for k in residual.FIELDS}, lone, f"Re {Re}")
+        same_bits({k: series[k][:, b] for k in residual.FIELDS}, lone, residual.FIELDS, f"Re {Re}")
     assert len({tuple(series["sum_du2"][:, b]) for b in range(3)}) == 3
 
 
@@ -318,7 +238,7 @@ def test_three_slabs_combine_to_the_lone_lattice():
     with CavitySolver(nx, ny, 1000.0, dtype=np.float32, turb=1) as whole:
         slabs = [CavitySolver(nx, ny, 1000.0, dtype=np.float32, turb=1, rows=r, min_rows=mr) for r in parts]
         try:
-            f = _perturbed(nx, ny, np.float32, 11)
+            f = perturbed(nx, ny, np.float32, 11)
             whole.set_state(f)
             for sl in slabs:
                 sl.set_state(f)
@@ -339,12 +259,12 @@ def test_three_slabs_combine_to_the_lone_lattice():
                 w = residual.record_at(want, i)
                 for key in EXACT:
                     assert got[key] == w[key], (key, i)
-                tol = _sum_bounds(samples[i][1:], samples[i + 1][1:])
+                tol = residual_sum_bounds(samples[i][1:], samples[i + 1][1:])
                 for key in SUMS:
                     assert abs(got[key] - w[key]) <= tol[key], (key, i)
-                _same_record(got, samples[i], samples[i + 1], f"slabs combined, record {i}")
+                same_residual_record(got, samples[i], samples[i + 1], f"slabs combined, record {i}")
                 for sl, e in zip(slabs, each):             # every slab's own record is the host statement of its rows
-                    _same_record(residual.record_at(e, i), samples[i], samples[i + 1], f"slab {sl.y0}", rows=(sl.y0, sl.ny_local))
+                    same_residual_record(residual.record_at(e, i), samples[i], samples[i + 1], f"slab {sl.y0}", rows=(sl.y0, sl.ny_local))
         finally:
             for sl in slabs:
                 sl.close()
@@ -383,7 +303,7 @@ def test_life_cycle_refusals_and_repeatability():
         s.step_unit(3)                                    # every = 0 does not refuse
         s.sample_residual().step(2).sample_residual()
         assert s.residual_series()["count"] == 1
-        s.set_state(_perturbed(nx, ny, np.float32, 3))    # ends the series
+        s.set_state(perturbed(nx, ny, np.float32, 3))    # ends the series
         with pytest.raises(RuntimeError, match=r"\(-4\)"):
             s.residual_series()
         s.begin_residual(every=2, capacity=8).step(6)

@@ -2,21 +2,17 @@
 compare the device with), the host restatement latticeboltzmannsimulations_amd/solid.py against the reference's own link sets and
 force, the dry-run plan of the new semantics with every refused combination, and the front ends -- argument checks, the command
 lines' masks, the force lines of run_cavity, solid.npy of the sweep -- through the stand-ins of tests/front_end_standin.py."""
-import os
-import sys
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tests"))
 
-import front_end_standin as FS  # noqa: E402
-from bounce_back_ref import BounceBackOracle  # noqa: E402
-from solid_ref import SolidOracle  # noqa: E402
-from latticeboltzmannsimulations_amd import _lib as L  # noqa: E402
-from latticeboltzmannsimulations_amd import datagen, launch_plan, mrt_gpu, solid  # noqa: E402
-from latticeboltzmannsimulations_amd.solver import CavitySolver  # noqa: E402
+import front_end_standin as FS
+from bounce_back_ref import BounceBackOracle
+from solid_ref import SolidOracle
+from latticeboltzmannsimulations_amd import _lib as L
+from latticeboltzmannsimulations_amd import datagen, launch_plan, mrt_gpu, solid
+from latticeboltzmannsimulations_amd.solver import CavitySolver
 
 NX, NY = 48, 40
 

@@ -1,67 +1,22 @@
 """GPU tests of solid obstacles in the bounce-back cavity (CavitySolver(..., semantics='bounce_back', solid=mask),
 LBM_SEM_BOUNCE_BACK_SOLID): strict arithmetic bit for bit against the NumPy reference tests/solid_ref.py on the vector kernel
 (k_step_solid) and the generic route, the all-fluid mask against plain bounce-back, `fast` arithmetic within the bound of
-tests/test_bounce_back_gpu.py, batches, the samplers on a masked lattice, the force on the obstacles, a mirror-image pair,
+plain bounce-back (checks.FAST_BOUND), batches, the samplers on a masked lattice, the force on the obstacles, a mirror-image pair,
 checkpoints and the error paths."""
 import math
-import os
-import sys
+import warnings
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-
-from solid_ref import SolidOracle  # noqa: E402
-from test_bounce_back_gpu import FAST_BOUND  # noqa: E402  (the bound of fast bounce-back: the mask selects populations, adds no arithmetic)
-from latticeboltzmannsimulations_amd import CavityBatch, CavitySolver, solid  # noqa: E402
+from cases import _masks
+from checks import FAST_BOUND      # (the bound of fast bounce-back: the mask selects populations, adds no arithmetic)
+from checks import HostStats, check_topology, same_as_oracle, same_fields, same_monitor_record, same_residual_record, same_stats
+from solid_ref import SolidOracle
+from latticeboltzmannsimulations_amd import CavityBatch, CavitySolver, solid
 
 pytestmark = pytest.mark.gpu
 BB = dict(semantics="bounce_back")
-
-
-def _masks(nx, ny, seed=11):
-    """name -> mask: the cases the kernel can get wrong.  Block edges fall at x = 3 and x = 0 (mod 4) -- the last and the first cell of
-    a thread's four (two) -- and, on the wide lattices, straddle the seams between two workgroups' cells at x = 511 | 512 and 1023 | 1024."""
-    z = lambda: np.zeros((nx, ny), dtype=bool)  # noqa: E731
-    out = {"fluid": z()}
-    m = z(); m[nx // 2, ny // 2] = True
-    out["cell"] = m
-    m = z()
-    y0, y1 = max(1, ny // 4), min(ny - 1, ny // 4 + 6)
-    m[19:25, y0:y1] = True                       # columns 19 .. 24
-    for seam in (512, 1024):
-        if nx > seam + 4:
-            m[seam - 5:seam + 5, y0:y1] = True   # columns seam - 5 (= 3 mod 4) .. seam + 4 (= 0 mod 4)
-    out["block"] = m
-    m = z()
-    for i in range(min(nx, ny) - 3):             # a diagonal staircase: solid cells that touch at corners only
-        m[2 + i, 1 + i] = True
-    out["stairs"] = m
-    m = z()                                      # cells on each wall, in each corner and in the lid row
-    m[0, ny // 2] = m[nx - 1, ny // 3] = m[nx // 2, ny - 1] = True
-    m[0, 0] = m[nx - 1, 0] = m[0, ny - 1] = m[nx - 1, ny - 1] = True
-    m[nx // 3:nx // 3 + 5, 0] = True
-    m[7, 0:2] = True
-    out["walls"] = m
-    out["random"] = np.random.default_rng(seed).random((nx, ny)) < 0.2
-    return out
-
-
-def _same(s, o, what):
-    u, rho, fin = s.get_fields(want_fin=True)
-    assert np.isfinite(fin).all() and np.isfinite(u).all() and np.isfinite(rho).all(), f"{what}: not finite"
-    assert np.array_equal(fin, o.fin), f"{what}: fin differs in {np.count_nonzero(fin != o.fin)} values, max abs {np.abs(fin - o.fin).max()}"
-    assert np.array_equal(rho, o.rho), f"{what}: rho differs"
-    assert np.array_equal(u, o.u), f"{what}: u differs"
-    return u, rho, fin
-
-
-def _same_fields(a, b, what):
-    fa, fb = a.get_fields(want_fin=True), b.get_fields(want_fin=True)
-    for x, y, name in zip(fa, fb, ("u", "rho", "fin")):
-        assert np.array_equal(x, y), f"{what}: {name} differs"
 
 
 # 72 x 40: one partial workgroup; 70 x 66: the generic route (70 is no multiple of 4; in fp64 the vector route, 70 % 2 == 0);
@@ -95,8 +50,8 @@ def test_strict_bit_identical_to_reference(coll, dtype, shape):
                 for n in (1, 1, 5, 30):
                     s.step(n); g.step(n); o.step(n)
                     what = f"{nx}x{ny} {coll} {np.dtype(dtype).name} mask {name} phase {phase} after {o.nsteps}"
-                    _, _, fin = _same(s, o, what)
-                    _same_fields(g, s, what + " generic")
+                    _, _, fin = same_as_oracle(s, o, what)
+                    same_fields(g, s, what + " generic")
                     assert np.array_equal(fin[:, m], np.broadcast_to(o.t[:, None], (9, int(m.sum())))), what + ": solid cells"
 
 
@@ -107,7 +62,7 @@ def test_all_fluid_mask_equals_plain_bounce_back(dtype):
                 CavitySolver(nx, ny, 400.0, RT="MRT", dtype=dtype, solid=np.zeros((nx, ny), bool), **BB) as s:
             for n in (1, 6, 30):
                 plain.step(n); s.step(n)
-                _same_fields(s, plain, f"{nx}x{ny} after {s.steps_done}")
+                same_fields(s, plain, f"{nx}x{ny} after {s.steps_done}")
 
 
 @pytest.mark.parametrize("dtype", [np.float32, np.float64])
@@ -156,11 +111,6 @@ def test_batch_of_masks_equals_lattices_alone(dtype):
 def test_samplers_see_a_steady_finite_body():
     """monitor, residual, topology and statistics on a masked lattice against their host restatements applied to get_fields of the same
     context (u = 0 in the body), with the assertions of their own GPU tests."""
-    import warnings
-    from test_monitor_gpu import _same_record as same_monitor
-    from test_residual_gpu import _same_record as same_residual
-    from test_statistics_gpu import HostStats, _same_stats
-    from test_topology_gpu import _check as check_topology
     nx, ny = 72, 40
     m = _masks(nx, ny)["block"] | _masks(nx, ny)["walls"]
     for dtype in (np.float32, np.float64):
@@ -170,7 +120,7 @@ def test_samplers_see_a_steady_finite_body():
             assert not u[:, m].any() and np.all(rho[m] == rho[m][0]) and abs(float(rho[m][0]) - 1.0) < 1e-6
             rec = s.monitor(probes=((20, ny // 4 + 1), (3, 3)))
             assert rec["nonfinite"] == 0
-            same_monitor(rec, u, rho, s.uLB, "monitor", probes=((20, ny // 4 + 1), (3, 3)))
+            same_monitor_record(rec, u, rho, s.uLB, "monitor", probes=((20, ny // 4 + 1), (3, 3)))
             host = HostStats()
             s.begin_statistics(); s.begin_residual()
             samples = []
@@ -180,13 +130,13 @@ def test_samplers_see_a_steady_finite_body():
                 uu, rr = s.get_fields()
                 host.add(uu, rr)
                 samples.append((s.steps_done, uu, rr))
-            _same_stats(s, host, "statistics")
+            same_stats(s, host, "statistics")
             got = s.residual_series()
             assert got["count"] == 2 and got["dropped"] == 0
             for i in range(2):
                 r = {k: got[k][i] for k in got if k not in ("count", "dropped")}
                 assert r["nonfinite"] == 0 and r["cells"] == nx * ny
-                same_residual(r, samples[i], samples[i + 1], f"residual {i}")
+                same_residual_record(r, samples[i], samples[i + 1], f"residual {i}")
             with warnings.catch_warnings():
                 warnings.simplefilter("ignore")
                 check_topology(s, "topology", (dtype,))

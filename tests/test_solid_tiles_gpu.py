@@ -11,36 +11,19 @@ V = 4 (fp32) or 2 (fp64) cells per vector, RV = ceil((S - 1) / V) rim vectors pe
 rows).  fp32, S = 4 / 5 (F = 8): 136 x 80 (120 = 2 x 56 + 8; 64 = 2 x 26 + 12 = 2 x 24 + 16) -- 128 x 72 has exactly two tiles per row
 there.  fp64: 72 x 72 for every S (S = 3: 64 = 2 x 28 + 8 both ways; S = 4 / 5: 56 = 2 x 24 + 8 columns, 2 x 26 + 4 / 2 x 24 + 8 rows)."""
 import math
-import os
-import sys
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-
-from solid_ref import SolidOracle  # noqa: E402
-from test_bounce_back_gpu import FAST_BOUND  # noqa: E402
-from test_solid_gpu import _masks  # noqa: E402
-from latticeboltzmannsimulations_amd import CavityBatch, CavitySolver, solid  # noqa: E402
+from cases import _masks, _tile
+from cases import _tile_shape as _shape
+from checks import FAST_BOUND, same_fields
+from solid_ref import SolidOracle
+from latticeboltzmannsimulations_amd import CavityBatch, CavitySolver, solid
 
 pytestmark = pytest.mark.gpu
 BB = dict(semantics="bounce_back")
 TILES = dict(solid_tiles=True)
-
-
-def _tile(dtype, S):
-    """(F, TX, TY) of the tile kernel for S steps per launch (k_stepS_deep)."""
-    V = 4 if np.dtype(dtype) == np.float32 else 2
-    RV = (S - 1 + V - 1) // V
-    return (4 if S == 3 else 8), (16 - 2 * RV) * V, 32 - 2 * (S - 1)
-
-
-def _shape(dtype, S):
-    if np.dtype(dtype) == np.float64:
-        return 72, 72
-    return (128, 72) if S == 3 else (136, 80)
 
 
 def _seam_masks(nx, ny, dtype, steps):
@@ -97,12 +80,6 @@ def _all_masks(nx, ny, dtype, steps):
     return out
 
 
-def _fields_equal(got, want, what):
-    for a, b, name in zip(got, want, ("u", "rho", "fin")):
-        assert np.isfinite(a).all(), f"{what}: {name} not finite"
-        assert np.array_equal(a, b), f"{what}: {name} differs in {np.count_nonzero(a != b)} values, max abs {np.abs(a - b).max()}"
-
-
 def _walk(o, single, tiled, marks, what):
     """Advance the reference, the one-step solver and the tile solvers {S: solver} together; at every step count in marks[S] solver S is
     compared with the reference and with the one-step route."""
@@ -112,13 +89,13 @@ def _walk(o, single, tiled, marks, what):
         single.step(n - (single.steps_done - n0))
         ref = (o.u, o.rho, o.fin)
         one = single.get_fields(want_fin=True)
-        _fields_equal(one, ref, f"{what} after {n}: one step per launch against the reference")
+        same_fields(one, ref, f"{what} after {n}: one step per launch against the reference")
         for S, s in tiled.items():
             if n in marks[S]:
                 s.step(n - (s.steps_done - n0))
                 got = s.get_fields(want_fin=True)
-                _fields_equal(got, ref, f"{what} S={S} after {n}: against the reference")
-                _fields_equal(got, one, f"{what} S={S} after {n}: against one step per launch")
+                same_fields(got, ref, f"{what} S={S} after {n}: against the reference")
+                same_fields(got, one, f"{what} S={S} after {n}: against one step per launch")
 
 
 GROUPS = [(c, d, g) for d in (np.float32, np.float64) for c in ("SRT", "TRT", "MRT") for g in ((3,), (4, 5))]
@@ -176,7 +153,7 @@ def test_other_frame_routes(dtype, tune):
                     s.set_solid(ms[name]); g.set_solid(ms[name])
                 for n in (1, S, 2 * S + 3, 17):
                     s.step(n); g.step(n)
-                    _fields_equal(s.get_fields(want_fin=True), g.get_fields(want_fin=True), f"{tune} S={S} {name} after {s.steps_done}")
+                    same_fields(s.get_fields(want_fin=True), g.get_fields(want_fin=True), f"{tune} S={S} {name} after {s.steps_done}")
 
 
 @pytest.mark.parametrize("dtype", [np.float32, np.float64])
@@ -216,7 +193,7 @@ def test_all_fluid_mask_equals_plain_bounce_back_tiles(dtype):
                 for n in (1, S, 2 * S + 1, 30):
                     assert s.next_unit(n) == plain.next_unit(n)
                     plain.step(n); s.step(n)
-                    _fields_equal(s.get_fields(want_fin=True), plain.get_fields(want_fin=True), f"{nx}x{ny} S={S} {arith} after {s.steps_done}")
+                    same_fields(s.get_fields(want_fin=True), plain.get_fields(want_fin=True), f"{nx}x{ny} S={S} {arith} after {s.steps_done}")
 
 
 @pytest.mark.parametrize("dtype", [np.float32, np.float64])
@@ -235,7 +212,7 @@ def test_batch_of_masks_equals_lattices_alone(dtype):
         for i, Re in enumerate(Res):
             with CavitySolver(nx, ny, Re, RT="MRT", dtype=dtype, solid=masks[i], **BB) as s:
                 s.step(23)
-                _fields_equal((u[i], rho[i], fin[i]), s.get_fields(want_fin=True), f"lattice {i} {tune}")
+                same_fields((u[i], rho[i], fin[i]), s.get_fields(want_fin=True), f"lattice {i} {tune}")
                 assert {k: F[k][i] for k in F} == s.solid_force(), Re
 
 
@@ -313,7 +290,7 @@ def test_checkpoint_round_trip(tmp_path):
         with CavitySolver(nx, ny, 400.0, RT="MRT", dtype=np.float32, solid=m, tuning=tune, **BB) as r:
             assert r.load_checkpoint(path) == 25
             r.step(30)
-            _fields_equal(r.get_fields(want_fin=True), want, f"restart {tune}")
+            same_fields(r.get_fields(want_fin=True), want, f"restart {tune}")
 
 
 def test_describe_next_unit_and_error_paths():

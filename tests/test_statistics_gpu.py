@@ -3,96 +3,26 @@ same step counts on every kernel route, dtype, operator, closure, semantics and 
 stepping; batches and slabs reproduce the lone lattice; the life cycle; a steady flow has a mean equal to its final field; and the
 time-mean of the reference's LES default run (SRT, Smagorinsky, Re 7500 / 10000, 160^2) against Ghia's columns."""
 import ctypes
-import itertools
-import os
-import sys
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+from latticeboltzmannsimulations_amd import CavityBatch, CavitySolver, ghia
+from latticeboltzmannsimulations_amd.mrt_gpu import run_cavity
+from latticeboltzmannsimulations_amd.slab import LOW, HIGH, LocalSlabs, partition_rows
 
-from latticeboltzmannsimulations_amd import CavityBatch, CavitySolver, _lib, ghia  # noqa: E402
-from latticeboltzmannsimulations_amd.mrt_gpu import run_cavity  # noqa: E402
-from latticeboltzmannsimulations_amd.slab import LOW, HIGH, LocalSlabs, partition_rows  # noqa: E402
-from latticeboltzmannsimulations_amd.solver import launch_plan  # noqa: E402
+from cases import route_cases, route_id
+from checks import HostStats, perturbed, raw_stats, same_stats
 
 pytestmark = pytest.mark.gpu
 
 
-def _perturbed(nx, ny, dtype, seed):
-    """A non-trivial state for set_state: equilibrium-like populations with a seeded perturbation of a few per cent."""
-    rng = np.random.default_rng(seed)
-    t = np.array([4 / 9] + [1 / 9] * 4 + [1 / 36] * 4)
-    return (t[:, None, None] * (1.0 + 0.03 * rng.standard_normal((9, nx, ny)))).astype(dtype)
-
-
-def _raw(s):
-    """lbm_stats_get as it comes: (E[u], E[rho], [E[uu], E[vv], E[uv]], count), float64, whole-lattice shaped."""
-    lead = s._lead
-    mu, mrho, sec = np.zeros(lead + (2, s.nx, s.ny)), np.zeros(lead + (s.nx, s.ny)), np.zeros(lead + (3, s.nx, s.ny))
-    n = ctypes.c_longlong(-1)
-    rc = s.lib.lbm_stats_get(s._h, mu.ctypes.data, mrho.ctypes.data, sec.ctypes.data, ctypes.byref(n))
-    assert rc == 0, s.lib.lbm_last_error(s._h)
-    return mu, mrho, sec, n.value
-
-
-class HostStats:
-    """The contract's host loop: acc += u.astype(f64); acc2 += u64 * u64; ...; acc / count."""
-
-    def __init__(self):
-        self.S, self.n = None, 0
-
-    def add(self, u, rho):
-        u, rho = u.astype(np.float64), rho.astype(np.float64)
-        ux, uy = u[..., 0, :, :], u[..., 1, :, :]
-        terms = [u, rho, np.stack([ux * ux, uy * uy, ux * uy], axis=-3)]
-        self.S = terms if self.S is None else [a + b for a, b in zip(self.S, terms)]
-        self.n += 1
-
-    def means(self):
-        return [a / self.n for a in self.S] + [self.n]
-
-
-def _same_stats(s, host, what):
-    got = _raw(s)
-    if host.n == 0:
-        assert got[3] == 0, f"{what}: {got[3]} samples, host none"
-        return
-    want = host.means()
-    assert got[3] == want[3], f"{what}: {got[3]} samples, host {want[3]}"
-    for name, a, b in zip(("u", "rho", "second"), got[:3], want[:3]):
-        assert np.array_equal(a, b), f"{what}: E[{name}] differs, max abs {np.abs(a - b).max()}"
-
-
-def _valid(cfg):
-    kernel, dtype, coll, turb, sem, arith = cfg
-    try:
-        launch_plan(192, 160, 1000.0, RT=coll, dtype=dtype, turb=turb, semantics=sem, kernel=kernel, arith=arith)
-        return True
-    except (RuntimeError, ValueError):
-        return False
-
-
-ROUTES = ["generic", "vec", "tb", "stream", "push"]
-ALL = [c for c in itertools.product(ROUTES, [np.float32, np.float64], ["SRT", "TRT", "MRT"], [0, 1], ["mrt_gpu", "mrt_py", "bounce_back"],
-                                    ["strict", "fast", "promoted"]) if _valid(c)]
-# every route with each of its semantics and arithmetics once, then a seeded sample of the rest
-_pick = {}
-for c in ALL:
-    _pick.setdefault((c[0], c[4], c[5]), c)
-_rest = [c for c in ALL if c not in _pick.values()]
-_rng = np.random.default_rng(2026)
-CASES = list(_pick.values()) + [_rest[i] for i in sorted(_rng.choice(len(_rest), size=min(16, len(_rest)), replace=False))]
+# every route with each of its semantics and arithmetics once, then a seeded sample of the rest (cases.route_cases)
+CASES = route_cases(["generic", "vec", "tb", "stream", "push"], ["strict", "fast", "promoted"], (192, 160), seed=2026, sample=16)
 EVERY = (1, 3, 8, 13)
 
 
-def _ids(c):
-    return f"{c[0]}-{np.dtype(c[1]).name}-{c[2]}-t{c[3]}-{c[4]}-{c[5]}"
-
-
-@pytest.mark.parametrize("cfg", CASES, ids=_ids)
+@pytest.mark.parametrize("cfg", CASES, ids=route_id)
 def test_bit_identical_to_host_loop_and_stepping_unchanged(cfg):
     """From an upload (the first sample is the raw step's), lbm_step calls that do not line up with `every`; then statistics begun
     again mid-run after a multi-step unit.  After every call: the device statistics equal the host loop over get_fields() of a second
@@ -109,7 +39,7 @@ def _sampled_run_equals_host_loop(cfg, i, tuning=None, described=None):
     with CavitySolver(nx, ny, 1000.0, **kw) as s, CavitySolver(nx, ny, 1000.0, **kw) as ref:
         for name, value in (described or {}).items():
             assert s.describe()[name] == value and ref.describe()[name] == value, (name, s.describe()[name])
-        f = _perturbed(nx, ny, dtype, i)
+        f = perturbed(nx, ny, dtype, i)
         s.set_state(f); ref.set_state(f)
         for phase, (every, calls) in enumerate(((EVERY[i % 4], (5, 20, 1, 13)), (EVERY[(i + 1) % 4], (17, 5, 20, 1)))):
             if phase == 1:   # mid-run, behind a call that ends in a multi-step unit
@@ -124,9 +54,9 @@ def _sampled_run_equals_host_loop(cfg, i, tuning=None, described=None):
                         host.add(*ref.get_fields())
                 if ref.steps_done < s.steps_done:
                     ref.step(s.steps_done - ref.steps_done)
-                _same_stats(s, host, f"{_ids(cfg)} every={every} after {s.steps_done}")
+                same_stats(s, host, f"{route_id(cfg)} every={every} after {s.steps_done}")
                 a, b = s.get_fields(want_fin=True), ref.get_fields(want_fin=True)
-                assert all(np.array_equal(x, y) for x, y in zip(a, b)), f"{_ids(cfg)}: stepping perturbed at {s.steps_done}"
+                assert all(np.array_equal(x, y) for x, y in zip(a, b)), f"{route_id(cfg)}: stepping perturbed at {s.steps_done}"
 
 
 @pytest.mark.parametrize("dtype", [np.float32, np.float64], ids=["float32", "float64"])
@@ -155,7 +85,7 @@ def test_auto_route_with_the_walls_inside_the_streaming_kernel():
                 ref.step(n - ref.steps_done)
                 host.add(*ref.get_fields())
             ref.step(s.steps_done - ref.steps_done)
-            _same_stats(s, host, f"auto every={every}")
+            same_stats(s, host, f"auto every={every}")
             a, b = s.get_fields(want_fin=True), ref.get_fields(want_fin=True)
             assert all(np.array_equal(x, y) for x, y in zip(a, b))
 
@@ -167,14 +97,14 @@ def test_batch_of_mixed_reynolds_numbers_gives_each_lattice_its_own_statistics()
         bt.begin_statistics(3)
         for k in (5, 20, 1):
             bt.step(k)
-        mu, mrho, sec, n = _raw(bt)
+        mu, mrho, sec, n = raw_stats(bt)
         st = bt.statistics()
     for b, Re in enumerate(Res):
         with CavitySolver(nx, ny, Re, RT="MRT", dtype=np.float32, turb=1) as s:
             s.begin_statistics(3)
             for k in (5, 20, 1):
                 s.step(k)
-            one = _raw(s)
+            one = raw_stats(s)
         assert one[3] == n == 8
         assert np.array_equal(one[0], mu[b]) and np.array_equal(one[1], mrho[b]) and np.array_equal(one[2], sec[b]), Re
         assert st["u"].shape == (3, 2, nx, ny) and st["uu"].shape == (3, nx, ny)
@@ -201,10 +131,10 @@ def test_three_slabs_with_caller_driven_halos_reproduce_the_lone_lattice(dtype):
                 whole.sample_statistics()
                 for sl in slabs:
                     sl.sample_statistics()
-            want = _raw(whole)
+            want = raw_stats(whole)
             got = [np.zeros_like(a) for a in want[:3]]
             for sl in slabs:   # (each slab writes its own rows only)
-                mu, mrho, sec, n = _raw(sl)
+                mu, mrho, sec, n = raw_stats(sl)
                 y0, m = sl.y0, sl.ny_local
                 got[0][..., y0:y0 + m] = mu[..., y0:y0 + m]
                 got[1][..., y0:y0 + m] = mrho[..., y0:y0 + m]
@@ -227,7 +157,7 @@ def test_loopback_slab_with_manual_samples():
         a.comm_loopback()
         with pytest.raises(RuntimeError, match=r"\(-4\)"):
             a.begin_statistics(8)
-        fin0 = _perturbed(nx, NY, np.float32, 5)
+        fin0 = perturbed(nx, NY, np.float32, 5)
         a.set_state(fin0); b.set_state(fin0)
         a.begin_statistics(0); b.begin_statistics(0)
         up = np.empty(b.halo_elems(), dtype=np.float32); down = np.empty(b.halo_elems(), dtype=np.float32)
@@ -238,7 +168,7 @@ def test_loopback_slab_with_manual_samples():
                 b.halo_export(LOW, up.ctypes.data); b.halo_export(HIGH, down.ctypes.data)
                 b.halo_import(HIGH, up.ctypes.data); b.halo_import(LOW, down.ctypes.data)
             a.sample_statistics(); b.sample_statistics()
-        ra, rb = _raw(a), _raw(b)
+        ra, rb = raw_stats(a), raw_stats(b)
         assert ra[3] == rb[3] == 4
         assert all(np.array_equal(x, y) for x, y in zip(ra[:3], rb[:3]))
         assert np.isfinite(ra[0][..., rows[0]:rows[0] + rows[1]]).all()
@@ -255,7 +185,7 @@ def test_life_cycle():
         with pytest.raises(RuntimeError, match=r"\(-4\)"):
             s.sample_statistics()                      # no step yet
         s.step(10).sample_statistics()
-        assert _raw(s)[3] == 1
+        assert raw_stats(s)[3] == 1
         s.begin_statistics(4)                          # begin resets the sums
         mu, mrho, sec = np.full((2, nx, ny), 7.0), np.full((nx, ny), 7.0), np.full((3, nx, ny), 7.0)
         n = ctypes.c_longlong(-1)
@@ -272,7 +202,7 @@ def test_life_cycle():
         s.step(5)
         s.begin_statistics(1).step(3)
         assert s.statistics()["samples"] == 3
-        s.set_state(_perturbed(nx, ny, np.float64, 1))  # ends statistics
+        s.set_state(perturbed(nx, ny, np.float64, 1))  # ends statistics
         with pytest.raises(RuntimeError, match=r"\(-4\)"):
             s.sample_statistics()
         s.step(2).begin_statistics(2).step(4)
@@ -283,11 +213,11 @@ def test_life_cycle():
         s.begin_statistics(2).step(4)                  # end, then begin again
         host = HostStats()
         with CavitySolver(nx, ny, 400.0, dtype=np.float64, kernel="tb") as ref:
-            ref.set_state(_perturbed(nx, ny, np.float64, 1))
+            ref.set_state(perturbed(nx, ny, np.float64, 1))
             for n in (8, 10):
                 ref.step(n - ref.steps_done)
                 host.add(*ref.get_fields())
-        _same_stats(s, host, "end + begin")
+        same_stats(s, host, "end + begin")
 
 
 def test_steady_flow_mean_is_the_final_field():

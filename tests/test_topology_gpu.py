@@ -3,108 +3,34 @@ topology.host_topology / host_stream_function of get_fields(out_dtype) of the sa
 every omega, every record field, no tolerance -- on every kernel route, semantics and arithmetic, on shapes around the 64-cell block
 of the prefix sum, for both host dtypes and in a batch; ties, cells that are not finite, the error cases, the stepping left alone;
 the physics pin against Ghia's vortex table and the front end."""
-import itertools
-import warnings
-
 import numpy as np
 import pytest
 
 from latticeboltzmannsimulations_amd import CavityBatch, CavitySolver, ghia
 from latticeboltzmannsimulations_amd import topology as T
 from latticeboltzmannsimulations_amd.mrt_gpu import run_cavity
-from latticeboltzmannsimulations_amd.solver import launch_plan
+
+from cases import route_cases, route_id, windows
+from checks import check_topology, perturbed, rest, same_topology_record
 
 pytestmark = pytest.mark.gpu
 
-W = np.array([4 / 9] + [1 / 9] * 4 + [1 / 36] * 4)
+# every route with each of its semantics and arithmetics once (cases.route_cases without a sample), then four named cases
+CASES = route_cases(["generic", "vec", "tb", "stream", "push"], ["strict", "fast", "promoted"], (192, 160),
+                    extras=[("tb", np.float64, "MRT", 0, "mrt_gpu", "strict"), ("stream", np.float64, "SRT", 1, "mrt_gpu", "strict"),
+                            ("generic", np.float32, "MRT", 1, "mrt_gpu", "strict"), ("tb", np.float32, "TRT", 0, "mrt_py", "strict")])
 
 
-def _perturbed(nx, ny, dtype, seed):
-    """A non-trivial state for set_state: equilibrium-like populations with a seeded perturbation of a few per cent."""
-    rng = np.random.default_rng(seed)
-    return (W[:, None, None] * (1.0 + 0.03 * rng.standard_normal((9, nx, ny)))).astype(dtype)
-
-
-def _rest(nx, ny, dtype):
-    return np.ascontiguousarray(np.broadcast_to(W[:, None, None], (9, nx, ny))).astype(dtype)
-
-
-def _windows(nx, ny):
-    """Four windows, one of them empty: the interior, one that straddles the first block boundary (where there is one), one cell
-    column at the right wall, nothing."""
-    return ((1, nx - 1, 1, ny - 1), (min(60, nx // 2), min(70, nx), 0, ny // 2 + 1), (nx - 1, nx, ny // 3, ny), (nx // 2, nx // 2, 0, ny))
-
-
-def _eq(a, b):
-    return a == b or (a != a and b != b)
-
-
-def _same_record(got, want, what):
-    assert got["step"] == want["step"], f"{what}: step {got['step']} != {want['step']}"
-    assert got["closure"] == want["closure"], f"{what}: closure {got['closure']} != {want['closure']}"
-    assert len(got["window"]) == len(want["window"]), what
-    for i, (g, w) in enumerate(zip(got["window"], want["window"])):
-        for side in ("min", "max"):
-            for k in ("psi", "x", "y", "omega"):
-                assert _eq(g[side][k], w[side][k]), f"{what}: window {i} {side} {k}: {g[side]} != {w[side]}"
-
-
-def _check(s, what, out_dtypes, windows=None):
-    wins = _windows(s.nx, s.ny) if windows is None else windows
-    for dt in out_dtypes:
-        with warnings.catch_warnings():
-            warnings.simplefilter("ignore")
-            u, _ = s.get_fields(out_dtype=dt)
-        tag = f"{what} out={np.dtype(dt).name} after {s.steps_done}"
-        want = T.host_topology(u, s.uLB, wins, step=s.steps_done)
-        _same_record(s.topology(wins, out_dtype=dt), want, tag)
-        psi, omega = s.stream_function(out_dtype=dt)
-        hpsi, homega = T.host_stream_function(u)
-        assert psi.dtype == omega.dtype == np.float64
-        assert np.array_equal(psi, hpsi, equal_nan=True), f"{tag}: psi differs in {np.count_nonzero(~((psi == hpsi) | (np.isnan(psi) & np.isnan(hpsi))))} cells"
-        assert np.array_equal(omega, homega, equal_nan=True), f"{tag}: omega differs"
-        for w_ in want["window"]:      # the record's omega is the field's, the same bits
-            for e in (w_["min"], w_["max"]):
-                if e["x"] >= 0:
-                    assert _eq(e["omega"], omega[e["x"], e["y"]]) and e["psi"] == psi[e["x"], e["y"]]
-    return want
-
-
-def _valid(cfg):
-    kernel, dtype, coll, turb, sem, arith = cfg
-    try:
-        launch_plan(192, 160, 1000.0, RT=coll, dtype=dtype, turb=turb, semantics=sem, kernel=kernel, arith=arith)
-        return True
-    except (RuntimeError, ValueError):
-        return False
-
-
-# every route with each of its semantics and arithmetics once (the selection scheme of tests/test_monitor_gpu.py)
-ROUTES = ["generic", "vec", "tb", "stream", "push"]
-_pick = {}
-for _c in itertools.product(ROUTES, [np.float32, np.float64], ["SRT", "TRT", "MRT"], [0, 1], ["mrt_gpu", "mrt_py", "bounce_back"],
-                            ["strict", "fast", "promoted"]):
-    if (_c[0], _c[4], _c[5]) not in _pick and _valid(_c):
-        _pick[(_c[0], _c[4], _c[5])] = _c
-CASES = list(_pick.values())
-CASES += [c for c in [("tb", np.float64, "MRT", 0, "mrt_gpu", "strict"), ("stream", np.float64, "SRT", 1, "mrt_gpu", "strict"),
-                      ("generic", np.float32, "MRT", 1, "mrt_gpu", "strict"), ("tb", np.float32, "TRT", 0, "mrt_py", "strict")] if c not in CASES]
-
-
-def _ids(c):
-    return f"{c[0]}-{np.dtype(c[1]).name}-{c[2]}-t{c[3]}-{c[4]}-{c[5]}"
-
-
-@pytest.mark.parametrize("cfg", CASES, ids=_ids)
+@pytest.mark.parametrize("cfg", CASES, ids=route_id)
 def test_record_and_fields_equal_the_host_statement_on_every_route(cfg):
     """192 x 160 from an upload, 37 steps in one call: the last launch unit of the multi-step routes is a multi-step one, so the
     sampled lattice is the recomputed one."""
     kernel, dtype, coll, turb, sem, arith = cfg
     nx, ny = 192, 160
     with CavitySolver(nx, ny, 1000.0, RT=coll, dtype=dtype, turb=turb, semantics=sem, kernel=kernel, arith=arith) as s:
-        s.set_state(_perturbed(nx, ny, dtype, CASES.index(cfg)))
+        s.set_state(perturbed(nx, ny, dtype, CASES.index(cfg)))
         s.step(37)
-        want = _check(s, _ids(cfg), (np.float32,) if dtype == np.float32 else (np.float64,))
+        want = check_topology(s, route_id(cfg), (np.float32,) if dtype == np.float32 else (np.float64,))
         assert want["window"][0]["min"]["x"] > 0 and want["window"][3]["min"]["x"] == -1 and np.isfinite(want["closure"])
 
 
@@ -119,23 +45,23 @@ def test_shapes_around_the_block_of_the_prefix_sum(nx, ny, dtype, kernel):
     with CavitySolver(nx, ny, 400.0, dtype=dtype, kernel=kernel) as s:
         if (nx, ny) == (64, 64):
             assert s.describe()["kernel"].startswith("k_stepS")
-        s.set_state(_perturbed(nx, ny, dtype, nx + ny))
+        s.set_state(perturbed(nx, ny, dtype, nx + ny))
         for n in (1, 12):
             s.step(n - s.steps_done)
-            _check(s, f"{nx}x{ny} {np.dtype(dtype).name} {kernel}", (np.float32,) if dtype == np.float32 else (np.float64,))
-        _check(s, "the whole lattice and single cells", (np.float32,), windows=((0, nx, 0, ny), (0, 1, 0, 1), (nx - 1, nx, ny - 1, ny)))
+            check_topology(s, f"{nx}x{ny} {np.dtype(dtype).name} {kernel}", (np.float32,) if dtype == np.float32 else (np.float64,))
+        check_topology(s, "the whole lattice and single cells", (np.float32,), wins=((0, nx, 0, ny), (0, 1, 0, 1), (nx - 1, nx, ny - 1, ny)))
 
 
 def test_each_host_dtype_matches_its_own_host_statement_and_the_two_differ():
     nx, ny = 200, 72
     with CavitySolver(nx, ny, 1000.0, dtype=np.float64) as s:
-        s.set_state(_perturbed(nx, ny, np.float64, 5))
+        s.set_state(perturbed(nx, ny, np.float64, 5))
         s.step(9)
-        _check(s, "fp64 lattice", (np.float32, np.float64))
+        check_topology(s, "fp64 lattice", (np.float32, np.float64))
         p32, o32 = s.stream_function(out_dtype=np.float32)
         p64, o64 = s.stream_function(out_dtype=np.float64)
         assert not np.array_equal(p32, p64) and not np.array_equal(o32, o64)
-        assert s.topology(_windows(nx, ny), out_dtype=np.float32)["closure"] != s.topology(_windows(nx, ny), out_dtype=np.float64)["closure"]
+        assert s.topology(windows(nx, ny), out_dtype=np.float32)["closure"] != s.topology(windows(nx, ny), out_dtype=np.float64)["closure"]
         pd, _ = s.stream_function()                      # the default is the lattice's dtype
         assert np.array_equal(pd, p64)
 
@@ -143,7 +69,7 @@ def test_each_host_dtype_matches_its_own_host_statement_and_the_two_differ():
 def test_batch_of_three_reynolds_numbers_gives_each_lattice_its_own_record_and_fields():
     Res = [100.0, 400.0, 1000.0]
     nx, ny = 136, 96
-    wins = _windows(nx, ny)
+    wins = windows(nx, ny)
     with CavityBatch(nx, ny, Res, RT="MRT", dtype=np.float32) as bt:
         bt.step(26)
         recs = bt.topology(wins)
@@ -158,8 +84,8 @@ def test_batch_of_three_reynolds_numbers_gives_each_lattice_its_own_record_and_f
             lone = s.topology(wins)
             lp, lo = s.stream_function()
             assert s.vortex_table() == tables[b] == T.host_vortex_table(ub[b], s.uLB)
-        _same_record(recs[b], lone, f"Re {Re}")
-        _same_record(recs[b], T.host_topology(ub[b], 0.08, wins, step=26), f"Re {Re} against the host")
+        same_topology_record(recs[b], lone, f"Re {Re}")
+        same_topology_record(recs[b], T.host_topology(ub[b], 0.08, wins, step=26), f"Re {Re} against the host")
         assert np.array_equal(psi[b], lp) and np.array_equal(omega[b], lo)
         hp, ho = T.host_stream_function(ub[b])
         assert np.array_equal(psi[b], hp) and np.array_equal(omega[b], ho)
@@ -171,7 +97,7 @@ def test_ties_go_to_the_first_cell_of_the_window_for_the_minimum_and_the_maximum
     its (x_lo, y_lo) -- across tiles, blocks, waves and lanes."""
     nx, ny = 200, 104
     with CavitySolver(nx, ny, 1000.0, dtype=np.float64) as s:
-        s.set_state(_rest(nx, ny, np.float64))
+        s.set_state(rest(nx, ny, np.float64))
         s.step(1)
         u, _ = s.get_fields()
         assert not u[1].any()
@@ -181,19 +107,19 @@ def test_ties_go_to_the_first_cell_of_the_window_for_the_minimum_and_the_maximum
             for side in ("min", "max"):
                 assert (e[side]["psi"], e[side]["x"], e[side]["y"]) == (0.0, w[0], w[2]), (w, side, e[side])
         assert rec["closure"] == 0.0
-        _check(s, "rest", (np.float64,), windows=wins)
+        check_topology(s, "rest", (np.float64,), wins=wins)
 
 
 def test_cells_that_are_not_finite_are_skipped_not_faulted_on():
     """One NaN population at one cell: psi is NaN from that cell to the right wall of its row, omega in the cells around it."""
     nx, ny = 200, 72
-    fin = _perturbed(nx, ny, np.float32, 3)
+    fin = perturbed(nx, ny, np.float32, 3)
     fin[3, 70, 40] = np.nan
     with CavitySolver(nx, ny, 1000.0, dtype=np.float32) as s:
         s.set_state(fin)
         s.step(1)
         wins = ((0, nx, 0, ny), (70, nx, 40, 41), (60, 80, 39, 42), (0, 70, 40, 41))
-        want = _check(s, "one NaN", (np.float32,), windows=wins)
+        want = check_topology(s, "one NaN", (np.float32,), wins=wins)
         psi, omega = s.stream_function()
         assert np.isnan(psi[70:, 40]).all() and np.isfinite(psi[:70, 40]).all() and np.isfinite(np.delete(psi, 40, axis=1)).all()
         # (omega of the cell itself is a central difference of its four neighbours: finite)
@@ -206,19 +132,19 @@ def test_errors():
     nx, ny = 192, 160
     with CavitySolver(nx, ny, 1000.0, dtype=np.float32) as s:
         with pytest.raises(RuntimeError, match=r"\(-4\)"):
-            s.topology(_windows(nx, ny))                    # no step yet: LBM_ERR_STATE
+            s.topology(windows(nx, ny))                    # no step yet: LBM_ERR_STATE
         with pytest.raises(RuntimeError, match=r"\(-4\)"):
             s.stream_function()
         s.step(10)
         rec = (T.lbm_topology_record * 1)()
-        good = T.make_spec(nx, ny, 0, _windows(nx, ny))
+        good = T.make_spec(nx, ny, 0, windows(nx, ny))
         assert s.lib.lbm_topology(s._h, good, rec) == 0
         for field, value in (("struct_size", 8), ("host_dtype", 2), ("nwindows", 9), ("nwindows", -1)):
-            spec = T.make_spec(nx, ny, 0, _windows(nx, ny))
+            spec = T.make_spec(nx, ny, 0, windows(nx, ny))
             setattr(spec, field, value)
             assert s.lib.lbm_topology(s._h, spec, rec) == -1, field          # LBM_ERR_INVALID
         for j, value in ((1, nx + 1), (0, -1), (3, ny + 1), (2, ny // 2 + 2)):   # hi beyond the lattice, lo < 0, lo > hi
-            spec = T.make_spec(nx, ny, 0, _windows(nx, ny))
+            spec = T.make_spec(nx, ny, 0, windows(nx, ny))
             spec.window[1][j] = value
             assert s.lib.lbm_topology(s._h, spec, rec) == -1, (j, value)
         assert s.lib.lbm_topology(s._h, None, rec) == -1 and s.lib.lbm_topology(s._h, good, None) == -1
@@ -237,16 +163,16 @@ def test_errors():
 def test_the_stepping_is_left_alone_and_two_calls_give_the_same_bits(kernel):
     nx, ny = 192, 160
     kw = dict(dtype=np.float32, kernel=kernel)
-    wins = _windows(nx, ny)
+    wins = windows(nx, ny)
     with CavitySolver(nx, ny, 1000.0, **kw) as s, CavitySolver(nx, ny, 1000.0, **kw) as ref:
-        f = _perturbed(nx, ny, np.float32, 9)
+        f = perturbed(nx, ny, np.float32, 9)
         s.set_state(f); ref.set_state(f)
         s.step(13)
         a = s.topology(wins)
         p1, o1 = s.stream_function()
         b = s.topology(wins)
         p2, o2 = s.stream_function()
-        _same_record(a, b, "second call")
+        same_topology_record(a, b, "second call")
         assert np.array_equal(p1, p2) and np.array_equal(o1, o2)
         s.step(20)
         s.vortex_table()
@@ -254,7 +180,7 @@ def test_the_stepping_is_left_alone_and_two_calls_give_the_same_bits(kernel):
         ref.step(37)
         x, y = s.get_fields(want_fin=True), ref.get_fields(want_fin=True)
         assert all(np.array_equal(p, q) for p, q in zip(x, y)), "stepping perturbed"
-        _same_record(s.topology(wins), ref.topology(wins), "against a run without the calls")
+        same_topology_record(s.topology(wins), ref.topology(wins), "against a run without the calls")
 
 
 def test_physics_pin_vortex_table_at_re_1000_against_ghia():
