@@ -579,6 +579,49 @@ int lbm_force_end(lbm_ctx* c);
 int lbm_set_body_motion(lbm_ctx* c, const double* motion);
 int lbm_get_body_motion(lbm_ctx* c, double* motion_out);
 
+/* --- curved obstacle surfaces: a wall distance per link, interpolated bounce-back ------------------- */
+/* No reference counterpart.  Without a shape every wall sits half-way along its link, so a round body is a staircase and force, torque
+ * and motion are first order in the lattice spacing.  With a shape every link carries q, the fraction of the link from the fluid cell
+ * (x, y) to the wall, towards the source (x - cx_k, y + cy_k), and bounces by Bouzidi, Firdaouss and Lallemand's linear interpolation,
+ * second order.  Opt-in: a context that never sets a shape launches the kernels it always did and gives their bits.  A shaped lattice does
+ * NOT conserve its mass (the interpolation weights two populations): it trades mass conservation for accuracy.
+ *
+ * Per link (cell P = (x, y), slot k, body b), on the host in double without contraction, every operation rounded in the order written:
+ *     near = q < 1/2 and N = (x + cx_k, y - cy_k) is a fluid cell inside the lattice; a link with q < 1/2 whose N is no such cell (a
+ *       fluid cell between two bodies, or against a wall) falls back to the effective q = 1/2
+ *     a = near ? 2 q : 1 / (2 q)
+ *     (rx, ry) = ((x - q cx_k) - x0, (y + q cy_k) - y0)      the wall point; at q = 1/2 the bits of the midpoint of lbm_body_force
+ *     delta = (6 w_k) (cx_k uwx + cy_k uwy), uwx = Ux + Om ry, uwy = Uy + Om rx      as lbm_set_body_motion forms it, at the wall point
+ *     d = near ? delta : a delta
+ *   a and d are rounded once to the lattice type.  The flux check of lbm_set_body_motion is unchanged: it is formed from the deltas of
+ *   the same motion at q = 1/2.
+ * The rule, on the read side -- the same in the step kernels and in every gather, in the lattice type, no contraction:
+ *     own = fpost_opp(k)(P);   other = near ? fpost_opp(k)(N) : fpost_k(P)
+ *     a == 1:     g_k = own + d                                       (a select, not a multiply by zero)
+ *     otherwise:  t1 = a own;  b = 1 - a;  t2 = b other;  g_k = (t1 + t2) + d
+ *   Sources outside the lattice and the lid term are applied afterwards as without a shape.
+ * Stores of a shaped context are the pure post-collision values: there is no store-side add, and the raw first step after an upload
+ * applies nothing.  lbm_get_fields returns the arriving populations with the rule applied, and lbm_set_state of that fin is an exact
+ * restart.  THE DIFFERENCE from a context without a shape, which adds a motion's term where it stores: here a motion set after n steps
+ * shows in the populations arriving for step n + 1, and in every export and sampler from that moment.
+ * Force (lbm_solid_force, lbm_body_force, the force series): per link f_out = fpost_opp(k)(P) as the lattice holds it, f_in = g_k, both
+ *   converted to double, (tx, ty) = c_opp(k) (f_out + f_in), tz = rx ty + ry tx with the wall point above; tree, order and chunks as
+ *   without a shape; lbm_solid_force equals the bodies' sum.
+ *
+ * lbm_set_solid_shape: q[B][8][X][Y] doubles in the host layout of the mask, plane k - 1 for slot k.  On every link 0 < q <= 1 and
+ *   finite, else LBM_ERR_INVALID (the text names the first offending link: lattices in order, cells in [y][x] order, then k); values
+ *   off the links are ignored.  NULL clears the shape: the context returns to the half-way rule and its kernels.  LBM_ERR_STATE on a
+ *   context of another semantics, on a LBM_FLAG_SOLID_TILES context (the tile kernel keeps the half-way rule), and -- for setting and
+ *   for clearing -- while a nonzero body motion is set: a context without a shape keeps the motion's term on the store side, a shaped one
+ *   on the read side, and switching under a stored term would corrupt one step.  The order is the shape first, then the motion.
+ *   Touches neither the lattice nor the step count and ends no sampler.  Builds the tables on the host and uploads them (there and in
+ *   lbm_set_solid_bodies / lbm_set_body_motion, never inside lbm_step).  lbm_set_solid resets the shape; lbm_set_solid_bodies keeps q and
+ *   rebuilds what depends on labels and centres.  lbm_describe appends ` wall_shape=1` while a shape is set.
+ * lbm_get_solid_shape: q_out[B][8][X][Y] receives the effective q on the links (after the fallback) and 0 elsewhere; all 0 without a
+ *   shape. */
+int lbm_set_solid_shape(lbm_ctx* c, const double* q);
+int lbm_get_solid_shape(lbm_ctx* c, double* q_out);
+
 /* --- slab decomposition, externally driven exchange ---------------------------------- */
 /* No reference counterpart (the reference is single-GPU, MRT_GPU.py:29).  A step of a slab
  * is split so that a host-language driver can move halos with any transport:

@@ -96,8 +96,8 @@ def sources():
 
 def build(force=False, verbose=False):
     """Compile csrc/*.hip for gfx950 into liblbm_hip.so next to this file (in-tree).  The translation units (eight of host code +
-    C ABI: lbm_hip / lbm_plan / lbm_launch / lbm_comm / lbm_sampling / lbm_monitor / lbm_residual / lbm_topology / lbm_solid / lbm_bodies / lbm_body_motion; the explicit instantiations of the tile, streaming,
-    solid-mask and moving-body kernels, and of the tile kernel with solid cells, for float and for double) are compiled in parallel into csrc/_obj/ and linked."""
+    C ABI: lbm_hip / lbm_plan / lbm_launch / lbm_comm / lbm_sampling / lbm_monitor / lbm_residual / lbm_topology / lbm_solid / lbm_bodies / lbm_body_motion / lbm_body_shape; the explicit instantiations of the tile, streaming,
+    solid-mask, moving-body and shaped-body kernels, and of the tile kernel with solid cells, for float and for double) are compiled in parallel into csrc/_obj/ and linked."""
     srcs = sources()
     if not force and os.path.exists(LIB_PATH) and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(s) for s in srcs):
         return LIB_PATH
@@ -176,6 +176,8 @@ SIGNATURES = {
     "lbm_force_end": (_i, [_vp]),
     "lbm_set_body_motion": (_i, [_vp, _vp]),            # (motion: [B][nbodies][3] doubles, or NULL)
     "lbm_get_body_motion": (_i, [_vp, _vp]),
+    "lbm_set_solid_shape": (_i, [_vp, _vp]),            # (q: [B][8][X][Y] doubles, or NULL)
+    "lbm_get_solid_shape": (_i, [_vp, _vp]),
     "lbm_halo_elems": (_i, [_vp]),
     "lbm_halo_export": (_i, [_vp, _i, _vp]),
     "lbm_halo_import": (_i, [_vp, _i, _vp]),

@@ -93,6 +93,46 @@ __global__ __launch_bounds__(BLK) void k_body_force_move(const R* __restrict__ s
     body_force_chunk<R, true>(src, geo, bstride, links, chunks, centre, nbodies, partial, link_delta);
 }
 
+// A shape is set (lbm_set_solid_shape): f_out = f, f_in = shape_rule of the link (k_solid_force_shape), (tx, ty) = c_opp(k) (f_out + f_in),
+// and the arm of the torque is the wall point, (rx, ry) = ((x - q cx_k) - x0, (y + q cy_k) - y0), q the link's entry of link_q (the
+// effective q); chunks, order and tree as k_body_force.
+template <typename R>
+__global__ __launch_bounds__(BLK) void k_body_force_shape(const R* __restrict__ src, Geo geo, long long bstride, const BodyLink* __restrict__ links,
+                                                          const BodyChunk* __restrict__ chunks, const double* __restrict__ centre, int nbodies,
+                                                          double* __restrict__ partial, ShapeTable<R> sh, const double* __restrict__ link_q) {
+#pragma clang fp contract(off)
+    __shared__ double shm[BLK / RED_WAVE][BodyAcc::VALS];
+    const size_t slot = (size_t)blockIdx.z * gridDim.x + blockIdx.x;
+    const BodyChunk ch = chunks[slot];
+    src += blockIdx.z * bstride;
+    sh.cell_row += (long long)blockIdx.z * geo.nx * geo.ny;
+    BodyAcc a = BodyAcc::identity();
+    if (ch.n > 0) {
+        const double x0 = centre[((size_t)blockIdx.z * nbodies + ch.body) * 2], y0 = centre[((size_t)blockIdx.z * nbodies + ch.body) * 2 + 1];
+        for (int i = threadIdx.x; i < ch.n; i += BLK) {
+            const BodyLink l = links[ch.begin + i];
+            const int x = l.x, y = l.yk >> 4, k = l.yk & 15, o = opp(k);
+            const long long me = geo.at(x, y);
+            const R own = src[o * geo.plane + me];
+            const long long row = sh.cell_row[(long long)y * geo.nx + x];
+            R g = own;
+            if (row >= 0) {
+                const R other = ((sh.near[row] >> (k - 1)) & 1) ? src[o * geo.plane + geo.at(x + cxk(k), y - cyk(k))] : src[k * geo.plane + me];
+                g = shape_rule<R>(own, other, sh.ad[row * 16 + (k - 1)], sh.ad[row * 16 + 8 + (k - 1)]);
+            }
+            const double t = (double)own + (double)g, q = link_q[ch.begin + i];
+            const double tx = (double)cxk(o) * t, ty = (double)cyk(o) * t;
+            const double rx = ((double)x - q * (double)cxk(k)) - x0, ry = ((double)y + q * (double)cyk(k)) - y0;
+            a.links = a.links + 1.0;
+            a.fx = a.fx + tx;
+            a.fy = a.fy + ty;
+            a.tz = a.tz + (rx * ty + ry * tx);
+        }
+    }
+    red_wave(a);
+    if (red_workgroup<BodyAcc, BLK / RED_WAVE>(a, shm)) red_store(partial + slot * BodyAcc::VALS, a);
+}
+
 // The final pass, one wave per body and lattice over the body's chunks: rec[z][body] = {step, body, links, fx, fy, tz}
 __global__ __launch_bounds__(RED_WAVE) void k_body_force_final(const double* __restrict__ partial, const int32_t* __restrict__ first, int maxchunks,
                                                                double step, double* __restrict__ rec) {
@@ -128,7 +168,9 @@ static int body_tables(lbm_ctx* c, const std::vector<uint8_t>& mask, const Obsta
 // levels below it are reset -- a new mask: one body that holds every solid cell, centred at its centroid; new bodies: every body at
 // rest -- the tables of everything that changed are built aside, and only then does the context change, by moves: on any failure
 // its obstacle state is what it was.  before_commit runs between the two (lbm_set_solid: the link planes).  The caller has
-// synchronised the streams.
+// synchronised the streams.  The shape (lbm_set_solid_shape) stands beside the motion: ObsLevel::shape replaces or clears it (next.shape_q,
+// every body at rest: the caller checked) and touches nothing else; a new mask drops it; new bodies and a new motion keep q and rebuild
+// its tables, which then carry the motion's term -- a shaped context never holds MotionTables.
 int obstacles_change(lbm_ctx* c, ObsLevel level, Obstacles& next, int (*before_commit)(lbm_ctx*, const Obstacles&)) {
     Obstacles& cur = c->obs;
     const int B = c->plan.batch, nx = c->plan.geo.nx, ny = c->plan.geo.ny;
@@ -141,15 +183,43 @@ int obstacles_change(lbm_ctx* c, ObsLevel level, Obstacles& next, int (*before_c
         next.centre.assign((size_t)B * 2, 0.0);
         for (int b = 0; b < B; ++b) body_centroids(next.mask.data() + b * n, next.label.data() + b * n, nx, ny, 1, next.centre.data() + 2 * b);
     }
+    const bool shaped = level != ObsLevel::mask && !cur.shape_q.empty();   // (the levels that keep a shape)
+    if (level == ObsLevel::shape) {
+        if (!next.shape_q.empty()) {
+            next.nbodies = cur.nbodies; next.label = cur.label; next.centre = cur.centre; next.motion = cur.motion;
+            rc = shape_tables(c, next, next.shape_q, next.shaped, &next.shape_eff);
+        }
+        if (rc) return rc;
+        cur.shape_q = std::move(next.shape_q);
+        cur.shape_eff = std::move(next.shape_eff);
+        cur.shaped = std::move(next.shaped);
+        return LBM_OK;
+    }
     if (level != ObsLevel::motion) {
         next.motion.assign((size_t)B * next.nbodies * 3, 0.0);
         rc = body_tables(c, level == ObsLevel::mask ? next.mask : cur.mask, next, next.body);
+        if (rc == LBM_OK && shaped) rc = shape_tables(c, next, cur.shape_q, next.shaped, &next.shape_eff);
+    } else if (shaped) {
+        rc = motion_tables(c, next, next.moving, true);
+        if (rc == LBM_OK) {
+            next.nbodies = cur.nbodies; next.label = cur.label; next.centre = cur.centre;
+            rc = shape_tables(c, next, cur.shape_q, next.shaped, &next.shape_eff);
+        }
     } else {
         rc = motion_tables(c, next, next.moving);
     }
     if (rc == LBM_OK && before_commit) rc = before_commit(c, next);
     if (rc) return rc;
-    if (level == ObsLevel::mask) cur.mask = std::move(next.mask);
+    if (level == ObsLevel::mask) {
+        cur.mask = std::move(next.mask);
+        cur.shape_q.clear();
+        cur.shape_eff.clear();
+        cur.shaped = ShapeTables{};
+    }
+    if (shaped) {
+        cur.shape_eff = std::move(next.shape_eff);
+        cur.shaped = std::move(next.shaped);
+    }
     if (level != ObsLevel::motion) {
         sampler_free(c, SMP_FORCE);   // (its records are per body)
         cur.nbodies = next.nbodies;
@@ -169,7 +239,11 @@ static int body_force_enqueue(lbm_ctx* c, double* rec) {
     const double* link_delta = c->obs.moving.base ? c->obs.moving.link_delta : nullptr;
     return launch_variant(c, [&](auto v) {
         using R = typename decltype(v)::R;
-        if (link_delta)
+        if (c->obs.shaped.base)
+            hipLaunchKernelGGL((k_body_force_shape<R>), dim3(t.maxchunks, 1, c->plan.batch), dim3(BLK), 0, c->s_compute, c->lat[c->cur].as<const R>(),
+                               c->plan.geo, c->plan.bstride, t.links, t.chunks, t.centre, nbodies, t.partial, c->obs.shaped.template table<R>(),
+                               c->obs.shaped.link_q);
+        else if (link_delta)
             hipLaunchKernelGGL((k_body_force_move<R>), dim3(t.maxchunks, 1, c->plan.batch), dim3(BLK), 0, c->s_compute, c->lat[c->cur].as<const R>(),
                                c->plan.geo, c->plan.bstride, t.links, t.chunks, t.centre, nbodies, t.partial, link_delta);
         else

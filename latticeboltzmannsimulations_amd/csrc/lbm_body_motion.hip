@@ -11,8 +11,9 @@
 namespace lbmhost {
 
 // The tables of next.motion over the mask, the labels and the centres the context holds (lbm_wall_motion.hpp lays them out, in the order
-// of the link list the device holds: body_tables), uploaded into `out`; every body at rest: none, and `out` stays empty.
-int motion_tables(lbm_ctx* c, const Obstacles& next, MotionTables& out) {
+// of the link list the device holds: body_tables), uploaded into `out`; every body at rest: none, and `out` stays empty.  check_only (a
+// context with a shape, whose own table carries the term): the flux check alone, formed from the deltas at the links' midpoints.
+int motion_tables(lbm_ctx* c, const Obstacles& next, MotionTables& out, bool check_only) {
     if (std::all_of(next.motion.begin(), next.motion.end(), [](double v) { return v == 0.0; })) return LBM_OK;
     const Obstacles& o = c->obs;
     const MotionParts t = motion_parts(o.mask.data(), o.label.data(), o.centre.data(), next.motion.data(), c->plan.batch, c->plan.geo.nx, c->plan.geo.ny,
@@ -26,6 +27,7 @@ int motion_tables(lbm_ctx* c, const Obstacles& next, MotionTables& out) {
         return fail(c, LBM_ERR_INVALID, text);
     }
     if (t.refusal == MotionParts::TOO_MANY_ROWS) return fail(c, LBM_ERR_INVALID, "lbm_set_body_motion: too many cells with links");
+    if (check_only) return LBM_OK;
     Pack<HipMem> p = upload<HipMem>(t.parts(), "body motion tables");
     if (!p.err.empty()) return fail(c, p.no_memory ? LBM_ERR_NOMEM : LBM_ERR_HIP, p.err);
     out.cell_row = p.at<const int32_t>(MotionParts::CELL_ROW);

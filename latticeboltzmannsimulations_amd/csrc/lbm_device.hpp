@@ -492,6 +492,26 @@ __device__ __forceinline__ R lid_term(R rho_w, R uLB) { return (rho_w * uLB) * (
 constexpr int K_LINK = Q;
 constexpr int LINK_SOLID = 256;
 
+// Curved obstacle surfaces (lbm_set_solid_shape; contract in include/lbm.h): the per-cell table of a shaped context, built on
+// the host (lbm_wall_shape.hpp).  cell_row[ny][nx] of one lattice (x fastest): -1, or the cell's row; ad[rows][16] in the lattice type:
+// slot k - 1 holds a, slot 8 + k - 1 holds d of the cell's link k; near[rows]: bit k - 1 set where link k interpolates with the next fluid
+// cell.  Only cells with a link bit read it.
+template <typename R>
+struct ShapeTable {
+    const int32_t* cell_row;
+    const R* ad;
+    const uint8_t* near;
+};
+// The interpolated bounce-back of one link, the one spelling every step kernel, gather and force kernel shares: own = the cell's
+// post-collision population of direction opp(k); other = that of the next fluid cell (near) or the cell's own of direction k (far).
+// Every operation in the lattice type, rounded in the order written.  a == 1 (the wall half-way) selects: no multiply by zero.
+template <typename R>
+__device__ __forceinline__ R shape_rule(R own, R other, R a, R d) {
+    if (a == (R)1) return own + d;
+    const R t1 = a * own, b = (R)1 - a, t2 = b * other;
+    return (t1 + t2) + d;
+}
+
 // Gather the post-stream, post-wall-rule populations of cell (x, y) from a lattice that
 // holds post-collision values (+ kept slots + parked wall densities); raw != 0: the lattice
 // holds plain populations (state just set by the host), nothing to stream.  PROM: the wall rules' equilibrium in the promoted form.
@@ -503,9 +523,11 @@ __device__ __forceinline__ int link_word(const R* __restrict__ src, const AS& as
     else return (int)src[K_LINK * as.plane + as.at(x, y)];
 }
 
-template <typename R, int SEM, typename AS, bool PROM = false>
+// SHAPE (SEM_SOLID on a lattice in memory, while lbm_set_solid_shape holds a shape; off everywhere else): a link takes shape_rule of the
+// cell's table row instead of the plain bounce.
+template <typename R, int SEM, typename AS, bool PROM = false, bool SHAPE = false>
 __device__ __forceinline__ void gather_a(const R* __restrict__ src, const AS& as, const Geo& geo, int raw, R uLB, int x, int y, R (&g)[Q],
-                                         const R* __restrict__ lnk = nullptr) {
+                                         const R* __restrict__ lnk = nullptr, ShapeTable<R> sh = ShapeTable<R>{}) {
     const int gy = geo.y0 + y;
     int lw = 0;
     if (SEM == SEM_SOLID) {
@@ -529,6 +551,22 @@ __device__ __forceinline__ void gather_a(const R* __restrict__ src, const AS& as
 #pragma unroll
         for (int k = 1; k < Q; ++k)
             if ((lw >> (k - 1)) & 1) g[k] = src[opp(k) * as.plane + as.at(x, y)];
+        if constexpr (SHAPE) {
+            // the plain bounce above is `own`; a near link's `other` is the regular pull of slot opp(k) (its source N is a fluid cell
+            // inside the lattice), a far link's the cell's own stored slot k: one load from either place
+            const int row = sh.cell_row[(long long)y * geo.nx + x];
+            if (row >= 0) {
+                const R* const ad = sh.ad + (long long)row * 16;
+                const unsigned nm = sh.near[row];
+#pragma unroll
+                for (int k = 1; k < Q; ++k)
+                    if ((lw >> (k - 1)) & 1) {
+                        const bool near = (nm >> (k - 1)) & 1u;
+                        const R other = src[near ? opp(k) * as.plane + as.at(x + cxk(k), y - cyk(k)) : k * as.plane + as.at(x, y)];
+                        g[k] = shape_rule<R>(g[k], other, ad[k - 1], ad[8 + k - 1]);
+                    }
+            }
+        }
     }
     if (sem_is_bb(SEM)) {
         // a source outside [0, nx) x [0, NY): the cell's own post-collision population of the opposite direction; beyond the lid
@@ -565,15 +603,18 @@ __device__ __forceinline__ void gather(const R* __restrict__ src, const Geo& geo
 // MOVE (SEM_SOLID on a lattice in memory, k_step_generic_move of lbm_solid_move.hpp; off everywhere else): the bodies' surfaces move.  A
 // cell with links adds the delta of link k (cell_row / delta: the per-cell table of lbm_wall_motion.hpp) to its post-collision
 // population of direction opp(k) before it stores it, one add in the lattice type; no gather changes.
-template <typename R, int COLL, int SEM, bool TURB, typename AS, typename AD, bool MOVE = false>
+// SHAPE (k_step_generic_shape of lbm_solid_shape.hpp; off everywhere else): the gather applies shape_rule on the links, the stores are
+// the pure post-collision values.
+template <typename R, int COLL, int SEM, bool TURB, typename AS, typename AD, bool MOVE = false, bool SHAPE = false>
 __device__ __forceinline__ void update_cell_a(const R* __restrict__ src, const AS& as, R* __restrict__ dst, const AD& ad, const Geo& geo,
                                               const Relax<R>& w0, int raw, int x, int y, const R* __restrict__ lnk = nullptr,
-                                              const int32_t* __restrict__ cell_row = nullptr, const R* __restrict__ delta = nullptr) {
+                                              const int32_t* __restrict__ cell_row = nullptr, const R* __restrict__ delta = nullptr,
+                                              ShapeTable<R> sh = ShapeTable<R>{}) {
     // lnk (SEM_SOLID with an LDS window as the source): plane K_LINK of the lattice, see link_word
     const int X = geo.nx, Y = geo.NY, gy = geo.y0 + y;
     if (SEM == SEM_SOLID && (link_word<R, AS>(src, as, geo, lnk, x, y) & LINK_SOLID)) return;   // a solid cell is never updated
     R g[Q];
-    gather_a<R, SEM, AS, coll_is_prom(COLL)>(src, as, geo, raw, w0.uLB, x, y, g, lnk);
+    gather_a<R, SEM, AS, coll_is_prom(COLL), SHAPE>(src, as, geo, raw, w0.uLB, x, y, g, lnk, sh);
     // kept slots: a slot outside its streaming window keeps its value; park it where the
     // next pull of this cell will look for it.
     const bool near_edge = (x <= 0) || (x >= X - 2) || (gy <= 0) || (gy >= Y - 2);

@@ -12,16 +12,33 @@ __device__ __forceinline__ double as_exported(R v, int host_f32) { return host_f
 
 // The view.  src holds post-collision values (+ kept slots + parked wall densities), or plain populations where raw != 0; SEM, PROM:
 // those of the context's Variant.  x: column, y: local row.  By value in the kernel arguments.
-template <typename R, int SEM, bool PROM>
-struct Fields {
+// SHAPE (SEM_SOLID while lbm_set_solid_shape holds a shape; the default, off, is the view as it always was, member for member): the
+// table of the interpolated bounce-back, which the gather then applies on the links -- so every reader sees the rule through this view.
+template <typename R, bool SHAPE>
+struct FieldsShape {};
+template <typename R>
+struct FieldsShape<R, true> {
+    ShapeTable<R> sh;
+};
+template <typename R, int SEM, bool PROM, bool SHAPE = false>
+struct Fields : FieldsShape<R, SHAPE> {
+    static constexpr bool SHAPED = SHAPE;
     const R* src;
     Geo geo;
     int raw;
     R uLB;
     long long bstride;   // elements from one lattice of a batch to the next
-    __device__ __forceinline__ Fields lattice(unsigned z) const { return Fields{src + z * bstride, geo, raw, uLB, bstride}; }
+    __device__ __forceinline__ Fields lattice(unsigned z) const {
+        Fields f = *this;
+        f.src = src + z * bstride;
+        if constexpr (SHAPE) f.sh.cell_row += (long long)z * geo.nx * geo.ny;
+        return f;
+    }
     // the populations after streaming and the wall rules (the link plane of a solid mask, the promoted wall equilibrium)
-    __device__ __forceinline__ void populations(int x, int y, R (&g)[Q]) const { gather<R, SEM, PROM>(src, geo, raw, uLB, x, y, g); }
+    __device__ __forceinline__ void populations(int x, int y, R (&g)[Q]) const {
+        if constexpr (SHAPE) gather_a<R, SEM, Geo, PROM, true>(src, geo, geo, raw, uLB, x, y, g, nullptr, this->sh);
+        else gather<R, SEM, PROM>(src, geo, raw, uLB, x, y, g);
+    }
     // ... and their moments with the wall overrides, which go by the global row
     __device__ __forceinline__ void macro(int x, int y, R& ux, R& uy, R& rho) const {
         R g[Q];
@@ -36,8 +53,8 @@ struct Fields {
 };
 
 // lattice -> staging: current populations (post stream + wall rules) in host layout
-template <typename R, int SEM, bool PROM>
-__global__ __launch_bounds__(BLK) void k_export_fin(Fields<R, SEM, PROM> f, R* __restrict__ stage) {
+template <typename R, int SEM, bool PROM, bool SHAPE = false>
+__global__ __launch_bounds__(BLK) void k_export_fin(Fields<R, SEM, PROM, SHAPE> f, R* __restrict__ stage) {
     const Geo& geo = f.geo;
     constexpr int TRX = trx<R>(), RY = BLK / TRX;
     __shared__ R t[Q][TRX][33];
@@ -65,8 +82,8 @@ __global__ __launch_bounds__(BLK) void k_export_fin(Fields<R, SEM, PROM> f, R* _
 
 // lattice -> staging: the macroscopic fields of the view (with wall overrides; SEM_BB: none); stage = [ux | uy | rho], each
 // [nx][ny_local]
-template <typename R, int SEM, bool PROM>
-__global__ __launch_bounds__(BLK) void k_export_macro(Fields<R, SEM, PROM> f, R* __restrict__ stage) {
+template <typename R, int SEM, bool PROM, bool SHAPE = false>
+__global__ __launch_bounds__(BLK) void k_export_macro(Fields<R, SEM, PROM, SHAPE> f, R* __restrict__ stage) {
     const Geo& geo = f.geo;
     constexpr int TRX = trx<R>(), RY = BLK / TRX;
     __shared__ R t[3][TRX][33];
@@ -127,8 +144,8 @@ __global__ __launch_bounds__(BLK) void k_export_tau(Fields<R, SEM_GPU, PROM> f, 
 // Sum over the slab of ux + uy of the view's macroscopic state (what k_export_macro would write), in double:
 // partial[blockIdx.z * gridDim.x + blockIdx.x] = the block's sum; k_reduce_final adds the partial sums of each lattice in
 // index order -- a fixed summation tree, so the result does not vary from run to run.
-template <typename R, int SEM, bool PROM>
-__global__ __launch_bounds__(BLK) void k_reduce_u(Fields<R, SEM, PROM> f, double* __restrict__ partial) {
+template <typename R, int SEM, bool PROM, bool SHAPE = false>
+__global__ __launch_bounds__(BLK) void k_reduce_u(Fields<R, SEM, PROM, SHAPE> f, double* __restrict__ partial) {
     __shared__ double red[BLK];
     const Geo& geo = f.geo;
     const auto lat = f.lattice(blockIdx.z);
@@ -156,8 +173,8 @@ __global__ __launch_bounds__(BLK) void k_reduce_u(Fields<R, SEM, PROM> f, double
 // coalesced along x.  Contraction off: each product is rounded in double, then added -- the same operations, in the same order, as
 // the host loop  acc += u.astype(f64); acc2 += u64 * u64  over lbm_get_fields.  One thread owns a cell: no atomics, samples add in
 // the order they are enqueued.  Pure streaming: 9 * sizeof(R) + 48 B read and 48 B written per cell.
-template <typename R, int SEM, bool PROM>
-__global__ __launch_bounds__(BLK) void k_stats_accumulate(Fields<R, SEM, PROM> f, double* __restrict__ acc) {
+template <typename R, int SEM, bool PROM, bool SHAPE = false>
+__global__ __launch_bounds__(BLK) void k_stats_accumulate(Fields<R, SEM, PROM, SHAPE> f, double* __restrict__ acc) {
 #pragma clang fp contract(off)
     typedef double d2 __attribute__((ext_vector_type(2)));
     const Geo& geo = f.geo;

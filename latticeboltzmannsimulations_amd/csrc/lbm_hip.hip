@@ -111,7 +111,9 @@ int export_fin(lbm_ctx* c) {
     return launch_variant(c, [&](auto v) {
         using VT = decltype(v);
         using R = typename VT::R;
-        hipLaunchKernelGGL((k_export_fin<R, VT::SEM, coll_is_prom(VT::COLL)>), grid_tiles<R>(c), dim3(BLK), 0, c->s_compute, fields_of<VT>(c, c->cur), c->stage.as<R>());
+        with_fields<VT>(c, c->cur, [&](auto f) {
+            hipLaunchKernelGGL((k_export_fin<R, VT::SEM, coll_is_prom(VT::COLL), decltype(f)::SHAPED>), grid_tiles<R>(c), dim3(BLK), 0, c->s_compute, f, c->stage.as<R>());
+        });
     });
 }
 
@@ -120,7 +122,9 @@ int export_macro(lbm_ctx* c, int which) {
     return launch_variant(c, [&](auto v) {
         using VT = decltype(v);
         using R = typename VT::R;
-        hipLaunchKernelGGL((k_export_macro<R, VT::SEM, coll_is_prom(VT::COLL)>), grid_tiles<R>(c), dim3(BLK), 0, c->s_compute, fields_of<VT>(c, which), c->stage.as<R>());
+        with_fields<VT>(c, which, [&](auto f) {
+            hipLaunchKernelGGL((k_export_macro<R, VT::SEM, coll_is_prom(VT::COLL), decltype(f)::SHAPED>), grid_tiles<R>(c), dim3(BLK), 0, c->s_compute, f, c->stage.as<R>());
+        });
     });
 }
 
@@ -141,8 +145,10 @@ int reduce_u(lbm_ctx* c, int which) {
     return launch_variant(c, [&](auto v) {
         using VT = decltype(v);
         using R = typename VT::R;
-        hipLaunchKernelGGL((k_reduce_u<R, VT::SEM, coll_is_prom(VT::COLL)>), dim3(RED_BLOCKS, 1, c->plan.batch), dim3(BLK), 0, c->s_compute,
-                           fields_of<VT>(c, which), c->red_dev.as<double>());
+        with_fields<VT>(c, which, [&](auto f) {
+            hipLaunchKernelGGL((k_reduce_u<R, VT::SEM, coll_is_prom(VT::COLL), decltype(f)::SHAPED>), dim3(RED_BLOCKS, 1, c->plan.batch), dim3(BLK), 0,
+                               c->s_compute, f, c->red_dev.as<double>());
+        });
     });
 }
 

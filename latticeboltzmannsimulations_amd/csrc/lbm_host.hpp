@@ -15,6 +15,7 @@
 //   lbm_bodies.hip  the one writer of the obstacle state (struct Obstacles); the bodies of a mask: force and torque on each, one-shot
 //                   and as a series                                                          (C ABI: set_solid_bodies, get_solid_bodies, body_force, force_*)
 //   lbm_body_motion.hip the wall velocity of moving bodies: its tables                         (C ABI: set_body_motion, get_body_motion)
+//   lbm_body_shape.hip  curved obstacle surfaces, a wall distance per link: its tables         (C ABI: set_solid_shape, get_solid_shape)
 // one header of device code that the step units never see:
 //   lbm_fields.hpp  the exported state ("what lbm_get_fields would return"): the view Fields that every reader kernel takes -- built
 //                   on the host by fields_of below alone -- and the kernels of the field export, lbm_mean_u and the statistics
@@ -23,6 +24,7 @@
 //   lbm_devmem.hpp   the owner of a device allocation, and several tables uploaded into one (the device: HipMem below)
 //   lbm_bodies.hpp   the labels of a mask's bodies, their centroids, the link list and its chunks; the tables of a batch
 //   lbm_wall_motion.hpp the moving-wall term of every link, the flux check; the tables of a batch
+//   lbm_wall_shape.hpp the interpolated bounce-back of every link from its wall distance; the tables of a batch
 //   lbm_order.hpp    the ordering of the two streams: the state carried between units, the skeletons of a unit, the argument
 #pragma once
 #include <hip/hip_runtime.h>
@@ -46,6 +48,7 @@
 #include "lbm_bodies.hpp"
 #include "lbm_solid.hpp"  // k_step_solid, extern (compiled in lbm_solid_f32/f64.hip)
 #include "lbm_solid_move.hpp"  // k_step_solid_move, k_step_generic_move, extern (compiled in lbm_solid_move_f32/f64.hip)
+#include "lbm_solid_shape.hpp"  // k_step_solid_shape, k_step_generic_shape, extern (compiled in lbm_solid_shape_f32/f64.hip)
 #include "lbm_fields.hpp" // the view of the exported state and the kernels of the field export
 #include "lbm_inst.hpp"   // the kernels, and extern template declarations of the multi-step ones (compiled in lbm_{tiles,stream*}_f32/f64.hip)
 
@@ -147,6 +150,21 @@ struct MotionTables {
     const double* link_delta = nullptr;
 };
 
+// The tables of a shape on the device (shape_tables, lbm_body_shape.hip), all inside the one allocation `base`, laid out by
+// lbmhost::ShapeParts (lbm_wall_shape.hpp): cell_row[batch][ny][nx], -1 or the cell's row in ad[rows][16] (the lattice type; a and d of
+// the cell's eight links) and near[rows]; link_q, one double per entry of BodyTables::links: the effective q, for the wall point of the
+// torque.  The moving-wall term of a shaped context is the d of these tables: they are rebuilt by every call that changes the labels,
+// the centres or the motion, and MotionTables stays empty.
+struct ShapeTables {
+    DevBuf base;
+    const int32_t* cell_row = nullptr;
+    const void* ad = nullptr;
+    const uint8_t* near = nullptr;
+    const double* link_q = nullptr;
+    template <typename R>
+    ShapeTable<R> table() const { return ShapeTable<R>{cell_row, (const R*)ad, near}; }
+};
+
 // Solid obstacles (LBM_SEM_BOUNCE_BACK_SOLID; empty in the other semantics).  Three levels of host state, each with what the device
 // holds of it; obstacles_change (lbm_bodies.hip) is the only writer: a change at one level resets the levels below it.
 //   mask    as lbm_set_solid stored it, 0 / 1, [batch][nx][ny] (all fluid in a fresh context); its link plane lives in the lattices
@@ -154,8 +172,11 @@ struct MotionTables {
 //           lbm_create and lbm_set_solid.  body: the tables; force_series: the records of lbm_force_begin, [capacity][batch][nbodies]
 //   motion  motion[batch][nbodies][3] = (Ux, Uy, Om), all zero after lbm_create, lbm_set_solid and lbm_set_solid_bodies.  moving: the
 //           tables, empty while every body is at rest -- then the step and the force run the kernels of obstacles that never move
+//   shape   beside the motion, not below it: shape_q[batch][8][nx][ny] as lbm_set_solid_shape took it (empty without a shape), shape_eff
+//           the effective q (what lbm_get_solid_shape returns), shaped: the tables.  A new mask drops the shape; new bodies and a new
+//           motion rebuild the tables from shape_q; the shape itself changes only while every body is at rest.
 // force_part: the workgroups' partial results of lbm_solid_force and, behind them, its records (allocated on first use, kept).
-enum class ObsLevel { mask, bodies, motion };
+enum class ObsLevel { mask, bodies, motion, shape };
 struct Obstacles {
     std::vector<uint8_t> mask;
     int nbodies = 1;
@@ -165,6 +186,8 @@ struct Obstacles {
     Series force_series;
     std::vector<double> motion;
     MotionTables moving;
+    std::vector<double> shape_q, shape_eff;
+    ShapeTables shaped;
     DevBuf force_part;
 };
 
@@ -359,10 +382,29 @@ void dispatch(const lbm_params& p, F&& f) {
 // The view of lat[which] for the kernels that read the exported state (VT: the context's Variant): the one place outside the step
 // launchers that pairs a lattice with its raw flag, the lid velocity and the batch stride.  which: reader_source's for what
 // lbm_get_fields exports now; c->cur for the sample of the iteration about to start (sample_if_due) and for the populations.
-template <typename VT>
-Fields<typename VT::R, VT::SEM, coll_is_prom(VT::COLL)> fields_of(const lbm_ctx* c, int which) {
+template <typename VT, bool SHAPE = false>
+Fields<typename VT::R, VT::SEM, coll_is_prom(VT::COLL), SHAPE> fields_of(const lbm_ctx* c, int which) {
     using R = typename VT::R;
-    return {c->lat[which].as<const R>(), c->plan.geo, c->raw[which], (R)c->p.uLB, c->plan.bstride};
+    Fields<R, VT::SEM, coll_is_prom(VT::COLL), SHAPE> f;
+    f.src = c->lat[which].as<const R>();
+    f.geo = c->plan.geo;
+    f.raw = c->raw[which];
+    f.uLB = (R)c->p.uLB;
+    f.bstride = c->plan.bstride;
+    if constexpr (SHAPE) f.sh = c->obs.shaped.template table<R>();
+    return f;
+}
+// ... and what every launcher of a reader kernel goes through: launch(view), the view with the shape table compiled in while a shape
+// is set (lbm_set_solid_shape), the plain one otherwise.  The kernel takes decltype(view)::SHAPED as its last template argument.
+template <typename VT, typename F>
+void with_fields(const lbm_ctx* c, int which, F&& launch) {
+    if constexpr (VT::SEM == SEM_SOLID) {
+        if (c->obs.shaped.base) {
+            launch(fields_of<VT, true>(c, which));
+            return;
+        }
+    }
+    launch(fields_of<VT, false>(c, which));
 }
 // A launcher's body: f(Variant) enqueues the kernels of the context's variant, then the launch error check
 template <typename F>
@@ -484,7 +526,9 @@ int solid_copy_links(lbm_ctx* c, int to);
 int obstacles_change(lbm_ctx* c, ObsLevel level, Obstacles& next, int (*before_commit)(lbm_ctx*, const Obstacles&) = nullptr);
 int force_series_sample(lbm_ctx* c);
 // lbm_body_motion.hip
-int motion_tables(lbm_ctx* c, const Obstacles& next, MotionTables& out);
+int motion_tables(lbm_ctx* c, const Obstacles& next, MotionTables& out, bool check_only = false);
+// lbm_body_shape.hip
+int shape_tables(lbm_ctx* c, const Obstacles& next, const std::vector<double>& q, ShapeTables& out, std::vector<double>* q_eff);
 // lbm_residual.hip
 int residual_series_sample(lbm_ctx* c, int which, long long step);
 void residual_free(lbm_ctx* c);

@@ -47,10 +47,22 @@ int launch_rows(lbm_ctx* c, int from, int to, int row0, int stride, int nrows, h
             const MotionTables& m = c->obs.moving;
             const bool moving = (bool)m.base;
             const R* delta = (const R*)m.delta;
+            // (a shape, lbm_set_solid_shape: the same two routes with the interpolated bounce-back in their gathers, the motion's term
+            // in its table; never together with the store-side add)
+            const bool shaped = (bool)c->obs.shaped.base;
+            const ShapeTable<R> sh = c->obs.shaped.template table<R>();
+            if (shaped && !c->plan.use_vec) {
+                hipLaunchKernelGGL((k_step_generic_shape<R, VT::COLL>), grid_rows(c, nrows), dim3(BLK), 0, s, src, dst, c->plan.geo, relax_of<R>(c->p),
+                                   batch_of<R>(c), raw, row0, stride, sh);
+                return;
+            }
             if (c->plan.use_vec) {   // (nx a multiple of the vector width, kernel = AUTO: plan_kernel)
                 by_nt([&](auto nt) {
                     constexpr bool NT = decltype(nt)::value;
-                    if (moving)
+                    if (shaped)
+                        hipLaunchKernelGGL((k_step_solid_shape<R, VT::COLL, NT>), gvec, dim3(BLK), 0, s, src, dst, c->plan.geo, relax_of<R>(c->p),
+                                           batch_of<R>(c), raw, row0, stride, nxb, nblocks, sh);
+                    else if (moving)
                         hipLaunchKernelGGL((k_step_solid_move<R, VT::COLL, NT>), gvec, dim3(BLK), 0, s, src, dst, c->plan.geo, relax_of<R>(c->p),
                                            batch_of<R>(c), raw, row0, stride, nxb, nblocks, m.cell_row, delta);
                     else

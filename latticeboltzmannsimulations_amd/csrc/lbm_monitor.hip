@@ -62,10 +62,13 @@ static int monitor_enqueue(lbm_ctx* c, int which, const lbm_monitor_spec& spec, 
     return launch_variant(c, [&](auto v) {
         using VT = decltype(v);
         using R = typename VT::R;
-        hipLaunchKernelGGL((k_monitor<R, VT::SEM, coll_is_prom(VT::COLL)>), dim3(blocks, 1, c->plan.batch), dim3(BLK), 0, c->s_compute,
-                           fields_of<VT>(c, which), den, sp, c->mon_part.as<double>());
-        hipLaunchKernelGGL((k_monitor_final<R, VT::SEM, coll_is_prom(VT::COLL)>), dim3(c->plan.batch), dim3(RED_WAVE), 0, c->s_compute,
-                           c->mon_part.as<const double>(), blocks, fields_of<VT>(c, which), sp, (double)step, (double*)rec);
+        with_fields<VT>(c, which, [&](auto f) {
+            constexpr bool SH = decltype(f)::SHAPED;
+            hipLaunchKernelGGL((k_monitor<R, VT::SEM, coll_is_prom(VT::COLL), SH>), dim3(blocks, 1, c->plan.batch), dim3(BLK), 0, c->s_compute, f, den, sp,
+                               c->mon_part.as<double>());
+            hipLaunchKernelGGL((k_monitor_final<R, VT::SEM, coll_is_prom(VT::COLL), SH>), dim3(c->plan.batch), dim3(RED_WAVE), 0, c->s_compute,
+                               c->mon_part.as<const double>(), blocks, f, sp, (double)step, (double*)rec);
+        });
     });
 }
 
@@ -137,8 +140,10 @@ int lbm_get_lines(lbm_ctx* c, int x, int gy, void* col_out, void* row_out, int h
     rc = launch_variant(c, [&](auto v) {
         using VT = decltype(v);
         using R = typename VT::R;
-        hipLaunchKernelGGL((k_export_lines<R, VT::SEM, coll_is_prom(VT::COLL)>), dim3((ny + nx + BLK - 1) / BLK, 1, B), dim3(BLK), 0, c->s_compute,
-                           fields_of<VT>(c, which), cx, ly, c->stage.as<R>());
+        with_fields<VT>(c, which, [&](auto f) {
+            hipLaunchKernelGGL((k_export_lines<R, VT::SEM, coll_is_prom(VT::COLL), decltype(f)::SHAPED>), dim3((ny + nx + BLK - 1) / BLK, 1, B), dim3(BLK), 0,
+                               c->s_compute, f, cx, ly, c->stage.as<R>());
+        });
     });
     if (rc) return rc;
     std::vector<char> tmp(per * B * c->plan.es);

@@ -60,8 +60,8 @@ __device__ __forceinline__ void MonAcc::fold(MonAcc& a, const MonAcc& b) { mon_f
 // The fused monitor pass: grid-stride over the cells of one lattice (blockIdx.z: lattice of the batch), x fastest; per cell the
 // exported values of the view.  The tree of lbm_reduce.hpp leaves one partial result per workgroup:
 // partial[(blockIdx.z * gridDim.x + blockIdx.x) * MON_VALS ...].  Reads the nine planes once, like k_reduce_u.
-template <typename R, int SEM, bool PROM>
-__global__ __launch_bounds__(BLK) void k_monitor(Fields<R, SEM, PROM> f, double den, MonSpec sp, double* __restrict__ partial) {
+template <typename R, int SEM, bool PROM, bool SHAPE = false>
+__global__ __launch_bounds__(BLK) void k_monitor(Fields<R, SEM, PROM, SHAPE> f, double den, MonSpec sp, double* __restrict__ partial) {
 #pragma clang fp contract(off)
     __shared__ double sh[BLK / RED_WAVE][MON_VALS];
     const Geo& geo = f.geo;
@@ -95,8 +95,8 @@ __global__ __launch_bounds__(BLK) void k_monitor(Fields<R, SEM, PROM> f, double 
 
 // The final pass, one wave per lattice (red_final): lane 0 writes the record; lanes 0 .. 7 evaluate the probe cells (the exported
 // values of the one cell).  rec: the records of this sample, [batch].
-template <typename R, int SEM, bool PROM>
-__global__ __launch_bounds__(RED_WAVE) void k_monitor_final(const double* __restrict__ partial, int nper, Fields<R, SEM, PROM> f, MonSpec sp, double step,
+template <typename R, int SEM, bool PROM, bool SHAPE = false>
+__global__ __launch_bounds__(RED_WAVE) void k_monitor_final(const double* __restrict__ partial, int nper, Fields<R, SEM, PROM, SHAPE> f, MonSpec sp, double step,
                                                             double* __restrict__ rec) {
     const int z = blockIdx.x, lane = threadIdx.x;
     rec += (size_t)z * MON_REC;
@@ -118,8 +118,8 @@ __global__ __launch_bounds__(RED_WAVE) void k_monitor_final(const double* __rest
 
 // Column x (all local rows) and local row ly (ly < 0: none) of the exported state, in host layout:
 // stage of lattice z = [ux | uy | rho][ny] of the column, then [ux | uy | rho][nx] of the row.  One thread per cell of either line.
-template <typename R, int SEM, bool PROM>
-__global__ __launch_bounds__(BLK) void k_export_lines(Fields<R, SEM, PROM> f, int cx, int ly, R* __restrict__ stage) {
+template <typename R, int SEM, bool PROM, bool SHAPE = false>
+__global__ __launch_bounds__(BLK) void k_export_lines(Fields<R, SEM, PROM, SHAPE> f, int cx, int ly, R* __restrict__ stage) {
     const Geo& geo = f.geo;
     stage += (size_t)blockIdx.z * 3 * (geo.ny + geo.nx);
     const int t = blockIdx.x * BLK + threadIdx.x;

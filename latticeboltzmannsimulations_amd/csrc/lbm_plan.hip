@@ -531,11 +531,17 @@ int lbm_describe(const lbm_ctx* c, char* buf, size_t len) {
     if (!c || !buf || len == 0) return LBM_ERR_INVALID;
     int nlat = 0;
     for (int i = 0; i < NLAT; ++i) nlat += c->lat[i] ? 1 : 0;
-    const int n = describe_plan(c->plan, nlat, buf, len);
-    if (n < 0 || !c->obs.moving.base) return n;
-    // (a nonzero lbm_set_body_motion: the single steps run k_step_solid_move / k_step_generic_move)
-    const int m = std::snprintf(buf + n, len - (size_t)n, " wall_motion=1");
-    return m < 0 ? n : std::min<int>(n + m, (int)len - 1);
+    int n = describe_plan(c->plan, nlat, buf, len);
+    if (n < 0) return n;
+    // (a nonzero lbm_set_body_motion: the single steps run k_step_solid_move / k_step_generic_move; a shape, lbm_set_solid_shape:
+    // k_step_solid_shape / k_step_generic_shape, whose table holds the motion's term too)
+    const bool shaped = (bool)c->obs.shaped.base;
+    const bool moving = c->obs.moving.base || (shaped && std::any_of(c->obs.motion.begin(), c->obs.motion.end(), [](double v) { return v != 0.0; }));
+    for (const char* word : {moving ? " wall_motion=1" : "", shaped ? " wall_shape=1" : ""}) {
+        const int m = std::snprintf(buf + n, len - (size_t)n, "%s", word);
+        if (m > 0) n = std::min<int>(n + m, (int)len - 1);
+    }
+    return n;
 }
 
 // Dry run of the launch plan: what lbm_create(p) would plan and which launch units lbm_step(steps) would then run from a fresh

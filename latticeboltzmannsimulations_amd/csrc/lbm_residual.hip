@@ -31,13 +31,17 @@ int residual_series_sample(lbm_ctx* c, int which, long long step) {
         const dim3 grid(blocks, 1, c->plan.batch);
         if constexpr (std::is_same<R, double>::value) {
             if (!snap_is_f32(c)) {
-                hipLaunchKernelGGL((k_residual<double, double, VT::SEM, PROM>), grid, dim3(BLK), 0, c->s_compute, fields_of<VT>(c, which),
-                                   c->res_snap.as<double>(), c->res_part.as<double>());
+                with_fields<VT>(c, which, [&](auto f) {
+                    hipLaunchKernelGGL((k_residual<double, double, VT::SEM, PROM, decltype(f)::SHAPED>), grid, dim3(BLK), 0, c->s_compute, f,
+                                       c->res_snap.as<double>(), c->res_part.as<double>());
+                });
                 return;
             }
         }
-        hipLaunchKernelGGL((k_residual<R, float, VT::SEM, PROM>), grid, dim3(BLK), 0, c->s_compute, fields_of<VT>(c, which),
-                           c->res_snap.as<float>(), c->res_part.as<double>());
+        with_fields<VT>(c, which, [&](auto f) {
+            hipLaunchKernelGGL((k_residual<R, float, VT::SEM, PROM, decltype(f)::SHAPED>), grid, dim3(BLK), 0, c->s_compute, f, c->res_snap.as<float>(),
+                               c->res_part.as<double>());
+        });
     });
     if (rc) return rc;
     const long long prev = c->res_prev;

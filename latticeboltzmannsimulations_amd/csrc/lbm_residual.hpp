@@ -61,8 +61,8 @@ struct ResGroup {
 // state of the view.  Reads the snapshot, writes the current sample over it, reduces; one partial result per workgroup:
 // partial[(blockIdx.z * gridDim.x + blockIdx.x) * RES_VALS ...].  No atomics.  Pure streaming: 9 sizeof(R) + 3 sizeof(S) read and
 // 3 sizeof(S) written per cell.
-template <typename R, typename S, int SEM, bool PROM>
-__global__ __launch_bounds__(BLK) void k_residual(Fields<R, SEM, PROM> f, S* __restrict__ snap, double* __restrict__ partial) {
+template <typename R, typename S, int SEM, bool PROM, bool SHAPE = false>
+__global__ __launch_bounds__(BLK) void k_residual(Fields<R, SEM, PROM, SHAPE> f, S* __restrict__ snap, double* __restrict__ partial) {
 #pragma clang fp contract(off)
     constexpr int CPL = ResGroup<S>::CPL;
     typedef typename ResGroup<S>::vec vec;

@@ -56,8 +56,10 @@ static int stats_accumulate(lbm_ctx* c, int which) {
     const int rc = launch_variant(c, [&](auto v) {
         using VT = decltype(v);
         using R = typename VT::R;
-        hipLaunchKernelGGL((k_stats_accumulate<R, VT::SEM, coll_is_prom(VT::COLL)>), dim3(blocks, 1, c->plan.batch), dim3(BLK), 0, c->s_compute,
-                           fields_of<VT>(c, which), c->stats_dev.as<double>());
+        with_fields<VT>(c, which, [&](auto f) {
+            hipLaunchKernelGGL((k_stats_accumulate<R, VT::SEM, coll_is_prom(VT::COLL), decltype(f)::SHAPED>), dim3(blocks, 1, c->plan.batch), dim3(BLK), 0,
+                               c->s_compute, f, c->stats_dev.as<double>());
+        });
     });
     if (rc) return rc;
     ++c->stats_count;

@@ -91,6 +91,43 @@ __global__ __launch_bounds__(BLK) void k_solid_force_move(const R* __restrict__ 
     solid_force_cells<R, true>(src, geo, bstride, partial, cell_row, delta);
 }
 
+// A shape is set (lbm_set_solid_shape): per link f_out = the cell's post-collision population of direction opp(k) as the lattice holds it
+// (its stores carry no term) and f_in = shape_rule, what the next gather of the cell returns as slot k; both converted to double, the
+// term of the link c_opp(k) (f_out + f_in).  Cells, slots and tree as k_solid_force.
+template <typename R>
+__global__ __launch_bounds__(BLK) void k_solid_force_shape(const R* __restrict__ src, Geo geo, long long bstride, double* __restrict__ partial,
+                                                           ShapeTable<R> sh) {
+#pragma clang fp contract(off)
+    __shared__ double shm[BLK / RED_WAVE][ForceAcc::VALS];
+    src += blockIdx.z * bstride;
+    const long long n = (long long)geo.nx * geo.ny;
+    sh.cell_row += blockIdx.z * n;
+    ForceAcc a = ForceAcc::identity();
+    for (long long i = (long long)blockIdx.x * BLK + threadIdx.x; i < n; i += (long long)gridDim.x * BLK) {
+        const int y = (int)(i / geo.nx), x = (int)(i - (long long)y * geo.nx);
+        const long long me = geo.at(x, y);
+        const int lw = (int)src[K_LINK * geo.plane + me];
+        if ((lw & LINK_SOLID) || !(lw & 255)) continue;
+        const long long row = sh.cell_row[i];
+#pragma unroll
+        for (int k = 1; k < Q; ++k)
+            if ((lw >> (k - 1)) & 1) {
+                const R own = src[opp(k) * geo.plane + me];
+                R g = own;
+                if (row >= 0) {
+                    const R other = ((sh.near[row] >> (k - 1)) & 1) ? src[opp(k) * geo.plane + geo.at(x + cxk(k), y - cyk(k))] : src[k * geo.plane + me];
+                    g = shape_rule<R>(own, other, sh.ad[row * 16 + (k - 1)], sh.ad[row * 16 + 8 + (k - 1)]);
+                }
+                const double t = (double)own + (double)g;
+                a.links = a.links + 1.0;
+                a.fx = a.fx + (double)cxk(opp(k)) * t;
+                a.fy = a.fy + (double)cyk(opp(k)) * t;
+            }
+    }
+    red_wave(a);
+    if (red_workgroup<ForceAcc, BLK / RED_WAVE>(a, shm)) red_store(partial + ((size_t)blockIdx.z * gridDim.x + blockIdx.x) * ForceAcc::VALS, a);
+}
+
 // The final pass, one wave per lattice: rec[z] = {step, links, fx, fy}
 __global__ __launch_bounds__(RED_WAVE) void k_solid_force_final(const double* __restrict__ partial, int nper, double step, double* __restrict__ rec) {
     const int z = blockIdx.x;
@@ -220,7 +257,10 @@ int lbm_solid_force(lbm_ctx* c, lbm_solid_force_record* out) {
     const MotionTables& m = c->obs.moving;
     rc = launch_variant(c, [&](auto v) {
         using R = typename decltype(v)::R;
-        if (m.base)
+        if (c->obs.shaped.base)
+            hipLaunchKernelGGL((k_solid_force_shape<R>), dim3(FORCE_BLOCKS, 1, B), dim3(BLK), 0, c->s_compute, c->lat[c->cur].as<const R>(), c->plan.geo,
+                               c->plan.bstride, part, c->obs.shaped.template table<R>());
+        else if (m.base)
             hipLaunchKernelGGL((k_solid_force_move<R>), dim3(FORCE_BLOCKS, 1, B), dim3(BLK), 0, c->s_compute, c->lat[c->cur].as<const R>(), c->plan.geo,
                                c->plan.bstride, part, m.cell_row, (const R*)m.delta);
         else

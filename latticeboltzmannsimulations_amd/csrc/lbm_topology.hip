@@ -67,19 +67,21 @@ static int topology_enqueue(lbm_ctx* c, int which, const TopoSpec& sp, long long
         using VT = decltype(v);
         using R = typename VT::R;
         constexpr bool PROM = coll_is_prom(VT::COLL);
-        const auto f = fields_of<VT>(c, which);
-        hipLaunchKernelGGL((k_topo_totals<R, VT::SEM, PROM>), tiles, dim3(BLK), 0, c->s_compute, f, sp.host_f32, b.total);
+        with_fields<VT>(c, which, [&](auto f) {
+        constexpr bool SH = decltype(f)::SHAPED;
+        hipLaunchKernelGGL((k_topo_totals<R, VT::SEM, PROM, SH>), tiles, dim3(BLK), 0, c->s_compute, f, sp.host_f32, b.total);
         hipLaunchKernelGGL(k_topo_offsets, dim3((c->plan.geo.ny + BLK - 1) / BLK, 1, c->plan.batch), dim3(BLK), 0, c->s_compute, b.total, g.nb,
                            c->plan.geo.ny, b.close);
         if (psi_out)
-            hipLaunchKernelGGL((k_topo_extrema<R, VT::SEM, PROM, true>), tiles, dim3(BLK), 0, c->s_compute, f, sp, (const double*)b.total, b.partial,
+            hipLaunchKernelGGL((k_topo_extrema<R, VT::SEM, PROM, true, SH>), tiles, dim3(BLK), 0, c->s_compute, f, sp, (const double*)b.total, b.partial,
                                psi_out);
         else
-            hipLaunchKernelGGL((k_topo_extrema<R, VT::SEM, PROM, false>), tiles, dim3(BLK), 0, c->s_compute, f, sp, (const double*)b.total, b.partial,
+            hipLaunchKernelGGL((k_topo_extrema<R, VT::SEM, PROM, false, SH>), tiles, dim3(BLK), 0, c->s_compute, f, sp, (const double*)b.total, b.partial,
                                (double*)nullptr);
         if (with_record)
-            hipLaunchKernelGGL((k_topo_final<R, VT::SEM, PROM>), dim3(LBM_TOPOLOGY_MAX_WINDOWS, c->plan.batch), dim3(BLK), 0, c->s_compute,
+            hipLaunchKernelGGL((k_topo_final<R, VT::SEM, PROM, SH>), dim3(LBM_TOPOLOGY_MAX_WINDOWS, c->plan.batch), dim3(BLK), 0, c->s_compute,
                                (const double*)b.partial, (int)g.nwg(), (const double*)b.close, f, sp, (double)step, (double*)b.rec);
+        });
     });
 }
 
@@ -134,8 +136,10 @@ int lbm_get_stream_function(lbm_ctx* c, double* psi_out, double* omega_out, int 
         rc = launch_variant(c, [&](auto v) {
             using VT = decltype(v);
             using R = typename VT::R;
-            hipLaunchKernelGGL((k_export_macro<R, VT::SEM, coll_is_prom(VT::COLL)>), grid_tiles<R>(c), dim3(BLK), 0, c->s_compute, fields_of<VT>(c, which),
-                               c->stage.as<R>());
+            with_fields<VT>(c, which, [&](auto f) {
+                hipLaunchKernelGGL((k_export_macro<R, VT::SEM, coll_is_prom(VT::COLL), decltype(f)::SHAPED>), grid_tiles<R>(c), dim3(BLK), 0, c->s_compute, f,
+                                   c->stage.as<R>());
+            });
             hipLaunchKernelGGL((k_topo_omega<R>), dim3((unsigned)((n + BLK - 1) / BLK), 1, B), dim3(BLK), 0, c->s_compute, c->stage.as<const R>(), nx, ny,
                                (int)(host_dtype == LBM_F32), omega_dev);
         });

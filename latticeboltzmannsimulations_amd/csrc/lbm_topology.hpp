@@ -115,8 +115,8 @@ __device__ __forceinline__ double topo_tile_scan(double* __restrict__ u, int x0,
 }
 
 // total[(z * nb + b) * ny + y] = the sum of the terms of block b of row y.  Grid (nb, tiles of rows, batch).
-template <typename R, int SEM, bool PROM>
-__global__ __launch_bounds__(BLK) void k_topo_totals(Fields<R, SEM, PROM> f, int host_f32, double* __restrict__ total) {
+template <typename R, int SEM, bool PROM, bool SHAPE = false>
+__global__ __launch_bounds__(BLK) void k_topo_totals(Fields<R, SEM, PROM, SHAPE> f, int host_f32, double* __restrict__ total) {
     __shared__ double u[TOPO_ROWS][TOPO_PITCH];
     const Geo& geo = f.geo;
     const int x0 = blockIdx.x * TOPO_W, ty0 = blockIdx.y * TOPO_ROWS;
@@ -146,8 +146,8 @@ __global__ __launch_bounds__(BLK) void k_topo_offsets(double* __restrict__ total
 // psi of the tile, then per window of the spec the extrema over the tile's cells with a finite psi inside it:
 // partial[((z * MAX_WINDOWS + w) * nwg + wg) * TOPO_PART ...], wg = blockIdx.y * gridDim.x + blockIdx.x.  FIELDS: psi also goes to
 // psi_out[z][nx][ny] (host layout, written along y).
-template <typename R, int SEM, bool PROM, bool FIELDS>
-__global__ __launch_bounds__(BLK) void k_topo_extrema(Fields<R, SEM, PROM> f, TopoSpec sp, const double* __restrict__ offs, double* __restrict__ partial,
+template <typename R, int SEM, bool PROM, bool FIELDS, bool SHAPE = false>
+__global__ __launch_bounds__(BLK) void k_topo_extrema(Fields<R, SEM, PROM, SHAPE> f, TopoSpec sp, const double* __restrict__ offs, double* __restrict__ partial,
                                                      double* __restrict__ psi_out) {
     __shared__ double u[TOPO_ROWS][TOPO_PITCH];
     __shared__ double sh[BLK / RED_WAVE][TOPO_PART];
@@ -202,8 +202,8 @@ __device__ __forceinline__ double topo_omega_at(const F& lat, int host_f32, int 
 // One workgroup per (window blockIdx.x, lattice blockIdx.y): folds the nwg partial results of the window, evaluates omega at the two
 // extrema and writes the window's entry of the record; the workgroup of window 0 also writes step and closure (the maximum of the
 // finite close[y]; -inf when there is none).  Windows beyond the spec's: psi = omega = NaN, cell (-1, -1).
-template <typename R, int SEM, bool PROM>
-__global__ __launch_bounds__(BLK) void k_topo_final(const double* __restrict__ partial, int nwg, const double* __restrict__ close, Fields<R, SEM, PROM> f,
+template <typename R, int SEM, bool PROM, bool SHAPE = false>
+__global__ __launch_bounds__(BLK) void k_topo_final(const double* __restrict__ partial, int nwg, const double* __restrict__ close, Fields<R, SEM, PROM, SHAPE> f,
                                                    TopoSpec sp, double step, double* __restrict__ rec) {
     __shared__ double sh[BLK / RED_WAVE][TOPO_PART + 1];
     const int i = blockIdx.x, z = blockIdx.y, wave = threadIdx.x / RED_WAVE;

@@ -27,7 +27,7 @@ from . import ghia
 from . import residual as RS
 from .VTKWrapper import saveToVTK
 from .monitor import vortex_window
-from .solid import labels_from, mask_from
+from .solid import disc_fractions, discs_into, labels_from, mask_from
 from .solver import CavitySolver
 from .stopping import MeanUStop, ResidualStop, by_residual, wall_model
 
@@ -152,8 +152,16 @@ def _vortex_lines(table, Re, xsize, ysize, uLB):
 
 
 def _check_arguments(criterion, residual_tol, residual_hits, monitor, MonitorEvery, convergence, AverageFrom, AverageEvery, BC, semantics, turb,
-                     solid=None, solid_tiles=False, bodies=None, force_every=None, body_motion=None):
+                     solid=None, solid_tiles=False, bodies=None, force_every=None, body_motion=None, solid_shape=None):
     """(criterion is 'residual', semantics); ValueError for an argument run_cavity cannot run with."""
+    if solid_shape is not None:
+        if solid is None:
+            raise ValueError("solid_shape gives the obstacles of a solid mask their wall distances: it needs solid=... (--solid-disc / --solid-box / --solid-file)")
+        q = np.asarray(solid_shape, dtype=np.float64)
+        if q.shape != (8,) + np.asarray(solid).shape:
+            raise ValueError("solid_shape must be an array [8, xsize, ysize]: q of slot k in plane k - 1")
+        if solid_tiles:
+            raise ValueError("solid_shape needs one step per launch: the tile kernel (solid_tiles) keeps the half-way rule")
     if (bodies is not None or force_every is not None) and solid is None:
         raise ValueError("bodies and force_every describe the obstacles of a solid mask: they need solid=... (--solid-box / --solid-file)")
     if body_motion is not None:
@@ -318,7 +326,7 @@ def run_cavity(maxIt=3000000, Re=10000.0, RT="SRT", turb=1, xsize=32 * 5, ysize=
                dtype=np.float32, semantics="mrt_gpu", device=0, quiet=False, solver_factory=None, arith="strict",
                convergence="host", vtk_correct=False, BC="EB-NEBB ", AverageFrom=None, AverageEvery=100, monitor="host",
                MonitorEvery=None, Probes=(), vortex_table=False, criterion="mean_u", residual_tol=None, residual_hits=1, solid=None,
-               solid_tiles=False, bodies=None, force_every=None, body_motion=None):
+               solid_tiles=False, bodies=None, force_every=None, body_motion=None, solid_shape=None):
     """Run the lid-driven cavity like MRT_GPU.py does; returns a :class:`CavityResult`.
 
     Argument names and defaults are the module constants of MRT_GPU.py:38-58.
@@ -365,9 +373,12 @@ def run_cavity(maxIt=3000000, Re=10000.0, RT="SRT", turb=1, xsize=32 * 5, ysize=
     crosses PCIe before the run ends.  With SavePlot or SaveVTK, OutputFolder/force.npy holds [samples, nbodies, 6]: step, body, links,
     fx, fy, tz.  None (default): nothing changes.
     body_motion (with solid=...): [nbodies, 3] of (Ux, Uy, Omega), the wall velocity on the surface of every body
-    (CavitySolver.set_body_motion) from the first iteration on: the bodies keep their cells.  None (default): obstacles at rest."""
+    (CavitySolver.set_body_motion) from the first iteration on: the bodies keep their cells.  None (default): obstacles at rest.
+    solid_shape (with solid=...): q[8, xsize, ysize], the wall distance of every link (CavitySolver.set_shape; solid.disc_fractions,
+    solid.fractions_from_distance), set before the motion and the first iteration: the links bounce by linear interpolation, second
+    order for curved walls, and the lattice no longer conserves its mass.  None (default): the half-way rule, nothing changes."""
     by_res, semantics = _check_arguments(criterion, residual_tol, residual_hits, monitor, MonitorEvery, convergence, AverageFrom,
-                                         AverageEvery, BC, semantics, turb, solid, solid_tiles, bodies, force_every, body_motion)
+                                         AverageEvery, BC, semantics, turb, solid, solid_tiles, bodies, force_every, body_motion, solid_shape)
     on_device = monitor == "device"
     say = (lambda *a: None) if quiet else print
     tstart = timer()
@@ -383,9 +394,12 @@ def run_cavity(maxIt=3000000, Re=10000.0, RT="SRT", turb=1, xsize=32 * 5, ysize=
         extra["bodies"] = bodies
     solver = make(xsize, ysize, Re, RT=RT, uLB=uLB, semantics=semantics, dtype=dtype, turb=turb, device=device, **extra)
     _banner(say, Re, RT, turb, solver.relax)
-    if body_motion is not None:
+    if solid_shape is not None or body_motion is not None:
         try:
-            solver.set_body_motion(np.asarray(body_motion, dtype=np.float64))
+            if solid_shape is not None:     # (the shape first, then the motion)
+                solver.set_shape(np.asarray(solid_shape, dtype=np.float64))
+            if body_motion is not None:
+                solver.set_body_motion(np.asarray(body_motion, dtype=np.float64))
         except Exception:
             solver.close()
             raise
@@ -518,13 +532,26 @@ def main(argv=None):
                     help="with --solid-box / --solid-file: the surface of body BODY moves with the velocity (UX, UY) and turns with OMEGA radians "
                          "per iteration, counter-clockwise with the lid on top, about the body's centroid; the body keeps its cells (repeatable; "
                          "bodies as for --force-every; not with --solid-tiles)")
+    ap.add_argument("--solid-disc", type=float, nargs=3, action="append", default=[], metavar=("X0", "Y0", "R"),
+                    help="a solid disc: the cells whose centre lies within R of (X0, Y0), index coordinates (repeatable; a body of its own "
+                         "after the boxes and the file; needs --BC BB --turb 0)")
+    ap.add_argument("--curved", action="store_true",
+                    help="with --solid-disc: every link of a disc carries its exact distance to the circle and bounces by linear interpolation "
+                         "(second order; the lattice no longer conserves its mass; not with --solid-tiles)")
     a = ap.parse_args(argv)
-    mask = labels = motion = None
-    if a.solid_box or a.solid_file is not None or a.solid_tiles or a.force_every is not None or a.body_motion:      # an obstacle the run cannot have is an argument error, through the one check
+    mask = labels = motion = shape = None
+    if a.solid_box or a.solid_file is not None or a.solid_tiles or a.force_every is not None or a.body_motion or a.solid_disc or a.curved:      # an obstacle the run cannot have is an argument error, through the one check
         try:
             mask = mask_from(a.xsize, a.ysize, a.solid_box, a.solid_file)
-            if a.force_every is not None or a.body_motion:
+            if a.force_every is not None or a.body_motion or a.solid_disc:
                 labels, nbodies = labels_from(a.xsize, a.ysize, a.solid_box, a.solid_file)[1:]
+            if a.curved and not a.solid_disc:
+                raise ValueError("--curved gives the discs of --solid-disc their exact wall distances: it needs --solid-disc")
+            if a.solid_disc:
+                mask, labels, nbodies = discs_into(a.xsize, a.ysize, a.solid_disc, mask, labels, nbodies)
+                if a.curved:
+                    for x0, y0, R in a.solid_disc:
+                        shape = disc_fractions(mask, x0, y0, R, shape)
             if a.body_motion:
                 motion = np.zeros((max(nbodies, 1), 3))
                 for b, ux, uy, om in a.body_motion:
@@ -532,7 +559,7 @@ def main(argv=None):
                         raise ValueError(f"--body-motion names body {b:g}, the mask has the bodies 0 .. {nbodies - 1}")
                     motion[int(b) if mask is not None else 0] = ux, uy, om
             _check_arguments(a.criterion, a.residual_tol, a.residual_hits, a.monitor, a.monitor_every, a.convergence, a.average_from,
-                             a.average_every, a.BC, a.semantics, a.turb, mask, a.solid_tiles, labels, a.force_every, motion)
+                             a.average_every, a.BC, a.semantics, a.turb, mask, a.solid_tiles, labels, a.force_every, motion, shape)
         except (ValueError, OSError) as e:
             ap.error(str(e))
     r = run_cavity(maxIt=a.maxIt, Re=a.Re, RT=a.RT, turb=a.turb, xsize=a.xsize, ysize=a.ysize, uLB=a.uLB,
@@ -542,7 +569,8 @@ def main(argv=None):
                    AverageFrom=a.average_from, AverageEvery=a.average_every, monitor=a.monitor, MonitorEvery=a.monitor_every,
                    Probes=tuple(tuple(p) for p in a.probe), vortex_table=a.vortex_table, criterion=a.criterion,
                    residual_tol=a.residual_tol, residual_hits=a.residual_hits, solid=mask, **(dict(solid_tiles=True) if a.solid_tiles else {}),
-                   **(dict(bodies=labels) if a.force_every is not None or motion is not None else {}),
+                   **(dict(bodies=labels) if a.force_every is not None or motion is not None or a.solid_disc else {}),
+                   **(dict(solid_shape=shape) if shape is not None else {}),
                    **(dict(force_every=a.force_every) if a.force_every is not None else {}),
                    **(dict(body_motion=motion) if motion is not None else {}))
     print("MLUPS : ", r.mlups)

@@ -88,9 +88,14 @@ def force_terms(fin, mask, delta=None):
     return np.concatenate(tx), np.concatenate(ty)
 
 
-def host_force(fin, mask, delta=None):
+def host_force(fin, mask, delta=None, shape=None):
     """dict(links, fx, fy) from the populations fin[9, X, Y] that get_fields returns and the mask: the exactly rounded sums
-    (math.fsum) of force_terms.  delta: wall_delta_field(...) while the bodies move (CavitySolver.set_body_motion)."""
+    (math.fsum) of force_terms.  delta: wall_delta_field(...) while the bodies move (CavitySolver.set_body_motion).  shape: on a
+    solver with a shape (set_shape), the post-collision populations fpost[9, X, Y] of the last step: the terms are
+    c_opp(k) (fpost_opp(k) + fin_k), see shaped_force_terms."""
+    if shape is not None:
+        _, tx, ty = shaped_force_terms(fin, shape, mask)
+        return dict(links=int(tx.size), fx=math.fsum(tx.tolist()), fy=math.fsum(ty.tolist()))
     tx, ty = force_terms(fin, mask, delta)
     return dict(links=int(tx.size), fx=math.fsum(tx.tolist()), fy=math.fsum(ty.tolist()))
 
@@ -118,6 +123,23 @@ def labels_from(nx, ny, boxes=(), path=None):
             lab[f == v] = n
             n += 1
     return lab >= 0, lab, n
+
+
+def discs_into(nx, ny, discs, mask=None, labels=None, nbodies=0):
+    """(mask, labels, nbodies) with the discs of --solid-disc added: (x0, y0, R) in index coordinates, the cells whose centre lies
+    inside the circle, each disc a body of its own after the bodies already there (a later disc wins an overlap)."""
+    m = np.zeros((int(nx), int(ny)), dtype=bool) if mask is None else np.array(mask) != 0
+    lab = np.where(m, 0, -1).astype(np.int32) if labels is None else np.array(labels, dtype=np.int32)
+    n = int(nbodies) if labels is not None else int(m.any())
+    xs, ys = np.meshgrid(np.arange(int(nx)), np.arange(int(ny)), indexing="ij")
+    for x0, y0, R in discs:
+        inside = (xs - float(x0)) ** 2 + (ys - float(y0)) ** 2 < float(R) ** 2
+        if not R > 0 or not inside.any():
+            raise ValueError(f"solid disc {(x0, y0, R)} holds no cell of the {nx} x {ny} lattice")
+        m |= inside
+        lab[inside] = n
+        n += 1
+    return m, lab, n
 
 
 def centroids(mask, labels, nbodies):
@@ -195,11 +217,22 @@ def body_force_terms(fin, mask, labels, centres, delta=None):
     return b, tx, ty, rx * ty, ry * tx
 
 
-def host_body_force(fin, mask, labels, centres, delta=None):
+def host_body_force(fin, mask, labels, centres, delta=None, shape=None, fpost=None):
     """dict(links, fx, fy, tz) of arrays [nbodies] (nbodies = len(centres)) from the populations fin[9, X, Y] that
     get_fields(want_fin=True) returns: per body the exactly rounded sums (math.fsum) of body_force_terms.  delta:
-    wall_delta_field(...) while the bodies move."""
-    b, tx, ty, mx, my = body_force_terms(fin, mask, labels, centres, delta)
+    wall_delta_field(...) while the bodies move.  shape: the q of a solver with a shape (CavitySolver.shape, the effective q), with
+    fpost[9, X, Y], the post-collision populations of the last step: the terms are those of shaped_force_terms and the arm of the
+    torque is the wall point."""
+    if shape is None:
+        b, tx, ty, mx, my = body_force_terms(fin, mask, labels, centres, delta)
+    else:
+        ln, tx, ty = shaped_force_terms(fin, fpost, mask, labels)
+        x, y, k, b = ln[:, 0], ln[:, 1], ln[:, 2], ln[:, 3]
+        cen = np.asarray(centres, dtype=np.float64)
+        qe = np.asarray(shape, dtype=np.float64)[k - 1, x, y]
+        rx = (x.astype(np.float64) - qe * np.array(CX, dtype=np.float64)[k]) - cen[b, 0]
+        ry = (y.astype(np.float64) + qe * np.array(CY, dtype=np.float64)[k]) - cen[b, 1]
+        mx, my = rx * ty, ry * tx
     n = len(centres)
     out = dict(links=np.zeros(n, dtype=np.int64), fx=np.zeros(n), fy=np.zeros(n), tz=np.zeros(n))
     for i in range(n):
@@ -209,3 +242,102 @@ def host_body_force(fin, mask, labels, centres, delta=None):
         out["fy"][i] = math.fsum(ty[sel].tolist())
         out["tz"][i] = math.fsum(mx[sel].tolist() + my[sel].tolist())
     return out
+
+
+# ---- curved surfaces: a wall distance per link (CavitySolver.set_shape, lbm_set_solid_shape) -------------------------------------------
+def _link_arrays(mask):
+    """(x, y, k) of every link, slots in order -- and the source cells (sx, sy)."""
+    rows = []
+    for k, lk in enumerate(links(mask)):
+        if k:
+            x, y = np.nonzero(lk)
+            rows.append(np.stack([x, y, np.full(x.shape, k)], axis=1))
+    ln = np.concatenate(rows).astype(np.int64) if rows else np.zeros((0, 3), dtype=np.int64)
+    cx, cy = np.array(CX), np.array(CY)
+    return ln[:, 0], ln[:, 1], ln[:, 2], ln[:, 0] - cx[ln[:, 2]], ln[:, 1] + cy[ln[:, 2]]
+
+
+def disc_fractions(mask, x0, y0, R, q=None):
+    """q[8, X, Y] for set_shape: on every link whose cell and source lie on different sides of the circle of radius R about (x0, y0)
+    (index coordinates), the exact fraction of the link from the fluid cell to the circle, plane k - 1 for slot k; every other entry
+    keeps the value of q (default: 1/2, the half-way wall).  Serves a solid disc (the cells inside) and a ring that is solid outside R
+    alike; call it once per circle, passing the result on."""
+    m = np.asarray(mask) != 0
+    out = np.full((8,) + m.shape, 0.5) if q is None else np.array(q, dtype=np.float64)
+    x, y, k, sx, sy = _link_arrays(m)
+    px, py = x - float(x0), y - float(y0)
+    ex, ey = (sx - x).astype(np.float64), (sy - y).astype(np.float64)
+    inside_p = px * px + py * py < R * R
+    inside_s = (sx - float(x0)) ** 2 + (sy - float(y0)) ** 2 < R * R
+    cross = inside_p != inside_s
+    A, B, C = ex * ex + ey * ey, px * ex + py * ey, px * px + py * py - R * R
+    with np.errstate(invalid="ignore"):
+        root = np.sqrt(np.maximum(B * B - A * C, 0.0))
+        t = np.where(inside_p, (-B + root) / A, (-B - root) / A)       # leaving the disc: the far root; entering it: the near one
+    t = np.clip(t, 2.0 ** -20, 1.0)
+    out[k[cross] - 1, x[cross], y[cross]] = t[cross]
+    return out
+
+
+def fractions_from_distance(mask, phi):
+    """q[8, X, Y] for set_shape from a signed distance phi[X, Y] at the cell centres (one sign in the fluid, the other in the solid):
+    the linear estimate phi(P) / (phi(P) - phi(source)) on every link whose ends differ in sign, clipped into (0, 1]; 1/2 elsewhere."""
+    m = np.asarray(mask) != 0
+    phi = np.asarray(phi, dtype=np.float64)
+    out = np.full((8,) + m.shape, 0.5)
+    x, y, k, sx, sy = _link_arrays(m)
+    a, b = phi[x, y], phi[sx, sy]
+    ok = (a * b < 0.0) | ((a != 0.0) & (b == 0.0))
+    with np.errstate(all="ignore"):
+        t = np.clip(a / (a - b), 2.0 ** -20, 1.0)
+    out[k[ok] - 1, x[ok], y[ok]] = t[ok]
+    return out
+
+
+def shape_table(mask, labels, centres, motion, q, dtype=None):
+    """The public restatement of what lbm_set_solid_shape derives: dict of arrays [links] in the order of body_links(mask, labels) --
+    links (x, y, k, body), q (the effective one: 1/2 where q < 1/2 and the next cell N = (x + cx_k, y - cy_k) is no fluid cell of the
+    lattice), near, a = near ? 2 q : 1 / (2 q), the wall point (rx, ry) = ((x - q cx_k) - x0, (y + q cy_k) - y0), and
+    d = near ? delta : a delta with delta = (6 w_k) (cx_k uwx + cy_k uwy) of the motion at the wall point -- float64, every operation
+    rounded in this order.  dtype: the lattice type, to which a and d are rounded once."""
+    m = np.asarray(mask) != 0
+    X, Y = m.shape
+    cen, mot, q = np.asarray(centres, dtype=np.float64), np.asarray(motion, dtype=np.float64), np.asarray(q, dtype=np.float64)
+    ln = body_links(m, labels)
+    x, y, k, b = ln[:, 0], ln[:, 1], ln[:, 2], ln[:, 3]
+    cx, cy = np.array(CX, dtype=np.float64), np.array(CY, dtype=np.float64)
+    nx_, ny_ = x + np.array(CX)[k], y - np.array(CY)[k]
+    inside = (nx_ >= 0) & (nx_ < X) & (ny_ >= 0) & (ny_ < Y)
+    next_fluid = inside & ~m[np.clip(nx_, 0, X - 1), np.clip(ny_, 0, Y - 1)]
+    qv = q[k - 1, x, y]
+    near = (qv < 0.5) & next_fluid
+    qe = np.where((qv < 0.5) & ~next_fluid, 0.5, qv)
+    a = np.where(near, 2.0 * qe, 1.0 / (2.0 * qe))
+    rx = (x.astype(np.float64) - qe * cx[k]) - cen[b, 0]
+    ry = (y.astype(np.float64) + qe * cy[k]) - cen[b, 1]
+    uwx = mot[b, 0] + mot[b, 2] * ry
+    uwy = mot[b, 1] + mot[b, 2] * rx
+    delta = np.where(k < 5, 2.0 / 3.0, 1.0 / 6.0) * (cx[k] * uwx + cy[k] * uwy)
+    d = np.where(near, delta, a * delta)
+    if dtype is not None:
+        a, d = a.astype(dtype).astype(np.float64), d.astype(dtype).astype(np.float64)
+    return dict(links=ln, q=qe, near=near, a=a, d=d, rx=rx, ry=ry)
+
+
+def shaped_force_terms(fin, fpost, mask, labels=None):
+    """(links, tx, ty) of a solver with a shape: per link f_in = fin_k(x, y), the arriving population with the rule applied, as
+    get_fields returns it, and f_out = fpost_opp(k)(x, y), the population the cell sent towards the wall; (tx, ty) =
+    c_opp(k) (f_out + f_in), both converted to float64 first.  f_out never arrives anywhere and is in no exported field -- only where
+    the wall sits half-way does fin_k hold it -- so the post-collision populations fpost[9, X, Y] come from the caller (a reference, or
+    a replay of the last step).  links: body_links order with labels, else slots in order."""
+    m = np.asarray(mask) != 0
+    fin, fpost = np.asarray(fin), np.asarray(fpost)
+    if labels is None:
+        x, y, k, _, _ = _link_arrays(m)
+        ln = np.stack([x, y, k], axis=1)
+    else:
+        ln = body_links(m, labels)
+        x, y, k = ln[:, 0], ln[:, 1], ln[:, 2]
+    opp = np.array(OPP)
+    t = fpost[opp[k], x, y].astype(np.float64) + fin[k, x, y].astype(np.float64)
+    return ln, np.array(CX, dtype=np.float64)[opp[k]] * t, np.array(CY, dtype=np.float64)[opp[k]] * t

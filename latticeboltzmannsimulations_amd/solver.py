@@ -463,7 +463,7 @@ class CavitySolver:
         self._need_solid()
         m = self._mask(mask)
         self._check(self.lib.lbm_set_solid(self._h, m.ctypes.data), "lbm_set_solid")
-        self._bodies_given = self._motion_given = False
+        self._bodies_given = self._motion_given = self._shape_given = False
         return self
 
     @property
@@ -607,6 +607,39 @@ class CavitySolver:
         self._check(self.lib.lbm_get_body_motion(self._h, m.ctypes.data), "lbm_get_body_motion")
         return m
 
+    # -- curved surfaces (lbm_set_solid_shape, lbm_get_solid_shape) --------------------------------------
+    def set_shape(self, q):
+        """Give every link of the mask a wall distance (lbm_set_solid_shape): q is [8, X, Y] (a batch: [B, 8, X, Y], or [8, X, Y] for
+        every lattice), plane k - 1 for slot k, on every link the fraction 0 < q <= 1 of the link from the fluid cell to the wall
+        (solid.disc_fractions, solid.fractions_from_distance); values off the links are ignored.  The links then bounce by linear
+        interpolation, second order for curved walls, instead of half-way -- at the price of the lattice's mass, which a shape does not
+        conserve.  None clears the shape.  Only while every body is at rest: the shape first, then set_body_motion.  The lattice, the
+        step count and the samplers stay; set_solid drops the shape, set_bodies keeps it."""
+        self._need_solid()
+        if q is None:
+            self._check(self.lib.lbm_set_solid_shape(self._h, None), "lbm_set_solid_shape")
+            self._shape_given = False
+            return self
+        a = np.asarray(q, dtype=np.float64)
+        if self._lead and a.shape == (8, self.nx, self.ny):
+            a = np.broadcast_to(a, self._lead + a.shape)
+        if a.shape != self._lead + (8, self.nx, self.ny):
+            raise ValueError(f"the shape must have shape {self._lead + (8, self.nx, self.ny)}: q of slot k in plane k - 1")
+        a = np.ascontiguousarray(a)
+        self._check(self.lib.lbm_set_solid_shape(self._h, a.ctypes.data), "lbm_set_solid_shape")
+        self._shape_given = True      # (a checkpoint then carries it)
+        return self
+
+    @property
+    def shape(self):
+        """A copy of the effective q, float64 [8, X, Y] (a batch: [B, 8, X, Y]): on the links the q in force (1/2 where a link with
+        q < 1/2 has no fluid cell behind it), 0 elsewhere; None without a shape."""
+        if not self.has_solid or not getattr(self, "_shape_given", False):
+            return None
+        a = np.zeros(self._lead + (8, self.nx, self.ny))
+        self._check(self.lib.lbm_get_solid_shape(self._h, a.ctypes.data), "lbm_get_solid_shape")
+        return a
+
     # -- checkpoint / restart (the reference has neither; SURVEY 8f item 4) -------------------
     def save_checkpoint(self, path):
         """Write the populations and the run parameters to `path` (.npz).  Restarting from it continues bit-identically
@@ -618,8 +651,13 @@ class CavitySolver:
                  semantics=self.semantics, dtype=self.dtype.name, rows=np.array([self.y0, self.ny_local]), turb=self.turb, u=u, rho=rho,
                  arith=self.arith, **(dict(solid=self.solid) if self.has_solid else {}),
                  **{**(dict(zip(("body_labels", "body_centres"), self.bodies)) if getattr(self, "_bodies_given", False) else {}),
-                    **self._motion_entry()})
+                    **self._motion_entry(), **self._shape_entry()})
         return path
+
+    def _shape_entry(self):
+        """What a checkpoint says of the shape: nothing without one (the file of such a run is what it was), else the effective q."""
+        q = self.shape if self.has_solid else None
+        return {} if q is None else dict(solid_shape=q)
 
     def _motion_entry(self):
         """What a checkpoint says of the bodies' motion: nothing at rest (the file of a run without it is what it was), else the
@@ -658,6 +696,10 @@ class CavitySolver:
                 if diff:
                     raise ValueError(f"checkpoint was written by a different run (checkpoint, this solver): {diff}")
             self.set_state(np.ascontiguousarray(z["fin"]))
+            same_mask = self.has_solid and "solid" in z and np.array_equal(np.asarray(z["solid"], dtype=bool), self.solid)
+            if same_mask and ("solid_shape" in z or self.shape is not None):     # (the shape first, then the motion)
+                self.set_body_motion(None)
+                self.set_shape(np.where(np.asarray(z["solid_shape"]) > 0.0, z["solid_shape"], 0.5) if "solid_shape" in z else None)
             if "body_labels" in z and self.has_solid and np.array_equal(np.asarray(z["solid"], dtype=bool), self.solid):
                 self.set_bodies(np.asarray(z["body_labels"]), np.asarray(z["body_centres"]))     # (files without them: the bodies stay)
                 if "body_motion" in z:

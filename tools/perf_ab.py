@@ -8,7 +8,8 @@ A case is  size:dtype:arith[:key=value,...]  e.g.  4096:f32:fast   4096:f32:stri
 block -- one block of an eighth of the width squared in the middle --, disc -- one disc of an eighth of the width across in the middle --,
 random -- 20 % of the cells, seeded --, interior -- the same, one cell clear of the perimeter), motion (with solid: rest -- set_body_motion of
 zeros, the kernels of obstacles at rest -- or rotate -- the solid cells turn as one body about their centroid, 0.05 at three quarters of the
-width from it; not with route=tiles), route (with solid: single --
+width from it; not with route=tiles), shape (with solid: disc -- set_shape with the exact fractions of the circle of solid=disc --, random -- q uniform in (0, 1], seeded, for any
+mask -- or half -- 1/2 on every link: the kernels of a shaped lattice; set before the motion; not with route=tiles), route (with solid: single --
 one step per launch, the default -- or tiles -- the multi-step tile kernel, tuning solid_tiles), force (with solid: series.E -- the run
 with begin_force(every=E) --, loop.E -- the host loop step(E); solid_force() --, plain.E -- step(E); sync() without any force --, or call -- no stepping: microseconds per call of
 body_force() and of solid_force(); these three are timed with the host clock around work that ends in a synchronisation), batch (that
@@ -23,7 +24,7 @@ import time
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from latticeboltzmannsimulations_amd import CavityBatch, CavitySolver  # noqa: E402
+from latticeboltzmannsimulations_amd import CavityBatch, CavitySolver, solid  # noqa: E402
 
 
 def solid_mask(kind, nx, ny):
@@ -72,6 +73,10 @@ def parse(case):
                 if v not in ("rest", "rotate"):
                     raise ValueError("motion must be rest or rotate")
                 kw["motion"] = v
+            elif k == "shape":
+                if v not in ("disc", "half", "random"):
+                    raise ValueError("shape must be disc, half or random")
+                kw["shape"] = v
             elif k == "batch":
                 kw["batch"] = int(v)
             elif k in ("tb_steps", "frame_seg"):
@@ -92,8 +97,13 @@ def main():
         B = kw.pop("batch", 1)
         force = kw.pop("force", None)
         motion = kw.pop("motion", None)
+        shape = kw.pop("shape", None)
         make = (lambda *a_, **k_: CavityBatch(a_[0], a_[1], [a_[2]] * B, **k_)) if B > 1 else CavitySolver
         with make(nx, ny, 1000.0, dtype=dtype, arith=arith, tuning=tune, **kw) as s:
+            if shape is not None:
+                q = {"half": lambda: np.full((8, nx, ny), 0.5), "random": lambda: 1.0 - np.random.default_rng(2).random((8, nx, ny)),
+                     "disc": lambda: solid.disc_fractions(kw["solid"], (nx - 1) / 2, (ny - 1) / 2, nx / 16)}[shape]()
+                s.set_shape(q)
             if motion is not None:
                 s.set_body_motion(np.broadcast_to([0.0, 0.0, 0.05 / (0.75 * nx) if motion == "rotate" else 0.0], (B, 1, 3)[B == 1:]))
             s.copy_bandwidth(1 << 30, 60)
@@ -131,7 +141,7 @@ def main():
             else:
                 reps = [s.time_steps(a.steps) / a.steps for _ in range(a.reps)]
             ms = min(reps)
-            print(f"{case:48s} S={s.next_unit(1000)}{' move' if s.describe().get('wall_motion') else ''}  {B * nx * ny / ms / 1e6:8.1f} GLUPS  {ms * 1e3:9.2f} us/step  "
+            print(f"{case:48s} S={s.next_unit(1000)}{' move' if s.describe().get('wall_motion') else ''}{' shape' if s.describe().get('wall_shape') else ''}  {B * nx * ny / ms / 1e6:8.1f} GLUPS  {ms * 1e3:9.2f} us/step  "
                   f"repeats {' '.join('%.1f' % (B * nx * ny / r / 1e6) for r in reps)}"
                   + (f"  us/step {' '.join('%.2f' % (r * 1e3) for r in reps)}" if force else ""), flush=True)
 
