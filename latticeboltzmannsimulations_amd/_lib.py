@@ -96,8 +96,9 @@ def sources():
 
 def build(force=False, verbose=False):
     """Compile csrc/*.hip for gfx950 into liblbm_hip.so next to this file (in-tree).  The translation units (eight of host code +
-    C ABI: lbm_hip / lbm_plan / lbm_launch / lbm_comm / lbm_sampling / lbm_monitor / lbm_residual / lbm_topology / lbm_solid / lbm_bodies / lbm_body_motion / lbm_body_shape; the explicit instantiations of the tile, streaming,
-    solid-mask, moving-body and shaped-body kernels, and of the tile kernel with solid cells, for float and for double) are compiled in parallel into csrc/_obj/ and linked."""
+    C ABI: lbm_hip / lbm_plan / lbm_launch / lbm_comm / lbm_sampling / lbm_monitor / lbm_residual / lbm_topology / lbm_solid / lbm_bodies / lbm_body_motion / lbm_body_shape; the explicit instantiations of the tile and
+    streaming kernels, of the one-step kernels with a solid mask per mode of the wall rule -- lbm_solid / lbm_solid_move / lbm_solid_shape,
+    all three from lbm_solid.hpp -- and of the tile kernel with solid cells, for float and for double) are compiled in parallel into csrc/_obj/ and linked."""
     srcs = sources()
     if not force and os.path.exists(LIB_PATH) and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(s) for s in srcs):
         return LIB_PATH

@@ -41,87 +41,46 @@ struct BodyAcc {
 // One workgroup per chunk of the list (BODY_CHUNK links of one body; grid x: the chunks of a lattice, padded to the longest of the
 // batch with empty ones; grid z: the lattice).  Lane t folds links t, t + BLK, .. of its chunk in this order; then the tree.  The
 // chunks are cut from the list alone, so a lattice's partial results are the same alone and in a batch.
-// MOVE (k_body_force_move, while a body motion is set): f_out = f - delta, so (tx, ty) = c_opp(k) (2 f - delta), delta the link's entry
-// of link_delta -- the term as the lattice adds it, a double; the midpoint, the order and the tree are the same.
-template <typename R, bool MOVE>
-__device__ __forceinline__ void body_force_chunk(const R* __restrict__ src, const Geo& geo, long long bstride, const BodyLink* __restrict__ links,
-                                                 const BodyChunk* __restrict__ chunks, const double* __restrict__ centre, int nbodies,
-                                                 double* __restrict__ partial, const double* __restrict__ link_delta) {
-#pragma clang fp contract(off)
-    __shared__ double sh[BLK / RED_WAVE][BodyAcc::VALS];
-    const size_t slot = (size_t)blockIdx.z * gridDim.x + blockIdx.x;
-    const BodyChunk ch = chunks[slot];
-    src += blockIdx.z * bstride;
-    BodyAcc a = BodyAcc::identity();
-    if (ch.n > 0) {
-        const double x0 = centre[((size_t)blockIdx.z * nbodies + ch.body) * 2], y0 = centre[((size_t)blockIdx.z * nbodies + ch.body) * 2 + 1];
-        for (int i = threadIdx.x; i < ch.n; i += BLK) {
-            const BodyLink l = links[ch.begin + i];
-            const int x = l.x, y = l.yk >> 4, k = l.yk & 15, o = opp(k);
-            const double f = (double)src[o * geo.plane + geo.at(x, y)];
-            double tx, ty;
-            if (MOVE) {
-                const double t = 2.0 * f - link_delta[ch.begin + i];
-                tx = (double)cxk(o) * t;
-                ty = (double)cyk(o) * t;
-            } else {
-                tx = (double)(2 * cxk(o)) * f;
-                ty = (double)(2 * cyk(o)) * f;
-            }
-            const double rx = ((double)x - 0.5 * (double)cxk(k)) - x0, ry = ((double)y + 0.5 * (double)cyk(k)) - y0;
-            a.links = a.links + 1.0;
-            a.fx = a.fx + tx;
-            a.fy = a.fy + ty;
-            a.tz = a.tz + (rx * ty + ry * tx);
-        }
-    }
-    red_wave(a);
-    if (red_workgroup<BodyAcc, BLK / RED_WAVE>(a, sh)) red_store(partial + slot * BodyAcc::VALS, a);
-}
-
-template <typename R>
+// The term of a link by the mode of the wall rule (WallArg), as k_solid_force; link: the mode's double per entry of the list.
+//   WALL_REST   (tx, ty) = 2 c_opp(k) f; the arm of the torque is the link's midpoint, q = 1/2
+//   WALL_MOVE   f_out = f - delta, so (tx, ty) = c_opp(k) (2 f - delta), delta = link[i] (link_delta) -- the term as the lattice adds it, a
+//               double; the midpoint again
+//   WALL_SHAPE  f_out = f, f_in = shape_link, (tx, ty) = c_opp(k) (f_out + f_in), and the arm is the wall point,
+//               (rx, ry) = ((x - q cx_k) - x0, (y + q cy_k) - y0), q = link[i] (link_q, the effective q)
+template <typename R, int WALL>
 __global__ __launch_bounds__(BLK) void k_body_force(const R* __restrict__ src, Geo geo, long long bstride, const BodyLink* __restrict__ links,
                                                     const BodyChunk* __restrict__ chunks, const double* __restrict__ centre, int nbodies,
-                                                    double* __restrict__ partial) {
-    body_force_chunk<R, false>(src, geo, bstride, links, chunks, centre, nbodies, partial, nullptr);
-}
-
-template <typename R>
-__global__ __launch_bounds__(BLK) void k_body_force_move(const R* __restrict__ src, Geo geo, long long bstride, const BodyLink* __restrict__ links,
-                                                         const BodyChunk* __restrict__ chunks, const double* __restrict__ centre, int nbodies,
-                                                         double* __restrict__ partial, const double* __restrict__ link_delta) {
-    body_force_chunk<R, true>(src, geo, bstride, links, chunks, centre, nbodies, partial, link_delta);
-}
-
-// A shape is set (lbm_set_solid_shape): f_out = f, f_in = shape_rule of the link (k_solid_force_shape), (tx, ty) = c_opp(k) (f_out + f_in),
-// and the arm of the torque is the wall point, (rx, ry) = ((x - q cx_k) - x0, (y + q cy_k) - y0), q the link's entry of link_q (the
-// effective q); chunks, order and tree as k_body_force.
-template <typename R>
-__global__ __launch_bounds__(BLK) void k_body_force_shape(const R* __restrict__ src, Geo geo, long long bstride, const BodyLink* __restrict__ links,
-                                                          const BodyChunk* __restrict__ chunks, const double* __restrict__ centre, int nbodies,
-                                                          double* __restrict__ partial, ShapeTable<R> sh, const double* __restrict__ link_q) {
+                                                    double* __restrict__ partial, WallArg<R, WALL> wa, const double* __restrict__ link) {
 #pragma clang fp contract(off)
     __shared__ double shm[BLK / RED_WAVE][BodyAcc::VALS];
     const size_t slot = (size_t)blockIdx.z * gridDim.x + blockIdx.x;
     const BodyChunk ch = chunks[slot];
     src += blockIdx.z * bstride;
-    sh.cell_row += (long long)blockIdx.z * geo.nx * geo.ny;
+    wall_batch(wa, blockIdx.z, geo);
     BodyAcc a = BodyAcc::identity();
     if (ch.n > 0) {
         const double x0 = centre[((size_t)blockIdx.z * nbodies + ch.body) * 2], y0 = centre[((size_t)blockIdx.z * nbodies + ch.body) * 2 + 1];
         for (int i = threadIdx.x; i < ch.n; i += BLK) {
             const BodyLink l = links[ch.begin + i];
             const int x = l.x, y = l.yk >> 4, k = l.yk & 15, o = opp(k);
-            const long long me = geo.at(x, y);
-            const R own = src[o * geo.plane + me];
-            const long long row = sh.cell_row[(long long)y * geo.nx + x];
-            R g = own;
-            if (row >= 0) {
-                const R other = ((sh.near[row] >> (k - 1)) & 1) ? src[o * geo.plane + geo.at(x + cxk(k), y - cyk(k))] : src[k * geo.plane + me];
-                g = shape_rule<R>(own, other, sh.ad[row * 16 + (k - 1)], sh.ad[row * 16 + 8 + (k - 1)]);
+            const R own = src[o * geo.plane + geo.at(x, y)];
+            double tx, ty, q = 0.5;
+            if constexpr (WALL == WALL_REST) {
+                const double f = (double)own;
+                tx = (double)(2 * cxk(o)) * f;
+                ty = (double)(2 * cyk(o)) * f;
+            } else {
+                double t;
+                if constexpr (WALL == WALL_MOVE) {
+                    t = 2.0 * (double)own - link[ch.begin + i];
+                } else {
+                    const long long row = wa.sh.cell_row[(long long)y * geo.nx + x];
+                    t = (double)own + (double)(row >= 0 ? shape_link<R, Geo>(src, geo, wa.sh.ad + row * 16, wa.sh.near[row], k, x, y, own) : own);
+                    q = link[ch.begin + i];
+                }
+                tx = (double)cxk(o) * t;
+                ty = (double)cyk(o) * t;
             }
-            const double t = (double)own + (double)g, q = link_q[ch.begin + i];
-            const double tx = (double)cxk(o) * t, ty = (double)cyk(o) * t;
             const double rx = ((double)x - q * (double)cxk(k)) - x0, ry = ((double)y + q * (double)cyk(k)) - y0;
             a.links = a.links + 1.0;
             a.fx = a.fx + tx;
@@ -236,19 +195,13 @@ int obstacles_change(lbm_ctx* c, ObsLevel level, Obstacles& next, int (*before_c
 static int body_force_enqueue(lbm_ctx* c, double* rec) {
     const BodyTables& t = c->obs.body;
     const int nbodies = c->obs.nbodies;
-    const double* link_delta = c->obs.moving.base ? c->obs.moving.link_delta : nullptr;
     return launch_variant(c, [&](auto v) {
-        using R = typename decltype(v)::R;
-        if (c->obs.shaped.base)
-            hipLaunchKernelGGL((k_body_force_shape<R>), dim3(t.maxchunks, 1, c->plan.batch), dim3(BLK), 0, c->s_compute, c->lat[c->cur].as<const R>(),
-                               c->plan.geo, c->plan.bstride, t.links, t.chunks, t.centre, nbodies, t.partial, c->obs.shaped.template table<R>(),
-                               c->obs.shaped.link_q);
-        else if (link_delta)
-            hipLaunchKernelGGL((k_body_force_move<R>), dim3(t.maxchunks, 1, c->plan.batch), dim3(BLK), 0, c->s_compute, c->lat[c->cur].as<const R>(),
-                               c->plan.geo, c->plan.bstride, t.links, t.chunks, t.centre, nbodies, t.partial, link_delta);
-        else
-            hipLaunchKernelGGL((k_body_force<R>), dim3(t.maxchunks, 1, c->plan.batch), dim3(BLK), 0, c->s_compute, c->lat[c->cur].as<const R>(), c->plan.geo,
-                               c->plan.bstride, t.links, t.chunks, t.centre, nbodies, t.partial);
+        using VT = decltype(v);
+        using R = typename VT::R;
+        with_wall<VT>(c, [&](auto wa, const double* link) {
+            hipLaunchKernelGGL((k_body_force<R, decltype(wa)::MODE>), dim3(t.maxchunks, 1, c->plan.batch), dim3(BLK), 0, c->s_compute,
+                               c->lat[c->cur].as<const R>(), c->plan.geo, c->plan.bstride, t.links, t.chunks, t.centre, nbodies, t.partial, wa, link);
+        });
         hipLaunchKernelGGL(k_body_force_final, dim3(nbodies, c->plan.batch), dim3(RED_WAVE), 0, c->s_compute, (const double*)t.partial, t.first,
                            t.maxchunks, (double)c->nsteps, rec);
     });

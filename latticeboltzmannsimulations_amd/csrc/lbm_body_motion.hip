@@ -1,8 +1,8 @@
 // lbm_body_motion.hip -- liblbm_hip.so: the wall velocity of moving bodies (lbm_set_body_motion, lbm_get_body_motion of the C ABI declared
 // in include/lbm.h; LBM_SEM_BOUNCE_BACK_SOLID).  A body keeps its cells and its surface moves: every link carries Ladd's term, a constant
 // of the link, built on the host (lbm_wall_motion.hpp) and uploaded here, never inside lbm_step.  The step kernels that add it are
-// k_step_solid_move / k_step_generic_move (lbm_solid_move.hpp), the force kernels that subtract it k_solid_force_move / k_body_force_move;
-// all of them run only while a nonzero motion is set.  gfx950 only.  DESIGN.md 2.10.
+// k_step_solid / k_step_generic_wall in their mode WALL_MOVE (lbm_solid.hpp), the force kernels that subtract it k_solid_force / k_body_force
+// in the same mode; with_wall (lbm_host.hpp) picks it only while a nonzero motion is set.  gfx950 only.  DESIGN.md 2.10.
 #include <cmath>
 
 #include "lbm_host.hpp"

@@ -1,9 +1,9 @@
 // lbm_body_shape.hip -- liblbm_hip.so: curved obstacle surfaces (lbm_set_solid_shape, lbm_get_solid_shape of the C ABI declared in
 // include/lbm.h; LBM_SEM_BOUNCE_BACK_SOLID).  Every link carries the fraction q of its length at which the wall sits; the coefficients of
 // the interpolated bounce-back and the moving-wall term at the wall point are built on the host (lbm_wall_shape.hpp) and uploaded here and
-// in the other set_* calls, never inside lbm_step.  The step kernels that apply the rule are k_step_solid_shape / k_step_generic_shape
-// (lbm_solid_shape.hpp), the readers see it through Fields (lbm_fields.hpp), the force kernels are k_solid_force_shape / k_body_force_shape;
-// all of them run only while a shape is set.  gfx950 only.  DESIGN.md 2.10.
+// in the other set_* calls, never inside lbm_step.  The step kernels that apply the rule are k_step_solid / k_step_generic_wall in their mode
+// WALL_SHAPE (lbm_solid.hpp), the readers see it through Fields (lbm_fields.hpp), the force kernels are k_solid_force / k_body_force in the
+// same mode; with_wall (lbm_host.hpp) picks it only while a shape is set.  gfx950 only.  DESIGN.md 2.10.
 #include <cmath>
 
 #include "lbm_host.hpp"

@@ -511,6 +511,52 @@ __device__ __forceinline__ R shape_rule(R own, R other, R a, R d) {
     const R t1 = a * own, b = (R)1 - a, t2 = b * other;
     return (t1 + t2) + d;
 }
+// Link k of the cell at (x, y), from a lattice that holds post-collision populations and the cell's row of the table -- ad: its sixteen
+// a and d, nm: its near bits, read by the caller.  The link's near bit picks `other`, the next fluid cell's population of direction
+// opp(k) or the cell's own of direction k (far), one load from either place; a and d of the link go into shape_rule.  own: the cell's
+// population of direction opp(k), which every caller holds already.  The force kernels call it; gather_a below and k_step_solid
+// (lbm_solid.hpp) spell the same three lines in place, the one to keep the code of the reader kernels what it was, the
+// other because both candidates for `other` are in registers there.
+template <typename R, typename AS>
+__device__ __forceinline__ R shape_link(const R* src, const AS& as, const R* ad, unsigned nm, int k, int x, int y, R own) {
+    const bool near = (nm >> (k - 1)) & 1u;
+    const R other = src[near ? opp(k) * as.plane + as.at(x + cxk(k), y - cyk(k)) : k * as.plane + as.at(x, y)];
+    return shape_rule<R>(own, other, ad[k - 1], ad[8 + k - 1]);
+}
+
+// The mode of the obstacle wall rule, a compile-time argument of every kernel that applies it (the step kernels of lbm_solid.hpp,
+// update_cell_a below, the force kernels of lbm_solid.hip and lbm_bodies.hip), and what the mode reads, the kernels' last argument;
+// chosen on the host by with_wall (lbm_host.hpp) alone.
+//   WALL_REST   every body at rest, no shape: the plain bounce, nothing to read
+//   WALL_MOVE   a nonzero lbm_set_body_motion: a cell with links adds Ladd's term of link k to its post-collision population of
+//               direction opp(k) before it stores it.  cell_row[batch][ny][nx] (x fastest; -1, or the cell's row of delta),
+//               delta[rows][8] in the lattice type: lbm_wall_motion.hpp
+//   WALL_SHAPE  lbm_set_solid_shape holds a shape: shape_rule on the read side of every link; the motion's term is part of the table, the
+//               stores are the pure post-collision values
+constexpr int WALL_REST = 0, WALL_MOVE = 1, WALL_SHAPE = 2;
+template <typename R, int WALL>
+struct WallArg {
+    static constexpr int MODE = WALL;
+};
+template <typename R>
+struct WallArg<R, WALL_MOVE> {
+    static constexpr int MODE = WALL_MOVE;
+    const int32_t* cell_row;
+    const R* delta;
+};
+template <typename R>
+struct WallArg<R, WALL_SHAPE> {
+    static constexpr int MODE = WALL_SHAPE;
+    ShapeTable<R> sh;
+};
+// cell_row is [batch][ny][nx]: the offset of lattice z's table, and wa made the tables of that lattice -- the one spelling of the batch
+// offset, whatever the mode (the vector kernel adds batch_cells to its own row offset, the other kernels call wall_batch)
+__device__ __forceinline__ long long batch_cells(unsigned z, const Geo& geo) { return (long long)z * geo.nx * geo.ny; }
+template <typename R, int WALL>
+__device__ __forceinline__ void wall_batch(WallArg<R, WALL>& wa, unsigned z, const Geo& geo) {
+    if constexpr (WALL == WALL_MOVE) wa.cell_row += batch_cells(z, geo);
+    if constexpr (WALL == WALL_SHAPE) wa.sh.cell_row += batch_cells(z, geo);
+}
 
 // Gather the post-stream, post-wall-rule populations of cell (x, y) from a lattice that
 // holds post-collision values (+ kept slots + parked wall densities); raw != 0: the lattice
@@ -560,7 +606,7 @@ __device__ __forceinline__ void gather_a(const R* __restrict__ src, const AS& as
                 const unsigned nm = sh.near[row];
 #pragma unroll
                 for (int k = 1; k < Q; ++k)
-                    if ((lw >> (k - 1)) & 1) {
+                    if ((lw >> (k - 1)) & 1) {   // (shape_link, spelled in place: the call changes the code of every reader kernel)
                         const bool near = (nm >> (k - 1)) & 1u;
                         const R other = src[near ? opp(k) * as.plane + as.at(x + cxk(k), y - cyk(k)) : k * as.plane + as.at(x, y)];
                         g[k] = shape_rule<R>(g[k], other, ad[k - 1], ad[8 + k - 1]);
@@ -600,21 +646,20 @@ __device__ __forceinline__ void gather(const R* __restrict__ src, const Geo& geo
 
 // One fused update of cell (x, y): gather -> (kept slots) -> moments -> collide -> store.
 // as / ad: addressing of the source / destination (Geo = lattice in memory, Window = LDS window of the fused frame passes).
-// MOVE (SEM_SOLID on a lattice in memory, k_step_generic_move of lbm_solid_move.hpp; off everywhere else): the bodies' surfaces move.  A
-// cell with links adds the delta of link k (cell_row / delta: the per-cell table of lbm_wall_motion.hpp) to its post-collision
-// population of direction opp(k) before it stores it, one add in the lattice type; no gather changes.
-// SHAPE (k_step_generic_shape of lbm_solid_shape.hpp; off everywhere else): the gather applies shape_rule on the links, the stores are
-// the pure post-collision values.
-template <typename R, int COLL, int SEM, bool TURB, typename AS, typename AD, bool MOVE = false, bool SHAPE = false>
+// WALL (SEM_SOLID on a lattice in memory, k_step_generic_wall of lbm_solid.hpp; WALL_REST everywhere else), wa: the mode's tables of the
+// cell's lattice.  WALL_MOVE: a cell with links adds the delta of link k to its post-collision population of direction opp(k) before it
+// stores it, one add in the lattice type; no gather changes.  WALL_SHAPE: the gather applies shape_rule on the links, the stores are the
+// pure post-collision values.
+template <typename R, int COLL, int SEM, bool TURB, typename AS, typename AD, int WALL = WALL_REST>
 __device__ __forceinline__ void update_cell_a(const R* __restrict__ src, const AS& as, R* __restrict__ dst, const AD& ad, const Geo& geo,
                                               const Relax<R>& w0, int raw, int x, int y, const R* __restrict__ lnk = nullptr,
-                                              const int32_t* __restrict__ cell_row = nullptr, const R* __restrict__ delta = nullptr,
-                                              ShapeTable<R> sh = ShapeTable<R>{}) {
+                                              WallArg<R, WALL> wa = WallArg<R, WALL>{}) {
     // lnk (SEM_SOLID with an LDS window as the source): plane K_LINK of the lattice, see link_word
     const int X = geo.nx, Y = geo.NY, gy = geo.y0 + y;
     if (SEM == SEM_SOLID && (link_word<R, AS>(src, as, geo, lnk, x, y) & LINK_SOLID)) return;   // a solid cell is never updated
     R g[Q];
-    gather_a<R, SEM, AS, coll_is_prom(COLL), SHAPE>(src, as, geo, raw, w0.uLB, x, y, g, lnk, sh);
+    if constexpr (WALL == WALL_SHAPE) gather_a<R, SEM, AS, coll_is_prom(COLL), true>(src, as, geo, raw, w0.uLB, x, y, g, lnk, wa.sh);
+    else gather_a<R, SEM, AS, coll_is_prom(COLL)>(src, as, geo, raw, w0.uLB, x, y, g, lnk);
     // kept slots: a slot outside its streaming window keeps its value; park it where the
     // next pull of this cell will look for it.
     const bool near_edge = (x <= 0) || (x >= X - 2) || (gy <= 0) || (gy >= Y - 2);
@@ -635,13 +680,13 @@ __device__ __forceinline__ void update_cell_a(const R* __restrict__ src, const A
         dst[K_QEQ * ad.plane + me] = q2;
         dst[K_RHO * ad.plane + me] = rho;
     }
-    if constexpr (MOVE && SEM == SEM_SOLID) {
+    if constexpr (WALL == WALL_MOVE && SEM == SEM_SOLID) {
         const int lw = link_word<R, AS>(src, as, geo, lnk, x, y);
-        const int row = (lw & 255) ? cell_row[(long long)y * geo.nx + x] : -1;
+        const int row = (lw & 255) ? wa.cell_row[(long long)y * geo.nx + x] : -1;
         if (row >= 0) {
 #pragma unroll
             for (int k = 1; k < Q; ++k)
-                if ((lw >> (k - 1)) & 1) out[opp(k)] = out[opp(k)] + delta[(long long)row * 8 + (k - 1)];
+                if ((lw >> (k - 1)) & 1) out[opp(k)] = out[opp(k)] + wa.delta[(long long)row * 8 + (k - 1)];
         }
     }
     if (!near_edge) {

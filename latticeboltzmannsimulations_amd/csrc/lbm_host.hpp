@@ -11,7 +11,8 @@
 //   lbm_monitor.hip the run monitor and the line export (kernels: lbm_monitor.hpp)        (C ABI: monitor*, get_lines)
 //   lbm_residual.hip the field residual (kernels: lbm_residual.hpp)                        (C ABI: residual_*)
 //   lbm_topology.hip stream function, vorticity, extrema of psi (kernels: lbm_topology.hpp) (C ABI: topology, get_stream_function)
-//   lbm_solid.hip   solid obstacles: the mask and its link plane, the force on the obstacles (step kernel: lbm_solid.hpp) (C ABI: set_solid, get_solid, solid_force)
+//   lbm_solid.hip   solid obstacles: the mask and its link plane, the force on the obstacles (k_solid_force) (C ABI: set_solid, get_solid, solid_force)
+//                   (step kernels, all three wall modes: k_step_solid, k_step_generic_wall of lbm_solid.hpp; the mode: with_wall below)
 //   lbm_bodies.hip  the one writer of the obstacle state (struct Obstacles); the bodies of a mask: force and torque on each, one-shot
 //                   and as a series                                                          (C ABI: set_solid_bodies, get_solid_bodies, body_force, force_*)
 //   lbm_body_motion.hip the wall velocity of moving bodies: its tables                         (C ABI: set_body_motion, get_body_motion)
@@ -46,9 +47,7 @@
 #include "lbm_order.hpp"
 #include "lbm_devmem.hpp"
 #include "lbm_bodies.hpp"
-#include "lbm_solid.hpp"  // k_step_solid, extern (compiled in lbm_solid_f32/f64.hip)
-#include "lbm_solid_move.hpp"  // k_step_solid_move, k_step_generic_move, extern (compiled in lbm_solid_move_f32/f64.hip)
-#include "lbm_solid_shape.hpp"  // k_step_solid_shape, k_step_generic_shape, extern (compiled in lbm_solid_shape_f32/f64.hip)
+#include "lbm_solid.hpp"  // k_step_solid, k_step_generic_wall, extern (compiled per wall mode in lbm_solid{,_move,_shape}_f32/f64.hip)
 #include "lbm_fields.hpp" // the view of the exported state and the kernels of the field export
 #include "lbm_inst.hpp"   // the kernels, and extern template declarations of the multi-step ones (compiled in lbm_{tiles,stream*}_f32/f64.hip)
 
@@ -405,6 +404,19 @@ void with_fields(const lbm_ctx* c, int which, F&& launch) {
         }
     }
     launch(fields_of<VT, false>(c, which));
+}
+// The mode of the obstacle wall rule (WallArg, lbm_device.hpp), and the one place that reads the obstacle state to pick it:
+// launch(wa, link), wa the tables of the mode -- a shape (which carries a motion's term in its table), else a nonzero motion, else
+// nothing -- and link the mode's double per entry of BodyTables::links (link_q, link_delta, null).  The kernel takes decltype(wa)::MODE
+// as its last template argument and wa as its last argument.
+template <typename VT, typename F>
+void with_wall(const lbm_ctx* c, F&& launch) {
+    using R = typename VT::R;
+    const ShapeTables& sh = c->obs.shaped;
+    const MotionTables& m = c->obs.moving;
+    if (sh.base) launch(WallArg<R, WALL_SHAPE>{sh.template table<R>()}, sh.link_q);
+    else if (m.base) launch(WallArg<R, WALL_MOVE>{m.cell_row, (const R*)m.delta}, m.link_delta);
+    else launch(WallArg<R, WALL_REST>{}, (const double*)nullptr);
 }
 // A launcher's body: f(Variant) enqueues the kernels of the context's variant, then the launch error check
 template <typename F>

@@ -43,39 +43,21 @@ int launch_rows(lbm_ctx* c, int from, int to, int row0, int stride, int nrows, h
             else launch(std::false_type{});
         };
         if constexpr (VT::SEM == SEM_SOLID) {
-            // (a nonzero lbm_set_body_motion: the same two routes with the moving-wall term in their stores)
-            const MotionTables& m = c->obs.moving;
-            const bool moving = (bool)m.base;
-            const R* delta = (const R*)m.delta;
-            // (a shape, lbm_set_solid_shape: the same two routes with the interpolated bounce-back in their gathers, the motion's term
-            // in its table; never together with the store-side add)
-            const bool shaped = (bool)c->obs.shaped.base;
-            const ShapeTable<R> sh = c->obs.shaped.template table<R>();
-            if (shaped && !c->plan.use_vec) {
-                hipLaunchKernelGGL((k_step_generic_shape<R, VT::COLL>), grid_rows(c, nrows), dim3(BLK), 0, s, src, dst, c->plan.geo, relax_of<R>(c->p),
-                                   batch_of<R>(c), raw, row0, stride, sh);
-                return;
-            }
-            if (c->plan.use_vec) {   // (nx a multiple of the vector width, kernel = AUTO: plan_kernel)
-                by_nt([&](auto nt) {
-                    constexpr bool NT = decltype(nt)::value;
-                    if (shaped)
-                        hipLaunchKernelGGL((k_step_solid_shape<R, VT::COLL, NT>), gvec, dim3(BLK), 0, s, src, dst, c->plan.geo, relax_of<R>(c->p),
-                                           batch_of<R>(c), raw, row0, stride, nxb, nblocks, sh);
-                    else if (moving)
-                        hipLaunchKernelGGL((k_step_solid_move<R, VT::COLL, NT>), gvec, dim3(BLK), 0, s, src, dst, c->plan.geo, relax_of<R>(c->p),
-                                           batch_of<R>(c), raw, row0, stride, nxb, nblocks, m.cell_row, delta);
-                    else
-                        hipLaunchKernelGGL((k_step_solid<R, VT::COLL, NT>), gvec, dim3(BLK), 0, s, src, dst, c->plan.geo, relax_of<R>(c->p),
-                                           batch_of<R>(c), raw, row0, stride, nxb, nblocks);
-                });
-                return;
-            }
-            if (moving) {
-                hipLaunchKernelGGL((k_step_generic_move<R, VT::COLL>), grid_rows(c, nrows), dim3(BLK), 0, s, src, dst, c->plan.geo, relax_of<R>(c->p),
-                                   batch_of<R>(c), raw, row0, stride, m.cell_row, delta);
-                return;
-            }
+            // the wall mode's kernel on either route (with_wall); at rest the one-cell route is k_step_generic below, as without a mask
+            bool launched = true;
+            with_wall<VT>(c, [&](auto wa, const double*) {
+                constexpr int WALL = decltype(wa)::MODE;
+                if (c->plan.use_vec)   // (nx a multiple of the vector width, kernel = AUTO: plan_kernel)
+                    by_nt([&](auto nt) {
+                        hipLaunchKernelGGL((k_step_solid<R, VT::COLL, decltype(nt)::value, WALL>), gvec, dim3(BLK), 0, s, src, dst, c->plan.geo,
+                                           relax_of<R>(c->p), batch_of<R>(c), raw, row0, stride, nxb, nblocks, wa);
+                    });
+                else if constexpr (WALL != WALL_REST)
+                    hipLaunchKernelGGL((k_step_generic_wall<R, VT::COLL, WALL>), grid_rows(c, nrows), dim3(BLK), 0, s, src, dst, c->plan.geo,
+                                       relax_of<R>(c->p), batch_of<R>(c), raw, row0, stride, wa);
+                else launched = false;
+            });
+            if (launched) return;
         }
         if (VT::SEM == SEM_GPU && c->plan.use_vec)
             by_nt([&](auto nt) {

@@ -533,8 +533,8 @@ int lbm_describe(const lbm_ctx* c, char* buf, size_t len) {
     for (int i = 0; i < NLAT; ++i) nlat += c->lat[i] ? 1 : 0;
     int n = describe_plan(c->plan, nlat, buf, len);
     if (n < 0) return n;
-    // (a nonzero lbm_set_body_motion: the single steps run k_step_solid_move / k_step_generic_move; a shape, lbm_set_solid_shape:
-    // k_step_solid_shape / k_step_generic_shape, whose table holds the motion's term too)
+    // (a nonzero lbm_set_body_motion: the single steps run k_step_solid / k_step_generic_wall in their mode WALL_MOVE; a shape,
+    // lbm_set_solid_shape: in their mode WALL_SHAPE, whose table holds the motion's term too)
     const bool shaped = (bool)c->obs.shaped.base;
     const bool moving = c->obs.moving.base || (shaped && std::any_of(c->obs.motion.begin(), c->obs.motion.end(), [](double v) { return v != 0.0; }));
     for (const char* word : {moving ? " wall_motion=1" : "", shaped ? " wall_shape=1" : ""}) {

@@ -1,7 +1,8 @@
 // lbm_solid.hip -- liblbm_hip.so: solid obstacles in the bounce-back cavity (lbm_set_solid, lbm_get_solid, lbm_solid_force of the C ABI
 // declared in include/lbm.h; LBM_SEM_BOUNCE_BACK_SOLID).  The rule is gather_a<.., SEM_SOLID> (lbm_device.hpp), the step kernel
 // k_step_solid (lbm_solid.hpp); here: the mask and the link plane derived from it, the constants of solid cells, and the momentum-
-// exchange force reduced by the tree of lbm_reduce.hpp.  gfx950 only.  DESIGN.md 2.10.
+// exchange force (k_solid_force, one template for the three modes of the wall rule) reduced by the tree of lbm_reduce.hpp.  gfx950
+// only.  DESIGN.md 2.10.
 #include "lbm_host.hpp"
 #include "lbm_reduce.hpp"
 
@@ -44,84 +45,45 @@ struct ForceAcc {
 };
 constexpr int FORCE_BLOCKS = 256;   // partial results per lattice
 
-// MOVE (k_solid_force_move, while a body motion is set): the surface moves, f_out = f - delta, and the term of a link is
-// c_opp(k) (2 f - delta), delta as the lattice adds it (the cell's row of the table of lbm_wall_motion.hpp) converted to double.
-template <typename R, bool MOVE>
-__device__ __forceinline__ void solid_force_cells(const R* __restrict__ src, const Geo& geo, long long bstride, double* __restrict__ partial,
-                                                  const int32_t* __restrict__ cell_row, const R* __restrict__ delta) {
-#pragma clang fp contract(off)
-    __shared__ double sh[BLK / RED_WAVE][ForceAcc::VALS];
-    src += blockIdx.z * bstride;
-    const long long n = (long long)geo.nx * geo.ny;
-    if (MOVE) cell_row += blockIdx.z * n;
-    ForceAcc a = ForceAcc::identity();
-    for (long long i = (long long)blockIdx.x * BLK + threadIdx.x; i < n; i += (long long)gridDim.x * BLK) {
-        const int y = (int)(i / geo.nx), x = (int)(i - (long long)y * geo.nx);
-        const long long me = geo.at(x, y);
-        const int lw = (int)src[K_LINK * geo.plane + me];
-        if ((lw & LINK_SOLID) || !(lw & 255)) continue;
-        const long long row = MOVE ? cell_row[i] : -1;
-#pragma unroll
-        for (int k = 1; k < Q; ++k)
-            if ((lw >> (k - 1)) & 1) {
-                const double f = (double)src[opp(k) * geo.plane + me];
-                a.links = a.links + 1.0;
-                if (MOVE) {
-                    const double t = 2.0 * f - (row >= 0 ? (double)delta[row * 8 + (k - 1)] : 0.0);
-                    a.fx = a.fx + (double)cxk(opp(k)) * t;
-                    a.fy = a.fy + (double)cyk(opp(k)) * t;
-                } else {
-                    a.fx = a.fx + (double)(2 * cxk(opp(k))) * f;
-                    a.fy = a.fy + (double)(2 * cyk(opp(k))) * f;
-                }
-            }
-    }
-    red_wave(a);
-    if (red_workgroup<ForceAcc, BLK / RED_WAVE>(a, sh)) red_store(partial + ((size_t)blockIdx.z * gridDim.x + blockIdx.x) * ForceAcc::VALS, a);
-}
-
-template <typename R>
-__global__ __launch_bounds__(BLK) void k_solid_force(const R* __restrict__ src, Geo geo, long long bstride, double* __restrict__ partial) {
-    solid_force_cells<R, false>(src, geo, bstride, partial, nullptr, nullptr);
-}
-
-template <typename R>
-__global__ __launch_bounds__(BLK) void k_solid_force_move(const R* __restrict__ src, Geo geo, long long bstride, double* __restrict__ partial,
-                                                          const int32_t* __restrict__ cell_row, const R* __restrict__ delta) {
-    solid_force_cells<R, true>(src, geo, bstride, partial, cell_row, delta);
-}
-
-// A shape is set (lbm_set_solid_shape): per link f_out = the cell's post-collision population of direction opp(k) as the lattice holds it
-// (its stores carry no term) and f_in = shape_rule, what the next gather of the cell returns as slot k; both converted to double, the
-// term of the link c_opp(k) (f_out + f_in).  Cells, slots and tree as k_solid_force.
-template <typename R>
-__global__ __launch_bounds__(BLK) void k_solid_force_shape(const R* __restrict__ src, Geo geo, long long bstride, double* __restrict__ partial,
-                                                           ShapeTable<R> sh) {
+// The term of a link by the mode of the wall rule (WallArg), in double without contraction:
+//   WALL_REST   f_out = f_in = f:                                         fx += 2 cx_opp(k) f
+//   WALL_MOVE   the surface moves, f_out = f - delta:                     fx += cx_opp(k) (2 f - delta), delta as the lattice adds it (the
+//               cell's row of the table of lbm_wall_motion.hpp) converted to double
+//   WALL_SHAPE  f_out = f (the stores carry no term), f_in = shape_link, what the next gather of the cell returns as slot k:
+//                                                                         fx += cx_opp(k) (f_out + f_in), both converted to double
+template <typename R, int WALL>
+__global__ __launch_bounds__(BLK) void k_solid_force(const R* __restrict__ src, Geo geo, long long bstride, double* __restrict__ partial,
+                                                     WallArg<R, WALL> wa) {
 #pragma clang fp contract(off)
     __shared__ double shm[BLK / RED_WAVE][ForceAcc::VALS];
     src += blockIdx.z * bstride;
     const long long n = (long long)geo.nx * geo.ny;
-    sh.cell_row += blockIdx.z * n;
+    wall_batch(wa, blockIdx.z, geo);
     ForceAcc a = ForceAcc::identity();
     for (long long i = (long long)blockIdx.x * BLK + threadIdx.x; i < n; i += (long long)gridDim.x * BLK) {
         const int y = (int)(i / geo.nx), x = (int)(i - (long long)y * geo.nx);
         const long long me = geo.at(x, y);
         const int lw = (int)src[K_LINK * geo.plane + me];
         if ((lw & LINK_SOLID) || !(lw & 255)) continue;
-        const long long row = sh.cell_row[i];
+        long long row = -1;
+        if constexpr (WALL == WALL_MOVE) row = wa.cell_row[i];
+        if constexpr (WALL == WALL_SHAPE) row = wa.sh.cell_row[i];
 #pragma unroll
         for (int k = 1; k < Q; ++k)
             if ((lw >> (k - 1)) & 1) {
                 const R own = src[opp(k) * geo.plane + me];
-                R g = own;
-                if (row >= 0) {
-                    const R other = ((sh.near[row] >> (k - 1)) & 1) ? src[opp(k) * geo.plane + geo.at(x + cxk(k), y - cyk(k))] : src[k * geo.plane + me];
-                    g = shape_rule<R>(own, other, sh.ad[row * 16 + (k - 1)], sh.ad[row * 16 + 8 + (k - 1)]);
-                }
-                const double t = (double)own + (double)g;
                 a.links = a.links + 1.0;
-                a.fx = a.fx + (double)cxk(opp(k)) * t;
-                a.fy = a.fy + (double)cyk(opp(k)) * t;
+                if constexpr (WALL == WALL_REST) {
+                    const double f = (double)own;
+                    a.fx = a.fx + (double)(2 * cxk(opp(k))) * f;
+                    a.fy = a.fy + (double)(2 * cyk(opp(k))) * f;
+                } else {
+                    double t;
+                    if constexpr (WALL == WALL_MOVE) t = 2.0 * (double)own - (row >= 0 ? (double)wa.delta[row * 8 + (k - 1)] : 0.0);
+                    else t = (double)own + (double)(row >= 0 ? shape_link<R, Geo>(src, geo, wa.sh.ad + row * 16, wa.sh.near[row], k, x, y, own) : own);
+                    a.fx = a.fx + (double)cxk(opp(k)) * t;
+                    a.fy = a.fy + (double)cyk(opp(k)) * t;
+                }
             }
     }
     red_wave(a);
@@ -254,18 +216,13 @@ int lbm_solid_force(lbm_ctx* c, lbm_solid_force_record* out) {
     if (rc) return rc;
     double* part = c->obs.force_part.as<double>();
     double* rec = part + (size_t)B * FORCE_BLOCKS * ForceAcc::VALS;
-    const MotionTables& m = c->obs.moving;
     rc = launch_variant(c, [&](auto v) {
-        using R = typename decltype(v)::R;
-        if (c->obs.shaped.base)
-            hipLaunchKernelGGL((k_solid_force_shape<R>), dim3(FORCE_BLOCKS, 1, B), dim3(BLK), 0, c->s_compute, c->lat[c->cur].as<const R>(), c->plan.geo,
-                               c->plan.bstride, part, c->obs.shaped.template table<R>());
-        else if (m.base)
-            hipLaunchKernelGGL((k_solid_force_move<R>), dim3(FORCE_BLOCKS, 1, B), dim3(BLK), 0, c->s_compute, c->lat[c->cur].as<const R>(), c->plan.geo,
-                               c->plan.bstride, part, m.cell_row, (const R*)m.delta);
-        else
-            hipLaunchKernelGGL((k_solid_force<R>), dim3(FORCE_BLOCKS, 1, B), dim3(BLK), 0, c->s_compute, c->lat[c->cur].as<const R>(), c->plan.geo,
-                               c->plan.bstride, part);
+        using VT = decltype(v);
+        using R = typename VT::R;
+        with_wall<VT>(c, [&](auto wa, const double*) {
+            hipLaunchKernelGGL((k_solid_force<R, decltype(wa)::MODE>), dim3(FORCE_BLOCKS, 1, B), dim3(BLK), 0, c->s_compute, c->lat[c->cur].as<const R>(),
+                               c->plan.geo, c->plan.bstride, part, wa);
+        });
         hipLaunchKernelGGL(k_solid_force_final, dim3(B), dim3(RED_WAVE), 0, c->s_compute, (const double*)part, FORCE_BLOCKS, (double)c->nsteps, rec);
     });
     if (rc) return rc;

@@ -1,8 +1,11 @@
 // lbm_solid.hpp -- solid obstacles in the bounce-back cavity (LBM_SEM_BOUNCE_BACK_SOLID; contract in include/lbm.h):
-// the one-step vector kernel of a lattice with a solid mask.  The rule itself is gather_a<.., SEM_SOLID> of lbm_device.hpp;
-// k_step_generic<.., SEM_SOLID> runs it cell by cell and is what this kernel must equal bit for bit.  Instantiated in
-// lbm_solid_f32.hip / lbm_solid_f64.hip (LBM_INST_SOLID below); lbm_solid.hip holds the host side, the kernel that gives solid cells
-// their constants and the force reduction.
+// the one-step kernels of a lattice with a solid mask, one template for the three modes of the wall rule (WALL_REST, WALL_MOVE,
+// WALL_SHAPE: WallArg, lbm_device.hpp).  The rule itself is gather_a<.., SEM_SOLID> and update_cell_a of lbm_device.hpp, which
+// k_step_generic<.., SEM_SOLID> (at rest) and k_step_generic_wall (a motion or a shape) run cell by cell; the vector kernel must equal
+// them bit for bit.  Instantiated per mode and real type in lbm_solid{,_move,_shape}_f32/f64.hip (LBM_INST_SOLID below), six units that
+// compile in parallel; lbm_solid.hip holds the host side, the kernel that gives solid cells their constants and the force reduction.
+// The mode blocks sit under `if constexpr` of the kernel template itself, so every mode's kernel is the text it would have alone (a
+// shared __forceinline__ body with a bool switch was tried first and changed the register allocation of the kernel at rest: DESIGN.md 2.10).
 #pragma once
 #include "lbm_kernels.hpp"
 
@@ -12,9 +15,16 @@
 // a solid cell takes the cell's own post-collision population of the opposite direction (one more aligned 16-byte load per direction),
 // the lid row adds Ladd's term from the parked density and parks the new one, and solid lanes keep their constants w_k.  Arithmetic
 // per cell: collide_vec, the operations of update_cell.
-template <typename R, int COLL, bool NT>
+//   WALL_SHAPE  the cell's eight stored slots are loaded first; a lane's link k then takes shape_rule(own = stored opp(k), other = the
+//               regular pull of slot opp(k) (near) or stored k (far), a, d) from the cell's row of the table.  The pull of a near link's
+//               slot opp(k) is never overwritten: its source is a fluid cell inside the lattice.  (shape_link of lbm_device.hpp loads
+//               `other`; here both candidates are in registers already, so the choice is spelled in place.)
+//   WALL_MOVE   between the collision and the pinning of the solid lanes a fluid lane with links adds the delta of link k to its
+//               post-collision population of direction opp(k), one add in the lattice type, in the raw first step too.  Only lanes
+//               whose link word has a link bit read the table.
+template <typename R, int COLL, bool NT, int WALL>
 __global__ __launch_bounds__(BLK) void k_step_solid(const R* __restrict__ src, R* __restrict__ dst, Geo geo, Relax<R> w, Batch<R> bt, int raw,
-                                                    int row0, int row_stride, int nxb, int nblocks) {
+                                                    int row0, int row_stride, int nxb, int nblocks, WallArg<R, WALL> wa) {
     constexpr int V = 16 / (int)sizeof(R);
     typedef typename VecT<R, V>::type T;
     LBM_BATCH_SELECT(blockIdx.y)
@@ -39,15 +49,51 @@ __global__ __launch_bounds__(BLK) void k_step_solid(const R* __restrict__ src, R
     const bool lid = gy == 0;
     const bool special = any != 0 || x0 == 0 || x0 + V >= geo.nx || lid || gy == geo.NY - 1;
     if (special && !raw) {
+        if constexpr (WALL == WALL_SHAPE) {
+            T st[Q];   // the cell's own stored slots
 #pragma unroll
-        for (int k = 1; k < Q; ++k) {
-            const T own = vload<R, V, NT>(src + opp(k) * geo.plane + me, true);
-            const int sgy = gy + cyk(k);
-            const bool out_y = sgy < 0 || sgy >= geo.NY;
+            for (int k = 1; k < Q; ++k) st[k] = vload<R, V, NT>(src + k * geo.plane + me, true);
+            // the rows of the lanes that have links (fluid lanes only)
+            int row[V];
 #pragma unroll
-            for (int c = 0; c < V; ++c) {
-                const int sx = x0 + c - cxk(k);
-                if (out_y || sx < 0 || sx >= geo.nx || ((lw[c] >> (k - 1)) & 1)) in[k][c] = own[c];
+            for (int c = 0; c < V; ++c) row[c] = -1;
+            if (any & 255) {
+                const int32_t* const cr = wa.sh.cell_row + batch_cells(blockIdx.y, geo) + (long long)y * geo.nx + x0;
+#pragma unroll
+                for (int c = 0; c < V; ++c)
+                    if ((lw[c] & 255) && !(lw[c] & LINK_SOLID)) row[c] = cr[c];
+            }
+#pragma unroll
+            for (int k = 1; k < Q; ++k) {
+                const int sgy = gy + cyk(k);
+                const bool out_y = sgy < 0 || sgy >= geo.NY;
+#pragma unroll
+                for (int c = 0; c < V; ++c) {
+                    const int sx = x0 + c - cxk(k);
+                    if (out_y || sx < 0 || sx >= geo.nx) {
+                        in[k][c] = st[opp(k)][c];
+                    } else if ((lw[c] >> (k - 1)) & 1) {
+                        if (row[c] >= 0) {
+                            const R* const ad = wa.sh.ad + (long long)row[c] * 16;
+                            const R other = ((wa.sh.near[row[c]] >> (k - 1)) & 1) ? in[opp(k)][c] : st[k][c];
+                            in[k][c] = shape_rule<R>(st[opp(k)][c], other, ad[k - 1], ad[8 + k - 1]);
+                        } else {
+                            in[k][c] = st[opp(k)][c];
+                        }
+                    }
+                }
+            }
+        } else {   // (at rest, and a motion: its term is on the store side)
+#pragma unroll
+            for (int k = 1; k < Q; ++k) {
+                const T own = vload<R, V, NT>(src + opp(k) * geo.plane + me, true);
+                const int sgy = gy + cyk(k);
+                const bool out_y = sgy < 0 || sgy >= geo.NY;
+#pragma unroll
+                for (int c = 0; c < V; ++c) {
+                    const int sx = x0 + c - cxk(k);
+                    if (out_y || sx < 0 || sx >= geo.nx || ((lw[c] >> (k - 1)) & 1)) in[k][c] = own[c];
+                }
             }
         }
         if (lid) {
@@ -61,6 +107,23 @@ __global__ __launch_bounds__(BLK) void k_step_solid(const R* __restrict__ src, R
         }
     }
     collide_vec<R, COLL, V, false>(in, w, outv, hq, hr);
+    if constexpr (WALL == WALL_MOVE) {
+        if (any & 255) {
+            const int32_t* cell_row = wa.cell_row;
+            const R* const delta = wa.delta;
+            cell_row += batch_cells(blockIdx.y, geo) + (long long)y * geo.nx + x0;
+#pragma unroll
+            for (int c = 0; c < V; ++c)
+                if ((lw[c] & 255) && !(lw[c] & LINK_SOLID)) {
+                    const int row = cell_row[c];
+                    if (row < 0) continue;
+                    const R* const d = delta + (long long)row * 8;
+#pragma unroll
+                    for (int k = 1; k < Q; ++k)
+                        if ((lw[c] >> (k - 1)) & 1) outv[opp(k)][c] = outv[opp(k)][c] + d[k - 1];
+                }
+        }
+    }
     if (any & LINK_SOLID) {
 #pragma unroll
         for (int c = 0; c < V; ++c)
@@ -83,15 +146,41 @@ __global__ __launch_bounds__(BLK) void k_step_solid(const R* __restrict__ src, R
     }
 }
 
-#define LBM_SOLID_ONE(R, COLL)                                                                                                  \
-    LBM_SX template __global__ void k_step_solid<R, COLL, false>(const R* __restrict__, R* __restrict__, Geo, Relax<R>, Batch<R>, int, int, int, int, int); \
-    LBM_SX template __global__ void k_step_solid<R, COLL, true>(const R* __restrict__, R* __restrict__, Geo, Relax<R>, Batch<R>, int, int, int, int, int);
-#define LBM_INST_SOLID(R) \
-    LBM_SOLID_ONE(R, C_SRT) LBM_SOLID_ONE(R, C_TRT) LBM_SOLID_ONE(R, C_MRT) LBM_SOLID_ONE(R, C_MRT_FAST) LBM_SOLID_ONE(R, C_SRT_FAST) LBM_SOLID_ONE(R, C_TRT_FAST)
+// One thread per cell (kernel = GENERIC, and lattices whose nx is no multiple of the vector width) while a motion or a shape is set:
+// k_step_generic<.., SEM_SOLID> with the mode of update_cell_a.  At rest k_step_generic itself is what launches.
+template <typename R, int COLL, int WALL>
+__global__ __launch_bounds__(BLK) void k_step_generic_wall(const R* __restrict__ src, R* __restrict__ dst, Geo geo, Relax<R> w, Batch<R> bt, int raw,
+                                                           int row0, int row_stride, WallArg<R, WALL> wa) {
+    const int x = blockIdx.x * BLK + threadIdx.x;
+    const int y = row0 + blockIdx.y * row_stride;
+    if (x >= geo.nx) return;
+    LBM_BATCH_SELECT(blockIdx.z)
+    wall_batch(wa, blockIdx.z, geo);
+    update_cell_a<R, COLL, SEM_SOLID, false, Geo, Geo, WALL>(src, geo, dst, geo, geo, w, raw, x, y, nullptr, wa);
+}
+
+// LBM_INST_SOLID(R, WALL): the six operator variants of one real type and mode -- the vector kernel with and without non-temporal
+// accesses, and k_step_generic_wall where the mode has one (LBM_SX: `extern`, or nothing in the unit that compiles them)
+#define LBM_SOLID_GENERIC_WALL_REST(R, COLL)
+#define LBM_SOLID_GENERIC_WALL_MOVE(R, COLL) \
+    LBM_SX template __global__ void k_step_generic_wall<R, COLL, WALL_MOVE>(const R* __restrict__, R* __restrict__, Geo, Relax<R>, Batch<R>, int, int, int, WallArg<R, WALL_MOVE>);
+#define LBM_SOLID_GENERIC_WALL_SHAPE(R, COLL) \
+    LBM_SX template __global__ void k_step_generic_wall<R, COLL, WALL_SHAPE>(const R* __restrict__, R* __restrict__, Geo, Relax<R>, Batch<R>, int, int, int, WallArg<R, WALL_SHAPE>);
+#define LBM_SOLID_ONE(R, COLL, WALL)                                                                                                                          \
+    LBM_SX template __global__ void k_step_solid<R, COLL, false, WALL>(const R* __restrict__, R* __restrict__, Geo, Relax<R>, Batch<R>, int, int, int, int, int, \
+                                                                       WallArg<R, WALL>);                                                                     \
+    LBM_SX template __global__ void k_step_solid<R, COLL, true, WALL>(const R* __restrict__, R* __restrict__, Geo, Relax<R>, Batch<R>, int, int, int, int, int,  \
+                                                                      WallArg<R, WALL>);                                                                      \
+    LBM_SOLID_GENERIC_##WALL(R, COLL)
+#define LBM_INST_SOLID(R, WALL)                                                                                                  \
+    LBM_SOLID_ONE(R, C_SRT, WALL) LBM_SOLID_ONE(R, C_TRT, WALL) LBM_SOLID_ONE(R, C_MRT, WALL) LBM_SOLID_ONE(R, C_MRT_FAST, WALL) \
+    LBM_SOLID_ONE(R, C_SRT_FAST, WALL) LBM_SOLID_ONE(R, C_TRT_FAST, WALL)
 #ifdef LBM_SOLID_INST
 #define LBM_SX
 LBM_SOLID_INST
 #else
 #define LBM_SX extern
-LBM_INST_SOLID(float) LBM_INST_SOLID(double)
+LBM_INST_SOLID(float, WALL_REST) LBM_INST_SOLID(double, WALL_REST)
+LBM_INST_SOLID(float, WALL_MOVE) LBM_INST_SOLID(double, WALL_MOVE)
+LBM_INST_SOLID(float, WALL_SHAPE) LBM_INST_SOLID(double, WALL_SHAPE)
 #endif

@@ -1,4 +1,4 @@
-// lbm_solid_f64.hip -- the double instantiations of k_step_solid (lbm_solid.hpp): the six operator variants, with and without
-// non-temporal accesses.
-#define LBM_SOLID_INST LBM_INST_SOLID(double)
+// lbm_solid_f64.hip -- the double instantiations of k_step_solid at rest (lbm_solid.hpp): the six operator
+// variants, the vector kernel with and without non-temporal accesses.
+#define LBM_SOLID_INST LBM_INST_SOLID(double, WALL_REST)
 #include "lbm_solid.hpp"

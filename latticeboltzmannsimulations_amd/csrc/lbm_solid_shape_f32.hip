@@ -1,4 +1,4 @@
-// lbm_solid_shape_f32.hip -- the float instantiations of k_step_solid_shape and k_step_generic_shape (lbm_solid_shape.hpp): the six operator
+// lbm_solid_shape_f32.hip -- the float instantiations of k_step_solid and k_step_generic_wall with a shape (WALL_SHAPE) (lbm_solid.hpp): the six operator
 // variants, the vector kernel with and without non-temporal accesses.
-#define LBM_SHAPE_INST LBM_INST_SHAPE(float)
-#include "lbm_solid_shape.hpp"
+#define LBM_SOLID_INST LBM_INST_SOLID(float, WALL_SHAPE)
+#include "lbm_solid.hpp"

@@ -227,7 +227,7 @@ def test_every_route_at_rest_gives_the_same_bits_at_distinct_rates(dtype, coll):
 @pytest.mark.parametrize("coll", COLLS)
 @pytest.mark.parametrize("dtype", [np.float32, np.float64])
 def test_the_moving_twins_give_the_same_bits_at_distinct_rates(dtype, coll):
-    """k_step_solid_move (96 x 80) and k_step_generic_move (96 x 80 with kernel="generic"; 70 x 66 under `auto` in fp32) from S2 at the
+    """k_step_solid<.., WALL_MOVE> (96 x 80) and k_step_generic_wall<.., WALL_MOVE> (96 x 80 with kernel="generic"; 70 x 66 under `auto` in fp32) from S2 at the
     distinct rates: strict is MovingWallOracle's bits, fast one set of bits per shape.  (On 70 x 66 in fp32 `auto` and "generic" are
     the same kernel and the fast comparison is trivial; 96 x 80 in both types and 70 x 66 in fp64 compare the two twins.)"""
     V = 4 if dtype == np.float32 else 2

@@ -1,6 +1,6 @@
 """GPU tests of the wall velocity on solid bodies (CavitySolver.set_body_motion, lbm_set_body_motion): strict arithmetic bit for bit
-against the NumPy reference tests/moving_wall_ref.py on the vector kernel (k_step_solid_move) and the generic route
-(k_step_generic_move); zero motion gives the bits and the kernels of obstacles at rest; `fast` arithmetic within the bound of a mask at
+against the NumPy reference tests/moving_wall_ref.py on the vector kernel (k_step_solid<.., WALL_MOVE>) and the generic route
+(k_step_generic_wall<.., WALL_MOVE>); zero motion gives the bits and the kernels of obstacles at rest; `fast` arithmetic within the bound of a mask at
 rest; batches; the force with 2 f - delta, one-shot, as a series and summed; the error paths; the checkpoint; and Taylor-Couette flow
 between a rotating disc and a ring at rest against its closed form."""
 import numpy as np

@@ -1,5 +1,5 @@
 """GPU tests of curved obstacle surfaces (CavitySolver.set_shape, lbm_set_solid_shape): strict arithmetic bit for bit against the NumPy
-reference tests/curved_wall_ref.py on the vector kernel (k_step_solid_shape) and the generic route (k_step_generic_shape), at rest, with a
+reference tests/curved_wall_ref.py on the vector kernel (k_step_solid<.., WALL_SHAPE>) and the generic route (k_step_generic_wall<.., WALL_SHAPE>), at rest, with a
 motion and with a motion changed between two steps; all q = 1/2 gives the bits of the contexts without a shape; every sampler sees the
 rule through the one view; the force with f_out + f_in and the wall point; `fast` arithmetic against the same mask without a shape; the
 error paths; the checkpoint; and the point of it all: the torque of Taylor-Couette flow converges at second order with the shape and
@@ -121,7 +121,7 @@ def test_strict_bit_identical_to_reference(coll, dtype, shape):
 @pytest.mark.parametrize("dtype", [np.float32, np.float64])
 def test_all_half_is_the_half_way_context(dtype):
     """All q = 1/2, at rest and with a motion, on both routes: every exported bit of the contexts that never heard of a shape (which run
-    k_step_solid / k_step_solid_move and their generic twins), and after the shape is cleared their kernels again."""
+    k_step_solid at rest / with WALL_MOVE and their generic twins), and after the shape is cleared their kernels again."""
     nx, ny = 72, 40
     m, lab, nb, mot = _own_cases(nx, ny)["between"]
     half = np.full((8, nx, ny), 0.5)
@@ -261,7 +261,7 @@ def test_force_is_f_out_plus_f_in_at_the_wall_point(dtype):
 @pytest.mark.parametrize("coll", ["SRT", "TRT", "MRT"])
 def test_fast_arithmetic(coll, dtype):
     """`fast` with a shape: the two routes agree bit for bit, and after 26 steps from an off-equilibrium state its distance from strict
-    fp64 is at most twice the distance the same mask and motion show WITHOUT a shape (all walls half-way: k_step_solid_move, the kernel
+    fp64 is at most twice the distance the same mask and motion show WITHOUT a shape (all walls half-way: k_step_solid<.., WALL_MOVE>, the kernel
     the shape did not touch), measured here in the same way: the rule adds no `fast` arithmetic of its own."""
     nx, ny = 72, 40
     m, lab, nb, mot = _own_cases(nx, ny)["block"]
