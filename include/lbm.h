@@ -622,6 +622,47 @@ int lbm_get_body_motion(lbm_ctx* c, double* motion_out);
 int lbm_set_solid_shape(lbm_ctx* c, const double* q);
 int lbm_get_solid_shape(lbm_ctx* c, double* q_out);
 
+/* --- open boundaries: held outlet cells and a wall velocity per solid cell -------------------------- */
+/* No reference counterpart.  The two pieces that turn the closed cavity into a stream or a channel (LBM_SEM_BOUNCE_BACK_SOLID only): cells
+ * that keep prescribed populations -- a pressure or far-field outlet, a reservoir -- and a wall velocity on single solid cells -- a velocity
+ * bounce-back inlet with any profile.  Bodies, force series, shapes, samplers, topology and checkpoints work on such a lattice unchanged.
+ *
+ * Hold cells.  A hold cell is never updated: it holds f_k, rounded once to the lattice type, in both lattices, the way a solid cell holds
+ *   w_k.  It is NOT a wall: a neighbour pulls f_k from it by the plain pull.  In plane K_LINK the hold cell's own word is exactly 512 (bit
+ *   9, no link bits: it reads no wall table), and no neighbour's word has a bit for it.  A gather on it returns the nine stored values, so
+ *   every export and sampler sees fin_k = the held value and u, rho its moments.  For the `near` test of a shape a hold cell is no fluid
+ *   cell (the effective q = 1/2 applies), and no link of the force lists starts at one.
+ * lbm_set_open_cells: hold[B][X][Y] in the layout of the mask, nonzero = hold cell, NULL (or all zero) clears; f[B][9][X][Y] doubles, read
+ *   on hold cells only.  Ends every sampler, stores the cells, rewrites plane K_LINK and performs lbm_init_equilibrium, as lbm_set_solid
+ *   does; after every initialisation and lbm_set_state the hold cells are written again from the context's table (host values there are
+ *   ignored).  LBM_ERR_INVALID: a hold cell that is solid, a value on a hold cell that is not finite or is negative, a lattice left without
+ *   a fluid cell, hold without f.  LBM_ERR_STATE: another semantics; a LBM_FLAG_SOLID_TILES context (the tile kernel never sees bit 9);
+ *   a shape, a nonzero motion or a nonzero wall velocity is set -- geometry comes first.  lbm_set_solid clears the hold cells;
+ *   lbm_set_solid_bodies keeps them.  lbm_describe appends ` open_cells=1` while there are any.
+ * lbm_get_open_cells: hold_out[B][X][Y] receives 0 / 1, f_out[B][9][X][Y] the values as given on the hold cells and 0 elsewhere; either
+ *   may be NULL.
+ *
+ * Wall velocity per solid cell.  uw[B][2][X][Y], components as u, read on solid cells only.  For a link with the fluid cell P, slot k and
+ *   the source solid cell S = (x - cx_k, y + cy_k) the delta of lbm_set_body_motion becomes
+ *       delta = delta_body + (6 w_k) (cx_k uwx(S) + cy_k uwy(S))
+ *   in double without contraction: the rigid-body term first, formed exactly as above (at the wall point under a shape); then the cell
+ *   term, each product and sum rounded in the order written; then the add.  From there everything is what a motion does: the store-side
+ *   add, `d = near ? delta : a delta` of a shape's table, (2 f - delta) in the forces.  One table holds both; each of the two calls
+ *   rebuilds it from both, in either order.
+ * Flux check: a lattice with at least one hold cell is open and the check of lbm_set_body_motion is waived for it; a lattice without one
+ *   is checked as before, with the cell terms inside S and A.
+ * lbm_set_wall_velocity: NULL means all zero.  The rules of lbm_set_body_motion: LBM_ERR_STATE on another semantics and, nonzero, on a
+ *   LBM_FLAG_SOLID_TILES context; LBM_ERR_INVALID for a value on a solid cell that is not finite and for a refused flux; the shape first,
+ *   then velocities (lbm_set_solid_shape refuses while one is set); touches neither the lattice nor the step count and ends no sampler.
+ *   An all-zero motion with an all-zero velocity frees the table: the context launches the kernels of obstacles at rest.  lbm_set_solid
+ *   resets it; lbm_set_solid_bodies keeps it and rebuilds the table for the new labels and centres (and may therefore refuse a flux).
+ *   lbm_describe appends ` wall_velocity=1` while a nonzero velocity is set.
+ * lbm_get_wall_velocity: uw_out[B][2][X][Y] receives the velocity as set on solid cells and 0 elsewhere. */
+int lbm_set_open_cells(lbm_ctx* c, const uint8_t* hold, const double* f);
+int lbm_get_open_cells(lbm_ctx* c, uint8_t* hold_out, double* f_out);
+int lbm_set_wall_velocity(lbm_ctx* c, const double* uw);
+int lbm_get_wall_velocity(lbm_ctx* c, double* uw_out);
+
 /* --- slab decomposition, externally driven exchange ---------------------------------- */
 /* No reference counterpart (the reference is single-GPU, MRT_GPU.py:29).  A step of a slab
  * is split so that a host-language driver can move halos with any transport:

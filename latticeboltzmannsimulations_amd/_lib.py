@@ -179,6 +179,10 @@ SIGNATURES = {
     "lbm_get_body_motion": (_i, [_vp, _vp]),
     "lbm_set_solid_shape": (_i, [_vp, _vp]),            # (q: [B][8][X][Y] doubles, or NULL)
     "lbm_get_solid_shape": (_i, [_vp, _vp]),
+    "lbm_set_open_cells": (_i, [_vp, _vp, _vp]),        # (hold: [B][X][Y] uint8 or NULL; f: [B][9][X][Y] doubles)
+    "lbm_get_open_cells": (_i, [_vp, _vp, _vp]),
+    "lbm_set_wall_velocity": (_i, [_vp, _vp]),          # (uw: [B][2][X][Y] doubles, or NULL)
+    "lbm_get_wall_velocity": (_i, [_vp, _vp]),
     "lbm_halo_elems": (_i, [_vp]),
     "lbm_halo_export": (_i, [_vp, _i, _vp]),
     "lbm_halo_import": (_i, [_vp, _i, _vp]),

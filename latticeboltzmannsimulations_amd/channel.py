@@ -1,0 +1,136 @@
+"""Flow past a body in a stream or a channel, on the bounce-back cavity with open boundaries (CavitySolver.set_open_cells,
+set_wall_velocity).
+
+The lattice is [X, Y] with the stream along x.  Rows 0 and Y - 1 are solid side walls, so the walls sit half-way between rows 0 / 1 and
+Y - 2 / Y - 1 and the channel is H = Y - 2 cells wide; column 0 is a solid inlet wall whose cells carry the inflow profile as their wall
+velocity (a velocity bounce-back inlet); the cells of column X - 1 between the walls are hold cells at the equilibrium of rho = 1 and
+the same profile (a pressure outlet with the far-field velocity).  The lid of the cavity lies behind the solid row 0 and drives nothing.
+
+    python -m latticeboltzmannsimulations_amd.channel --xsize 440 --ysize 84 --Re-D 20 --umax 0.05 --disc 40 41.5 10 --curved --force-every 50
+"""
+import argparse
+import sys
+
+import numpy as np
+
+from . import solid as S
+
+
+def inflow_profile(ny, umax, kind="parabolic"):
+    """ux[Y] of the inflow: 'parabolic' -- umax 4 (y - 1/2) (Y - 3/2 - y) / (Y - 2)^2, which vanishes on the walls, half a cell outside
+    rows 1 and Y - 2 -- or 'plug', umax on every row; zero on the wall rows 0 and Y - 1 themselves."""
+    if kind not in ("parabolic", "plug"):
+        raise ValueError("profile must be 'parabolic' or 'plug'")
+    y = np.arange(int(ny), dtype=np.float64)
+    u = np.full(int(ny), float(umax)) if kind == "plug" else float(umax) * 4.0 * (y - 0.5) * (ny - 1.5 - y) / (ny - 2.0) ** 2
+    u[0] = u[-1] = 0.0
+    return u
+
+
+def channel(nx, ny, umax, profile="parabolic", walls="rest", disc=None, curved=False):
+    """The geometry of a channel (walls='rest': side walls at rest) or of a free stream (walls='stream': the side rows slide at umax) as a
+    dict: solid [X, Y]; labels [X, Y] -- body 0 the side walls, body 1 the inlet column, each obstacle a body of its own after them --
+    and nbodies; hold [X, Y] with f [9, X, Y]; wall_velocity [2, X, Y]; profile [Y], mean (the mean of the profile over the H = Y - 2
+    rows between the walls) and H.  disc=(x0, y0, r), or a list of them: solid discs (solid.discs_into); curved=True: `shape`
+    [8, X, Y], the exact wall distances of the discs' links (solid.disc_fractions), 1/2 on every other link."""
+    nx, ny = int(nx), int(ny)
+    if nx < 4 or ny < 4:
+        raise ValueError("a channel needs at least 4 x 4 cells")
+    if walls not in ("rest", "stream"):
+        raise ValueError("walls must be 'rest' or 'stream'")
+    prof = inflow_profile(ny, umax, profile)
+    m = np.zeros((nx, ny), dtype=bool)
+    m[:, 0] = m[:, ny - 1] = m[0, :] = True
+    lab = np.full((nx, ny), -1, dtype=np.int32)
+    lab[0, :] = 1
+    lab[:, 0] = lab[:, ny - 1] = 0
+    n = 2
+    discs = [] if disc is None else ([tuple(disc)] if np.ndim(disc) == 1 else [tuple(d) for d in disc])
+    if discs:
+        m, lab, n = S.discs_into(nx, ny, discs, m, lab, n)
+    hold = np.zeros((nx, ny), dtype=bool)
+    hold[nx - 1, 1:ny - 1] = True
+    if (hold & m).any():
+        raise ValueError("an obstacle covers the outlet column")
+    uw = np.zeros((2, nx, ny))
+    uw[0, 0, :] = prof
+    if walls == "stream":
+        uw[0, :, 0] = uw[0, :, ny - 1] = float(umax)
+    f = S.equilibrium(1.0, np.broadcast_to(prof[None, :], (nx, ny)), 0.0)
+    out = dict(solid=m, labels=lab, nbodies=n, hold=hold, f=f, wall_velocity=uw, profile=prof, mean=float(prof[1:ny - 1].mean()), H=ny - 2,
+               discs=discs)
+    if curved:
+        q = None
+        for x0, y0, r in discs:
+            q = S.disc_fractions(m, x0, y0, r, q)
+        out["shape"] = np.full((8, nx, ny), 0.5) if q is None else q
+    return out
+
+
+def solver_re(Re_D, D, umax, mean, ny):
+    """The solver's Re for a Reynolds number of the obstacle, Re_D = mean D / nu: the solver derives nu = uLB ysize / Re with
+    uLB = umax, so Re = umax ysize Re_D / (mean D)."""
+    return float(umax) * float(ny) * float(Re_D) / (float(mean) * float(D))
+
+
+def run_channel(nx, ny, Re_D, umax=0.05, disc=None, curved=False, profile="parabolic", walls="rest", steps=20000, force_every=100, RT="MRT",
+                dtype=np.float32, arith="strict", device=0, solver_factory=None, quiet=False):
+    """Step a channel and keep the force series of the (first) obstacle on the device.  Returns dict(Cd, Cl, fx, fy, steps, Re, nu,
+    series): Cd = 2 Fx / (rho mean^2 D), Cl likewise from Fy, of the last sample (rho = 1); D = 2 r of the disc (without one: the
+    channel's width and the force on the side walls).  Re_D = mean D / nu is converted to the solver's Re (solver_re)."""
+    g = channel(nx, ny, umax, profile, walls, disc, curved)
+    D = 2.0 * g["discs"][0][2] if g["discs"] else float(g["H"])
+    body = 2 if g["discs"] else 0
+    Re = solver_re(Re_D, D, umax, g["mean"], ny)
+    nu = float(umax) * ny / Re
+    if solver_factory is None:
+        from .solver import CavitySolver as solver_factory
+    if not quiet:
+        print(f"channel {nx} x {ny}: Re_D = {Re_D:g} on D = {D:g} with the mean velocity {g['mean']:.6g} -> nu = {nu:.6g}, "
+              f"the solver's Re = umax ysize / nu = {Re:.6g}")
+    with solver_factory(nx, ny, Re, RT=RT, uLB=umax, semantics="bounce_back", dtype=dtype, arith=arith, device=device, solid=g["solid"],
+                        bodies=g["labels"]) as s:
+        s.set_open_cells(g["hold"], g["f"])
+        if curved:
+            s.set_shape(g["shape"])
+        s.set_wall_velocity(g["wall_velocity"])
+        every = max(1, int(force_every))
+        s.step(1)
+        s.begin_force(every=every, capacity=max(1, int(steps) // every + 1))
+        s.step(int(steps) - 1)
+        s.sample_force()
+        series = s.force_series()
+        s.end_force()
+    fx, fy = float(series["fx"][-1][body]), float(series["fy"][-1][body])
+    scale = 2.0 / (g["mean"] ** 2 * D)
+    out = dict(Cd=scale * fx, Cl=scale * fy, fx=fx, fy=fy, steps=int(steps), Re=Re, nu=nu, series=series, body=body)
+    if not quiet:
+        print(f"after {steps} steps: Fx = {fx:.8g}, Fy = {fy:.8g}, Cd = 2 Fx / (rho mean^2 D) = {out['Cd']:.6g}, Cl = {out['Cl']:.6g}")
+    return out
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(prog="python -m latticeboltzmannsimulations_amd.channel", description=__doc__.split("\n\n")[0])
+    ap.add_argument("--xsize", type=int, default=440)
+    ap.add_argument("--ysize", type=int, default=84)
+    ap.add_argument("--Re-D", dest="Re_D", type=float, default=20.0)
+    ap.add_argument("--umax", type=float, default=0.05)
+    ap.add_argument("--disc", type=float, nargs=3, metavar=("X0", "Y0", "R"), default=None)
+    ap.add_argument("--curved", action="store_true")
+    ap.add_argument("--profile", choices=("parabolic", "plug"), default="parabolic")
+    ap.add_argument("--walls", choices=("rest", "stream"), default="rest")
+    ap.add_argument("--steps", type=int, default=20000)
+    ap.add_argument("--force-every", dest="force_every", type=int, default=100)
+    ap.add_argument("--RT", choices=("SRT", "TRT", "MRT"), default="MRT")
+    ap.add_argument("--dtype", choices=("float32", "float64"), default="float32")
+    ap.add_argument("--device", type=int, default=0)
+    a = ap.parse_args(argv)
+    if a.curved and a.disc is None:
+        ap.error("--curved gives the disc its exact wall distances: it needs --disc")
+    run_channel(a.xsize, a.ysize, a.Re_D, a.umax, a.disc, a.curved, a.profile, a.walls, a.steps, a.force_every, a.RT, np.dtype(a.dtype).type,
+                device=a.device)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

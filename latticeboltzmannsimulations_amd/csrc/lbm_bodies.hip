@@ -106,9 +106,11 @@ __global__ __launch_bounds__(RED_WAVE) void k_body_force_final(const double* __r
     }
 }
 
-// The tables of the mask, labels and centres of `o` (lbm_bodies.hpp lays them out), built on the host and uploaded into `out`.
-static int body_tables(lbm_ctx* c, const std::vector<uint8_t>& mask, const Obstacles& o, BodyTables& out) {
-    const BodyParts t = body_parts(mask.data(), o.label.data(), o.centre.data(), c->plan.batch, c->plan.geo.nx, c->plan.geo.ny, o.nbodies, BodyAcc::VALS, REC);
+// The tables of the mask, labels and centres of `o` (lbm_bodies.hpp lays them out), built on the host and uploaded into `out`.  hold:
+// the hold cells (null: none), at which no link starts.
+static int body_tables(lbm_ctx* c, const std::vector<uint8_t>& mask, const Obstacles& o, BodyTables& out, const uint8_t* hold) {
+    const BodyParts t = body_parts(mask.data(), o.label.data(), o.centre.data(), c->plan.batch, c->plan.geo.nx, c->plan.geo.ny, o.nbodies, BodyAcc::VALS, REC,
+                                   hold);
     if (t.maxchunks > 0x7fffffffu) return fail(c, LBM_ERR_INVALID, "the mask has too many links for the force tables");
     Pack<HipMem> p = upload<HipMem>(t.parts(), "body tables");
     if (!p.err.empty()) return fail(c, p.no_memory ? LBM_ERR_NOMEM : LBM_ERR_HIP, p.err);
@@ -123,14 +125,18 @@ static int body_tables(lbm_ctx* c, const std::vector<uint8_t>& mask, const Obsta
     return LBM_OK;
 }
 
-// The one writer of c->obs.  `next` holds the new host state of `level` (mask; nbodies, label, centre; motion) and nothing else.  The
-// levels below it are reset -- a new mask: one body that holds every solid cell, centred at its centroid; new bodies: every body at
-// rest -- the tables of everything that changed are built aside, and only then does the context change, by moves: on any failure
-// its obstacle state is what it was.  before_commit runs between the two (lbm_set_solid: the link planes).  The caller has
-// synchronised the streams.  The shape (lbm_set_solid_shape) stands beside the motion: ObsLevel::shape replaces or clears it (next.shape_q,
-// every body at rest: the caller checked) and touches nothing else; a new mask drops it; new bodies and a new motion keep q and rebuild
-// its tables, which then carry the motion's term -- a shaped context never holds MotionTables.
-int obstacles_change(lbm_ctx* c, ObsLevel level, Obstacles& next, int (*before_commit)(lbm_ctx*, const Obstacles&)) {
+// The one writer of c->obs.  `next` holds the new host state of `level` (mask; nbodies, label, centre; motion and wall_uw) and nothing
+// else.  The levels below it are reset -- a new mask: one body that holds every solid cell, centred at its centroid, no hold cells, no
+// wall velocity; new bodies: every body at rest (the wall velocity per cell stays) -- the tables of everything that changed are built
+// aside, and only then does the context change, by moves: on any failure its obstacle state is what it was.  before_commit runs between
+// the two (lbm_set_solid, lbm_set_open_cells: the link planes).  The caller has synchronised the streams.  The shape
+// (lbm_set_solid_shape) stands beside the motion: ObsLevel::shape replaces or clears it (next.shape_q, every surface at rest: the caller
+// checked) and touches nothing else; a new mask drops it; new bodies and a new motion keep q and rebuild its tables, which then carry
+// the motion's term -- a shaped context never holds MotionTables.  ObsLevel::motion takes both halves of the wall velocity, the bodies'
+// motion and the cells' own (lbm_set_body_motion and lbm_set_wall_velocity each pass the other's as the context holds it; `call`: who,
+// for the refusal of the flux check).  ObsLevel::open (lbm_set_open_cells; nothing moves and there is no shape: the caller checked):
+// next.hold, next.hold_f and next.open replace the hold cells, and the bodies' tables are rebuilt, since no link starts at a hold cell.
+int obstacles_change(lbm_ctx* c, ObsLevel level, Obstacles& next, int (*before_commit)(lbm_ctx*, const Obstacles&), const char* call) {
     Obstacles& cur = c->obs;
     const int B = c->plan.batch, nx = c->plan.geo.nx, ny = c->plan.geo.ny;
     const size_t n = (size_t)nx * ny;
@@ -154,18 +160,29 @@ int obstacles_change(lbm_ctx* c, ObsLevel level, Obstacles& next, int (*before_c
         cur.shaped = std::move(next.shaped);
         return LBM_OK;
     }
+    if (level == ObsLevel::open) {
+        next.nbodies = cur.nbodies; next.label = cur.label; next.centre = cur.centre;
+        rc = body_tables(c, cur.mask, next, next.body, next.hold_or_null());
+        if (rc == LBM_OK && before_commit) rc = before_commit(c, next);
+        if (rc) return rc;
+        sampler_free(c, SMP_FORCE);   // (its link list changed)
+        cur.body = std::move(next.body);
+        cur.hold = std::move(next.hold);
+        cur.hold_f = std::move(next.hold_f);
+        cur.open = std::move(next.open);
+        return LBM_OK;
+    }
     if (level != ObsLevel::motion) {
         next.motion.assign((size_t)B * next.nbodies * 3, 0.0);
-        rc = body_tables(c, level == ObsLevel::mask ? next.mask : cur.mask, next, next.body);
+        if (level == ObsLevel::bodies) next.wall_uw = cur.wall_uw;   // (a new mask: none)
+        rc = body_tables(c, level == ObsLevel::mask ? next.mask : cur.mask, next, next.body, level == ObsLevel::mask ? nullptr : cur.hold_or_null());
+        if (rc == LBM_OK && shaped) rc = motion_tables(c, next, next.moving, true, call);
         if (rc == LBM_OK && shaped) rc = shape_tables(c, next, cur.shape_q, next.shaped, &next.shape_eff);
-    } else if (shaped) {
-        rc = motion_tables(c, next, next.moving, true);
-        if (rc == LBM_OK) {
-            next.nbodies = cur.nbodies; next.label = cur.label; next.centre = cur.centre;
-            rc = shape_tables(c, next, cur.shape_q, next.shaped, &next.shape_eff);
-        }
+        else if (rc == LBM_OK && level == ObsLevel::bodies) rc = motion_tables(c, next, next.moving, false, call);
     } else {
-        rc = motion_tables(c, next, next.moving);
+        next.nbodies = cur.nbodies; next.label = cur.label; next.centre = cur.centre;
+        rc = motion_tables(c, next, next.moving, shaped, call);
+        if (rc == LBM_OK && shaped) rc = shape_tables(c, next, cur.shape_q, next.shaped, &next.shape_eff);
     }
     if (rc == LBM_OK && before_commit) rc = before_commit(c, next);
     if (rc) return rc;
@@ -174,6 +191,9 @@ int obstacles_change(lbm_ctx* c, ObsLevel level, Obstacles& next, int (*before_c
         cur.shape_q.clear();
         cur.shape_eff.clear();
         cur.shaped = ShapeTables{};
+        cur.hold.clear();
+        cur.hold_f.clear();
+        cur.open = OpenTables{};
     }
     if (shaped) {
         cur.shape_eff = std::move(next.shape_eff);
@@ -187,6 +207,7 @@ int obstacles_change(lbm_ctx* c, ObsLevel level, Obstacles& next, int (*before_c
         cur.body = std::move(next.body);
     }
     cur.motion = std::move(next.motion);
+    cur.wall_uw = std::move(next.wall_uw);
     cur.moving = std::move(next.moving);
     return LBM_OK;
 }
@@ -255,7 +276,7 @@ int lbm_set_solid_bodies(lbm_ctx* c, const int32_t* body, int nbodies, const dou
     else next.centre.resize((size_t)B * nbodies * 2);
     for (int b = 0; b < B && !centre; ++b)
         body_centroids(mask.data() + b * n, next.label.data() + b * n, c->plan.geo.nx, c->plan.geo.ny, nbodies, next.centre.data() + (size_t)b * nbodies * 2);
-    return obstacles_change(c, ObsLevel::bodies, next);
+    return obstacles_change(c, ObsLevel::bodies, next, nullptr, "lbm_set_solid_bodies");
 }
 
 int lbm_get_solid_bodies(lbm_ctx* c, int32_t* body_out, double* centre_out) {

@@ -55,12 +55,14 @@ inline void body_centroids(const uint8_t* mask, const int32_t* body, int nx, int
 }
 
 // The link list of one lattice, appended to `links`: sorted by body, then by cell in [y][x] order, then by k.  start[nbodies + 1]
-// receives the bodies' ranges, as indices into `links`.
-inline void body_links(const uint8_t* mask, const int32_t* body, int nx, int ny, int nbodies, std::vector<BodyLink>& links, long long* start) {
+// receives the bodies' ranges, as indices into `links`.  hold (lbm_set_open_cells; null: none): the hold cells of the lattice, which are
+// no fluid cells -- a hold cell is never updated and bounces nothing, so no link starts at one.
+inline void body_links(const uint8_t* mask, const int32_t* body, int nx, int ny, int nbodies, std::vector<BodyLink>& links, long long* start,
+                       const uint8_t* hold = nullptr) {
     auto each = [&](auto&& f) {
         for (int y = 0; y < ny; ++y)
             for (int x = 0; x < nx; ++x) {
-                if (mask[(size_t)x * ny + y]) continue;
+                if (mask[(size_t)x * ny + y] || (hold && hold[(size_t)x * ny + y])) continue;
                 for (int k = 1; k < 9; ++k) {
                     const int sx = x - BODY_CX[k], sy = y + BODY_CY[k];
                     if (sx < 0 || sx >= nx || sy < 0 || sy >= ny || !mask[(size_t)sx * ny + sy]) continue;
@@ -93,7 +95,7 @@ inline void body_chunks(const long long* start, int nbodies, std::vector<BodyChu
 // The tables of the bodies of a whole batch (mask and label [batch][nx][ny], centre[batch][nbodies][2]) as the device holds them in one
 // allocation: the link list of every lattice, one after the other; chunks[batch][maxchunks], padded with empty chunks to the longest
 // lattice's; first[batch][nbodies + 1]; centre; then, only reserved, the workgroups' partial results of one pass (acc_vals doubles per
-// chunk) and the records of the one-shot call (rec_vals doubles per body).
+// chunk) and the records of the one-shot call (rec_vals doubles per body).  hold: the hold cells [batch][nx][ny] (null: none), see body_links.
 struct BodyParts {
     enum { LINKS, CHUNKS, FIRST, CENTRE, PARTIAL, REC };
     std::vector<BodyLink> links;
@@ -108,14 +110,14 @@ struct BodyParts {
     }
 };
 inline BodyParts body_parts(const uint8_t* mask, const int32_t* label, const double* centre, int batch, int nx, int ny, int nbodies, int acc_vals,
-                            int rec_vals) {
+                            int rec_vals, const uint8_t* hold = nullptr) {
     const size_t n = (size_t)nx * ny, B = (size_t)batch, nb1 = (size_t)nbodies + 1;
     BodyParts t;
     std::vector<long long> start(nb1);
     std::vector<std::vector<BodyChunk>> chunks(B);
     t.first.resize(B * nb1);
     for (size_t b = 0; b < B; ++b) {
-        body_links(mask + b * n, label + b * n, nx, ny, nbodies, t.links, start.data());
+        body_links(mask + b * n, label + b * n, nx, ny, nbodies, t.links, start.data(), hold ? hold + b * n : nullptr);
         body_chunks(start.data(), nbodies, chunks[b], t.first.data() + b * nb1);
         if (chunks[b].size() > t.maxchunks) t.maxchunks = chunks[b].size();
     }

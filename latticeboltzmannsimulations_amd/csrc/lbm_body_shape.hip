@@ -15,7 +15,7 @@ namespace lbmhost {
 // out, link_q in the order of the link list the device holds: body_tables), uploaded into `out`; *q_eff: the effective q.
 int shape_tables(lbm_ctx* c, const Obstacles& next, const std::vector<double>& q, ShapeTables& out, std::vector<double>* q_eff) {
     ShapeParts t = shape_parts(c->obs.mask.data(), next.label.data(), next.centre.data(), next.motion.data(), q.data(), c->plan.batch, c->plan.geo.nx,
-                               c->plan.geo.ny, next.nbodies, c->plan.es == 4);
+                               c->plan.geo.ny, next.nbodies, c->plan.es == 4, c->obs.hold_or_null(), next.uw_or_null());
     if (t.too_many_rows) return fail(c, LBM_ERR_INVALID, "lbm_set_solid_shape: too many cells with links");
     Pack<HipMem> p = upload<HipMem>(t.parts(), "solid shape tables");
     if (!p.err.empty()) return fail(c, p.no_memory ? LBM_ERR_NOMEM : LBM_ERR_HIP, p.err);
@@ -40,9 +40,9 @@ int lbm_set_solid_shape(lbm_ctx* c, const double* q) {
     if (c->plan.solid_tiles)
         return fail(c, LBM_ERR_STATE, "lbm_set_solid_shape: the tile kernel keeps the half-way rule (LBM_FLAG_SOLID_TILES takes no shape; create the "
                                       "context without the flag)");
-    if (std::any_of(c->obs.motion.begin(), c->obs.motion.end(), [](double v) { return v != 0.0; }))
-        return fail(c, LBM_ERR_STATE, "lbm_set_solid_shape: a body motion is set (the shape is set or cleared while every body is at rest: the shape "
-                                      "first, then lbm_set_body_motion)");
+    if (c->obs.moves())
+        return fail(c, LBM_ERR_STATE, "lbm_set_solid_shape: a body motion or a wall velocity is set (the shape is set or cleared while every surface "
+                                      "is at rest: the shape first, then lbm_set_body_motion and lbm_set_wall_velocity)");
     const Geo& g = c->plan.geo;
     Obstacles next;
     if (q) {

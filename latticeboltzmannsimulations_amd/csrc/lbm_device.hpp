@@ -489,8 +489,11 @@ __device__ __forceinline__ R lid_term(R rho_w, R uLB) { return (rho_w * uLB) * (
 // Solid obstacles (SEM_SOLID): plane K_LINK of the lattice holds one small integer per cell, exact in fp32 and fp64 -- bit k - 1: the
 // source (x - cx_k, y + cy_k) of slot k is a solid cell inside the lattice; bit 8: the cell itself is solid.  Written by lbm_set_solid
 // into both lattices, never by a step.  A solid cell is never updated and holds the rest equilibrium w_k in both lattices.
+// Bit 9: a hold cell (lbm_set_open_cells), whose word is exactly LINK_HOLD -- it is never updated either and holds its prescribed
+// populations in both lattices, but it is no wall: a neighbour pulls from it by the plain pull, and no link bit points at it.
 constexpr int K_LINK = Q;
 constexpr int LINK_SOLID = 256;
+constexpr int LINK_HOLD = 512;
 
 // Curved obstacle surfaces (lbm_set_solid_shape; contract in include/lbm.h): the per-cell table of a shaped context, built on
 // the host (lbm_wall_shape.hpp).  cell_row[ny][nx] of one lattice (x fastest): -1, or the cell's row; ad[rows][16] in the lattice type:
@@ -584,7 +587,7 @@ __device__ __forceinline__ void gather_a(const R* __restrict__ src, const AS& as
             return;
         }
     }
-    if (raw) {
+    if (raw || (SEM == SEM_SOLID && (lw & LINK_HOLD))) {   // (a hold cell: the nine values it holds, as every export sees them)
 #pragma unroll
         for (int k = 0; k < Q; ++k) g[k] = src[k * as.plane + as.at(x, y)];
         return;
@@ -656,7 +659,7 @@ __device__ __forceinline__ void update_cell_a(const R* __restrict__ src, const A
                                               WallArg<R, WALL> wa = WallArg<R, WALL>{}) {
     // lnk (SEM_SOLID with an LDS window as the source): plane K_LINK of the lattice, see link_word
     const int X = geo.nx, Y = geo.NY, gy = geo.y0 + y;
-    if (SEM == SEM_SOLID && (link_word<R, AS>(src, as, geo, lnk, x, y) & LINK_SOLID)) return;   // a solid cell is never updated
+    if (SEM == SEM_SOLID && (link_word<R, AS>(src, as, geo, lnk, x, y) & (LINK_SOLID | LINK_HOLD))) return;   // a solid cell, or a hold cell, is never updated
     R g[Q];
     if constexpr (WALL == WALL_SHAPE) gather_a<R, SEM, AS, coll_is_prom(COLL), true>(src, as, geo, raw, w0.uLB, x, y, g, lnk, wa.sh);
     else gather_a<R, SEM, AS, coll_is_prom(COLL)>(src, as, geo, raw, w0.uLB, x, y, g, lnk);

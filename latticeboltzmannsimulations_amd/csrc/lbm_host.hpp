@@ -11,11 +11,13 @@
 //   lbm_monitor.hip the run monitor and the line export (kernels: lbm_monitor.hpp)        (C ABI: monitor*, get_lines)
 //   lbm_residual.hip the field residual (kernels: lbm_residual.hpp)                        (C ABI: residual_*)
 //   lbm_topology.hip stream function, vorticity, extrema of psi (kernels: lbm_topology.hpp) (C ABI: topology, get_stream_function)
-//   lbm_solid.hip   solid obstacles: the mask and its link plane, the force on the obstacles (k_solid_force) (C ABI: set_solid, get_solid, solid_force)
+//   lbm_solid.hip   solid obstacles: the mask and its link plane, the hold cells, the force on the obstacles (k_solid_force)
+//                                                                                          (C ABI: set_solid, get_solid, solid_force, set_open_cells, get_open_cells)
 //                   (step kernels, all three wall modes: k_step_solid, k_step_generic_wall of lbm_solid.hpp; the mode: with_wall below)
 //   lbm_bodies.hip  the one writer of the obstacle state (struct Obstacles); the bodies of a mask: force and torque on each, one-shot
 //                   and as a series                                                          (C ABI: set_solid_bodies, get_solid_bodies, body_force, force_*)
-//   lbm_body_motion.hip the wall velocity of moving bodies: its tables                         (C ABI: set_body_motion, get_body_motion)
+//   lbm_body_motion.hip the wall velocity of moving bodies and of single solid cells: its tables (C ABI: set_body_motion, get_body_motion,
+//                                                                                          set_wall_velocity, get_wall_velocity)
 //   lbm_body_shape.hip  curved obstacle surfaces, a wall distance per link: its tables         (C ABI: set_solid_shape, get_solid_shape)
 // one header of device code that the step units never see:
 //   lbm_fields.hpp  the exported state ("what lbm_get_fields would return"): the view Fields that every reader kernel takes -- built
@@ -164,6 +166,16 @@ struct ShapeTables {
     ShapeTable<R> table() const { return ShapeTable<R>{cell_row, (const R*)ad, near}; }
 };
 
+// The hold cells on the device (open_tables, lbm_solid.hip), all inside the one allocation `base`: cell[n][3] = (lattice, x, y) of every
+// hold cell and val[n][9] in the lattice type, the populations it holds -- what k_open_fix writes into both lattices after every
+// initialisation and upload.  Empty without hold cells.
+struct OpenTables {
+    DevBuf base;
+    const int32_t* cell = nullptr;
+    const void* val = nullptr;
+    int n = 0;
+};
+
 // Solid obstacles (LBM_SEM_BOUNCE_BACK_SOLID; empty in the other semantics).  Three levels of host state, each with what the device
 // holds of it; obstacles_change (lbm_bodies.hip) is the only writer: a change at one level resets the levels below it.
 //   mask    as lbm_set_solid stored it, 0 / 1, [batch][nx][ny] (all fluid in a fresh context); its link plane lives in the lattices
@@ -174,8 +186,14 @@ struct ShapeTables {
 //   shape   beside the motion, not below it: shape_q[batch][8][nx][ny] as lbm_set_solid_shape took it (empty without a shape), shape_eff
 //           the effective q (what lbm_get_solid_shape returns), shaped: the tables.  A new mask drops the shape; new bodies and a new
 //           motion rebuild the tables from shape_q; the shape itself changes only while every body is at rest.
+//   open    below the mask, beside the bodies (lbm_set_open_cells): hold[batch][nx][ny], 0 / 1 (empty without hold cells), hold_f[cells][9]
+//           the populations of the hold cells in the order of hold (lattice, x, y), open: the tables.  A new mask drops them; they change
+//           only while there is no shape, no motion and no wall velocity, and rebuild the bodies' tables (no link starts at a hold cell).
+//   wall_uw with the motion (lbm_set_wall_velocity): uw[batch][2][nx][ny], empty while all zero; its term is part of the one table of the
+//           deltas (`moving`, or the d of `shaped`), which every call at the level of the motion rebuilds from both.  A new mask drops
+//           it, new bodies keep it.
 // force_part: the workgroups' partial results of lbm_solid_force and, behind them, its records (allocated on first use, kept).
-enum class ObsLevel { mask, bodies, motion, shape };
+enum class ObsLevel { mask, bodies, motion, shape, open };
 struct Obstacles {
     std::vector<uint8_t> mask;
     int nbodies = 1;
@@ -187,7 +205,16 @@ struct Obstacles {
     MotionTables moving;
     std::vector<double> shape_q, shape_eff;
     ShapeTables shaped;
+    std::vector<uint8_t> hold;
+    std::vector<double> hold_f;
+    OpenTables open;
+    std::vector<double> wall_uw;
     DevBuf force_part;
+    const uint8_t* hold_or_null() const { return hold.empty() ? nullptr : hold.data(); }
+    const double* uw_or_null() const { return wall_uw.empty() ? nullptr : wall_uw.data(); }
+    bool moves() const {
+        return !wall_uw.empty() || std::any_of(motion.begin(), motion.end(), [](double v) { return v != 0.0; });
+    }
 };
 
 // Run state.  What was decided once is in `plan`; p stays for the fields later code branches on (dtype, collision, semantics, turb,
@@ -535,10 +562,11 @@ int monitor_series_sample(lbm_ctx* c, int which, long long step);
 int solid_fix(lbm_ctx* c);
 int solid_copy_links(lbm_ctx* c, int to);
 // lbm_bodies.hip
-int obstacles_change(lbm_ctx* c, ObsLevel level, Obstacles& next, int (*before_commit)(lbm_ctx*, const Obstacles&) = nullptr);
+int obstacles_change(lbm_ctx* c, ObsLevel level, Obstacles& next, int (*before_commit)(lbm_ctx*, const Obstacles&) = nullptr,
+                     const char* call = "lbm_set_body_motion");
 int force_series_sample(lbm_ctx* c);
 // lbm_body_motion.hip
-int motion_tables(lbm_ctx* c, const Obstacles& next, MotionTables& out, bool check_only = false);
+int motion_tables(lbm_ctx* c, const Obstacles& next, MotionTables& out, bool check_only = false, const char* call = "lbm_set_body_motion");
 // lbm_body_shape.hip
 int shape_tables(lbm_ctx* c, const Obstacles& next, const std::vector<double>& q, ShapeTables& out, std::vector<double>* q_eff);
 // lbm_residual.hip

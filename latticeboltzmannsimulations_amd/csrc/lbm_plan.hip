@@ -536,8 +536,10 @@ int lbm_describe(const lbm_ctx* c, char* buf, size_t len) {
     // (a nonzero lbm_set_body_motion: the single steps run k_step_solid / k_step_generic_wall in their mode WALL_MOVE; a shape,
     // lbm_set_solid_shape: in their mode WALL_SHAPE, whose table holds the motion's term too)
     const bool shaped = (bool)c->obs.shaped.base;
-    const bool moving = c->obs.moving.base || (shaped && std::any_of(c->obs.motion.begin(), c->obs.motion.end(), [](double v) { return v != 0.0; }));
-    for (const char* word : {moving ? " wall_motion=1" : "", shaped ? " wall_shape=1" : ""}) {
+    const bool moving = std::any_of(c->obs.motion.begin(), c->obs.motion.end(), [](double v) { return v != 0.0; });
+    // (hold cells, lbm_set_open_cells; a nonzero lbm_set_wall_velocity, whose term shares the motion's table and mode)
+    for (const char* word : {moving ? " wall_motion=1" : "", shaped ? " wall_shape=1" : "", c->obs.hold.empty() ? "" : " open_cells=1",
+                             c->obs.wall_uw.empty() ? "" : " wall_velocity=1"}) {
         const int m = std::snprintf(buf + n, len - (size_t)n, "%s", word);
         if (m > 0) n = std::min<int>(n + m, (int)len - 1);
     }

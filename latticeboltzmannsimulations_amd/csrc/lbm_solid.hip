@@ -1,5 +1,5 @@
-// lbm_solid.hip -- liblbm_hip.so: solid obstacles in the bounce-back cavity (lbm_set_solid, lbm_get_solid, lbm_solid_force of the C ABI
-// declared in include/lbm.h; LBM_SEM_BOUNCE_BACK_SOLID).  The rule is gather_a<.., SEM_SOLID> (lbm_device.hpp), the step kernel
+// lbm_solid.hip -- liblbm_hip.so: solid obstacles in the bounce-back cavity (lbm_set_solid, lbm_get_solid, lbm_solid_force, and the hold
+// cells lbm_set_open_cells, lbm_get_open_cells of the C ABI declared in include/lbm.h; LBM_SEM_BOUNCE_BACK_SOLID).  The rule is gather_a<.., SEM_SOLID> (lbm_device.hpp), the step kernel
 // k_step_solid (lbm_solid.hpp); here: the mask and the link plane derived from it, the constants of solid cells, and the momentum-
 // exchange force (k_solid_force, one template for the three modes of the wall rule) reduced by the tree of lbm_reduce.hpp.  gfx950
 // only.  DESIGN.md 2.10.
@@ -24,6 +24,22 @@ __global__ __launch_bounds__(BLK) void k_solid_fix(R* __restrict__ a, R* __restr
     for (int k = 0; k < Q; ++k) {
         a[k * geo.plane + me] = weight<R>(k);
         b[k * geo.plane + me] = weight<R>(k);
+    }
+}
+
+// Hold cells (lbm_set_open_cells) hold their prescribed populations, rounded once to the lattice type, in both lattices: written with the
+// constants of the solid cells, from the context's table (OpenTables): one thread per hold cell, cell[i] = (lattice, x, y), val[i][9].
+template <typename R>
+__global__ __launch_bounds__(BLK) void k_open_fix(R* __restrict__ a, R* __restrict__ b, Geo geo, long long bstride, const int32_t* __restrict__ cell,
+                                                  const R* __restrict__ val, int n) {
+    const int i = blockIdx.x * BLK + threadIdx.x;
+    if (i >= n) return;
+    const long long me = (long long)cell[3 * i] * bstride + geo.at(cell[3 * i + 1], cell[3 * i + 2]);
+#pragma unroll
+    for (int k = 0; k < Q; ++k) {
+        const R v = val[(long long)i * Q + k];
+        a[k * geo.plane + me] = v;
+        b[k * geo.plane + me] = v;
     }
 }
 
@@ -106,6 +122,10 @@ int solid_fix(lbm_ctx* c) {
         using R = typename decltype(v)::R;
         hipLaunchKernelGGL((k_solid_fix<R>), grid_rows(c, c->plan.geo.ny), dim3(BLK), 0, c->s_compute, c->lat[0].as<R>(), c->lat[1].as<R>(), c->plan.geo,
                            c->plan.bstride);
+        const OpenTables& t = c->obs.open;
+        if (t.n > 0)
+            hipLaunchKernelGGL((k_open_fix<R>), dim3((t.n + BLK - 1) / BLK), dim3(BLK), 0, c->s_compute, c->lat[0].as<R>(), c->lat[1].as<R>(), c->plan.geo,
+                               c->plan.bstride, t.cell, (const R*)t.val, t.n);
     });
 }
 
@@ -126,12 +146,17 @@ int solid_copy_links(lbm_ctx* c, int to) {
     return LBM_OK;
 }
 
-// The link words of one lattice from its mask m[nx][ny] (0 / 1), as the lattice stores them: [ny][nx], x fastest.
+// The link words of one lattice from its mask m[nx][ny] (0 / 1) and its hold cells h[nx][ny] (0 / 1; null: none), as the lattice stores
+// them: [ny][nx], x fastest.  A hold cell's word is LINK_HOLD alone.
 template <typename R>
-static void link_words(const uint8_t* m, int nx, int ny, R* out) {
+static void link_words(const uint8_t* m, const uint8_t* h, int nx, int ny, R* out) {
     for (int y = 0; y < ny; ++y)
         for (int x = 0; x < nx; ++x) {
             int wd = m[(size_t)x * ny + y] ? LINK_SOLID : 0;
+            if (h && h[(size_t)x * ny + y]) {
+                out[(size_t)y * nx + x] = (R)LINK_HOLD;
+                continue;
+            }
             for (int k = 1; k < Q; ++k) {
                 const int sx = x - cxk(k), sy = y + cyk(k);
                 if (sx >= 0 && sx < nx && sy >= 0 && sy < ny && m[(size_t)sx * ny + sy]) wd |= 1 << (k - 1);
@@ -140,14 +165,14 @@ static void link_words(const uint8_t* m, int nx, int ny, R* out) {
         }
 }
 
-// mask: 0 / 1, [batch][nx][ny]
+// mask, hold (null: none): 0 / 1, [batch][nx][ny]
 template <typename R>
-static int upload_links_as(lbm_ctx* c, const uint8_t* mask) {
+static int upload_links_as(lbm_ctx* c, const uint8_t* mask, const uint8_t* hold) {
     const Geo& g = c->plan.geo;
     const size_t n = (size_t)g.nx * g.ny;
     std::vector<R> words(n);
     for (int b = 0; b < c->plan.batch; ++b) {
-        link_words<R>(mask + (size_t)b * n, g.nx, g.ny, words.data());
+        link_words<R>(mask + (size_t)b * n, hold ? hold + (size_t)b * n : nullptr, g.nx, g.ny, words.data());
         for (int l = 0; l < 2; ++l) {   // plane K_LINK of both lattices: rows of nx words, geo.row elements apart
             R* dst = c->lat[l].as<R>() + (size_t)b * c->plan.bstride + K_LINK * g.plane + g.at(0, 0);
             HIP_TRY(c, hipMemcpy2D(dst, (size_t)g.row * sizeof(R), words.data(), (size_t)g.nx * sizeof(R), (size_t)g.nx * sizeof(R), (size_t)g.ny,
@@ -157,13 +182,42 @@ static int upload_links_as(lbm_ctx* c, const uint8_t* mask) {
     return LBM_OK;
 }
 
-// The link planes of next.mask into every lattice the context holds, before obstacles_change commits it.  A copy that fails part-way
-// leaves the planes of the two lattices in an undefined mix of the old and the new mask: the call returns LBM_ERR_HIP, lbm_get_solid
-// still reports the old mask, and the context must be given a mask again (or destroyed) before it steps.
+// The link planes of next.mask (lbm_set_solid; no hold cells) or of the context's mask with next.hold (lbm_set_open_cells) into every
+// lattice the context holds, before obstacles_change commits it.  A copy that fails part-way leaves the planes of the two lattices in an
+// undefined mix of the old and the new: the call returns LBM_ERR_HIP, lbm_get_solid and lbm_get_open_cells still report the old state,
+// and the context must be given a mask again (or destroyed) before it steps.
 static int upload_links(lbm_ctx* c, const Obstacles& next) {
-    int rc = c->plan.es == 4 ? upload_links_as<float>(c, next.mask.data()) : upload_links_as<double>(c, next.mask.data());
+    const uint8_t* mask = next.mask.empty() ? c->obs.mask.data() : next.mask.data();
+    int rc = c->plan.es == 4 ? upload_links_as<float>(c, mask, next.hold_or_null()) : upload_links_as<double>(c, mask, next.hold_or_null());
     for (int i = 2; i < NLAT && rc == LBM_OK; ++i) rc = solid_copy_links(c, i);   // (the lattices allocated since: scratch, the lagged one)
     return rc ? rc : sync_all(c);
+}
+
+// The tables of the hold cells (OpenTables): next.hold in the order lattice, x, y, and next.hold_f rounded once to the lattice type.
+static int open_tables(lbm_ctx* c, Obstacles& next) {
+    if (next.hold.empty()) return LBM_OK;
+    const size_t n = (size_t)c->plan.geo.nx * c->plan.geo.ny, ny = (size_t)c->plan.geo.ny;
+    std::vector<int32_t> cell;
+    for (size_t i = 0; i < next.hold.size(); ++i)
+        if (next.hold[i]) {
+            cell.push_back((int32_t)(i / n));
+            cell.push_back((int32_t)((i % n) / ny));
+            cell.push_back((int32_t)(i % ny));
+        }
+    const bool f32 = c->plan.es == 4;
+    std::vector<char> val(next.hold_f.size() * (f32 ? sizeof(float) : sizeof(double)));
+    for (size_t i = 0; i < next.hold_f.size(); ++i) {
+        if (f32) ((float*)val.data())[i] = (float)next.hold_f[i];
+        else ((double*)val.data())[i] = next.hold_f[i];
+    }
+    if (cell.size() / 3 > 0x7fffffffu) return fail(c, LBM_ERR_INVALID, "lbm_set_open_cells: too many hold cells");
+    Pack<HipMem> p = upload<HipMem>({{cell.data(), cell.size() * sizeof(int32_t)}, {val.data(), val.size()}}, "hold cell tables");
+    if (!p.err.empty()) return fail(c, p.no_memory ? LBM_ERR_NOMEM : LBM_ERR_HIP, p.err);
+    next.open.cell = p.at<const int32_t>(0);
+    next.open.val = p.at<const void>(1);
+    next.open.n = (int)(cell.size() / 3);
+    next.open.base = std::move(p.buf);
+    return LBM_OK;
 }
 }  // namespace lbmhost
 
@@ -199,6 +253,73 @@ int lbm_get_solid(lbm_ctx* c, uint8_t* mask_out) {
     const int rc = need_solid(c, "lbm_get_solid");
     if (rc) return rc;
     std::memcpy(mask_out, c->obs.mask.data(), c->obs.mask.size());
+    return LBM_OK;
+}
+
+int lbm_set_open_cells(lbm_ctx* c, const uint8_t* hold, const double* f) {
+    if (!c) return LBM_ERR_INVALID;
+    int rc = need_solid(c, "lbm_set_open_cells");
+    if (rc) return rc;
+    if (c->plan.solid_tiles)
+        return fail(c, LBM_ERR_STATE, "lbm_set_open_cells: the tile kernel knows no hold cells (LBM_FLAG_SOLID_TILES takes none; create the context "
+                                      "without the flag)");
+    if (!c->obs.shape_q.empty() || c->obs.moves())
+        return fail(c, LBM_ERR_STATE, "lbm_set_open_cells: a shape, a body motion or a wall velocity is set (geometry comes first: the hold cells, "
+                                      "then lbm_set_solid_shape, lbm_set_body_motion and lbm_set_wall_velocity)");
+    const size_t n = (size_t)c->plan.geo.nx * c->plan.geo.ny, B = (size_t)c->plan.batch;
+    Obstacles next;
+    bool any = false;
+    for (size_t i = 0; hold && i < B * n && !any; ++i) any = hold[i] != 0;
+    if (any && !f) return fail(c, LBM_ERR_INVALID, "lbm_set_open_cells: hold cells need their populations (f is NULL)");   // (all zero clears, as NULL)
+    if (any) {
+        next.hold.resize(B * n);
+        for (size_t b = 0; b < B; ++b) {
+            size_t fluid = 0;
+            for (size_t i = 0; i < n; ++i) {
+                const bool h = hold[b * n + i] != 0;
+                next.hold[b * n + i] = h ? 1 : 0;
+                fluid += !h && !c->obs.mask[b * n + i] ? 1 : 0;
+                if (!h) continue;
+                if (c->obs.mask[b * n + i])
+                    return fail(c, LBM_ERR_INVALID, "lbm_set_open_cells: lattice " + std::to_string(b) + ": hold cell " + std::to_string(i) + " is a solid cell");
+                for (int k = 0; k < Q; ++k) {
+                    const double v = f[(b * Q + k) * n + i];
+                    if (!std::isfinite(v) || v < 0.0)
+                        return fail(c, LBM_ERR_INVALID, "lbm_set_open_cells: lattice " + std::to_string(b) + ": a population of hold cell " + std::to_string(i) +
+                                                            " is not finite or is negative");
+                    next.hold_f.push_back(v);
+                }
+            }
+            if (fluid == 0) return fail(c, LBM_ERR_INVALID, "lbm_set_open_cells: lattice " + std::to_string(b) + " is left without a fluid cell");
+        }
+    }
+    HIP_TRY(c, hipSetDevice(c->p.device));
+    rc = sync_all(c);
+    if (rc == LBM_OK) rc = open_tables(c, next);
+    if (rc == LBM_OK) rc = obstacles_change(c, ObsLevel::open, next, upload_links, "lbm_set_open_cells");
+    if (rc) return rc;
+    return lbm_init_equilibrium(c);   // (ends every sampler; hold cells get their populations: solid_fix)
+}
+
+int lbm_get_open_cells(lbm_ctx* c, uint8_t* hold_out, double* f_out) {
+    if (!c) return LBM_ERR_INVALID;
+    const int rc = need_solid(c, "lbm_get_open_cells");
+    if (rc) return rc;
+    const size_t n = (size_t)c->plan.geo.nx * c->plan.geo.ny, B = (size_t)c->plan.batch;
+    const std::vector<uint8_t>& h = c->obs.hold;
+    if (hold_out) {
+        if (h.empty()) std::memset(hold_out, 0, B * n);
+        else std::memcpy(hold_out, h.data(), B * n);
+    }
+    if (f_out) {
+        std::memset(f_out, 0, B * Q * n * sizeof(double));
+        size_t at = 0;
+        for (size_t i = 0; i < h.size(); ++i)
+            if (h[i]) {
+                for (int k = 0; k < Q; ++k) f_out[((i / n) * Q + k) * n + i % n] = c->obs.hold_f[at + k];
+                at += Q;
+            }
+    }
     return LBM_OK;
 }
 

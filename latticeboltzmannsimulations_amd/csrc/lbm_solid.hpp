@@ -13,8 +13,8 @@
 // the XCDs in bands of rows; lattices of a batch on grid axis y).  It reads its V link words first.  Where they are all zero and the
 // cells touch neither a wall nor the lid the step is the plain pull.  Otherwise every slot whose source lies outside the lattice or is
 // a solid cell takes the cell's own post-collision population of the opposite direction (one more aligned 16-byte load per direction),
-// the lid row adds Ladd's term from the parked density and parks the new one, and solid lanes keep their constants w_k.  Arithmetic
-// per cell: collide_vec, the operations of update_cell.
+// the lid row adds Ladd's term from the parked density and parks the new one, and solid lanes keep their constants w_k, hold lanes (bit
+// LINK_HOLD of the link word) the values they hold.  Arithmetic per cell: collide_vec, the operations of update_cell.
 //   WALL_SHAPE  the cell's eight stored slots are loaded first; a lane's link k then takes shape_rule(own = stored opp(k), other = the
 //               regular pull of slot opp(k) (near) or stored k (far), a, d) from the cell's row of the table.  The pull of a near link's
 //               slot opp(k) is never overwritten: its source is a fluid cell inside the lattice.  (shape_link of lbm_device.hpp loads
@@ -132,11 +132,22 @@ __global__ __launch_bounds__(BLK) void k_step_solid(const R* __restrict__ src, R
                 for (int k = 0; k < Q; ++k) outv[k][c] = weight<R>(k);
             }
     }
+    // a hold lane (lbm_set_open_cells) keeps the nine values the cell holds: its own stored slots, so the 16-byte stores stay whole
+    if (any & LINK_HOLD) {
+#pragma unroll
+        for (int k = 0; k < Q; ++k) {
+            const T own = vload<R, V, NT>(src + k * geo.plane + me, true);
+#pragma unroll
+            for (int c = 0; c < V; ++c)
+                if (lw[c] & LINK_HOLD) outv[k][c] = own[c];
+        }
+    }
 #pragma unroll
     for (int k = 0; k < Q; ++k) vstore<R, V, NT>(dst + k * geo.plane + me, outv[k]);
     // park the lid cells' densities for the next step's lid term (update_cell_a; the same sum, the same bits).  A solid lane parks a sum
     // too, where the generic route parks nothing: only that solid cell would read it, and its gather returns the constants before it
-    // does -- the ghost rows are not part of the equality of the two routes, the lattice's own cells and every export are.
+    // does -- the ghost rows are not part of the equality of the two routes, the lattice's own cells and every export are.  A hold lane
+    // likewise: its gather returns the held values and never reads what it parked.
     if (lid) {
         T rho;
 #pragma unroll

@@ -37,6 +37,20 @@ LBM_WM_ATTR inline double wall_delta(int x, int y, int k, double x0, double y0, 
     return w6 * ((double)BODY_CX[k] * uwx + (double)BODY_CY[k] * uwy);
 }
 
+// The wall velocity of a solid cell (lbm_set_wall_velocity): what the source cell S = (x - cx_k, y + cy_k) of a link adds to the link's
+// delta, (6 w_k) (cx_k uwx(S) + cy_k uwy(S)), every product and sum rounded in the order written, 6 w_k as wall_delta rounds it.  The
+// link's delta is then wall_delta(...) + wall_cell_term(...), one more add.
+LBM_WM_ATTR inline double wall_cell_term(int k, double uwx, double uwy) {
+    LBM_WM_NO_CONTRACT
+    const double w6 = k < 5 ? 2.0 / 3.0 : 1.0 / 6.0;
+    return w6 * ((double)BODY_CX[k] * uwx + (double)BODY_CY[k] * uwy);
+}
+// ... of the link (cell (x, y), slot k) from uw[2][nx][ny] of its lattice (the components as u, the host layout of the mask)
+inline double wall_cell_term_at(const double* uw, int nx, int ny, int x, int y, int k) {
+    const size_t s = (size_t)(x - BODY_CX[k]) * ny + (size_t)(y + BODY_CY[k]);
+    return wall_cell_term(k, uw[s], uw[(size_t)nx * ny + s]);
+}
+
 // delta as the lattice holds it: rounded once to the lattice type, then a double again (what the force subtracts)
 inline double wall_delta_rounded(double d, bool f32) { return f32 ? (double)(float)d : d; }
 
@@ -49,9 +63,10 @@ struct WallMotion {
 };
 
 // links[start[0] .. start[nbodies]) of one lattice (body_links), centre[nbodies][2], motion[nbodies][3] = (Ux, Uy, Om).  row_base: the
-// rows of this lattice follow that many rows of the lattices before it (a batch shares one table).
+// rows of this lattice follow that many rows of the lattices before it (a batch shares one table).  uw (null: none): the wall velocity
+// per solid cell of this lattice, uw[2][nx][ny], whose term every link adds to the rigid-body one (wall_cell_term).
 LBM_WM_ATTR inline WallMotion wall_motion(const std::vector<BodyLink>& links, const long long* start, int nx, int ny, int nbodies, const double* centre,
-                                          const double* motion, long long row_base = 0) {
+                                          const double* motion, long long row_base = 0, const double* uw = nullptr) {
     LBM_WM_NO_CONTRACT
     WallMotion m;
     m.delta.resize((size_t)(start[nbodies] - start[0]));
@@ -60,7 +75,8 @@ LBM_WM_ATTR inline WallMotion wall_motion(const std::vector<BodyLink>& links, co
     for (int b = 0; b < nbodies; ++b)
         for (long long i = start[b]; i < start[b + 1]; ++i) {
             const int x = links[(size_t)i].x, y = links[(size_t)i].yk >> 4, k = links[(size_t)i].yk & 15;
-            const double d = wall_delta(x, y, k, centre[2 * b], centre[2 * b + 1], motion[3 * b], motion[3 * b + 1], motion[3 * b + 2]);
+            double d = wall_delta(x, y, k, centre[2 * b], centre[2 * b + 1], motion[3 * b], motion[3 * b + 1], motion[3 * b + 2]);
+            if (uw) d = d + wall_cell_term_at(uw, nx, ny, x, y, k);
             m.delta[(size_t)(i - start[0])] = d;
             m.S = m.S + d;
             m.A = m.A + std::fabs(d);
@@ -83,6 +99,8 @@ inline bool wall_motion_closed(const WallMotion& m) { return !(std::fabs(m.S) > 
 // as the device holds them in one allocation: cell_row[batch][ny][nx]; delta[rows][8], already rounded to the lattice type (f32: float);
 // link_delta, one double per entry of the batch's link list (body_parts), the same terms as the lattice adds them.  Or why there are
 // none: the first lattice whose motion fails the flux check, with its sums and its count of links, or too many rows for cell_row.
+// hold[batch][nx][ny] (null: none): the hold cells of lbm_set_open_cells -- no link starts at one (body_links), and a lattice that has
+// one is open: the flux check is waived for it.  uw[batch][2][nx][ny] (null: none): the wall velocity per solid cell (wall_motion).
 struct MotionParts {
     enum { CELL_ROW, DELTA, LINK_DELTA };
     enum Refusal { NONE, OPEN_FLUX, TOO_MANY_ROWS };
@@ -98,7 +116,7 @@ struct MotionParts {
     }
 };
 inline MotionParts motion_parts(const uint8_t* mask, const int32_t* label, const double* centre, const double* motion, int batch, int nx, int ny,
-                                int nbodies, bool f32) {
+                                int nbodies, bool f32, const uint8_t* hold = nullptr, const double* uw = nullptr) {
     const size_t n = (size_t)nx * ny;
     MotionParts t;
     t.cell_row.resize(batch * n);
@@ -106,10 +124,12 @@ inline MotionParts motion_parts(const uint8_t* mask, const int32_t* label, const
     for (int b = 0; b < batch; ++b) {
         std::vector<BodyLink> links;
         std::vector<long long> start((size_t)nbodies + 1);
-        body_links(mask + b * n, label + b * n, nx, ny, nbodies, links, start.data());
+        const uint8_t* h = hold ? hold + b * n : nullptr;
+        body_links(mask + b * n, label + b * n, nx, ny, nbodies, links, start.data(), h);
         const WallMotion m = wall_motion(links, start.data(), nx, ny, nbodies, centre + (size_t)b * nbodies * 2, motion + (size_t)b * nbodies * 3,
-                                         (long long)(rows.size() / 8));
-        if (!wall_motion_closed(m)) {
+                                         (long long)(rows.size() / 8), uw ? uw + (size_t)b * 2 * n : nullptr);
+        const bool open = h && std::any_of(h, h + n, [](uint8_t v) { return v != 0; });
+        if (!open && !wall_motion_closed(m)) {
             t.refusal = MotionParts::OPEN_FLUX; t.lattice = b; t.S = m.S; t.A = m.A; t.links = m.delta.size();
             return t;
         }

@@ -26,7 +26,9 @@ struct ShapeLink {
     double q, a, d, rx, ry;
     bool near;
 };
-LBM_WM_ATTR inline ShapeLink shape_link(int x, int y, int k, double q, bool next_fluid, double x0, double y0, double Ux, double Uy, double Om) {
+// cell (null: none): the term of the source cell's own wall velocity (wall_cell_term, lbm_wall_motion.hpp), added to delta before d.
+LBM_WM_ATTR inline ShapeLink shape_link(int x, int y, int k, double q, bool next_fluid, double x0, double y0, double Ux, double Uy, double Om,
+                                        const double* cell = nullptr) {
     LBM_WM_NO_CONTRACT
     ShapeLink l;
     l.near = q < 0.5 && next_fluid;
@@ -36,7 +38,8 @@ LBM_WM_ATTR inline ShapeLink shape_link(int x, int y, int k, double q, bool next
     l.ry = ((double)y + l.q * (double)BODY_CY[k]) - y0;
     const double uwx = Ux + Om * l.ry, uwy = Uy + Om * l.rx;
     const double w6 = k < 5 ? 2.0 / 3.0 : 1.0 / 6.0;
-    const double delta = w6 * ((double)BODY_CX[k] * uwx + (double)BODY_CY[k] * uwy);
+    double delta = w6 * ((double)BODY_CX[k] * uwx + (double)BODY_CY[k] * uwy);
+    if (cell) delta = delta + *cell;
     l.d = l.near ? delta : l.a * delta;
     return l;
 }
@@ -74,6 +77,8 @@ inline bool shape_bad_link(const uint8_t* mask, const double* q, int batch, int 
 // rounded to the lattice type (f32: float), a in slots 0 .. 7 (1 where the cell has no link k), d in slots 8 .. 15; near[rows], bit
 // k - 1; link_q, the effective q of every entry of the batch's link list (body_parts), for the wall point of the torque.  q_eff: what
 // lbm_get_solid_shape returns, the effective q on the links and 0 elsewhere (host only).  too_many_rows: no tables.
+// hold[batch][nx][ny] (null: none): the hold cells of lbm_set_open_cells, no fluid cells -- no link starts at one and none is a link's
+// next fluid cell.  uw[batch][2][nx][ny] (null: none): the wall velocity per solid cell, whose term joins delta.
 struct ShapeParts {
     enum { CELL_ROW, AD, NEAR, LINK_Q };
     std::vector<int32_t> cell_row;
@@ -88,7 +93,7 @@ struct ShapeParts {
     }
 };
 inline ShapeParts shape_parts(const uint8_t* mask, const int32_t* label, const double* centre, const double* motion, const double* q, int batch,
-                              int nx, int ny, int nbodies, bool f32) {
+                              int nx, int ny, int nbodies, bool f32, const uint8_t* hold = nullptr, const double* uw = nullptr) {
     const size_t n = (size_t)nx * ny;
     ShapeParts t;
     t.cell_row.assign(batch * n, -1);
@@ -98,15 +103,18 @@ inline ShapeParts shape_parts(const uint8_t* mask, const int32_t* label, const d
         const uint8_t* m = mask + b * n;
         std::vector<BodyLink> links;
         std::vector<long long> start((size_t)nbodies + 1);
-        body_links(m, label + b * n, nx, ny, nbodies, links, start.data());
+        const uint8_t* h = hold ? hold + b * n : nullptr;
+        body_links(m, label + b * n, nx, ny, nbodies, links, start.data(), h);
         for (int body = 0; body < nbodies; ++body) {
             const double* cen = centre + ((size_t)b * nbodies + body) * 2;
             const double* mot = motion + ((size_t)b * nbodies + body) * 3;
             for (long long i = start[body]; i < start[body + 1]; ++i) {
                 const int x = links[(size_t)i].x, y = links[(size_t)i].yk >> 4, k = links[(size_t)i].yk & 15;
                 const int fx = x + BODY_CX[k], fy = y - BODY_CY[k];
-                const bool next_fluid = fx >= 0 && fx < nx && fy >= 0 && fy < ny && !m[(size_t)fx * ny + fy];
-                const ShapeLink l = shape_link(x, y, k, q[shape_q_index(b, k, x, y, nx, ny)], next_fluid, cen[0], cen[1], mot[0], mot[1], mot[2]);
+                const bool next_fluid = fx >= 0 && fx < nx && fy >= 0 && fy < ny && !m[(size_t)fx * ny + fy] && !(h && h[(size_t)fx * ny + fy]);
+                const double cell = uw ? wall_cell_term_at(uw + (size_t)b * 2 * n, nx, ny, x, y, k) : 0.0;
+                const ShapeLink l = shape_link(x, y, k, q[shape_q_index(b, k, x, y, nx, ny)], next_fluid, cen[0], cen[1], mot[0], mot[1], mot[2],
+                                               uw ? &cell : nullptr);
                 int32_t& row = t.cell_row[b * n + (size_t)y * nx + x];
                 if (row < 0) {
                     if (rows.size() / 16 >= 0x7fffffffu) {

@@ -341,3 +341,78 @@ def shaped_force_terms(fin, fpost, mask, labels=None):
     opp = np.array(OPP)
     t = fpost[opp[k], x, y].astype(np.float64) + fin[k, x, y].astype(np.float64)
     return ln, np.array(CX, dtype=np.float64)[opp[k]] * t, np.array(CY, dtype=np.float64)[opp[k]] * t
+
+
+# ---- open boundaries: hold cells and a wall velocity per solid cell (CavitySolver.set_open_cells, set_wall_velocity) ---------------------
+def equilibrium(rho, ux, uy):
+    """feq[9, ...] in float64 of a density and a velocity (scalars or arrays that broadcast): w_k rho (1 + 3 cu + 4.5 cu^2 - 1.5 u^2),
+    cu = cx_k ux + cy_k uy, uy > 0 towards the lid -- what a hold cell holds to stand for a stream of that state (set_open_cells)."""
+    rho, ux, uy = (np.asarray(a, dtype=np.float64) for a in np.broadcast_arrays(rho, ux, uy))
+    w = (4.0 / 9.0,) + (1.0 / 9.0,) * 4 + (1.0 / 36.0,) * 4
+    usq = ux * ux + uy * uy
+    out = np.empty((9,) + rho.shape)
+    for k in range(9):
+        cu = CX[k] * ux + CY[k] * uy
+        out[k] = w[k] * rho * (1.0 + 3.0 * cu + 4.5 * cu * cu - 1.5 * usq)
+    return out
+
+
+def host_open_tables(mask, labels, centres, motion, wall_velocity=None, hold=None, q=None, dtype=None):
+    """The public restatement of the per-link deltas of a lattice with hold cells and a wall velocity per solid cell, as shape_table is
+    for the shape: dict of arrays [links] in the order of the library's link list -- body_links(mask, labels) without the links that
+    start at a hold cell, which bounces nothing.  links (x, y, k, body); delta, float64:
+
+        delta = delta_body + (6 w_k) (cx_k uwx(S) + cy_k uwy(S)),        S = (x - cx_k, y + cy_k) the link's source cell,
+
+    delta_body as wall_deltas forms it at the link's midpoint, then the cell term of wall_velocity[2, X, Y], each product and sum
+    rounded in the order written, then the add.  S, A: the sums of delta and |delta| in the list's order; closed: what the flux check
+    of set_body_motion / set_wall_velocity decides -- |S| <= links 2^-52 A, and always True on a lattice with a hold cell, which is
+    open.  With q[8, X, Y] (set_shape) also q, near, a, d, rx, ry as shape_table gives them, the rigid-body part of delta at the wall
+    point and a hold cell counting as no fluid cell behind a link; `delta` stays the midpoint's, which the flux check sums.
+    dtype: the lattice type, to which delta (and a, d) are rounded once; S and A are formed before that."""
+    m = np.asarray(mask) != 0
+    X, Y = m.shape
+    h = np.zeros_like(m) if hold is None else np.asarray(hold) != 0
+    cen, mot = np.asarray(centres, dtype=np.float64), np.asarray(motion, dtype=np.float64)
+    ln = body_links(m, labels)
+    ln = ln[~h[ln[:, 0], ln[:, 1]]]
+    x, y, k, b = ln[:, 0], ln[:, 1], ln[:, 2], ln[:, 3]
+    cx, cy = np.array(CX, dtype=np.float64), np.array(CY, dtype=np.float64)
+    w6 = np.where(k < 5, 2.0 / 3.0, 1.0 / 6.0)
+
+    def body_term(rx, ry):
+        uwx = mot[b, 0] + mot[b, 2] * ry
+        uwy = mot[b, 1] + mot[b, 2] * rx
+        return w6 * (cx[k] * uwx + cy[k] * uwy)
+
+    cell = None
+    if wall_velocity is not None:
+        uw = np.where(m[None], np.asarray(wall_velocity, dtype=np.float64), 0.0)
+        sx, sy = x - np.array(CX)[k], y + np.array(CY)[k]
+        cell = w6 * (cx[k] * uw[0, sx, sy] + cy[k] * uw[1, sx, sy])
+    rnd = (lambda v: v) if dtype is None else (lambda v: v.astype(dtype).astype(np.float64))
+    delta = body_term((x.astype(np.float64) - 0.5 * cx[k]) - cen[b, 0], (y.astype(np.float64) + 0.5 * cy[k]) - cen[b, 1])
+    if cell is not None:
+        delta = delta + cell
+    S = A = 0.0
+    for d in delta.tolist():
+        S = S + d
+        A = A + abs(d)
+    out = dict(links=ln, delta=rnd(delta), S=S, A=A, closed=bool(h.any()) or not abs(S) > len(ln) * 2.0 ** -52 * A)
+    if q is not None:
+        q = np.asarray(q, dtype=np.float64)
+        nx_, ny_ = x + np.array(CX)[k], y - np.array(CY)[k]
+        inside = (nx_ >= 0) & (nx_ < X) & (ny_ >= 0) & (ny_ < Y)
+        cxn, cyn = np.clip(nx_, 0, X - 1), np.clip(ny_, 0, Y - 1)
+        next_fluid = inside & ~m[cxn, cyn] & ~h[cxn, cyn]
+        qv = q[k - 1, x, y]
+        near = (qv < 0.5) & next_fluid
+        qe = np.where((qv < 0.5) & ~next_fluid, 0.5, qv)
+        a = np.where(near, 2.0 * qe, 1.0 / (2.0 * qe))
+        rx = (x.astype(np.float64) - qe * cx[k]) - cen[b, 0]
+        ry = (y.astype(np.float64) + qe * cy[k]) - cen[b, 1]
+        dw = body_term(rx, ry)
+        if cell is not None:
+            dw = dw + cell
+        out.update(q=qe, near=near, a=rnd(a), d=rnd(np.where(near, dw, a * dw)), rx=rx, ry=ry)
+    return out

@@ -640,6 +640,72 @@ class CavitySolver:
         self._check(self.lib.lbm_get_solid_shape(self._h, a.ctypes.data), "lbm_get_solid_shape")
         return a
 
+    # -- open boundaries (lbm_set_open_cells, lbm_get_open_cells, lbm_set_wall_velocity, lbm_get_wall_velocity) ---------
+    def set_open_cells(self, hold, f=None):
+        """Hold cells (lbm_set_open_cells): hold is a mask of the solid mask's shape (one [X, Y] array serves every lattice of a
+        batch), f is [9, X, Y] (a batch: [B, 9, X, Y], or [9, X, Y] for every lattice), read on the hold cells only -- for a stream of
+        density rho and velocity (ux, uy), solid.equilibrium(rho, ux, uy).  A hold cell is never updated and keeps f_k; it is no wall:
+        its neighbours pull from it as from a fluid cell.  It serves as a pressure or far-field outlet, or as a reservoir.  Ends every
+        sampler and restarts the lattice from the initial equilibrium, as set_solid does.  None clears.  Geometry comes first: before
+        set_shape, set_body_motion and set_wall_velocity.  set_solid drops the hold cells, set_bodies keeps them."""
+        self._need_solid()
+        if hold is None:
+            self._check(self.lib.lbm_set_open_cells(self._h, None, None), "lbm_set_open_cells")
+            return self
+        h = self._mask(hold)
+        a = np.asarray(f, dtype=np.float64)
+        if self._lead and a.shape == (9, self.nx, self.ny):
+            a = np.broadcast_to(a, self._lead + a.shape)
+        if a.shape != self._lead + (9, self.nx, self.ny):
+            raise ValueError(f"the held populations must have shape {self._lead + (9, self.nx, self.ny)}")
+        a = np.ascontiguousarray(a)
+        self._check(self.lib.lbm_set_open_cells(self._h, h.ctypes.data, a.ctypes.data), "lbm_set_open_cells")
+        return self
+
+    @property
+    def open_cells(self):
+        """(hold, f): copies of the hold cells, bool [X, Y], and of their populations, float64 [9, X, Y], zero elsewhere (a batch:
+        [B, X, Y] and [B, 9, X, Y]); None without hold cells."""
+        if not self.has_solid or self._h is None:
+            return None
+        h = np.zeros(self._lead + (self.nx, self.ny), dtype=np.uint8)
+        self._check(self.lib.lbm_get_open_cells(self._h, h.ctypes.data, None), "lbm_get_open_cells")      # (the library's answer, as wall_velocity)
+        if not h.any():
+            return None
+        f = np.zeros(self._lead + (9, self.nx, self.ny))
+        self._check(self.lib.lbm_get_open_cells(self._h, None, f.ctypes.data), "lbm_get_open_cells")
+        return h.astype(bool), f
+
+    def set_wall_velocity(self, uw):
+        """Give single solid cells a wall velocity (lbm_set_wall_velocity): uw is [2, X, Y] (a batch: [B, 2, X, Y], or [2, X, Y] for
+        every lattice), components as u, read on solid cells only.  Every link adds Ladd's term of its source cell's velocity to that of
+        its body's motion (set_body_motion), in either order of the two calls: a velocity bounce-back inlet with any profile, a sliding
+        side wall.  None, or all zero: no term.  The lattice, the step count and the samplers stay.  On a lattice without hold cells a
+        velocity with a net flux is refused, as a motion is; a lattice with hold cells (set_open_cells) is open.  The shape first, then
+        velocities.  set_solid resets it, set_bodies keeps it."""
+        self._need_solid()
+        if uw is None:
+            self._check(self.lib.lbm_set_wall_velocity(self._h, None), "lbm_set_wall_velocity")
+            return self
+        a = np.asarray(uw, dtype=np.float64)
+        if self._lead and a.shape == (2, self.nx, self.ny):
+            a = np.broadcast_to(a, self._lead + a.shape)
+        if a.shape != self._lead + (2, self.nx, self.ny):
+            raise ValueError(f"the wall velocity must have shape {self._lead + (2, self.nx, self.ny)}")
+        a = np.ascontiguousarray(a)
+        self._check(self.lib.lbm_set_wall_velocity(self._h, a.ctypes.data), "lbm_set_wall_velocity")
+        return self
+
+    @property
+    def wall_velocity(self):
+        """A copy of the wall velocity of the solid cells, float64 [2, X, Y] (a batch: [B, 2, X, Y]), zero on every other cell and all
+        zero when none is set; None without solid=..."""
+        if not self.has_solid:
+            return None
+        a = np.zeros(self._lead + (2, self.nx, self.ny))
+        self._check(self.lib.lbm_get_wall_velocity(self._h, a.ctypes.data), "lbm_get_wall_velocity")
+        return a
+
     # -- checkpoint / restart (the reference has neither; SURVEY 8f item 4) -------------------
     def save_checkpoint(self, path):
         """Write the populations and the run parameters to `path` (.npz).  Restarting from it continues bit-identically
@@ -651,8 +717,20 @@ class CavitySolver:
                  semantics=self.semantics, dtype=self.dtype.name, rows=np.array([self.y0, self.ny_local]), turb=self.turb, u=u, rho=rho,
                  arith=self.arith, **(dict(solid=self.solid) if self.has_solid else {}),
                  **{**(dict(zip(("body_labels", "body_centres"), self.bodies)) if getattr(self, "_bodies_given", False) else {}),
-                    **self._motion_entry(), **self._shape_entry()})
+                    **self._motion_entry(), **self._shape_entry(), **self._open_entry()})
         return path
+
+    def _open_entry(self):
+        """What a checkpoint says of the open boundaries: nothing without them (the file of such a run is what it was), else the hold
+        cells with their populations, and the wall velocity of the solid cells."""
+        out = {}
+        oc = self.open_cells if self.has_solid else None
+        if oc is not None:
+            out.update(open_hold=oc[0], open_f=oc[1])
+        uw = self.wall_velocity if self.has_solid and self._h is not None else None
+        if uw is not None and uw.any():
+            out.update(wall_velocity=uw)
+        return out
 
     def _shape_entry(self):
         """What a checkpoint says of the shape: nothing without one (the file of such a run is what it was), else the effective q."""
@@ -695,15 +773,34 @@ class CavitySolver:
                                      f"{int(self.solid.sum())} solid cells" if self.has_solid else "none")
                 if diff:
                     raise ValueError(f"checkpoint was written by a different run (checkpoint, this solver): {diff}")
-            self.set_state(np.ascontiguousarray(z["fin"]))
             same_mask = self.has_solid and "solid" in z and np.array_equal(np.asarray(z["solid"], dtype=bool), self.solid)
+            if same_mask and self._h is not None and self.wall_velocity.any():     # (this solver's own velocity goes first: it would stand in the
+                self.set_wall_velocity(None)                                      # flux check of every call below)
+            if same_mask and ("open_hold" in z or self.open_cells is not None):     # (geometry first: it restarts the lattice, so before the state)
+                self.set_body_motion(None)
+                self.set_shape(None)
+                self.set_open_cells(*((np.asarray(z["open_hold"]), np.asarray(z["open_f"])) if "open_hold" in z else (None,)))
+            self.set_state(np.ascontiguousarray(z["fin"]))
             if same_mask and ("solid_shape" in z or self.shape is not None):     # (the shape first, then the motion)
                 self.set_body_motion(None)
                 self.set_shape(np.where(np.asarray(z["solid_shape"]) > 0.0, z["solid_shape"], 0.5) if "solid_shape" in z else None)
+            uw = np.asarray(z["wall_velocity"]) if same_mask and "wall_velocity" in z else None
             if "body_labels" in z and self.has_solid and np.array_equal(np.asarray(z["solid"], dtype=bool), self.solid):
                 self.set_bodies(np.asarray(z["body_labels"]), np.asarray(z["body_centres"]))     # (files without them: the bodies stay)
                 if "body_motion" in z:
-                    self.set_body_motion(np.asarray(z["body_motion"]))
+                    # The two halves of the wall velocity are two calls, each with the flux check of a closed lattice: the motion
+                    # first, and where it is refused on its own, the cells' velocity first.  A pair of which neither half is closed
+                    # alone (only their sum is) cannot be set by two calls and is refused here as it was when it was first set.
+                    try:
+                        self.set_body_motion(np.asarray(z["body_motion"]))
+                    except RuntimeError:
+                        if uw is None:
+                            raise
+                        self.set_wall_velocity(uw)
+                        self.set_body_motion(np.asarray(z["body_motion"]))
+                        uw = None
+            if uw is not None:
+                self.set_wall_velocity(uw)
             return int(z["steps_done"])
 
     # -- slab exchange primitives ---------------------------------------------------------
