@@ -663,6 +663,49 @@ int lbm_get_open_cells(lbm_ctx* c, uint8_t* hold_out, double* f_out);
 int lbm_set_wall_velocity(lbm_ctx* c, const double* uw);
 int lbm_get_wall_velocity(lbm_ctx* c, double* uw_out);
 
+/* --- periodic sides and a uniform driving force ---------------------------------------------------- */
+/* No reference counterpart.  What force-driven and periodic flows need (LBM_SEM_BOUNCE_BACK_SOLID only): Poiseuille flow without an inlet,
+ * a periodic array of obstacles, periodic Couette flow, Taylor-Green decay.  Each works without the other: a closed box under gravity is
+ * legal, and so is a periodic lattice without a force.
+ *
+ * Image cells.  With px, columns 0 and nx - 1 are image columns of the columns nx - 2 and 1, and the periodic domain is columns
+ *   1 .. nx - 2; with py the same holds for rows 0 and ny - 1; with both the four corners are images of the diagonally opposite real cells.
+ *   The partner of an image cell, x -> nx - 2 if x == 0, 1 if x == nx - 1 (likewise y), is always a real cell.  An image cell whose partner
+ *   is not solid is a hold cell (its word in plane K_LINK is exactly 512): never updated, pulled from by the plain pull, no force link
+ *   starts at it, no fluid cell for the `near` test of a shape.  An image cell whose partner is solid must be solid.  After every single
+ *   step, and behind the constants of the solid and hold cells after every initialisation and lbm_set_state (there on both lattices), the
+ *   kernel k_wrap copies the nine slots of every partner into its image, on the compute stream.  The lattice holds post-collision
+ *   populations, so the image's neighbours pull exactly what they would pull across the seam.
+ * lbm_set_periodic: geometry -- it ends every sampler, rewrites plane K_LINK and the bodies' tables and performs lbm_init_equilibrium, as
+ *   lbm_set_open_cells does.  LBM_ERR_INVALID (the text names the first offending cell, index x * ny + y): the mask differs from its own
+ *   wrap on an image cell; the body labels differ from their own wrap (lbm_set_solid_bodies checks the same when called later); a user
+ *   hold cell on an image cell (lbm_set_open_cells refuses it likewise); nx < 4 with px, ny < 4 with py; a lattice left without a fluid
+ *   cell.  LBM_ERR_STATE: another semantics; a LBM_FLAG_SOLID_TILES context; a shape, a nonzero motion or a nonzero wall velocity is set --
+ *   geometry comes first.  lbm_set_solid clears the periodic sides; lbm_set_open_cells and lbm_set_solid_bodies keep them.
+ *   lbm_set_periodic(c, 0, 0) restores the closed box, its kernels and its bits.  lbm_describe appends ` periodic=x`, ` periodic=y` or
+ *   ` periodic=xy` while a side is periodic.
+ *   Limits.  The exported arrays include the image cells, and the device samplers (statistics, monitor, residual, topology) count them as
+ *   cells.  lbm_get_open_cells reports the user's hold cells only.  The torque of a body that crosses the seam is meaningless; its force is
+ *   right: every physical link is counted once, from its real fluid cell.  The flux check of a motion is waived, as on every lattice with
+ *   hold cells.  Under a shape a near link whose next fluid cell is an image falls back to q = 1/2: keep shaped bodies two cells from the
+ *   seam.  Wall velocities and wall distances on image solids are the caller's to wrap.  One step per launch, no slabs.
+ * lbm_get_periodic: *px_out, *py_out receive 0 / 1; either may be NULL.
+ *
+ * Driving force.  (fx, fy) is the force density per cell, in the components of u.  On the host, in double without contraction and in this
+ *   order, F_k = (3 w_k) (cx_k fx + cy_k fy) for k = 1 .. 8, 3 w_k = 1/3 (k <= 4) or 1/12, each rounded once to the lattice type.  Every
+ *   collision of a cell that is neither solid nor held is followed by f*_k = f*_k + F_k, one add in the lattice type, never fused (arith =
+ *   fast too), in the raw first step too, before the delta of a moving wall.  The scheme is the first-order one: the equilibrium uses the
+ *   bare velocity, the physical velocity is (sum c f + F / 2) / rho, and the exports and samplers keep reporting the bare moments.  It is
+ *   exact for a steady uniform driver; a force that varies in space or time is out of scope.  All lattices of a batch share one force.
+ * lbm_set_driving_force: may be called at any time; it touches neither the lattice nor the step count and ends no sampler.
+ *   LBM_ERR_INVALID: a value that is not finite.  LBM_ERR_STATE, for a nonzero force: another semantics, a LBM_FLAG_SOLID_TILES context.
+ *   (0, 0) restores the launches and the bits of a context without a force.  lbm_describe appends ` driving_force=1` while it is nonzero.
+ * lbm_get_driving_force: *fx_out, *fy_out receive the force as set; either may be NULL. */
+int lbm_set_periodic(lbm_ctx* c, int px, int py);
+int lbm_get_periodic(lbm_ctx* c, int* px_out, int* py_out);
+int lbm_set_driving_force(lbm_ctx* c, double fx, double fy);
+int lbm_get_driving_force(lbm_ctx* c, double* fx_out, double* fy_out);
+
 /* --- slab decomposition, externally driven exchange ---------------------------------- */
 /* No reference counterpart (the reference is single-GPU, MRT_GPU.py:29).  A step of a slab
  * is split so that a host-language driver can move halos with any transport:

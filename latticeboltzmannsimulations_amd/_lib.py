@@ -183,6 +183,10 @@ SIGNATURES = {
     "lbm_get_open_cells": (_i, [_vp, _vp, _vp]),
     "lbm_set_wall_velocity": (_i, [_vp, _vp]),          # (uw: [B][2][X][Y] doubles, or NULL)
     "lbm_get_wall_velocity": (_i, [_vp, _vp]),
+    "lbm_set_periodic": (_i, [_vp, _i, _i]),            # (px, py: 0 / 1)
+    "lbm_get_periodic": (_i, [_vp, ctypes.POINTER(_i), ctypes.POINTER(_i)]),
+    "lbm_set_driving_force": (_i, [_vp, _d, _d]),       # (fx, fy: force density per cell)
+    "lbm_get_driving_force": (_i, [_vp, ctypes.POINTER(_d), ctypes.POINTER(_d)]),
     "lbm_halo_elems": (_i, [_vp]),
     "lbm_halo_export": (_i, [_vp, _i, _vp]),
     "lbm_halo_import": (_i, [_vp, _i, _vp]),

@@ -170,6 +170,9 @@ int obstacles_change(lbm_ctx* c, ObsLevel level, Obstacles& next, int (*before_c
         cur.hold = std::move(next.hold);
         cur.hold_f = std::move(next.hold_f);
         cur.open = std::move(next.open);
+        cur.per_x = next.per_x;
+        cur.per_y = next.per_y;
+        cur.hold_all = std::move(next.hold_all);
         return LBM_OK;
     }
     if (level != ObsLevel::motion) {
@@ -194,6 +197,8 @@ int obstacles_change(lbm_ctx* c, ObsLevel level, Obstacles& next, int (*before_c
         cur.hold.clear();
         cur.hold_f.clear();
         cur.open = OpenTables{};
+        cur.per_x = cur.per_y = false;
+        cur.hold_all.clear();
     }
     if (shaped) {
         cur.shape_eff = std::move(next.shape_eff);
@@ -263,6 +268,13 @@ int lbm_set_solid_bodies(lbm_ctx* c, const int32_t* body, int nbodies, const dou
     const long long bad = body_bad_label(mask.data(), body, B * n, nbodies);
     if (bad >= 0)
         return fail(c, LBM_ERR_INVALID, "lbm_set_solid_bodies: the label of solid cell " + std::to_string(bad) + " is not in [0, nbodies)");
+    for (int b = 0; b < B && c->obs.periodic(); ++b) {   // (periodic sides: an image cell belongs to the body of its partner)
+        bool lab = false;
+        const long long bad_img = periodic_bad_cell(mask.data() + b * n, body + b * n, c->plan.geo.nx, c->plan.geo.ny, c->obs.per_x, c->obs.per_y, &lab);
+        if (bad_img >= 0)
+            return fail(c, LBM_ERR_INVALID, "lbm_set_solid_bodies: lattice " + std::to_string(b) + ": the body label of image cell " + std::to_string(bad_img) +
+                                                " differs from its partner's");
+    }
     for (size_t i = 0; centre && i < (size_t)B * nbodies * 2; ++i)
         if (!std::isfinite(centre[i])) return fail(c, LBM_ERR_INVALID, "lbm_set_solid_bodies: a centre is not finite");
     HIP_TRY(c, hipSetDevice(c->p.device));

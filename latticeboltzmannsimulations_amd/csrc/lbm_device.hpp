@@ -561,6 +561,16 @@ __device__ __forceinline__ void wall_batch(WallArg<R, WALL>& wa, unsigned z, con
     if constexpr (WALL == WALL_SHAPE) wa.sh.cell_row += batch_cells(z, geo);
 }
 
+// The uniform driving force (lbm_set_driving_force): f[k - 1] = F_k of direction k = 1 .. 8, rounded once to the lattice type on the host
+// (drive_terms, lbm_periodic.hpp), and on != 0 while it is nonzero.  A kernel argument of the one-step obstacle kernels (lbm_solid.hpp);
+// every cell that is neither solid nor held adds F_k to its post-collision population of direction k, one add in the lattice type, before
+// the delta of WALL_MOVE.  Every other kernel passes the default, no force, and compiles to what it was.
+template <typename R>
+struct Drive {
+    R f[8];
+    int on;
+};
+
 // Gather the post-stream, post-wall-rule populations of cell (x, y) from a lattice that
 // holds post-collision values (+ kept slots + parked wall densities); raw != 0: the lattice
 // holds plain populations (state just set by the host), nothing to stream.  PROM: the wall rules' equilibrium in the promoted form.
@@ -652,11 +662,12 @@ __device__ __forceinline__ void gather(const R* __restrict__ src, const Geo& geo
 // WALL (SEM_SOLID on a lattice in memory, k_step_generic_wall of lbm_solid.hpp; WALL_REST everywhere else), wa: the mode's tables of the
 // cell's lattice.  WALL_MOVE: a cell with links adds the delta of link k to its post-collision population of direction opp(k) before it
 // stores it, one add in the lattice type; no gather changes.  WALL_SHAPE: the gather applies shape_rule on the links, the stores are the
-// pure post-collision values.
+// pure post-collision values.  dr: the driving force (k_step_generic_wall alone passes one), added after the collision and before the
+// delta of WALL_MOVE, in the raw first step too.
 template <typename R, int COLL, int SEM, bool TURB, typename AS, typename AD, int WALL = WALL_REST>
 __device__ __forceinline__ void update_cell_a(const R* __restrict__ src, const AS& as, R* __restrict__ dst, const AD& ad, const Geo& geo,
                                               const Relax<R>& w0, int raw, int x, int y, const R* __restrict__ lnk = nullptr,
-                                              WallArg<R, WALL> wa = WallArg<R, WALL>{}) {
+                                              WallArg<R, WALL> wa = WallArg<R, WALL>{}, Drive<R> dr = Drive<R>{}) {
     // lnk (SEM_SOLID with an LDS window as the source): plane K_LINK of the lattice, see link_word
     const int X = geo.nx, Y = geo.NY, gy = geo.y0 + y;
     if (SEM == SEM_SOLID && (link_word<R, AS>(src, as, geo, lnk, x, y) & (LINK_SOLID | LINK_HOLD))) return;   // a solid cell, or a hold cell, is never updated
@@ -682,6 +693,10 @@ __device__ __forceinline__ void update_cell_a(const R* __restrict__ src, const A
     if (TURB) {
         dst[K_QEQ * ad.plane + me] = q2;
         dst[K_RHO * ad.plane + me] = rho;
+    }
+    if (dr.on) {
+#pragma unroll
+        for (int k = 1; k < Q; ++k) out[k] = out[k] + dr.f[k - 1];
     }
     if constexpr (WALL == WALL_MOVE && SEM == SEM_SOLID) {
         const int lw = link_word<R, AS>(src, as, geo, lnk, x, y);

@@ -11,8 +11,10 @@
 //   lbm_monitor.hip the run monitor and the line export (kernels: lbm_monitor.hpp)        (C ABI: monitor*, get_lines)
 //   lbm_residual.hip the field residual (kernels: lbm_residual.hpp)                        (C ABI: residual_*)
 //   lbm_topology.hip stream function, vorticity, extrema of psi (kernels: lbm_topology.hpp) (C ABI: topology, get_stream_function)
-//   lbm_solid.hip   solid obstacles: the mask and its link plane, the hold cells, the force on the obstacles (k_solid_force)
-//                                                                                          (C ABI: set_solid, get_solid, solid_force, set_open_cells, get_open_cells)
+//   lbm_solid.hip   solid obstacles: the mask and its link plane, the hold cells, the force on the obstacles (k_solid_force); periodic
+//                   sides (k_wrap) and the driving force
+//                                                                                          (C ABI: set_solid, get_solid, solid_force, set_open_cells, get_open_cells,
+//                                                                                           set_periodic, get_periodic, set_driving_force, get_driving_force)
 //                   (step kernels, all three wall modes: k_step_solid, k_step_generic_wall of lbm_solid.hpp; the mode: with_wall below)
 //   lbm_bodies.hip  the one writer of the obstacle state (struct Obstacles); the bodies of a mask: force and torque on each, one-shot
 //                   and as a series                                                          (C ABI: set_solid_bodies, get_solid_bodies, body_force, force_*)
@@ -22,12 +24,13 @@
 // one header of device code that the step units never see:
 //   lbm_fields.hpp  the exported state ("what lbm_get_fields would return"): the view Fields that every reader kernel takes -- built
 //                   on the host by fields_of below alone -- and the kernels of the field export, lbm_mean_u and the statistics
-// and five headers free of HIP, each driven by a CPU test through a program of its own:
+// and six headers free of HIP, each driven by a CPU test through a program of its own:
 //   lbm_schedule.hpp the schedule of automatic sampling
 //   lbm_devmem.hpp   the owner of a device allocation, and several tables uploaded into one (the device: HipMem below)
 //   lbm_bodies.hpp   the labels of a mask's bodies, their centroids, the link list and its chunks; the tables of a batch
 //   lbm_wall_motion.hpp the moving-wall term of every link, the flux check; the tables of a batch
 //   lbm_wall_shape.hpp the interpolated bounce-back of every link from its wall distance; the tables of a batch
+//   lbm_periodic.hpp periodic sides: the partner of an image cell, the wrap check, the hold cells; the constants of the driving force
 //   lbm_order.hpp    the ordering of the two streams: the state carried between units, the skeletons of a unit, the argument
 #pragma once
 #include <hip/hip_runtime.h>
@@ -49,6 +52,7 @@
 #include "lbm_order.hpp"
 #include "lbm_devmem.hpp"
 #include "lbm_bodies.hpp"
+#include "lbm_periodic.hpp"
 #include "lbm_solid.hpp"  // k_step_solid, k_step_generic_wall, extern (compiled per wall mode in lbm_solid{,_move,_shape}_f32/f64.hip)
 #include "lbm_fields.hpp" // the view of the exported state and the kernels of the field export
 #include "lbm_inst.hpp"   // the kernels, and extern template declarations of the multi-step ones (compiled in lbm_{tiles,stream*}_f32/f64.hip)
@@ -192,6 +196,9 @@ struct OpenTables {
 //   wall_uw with the motion (lbm_set_wall_velocity): uw[batch][2][nx][ny], empty while all zero; its term is part of the one table of the
 //           deltas (`moving`, or the d of `shaped`), which every call at the level of the motion rebuilds from both.  A new mask drops
 //           it, new bodies keep it.
+//   periodic beside the hold cells (lbm_set_periodic): per_x, per_y, and hold_all[batch][nx][ny] = hold and every image cell that is not
+//           solid -- what the link planes and every table see as the hold cells (hold_or_null); hold and hold_f stay the user's.  Empty
+//           while no side is periodic.  A new mask clears it; lbm_set_open_cells keeps it.
 // force_part: the workgroups' partial results of lbm_solid_force and, behind them, its records (allocated on first use, kept).
 enum class ObsLevel { mask, bodies, motion, shape, open };
 struct Obstacles {
@@ -209,8 +216,11 @@ struct Obstacles {
     std::vector<double> hold_f;
     OpenTables open;
     std::vector<double> wall_uw;
+    bool per_x = false, per_y = false;
+    std::vector<uint8_t> hold_all;
     DevBuf force_part;
-    const uint8_t* hold_or_null() const { return hold.empty() ? nullptr : hold.data(); }
+    bool periodic() const { return per_x || per_y; }
+    const uint8_t* hold_or_null() const { return !hold_all.empty() ? hold_all.data() : (hold.empty() ? nullptr : hold.data()); }
     const double* uw_or_null() const { return wall_uw.empty() ? nullptr : wall_uw.data(); }
     bool moves() const {
         return !wall_uw.empty() || std::any_of(motion.begin(), motion.end(), [](double v) { return v != 0.0; });
@@ -260,6 +270,8 @@ struct lbm_ctx {
     // the records of the record path, topo_fields the staged psi and omega of the field path; each allocated on first use, kept.
     DevBuf topo_part, topo_fields;
     Obstacles obs;              // (above)
+    double drive[2] = {0.0, 0.0};   // the driving force (lbm_set_driving_force): (fx, fy); no geometry, so it outlives every obstacle call
+    bool driven() const { return drive[0] != 0.0 || drive[1] != 0.0; }
     ncclComm_t comm = nullptr;
     int nranks = 1, rank = 0;
     bool loopback = false;      // diagnostic: 1-rank communicator, the slab exchanges halos with itself
@@ -333,6 +345,18 @@ Relax<R> relax_of(const lbm_params& p) {
     w.uLB = (R)p.uLB; w.w_nu = (R)p.omega; w.w_m = (R)p.omegam;
     w.w_e = (R)p.omega_e; w.w_eps = (R)p.omega_eps; w.w_q = (R)p.omega_q;
     return w;
+}
+
+// The driving force as the one-step obstacle kernels take it: F_k in double (drive_terms), each rounded once to the lattice type.
+template <typename R>
+Drive<R> drive_of(const lbm_ctx* c) {
+    Drive<R> d{};
+    if (!c->driven()) return d;
+    double f[8];
+    drive_terms(c->drive[0], c->drive[1], f);
+    for (int k = 0; k < 8; ++k) d.f[k] = (R)f[k];
+    d.on = 1;
+    return d;
 }
 
 template <typename R>
@@ -561,6 +585,7 @@ int monitor_series_sample(lbm_ctx* c, int which, long long step);
 // lbm_solid.hip
 int solid_fix(lbm_ctx* c);
 int solid_copy_links(lbm_ctx* c, int to);
+int periodic_wrap(lbm_ctx* c, int which, hipStream_t s);
 // lbm_bodies.hip
 int obstacles_change(lbm_ctx* c, ObsLevel level, Obstacles& next, int (*before_commit)(lbm_ctx*, const Obstacles&) = nullptr,
                      const char* call = "lbm_set_body_motion");

@@ -50,11 +50,11 @@ int launch_rows(lbm_ctx* c, int from, int to, int row0, int stride, int nrows, h
                 if (c->plan.use_vec)   // (nx a multiple of the vector width, kernel = AUTO: plan_kernel)
                     by_nt([&](auto nt) {
                         hipLaunchKernelGGL((k_step_solid<R, VT::COLL, decltype(nt)::value, WALL>), gvec, dim3(BLK), 0, s, src, dst, c->plan.geo,
-                                           relax_of<R>(c->p), batch_of<R>(c), raw, row0, stride, nxb, nblocks, wa);
+                                           relax_of<R>(c->p), batch_of<R>(c), raw | (c->driven() ? SOLID_DRIVE : 0), row0, stride, nxb, nblocks, wa, drive_of<R>(c));
                     });
-                else if constexpr (WALL != WALL_REST)
+                else if (WALL != WALL_REST || c->driven())   // (at rest the kernel with a mode launches for the driving force alone)
                     hipLaunchKernelGGL((k_step_generic_wall<R, VT::COLL, WALL>), grid_rows(c, nrows), dim3(BLK), 0, s, src, dst, c->plan.geo,
-                                       relax_of<R>(c->p), batch_of<R>(c), raw, row0, stride, wa);
+                                       relax_of<R>(c->p), batch_of<R>(c), raw, row0, stride, wa, drive_of<R>(c));
                 else launched = false;
             });
             if (launched) return;
@@ -306,7 +306,9 @@ int run_unit(lbm_ctx* c, bool* comm_used, int S, bool rccl_x) {
     int rc;
     if (S > 1 ? route == Route::one_launch : !slab) {
         rc = one_stream_unit(c->order, dev, [&] {
-            return S > 1 ? launch_deep(c, a, b, c->s_compute, S, true) : launch_rows(c, a, b, 0, 1, ny, c->s_compute);
+            if (S > 1) return launch_deep(c, a, b, c->s_compute, S, true);
+            const int rc1 = launch_rows(c, a, b, 0, 1, ny, c->s_compute);
+            return rc1 ? rc1 : periodic_wrap(c, b, c->s_compute);   // (periodic sides: the image cells of the lattice just written)
         });
     } else {
         if (S > 1 && slab && !deep && !rccl_x) return fail(c, LBM_ERR_STATE, "a multi-step unit of a slab needs the deep halo (MRT_GPU semantics) or the in-library exchange");
@@ -485,6 +487,9 @@ int lbm_step_interior(lbm_ctx* c) {
 int lbm_step_finish(lbm_ctx* c) {
     if (!c) return LBM_ERR_INVALID;
     if (c->plan.push) return fail(c, LBM_ERR_STATE, "the split-step calls do not apply to kernel = PUSH");
+    HIP_TRY(c, hipSetDevice(c->p.device));
+    const int rc = periodic_wrap(c, c->cur ^ 1, c->s_compute);   // (periodic sides: the image cells of the lattice the two calls wrote)
+    if (rc) return rc;
     finish_unit(c, 1);
     return LBM_OK;
 }

@@ -538,8 +538,10 @@ int lbm_describe(const lbm_ctx* c, char* buf, size_t len) {
     const bool shaped = (bool)c->obs.shaped.base;
     const bool moving = std::any_of(c->obs.motion.begin(), c->obs.motion.end(), [](double v) { return v != 0.0; });
     // (hold cells, lbm_set_open_cells; a nonzero lbm_set_wall_velocity, whose term shares the motion's table and mode)
+    // (periodic sides, lbm_set_periodic; a nonzero lbm_set_driving_force)
+    const char* const per = c->obs.per_x ? (c->obs.per_y ? " periodic=xy" : " periodic=x") : (c->obs.per_y ? " periodic=y" : "");
     for (const char* word : {moving ? " wall_motion=1" : "", shaped ? " wall_shape=1" : "", c->obs.hold.empty() ? "" : " open_cells=1",
-                             c->obs.wall_uw.empty() ? "" : " wall_velocity=1"}) {
+                             c->obs.wall_uw.empty() ? "" : " wall_velocity=1", per, c->driven() ? " driving_force=1" : ""}) {
         const int m = std::snprintf(buf + n, len - (size_t)n, "%s", word);
         if (m > 0) n = std::min<int>(n + m, (int)len - 1);
     }

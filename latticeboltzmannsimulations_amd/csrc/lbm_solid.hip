@@ -1,8 +1,11 @@
 // lbm_solid.hip -- liblbm_hip.so: solid obstacles in the bounce-back cavity (lbm_set_solid, lbm_get_solid, lbm_solid_force, and the hold
-// cells lbm_set_open_cells, lbm_get_open_cells of the C ABI declared in include/lbm.h; LBM_SEM_BOUNCE_BACK_SOLID).  The rule is gather_a<.., SEM_SOLID> (lbm_device.hpp), the step kernel
+// cells lbm_set_open_cells, lbm_get_open_cells, the periodic sides lbm_set_periodic, lbm_get_periodic with their kernel k_wrap, and the driving
+// force lbm_set_driving_force, lbm_get_driving_force of the C ABI declared in include/lbm.h; LBM_SEM_BOUNCE_BACK_SOLID).  The rule is gather_a<.., SEM_SOLID> (lbm_device.hpp), the step kernel
 // k_step_solid (lbm_solid.hpp); here: the mask and the link plane derived from it, the constants of solid cells, and the momentum-
 // exchange force (k_solid_force, one template for the three modes of the wall rule) reduced by the tree of lbm_reduce.hpp.  gfx950
 // only.  DESIGN.md 2.10.
+#include <cmath>
+
 #include "lbm_host.hpp"
 #include "lbm_reduce.hpp"
 
@@ -41,6 +44,32 @@ __global__ __launch_bounds__(BLK) void k_open_fix(R* __restrict__ a, R* __restri
         a[k * geo.plane + me] = v;
         b[k * geo.plane + me] = v;
     }
+}
+
+// Periodic sides (lbm_set_periodic): one thread per image cell copies the nine slots of its partner, a real cell, into the image, in the
+// lattice a step has just written (or an initialisation, a set_state).  That lattice holds post-collision populations, so the image's
+// neighbours then pull what they would pull across the seam.  Thread i: the two image columns first (px: x = 0, then x = nx - 1, y
+// running), then the two image rows without the columns' cells (py: y = 0, then y = ny - 1).  A solid image copies the w_k of its solid
+// partner.  Plane K_LINK is never copied.  Lattices of a batch on grid axis y.
+template <typename R>
+__global__ __launch_bounds__(BLK) void k_wrap(R* __restrict__ lat, Geo geo, long long bstride, int px, int py) {
+    const int nx = geo.nx, ny = geo.ny;
+    const int ncol = px ? 2 * ny : 0, w = px ? nx - 2 : nx, nrow = py ? 2 * w : 0;
+    int i = blockIdx.x * BLK + threadIdx.x, x, y;
+    if (i >= ncol + nrow) return;
+    if (i < ncol) {
+        x = i < ny ? 0 : nx - 1;
+        y = i < ny ? i : i - ny;
+    } else {
+        i -= ncol;
+        y = i < w ? 0 : ny - 1;
+        x = (i < w ? i : i - w) + (px ? 1 : 0);
+    }
+    const int sx = periodic_partner(x, nx, px != 0), sy = periodic_partner(y, ny, py != 0);
+    lat += blockIdx.y * bstride;
+    const long long me = geo.at(x, y), from = geo.at(sx, sy);
+#pragma unroll
+    for (int k = 0; k < Q; ++k) lat[k * geo.plane + me] = lat[k * geo.plane + from];
 }
 
 // Momentum exchange: over the (fluid cell, slot k) pairs whose source is a solid cell, links += 1, fx += 2 cx_opp(k) f,
@@ -116,6 +145,15 @@ __global__ __launch_bounds__(RED_WAVE) void k_solid_force_final(const double* __
     }
 }
 
+template <typename R>
+static void wrap_launch(lbm_ctx* c, int which, hipStream_t s) {
+    const Obstacles& o = c->obs;
+    if (!o.periodic()) return;
+    const long long n = periodic_images(c->plan.geo.nx, c->plan.geo.ny, o.per_x, o.per_y);
+    hipLaunchKernelGGL((k_wrap<R>), dim3((unsigned)((n + BLK - 1) / BLK), c->plan.batch), dim3(BLK), 0, s, c->lat[which].as<R>(), c->plan.geo,
+                       c->plan.bstride, o.per_x ? 1 : 0, o.per_y ? 1 : 0);
+}
+
 int solid_fix(lbm_ctx* c) {
     if (c->p.semantics != LBM_SEM_BOUNCE_BACK_SOLID) return LBM_OK;
     return launch_variant(c, [&](auto v) {
@@ -126,7 +164,14 @@ int solid_fix(lbm_ctx* c) {
         if (t.n > 0)
             hipLaunchKernelGGL((k_open_fix<R>), dim3((t.n + BLK - 1) / BLK), dim3(BLK), 0, c->s_compute, c->lat[0].as<R>(), c->lat[1].as<R>(), c->plan.geo,
                                c->plan.bstride, t.cell, (const R*)t.val, t.n);
+        for (int l = 0; l < 2; ++l) wrap_launch<R>(c, l, c->s_compute);   // (periodic sides: behind the constants, on both lattices)
     });
+}
+
+// The image cells of lat[which] from their partners, on stream s; nothing on a context without periodic sides.
+int periodic_wrap(lbm_ctx* c, int which, hipStream_t s) {
+    if (!c->obs.periodic()) return LBM_OK;
+    return launch_variant(c, [&](auto v) { wrap_launch<typename decltype(v)::R>(c, which, s); });
 }
 
 // Plane K_LINK of lat[0] -> lat[to], all lattices of a batch, on s_compute.  The two lattices get their link planes from lbm_set_solid;
@@ -219,6 +264,28 @@ static int open_tables(lbm_ctx* c, Obstacles& next) {
     next.open.base = std::move(p.buf);
     return LBM_OK;
 }
+
+// next.per_x, per_y and next.hold_all for the user's hold cells next.hold over the context's mask (lbm_periodic.hpp); a user hold cell on
+// an image cell is refused.  Without a periodic side hold_all stays empty.
+static int periodic_hold_all(lbm_ctx* c, Obstacles& next, bool px, bool py, const char* call) {
+    next.per_x = px;
+    next.per_y = py;
+    next.hold_all.clear();
+    if (!px && !py) return LBM_OK;
+    const size_t n = (size_t)c->plan.geo.nx * c->plan.geo.ny, B = (size_t)c->plan.batch;
+    next.hold_all.resize(B * n);
+    for (size_t b = 0; b < B; ++b) {
+        const long long bad = periodic_hold(c->obs.mask.data() + b * n, next.hold.empty() ? nullptr : next.hold.data() + b * n, c->plan.geo.nx, c->plan.geo.ny, px,
+                                            py, next.hold_all.data() + b * n);
+        if (bad >= 0)
+            return fail(c, LBM_ERR_INVALID, std::string(call) + ": lattice " + std::to_string(b) + ": hold cell " + std::to_string(bad) +
+                                                " is an image cell of a periodic side (it holds its partner's populations)");
+        size_t fluid = 0;
+        for (size_t i = 0; i < n; ++i) fluid += !next.hold_all[b * n + i] && !c->obs.mask[b * n + i] ? 1 : 0;
+        if (fluid == 0) return fail(c, LBM_ERR_INVALID, std::string(call) + ": lattice " + std::to_string(b) + " is left without a fluid cell");
+    }
+    return LBM_OK;
+}
 }  // namespace lbmhost
 
 using namespace lbmhost;
@@ -293,12 +360,79 @@ int lbm_set_open_cells(lbm_ctx* c, const uint8_t* hold, const double* f) {
             if (fluid == 0) return fail(c, LBM_ERR_INVALID, "lbm_set_open_cells: lattice " + std::to_string(b) + " is left without a fluid cell");
         }
     }
+    rc = periodic_hold_all(c, next, c->obs.per_x, c->obs.per_y, "lbm_set_open_cells");   // (periodic sides stay)
+    if (rc) return rc;
     HIP_TRY(c, hipSetDevice(c->p.device));
     rc = sync_all(c);
     if (rc == LBM_OK) rc = open_tables(c, next);
     if (rc == LBM_OK) rc = obstacles_change(c, ObsLevel::open, next, upload_links, "lbm_set_open_cells");
     if (rc) return rc;
     return lbm_init_equilibrium(c);   // (ends every sampler; hold cells get their populations: solid_fix)
+}
+
+int lbm_set_periodic(lbm_ctx* c, int px, int py) {
+    if (!c) return LBM_ERR_INVALID;
+    int rc = need_solid(c, "lbm_set_periodic");
+    if (rc) return rc;
+    if (c->plan.solid_tiles)
+        return fail(c, LBM_ERR_STATE, "lbm_set_periodic: the tile kernel knows no image cells (LBM_FLAG_SOLID_TILES takes none; create the context "
+                                      "without the flag)");
+    if (!c->obs.shape_q.empty() || c->obs.moves())
+        return fail(c, LBM_ERR_STATE, "lbm_set_periodic: a shape, a body motion or a wall velocity is set (geometry comes first: the periodic sides, "
+                                      "then lbm_set_solid_shape, lbm_set_body_motion and lbm_set_wall_velocity)");
+    const int nx = c->plan.geo.nx, ny = c->plan.geo.ny;
+    const bool x = px != 0, y = py != 0;
+    if ((x && nx < 4) || (y && ny < 4)) return fail(c, LBM_ERR_INVALID, "lbm_set_periodic: a periodic direction needs at least 4 cells (two images, two real cells)");
+    const size_t n = (size_t)nx * ny;
+    for (int b = 0; b < c->plan.batch; ++b) {
+        bool lab = false;
+        const long long bad = periodic_bad_cell(c->obs.mask.data() + b * n, c->obs.label.data() + b * n, nx, ny, x, y, &lab);
+        if (bad >= 0)
+            return fail(c, LBM_ERR_INVALID, "lbm_set_periodic: lattice " + std::to_string(b) + ": the " + (lab ? "body label" : "mask") + " of image cell " +
+                                                std::to_string(bad) + " differs from its partner's (an image cell is solid where its partner is, in the same body)");
+    }
+    Obstacles next;
+    next.hold = c->obs.hold;
+    next.hold_f = c->obs.hold_f;
+    rc = periodic_hold_all(c, next, x, y, "lbm_set_periodic");
+    if (rc) return rc;
+    HIP_TRY(c, hipSetDevice(c->p.device));
+    rc = sync_all(c);
+    if (rc == LBM_OK) rc = open_tables(c, next);
+    if (rc == LBM_OK) rc = obstacles_change(c, ObsLevel::open, next, upload_links, "lbm_set_periodic");
+    if (rc) return rc;
+    return lbm_init_equilibrium(c);   // (ends every sampler; the image cells get their partners' populations: solid_fix)
+}
+
+int lbm_get_periodic(lbm_ctx* c, int* px_out, int* py_out) {
+    if (!c) return LBM_ERR_INVALID;
+    const int rc = need_solid(c, "lbm_get_periodic");
+    if (rc) return rc;
+    if (px_out) *px_out = c->obs.per_x ? 1 : 0;
+    if (py_out) *py_out = c->obs.per_y ? 1 : 0;
+    return LBM_OK;
+}
+
+int lbm_set_driving_force(lbm_ctx* c, double fx, double fy) {
+    if (!c) return LBM_ERR_INVALID;
+    if (!std::isfinite(fx) || !std::isfinite(fy)) return fail(c, LBM_ERR_INVALID, "lbm_set_driving_force: the force is not finite");
+    if (fx != 0.0 || fy != 0.0) {
+        const int rc = need_solid(c, "lbm_set_driving_force");
+        if (rc) return rc;
+        if (c->plan.solid_tiles)
+            return fail(c, LBM_ERR_STATE, "lbm_set_driving_force: the tile kernel adds no force (LBM_FLAG_SOLID_TILES takes none; create the context "
+                                          "without the flag)");
+    }
+    c->drive[0] = fx;   // (travels by value with every launch: the steps already enqueued keep theirs)
+    c->drive[1] = fy;
+    return LBM_OK;
+}
+
+int lbm_get_driving_force(lbm_ctx* c, double* fx_out, double* fy_out) {
+    if (!c) return LBM_ERR_INVALID;
+    if (fx_out) *fx_out = c->drive[0];
+    if (fy_out) *fy_out = c->drive[1];
+    return LBM_OK;
 }
 
 int lbm_get_open_cells(lbm_ctx* c, uint8_t* hold_out, double* f_out) {

@@ -22,10 +22,18 @@
 //   WALL_MOVE   between the collision and the pinning of the solid lanes a fluid lane with links adds the delta of link k to its
 //               post-collision population of direction opp(k), one add in the lattice type, in the raw first step too.  Only lanes
 //               whose link word has a link bit read the table.
+//   dr          the driving force (lbm_set_driving_force; Drive, lbm_device.hpp): while bit SOLID_DRIVE of the argument raw_drive is set,
+//               every lane adds F_k to its post-collision population of direction k, one add in the lattice type, before the delta of
+//               WALL_MOVE and before the solid and the hold lanes are pinned; a uniform run-time test, no template parameter (DESIGN.md
+//               2.10).  The vector kernel never reads dr.on, which the one-cell route tests.
+constexpr int SOLID_DRIVE = 2;
 template <typename R, int COLL, bool NT, int WALL>
-__global__ __launch_bounds__(BLK) void k_step_solid(const R* __restrict__ src, R* __restrict__ dst, Geo geo, Relax<R> w, Batch<R> bt, int raw,
-                                                    int row0, int row_stride, int nxb, int nblocks, WallArg<R, WALL> wa) {
+__global__ __launch_bounds__(BLK) void k_step_solid(const R* __restrict__ src, R* __restrict__ dst, Geo geo, Relax<R> w, Batch<R> bt, int raw_drive,
+                                                    int row0, int row_stride, int nxb, int nblocks, WallArg<R, WALL> wa, Drive<R> dr) {
     constexpr int V = 16 / (int)sizeof(R);
+    // bit 0: the lattice is raw; bit 1 (SOLID_DRIVE): a driving force is set.  The flag rides in the word every thread reads first, so
+    // a context without a force waits for no scalar load of its own behind the collision (160^2: DESIGN.md 2.10)
+    const int raw = raw_drive & 1;
     typedef typename VecT<R, V>::type T;
     LBM_BATCH_SELECT(blockIdx.y)
     const int b = xcd_band(blockIdx.x, nblocks);
@@ -107,6 +115,15 @@ __global__ __launch_bounds__(BLK) void k_step_solid(const R* __restrict__ src, R
         }
     }
     collide_vec<R, COLL, V, false>(in, w, outv, hq, hr);
+    // the driving force (lbm_set_driving_force), a uniform run-time test: every lane adds F_k, one add in the lattice type; the solid and
+    // the hold lanes are pinned below, so the sums of fluid lanes alone are stored
+    if (raw_drive & SOLID_DRIVE) {
+#pragma unroll
+        for (int k = 1; k < Q; ++k) {
+#pragma unroll
+            for (int c = 0; c < V; ++c) outv[k][c] = outv[k][c] + dr.f[k - 1];
+        }
+    }
     if constexpr (WALL == WALL_MOVE) {
         if (any & 255) {
             const int32_t* cell_row = wa.cell_row;
@@ -157,31 +174,33 @@ __global__ __launch_bounds__(BLK) void k_step_solid(const R* __restrict__ src, R
     }
 }
 
-// One thread per cell (kernel = GENERIC, and lattices whose nx is no multiple of the vector width) while a motion or a shape is set:
-// k_step_generic<.., SEM_SOLID> with the mode of update_cell_a.  At rest k_step_generic itself is what launches.
+// One thread per cell (kernel = GENERIC, and lattices whose nx is no multiple of the vector width) while a motion, a shape or a driving
+// force is set: k_step_generic<.., SEM_SOLID> with the mode and the force of update_cell_a.  At rest and without a force k_step_generic
+// itself is what launches.
 template <typename R, int COLL, int WALL>
 __global__ __launch_bounds__(BLK) void k_step_generic_wall(const R* __restrict__ src, R* __restrict__ dst, Geo geo, Relax<R> w, Batch<R> bt, int raw,
-                                                           int row0, int row_stride, WallArg<R, WALL> wa) {
+                                                           int row0, int row_stride, WallArg<R, WALL> wa, Drive<R> dr) {
     const int x = blockIdx.x * BLK + threadIdx.x;
     const int y = row0 + blockIdx.y * row_stride;
     if (x >= geo.nx) return;
     LBM_BATCH_SELECT(blockIdx.z)
     wall_batch(wa, blockIdx.z, geo);
-    update_cell_a<R, COLL, SEM_SOLID, false, Geo, Geo, WALL>(src, geo, dst, geo, geo, w, raw, x, y, nullptr, wa);
+    update_cell_a<R, COLL, SEM_SOLID, false, Geo, Geo, WALL>(src, geo, dst, geo, geo, w, raw, x, y, nullptr, wa, dr);
 }
 
 // LBM_INST_SOLID(R, WALL): the six operator variants of one real type and mode -- the vector kernel with and without non-temporal
 // accesses, and k_step_generic_wall where the mode has one (LBM_SX: `extern`, or nothing in the unit that compiles them)
-#define LBM_SOLID_GENERIC_WALL_REST(R, COLL)
+#define LBM_SOLID_GENERIC_WALL_REST(R, COLL) \
+    LBM_SX template __global__ void k_step_generic_wall<R, COLL, WALL_REST>(const R* __restrict__, R* __restrict__, Geo, Relax<R>, Batch<R>, int, int, int, WallArg<R, WALL_REST>, Drive<R>);
 #define LBM_SOLID_GENERIC_WALL_MOVE(R, COLL) \
-    LBM_SX template __global__ void k_step_generic_wall<R, COLL, WALL_MOVE>(const R* __restrict__, R* __restrict__, Geo, Relax<R>, Batch<R>, int, int, int, WallArg<R, WALL_MOVE>);
+    LBM_SX template __global__ void k_step_generic_wall<R, COLL, WALL_MOVE>(const R* __restrict__, R* __restrict__, Geo, Relax<R>, Batch<R>, int, int, int, WallArg<R, WALL_MOVE>, Drive<R>);
 #define LBM_SOLID_GENERIC_WALL_SHAPE(R, COLL) \
-    LBM_SX template __global__ void k_step_generic_wall<R, COLL, WALL_SHAPE>(const R* __restrict__, R* __restrict__, Geo, Relax<R>, Batch<R>, int, int, int, WallArg<R, WALL_SHAPE>);
+    LBM_SX template __global__ void k_step_generic_wall<R, COLL, WALL_SHAPE>(const R* __restrict__, R* __restrict__, Geo, Relax<R>, Batch<R>, int, int, int, WallArg<R, WALL_SHAPE>, Drive<R>);
 #define LBM_SOLID_ONE(R, COLL, WALL)                                                                                                                          \
     LBM_SX template __global__ void k_step_solid<R, COLL, false, WALL>(const R* __restrict__, R* __restrict__, Geo, Relax<R>, Batch<R>, int, int, int, int, int, \
-                                                                       WallArg<R, WALL>);                                                                     \
+                                                                       WallArg<R, WALL>, Drive<R>);                                                           \
     LBM_SX template __global__ void k_step_solid<R, COLL, true, WALL>(const R* __restrict__, R* __restrict__, Geo, Relax<R>, Batch<R>, int, int, int, int, int,  \
-                                                                      WallArg<R, WALL>);                                                                      \
+                                                                      WallArg<R, WALL>, Drive<R>);                                                            \
     LBM_SOLID_GENERIC_##WALL(R, COLL)
 #define LBM_INST_SOLID(R, WALL)                                                                                                  \
     LBM_SOLID_ONE(R, C_SRT, WALL) LBM_SOLID_ONE(R, C_TRT, WALL) LBM_SOLID_ONE(R, C_MRT, WALL) LBM_SOLID_ONE(R, C_MRT_FAST, WALL) \

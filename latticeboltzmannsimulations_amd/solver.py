@@ -706,6 +706,41 @@ class CavitySolver:
         self._check(self.lib.lbm_get_wall_velocity(self._h, a.ctypes.data), "lbm_get_wall_velocity")
         return a
 
+    # -- periodic sides and the driving force (lbm_set_periodic, lbm_get_periodic, lbm_set_driving_force, lbm_get_driving_force) ---------
+    def set_periodic(self, x=False, y=False):
+        """Periodic sides (lbm_set_periodic): with x, columns 0 and nx - 1 become images of columns nx - 2 and 1 and the periodic domain is
+        columns 1 .. nx - 2; with y the same for rows 0 and ny - 1.  The mask and the body labels must equal their own wrap on the image
+        cells (periodic.wrap fills them).  Geometry: it ends every sampler and restarts the lattice from the initial equilibrium, and comes
+        before set_shape, set_body_motion and set_wall_velocity.  The exported arrays include the image cells (periodic.interior cuts them
+        off).  set_solid clears it; set_open_cells and set_bodies keep it.  set_periodic() restores the closed box."""
+        self._need_solid()
+        self._check(self.lib.lbm_set_periodic(self._h, int(bool(x)), int(bool(y))), "lbm_set_periodic")
+        return self
+
+    @property
+    def periodic(self):
+        """(x, y): which sides are periodic; None without solid=..."""
+        if not self.has_solid or self._h is None:
+            return None
+        px, py = ctypes.c_int(0), ctypes.c_int(0)
+        self._check(self.lib.lbm_get_periodic(self._h, ctypes.byref(px), ctypes.byref(py)), "lbm_get_periodic")
+        return bool(px.value), bool(py.value)
+
+    def set_driving_force(self, fx, fy):
+        """A uniform driving force (lbm_set_driving_force): (fx, fy) is the force density per cell, components as u.  Every collision of
+        a cell that is neither solid nor held adds (3 w_k) (cx_k fx + cy_k fy) to its post-collision population of direction k.  The
+        lattice, the step count and the samplers stay; every lattice of a batch takes the same force.  The exported u is the bare moment:
+        the physical velocity is periodic.velocity(u, rho, (fx, fy)).  (0, 0): no force."""
+        self._check(self.lib.lbm_set_driving_force(self._h, float(fx), float(fy)), "lbm_set_driving_force")
+        return self
+
+    @property
+    def driving_force(self):
+        """(fx, fy) as set; (0.0, 0.0) without a force."""
+        fx, fy = ctypes.c_double(0.0), ctypes.c_double(0.0)
+        self._check(self.lib.lbm_get_driving_force(self._h, ctypes.byref(fx), ctypes.byref(fy)), "lbm_get_driving_force")
+        return fx.value, fy.value
+
     # -- checkpoint / restart (the reference has neither; SURVEY 8f item 4) -------------------
     def save_checkpoint(self, path):
         """Write the populations and the run parameters to `path` (.npz).  Restarting from it continues bit-identically
@@ -730,6 +765,11 @@ class CavitySolver:
         uw = self.wall_velocity if self.has_solid and self._h is not None else None
         if uw is not None and uw.any():
             out.update(wall_velocity=uw)
+        per = self.periodic
+        if per is not None and any(per):
+            out.update(periodic=np.array(per))
+        if self._h is not None and any(self.driving_force):
+            out.update(driving_force=np.array(self.driving_force))
         return out
 
     def _shape_entry(self):
@@ -776,6 +816,15 @@ class CavitySolver:
             same_mask = self.has_solid and "solid" in z and np.array_equal(np.asarray(z["solid"], dtype=bool), self.solid)
             if same_mask and self._h is not None and self.wall_velocity.any():     # (this solver's own velocity goes first: it would stand in the
                 self.set_wall_velocity(None)                                      # flux check of every call below)
+            per = tuple(bool(v) for v in z["periodic"]) if same_mask and "periodic" in z else (False, False)
+            if same_mask and self.periodic is not None and per != self.periodic:      # (geometry first, as the hold cells: the periodic sides)
+                self.set_body_motion(None)
+                self.set_shape(None)
+                if not any(per):
+                    self.set_periodic()
+                else:
+                    self.set_open_cells(None)                                       # (a hold cell of this solver's may sit on an image cell)
+                    self.set_periodic(*per)
             if same_mask and ("open_hold" in z or self.open_cells is not None):     # (geometry first: it restarts the lattice, so before the state)
                 self.set_body_motion(None)
                 self.set_shape(None)
@@ -801,6 +850,8 @@ class CavitySolver:
                         uw = None
             if uw is not None:
                 self.set_wall_velocity(uw)
+            if "driving_force" in z or (self._h is not None and any(self.driving_force)):      # (the force last: it is no geometry)
+                self.set_driving_force(*(np.asarray(z["driving_force"]) if "driving_force" in z else (0.0, 0.0)))
             return int(z["steps_done"])
 
     # -- slab exchange primitives ---------------------------------------------------------

@@ -9,7 +9,9 @@ block -- one block of an eighth of the width squared in the middle --, disc -- o
 random -- 20 % of the cells, seeded --, interior -- the same, one cell clear of the perimeter), motion (with solid: rest -- set_body_motion of
 zeros, the kernels of obstacles at rest -- or rotate -- the solid cells turn as one body about their centroid, 0.05 at three quarters of the
 width from it; not with route=tiles), shape (with solid: disc -- set_shape with the exact fractions of the circle of solid=disc --, random -- q uniform in (0, 1], seeded, for any
-mask -- or half -- 1/2 on every link: the kernels of a shaped lattice; set before the motion; not with route=tiles), route (with solid: single --
+mask -- or half -- 1/2 on every link: the kernels of a shaped lattice; set before the motion; not with route=tiles), periodic (with solid: x, y
+or xy -- set_periodic, the k_wrap launch behind every step; the mask is wrapped first), drive (with solid: 1 -- set_driving_force(1e-6, 0)),
+route (with solid: single --
 one step per launch, the default -- or tiles -- the multi-step tile kernel, tuning solid_tiles), force (with solid: series.E -- the run
 with begin_force(every=E) --, loop.E -- the host loop step(E); solid_force() --, plain.E -- step(E); sync() without any force --, or call -- no stepping: microseconds per call of
 body_force() and of solid_force(); these three are timed with the host clock around work that ends in a synchronisation), batch (that
@@ -77,6 +79,12 @@ def parse(case):
                 if v not in ("disc", "half", "random"):
                     raise ValueError("shape must be disc, half or random")
                 kw["shape"] = v
+            elif k == "periodic":
+                if v not in ("x", "y", "xy"):
+                    raise ValueError("periodic must be x, y or xy")
+                kw["periodic"] = v
+            elif k == "drive":
+                kw["drive"] = int(v)
             elif k == "batch":
                 kw["batch"] = int(v)
             elif k in ("tb_steps", "frame_seg"):
@@ -98,8 +106,17 @@ def main():
         force = kw.pop("force", None)
         motion = kw.pop("motion", None)
         shape = kw.pop("shape", None)
+        per = kw.pop("periodic", None)
+        drive = kw.pop("drive", 0)
+        if per is not None:
+            from latticeboltzmannsimulations_amd import periodic
+            kw["solid"] = periodic.wrap(kw["solid"], "x" in per, "y" in per)
         make = (lambda *a_, **k_: CavityBatch(a_[0], a_[1], [a_[2]] * B, **k_)) if B > 1 else CavitySolver
         with make(nx, ny, 1000.0, dtype=dtype, arith=arith, tuning=tune, **kw) as s:
+            if per is not None:
+                s.set_periodic("x" in per, "y" in per)
+            if drive:
+                s.set_driving_force(1e-6, 0.0)
             if shape is not None:
                 q = {"half": lambda: np.full((8, nx, ny), 0.5), "random": lambda: 1.0 - np.random.default_rng(2).random((8, nx, ny)),
                      "disc": lambda: solid.disc_fractions(kw["solid"], (nx - 1) / 2, (ny - 1) / 2, nx / 16)}[shape]()
@@ -141,7 +158,7 @@ def main():
             else:
                 reps = [s.time_steps(a.steps) / a.steps for _ in range(a.reps)]
             ms = min(reps)
-            print(f"{case:48s} S={s.next_unit(1000)}{' move' if s.describe().get('wall_motion') else ''}{' shape' if s.describe().get('wall_shape') else ''}  {B * nx * ny / ms / 1e6:8.1f} GLUPS  {ms * 1e3:9.2f} us/step  "
+            print(f"{case:48s} S={s.next_unit(1000)}{' move' if s.describe().get('wall_motion') else ''}{' shape' if s.describe().get('wall_shape') else ''}{' periodic=' + s.describe()['periodic'] if 'periodic' in s.describe() else ''}{' drive' if s.describe().get('driving_force') else ''}  {B * nx * ny / ms / 1e6:8.1f} GLUPS  {ms * 1e3:9.2f} us/step  "
                   f"repeats {' '.join('%.1f' % (B * nx * ny / r / 1e6) for r in reps)}"
                   + (f"  us/step {' '.join('%.2f' % (r * 1e3) for r in reps)}" if force else ""), flush=True)
 
