@@ -706,6 +706,80 @@ int lbm_get_periodic(lbm_ctx* c, int* px_out, int* py_out);
 int lbm_set_driving_force(lbm_ctx* c, double fx, double fy);
 int lbm_get_driving_force(lbm_ctx* c, double* fx_out, double* fy_out);
 
+/* --- a passive scalar on an obstacle lattice: temperature or dye ------------------------------------ */
+/* No reference counterpart.  An advected, diffusing scalar C carried by the flow of a LBM_SEM_BOUNCE_BACK_SOLID context (a lone lattice,
+ * one step per launch, batch = 1): a second set of nine populations g_k on the flow's own D2Q9 stencil, weights and (x, y) conventions, in
+ * two ping-pong lattices of the flow's layout that hold post-collision populations and are pulled from, as the flow's are.  The scalar has
+ * no link plane: it reads the flow's.  It never acts on the flow: the flow's bits with a scalar are those without.
+ *
+ * One scalar step of a cell that is neither solid nor held, every operation in the lattice type, none fused, in the order written:
+ *   gather   g_k = g*_k(x - cx_k, y + cy_k).  A source outside the lattice: g_k = g*_opp(k) of the cell itself (the box edges and the lid
+ *            are adiabatic; the lid adds nothing).  A source that is a solid cell (bit k - 1 of the cell's link word): adiabatic,
+ *            g_k = g*_opp(k); Dirichlet with the value Cw (anti-bounce-back), g_k = t - g*_opp(k), t = 2 w_k Cw formed in double and rounded
+ *            once to the lattice type (one table row per fluid cell with a Dirichlet link, built on the host).
+ *   moments  C = (((((((g_0 + g_1) + g_2) + g_3) + g_4) + g_5) + g_6) + g_7) + g_8.  (ux, uy): the moments of the flow lattice that the
+ *            flow step of the same lbm_step iteration has just written, image cells wrapped -- the bits lbm_get_fields exports, in the
+ *            lattice type, after the NEXT step (under a shape, through the shaped gather).  A driving force's half-force shift is NOT
+ *            added: the scalar is advected by the bare moment.
+ *   collide  TRT on the pairs (a, b) = (1, 3), (2, 4), (5, 7), (6, 8), cu = c_a.u:  g*_0 = g_0 - w+ (g_0 - w_0 C);
+ *            gp = (g_a + g_b) / 2;  gm = (g_a - g_b) / 2;  e = w_a C;  dp = w+ (gp - e);  dm = w- (gm - (3 e) cu);
+ *            g*_a = (g_a - dp) - dm;  g*_b = (g_b - dp) + dm.
+ *            In double on the host: tm = 3 D + 1/2, w- = 1 / tm, w+ = 1 / (magic / (tm - 1/2) + 1/2), each rounded once to the lattice
+ *            type.  magic is the TRT product (1/w+ - 1/2)(1/w- - 1/2), 1/4 by convention; BGK is magic = (3 D)^2.
+ *   There is one arithmetic: under a flow with arith = fast the scalar kernel is the same code fed other velocities.
+ * Solid cells store zeros.  A hold cell of the flow is a hold cell of the scalar: a user's hold cell (lbm_set_open_cells) keeps
+ *   g_k = (w_k Ch) (1 + 3 (cx_k ux + cy_k uy)), formed in double in this order and rounded once, (ux, uy) the moments of the flow
+ *   populations it holds (as given, in double), Ch its hold value, or its initial value where hold_value is NULL; an image cell of a
+ *   periodic side is refreshed from its partner after every scalar step by the k_wrap launch on the scalar lattice.
+ * The first scalar step after lbm_scalar_begin or lbm_scalar_set_state is raw, as the flow's: the lattice holds plain populations, which
+ *   are collided without streaming.  Inside lbm_step (and lbm_step_finish) every flow step and its wrap are followed by the scalar step
+ *   and its wrap, on the compute stream.
+ * Limits.  Wall velocities, body motions and shapes do not enter the scalar's wall rule, which stays half-way (the velocity it is
+ *   advected by is the one every export sees).  The scheme is not positivity-preserving.  A held outlet holds a value; there is no
+ *   convective or zero-gradient outlet.  No buoyancy: nothing feeds back on the flow.
+ *
+ * lbm_scalar_begin: arrays [X][Y] in the host layout of lbm_set_solid's mask.  c0: the initial values (read on cells that are not
+ *   solid); the lattice starts from the plain populations w_k C0, weight and C0 rounded to the lattice type.  dirichlet (NULL: none):
+ *   nonzero marks a solid cell that holds wall_value there; every other solid cell is adiabatic.  hold_value (NULL: the initial values):
+ *   read on the user's hold cells.  Replaces a scalar that is active.  LBM_ERR_STATE with a reason: another semantics, a slab, batch > 1, a
+ *   LBM_FLAG_SOLID_TILES context.  LBM_ERR_INVALID with a reason: D or magic not finite or <= 0; c0 NULL or not finite on a cell that is
+ *   not solid; a Dirichlet flag on a cell that is not solid; a Dirichlet cell without a finite wall value; a hold value that is not
+ *   finite.  lbm_describe appends ` scalar=D,magic` while a scalar is active.
+ * Whatever ends the samplers and restarts the lattice because the geometry changed -- lbm_set_solid, lbm_set_open_cells,
+ *   lbm_set_periodic -- ends the scalar.  lbm_set_state and lbm_init_equilibrium keep it and leave its populations alone;
+ *   lbm_set_solid_bodies, motions, shapes and the driving force keep it too.
+ * lbm_scalar_end: ends the scalar and frees its lattices and tables; LBM_OK without one.  The flow's launches, bits and describe text are
+ *   then those of a context that never had one.
+ * lbm_scalar_active: 1 and the parameters (either pointer may be NULL) while a scalar is active, 0 otherwise.
+ * lbm_scalar_get: g_out[9][X][Y] receives the arriving populations of the current state (what the next scalar step gathers: zeros on solid
+ *   cells, the held values on hold cells); conc_out[X][Y] receives C of the state the last scalar step started from -- the one-step lag
+ *   of lbm_get_fields, so that C and u of one call belong to the same iteration; before the first step, of the state as set.  Either may be
+ *   NULL.
+ * lbm_scalar_get_stored: g_out[9][X][Y] receives the post-collision populations as the lattice holds them (what lbm_scalar_flux reads).
+ * lbm_scalar_set_state: plain populations g[9][X][Y]; values on solid and hold cells are ignored; the next scalar step is raw.  The
+ *   populations of lbm_scalar_get continue a run bit for bit (with lbm_set_state of the flow's).
+ * lbm_scalar_totals: over the cells that are neither solid nor image cells of a periodic side, of C as lbm_scalar_get returns it,
+ *   converted to double: their count, the sum, the minimum and the maximum, by the fixed tree of the samplers.  step: scalar steps since
+ *   lbm_scalar_begin or lbm_scalar_set_state.
+ * lbm_scalar_flux: out[nbodies] (lbm_solid_body_count), one record per body over the links of the list lbm_body_force walks:
+ *   flux = sum of (double)g_k - (double)g*_opp(k), g_k what the next gather returns for the link -- the scalar that enters the fluid from
+ *   the body per step; an exact zero on adiabatic links.  LBM_ERR_STATE before the first scalar step. */
+typedef struct lbm_scalar_record {
+    double step, cells, sum, min, max;
+} lbm_scalar_record;
+typedef struct lbm_scalar_flux_record {
+    double step, links, flux;
+} lbm_scalar_flux_record;
+int lbm_scalar_begin(lbm_ctx* c, double diffusivity, double magic, const double* c0, const uint8_t* dirichlet, const double* wall_value,
+                     const double* hold_value);
+int lbm_scalar_end(lbm_ctx* c);
+int lbm_scalar_active(const lbm_ctx* c, double* diffusivity_out, double* magic_out);
+int lbm_scalar_get(lbm_ctx* c, void* conc_out, void* g_out, int host_dtype);
+int lbm_scalar_get_stored(lbm_ctx* c, void* g_out, int host_dtype);
+int lbm_scalar_set_state(lbm_ctx* c, const void* g_host, int host_dtype);
+int lbm_scalar_totals(lbm_ctx* c, lbm_scalar_record* out);
+int lbm_scalar_flux(lbm_ctx* c, lbm_scalar_flux_record* out);
+
 /* --- slab decomposition, externally driven exchange ---------------------------------- */
 /* No reference counterpart (the reference is single-GPU, MRT_GPU.py:29).  A step of a slab
  * is split so that a host-language driver can move halos with any transport:

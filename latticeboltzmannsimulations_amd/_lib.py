@@ -90,13 +90,21 @@ class lbm_body_force_record(ctypes.Structure):
     _fields_ = [(n, ctypes.c_double) for n in ("step", "body", "links", "fx", "fy", "tz")]
 
 
+class lbm_scalar_record(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_double) for n in ("step", "cells", "sum", "min", "max")]
+
+
+class lbm_scalar_flux_record(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_double) for n in ("step", "links", "flux")]
+
+
 def sources():
     return [os.path.join(_CSRC, f) for f in sorted(os.listdir(_CSRC)) if f.endswith((".hip", ".hpp"))] + [HEADER]
 
 
 def build(force=False, verbose=False):
     """Compile csrc/*.hip for gfx950 into liblbm_hip.so next to this file (in-tree).  The translation units (eight of host code +
-    C ABI: lbm_hip / lbm_plan / lbm_launch / lbm_comm / lbm_sampling / lbm_monitor / lbm_residual / lbm_topology / lbm_solid / lbm_bodies / lbm_body_motion / lbm_body_shape; the explicit instantiations of the tile and
+    C ABI: lbm_hip / lbm_plan / lbm_launch / lbm_comm / lbm_sampling / lbm_monitor / lbm_residual / lbm_topology / lbm_solid / lbm_bodies / lbm_body_motion / lbm_body_shape / lbm_scalar (with its kernels, from lbm_scalar.hpp); the explicit instantiations of the tile and
     streaming kernels, of the one-step kernels with a solid mask per mode of the wall rule -- lbm_solid / lbm_solid_move / lbm_solid_shape,
     all three from lbm_solid.hpp -- and of the tile kernel with solid cells, for float and for double) are compiled in parallel into csrc/_obj/ and linked."""
     srcs = sources()
@@ -187,6 +195,14 @@ SIGNATURES = {
     "lbm_get_periodic": (_i, [_vp, ctypes.POINTER(_i), ctypes.POINTER(_i)]),
     "lbm_set_driving_force": (_i, [_vp, _d, _d]),       # (fx, fy: force density per cell)
     "lbm_get_driving_force": (_i, [_vp, ctypes.POINTER(_d), ctypes.POINTER(_d)]),
+    "lbm_scalar_begin": (_i, [_vp, _d, _d, _vp, _vp, _vp, _vp]),   # (D, magic; c0, dirichlet, wall_value, hold_value: [X][Y] or NULL)
+    "lbm_scalar_end": (_i, [_vp]),
+    "lbm_scalar_active": (_i, [_vp, ctypes.POINTER(_d), ctypes.POINTER(_d)]),
+    "lbm_scalar_get": (_i, [_vp, _vp, _vp, _i]),
+    "lbm_scalar_get_stored": (_i, [_vp, _vp, _i]),
+    "lbm_scalar_set_state": (_i, [_vp, _vp, _i]),
+    "lbm_scalar_totals": (_i, [_vp, ctypes.POINTER(lbm_scalar_record)]),
+    "lbm_scalar_flux": (_i, [_vp, ctypes.POINTER(lbm_scalar_flux_record)]),
     "lbm_halo_elems": (_i, [_vp]),
     "lbm_halo_export": (_i, [_vp, _i, _vp]),
     "lbm_halo_import": (_i, [_vp, _i, _vp]),

@@ -166,6 +166,7 @@ int obstacles_change(lbm_ctx* c, ObsLevel level, Obstacles& next, int (*before_c
         if (rc == LBM_OK && before_commit) rc = before_commit(c, next);
         if (rc) return rc;
         sampler_free(c, SMP_FORCE);   // (its link list changed)
+        scalar_free(c);               // (geometry: its wall values and hold cells refer to the old one)
         cur.body = std::move(next.body);
         cur.hold = std::move(next.hold);
         cur.hold_f = std::move(next.hold_f);
@@ -190,6 +191,7 @@ int obstacles_change(lbm_ctx* c, ObsLevel level, Obstacles& next, int (*before_c
     if (rc == LBM_OK && before_commit) rc = before_commit(c, next);
     if (rc) return rc;
     if (level == ObsLevel::mask) {
+        scalar_free(c);   // (a new mask ends the scalar, as it ends the shape and the hold cells)
         cur.mask = std::move(next.mask);
         cur.shape_q.clear();
         cur.shape_eff.clear();

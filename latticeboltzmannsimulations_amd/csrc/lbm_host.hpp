@@ -21,6 +21,7 @@
 //   lbm_body_motion.hip the wall velocity of moving bodies and of single solid cells: its tables (C ABI: set_body_motion, get_body_motion,
 //                                                                                          set_wall_velocity, get_wall_velocity)
 //   lbm_body_shape.hip  curved obstacle surfaces, a wall distance per link: its tables         (C ABI: set_solid_shape, get_solid_shape)
+//   lbm_scalar.hip  the passive scalar of an obstacle lattice: its lattices, tables and step (kernels: lbm_scalar.hpp)   (C ABI: scalar_*)
 // one header of device code that the step units never see:
 //   lbm_fields.hpp  the exported state ("what lbm_get_fields would return"): the view Fields that every reader kernel takes -- built
 //                   on the host by fields_of below alone -- and the kernels of the field export, lbm_mean_u and the statistics
@@ -227,6 +228,28 @@ struct Obstacles {
     }
 };
 
+// The passive scalar (lbm_scalar_*, lbm_scalar.hip; kernels and host tables: lbm_scalar.hpp), empty while none is active: the two
+// ping-pong lattices in the flow's layout, lat[cur] the source of the next scalar step and raw[i] != 0 while lat[i] holds plain
+// populations; the wall-value table (cell_row[ny][nx], val[rows][8] in the lattice type, bits[rows]) and the constants of the user's hold
+// cells (hold_cell[n][2] = (x, y), hold_val[n][9] in the lattice type), each inside one allocation; part: the workgroups' partial results
+// of the totals and of the flux and, behind them, their records (allocated on first use, kept).  steps: scalar steps since
+// lbm_scalar_begin or lbm_scalar_set_state.
+struct ScalarState {
+    bool active = false;
+    double D = 0.0, magic = 0.0;
+    DevBuf lat[2];
+    int raw[2] = {1, 1};
+    int cur = 0;
+    long long steps = 0;
+    DevBuf walls, holds, part;
+    const int32_t* cell_row = nullptr;
+    const void* val = nullptr;
+    const uint8_t* bits = nullptr;
+    const int32_t* hold_cell = nullptr;
+    const void* hold_val = nullptr;
+    int nhold = 0;
+};
+
 // Run state.  What was decided once is in `plan`; p stays for the fields later code branches on (dtype, collision, semantics, turb,
 // arith, device) and for the relaxation rates, which lbm_set_relaxation rewrites.
 struct lbm_ctx {
@@ -270,6 +293,7 @@ struct lbm_ctx {
     // the records of the record path, topo_fields the staged psi and omega of the field path; each allocated on first use, kept.
     DevBuf topo_part, topo_fields;
     Obstacles obs;              // (above)
+    ScalarState scalar;         // (above)
     double drive[2] = {0.0, 0.0};   // the driving force (lbm_set_driving_force): (fx, fy); no geometry, so it outlives every obstacle call
     bool driven() const { return drive[0] != 0.0 || drive[1] != 0.0; }
     ncclComm_t comm = nullptr;
@@ -586,6 +610,10 @@ int monitor_series_sample(lbm_ctx* c, int which, long long step);
 int solid_fix(lbm_ctx* c);
 int solid_copy_links(lbm_ctx* c, int to);
 int periodic_wrap(lbm_ctx* c, int which, hipStream_t s);
+int periodic_wrap_lattice(lbm_ctx* c, void* lat, hipStream_t s);
+// lbm_scalar.hip
+int scalar_step(lbm_ctx* c);
+void scalar_free(lbm_ctx* c);
 // lbm_bodies.hip
 int obstacles_change(lbm_ctx* c, ObsLevel level, Obstacles& next, int (*before_commit)(lbm_ctx*, const Obstacles&) = nullptr,
                      const char* call = "lbm_set_body_motion");

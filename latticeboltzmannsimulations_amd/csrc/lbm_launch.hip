@@ -333,7 +333,8 @@ int run_unit(lbm_ctx* c, bool* comm_used, int S, bool rccl_x) {
     }
     if (rc) return rc;
     finish_unit(c, S);
-    return LBM_OK;
+    // a passive scalar (lbm_scalar_begin: a lone lattice, one step per launch) follows the flow step and its wrap, on s_compute
+    return c->scalar.active ? scalar_step(c) : LBM_OK;
 }
 
 // Recompute the lattice of the step before the last into lat[LAT_LAG] (see lbm_ctx::lag); returns the index of the lattice
@@ -491,7 +492,7 @@ int lbm_step_finish(lbm_ctx* c) {
     const int rc = periodic_wrap(c, c->cur ^ 1, c->s_compute);   // (periodic sides: the image cells of the lattice the two calls wrote)
     if (rc) return rc;
     finish_unit(c, 1);
-    return LBM_OK;
+    return c->scalar.active ? scalar_step(c) : LBM_OK;
 }
 
 int lbm_step_unit(lbm_ctx* c, int S) {

@@ -545,6 +545,10 @@ int lbm_describe(const lbm_ctx* c, char* buf, size_t len) {
         const int m = std::snprintf(buf + n, len - (size_t)n, "%s", word);
         if (m > 0) n = std::min<int>(n + m, (int)len - 1);
     }
+    if (c->scalar.active) {   // (a passive scalar, lbm_scalar_begin: its diffusivity and its TRT product)
+        const int m = std::snprintf(buf + n, len - (size_t)n, " scalar=%.17g,%.17g", c->scalar.D, c->scalar.magic);
+        if (m > 0) n = std::min<int>(n + m, (int)len - 1);
+    }
     return n;
 }
 

@@ -146,12 +146,12 @@ __global__ __launch_bounds__(RED_WAVE) void k_solid_force_final(const double* __
 }
 
 template <typename R>
-static void wrap_launch(lbm_ctx* c, int which, hipStream_t s) {
+static void wrap_launch(lbm_ctx* c, R* lat, hipStream_t s) {
     const Obstacles& o = c->obs;
     if (!o.periodic()) return;
     const long long n = periodic_images(c->plan.geo.nx, c->plan.geo.ny, o.per_x, o.per_y);
-    hipLaunchKernelGGL((k_wrap<R>), dim3((unsigned)((n + BLK - 1) / BLK), c->plan.batch), dim3(BLK), 0, s, c->lat[which].as<R>(), c->plan.geo,
-                       c->plan.bstride, o.per_x ? 1 : 0, o.per_y ? 1 : 0);
+    hipLaunchKernelGGL((k_wrap<R>), dim3((unsigned)((n + BLK - 1) / BLK), c->plan.batch), dim3(BLK), 0, s, lat, c->plan.geo, c->plan.bstride,
+                       o.per_x ? 1 : 0, o.per_y ? 1 : 0);
 }
 
 int solid_fix(lbm_ctx* c) {
@@ -164,14 +164,19 @@ int solid_fix(lbm_ctx* c) {
         if (t.n > 0)
             hipLaunchKernelGGL((k_open_fix<R>), dim3((t.n + BLK - 1) / BLK), dim3(BLK), 0, c->s_compute, c->lat[0].as<R>(), c->lat[1].as<R>(), c->plan.geo,
                                c->plan.bstride, t.cell, (const R*)t.val, t.n);
-        for (int l = 0; l < 2; ++l) wrap_launch<R>(c, l, c->s_compute);   // (periodic sides: behind the constants, on both lattices)
+        for (int l = 0; l < 2; ++l) wrap_launch<R>(c, c->lat[l].as<R>(), c->s_compute);   // (periodic sides: behind the constants, on both lattices)
     });
 }
 
 // The image cells of lat[which] from their partners, on stream s; nothing on a context without periodic sides.
 int periodic_wrap(lbm_ctx* c, int which, hipStream_t s) {
     if (!c->obs.periodic()) return LBM_OK;
-    return launch_variant(c, [&](auto v) { wrap_launch<typename decltype(v)::R>(c, which, s); });
+    return periodic_wrap_lattice(c, c->lat[which].get(), s);
+}
+// ... of any lattice in the context's layout and type (the scalar lattices: lbm_scalar.hip), by the same launch
+int periodic_wrap_lattice(lbm_ctx* c, void* lat, hipStream_t s) {
+    if (!c->obs.periodic()) return LBM_OK;
+    return launch_variant(c, [&](auto v) { wrap_launch<typename decltype(v)::R>(c, (typename decltype(v)::R*)lat, s); });
 }
 
 // Plane K_LINK of lat[0] -> lat[to], all lattices of a batch, on s_compute.  The two lattices get their link planes from lbm_set_solid;

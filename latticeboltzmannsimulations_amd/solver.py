@@ -741,6 +741,104 @@ class CavitySolver:
         self._check(self.lib.lbm_get_driving_force(self._h, ctypes.byref(fx), ctypes.byref(fy)), "lbm_get_driving_force")
         return fx.value, fy.value
 
+    # -- a passive scalar: temperature or dye (lbm_scalar_*) ---------------------------------------------------------------
+    def _cells(self, a, name, fill=None):
+        """A float64 [X, Y] array as the scalar calls take it; a number fills the lattice."""
+        a = np.asarray(fill if a is None else a, dtype=np.float64)
+        if a.ndim == 0:
+            a = np.full((self.nx, self.ny), float(a))
+        if a.shape != (self.nx, self.ny):
+            raise ValueError(f"{name} must be a number or an array of shape {(self.nx, self.ny)}")
+        return np.ascontiguousarray(a)
+
+    def begin_scalar(self, D, c0=0.0, magic=0.25, wall_value=None, hold_value=None):
+        """Start a passive scalar C (lbm_scalar_begin) that every later flow step carries along: advected by the exported velocity,
+        diffusing with the diffusivity D (lattice units; TRT with the product `magic`, BGK is magic = (3 D)**2).  c0: the initial values,
+        a number or [X, Y].  wall_value: [X, Y] with the value a solid cell holds (Dirichlet, anti-bounce-back) and NaN on adiabatic
+        cells; None: every wall is adiabatic, as the box edges and the lid always are.  hold_value: a number or [X, Y], what the user's
+        hold cells (set_open_cells) hold; None: their initial values.  One lattice with solid=..., one step per launch.  set_solid,
+        set_open_cells and set_periodic end the scalar; set_state and init_equilibrium keep it.  Replaces an active scalar."""
+        self._need_solid()
+        if self._lead:
+            raise RuntimeError("the scalar knows no batches")
+        c0 = self._cells(c0, "c0")
+        flag = value = None
+        if wall_value is not None:
+            wv = self._cells(wall_value, "wall_value")
+            flag = np.ascontiguousarray(~np.isnan(wv), dtype=np.uint8)
+            value = np.ascontiguousarray(np.where(flag != 0, wv, 0.0))
+        hv = None if hold_value is None else self._cells(hold_value, "hold_value")
+        self._check(self.lib.lbm_scalar_begin(self._h, float(D), float(magic), c0.ctypes.data, None if flag is None else flag.ctypes.data,
+                                              None if value is None else value.ctypes.data, None if hv is None else hv.ctypes.data),
+                    "lbm_scalar_begin")
+        self._scalar_given = dict(scalar_c0=c0, **({} if wall_value is None else dict(scalar_wall_value=wv)),
+                                  **({} if hv is None else dict(scalar_hold_value=hv)))
+        return self
+
+    def end_scalar(self):
+        """End the scalar (lbm_scalar_end): the flow steps, and describe(), are then those of a solver that never had one."""
+        self._check(self.lib.lbm_scalar_end(self._h), "lbm_scalar_end")
+        self._scalar_given = None
+        return self
+
+    @property
+    def scalar_active(self):
+        """None, or dict(D, magic) of the active scalar."""
+        if self._h is None:
+            return None
+        D, m = ctypes.c_double(0.0), ctypes.c_double(0.0)
+        rc = self.lib.lbm_scalar_active(self._h, ctypes.byref(D), ctypes.byref(m))
+        if rc < 0:
+            self._check(rc, "lbm_scalar_active")
+        return dict(D=D.value, magic=m.value) if rc else None
+
+    def scalar(self, out_dtype=None):
+        """C[X, Y] of the state the last scalar step started from (the one-step lag of get_fields: C and u of one moment belong to the
+        same iteration); zero on solid cells.  Image cells of periodic sides included (scalar.interior cuts them off)."""
+        dt = self.dtype if out_dtype is None else np.dtype(out_dtype)
+        C = np.zeros((self.nx, self.ny), dtype=dt)
+        self._check(self.lib.lbm_scalar_get(self._h, C.ctypes.data, None, _DT[dt]), "lbm_scalar_get")
+        return C
+
+    def scalar_populations(self, stored=False, out_dtype=None):
+        """g[9, X, Y]: the arriving populations of the current state (what the next scalar step gathers; set_scalar_state of them continues
+        the run bit for bit), or, stored=True, the post-collision populations as the lattice holds them."""
+        dt = self.dtype if out_dtype is None else np.dtype(out_dtype)
+        g = np.zeros((9, self.nx, self.ny), dtype=dt)
+        if stored:
+            self._check(self.lib.lbm_scalar_get_stored(self._h, g.ctypes.data, _DT[dt]), "lbm_scalar_get_stored")
+        else:
+            self._check(self.lib.lbm_scalar_get(self._h, None, g.ctypes.data, _DT[dt]), "lbm_scalar_get")
+        return g
+
+    def set_scalar_state(self, g):
+        """Upload plain scalar populations g[9, X, Y] (lbm_scalar_set_state); the next scalar step is raw, as the flow's after set_state."""
+        g = self._host(g, (9, self.nx, self.ny), "g")
+        self._check(self.lib.lbm_scalar_set_state(self._h, g.ctypes.data, _DT[g.dtype]), "lbm_scalar_set_state")
+        return self
+
+    def scalar_totals(self):
+        """dict(step, cells, sum, min, max) of scalar() over the cells that are neither solid nor images, reduced on the device in double."""
+        rec = L.lbm_scalar_record()
+        self._check(self.lib.lbm_scalar_totals(self._h, ctypes.byref(rec)), "lbm_scalar_totals")
+        return dict(step=int(rec.step), cells=int(rec.cells), sum=rec.sum, min=rec.min, max=rec.max)
+
+    def scalar_flux(self):
+        """The scalar that enters the fluid per step from each body (lbm_scalar_flux): dict(step, links, flux) of arrays [nbodies]; zero on
+        adiabatic bodies.  Not before the first scalar step."""
+        self._need_solid()
+        rec = (L.lbm_scalar_flux_record * self.nbodies)()
+        self._check(self.lib.lbm_scalar_flux(self._h, rec), "lbm_scalar_flux")
+        return dict(step=np.array([int(r.step) for r in rec]), links=np.array([int(r.links) for r in rec]), flux=np.array([r.flux for r in rec]))
+
+    def _scalar_entry(self):
+        """What a checkpoint says of the scalar: nothing without one (the file of such a run is what it was), else its parameters, the
+        arrays begin_scalar took and the arriving populations."""
+        act = self.scalar_active if self.has_solid and not self._lead else None
+        if act is None:
+            return {}
+        return dict(scalar_D=act["D"], scalar_magic=act["magic"], scalar_g=self.scalar_populations(), **(getattr(self, "_scalar_given", None) or {}))
+
     # -- checkpoint / restart (the reference has neither; SURVEY 8f item 4) -------------------
     def save_checkpoint(self, path):
         """Write the populations and the run parameters to `path` (.npz).  Restarting from it continues bit-identically
@@ -752,7 +850,7 @@ class CavitySolver:
                  semantics=self.semantics, dtype=self.dtype.name, rows=np.array([self.y0, self.ny_local]), turb=self.turb, u=u, rho=rho,
                  arith=self.arith, **(dict(solid=self.solid) if self.has_solid else {}),
                  **{**(dict(zip(("body_labels", "body_centres"), self.bodies)) if getattr(self, "_bodies_given", False) else {}),
-                    **self._motion_entry(), **self._shape_entry(), **self._open_entry()})
+                    **self._motion_entry(), **self._shape_entry(), **self._open_entry(), **self._scalar_entry()})
         return path
 
     def _open_entry(self):
@@ -852,6 +950,11 @@ class CavitySolver:
                 self.set_wall_velocity(uw)
             if "driving_force" in z or (self._h is not None and any(self.driving_force)):      # (the force last: it is no geometry)
                 self.set_driving_force(*(np.asarray(z["driving_force"]) if "driving_force" in z else (0.0, 0.0)))
+            if same_mask and "scalar_g" in z:      # (the scalar last: the geometry calls above end one; a file without it leaves this solver's as it is)
+                self.begin_scalar(float(z["scalar_D"]), np.asarray(z["scalar_c0"]), float(z["scalar_magic"]),
+                                  np.asarray(z["scalar_wall_value"]) if "scalar_wall_value" in z else None,
+                                  np.asarray(z["scalar_hold_value"]) if "scalar_hold_value" in z else None)
+                self.set_scalar_state(np.ascontiguousarray(z["scalar_g"]))
             return int(z["steps_done"])
 
     # -- slab exchange primitives ---------------------------------------------------------
