@@ -696,7 +696,8 @@ int lbm_get_wall_velocity(lbm_ctx* c, double* uw_out);
  *   collision of a cell that is neither solid nor held is followed by f*_k = f*_k + F_k, one add in the lattice type, never fused (arith =
  *   fast too), in the raw first step too, before the delta of a moving wall.  The scheme is the first-order one: the equilibrium uses the
  *   bare velocity, the physical velocity is (sum c f + F / 2) / rho, and the exports and samplers keep reporting the bare moments.  It is
- *   exact for a steady uniform driver; a force that varies in space or time is out of scope.  All lattices of a batch share one force.
+ *   exact for a steady uniform driver; the one force that varies in space and time is lbm_set_buoyancy's, by this same scheme.  All lattices
+ *   of a batch share one force.
  * lbm_set_driving_force: may be called at any time; it touches neither the lattice nor the step count and ends no sampler.
  *   LBM_ERR_INVALID: a value that is not finite.  LBM_ERR_STATE, for a nonzero force: another semantics, a LBM_FLAG_SOLID_TILES context.
  *   (0, 0) restores the launches and the bits of a context without a force.  lbm_describe appends ` driving_force=1` while it is nonzero.
@@ -710,7 +711,8 @@ int lbm_get_driving_force(lbm_ctx* c, double* fx_out, double* fy_out);
 /* No reference counterpart.  An advected, diffusing scalar C carried by the flow of a LBM_SEM_BOUNCE_BACK_SOLID context (a lone lattice,
  * one step per launch, batch = 1): a second set of nine populations g_k on the flow's own D2Q9 stencil, weights and (x, y) conventions, in
  * two ping-pong lattices of the flow's layout that hold post-collision populations and are pulled from, as the flow's are.  The scalar has
- * no link plane: it reads the flow's.  It never acts on the flow: the flow's bits with a scalar are those without.
+ * no link plane: it reads the flow's.  It never acts on the flow unless lbm_set_buoyancy: the flow's bits with a
+ * scalar are those without.
  *
  * One scalar step of a cell that is neither solid nor held, every operation in the lattice type, none fused, in the order written:
  *   gather   g_k = g*_k(x - cx_k, y + cy_k).  A source outside the lattice: g_k = g*_opp(k) of the cell itself (the box edges and the lid
@@ -736,7 +738,7 @@ int lbm_get_driving_force(lbm_ctx* c, double* fx_out, double* fy_out);
  *   and its wrap, on the compute stream.
  * Limits.  Wall velocities, body motions and shapes do not enter the scalar's wall rule, which stays half-way (the velocity it is
  *   advected by is the one every export sees).  The scheme is not positivity-preserving.  A held outlet holds a value; there is no
- *   convective or zero-gradient outlet.  No buoyancy: nothing feeds back on the flow.
+ *   convective or zero-gradient outlet.  Nothing feeds back on the flow but lbm_set_buoyancy (below).
  *
  * lbm_scalar_begin: arrays [X][Y] in the host layout of lbm_set_solid's mask.  c0: the initial values (read on cells that are not
  *   solid); the lattice starts from the plain populations w_k C0, weight and C0 rounded to the lattice type.  dirichlet (NULL: none):
@@ -779,6 +781,39 @@ int lbm_scalar_get_stored(lbm_ctx* c, void* g_out, int host_dtype);
 int lbm_scalar_set_state(lbm_ctx* c, const void* g_host, int host_dtype);
 int lbm_scalar_totals(lbm_ctx* c, lbm_scalar_record* out);
 int lbm_scalar_flux(lbm_ctx* c, lbm_scalar_flux_record* out);
+
+/* --- Boussinesq buoyancy: the scalar acts on the flow ------------------------------------------------ */
+/* No reference counterpart.  With buoyancy (ax, ay, c_ref) set, (ax, ay) is the acceleration per unit of C in the components of u (hot
+ * fluid that rises toward the lid row y = 0 is ay > 0).  On the host, in double without contraction, B_k = (3 w_k) (cx_k ax + cy_k ay) for
+ * k = 1 .. 8 -- the arithmetic of the driving force's F_k; each B_k and c_ref are rounded once to the lattice type.  Every collision of a
+ * cell that is neither solid nor held is followed by
+ *     t = Cp - c_ref;   d_k = F_k + B_k t;   f*_k = f*_k + d_k     (k = 1 .. 8)
+ * every operation in the lattice type, none fused (arith = fast too); F_k are the constants of lbm_set_driving_force, zeros without one.
+ * The one add to f*_k sits where the driving force's sits: in the raw first step too, before the delta of a moving wall, before the solid
+ * and the hold cells are pinned.  The density does not enter (rho0 = 1).
+ * Cp is the buoyancy plane, one value per cell in the lattice type, owned by the scalar: the C that the most recent scalar step summed;
+ * after lbm_set_buoyancy, lbm_scalar_begin and lbm_scalar_set_state, C of the state as it is -- at every moment what lbm_scalar_get's
+ * conc_out returns.  Inside lbm_step the order stays flow step, wrap, scalar step, wrap: flow step n + 1 reads the C that scalar step n
+ * summed, scalar step n the velocity of the lattice flow step n wrote.  The coupling is sequential and explicit.
+ * With buoyancy set the flow's bits are no longer those of a context without a scalar.
+ * Limits.  The first-order forcing of the driving force: the equilibrium uses the bare velocity, the physical velocity is
+ *   (sum c f + a (C - c_ref) / 2) / rho, the scalar is advected by the bare moment and every export and sampler reports the bare moment.
+ *   No shaped lattice, no LBM_FLAG_SOLID_TILES, no slab, no batch.  One flow launch and one scalar launch per step.
+ * lbm_set_buoyancy: needs an active scalar (else LBM_ERR_STATE with a reason); allocates and fills the plane; touches neither lattice nor
+ *   the step counts and ends no sampler; may be called again at any time with other values.  (ax, ay) = (0, 0) frees the plane and restores
+ *   the launches, the bits and the lbm_describe text of a context without it.  LBM_ERR_INVALID: a value that is not finite.  LBM_ERR_STATE
+ *   with a reason: a shape is set; a LBM_FLAG_SOLID_TILES context.  While it is set lbm_set_solid_shape is refused with a reason, and
+ *   lbm_describe appends ` buoyancy=1`.  Everything that ends the scalar ends the buoyancy first: lbm_scalar_end, lbm_set_solid,
+ *   lbm_set_open_cells, lbm_set_periodic.  Motions, wall velocities, bodies, the driving force and a lbm_scalar_begin that replaces the
+ *   scalar keep it.
+ * lbm_get_buoyancy: returns 1 while it is set, else 0 (the values are then zeros); any pointer may be NULL.
+ * lbm_set_buoyancy_plane: conc[X][Y] (the host layout, as lbm_scalar_get's conc_out) replaces the plane, each value rounded once to the
+ *   lattice type.  What a restart needs on top of the two states: after lbm_set_state and lbm_scalar_set_state the plane holds C of the
+ *   scalar state as set, while the run that wrote the states would next read the C of one scalar step earlier -- lbm_scalar_get's conc_out
+ *   at that moment; with it uploaded here the run continues bit for bit.  LBM_ERR_STATE without buoyancy. */
+int lbm_set_buoyancy(lbm_ctx* c, double ax, double ay, double c_ref);
+int lbm_set_buoyancy_plane(lbm_ctx* c, const void* conc_host, int host_dtype);
+int lbm_get_buoyancy(lbm_ctx* c, double* ax_out, double* ay_out, double* c_ref_out);
 
 /* --- slab decomposition, externally driven exchange ---------------------------------- */
 /* No reference counterpart (the reference is single-GPU, MRT_GPU.py:29).  A step of a slab

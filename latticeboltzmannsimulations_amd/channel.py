@@ -75,14 +75,15 @@ def solver_re(Re_D, D, umax, mean, ny):
 
 
 def run_channel(nx, ny, Re_D, umax=0.05, disc=None, curved=False, profile="parabolic", walls="rest", steps=20000, force_every=100, RT="MRT",
-                dtype=np.float32, arith="strict", device=0, solver_factory=None, quiet=False, scalar=None):
+                dtype=np.float32, arith="strict", device=0, solver_factory=None, quiet=False, scalar=None, buoyancy=None):
     """Step a channel and keep the force series of the (first) obstacle on the device.  Returns dict(Cd, Cl, fx, fy, steps, Re, nu,
     series): Cd = 2 Fx / (rho mean^2 D), Cl likewise from Fy, of the last sample (rho = 1); D = 2 r of the disc (without one: the
     channel's width and the force on the side walls).  Re_D = mean D / nu is converted to the solver's Re (solver_re).
     scalar=dict(D=..., disc_value=1.0, inlet_value=0.0, magic=0.25): a passive scalar (CavitySolver.begin_scalar) that starts at
     inlet_value, with the inlet column's solid cells Dirichlet at inlet_value, the obstacles Dirichlet at disc_value, the side walls
     adiabatic and the held outlet holding inlet_value; the result gains Nu, the Nusselt number of the (first) disc on its diameter
-    (scalar.nusselt), its flux `scalar_flux` and the scalar diffusivity."""
+    (scalar.nusselt), its flux `scalar_flux` and the scalar diffusivity.  buoyancy=(ax, ay, c_ref): the scalar acts on the flow
+    (CavitySolver.set_buoyancy; needs scalar=...)."""
     g = channel(nx, ny, umax, profile, walls, disc, curved)
     D = 2.0 * g["discs"][0][2] if g["discs"] else float(g["H"])
     body = 2 if g["discs"] else 0
@@ -107,6 +108,8 @@ def run_channel(nx, ny, Re_D, umax=0.05, disc=None, curved=False, profile="parab
             wv[g["labels"] == 1] = float(sc["inlet_value"])
             wv[g["labels"] >= 2] = float(sc["disc_value"])
             s.begin_scalar(sc["D"], float(sc["inlet_value"]), sc["magic"], wall_value=wv, hold_value=float(sc["inlet_value"]))
+        if buoyancy is not None:
+            s.set_buoyancy(*buoyancy)
         every = max(1, int(force_every))
         s.step(1)
         s.begin_force(every=every, capacity=max(1, int(steps) // every + 1))
@@ -144,13 +147,15 @@ def main(argv=None):
     ap.add_argument("--scalar-D", dest="scalar_D", type=float, default=None, help="carry a passive scalar with this diffusivity; prints the disc's Nusselt number")
     ap.add_argument("--disc-value", dest="disc_value", type=float, default=1.0)
     ap.add_argument("--inlet-value", dest="inlet_value", type=float, default=0.0)
+    ap.add_argument("--buoyancy", type=float, nargs=3, metavar=("AX", "AY", "CREF"), default=None, help="let the scalar act on the flow (needs --scalar-D)")
     a = ap.parse_args(argv)
     if a.curved and a.disc is None:
         ap.error("--curved gives the disc its exact wall distances: it needs --disc")
     if a.scalar_D is not None and a.disc is None:
         ap.error("--scalar-D reports the disc's Nusselt number: it needs --disc")
     run_channel(a.xsize, a.ysize, a.Re_D, a.umax, a.disc, a.curved, a.profile, a.walls, a.steps, a.force_every, a.RT, np.dtype(a.dtype).type,
-                device=a.device, scalar=None if a.scalar_D is None else dict(D=a.scalar_D, disc_value=a.disc_value, inlet_value=a.inlet_value))
+                device=a.device, scalar=None if a.scalar_D is None else dict(D=a.scalar_D, disc_value=a.disc_value, inlet_value=a.inlet_value),
+                buoyancy=a.buoyancy)
     return 0
 
 

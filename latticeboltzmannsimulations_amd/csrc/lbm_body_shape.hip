@@ -43,6 +43,9 @@ int lbm_set_solid_shape(lbm_ctx* c, const double* q) {
     if (c->obs.moves())
         return fail(c, LBM_ERR_STATE, "lbm_set_solid_shape: a body motion or a wall velocity is set (the shape is set or cleared while every surface "
                                       "is at rest: the shape first, then lbm_set_body_motion and lbm_set_wall_velocity)");
+    if (q && c->scalar.buoyant)
+        return fail(c, LBM_ERR_STATE, "lbm_set_solid_shape: buoyancy is set (the shaped kernels add no buoyancy; clear it with lbm_set_buoyancy(c, 0, 0, 0) "
+                                      "first)");
     const Geo& g = c->plan.geo;
     Obstacles next;
     if (q) {

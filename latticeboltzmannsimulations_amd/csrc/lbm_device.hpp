@@ -571,6 +571,39 @@ struct Drive {
     int on;
 };
 
+// Buoyancy (lbm_set_buoyancy): the scalar acts on the flow.  cp: the buoyancy plane, one plane of the lattice's rows (buoy_at) that holds
+// the C the most recent scalar step summed; b[k - 1] = B_k = (3 w_k)(cx_k ax + cy_k ay) in double (drive_terms) and c_ref, each rounded once
+// to the lattice type on the host.  Every collision of a cell that is neither solid nor held is followed by
+//     t = cp - c_ref;  d_k = F_k + B_k t;  fpost_k = fpost_k + d_k      (every operation in the lattice type, none fused)
+// where the driving force is added alone without it.  A mode of its own of the wall rule, WALL_REST_BUOY / WALL_MOVE_BUOY = the mode |
+// WALL_BUOY (no shape), so the kernels of a context without buoyancy are the instantiations they were, names and arguments included.
+constexpr int WALL_BUOY = 4, WALL_REST_BUOY = WALL_REST | WALL_BUOY, WALL_MOVE_BUOY = WALL_MOVE | WALL_BUOY;
+constexpr int wall_base(int wall) { return wall & 3; }
+constexpr bool wall_buoyant(int wall) { return (wall & WALL_BUOY) != 0; }
+// The plane has an addressing of its own, buoy_at: rows of geo.pitch elements with the lattice's ghost margins, whatever the lattice's
+// layout is (in the rows layout Geo::at strides over all planes of a row and Geo::plane is one row).  buoy_at(x0, y) of a vector's first cell
+// is 16-byte aligned where Geo::at(x0, y) is: pitch and Geo::row are multiples of 4.  buoy_elems: the elements of the allocation.
+__host__ __device__ __forceinline__ long long buoy_at(const Geo& g, int x, int y) { return (long long)(y + GHY) * g.pitch + GH + x; }
+__host__ __device__ __forceinline__ long long buoy_elems(const Geo& g) { return (long long)(g.ny + 2 * GHY) * g.pitch; }
+template <typename R>
+struct Buoy {
+    const R* cp;
+    R b[8];
+    R c_ref;
+};
+template <typename R>
+struct WallArg<R, WALL_REST_BUOY> {
+    static constexpr int MODE = WALL_REST_BUOY;
+    Buoy<R> by;
+};
+template <typename R>
+struct WallArg<R, WALL_MOVE_BUOY> {
+    static constexpr int MODE = WALL_MOVE_BUOY;
+    const int32_t* cell_row;
+    const R* delta;
+    Buoy<R> by;
+};
+
 // Gather the post-stream, post-wall-rule populations of cell (x, y) from a lattice that
 // holds post-collision values (+ kept slots + parked wall densities); raw != 0: the lattice
 // holds plain populations (state just set by the host), nothing to stream.  PROM: the wall rules' equilibrium in the promoted form.

@@ -21,7 +21,8 @@
 //   lbm_body_motion.hip the wall velocity of moving bodies and of single solid cells: its tables (C ABI: set_body_motion, get_body_motion,
 //                                                                                          set_wall_velocity, get_wall_velocity)
 //   lbm_body_shape.hip  curved obstacle surfaces, a wall distance per link: its tables         (C ABI: set_solid_shape, get_solid_shape)
-//   lbm_scalar.hip  the passive scalar of an obstacle lattice: its lattices, tables and step (kernels: lbm_scalar.hpp)   (C ABI: scalar_*)
+//   lbm_scalar.hip  the passive scalar of an obstacle lattice: its lattices, tables and step (kernels: lbm_scalar.hpp); the buoyancy
+//                                                                                          (C ABI: scalar_*, set_buoyancy, get_buoyancy, set_buoyancy_plane)
 // one header of device code that the step units never see:
 //   lbm_fields.hpp  the exported state ("what lbm_get_fields would return"): the view Fields that every reader kernel takes -- built
 //                   on the host by fields_of below alone -- and the kernels of the field export, lbm_mean_u and the statistics
@@ -54,7 +55,7 @@
 #include "lbm_devmem.hpp"
 #include "lbm_bodies.hpp"
 #include "lbm_periodic.hpp"
-#include "lbm_solid.hpp"  // k_step_solid, k_step_generic_wall, extern (compiled per wall mode in lbm_solid{,_move,_shape}_f32/f64.hip)
+#include "lbm_solid.hpp"  // k_step_solid, k_step_generic_wall, extern (compiled per wall mode in lbm_solid{,_move,_shape,_buoy}_f32/f64.hip)
 #include "lbm_fields.hpp" // the view of the exported state and the kernels of the field export
 #include "lbm_inst.hpp"   // the kernels, and extern template declarations of the multi-step ones (compiled in lbm_{tiles,stream*}_f32/f64.hip)
 
@@ -248,6 +249,12 @@ struct ScalarState {
     const int32_t* hold_cell = nullptr;
     const void* hold_val = nullptr;
     int nhold = 0;
+    // Buoyancy (lbm_set_buoyancy), part of the scalar's state so that whatever ends the scalar ends it first: buoy = (ax, ay, c_ref) and cp,
+    // the buoyancy plane -- one plane of the flow's rows and type (buoy_at, lbm_device.hpp) that holds the C the most recent scalar step summed (after
+    // lbm_set_buoyancy, lbm_scalar_begin and lbm_scalar_set_state: C of the state as it is, scalar_fill_plane).  Empty while none is set.
+    bool buoyant = false;
+    double buoy[3] = {0.0, 0.0, 0.0};
+    DevBuf cp;
 };
 
 // Run state.  What was decided once is in `plan`; p stays for the fields later code branches on (dtype, collision, semantics, turb,
@@ -383,6 +390,19 @@ Drive<R> drive_of(const lbm_ctx* c) {
     return d;
 }
 
+// Buoyancy as the one-step obstacle kernels take it: B_k in double (the arithmetic of drive_terms on (ax, ay)) and c_ref, each rounded
+// once to the lattice type, and the plane.
+template <typename R>
+Buoy<R> buoy_of(const lbm_ctx* c) {
+    Buoy<R> b{};
+    double f[8];
+    drive_terms(c->scalar.buoy[0], c->scalar.buoy[1], f);
+    for (int k = 0; k < 8; ++k) b.b[k] = (R)f[k];
+    b.c_ref = (R)c->scalar.buoy[2];
+    b.cp = c->scalar.cp.as<const R>();
+    return b;
+}
+
 template <typename R>
 Batch<R> batch_of(const lbm_ctx* c) {
     return Batch<R>{c->plan.bstride, c->plan.batch > 1 ? c->relax_dev.as<const Relax<R>>() : nullptr};
@@ -492,6 +512,16 @@ void with_wall(const lbm_ctx* c, F&& launch) {
     if (sh.base) launch(WallArg<R, WALL_SHAPE>{sh.template table<R>()}, sh.link_q);
     else if (m.base) launch(WallArg<R, WALL_MOVE>{m.cell_row, (const R*)m.delta}, m.link_delta);
     else launch(WallArg<R, WALL_REST>{}, (const double*)nullptr);
+}
+// ... and for the step kernels alone (launch_rows): with buoyancy (lbm_set_buoyancy: no shape) the buoyant twin of the mode, which reads
+// the buoyancy plane; the force kernels keep with_wall -- what they read of the lattice does not change.
+template <typename VT, typename F>
+void with_wall_step(const lbm_ctx* c, F&& launch) {
+    using R = typename VT::R;
+    if (!c->scalar.buoyant) return with_wall<VT>(c, launch);
+    const MotionTables& m = c->obs.moving;
+    if (m.base) launch(WallArg<R, WALL_MOVE_BUOY>{m.cell_row, (const R*)m.delta, buoy_of<R>(c)}, m.link_delta);
+    else launch(WallArg<R, WALL_REST_BUOY>{buoy_of<R>(c)}, (const double*)nullptr);
 }
 // A launcher's body: f(Variant) enqueues the kernels of the context's variant, then the launch error check
 template <typename F>

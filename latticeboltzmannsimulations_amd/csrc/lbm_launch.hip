@@ -45,7 +45,7 @@ int launch_rows(lbm_ctx* c, int from, int to, int row0, int stride, int nrows, h
         if constexpr (VT::SEM == SEM_SOLID) {
             // the wall mode's kernel on either route (with_wall); at rest the one-cell route is k_step_generic below, as without a mask
             bool launched = true;
-            with_wall<VT>(c, [&](auto wa, const double*) {
+            with_wall_step<VT>(c, [&](auto wa, const double*) {   // (with buoyancy: the mode's buoyant twin)
                 constexpr int WALL = decltype(wa)::MODE;
                 if (c->plan.use_vec)   // (nx a multiple of the vector width, kernel = AUTO: plan_kernel)
                     by_nt([&](auto nt) {

@@ -549,6 +549,10 @@ int lbm_describe(const lbm_ctx* c, char* buf, size_t len) {
         const int m = std::snprintf(buf + n, len - (size_t)n, " scalar=%.17g,%.17g", c->scalar.D, c->scalar.magic);
         if (m > 0) n = std::min<int>(n + m, (int)len - 1);
     }
+    if (c->scalar.buoyant) {   // (lbm_set_buoyancy: the flow steps run the buoyant twins of their kernels)
+        const int m = std::snprintf(buf + n, len - (size_t)n, " buoyancy=1");
+        if (m > 0) n = std::min<int>(n + m, (int)len - 1);
+    }
     return n;
 }
 

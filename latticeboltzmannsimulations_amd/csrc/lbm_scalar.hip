@@ -1,5 +1,6 @@
 // lbm_scalar.hip -- liblbm_hip.so: the passive scalar of an obstacle lattice (lbm_scalar_begin, lbm_scalar_end, lbm_scalar_active,
-// lbm_scalar_get, lbm_scalar_get_stored, lbm_scalar_set_state, lbm_scalar_totals, lbm_scalar_flux of the C ABI declared in include/lbm.h;
+// lbm_scalar_get, lbm_scalar_get_stored, lbm_scalar_set_state, lbm_scalar_totals, lbm_scalar_flux, and the buoyancy through which it acts on
+// the flow, lbm_set_buoyancy, lbm_get_buoyancy, lbm_set_buoyancy_plane, of the C ABI declared in include/lbm.h;
 // LBM_SEM_BOUNCE_BACK_SOLID, a lone lattice, one step per launch).  The rule, the kernels and the host tables are lbm_scalar.hpp's; here:
 // the state (ScalarState, lbm_host.hpp), the step that run_unit enqueues behind every flow step, the uploads and the exports.  gfx950
 // only.  DESIGN.md 2.10.
@@ -35,6 +36,24 @@ int scalar_step(lbm_ctx* c) {
             R* dst = sc.lat[b].as<R>();
             with_fields<VT>(c, c->cur, [&](auto f) {
                 constexpr bool SHAPED = decltype(f)::SHAPED;
+                if constexpr (!SHAPED) {
+                    if (sc.buoyant) {   // (buoyancy, never with a shape: the same step, and the C it sums into the buoyancy plane)
+                        R* cp = sc.cp.as<R>();
+                        if (c->plan.use_vec) {
+                            const int nxb = (g.nx / V + BLK - 1) / BLK, nblocks = nxb * g.ny;
+                            if (c->plan.use_nt)
+                                hipLaunchKernelGGL((k_scalar_step_cp<R, true>), dim3(nblocks), dim3(BLK), 0, c->s_compute, src, dst, f, scalar_arg<R>(c), sc.raw[a],
+                                                   nxb, nblocks, cp);
+                            else
+                                hipLaunchKernelGGL((k_scalar_step_cp<R, false>), dim3(nblocks), dim3(BLK), 0, c->s_compute, src, dst, f, scalar_arg<R>(c), sc.raw[a],
+                                                   nxb, nblocks, cp);
+                        } else {
+                            hipLaunchKernelGGL((k_scalar_generic_cp<R>), dim3((g.nx + BLK - 1) / BLK, g.ny), dim3(BLK), 0, c->s_compute, src, dst, f,
+                                               scalar_arg<R>(c), sc.raw[a], cp);
+                        }
+                        return;
+                    }
+                }
                 if (c->plan.use_vec) {
                     const int nxb = (g.nx / V + BLK - 1) / BLK, nblocks = nxb * g.ny;
                     if (c->plan.use_nt)
@@ -58,7 +77,18 @@ int scalar_step(lbm_ctx* c) {
     return LBM_OK;
 }
 
-// The scalar ends: its lattices and tables are freed.  The caller has synchronised the streams.
+// The buoyancy plane from the scalar lattice `which` as it is (k_scalar_plane): C as lbm_scalar_get's conc_out forms it; on s_compute.
+static int scalar_fill_plane(lbm_ctx* c, int which) {
+    ScalarState& sc = c->scalar;
+    const Geo& g = c->plan.geo;
+    return launch_variant(c, [&](auto v) {
+        using R = typename decltype(v)::R;
+        hipLaunchKernelGGL((k_scalar_plane<R>), dim3((g.nx + BLK - 1) / BLK, g.ny), dim3(BLK), 0, c->s_compute, sc.lat[which].as<const R>(), c->lat[0].as<const R>(),
+                           g, scalar_arg<R>(c), sc.raw[which], sc.cp.as<R>());
+    });
+}
+
+// The scalar ends (and with it the buoyancy): its lattices and tables are freed.  The caller has synchronised the streams.
 void scalar_free(lbm_ctx* c) { c->scalar = ScalarState{}; }
 
 // Plain populations g[9][nx][ny] of the lattice type in the staging buffer -> lat[0]; then the zeros of the solid cells and the constants
@@ -80,6 +110,10 @@ static int scalar_from_stage(lbm_ctx* c) {
     sc.cur = 0;
     sc.raw[0] = sc.raw[1] = 1;
     sc.steps = 0;
+    if (sc.buoyant) {   // (buoyancy: the plane holds C of the state just set)
+        rc = scalar_fill_plane(c, 0);
+        if (rc) return rc;
+    }
     HIP_TRY(c, hipStreamSynchronize(c->s_compute));
     return LBM_OK;
 }
@@ -189,6 +223,11 @@ int lbm_scalar_begin(lbm_ctx* c, double diffusivity, double magic, const double*
         }
     rc = host_to_stage(c, g0.data(), c->p.dtype, Q);
     if (rc) return rc;
+    if (c->scalar.buoyant) {   // (replacing a buoyant scalar: the buoyancy stays, its plane is filled from the new state below)
+        next.buoyant = true;
+        for (int i = 0; i < 3; ++i) next.buoy[i] = c->scalar.buoy[i];
+        next.cp = std::move(c->scalar.cp);
+    }
     c->scalar = std::move(next);
     c->scalar.active = true;
     rc = scalar_from_stage(c);
@@ -203,6 +242,75 @@ int lbm_scalar_end(lbm_ctx* c) {
     if (rc) return rc;
     scalar_free(c);
     return LBM_OK;
+}
+
+int lbm_set_buoyancy(lbm_ctx* c, double ax, double ay, double c_ref) {
+    if (!c) return LBM_ERR_INVALID;
+    if (!std::isfinite(ax) || !std::isfinite(ay) || !std::isfinite(c_ref))
+        return fail(c, LBM_ERR_INVALID, "lbm_set_buoyancy: the acceleration and the reference value must be finite");
+    if (c->plan.solid_tiles)   // (such a context cannot have a scalar either: the reason that helps comes first)
+        return fail(c, LBM_ERR_STATE, "lbm_set_buoyancy: the tile kernel adds no force (LBM_FLAG_SOLID_TILES takes none; create the context without the flag)");
+    if (!c->scalar.active) return fail(c, LBM_ERR_STATE, "lbm_set_buoyancy: no scalar is active (lbm_scalar_begin first: the buoyancy acts through its C)");
+    const bool on = ax != 0.0 || ay != 0.0;
+    if (on && c->obs.shaped.base)
+        return fail(c, LBM_ERR_STATE, "lbm_set_buoyancy: a shape is set (the shaped kernels add no buoyancy; clear the shape with "
+                                      "lbm_set_solid_shape(NULL) first)");
+    HIP_TRY(c, hipSetDevice(c->p.device));
+    int rc = sync_all(c);
+    if (rc) return rc;
+    ScalarState& sc = c->scalar;
+    if (!on) {   // the launches, the bits and the describe text of a context without it
+        sc.buoyant = false;
+        sc.buoy[0] = sc.buoy[1] = sc.buoy[2] = 0.0;
+        sc.cp = DevBuf{};
+        return LBM_OK;
+    }
+    if (!sc.cp) {
+        DevBuf plane;
+        const size_t bytes = (size_t)buoy_elems(c->plan.geo) * (size_t)c->plan.es;   // (rows of pitch elements: not Geo::plane, one row in the rows layout)
+        rc = alloc_ok(c, plane.alloc(bytes, "buoyancy plane"));
+        if (rc) return rc;
+        HIP_TRY(c, hipMemsetAsync(plane.get(), 0, bytes, c->s_compute));   // (ghost cells: never read)
+        sc.cp = std::move(plane);
+        rc = scalar_fill_plane(c, scalar_lagged(sc));
+        if (rc == LBM_OK && hipStreamSynchronize(c->s_compute) != hipSuccess) rc = fail(c, LBM_ERR_HIP, "lbm_set_buoyancy: filling the plane failed");
+        if (rc) {
+            sc.cp = DevBuf{};
+            return rc;
+        }
+    }
+    sc.buoyant = true;
+    sc.buoy[0] = ax;
+    sc.buoy[1] = ay;
+    sc.buoy[2] = c_ref;
+    return LBM_OK;
+}
+
+int lbm_set_buoyancy_plane(lbm_ctx* c, const void* conc_host, int host_dtype) {
+    if (!c || !conc_host || (host_dtype != LBM_F32 && host_dtype != LBM_F64)) return fail(c, LBM_ERR_INVALID, "lbm_set_buoyancy_plane: bad argument");
+    if (!c->scalar.buoyant) return fail(c, LBM_ERR_STATE, "lbm_set_buoyancy_plane: no buoyancy is set (lbm_set_buoyancy)");
+    int rc = scalar_ready(c, "lbm_set_buoyancy_plane");
+    if (rc == LBM_OK) rc = ensure_field_stage(c);
+    if (rc == LBM_OK) rc = host_to_stage(c, conc_host, host_dtype, 1);
+    if (rc) return rc;
+    const Geo& g = c->plan.geo;
+    rc = launch_variant(c, [&](auto v) {
+        using R = typename decltype(v)::R;
+        hipLaunchKernelGGL((k_scalar_plane_import<R>), dim3((g.nx + BLK - 1) / BLK, g.ny), dim3(BLK), 0, c->s_compute, c->stage.as<const R>(),
+                           c->scalar.cp.as<R>(), g);
+    });
+    if (rc) return rc;
+    HIP_TRY(c, hipStreamSynchronize(c->s_compute));
+    return LBM_OK;
+}
+
+int lbm_get_buoyancy(lbm_ctx* c, double* ax_out, double* ay_out, double* c_ref_out) {
+    if (!c) return LBM_ERR_INVALID;
+    const ScalarState& sc = c->scalar;
+    if (ax_out) *ax_out = sc.buoyant ? sc.buoy[0] : 0.0;
+    if (ay_out) *ay_out = sc.buoyant ? sc.buoy[1] : 0.0;
+    if (c_ref_out) *c_ref_out = sc.buoyant ? sc.buoy[2] : 0.0;
+    return sc.buoyant ? 1 : 0;
 }
 
 int lbm_scalar_active(const lbm_ctx* c, double* diffusivity_out, double* magic_out) {

@@ -6,7 +6,9 @@
 //                tests/test_scalar_cpu.py drives it from a program of its own); arrays in the host layout of the mask, [nx][ny], y fastest
 //   device part  (under __HIPCC__) scalar_gather and scalar_collide, the rule of one cell (scalar_cell), the one-cell kernel
 //                k_scalar_generic and the vector kernel k_scalar_step, which must equal it bit for bit; the export, the totals, the flux
-// One lattice, one step per launch.  No existing kernel knows of the scalar: a context without one launches what it always did.
+// One lattice, one step per launch.  No existing kernel knows of the scalar: a context without one launches what it always did.  With
+// buoyancy (lbm_set_buoyancy) the step also stores the C it sums into the buoyancy plane the next flow step reads: k_scalar_generic_cp,
+// k_scalar_step_cp; k_scalar_plane fills the plane from a lattice as it is.
 #pragma once
 #include <cmath>
 #include <cstddef>
@@ -157,9 +159,11 @@ __device__ __forceinline__ void scalar_collide(const T (&g)[Q], T ux, T uy, R wp
 // One scalar step of cell (x, y): the definition.  f: the view of the flow lattice the flow step has just written, whose link plane and
 // whose velocity (Fields::macro: what lbm_get_fields exports after the next step, in the lattice type) the scalar takes.  A solid cell and
 // a hold cell are never written: both scalar lattices hold their constants (zeros; the held values), and the wrap refreshes an image.
-template <typename R, bool SHAPE>
+// CP (buoyancy, lbm_set_buoyancy): the C the collision summed goes into the buoyancy plane cp as well (buoy_at, lbm_device.hpp); a
+// solid cell and a hold cell keep what the fill wrote there (k_scalar_plane).
+template <typename R, bool SHAPE, bool CP = false>
 __device__ __forceinline__ void scalar_cell(const R* __restrict__ src, R* __restrict__ dst, const Fields<R, SEM_SOLID, false, SHAPE>& f,
-                                            const ScalarArg<R>& a, int raw, int x, int y) {
+                                            const ScalarArg<R>& a, int raw, int x, int y, R* __restrict__ cp = nullptr) {
     const Geo& geo = f.geo;
     const long long me = geo.at(x, y);
     const int lw = (int)f.src[K_LINK * geo.plane + me];
@@ -170,6 +174,7 @@ __device__ __forceinline__ void scalar_cell(const R* __restrict__ src, R* __rest
     scalar_collide<R, R>(g, ux, uy, a.w_plus, a.w_minus, out, C);
 #pragma unroll
     for (int k = 0; k < Q; ++k) dst[k * geo.plane + me] = out[k];
+    if constexpr (CP) cp[buoy_at(geo, x, y)] = C;
 }
 
 // One thread per cell: kernel = GENERIC, and lattices whose nx is no multiple of the vector width.
@@ -179,6 +184,14 @@ __global__ __launch_bounds__(BLK) void k_scalar_generic(const R* __restrict__ sr
     const int x = blockIdx.x * BLK + threadIdx.x, y = blockIdx.y;
     if (x >= f.geo.nx) return;
     scalar_cell<R, SHAPE>(src, dst, f, a, raw, x, y);
+}
+// ... and with buoyancy (no shape): the same step, C into the buoyancy plane too
+template <typename R>
+__global__ __launch_bounds__(BLK) void k_scalar_generic_cp(const R* __restrict__ src, R* __restrict__ dst, Fields<R, SEM_SOLID, false, false> f, ScalarArg<R> a,
+                                                           int raw, R* __restrict__ cp) {
+    const int x = blockIdx.x * BLK + threadIdx.x, y = blockIdx.y;
+    if (x >= f.geo.nx) return;
+    scalar_cell<R, false, true>(src, dst, f, a, raw, x, y, cp);
 }
 
 // 16 B per access, the shape of k_step_solid: a thread owns V consecutive cells of a row and reads their V link words first.  Where they
@@ -266,6 +279,108 @@ __global__ __launch_bounds__(BLK) void k_scalar_step(const R* __restrict__ src, 
 #pragma unroll
     for (int k = 0; k < Q; ++k) vstore<R, V, NT>(dst + k * geo.plane + me, outv[k]);
 }
+// ... and with buoyancy (lbm_set_buoyancy; no shape): the same step with one more 16-byte store.  A kernel text of its own: the passive
+// kernel above keeps the text it had, so its code is what it was (a body shared through a __forceinline__ function changed its register
+// allocation, as lbm_solid.hpp found for the flow's).  tests/test_buoyancy_gpu.py holds the two to the same bits through the reference.
+template <typename R, bool NT>
+__global__ __launch_bounds__(BLK) void k_scalar_step_cp(const R* __restrict__ src, R* __restrict__ dst, Fields<R, SEM_SOLID, false, false> f, ScalarArg<R> a,
+                                                        int raw, int nxb, int nblocks, R* __restrict__ cp) {
+    constexpr int V = 16 / (int)sizeof(R);
+    typedef typename VecT<R, V>::type T;
+    const Geo& geo = f.geo;
+    const int b = xcd_band(blockIdx.x, nblocks);
+    const int y = b / nxb;
+    const int x0 = ((b % nxb) * BLK + threadIdx.x) * V;
+    if (x0 >= geo.nx) return;
+    const long long me = geo.at(x0, y);
+    const T lk = vload<R, V, false>(f.src + K_LINK * geo.plane + me, true);
+    int lw[V], any = 0;
+#pragma unroll
+    for (int c = 0; c < V; ++c) {
+        lw[c] = (int)lk[c];
+        any |= lw[c];
+    }
+    T in[Q], outv[Q];
+#pragma unroll
+    for (int k = 0; k < Q; ++k) {
+        const int cx = raw ? 0 : cxk(k), cy = raw ? 0 : cyk(k);
+        in[k] = vload<R, V, NT>(src + k * geo.plane + geo.at(x0 - cx, y + cy), cxk(k) == 0 || raw);
+    }
+    const bool special = any != 0 || x0 == 0 || x0 + V >= geo.nx || y == 0 || y == geo.ny - 1;
+    if (special && !raw) {
+        int row[V];
+#pragma unroll
+        for (int c = 0; c < V; ++c) row[c] = -1;
+        if (any & 255) {
+            const int32_t* const cr = a.cell_row + (long long)y * geo.nx + x0;
+#pragma unroll
+            for (int c = 0; c < V; ++c)
+                if ((lw[c] & 255) && !(lw[c] & (LINK_SOLID | LINK_HOLD))) row[c] = cr[c];
+        }
+#pragma unroll
+        for (int k = 1; k < Q; ++k) {
+            const T own = vload<R, V, NT>(src + opp(k) * geo.plane + me, true);
+            const int sy = y + cyk(k);
+            const bool out_y = sy < 0 || sy >= geo.ny;
+#pragma unroll
+            for (int c = 0; c < V; ++c) {
+                const int sx = x0 + c - cxk(k);
+                if (out_y || sx < 0 || sx >= geo.nx) {
+                    in[k][c] = own[c];
+                } else if ((lw[c] >> (k - 1)) & 1) {
+                    const bool dir = row[c] >= 0 && ((a.bits[row[c]] >> (k - 1)) & 1u);
+                    in[k][c] = dir ? a.val[(long long)row[c] * 8 + (k - 1)] - own[c] : own[c];
+                }
+            }
+        }
+    }
+    T ux, uy, C;
+#pragma unroll
+    for (int c = 0; c < V; ++c) {
+        R u, v, rho;
+        f.macro(x0 + c, y, u, v, rho);
+        ux[c] = u;
+        uy[c] = v;
+    }
+    scalar_collide<T, R>(in, ux, uy, a.w_plus, a.w_minus, outv, C);
+    if (any & LINK_SOLID) {
+#pragma unroll
+        for (int c = 0; c < V; ++c)
+            if (lw[c] & LINK_SOLID) {
+#pragma unroll
+                for (int k = 0; k < Q; ++k) outv[k][c] = (R)0;
+            }
+    }
+    if (any & LINK_HOLD) {
+#pragma unroll
+        for (int k = 0; k < Q; ++k) {
+            const T own = vload<R, V, NT>(src + k * geo.plane + me, true);
+#pragma unroll
+            for (int c = 0; c < V; ++c)
+                if (lw[c] & LINK_HOLD) outv[k][c] = own[c];
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < Q; ++k) vstore<R, V, NT>(dst + k * geo.plane + me, outv[k]);
+    // the C of the collision into the buoyancy plane, zeros on solid lanes (a hold lane stores the sum of what it pulled: a number no
+    // flow step uses); the next flow step reads it, so no non-temporal store
+#pragma unroll
+    for (int c = 0; c < V; ++c)
+        if (lw[c] & LINK_SOLID) C[c] = (R)0;
+    vstore<R, V, false>(cp + buoy_at(geo, x0, y), C);
+}
+
+// The buoyancy plane of a scalar lattice as it is: C as k_scalar_export forms it (the sum of the arriving populations; zeros on solid cells),
+// addressed by buoy_at.  After lbm_set_buoyancy, lbm_scalar_begin and lbm_scalar_set_state; every scalar step then keeps it.
+template <typename R>
+__global__ __launch_bounds__(BLK) void k_scalar_plane(const R* __restrict__ s, const R* __restrict__ links, Geo geo, ScalarArg<R> a, int raw, R* __restrict__ cp) {
+    const int x = blockIdx.x * BLK + threadIdx.x, y = blockIdx.y;
+    if (x >= geo.nx) return;
+    const int lw = (int)links[K_LINK * geo.plane + geo.at(x, y)];
+    R g[Q];
+    scalar_gather<R>(s, geo, lw, raw, x, y, a, g);
+    cp[buoy_at(geo, x, y)] = ((((((((g[0] + g[1]) + g[2]) + g[3]) + g[4]) + g[5]) + g[6]) + g[7]) + g[8]);
+}
 
 // Solid cells hold zeros in both scalar lattices: written after every upload, from the link plane of the flow lattice `links`.
 template <typename R>
@@ -279,6 +394,14 @@ __global__ __launch_bounds__(BLK) void k_scalar_fix(R* __restrict__ a, R* __rest
         a[k * geo.plane + me] = (R)0;
         b[k * geo.plane + me] = (R)0;
     }
+}
+
+// staging [nx][ny] (host layout, the lattice type) -> the buoyancy plane (lbm_set_buoyancy_plane: a checkpoint's)
+template <typename R>
+__global__ __launch_bounds__(BLK) void k_scalar_plane_import(const R* __restrict__ stage, R* __restrict__ cp, Geo geo) {
+    const int x = blockIdx.x * BLK + threadIdx.x, y = blockIdx.y;
+    if (x >= geo.nx) return;
+    cp[buoy_at(geo, x, y)] = stage[(long long)x * geo.ny + y];
 }
 
 // The user's hold cells hold their nine values (scalar_hold_values, rounded once) in both scalar lattices: cell[i] = (x, y), val[i][9].

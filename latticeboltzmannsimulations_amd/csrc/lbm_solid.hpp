@@ -3,7 +3,8 @@
 // WALL_SHAPE: WallArg, lbm_device.hpp).  The rule itself is gather_a<.., SEM_SOLID> and update_cell_a of lbm_device.hpp, which
 // k_step_generic<.., SEM_SOLID> (at rest) and k_step_generic_wall (a motion or a shape) run cell by cell; the vector kernel must equal
 // them bit for bit.  Instantiated per mode and real type in lbm_solid{,_move,_shape}_f32/f64.hip (LBM_INST_SOLID below), six units that
-// compile in parallel; lbm_solid.hip holds the host side, the kernel that gives solid cells their constants and the force reduction.
+// compile in parallel, and the buoyant twins of the modes at rest and with a motion (WALL_REST_BUOY, WALL_MOVE_BUOY: lbm_set_buoyancy) in
+// lbm_solid_buoy_f32/f64.hip; lbm_solid.hip holds the host side, the kernel that gives solid cells their constants and the force reduction.
 // The mode blocks sit under `if constexpr` of the kernel template itself, so every mode's kernel is the text it would have alone (a
 // shared __forceinline__ body with a bool switch was tried first and changed the register allocation of the kernel at rest: DESIGN.md 2.10).
 #pragma once
@@ -26,6 +27,10 @@
 //               every lane adds F_k to its post-collision population of direction k, one add in the lattice type, before the delta of
 //               WALL_MOVE and before the solid and the hold lanes are pinned; a uniform run-time test, no template parameter (DESIGN.md
 //               2.10).  The vector kernel never reads dr.on, which the one-cell route tests.
+//   buoyancy    (WALL_REST_BUOY, WALL_MOVE_BUOY: the mode | WALL_BUOY; Buoy, lbm_device.hpp) one more aligned 16-byte load, the cells' values
+//               of the buoyancy plane, next to the link words; in the place of the driving force every lane adds d_k = F_k + B_k (Cp - c_ref)
+//               to its post-collision population of direction k: t per lane, d_k per lane and slot, one add, all in the lattice type.  A
+//               compile-time mode, so the kernels without it are the instantiations they were.
 constexpr int SOLID_DRIVE = 2;
 template <typename R, int COLL, bool NT, int WALL>
 __global__ __launch_bounds__(BLK) void k_step_solid(const R* __restrict__ src, R* __restrict__ dst, Geo geo, Relax<R> w, Batch<R> bt, int raw_drive,
@@ -42,6 +47,8 @@ __global__ __launch_bounds__(BLK) void k_step_solid(const R* __restrict__ src, R
     if (x0 >= geo.nx) return;
     const long long me = geo.at(x0, y);
     const T lk = vload<R, V, NT>(src + K_LINK * geo.plane + me, true);
+    T cpv;   // (buoyancy: the cells' values of the buoyancy plane)
+    if constexpr (wall_buoyant(WALL)) cpv = vload<R, V, NT>(wa.by.cp + buoy_at(geo, x0, y), true);
     int lw[V], any = 0;
 #pragma unroll
     for (int c = 0; c < V; ++c) {
@@ -57,7 +64,7 @@ __global__ __launch_bounds__(BLK) void k_step_solid(const R* __restrict__ src, R
     const bool lid = gy == 0;
     const bool special = any != 0 || x0 == 0 || x0 + V >= geo.nx || lid || gy == geo.NY - 1;
     if (special && !raw) {
-        if constexpr (WALL == WALL_SHAPE) {
+        if constexpr (wall_base(WALL) == WALL_SHAPE) {
             T st[Q];   // the cell's own stored slots
 #pragma unroll
             for (int k = 1; k < Q; ++k) st[k] = vload<R, V, NT>(src + k * geo.plane + me, true);
@@ -117,14 +124,26 @@ __global__ __launch_bounds__(BLK) void k_step_solid(const R* __restrict__ src, R
     collide_vec<R, COLL, V, false>(in, w, outv, hq, hr);
     // the driving force (lbm_set_driving_force), a uniform run-time test: every lane adds F_k, one add in the lattice type; the solid and
     // the hold lanes are pinned below, so the sums of fluid lanes alone are stored
-    if (raw_drive & SOLID_DRIVE) {
+    if constexpr (wall_buoyant(WALL)) {
+        // buoyancy (lbm_set_buoyancy; Buoy, lbm_device.hpp): t = Cp - c_ref per lane, d_k = F_k + B_k t per lane and slot, one add of d_k;
+        // F_k are zeros without a driving force, so bit SOLID_DRIVE is not read
+#pragma unroll
+        for (int c = 0; c < V; ++c) {
+            const R t = cpv[c] - wa.by.c_ref;
+#pragma unroll
+            for (int k = 1; k < Q; ++k) {
+                const R d = dr.f[k - 1] + wa.by.b[k - 1] * t;
+                outv[k][c] = outv[k][c] + d;
+            }
+        }
+    } else if (raw_drive & SOLID_DRIVE) {
 #pragma unroll
         for (int k = 1; k < Q; ++k) {
 #pragma unroll
             for (int c = 0; c < V; ++c) outv[k][c] = outv[k][c] + dr.f[k - 1];
         }
     }
-    if constexpr (WALL == WALL_MOVE) {
+    if constexpr (wall_base(WALL) == WALL_MOVE) {
         if (any & 255) {
             const int32_t* cell_row = wa.cell_row;
             const R* const delta = wa.delta;
@@ -176,7 +195,8 @@ __global__ __launch_bounds__(BLK) void k_step_solid(const R* __restrict__ src, R
 
 // One thread per cell (kernel = GENERIC, and lattices whose nx is no multiple of the vector width) while a motion, a shape or a driving
 // force is set: k_step_generic<.., SEM_SOLID> with the mode and the force of update_cell_a.  At rest and without a force k_step_generic
-// itself is what launches.
+// itself is what launches.  The buoyant modes read Cp of the cell and pass update_cell_a, in the base mode, a Drive of the cell's own:
+// d_k = F_k + B_k (Cp - c_ref) with on = 1 -- which is why the rule is spelled f* + (F + B t).
 template <typename R, int COLL, int WALL>
 __global__ __launch_bounds__(BLK) void k_step_generic_wall(const R* __restrict__ src, R* __restrict__ dst, Geo geo, Relax<R> w, Batch<R> bt, int raw,
                                                            int row0, int row_stride, WallArg<R, WALL> wa, Drive<R> dr) {
@@ -184,8 +204,24 @@ __global__ __launch_bounds__(BLK) void k_step_generic_wall(const R* __restrict__
     const int y = row0 + blockIdx.y * row_stride;
     if (x >= geo.nx) return;
     LBM_BATCH_SELECT(blockIdx.z)
-    wall_batch(wa, blockIdx.z, geo);
-    update_cell_a<R, COLL, SEM_SOLID, false, Geo, Geo, WALL>(src, geo, dst, geo, geo, w, raw, x, y, nullptr, wa, dr);
+    if constexpr (wall_buoyant(WALL)) {
+        // buoyancy (a lone lattice): the cell's own force d_k = F_k + B_k (Cp - c_ref) as the driving force of update_cell_a, in the base mode
+        constexpr int BASE = wall_base(WALL);
+        WallArg<R, BASE> wb{};
+        if constexpr (BASE == WALL_MOVE) {
+            wb.cell_row = wa.cell_row;
+            wb.delta = wa.delta;
+        }
+        const R t = wa.by.cp[buoy_at(geo, x, y)] - wa.by.c_ref;
+        Drive<R> d;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) d.f[k] = dr.f[k] + wa.by.b[k] * t;
+        d.on = 1;
+        update_cell_a<R, COLL, SEM_SOLID, false, Geo, Geo, BASE>(src, geo, dst, geo, geo, w, raw, x, y, nullptr, wb, d);
+    } else {
+        wall_batch(wa, blockIdx.z, geo);
+        update_cell_a<R, COLL, SEM_SOLID, false, Geo, Geo, WALL>(src, geo, dst, geo, geo, w, raw, x, y, nullptr, wa, dr);
+    }
 }
 
 // LBM_INST_SOLID(R, WALL): the six operator variants of one real type and mode -- the vector kernel with and without non-temporal
@@ -196,6 +232,10 @@ __global__ __launch_bounds__(BLK) void k_step_generic_wall(const R* __restrict__
     LBM_SX template __global__ void k_step_generic_wall<R, COLL, WALL_MOVE>(const R* __restrict__, R* __restrict__, Geo, Relax<R>, Batch<R>, int, int, int, WallArg<R, WALL_MOVE>, Drive<R>);
 #define LBM_SOLID_GENERIC_WALL_SHAPE(R, COLL) \
     LBM_SX template __global__ void k_step_generic_wall<R, COLL, WALL_SHAPE>(const R* __restrict__, R* __restrict__, Geo, Relax<R>, Batch<R>, int, int, int, WallArg<R, WALL_SHAPE>, Drive<R>);
+#define LBM_SOLID_GENERIC_WALL_REST_BUOY(R, COLL) \
+    LBM_SX template __global__ void k_step_generic_wall<R, COLL, WALL_REST_BUOY>(const R* __restrict__, R* __restrict__, Geo, Relax<R>, Batch<R>, int, int, int, WallArg<R, WALL_REST_BUOY>, Drive<R>);
+#define LBM_SOLID_GENERIC_WALL_MOVE_BUOY(R, COLL) \
+    LBM_SX template __global__ void k_step_generic_wall<R, COLL, WALL_MOVE_BUOY>(const R* __restrict__, R* __restrict__, Geo, Relax<R>, Batch<R>, int, int, int, WallArg<R, WALL_MOVE_BUOY>, Drive<R>);
 #define LBM_SOLID_ONE(R, COLL, WALL)                                                                                                                          \
     LBM_SX template __global__ void k_step_solid<R, COLL, false, WALL>(const R* __restrict__, R* __restrict__, Geo, Relax<R>, Batch<R>, int, int, int, int, int, \
                                                                        WallArg<R, WALL>, Drive<R>);                                                           \
@@ -213,4 +253,6 @@ LBM_SOLID_INST
 LBM_INST_SOLID(float, WALL_REST) LBM_INST_SOLID(double, WALL_REST)
 LBM_INST_SOLID(float, WALL_MOVE) LBM_INST_SOLID(double, WALL_MOVE)
 LBM_INST_SOLID(float, WALL_SHAPE) LBM_INST_SOLID(double, WALL_SHAPE)
+LBM_INST_SOLID(float, WALL_REST_BUOY) LBM_INST_SOLID(double, WALL_REST_BUOY)
+LBM_INST_SOLID(float, WALL_MOVE_BUOY) LBM_INST_SOLID(double, WALL_MOVE_BUOY)
 #endif

@@ -831,13 +831,37 @@ class CavitySolver:
         self._check(self.lib.lbm_scalar_flux(self._h, rec), "lbm_scalar_flux")
         return dict(step=np.array([int(r.step) for r in rec]), links=np.array([int(r.links) for r in rec]), flux=np.array([r.flux for r in rec]))
 
+    # -- Boussinesq buoyancy: the scalar acts on the flow (lbm_set_buoyancy, lbm_get_buoyancy) ------------------------------------
+    def set_buoyancy(self, ax, ay, c_ref=0.0):
+        """Let the scalar act on the flow (lbm_set_buoyancy): (ax, ay) is the acceleration per unit of C, components as u -- hot fluid
+        rising toward the lid row y = 0 is ay > 0.  Every collision of a cell that is neither solid nor held adds
+        F_k + B_k (C - c_ref), B_k = (3 w_k) (cx_k ax + cy_k ay), to its post-collision population of direction k; C is what scalar()
+        returns at that moment.  Needs an active scalar; no shape.  The lattices, the step counts and the samplers stay.  The exported u is
+        the bare moment: the physical velocity is convection.velocity(u, rho, C, (ax, ay), c_ref).  (0, 0): no buoyancy."""
+        self._check(self.lib.lbm_set_buoyancy(self._h, float(ax), float(ay), float(c_ref)), "lbm_set_buoyancy")
+        return self
+
+    @property
+    def buoyancy(self):
+        """None, or (ax, ay, c_ref) as set."""
+        if self._h is None:
+            return None
+        ax, ay, cr = ctypes.c_double(0.0), ctypes.c_double(0.0), ctypes.c_double(0.0)
+        rc = self.lib.lbm_get_buoyancy(self._h, ctypes.byref(ax), ctypes.byref(ay), ctypes.byref(cr))
+        if rc < 0:
+            self._check(rc, "lbm_get_buoyancy")
+        return (ax.value, ay.value, cr.value) if rc else None
+
     def _scalar_entry(self):
         """What a checkpoint says of the scalar: nothing without one (the file of such a run is what it was), else its parameters, the
-        arrays begin_scalar took and the arriving populations."""
+        arrays begin_scalar took and the arriving populations; with buoyancy its three numbers and the plane (scalar(): the C the next
+        flow step reads)."""
         act = self.scalar_active if self.has_solid and not self._lead else None
         if act is None:
             return {}
-        return dict(scalar_D=act["D"], scalar_magic=act["magic"], scalar_g=self.scalar_populations(), **(getattr(self, "_scalar_given", None) or {}))
+        by = self.buoyancy
+        return dict(scalar_D=act["D"], scalar_magic=act["magic"], scalar_g=self.scalar_populations(), **(getattr(self, "_scalar_given", None) or {}),
+                    **({} if by is None else dict(buoyancy=np.array(by), buoyancy_plane=self.scalar())))
 
     # -- checkpoint / restart (the reference has neither; SURVEY 8f item 4) -------------------
     def save_checkpoint(self, path):
@@ -955,6 +979,12 @@ class CavitySolver:
                                   np.asarray(z["scalar_wall_value"]) if "scalar_wall_value" in z else None,
                                   np.asarray(z["scalar_hold_value"]) if "scalar_hold_value" in z else None)
                 self.set_scalar_state(np.ascontiguousarray(z["scalar_g"]))
+                if "buoyancy" in z:      # (after the state: the plane is the C the checkpointed run would have read next)
+                    self.set_buoyancy(*np.asarray(z["buoyancy"]))
+                    plane = np.ascontiguousarray(z["buoyancy_plane"])
+                    self._check(self.lib.lbm_set_buoyancy_plane(self._h, plane.ctypes.data, _DT[plane.dtype]), "lbm_set_buoyancy_plane")
+                elif self.buoyancy is not None:
+                    self.set_buoyancy(0.0, 0.0)
             return int(z["steps_done"])
 
     # -- slab exchange primitives ---------------------------------------------------------
