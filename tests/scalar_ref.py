@@ -64,14 +64,18 @@ def partner(i, n, periodic):
 
 class ScalarOracle:
     def __init__(self, mask, D, c0=0.0, dtype=np.float32, magic=0.25, wall_value=None, hold=None, hold_f=None, hold_value=None,
-                 periodic=(False, False)):
+                 periodic=(False, False), param_dtype=None):
+        """param_dtype (as CavityOracle's; default: dtype, or float64 when dtype is long double) is the lattice type the device runs
+        in: the rates, the Dirichlet table, the held constants and the initial c0 are rounded once to it, then widened exactly."""
         self.R = np.dtype(dtype).type
         R = self.R
+        P = np.dtype(param_dtype if param_dtype is not None else (np.float64 if np.dtype(dtype) == np.longdouble else dtype)).type
+        self.par = lambda v: R(P(v))      # a parameter as the device holds it, in the arithmetic type
         self.mask = np.asarray(mask) != 0
         X, Y = self.X, self.Y = self.mask.shape
         self.per = (bool(periodic[0]), bool(periodic[1]))
         wp, wm = rates(D, magic)
-        self.wp, self.wm = R(wp), R(wm)
+        self.wp, self.wm = self.par(wp), self.par(wm)
         xs, ys = np.meshgrid(np.arange(X), np.arange(Y), indexing="ij")
         self.img = (self.per[0] & ((xs == 0) | (xs == X - 1))) | (self.per[1] & ((ys == 0) | (ys == Y - 1)))
         self.uhold = np.zeros((X, Y), bool) if hold is None else (np.asarray(hold) != 0)
@@ -95,13 +99,13 @@ class ScalarOracle:
             self.outside[k] = out & free
             self.link[k] = ~out & self.mask[sxc, syc] & free
             self.dlink[k] = self.link[k] & self.dirichlet[sxc, syc]
-            self.t[k] = ((2.0 * WEIGHT[k]) * np.where(self.dlink[k], wv[sxc, syc], 0.0)).astype(R)
+            self.t[k] = ((2.0 * WEIGHT[k]) * np.where(self.dlink[k], wv[sxc, syc], 0.0)).astype(P).astype(R)
         # the constants of the user's hold cells, rounded once
         self.held = np.zeros((9, X, Y), dtype=R)
         hv = c0 if hold_value is None else np.broadcast_to(np.asarray(hold_value, dtype=np.float64), (X, Y))
         for x, y in zip(*np.nonzero(self.uhold)):
-            self.held[:, x, y] = np.array(hold_values(np.asarray(hold_f, dtype=np.float64)[:, x, y], hv[x, y])).astype(R)
-        c0r = c0.astype(R)
+            self.held[:, x, y] = np.array(hold_values(np.asarray(hold_f, dtype=np.float64)[:, x, y], hv[x, y])).astype(P).astype(R)
+        c0r = c0.astype(P).astype(R)
         self.set_state(np.stack([R(WEIGHT[k]) * c0r for k in range(9)]))
 
     # -- what the lattice stores -----------------------------------------------------------------------------------------------------

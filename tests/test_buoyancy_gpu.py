@@ -227,7 +227,9 @@ def _cavity(n, dtype, arith="strict", kernel="auto", steps=2000):
 @pytest.mark.parametrize("dtype", [np.float32, np.float64], ids=["float32", "float64"])
 def test_fast_arithmetic(dtype):
     """heated_cavity(62), a 64 x 64 lattice, Ra = 1e4, MRT, 2000 steps: the two routes agree bit for bit under `fast`, and the distance of
-    the flow populations from the strict fp64 device run stays within FAST_HEADROOM x the recorded figure."""
+    the flow populations from the strict fp64 device run stays within FAST_HEADROOM x the recorded figure.  A long-run smoke check (MRT,
+    the default rates, against the device's own strict run): the bound on `fast` with buoyancy, for the three operators and both buoyant
+    modes against a long-double reference, is tests/test_arith_error_budget_rules_gpu.py."""
     f_ref, _, _ = _cavity(62, np.float64)
     a, ga, ka = _cavity(62, dtype, "fast")
     b, gb, kb = _cavity(62, dtype, "fast", "generic")

@@ -186,7 +186,9 @@ def test_clearing_gives_the_bits_of_a_context_that_never_set_them(dtype):
 @pytest.mark.parametrize("dtype", [np.float32, np.float64])
 def test_fast_arithmetic(dtype):
     """The configuration of test_solid_gpu.test_fast_arithmetic (128 x 96, Re 1000, 2000 steps) with the geometry of channel() and a
-    disc: the two routes agree bit for bit, and the distance from the strict fp64 run stays inside checks.FAST_BOUND."""
+    disc: the two routes agree bit for bit, and the distance from the strict fp64 run stays inside checks.FAST_BOUND.  A long-run smoke
+    check (MRT, the default rates, against the device's own strict run): the bound on `fast` with hold cells and a wall velocity, for the
+    three operators against a long-double reference, is tests/test_arith_error_budget_rules_gpu.py."""
     nx, ny = 128, 96
     g = channel.channel(nx, ny, 0.08, disc=(40, 47.5, 9.0))
 

@@ -195,7 +195,9 @@ def test_clearing_gives_the_bits_of_a_context_that_never_set_them(dtype):
 @pytest.mark.parametrize("dtype", [np.float32, np.float64])
 def test_fast_arithmetic(dtype):
     """Poiseuille flow past a disc, 128 x 96, Re 1000, 2000 steps: the two routes agree bit for bit, and the distance from the strict fp64
-    run stays inside checks.FAST_BOUND, the bounds of tests/test_open_flow_gpu.py."""
+    run stays inside checks.FAST_BOUND, the bounds of tests/test_open_flow_gpu.py.  A long-run smoke check (MRT, the default rates,
+    against the device's own strict run): the bound on `fast` with periodic sides and the driving force, for the three operators
+    against a long-double reference, is tests/test_arith_error_budget_rules_gpu.py."""
     nx, ny = 128, 96
     g = periodic.poiseuille(nx, ny)
     m, lab, _ = solid.discs_into(nx, ny, [(40, 47.5, 9.0)], g["solid"], np.where(g["solid"], 0, -1).astype(np.int32), 1)
