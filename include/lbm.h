@@ -815,6 +815,32 @@ int lbm_set_buoyancy(lbm_ctx* c, double ax, double ay, double c_ref);
 int lbm_set_buoyancy_plane(lbm_ctx* c, const void* conc_host, int host_dtype);
 int lbm_get_buoyancy(lbm_ctx* c, double* ax_out, double* ay_out, double* c_ref_out);
 
+/* --- sub-grid viscosity of an obstacle lattice ------------------------------------------------------- */
+/* No reference counterpart (the reference's closure, turb = 1, stays what it is and stays refused on these lattices).  The local
+ * Smagorinsky closure of Hou et al. (1996) on a LBM_SEM_BOUNCE_BACK_SOLID context at one step per launch; the mask may be empty, which is
+ * the plain bounce-back cavity.  After the gather a cell that is neither solid nor held has populations f_k and the moments rho, ux, uy
+ * that its collision takes; with S.. the plain sums of c c f_k in the order of k,
+ *     Pxx = Sxx - (rho / 3 + (rho ux) ux)   Pyy = Syy - (rho / 3 + (rho uy) uy)   Pxy = Sxy - (rho ux) uy
+ *     N   = sqrt((Pxx Pxx + 2 (Pxy Pxy)) + Pyy Pyy)
+ *     tau = 0.5 (tau0 + sqrt(tau0 tau0 + (k N) / rho)),   tau0 = 1 / omega of the lattice,   k = 18 sqrt(2) cs2
+ * every operation in the lattice type in the order written (k is formed in double and rounded once); arith = fast takes its reciprocal
+ * and square-root instructions for the two divisions and the two square roots.  1 / tau enters the collision of that step where the
+ * lattice's viscous rate would: SRT's omega, TRT's omega+, MRT's omega_nu.  The eddy viscosity is nu_t = cs2 |S|, |S| = sqrt(2 S:S).
+ * There is no history and no plane: the layout is untouched, the driving force and the wall terms are added after the collision as
+ * before.  Each lattice of a batch has its own tau0; all share cs2.
+ * Limits.  No wall damping (Van Driest).  A passive scalar keeps its molecular diffusivity; with buoyancy the closure is refused (an eddy
+ *   diffusivity would be needed).  No LBM_FLAG_SOLID_TILES, no slab.
+ * lbm_set_subgrid: may be called at any time; it touches neither the lattice nor the step count and ends no sampler.  cs2 = 0 clears it
+ *   and restores the launches, the bits and the lbm_describe text of a context without it; cs2 > 0 appends ` subgrid=<cs2>` to that
+ *   text.  LBM_ERR_INVALID: cs2 negative or not finite.  LBM_ERR_STATE with a reason, for cs2 > 0: another semantics, a
+ *   LBM_FLAG_SOLID_TILES context, buoyancy is set.  While cs2 > 0 lbm_set_buoyancy is refused with a reason.
+ * lbm_get_subgrid: cs2 as set, 0 without it.
+ * lbm_get_tau on such a context: the tau of the step that starts from the current state, gathered through the view of the exported
+ *   fields under the context's wall rule; a solid cell and a hold cell (lbm_set_open_cells, the image cells of lbm_set_periodic), which no
+ *   step updates, report tau0. */
+int lbm_set_subgrid(lbm_ctx* c, double cs2);
+int lbm_get_subgrid(lbm_ctx* c, double* cs2_out);
+
 /* --- slab decomposition, externally driven exchange ---------------------------------- */
 /* No reference counterpart (the reference is single-GPU, MRT_GPU.py:29).  A step of a slab
  * is split so that a host-language driver can move halos with any transport:

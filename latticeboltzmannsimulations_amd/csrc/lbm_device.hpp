@@ -404,6 +404,36 @@ __device__ __forceinline__ T smagorinsky_omega(const T (&f)[Q], T qeq_prev, T rh
     return div_<FAST>(T((R)1.0), smagorinsky_tau<T, FAST, PROM>(f, qeq_prev, rho_prev, omega));
 }
 
+// The local sub-grid closure of the obstacle lattices (lbm_set_subgrid; Hou et al. 1996; no reference counterpart: DESIGN.md 2.10).  From
+// the gathered populations of a cell and the moments the collision takes anyway, the whole non-equilibrium momentum flux -- all three
+// components, so the rule does not know the axes --
+//     Sxx = ((((f1 + f3) + f5) + f6) + f7) + f8      Syy = ((((f2 + f4) + f5) + f6) + f7) + f8      Sxy = ((f5 - f6) + f7) - f8
+//     Pxx = Sxx - (rho / 3 + (rho ux) ux)            Pyy = Syy - (rho / 3 + (rho uy) uy)            Pxy = Sxy - (rho ux) uy
+//     N   = sqrt((Pxx Pxx + 2 (Pxy Pxy)) + Pyy Pyy)
+//     tau = 0.5 (tau0 + sqrt(tau0 tau0 + (k N) / rho)),   tau0 = 1 / omega,   k = 18 sqrt(2) Cs2 (formed in double on the host, rounded once)
+// every operation in the lattice type, one rounding each, in the order written (rho / 3 is rho * (R)(1.0 / 3)); FAST: the two square roots
+// and the two divisions ((k N) / rho here, 1 / tau in subgrid_omega) by sqrt_<FAST> / div_<FAST>, as the closure above.  No history: the
+// step that computes tau uses it.  tests/subgrid_ref.py restates the order.
+template <typename T, bool FAST = false>
+__device__ __forceinline__ T subgrid_tau(const T (&f)[Q], T rho, T ux, T uy, typename ScalarOf<T>::type omega, typename ScalarOf<T>::type k) {
+    typedef typename ScalarOf<T>::type R;
+    const R tau0 = (R)1.0 / omega;
+    const T sxx = ((((f[1] + f[3]) + f[5]) + f[6]) + f[7]) + f[8];
+    const T syy = ((((f[2] + f[4]) + f[5]) + f[6]) + f[7]) + f[8];
+    const T sxy = ((f[5] - f[6]) + f[7]) - f[8];
+    const T r3 = rho * (R)(1.0 / 3), jx = rho * ux;
+    const T pxx = sxx - (r3 + jx * ux);
+    const T pyy = syy - (r3 + (rho * uy) * uy);
+    const T pxy = sxy - jx * uy;
+    const T n = sqrt_<FAST>((pxx * pxx + (R)2 * (pxy * pxy)) + pyy * pyy);
+    return (R)0.5 * (tau0 + sqrt_<FAST>(tau0 * tau0 + div_<FAST>(k * n, rho)));
+}
+template <typename T, bool FAST = false>
+__device__ __forceinline__ T subgrid_omega(const T (&f)[Q], T rho, T ux, T uy, typename ScalarOf<T>::type omega, typename ScalarOf<T>::type k) {
+    typedef typename ScalarOf<T>::type R;
+    return div_<FAST>(T((R)1.0), subgrid_tau<T, FAST>(f, rho, ux, uy, omega, k));
+}
+
 // a8: wall rules on the populations of ONE perimeter cell, given the equilibrium of the
 // previous macroscopic state of that cell.  SEM_PY: MRT.py:450-453 in statement order
 // (left equilibrium, right mirror pairing, bottom, lid); SEM_GPU: MRT_GPU.py:674-692
@@ -604,6 +634,32 @@ struct WallArg<R, WALL_MOVE_BUOY> {
     Buoy<R> by;
 };
 
+// The sub-grid closure (lbm_set_subgrid; subgrid_tau above) as one more bit of the mode, WALL_SGS, on each of the three base modes: the
+// mode's tables plus k = 18 sqrt(2) Cs2 in the lattice type.  Every cell that is neither solid nor held takes w_nu = 1 / tau of its own
+// gathered populations into the collision, in the place of the lattice's rate; nothing else of the step changes.  Compile-time, so the
+// kernels of a context without it are the instantiations they were, names and arguments included.  (No buoyant twin: lbm_set_subgrid and
+// lbm_set_buoyancy refuse each other.)
+constexpr int WALL_SGS = 8, WALL_REST_SGS = WALL_REST | WALL_SGS, WALL_MOVE_SGS = WALL_MOVE | WALL_SGS, WALL_SHAPE_SGS = WALL_SHAPE | WALL_SGS;
+constexpr bool wall_subgrid(int wall) { return (wall & WALL_SGS) != 0; }
+template <typename R>
+struct WallArg<R, WALL_REST_SGS> {
+    static constexpr int MODE = WALL_REST_SGS;
+    R sgs;
+};
+template <typename R>
+struct WallArg<R, WALL_MOVE_SGS> {
+    static constexpr int MODE = WALL_MOVE_SGS;
+    const int32_t* cell_row;
+    const R* delta;
+    R sgs;
+};
+template <typename R>
+struct WallArg<R, WALL_SHAPE_SGS> {
+    static constexpr int MODE = WALL_SHAPE_SGS;
+    ShapeTable<R> sh;
+    R sgs;
+};
+
 // Gather the post-stream, post-wall-rule populations of cell (x, y) from a lattice that
 // holds post-collision values (+ kept slots + parked wall densities); raw != 0: the lattice
 // holds plain populations (state just set by the host), nothing to stream.  PROM: the wall rules' equilibrium in the promoted form.
@@ -697,10 +753,12 @@ __device__ __forceinline__ void gather(const R* __restrict__ src, const Geo& geo
 // stores it, one add in the lattice type; no gather changes.  WALL_SHAPE: the gather applies shape_rule on the links, the stores are the
 // pure post-collision values.  dr: the driving force (k_step_generic_wall alone passes one), added after the collision and before the
 // delta of WALL_MOVE, in the raw first step too.
-template <typename R, int COLL, int SEM, bool TURB, typename AS, typename AD, int WALL = WALL_REST>
+// SGS (k_step_generic_wall in a mode with WALL_SGS alone; WALL is then the base mode), sgs: the sub-grid closure -- w_nu = subgrid_omega of
+// the gathered populations and the moments of the cell, k = sgs.
+template <typename R, int COLL, int SEM, bool TURB, typename AS, typename AD, int WALL = WALL_REST, bool SGS = false>
 __device__ __forceinline__ void update_cell_a(const R* __restrict__ src, const AS& as, R* __restrict__ dst, const AD& ad, const Geo& geo,
                                               const Relax<R>& w0, int raw, int x, int y, const R* __restrict__ lnk = nullptr,
-                                              WallArg<R, WALL> wa = WallArg<R, WALL>{}, Drive<R> dr = Drive<R>{}) {
+                                              WallArg<R, WALL> wa = WallArg<R, WALL>{}, Drive<R> dr = Drive<R>{}, R sgs = R(0)) {
     // lnk (SEM_SOLID with an LDS window as the source): plane K_LINK of the lattice, see link_word
     const int X = geo.nx, Y = geo.NY, gy = geo.y0 + y;
     if (SEM == SEM_SOLID && (link_word<R, AS>(src, as, geo, lnk, x, y) & (LINK_SOLID | LINK_HOLD))) return;   // a solid cell, or a hold cell, is never updated
@@ -722,6 +780,7 @@ __device__ __forceinline__ void update_cell_a(const R* __restrict__ src, const A
     R w_nu = w0.w_nu;
     if (TURB) w_nu = smagorinsky_omega<R, coll_is_fast(COLL), coll_is_prom(COLL)>(g, src[K_QEQ * as.plane + me_s], src[K_RHO * as.plane + me_s], w0.w_nu);
     macros<R, coll_is_fast(COLL), SEM>(g, x, gy, X, Y, w.uLB, rho, ux, uy);
+    if constexpr (SGS) w_nu = subgrid_omega<R, coll_is_fast(COLL)>(g, rho, ux, uy, w0.w_nu, sgs);
     equ_collide<R, COLL, TURB>(g, rho, ux, uy, w, w_nu, out, q2, COLL == C_MRT_FAST && gy == 0 && !sem_is_bb(SEM));
     if (TURB) {
         dst[K_QEQ * ad.plane + me] = q2;
@@ -857,11 +916,13 @@ __device__ __forceinline__ void update_vec(const R* __restrict__ src, R* __restr
 // hold garbage -- harmless.  Per-cell arithmetic is the same operation sequence as update_cell,
 // so the result is bit-identical to two single steps.
 // ------------------------------------------------------------------------------------------
-template <typename R, int COLL, int V, bool TURB>
+template <typename R, int COLL, int V, bool TURB, bool SGS = false>
 __device__ __forceinline__ void collide_vec(const typename VecT<R, V>::type (&in)[Q], const Relax<R>& w0,
                                             typename VecT<R, V>::type (&outv)[Q],
                                             typename VecT<R, V>::type& hq, typename VecT<R, V>::type& hr, bool wl = false, bool wr = false,
-                                            int kind = 0) {
+                                            int kind = 0, R sgs = R(0)) {
+    // SGS (k_step_solid in a mode with WALL_SGS alone, kind 0): the sub-grid closure, w_nu = subgrid_omega of the cell's populations and
+    // moments with k = sgs -- the MRT operators then form the velocity too
     // hq, hr: Smagorinsky history of the cells (in: previous step, out: this step); untouched unless TURB
     // The streaming kernel with the walls inside (lbm_stream.hpp) passes wall cells, their wall rules already applied to in[]:
     // wl / wr: the first / last cell is a side-wall cell (x = 0 / X - 1): u = 0 (MRT_GPU.py:396-399; as update_vec);
@@ -879,7 +940,7 @@ __device__ __forceinline__ void collide_vec(const typename VecT<R, V>::type (&in
             f32x2 rho = ((((((((g[0] + g[1]) + g[2]) + g[3]) + g[4]) + g[5]) + g[6]) + g[7]) + g[8]);
             if (kind == 1) rho = ((g[0] + g[1]) + g[3]) + 2.f * ((g[2] + g[5]) + g[6]);
             f32x2 ux = f32x2(0.f), uy = f32x2(0.f);
-            if (!coll_is_mrt(COLL) || TURB) {
+            if (!coll_is_mrt(COLL) || TURB || SGS) {
                 if (kind == 0) {
                     ux = div_<coll_is_fast(COLL)>((((((g[1] - g[3]) + g[5]) - g[6]) - g[7]) + g[8]), rho);
                     uy = div_<coll_is_fast(COLL)>((((((g[2] - g[4]) + g[5]) + g[6]) - g[7]) - g[8]), rho);
@@ -889,6 +950,7 @@ __device__ __forceinline__ void collide_vec(const typename VecT<R, V>::type (&in
                     ux = f32x2(kind == 1 ? w0.uLB : 0.f); uy = f32x2(0.f);
                 }
             }
+            if constexpr (SGS) w_nu = subgrid_omega<f32x2, coll_is_fast(COLL)>(g, rho, ux, uy, w0.w_nu, sgs);
             equ_collide<f32x2, COLL, TURB>(g, rho, ux, uy, w0, w_nu, out, q2, COLL == C_MRT_FAST && kind == 1);
 #pragma unroll
             for (int k = 0; k < Q; ++k) {
@@ -914,7 +976,7 @@ __device__ __forceinline__ void collide_vec(const typename VecT<R, V>::type (&in
             R rho = ((((((((g[0] + g[1]) + g[2]) + g[3]) + g[4]) + g[5]) + g[6]) + g[7]) + g[8]);
             if (kind == 1) rho = ((g[0] + g[1]) + g[3]) + (R)2. * ((g[2] + g[5]) + g[6]);
             R ux = (R)0, uy = (R)0;
-            if (!coll_is_mrt(COLL) || TURB) {
+            if (!coll_is_mrt(COLL) || TURB || SGS) {
                 if (kind == 0) {
                     ux = div_<coll_is_fast(COLL)>((((((g[1] - g[3]) + g[5]) - g[6]) - g[7]) + g[8]), rho);
                     uy = div_<coll_is_fast(COLL)>((((((g[2] - g[4]) + g[5]) + g[6]) - g[7]) - g[8]), rho);
@@ -923,6 +985,7 @@ __device__ __forceinline__ void collide_vec(const typename VecT<R, V>::type (&in
                     ux = kind == 1 ? w0.uLB : (R)0; uy = (R)0;
                 }
             }
+            if constexpr (SGS) w_nu = subgrid_omega<R, coll_is_fast(COLL)>(g, rho, ux, uy, w0.w_nu, sgs);
             equ_collide<R, COLL, TURB>(g, rho, ux, uy, w0, w_nu, out, q2, COLL == C_MRT_FAST && kind == 1);
 #pragma unroll
             for (int k = 0; k < Q; ++k) outv[k][c] = out[k];

@@ -141,6 +141,38 @@ __global__ __launch_bounds__(BLK) void k_export_tau(Fields<R, SEM_GPU, PROM> f, 
         if (x0 + xx < geo.nx && y0 + yy < geo.ny) stage[(long long)(x0 + xx) * geo.ny + y0 + yy] = t[xx][yy];
 }
 
+// ... of an obstacle lattice with the sub-grid closure (lbm_set_subgrid): the tau that the step from the view's lattice gives each cell --
+// subgrid_tau of the populations the view gathers under the context's wall rule and of their moments, the operations of the step
+// (FAST: its divisions and square roots); a solid cell and a hold cell, which no step updates, report tau0.  k: sgs_k.  stage = [nx][ny_local]
+template <typename R, bool FAST, bool SHAPE>
+__global__ __launch_bounds__(BLK) void k_export_tau_subgrid(Fields<R, SEM_SOLID, false, SHAPE> f, Relax<R> w, Batch<R> bt, R k, R* __restrict__ stage) {
+    const Geo& geo = f.geo;
+    constexpr int TRX = trx<R>(), RY = BLK / TRX;
+    __shared__ R t[TRX][33];
+    const long long n = (long long)geo.nx * geo.ny;
+    const auto lat = f.lattice(blockIdx.z);
+    if (bt.w) w = bt.w[blockIdx.z];
+    stage += blockIdx.z * n;
+    const int x0 = blockIdx.x * TRX, y0 = blockIdx.y * 32;
+    const int tx = threadIdx.x % TRX, x = x0 + tx;
+    for (int ty = threadIdx.x / TRX; ty < 32; ty += RY) {
+        const int y = y0 + ty;
+        if (x >= geo.nx || y >= geo.ny) continue;
+        R tau = (R)1.0 / w.w_nu;
+        if (!((int)lat.src[K_LINK * geo.plane + geo.at(x, y)] & (LINK_SOLID | LINK_HOLD))) {
+            R g[Q], rho, ux, uy;
+            lat.populations(x, y, g);
+            macros<R, FAST, SEM_SOLID>(g, x, geo.y0 + y, geo.nx, geo.NY, lat.uLB, rho, ux, uy);
+            tau = subgrid_tau<R, FAST>(g, rho, ux, uy, w.w_nu, k);
+        }
+        t[tx][ty] = tau;
+    }
+    __syncthreads();
+    const int yy = threadIdx.x & 31, xb = threadIdx.x >> 5;
+    for (int xx = xb; xx < TRX; xx += BLK / 32)
+        if (x0 + xx < geo.nx && y0 + yy < geo.ny) stage[(long long)(x0 + xx) * geo.ny + y0 + yy] = t[xx][yy];
+}
+
 // Sum over the slab of ux + uy of the view's macroscopic state (what k_export_macro would write), in double:
 // partial[blockIdx.z * gridDim.x + blockIdx.x] = the block's sum; k_reduce_final adds the partial sums of each lattice in
 // index order -- a fixed summation tree, so the result does not vary from run to run.

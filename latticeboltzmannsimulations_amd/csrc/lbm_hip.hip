@@ -134,6 +134,16 @@ int export_tau(lbm_ctx* c, int which) {
     return launch_variant(c, [&](auto v) {
         using VT = decltype(v);
         using R = typename VT::R;
+        if constexpr (VT::SEM == SEM_SOLID) {
+            // the sub-grid closure (lbm_set_subgrid): the tau of the step that starts from the current state, lat[cur], through the view
+            if (c->subgrid > 0.0) {
+                with_fields<VT>(c, c->cur, [&](auto f) {
+                    hipLaunchKernelGGL((k_export_tau_subgrid<R, coll_is_fast(VT::COLL), decltype(f)::SHAPED>), grid_tiles<R>(c), dim3(BLK), 0, c->s_compute, f,
+                                       relax_of<R>(c->p), batch_of<R>(c), sgs_k<R>(c), c->stage.as<R>());
+                });
+                return;
+            }
+        }
         hipLaunchKernelGGL((k_export_tau<R, coll_is_fast(VT::COLL), coll_is_prom(VT::COLL)>), grid_tiles<R>(c), dim3(BLK), 0, c->s_compute,
                            fields_of<Variant<R, VT::COLL, SEM_GPU, VT::TURB>>(c, which), relax_of<R>(c->p), batch_of<R>(c), c->p.turb, c->stage.as<R>());
     });

@@ -41,6 +41,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -55,7 +56,7 @@
 #include "lbm_devmem.hpp"
 #include "lbm_bodies.hpp"
 #include "lbm_periodic.hpp"
-#include "lbm_solid.hpp"  // k_step_solid, k_step_generic_wall, extern (compiled per wall mode in lbm_solid{,_move,_shape,_buoy}_f32/f64.hip)
+#include "lbm_solid.hpp"  // k_step_solid, k_step_generic_wall, extern (compiled per wall mode in lbm_solid{,_move,_shape,_buoy}_f32/f64.hip, lbm_solid_sgs*)
 #include "lbm_fields.hpp" // the view of the exported state and the kernels of the field export
 #include "lbm_inst.hpp"   // the kernels, and extern template declarations of the multi-step ones (compiled in lbm_{tiles,stream*}_f32/f64.hip)
 
@@ -303,6 +304,7 @@ struct lbm_ctx {
     ScalarState scalar;         // (above)
     double drive[2] = {0.0, 0.0};   // the driving force (lbm_set_driving_force): (fx, fy); no geometry, so it outlives every obstacle call
     bool driven() const { return drive[0] != 0.0 || drive[1] != 0.0; }
+    double subgrid = 0.0;           // the sub-grid constant Cs2 (lbm_set_subgrid), 0 without the closure; no geometry and no history either
     ncclComm_t comm = nullptr;
     int nranks = 1, rank = 0;
     bool loopback = false;      // diagnostic: 1-rank communicator, the slab exchanges halos with itself
@@ -403,6 +405,12 @@ Buoy<R> buoy_of(const lbm_ctx* c) {
     return b;
 }
 
+// The sub-grid constant as the kernels take it: k = 18 sqrt(2) Cs2 in double, rounded once to the lattice type (subgrid_tau, lbm_device.hpp).
+template <typename R>
+R sgs_k(const lbm_ctx* c) {
+    return (R)((18.0 * std::sqrt(2.0)) * c->subgrid);
+}
+
 template <typename R>
 Batch<R> batch_of(const lbm_ctx* c) {
     return Batch<R>{c->plan.bstride, c->plan.batch > 1 ? c->relax_dev.as<const Relax<R>>() : nullptr};
@@ -423,16 +431,18 @@ template <typename R>
 dim3 grid_tiles(const lbm_ctx* c) { return dim3((c->plan.geo.nx + trx<R>() - 1) / trx<R>(), (c->plan.geo.ny + 31) / 32, c->plan.batch); }
 
 // Run-time parameters -> compile-time kernel variant (real type, collision operator, semantics, Smagorinsky).
-template <typename R_, int COLL_, int SEM_, bool TURB_>
+// SGS: the sub-grid closure of an obstacle lattice (lbm_set_subgrid) -- asked for by the step launcher alone (launch_rows), which then
+// takes the wall mode's twin with WALL_SGS; every other launcher sees the variant without it.
+template <typename R_, int COLL_, int SEM_, bool TURB_, bool SGS_ = false>
 struct Variant {
     using R = R_;
     static constexpr int COLL = COLL_, SEM = SEM_;
-    static constexpr bool TURB = TURB_;
+    static constexpr bool TURB = TURB_, SGS = SGS_;
 };
 
 // arith = promoted: fp32 takes the promoted operators, fp64 the strict ones (the promotion's casts are no-ops there).
 template <typename F>
-void dispatch(const lbm_params& p, F&& f) {
+void dispatch(const lbm_params& p, F&& f, bool subgrid = false) {   // subgrid: the step of a context with a sub-grid constant (SEM_SOLID only)
     auto by_sem = [&](auto real, auto coll) {
         using R = decltype(real);
         constexpr int C = decltype(coll)::value;
@@ -443,7 +453,10 @@ void dispatch(const lbm_params& p, F&& f) {
         } else {
             if (p.semantics == LBM_SEM_MRT_PY) f(Variant<R, CS, SEM_PY, false>{});   // (arith = fast: MRT_GPU semantics only)
             else if (p.semantics == LBM_SEM_BOUNCE_BACK) f(Variant<R, C, SEM_BB, false>{});   // (strict and fast; no closure: validate_params)
-            else if (p.semantics == LBM_SEM_BOUNCE_BACK_SOLID) f(Variant<R, C, SEM_SOLID, false>{});   // (the same, one step per launch)
+            else if (p.semantics == LBM_SEM_BOUNCE_BACK_SOLID) {   // (the same, one step per launch)
+                if (subgrid) f(Variant<R, C, SEM_SOLID, false, true>{});
+                else f(Variant<R, C, SEM_SOLID, false>{});
+            }
             else if (p.turb) f(Variant<R, C, SEM_GPU, true>{});
             else f(Variant<R, C, SEM_GPU, false>{});
         }
@@ -515,9 +528,19 @@ void with_wall(const lbm_ctx* c, F&& launch) {
 }
 // ... and for the step kernels alone (launch_rows): with buoyancy (lbm_set_buoyancy: no shape) the buoyant twin of the mode, which reads
 // the buoyancy plane; the force kernels keep with_wall -- what they read of the lattice does not change.
+// With the sub-grid closure (VT::SGS, chosen by dispatch) the mode's twin with WALL_SGS, which carries k = 18 sqrt(2) Cs2 (sgs_k).
 template <typename VT, typename F>
 void with_wall_step(const lbm_ctx* c, F&& launch) {
     using R = typename VT::R;
+    if constexpr (VT::SGS) {
+        const ShapeTables& sh = c->obs.shaped;
+        const MotionTables& mv = c->obs.moving;
+        const R k = sgs_k<R>(c);
+        if (sh.base) launch(WallArg<R, WALL_SHAPE_SGS>{sh.template table<R>(), k}, sh.link_q);
+        else if (mv.base) launch(WallArg<R, WALL_MOVE_SGS>{mv.cell_row, (const R*)mv.delta, k}, mv.link_delta);
+        else launch(WallArg<R, WALL_REST_SGS>{k}, (const double*)nullptr);
+        return;
+    }
     if (!c->scalar.buoyant) return with_wall<VT>(c, launch);
     const MotionTables& m = c->obs.moving;
     if (m.base) launch(WallArg<R, WALL_MOVE_BUOY>{m.cell_row, (const R*)m.delta, buoy_of<R>(c)}, m.link_delta);
@@ -525,8 +548,8 @@ void with_wall_step(const lbm_ctx* c, F&& launch) {
 }
 // A launcher's body: f(Variant) enqueues the kernels of the context's variant, then the launch error check
 template <typename F>
-int launch_variant(lbm_ctx* c, F&& f) {
-    dispatch(c->p, f);
+int launch_variant(lbm_ctx* c, F&& f, bool subgrid = false) {
+    dispatch(c->p, f, subgrid);
     HIP_TRY(c, hipGetLastError());
     return LBM_OK;
 }

@@ -52,7 +52,7 @@ int launch_rows(lbm_ctx* c, int from, int to, int row0, int stride, int nrows, h
                         hipLaunchKernelGGL((k_step_solid<R, VT::COLL, decltype(nt)::value, WALL>), gvec, dim3(BLK), 0, s, src, dst, c->plan.geo,
                                            relax_of<R>(c->p), batch_of<R>(c), raw | (c->driven() ? SOLID_DRIVE : 0), row0, stride, nxb, nblocks, wa, drive_of<R>(c));
                     });
-                else if (WALL != WALL_REST || c->driven())   // (at rest the kernel with a mode launches for the driving force alone)
+                else if (WALL != WALL_REST || c->driven())   // (at rest the kernel with a mode launches for the driving force alone; the closure is a mode)
                     hipLaunchKernelGGL((k_step_generic_wall<R, VT::COLL, WALL>), grid_rows(c, nrows), dim3(BLK), 0, s, src, dst, c->plan.geo,
                                        relax_of<R>(c->p), batch_of<R>(c), raw, row0, stride, wa, drive_of<R>(c));
                 else launched = false;
@@ -67,7 +67,7 @@ int launch_rows(lbm_ctx* c, int from, int to, int row0, int stride, int nrows, h
         else
             hipLaunchKernelGGL((k_step_generic<R, VT::COLL, VT::SEM, VT::TURB>), grid_rows(c, nrows), dim3(BLK), 0, s, src, dst, c->plan.geo,
                                relax_of<R>(c->p), batch_of<R>(c), raw, row0, stride);
-    });
+    }, c->subgrid > 0.0);   // (lbm_set_subgrid: dispatch picks the variant with the closure)
 }
 
 // One single step on the frame of width W, lat[from] -> lat[to] (one pass of a multi-step; never a raw lattice).

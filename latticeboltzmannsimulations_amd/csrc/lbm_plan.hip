@@ -553,6 +553,10 @@ int lbm_describe(const lbm_ctx* c, char* buf, size_t len) {
         const int m = std::snprintf(buf + n, len - (size_t)n, " buoyancy=1");
         if (m > 0) n = std::min<int>(n + m, (int)len - 1);
     }
+    if (c->subgrid > 0.0) {   // (lbm_set_subgrid: the flow steps run the twins of their kernels with the closure)
+        const int m = std::snprintf(buf + n, len - (size_t)n, " subgrid=%.17g", c->subgrid);
+        if (m > 0) n = std::min<int>(n + m, (int)len - 1);
+    }
     return n;
 }
 

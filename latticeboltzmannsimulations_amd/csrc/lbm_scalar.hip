@@ -255,6 +255,9 @@ int lbm_set_buoyancy(lbm_ctx* c, double ax, double ay, double c_ref) {
     if (on && c->obs.shaped.base)
         return fail(c, LBM_ERR_STATE, "lbm_set_buoyancy: a shape is set (the shaped kernels add no buoyancy; clear the shape with "
                                       "lbm_set_solid_shape(NULL) first)");
+    if (on && c->subgrid > 0.0)
+        return fail(c, LBM_ERR_STATE, "lbm_set_buoyancy: a sub-grid constant is set (a buoyant flow with the closure needs an eddy diffusivity for the "
+                                      "scalar, which there is none; clear it with lbm_set_subgrid(c, 0) first)");
     HIP_TRY(c, hipSetDevice(c->p.device));
     int rc = sync_all(c);
     if (rc) return rc;

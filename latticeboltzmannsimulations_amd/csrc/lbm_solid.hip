@@ -440,6 +440,29 @@ int lbm_get_driving_force(lbm_ctx* c, double* fx_out, double* fy_out) {
     return LBM_OK;
 }
 
+int lbm_set_subgrid(lbm_ctx* c, double cs2) {
+    if (!c) return LBM_ERR_INVALID;
+    if (!std::isfinite(cs2) || cs2 < 0.0) return fail(c, LBM_ERR_INVALID, "lbm_set_subgrid: the constant is negative or not finite");
+    if (cs2 != 0.0) {
+        const int rc = need_solid(c, "lbm_set_subgrid");
+        if (rc) return rc;
+        if (c->plan.solid_tiles)
+            return fail(c, LBM_ERR_STATE, "lbm_set_subgrid: the tile kernel has no closure (LBM_FLAG_SOLID_TILES takes none; create the context "
+                                          "without the flag)");
+        if (c->scalar.buoyant)
+            return fail(c, LBM_ERR_STATE, "lbm_set_subgrid: buoyancy is set (a buoyant flow with the closure needs an eddy diffusivity for the scalar, "
+                                          "which there is none; clear it with lbm_set_buoyancy(c, 0, 0, 0) first)");
+    }
+    c->subgrid = cs2;   // (travels by value with every launch: the steps already enqueued keep theirs; no history, so the state stays)
+    return LBM_OK;
+}
+
+int lbm_get_subgrid(lbm_ctx* c, double* cs2_out) {
+    if (!c) return LBM_ERR_INVALID;
+    if (cs2_out) *cs2_out = c->subgrid;
+    return LBM_OK;
+}
+
 int lbm_get_open_cells(lbm_ctx* c, uint8_t* hold_out, double* f_out) {
     if (!c) return LBM_ERR_INVALID;
     const int rc = need_solid(c, "lbm_get_open_cells");

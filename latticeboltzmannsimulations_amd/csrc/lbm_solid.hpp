@@ -31,6 +31,10 @@
 //               of the buoyancy plane, next to the link words; in the place of the driving force every lane adds d_k = F_k + B_k (Cp - c_ref)
 //               to its post-collision population of direction k: t per lane, d_k per lane and slot, one add, all in the lattice type.  A
 //               compile-time mode, so the kernels without it are the instantiations they were.
+//   sub-grid    (WALL_REST_SGS, WALL_MOVE_SGS, WALL_SHAPE_SGS: the mode | WALL_SGS; lbm_set_subgrid, subgrid_tau of lbm_device.hpp) no load and no
+//               store more: collide_vec forms every lane's tau from the lane's gathered populations and its moments -- the MRT operators
+//               then form the velocity too -- and takes 1 / tau into the collision in the place of the lattice's rate.  Solid and hold lanes
+//               compute a tau that nobody uses and are pinned as ever.  Instantiated in lbm_solid_sgs{,_move,_shape}_f32/f64.hip.
 constexpr int SOLID_DRIVE = 2;
 template <typename R, int COLL, bool NT, int WALL>
 __global__ __launch_bounds__(BLK) void k_step_solid(const R* __restrict__ src, R* __restrict__ dst, Geo geo, Relax<R> w, Batch<R> bt, int raw_drive,
@@ -121,7 +125,8 @@ __global__ __launch_bounds__(BLK) void k_step_solid(const R* __restrict__ src, R
             }
         }
     }
-    collide_vec<R, COLL, V, false>(in, w, outv, hq, hr);
+    if constexpr (wall_subgrid(WALL)) collide_vec<R, COLL, V, false, true>(in, w, outv, hq, hr, false, false, 0, wa.sgs);
+    else collide_vec<R, COLL, V, false>(in, w, outv, hq, hr);
     // the driving force (lbm_set_driving_force), a uniform run-time test: every lane adds F_k, one add in the lattice type; the solid and
     // the hold lanes are pinned below, so the sums of fluid lanes alone are stored
     if constexpr (wall_buoyant(WALL)) {
@@ -218,6 +223,17 @@ __global__ __launch_bounds__(BLK) void k_step_generic_wall(const R* __restrict__
         for (int k = 0; k < 8; ++k) d.f[k] = dr.f[k] + wa.by.b[k] * t;
         d.on = 1;
         update_cell_a<R, COLL, SEM_SOLID, false, Geo, Geo, BASE>(src, geo, dst, geo, geo, w, raw, x, y, nullptr, wb, d);
+    } else if constexpr (wall_subgrid(WALL)) {
+        // the sub-grid closure: update_cell_a in the base mode with the closure switched on
+        constexpr int BASE = wall_base(WALL);
+        WallArg<R, BASE> wb{};
+        if constexpr (BASE == WALL_MOVE) {
+            wb.cell_row = wa.cell_row;
+            wb.delta = wa.delta;
+        }
+        if constexpr (BASE == WALL_SHAPE) wb.sh = wa.sh;
+        wall_batch(wb, blockIdx.z, geo);
+        update_cell_a<R, COLL, SEM_SOLID, false, Geo, Geo, BASE, true>(src, geo, dst, geo, geo, w, raw, x, y, nullptr, wb, dr, wa.sgs);
     } else {
         wall_batch(wa, blockIdx.z, geo);
         update_cell_a<R, COLL, SEM_SOLID, false, Geo, Geo, WALL>(src, geo, dst, geo, geo, w, raw, x, y, nullptr, wa, dr);
@@ -236,6 +252,12 @@ __global__ __launch_bounds__(BLK) void k_step_generic_wall(const R* __restrict__
     LBM_SX template __global__ void k_step_generic_wall<R, COLL, WALL_REST_BUOY>(const R* __restrict__, R* __restrict__, Geo, Relax<R>, Batch<R>, int, int, int, WallArg<R, WALL_REST_BUOY>, Drive<R>);
 #define LBM_SOLID_GENERIC_WALL_MOVE_BUOY(R, COLL) \
     LBM_SX template __global__ void k_step_generic_wall<R, COLL, WALL_MOVE_BUOY>(const R* __restrict__, R* __restrict__, Geo, Relax<R>, Batch<R>, int, int, int, WallArg<R, WALL_MOVE_BUOY>, Drive<R>);
+#define LBM_SOLID_GENERIC_WALL_REST_SGS(R, COLL) \
+    LBM_SX template __global__ void k_step_generic_wall<R, COLL, WALL_REST_SGS>(const R* __restrict__, R* __restrict__, Geo, Relax<R>, Batch<R>, int, int, int, WallArg<R, WALL_REST_SGS>, Drive<R>);
+#define LBM_SOLID_GENERIC_WALL_MOVE_SGS(R, COLL) \
+    LBM_SX template __global__ void k_step_generic_wall<R, COLL, WALL_MOVE_SGS>(const R* __restrict__, R* __restrict__, Geo, Relax<R>, Batch<R>, int, int, int, WallArg<R, WALL_MOVE_SGS>, Drive<R>);
+#define LBM_SOLID_GENERIC_WALL_SHAPE_SGS(R, COLL) \
+    LBM_SX template __global__ void k_step_generic_wall<R, COLL, WALL_SHAPE_SGS>(const R* __restrict__, R* __restrict__, Geo, Relax<R>, Batch<R>, int, int, int, WallArg<R, WALL_SHAPE_SGS>, Drive<R>);
 #define LBM_SOLID_ONE(R, COLL, WALL)                                                                                                                          \
     LBM_SX template __global__ void k_step_solid<R, COLL, false, WALL>(const R* __restrict__, R* __restrict__, Geo, Relax<R>, Batch<R>, int, int, int, int, int, \
                                                                        WallArg<R, WALL>, Drive<R>);                                                           \
@@ -255,4 +277,7 @@ LBM_INST_SOLID(float, WALL_MOVE) LBM_INST_SOLID(double, WALL_MOVE)
 LBM_INST_SOLID(float, WALL_SHAPE) LBM_INST_SOLID(double, WALL_SHAPE)
 LBM_INST_SOLID(float, WALL_REST_BUOY) LBM_INST_SOLID(double, WALL_REST_BUOY)
 LBM_INST_SOLID(float, WALL_MOVE_BUOY) LBM_INST_SOLID(double, WALL_MOVE_BUOY)
+LBM_INST_SOLID(float, WALL_REST_SGS) LBM_INST_SOLID(double, WALL_REST_SGS)
+LBM_INST_SOLID(float, WALL_MOVE_SGS) LBM_INST_SOLID(double, WALL_MOVE_SGS)
+LBM_INST_SOLID(float, WALL_SHAPE_SGS) LBM_INST_SOLID(double, WALL_SHAPE_SGS)
 #endif

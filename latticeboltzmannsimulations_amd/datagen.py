@@ -24,11 +24,11 @@ import numpy as np
 from . import residual as RS
 from .solid import mask_from
 from .solver import CavityBatch
-from .stopping import MeanUStop, ResidualStop, by_residual, wall_model
+from .stopping import MeanUStop, ResidualStop, by_residual, subgrid_constant, wall_model
 
 
 def _solve_batch(idx, Re_range, xsize, ysize, RT, turb, uLB, maxIt, Pinterval, tolerance, device, dtype, say, out, arith, convergence="host",
-                 semantics="mrt_gpu", residual_tol=None, residual_final=None, batch_factory=None, solid=None, solid_tiles=False):
+                 semantics="mrt_gpu", residual_tol=None, residual_final=None, batch_factory=None, solid=None, solid_tiles=False, subgrid=None):
     """Runs the lattices Re_range[idx] in lock step; fills out = (f_final, u_final, its) rows idx.  The per-lattice logic is
     the reference's loop body (MRT_GPU_datagen.py:707-731,862-871): a check after iteration It = 0, Pinterval, 2 Pinterval, ...
     (i.e. after It + 1 steps), and a lattice stops where its stop rule says so (stopping.MeanUStop with `tolerance`).
@@ -40,10 +40,14 @@ def _solve_batch(idx, Re_range, xsize, ysize, RT, turb, uLB, maxIt, Pinterval, t
     sem = {} if semantics == "mrt_gpu" else {"semantics": semantics}
     if solid is not None:      # [n, X, Y]: every lattice of the batch its own mask
         sem["solid"] = np.ascontiguousarray(solid[idx])
+    elif subgrid is not None:  # (the closure lives on the obstacle lattices: an empty mask is the plain bounce-back cavity)
+        sem["solid"] = np.zeros((len(idx), xsize, ysize), dtype=bool)
     if solid_tiles:
         sem["tuning"] = dict(solid_tiles=True)
     make = CavityBatch if batch_factory is None else batch_factory
     with make(xsize, ysize, [float(Re_range[i]) for i in idx], RT=RT, uLB=uLB, dtype=dtype, turb=turb, device=device, arith=arith, **sem) as b:
+        if subgrid is not None:
+            b.set_subgrid(subgrid)
         feq_initial = b.get_fields(want_fin=True, out_dtype=np.float32)[2][0]      # fin = equ(1, InitVel) = feq_initial
         stops = [ResidualStop(uLB, residual_tol) if by_res else MeanUStop(uLB, tolerance) for _ in idx]
         open_ = set(range(len(idx)))
@@ -103,7 +107,7 @@ def _solve_batch(idx, Re_range, xsize, ysize, RT, turb, uLB, maxIt, Pinterval, t
 def generate(Re_range=None, xsize=32 * 12, ysize=32 * 12, RT="SRT", turb=1, uLB=0.08, maxIt=3000000, Pinterval=10000,
              tolerance=0.0000001, OutputFolder="./output", save=True, concurrent=64, devices=(0,), dtype=np.float32,
              quiet=False, arith="strict", convergence="host", BC="EB-NEBB ", criterion="mean_u", residual_tol=None, batch_factory=None,
-             solid=None, solid_tiles=False):
+             solid=None, solid_tiles=False, subgrid=None):
     """Returns (feq_initial, f_final, u_final, Re_range, iterations_per_Re); writes the four .npy files when `save`.
     criterion: 'mean_u' (default, the reference's rule) or 'residual' -- each lattice stops at the first check whose field residual (the
     relative L2 change of u per step since the previous check, reduced on the device) is below residual_tol, which must be given; the
@@ -115,10 +119,14 @@ def generate(Re_range=None, xsize=32 * 12, ysize=32 * 12, RT="SRT", turb=1, uLB=
     [n, X, Y], one per Reynolds number; saved as solid.npy [n, X, Y] beside u_final.npy.  None (default): nothing changes.
     solid_tiles=True (with solid=...): the batches step three to five steps per launch on the tile kernel
     (CavityBatch(tuning=dict(solid_tiles=True))) instead of one; the same bits.
+    subgrid (BC='BB'): the constant Cs^2 of the local Smagorinsky closure (CavityBatch.set_subgrid; the reference's is 0.025) in every
+    lattice, each with its own tau0 -- a sweep to Reynolds numbers a coarse lattice cannot resolve; without solid=... the cavities run
+    as obstacle lattices with an empty mask.  None (default) and 0: no closure, nothing changes.
     batch_factory (default: CavityBatch, i.e. liblbm_hip.so) exists so that the sweep's loop can be unit-tested with a stand-in, like
     run_cavity's solver_factory; it is not a fallback."""
     semantics = wall_model(BC, "mrt_gpu", turb, solid is not None, solid_tiles)
     by_res = by_residual(criterion, residual_tol)
+    cs2 = subgrid_constant(subgrid, BC, solid_tiles)
     say = (lambda *a: None) if quiet else print
     Re_range = np.arange(100, 5100, 10) if Re_range is None else np.asarray(Re_range)   # MRT_GPU_datagen.py:55
     n = len(Re_range)
@@ -137,7 +145,7 @@ def generate(Re_range=None, xsize=32 * 12, ysize=32 * 12, RT="SRT", turb=1, uLB=
     def work(k):
         return _solve_batch(chunks[k], Re_range, xsize, ysize, RT, turb, uLB, maxIt, Pinterval, tolerance,
                             devices[k % len(devices)], dtype, say, out, arith, convergence, semantics,
-                            float(residual_tol) if by_res else None, residual_final, batch_factory, solid, solid_tiles)
+                            float(residual_tol) if by_res else None, residual_final, batch_factory, solid, solid_tiles, cs2)
     if len(devices) > 1 and len(chunks) > 1:
         with ThreadPoolExecutor(max_workers=len(devices)) as pool:      # lbm_step runs in C with the GIL released
             feq = list(pool.map(work, range(len(chunks))))
@@ -184,8 +192,16 @@ def main(argv=None):
                     help="a solid obstacle in every cavity: the cells [X0, X1) x [Y0, Y1), y = 0 the lid (repeatable; needs --BC BB)")
     ap.add_argument("--solid-tiles", action="store_true",
                     help="with --solid-box: three to five steps per launch on the tile kernel instead of one (the same bits)")
+    ap.add_argument("--subgrid", type=float, default=None, metavar="CS2",
+                    help="the local Smagorinsky closure in every cavity with this constant (the reference's is 0.025; needs --BC BB)")
     a = ap.parse_args(argv)
     bb = dict(BC="BB", turb=0) if a.BC == "BB" else {}
+    if a.subgrid is not None:
+        try:
+            subgrid_constant(a.subgrid, a.BC, a.solid_tiles)
+        except ValueError as e:
+            ap.error(str(e))
+        bb["subgrid"] = a.subgrid
     if a.solid_box or a.solid_tiles:
         try:
             mask = mask_from(a.size, a.size, a.solid_box)

@@ -29,7 +29,7 @@ from .VTKWrapper import saveToVTK
 from .monitor import vortex_window
 from .solid import disc_fractions, discs_into, labels_from, mask_from
 from .solver import CavitySolver
-from .stopping import MeanUStop, ResidualStop, by_residual, wall_model
+from .stopping import MeanUStop, ResidualStop, by_residual, subgrid_constant, wall_model
 
 
 class CavityResult:
@@ -57,12 +57,13 @@ class CavityResult:
         self.residuals = []         # run_cavity(criterion="residual"): (iteration, residual record) at every output iteration after the first
         self.forces = []            # run_cavity(solid=mask): (iteration, CavitySolver.solid_force()) at every output iteration
         self.force_series = None    # run_cavity(force_every=N): CavitySolver.force_series() of the whole run
+        self.tau_mean = []          # run_cavity(subgrid=cs2): (iteration, mean of get_tau() over the fluid cells) at every output iteration
 
 
 CS2_EFFECTIVE, CS_BULK = 0.025, 0.16     # MRT_GPU.py:350,374-376: Van Driest damping is overwritten by Cs2 = 0.025
 
 
-def _dashboard(path, u, rho, It, hist, Re, RT, regime, BC, xsize, ysize, uLB, relax, tau_mean=None):
+def _dashboard(path, u, rho, It, hist, Re, RT, regime, BC, xsize, ysize, uLB, relax, tau_mean=None, cs2=None):
     """PNG dashboard of MRT_GPU.py:786-870 (centreline plots vs Ghia, streamlines with vortex
     markers, regression history, parameter text)."""
     import matplotlib
@@ -123,7 +124,11 @@ def _dashboard(path, u, rho, It, hist, Re, RT, regime, BC, xsize, ysize, uLB, re
         # MRT_GPU.py:862-866.  The reference prints these two lines under its `regime == 'Turbulent'` label (which it assigns to
         # turb = 0, lines 277-280) from host names that do not exist (`Cs`, `Csbulk`: NameError) and from a `tauS` that is never
         # downloaded; here they appear when the closure is on, with the constant the kernel really uses and the mean of taus_g.
-        pyplot.figtext(0.65, 0.17, "Smagorinsky constant, Cs = " + str(round(CS2_EFFECTIVE ** 0.5, 4)) + " at wall to " + str(CS_BULK) + " at bulk")
+        # cs2 (run_cavity(subgrid=...)): the local closure of the bounce-back lattices, one constant everywhere, tau from get_tau()
+        if cs2 is None:
+            pyplot.figtext(0.65, 0.17, "Smagorinsky constant, Cs = " + str(round(CS2_EFFECTIVE ** 0.5, 4)) + " at wall to " + str(CS_BULK) + " at bulk")
+        else:
+            pyplot.figtext(0.65, 0.17, "Smagorinsky constant, Cs = " + str(round(cs2 ** 0.5, 4)) + " everywhere (local closure)")
         pyplot.figtext(0.65, 0.15, "Mean relaxation time, tau+tau_turbulent, is  " + str(tau_mean))
     f.suptitle("Lid Driven Cavity - Re" + str(int(Re)) + " " + regime + " " + RT + " " + BC + " " + str(xsize) + "*"
                + str(ysize), fontsize=30, y=1.04)
@@ -295,6 +300,12 @@ def _collect(res, solver, with_series, averaging):
         res.u_mean, res.rho_mean, res.uu, res.vv, res.uv, res.samples = st["u"], st["rho"], st["uu"], st["vv"], st["uv"], st["samples"]
 
 
+def _fluid_tau_mean(solver, run):
+    """The mean over the fluid cells of get_tau() of a run with a sub-grid constant: the tau of the iteration that comes next."""
+    tau = solver.get_tau()
+    return float(np.mean(tau if run.fluid is None else tau[run.fluid], dtype=np.float64))
+
+
 def _write_files(solver, run, c, It, hist):
     """The dashboard and the .vtr files of output iteration It (and <project>_mean.#####.vtr once the statistics hold samples)."""
     xsize, ysize = run.xsize, run.ysize
@@ -302,8 +313,10 @@ def _write_files(solver, run, c, It, hist):
     if run.SavePlot and run.have_ghia:
         u, rho = c.fields
         tau_mean = float(np.mean(solver.get_tau())) if (run.turb == 1 and hasattr(solver, "get_tau")) else None
+        if run.subgrid is not None:
+            tau_mean = _fluid_tau_mean(solver, run)
         _dashboard(os.path.join(run.OutputFolder, run.project + "_" + index + ".png"), u, rho, It, hist, run.Re, run.RT, run.regime, run.BC,
-                   xsize, ysize, run.uLB, solver.relax, tau_mean)
+                   xsize, ysize, run.uLB, solver.relax, tau_mean, run.subgrid)
     if run.SaveVTK:
         u, rho = c.fields
         grid = (np.arange(0, xsize, dtype="float64"), np.arange(0, ysize, dtype="float64"), np.arange(0, 1, dtype="float64"))
@@ -326,7 +339,7 @@ def run_cavity(maxIt=3000000, Re=10000.0, RT="SRT", turb=1, xsize=32 * 5, ysize=
                dtype=np.float32, semantics="mrt_gpu", device=0, quiet=False, solver_factory=None, arith="strict",
                convergence="host", vtk_correct=False, BC="EB-NEBB ", AverageFrom=None, AverageEvery=100, monitor="host",
                MonitorEvery=None, Probes=(), vortex_table=False, criterion="mean_u", residual_tol=None, residual_hits=1, solid=None,
-               solid_tiles=False, bodies=None, force_every=None, body_motion=None, solid_shape=None):
+               solid_tiles=False, bodies=None, force_every=None, body_motion=None, solid_shape=None, subgrid=None):
     """Run the lid-driven cavity like MRT_GPU.py does; returns a :class:`CavityResult`.
 
     Argument names and defaults are the module constants of MRT_GPU.py:38-58.
@@ -376,7 +389,13 @@ def run_cavity(maxIt=3000000, Re=10000.0, RT="SRT", turb=1, xsize=32 * 5, ysize=
     (CavitySolver.set_body_motion) from the first iteration on: the bodies keep their cells.  None (default): obstacles at rest.
     solid_shape (with solid=...): q[8, xsize, ysize], the wall distance of every link (CavitySolver.set_shape; solid.disc_fractions,
     solid.fractions_from_distance), set before the motion and the first iteration: the links bounce by linear interpolation, second
-    order for curved walls, and the lattice no longer conserves its mass.  None (default): the half-way rule, nothing changes."""
+    order for curved walls, and the lattice no longer conserves its mass.  None (default): the half-way rule, nothing changes.
+    subgrid (BC='BB', turb=0; with or without solid=...): the constant Cs^2 of the local Smagorinsky closure (CavitySolver.set_subgrid;
+    the reference's value is 0.025), from the first iteration on: a coarse lattice at a high Reynolds number stays finite.  Without a
+    mask the cavity runs as an obstacle lattice with an empty one.  Every output iteration prints `current mean relaxation time is
+    <mean of get_tau() over the fluid cells>`, and the dashboard shows the reference's "Mean relaxation time" line with it.  A passive
+    scalar would keep its molecular diffusivity.  None (default) and 0: no closure, nothing changes."""
+    cs2 = subgrid_constant(subgrid, BC, solid_tiles)
     by_res, semantics = _check_arguments(criterion, residual_tol, residual_hits, monitor, MonitorEvery, convergence, AverageFrom,
                                          AverageEvery, BC, semantics, turb, solid, solid_tiles, bodies, force_every, body_motion, solid_shape)
     on_device = monitor == "device"
@@ -388,14 +407,19 @@ def run_cavity(maxIt=3000000, Re=10000.0, RT="SRT", turb=1, xsize=32 * 5, ysize=
     extra = {} if arith == "strict" else {"arith": arith}      # 'fast' / 'promoted': see CavitySolver
     if solid is not None:
         extra["solid"] = solid
+    elif cs2 is not None:      # (the closure lives on the obstacle lattices: the plain bounce-back cavity is one with an empty mask)
+        extra["solid"] = np.zeros((xsize, ysize), dtype=bool)
     if solid_tiles:
         extra["tuning"] = dict(solid_tiles=True)
     if bodies is not None:
         extra["bodies"] = bodies
     solver = make(xsize, ysize, Re, RT=RT, uLB=uLB, semantics=semantics, dtype=dtype, turb=turb, device=device, **extra)
     _banner(say, Re, RT, turb, solver.relax)
-    if solid_shape is not None or body_motion is not None:
+    if solid_shape is not None or body_motion is not None or cs2 is not None:
         try:
+            if cs2 is not None:
+                solver.set_subgrid(cs2)
+                say("Sub-grid closure is on, Cs2 = ", cs2)
             if solid_shape is not None:     # (the shape first, then the motion)
                 solver.set_shape(np.asarray(solid_shape, dtype=np.float64))
             if body_motion is not None:
@@ -410,12 +434,13 @@ def run_cavity(maxIt=3000000, Re=10000.0, RT="SRT", turb=1, xsize=32 * 5, ysize=
             pass
     run = SimpleNamespace(Re=Re, RT=RT, turb=turb, xsize=xsize, ysize=ysize, uLB=uLB, Pinterval=Pinterval, SavePlot=SavePlot, SaveVTK=SaveVTK,
                           project=project, OutputFolder=OutputFolder, vtk_correct=vtk_correct, vortex_table=bool(vortex_table),
-                          have_ghia=int(round(float(Re))) in ghia.RE_COLUMNS,
+                          have_ghia=int(round(float(Re))) in ghia.RE_COLUMNS, subgrid=cs2,
+                          fluid=None if solid is None else ~(np.asarray(solid) != 0),
                           regime="Laminar" if turb == 1 else "Turbulent",   # labels exactly as (mis)assigned at MRT_GPU.py:277-280
                           BC="BB" if semantics == "bounce_back" else "EB-NEBB ")   # (the dashboard's label; MRT_GPU.py:281 spells the default so)
     res = CavityResult()
     done = 0          # iterations performed
-    outputs = SaveVTK or SavePlot or on_device or bool(vortex_table) or by_res or solid is not None
+    outputs = SaveVTK or SavePlot or on_device or bool(vortex_table) or by_res or solid is not None or cs2 is not None
     averaging = False
 
     def advance(n):   # n iterations; statistics begin once `done` reaches AverageFrom
@@ -457,6 +482,9 @@ def run_cavity(maxIt=3000000, Re=10000.0, RT="SRT", turb=1, xsize=32 * 5, ysize=
                     F = solver.solid_force()
                     res.forces.append((It, F))
                     say("current force on the obstacles is (" + str(F["fx"]) + ", " + str(F["fy"]) + ") over " + str(F["links"]) + " links")
+                if cs2 is not None:
+                    res.tau_mean.append((It, _fluid_tau_mean(solver, run)))
+                    say("current mean relaxation time is " + str(res.tau_mean[-1][1]))
                 _write_files(solver, run, c, It, res.regression)
                 say("time elapsed is ", (timer() - tstart), "seconds")
                 if by_res:
@@ -535,11 +563,20 @@ def main(argv=None):
     ap.add_argument("--solid-disc", type=float, nargs=3, action="append", default=[], metavar=("X0", "Y0", "R"),
                     help="a solid disc: the cells whose centre lies within R of (X0, Y0), index coordinates (repeatable; a body of its own "
                          "after the boxes and the file; needs --BC BB --turb 0)")
+    ap.add_argument("--subgrid", type=float, default=None, metavar="CS2",
+                    help="the local Smagorinsky closure of the bounce-back and obstacle lattices with this constant (the reference's is 0.025; "
+                         "needs --BC BB --turb 0; not with --solid-tiles)")
     ap.add_argument("--curved", action="store_true",
                     help="with --solid-disc: every link of a disc carries its exact distance to the circle and bounces by linear interpolation "
                          "(second order; the lattice no longer conserves its mass; not with --solid-tiles)")
     a = ap.parse_args(argv)
     mask = labels = motion = shape = None
+    try:
+        subgrid_constant(a.subgrid, a.BC, a.solid_tiles)
+        if a.subgrid:
+            wall_model(a.BC, a.semantics, a.turb)
+    except ValueError as e:
+        ap.error(str(e))
     if a.solid_box or a.solid_file is not None or a.solid_tiles or a.force_every is not None or a.body_motion or a.solid_disc or a.curved:      # an obstacle the run cannot have is an argument error, through the one check
         try:
             mask = mask_from(a.xsize, a.ysize, a.solid_box, a.solid_file)
@@ -572,7 +609,8 @@ def main(argv=None):
                    **(dict(bodies=labels) if a.force_every is not None or motion is not None or a.solid_disc else {}),
                    **(dict(solid_shape=shape) if shape is not None else {}),
                    **(dict(force_every=a.force_every) if a.force_every is not None else {}),
-                   **(dict(body_motion=motion) if motion is not None else {}))
+                   **(dict(body_motion=motion) if motion is not None else {}),
+                   **(dict(subgrid=a.subgrid) if a.subgrid is not None else {}))
     print("MLUPS : ", r.mlups)
     return 0
 

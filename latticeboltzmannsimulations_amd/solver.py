@@ -254,7 +254,8 @@ class CavitySolver:
         return np.array(out[:]) if self._lead else float(out[0])
 
     def get_tau(self, out_dtype=None):
-        """tau + tau_turbulent per cell of the last iteration (taus_g, MRT_GPU.py:387); 1 / omega everywhere when turb = 0."""
+        """tau + tau_turbulent per cell of the last iteration (taus_g, MRT_GPU.py:387); 1 / omega everywhere when turb = 0.  With a
+        sub-grid constant (set_subgrid): the tau of the step that starts from the current state, solid and hold cells at 1 / omega."""
         dt = self.dtype if out_dtype is None else np.dtype(out_dtype)
         tau = np.zeros(self._lead + (self.nx, self.ny), dtype=dt)
         self._check(self.lib.lbm_get_tau(self._h, tau.ctypes.data, _DT[tau.dtype]), "lbm_get_tau")
@@ -741,6 +742,23 @@ class CavitySolver:
         self._check(self.lib.lbm_get_driving_force(self._h, ctypes.byref(fx), ctypes.byref(fy)), "lbm_get_driving_force")
         return fx.value, fy.value
 
+    # -- sub-grid viscosity (lbm_set_subgrid, lbm_get_subgrid) ------------------------------------------------------------------
+    def set_subgrid(self, cs2=0.025):
+        """The local Smagorinsky closure of an obstacle lattice (lbm_set_subgrid; solid=..., one step per launch): every collision of a
+        cell that is neither solid nor held takes the rate 1 / tau, tau = (tau0 + sqrt(tau0^2 + 18 sqrt(2) cs2 |P| / rho)) / 2, |P| the
+        norm of the cell's whole non-equilibrium momentum flux -- nu_t = cs2 |S|.  No history: the lattice, the step count and the
+        samplers stay; every lattice of a batch takes the same constant with its own tau0.  A passive scalar keeps its molecular
+        diffusivity; with buoyancy the call is refused.  get_tau() returns the field.  0: no closure."""
+        self._check(self.lib.lbm_set_subgrid(self._h, float(cs2)), "lbm_set_subgrid")
+        return self
+
+    @property
+    def subgrid(self):
+        """The sub-grid constant as set; 0.0 without the closure."""
+        cs2 = ctypes.c_double(0.0)
+        self._check(self.lib.lbm_get_subgrid(self._h, ctypes.byref(cs2)), "lbm_get_subgrid")
+        return cs2.value
+
     # -- a passive scalar: temperature or dye (lbm_scalar_*) ---------------------------------------------------------------
     def _cells(self, a, name, fill=None):
         """A float64 [X, Y] array as the scalar calls take it; a number fills the lattice."""
@@ -892,6 +910,8 @@ class CavitySolver:
             out.update(periodic=np.array(per))
         if self._h is not None and any(self.driving_force):
             out.update(driving_force=np.array(self.driving_force))
+        if self._h is not None and self.subgrid > 0.0:
+            out.update(subgrid=np.float64(self.subgrid))
         return out
 
     def _shape_entry(self):
@@ -914,7 +934,9 @@ class CavitySolver:
         closure and Reynolds number -- a continuation is bit-identical only then -- and, where either side is 'promoted', the
         arithmetic (strict and fast states mix as before; a checkpoint without the key counts as strict) and the solid mask (none on either
         side, or the same cells; without `strict` the populations are uploaded under this solver's own mask).  The array is the whole lattice, so a slab
-        may restart from a checkpoint of the undivided lattice (each context reads its own rows) but not from another slab's."""
+        may restart from a checkpoint of the undivided lattice (each context reads its own rows) but not from another slab's.
+        A file that carries a sub-grid constant sets it and clears a buoyancy this solver had set (the two refuse each other); a file
+        without one clears the constant."""
         with np.load(_npz(path), allow_pickle=False) as z:
             if int(z["nx"]) != self.nx or int(z["ny"]) != self.ny:
                 raise ValueError("checkpoint lattice size differs")
@@ -974,6 +996,11 @@ class CavitySolver:
                 self.set_wall_velocity(uw)
             if "driving_force" in z or (self._h is not None and any(self.driving_force)):      # (the force last: it is no geometry)
                 self.set_driving_force(*(np.asarray(z["driving_force"]) if "driving_force" in z else (0.0, 0.0)))
+            cs2 = float(z["subgrid"]) if "subgrid" in z else 0.0      # (the sub-grid constant: no geometry, no history)
+            if cs2 > 0.0 or (self._h is not None and self.subgrid > 0.0):
+                if cs2 > 0.0 and self.buoyancy is not None:      # (this solver's own buoyancy would refuse the constant)
+                    self.set_buoyancy(0.0, 0.0)
+                self.set_subgrid(cs2)
             if same_mask and "scalar_g" in z:      # (the scalar last: the geometry calls above end one; a file without it leaves this solver's as it is)
                 self.begin_scalar(float(z["scalar_D"]), np.asarray(z["scalar_c0"]), float(z["scalar_magic"]),
                                   np.asarray(z["scalar_wall_value"]) if "scalar_wall_value" in z else None,

@@ -55,6 +55,23 @@ def wall_model(BC, semantics, turb, solid=False, solid_tiles=False):
     return semantics
 
 
+def subgrid_constant(subgrid, BC, solid_tiles=False):
+    """The sub-grid constant of a run (CavitySolver.set_subgrid), or None: a finite number > 0 (None and 0: no closure), with the
+    bounce-back walls, one step per launch."""
+    if subgrid is None:
+        return None
+    cs2 = float(subgrid)
+    if not (cs2 >= 0.0 and cs2 != float("inf")):
+        raise ValueError("subgrid must be a finite constant >= 0 (Cs^2 of the local Smagorinsky closure; the reference's is 0.025)")
+    if cs2 == 0.0:
+        return None
+    if BC.strip() != "BB":
+        raise ValueError("subgrid is the closure of the bounce-back and obstacle lattices: pass BC='BB' (the wet-node walls have turb=1)")
+    if solid_tiles:
+        raise ValueError("subgrid needs one step per launch: the tile kernel (solid_tiles) has no closure")
+    return cs2
+
+
 def by_residual(criterion, residual_tol, residual_hits=1):
     """True for criterion='residual' (False for 'mean_u'), with its arguments checked."""
     if criterion not in ("mean_u", "residual"):
