@@ -841,6 +841,33 @@ int lbm_get_buoyancy(lbm_ctx* c, double* ax_out, double* ay_out, double* c_ref_o
 int lbm_set_subgrid(lbm_ctx* c, double cs2);
 int lbm_get_subgrid(lbm_ctx* c, double* cs2_out);
 
+/* --- per-cell relaxation rates of an obstacle lattice: a viscosity field ------------------------------ */
+/* No reference counterpart.  On a LBM_SEM_BOUNCE_BACK_SOLID context at one step per launch every cell that is neither solid nor held takes
+ * its own rates into the collision, the same operations on a value per cell; nothing else of the step changes: the driving force and the
+ * wall terms are added after the collision as before, and the raw first step after lbm_set_state uses the field too.
+ *   omega[B][nx][ny], indexed like tau_host of lbm_get_tau (B = 1 for a single lattice): the viscous rate of each cell -- SRT's omega,
+ *     TRT's omega+, MRT's omega_nu; nu = (1 / omega - 1/2) / 3 in lattice units.  MRT's other rates (omega_e, omega_eps, omega_q) stay the
+ *     lattice's.
+ *   omegam, the same shape, or NULL: TRT's omega- of each cell.  NULL: every cell keeps the lattice's omegam.  A two-layer Poiseuille flow
+ *     is exact only with the magic parameter (1/omega+ - 1/2)(1/omega- - 1/2) kept per cell; with a uniform omega- it is second order.
+ * Each value is rounded once to the lattice type on the host and kept in one read-only plane per rate and lattice on the device.
+ * lbm_set_relaxation_field: may be called at any time; it touches neither the lattice nor the step count and ends no sampler, and it
+ *   survives lbm_set_solid, lbm_set_relaxation and the other setters (a later lbm_set_relaxation changes the rates of solid and hold cells'
+ *   reports and MRT's other rates only).  omega = NULL (omegam NULL too) clears the field and restores the launches, the bits and the
+ *   lbm_describe text of a context without it; while a field is set that text gains ` relax_field` (` relax_field+m` with omegam).
+ *   LBM_ERR_INVALID: a value that is not finite or not in (0, 2) -- the message names the first offending cell; values at solid and hold
+ *   cells are checked the same way but never used.  LBM_ERR_STATE with a reason: another semantics (which covers slabs: an obstacle
+ *   lattice is whole), a LBM_FLAG_SOLID_TILES context, buoyancy is set, omegam on a context whose collision is not TRT.  While a field is
+ *   set lbm_set_buoyancy is refused with a reason (the pairing would be one more set of kernel twins).  A passive scalar keeps its own
+ *   diffusivity.
+ * With lbm_set_subgrid(cs2 > 0): tau0 of the closure is 1 / omega of the cell, one division in the lattice type; omega- stays the cell's.
+ * lbm_get_relaxation_field: 1 and the planes as the device holds them (rounded to the lattice type; omegam_out untouched without an
+ *   omega- plane; either pointer may be NULL) if a field is set, 0 if not.
+ * lbm_get_tau on such a context: a cell that is neither solid nor held reports the tau of the step that starts from the current state --
+ *   1 / omega of the cell in the lattice type, or the closure's value on that tau0; solid and hold cells report the lattice's tau0. */
+int lbm_set_relaxation_field(lbm_ctx* c, const double* omega, const double* omegam);
+int lbm_get_relaxation_field(lbm_ctx* c, double* omega_out, double* omegam_out);
+
 /* --- slab decomposition, externally driven exchange ---------------------------------- */
 /* No reference counterpart (the reference is single-GPU, MRT_GPU.py:29).  A step of a slab
  * is split so that a host-language driver can move halos with any transport:

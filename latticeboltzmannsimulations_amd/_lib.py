@@ -106,7 +106,8 @@ def build(force=False, verbose=False):
     """Compile csrc/*.hip for gfx950 into liblbm_hip.so next to this file (in-tree).  The translation units (eight of host code +
     C ABI: lbm_hip / lbm_plan / lbm_launch / lbm_comm / lbm_sampling / lbm_monitor / lbm_residual / lbm_topology / lbm_solid / lbm_bodies / lbm_body_motion / lbm_body_shape / lbm_scalar (with its kernels, from lbm_scalar.hpp); the explicit instantiations of the tile and
     streaming kernels, of the one-step kernels with a solid mask per mode of the wall rule -- lbm_solid / lbm_solid_move / lbm_solid_shape / lbm_solid_buoy
-    and, with the sub-grid closure, lbm_solid_sgs / lbm_solid_sgs_move / lbm_solid_sgs_shape, all from lbm_solid.hpp -- and of the tile kernel with solid cells, for float and for double) are compiled in parallel into csrc/_obj/ and linked."""
+    and, with the sub-grid closure, lbm_solid_sgs / lbm_solid_sgs_move / lbm_solid_sgs_shape, with a relaxation field lbm_solid_relax / lbm_solid_relax_move /
+    lbm_solid_relax_shape and with both lbm_solid_relax_sgs / lbm_solid_relax_sgs_move / lbm_solid_relax_sgs_shape, all from lbm_solid.hpp -- and of the tile kernel with solid cells, for float and for double) are compiled in parallel into csrc/_obj/ and linked."""
     srcs = sources()
     if not force and os.path.exists(LIB_PATH) and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(s) for s in srcs):
         return LIB_PATH
@@ -208,6 +209,8 @@ SIGNATURES = {
     "lbm_get_buoyancy": (_i, [_vp, ctypes.POINTER(_d), ctypes.POINTER(_d), ctypes.POINTER(_d)]),
     "lbm_set_subgrid": (_i, [_vp, _d]),                 # (cs2: the sub-grid constant; 0 clears)
     "lbm_get_subgrid": (_i, [_vp, ctypes.POINTER(_d)]),
+    "lbm_set_relaxation_field": (_i, [_vp, _vp, _vp]),  # (omega[B][nx][ny] doubles, omegam the same or NULL; both NULL clears)
+    "lbm_get_relaxation_field": (_i, [_vp, _vp, _vp]),  # -> 1 if set, 0 if not
     "lbm_halo_elems": (_i, [_vp]),
     "lbm_halo_export": (_i, [_vp, _i, _vp]),
     "lbm_halo_import": (_i, [_vp, _i, _vp]),

@@ -15,6 +15,7 @@ import numpy as np
 
 from . import scalar as SC
 from . import solid as S
+from . import viscosity as V
 
 
 def inflow_profile(ny, umax, kind="parabolic"):
@@ -75,7 +76,7 @@ def solver_re(Re_D, D, umax, mean, ny):
 
 
 def run_channel(nx, ny, Re_D, umax=0.05, disc=None, curved=False, profile="parabolic", walls="rest", steps=20000, force_every=100, RT="MRT",
-                dtype=np.float32, arith="strict", device=0, solver_factory=None, quiet=False, scalar=None, buoyancy=None, subgrid=None):
+                dtype=np.float32, arith="strict", device=0, solver_factory=None, quiet=False, scalar=None, buoyancy=None, subgrid=None, sponge=None):
     """Step a channel and keep the force series of the (first) obstacle on the device.  Returns dict(Cd, Cl, fx, fy, steps, Re, nu,
     series): Cd = 2 Fx / (rho mean^2 D), Cl likewise from Fy, of the last sample (rho = 1); D = 2 r of the disc (without one: the
     channel's width and the force on the side walls).  Re_D = mean D / nu is converted to the solver's Re (solver_re).
@@ -85,7 +86,13 @@ def run_channel(nx, ny, Re_D, umax=0.05, disc=None, curved=False, profile="parab
     (scalar.nusselt), its flux `scalar_flux` and the scalar diffusivity.  buoyancy=(ax, ay, c_ref): the scalar acts on the flow
     (CavitySolver.set_buoyancy; needs scalar=...).  subgrid=cs2: the local Smagorinsky closure (CavitySolver.set_subgrid) from the first
     step on, for a channel beyond the steady regime on a coarse lattice; the result gains tau_mean, the mean over the fluid cells of
-    get_tau() after the last step.  The scalar keeps its molecular diffusivity; not with buoyancy."""
+    get_tau() after the last step.  The scalar keeps its molecular diffusivity; not with buoyancy.
+    sponge=(length, factor): a zone of raised viscosity in front of the held outlet (CavitySolver.set_viscosity with nu times
+    viscosity.sponge(nx, ny, length, factor), a quadratic ramp to factor nu at the outlet column; under TRT the magic parameter of the
+    solver's rates is kept in every cell), which relaxes a wake towards the profile the outlet holds; the result gains outlet_drho, the
+    largest |rho - 1| over the fluid cells of the last 20 columns in front of the outlet after the last step.  Not with buoyancy."""
+    if sponge is not None and buoyancy is not None:
+        raise ValueError("sponge and buoyancy exclude each other: the buoyant kernels read no viscosity field")
     if subgrid is not None and buoyancy is not None and float(subgrid) > 0.0:
         raise ValueError("subgrid and buoyancy exclude each other: a buoyant flow with the closure needs an eddy diffusivity for the scalar")
     g = channel(nx, ny, umax, profile, walls, disc, curved)
@@ -106,6 +113,11 @@ def run_channel(nx, ny, Re_D, umax=0.05, disc=None, curved=False, profile="parab
         s.set_wall_velocity(g["wall_velocity"])
         if subgrid is not None:
             s.set_subgrid(float(subgrid))
+        if sponge is not None:
+            length, factor = int(sponge[0]), float(sponge[1])
+            rl = s.relax
+            magic = (1.0 / rl["omega"] - 0.5) * (1.0 / rl["omegam"] - 0.5) if RT == "TRT" else None
+            s.set_viscosity(nu * V.sponge(nx, ny, length, factor), magic)
         if scalar is not None:
             sc = dict(dict(disc_value=1.0, inlet_value=0.0, magic=0.25), **scalar)
             if not g["discs"]:
@@ -125,6 +137,11 @@ def run_channel(nx, ny, Re_D, umax=0.05, disc=None, curved=False, profile="parab
         s.end_force()
         flux = float(s.scalar_flux()["flux"][body]) if scalar is not None else None
         tau_mean = float(np.mean(s.get_tau()[~g["solid"] & ~g["hold"]], dtype=np.float64)) if subgrid is not None else None
+        if sponge is not None:
+            rho = np.asarray(s.get_fields()[1], dtype=np.float64)
+            tail = np.zeros((nx, ny), dtype=bool)
+            tail[max(nx - 21, 1):nx - 1, :] = True
+            outlet_drho = float(np.abs(rho - 1.0)[tail & ~g["solid"] & ~g["hold"]].max())
     fx, fy = float(series["fx"][-1][body]), float(series["fy"][-1][body])
     scale = 2.0 / (g["mean"] ** 2 * D)
     out = dict(Cd=scale * fx, Cl=scale * fy, fx=fx, fy=fy, steps=int(steps), Re=Re, nu=nu, series=series, body=body)
@@ -132,10 +149,13 @@ def run_channel(nx, ny, Re_D, umax=0.05, disc=None, curved=False, profile="parab
         out.update(scalar_flux=flux, scalar_D=float(sc["D"]), Nu=SC.nusselt(flux, sc["D"], float(sc["disc_value"]) - float(sc["inlet_value"]), D))
     if subgrid is not None:
         out.update(subgrid=float(subgrid), tau_mean=tau_mean)
+    if sponge is not None:
+        out.update(sponge=(length, factor), outlet_drho=outlet_drho)
     if not quiet:
         print(f"after {steps} steps: Fx = {fx:.8g}, Fy = {fy:.8g}, Cd = 2 Fx / (rho mean^2 D) = {out['Cd']:.6g}, Cl = {out['Cl']:.6g}" +
               (f", Nu = flux / (pi D_s dC) = {out['Nu']:.6g}" if scalar is not None else "") +
-              (f", mean relaxation time {tau_mean:.6g}" if subgrid is not None else ""))
+              (f", mean relaxation time {tau_mean:.6g}" if subgrid is not None else "") +
+              (f", max |rho - 1| in the last 20 columns {outlet_drho:.3e}" if sponge is not None else ""))
     return out
 
 
@@ -159,16 +179,20 @@ def main(argv=None):
     ap.add_argument("--inlet-value", dest="inlet_value", type=float, default=0.0)
     ap.add_argument("--buoyancy", type=float, nargs=3, metavar=("AX", "AY", "CREF"), default=None, help="let the scalar act on the flow (needs --scalar-D)")
     ap.add_argument("--subgrid", type=float, default=None, metavar="CS2", help="the local Smagorinsky closure with this constant (the reference's is 0.025; not with --buoyancy)")
+    ap.add_argument("--sponge", type=float, nargs=2, metavar=("LENGTH", "FACTOR"), default=None,
+                    help="raise the viscosity over the last LENGTH columns in front of the held outlet, a quadratic ramp to FACTOR times nu (not with --buoyancy)")
     a = ap.parse_args(argv)
     if a.subgrid is not None and a.buoyancy is not None:
         ap.error("--subgrid and --buoyancy exclude each other")
+    if a.sponge is not None and a.buoyancy is not None:
+        ap.error("--sponge and --buoyancy exclude each other")
     if a.curved and a.disc is None:
         ap.error("--curved gives the disc its exact wall distances: it needs --disc")
     if a.scalar_D is not None and a.disc is None:
         ap.error("--scalar-D reports the disc's Nusselt number: it needs --disc")
     run_channel(a.xsize, a.ysize, a.Re_D, a.umax, a.disc, a.curved, a.profile, a.walls, a.steps, a.force_every, a.RT, np.dtype(a.dtype).type,
                 device=a.device, scalar=None if a.scalar_D is None else dict(D=a.scalar_D, disc_value=a.disc_value, inlet_value=a.inlet_value),
-                buoyancy=a.buoyancy, subgrid=a.subgrid)
+                buoyancy=a.buoyancy, subgrid=a.subgrid, sponge=a.sponge)
     return 0
 
 

@@ -179,10 +179,11 @@ __device__ __forceinline__ f32x2 fma_(f32x2 a, f32x2 b, f32x2 c) { return __buil
 // MRT MRT_GPU.py:633-655 (m = M f with jx = m3, jy = m5 from the raw populations, the
 // reference's own m_eq polynomial, f* = Minv m).  Zero matrix entries are skipped and the
 // +-1, +-2, +-4 entries of M are exact scalings: value-identical to the dense products.
-template <typename T, int COLL>
+template <typename T, int COLL, bool WM = false>
 __device__ __forceinline__ void collide(const T (&f)[Q], T rho, const T (&feq)[Q],
-                                        const Relax<typename ScalarOf<T>::type>& w, T w_nu, T (&out)[Q], bool lid = false) {
-    // w_nu: the viscous rate of each cell (w.w_nu, or the Smagorinsky value); the other rates are lattice-wide scalars
+                                        const Relax<typename ScalarOf<T>::type>& w, T w_nu, T (&out)[Q], bool lid = false, T w_m = T{}) {
+    // w_nu: the viscous rate of each cell (w.w_nu, the Smagorinsky value, or the cell's of a relaxation field); the other rates are
+    // lattice-wide scalars -- but for WM (lbm_set_relaxation_field): TRT's odd rate of each cell is w_m, in the place of w.w_m
     // lid (C_MRT_FAST only): the cells are on the lid row, where rho is the overridden rho_l, not the population sum m0
     typedef typename ScalarOf<T>::type R;
     if (COLL == C_SRT || COLL == C_SRT_FAST || COLL == C_SRT_PROM) {
@@ -201,7 +202,10 @@ __device__ __forceinline__ void collide(const T (&f)[Q], T rho, const T (&feq)[Q
         }
         fp[0] = f[0]; fm[0] = T{}; ep[0] = feq[0]; em[0] = T{};
 #pragma unroll
-        for (int k = 0; k < Q; ++k) out[k] = (f[k] - w_nu * (fp[k] - ep[k])) - w.w_m * (fm[k] - em[k]);
+        for (int k = 0; k < Q; ++k) {
+            if constexpr (WM) out[k] = (f[k] - w_nu * (fp[k] - ep[k])) - w_m * (fm[k] - em[k]);
+            else out[k] = (f[k] - w_nu * (fp[k] - ep[k])) - w.w_m * (fm[k] - em[k]);
+        }
     } else if (COLL == C_MRT_FAST) {
         // The same operator, m = M f, m* = m - S (m - m_eq), f* = Minv m*, with the sums of M and Minv factored through the
         // pairs f1 +- f3, f2 +- f4, f5 +- f7, f6 +- f8 and explicit fused multiply-adds: ~75 operations per cell instead of
@@ -327,9 +331,11 @@ __device__ __forceinline__ T diag_flux(const T (&f)[Q]) {   // product = cx cy f
 // with fused multiply-adds: ~50 / ~65 operations per cell after the moments instead of ~105 / ~140, and sum_k cx cy feq_k = rho ux uy
 // exactly.  Same operator, other rounding: NOT the reference's operation order (tolerances: tests/test_gpu_parity.py::test_fast_arithmetic_*);
 // one spelling for every kernel, so a lattice gives the same bits however it is cut.
-template <typename T, int COLL, bool TURB>
+// WM (the kernels of a relaxation field alone, lbm_set_relaxation_field): w_m is TRT's odd rate of each cell, in the place of w.w_m -- the
+// same operations on a value per cell.
+template <typename T, int COLL, bool TURB, bool WM = false>
 __device__ __forceinline__ void equ_collide(const T (&g)[Q], T rho, T ux, T uy, const Relax<typename ScalarOf<T>::type>& w, T w_nu, T (&out)[Q], T& q2,
-                                            bool lid = false) {   // lid: the cells are on the lid row (only the factored MRT form asks)
+                                            bool lid = false, T w_m = T{}) {   // lid: the cells are on the lid row (only the factored MRT form asks)
     typedef typename ScalarOf<T>::type R;
     // (fp32 SRT with the closure keeps the unfused sequence: at the streaming kernels' 128 registers the fused one spills there -- 4096^2
     // 256 -> 210 GLUPS, while fp64 gains, 108 -> 134; without the closure it is what lets fp32 SRT take the walls kernel, 251 -> 414)
@@ -349,9 +355,10 @@ __device__ __forceinline__ void equ_collide(const T (&g)[Q], T rho, T ux, T uy, 
             pair(ux + uy, r5, g[5], g[7], out[5], out[7]);
             pair(ux - uy, r5, g[8], g[6], out[8], out[6]);
         } else {
-            const T mrho = w.w_m * rho, hp = (R)0.5 * w_nu;
+            const auto wm = [&] { if constexpr (WM) return w_m; else return w.w_m; }();   // (T per cell, or the lattice's R)
+            const T mrho = wm * rho, hp = (R)0.5 * w_nu;
             const T m1 = (R)(1.0 / 9) * mrho, m5 = (R)(1.0 / 36) * mrho;
-            const R hm = (R)0.5 * w.w_m;
+            const auto hm = (R)0.5 * wm;
             auto pair = [&](T cu, T rp, T rm, const T& ga, const T& gb, T& oa, T& ob) {
                 const T e = fma_((R)4.5 * cu, cu, base), o = (R)3 * cu;
                 const T P = fma_(-rp, e, hp * (ga + gb)), M = fma_(-rm, o, hm * (ga - gb));
@@ -373,7 +380,8 @@ __device__ __forceinline__ void equ_collide(const T (&g)[Q], T rho, T ux, T uy, 
     } else {
         T fe[Q];
         if (!coll_is_mrt(COLL) || TURB) equ<T, coll_is_prom(COLL)>(rho, ux, uy, fe);     // (the plain MRT operator needs neither u nor feq: MRT_GPU.py:633-648)
-        collide<T, COLL>(g, rho, fe, w, w_nu, out);
+        if constexpr (WM) collide<T, COLL, true>(g, rho, fe, w, w_nu, out, false, w_m);
+        else collide<T, COLL>(g, rho, fe, w, w_nu, out);
         if (TURB) q2 = diag_flux<T>(fe);
     }
 }
@@ -414,10 +422,12 @@ __device__ __forceinline__ T smagorinsky_omega(const T (&f)[Q], T qeq_prev, T rh
 // every operation in the lattice type, one rounding each, in the order written (rho / 3 is rho * (R)(1.0 / 3)); FAST: the two square roots
 // and the two divisions ((k N) / rho here, 1 / tau in subgrid_omega) by sqrt_<FAST> / div_<FAST>, as the closure above.  No history: the
 // step that computes tau uses it.  tests/subgrid_ref.py restates the order.
-template <typename T, bool FAST = false>
-__device__ __forceinline__ T subgrid_tau(const T (&f)[Q], T rho, T ux, T uy, typename ScalarOf<T>::type omega, typename ScalarOf<T>::type k) {
+// W: the type of omega -- the lattice's rate, a scalar, or (a relaxation field, lbm_set_relaxation_field) the cells' own, a T: tau0 is then
+// 1 / omega of the cell, the same division per cell.
+template <typename T, bool FAST = false, typename W = typename ScalarOf<T>::type>
+__device__ __forceinline__ T subgrid_tau(const T (&f)[Q], T rho, T ux, T uy, W omega, typename ScalarOf<T>::type k) {
     typedef typename ScalarOf<T>::type R;
-    const R tau0 = (R)1.0 / omega;
+    const W tau0 = (R)1.0 / omega;
     const T sxx = ((((f[1] + f[3]) + f[5]) + f[6]) + f[7]) + f[8];
     const T syy = ((((f[2] + f[4]) + f[5]) + f[6]) + f[7]) + f[8];
     const T sxy = ((f[5] - f[6]) + f[7]) - f[8];
@@ -428,10 +438,10 @@ __device__ __forceinline__ T subgrid_tau(const T (&f)[Q], T rho, T ux, T uy, typ
     const T n = sqrt_<FAST>((pxx * pxx + (R)2 * (pxy * pxy)) + pyy * pyy);
     return (R)0.5 * (tau0 + sqrt_<FAST>(tau0 * tau0 + div_<FAST>(k * n, rho)));
 }
-template <typename T, bool FAST = false>
-__device__ __forceinline__ T subgrid_omega(const T (&f)[Q], T rho, T ux, T uy, typename ScalarOf<T>::type omega, typename ScalarOf<T>::type k) {
+template <typename T, bool FAST = false, typename W = typename ScalarOf<T>::type>
+__device__ __forceinline__ T subgrid_omega(const T (&f)[Q], T rho, T ux, T uy, W omega, typename ScalarOf<T>::type k) {
     typedef typename ScalarOf<T>::type R;
-    return div_<FAST>(T((R)1.0), subgrid_tau<T, FAST>(f, rho, ux, uy, omega, k));
+    return div_<FAST>(T((R)1.0), subgrid_tau<T, FAST, W>(f, rho, ux, uy, omega, k));
 }
 
 // a8: wall rules on the populations of ONE perimeter cell, given the equilibrium of the
@@ -660,6 +670,62 @@ struct WallArg<R, WALL_SHAPE_SGS> {
     R sgs;
 };
 
+// A relaxation field (lbm_set_relaxation_field): one more bit of the mode, WALL_RELAX, on the three base modes and on their twins with the
+// closure.  rw: the plane of the cells' viscous rates (SRT's omega, TRT's omega+, MRT's omega_nu), rwm: the plane of TRT's omega- or null
+// (every cell then keeps the lattice's w_m: a wave-uniform run-time test) -- read-only, in the lattice type, addressed as the buoyancy
+// plane (buoy_at; lattice z of a batch at z * buoy_elems), so a vector's rates are one aligned 16-byte load.  Every cell that is neither
+// solid nor held takes its own rates into the collision; with the closure tau0 of subgrid_tau is 1 / rw of the cell.  Compile-time, so
+// the kernels of a context without a field are the instantiations they were.  (No buoyant twin: the two refuse each other.)
+constexpr int WALL_RELAX = 16, WALL_REST_RELAX = WALL_REST | WALL_RELAX, WALL_MOVE_RELAX = WALL_MOVE | WALL_RELAX, WALL_SHAPE_RELAX = WALL_SHAPE | WALL_RELAX,
+              WALL_REST_SGS_RELAX = WALL_REST_SGS | WALL_RELAX, WALL_MOVE_SGS_RELAX = WALL_MOVE_SGS | WALL_RELAX,
+              WALL_SHAPE_SGS_RELAX = WALL_SHAPE_SGS | WALL_RELAX;
+constexpr bool wall_relax(int wall) { return (wall & WALL_RELAX) != 0; }
+template <typename R>
+struct WallArg<R, WALL_REST_RELAX> {
+    static constexpr int MODE = WALL_REST_RELAX;
+    const R* rw;
+    const R* rwm;
+};
+template <typename R>
+struct WallArg<R, WALL_MOVE_RELAX> {
+    static constexpr int MODE = WALL_MOVE_RELAX;
+    const int32_t* cell_row;
+    const R* delta;
+    const R* rw;
+    const R* rwm;
+};
+template <typename R>
+struct WallArg<R, WALL_SHAPE_RELAX> {
+    static constexpr int MODE = WALL_SHAPE_RELAX;
+    ShapeTable<R> sh;
+    const R* rw;
+    const R* rwm;
+};
+template <typename R>
+struct WallArg<R, WALL_REST_SGS_RELAX> {
+    static constexpr int MODE = WALL_REST_SGS_RELAX;
+    R sgs;
+    const R* rw;
+    const R* rwm;
+};
+template <typename R>
+struct WallArg<R, WALL_MOVE_SGS_RELAX> {
+    static constexpr int MODE = WALL_MOVE_SGS_RELAX;
+    const int32_t* cell_row;
+    const R* delta;
+    R sgs;
+    const R* rw;
+    const R* rwm;
+};
+template <typename R>
+struct WallArg<R, WALL_SHAPE_SGS_RELAX> {
+    static constexpr int MODE = WALL_SHAPE_SGS_RELAX;
+    ShapeTable<R> sh;
+    R sgs;
+    const R* rw;
+    const R* rwm;
+};
+
 // Gather the post-stream, post-wall-rule populations of cell (x, y) from a lattice that
 // holds post-collision values (+ kept slots + parked wall densities); raw != 0: the lattice
 // holds plain populations (state just set by the host), nothing to stream.  PROM: the wall rules' equilibrium in the promoted form.
@@ -755,10 +821,13 @@ __device__ __forceinline__ void gather(const R* __restrict__ src, const Geo& geo
 // delta of WALL_MOVE, in the raw first step too.
 // SGS (k_step_generic_wall in a mode with WALL_SGS alone; WALL is then the base mode), sgs: the sub-grid closure -- w_nu = subgrid_omega of
 // the gathered populations and the moments of the cell, k = sgs.
-template <typename R, int COLL, int SEM, bool TURB, typename AS, typename AD, int WALL = WALL_REST, bool SGS = false>
+// RLX (k_step_generic_wall in a mode with WALL_RELAX alone), rw, rwm: the cell's own rates of a relaxation field -- rw where the lattice's
+// w_nu stands (with SGS: as the closure's omega), rwm as TRT's odd rate.
+template <typename R, int COLL, int SEM, bool TURB, typename AS, typename AD, int WALL = WALL_REST, bool SGS = false, bool RLX = false>
 __device__ __forceinline__ void update_cell_a(const R* __restrict__ src, const AS& as, R* __restrict__ dst, const AD& ad, const Geo& geo,
                                               const Relax<R>& w0, int raw, int x, int y, const R* __restrict__ lnk = nullptr,
-                                              WallArg<R, WALL> wa = WallArg<R, WALL>{}, Drive<R> dr = Drive<R>{}, R sgs = R(0)) {
+                                              WallArg<R, WALL> wa = WallArg<R, WALL>{}, Drive<R> dr = Drive<R>{}, R sgs = R(0), R rw = R(0),
+                                              R rwm = R(0)) {
     // lnk (SEM_SOLID with an LDS window as the source): plane K_LINK of the lattice, see link_word
     const int X = geo.nx, Y = geo.NY, gy = geo.y0 + y;
     if (SEM == SEM_SOLID && (link_word<R, AS>(src, as, geo, lnk, x, y) & (LINK_SOLID | LINK_HOLD))) return;   // a solid cell, or a hold cell, is never updated
@@ -780,8 +849,14 @@ __device__ __forceinline__ void update_cell_a(const R* __restrict__ src, const A
     R w_nu = w0.w_nu;
     if (TURB) w_nu = smagorinsky_omega<R, coll_is_fast(COLL), coll_is_prom(COLL)>(g, src[K_QEQ * as.plane + me_s], src[K_RHO * as.plane + me_s], w0.w_nu);
     macros<R, coll_is_fast(COLL), SEM>(g, x, gy, X, Y, w.uLB, rho, ux, uy);
-    if constexpr (SGS) w_nu = subgrid_omega<R, coll_is_fast(COLL)>(g, rho, ux, uy, w0.w_nu, sgs);
-    equ_collide<R, COLL, TURB>(g, rho, ux, uy, w, w_nu, out, q2, COLL == C_MRT_FAST && gy == 0 && !sem_is_bb(SEM));
+    if constexpr (RLX) {
+        w_nu = rw;
+        if constexpr (SGS) w_nu = subgrid_omega<R, coll_is_fast(COLL)>(g, rho, ux, uy, rw, sgs);
+        equ_collide<R, COLL, TURB, true>(g, rho, ux, uy, w, w_nu, out, q2, COLL == C_MRT_FAST && gy == 0 && !sem_is_bb(SEM), rwm);
+    } else {
+        if constexpr (SGS) w_nu = subgrid_omega<R, coll_is_fast(COLL)>(g, rho, ux, uy, w0.w_nu, sgs);
+        equ_collide<R, COLL, TURB>(g, rho, ux, uy, w, w_nu, out, q2, COLL == C_MRT_FAST && gy == 0 && !sem_is_bb(SEM));
+    }
     if (TURB) {
         dst[K_QEQ * ad.plane + me] = q2;
         dst[K_RHO * ad.plane + me] = rho;
@@ -916,11 +991,15 @@ __device__ __forceinline__ void update_vec(const R* __restrict__ src, R* __restr
 // hold garbage -- harmless.  Per-cell arithmetic is the same operation sequence as update_cell,
 // so the result is bit-identical to two single steps.
 // ------------------------------------------------------------------------------------------
-template <typename R, int COLL, int V, bool TURB, bool SGS = false>
+template <typename R, int COLL, int V, bool TURB, bool SGS = false, bool RLX = false>
 __device__ __forceinline__ void collide_vec(const typename VecT<R, V>::type (&in)[Q], const Relax<R>& w0,
                                             typename VecT<R, V>::type (&outv)[Q],
                                             typename VecT<R, V>::type& hq, typename VecT<R, V>::type& hr, bool wl = false, bool wr = false,
-                                            int kind = 0, R sgs = R(0)) {
+                                            int kind = 0, R sgs = R(0), typename VecT<R, V>::type rw = typename VecT<R, V>::type{},
+                                            typename VecT<R, V>::type rwm = typename VecT<R, V>::type{}) {
+    // RLX (k_step_solid in a mode with WALL_RELAX alone, kind 0): rw, rwm -- the V cells' own rates of a relaxation field, in the lane
+    // order of in[k] (the packed halves p = 0 / 1 take .xy / .zw of them as they do of in[k]): rw where the lattice's w_nu stands (with
+    // SGS: as the closure's omega), rwm as TRT's odd rate
     // SGS (k_step_solid in a mode with WALL_SGS alone, kind 0): the sub-grid closure, w_nu = subgrid_omega of the cell's populations and
     // moments with k = sgs -- the MRT operators then form the velocity too
     // hq, hr: Smagorinsky history of the cells (in: previous step, out: this step); untouched unless TURB
@@ -950,8 +1029,15 @@ __device__ __forceinline__ void collide_vec(const typename VecT<R, V>::type (&in
                     ux = f32x2(kind == 1 ? w0.uLB : 0.f); uy = f32x2(0.f);
                 }
             }
-            if constexpr (SGS) w_nu = subgrid_omega<f32x2, coll_is_fast(COLL)>(g, rho, ux, uy, w0.w_nu, sgs);
-            equ_collide<f32x2, COLL, TURB>(g, rho, ux, uy, w0, w_nu, out, q2, COLL == C_MRT_FAST && kind == 1);
+            if constexpr (RLX) {
+                const f32x2 rwp = p == 0 ? rw.xy : rw.zw, rmp = p == 0 ? rwm.xy : rwm.zw;
+                w_nu = rwp;
+                if constexpr (SGS) w_nu = subgrid_omega<f32x2, coll_is_fast(COLL), f32x2>(g, rho, ux, uy, rwp, sgs);
+                equ_collide<f32x2, COLL, TURB, true>(g, rho, ux, uy, w0, w_nu, out, q2, COLL == C_MRT_FAST && kind == 1, rmp);
+            } else {
+                if constexpr (SGS) w_nu = subgrid_omega<f32x2, coll_is_fast(COLL)>(g, rho, ux, uy, w0.w_nu, sgs);
+                equ_collide<f32x2, COLL, TURB>(g, rho, ux, uy, w0, w_nu, out, q2, COLL == C_MRT_FAST && kind == 1);
+            }
 #pragma unroll
             for (int k = 0; k < Q; ++k) {
                 if (p == 0) outv[k].xy = out[k];
@@ -985,8 +1071,14 @@ __device__ __forceinline__ void collide_vec(const typename VecT<R, V>::type (&in
                     ux = kind == 1 ? w0.uLB : (R)0; uy = (R)0;
                 }
             }
-            if constexpr (SGS) w_nu = subgrid_omega<R, coll_is_fast(COLL)>(g, rho, ux, uy, w0.w_nu, sgs);
-            equ_collide<R, COLL, TURB>(g, rho, ux, uy, w0, w_nu, out, q2, COLL == C_MRT_FAST && kind == 1);
+            if constexpr (RLX) {
+                w_nu = rw[c];
+                if constexpr (SGS) w_nu = subgrid_omega<R, coll_is_fast(COLL)>(g, rho, ux, uy, rw[c], sgs);
+                equ_collide<R, COLL, TURB, true>(g, rho, ux, uy, w0, w_nu, out, q2, COLL == C_MRT_FAST && kind == 1, rwm[c]);
+            } else {
+                if constexpr (SGS) w_nu = subgrid_omega<R, coll_is_fast(COLL)>(g, rho, ux, uy, w0.w_nu, sgs);
+                equ_collide<R, COLL, TURB>(g, rho, ux, uy, w0, w_nu, out, q2, COLL == C_MRT_FAST && kind == 1);
+            }
 #pragma unroll
             for (int k = 0; k < Q; ++k) outv[k][c] = out[k];
             if (TURB) { hq[c] = q2; hr[c] = rho; }

@@ -173,6 +173,44 @@ __global__ __launch_bounds__(BLK) void k_export_tau_subgrid(Fields<R, SEM_SOLID,
         if (x0 + xx < geo.nx && y0 + yy < geo.ny) stage[(long long)(x0 + xx) * geo.ny + y0 + yy] = t[xx][yy];
 }
 
+// ... with a relaxation field (lbm_set_relaxation_field; rw: the plane of the cells' viscous rates, buoy_at): a cell that is neither solid
+// nor held reports 1 / rw of the cell in the lattice type or, SGS (the closure with k), subgrid_tau on that rate; the others tau0.
+template <typename R, bool FAST, bool SHAPE, bool SGS>
+__global__ __launch_bounds__(BLK) void k_export_tau_relax(Fields<R, SEM_SOLID, false, SHAPE> f, Relax<R> w, Batch<R> bt, R k, const R* __restrict__ rw,
+                                                          R* __restrict__ stage) {
+    const Geo& geo = f.geo;
+    constexpr int TRX = trx<R>(), RY = BLK / TRX;
+    __shared__ R t[TRX][33];
+    const long long n = (long long)geo.nx * geo.ny;
+    const auto lat = f.lattice(blockIdx.z);
+    if (bt.w) w = bt.w[blockIdx.z];
+    stage += blockIdx.z * n;
+    rw += blockIdx.z * buoy_elems(geo);
+    const int x0 = blockIdx.x * TRX, y0 = blockIdx.y * 32;
+    const int tx = threadIdx.x % TRX, x = x0 + tx;
+    for (int ty = threadIdx.x / TRX; ty < 32; ty += RY) {
+        const int y = y0 + ty;
+        if (x >= geo.nx || y >= geo.ny) continue;
+        R tau = (R)1.0 / w.w_nu;
+        if (!((int)lat.src[K_LINK * geo.plane + geo.at(x, y)] & (LINK_SOLID | LINK_HOLD))) {
+            const R wc = rw[buoy_at(geo, x, y)];
+            if constexpr (SGS) {
+                R g[Q], rho, ux, uy;
+                lat.populations(x, y, g);
+                macros<R, FAST, SEM_SOLID>(g, x, geo.y0 + y, geo.nx, geo.NY, lat.uLB, rho, ux, uy);
+                tau = subgrid_tau<R, FAST>(g, rho, ux, uy, wc, k);
+            } else {
+                tau = (R)1.0 / wc;
+            }
+        }
+        t[tx][ty] = tau;
+    }
+    __syncthreads();
+    const int yy = threadIdx.x & 31, xb = threadIdx.x >> 5;
+    for (int xx = xb; xx < TRX; xx += BLK / 32)
+        if (x0 + xx < geo.nx && y0 + yy < geo.ny) stage[(long long)(x0 + xx) * geo.ny + y0 + yy] = t[xx][yy];
+}
+
 // Sum over the slab of ux + uy of the view's macroscopic state (what k_export_macro would write), in double:
 // partial[blockIdx.z * gridDim.x + blockIdx.x] = the block's sum; k_reduce_final adds the partial sums of each lattice in
 // index order -- a fixed summation tree, so the result does not vary from run to run.

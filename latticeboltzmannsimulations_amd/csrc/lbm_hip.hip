@@ -136,6 +136,19 @@ int export_tau(lbm_ctx* c, int which) {
         using R = typename VT::R;
         if constexpr (VT::SEM == SEM_SOLID) {
             // the sub-grid closure (lbm_set_subgrid): the tau of the step that starts from the current state, lat[cur], through the view
+            // ... and with a relaxation field (lbm_set_relaxation_field) the cell's own tau0, with and without the closure
+            if (c->relax_field()) {
+                with_fields<VT>(c, c->cur, [&](auto f) {
+                    const R* const rw = c->relax_w.as<const R>();
+                    if (c->subgrid > 0.0)
+                        hipLaunchKernelGGL((k_export_tau_relax<R, coll_is_fast(VT::COLL), decltype(f)::SHAPED, true>), grid_tiles<R>(c), dim3(BLK), 0, c->s_compute, f,
+                                           relax_of<R>(c->p), batch_of<R>(c), sgs_k<R>(c), rw, c->stage.as<R>());
+                    else
+                        hipLaunchKernelGGL((k_export_tau_relax<R, coll_is_fast(VT::COLL), decltype(f)::SHAPED, false>), grid_tiles<R>(c), dim3(BLK), 0, c->s_compute, f,
+                                           relax_of<R>(c->p), batch_of<R>(c), (R)0, rw, c->stage.as<R>());
+                });
+                return;
+            }
             if (c->subgrid > 0.0) {
                 with_fields<VT>(c, c->cur, [&](auto f) {
                     hipLaunchKernelGGL((k_export_tau_subgrid<R, coll_is_fast(VT::COLL), decltype(f)::SHAPED>), grid_tiles<R>(c), dim3(BLK), 0, c->s_compute, f,

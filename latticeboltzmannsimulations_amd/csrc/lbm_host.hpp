@@ -56,7 +56,7 @@
 #include "lbm_devmem.hpp"
 #include "lbm_bodies.hpp"
 #include "lbm_periodic.hpp"
-#include "lbm_solid.hpp"  // k_step_solid, k_step_generic_wall, extern (compiled per wall mode in lbm_solid{,_move,_shape,_buoy}_f32/f64.hip, lbm_solid_sgs*)
+#include "lbm_solid.hpp"  // k_step_solid, k_step_generic_wall, extern (compiled per wall mode in lbm_solid{,_move,_shape,_buoy}_f32/f64.hip, lbm_solid_sgs*, lbm_solid_relax*)
 #include "lbm_fields.hpp" // the view of the exported state and the kernels of the field export
 #include "lbm_inst.hpp"   // the kernels, and extern template declarations of the multi-step ones (compiled in lbm_{tiles,stream*}_f32/f64.hip)
 
@@ -305,6 +305,11 @@ struct lbm_ctx {
     double drive[2] = {0.0, 0.0};   // the driving force (lbm_set_driving_force): (fx, fy); no geometry, so it outlives every obstacle call
     bool driven() const { return drive[0] != 0.0 || drive[1] != 0.0; }
     double subgrid = 0.0;           // the sub-grid constant Cs2 (lbm_set_subgrid), 0 without the closure; no geometry and no history either
+    // A relaxation field (lbm_set_relaxation_field), empty while none is set: relax_w the plane of the cells' viscous rates, relax_wm the
+    // plane of TRT's odd rates or empty -- read-only, in the lattice type, rows as the buoyancy plane's (buoy_at), lattice b of a batch at
+    // b * buoy_elems; ghost and pad elements hold the rate the lattice had when the field was set.  No geometry and no history.
+    DevBuf relax_w, relax_wm;
+    bool relax_field() const { return (bool)relax_w; }
     ncclComm_t comm = nullptr;
     int nranks = 1, rank = 0;
     bool loopback = false;      // diagnostic: 1-rank communicator, the slab exchanges halos with itself
@@ -433,16 +438,18 @@ dim3 grid_tiles(const lbm_ctx* c) { return dim3((c->plan.geo.nx + trx<R>() - 1) 
 // Run-time parameters -> compile-time kernel variant (real type, collision operator, semantics, Smagorinsky).
 // SGS: the sub-grid closure of an obstacle lattice (lbm_set_subgrid) -- asked for by the step launcher alone (launch_rows), which then
 // takes the wall mode's twin with WALL_SGS; every other launcher sees the variant without it.
-template <typename R_, int COLL_, int SEM_, bool TURB_, bool SGS_ = false>
+// RELAX: a relaxation field (lbm_set_relaxation_field), likewise: the twin with WALL_RELAX.
+template <typename R_, int COLL_, int SEM_, bool TURB_, bool SGS_ = false, bool RELAX_ = false>
 struct Variant {
     using R = R_;
     static constexpr int COLL = COLL_, SEM = SEM_;
-    static constexpr bool TURB = TURB_, SGS = SGS_;
+    static constexpr bool TURB = TURB_, SGS = SGS_, RELAX = RELAX_;
 };
+constexpr int STEP_SGS = 1, STEP_RELAX = 2;   // what the step launcher asks of dispatch()
 
 // arith = promoted: fp32 takes the promoted operators, fp64 the strict ones (the promotion's casts are no-ops there).
 template <typename F>
-void dispatch(const lbm_params& p, F&& f, bool subgrid = false) {   // subgrid: the step of a context with a sub-grid constant (SEM_SOLID only)
+void dispatch(const lbm_params& p, F&& f, int step = 0) {   // step: STEP_SGS -- the step of a context with a sub-grid constant, STEP_RELAX -- with a relaxation field (SEM_SOLID only)
     auto by_sem = [&](auto real, auto coll) {
         using R = decltype(real);
         constexpr int C = decltype(coll)::value;
@@ -454,7 +461,9 @@ void dispatch(const lbm_params& p, F&& f, bool subgrid = false) {   // subgrid: 
             if (p.semantics == LBM_SEM_MRT_PY) f(Variant<R, CS, SEM_PY, false>{});   // (arith = fast: MRT_GPU semantics only)
             else if (p.semantics == LBM_SEM_BOUNCE_BACK) f(Variant<R, C, SEM_BB, false>{});   // (strict and fast; no closure: validate_params)
             else if (p.semantics == LBM_SEM_BOUNCE_BACK_SOLID) {   // (the same, one step per launch)
-                if (subgrid) f(Variant<R, C, SEM_SOLID, false, true>{});
+                if (step == (STEP_SGS | STEP_RELAX)) f(Variant<R, C, SEM_SOLID, false, true, true>{});
+                else if (step == STEP_RELAX) f(Variant<R, C, SEM_SOLID, false, false, true>{});
+                else if (step == STEP_SGS) f(Variant<R, C, SEM_SOLID, false, true>{});
                 else f(Variant<R, C, SEM_SOLID, false>{});
             }
             else if (p.turb) f(Variant<R, C, SEM_GPU, true>{});
@@ -532,6 +541,23 @@ void with_wall(const lbm_ctx* c, F&& launch) {
 template <typename VT, typename F>
 void with_wall_step(const lbm_ctx* c, F&& launch) {
     using R = typename VT::R;
+    if constexpr (VT::RELAX) {   // (a relaxation field: the mode's twin with WALL_RELAX, which carries the two planes; with the closure, k too)
+        const ShapeTables& sh = c->obs.shaped;
+        const MotionTables& mv = c->obs.moving;
+        const R* const rw = c->relax_w.as<const R>();
+        const R* const rwm = c->relax_wm.as<const R>();
+        if constexpr (VT::SGS) {
+            const R k = sgs_k<R>(c);
+            if (sh.base) launch(WallArg<R, WALL_SHAPE_SGS_RELAX>{sh.template table<R>(), k, rw, rwm}, sh.link_q);
+            else if (mv.base) launch(WallArg<R, WALL_MOVE_SGS_RELAX>{mv.cell_row, (const R*)mv.delta, k, rw, rwm}, mv.link_delta);
+            else launch(WallArg<R, WALL_REST_SGS_RELAX>{k, rw, rwm}, (const double*)nullptr);
+        } else {
+            if (sh.base) launch(WallArg<R, WALL_SHAPE_RELAX>{sh.template table<R>(), rw, rwm}, sh.link_q);
+            else if (mv.base) launch(WallArg<R, WALL_MOVE_RELAX>{mv.cell_row, (const R*)mv.delta, rw, rwm}, mv.link_delta);
+            else launch(WallArg<R, WALL_REST_RELAX>{rw, rwm}, (const double*)nullptr);
+        }
+        return;
+    }
     if constexpr (VT::SGS) {
         const ShapeTables& sh = c->obs.shaped;
         const MotionTables& mv = c->obs.moving;
@@ -548,8 +574,8 @@ void with_wall_step(const lbm_ctx* c, F&& launch) {
 }
 // A launcher's body: f(Variant) enqueues the kernels of the context's variant, then the launch error check
 template <typename F>
-int launch_variant(lbm_ctx* c, F&& f, bool subgrid = false) {
-    dispatch(c->p, f, subgrid);
+int launch_variant(lbm_ctx* c, F&& f, int step = 0) {
+    dispatch(c->p, f, step);
     HIP_TRY(c, hipGetLastError());
     return LBM_OK;
 }

@@ -67,7 +67,7 @@ int launch_rows(lbm_ctx* c, int from, int to, int row0, int stride, int nrows, h
         else
             hipLaunchKernelGGL((k_step_generic<R, VT::COLL, VT::SEM, VT::TURB>), grid_rows(c, nrows), dim3(BLK), 0, s, src, dst, c->plan.geo,
                                relax_of<R>(c->p), batch_of<R>(c), raw, row0, stride);
-    }, c->subgrid > 0.0);   // (lbm_set_subgrid: dispatch picks the variant with the closure)
+    }, (c->subgrid > 0.0 ? STEP_SGS : 0) | (c->relax_field() ? STEP_RELAX : 0));   // (lbm_set_subgrid, lbm_set_relaxation_field: dispatch picks the variant)
 }
 
 // One single step on the frame of width W, lat[from] -> lat[to] (one pass of a multi-step; never a raw lattice).

@@ -557,6 +557,10 @@ int lbm_describe(const lbm_ctx* c, char* buf, size_t len) {
         const int m = std::snprintf(buf + n, len - (size_t)n, " subgrid=%.17g", c->subgrid);
         if (m > 0) n = std::min<int>(n + m, (int)len - 1);
     }
+    if (c->relax_field()) {   // (lbm_set_relaxation_field: the flow steps run the twins of their kernels that read the planes)
+        const int m = std::snprintf(buf + n, len - (size_t)n, "%s", c->relax_wm ? " relax_field+m" : " relax_field");
+        if (m > 0) n = std::min<int>(n + m, (int)len - 1);
+    }
     return n;
 }
 

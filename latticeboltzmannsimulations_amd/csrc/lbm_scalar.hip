@@ -258,6 +258,9 @@ int lbm_set_buoyancy(lbm_ctx* c, double ax, double ay, double c_ref) {
     if (on && c->subgrid > 0.0)
         return fail(c, LBM_ERR_STATE, "lbm_set_buoyancy: a sub-grid constant is set (a buoyant flow with the closure needs an eddy diffusivity for the "
                                       "scalar, which there is none; clear it with lbm_set_subgrid(c, 0) first)");
+    if (on && c->relax_field())
+        return fail(c, LBM_ERR_STATE, "lbm_set_buoyancy: a relaxation field is set (the buoyant kernels read no rate planes: every such pairing is one more "
+                                      "set of kernel twins; clear it with lbm_set_relaxation_field(c, NULL, NULL) first)");
     HIP_TRY(c, hipSetDevice(c->p.device));
     int rc = sync_all(c);
     if (rc) return rc;

@@ -291,6 +291,46 @@ static int periodic_hold_all(lbm_ctx* c, Obstacles& next, bool px, bool py, cons
     }
     return LBM_OK;
 }
+// One plane of a relaxation field from the caller's [B][nx][ny]: rows as the buoyancy plane's (buoy_at), each value rounded once to the
+// lattice type; ghost and pad elements hold `fill`.
+template <typename R>
+static std::vector<R> relax_plane(const lbm_ctx* c, const double* v, double fill) {
+    const Geo& g = c->plan.geo;
+    const size_t per = (size_t)buoy_elems(g), n = (size_t)g.nx * g.ny;
+    std::vector<R> h(per * c->plan.batch, (R)fill);
+    for (int b = 0; b < c->plan.batch; ++b)
+        for (int x = 0; x < g.nx; ++x)
+            for (int y = 0; y < g.ny; ++y) h[b * per + (size_t)buoy_at(g, x, y)] = (R)v[b * n + (size_t)x * g.ny + y];
+    return h;
+}
+template <typename R>
+static int relax_upload(lbm_ctx* c, const double* v, double fill, const char* what, DevBuf* out) {
+    const std::vector<R> h = relax_plane<R>(c, v, fill);
+    DevBuf d;
+    const int rc = alloc_ok(c, d.alloc(h.size() * sizeof(R), what));
+    if (rc) return rc;
+    HIP_TRY(c, hipMemcpy(d.get(), h.data(), h.size() * sizeof(R), hipMemcpyHostToDevice));
+    *out = std::move(d);
+    return LBM_OK;
+}
+template <typename R>
+static int relax_download(lbm_ctx* c, const DevBuf& d, double* out) {
+    const Geo& g = c->plan.geo;
+    const size_t per = (size_t)buoy_elems(g), n = (size_t)g.nx * g.ny;
+    std::vector<R> h(per * c->plan.batch);
+    HIP_TRY(c, hipMemcpy(h.data(), d.get(), h.size() * sizeof(R), hipMemcpyDeviceToHost));
+    for (int b = 0; b < c->plan.batch; ++b)
+        for (int x = 0; x < g.nx; ++x)
+            for (int y = 0; y < g.ny; ++y) out[b * n + (size_t)x * g.ny + y] = (double)h[b * per + (size_t)buoy_at(g, x, y)];
+    return LBM_OK;
+}
+// The first value that is not finite or not in (0, 2): its index, or -1
+static long long relax_bad(const double* v, size_t n) {
+    for (size_t i = 0; i < n; ++i)
+        if (!(std::isfinite(v[i]) && v[i] > 0.0 && v[i] < 2.0)) return (long long)i;
+    return -1;
+}
+
 }  // namespace lbmhost
 
 using namespace lbmhost;
@@ -461,6 +501,69 @@ int lbm_get_subgrid(lbm_ctx* c, double* cs2_out) {
     if (!c) return LBM_ERR_INVALID;
     if (cs2_out) *cs2_out = c->subgrid;
     return LBM_OK;
+}
+
+int lbm_set_relaxation_field(lbm_ctx* c, const double* omega, const double* omegam) {
+    if (!c) return LBM_ERR_INVALID;
+    if (!omega) {
+        if (omegam) return fail(c, LBM_ERR_INVALID, "lbm_set_relaxation_field: omegam without omega (the field is cleared with both NULL)");
+        if (!c->relax_field()) return LBM_OK;
+        HIP_TRY(c, hipSetDevice(c->p.device));
+        const int rc = sync_all(c);   // (the steps enqueued read the planes)
+        if (rc) return rc;
+        c->relax_w = DevBuf{};
+        c->relax_wm = DevBuf{};
+        return LBM_OK;
+    }
+    int rc = need_solid(c, "lbm_set_relaxation_field");
+    if (rc) return rc;
+    if (c->plan.solid_tiles)
+        return fail(c, LBM_ERR_STATE, "lbm_set_relaxation_field: the tile kernel reads no rate planes (LBM_FLAG_SOLID_TILES takes none; create the "
+                                      "context without the flag)");
+    if (c->scalar.buoyant)
+        return fail(c, LBM_ERR_STATE, "lbm_set_relaxation_field: buoyancy is set (the buoyant kernels read no rate planes: every such pairing is one "
+                                      "more set of kernel twins; clear it with lbm_set_buoyancy(c, 0, 0, 0) first)");
+    if (omegam && c->p.collision != LBM_TRT)
+        return fail(c, LBM_ERR_STATE, "lbm_set_relaxation_field: omegam is TRT's odd rate and this context's collision is not TRT (pass NULL: MRT's "
+                                      "other rates stay the lattice's)");
+    const Geo& g = c->plan.geo;
+    const size_t n = (size_t)g.nx * g.ny, all = n * c->plan.batch;
+    for (const double* v : {omega, omegam}) {
+        if (!v) continue;
+        const long long bad = relax_bad(v, all);
+        if (bad < 0) continue;
+        const size_t cell = (size_t)bad % n;
+        char val[40];
+        std::snprintf(val, sizeof val, "%.17g", v[bad]);
+        return fail(c, LBM_ERR_INVALID, std::string("lbm_set_relaxation_field: ") + (v == omega ? "omega" : "omegam") + " of lattice " +
+                                            std::to_string((size_t)bad / n) + ", cell (" + std::to_string(cell / g.ny) + ", " + std::to_string(cell % g.ny) +
+                                            ") is " + val + ": every rate must be finite and in (0, 2)");
+    }
+    HIP_TRY(c, hipSetDevice(c->p.device));
+    rc = sync_all(c);
+    if (rc) return rc;
+    DevBuf w, wm;
+    const bool f32 = c->p.dtype == LBM_F32;
+    rc = f32 ? relax_upload<float>(c, omega, c->p.omega, "relaxation field", &w) : relax_upload<double>(c, omega, c->p.omega, "relaxation field", &w);
+    if (rc == LBM_OK && omegam)
+        rc = f32 ? relax_upload<float>(c, omegam, c->p.omegam, "relaxation field (omegam)", &wm)
+                 : relax_upload<double>(c, omegam, c->p.omegam, "relaxation field (omegam)", &wm);
+    if (rc) return rc;
+    c->relax_w = std::move(w);
+    c->relax_wm = std::move(wm);
+    return LBM_OK;
+}
+
+int lbm_get_relaxation_field(lbm_ctx* c, double* omega_out, double* omegam_out) {
+    if (!c) return LBM_ERR_INVALID;
+    if (!c->relax_field()) return 0;
+    HIP_TRY(c, hipSetDevice(c->p.device));
+    const bool f32 = c->p.dtype == LBM_F32;
+    int rc = LBM_OK;
+    if (omega_out) rc = f32 ? relax_download<float>(c, c->relax_w, omega_out) : relax_download<double>(c, c->relax_w, omega_out);
+    if (rc == LBM_OK && omegam_out && c->relax_wm)
+        rc = f32 ? relax_download<float>(c, c->relax_wm, omegam_out) : relax_download<double>(c, c->relax_wm, omegam_out);
+    return rc ? rc : 1;
 }
 
 int lbm_get_open_cells(lbm_ctx* c, uint8_t* hold_out, double* f_out) {

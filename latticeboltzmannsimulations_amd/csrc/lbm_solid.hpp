@@ -35,6 +35,12 @@
 //               store more: collide_vec forms every lane's tau from the lane's gathered populations and its moments -- the MRT operators
 //               then form the velocity too -- and takes 1 / tau into the collision in the place of the lattice's rate.  Solid and hold lanes
 //               compute a tau that nobody uses and are pinned as ever.  Instantiated in lbm_solid_sgs{,_move,_shape}_f32/f64.hip.
+//   relaxation  (the mode | WALL_RELAX, with and without WALL_SGS; lbm_set_relaxation_field) one more aligned 16-byte load per plane next to
+//   field       the link words -- the cells' viscous rates, and TRT's odd rates where that plane is set (a wave-uniform test of the pointer;
+//               the lattice's w_m in every lane otherwise): collide_vec takes each lane's own rates into the collision, with the closure
+//               as the closure's omega.  Solid and hold lanes load rates that nobody uses and are pinned as ever; the force and the wall
+//               deltas are added after the collision, unchanged.  Instantiated in lbm_solid_relax{,_move,_shape}_f32/f64.hip and
+//               lbm_solid_relax_sgs{,_move,_shape}_f32/f64.hip.
 constexpr int SOLID_DRIVE = 2;
 template <typename R, int COLL, bool NT, int WALL>
 __global__ __launch_bounds__(BLK) void k_step_solid(const R* __restrict__ src, R* __restrict__ dst, Geo geo, Relax<R> w, Batch<R> bt, int raw_drive,
@@ -53,6 +59,17 @@ __global__ __launch_bounds__(BLK) void k_step_solid(const R* __restrict__ src, R
     const T lk = vload<R, V, NT>(src + K_LINK * geo.plane + me, true);
     T cpv;   // (buoyancy: the cells' values of the buoyancy plane)
     if constexpr (wall_buoyant(WALL)) cpv = vload<R, V, NT>(wa.by.cp + buoy_at(geo, x0, y), true);
+    T rwv, rmv;   // (a relaxation field: the cells' own rates)
+    if constexpr (wall_relax(WALL)) {
+        const long long at = (long long)blockIdx.y * buoy_elems(geo) + buoy_at(geo, x0, y);
+        rwv = vload<R, V, false>(wa.rw + at, true);
+        if (wa.rwm) {
+            rmv = vload<R, V, false>(wa.rwm + at, true);
+        } else {
+#pragma unroll
+            for (int c = 0; c < V; ++c) rmv[c] = w.w_m;
+        }
+    }
     int lw[V], any = 0;
 #pragma unroll
     for (int c = 0; c < V; ++c) {
@@ -125,7 +142,9 @@ __global__ __launch_bounds__(BLK) void k_step_solid(const R* __restrict__ src, R
             }
         }
     }
-    if constexpr (wall_subgrid(WALL)) collide_vec<R, COLL, V, false, true>(in, w, outv, hq, hr, false, false, 0, wa.sgs);
+    if constexpr (wall_relax(WALL) && wall_subgrid(WALL)) collide_vec<R, COLL, V, false, true, true>(in, w, outv, hq, hr, false, false, 0, wa.sgs, rwv, rmv);
+    else if constexpr (wall_relax(WALL)) collide_vec<R, COLL, V, false, false, true>(in, w, outv, hq, hr, false, false, 0, R(0), rwv, rmv);
+    else if constexpr (wall_subgrid(WALL)) collide_vec<R, COLL, V, false, true>(in, w, outv, hq, hr, false, false, 0, wa.sgs);
     else collide_vec<R, COLL, V, false>(in, w, outv, hq, hr);
     // the driving force (lbm_set_driving_force), a uniform run-time test: every lane adds F_k, one add in the lattice type; the solid and
     // the hold lanes are pinned below, so the sums of fluid lanes alone are stored
@@ -223,6 +242,22 @@ __global__ __launch_bounds__(BLK) void k_step_generic_wall(const R* __restrict__
         for (int k = 0; k < 8; ++k) d.f[k] = dr.f[k] + wa.by.b[k] * t;
         d.on = 1;
         update_cell_a<R, COLL, SEM_SOLID, false, Geo, Geo, BASE>(src, geo, dst, geo, geo, w, raw, x, y, nullptr, wb, d);
+    } else if constexpr (wall_relax(WALL)) {
+        // a relaxation field: update_cell_a in the base mode with the cell's own rates (and the closure, where the mode has it)
+        constexpr int BASE = wall_base(WALL);
+        WallArg<R, BASE> wb{};
+        if constexpr (BASE == WALL_MOVE) {
+            wb.cell_row = wa.cell_row;
+            wb.delta = wa.delta;
+        }
+        if constexpr (BASE == WALL_SHAPE) wb.sh = wa.sh;
+        wall_batch(wb, blockIdx.z, geo);
+        const long long at = (long long)blockIdx.z * buoy_elems(geo) + buoy_at(geo, x, y);
+        const R rw = wa.rw[at], rwm = wa.rwm ? wa.rwm[at] : w.w_m;
+        if constexpr (wall_subgrid(WALL))
+            update_cell_a<R, COLL, SEM_SOLID, false, Geo, Geo, BASE, true, true>(src, geo, dst, geo, geo, w, raw, x, y, nullptr, wb, dr, wa.sgs, rw, rwm);
+        else
+            update_cell_a<R, COLL, SEM_SOLID, false, Geo, Geo, BASE, false, true>(src, geo, dst, geo, geo, w, raw, x, y, nullptr, wb, dr, R(0), rw, rwm);
     } else if constexpr (wall_subgrid(WALL)) {
         // the sub-grid closure: update_cell_a in the base mode with the closure switched on
         constexpr int BASE = wall_base(WALL);
@@ -258,6 +293,18 @@ __global__ __launch_bounds__(BLK) void k_step_generic_wall(const R* __restrict__
     LBM_SX template __global__ void k_step_generic_wall<R, COLL, WALL_MOVE_SGS>(const R* __restrict__, R* __restrict__, Geo, Relax<R>, Batch<R>, int, int, int, WallArg<R, WALL_MOVE_SGS>, Drive<R>);
 #define LBM_SOLID_GENERIC_WALL_SHAPE_SGS(R, COLL) \
     LBM_SX template __global__ void k_step_generic_wall<R, COLL, WALL_SHAPE_SGS>(const R* __restrict__, R* __restrict__, Geo, Relax<R>, Batch<R>, int, int, int, WallArg<R, WALL_SHAPE_SGS>, Drive<R>);
+#define LBM_SOLID_GENERIC_WALL_REST_RELAX(R, COLL) \
+    LBM_SX template __global__ void k_step_generic_wall<R, COLL, WALL_REST_RELAX>(const R* __restrict__, R* __restrict__, Geo, Relax<R>, Batch<R>, int, int, int, WallArg<R, WALL_REST_RELAX>, Drive<R>);
+#define LBM_SOLID_GENERIC_WALL_MOVE_RELAX(R, COLL) \
+    LBM_SX template __global__ void k_step_generic_wall<R, COLL, WALL_MOVE_RELAX>(const R* __restrict__, R* __restrict__, Geo, Relax<R>, Batch<R>, int, int, int, WallArg<R, WALL_MOVE_RELAX>, Drive<R>);
+#define LBM_SOLID_GENERIC_WALL_SHAPE_RELAX(R, COLL) \
+    LBM_SX template __global__ void k_step_generic_wall<R, COLL, WALL_SHAPE_RELAX>(const R* __restrict__, R* __restrict__, Geo, Relax<R>, Batch<R>, int, int, int, WallArg<R, WALL_SHAPE_RELAX>, Drive<R>);
+#define LBM_SOLID_GENERIC_WALL_REST_SGS_RELAX(R, COLL) \
+    LBM_SX template __global__ void k_step_generic_wall<R, COLL, WALL_REST_SGS_RELAX>(const R* __restrict__, R* __restrict__, Geo, Relax<R>, Batch<R>, int, int, int, WallArg<R, WALL_REST_SGS_RELAX>, Drive<R>);
+#define LBM_SOLID_GENERIC_WALL_MOVE_SGS_RELAX(R, COLL) \
+    LBM_SX template __global__ void k_step_generic_wall<R, COLL, WALL_MOVE_SGS_RELAX>(const R* __restrict__, R* __restrict__, Geo, Relax<R>, Batch<R>, int, int, int, WallArg<R, WALL_MOVE_SGS_RELAX>, Drive<R>);
+#define LBM_SOLID_GENERIC_WALL_SHAPE_SGS_RELAX(R, COLL) \
+    LBM_SX template __global__ void k_step_generic_wall<R, COLL, WALL_SHAPE_SGS_RELAX>(const R* __restrict__, R* __restrict__, Geo, Relax<R>, Batch<R>, int, int, int, WallArg<R, WALL_SHAPE_SGS_RELAX>, Drive<R>);
 #define LBM_SOLID_ONE(R, COLL, WALL)                                                                                                                          \
     LBM_SX template __global__ void k_step_solid<R, COLL, false, WALL>(const R* __restrict__, R* __restrict__, Geo, Relax<R>, Batch<R>, int, int, int, int, int, \
                                                                        WallArg<R, WALL>, Drive<R>);                                                           \
@@ -280,4 +327,10 @@ LBM_INST_SOLID(float, WALL_MOVE_BUOY) LBM_INST_SOLID(double, WALL_MOVE_BUOY)
 LBM_INST_SOLID(float, WALL_REST_SGS) LBM_INST_SOLID(double, WALL_REST_SGS)
 LBM_INST_SOLID(float, WALL_MOVE_SGS) LBM_INST_SOLID(double, WALL_MOVE_SGS)
 LBM_INST_SOLID(float, WALL_SHAPE_SGS) LBM_INST_SOLID(double, WALL_SHAPE_SGS)
+LBM_INST_SOLID(float, WALL_REST_RELAX) LBM_INST_SOLID(double, WALL_REST_RELAX)
+LBM_INST_SOLID(float, WALL_MOVE_RELAX) LBM_INST_SOLID(double, WALL_MOVE_RELAX)
+LBM_INST_SOLID(float, WALL_SHAPE_RELAX) LBM_INST_SOLID(double, WALL_SHAPE_RELAX)
+LBM_INST_SOLID(float, WALL_REST_SGS_RELAX) LBM_INST_SOLID(double, WALL_REST_SGS_RELAX)
+LBM_INST_SOLID(float, WALL_MOVE_SGS_RELAX) LBM_INST_SOLID(double, WALL_MOVE_SGS_RELAX)
+LBM_INST_SOLID(float, WALL_SHAPE_SGS_RELAX) LBM_INST_SOLID(double, WALL_SHAPE_SGS_RELAX)
 #endif

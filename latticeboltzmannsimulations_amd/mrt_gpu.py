@@ -339,7 +339,7 @@ def run_cavity(maxIt=3000000, Re=10000.0, RT="SRT", turb=1, xsize=32 * 5, ysize=
                dtype=np.float32, semantics="mrt_gpu", device=0, quiet=False, solver_factory=None, arith="strict",
                convergence="host", vtk_correct=False, BC="EB-NEBB ", AverageFrom=None, AverageEvery=100, monitor="host",
                MonitorEvery=None, Probes=(), vortex_table=False, criterion="mean_u", residual_tol=None, residual_hits=1, solid=None,
-               solid_tiles=False, bodies=None, force_every=None, body_motion=None, solid_shape=None, subgrid=None):
+               solid_tiles=False, bodies=None, force_every=None, body_motion=None, solid_shape=None, subgrid=None, viscosity_field=None):
     """Run the lid-driven cavity like MRT_GPU.py does; returns a :class:`CavityResult`.
 
     Argument names and defaults are the module constants of MRT_GPU.py:38-58.
@@ -394,8 +394,19 @@ def run_cavity(maxIt=3000000, Re=10000.0, RT="SRT", turb=1, xsize=32 * 5, ysize=
     the reference's value is 0.025), from the first iteration on: a coarse lattice at a high Reynolds number stays finite.  Without a
     mask the cavity runs as an obstacle lattice with an empty one.  Every output iteration prints `current mean relaxation time is
     <mean of get_tau() over the fluid cells>`, and the dashboard shows the reference's "Mean relaxation time" line with it.  A passive
-    scalar would keep its molecular diffusivity.  None (default) and 0: no closure, nothing changes."""
+    scalar would keep its molecular diffusivity.  None (default) and 0: no closure, nothing changes.
+    viscosity_field (BC='BB', turb=0; with or without solid=...): nu[xsize, ysize] in lattice units, the viscosity of each cell
+    (CavitySolver.set_viscosity; viscosity.layers, viscosity.sponge) from the first iteration on; under TRT the magic parameter of the
+    solver's own rates is kept in every cell.  Without a mask the cavity runs as an obstacle lattice with an empty one.  None
+    (default): the one viscosity of Re, nothing changes."""
     cs2 = subgrid_constant(subgrid, BC, solid_tiles)
+    if viscosity_field is not None:
+        if BC.strip() != "BB" or solid_tiles:
+            raise ValueError("viscosity_field lives on the bounce-back and obstacle lattices at one step per launch: pass BC='BB' (and turb=0), "
+                             "without solid_tiles")
+        viscosity_field = np.asarray(viscosity_field, dtype=np.float64)
+        if viscosity_field.shape != (xsize, ysize):
+            raise ValueError(f"viscosity_field must have shape {(xsize, ysize)}")
     by_res, semantics = _check_arguments(criterion, residual_tol, residual_hits, monitor, MonitorEvery, convergence, AverageFrom,
                                          AverageEvery, BC, semantics, turb, solid, solid_tiles, bodies, force_every, body_motion, solid_shape)
     on_device = monitor == "device"
@@ -407,7 +418,7 @@ def run_cavity(maxIt=3000000, Re=10000.0, RT="SRT", turb=1, xsize=32 * 5, ysize=
     extra = {} if arith == "strict" else {"arith": arith}      # 'fast' / 'promoted': see CavitySolver
     if solid is not None:
         extra["solid"] = solid
-    elif cs2 is not None:      # (the closure lives on the obstacle lattices: the plain bounce-back cavity is one with an empty mask)
+    elif cs2 is not None or viscosity_field is not None:      # (the closure and the field live on the obstacle lattices: the plain bounce-back cavity is one with an empty mask)
         extra["solid"] = np.zeros((xsize, ysize), dtype=bool)
     if solid_tiles:
         extra["tuning"] = dict(solid_tiles=True)
@@ -415,11 +426,15 @@ def run_cavity(maxIt=3000000, Re=10000.0, RT="SRT", turb=1, xsize=32 * 5, ysize=
         extra["bodies"] = bodies
     solver = make(xsize, ysize, Re, RT=RT, uLB=uLB, semantics=semantics, dtype=dtype, turb=turb, device=device, **extra)
     _banner(say, Re, RT, turb, solver.relax)
-    if solid_shape is not None or body_motion is not None or cs2 is not None:
+    if solid_shape is not None or body_motion is not None or cs2 is not None or viscosity_field is not None:
         try:
             if cs2 is not None:
                 solver.set_subgrid(cs2)
                 say("Sub-grid closure is on, Cs2 = ", cs2)
+            if viscosity_field is not None:
+                rl = solver.relax
+                solver.set_viscosity(viscosity_field, (1.0 / rl["omega"] - 0.5) * (1.0 / rl["omegam"] - 0.5) if RT == "TRT" else None)
+                say("Viscosity field is on, nu from ", float(viscosity_field.min()), " to ", float(viscosity_field.max()))
             if solid_shape is not None:     # (the shape first, then the motion)
                 solver.set_shape(np.asarray(solid_shape, dtype=np.float64))
             if body_motion is not None:

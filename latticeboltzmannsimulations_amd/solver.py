@@ -218,6 +218,9 @@ class CavitySolver:
             raise RuntimeError("lbm_describe failed")
         out = {}
         for kv in buf.value.decode().split():
+            if "=" not in kv:      # (a bare word: `relax_field`, `relax_field+m`)
+                out[kv] = True
+                continue
             k, v = kv.split("=", 1)
             out[k] = int(v) if v.lstrip("-").isdigit() else v
         return out
@@ -759,6 +762,55 @@ class CavitySolver:
         self._check(self.lib.lbm_get_subgrid(self._h, ctypes.byref(cs2)), "lbm_get_subgrid")
         return cs2.value
 
+    # -- per-cell relaxation rates: a viscosity field (lbm_set_relaxation_field, lbm_get_relaxation_field) -----------------------
+    def _rate_cells(self, a, name):
+        a = np.asarray(a, dtype=np.float64)
+        if self._lead and a.shape == (self.nx, self.ny):
+            a = np.broadcast_to(a, self._lead + a.shape)
+        if a.shape != self._lead + (self.nx, self.ny):
+            raise ValueError(f"{name} must have shape {self._lead + (self.nx, self.ny)}")
+        return np.ascontiguousarray(a)
+
+    def set_relaxation_field(self, omega, omegam=None):
+        """Per-cell relaxation rates of an obstacle lattice (lbm_set_relaxation_field; solid=..., one step per launch): omega[X, Y]
+        ([B, X, Y], or [X, Y] for every lattice of a batch) is the viscous rate of each cell -- SRT's omega, TRT's omega+, MRT's
+        omega_nu -- and omegam, the same shape, TRT's omega- (None: the lattice's; a TRT solver only).  Every value in (0, 2).  The
+        lattice, the step count and the samplers stay; the field survives set_solid, set_relaxation and the other setters.  With
+        set_subgrid the closure's tau0 is 1 / omega of the cell.  A passive scalar keeps its own diffusivity; with buoyancy the call
+        is refused.  omega=None clears the field: the kernels and the bits of a solver without one."""
+        if omega is None:
+            if omegam is not None:
+                raise ValueError("omegam without omega")
+            self._check(self.lib.lbm_set_relaxation_field(self._h, None, None), "lbm_set_relaxation_field")
+            return self
+        w = self._rate_cells(omega, "omega")
+        wm = None if omegam is None else self._rate_cells(omegam, "omegam")
+        self._check(self.lib.lbm_set_relaxation_field(self._h, w.ctypes.data, None if wm is None else wm.ctypes.data), "lbm_set_relaxation_field")
+        return self
+
+    @property
+    def relaxation_field(self):
+        """(omega, omegam) as the device holds them (rounded to the lattice type), omegam None without that plane; None without a field."""
+        if self._h is None:
+            return None
+        w = np.zeros(self._lead + (self.nx, self.ny))
+        wm = np.full(self._lead + (self.nx, self.ny), np.nan)
+        rc = self.lib.lbm_get_relaxation_field(self._h, w.ctypes.data, wm.ctypes.data)
+        if rc == 0:
+            return None
+        if rc != 1:
+            self._check(rc, "lbm_get_relaxation_field")
+        return w, (None if np.isnan(wm).all() else wm)
+
+    def set_viscosity(self, nu, magic=None):
+        """The viscosity of each cell in lattice units, nu[X, Y] or [B, X, Y] ([X, Y] is broadcast over a batch): omega = 1 / (3 nu +
+        1/2) (viscosity.rates).  magic=L on a TRT solver: omega- = 1 / (1/2 + L / (3 nu)) per cell as well, so that the magic parameter
+        (1/omega+ - 1/2)(1/omega- - 1/2) = L holds in every cell.  None clears the field."""
+        if nu is None:
+            return self.set_relaxation_field(None)
+        from .viscosity import rates
+        return self.set_relaxation_field(*rates(nu, magic))
+
     # -- a passive scalar: temperature or dye (lbm_scalar_*) ---------------------------------------------------------------
     def _cells(self, a, name, fill=None):
         """A float64 [X, Y] array as the scalar calls take it; a number fills the lattice."""
@@ -912,6 +964,9 @@ class CavitySolver:
             out.update(driving_force=np.array(self.driving_force))
         if self._h is not None and self.subgrid > 0.0:
             out.update(subgrid=np.float64(self.subgrid))
+        rf = self.relaxation_field if self.has_solid else None
+        if rf is not None:
+            out.update(relax_omega=rf[0], **({} if rf[1] is None else dict(relax_omegam=rf[1])))
         return out
 
     def _shape_entry(self):
@@ -936,7 +991,8 @@ class CavitySolver:
         side, or the same cells; without `strict` the populations are uploaded under this solver's own mask).  The array is the whole lattice, so a slab
         may restart from a checkpoint of the undivided lattice (each context reads its own rows) but not from another slab's.
         A file that carries a sub-grid constant sets it and clears a buoyancy this solver had set (the two refuse each other); a file
-        without one clears the constant."""
+        without one clears the constant.  A relaxation field (set_relaxation_field) likewise: a file with one sets both arrays and clears
+        this solver's buoyancy, a file without one clears the field."""
         with np.load(_npz(path), allow_pickle=False) as z:
             if int(z["nx"]) != self.nx or int(z["ny"]) != self.ny:
                 raise ValueError("checkpoint lattice size differs")
@@ -1001,6 +1057,12 @@ class CavitySolver:
                 if cs2 > 0.0 and self.buoyancy is not None:      # (this solver's own buoyancy would refuse the constant)
                     self.set_buoyancy(0.0, 0.0)
                 self.set_subgrid(cs2)
+            if "relax_omega" in z:      # (the relaxation field: no geometry, no history)
+                if self.buoyancy is not None:
+                    self.set_buoyancy(0.0, 0.0)
+                self.set_relaxation_field(np.asarray(z["relax_omega"]), np.asarray(z["relax_omegam"]) if "relax_omegam" in z else None)
+            elif self.has_solid and self.relaxation_field is not None:
+                self.set_relaxation_field(None)
             if same_mask and "scalar_g" in z:      # (the scalar last: the geometry calls above end one; a file without it leaves this solver's as it is)
                 self.begin_scalar(float(z["scalar_D"]), np.asarray(z["scalar_c0"]), float(z["scalar_magic"]),
                                   np.asarray(z["scalar_wall_value"]) if "scalar_wall_value" in z else None,

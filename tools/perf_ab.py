@@ -14,6 +14,8 @@ or xy -- set_periodic, the k_wrap launch behind every step; the mask is wrapped 
 scalar (with solid: D -- begin_scalar(D, 1.0), every wall adiabatic: the scalar step behind every flow step),
 buoyancy (with scalar: A -- set_buoyancy(0, A, 1.0): the buoyant twins of the flow and scalar kernels),
 subgrid (with solid: CS2 -- set_subgrid(CS2): the kernels with the sub-grid closure; 0 sets nothing),
+relax (with solid: 1 -- set_relaxation_field with one plane, the lattice's omega jittered by 5 %, seeded: the kernels that read a rate per cell --
+or 2 -- with TRT's second plane as well (coll=TRT); 0 sets nothing),
 route (with solid: single --
 one step per launch, the default -- or tiles -- the multi-step tile kernel, tuning solid_tiles), force (with solid: series.E -- the run
 with begin_force(every=E) --, loop.E -- the host loop step(E); solid_force() --, plain.E -- step(E); sync() without any force --, or call -- no stepping: microseconds per call of
@@ -94,6 +96,10 @@ def parse(case):
                 kw["buoyancy"] = float(v)
             elif k == "subgrid":
                 kw["subgrid"] = float(v)
+            elif k == "relax":
+                if v not in ("0", "1", "2"):
+                    raise ValueError("relax must be 0, 1 or 2")
+                kw["relax"] = int(v)
             elif k == "batch":
                 kw["batch"] = int(v)
             elif k in ("tb_steps", "frame_seg"):
@@ -120,6 +126,7 @@ def main():
         scalar_D = kw.pop("scalar", None)
         buoy = kw.pop("buoyancy", None)
         cs2 = kw.pop("subgrid", 0.0)
+        relax = kw.pop("relax", 0)
         if per is not None:
             from latticeboltzmannsimulations_amd import periodic
             kw["solid"] = periodic.wrap(kw["solid"], "x" in per, "y" in per)
@@ -141,6 +148,10 @@ def main():
                 s.set_buoyancy(0.0, buoy, 1.0)
             if cs2:
                 s.set_subgrid(cs2)
+            if relax:
+                r = np.random.default_rng(3)
+                planes = [np.clip(s.relax[k] * (1.0 + 0.05 * r.standard_normal((nx, ny))), 0.05, 1.95) for k in ("omega", "omegam")[:relax]]
+                s.set_relaxation_field(*planes)
             s.copy_bandwidth(1 << 30, 60)
             s.step(max(60, a.steps // 10)); s.sync()
             if force == "call":
@@ -176,7 +187,7 @@ def main():
             else:
                 reps = [s.time_steps(a.steps) / a.steps for _ in range(a.reps)]
             ms = min(reps)
-            print(f"{case:48s} S={s.next_unit(1000)}{' move' if s.describe().get('wall_motion') else ''}{' shape' if s.describe().get('wall_shape') else ''}{' periodic=' + s.describe()['periodic'] if 'periodic' in s.describe() else ''}{' drive' if s.describe().get('driving_force') else ''}{' buoyant' if s.describe().get('buoyancy') else ''}{' subgrid' if s.describe().get('subgrid') else ''}  {B * nx * ny / ms / 1e6:8.1f} GLUPS  {ms * 1e3:9.2f} us/step  "
+            print(f"{case:48s} S={s.next_unit(1000)}{' move' if s.describe().get('wall_motion') else ''}{' shape' if s.describe().get('wall_shape') else ''}{' periodic=' + s.describe()['periodic'] if 'periodic' in s.describe() else ''}{' drive' if s.describe().get('driving_force') else ''}{' buoyant' if s.describe().get('buoyancy') else ''}{' subgrid' if s.describe().get('subgrid') else ''}{' relax_field' if s.describe().get('relax_field') else ''}{' relax_field+m' if s.describe().get('relax_field+m') else ''}  {B * nx * ny / ms / 1e6:8.1f} GLUPS  {ms * 1e3:9.2f} us/step  "
                   f"repeats {' '.join('%.1f' % (B * nx * ny / r / 1e6) for r in reps)}"
                   + (f"  us/step {' '.join('%.2f' % (r * 1e3) for r in reps)}" if force else ""), flush=True)
 
