@@ -105,9 +105,9 @@ def sources():
 def build(force=False, verbose=False):
     """Compile csrc/*.hip for gfx950 into liblbm_hip.so next to this file (in-tree).  The translation units (eight of host code +
     C ABI: lbm_hip / lbm_plan / lbm_launch / lbm_comm / lbm_sampling / lbm_monitor / lbm_residual / lbm_topology / lbm_solid / lbm_bodies / lbm_body_motion / lbm_body_shape / lbm_scalar (with its kernels, from lbm_scalar.hpp); the explicit instantiations of the tile and
-    streaming kernels, of the one-step kernels with a solid mask per mode of the wall rule -- lbm_solid / lbm_solid_move / lbm_solid_shape / lbm_solid_buoy
-    and, with the sub-grid closure, lbm_solid_sgs / lbm_solid_sgs_move / lbm_solid_sgs_shape, with a relaxation field lbm_solid_relax / lbm_solid_relax_move /
-    lbm_solid_relax_shape and with both lbm_solid_relax_sgs / lbm_solid_relax_sgs_move / lbm_solid_relax_sgs_shape, all from lbm_solid.hpp -- and of the tile kernel with solid cells, for float and for double) are compiled in parallel into csrc/_obj/ and linked."""
+    streaming kernels, of the one-step kernels with a solid mask per mode of the wall rule, a base | feature bits -- lbm_solid{,_move,_shape} the bases,
+    lbm_solid_buoy buoyancy, lbm_solid_sgs{,_move,_shape} the sub-grid closure, lbm_solid_relax{,_move,_shape} a relaxation field, lbm_solid_relax_sgs{,_move,_shape}
+    both, all from the one macro of lbm_solid.hpp -- and of the tile kernel with solid cells, for float and for double) are compiled in parallel into csrc/_obj/ and linked."""
     srcs = sources()
     if not force and os.path.exists(LIB_PATH) and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(s) for s in srcs):
         return LIB_PATH

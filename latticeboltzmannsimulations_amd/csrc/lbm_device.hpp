@@ -569,37 +569,34 @@ __device__ __forceinline__ R shape_link(const R* src, const AS& as, const R* ad,
 
 // The mode of the obstacle wall rule, a compile-time argument of every kernel that applies it (the step kernels of lbm_solid.hpp,
 // update_cell_a below, the force kernels of lbm_solid.hip and lbm_bodies.hip), and what the mode reads, the kernels' last argument;
-// chosen on the host by with_wall (lbm_host.hpp) alone.
+// chosen on the host by with_wall_bits (lbm_host.hpp) alone.  A mode is base | bits: a base in the low two bits --
 //   WALL_REST   every body at rest, no shape: the plain bounce, nothing to read
 //   WALL_MOVE   a nonzero lbm_set_body_motion: a cell with links adds Ladd's term of link k to its post-collision population of
 //               direction opp(k) before it stores it.  cell_row[batch][ny][nx] (x fastest; -1, or the cell's row of delta),
 //               delta[rows][8] in the lattice type: lbm_wall_motion.hpp
 //   WALL_SHAPE  lbm_set_solid_shape holds a shape: shape_rule on the read side of every link; the motion's term is part of the table, the
 //               stores are the pure post-collision values
+// -- and one bit per feature of the one-step kernels, each compile-time, so the kernels of a context without the feature are the
+// instantiations they were, names and arguments included; update_cell_a and the force kernels take the base alone.
+//   WALL_BUOY   buoyancy (lbm_set_buoyancy; Buoy below): by
+//   WALL_SGS    the sub-grid closure (lbm_set_subgrid; subgrid_tau above): sgs = k = 18 sqrt(2) Cs2 in the lattice type.  Every cell that is
+//               neither solid nor held takes w_nu = 1 / tau of its own gathered populations into the collision, in the place of the
+//               lattice's rate; nothing else of the step changes
+//   WALL_RELAX  a relaxation field (lbm_set_relaxation_field): rw, the plane of the cells' viscous rates (SRT's omega, TRT's omega+, MRT's
+//               omega_nu), and rwm, the plane of TRT's omega- or null (every cell then keeps the lattice's w_m: a wave-uniform run-time
+//               test) -- read-only, in the lattice type, addressed as the buoyancy plane (buoy_at; lattice z of a batch at
+//               z * buoy_elems), so a vector's rates are one aligned 16-byte load.  Every cell that is neither solid nor held takes its
+//               own rates into the collision; with the closure tau0 of subgrid_tau is 1 / rw of the cell
+// Instantiated (lbm_solid.hpp) and picked (lbm_host.hpp): the three bases alone, with WALL_SGS, with WALL_RELAX and with both, and
+// WALL_BUOY on WALL_REST and WALL_MOVE alone -- the setters refuse buoyancy with a shape, the closure or a field.
 constexpr int WALL_REST = 0, WALL_MOVE = 1, WALL_SHAPE = 2;
-template <typename R, int WALL>
-struct WallArg {
-    static constexpr int MODE = WALL;
-};
-template <typename R>
-struct WallArg<R, WALL_MOVE> {
-    static constexpr int MODE = WALL_MOVE;
-    const int32_t* cell_row;
-    const R* delta;
-};
-template <typename R>
-struct WallArg<R, WALL_SHAPE> {
-    static constexpr int MODE = WALL_SHAPE;
-    ShapeTable<R> sh;
-};
-// cell_row is [batch][ny][nx]: the offset of lattice z's table, and wa made the tables of that lattice -- the one spelling of the batch
-// offset, whatever the mode (the vector kernel adds batch_cells to its own row offset, the other kernels call wall_batch)
-__device__ __forceinline__ long long batch_cells(unsigned z, const Geo& geo) { return (long long)z * geo.nx * geo.ny; }
-template <typename R, int WALL>
-__device__ __forceinline__ void wall_batch(WallArg<R, WALL>& wa, unsigned z, const Geo& geo) {
-    if constexpr (WALL == WALL_MOVE) wa.cell_row += batch_cells(z, geo);
-    if constexpr (WALL == WALL_SHAPE) wa.sh.cell_row += batch_cells(z, geo);
-}
+constexpr int WALL_BUOY = 4;
+constexpr int WALL_SGS = 8;
+constexpr int WALL_RELAX = 16;
+constexpr int wall_base(int wall) { return wall & 3; }
+constexpr bool wall_buoyant(int wall) { return (wall & WALL_BUOY) != 0; }
+constexpr bool wall_subgrid(int wall) { return (wall & WALL_SGS) != 0; }
+constexpr bool wall_relax(int wall) { return (wall & WALL_RELAX) != 0; }
 
 // The uniform driving force (lbm_set_driving_force): f[k - 1] = F_k of direction k = 1 .. 8, rounded once to the lattice type on the host
 // (drive_terms, lbm_periodic.hpp), and on != 0 while it is nonzero.  A kernel argument of the one-step obstacle kernels (lbm_solid.hpp);
@@ -615,11 +612,7 @@ struct Drive {
 // the C the most recent scalar step summed; b[k - 1] = B_k = (3 w_k)(cx_k ax + cy_k ay) in double (drive_terms) and c_ref, each rounded once
 // to the lattice type on the host.  Every collision of a cell that is neither solid nor held is followed by
 //     t = cp - c_ref;  d_k = F_k + B_k t;  fpost_k = fpost_k + d_k      (every operation in the lattice type, none fused)
-// where the driving force is added alone without it.  A mode of its own of the wall rule, WALL_REST_BUOY / WALL_MOVE_BUOY = the mode |
-// WALL_BUOY (no shape), so the kernels of a context without buoyancy are the instantiations they were, names and arguments included.
-constexpr int WALL_BUOY = 4, WALL_REST_BUOY = WALL_REST | WALL_BUOY, WALL_MOVE_BUOY = WALL_MOVE | WALL_BUOY;
-constexpr int wall_base(int wall) { return wall & 3; }
-constexpr bool wall_buoyant(int wall) { return (wall & WALL_BUOY) != 0; }
+// where the driving force is added alone without it.
 // The plane has an addressing of its own, buoy_at: rows of geo.pitch elements with the lattice's ghost margins, whatever the lattice's
 // layout is (in the rows layout Geo::at strides over all planes of a row and Geo::plane is one row).  buoy_at(x0, y) of a vector's first cell
 // is 16-byte aligned where Geo::at(x0, y) is: pitch and Geo::row are multiples of 4.  buoy_elems: the elements of the allocation.
@@ -631,100 +624,60 @@ struct Buoy {
     R b[8];
     R c_ref;
 };
+
+// What a mode reads, composed of its parts in this order -- the base's tables, then each set bit's fields; a part is empty where the mode
+// does not have it.
+template <typename R, int BASE>
+struct WallTables {};
 template <typename R>
-struct WallArg<R, WALL_REST_BUOY> {
-    static constexpr int MODE = WALL_REST_BUOY;
+struct WallTables<R, WALL_MOVE> {
+    const int32_t* cell_row;
+    const R* delta;
+};
+template <typename R>
+struct WallTables<R, WALL_SHAPE> {
+    ShapeTable<R> sh;
+};
+template <typename R, bool ON>
+struct WallBuoy {};
+template <typename R>
+struct WallBuoy<R, true> {
     Buoy<R> by;
 };
+template <typename R, bool ON>
+struct WallSgs {};
 template <typename R>
-struct WallArg<R, WALL_MOVE_BUOY> {
-    static constexpr int MODE = WALL_MOVE_BUOY;
-    const int32_t* cell_row;
-    const R* delta;
-    Buoy<R> by;
-};
-
-// The sub-grid closure (lbm_set_subgrid; subgrid_tau above) as one more bit of the mode, WALL_SGS, on each of the three base modes: the
-// mode's tables plus k = 18 sqrt(2) Cs2 in the lattice type.  Every cell that is neither solid nor held takes w_nu = 1 / tau of its own
-// gathered populations into the collision, in the place of the lattice's rate; nothing else of the step changes.  Compile-time, so the
-// kernels of a context without it are the instantiations they were, names and arguments included.  (No buoyant twin: lbm_set_subgrid and
-// lbm_set_buoyancy refuse each other.)
-constexpr int WALL_SGS = 8, WALL_REST_SGS = WALL_REST | WALL_SGS, WALL_MOVE_SGS = WALL_MOVE | WALL_SGS, WALL_SHAPE_SGS = WALL_SHAPE | WALL_SGS;
-constexpr bool wall_subgrid(int wall) { return (wall & WALL_SGS) != 0; }
-template <typename R>
-struct WallArg<R, WALL_REST_SGS> {
-    static constexpr int MODE = WALL_REST_SGS;
+struct WallSgs<R, true> {
     R sgs;
 };
+template <typename R, bool ON>
+struct WallField {};
 template <typename R>
-struct WallArg<R, WALL_MOVE_SGS> {
-    static constexpr int MODE = WALL_MOVE_SGS;
-    const int32_t* cell_row;
-    const R* delta;
-    R sgs;
-};
-template <typename R>
-struct WallArg<R, WALL_SHAPE_SGS> {
-    static constexpr int MODE = WALL_SHAPE_SGS;
-    ShapeTable<R> sh;
-    R sgs;
-};
-
-// A relaxation field (lbm_set_relaxation_field): one more bit of the mode, WALL_RELAX, on the three base modes and on their twins with the
-// closure.  rw: the plane of the cells' viscous rates (SRT's omega, TRT's omega+, MRT's omega_nu), rwm: the plane of TRT's omega- or null
-// (every cell then keeps the lattice's w_m: a wave-uniform run-time test) -- read-only, in the lattice type, addressed as the buoyancy
-// plane (buoy_at; lattice z of a batch at z * buoy_elems), so a vector's rates are one aligned 16-byte load.  Every cell that is neither
-// solid nor held takes its own rates into the collision; with the closure tau0 of subgrid_tau is 1 / rw of the cell.  Compile-time, so
-// the kernels of a context without a field are the instantiations they were.  (No buoyant twin: the two refuse each other.)
-constexpr int WALL_RELAX = 16, WALL_REST_RELAX = WALL_REST | WALL_RELAX, WALL_MOVE_RELAX = WALL_MOVE | WALL_RELAX, WALL_SHAPE_RELAX = WALL_SHAPE | WALL_RELAX,
-              WALL_REST_SGS_RELAX = WALL_REST_SGS | WALL_RELAX, WALL_MOVE_SGS_RELAX = WALL_MOVE_SGS | WALL_RELAX,
-              WALL_SHAPE_SGS_RELAX = WALL_SHAPE_SGS | WALL_RELAX;
-constexpr bool wall_relax(int wall) { return (wall & WALL_RELAX) != 0; }
-template <typename R>
-struct WallArg<R, WALL_REST_RELAX> {
-    static constexpr int MODE = WALL_REST_RELAX;
+struct WallField<R, true> {
     const R* rw;
     const R* rwm;
 };
-template <typename R>
-struct WallArg<R, WALL_MOVE_RELAX> {
-    static constexpr int MODE = WALL_MOVE_RELAX;
-    const int32_t* cell_row;
-    const R* delta;
-    const R* rw;
-    const R* rwm;
+template <typename R, int WALL>
+struct WallArg : WallTables<R, wall_base(WALL)>, WallBuoy<R, wall_buoyant(WALL)>, WallSgs<R, wall_subgrid(WALL)>, WallField<R, wall_relax(WALL)> {
+    static constexpr int MODE = WALL;
 };
-template <typename R>
-struct WallArg<R, WALL_SHAPE_RELAX> {
-    static constexpr int MODE = WALL_SHAPE_RELAX;
-    ShapeTable<R> sh;
-    const R* rw;
-    const R* rwm;
-};
-template <typename R>
-struct WallArg<R, WALL_REST_SGS_RELAX> {
-    static constexpr int MODE = WALL_REST_SGS_RELAX;
-    R sgs;
-    const R* rw;
-    const R* rwm;
-};
-template <typename R>
-struct WallArg<R, WALL_MOVE_SGS_RELAX> {
-    static constexpr int MODE = WALL_MOVE_SGS_RELAX;
-    const int32_t* cell_row;
-    const R* delta;
-    R sgs;
-    const R* rw;
-    const R* rwm;
-};
-template <typename R>
-struct WallArg<R, WALL_SHAPE_SGS_RELAX> {
-    static constexpr int MODE = WALL_SHAPE_SGS_RELAX;
-    ShapeTable<R> sh;
-    R sgs;
-    const R* rw;
-    const R* rwm;
-};
+// The kernel-argument layout of the modes in use: the sizes of the structs that spelled each mode's fields out in full
+#define LBM_WALL_SIZE(WALL, F32, F64) static_assert(sizeof(WallArg<float, WALL>) == F32 && sizeof(WallArg<double, WALL>) == F64, "WallArg layout");
+LBM_WALL_SIZE(WALL_REST, 1, 1) LBM_WALL_SIZE(WALL_MOVE, 16, 16) LBM_WALL_SIZE(WALL_SHAPE, 24, 24)
+LBM_WALL_SIZE(WALL_REST | WALL_BUOY, 48, 80) LBM_WALL_SIZE(WALL_MOVE | WALL_BUOY, 64, 96)
+LBM_WALL_SIZE(WALL_REST | WALL_SGS, 4, 8) LBM_WALL_SIZE(WALL_MOVE | WALL_SGS, 24, 24) LBM_WALL_SIZE(WALL_SHAPE | WALL_SGS, 32, 32)
+LBM_WALL_SIZE(WALL_REST | WALL_RELAX, 16, 16) LBM_WALL_SIZE(WALL_MOVE | WALL_RELAX, 32, 32) LBM_WALL_SIZE(WALL_SHAPE | WALL_RELAX, 40, 40)
+LBM_WALL_SIZE(WALL_REST | WALL_SGS | WALL_RELAX, 24, 24) LBM_WALL_SIZE(WALL_MOVE | WALL_SGS | WALL_RELAX, 40, 40)
+LBM_WALL_SIZE(WALL_SHAPE | WALL_SGS | WALL_RELAX, 48, 48)
+#undef LBM_WALL_SIZE
+// cell_row is [batch][ny][nx]: the offset of lattice z's table, and wa made the tables of that lattice -- the one spelling of the batch
+// offset, whatever the mode (the vector kernel adds batch_cells to its own row offset, the other kernels call wall_batch)
+__device__ __forceinline__ long long batch_cells(unsigned z, const Geo& geo) { return (long long)z * geo.nx * geo.ny; }
+template <typename R, int WALL>
+__device__ __forceinline__ void wall_batch(WallArg<R, WALL>& wa, unsigned z, const Geo& geo) {
+    if constexpr (wall_base(WALL) == WALL_MOVE) wa.cell_row += batch_cells(z, geo);
+    if constexpr (wall_base(WALL) == WALL_SHAPE) wa.sh.cell_row += batch_cells(z, geo);
+}
 
 // Gather the post-stream, post-wall-rule populations of cell (x, y) from a lattice that
 // holds post-collision values (+ kept slots + parked wall densities); raw != 0: the lattice

@@ -15,7 +15,7 @@
 //                   sides (k_wrap) and the driving force
 //                                                                                          (C ABI: set_solid, get_solid, solid_force, set_open_cells, get_open_cells,
 //                                                                                           set_periodic, get_periodic, set_driving_force, get_driving_force)
-//                   (step kernels, all three wall modes: k_step_solid, k_step_generic_wall of lbm_solid.hpp; the mode: with_wall below)
+//                   (step kernels, every wall mode: k_step_solid, k_step_generic_wall of lbm_solid.hpp; the mode: with_wall_bits below)
 //   lbm_bodies.hip  the one writer of the obstacle state (struct Obstacles); the bodies of a mask: force and torque on each, one-shot
 //                   and as a series                                                          (C ABI: set_solid_bodies, get_solid_bodies, body_force, force_*)
 //   lbm_body_motion.hip the wall velocity of moving bodies and of single solid cells: its tables (C ABI: set_body_motion, get_body_motion,
@@ -347,6 +347,11 @@ inline int need_solid(lbm_ctx* c, const char* call) {
     if (c->p.semantics == LBM_SEM_BOUNCE_BACK_SOLID) return LBM_OK;
     return fail(c, LBM_ERR_STATE, std::string(call) + ": this context has no solid mask (create it with semantics = LBM_SEM_BOUNCE_BACK_SOLID)");
 }
+// The refusal of a setter in a context on the multi-step tile kernel (LBM_FLAG_SOLID_TILES); lacks: what that kernel does not do.
+inline int need_one_step(lbm_ctx* c, const char* call, const char* lacks) {
+    if (!c->plan.solid_tiles) return LBM_OK;
+    return fail(c, LBM_ERR_STATE, std::string(call) + ": the tile kernel " + lacks + " (LBM_FLAG_SOLID_TILES takes none; create the context without the flag)");
+}
 
 #define HIP_TRY(c, expr)                                                                               \
     do {                                                                                               \
@@ -436,20 +441,17 @@ template <typename R>
 dim3 grid_tiles(const lbm_ctx* c) { return dim3((c->plan.geo.nx + trx<R>() - 1) / trx<R>(), (c->plan.geo.ny + 31) / 32, c->plan.batch); }
 
 // Run-time parameters -> compile-time kernel variant (real type, collision operator, semantics, Smagorinsky).
-// SGS: the sub-grid closure of an obstacle lattice (lbm_set_subgrid) -- asked for by the step launcher alone (launch_rows), which then
-// takes the wall mode's twin with WALL_SGS; every other launcher sees the variant without it.
-// RELAX: a relaxation field (lbm_set_relaxation_field), likewise: the twin with WALL_RELAX.
-template <typename R_, int COLL_, int SEM_, bool TURB_, bool SGS_ = false, bool RELAX_ = false>
+// (The sub-grid closure and the relaxation field of an obstacle lattice are bits of the wall mode, not of the variant: with_wall_step.)
+template <typename R_, int COLL_, int SEM_, bool TURB_>
 struct Variant {
     using R = R_;
     static constexpr int COLL = COLL_, SEM = SEM_;
-    static constexpr bool TURB = TURB_, SGS = SGS_, RELAX = RELAX_;
+    static constexpr bool TURB = TURB_;
 };
-constexpr int STEP_SGS = 1, STEP_RELAX = 2;   // what the step launcher asks of dispatch()
 
 // arith = promoted: fp32 takes the promoted operators, fp64 the strict ones (the promotion's casts are no-ops there).
 template <typename F>
-void dispatch(const lbm_params& p, F&& f, int step = 0) {   // step: STEP_SGS -- the step of a context with a sub-grid constant, STEP_RELAX -- with a relaxation field (SEM_SOLID only)
+void dispatch(const lbm_params& p, F&& f) {
     auto by_sem = [&](auto real, auto coll) {
         using R = decltype(real);
         constexpr int C = decltype(coll)::value;
@@ -460,12 +462,7 @@ void dispatch(const lbm_params& p, F&& f, int step = 0) {   // step: STEP_SGS --
         } else {
             if (p.semantics == LBM_SEM_MRT_PY) f(Variant<R, CS, SEM_PY, false>{});   // (arith = fast: MRT_GPU semantics only)
             else if (p.semantics == LBM_SEM_BOUNCE_BACK) f(Variant<R, C, SEM_BB, false>{});   // (strict and fast; no closure: validate_params)
-            else if (p.semantics == LBM_SEM_BOUNCE_BACK_SOLID) {   // (the same, one step per launch)
-                if (step == (STEP_SGS | STEP_RELAX)) f(Variant<R, C, SEM_SOLID, false, true, true>{});
-                else if (step == STEP_RELAX) f(Variant<R, C, SEM_SOLID, false, false, true>{});
-                else if (step == STEP_SGS) f(Variant<R, C, SEM_SOLID, false, true>{});
-                else f(Variant<R, C, SEM_SOLID, false>{});
-            }
+            else if (p.semantics == LBM_SEM_BOUNCE_BACK_SOLID) f(Variant<R, C, SEM_SOLID, false>{});   // (the same, one step per launch)
             else if (p.turb) f(Variant<R, C, SEM_GPU, true>{});
             else f(Variant<R, C, SEM_GPU, false>{});
         }
@@ -522,60 +519,57 @@ void with_fields(const lbm_ctx* c, int which, F&& launch) {
     }
     launch(fields_of<VT, false>(c, which));
 }
-// The mode of the obstacle wall rule (WallArg, lbm_device.hpp), and the one place that reads the obstacle state to pick it:
-// launch(wa, link), wa the tables of the mode -- a shape (which carries a motion's term in its table), else a nonzero motion, else
-// nothing -- and link the mode's double per entry of BodyTables::links (link_q, link_delta, null).  The kernel takes decltype(wa)::MODE
-// as its last template argument and wa as its last argument.
-template <typename VT, typename F>
-void with_wall(const lbm_ctx* c, F&& launch) {
-    using R = typename VT::R;
+// The mode of the obstacle wall rule (WallArg, lbm_device.hpp: base | bits), and the one place that reads the obstacle state to pick the
+// base and to fill the mode: launch(wa, link), wa the tables of the base -- a shape (which carries a motion's term in its table), else a
+// nonzero motion, else nothing -- with the fields of every bit of BITS, and link the base's double per entry of BodyTables::links (link_q,
+// link_delta, null).  The kernel takes decltype(wa)::MODE as its last template argument and wa as its last argument.
+template <typename R, int BITS, typename F>
+void with_wall_bits(const lbm_ctx* c, F&& launch) {
     const ShapeTables& sh = c->obs.shaped;
     const MotionTables& m = c->obs.moving;
-    if (sh.base) launch(WallArg<R, WALL_SHAPE>{sh.template table<R>()}, sh.link_q);
-    else if (m.base) launch(WallArg<R, WALL_MOVE>{m.cell_row, (const R*)m.delta}, m.link_delta);
-    else launch(WallArg<R, WALL_REST>{}, (const double*)nullptr);
+    auto filled = [&](auto wa, const double* link) {
+        if constexpr (wall_buoyant(BITS)) wa.by = buoy_of<R>(c);
+        if constexpr (wall_subgrid(BITS)) wa.sgs = sgs_k<R>(c);   // (k = 18 sqrt(2) Cs2)
+        if constexpr (wall_relax(BITS)) {
+            wa.rw = c->relax_w.as<const R>();
+            wa.rwm = c->relax_wm.as<const R>();
+        }
+        launch(wa, link);
+    };
+    if constexpr (!wall_buoyant(BITS)) {   // (no buoyant mode with a shape: lbm_set_buoyancy and lbm_set_solid_shape refuse each other)
+        if (sh.base) {
+            WallArg<R, WALL_SHAPE | BITS> wa{};
+            wa.sh = sh.template table<R>();
+            return filled(wa, sh.link_q);
+        }
+    }
+    if (m.base) {
+        WallArg<R, WALL_MOVE | BITS> wa{};
+        wa.cell_row = m.cell_row;
+        wa.delta = (const R*)m.delta;
+        return filled(wa, m.link_delta);
+    }
+    filled(WallArg<R, WALL_REST | BITS>{}, (const double*)nullptr);
 }
-// ... and for the step kernels alone (launch_rows): with buoyancy (lbm_set_buoyancy: no shape) the buoyant twin of the mode, which reads
-// the buoyancy plane; the force kernels keep with_wall -- what they read of the lattice does not change.
-// With the sub-grid closure (VT::SGS, chosen by dispatch) the mode's twin with WALL_SGS, which carries k = 18 sqrt(2) Cs2 (sgs_k).
+// The force kernels: the base alone -- what they read of the lattice changes with no bit.
+template <typename VT, typename F>
+void with_wall(const lbm_ctx* c, F&& launch) { with_wall_bits<typename VT::R, 0>(c, launch); }
+// The step kernels (launch_rows): the bits of the context's run state -- a relaxation field (lbm_set_relaxation_field) and the sub-grid
+// closure (lbm_set_subgrid), alone or together, else buoyancy (lbm_set_buoyancy), which the setters let stand beside neither.
 template <typename VT, typename F>
 void with_wall_step(const lbm_ctx* c, F&& launch) {
     using R = typename VT::R;
-    if constexpr (VT::RELAX) {   // (a relaxation field: the mode's twin with WALL_RELAX, which carries the two planes; with the closure, k too)
-        const ShapeTables& sh = c->obs.shaped;
-        const MotionTables& mv = c->obs.moving;
-        const R* const rw = c->relax_w.as<const R>();
-        const R* const rwm = c->relax_wm.as<const R>();
-        if constexpr (VT::SGS) {
-            const R k = sgs_k<R>(c);
-            if (sh.base) launch(WallArg<R, WALL_SHAPE_SGS_RELAX>{sh.template table<R>(), k, rw, rwm}, sh.link_q);
-            else if (mv.base) launch(WallArg<R, WALL_MOVE_SGS_RELAX>{mv.cell_row, (const R*)mv.delta, k, rw, rwm}, mv.link_delta);
-            else launch(WallArg<R, WALL_REST_SGS_RELAX>{k, rw, rwm}, (const double*)nullptr);
-        } else {
-            if (sh.base) launch(WallArg<R, WALL_SHAPE_RELAX>{sh.template table<R>(), rw, rwm}, sh.link_q);
-            else if (mv.base) launch(WallArg<R, WALL_MOVE_RELAX>{mv.cell_row, (const R*)mv.delta, rw, rwm}, mv.link_delta);
-            else launch(WallArg<R, WALL_REST_RELAX>{rw, rwm}, (const double*)nullptr);
-        }
-        return;
-    }
-    if constexpr (VT::SGS) {
-        const ShapeTables& sh = c->obs.shaped;
-        const MotionTables& mv = c->obs.moving;
-        const R k = sgs_k<R>(c);
-        if (sh.base) launch(WallArg<R, WALL_SHAPE_SGS>{sh.template table<R>(), k}, sh.link_q);
-        else if (mv.base) launch(WallArg<R, WALL_MOVE_SGS>{mv.cell_row, (const R*)mv.delta, k}, mv.link_delta);
-        else launch(WallArg<R, WALL_REST_SGS>{k}, (const double*)nullptr);
-        return;
-    }
-    if (!c->scalar.buoyant) return with_wall<VT>(c, launch);
-    const MotionTables& m = c->obs.moving;
-    if (m.base) launch(WallArg<R, WALL_MOVE_BUOY>{m.cell_row, (const R*)m.delta, buoy_of<R>(c)}, m.link_delta);
-    else launch(WallArg<R, WALL_REST_BUOY>{buoy_of<R>(c)}, (const double*)nullptr);
+    const bool sgs = c->subgrid > 0.0, field = c->relax_field();
+    if (sgs && field) with_wall_bits<R, WALL_SGS | WALL_RELAX>(c, launch);
+    else if (field) with_wall_bits<R, WALL_RELAX>(c, launch);
+    else if (sgs) with_wall_bits<R, WALL_SGS>(c, launch);
+    else if (c->scalar.buoyant) with_wall_bits<R, WALL_BUOY>(c, launch);
+    else with_wall_bits<R, 0>(c, launch);
 }
 // A launcher's body: f(Variant) enqueues the kernels of the context's variant, then the launch error check
 template <typename F>
-int launch_variant(lbm_ctx* c, F&& f, int step = 0) {
-    dispatch(c->p, f, step);
+int launch_variant(lbm_ctx* c, F&& f) {
+    dispatch(c->p, f);
     HIP_TRY(c, hipGetLastError());
     return LBM_OK;
 }

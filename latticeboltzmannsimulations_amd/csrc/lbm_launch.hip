@@ -45,7 +45,7 @@ int launch_rows(lbm_ctx* c, int from, int to, int row0, int stride, int nrows, h
         if constexpr (VT::SEM == SEM_SOLID) {
             // the wall mode's kernel on either route (with_wall); at rest the one-cell route is k_step_generic below, as without a mask
             bool launched = true;
-            with_wall_step<VT>(c, [&](auto wa, const double*) {   // (with buoyancy: the mode's buoyant twin)
+            with_wall_step<VT>(c, [&](auto wa, const double*) {   // (the mode with the bits of the context's run state)
                 constexpr int WALL = decltype(wa)::MODE;
                 if (c->plan.use_vec)   // (nx a multiple of the vector width, kernel = AUTO: plan_kernel)
                     by_nt([&](auto nt) {
@@ -67,7 +67,7 @@ int launch_rows(lbm_ctx* c, int from, int to, int row0, int stride, int nrows, h
         else
             hipLaunchKernelGGL((k_step_generic<R, VT::COLL, VT::SEM, VT::TURB>), grid_rows(c, nrows), dim3(BLK), 0, s, src, dst, c->plan.geo,
                                relax_of<R>(c->p), batch_of<R>(c), raw, row0, stride);
-    }, (c->subgrid > 0.0 ? STEP_SGS : 0) | (c->relax_field() ? STEP_RELAX : 0));   // (lbm_set_subgrid, lbm_set_relaxation_field: dispatch picks the variant)
+    });
 }
 
 // One single step on the frame of width W, lat[from] -> lat[to] (one pass of a multi-step; never a raw lattice).

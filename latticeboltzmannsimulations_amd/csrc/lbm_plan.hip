@@ -549,15 +549,15 @@ int lbm_describe(const lbm_ctx* c, char* buf, size_t len) {
         const int m = std::snprintf(buf + n, len - (size_t)n, " scalar=%.17g,%.17g", c->scalar.D, c->scalar.magic);
         if (m > 0) n = std::min<int>(n + m, (int)len - 1);
     }
-    if (c->scalar.buoyant) {   // (lbm_set_buoyancy: the flow steps run the buoyant twins of their kernels)
+    if (c->scalar.buoyant) {   // (lbm_set_buoyancy: the flow steps run their kernels in the mode | WALL_BUOY)
         const int m = std::snprintf(buf + n, len - (size_t)n, " buoyancy=1");
         if (m > 0) n = std::min<int>(n + m, (int)len - 1);
     }
-    if (c->subgrid > 0.0) {   // (lbm_set_subgrid: the flow steps run the twins of their kernels with the closure)
+    if (c->subgrid > 0.0) {   // (lbm_set_subgrid: the flow steps run their kernels in the mode | WALL_SGS)
         const int m = std::snprintf(buf + n, len - (size_t)n, " subgrid=%.17g", c->subgrid);
         if (m > 0) n = std::min<int>(n + m, (int)len - 1);
     }
-    if (c->relax_field()) {   // (lbm_set_relaxation_field: the flow steps run the twins of their kernels that read the planes)
+    if (c->relax_field()) {   // (lbm_set_relaxation_field: the flow steps run their kernels in the mode | WALL_RELAX, which read the planes)
         const int m = std::snprintf(buf + n, len - (size_t)n, "%s", c->relax_wm ? " relax_field+m" : " relax_field");
         if (m > 0) n = std::min<int>(n + m, (int)len - 1);
     }

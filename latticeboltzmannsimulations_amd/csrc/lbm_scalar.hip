@@ -248,8 +248,8 @@ int lbm_set_buoyancy(lbm_ctx* c, double ax, double ay, double c_ref) {
     if (!c) return LBM_ERR_INVALID;
     if (!std::isfinite(ax) || !std::isfinite(ay) || !std::isfinite(c_ref))
         return fail(c, LBM_ERR_INVALID, "lbm_set_buoyancy: the acceleration and the reference value must be finite");
-    if (c->plan.solid_tiles)   // (such a context cannot have a scalar either: the reason that helps comes first)
-        return fail(c, LBM_ERR_STATE, "lbm_set_buoyancy: the tile kernel adds no force (LBM_FLAG_SOLID_TILES takes none; create the context without the flag)");
+    int rc = need_one_step(c, "lbm_set_buoyancy", "adds no force");   // (such a context cannot have a scalar either: the reason that helps comes first)
+    if (rc) return rc;
     if (!c->scalar.active) return fail(c, LBM_ERR_STATE, "lbm_set_buoyancy: no scalar is active (lbm_scalar_begin first: the buoyancy acts through its C)");
     const bool on = ax != 0.0 || ay != 0.0;
     if (on && c->obs.shaped.base)
@@ -262,7 +262,7 @@ int lbm_set_buoyancy(lbm_ctx* c, double ax, double ay, double c_ref) {
         return fail(c, LBM_ERR_STATE, "lbm_set_buoyancy: a relaxation field is set (the buoyant kernels read no rate planes: every such pairing is one more "
                                       "set of kernel twins; clear it with lbm_set_relaxation_field(c, NULL, NULL) first)");
     HIP_TRY(c, hipSetDevice(c->p.device));
-    int rc = sync_all(c);
+    rc = sync_all(c);
     if (rc) return rc;
     ScalarState& sc = c->scalar;
     if (!on) {   // the launches, the bits and the describe text of a context without it

@@ -372,9 +372,8 @@ int lbm_set_open_cells(lbm_ctx* c, const uint8_t* hold, const double* f) {
     if (!c) return LBM_ERR_INVALID;
     int rc = need_solid(c, "lbm_set_open_cells");
     if (rc) return rc;
-    if (c->plan.solid_tiles)
-        return fail(c, LBM_ERR_STATE, "lbm_set_open_cells: the tile kernel knows no hold cells (LBM_FLAG_SOLID_TILES takes none; create the context "
-                                      "without the flag)");
+    rc = need_one_step(c, "lbm_set_open_cells", "knows no hold cells");
+    if (rc) return rc;
     if (!c->obs.shape_q.empty() || c->obs.moves())
         return fail(c, LBM_ERR_STATE, "lbm_set_open_cells: a shape, a body motion or a wall velocity is set (geometry comes first: the hold cells, "
                                       "then lbm_set_solid_shape, lbm_set_body_motion and lbm_set_wall_velocity)");
@@ -419,9 +418,8 @@ int lbm_set_periodic(lbm_ctx* c, int px, int py) {
     if (!c) return LBM_ERR_INVALID;
     int rc = need_solid(c, "lbm_set_periodic");
     if (rc) return rc;
-    if (c->plan.solid_tiles)
-        return fail(c, LBM_ERR_STATE, "lbm_set_periodic: the tile kernel knows no image cells (LBM_FLAG_SOLID_TILES takes none; create the context "
-                                      "without the flag)");
+    rc = need_one_step(c, "lbm_set_periodic", "knows no image cells");
+    if (rc) return rc;
     if (!c->obs.shape_q.empty() || c->obs.moves())
         return fail(c, LBM_ERR_STATE, "lbm_set_periodic: a shape, a body motion or a wall velocity is set (geometry comes first: the periodic sides, "
                                       "then lbm_set_solid_shape, lbm_set_body_motion and lbm_set_wall_velocity)");
@@ -462,11 +460,10 @@ int lbm_set_driving_force(lbm_ctx* c, double fx, double fy) {
     if (!c) return LBM_ERR_INVALID;
     if (!std::isfinite(fx) || !std::isfinite(fy)) return fail(c, LBM_ERR_INVALID, "lbm_set_driving_force: the force is not finite");
     if (fx != 0.0 || fy != 0.0) {
-        const int rc = need_solid(c, "lbm_set_driving_force");
+        int rc = need_solid(c, "lbm_set_driving_force");
         if (rc) return rc;
-        if (c->plan.solid_tiles)
-            return fail(c, LBM_ERR_STATE, "lbm_set_driving_force: the tile kernel adds no force (LBM_FLAG_SOLID_TILES takes none; create the context "
-                                          "without the flag)");
+        rc = need_one_step(c, "lbm_set_driving_force", "adds no force");
+        if (rc) return rc;
     }
     c->drive[0] = fx;   // (travels by value with every launch: the steps already enqueued keep theirs)
     c->drive[1] = fy;
@@ -484,11 +481,10 @@ int lbm_set_subgrid(lbm_ctx* c, double cs2) {
     if (!c) return LBM_ERR_INVALID;
     if (!std::isfinite(cs2) || cs2 < 0.0) return fail(c, LBM_ERR_INVALID, "lbm_set_subgrid: the constant is negative or not finite");
     if (cs2 != 0.0) {
-        const int rc = need_solid(c, "lbm_set_subgrid");
+        int rc = need_solid(c, "lbm_set_subgrid");
         if (rc) return rc;
-        if (c->plan.solid_tiles)
-            return fail(c, LBM_ERR_STATE, "lbm_set_subgrid: the tile kernel has no closure (LBM_FLAG_SOLID_TILES takes none; create the context "
-                                          "without the flag)");
+        rc = need_one_step(c, "lbm_set_subgrid", "has no closure");
+        if (rc) return rc;
         if (c->scalar.buoyant)
             return fail(c, LBM_ERR_STATE, "lbm_set_subgrid: buoyancy is set (a buoyant flow with the closure needs an eddy diffusivity for the scalar, "
                                           "which there is none; clear it with lbm_set_buoyancy(c, 0, 0, 0) first)");
@@ -517,9 +513,8 @@ int lbm_set_relaxation_field(lbm_ctx* c, const double* omega, const double* omeg
     }
     int rc = need_solid(c, "lbm_set_relaxation_field");
     if (rc) return rc;
-    if (c->plan.solid_tiles)
-        return fail(c, LBM_ERR_STATE, "lbm_set_relaxation_field: the tile kernel reads no rate planes (LBM_FLAG_SOLID_TILES takes none; create the "
-                                      "context without the flag)");
+    rc = need_one_step(c, "lbm_set_relaxation_field", "reads no rate planes");
+    if (rc) return rc;
     if (c->scalar.buoyant)
         return fail(c, LBM_ERR_STATE, "lbm_set_relaxation_field: buoyancy is set (the buoyant kernels read no rate planes: every such pairing is one "
                                       "more set of kernel twins; clear it with lbm_set_buoyancy(c, 0, 0, 0) first)");

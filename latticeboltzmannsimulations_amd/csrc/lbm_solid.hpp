@@ -1,10 +1,12 @@
 // lbm_solid.hpp -- solid obstacles in the bounce-back cavity (LBM_SEM_BOUNCE_BACK_SOLID; contract in include/lbm.h):
-// the one-step kernels of a lattice with a solid mask, one template for the three modes of the wall rule (WALL_REST, WALL_MOVE,
-// WALL_SHAPE: WallArg, lbm_device.hpp).  The rule itself is gather_a<.., SEM_SOLID> and update_cell_a of lbm_device.hpp, which
-// k_step_generic<.., SEM_SOLID> (at rest) and k_step_generic_wall (a motion or a shape) run cell by cell; the vector kernel must equal
-// them bit for bit.  Instantiated per mode and real type in lbm_solid{,_move,_shape}_f32/f64.hip (LBM_INST_SOLID below), six units that
-// compile in parallel, and the buoyant twins of the modes at rest and with a motion (WALL_REST_BUOY, WALL_MOVE_BUOY: lbm_set_buoyancy) in
-// lbm_solid_buoy_f32/f64.hip; lbm_solid.hip holds the host side, the kernel that gives solid cells their constants and the force reduction.
+// the one-step kernels of a lattice with a solid mask, one template for every mode of the wall rule -- a base (WALL_REST, WALL_MOVE,
+// WALL_SHAPE) | the bits of buoyancy, the sub-grid closure and a relaxation field (WallArg, lbm_device.hpp).  The rule itself is
+// gather_a<.., SEM_SOLID> and update_cell_a of lbm_device.hpp, which k_step_generic<.., SEM_SOLID> (at rest) and k_step_generic_wall (every
+// other mode, and a driving force) run cell by cell; the vector kernel must equal them bit for bit.  Instantiated per mode and real type
+// by the one macro LBM_INST_SOLID below, a unit per mode and type that compile in parallel: lbm_solid{,_move,_shape}_f32/f64.hip the bases,
+// lbm_solid_buoy_* WALL_BUOY on the modes at rest and with a motion, lbm_solid_sgs{,_move,_shape}_* WALL_SGS, lbm_solid_relax{,_move,_shape}_*
+// WALL_RELAX, lbm_solid_relax_sgs{,_move,_shape}_* both; lbm_solid.hip holds the host side, the kernel that gives solid cells their
+// constants and the force reduction.
 // The mode blocks sit under `if constexpr` of the kernel template itself, so every mode's kernel is the text it would have alone (a
 // shared __forceinline__ body with a bool switch was tried first and changed the register allocation of the kernel at rest: DESIGN.md 2.10).
 #pragma once
@@ -27,20 +29,16 @@
 //               every lane adds F_k to its post-collision population of direction k, one add in the lattice type, before the delta of
 //               WALL_MOVE and before the solid and the hold lanes are pinned; a uniform run-time test, no template parameter (DESIGN.md
 //               2.10).  The vector kernel never reads dr.on, which the one-cell route tests.
-//   buoyancy    (WALL_REST_BUOY, WALL_MOVE_BUOY: the mode | WALL_BUOY; Buoy, lbm_device.hpp) one more aligned 16-byte load, the cells' values
-//               of the buoyancy plane, next to the link words; in the place of the driving force every lane adds d_k = F_k + B_k (Cp - c_ref)
-//               to its post-collision population of direction k: t per lane, d_k per lane and slot, one add, all in the lattice type.  A
-//               compile-time mode, so the kernels without it are the instantiations they were.
-//   sub-grid    (WALL_REST_SGS, WALL_MOVE_SGS, WALL_SHAPE_SGS: the mode | WALL_SGS; lbm_set_subgrid, subgrid_tau of lbm_device.hpp) no load and no
-//               store more: collide_vec forms every lane's tau from the lane's gathered populations and its moments -- the MRT operators
-//               then form the velocity too -- and takes 1 / tau into the collision in the place of the lattice's rate.  Solid and hold lanes
-//               compute a tau that nobody uses and are pinned as ever.  Instantiated in lbm_solid_sgs{,_move,_shape}_f32/f64.hip.
-//   relaxation  (the mode | WALL_RELAX, with and without WALL_SGS; lbm_set_relaxation_field) one more aligned 16-byte load per plane next to
-//   field       the link words -- the cells' viscous rates, and TRT's odd rates where that plane is set (a wave-uniform test of the pointer;
-//               the lattice's w_m in every lane otherwise): collide_vec takes each lane's own rates into the collision, with the closure
-//               as the closure's omega.  Solid and hold lanes load rates that nobody uses and are pinned as ever; the force and the wall
-//               deltas are added after the collision, unchanged.  Instantiated in lbm_solid_relax{,_move,_shape}_f32/f64.hip and
-//               lbm_solid_relax_sgs{,_move,_shape}_f32/f64.hip.
+//   WALL_BUOY   (lbm_set_buoyancy; Buoy, lbm_device.hpp) one more aligned 16-byte load, the cells' values of the buoyancy plane, next to
+//               the link words; in the place of the driving force every lane adds d_k = F_k + B_k (Cp - c_ref) to its post-collision
+//               population of direction k: t per lane, d_k per lane and slot, one add, all in the lattice type.
+//   WALL_SGS    (lbm_set_subgrid, subgrid_tau of lbm_device.hpp) no load and no store more: collide_vec forms every lane's tau from the
+//               lane's gathered populations and its moments -- the MRT operators then form the velocity too -- and takes 1 / tau into the
+//               collision in the place of the lattice's rate.  Solid and hold lanes compute a tau that nobody uses and are pinned as ever.
+//   WALL_RELAX  (lbm_set_relaxation_field) one more aligned 16-byte load per plane next to the link words -- the cells' viscous rates, and
+//               TRT's odd rates where that plane is set (a wave-uniform test of the pointer; the lattice's w_m in every lane otherwise):
+//               collide_vec takes each lane's own rates into the collision, with WALL_SGS as the closure's omega.  Solid and hold lanes
+//               load rates that nobody uses and are pinned as ever; the force and the wall deltas are added after the collision, unchanged.
 constexpr int SOLID_DRIVE = 2;
 template <typename R, int COLL, bool NT, int WALL>
 __global__ __launch_bounds__(BLK) void k_step_solid(const R* __restrict__ src, R* __restrict__ dst, Geo geo, Relax<R> w, Batch<R> bt, int raw_drive,
@@ -59,7 +57,7 @@ __global__ __launch_bounds__(BLK) void k_step_solid(const R* __restrict__ src, R
     const T lk = vload<R, V, NT>(src + K_LINK * geo.plane + me, true);
     T cpv;   // (buoyancy: the cells' values of the buoyancy plane)
     if constexpr (wall_buoyant(WALL)) cpv = vload<R, V, NT>(wa.by.cp + buoy_at(geo, x0, y), true);
-    T rwv, rmv;   // (a relaxation field: the cells' own rates)
+    T rwv{}, rmv{};   // (a relaxation field: the cells' own rates)
     if constexpr (wall_relax(WALL)) {
         const long long at = (long long)blockIdx.y * buoy_elems(geo) + buoy_at(geo, x0, y);
         rwv = vload<R, V, false>(wa.rw + at, true);
@@ -142,10 +140,9 @@ __global__ __launch_bounds__(BLK) void k_step_solid(const R* __restrict__ src, R
             }
         }
     }
-    if constexpr (wall_relax(WALL) && wall_subgrid(WALL)) collide_vec<R, COLL, V, false, true, true>(in, w, outv, hq, hr, false, false, 0, wa.sgs, rwv, rmv);
-    else if constexpr (wall_relax(WALL)) collide_vec<R, COLL, V, false, false, true>(in, w, outv, hq, hr, false, false, 0, R(0), rwv, rmv);
-    else if constexpr (wall_subgrid(WALL)) collide_vec<R, COLL, V, false, true>(in, w, outv, hq, hr, false, false, 0, wa.sgs);
-    else collide_vec<R, COLL, V, false>(in, w, outv, hq, hr);
+    R sgs = R(0);   // (the closure: its constant)
+    if constexpr (wall_subgrid(WALL)) sgs = wa.sgs;
+    collide_vec<R, COLL, V, false, wall_subgrid(WALL), wall_relax(WALL)>(in, w, outv, hq, hr, false, false, 0, sgs, rwv, rmv);
     // the driving force (lbm_set_driving_force), a uniform run-time test: every lane adds F_k, one add in the lattice type; the solid and
     // the hold lanes are pinned below, so the sums of fluid lanes alone are stored
     if constexpr (wall_buoyant(WALL)) {
@@ -219,8 +216,9 @@ __global__ __launch_bounds__(BLK) void k_step_solid(const R* __restrict__ src, R
 
 // One thread per cell (kernel = GENERIC, and lattices whose nx is no multiple of the vector width) while a motion, a shape or a driving
 // force is set: k_step_generic<.., SEM_SOLID> with the mode and the force of update_cell_a.  At rest and without a force k_step_generic
-// itself is what launches.  The buoyant modes read Cp of the cell and pass update_cell_a, in the base mode, a Drive of the cell's own:
-// d_k = F_k + B_k (Cp - c_ref) with on = 1 -- which is why the rule is spelled f* + (F + B t).
+// itself is what launches.  update_cell_a runs in the base mode, on the mode's tables narrowed once, with one switch and one argument per
+// bit: the closure's constant, the cell's own rates, and with buoyancy a Drive of the cell's own, d_k = F_k + B_k (Cp - c_ref) with on = 1
+// -- which is why the rule is spelled f* + (F + B t).
 template <typename R, int COLL, int WALL>
 __global__ __launch_bounds__(BLK) void k_step_generic_wall(const R* __restrict__ src, R* __restrict__ dst, Geo geo, Relax<R> w, Batch<R> bt, int raw,
                                                            int row0, int row_stride, WallArg<R, WALL> wa, Drive<R> dr) {
@@ -228,89 +226,47 @@ __global__ __launch_bounds__(BLK) void k_step_generic_wall(const R* __restrict__
     const int y = row0 + blockIdx.y * row_stride;
     if (x >= geo.nx) return;
     LBM_BATCH_SELECT(blockIdx.z)
-    if constexpr (wall_buoyant(WALL)) {
-        // buoyancy (a lone lattice): the cell's own force d_k = F_k + B_k (Cp - c_ref) as the driving force of update_cell_a, in the base mode
-        constexpr int BASE = wall_base(WALL);
-        WallArg<R, BASE> wb{};
-        if constexpr (BASE == WALL_MOVE) {
-            wb.cell_row = wa.cell_row;
-            wb.delta = wa.delta;
-        }
-        const R t = wa.by.cp[buoy_at(geo, x, y)] - wa.by.c_ref;
-        Drive<R> d;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) d.f[k] = dr.f[k] + wa.by.b[k] * t;
-        d.on = 1;
-        update_cell_a<R, COLL, SEM_SOLID, false, Geo, Geo, BASE>(src, geo, dst, geo, geo, w, raw, x, y, nullptr, wb, d);
-    } else if constexpr (wall_relax(WALL)) {
-        // a relaxation field: update_cell_a in the base mode with the cell's own rates (and the closure, where the mode has it)
-        constexpr int BASE = wall_base(WALL);
-        WallArg<R, BASE> wb{};
-        if constexpr (BASE == WALL_MOVE) {
-            wb.cell_row = wa.cell_row;
-            wb.delta = wa.delta;
-        }
-        if constexpr (BASE == WALL_SHAPE) wb.sh = wa.sh;
-        wall_batch(wb, blockIdx.z, geo);
-        const long long at = (long long)blockIdx.z * buoy_elems(geo) + buoy_at(geo, x, y);
-        const R rw = wa.rw[at], rwm = wa.rwm ? wa.rwm[at] : w.w_m;
-        if constexpr (wall_subgrid(WALL))
-            update_cell_a<R, COLL, SEM_SOLID, false, Geo, Geo, BASE, true, true>(src, geo, dst, geo, geo, w, raw, x, y, nullptr, wb, dr, wa.sgs, rw, rwm);
-        else
-            update_cell_a<R, COLL, SEM_SOLID, false, Geo, Geo, BASE, false, true>(src, geo, dst, geo, geo, w, raw, x, y, nullptr, wb, dr, R(0), rw, rwm);
-    } else if constexpr (wall_subgrid(WALL)) {
-        // the sub-grid closure: update_cell_a in the base mode with the closure switched on
-        constexpr int BASE = wall_base(WALL);
-        WallArg<R, BASE> wb{};
-        if constexpr (BASE == WALL_MOVE) {
-            wb.cell_row = wa.cell_row;
-            wb.delta = wa.delta;
-        }
-        if constexpr (BASE == WALL_SHAPE) wb.sh = wa.sh;
-        wall_batch(wb, blockIdx.z, geo);
-        update_cell_a<R, COLL, SEM_SOLID, false, Geo, Geo, BASE, true>(src, geo, dst, geo, geo, w, raw, x, y, nullptr, wb, dr, wa.sgs);
-    } else {
+    constexpr int BASE = wall_base(WALL);
+    if constexpr (WALL == BASE) {   // (no bits: the mode's own tables, offset in place)
         wall_batch(wa, blockIdx.z, geo);
         update_cell_a<R, COLL, SEM_SOLID, false, Geo, Geo, WALL>(src, geo, dst, geo, geo, w, raw, x, y, nullptr, wa, dr);
+    } else {
+        // update_cell_a in the base mode: the mode's tables, narrowed once, and what each bit of the mode adds.  Member by member, and in
+        // this function's own text: a copy of the part as a whole, or a helper that returns the narrowed tables, changes the register
+        // allocation of some of these kernels, and so does a narrowed copy in the modes without bits
+        WallArg<R, BASE> wb{};
+        if constexpr (BASE == WALL_MOVE) wb.cell_row = wa.cell_row, wb.delta = wa.delta;
+        if constexpr (BASE == WALL_SHAPE) wb.sh = wa.sh;
+        Drive<R> own;   // (buoyancy, a lone lattice: the cell's own force d_k = F_k + B_k (Cp - c_ref) as the driving force)
+        if constexpr (wall_buoyant(WALL)) {
+            const R t = wa.by.cp[buoy_at(geo, x, y)] - wa.by.c_ref;
+#pragma unroll
+            for (int k = 0; k < 8; ++k) own.f[k] = dr.f[k] + wa.by.b[k] * t;
+            own.on = 1;
+        } else {
+            wall_batch(wb, blockIdx.z, geo);
+        }
+        R sgs = R(0), rw = R(0), rwm = R(0);
+        if constexpr (wall_relax(WALL)) {   // (a relaxation field: the cell's own rates)
+            const long long at = (long long)blockIdx.z * buoy_elems(geo) + buoy_at(geo, x, y);
+            rw = wa.rw[at];
+            rwm = wa.rwm ? wa.rwm[at] : w.w_m;
+        }
+        if constexpr (wall_subgrid(WALL)) sgs = wa.sgs;   // (the sub-grid closure: its constant)
+        update_cell_a<R, COLL, SEM_SOLID, false, Geo, Geo, BASE, wall_subgrid(WALL), wall_relax(WALL)>(src, geo, dst, geo, geo, w, raw, x, y, nullptr, wb,
+                                                                                                       wall_buoyant(WALL) ? own : dr, sgs, rw, rwm);
     }
 }
 
 // LBM_INST_SOLID(R, WALL): the six operator variants of one real type and mode -- the vector kernel with and without non-temporal
-// accesses, and k_step_generic_wall where the mode has one (LBM_SX: `extern`, or nothing in the unit that compiles them)
-#define LBM_SOLID_GENERIC_WALL_REST(R, COLL) \
-    LBM_SX template __global__ void k_step_generic_wall<R, COLL, WALL_REST>(const R* __restrict__, R* __restrict__, Geo, Relax<R>, Batch<R>, int, int, int, WallArg<R, WALL_REST>, Drive<R>);
-#define LBM_SOLID_GENERIC_WALL_MOVE(R, COLL) \
-    LBM_SX template __global__ void k_step_generic_wall<R, COLL, WALL_MOVE>(const R* __restrict__, R* __restrict__, Geo, Relax<R>, Batch<R>, int, int, int, WallArg<R, WALL_MOVE>, Drive<R>);
-#define LBM_SOLID_GENERIC_WALL_SHAPE(R, COLL) \
-    LBM_SX template __global__ void k_step_generic_wall<R, COLL, WALL_SHAPE>(const R* __restrict__, R* __restrict__, Geo, Relax<R>, Batch<R>, int, int, int, WallArg<R, WALL_SHAPE>, Drive<R>);
-#define LBM_SOLID_GENERIC_WALL_REST_BUOY(R, COLL) \
-    LBM_SX template __global__ void k_step_generic_wall<R, COLL, WALL_REST_BUOY>(const R* __restrict__, R* __restrict__, Geo, Relax<R>, Batch<R>, int, int, int, WallArg<R, WALL_REST_BUOY>, Drive<R>);
-#define LBM_SOLID_GENERIC_WALL_MOVE_BUOY(R, COLL) \
-    LBM_SX template __global__ void k_step_generic_wall<R, COLL, WALL_MOVE_BUOY>(const R* __restrict__, R* __restrict__, Geo, Relax<R>, Batch<R>, int, int, int, WallArg<R, WALL_MOVE_BUOY>, Drive<R>);
-#define LBM_SOLID_GENERIC_WALL_REST_SGS(R, COLL) \
-    LBM_SX template __global__ void k_step_generic_wall<R, COLL, WALL_REST_SGS>(const R* __restrict__, R* __restrict__, Geo, Relax<R>, Batch<R>, int, int, int, WallArg<R, WALL_REST_SGS>, Drive<R>);
-#define LBM_SOLID_GENERIC_WALL_MOVE_SGS(R, COLL) \
-    LBM_SX template __global__ void k_step_generic_wall<R, COLL, WALL_MOVE_SGS>(const R* __restrict__, R* __restrict__, Geo, Relax<R>, Batch<R>, int, int, int, WallArg<R, WALL_MOVE_SGS>, Drive<R>);
-#define LBM_SOLID_GENERIC_WALL_SHAPE_SGS(R, COLL) \
-    LBM_SX template __global__ void k_step_generic_wall<R, COLL, WALL_SHAPE_SGS>(const R* __restrict__, R* __restrict__, Geo, Relax<R>, Batch<R>, int, int, int, WallArg<R, WALL_SHAPE_SGS>, Drive<R>);
-#define LBM_SOLID_GENERIC_WALL_REST_RELAX(R, COLL) \
-    LBM_SX template __global__ void k_step_generic_wall<R, COLL, WALL_REST_RELAX>(const R* __restrict__, R* __restrict__, Geo, Relax<R>, Batch<R>, int, int, int, WallArg<R, WALL_REST_RELAX>, Drive<R>);
-#define LBM_SOLID_GENERIC_WALL_MOVE_RELAX(R, COLL) \
-    LBM_SX template __global__ void k_step_generic_wall<R, COLL, WALL_MOVE_RELAX>(const R* __restrict__, R* __restrict__, Geo, Relax<R>, Batch<R>, int, int, int, WallArg<R, WALL_MOVE_RELAX>, Drive<R>);
-#define LBM_SOLID_GENERIC_WALL_SHAPE_RELAX(R, COLL) \
-    LBM_SX template __global__ void k_step_generic_wall<R, COLL, WALL_SHAPE_RELAX>(const R* __restrict__, R* __restrict__, Geo, Relax<R>, Batch<R>, int, int, int, WallArg<R, WALL_SHAPE_RELAX>, Drive<R>);
-#define LBM_SOLID_GENERIC_WALL_REST_SGS_RELAX(R, COLL) \
-    LBM_SX template __global__ void k_step_generic_wall<R, COLL, WALL_REST_SGS_RELAX>(const R* __restrict__, R* __restrict__, Geo, Relax<R>, Batch<R>, int, int, int, WallArg<R, WALL_REST_SGS_RELAX>, Drive<R>);
-#define LBM_SOLID_GENERIC_WALL_MOVE_SGS_RELAX(R, COLL) \
-    LBM_SX template __global__ void k_step_generic_wall<R, COLL, WALL_MOVE_SGS_RELAX>(const R* __restrict__, R* __restrict__, Geo, Relax<R>, Batch<R>, int, int, int, WallArg<R, WALL_MOVE_SGS_RELAX>, Drive<R>);
-#define LBM_SOLID_GENERIC_WALL_SHAPE_SGS_RELAX(R, COLL) \
-    LBM_SX template __global__ void k_step_generic_wall<R, COLL, WALL_SHAPE_SGS_RELAX>(const R* __restrict__, R* __restrict__, Geo, Relax<R>, Batch<R>, int, int, int, WallArg<R, WALL_SHAPE_SGS_RELAX>, Drive<R>);
+// accesses, and k_step_generic_wall (LBM_SX: `extern`, or nothing in the unit that compiles them)
 #define LBM_SOLID_ONE(R, COLL, WALL)                                                                                                                          \
     LBM_SX template __global__ void k_step_solid<R, COLL, false, WALL>(const R* __restrict__, R* __restrict__, Geo, Relax<R>, Batch<R>, int, int, int, int, int, \
                                                                        WallArg<R, WALL>, Drive<R>);                                                           \
     LBM_SX template __global__ void k_step_solid<R, COLL, true, WALL>(const R* __restrict__, R* __restrict__, Geo, Relax<R>, Batch<R>, int, int, int, int, int,  \
                                                                       WallArg<R, WALL>, Drive<R>);                                                            \
-    LBM_SOLID_GENERIC_##WALL(R, COLL)
+    LBM_SX template __global__ void k_step_generic_wall<R, COLL, WALL>(const R* __restrict__, R* __restrict__, Geo, Relax<R>, Batch<R>, int, int, int,             \
+                                                                      WallArg<R, WALL>, Drive<R>);
 #define LBM_INST_SOLID(R, WALL)                                                                                                  \
     LBM_SOLID_ONE(R, C_SRT, WALL) LBM_SOLID_ONE(R, C_TRT, WALL) LBM_SOLID_ONE(R, C_MRT, WALL) LBM_SOLID_ONE(R, C_MRT_FAST, WALL) \
     LBM_SOLID_ONE(R, C_SRT_FAST, WALL) LBM_SOLID_ONE(R, C_TRT_FAST, WALL)
@@ -322,15 +278,15 @@ LBM_SOLID_INST
 LBM_INST_SOLID(float, WALL_REST) LBM_INST_SOLID(double, WALL_REST)
 LBM_INST_SOLID(float, WALL_MOVE) LBM_INST_SOLID(double, WALL_MOVE)
 LBM_INST_SOLID(float, WALL_SHAPE) LBM_INST_SOLID(double, WALL_SHAPE)
-LBM_INST_SOLID(float, WALL_REST_BUOY) LBM_INST_SOLID(double, WALL_REST_BUOY)
-LBM_INST_SOLID(float, WALL_MOVE_BUOY) LBM_INST_SOLID(double, WALL_MOVE_BUOY)
-LBM_INST_SOLID(float, WALL_REST_SGS) LBM_INST_SOLID(double, WALL_REST_SGS)
-LBM_INST_SOLID(float, WALL_MOVE_SGS) LBM_INST_SOLID(double, WALL_MOVE_SGS)
-LBM_INST_SOLID(float, WALL_SHAPE_SGS) LBM_INST_SOLID(double, WALL_SHAPE_SGS)
-LBM_INST_SOLID(float, WALL_REST_RELAX) LBM_INST_SOLID(double, WALL_REST_RELAX)
-LBM_INST_SOLID(float, WALL_MOVE_RELAX) LBM_INST_SOLID(double, WALL_MOVE_RELAX)
-LBM_INST_SOLID(float, WALL_SHAPE_RELAX) LBM_INST_SOLID(double, WALL_SHAPE_RELAX)
-LBM_INST_SOLID(float, WALL_REST_SGS_RELAX) LBM_INST_SOLID(double, WALL_REST_SGS_RELAX)
-LBM_INST_SOLID(float, WALL_MOVE_SGS_RELAX) LBM_INST_SOLID(double, WALL_MOVE_SGS_RELAX)
-LBM_INST_SOLID(float, WALL_SHAPE_SGS_RELAX) LBM_INST_SOLID(double, WALL_SHAPE_SGS_RELAX)
+LBM_INST_SOLID(float, WALL_REST | WALL_BUOY) LBM_INST_SOLID(double, WALL_REST | WALL_BUOY)
+LBM_INST_SOLID(float, WALL_MOVE | WALL_BUOY) LBM_INST_SOLID(double, WALL_MOVE | WALL_BUOY)
+LBM_INST_SOLID(float, WALL_REST | WALL_SGS) LBM_INST_SOLID(double, WALL_REST | WALL_SGS)
+LBM_INST_SOLID(float, WALL_MOVE | WALL_SGS) LBM_INST_SOLID(double, WALL_MOVE | WALL_SGS)
+LBM_INST_SOLID(float, WALL_SHAPE | WALL_SGS) LBM_INST_SOLID(double, WALL_SHAPE | WALL_SGS)
+LBM_INST_SOLID(float, WALL_REST | WALL_RELAX) LBM_INST_SOLID(double, WALL_REST | WALL_RELAX)
+LBM_INST_SOLID(float, WALL_MOVE | WALL_RELAX) LBM_INST_SOLID(double, WALL_MOVE | WALL_RELAX)
+LBM_INST_SOLID(float, WALL_SHAPE | WALL_RELAX) LBM_INST_SOLID(double, WALL_SHAPE | WALL_RELAX)
+LBM_INST_SOLID(float, WALL_REST | WALL_SGS | WALL_RELAX) LBM_INST_SOLID(double, WALL_REST | WALL_SGS | WALL_RELAX)
+LBM_INST_SOLID(float, WALL_MOVE | WALL_SGS | WALL_RELAX) LBM_INST_SOLID(double, WALL_MOVE | WALL_SGS | WALL_RELAX)
+LBM_INST_SOLID(float, WALL_SHAPE | WALL_SGS | WALL_RELAX) LBM_INST_SOLID(double, WALL_SHAPE | WALL_SGS | WALL_RELAX)
 #endif

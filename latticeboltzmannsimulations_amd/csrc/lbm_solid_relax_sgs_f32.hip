@@ -1,4 +1,4 @@
-// lbm_solid_relax_sgs_f32.hip -- the float instantiations of k_step_solid and k_step_generic_wall with a relaxation field and the sub-grid closure, at rest (WALL_REST_SGS_RELAX)
+// lbm_solid_relax_sgs_f32.hip -- the float instantiations of k_step_solid and k_step_generic_wall with a relaxation field and the sub-grid closure, at rest (WALL_REST | WALL_SGS | WALL_RELAX)
 // (lbm_solid.hpp): the six operator variants, the vector kernel with and without non-temporal accesses.
-#define LBM_SOLID_INST LBM_INST_SOLID(float, WALL_REST_SGS_RELAX)
+#define LBM_SOLID_INST LBM_INST_SOLID(float, WALL_REST | WALL_SGS | WALL_RELAX)
 #include "lbm_solid.hpp"

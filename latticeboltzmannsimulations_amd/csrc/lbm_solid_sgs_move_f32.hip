@@ -1,4 +1,4 @@
-// lbm_solid_sgs_move_f32.hip -- the float instantiations of k_step_solid and k_step_generic_wall with the sub-grid closure, with a motion (WALL_MOVE_SGS)
+// lbm_solid_sgs_move_f32.hip -- the float instantiations of k_step_solid and k_step_generic_wall with the sub-grid closure, with a motion (WALL_MOVE | WALL_SGS)
 // (lbm_solid.hpp): the six operator variants, the vector kernel with and without non-temporal accesses.
-#define LBM_SOLID_INST LBM_INST_SOLID(float, WALL_MOVE_SGS)
+#define LBM_SOLID_INST LBM_INST_SOLID(float, WALL_MOVE | WALL_SGS)
 #include "lbm_solid.hpp"
