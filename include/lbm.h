@@ -868,6 +868,48 @@ int lbm_get_subgrid(lbm_ctx* c, double* cs2_out);
 int lbm_set_relaxation_field(lbm_ctx* c, const double* omega, const double* omegam);
 int lbm_get_relaxation_field(lbm_ctx* c, double* omega_out, double* omegam_out);
 
+/* --- shear-dependent viscosity of an obstacle lattice: a rheology table -------------------------------- */
+/* No reference counterpart.  A generalised Newtonian fluid: the viscosity of a cell is a function nu(gdot) of its own shear rate.  On a
+ * LBM_SEM_BOUNCE_BACK_SOLID context at one step per launch every cell that is neither solid nor held takes, once per step, from its gathered
+ * populations f and the moments rho, ux, uy its collision takes anyway,
+ *     jx = rho ux                      jy = rho uy
+ *     a  = ((f1 + f3) - (f2 + f4)) - (jx ux - jy uy)          (= Pxx - Pyy of the non-equilibrium momentum flux)
+ *     b  = (((f5 - f6) + f7) - f8) - jx uy                    (= Pxy)
+ *     N  = sqrt(0.5 (a a) + 2 (b b))                          (the Frobenius norm of its deviatoric part)
+ *     g  = N / rho
+ *     s  = g * inv_dg                  inv_dg = (n - 1) / g_max, formed in double, rounded once to the lattice type
+ *     sc = fmax(fmin(s, n - 1), 0)     (C fmin / fmax: a NaN s gives n - 1)
+ *     i  = min((int) sc, n - 2)        fr = sc - i
+ *     w_nu = t[i] + fr * d[i]          and, with omegam,  w_m = tm[i] + fr * dm[i]
+ * every operation in the lattice type, one rounding each, in the order written, none fused (arith = fast: its own square root and division,
+ * and a fused interpolation).  w_nu enters the collision as SRT's omega, TRT's omega+, MRT's omega_nu; w_m as TRT's omega-.  Nothing else of
+ * the step changes: the driving force and the wall terms are added after the collision as before, solid and hold cells are pinned, and the
+ * raw first step after lbm_set_state uses the table too.  i lies in [0, n - 2] for every state of the lattice, a blown-up one included;
+ * beyond g_max the table holds its last entry.
+ * Why a table in g: with tau = 1/2 + 3 nu the shear rate is gdot = (3 / sqrt 2) g / tau, which needs the tau that nu(gdot) yields.  The
+ * caller solves that once -- g = (sqrt 2 / 3) gdot (1/2 + 3 nu(gdot)) increases strictly wherever the stress nu gdot does not fall -- and
+ * tabulates omega = 1 / tau over g; the device needs g alone, no history, no plane and no store.
+ *   omega[n]: omega at g_i = i g_max / (n - 1), each value rounded once to the lattice type on the host; the slopes d[i] = t[i + 1] - t[i]
+ *     are formed in the lattice type on the host, d[n - 1] = 0.  2 <= n <= 65536.  One table per context, shared by every lattice of a batch.
+ *   omegam[n] or NULL: TRT's omega- at the same g_i.  NULL: every cell keeps the lattice's omegam.
+ *   g_max: the shear of the last entry, finite and positive.
+ * lbm_set_rheology: may be called at any time; it touches neither the lattice nor the step count and ends no sampler, and it survives
+ *   lbm_set_solid and the other setters.  omega = NULL (omegam NULL too; n and g_max ignored) clears the table and restores the launches, the
+ *   bits and the lbm_describe text of a context without it; while a table is set that text gains ` rheology=<n>` (` rheology=<n>+m` with
+ *   omegam).  LBM_ERR_INVALID: an entry that is not finite or not in (0, 2) -- the message names its index; n out of range; g_max not finite
+ *   or not positive.  LBM_ERR_STATE with a reason: another semantics (which covers slabs), a LBM_FLAG_SOLID_TILES context, omegam on a
+ *   context whose collision is not TRT, and buoyancy, a sub-grid constant or a relaxation field set -- each pairing would be one more set
+ *   of kernel twins; while a table is set lbm_set_buoyancy, lbm_set_subgrid (cs2 > 0) and lbm_set_relaxation_field refuse in turn.
+ * lbm_get_rheology: 1 and the table as the device holds it (rounded to the lattice type; omegam_out untouched without omegam; any pointer
+ *   may be NULL) if a table is set, 0 if not.
+ * lbm_get_tau on such a context: a cell that is neither solid nor held reports 1 / w_nu, one division in the lattice type, of the step that
+ *   starts from the current state; solid and hold cells report the lattice's tau0.
+ * lbm_get_shear: g of the rule above for every cell of the current state, indexed like tau_host of lbm_get_tau, with or without a table;
+ *   solid and hold cells report 0.  LBM_ERR_STATE on another semantics. */
+int lbm_set_rheology(lbm_ctx* c, const double* omega, const double* omegam, int n, double g_max);
+int lbm_get_rheology(lbm_ctx* c, double* omega_out, double* omegam_out, int* n_out, double* g_max_out);
+int lbm_get_shear(lbm_ctx* c, void* g_host, int host_dtype);
+
 /* --- slab decomposition, externally driven exchange ---------------------------------- */
 /* No reference counterpart (the reference is single-GPU, MRT_GPU.py:29).  A step of a slab
  * is split so that a host-language driver can move halos with any transport:

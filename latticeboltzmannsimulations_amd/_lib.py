@@ -107,7 +107,7 @@ def build(force=False, verbose=False):
     C ABI: lbm_hip / lbm_plan / lbm_launch / lbm_comm / lbm_sampling / lbm_monitor / lbm_residual / lbm_topology / lbm_solid / lbm_bodies / lbm_body_motion / lbm_body_shape / lbm_scalar (with its kernels, from lbm_scalar.hpp); the explicit instantiations of the tile and
     streaming kernels, of the one-step kernels with a solid mask per mode of the wall rule, a base | feature bits -- lbm_solid{,_move,_shape} the bases,
     lbm_solid_buoy buoyancy, lbm_solid_sgs{,_move,_shape} the sub-grid closure, lbm_solid_relax{,_move,_shape} a relaxation field, lbm_solid_relax_sgs{,_move,_shape}
-    both, all from the one macro of lbm_solid.hpp -- and of the tile kernel with solid cells, for float and for double) are compiled in parallel into csrc/_obj/ and linked."""
+    both, lbm_solid_rheo{,_move,_shape} a rheology table, all from the one macro of lbm_solid.hpp -- and of the tile kernel with solid cells, for float and for double) are compiled in parallel into csrc/_obj/ and linked."""
     srcs = sources()
     if not force and os.path.exists(LIB_PATH) and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(s) for s in srcs):
         return LIB_PATH
@@ -211,6 +211,9 @@ SIGNATURES = {
     "lbm_get_subgrid": (_i, [_vp, ctypes.POINTER(_d)]),
     "lbm_set_relaxation_field": (_i, [_vp, _vp, _vp]),  # (omega[B][nx][ny] doubles, omegam the same or NULL; both NULL clears)
     "lbm_get_relaxation_field": (_i, [_vp, _vp, _vp]),  # -> 1 if set, 0 if not
+    "lbm_set_rheology": (_i, [_vp, _vp, _vp, _i, _d]),  # (omega[n] doubles, omegam[n] or NULL, n, g_max; omega NULL clears)
+    "lbm_get_rheology": (_i, [_vp, _vp, _vp, ctypes.POINTER(_i), ctypes.POINTER(_d)]),  # -> 1 if set, 0 if not
+    "lbm_get_shear": (_i, [_vp, _vp, _i]),
     "lbm_halo_elems": (_i, [_vp]),
     "lbm_halo_export": (_i, [_vp, _i, _vp]),
     "lbm_halo_import": (_i, [_vp, _i, _vp]),

@@ -15,6 +15,7 @@ import numpy as np
 
 from . import scalar as SC
 from . import solid as S
+from . import rheology as RH
 from . import viscosity as V
 
 
@@ -76,7 +77,7 @@ def solver_re(Re_D, D, umax, mean, ny):
 
 
 def run_channel(nx, ny, Re_D, umax=0.05, disc=None, curved=False, profile="parabolic", walls="rest", steps=20000, force_every=100, RT="MRT",
-                dtype=np.float32, arith="strict", device=0, solver_factory=None, quiet=False, scalar=None, buoyancy=None, subgrid=None, sponge=None):
+                dtype=np.float32, arith="strict", device=0, solver_factory=None, quiet=False, scalar=None, buoyancy=None, subgrid=None, sponge=None, rheology=None):
     """Step a channel and keep the force series of the (first) obstacle on the device.  Returns dict(Cd, Cl, fx, fy, steps, Re, nu,
     series): Cd = 2 Fx / (rho mean^2 D), Cl likewise from Fy, of the last sample (rho = 1); D = 2 r of the disc (without one: the
     channel's width and the force on the side walls).  Re_D = mean D / nu is converted to the solver's Re (solver_re).
@@ -90,7 +91,13 @@ def run_channel(nx, ny, Re_D, umax=0.05, disc=None, curved=False, profile="parab
     sponge=(length, factor): a zone of raised viscosity in front of the held outlet (CavitySolver.set_viscosity with nu times
     viscosity.sponge(nx, ny, length, factor), a quadratic ramp to factor nu at the outlet column; under TRT the magic parameter of the
     solver's rates is kept in every cell), which relaxes a wake towards the profile the outlet holds; the result gains outlet_drho, the
-    largest |rho - 1| over the fluid cells of the last 20 columns in front of the outlet after the last step.  Not with buoyancy."""
+    largest |rho - 1| over the fluid cells of the last 20 columns in front of the outlet after the last step.  Not with buoyancy.
+    rheology=(omega, omegam, g_max) or dict(law=..., g_max=..., entries=..., magic=...) (rheology.resolve): a generalised Newtonian fluid
+    (CavitySolver.set_rheology) from the first step on; Re_D then only sets the lattice's own rates.  With the report after the last
+    step one warning is printed if the largest shear exceeds g_max; the result gains g_top, that shear, and tau_mean.  Not with
+    buoyancy, subgrid or sponge."""
+    if rheology is not None and (buoyancy is not None or sponge is not None or (subgrid is not None and float(subgrid) > 0.0)):
+        raise ValueError("rheology excludes buoyancy, subgrid and sponge: each pairing would be one more set of kernel twins")
     if sponge is not None and buoyancy is not None:
         raise ValueError("sponge and buoyancy exclude each other: the buoyant kernels read no viscosity field")
     if subgrid is not None and buoyancy is not None and float(subgrid) > 0.0:
@@ -113,6 +120,7 @@ def run_channel(nx, ny, Re_D, umax=0.05, disc=None, curved=False, profile="parab
         s.set_wall_velocity(g["wall_velocity"])
         if subgrid is not None:
             s.set_subgrid(float(subgrid))
+        g_max = RH.apply(s, rheology, RT) if rheology is not None else None
         if sponge is not None:
             length, factor = int(sponge[0]), float(sponge[1])
             rl = s.relax
@@ -136,7 +144,8 @@ def run_channel(nx, ny, Re_D, umax=0.05, disc=None, curved=False, profile="parab
         series = s.force_series()
         s.end_force()
         flux = float(s.scalar_flux()["flux"][body]) if scalar is not None else None
-        tau_mean = float(np.mean(s.get_tau()[~g["solid"] & ~g["hold"]], dtype=np.float64)) if subgrid is not None else None
+        tau_mean = float(np.mean(s.get_tau()[~g["solid"] & ~g["hold"]], dtype=np.float64)) if subgrid is not None or rheology is not None else None
+        g_top = RH.over_range(s, g_max, (lambda *a: None) if quiet else print) if rheology is not None else None
         if sponge is not None:
             rho = np.asarray(s.get_fields()[1], dtype=np.float64)
             tail = np.zeros((nx, ny), dtype=bool)
@@ -149,12 +158,14 @@ def run_channel(nx, ny, Re_D, umax=0.05, disc=None, curved=False, profile="parab
         out.update(scalar_flux=flux, scalar_D=float(sc["D"]), Nu=SC.nusselt(flux, sc["D"], float(sc["disc_value"]) - float(sc["inlet_value"]), D))
     if subgrid is not None:
         out.update(subgrid=float(subgrid), tau_mean=tau_mean)
+    if rheology is not None:
+        out.update(g_top=g_top, g_max=g_max, tau_mean=tau_mean)
     if sponge is not None:
         out.update(sponge=(length, factor), outlet_drho=outlet_drho)
     if not quiet:
         print(f"after {steps} steps: Fx = {fx:.8g}, Fy = {fy:.8g}, Cd = 2 Fx / (rho mean^2 D) = {out['Cd']:.6g}, Cl = {out['Cl']:.6g}" +
               (f", Nu = flux / (pi D_s dC) = {out['Nu']:.6g}" if scalar is not None else "") +
-              (f", mean relaxation time {tau_mean:.6g}" if subgrid is not None else "") +
+              (f", mean relaxation time {tau_mean:.6g}" if subgrid is not None or rheology is not None else "") +
               (f", max |rho - 1| in the last 20 columns {outlet_drho:.3e}" if sponge is not None else ""))
     return out
 
@@ -181,7 +192,17 @@ def main(argv=None):
     ap.add_argument("--subgrid", type=float, default=None, metavar="CS2", help="the local Smagorinsky closure with this constant (the reference's is 0.025; not with --buoyancy)")
     ap.add_argument("--sponge", type=float, nargs=2, metavar=("LENGTH", "FACTOR"), default=None,
                     help="raise the viscosity over the last LENGTH columns in front of the held outlet, a quadratic ramp to FACTOR times nu (not with --buoyancy)")
+    ap.add_argument("--power-law", dest="power_law", type=float, nargs=2, metavar=("K", "N"), default=None,
+                    help="a power-law fluid nu = K gdot^(N - 1) (clipped to [1e-3, 2]) through a rheology table (not with --buoyancy, --subgrid, --sponge)")
+    ap.add_argument("--carreau", type=float, nargs=4, metavar=("NU0", "NUINF", "LAMBDA", "N"), default=None,
+                    help="a Carreau fluid nu = NUINF + (NU0 - NUINF) (1 + (LAMBDA gdot)^2)^((N - 1) / 2) through a rheology table")
+    ap.add_argument("--g-max", dest="g_max", type=float, default=RH.G_MAX_DEFAULT, help="the shear of the table's last entry")
     a = ap.parse_args(argv)
+    if a.power_law is not None and a.carreau is not None:
+        ap.error("--power-law and --carreau exclude each other")
+    law = RH.power_law(*a.power_law) if a.power_law is not None else RH.carreau(*a.carreau) if a.carreau is not None else None
+    if law is not None and (a.buoyancy is not None or a.subgrid is not None or a.sponge is not None):
+        ap.error("--power-law / --carreau exclude --buoyancy, --subgrid and --sponge")
     if a.subgrid is not None and a.buoyancy is not None:
         ap.error("--subgrid and --buoyancy exclude each other")
     if a.sponge is not None and a.buoyancy is not None:
@@ -192,7 +213,8 @@ def main(argv=None):
         ap.error("--scalar-D reports the disc's Nusselt number: it needs --disc")
     run_channel(a.xsize, a.ysize, a.Re_D, a.umax, a.disc, a.curved, a.profile, a.walls, a.steps, a.force_every, a.RT, np.dtype(a.dtype).type,
                 device=a.device, scalar=None if a.scalar_D is None else dict(D=a.scalar_D, disc_value=a.disc_value, inlet_value=a.inlet_value),
-                buoyancy=a.buoyancy, subgrid=a.subgrid, sponge=a.sponge)
+                buoyancy=a.buoyancy, subgrid=a.subgrid, sponge=a.sponge,
+                rheology=None if law is None else dict(law=law, g_max=a.g_max, magic=V.MAGIC))
     return 0
 
 

@@ -9,6 +9,8 @@
 
 #include <type_traits>
 
+#include "lbm_rheology.hpp"   // the rheology table's index, host and device (lbm_set_rheology)
+
 namespace lbm {
 
 constexpr int Q = 9;
@@ -444,6 +446,66 @@ __device__ __forceinline__ T subgrid_omega(const T (&f)[Q], T rho, T ux, T uy, W
     return div_<FAST>(T((R)1.0), subgrid_tau<T, FAST, W>(f, rho, ux, uy, omega, k));
 }
 
+// The rheology table of the obstacle lattices (lbm_set_rheology; a generalised Newtonian fluid): the viscous rate of a cell
+// as a function of its own shear.  From the gathered populations and the moments the collision takes anyway, the DEVIATORIC part of the
+// non-equilibrium momentum flux (MRT relaxes the trace at omega_e, so only the deviatoric moments belong to omega_nu; the rho / 3 cancels)
+//     jx = rho ux                      jy = rho uy
+//     a  = ((f1 + f3) - (f2 + f4)) - (jx ux - jy uy)          (= Pxx - Pyy)
+//     b  = (((f5 - f6) + f7) - f8) - jx uy                    (= Pxy)
+//     N  = sqrt(0.5 (a a) + 2 (b b))                          g = N / rho
+//     s  = g inv_dg      i, fr = rheology_index(s)            w_nu = t[i] + fr d[i]     and, with a second table,  w_m = tm[i] + fr dm[i]
+// every operation in the lattice type, one rounding each, in the order written, nothing fused.  FAST: the square root and the division by
+// sqrt_<FAST> / div_<FAST>, and the interpolation is one fused multiply-add.  g needs no tau: the host has solved the implicit relation
+// between the shear rate and tau once, when it tabulated omega over g.  No history and no store.  tests/rheology_ref.py restates the order.
+// Rheo: the table (rheology_table of lbm_rheology.hpp, RHEO_STRIDE reals per entry), n - 1, inv_dg and whether the table carries TRT's odd
+// rate; the context's, shared by every lattice of a batch.
+template <typename R>
+struct Rheo {
+    const R* tab;
+    R inv_dg;
+    int nm1;
+    int has_m;
+};
+struct RheoNone {};   // (what a kernel without a table passes in its place: nothing)
+template <typename T, bool FAST = false>
+__device__ __forceinline__ T rheology_shear(const T (&f)[Q], T rho, T ux, T uy) {
+    typedef typename ScalarOf<T>::type R;
+    const T jx = rho * ux, jy = rho * uy;
+    const T a = ((f[1] + f[3]) - (f[2] + f[4])) - (jx * ux - jy * uy);
+    const T b = (((f[5] - f[6]) + f[7]) - f[8]) - jx * uy;
+    const T n = sqrt_<FAST>((R)0.5 * (a * a) + (R)2 * (b * b));
+    return div_<FAST>(n, rho);
+}
+template <typename R, bool FAST>
+__device__ __forceinline__ void rheology_lookup(R s, const Rheo<R>& rh, R w_m0, R& w_nu, R& w_m) {
+    typedef R P __attribute__((ext_vector_type(2)));   // (a rate's value and slope: one 8- or 16-byte load)
+    R fr;
+    const int i = rheology_index<R>(s, rh.nm1, fr);
+    const R* const e = rh.tab + (long long)i * RHEO_STRIDE;
+    const P td = *reinterpret_cast<const P*>(e);
+    w_nu = FAST ? fma_(fr, td.y, td.x) : td.x + fr * td.y;
+    w_m = w_m0;
+    if (rh.has_m) {   // (wave-uniform)
+        const P md = *reinterpret_cast<const P*>(e + 2);
+        w_m = FAST ? fma_(fr, md.y, md.x) : md.x + fr * md.y;
+    }
+}
+// w_m0: the lattice's odd rate, what w_m is without a second table
+template <typename T, bool FAST = false>
+__device__ __forceinline__ void rheology_rates(const T (&f)[Q], T rho, T ux, T uy, const Rheo<typename ScalarOf<T>::type>& rh,
+                                               typename ScalarOf<T>::type w_m0, T& w_nu, T& w_m) {
+    const T s = rheology_shear<T, FAST>(f, rho, ux, uy) * rh.inv_dg;
+    if constexpr (std::is_same<T, f32x2>::value) {   // (two cells side by side: a gather per half)
+        float n0, m0, n1, m1;
+        rheology_lookup<float, FAST>(s.x, rh, w_m0, n0, m0);
+        rheology_lookup<float, FAST>(s.y, rh, w_m0, n1, m1);
+        w_nu = f32x2{n0, n1};
+        w_m = f32x2{m0, m1};
+    } else {
+        rheology_lookup<T, FAST>(s, rh, w_m0, w_nu, w_m);
+    }
+}
+
 // a8: wall rules on the populations of ONE perimeter cell, given the equilibrium of the
 // previous macroscopic state of that cell.  SEM_PY: MRT.py:450-453 in statement order
 // (left equilibrium, right mirror pairing, bottom, lid); SEM_GPU: MRT_GPU.py:674-692
@@ -587,16 +649,22 @@ __device__ __forceinline__ R shape_link(const R* src, const AS& as, const R* ad,
 //               test) -- read-only, in the lattice type, addressed as the buoyancy plane (buoy_at; lattice z of a batch at
 //               z * buoy_elems), so a vector's rates are one aligned 16-byte load.  Every cell that is neither solid nor held takes its
 //               own rates into the collision; with the closure tau0 of subgrid_tau is 1 / rw of the cell
-// Instantiated (lbm_solid.hpp) and picked (lbm_host.hpp): the three bases alone, with WALL_SGS, with WALL_RELAX and with both, and
-// WALL_BUOY on WALL_REST and WALL_MOVE alone -- the setters refuse buoyancy with a shape, the closure or a field.
+//   WALL_RHEO   a rheology table (lbm_set_rheology; rheology_rates above): rh.  Every cell that is neither solid nor held takes the rates
+//               the table gives its own shear into the collision -- w_nu in the place of the lattice's rate and, where the table carries
+//               it, TRT's odd rate; nothing else of the step changes
+// Instantiated (lbm_solid.hpp) and picked (lbm_host.hpp): the three bases alone, with WALL_SGS, with WALL_RELAX and with both,
+// WALL_BUOY on WALL_REST and WALL_MOVE alone -- the setters refuse buoyancy with a shape, the closure or a field -- and WALL_RHEO on the
+// three bases alone: the table's setter and those of buoyancy, the closure and a field refuse each other.
 constexpr int WALL_REST = 0, WALL_MOVE = 1, WALL_SHAPE = 2;
 constexpr int WALL_BUOY = 4;
 constexpr int WALL_SGS = 8;
 constexpr int WALL_RELAX = 16;
+constexpr int WALL_RHEO = 32;
 constexpr int wall_base(int wall) { return wall & 3; }
 constexpr bool wall_buoyant(int wall) { return (wall & WALL_BUOY) != 0; }
 constexpr bool wall_subgrid(int wall) { return (wall & WALL_SGS) != 0; }
 constexpr bool wall_relax(int wall) { return (wall & WALL_RELAX) != 0; }
+constexpr bool wall_rheo(int wall) { return (wall & WALL_RHEO) != 0; }
 
 // The uniform driving force (lbm_set_driving_force): f[k - 1] = F_k of direction k = 1 .. 8, rounded once to the lattice type on the host
 // (drive_terms, lbm_periodic.hpp), and on != 0 while it is nonzero.  A kernel argument of the one-step obstacle kernels (lbm_solid.hpp);
@@ -657,8 +725,15 @@ struct WallField<R, true> {
     const R* rw;
     const R* rwm;
 };
+template <typename R, bool ON>
+struct WallRheo {};
+template <typename R>
+struct WallRheo<R, true> {
+    Rheo<R> rh;
+};
 template <typename R, int WALL>
-struct WallArg : WallTables<R, wall_base(WALL)>, WallBuoy<R, wall_buoyant(WALL)>, WallSgs<R, wall_subgrid(WALL)>, WallField<R, wall_relax(WALL)> {
+struct WallArg : WallTables<R, wall_base(WALL)>, WallBuoy<R, wall_buoyant(WALL)>, WallSgs<R, wall_subgrid(WALL)>, WallField<R, wall_relax(WALL)>,
+                 WallRheo<R, wall_rheo(WALL)> {
     static constexpr int MODE = WALL;
 };
 // The kernel-argument layout of the modes in use: the sizes of the structs that spelled each mode's fields out in full
@@ -669,6 +744,7 @@ LBM_WALL_SIZE(WALL_REST | WALL_SGS, 4, 8) LBM_WALL_SIZE(WALL_MOVE | WALL_SGS, 24
 LBM_WALL_SIZE(WALL_REST | WALL_RELAX, 16, 16) LBM_WALL_SIZE(WALL_MOVE | WALL_RELAX, 32, 32) LBM_WALL_SIZE(WALL_SHAPE | WALL_RELAX, 40, 40)
 LBM_WALL_SIZE(WALL_REST | WALL_SGS | WALL_RELAX, 24, 24) LBM_WALL_SIZE(WALL_MOVE | WALL_SGS | WALL_RELAX, 40, 40)
 LBM_WALL_SIZE(WALL_SHAPE | WALL_SGS | WALL_RELAX, 48, 48)
+LBM_WALL_SIZE(WALL_REST | WALL_RHEO, 24, 24) LBM_WALL_SIZE(WALL_MOVE | WALL_RHEO, 40, 40) LBM_WALL_SIZE(WALL_SHAPE | WALL_RHEO, 48, 48)
 #undef LBM_WALL_SIZE
 // cell_row is [batch][ny][nx]: the offset of lattice z's table, and wa made the tables of that lattice -- the one spelling of the batch
 // offset, whatever the mode (the vector kernel adds batch_cells to its own row offset, the other kernels call wall_batch)
@@ -776,11 +852,14 @@ __device__ __forceinline__ void gather(const R* __restrict__ src, const Geo& geo
 // the gathered populations and the moments of the cell, k = sgs.
 // RLX (k_step_generic_wall in a mode with WALL_RELAX alone), rw, rwm: the cell's own rates of a relaxation field -- rw where the lattice's
 // w_nu stands (with SGS: as the closure's omega), rwm as TRT's odd rate.
-template <typename R, int COLL, int SEM, bool TURB, typename AS, typename AD, int WALL = WALL_REST, bool SGS = false, bool RLX = false>
+// RHEO (k_step_generic_wall in a mode with WALL_RHEO alone), rh: the rheology table -- rheology_rates of the gathered populations and the
+// moments of the cell give both rates.
+template <typename R, int COLL, int SEM, bool TURB, typename AS, typename AD, int WALL = WALL_REST, bool SGS = false, bool RLX = false,
+          bool RHEO = false, typename RH = RheoNone>
 __device__ __forceinline__ void update_cell_a(const R* __restrict__ src, const AS& as, R* __restrict__ dst, const AD& ad, const Geo& geo,
                                               const Relax<R>& w0, int raw, int x, int y, const R* __restrict__ lnk = nullptr,
                                               WallArg<R, WALL> wa = WallArg<R, WALL>{}, Drive<R> dr = Drive<R>{}, R sgs = R(0), R rw = R(0),
-                                              R rwm = R(0)) {
+                                              R rwm = R(0), RH rh = RH{}) {
     // lnk (SEM_SOLID with an LDS window as the source): plane K_LINK of the lattice, see link_word
     const int X = geo.nx, Y = geo.NY, gy = geo.y0 + y;
     if (SEM == SEM_SOLID && (link_word<R, AS>(src, as, geo, lnk, x, y) & (LINK_SOLID | LINK_HOLD))) return;   // a solid cell, or a hold cell, is never updated
@@ -802,7 +881,11 @@ __device__ __forceinline__ void update_cell_a(const R* __restrict__ src, const A
     R w_nu = w0.w_nu;
     if (TURB) w_nu = smagorinsky_omega<R, coll_is_fast(COLL), coll_is_prom(COLL)>(g, src[K_QEQ * as.plane + me_s], src[K_RHO * as.plane + me_s], w0.w_nu);
     macros<R, coll_is_fast(COLL), SEM>(g, x, gy, X, Y, w.uLB, rho, ux, uy);
-    if constexpr (RLX) {
+    if constexpr (RHEO) {
+        R w_m;
+        rheology_rates<R, coll_is_fast(COLL)>(g, rho, ux, uy, rh, w0.w_m, w_nu, w_m);
+        equ_collide<R, COLL, TURB, true>(g, rho, ux, uy, w, w_nu, out, q2, COLL == C_MRT_FAST && gy == 0 && !sem_is_bb(SEM), w_m);
+    } else if constexpr (RLX) {
         w_nu = rw;
         if constexpr (SGS) w_nu = subgrid_omega<R, coll_is_fast(COLL)>(g, rho, ux, uy, rw, sgs);
         equ_collide<R, COLL, TURB, true>(g, rho, ux, uy, w, w_nu, out, q2, COLL == C_MRT_FAST && gy == 0 && !sem_is_bb(SEM), rwm);
@@ -944,12 +1027,14 @@ __device__ __forceinline__ void update_vec(const R* __restrict__ src, R* __restr
 // hold garbage -- harmless.  Per-cell arithmetic is the same operation sequence as update_cell,
 // so the result is bit-identical to two single steps.
 // ------------------------------------------------------------------------------------------
-template <typename R, int COLL, int V, bool TURB, bool SGS = false, bool RLX = false>
+template <typename R, int COLL, int V, bool TURB, bool SGS = false, bool RLX = false, bool RHEO = false, typename RH = RheoNone>
 __device__ __forceinline__ void collide_vec(const typename VecT<R, V>::type (&in)[Q], const Relax<R>& w0,
                                             typename VecT<R, V>::type (&outv)[Q],
                                             typename VecT<R, V>::type& hq, typename VecT<R, V>::type& hr, bool wl = false, bool wr = false,
                                             int kind = 0, R sgs = R(0), typename VecT<R, V>::type rw = typename VecT<R, V>::type{},
-                                            typename VecT<R, V>::type rwm = typename VecT<R, V>::type{}) {
+                                            typename VecT<R, V>::type rwm = typename VecT<R, V>::type{}, RH rh = RH{}) {
+    // RHEO (k_step_solid in a mode with WALL_RHEO alone, kind 0): rh, the rheology table -- rheology_rates of the cell's populations and
+    // moments give both rates (the packed halves gather per half); the MRT operators then form the velocity too
     // RLX (k_step_solid in a mode with WALL_RELAX alone, kind 0): rw, rwm -- the V cells' own rates of a relaxation field, in the lane
     // order of in[k] (the packed halves p = 0 / 1 take .xy / .zw of them as they do of in[k]): rw where the lattice's w_nu stands (with
     // SGS: as the closure's omega), rwm as TRT's odd rate
@@ -972,7 +1057,7 @@ __device__ __forceinline__ void collide_vec(const typename VecT<R, V>::type (&in
             f32x2 rho = ((((((((g[0] + g[1]) + g[2]) + g[3]) + g[4]) + g[5]) + g[6]) + g[7]) + g[8]);
             if (kind == 1) rho = ((g[0] + g[1]) + g[3]) + 2.f * ((g[2] + g[5]) + g[6]);
             f32x2 ux = f32x2(0.f), uy = f32x2(0.f);
-            if (!coll_is_mrt(COLL) || TURB || SGS) {
+            if (!coll_is_mrt(COLL) || TURB || SGS || RHEO) {
                 if (kind == 0) {
                     ux = div_<coll_is_fast(COLL)>((((((g[1] - g[3]) + g[5]) - g[6]) - g[7]) + g[8]), rho);
                     uy = div_<coll_is_fast(COLL)>((((((g[2] - g[4]) + g[5]) + g[6]) - g[7]) - g[8]), rho);
@@ -982,7 +1067,11 @@ __device__ __forceinline__ void collide_vec(const typename VecT<R, V>::type (&in
                     ux = f32x2(kind == 1 ? w0.uLB : 0.f); uy = f32x2(0.f);
                 }
             }
-            if constexpr (RLX) {
+            if constexpr (RHEO) {
+                f32x2 w_m;
+                rheology_rates<f32x2, coll_is_fast(COLL)>(g, rho, ux, uy, rh, w0.w_m, w_nu, w_m);
+                equ_collide<f32x2, COLL, TURB, true>(g, rho, ux, uy, w0, w_nu, out, q2, COLL == C_MRT_FAST && kind == 1, w_m);
+            } else if constexpr (RLX) {
                 const f32x2 rwp = p == 0 ? rw.xy : rw.zw, rmp = p == 0 ? rwm.xy : rwm.zw;
                 w_nu = rwp;
                 if constexpr (SGS) w_nu = subgrid_omega<f32x2, coll_is_fast(COLL), f32x2>(g, rho, ux, uy, rwp, sgs);
@@ -1015,7 +1104,7 @@ __device__ __forceinline__ void collide_vec(const typename VecT<R, V>::type (&in
             R rho = ((((((((g[0] + g[1]) + g[2]) + g[3]) + g[4]) + g[5]) + g[6]) + g[7]) + g[8]);
             if (kind == 1) rho = ((g[0] + g[1]) + g[3]) + (R)2. * ((g[2] + g[5]) + g[6]);
             R ux = (R)0, uy = (R)0;
-            if (!coll_is_mrt(COLL) || TURB || SGS) {
+            if (!coll_is_mrt(COLL) || TURB || SGS || RHEO) {
                 if (kind == 0) {
                     ux = div_<coll_is_fast(COLL)>((((((g[1] - g[3]) + g[5]) - g[6]) - g[7]) + g[8]), rho);
                     uy = div_<coll_is_fast(COLL)>((((((g[2] - g[4]) + g[5]) + g[6]) - g[7]) - g[8]), rho);
@@ -1024,7 +1113,11 @@ __device__ __forceinline__ void collide_vec(const typename VecT<R, V>::type (&in
                     ux = kind == 1 ? w0.uLB : (R)0; uy = (R)0;
                 }
             }
-            if constexpr (RLX) {
+            if constexpr (RHEO) {
+                R w_m;
+                rheology_rates<R, coll_is_fast(COLL)>(g, rho, ux, uy, rh, w0.w_m, w_nu, w_m);
+                equ_collide<R, COLL, TURB, true>(g, rho, ux, uy, w0, w_nu, out, q2, COLL == C_MRT_FAST && kind == 1, w_m);
+            } else if constexpr (RLX) {
                 w_nu = rw[c];
                 if constexpr (SGS) w_nu = subgrid_omega<R, coll_is_fast(COLL)>(g, rho, ux, uy, rw[c], sgs);
                 equ_collide<R, COLL, TURB, true>(g, rho, ux, uy, w0, w_nu, out, q2, COLL == C_MRT_FAST && kind == 1, rwm[c]);

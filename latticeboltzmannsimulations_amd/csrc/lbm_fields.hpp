@@ -211,6 +211,50 @@ __global__ __launch_bounds__(BLK) void k_export_tau_relax(Fields<R, SEM_SOLID, f
         if (x0 + xx < geo.nx && y0 + yy < geo.ny) stage[(long long)(x0 + xx) * geo.ny + y0 + yy] = t[xx][yy];
 }
 
+// ... with a rheology table (lbm_set_rheology; rh: the context's table, lbm_device.hpp), and the shear itself (lbm_get_shear), two outputs of
+// which either may be null: a cell that is neither solid nor held reports, in tau, 1 / w_nu of rheology_rates on the populations the view
+// gathers and their moments -- the operations of the step (FAST: its division, square root and fused interpolation), then one division in
+// the lattice type -- and, in shear, g = N / rho of rheology_shear; a solid cell and a hold cell report tau0 and 0.  tau needs a table
+// (rh.tab), shear does not.  tau, shear = [nx][ny_local] per lattice.
+template <typename R, bool FAST, bool SHAPE>
+__global__ __launch_bounds__(BLK) void k_export_rheology(Fields<R, SEM_SOLID, false, SHAPE> f, Relax<R> w, Batch<R> bt, Rheo<R> rh, R* __restrict__ tau,
+                                                         R* __restrict__ shear) {
+    const Geo& geo = f.geo;
+    constexpr int TRX = trx<R>(), RY = BLK / TRX;
+    __shared__ R t[2][TRX][33];
+    const long long n = (long long)geo.nx * geo.ny;
+    const auto lat = f.lattice(blockIdx.z);
+    if (bt.w) w = bt.w[blockIdx.z];
+    const int x0 = blockIdx.x * TRX, y0 = blockIdx.y * 32;
+    const int tx = threadIdx.x % TRX, x = x0 + tx;
+    for (int ty = threadIdx.x / TRX; ty < 32; ty += RY) {
+        const int y = y0 + ty;
+        if (x >= geo.nx || y >= geo.ny) continue;
+        R tc = (R)1.0 / w.w_nu, gc = (R)0;
+        if (!((int)lat.src[K_LINK * geo.plane + geo.at(x, y)] & (LINK_SOLID | LINK_HOLD))) {
+            R g[Q], rho, ux, uy;
+            lat.populations(x, y, g);
+            macros<R, FAST, SEM_SOLID>(g, x, geo.y0 + y, geo.nx, geo.NY, lat.uLB, rho, ux, uy);
+            gc = rheology_shear<R, FAST>(g, rho, ux, uy);
+            if (tau) {
+                R w_nu, w_m;
+                rheology_rates<R, FAST>(g, rho, ux, uy, rh, w.w_m, w_nu, w_m);
+                tc = div_<FAST>((R)1.0, w_nu);
+            }
+        }
+        t[0][tx][ty] = tc;
+        t[1][tx][ty] = gc;
+    }
+    __syncthreads();
+    const int yy = threadIdx.x & 31, xb = threadIdx.x >> 5;
+    for (int xx = xb; xx < TRX; xx += BLK / 32)
+        if (x0 + xx < geo.nx && y0 + yy < geo.ny) {
+            const long long o = blockIdx.z * n + (long long)(x0 + xx) * geo.ny + y0 + yy;
+            if (tau) tau[o] = t[0][xx][yy];
+            if (shear) shear[o] = t[1][xx][yy];
+        }
+}
+
 // Sum over the slab of ux + uy of the view's macroscopic state (what k_export_macro would write), in double:
 // partial[blockIdx.z * gridDim.x + blockIdx.x] = the block's sum; k_reduce_final adds the partial sums of each lattice in
 // index order -- a fixed summation tree, so the result does not vary from run to run.

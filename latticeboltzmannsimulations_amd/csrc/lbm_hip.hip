@@ -149,6 +149,13 @@ int export_tau(lbm_ctx* c, int which) {
                 });
                 return;
             }
+            if (c->rheology()) {   // (lbm_set_rheology: 1 / w_nu of the step that starts from lat[cur])
+                with_fields<VT>(c, c->cur, [&](auto f) {
+                    hipLaunchKernelGGL((k_export_rheology<R, coll_is_fast(VT::COLL), decltype(f)::SHAPED>), grid_tiles<R>(c), dim3(BLK), 0, c->s_compute, f,
+                                       relax_of<R>(c->p), batch_of<R>(c), rheo_of<R>(c), c->stage.as<R>(), (R*)nullptr);
+                });
+                return;
+            }
             if (c->subgrid > 0.0) {
                 with_fields<VT>(c, c->cur, [&](auto f) {
                     hipLaunchKernelGGL((k_export_tau_subgrid<R, coll_is_fast(VT::COLL), decltype(f)::SHAPED>), grid_tiles<R>(c), dim3(BLK), 0, c->s_compute, f,
@@ -159,6 +166,20 @@ int export_tau(lbm_ctx* c, int which) {
         }
         hipLaunchKernelGGL((k_export_tau<R, coll_is_fast(VT::COLL), coll_is_prom(VT::COLL)>), grid_tiles<R>(c), dim3(BLK), 0, c->s_compute,
                            fields_of<Variant<R, VT::COLL, SEM_GPU, VT::TURB>>(c, which), relax_of<R>(c->p), batch_of<R>(c), c->p.turb, c->stage.as<R>());
+    });
+}
+
+// the shear g = N / rho of the current state, lat[cur], through the view (lbm_get_shear): the kernel of the rheology table, its other output
+int export_shear(lbm_ctx* c) {
+    return launch_variant(c, [&](auto v) {
+        using VT = decltype(v);
+        using R = typename VT::R;
+        if constexpr (VT::SEM == SEM_SOLID) {
+            with_fields<VT>(c, c->cur, [&](auto f) {
+                hipLaunchKernelGGL((k_export_rheology<R, coll_is_fast(VT::COLL), decltype(f)::SHAPED>), grid_tiles<R>(c), dim3(BLK), 0, c->s_compute, f,
+                                   relax_of<R>(c->p), batch_of<R>(c), Rheo<R>{}, (R*)nullptr, c->stage.as<R>());
+            });
+        }
     });
 }
 
@@ -406,6 +427,19 @@ int lbm_get_tau(lbm_ctx* c, void* tau_host, int host_dtype) {
     if (rc) return rc;
     HIP_TRY(c, hipStreamSynchronize(c->s_compute));
     return stage_to_host(c, c->stage.get(), tau_host, host_dtype, c->plan.batch);
+}
+
+int lbm_get_shear(lbm_ctx* c, void* g_host, int host_dtype) {
+    if (!c || !g_host || (host_dtype != LBM_F32 && host_dtype != LBM_F64)) return fail(c, LBM_ERR_INVALID, "lbm_get_shear: bad argument");
+    int rc = need_solid(c, "lbm_get_shear");
+    if (rc) return rc;
+    int which = 0;
+    rc = reader_source(c, "lbm_get_shear", false, &which);
+    if (rc == LBM_OK) rc = ensure_field_stage(c);
+    if (rc == LBM_OK) rc = export_shear(c);
+    if (rc) return rc;
+    HIP_TRY(c, hipStreamSynchronize(c->s_compute));
+    return stage_to_host(c, c->stage.get(), g_host, host_dtype, c->plan.batch);
 }
 
 int lbm_copy_bandwidth(lbm_ctx* c, size_t bytes, int iters, double* gbps) {

@@ -56,7 +56,7 @@
 #include "lbm_devmem.hpp"
 #include "lbm_bodies.hpp"
 #include "lbm_periodic.hpp"
-#include "lbm_solid.hpp"  // k_step_solid, k_step_generic_wall, extern (compiled per wall mode in lbm_solid{,_move,_shape,_buoy}_f32/f64.hip, lbm_solid_sgs*, lbm_solid_relax*)
+#include "lbm_solid.hpp"  // k_step_solid, k_step_generic_wall, extern (compiled per wall mode in lbm_solid{,_move,_shape,_buoy}_f32/f64.hip, lbm_solid_sgs*, lbm_solid_relax*, lbm_solid_rheo*)
 #include "lbm_fields.hpp" // the view of the exported state and the kernels of the field export
 #include "lbm_inst.hpp"   // the kernels, and extern template declarations of the multi-step ones (compiled in lbm_{tiles,stream*}_f32/f64.hip)
 
@@ -310,6 +310,13 @@ struct lbm_ctx {
     // b * buoy_elems; ghost and pad elements hold the rate the lattice had when the field was set.  No geometry and no history.
     DevBuf relax_w, relax_wm;
     bool relax_field() const { return (bool)relax_w; }
+    // A rheology table (lbm_set_rheology), empty while none is set: rheo_tab the table as rheology_table (lbm_rheology.hpp) lays it out, in
+    // the lattice type, one for every lattice of a batch; rheo_w / rheo_wm the entries as the device holds them (rounded to the lattice
+    // type; rheo_wm empty without TRT's odd rate), rheo_gmax the shear of the last entry.  No geometry and no history.
+    DevBuf rheo_tab;
+    std::vector<double> rheo_w, rheo_wm;
+    double rheo_gmax = 0.0;
+    bool rheology() const { return (bool)rheo_tab; }
     ncclComm_t comm = nullptr;
     int nranks = 1, rank = 0;
     bool loopback = false;      // diagnostic: 1-rank communicator, the slab exchanges halos with itself
@@ -519,6 +526,18 @@ void with_fields(const lbm_ctx* c, int which, F&& launch) {
     }
     launch(fields_of<VT, false>(c, which));
 }
+// The rheology table as the kernels take it (Rheo, lbm_device.hpp); tab null without one
+template <typename R>
+Rheo<R> rheo_of(const lbm_ctx* c) {
+    Rheo<R> rh{};
+    if (!c->rheology()) return rh;
+    const int n = (int)c->rheo_w.size();
+    rh.tab = c->rheo_tab.as<const R>();
+    rh.inv_dg = rheology_inv_dg<R>(n, c->rheo_gmax);
+    rh.nm1 = n - 1;
+    rh.has_m = c->rheo_wm.empty() ? 0 : 1;
+    return rh;
+}
 // The mode of the obstacle wall rule (WallArg, lbm_device.hpp: base | bits), and the one place that reads the obstacle state to pick the
 // base and to fill the mode: launch(wa, link), wa the tables of the base -- a shape (which carries a motion's term in its table), else a
 // nonzero motion, else nothing -- with the fields of every bit of BITS, and link the base's double per entry of BodyTables::links (link_q,
@@ -534,6 +553,7 @@ void with_wall_bits(const lbm_ctx* c, F&& launch) {
             wa.rw = c->relax_w.as<const R>();
             wa.rwm = c->relax_wm.as<const R>();
         }
+        if constexpr (wall_rheo(BITS)) wa.rh = rheo_of<R>(c);
         launch(wa, link);
     };
     if constexpr (!wall_buoyant(BITS)) {   // (no buoyant mode with a shape: lbm_set_buoyancy and lbm_set_solid_shape refuse each other)
@@ -555,7 +575,8 @@ void with_wall_bits(const lbm_ctx* c, F&& launch) {
 template <typename VT, typename F>
 void with_wall(const lbm_ctx* c, F&& launch) { with_wall_bits<typename VT::R, 0>(c, launch); }
 // The step kernels (launch_rows): the bits of the context's run state -- a relaxation field (lbm_set_relaxation_field) and the sub-grid
-// closure (lbm_set_subgrid), alone or together, else buoyancy (lbm_set_buoyancy), which the setters let stand beside neither.
+// closure (lbm_set_subgrid), alone or together, else buoyancy (lbm_set_buoyancy), which the setters let stand beside neither, else a
+// rheology table (lbm_set_rheology), which they let stand beside none of the three.
 template <typename VT, typename F>
 void with_wall_step(const lbm_ctx* c, F&& launch) {
     using R = typename VT::R;
@@ -564,6 +585,7 @@ void with_wall_step(const lbm_ctx* c, F&& launch) {
     else if (field) with_wall_bits<R, WALL_RELAX>(c, launch);
     else if (sgs) with_wall_bits<R, WALL_SGS>(c, launch);
     else if (c->scalar.buoyant) with_wall_bits<R, WALL_BUOY>(c, launch);
+    else if (c->rheology()) with_wall_bits<R, WALL_RHEO>(c, launch);
     else with_wall_bits<R, 0>(c, launch);
 }
 // A launcher's body: f(Variant) enqueues the kernels of the context's variant, then the launch error check

@@ -561,6 +561,10 @@ int lbm_describe(const lbm_ctx* c, char* buf, size_t len) {
         const int m = std::snprintf(buf + n, len - (size_t)n, "%s", c->relax_wm ? " relax_field+m" : " relax_field");
         if (m > 0) n = std::min<int>(n + m, (int)len - 1);
     }
+    if (c->rheology()) {   // (lbm_set_rheology: the flow steps run their kernels in the mode | WALL_RHEO, which read the table)
+        const int m = std::snprintf(buf + n, len - (size_t)n, " rheology=%d%s", (int)c->rheo_w.size(), c->rheo_wm.empty() ? "" : "+m");
+        if (m > 0) n = std::min<int>(n + m, (int)len - 1);
+    }
     return n;
 }
 

@@ -261,6 +261,9 @@ int lbm_set_buoyancy(lbm_ctx* c, double ax, double ay, double c_ref) {
     if (on && c->relax_field())
         return fail(c, LBM_ERR_STATE, "lbm_set_buoyancy: a relaxation field is set (the buoyant kernels read no rate planes: every such pairing is one more "
                                       "set of kernel twins; clear it with lbm_set_relaxation_field(c, NULL, NULL) first)");
+    if (on && c->rheology())
+        return fail(c, LBM_ERR_STATE, "lbm_set_buoyancy: a rheology table is set (the buoyant kernels read no rheology table: every such pairing is one "
+                                      "more set of kernel twins; clear it with lbm_set_rheology(c, NULL, NULL, 0, 0) first)");
     HIP_TRY(c, hipSetDevice(c->p.device));
     rc = sync_all(c);
     if (rc) return rc;

@@ -488,6 +488,9 @@ int lbm_set_subgrid(lbm_ctx* c, double cs2) {
         if (c->scalar.buoyant)
             return fail(c, LBM_ERR_STATE, "lbm_set_subgrid: buoyancy is set (a buoyant flow with the closure needs an eddy diffusivity for the scalar, "
                                           "which there is none; clear it with lbm_set_buoyancy(c, 0, 0, 0) first)");
+        if (c->rheology())
+            return fail(c, LBM_ERR_STATE, "lbm_set_subgrid: a rheology table is set (the kernels with the closure read no rheology table: every such "
+                                          "pairing is one more set of kernel twins; clear it with lbm_set_rheology(c, NULL, NULL, 0, 0) first)");
     }
     c->subgrid = cs2;   // (travels by value with every launch: the steps already enqueued keep theirs; no history, so the state stays)
     return LBM_OK;
@@ -518,6 +521,9 @@ int lbm_set_relaxation_field(lbm_ctx* c, const double* omega, const double* omeg
     if (c->scalar.buoyant)
         return fail(c, LBM_ERR_STATE, "lbm_set_relaxation_field: buoyancy is set (the buoyant kernels read no rate planes: every such pairing is one "
                                       "more set of kernel twins; clear it with lbm_set_buoyancy(c, 0, 0, 0) first)");
+    if (c->rheology())
+        return fail(c, LBM_ERR_STATE, "lbm_set_relaxation_field: a rheology table is set (the kernels that read rate planes read no rheology table: "
+                                      "every such pairing is one more set of kernel twins; clear it with lbm_set_rheology(c, NULL, NULL, 0, 0) first)");
     if (omegam && c->p.collision != LBM_TRT)
         return fail(c, LBM_ERR_STATE, "lbm_set_relaxation_field: omegam is TRT's odd rate and this context's collision is not TRT (pass NULL: MRT's "
                                       "other rates stay the lattice's)");
@@ -559,6 +565,88 @@ int lbm_get_relaxation_field(lbm_ctx* c, double* omega_out, double* omegam_out) 
     if (rc == LBM_OK && omegam_out && c->relax_wm)
         rc = f32 ? relax_download<float>(c, c->relax_wm, omegam_out) : relax_download<double>(c, c->relax_wm, omegam_out);
     return rc ? rc : 1;
+}
+
+int lbm_set_rheology(lbm_ctx* c, const double* omega, const double* omegam, int n, double g_max) {
+    if (!c) return LBM_ERR_INVALID;
+    if (!omega) {
+        if (omegam) return fail(c, LBM_ERR_INVALID, "lbm_set_rheology: omegam without omega (the table is cleared with omega NULL)");
+        if (!c->rheology()) return LBM_OK;
+        HIP_TRY(c, hipSetDevice(c->p.device));
+        const int rc = sync_all(c);   // (the steps enqueued read the table)
+        if (rc) return rc;
+        c->rheo_tab = DevBuf{};
+        c->rheo_w.clear();
+        c->rheo_wm.clear();
+        c->rheo_gmax = 0.0;
+        return LBM_OK;
+    }
+    int rc = need_solid(c, "lbm_set_rheology");
+    if (rc) return rc;
+    rc = need_one_step(c, "lbm_set_rheology", "reads no rheology table");
+    if (rc) return rc;
+    const char* const twins = ": every such pairing is one more set of kernel twins; clear it with ";
+    if (c->scalar.buoyant)
+        return fail(c, LBM_ERR_STATE, std::string("lbm_set_rheology: buoyancy is set (the buoyant kernels read no rheology table") + twins +
+                                          "lbm_set_buoyancy(c, 0, 0, 0) first)");
+    if (c->subgrid > 0.0)
+        return fail(c, LBM_ERR_STATE, std::string("lbm_set_rheology: a sub-grid constant is set (the kernels with the closure read no rheology table") + twins +
+                                          "lbm_set_subgrid(c, 0) first)");
+    if (c->relax_field())
+        return fail(c, LBM_ERR_STATE, std::string("lbm_set_rheology: a relaxation field is set (the kernels that read rate planes read no rheology table") +
+                                          twins + "lbm_set_relaxation_field(c, NULL, NULL) first)");
+    if (omegam && c->p.collision != LBM_TRT)
+        return fail(c, LBM_ERR_STATE, "lbm_set_rheology: omegam is TRT's odd rate and this context's collision is not TRT (pass NULL: MRT's other "
+                                      "rates stay the lattice's)");
+    if (n < RHEO_MIN_ENTRIES || n > RHEO_MAX_ENTRIES)
+        return fail(c, LBM_ERR_INVALID, "lbm_set_rheology: n is " + std::to_string(n) + ": a table has 2 to 65536 entries");
+    if (!(std::isfinite(g_max) && g_max > 0.0)) {
+        char val[40];
+        std::snprintf(val, sizeof val, "%.17g", g_max);
+        return fail(c, LBM_ERR_INVALID, std::string("lbm_set_rheology: g_max is ") + val + ": the shear of the last entry must be finite and positive");
+    }
+    for (const double* v : {omega, omegam}) {
+        if (!v) continue;
+        const long long bad = relax_bad(v, (size_t)n);
+        if (bad < 0) continue;
+        char val[40];
+        std::snprintf(val, sizeof val, "%.17g", v[bad]);
+        return fail(c, LBM_ERR_INVALID, std::string("lbm_set_rheology: ") + (v == omega ? "omega" : "omegam") + " of entry " + std::to_string(bad) + " is " +
+                                            val + ": every rate must be finite and in (0, 2)");
+    }
+    HIP_TRY(c, hipSetDevice(c->p.device));
+    rc = sync_all(c);
+    if (rc) return rc;
+    const bool f32 = c->p.dtype == LBM_F32;
+    DevBuf tab;
+    std::vector<double> w((size_t)n), wm(omegam ? (size_t)n : 0);
+    auto upload = [&](const auto& t) -> int {   // t: the table in the lattice type
+        const int arc = alloc_ok(c, tab.alloc(t.size() * sizeof(t[0]), "rheology table"));
+        if (arc) return arc;
+        HIP_TRY(c, hipMemcpy(tab.get(), t.data(), t.size() * sizeof(t[0]), hipMemcpyHostToDevice));
+        for (int i = 0; i < n; ++i) {
+            w[i] = (double)t[(size_t)i * RHEO_STRIDE];
+            if (omegam) wm[i] = (double)t[(size_t)i * RHEO_STRIDE + 2];
+        }
+        return LBM_OK;
+    };
+    rc = f32 ? upload(rheology_table<float>(omega, omegam, n)) : upload(rheology_table<double>(omega, omegam, n));
+    if (rc) return rc;
+    c->rheo_tab = std::move(tab);
+    c->rheo_w = std::move(w);
+    c->rheo_wm = std::move(wm);
+    c->rheo_gmax = g_max;
+    return LBM_OK;
+}
+
+int lbm_get_rheology(lbm_ctx* c, double* omega_out, double* omegam_out, int* n_out, double* g_max_out) {
+    if (!c) return LBM_ERR_INVALID;
+    if (!c->rheology()) return 0;
+    if (n_out) *n_out = (int)c->rheo_w.size();
+    if (g_max_out) *g_max_out = c->rheo_gmax;
+    if (omega_out) std::memcpy(omega_out, c->rheo_w.data(), c->rheo_w.size() * sizeof(double));
+    if (omegam_out && !c->rheo_wm.empty()) std::memcpy(omegam_out, c->rheo_wm.data(), c->rheo_wm.size() * sizeof(double));
+    return 1;
 }
 
 int lbm_get_open_cells(lbm_ctx* c, uint8_t* hold_out, double* f_out) {

@@ -5,7 +5,7 @@
 // other mode, and a driving force) run cell by cell; the vector kernel must equal them bit for bit.  Instantiated per mode and real type
 // by the one macro LBM_INST_SOLID below, a unit per mode and type that compile in parallel: lbm_solid{,_move,_shape}_f32/f64.hip the bases,
 // lbm_solid_buoy_* WALL_BUOY on the modes at rest and with a motion, lbm_solid_sgs{,_move,_shape}_* WALL_SGS, lbm_solid_relax{,_move,_shape}_*
-// WALL_RELAX, lbm_solid_relax_sgs{,_move,_shape}_* both; lbm_solid.hip holds the host side, the kernel that gives solid cells their
+// WALL_RELAX, lbm_solid_relax_sgs{,_move,_shape}_* both, lbm_solid_rheo{,_move,_shape}_* WALL_RHEO; lbm_solid.hip holds the host side, the kernel that gives solid cells their
 // constants and the force reduction.
 // The mode blocks sit under `if constexpr` of the kernel template itself, so every mode's kernel is the text it would have alone (a
 // shared __forceinline__ body with a bool switch was tried first and changed the register allocation of the kernel at rest: DESIGN.md 2.10).
@@ -39,6 +39,10 @@
 //               TRT's odd rates where that plane is set (a wave-uniform test of the pointer; the lattice's w_m in every lane otherwise):
 //               collide_vec takes each lane's own rates into the collision, with WALL_SGS as the closure's omega.  Solid and hold lanes
 //               load rates that nobody uses and are pinned as ever; the force and the wall deltas are added after the collision, unchanged.
+//   WALL_RHEO   (lbm_set_rheology, rheology_rates of lbm_device.hpp) no plane and no store more: collide_vec forms every lane's shear from
+//               the lane's gathered populations and its moments -- the MRT operators then form the velocity too --, gathers the rates'
+//               values and slopes from the context's table, one small load per rate and lane, and takes the interpolated rates into the
+//               collision.  Solid and hold lanes look up rates that nobody uses (the index is safe for any value) and are pinned as ever.
 constexpr int SOLID_DRIVE = 2;
 template <typename R, int COLL, bool NT, int WALL>
 __global__ __launch_bounds__(BLK) void k_step_solid(const R* __restrict__ src, R* __restrict__ dst, Geo geo, Relax<R> w, Batch<R> bt, int raw_drive,
@@ -142,7 +146,8 @@ __global__ __launch_bounds__(BLK) void k_step_solid(const R* __restrict__ src, R
     }
     R sgs = R(0);   // (the closure: its constant)
     if constexpr (wall_subgrid(WALL)) sgs = wa.sgs;
-    collide_vec<R, COLL, V, false, wall_subgrid(WALL), wall_relax(WALL)>(in, w, outv, hq, hr, false, false, 0, sgs, rwv, rmv);
+    if constexpr (wall_rheo(WALL)) collide_vec<R, COLL, V, false, false, false, true, Rheo<R>>(in, w, outv, hq, hr, false, false, 0, R(0), T{}, T{}, wa.rh);
+    else collide_vec<R, COLL, V, false, wall_subgrid(WALL), wall_relax(WALL)>(in, w, outv, hq, hr, false, false, 0, sgs, rwv, rmv);
     // the driving force (lbm_set_driving_force), a uniform run-time test: every lane adds F_k, one add in the lattice type; the solid and
     // the hold lanes are pinned below, so the sums of fluid lanes alone are stored
     if constexpr (wall_buoyant(WALL)) {
@@ -253,8 +258,12 @@ __global__ __launch_bounds__(BLK) void k_step_generic_wall(const R* __restrict__
             rwm = wa.rwm ? wa.rwm[at] : w.w_m;
         }
         if constexpr (wall_subgrid(WALL)) sgs = wa.sgs;   // (the sub-grid closure: its constant)
-        update_cell_a<R, COLL, SEM_SOLID, false, Geo, Geo, BASE, wall_subgrid(WALL), wall_relax(WALL)>(src, geo, dst, geo, geo, w, raw, x, y, nullptr, wb,
-                                                                                                       wall_buoyant(WALL) ? own : dr, sgs, rw, rwm);
+        if constexpr (wall_rheo(WALL))   // (a rheology table: the context's)
+            update_cell_a<R, COLL, SEM_SOLID, false, Geo, Geo, BASE, false, false, true, Rheo<R>>(src, geo, dst, geo, geo, w, raw, x, y, nullptr, wb, dr, sgs, rw, rwm,
+                                                                                         wa.rh);
+        else
+            update_cell_a<R, COLL, SEM_SOLID, false, Geo, Geo, BASE, wall_subgrid(WALL), wall_relax(WALL)>(src, geo, dst, geo, geo, w, raw, x, y, nullptr, wb,
+                                                                                                           wall_buoyant(WALL) ? own : dr, sgs, rw, rwm);
     }
 }
 
@@ -289,4 +298,7 @@ LBM_INST_SOLID(float, WALL_SHAPE | WALL_RELAX) LBM_INST_SOLID(double, WALL_SHAPE
 LBM_INST_SOLID(float, WALL_REST | WALL_SGS | WALL_RELAX) LBM_INST_SOLID(double, WALL_REST | WALL_SGS | WALL_RELAX)
 LBM_INST_SOLID(float, WALL_MOVE | WALL_SGS | WALL_RELAX) LBM_INST_SOLID(double, WALL_MOVE | WALL_SGS | WALL_RELAX)
 LBM_INST_SOLID(float, WALL_SHAPE | WALL_SGS | WALL_RELAX) LBM_INST_SOLID(double, WALL_SHAPE | WALL_SGS | WALL_RELAX)
+LBM_INST_SOLID(float, WALL_REST | WALL_RHEO) LBM_INST_SOLID(double, WALL_REST | WALL_RHEO)
+LBM_INST_SOLID(float, WALL_MOVE | WALL_RHEO) LBM_INST_SOLID(double, WALL_MOVE | WALL_RHEO)
+LBM_INST_SOLID(float, WALL_SHAPE | WALL_RHEO) LBM_INST_SOLID(double, WALL_SHAPE | WALL_RHEO)
 #endif

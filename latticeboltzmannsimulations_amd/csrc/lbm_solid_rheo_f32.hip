@@ -1,0 +1,4 @@
+// lbm_solid_rheo_f32.hip -- the float instantiations of k_step_solid and k_step_generic_wall with a rheology table, at rest (WALL_REST | WALL_RHEO)
+// (lbm_solid.hpp): the six operator variants, the vector kernel with and without non-temporal accesses.
+#define LBM_SOLID_INST LBM_INST_SOLID(float, WALL_REST | WALL_RHEO)
+#include "lbm_solid.hpp"

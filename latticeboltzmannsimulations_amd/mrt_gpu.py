@@ -339,7 +339,8 @@ def run_cavity(maxIt=3000000, Re=10000.0, RT="SRT", turb=1, xsize=32 * 5, ysize=
                dtype=np.float32, semantics="mrt_gpu", device=0, quiet=False, solver_factory=None, arith="strict",
                convergence="host", vtk_correct=False, BC="EB-NEBB ", AverageFrom=None, AverageEvery=100, monitor="host",
                MonitorEvery=None, Probes=(), vortex_table=False, criterion="mean_u", residual_tol=None, residual_hits=1, solid=None,
-               solid_tiles=False, bodies=None, force_every=None, body_motion=None, solid_shape=None, subgrid=None, viscosity_field=None):
+               solid_tiles=False, bodies=None, force_every=None, body_motion=None, solid_shape=None, subgrid=None, viscosity_field=None,
+               rheology=None):
     """Run the lid-driven cavity like MRT_GPU.py does; returns a :class:`CavityResult`.
 
     Argument names and defaults are the module constants of MRT_GPU.py:38-58.
@@ -398,8 +399,18 @@ def run_cavity(maxIt=3000000, Re=10000.0, RT="SRT", turb=1, xsize=32 * 5, ysize=
     viscosity_field (BC='BB', turb=0; with or without solid=...): nu[xsize, ysize] in lattice units, the viscosity of each cell
     (CavitySolver.set_viscosity; viscosity.layers, viscosity.sponge) from the first iteration on; under TRT the magic parameter of the
     solver's own rates is kept in every cell.  Without a mask the cavity runs as an obstacle lattice with an empty one.  None
-    (default): the one viscosity of Re, nothing changes."""
+    (default): the one viscosity of Re, nothing changes.
+    rheology (BC='BB', turb=0; with or without solid=...): (omega, omegam, g_max) or dict(law=..., g_max=..., entries=..., magic=...)
+    (rheology.resolve), a generalised Newtonian fluid (CavitySolver.set_rheology) from the first iteration on; Re then only sets the
+    lattice's own rates.  Every output iteration prints one warning if the largest shear (get_shear) exceeds g_max, beyond which the
+    table holds its last entry.  Not with subgrid or viscosity_field.  None (default): nothing changes."""
     cs2 = subgrid_constant(subgrid, BC, solid_tiles)
+    if rheology is not None:
+        if BC.strip() != "BB" or solid_tiles:
+            raise ValueError("rheology lives on the bounce-back and obstacle lattices at one step per launch: pass BC='BB' (and turb=0), "
+                             "without solid_tiles")
+        if cs2 is not None or viscosity_field is not None:
+            raise ValueError("rheology excludes subgrid and viscosity_field: each pairing would be one more set of kernel twins")
     if viscosity_field is not None:
         if BC.strip() != "BB" or solid_tiles:
             raise ValueError("viscosity_field lives on the bounce-back and obstacle lattices at one step per launch: pass BC='BB' (and turb=0), "
@@ -418,7 +429,7 @@ def run_cavity(maxIt=3000000, Re=10000.0, RT="SRT", turb=1, xsize=32 * 5, ysize=
     extra = {} if arith == "strict" else {"arith": arith}      # 'fast' / 'promoted': see CavitySolver
     if solid is not None:
         extra["solid"] = solid
-    elif cs2 is not None or viscosity_field is not None:      # (the closure and the field live on the obstacle lattices: the plain bounce-back cavity is one with an empty mask)
+    elif cs2 is not None or viscosity_field is not None or rheology is not None:      # (the closure and the field live on the obstacle lattices: the plain bounce-back cavity is one with an empty mask)
         extra["solid"] = np.zeros((xsize, ysize), dtype=bool)
     if solid_tiles:
         extra["tuning"] = dict(solid_tiles=True)
@@ -426,8 +437,13 @@ def run_cavity(maxIt=3000000, Re=10000.0, RT="SRT", turb=1, xsize=32 * 5, ysize=
         extra["bodies"] = bodies
     solver = make(xsize, ysize, Re, RT=RT, uLB=uLB, semantics=semantics, dtype=dtype, turb=turb, device=device, **extra)
     _banner(say, Re, RT, turb, solver.relax)
-    if solid_shape is not None or body_motion is not None or cs2 is not None or viscosity_field is not None:
+    g_max = None
+    if solid_shape is not None or body_motion is not None or cs2 is not None or viscosity_field is not None or rheology is not None:
         try:
+            if rheology is not None:
+                from . import rheology as RH
+                g_max = RH.apply(solver, rheology, RT)
+                say("Rheology table is on, g_max = ", g_max)
             if cs2 is not None:
                 solver.set_subgrid(cs2)
                 say("Sub-grid closure is on, Cs2 = ", cs2)
@@ -455,7 +471,7 @@ def run_cavity(maxIt=3000000, Re=10000.0, RT="SRT", turb=1, xsize=32 * 5, ysize=
                           BC="BB" if semantics == "bounce_back" else "EB-NEBB ")   # (the dashboard's label; MRT_GPU.py:281 spells the default so)
     res = CavityResult()
     done = 0          # iterations performed
-    outputs = SaveVTK or SavePlot or on_device or bool(vortex_table) or by_res or solid is not None or cs2 is not None
+    outputs = SaveVTK or SavePlot or on_device or bool(vortex_table) or by_res or solid is not None or cs2 is not None or g_max is not None
     averaging = False
 
     def advance(n):   # n iterations; statistics begin once `done` reaches AverageFrom
@@ -500,6 +516,8 @@ def run_cavity(maxIt=3000000, Re=10000.0, RT="SRT", turb=1, xsize=32 * 5, ysize=
                 if cs2 is not None:
                     res.tau_mean.append((It, _fluid_tau_mean(solver, run)))
                     say("current mean relaxation time is " + str(res.tau_mean[-1][1]))
+                if g_max is not None:
+                    RH.over_range(solver, g_max, say)
                 _write_files(solver, run, c, It, res.regression)
                 say("time elapsed is ", (timer() - tstart), "seconds")
                 if by_res:

@@ -118,10 +118,16 @@ def _factory(solver_factory):
 
 
 def run_poiseuille(nx=6, ny=18, nu=0.1, force=1e-6, steps=20000, magic=MAGIC, dtype=np.float64, arith="strict", device=0, solver_factory=None,
-                   quiet=False):
+                   quiet=False, rheology=None, output_every=None):
     """A force-driven channel, periodic in x, under TRT with the product `magic` (None: the solver's default).  Returns dict(error -- the
     largest deviation of the shifted velocity from F / (2 nu) s (H - s) over the fluid cells, as a fraction of its maximum --, umax,
-    balance -- |wall force / (F fluid cells) - 1| --, u, rho, steps)."""
+    balance -- |wall force / (F fluid cells) - 1| --, u, rho, steps).
+    rheology=(omega, omegam, g_max) or dict(law=..., g_max=..., entries=..., magic=...) (rheology.resolve): a generalised Newtonian fluid
+    (CavitySolver.set_rheology) in the place of the one viscosity; nu then only sets the lattice's own rates, which solid cells report.
+    The steps run in pieces of output_every (default: all at once), and after each piece one warning is printed if the largest shear
+    exceeds g_max; the result gains g_top, the largest shear seen, and with rheology=dict(law=power_law(K, n), power=(K, n)) the error
+    is against rheology.power_law_profile."""
+    from . import rheology as RH
     g = poiseuille(nx, ny)
     Re = solver_re(nu, ny)
     with _factory(solver_factory)(nx, ny, Re, RT="TRT", semantics="bounce_back", dtype=dtype, arith=arith, device=device, solid=g["solid"]) as s:
@@ -129,11 +135,25 @@ def run_poiseuille(nx=6, ny=18, nu=0.1, force=1e-6, steps=20000, magic=MAGIC, dt
             s.set_relaxation(omegam=trt_omegam(s.relax["omega"], magic))
         s.set_periodic(*g["periodic"])
         s.set_driving_force(force, 0.0)
-        s.step(int(steps))
+        g_max = RH.apply(s, rheology, "TRT") if rheology is not None else None
+        g_top, left = 0.0, int(steps)
+        while left > 0:
+            n = left if not output_every else min(left, int(output_every))
+            s.step(n)
+            left -= n
+            if g_max is not None:
+                g_top = max(g_top, RH.over_range(s, g_max, (lambda *a: None) if quiet else print))
         u, rho = s.get_fields()[:2]
         wall = s.solid_force()
     out = poiseuille_figures(u, rho, wall["fx"], g, nu, force)
     out["steps"] = int(steps)
+    if rheology is not None:
+        out["g_top"] = g_top
+        if isinstance(rheology, dict) and "power" in rheology:
+            K, n = rheology["power"]
+            exact = RH.power_law_profile(g["H"], K, n, force)
+            ux = interior(velocity(u, rho, (force, 0.0))[0], True, False)[:, 1:-1]
+            out.update(error=float(np.abs(ux - exact[None, :]).max() / exact.max()), umax=float(exact.max()))
     if not quiet:
         print(f"Poiseuille {nx} x {ny}, nu = {nu:g}, F = {force:g}, {steps} steps: profile error {out['error']:.3e} of umax = {out['umax']:.6e}, "
               f"force balance {out['balance']:.3e}")
@@ -196,12 +216,20 @@ def main(argv=None):
     ap.add_argument("--steps", type=int, default=20000)
     ap.add_argument("--radius", type=float, default=6.0)
     ap.add_argument("--curved", action="store_true")
+    ap.add_argument("--power-law", dest="power_law", type=float, nargs=2, metavar=("K", "N"), default=None,
+                    help="poiseuille: a power-law fluid nu = K gdot^(N - 1) (clipped to [1e-3, 2]) through a rheology table")
+    ap.add_argument("--g-max", dest="g_max", type=float, default=None, help="the shear of the table's last entry (default 0.1)")
     ap.add_argument("--dtype", choices=("float32", "float64"), default="float64")
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args(argv)
     dt = np.dtype(a.dtype).type
     if a.run == "poiseuille":
-        run_poiseuille(a.xsize or 6, a.ysize or 18, a.nu, a.force, a.steps, dtype=dt, device=a.device)
+        rh = None
+        if a.power_law is not None:
+            from . import rheology as RH
+            K, n = a.power_law
+            rh = dict(law=RH.power_law(K, n), power=(K, n), g_max=RH.G_MAX_DEFAULT if a.g_max is None else a.g_max, magic=MAGIC)
+        run_poiseuille(a.xsize or 6, a.ysize or 18, a.nu, a.force, a.steps, dtype=dt, device=a.device, rheology=rh)
     else:
         run_array(a.xsize or 34, a.ysize or 34, a.radius, a.nu, a.force, a.steps, a.curved, dtype=dt, device=a.device)
     return 0

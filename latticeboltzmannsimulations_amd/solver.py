@@ -222,6 +222,9 @@ class CavitySolver:
                 out[kv] = True
                 continue
             k, v = kv.split("=", 1)
+            if k == "rheology":      # (`rheology=<n>` or `rheology=<n>+m`: the entries, and whether the table carries TRT's odd rate)
+                out[k], out["rheology_m"] = int(v.split("+")[0]), v.endswith("+m")
+                continue
             out[k] = int(v) if v.lstrip("-").isdigit() else v
         return out
 
@@ -258,7 +261,8 @@ class CavitySolver:
 
     def get_tau(self, out_dtype=None):
         """tau + tau_turbulent per cell of the last iteration (taus_g, MRT_GPU.py:387); 1 / omega everywhere when turb = 0.  With a
-        sub-grid constant (set_subgrid): the tau of the step that starts from the current state, solid and hold cells at 1 / omega."""
+        sub-grid constant (set_subgrid): the tau of the step that starts from the current state, solid and hold cells at 1 / omega.
+        With a rheology table (set_rheology) likewise: 1 / omega of the rate the table gives each cell's shear."""
         dt = self.dtype if out_dtype is None else np.dtype(out_dtype)
         tau = np.zeros(self._lead + (self.nx, self.ny), dtype=dt)
         self._check(self.lib.lbm_get_tau(self._h, tau.ctypes.data, _DT[tau.dtype]), "lbm_get_tau")
@@ -811,6 +815,55 @@ class CavitySolver:
         from .viscosity import rates
         return self.set_relaxation_field(*rates(nu, magic))
 
+    # -- shear-dependent viscosity: a rheology table (lbm_set_rheology, lbm_get_rheology, lbm_get_shear) ---------------------------
+    def set_rheology(self, omega, omegam=None, g_max=None):
+        """A generalised Newtonian fluid on an obstacle lattice (lbm_set_rheology; solid=..., one step per launch): omega[n], 2 <= n <=
+        65536, is the viscous rate -- SRT's omega, TRT's omega+, MRT's omega_nu -- at the shears g_i = i g_max / (n - 1), g = |deviatoric
+        non-equilibrium momentum flux| / rho of a cell (get_shear), and omegam[n] TRT's omega- there (None: the lattice's; a TRT solver
+        only).  Every value in (0, 2); between entries the rates are interpolated linearly, beyond g_max the table holds its last entry.
+        rheology.table builds both arrays from a law nu(gdot).  One table for every lattice of a batch.  The lattice, the step count and
+        the samplers stay; the table survives set_solid and the other setters.  With buoyancy, set_subgrid or a relaxation field the call
+        is refused, and they refuse while a table is set.  omega=None clears the table: the kernels and the bits of a solver without one."""
+        if omega is None:
+            if omegam is not None:
+                raise ValueError("omegam without omega")
+            self._check(self.lib.lbm_set_rheology(self._h, None, None, 0, 0.0), "lbm_set_rheology")
+            return self
+        if g_max is None:
+            raise ValueError("set_rheology needs g_max, the shear of the table's last entry")
+        w = np.ascontiguousarray(omega, dtype=np.float64)
+        wm = None if omegam is None else np.ascontiguousarray(omegam, dtype=np.float64)
+        if w.ndim != 1 or (wm is not None and wm.shape != w.shape):
+            raise ValueError("omega (and omegam) must be one-dimensional arrays of one length")
+        self._check(self.lib.lbm_set_rheology(self._h, w.ctypes.data, None if wm is None else wm.ctypes.data, int(w.size), float(g_max)),
+                    "lbm_set_rheology")
+        return self
+
+    @property
+    def rheology(self):
+        """(omega, omegam, g_max) as the device holds the table (rounded to the lattice type), omegam None without it; None without a
+        table."""
+        if self._h is None:
+            return None
+        n, g_max = ctypes.c_int(0), ctypes.c_double(0.0)
+        rc = self.lib.lbm_get_rheology(self._h, None, None, ctypes.byref(n), ctypes.byref(g_max))
+        if rc == 0:
+            return None
+        if rc != 1:
+            self._check(rc, "lbm_get_rheology")
+        w, wm = np.zeros(n.value), np.full(n.value, np.nan)
+        self._check(self.lib.lbm_get_rheology(self._h, w.ctypes.data, wm.ctypes.data, None, None) - 1, "lbm_get_rheology")
+        return w, (None if np.isnan(wm).all() else wm), g_max.value
+
+    def get_shear(self, out_dtype=None):
+        """g[X, Y] ([B, X, Y]) of the current state (lbm_get_shear): the Frobenius norm of the deviatoric non-equilibrium momentum flux
+        over rho, what a rheology table is indexed with; 0 on solid and hold cells.  Works without a table too (solid=... only).  The
+        shear rate is rheology.shear_rate(g, tau)."""
+        dt = self.dtype if out_dtype is None else np.dtype(out_dtype)
+        g = np.zeros(self._lead + (self.nx, self.ny), dtype=dt)
+        self._check(self.lib.lbm_get_shear(self._h, g.ctypes.data, _DT[g.dtype]), "lbm_get_shear")
+        return g
+
     # -- a passive scalar: temperature or dye (lbm_scalar_*) ---------------------------------------------------------------
     def _cells(self, a, name, fill=None):
         """A float64 [X, Y] array as the scalar calls take it; a number fills the lattice."""
@@ -967,6 +1020,9 @@ class CavitySolver:
         rf = self.relaxation_field if self.has_solid else None
         if rf is not None:
             out.update(relax_omega=rf[0], **({} if rf[1] is None else dict(relax_omegam=rf[1])))
+        rh = self.rheology if self.has_solid else None
+        if rh is not None:
+            out.update(rheology_omega=rh[0], rheology_gmax=np.float64(rh[2]), **({} if rh[1] is None else dict(rheology_omegam=rh[1])))
         return out
 
     def _shape_entry(self):
@@ -992,7 +1048,8 @@ class CavitySolver:
         may restart from a checkpoint of the undivided lattice (each context reads its own rows) but not from another slab's.
         A file that carries a sub-grid constant sets it and clears a buoyancy this solver had set (the two refuse each other); a file
         without one clears the constant.  A relaxation field (set_relaxation_field) likewise: a file with one sets both arrays and clears
-        this solver's buoyancy, a file without one clears the field."""
+        this solver's buoyancy, a file without one clears the field.  A rheology table (set_rheology) likewise: a file with one sets it
+        (and clears this solver's buoyancy), a file without one clears the table."""
         with np.load(_npz(path), allow_pickle=False) as z:
             if int(z["nx"]) != self.nx or int(z["ny"]) != self.ny:
                 raise ValueError("checkpoint lattice size differs")
@@ -1052,6 +1109,8 @@ class CavitySolver:
                 self.set_wall_velocity(uw)
             if "driving_force" in z or (self._h is not None and any(self.driving_force)):      # (the force last: it is no geometry)
                 self.set_driving_force(*(np.asarray(z["driving_force"]) if "driving_force" in z else (0.0, 0.0)))
+            if "rheology_omega" not in z and self.has_solid and self.rheology is not None:      # (first: the table would refuse the two below)
+                self.set_rheology(None)
             cs2 = float(z["subgrid"]) if "subgrid" in z else 0.0      # (the sub-grid constant: no geometry, no history)
             if cs2 > 0.0 or (self._h is not None and self.subgrid > 0.0):
                 if cs2 > 0.0 and self.buoyancy is not None:      # (this solver's own buoyancy would refuse the constant)
@@ -1063,6 +1122,11 @@ class CavitySolver:
                 self.set_relaxation_field(np.asarray(z["relax_omega"]), np.asarray(z["relax_omegam"]) if "relax_omegam" in z else None)
             elif self.has_solid and self.relaxation_field is not None:
                 self.set_relaxation_field(None)
+            if "rheology_omega" in z:      # (the rheology table: no geometry, no history; a file carries it with neither of the two above)
+                if self.buoyancy is not None:
+                    self.set_buoyancy(0.0, 0.0)
+                self.set_rheology(np.asarray(z["rheology_omega"]), np.asarray(z["rheology_omegam"]) if "rheology_omegam" in z else None,
+                                  float(z["rheology_gmax"]))
             if same_mask and "scalar_g" in z:      # (the scalar last: the geometry calls above end one; a file without it leaves this solver's as it is)
                 self.begin_scalar(float(z["scalar_D"]), np.asarray(z["scalar_c0"]), float(z["scalar_magic"]),
                                   np.asarray(z["scalar_wall_value"]) if "scalar_wall_value" in z else None,

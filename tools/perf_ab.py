@@ -16,6 +16,8 @@ buoyancy (with scalar: A -- set_buoyancy(0, A, 1.0): the buoyant twins of the fl
 subgrid (with solid: CS2 -- set_subgrid(CS2): the kernels with the sub-grid closure; 0 sets nothing),
 relax (with solid: 1 -- set_relaxation_field with one plane, the lattice's omega jittered by 5 %, seeded: the kernels that read a rate per cell --
 or 2 -- with TRT's second plane as well (coll=TRT); 0 sets nothing),
+rheo (with solid: 1 -- set_rheology with the table of a power-law fluid, n = 0.7, whose viscosity at the shear rate uLB / ny is ten times the lattice's and never below twice it,
+4096 entries, g_max 0.1: the kernels that look a rate up per cell; 0 sets nothing),
 route (with solid: single --
 one step per launch, the default -- or tiles -- the multi-step tile kernel, tuning solid_tiles), force (with solid: series.E -- the run
 with begin_force(every=E) --, loop.E -- the host loop step(E); solid_force() --, plain.E -- step(E); sync() without any force --, or call -- no stepping: microseconds per call of
@@ -100,6 +102,10 @@ def parse(case):
                 if v not in ("0", "1", "2"):
                     raise ValueError("relax must be 0, 1 or 2")
                 kw["relax"] = int(v)
+            elif k == "rheo":
+                if v not in ("0", "1"):
+                    raise ValueError("rheo must be 0 or 1")
+                kw["rheo"] = int(v)
             elif k == "batch":
                 kw["batch"] = int(v)
             elif k in ("tb_steps", "frame_seg"):
@@ -127,6 +133,7 @@ def main():
         buoy = kw.pop("buoyancy", None)
         cs2 = kw.pop("subgrid", 0.0)
         relax = kw.pop("relax", 0)
+        rheo = kw.pop("rheo", 0)
         if per is not None:
             from latticeboltzmannsimulations_amd import periodic
             kw["solid"] = periodic.wrap(kw["solid"], "x" in per, "y" in per)
@@ -152,6 +159,10 @@ def main():
                 r = np.random.default_rng(3)
                 planes = [np.clip(s.relax[k] * (1.0 + 0.05 * r.standard_normal((nx, ny))), 0.05, 1.95) for k in ("omega", "omegam")[:relax]]
                 s.set_relaxation_field(*planes)
+            if rheo:
+                from latticeboltzmannsimulations_amd import rheology
+                nu0, gd0 = (1.0 / s.relax["omega"] - 0.5) / 3.0, s.uLB / ny
+                s.set_rheology(*rheology.table(rheology.power_law(10.0 * nu0 / gd0 ** (0.7 - 1.0), 0.7, 2.0 * nu0, 2.0), 4096, 0.1), 0.1)
             s.copy_bandwidth(1 << 30, 60)
             s.step(max(60, a.steps // 10)); s.sync()
             if force == "call":
@@ -187,7 +198,7 @@ def main():
             else:
                 reps = [s.time_steps(a.steps) / a.steps for _ in range(a.reps)]
             ms = min(reps)
-            print(f"{case:48s} S={s.next_unit(1000)}{' move' if s.describe().get('wall_motion') else ''}{' shape' if s.describe().get('wall_shape') else ''}{' periodic=' + s.describe()['periodic'] if 'periodic' in s.describe() else ''}{' drive' if s.describe().get('driving_force') else ''}{' buoyant' if s.describe().get('buoyancy') else ''}{' subgrid' if s.describe().get('subgrid') else ''}{' relax_field' if s.describe().get('relax_field') else ''}{' relax_field+m' if s.describe().get('relax_field+m') else ''}  {B * nx * ny / ms / 1e6:8.1f} GLUPS  {ms * 1e3:9.2f} us/step  "
+            print(f"{case:48s} S={s.next_unit(1000)}{' move' if s.describe().get('wall_motion') else ''}{' shape' if s.describe().get('wall_shape') else ''}{' periodic=' + s.describe()['periodic'] if 'periodic' in s.describe() else ''}{' drive' if s.describe().get('driving_force') else ''}{' buoyant' if s.describe().get('buoyancy') else ''}{' subgrid' if s.describe().get('subgrid') else ''}{' relax_field' if s.describe().get('relax_field') else ''}{' relax_field+m' if s.describe().get('relax_field+m') else ''}{' rheology' if s.describe().get('rheology') else ''}  {B * nx * ny / ms / 1e6:8.1f} GLUPS  {ms * 1e3:9.2f} us/step  "
                   f"repeats {' '.join('%.1f' % (B * nx * ny / r / 1e6) for r in reps)}"
                   + (f"  us/step {' '.join('%.2f' % (r * 1e3) for r in reps)}" if force else ""), flush=True)
 
